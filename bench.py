@@ -42,11 +42,8 @@ import subprocess
 import sys
 import time
 
-# The HIP runtime maps a process's streams onto 4 hardware queues by default; this path uses the context's stream, up to
-# three side streams for the samples in flight, torch's default stream and RCCL's -- with 4 queues two of the side streams
-# share one and their kernels serialise (8-GPU share of the headline frame: 0.59 instead of 0.42 ms per sample).
-# Read by the runtime when it starts, so it has to be in the environment before anything touches the GPU.
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
+# The HIP runtime's hardware queues are left at its default: side streams that share a queue serialise (sharded runs,
+# several samples in flight), which the one-GPU headline (one sample in flight) does not use.
 os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")  # dmabuf IPC: RCCL across processes needs it on this driver
 # one node by contract (N GPUs over xGMI): no InfiniBand to probe, rendezvous over loopback
 os.environ.setdefault("NCCL_IB_DISABLE", "1")
@@ -329,6 +326,25 @@ def live_counters(timeout_s=150.0):
     return out, f"measured in this run: {len(PMC_PASSES)} rocprofv3 --pmc passes (--kernel-trace only) of `bench.py --counter-child`, {COUNTER_FRAMES} frames per leg, {took:.0f} s"
 
 
+DUMP_PIXELS = 1 << 20  # 3 planes x 16 B + an 8-B index per pixel: 56 MiB at most
+
+
+def dump_outputs(out_dir, fb, abi):
+    """--dump-outputs: the colour, normal/DoF and albedo/depth planes of `fb` (row-major pixels of the rows it holds, 4 floats
+    each) as float32 .npy files; above DUMP_PIXELS pixels, the same seeded sample of pixels in every plane."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    n = fb.row_count * fb.width
+    pick = None
+    if n > DUMP_PIXELS:
+        pick = np.sort(np.random.default_rng(0).choice(n, DUMP_PIXELS, replace=False))
+        np.save(os.path.join(out_dir, "pixel_index.npy"), pick.astype(np.float64))
+    for name, plane in (("color", abi.RM_PLANE_COLOR), ("normal_dof", abi.RM_PLANE_NORMAL_DOF), ("albedo_depth", abi.RM_PLANE_ALBEDO_DEPTH)):
+        a = np.ascontiguousarray(fb.download(plane), np.float32).reshape(n, 4)
+        np.save(os.path.join(out_dir, name + ".npy"), a if pick is None else a[pick])
+
+
 def self_launch(args):
     """--gpus N > 1 with no launcher: start N fresh ranks before this process touches a GPU."""
     import socket
@@ -393,6 +409,9 @@ def main():
     ap.add_argument("--no-live-counters", action="store_true", help="do not measure the hardware counters in this run (replay profiles/<round>_counters.json)")
     ap.add_argument("--no-workloads", action="store_true", help="skip the `workloads` legs (the other BASELINE configurations and the two parity builds of the headline, a few steps each)")
     ap.add_argument("--no-check-frame", action="store_true", help="sharded runs check the assembled frame by default (see --check-frame); this skips it")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write the three fp32 planes the job accumulated (what its caller receives) as DIR/<plane>.npy: "
+                         "every pixel of this rank's rows, or a fixed seeded sample of DUMP_PIXELS of them (DIR/pixel_index.npy) when they are more")
     ap.add_argument("--check-frame", action="store_true",
                     help="sharded runs: after the timed legs rank 0 renders the same samples on ONE framebuffer, presents it and compares "
                          "the bytes with the frame it assembled from the gathered rows (reported as `frame_check`)")
@@ -580,6 +599,8 @@ def main():
     # EXACTLY K steps per timed region; three regions, `value` from the median (the spread says what one region is worth)
     regions = sorted(timed(args.steps, yield_interval) for _ in range(max(1, args.repeats)))
     elapsed = regions[len(regions) // 2]
+    if args.dump_outputs and rank == 0:  # before anything below renders into the same framebuffer
+        dump_outputs(args.dump_outputs, fb, abi)
 
     px_frame = W * row_count if (rows_window is not None or stripes is not None) else W * H
     ms_per_step = elapsed / args.steps * 1e3

@@ -12,9 +12,7 @@
 // host is JavaScript with hand-written typings.)
 "use strict";
 // Process environment the device path depends on (read by the HIP / HSA runtime when it starts, i.e. when the addon
-// first touches the GPU): more hardware queues than the runtime's default 4, so that the side streams of the samples in
-// flight do not share one and serialise, and dmabuf IPC.  Set unless the user has set them (native.py does the same).
-if (process.env.GPU_MAX_HW_QUEUES === undefined) process.env.GPU_MAX_HW_QUEUES = "8";
+// first touches the GPU): dmabuf IPC.  Set unless the user has set it (native.py does the same).
 if (process.env.HSA_ENABLE_IPC_MODE_LEGACY === undefined) process.env.HSA_ENABLE_IPC_MODE_LEGACY = "0";
 const addon = require("./rm_napi.node");
 

@@ -17,13 +17,11 @@ from .scene import Scene
 import os
 
 # Process environment the device path depends on, set where the library is loaded so that EVERY host gets it (bench.py,
-# the job API, the tests), unless the user has set it.  Both are read by the HIP / HSA runtime when it starts, so they
-# have to be in place before anything in this process touches the GPU:
-#  * GPU_MAX_HW_QUEUES=8: the runtime deals a process's streams over 4 hardware queues by default, and streams that share
-#    one serialise -- with samples in flight (side streams), torch's stream and RCCL's, a sharded rank's renders stopped
-#    overlapping (0.59 instead of 0.42 ms per sample at 8 GPUs).  rm_ctx_set_samples_in_flight warns when it is lower.
+# the job API, the tests), unless the user has set it.  Read by the HIP / HSA runtime when it starts, so it has to be in
+# place before anything in this process touches the GPU:
 #  * HSA_ENABLE_IPC_MODE_LEGACY=0: dmabuf IPC, which RCCL needs across processes on this driver.
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
+# The runtime's hardware queues stay at its default: side streams that share one serialise, and
+# rm_ctx_set_samples_in_flight says so (rm_ctx_last_warning).
 os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
 
 # RM_LIB selects an experiment build of the SAME library (tools/); default = the in-tree product

@@ -2301,7 +2301,7 @@ def test_frame_gatherer_over_rccl_one_rank(payload, streams, tmp_path):
     script = tmp_path / "rccl_one_rank.py"
     script.write_text(_RCCL_ONE_RANK)
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    env = dict(os.environ, NCCL_IB_DISABLE="1", NCCL_SOCKET_IFNAME="lo", HSA_ENABLE_IPC_MODE_LEGACY="0", GPU_MAX_HW_QUEUES="8")
+    env = dict(os.environ, NCCL_IB_DISABLE="1", NCCL_SOCKET_IFNAME="lo", HSA_ENABLE_IPC_MODE_LEGACY="0")
     last = None
     for attempt in range(2):  # the library's start-up has been seen to stall once in a while on a shared box
         try:

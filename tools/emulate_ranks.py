@@ -7,7 +7,6 @@ rank allows: what the compute side of strong scaling can give (the receive side 
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 import torch
 import golden_cases as GC
 from raymarching_engine_amd import abi, job as J, native, scene as S, shard
