@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define RM_ABI_VERSION 8 /* 8: RM_PRIM_TORUS / _CYLINDER / _PLANE, RM_OP_SMOOTH_SUBTRACT / _INTERSECT, rm_probe_math (additions only); 7: rm_present_sharded_finish / rm_present_sharded take the size of the host buffer (a changed signature), rm_ctx_set_cull_min_pixels, rm_ctx_set_cull_budget, rm_ctx_cull_stats; 6: rm_present_striped_rows, rm_present_sharded_start / _finish, rm_ctx_last_warning, RM_PROBE_CAST_SHADOW, RM_PRIM_KIND (additions only); 3: rm_ctx_set_sample_batch, rm_buffer_*; 4: rm_ctx_set_gl_stack; 5: RmSurface / RmSceneDesc.surfaces (the struct grew), rm_pack_present_rows, rm_present_sharded, rm_ctx_last_pipeline, RM_RENDER_NO_FAR_JUMP, RM_RENDER_NO_CULL (additions only) */
+#define RM_ABI_VERSION 9 /* 9: RM_GBUFFER_F32 / _F16, rm_fb_create_fmt, rm_fb_create_striped_fmt, rm_fb_wrap_fmt, rm_fb_gbuffer, rm_fb_download_raw, rm_fb_upload_raw (additions only); 8: RM_PRIM_TORUS / _CYLINDER / _PLANE, RM_OP_SMOOTH_SUBTRACT / _INTERSECT, rm_probe_math (additions only); 7: rm_present_sharded_finish / rm_present_sharded take the size of the host buffer (a changed signature), rm_ctx_set_cull_min_pixels, rm_ctx_set_cull_budget, rm_ctx_cull_stats; 6: rm_present_striped_rows, rm_present_sharded_start / _finish, rm_ctx_last_warning, RM_PROBE_CAST_SHADOW, RM_PRIM_KIND (additions only); 3: rm_ctx_set_sample_batch, rm_buffer_*; 4: rm_ctx_set_gl_stack; 5: RmSurface / RmSceneDesc.surfaces (the struct grew), rm_pack_present_rows, rm_present_sharded, rm_ctx_last_pipeline, RM_RENDER_NO_FAR_JUMP, RM_RENDER_NO_CULL (additions only) */
 
 #define RM_MAX_BOUNCES 10 /* raymarchingStepCountsArray[10], raymarcher.frag:31 */
 #define RM_MAX_LIGHTS 10  /* lightPositions[10],             raymarcher.frag:37-39 */
@@ -412,6 +412,39 @@ RM_API int rm_fb_download(rm_fb* fb, int plane, float* host);
 RM_API int rm_fb_upload(rm_fb* fb, int plane, const float* host);
 /* Device address of a plane (for collectives / zero-copy wrapping). */
 RM_API void* rm_fb_device_ptr(rm_fb* fb, int plane);
+
+/* (ABI 9) The format of the G-buffer planes.  LoadRenderJobContext.tsx:81-119 allocates colour as RGBA32F and
+ * normal + DoF radius and albedo + depth as RGBA16F; the framebuffers above keep all three planes in fp32, which is what
+ * the reference computes on the software GL stack its golden images were rendered under (and stays the default).
+ * RM_GBUFFER_F16 stores planes 1 and 2 as 4 x IEEE binary16 per pixel (8 bytes, RGBA; rows as for fp32) and
+ * accumulates them as raymarcher.frag:347-351 does with an RGBA16F attachment: the stored value widened to fp32, the
+ * sample's contribution added in fp32, the sum rounded to binary16 to nearest even (overflow to +-inf, subnormals kept),
+ * after EVERY sample, whatever the batching.  So a pixel's summed normal stops at 2048 and a sky pixel's depth is +inf,
+ * as the reference's users see them.  The colour plane is float4 in both formats.  A frame is 64 bytes per pixel
+ * instead of 96.  A render that writes a half G-buffer is always staged (the samples-in-flight staging, 48 bytes per
+ * pixel of the tile per sample; one slot under RM_RENDER_NO_OVERLAP): when that staging cannot be allocated the call
+ * fails with RM_ERR_DEVICE instead of rendering unstaged -- render in tiles.  RM_RENDER_WAVEFRONT (the tests'
+ * cross-check library) renders a half G-buffer with the pixel kernel (rm_ctx_last_pipeline tells). */
+enum { RM_GBUFFER_F32 = 0, RM_GBUFFER_F16 = 1 };
+/* rm_fb_create / rm_fb_create_striped / rm_fb_wrap with a G-buffer format.  Caller-owned half planes address
+ * row_count*width*8 bytes and are 8-byte aligned (colour: float4, 16-byte aligned).  An unknown format or a misaligned
+ * plane is RM_ERR_INVALID. */
+RM_API int rm_fb_create_fmt(rm_ctx* ctx, int width, int height, int row_begin, int row_count, int gbuffer, rm_fb** out);
+RM_API int rm_fb_create_striped_fmt(rm_ctx* ctx, int width, int height, int stripe_rows, int parts, int part,
+                             void* color, void* normal_dof, void* albedo_depth, int gbuffer, rm_fb** out);
+RM_API int rm_fb_wrap_fmt(rm_ctx* ctx, int width, int height, int row_begin, int row_count,
+                   void* color, void* normal_dof, void* albedo_depth, int gbuffer, rm_fb** out);
+/* The G-buffer format of a framebuffer (RM_GBUFFER_F32 for every framebuffer made without one). */
+RM_API int rm_fb_gbuffer(const rm_fb* fb);
+/* A plane's bytes as stored, either format: `bytes` must be exactly row_count*width*16 (colour, fp32 G-buffer) or
+ * row_count*width*8 (half G-buffer), else RM_ERR_INVALID.  Synchronous.  rm_fb_download / rm_fb_upload keep working on
+ * half planes: the download widens exactly, the upload rounds to nearest even on the device, as the render kernels do.
+ * rm_fb_device_ptr of a half plane addresses binary16 data.  The raw-pointer entry points (rm_present_planes,
+ * rm_present_device, rm_present_striped_rows, rm_assemble_striped) take fp32 planes only: a framebuffer with the half
+ * G-buffer reaches them through rm_pack_present_rows, whose output is float4 in either format; rm_present,
+ * rm_present_rows, rm_pack_present_rows and rm_present_sharded* take either. */
+RM_API int rm_fb_download_raw(rm_fb* fb, int plane, void* host, size_t bytes);
+RM_API int rm_fb_upload_raw(rm_fb* fb, int plane, const void* host, size_t bytes);
 
 /* Raw device memory for hosts that have no allocator of their own: rm_present_rows, rm_present_device and
  * rm_assemble_striped_bytes take DEVICE pointers (in the reference these are textures the GL context owns,

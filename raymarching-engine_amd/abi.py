@@ -3,7 +3,7 @@ from __future__ import annotations
 
 import ctypes as C
 
-RM_ABI_VERSION = 8
+RM_ABI_VERSION = 9
 RM_MAX_BOUNCES = 10
 RM_MAX_LIGHTS = 10
 RM_MAX_PRIMS = 256
@@ -21,6 +21,7 @@ RM_RENDER_NO_FAR_JUMP = 64
 RM_RENDER_NO_CULL = 128
 RM_PIPELINE_NONE, RM_PIPELINE_PIXEL_KERNEL, RM_PIPELINE_WAVEFRONT = 0, 1, 2
 RM_PLANE_COLOR, RM_PLANE_NORMAL_DOF, RM_PLANE_ALBEDO_DEPTH = 0, 1, 2
+RM_GBUFFER_F32, RM_GBUFFER_F16 = 0, 1  # G-buffer formats (ABI 9)
 RM_PROBE_SDF, RM_PROBE_CAST_RAY, RM_PROBE_NORMAL, RM_PROBE_MATERIAL, RM_PROBE_CAST_STEPS, RM_PROBE_CAST_SHADOW = 0, 1, 2, 3, 4, 5
 RM_MATH_FUNCTIONS = ("sin", "cos", "log", "exp", "pow", "acos", "atan2", "tan", "pow_pair_nm1", "pow_pair_n", "sincos_s", "sincos_c", "sqrt", "div")  # RM_MATH_*
 

@@ -31,7 +31,7 @@ hipError_t rm_gl_launch_pixels(const void* kparams, hipStream_t stream);
 hipError_t rm_gl_launch_probe(const void* probe_params, hipStream_t stream);
 hipError_t rm_gl_launch_math_probe(int fn, const float* a, const float* b, int n, float* out, hipStream_t stream);
 hipError_t rm_gl_launch_camera_rng(const RmUniforms* u, int W, int H, int what, int count, float* out, hipStream_t stream);
-hipError_t rm_gl_launch_present(const float4* color, const float4* normal_dof, int W, int H, float brightness, uchar4* out, hipStream_t stream);
+hipError_t rm_gl_launch_present(const float4* color, const void* normal_dof, bool nd_half, int W, int H, float brightness, uchar4* out, hipStream_t stream);
 hipError_t rm_gl_launch_present_striped(const float4* color, const float4* normal_dof, int W, int H, float brightness, uchar4* out, int stripe_rows, int parts,
                                         int part, int local_rows, hipStream_t stream);
 hipError_t rm_gl_launch_present_rows(const float4* color, long long pixels, float brightness, uchar4* out, hipStream_t stream);
@@ -159,9 +159,14 @@ struct rm_fb {
   rm_ctx* ctx = nullptr;
   int width = 0, height = 0, row_begin = 0, row_count = 0;  // row_count = rows held by the planes
   int stripe_rows = 0, parts = 1, part = 0;                 // striped window when stripe_rows > 0
-  float4* plane[3] = {nullptr, nullptr, nullptr};
+  float4* plane[3] = {nullptr, nullptr, nullptr};  // planes 1 and 2 hold rm_half4 when gbuffer == RM_GBUFFER_F16
   bool owned = false;
+  int gbuffer = RM_GBUFFER_F32;
 };
+
+// bytes per pixel of a plane, and of the whole plane
+static size_t plane_px_bytes(int gbuffer, int plane) { return (plane > 0 && gbuffer == RM_GBUFFER_F16) ? sizeof(rm_half4) : sizeof(float4); }
+static size_t plane_bytes(const rm_fb* fb, int plane) { return plane_px_bytes(fb->gbuffer, plane) * (size_t)fb->width * (size_t)fb->row_count; }
 
 static thread_local std::string g_create_error;
 
@@ -755,18 +760,36 @@ static int fb_check(rm_ctx* ctx, int width, int height, int row_begin, int row_c
   return RM_OK;
 }
 
+static int gbuffer_check(rm_ctx* ctx, int gbuffer, const char* what) {
+  if (gbuffer != RM_GBUFFER_F32 && gbuffer != RM_GBUFFER_F16)
+    return fail(ctx, RM_ERR_INVALID, std::string(what) + ": unknown G-buffer format (RM_GBUFFER_F32 or RM_GBUFFER_F16)");
+  return RM_OK;
+}
+
+// caller-owned planes: colour 16-byte aligned, the G-buffer planes aligned to their own pixel (16 or 8 bytes)
+static int planes_aligned(const void* color, const void* normal_dof, const void* albedo_depth, int gbuffer) {
+  const uintptr_t g = (uintptr_t)plane_px_bytes(gbuffer, 1) - 1;
+  return !((reinterpret_cast<uintptr_t>(color) & 15u) || (reinterpret_cast<uintptr_t>(normal_dof) & g) || (reinterpret_cast<uintptr_t>(albedo_depth) & g));
+}
+
 int rm_fb_create(rm_ctx* ctx, int width, int height, int row_begin, int row_count, rm_fb** out) {
+  return rm_fb_create_fmt(ctx, width, height, row_begin, row_count, RM_GBUFFER_F32, out);
+}
+
+int rm_fb_create_fmt(rm_ctx* ctx, int width, int height, int row_begin, int row_count, int gbuffer, rm_fb** out) {
   if (!ctx || !out) return fail(ctx, RM_ERR_INVALID, "rm_fb_create: NULL argument");
   *out = nullptr;
+  if (int rc = gbuffer_check(ctx, gbuffer, "rm_fb_create")) return rc;
   if (int rc = fb_check(ctx, width, height, row_begin, row_count)) return rc;
   rm_fb* fb = new (std::nothrow) rm_fb();
   if (!fb) return fail(ctx, RM_ERR_DEVICE, "out of host memory");
   fb->ctx = ctx;
   fb->width = width; fb->height = height; fb->row_begin = row_begin; fb->row_count = row_count;
   fb->owned = true;
+  fb->gbuffer = gbuffer;
   (void)hipSetDevice(ctx->device);
-  const size_t bytes = sizeof(float4) * (size_t)width * (size_t)row_count;
   for (int i = 0; i < 3; i++) {
+    const size_t bytes = plane_bytes(fb, i);
     hipError_t e = hipMalloc(reinterpret_cast<void**>(&fb->plane[i]), bytes);
     if (e == hipSuccess) e = hipMemsetAsync(fb->plane[i], 0, bytes, ctx->stream);
     if (e != hipSuccess) {
@@ -791,13 +814,19 @@ static int striped_rows_below(int y, int stripe, int parts, int part) {
 
 int rm_fb_create_striped(rm_ctx* ctx, int width, int height, int stripe_rows, int parts, int part, void* color,
                          void* normal_dof, void* albedo_depth, rm_fb** out) {
+  return rm_fb_create_striped_fmt(ctx, width, height, stripe_rows, parts, part, color, normal_dof, albedo_depth, RM_GBUFFER_F32, out);
+}
+
+int rm_fb_create_striped_fmt(rm_ctx* ctx, int width, int height, int stripe_rows, int parts, int part, void* color,
+                             void* normal_dof, void* albedo_depth, int gbuffer, rm_fb** out) {
   if (!ctx || !out) return fail(ctx, RM_ERR_INVALID, "rm_fb_create_striped: NULL argument");
   *out = nullptr;
+  if (int rc = gbuffer_check(ctx, gbuffer, "rm_fb_create_striped")) return rc;
   if (int rc = fb_check(ctx, width, height, 0, 1)) return rc;
   if (stripe_rows < 1 || parts < 1 || part < 0 || part >= parts) return fail(ctx, RM_ERR_INVALID, "rm_fb_create_striped: need stripe_rows >= 1 and 0 <= part < parts");
   if ((normal_dof == nullptr) != (albedo_depth == nullptr) || (!color && normal_dof)) return fail(ctx, RM_ERR_INVALID, "rm_fb_create_striped: give all planes, colour only, or none");
-  if ((reinterpret_cast<uintptr_t>(color) | reinterpret_cast<uintptr_t>(normal_dof) | reinterpret_cast<uintptr_t>(albedo_depth)) & 15u)
-    return fail(ctx, RM_ERR_INVALID, "rm_fb_create_striped: planes must be 16-byte aligned");
+  if (!planes_aligned(color, normal_dof, albedo_depth, gbuffer))
+    return fail(ctx, RM_ERR_INVALID, "rm_fb_create_striped: planes must be aligned to their pixel (16 bytes; 8 for half G-buffer planes)");
   const int rows = striped_rows_below(height, stripe_rows, parts, part);
   if (rows < 1) return fail(ctx, RM_ERR_INVALID, "rm_fb_create_striped: this part holds no rows");
   rm_fb* fb = new (std::nothrow) rm_fb();
@@ -805,6 +834,7 @@ int rm_fb_create_striped(rm_ctx* ctx, int width, int height, int stripe_rows, in
   fb->ctx = ctx;
   fb->width = width; fb->height = height; fb->row_begin = 0; fb->row_count = rows;
   fb->stripe_rows = stripe_rows; fb->parts = parts; fb->part = part;
+  fb->gbuffer = gbuffer;
   if (color) {
     fb->plane[0] = static_cast<float4*>(color);
     fb->plane[1] = static_cast<float4*>(normal_dof);
@@ -813,8 +843,8 @@ int rm_fb_create_striped(rm_ctx* ctx, int width, int height, int stripe_rows, in
   } else {
     fb->owned = true;
     (void)hipSetDevice(ctx->device);
-    const size_t bytes = sizeof(float4) * (size_t)width * (size_t)rows;
     for (int i = 0; i < 3; i++) {
+      const size_t bytes = plane_bytes(fb, i);
       hipError_t e = hipMalloc(reinterpret_cast<void**>(&fb->plane[i]), bytes);
       if (e == hipSuccess) e = hipMemsetAsync(fb->plane[i], 0, bytes, ctx->stream);
       if (e != hipSuccess) {
@@ -835,12 +865,18 @@ int rm_fb_height(const rm_fb* fb) { return fb ? fb->height : 0; }
 
 int rm_fb_wrap(rm_ctx* ctx, int width, int height, int row_begin, int row_count, void* color, void* normal_dof,
                void* albedo_depth, rm_fb** out) {
+  return rm_fb_wrap_fmt(ctx, width, height, row_begin, row_count, color, normal_dof, albedo_depth, RM_GBUFFER_F32, out);
+}
+
+int rm_fb_wrap_fmt(rm_ctx* ctx, int width, int height, int row_begin, int row_count, void* color, void* normal_dof,
+                   void* albedo_depth, int gbuffer, rm_fb** out) {
   if (!ctx || !out || !color) return fail(ctx, RM_ERR_INVALID, "rm_fb_wrap: NULL argument");
   *out = nullptr;
+  if (int rc = gbuffer_check(ctx, gbuffer, "rm_fb_wrap")) return rc;
   if (int rc = fb_check(ctx, width, height, row_begin, row_count)) return rc;
   if ((normal_dof == nullptr) != (albedo_depth == nullptr)) return fail(ctx, RM_ERR_INVALID, "rm_fb_wrap: give both G-buffer planes or neither");
-  if ((reinterpret_cast<uintptr_t>(color) | reinterpret_cast<uintptr_t>(normal_dof) | reinterpret_cast<uintptr_t>(albedo_depth)) & 15u)
-    return fail(ctx, RM_ERR_INVALID, "rm_fb_wrap: planes must be 16-byte aligned");
+  if (!planes_aligned(color, normal_dof, albedo_depth, gbuffer))
+    return fail(ctx, RM_ERR_INVALID, "rm_fb_wrap: planes must be aligned to their pixel (16 bytes; 8 for half G-buffer planes)");
   rm_fb* fb = new (std::nothrow) rm_fb();
   if (!fb) return fail(ctx, RM_ERR_DEVICE, "out of host memory");
   fb->ctx = ctx;
@@ -849,16 +885,18 @@ int rm_fb_wrap(rm_ctx* ctx, int width, int height, int row_begin, int row_count,
   fb->plane[1] = static_cast<float4*>(normal_dof);
   fb->plane[2] = static_cast<float4*>(albedo_depth);
   fb->owned = false;
+  fb->gbuffer = gbuffer;
   *out = fb;
   return RM_OK;
 }
 
+int rm_fb_gbuffer(const rm_fb* fb) { return fb ? fb->gbuffer : RM_GBUFFER_F32; }
+
 int rm_fb_clear(rm_fb* fb) {
   if (!fb) return RM_ERR_INVALID;
   rm_ctx* ctx = fb->ctx;
-  const size_t bytes = sizeof(float4) * (size_t)fb->width * (size_t)fb->row_count;
   for (int i = 0; i < 3; i++)
-    if (fb->plane[i]) RM_HIP(ctx, hipMemsetAsync(fb->plane[i], 0, bytes, ctx->stream));
+    if (fb->plane[i]) RM_HIP(ctx, hipMemsetAsync(fb->plane[i], 0, plane_bytes(fb, i), ctx->stream));
   return RM_OK;
 }
 
@@ -872,12 +910,35 @@ void rm_fb_destroy(rm_fb* fb) {
   delete fb;
 }
 
+// a half plane through fp32 on the device (rm_narrow / rm_widen, the render kernels' own helpers): a scratch plane of float4
+static int convert_half_plane(rm_fb* fb, int plane, void* host, bool upload) {
+  rm_ctx* ctx = fb->ctx;
+  const long long pixels = (long long)fb->width * (long long)fb->row_count;
+  const size_t bytes = sizeof(float4) * (size_t)pixels;
+  RM_HIP(ctx, hipSetDevice(ctx->device));
+  void* tmp = nullptr;
+  RM_HIP(ctx, hipMalloc(&tmp, bytes));
+  hipError_t e;
+  if (upload) {
+    e = hipMemcpyAsync(tmp, host, bytes, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = rm::launch_convert(tmp, fb->plane[plane], pixels, true, ctx->stream);
+  } else {
+    e = rm::launch_convert(fb->plane[plane], tmp, pixels, false, ctx->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(host, tmp, bytes, hipMemcpyDeviceToHost, ctx->stream);
+  }
+  const hipError_t s = hipStreamSynchronize(ctx->stream);
+  (void)hipFree(tmp);
+  RM_HIP(ctx, e);
+  RM_HIP(ctx, s);
+  return RM_OK;
+}
+
 int rm_fb_download(rm_fb* fb, int plane, float* host) {
   if (!fb || !host || plane < 0 || plane > 2) return fb ? fail(fb->ctx, RM_ERR_INVALID, "rm_fb_download: bad argument") : RM_ERR_INVALID;
   rm_ctx* ctx = fb->ctx;
   if (!fb->plane[plane]) return fail(ctx, RM_ERR_INVALID, "rm_fb_download: this framebuffer has no such plane");
-  const size_t bytes = sizeof(float4) * (size_t)fb->width * (size_t)fb->row_count;
-  RM_HIP(ctx, hipMemcpyAsync(host, fb->plane[plane], bytes, hipMemcpyDeviceToHost, ctx->stream));
+  if (plane_px_bytes(fb->gbuffer, plane) != sizeof(float4)) return convert_half_plane(fb, plane, host, false);
+  RM_HIP(ctx, hipMemcpyAsync(host, fb->plane[plane], plane_bytes(fb, plane), hipMemcpyDeviceToHost, ctx->stream));
   RM_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return RM_OK;
 }
@@ -886,7 +947,35 @@ int rm_fb_upload(rm_fb* fb, int plane, const float* host) {
   if (!fb || !host || plane < 0 || plane > 2) return fb ? fail(fb->ctx, RM_ERR_INVALID, "rm_fb_upload: bad argument") : RM_ERR_INVALID;
   rm_ctx* ctx = fb->ctx;
   if (!fb->plane[plane]) return fail(ctx, RM_ERR_INVALID, "rm_fb_upload: this framebuffer has no such plane");
-  const size_t bytes = sizeof(float4) * (size_t)fb->width * (size_t)fb->row_count;
+  if (plane_px_bytes(fb->gbuffer, plane) != sizeof(float4)) return convert_half_plane(fb, plane, const_cast<float*>(host), true);
+  RM_HIP(ctx, hipMemcpyAsync(fb->plane[plane], host, plane_bytes(fb, plane), hipMemcpyHostToDevice, ctx->stream));
+  RM_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return RM_OK;
+}
+
+static int raw_check(rm_fb* fb, int plane, const void* host, size_t bytes, const char* what) {
+  if (!fb || !host || plane < 0 || plane > 2) return fb ? fail(fb->ctx, RM_ERR_INVALID, std::string(what) + ": bad argument") : RM_ERR_INVALID;
+  if (!fb->plane[plane]) return fail(fb->ctx, RM_ERR_INVALID, std::string(what) + ": this framebuffer has no such plane");
+  if (bytes != plane_bytes(fb, plane)) {
+    char buf[200];
+    std::snprintf(buf, sizeof buf, "%s: plane %d holds %zu bytes (%d x %d pixels of %zu bytes), not %zu", what, plane, plane_bytes(fb, plane), fb->row_count,
+                  fb->width, plane_px_bytes(fb->gbuffer, plane), bytes);
+    return fail(fb->ctx, RM_ERR_INVALID, buf);
+  }
+  return RM_OK;
+}
+
+int rm_fb_download_raw(rm_fb* fb, int plane, void* host, size_t bytes) {
+  if (int rc = raw_check(fb, plane, host, bytes, "rm_fb_download_raw")) return rc;
+  rm_ctx* ctx = fb->ctx;
+  RM_HIP(ctx, hipMemcpyAsync(host, fb->plane[plane], bytes, hipMemcpyDeviceToHost, ctx->stream));
+  RM_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return RM_OK;
+}
+
+int rm_fb_upload_raw(rm_fb* fb, int plane, const void* host, size_t bytes) {
+  if (int rc = raw_check(fb, plane, host, bytes, "rm_fb_upload_raw")) return rc;
+  rm_ctx* ctx = fb->ctx;
   RM_HIP(ctx, hipMemcpyAsync(fb->plane[plane], host, bytes, hipMemcpyHostToDevice, ctx->stream));
   RM_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return RM_OK;
@@ -1125,6 +1214,7 @@ static int build_params(rm_ctx* ctx, rm_scene* scene, rm_fb* fb, const RmUniform
   P->block_order = nullptr;
   P->block_cost = nullptr;
   P->no_far_jump = (flags & RM_RENDER_NO_FAR_JUMP) ? 1 : 0;
+  P->gbuffer_half = fb->gbuffer == RM_GBUFFER_F16 ? 1 : 0;
   if (P->no_far_jump) P->scene.far_end = 0, P->scene.clear_rho = 0.0f;  // the far-field shortcuts inside an evaluation (KIFS tree) read the scene block
   if (flags & RM_RENDER_NO_CULL) P->scene.cull.cells = nullptr;
   return RM_OK;
@@ -1332,6 +1422,7 @@ static bool uses_wavefront(const rm_ctx* ctx, const KParams& P, int flags) {
   if (!RM_WITH_WAVEFRONT) return false;  // the product library (build_params refuses the flag)
   if (ctx->gl_stack && !(flags & RM_RENDER_FAST)) return false;
   if (P.scene.table_flags & (RM_TABLE_HAS_SURFACES | RM_TABLE_HAS_KIND)) return false;
+  if (P.gbuffer_half) return false;  // the half G-buffer is blended by rm_combine_kernel behind the staged pixel kernel only
   return (flags & RM_RENDER_WAVEFRONT) ? true : (flags & RM_RENDER_MEGAKERNEL) ? false : prefer_wavefront(P, flags);
 }
 
@@ -1363,9 +1454,10 @@ static size_t staging_budget(rm_ctx* ctx) {
 
 // The pixel kernel of one sample -- or of a batch of `batch` samples, randNoise pairs in `noise` -- on a side stream,
 // staged, and its blend on the context's stream (see rm_ctx).
-static hipError_t launch_pixels_in_flight(rm_ctx* ctx, const KParams& P, int flags, int batch = 1, const float* noise = nullptr) {
+// depth: staging slots to rotate through (0 = the context's samples in flight; 1 = a sample's render waits for the previous blend)
+static hipError_t launch_pixels_in_flight(rm_ctx* ctx, const KParams& P, int flags, int batch = 1, const float* noise = nullptr, int depth = 0) {
   hipError_t e;
-  const int depth = ctx->samples_in_flight;
+  if (depth <= 0) depth = ctx->samples_in_flight;
   // side streams are made as the depth asks for them, not all RM_SP_MAX at once: the HIP runtime deals a process's streams
   // over a few hardware queues, and streams that share a queue serialise (measured: 0.59 instead of 0.42 ms per sample on a 1/8 shard)
   for (int s = 0; s < depth; s++) {
@@ -1504,6 +1596,12 @@ static hipError_t launch(rm_ctx* ctx, const KParams& P, int flags) {
 #if RM_WITH_WAVEFRONT
   if (wavefront) return launch_wavefront(ctx, P, flags);
 #endif
+  // The half G-buffer (RM_GBUFFER_F16) is blended by rm_combine_kernel only -- the pixel kernel's own blend is the fp32 one, left
+  // exactly as it was -- so a render that writes the G-buffer (full mode, a bounce, the planes asked for: raymarcher.frag:347-351
+  // runs at bounce 0) is always staged; with RM_RENDER_NO_OVERLAP on one staging slot, so that a sample's render waits for the
+  // previous sample's blend.  No unstaged fallback: without room for the staging of the tile the call fails (render in tiles).
+  if (P.gbuffer_half && P.normal_dof != nullptr && P.u.renderMode == 0 && P.u.reflections > 0.0f)
+    return launch_pixels_in_flight(ctx, P, flags, 1, nullptr, (flags & RM_RENDER_NO_OVERLAP) ? 1 : 0);
   // full mode with at least one bounce: the kernel's only use of the planes is the final blend, which can be split off
   if (ctx->samples_in_flight > 1 && !(flags & RM_RENDER_NO_OVERLAP) && P.u.renderMode == 0 && P.u.reflections > 0.0f) {
     const hipError_t e = launch_pixels_in_flight(ctx, P, flags);
@@ -1620,14 +1718,20 @@ int rm_assemble_striped(rm_ctx* ctx, const void* src, int parts, int max_rows, i
 
 // ---- present ---------------------------------------------------------------------
 
-int rm_present_device(rm_ctx* ctx, const void* color, const void* normal_dof, int width, int height, int samples, void* out_rgba8_device,
-                      void* hip_stream) {
+// nd_half: normal_dof is a plane of rm_half4 (rm_present of a framebuffer with the half G-buffer); the raw-pointer entry points are fp32
+static int present_device(rm_ctx* ctx, const void* color, const void* normal_dof, bool nd_half, int width, int height, int samples, void* out_rgba8_device,
+                          void* hip_stream) {
   if (!ctx || !color || !out_rgba8_device) return fail(ctx, RM_ERR_INVALID, "rm_present_device: NULL argument");
   if (width < 1 || height < 1 || samples < 1) return fail(ctx, RM_ERR_INVALID, "rm_present_device: width, height and samples must be >= 1");
   RM_HIP(ctx, hipSetDevice(ctx->device));
-  RM_HIP(ctx, (ctx->gl_stack ? rm_gl_launch_present : rm::launch_present)(static_cast<const float4*>(color), static_cast<const float4*>(normal_dof), width, height,
+  RM_HIP(ctx, (ctx->gl_stack ? rm_gl_launch_present : rm::launch_present)(static_cast<const float4*>(color), normal_dof, nd_half, width, height,
                                  1.0f / (float)samples, static_cast<uchar4*>(out_rgba8_device), hip_stream ? static_cast<hipStream_t>(hip_stream) : ctx->stream));
   return RM_OK;
+}
+
+int rm_present_device(rm_ctx* ctx, const void* color, const void* normal_dof, int width, int height, int samples, void* out_rgba8_device,
+                      void* hip_stream) {
+  return present_device(ctx, color, normal_dof, false, width, height, samples, out_rgba8_device, hip_stream);
 }
 
 int rm_present_rows(rm_ctx* ctx, rm_fb* fb, int samples, void* out_rgba8_device, void* hip_stream) {
@@ -1645,12 +1749,12 @@ int rm_pack_present_rows(rm_ctx* ctx, rm_fb* fb, void* out_float4_device, void* 
   if (fb->ctx != ctx) return fail(ctx, RM_ERR_INVALID, "rm_pack_present_rows: framebuffer belongs to another context");
   if (reinterpret_cast<uintptr_t>(out_float4_device) & 15u) return fail(ctx, RM_ERR_INVALID, "rm_pack_present_rows: the buffer must be 16-byte aligned");
   RM_HIP(ctx, hipSetDevice(ctx->device));
-  RM_HIP(ctx, rm::launch_pack_rows(fb->plane[0], fb->plane[1], (long long)fb->width * (long long)fb->row_count, static_cast<float4*>(out_float4_device),
+  RM_HIP(ctx, rm::launch_pack_rows(fb->plane[0], fb->plane[1], fb->gbuffer == RM_GBUFFER_F16, (long long)fb->width * (long long)fb->row_count, static_cast<float4*>(out_float4_device),
                                    hip_stream ? static_cast<hipStream_t>(hip_stream) : ctx->stream));
   return RM_OK;
 }
 
-int rm_present_planes(rm_ctx* ctx, const void* color, const void* normal_dof, int width, int height, int samples, uint8_t* out_rgba8) {
+static int present_planes(rm_ctx* ctx, const void* color, const void* normal_dof, bool nd_half, int width, int height, int samples, uint8_t* out_rgba8) {
   if (!ctx || !color || !out_rgba8) return fail(ctx, RM_ERR_INVALID, "rm_present_planes: NULL argument");
   if (width < 1 || height < 1 || samples < 1) return fail(ctx, RM_ERR_INVALID, "rm_present_planes: width, height and samples must be >= 1");
   RM_HIP(ctx, hipSetDevice(ctx->device));
@@ -1665,17 +1769,21 @@ int rm_present_planes(rm_ctx* ctx, const void* color, const void* normal_dof, in
     RM_HIP(ctx, hipMalloc(reinterpret_cast<void**>(&ctx->present_buf), pixels * 4));
     ctx->present_cap = pixels;
   }
-  if (int rc = rm_present_device(ctx, color, normal_dof, width, height, samples, ctx->present_buf, nullptr)) return rc;
+  if (int rc = present_device(ctx, color, normal_dof, nd_half, width, height, samples, ctx->present_buf, nullptr)) return rc;
   RM_HIP(ctx, hipMemcpyAsync(out_rgba8, ctx->present_buf, pixels * 4, hipMemcpyDeviceToHost, ctx->stream));
   RM_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return RM_OK;
+}
+
+int rm_present_planes(rm_ctx* ctx, const void* color, const void* normal_dof, int width, int height, int samples, uint8_t* out_rgba8) {
+  return present_planes(ctx, color, normal_dof, false, width, height, samples, out_rgba8);
 }
 
 int rm_present(rm_ctx* ctx, rm_fb* fb, int samples, uint8_t* out_rgba8) {
   if (!ctx || !fb) return fail(ctx, RM_ERR_INVALID, "rm_present: NULL argument");
   if (fb->stripe_rows > 0 || fb->row_begin != 0 || fb->row_count != fb->height)
     return fail(ctx, RM_ERR_INVALID, "rm_present: the blur reads neighbouring rows, so it needs the whole frame: gather the planes and use rm_present_planes (or rm_present_rows when depth of field is off)");
-  return rm_present_planes(ctx, fb->plane[0], fb->plane[1], fb->width, fb->height, samples, out_rgba8);
+  return present_planes(ctx, fb->plane[0], fb->plane[1], fb->gbuffer == RM_GBUFFER_F16, fb->width, fb->height, samples, out_rgba8);
 }
 
 // ---- present of a frame sharded over the GPUs of ONE process ----------------------------------------
@@ -1766,7 +1874,7 @@ int rm_present_sharded_start(rm_ctx* const* ctxs, rm_fb* const* fbs, int parts, 
     rm_fb* f = fbs[p];
     RM_HIP(root, hipSetDevice(c->device));
     const long long pixels = (long long)W * (long long)f->row_count;
-    if (dof) RM_HIP(root, rm::launch_pack_rows(f->plane[0], f->plane[1], pixels, static_cast<float4*>(c->shard_rows), c->stream));
+    if (dof) RM_HIP(root, rm::launch_pack_rows(f->plane[0], f->plane[1], f->gbuffer == RM_GBUFFER_F16, pixels, static_cast<float4*>(c->shard_rows), c->stream));
     else RM_HIP(root, (c->gl_stack ? rm_gl_launch_present_rows : rm::launch_present_rows)(f->plane[0], pixels, 1.0f / (float)samples, static_cast<uchar4*>(c->shard_rows), c->stream));
     RM_HIP(root, hipEventRecord(c->shard_snap, c->stream));
     RM_HIP(root, hipStreamWaitEvent(c->shard_stream, c->shard_snap, 0));

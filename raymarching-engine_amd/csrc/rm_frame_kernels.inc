@@ -61,7 +61,20 @@ __global__ __launch_bounds__(256) void rm_combine_kernel(const KParams P) {
       }
     }
     P.color[pix] = col;
-    if (P.normal_dof != nullptr) {
+    if (P.normal_dof != nullptr && P.gbuffer_half) {  // RGBA16F: rounded to half after EVERY sample, as separate draws would
+      rm_half4* const hn = reinterpret_cast<rm_half4*>(P.normal_dof);
+      rm_half4* const ha = reinterpret_cast<rm_half4*>(P.albedo_depth);
+      rm_half4 qn = hn[pix], qa = ha[pix];
+      for (int k = 0; k < samples; k++) {
+        const float4* st = P.stage + (long long)k * 3ll * P.stage_stride;
+        const float4 n = st[P.stage_stride + i], a = st[2 * P.stage_stride + i];
+        const float4 pn = rm_widen(qn), pa = rm_widen(qa);
+        qn = rm_narrow(make_float4(pn.x + n.x, pn.y + n.y, pn.z + n.z, pn.w + n.w));
+        qa = rm_narrow(make_float4(pa.x + a.x, pa.y + a.y, pa.z + a.z, pa.w + a.w));
+      }
+      hn[pix] = qn;
+      ha[pix] = qa;
+    } else if (P.normal_dof != nullptr) {
       float4 pn = P.normal_dof[pix], pa = P.albedo_depth[pix];
       for (int k = 0; k < samples; k++) {
         const float4* st = P.stage + (long long)k * 3ll * P.stage_stride;
@@ -95,8 +108,12 @@ hipError_t launch_combine(const KParams& P, hipStream_t stream) {
 // planes) and the result goes to the part's packed rows -- so that with depth of field on every GPU blurs the stripes it holds
 // instead of one GPU blurring the whole frame (display.frag:44-55 reads up to 16 rows either side of a pixel: other GPUs' rows).
 // The same taps in the same order with the same arithmetic: the bytes of the whole-frame pass (TY = 1: nothing is staged).
-template <int TY, bool STRIPED>
-__global__ __launch_bounds__(256) void rm_present_kernel(const float4* color, const float4* normal_dof, int W, int H, float brightness,
+// ND: the element of the normal_dof plane -- float4, or rm_half4 for a framebuffer with the half G-buffer (its .w widened exactly).
+__device__ inline float dof_of(const float4& v) { return v.w; }
+__device__ inline float dof_of(const rm_half4& v) { return rm_widen(v).w; }
+
+template <int TY, bool STRIPED, class ND = float4>
+__global__ __launch_bounds__(256) void rm_present_kernel(const float4* color, const ND* normal_dof, int W, int H, float brightness,
                                                          uchar4* out, int stripe_rows, int parts, int part, int local_rows) {
   constexpr int TX = 256 / TY;
   constexpr int SPAN_X = TX + 2 * RM_PRESENT_HALO, SPAN_Y = TY + 2 * RM_PRESENT_HALO;
@@ -108,7 +125,7 @@ __global__ __launch_bounds__(256) void rm_present_kernel(const float4* color, co
   const int row0 = STRIPED ? ((row0_local / stripe_rows) * parts + part) * stripe_rows + row0_local % stripe_rows : row0_local;  // rm_global_row
   const int y = row0 + ly;
   const bool inside = x < W && (STRIPED ? row0_local + ly < local_rows : y < H);
-  const float dof = (inside && normal_dof) ? normal_dof[(size_t)y * W + x].w * brightness : 0.0f;
+  const float dof = (inside && normal_dof) ? dof_of(normal_dof[(size_t)y * W + x]) * brightness : 0.0f;
   const float kernel = gclamp(dof * 200.0f, 0.0f, 16.0f);
   if (threadIdx.x == 0) wg_reach = 0;
   __syncthreads();
@@ -171,8 +188,14 @@ __global__ __launch_bounds__(256) void rm_present_kernel(const float4* color, co
   out[(size_t)(STRIPED ? row0_local + ly : y) * W + x] = make_uchar4(o[0], o[1], o[2], 255);
 }
 
-hipError_t launch_present(const float4* color, const float4* normal_dof, int W, int H, float brightness, uchar4* out, hipStream_t stream) {
-  hipLaunchKernelGGL((rm_present_kernel<16, false>), dim3((W + 15) / 16, (H + 15) / 16), dim3(256), 0, stream, color, normal_dof, W, H, brightness, out, 0, 0, 0, 0);
+// nd_half: normal_dof is a plane of rm_half4 (a framebuffer with the half G-buffer, rm_present)
+hipError_t launch_present(const float4* color, const void* normal_dof, bool nd_half, int W, int H, float brightness, uchar4* out, hipStream_t stream) {
+  if (nd_half)
+    hipLaunchKernelGGL((rm_present_kernel<16, false, rm_half4>), dim3((W + 15) / 16, (H + 15) / 16), dim3(256), 0, stream, color,
+                       static_cast<const rm_half4*>(normal_dof), W, H, brightness, out, 0, 0, 0, 0);
+  else
+    hipLaunchKernelGGL((rm_present_kernel<16, false>), dim3((W + 15) / 16, (H + 15) / 16), dim3(256), 0, stream, color,
+                       static_cast<const float4*>(normal_dof), W, H, brightness, out, 0, 0, 0, 0);
   return hipGetLastError();
 }
 
@@ -219,15 +242,37 @@ hipError_t launch_present_rows(const float4* color, long long pixels, float brig
 // colour (:19,:53) and the accumulated depth-of-field radius (:21-23) and nothing else.  A sharded frame WITH depth of field
 // gathers these rows instead of tone-mapped bytes (the blur reads up to 16 rows either side, which other ranks hold);
 // assembled in image order the buffer serves rm_present_device as BOTH its colour and its normal_dof plane.
-__global__ __launch_bounds__(256) void rm_pack_rows_kernel(const float4* color, const float4* normal_dof, long long pixels, float4* out) {
+// (With the half G-buffer the .w is widened exactly: the packed rows stay float4, and everything downstream of them is unchanged.)
+template <class ND>
+__global__ __launch_bounds__(256) void rm_pack_rows_kernel(const float4* color, const ND* normal_dof, long long pixels, float4* out) {
   for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < pixels; i += (long long)gridDim.x * 256) {
     const float4 c = color[i];
-    out[i] = make_float4(c.x, c.y, c.z, normal_dof != nullptr ? normal_dof[i].w : 0.0f);
+    out[i] = make_float4(c.x, c.y, c.z, normal_dof != nullptr ? dof_of(normal_dof[i]) : 0.0f);
   }
 }
 
-hipError_t launch_pack_rows(const float4* color, const float4* normal_dof, long long pixels, float4* out, hipStream_t stream) {
-  hipLaunchKernelGGL(rm_pack_rows_kernel, dim3(small_grid(pixels)), dim3(256), 0, stream, color, normal_dof, pixels, out);
+hipError_t launch_pack_rows(const float4* color, const void* normal_dof, bool nd_half, long long pixels, float4* out, hipStream_t stream) {
+  if (nd_half)
+    hipLaunchKernelGGL(rm_pack_rows_kernel<rm_half4>, dim3(small_grid(pixels)), dim3(256), 0, stream, color, static_cast<const rm_half4*>(normal_dof), pixels, out);
+  else
+    hipLaunchKernelGGL(rm_pack_rows_kernel<float4>, dim3(small_grid(pixels)), dim3(256), 0, stream, color, static_cast<const float4*>(normal_dof), pixels, out);
+  return hipGetLastError();
+}
+
+// ---- a half plane from / to fp32 (rm_fb_upload / rm_fb_download of a framebuffer with the half G-buffer) -------------------
+// The upload narrows with the helper the render kernels store with, so what a host uploads is rounded exactly as an accumulation is.
+__global__ __launch_bounds__(256) void rm_narrow_kernel(const float4* src, rm_half4* dst, long long pixels) {
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < pixels; i += (long long)gridDim.x * 256) dst[i] = rm_narrow(src[i]);
+}
+__global__ __launch_bounds__(256) void rm_widen_kernel(const rm_half4* src, float4* dst, long long pixels) {
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < pixels; i += (long long)gridDim.x * 256) dst[i] = rm_widen(src[i]);
+}
+
+hipError_t launch_convert(const void* src, void* dst, long long pixels, bool narrow, hipStream_t stream) {
+  if (narrow)
+    hipLaunchKernelGGL(rm_narrow_kernel, dim3(small_grid(pixels)), dim3(256), 0, stream, static_cast<const float4*>(src), static_cast<rm_half4*>(dst), pixels);
+  else
+    hipLaunchKernelGGL(rm_widen_kernel, dim3(small_grid(pixels)), dim3(256), 0, stream, static_cast<const rm_half4*>(src), static_cast<float4*>(dst), pixels);
   return hipGetLastError();
 }
 #endif

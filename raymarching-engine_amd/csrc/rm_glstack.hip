@@ -19,8 +19,8 @@ hipError_t rm_gl_launch_probe(const void* probe_params, hipStream_t stream) { re
 hipError_t rm_gl_launch_camera_rng(const RmUniforms* u, int W, int H, int what, int count, float* out, hipStream_t stream) {
   return rm_gl::launch_camera_rng(*u, W, H, what, count, out, stream);
 }
-hipError_t rm_gl_launch_present(const float4* color, const float4* normal_dof, int W, int H, float brightness, uchar4* out, hipStream_t stream) {
-  return rm_gl::launch_present(color, normal_dof, W, H, brightness, out, stream);
+hipError_t rm_gl_launch_present(const float4* color, const void* normal_dof, bool nd_half, int W, int H, float brightness, uchar4* out, hipStream_t stream) {
+  return rm_gl::launch_present(color, normal_dof, nd_half, W, H, brightness, out, stream);
 }
 hipError_t rm_gl_launch_present_striped(const float4* color, const float4* normal_dof, int W, int H, float brightness, uchar4* out, int stripe_rows, int parts,
                                         int part, int local_rows, hipStream_t stream) {

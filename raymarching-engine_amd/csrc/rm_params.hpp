@@ -216,6 +216,24 @@ struct DevScene {
   CullGrid cull;
 };
 
+// ---- the half-precision G-buffer (RM_GBUFFER_F16: LoadRenderJobContext.tsx:81-119 allocates normal + DoF radius and albedo + depth
+// as RGBA16F) ---------------------------------------------------------------------------------------------------------------------------
+// A pixel of such a plane is 4 x IEEE binary16, 8 bytes, RGBA.  An accumulation reads the stored value widened to fp32 (exact), adds
+// the sample's contribution in fp32 as the fp32 planes do, and stores the sum rounded to binary16 to nearest even (overflow to +-inf,
+// subnormals kept): what raymarcher.frag:347-351 does with an RGBA16F attachment.  Every kernel that touches a half plane goes
+// through these two helpers.  (_Float16)(float) is round-to-nearest-even; on gfx950 it lowers to v_cvt_pk_f16_f32 / v_cvt_f16_f32,
+// which round by the MODE register (RNE) -- never v_cvt_pkrtz_f16_f32, which truncates.  The kernels keep hipcc's default
+// float_denorm_mode_16_64 = 3: flushing f16 subnormals would change small normal components.
+typedef _Float16 rm_half4 __attribute__((ext_vector_type(4)));  // 8 bytes, 8-byte aligned: one dwordx2 load / store
+static_assert(sizeof(rm_half4) == 8, "rm_half4 is 8 bytes");
+
+__device__ inline float4 rm_widen(const rm_half4 h) { return make_float4((float)h.x, (float)h.y, (float)h.z, (float)h.w); }
+__device__ inline rm_half4 rm_narrow(const float4 v) {
+  rm_half4 h;
+  h.x = (_Float16)v.x; h.y = (_Float16)v.y; h.z = (_Float16)v.z; h.w = (_Float16)v.w;
+  return h;
+}
+
 struct KParams {
   RmUniforms u;
   DevScene scene;
@@ -244,6 +262,8 @@ struct KParams {
   const unsigned int* block_order;
   unsigned int* block_cost;
   int no_far_jump;  // RM_RENDER_NO_FAR_JUMP: march escaping rays step by step (a measurement / test switch, same bits)
+  int gbuffer_half;  // RM_GBUFFER_F16: normal_dof / albedo_depth point at rm_half4 planes -- read by rm_combine_kernel; a launch of
+                     // the pixel kernel that would blend into them itself is never made (rm_api.hip launch: always staged)
 };
 
 // a table long enough for the compacting pixel kernel (rm_device.hpp RM_KIND_TABLE_BIG); launcher and grid computation agree through this
@@ -322,9 +342,11 @@ hipError_t wf_launch_shade_strict(const WfParams& W, hipStream_t stream);
 hipError_t wf_launch_shade_fast(const WfParams& W, hipStream_t stream);
 bool wf_kind_has_cost_classes(int kind);
 hipError_t launch_assemble(const void* src, int parts, int max_rows, long long row_bytes, int H, int stripe_rows, void* dst, hipStream_t stream);
-hipError_t launch_pack_rows(const float4* color, const float4* normal_dof, long long pixels, float4* out, hipStream_t stream);
+hipError_t launch_pack_rows(const float4* color, const void* normal_dof, bool nd_half, long long pixels, float4* out, hipStream_t stream);
+// one plane between fp32 and half (rm_fb_upload / rm_fb_download of a half plane): narrow = fp32 -> half with rm_narrow, else rm_widen
+hipError_t launch_convert(const void* src, void* dst, long long pixels, bool narrow, hipStream_t stream);
 hipError_t launch_present_rows(const float4* color, long long pixels, float brightness, uchar4* out, hipStream_t stream);
-hipError_t launch_present(const float4* color, const float4* normal_dof, int W, int H, float brightness, uchar4* out, hipStream_t stream);
+hipError_t launch_present(const float4* color, const void* normal_dof, bool nd_half, int W, int H, float brightness, uchar4* out, hipStream_t stream);
 hipError_t launch_present_striped(const float4* color, const float4* normal_dof, int W, int H, float brightness, uchar4* out, int stripe_rows, int parts, int part,
                                   int local_rows, hipStream_t stream);
 hipError_t wf_launch_stage(const WfParams& W, int stage, hipStream_t stream);

@@ -258,7 +258,7 @@ class ShardedFramebuffer:
 
     sharded = True
 
-    def __init__(self, native_ctx, group: ShardGroup, width: int, height: int, render_stream: Optional[int] = None):
+    def __init__(self, native_ctx, group: ShardGroup, width: int, height: int, render_stream: Optional[int] = None, gbuffer: str = "f32"):
         import torch
 
         self.torch = torch
@@ -267,7 +267,10 @@ class ShardedFramebuffer:
                              "(job.RenderJobContext does), or ShardGroup(force=True) to run the collective path with one rank")
         self.ctx, self.group = native_ctx, group
         self.width, self.height = width, height
-        self.fb = native_ctx.create_striped_framebuffer(width, height, group.stripe_rows, group.world, group.rank)
+        # gbuffer "f16": half G-buffer planes (native.Context.create_framebuffer); the payloads gathered are the same in either format
+        fmt = {} if gbuffer == "f32" else {"gbuffer": gbuffer}
+        self.fb = native_ctx.create_striped_framebuffer(width, height, group.stripe_rows, group.world, group.rank, **fmt)
+        self.gbuffer = gbuffer
         self.row_count = self.fb.row_count
         self.render_stream = render_stream
         self.dof = False  # does the job that renders into this framebuffer have depth of field (set by do_render_job)

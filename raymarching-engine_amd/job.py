@@ -216,11 +216,16 @@ class RenderJobContext:
     stream = None  # the torch stream a sharded context orders its device work on (GPU)
 
     stripes = None  # (parts, part): this context holds one part's 8-row stripes of every frame, with no group (measurement: one GPU standing in for a rank)
+    # the G-buffer format of every framebuffer the context makes: "f32" (the default, the goldens' software GL stack) or "f16" (the
+    # reference's RGBA16F normal + DoF radius and albedo + depth planes on a hardware GL, LoadRenderJobContext.tsx:81-119)
+    gbuffer = "f32"
 
     def __init__(self, device: int = 0, flags: int = abi.RM_RENDER_STRICT, rows: Optional[Tuple[int, int]] = None, group=None,
-                 native_context=None, stripes: Optional[Tuple[int, int]] = None):
+                 native_context=None, stripes: Optional[Tuple[int, int]] = None, gbuffer: str = "f32"):
         from . import native
 
+        native.gbuffer_code(gbuffer)  # ValueError before any device work
+        self.gbuffer = gbuffer
         self.native = native_context if native_context is not None else native.Context(device)
         self.flags = flags
         self.rows = rows  # (row_begin, row_count) window of this GPU, None = whole image
@@ -336,18 +341,19 @@ class RenderJobContext:
                     pfb.clear()  # :196-208: a new frameid restarts the accumulation
                 self._live[key] = pfb
                 return pfb
+        fmt = {} if self.gbuffer == "f32" else {"gbuffer": self.gbuffer}  # (the default goes unsaid: stand-in contexts predate the argument)
         if self.group is not None:
             from . import dist as rmdist
 
             fb = rmdist.ShardedFramebuffer(self.native, self.group, width, height,
-                                           render_stream=self.stream.cuda_stream if self.stream is not None else None)
+                                           render_stream=self.stream.cuda_stream if self.stream is not None else None, **fmt)
         elif self.stripes is not None:
             from . import shard
 
-            fb = self.native.create_striped_framebuffer(width, height, shard.STRIPE_ROWS, self.stripes[0], self.stripes[1])
+            fb = self.native.create_striped_framebuffer(width, height, shard.STRIPE_ROWS, self.stripes[0], self.stripes[1], **fmt)
         else:
             rb, rc = self.rows if self.rows is not None else (0, height)
-            fb = self.native.create_framebuffer(width, height, rb, rc)
+            fb = self.native.create_framebuffer(width, height, rb, rc, **fmt)
         self._live[key] = fb
         return fb
 

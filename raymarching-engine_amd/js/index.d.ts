@@ -56,8 +56,13 @@ export type RenderJobFramebufferInfo = {
   toDataURL(samples: number): string;
 };
 export type ShaderError = { type: "vertex" | "fragment" | "program"; infoLog: string };
+/** The G-buffer format of a context's framebuffers: "f32" (default) or "f16", the reference's RGBA16F normal + DoF radius and
+ *  albedo + depth planes (accumulated in half precision; the colour plane stays fp32). */
+export type GBufferFormat = "f32" | "f16";
 export class RenderJobContext {
   constructor(device?: number, flags?: number);
+  constructor(options: { device?: number; flags?: number; gbuffer?: GBufferFormat });
+  readonly gbuffer: GBufferFormat;
   fboCreate(width: number, height: number, frameid: number): RenderJobFramebufferInfo;
   fboDelete(width: number, height: number, frameid: number): void;
   close(): void;
@@ -72,6 +77,8 @@ export type ShardedFramebufferInfo = {
 };
 export class ShardedRenderJobContext {
   constructor(devices?: number[], flags?: number, samplesInFlight?: number);
+  constructor(options: { devices?: number[]; flags?: number; samplesInFlight?: number; gbuffer?: GBufferFormat });
+  readonly gbuffer: GBufferFormat;
   fboCreate(width: number, height: number, frameid: number): ShardedFramebufferInfo;
   fboDelete(width: number, height: number, frameid: number): void;
   close(): void;

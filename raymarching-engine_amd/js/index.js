@@ -22,7 +22,15 @@ const RM = {
   PRIM_SPHERE: 0, PRIM_BOX: 1, PRIM_REPEAT: 2, PRIM_FOLD: 3, PRIM_KIND: 4, PRIM_TORUS: 5, PRIM_CYLINDER: 6, PRIM_PLANE: 7,
   OP_UNION: 0, OP_SMOOTH_UNION: 1, OP_SUBTRACT: 2, OP_INTERSECT: 3, OP_SMOOTH_SUBTRACT: 4, OP_SMOOTH_INTERSECT: 5,
   RENDER_STRICT: 0, RENDER_FAST: 1, RENDER_COLOR_ONLY: 2, RENDER_MEGAKERNEL: 4, RENDER_WAVEFRONT: 16, RENDER_NO_OVERLAP: 32, RENDER_NO_FAR_JUMP: 64, RENDER_NO_CULL: 128,
+  GBUFFER_F32: 0, GBUFFER_F16: 1,
 };
+// G-buffer formats of a context's framebuffers (include/hip_raymarch.h RM_GBUFFER_*): "f32", the default (the goldens' software GL
+// stack), or "f16", the reference's RGBA16F normal + DoF radius and albedo + depth planes (LoadRenderJobContext.tsx:81-119)
+const GBUFFER = { f32: RM.GBUFFER_F32, f16: RM.GBUFFER_F16 };
+function gbufferCode(name) {
+  if (!Object.prototype.hasOwnProperty.call(GBUFFER, name)) throw new RangeError(`gbuffer must be "f32" or "f16", not ${JSON.stringify(name)}`);
+  return GBUFFER[name];
+}
 
 // ---- struct layouts (include/hip_raymarch.h; all fields are 4 bytes) ----------------
 const U_FIELDS = [
@@ -253,7 +261,11 @@ const scenePins = {  // mixed into both contexts, for hosts that hold handles th
 };
 
 class RenderJobContext {  // RenderJobContext + loadRenderJobContext (LoadRenderJobContext.tsx:162-287)
+  // new RenderJobContext(device?, flags?) or new RenderJobContext({ device, flags, gbuffer })
   constructor(device = 0, flags = RM.RENDER_STRICT) {
+    let gbuffer = "f32";
+    if (device !== null && typeof device === "object") ({ device = 0, flags = RM.RENDER_STRICT, gbuffer = "f32" } = device);
+    this.gbuffer = gbuffer; this.gbufferCode = gbufferCode(gbuffer);  // (before any device work)
     this.ctx = addon.ctxCreate(device); this.flags = flags; this.scenes = new Map(); this.pins = new Map(); this.live = new Map(); this.purgatory = [];
   }
   evict(keep) { evictScenes(this.scenes, (s) => { if (!(s && s.infoLog)) addon.sceneDestroy(s); }, this.pins, keep); }
@@ -272,7 +284,7 @@ class RenderJobContext {  // RenderJobContext + loadRenderJobContext (LoadRender
     const i = this.purgatory.findIndex((e) => e.w === w && e.h === h);
     let fb;
     if (i >= 0) { const e = this.purgatory.splice(i, 1)[0]; if (e.frameid !== frameid) addon.fbClear(e.fb); fb = e.fb; }
-    else fb = addon.fbCreate(this.ctx, w, h, 0, h);
+    else fb = addon.fbCreate(this.ctx, w, h, 0, h, this.gbufferCode);
     const info = { fb, width: w, height: h, frameid, download: (plane = 0) => { const out = new Float32Array(w * h * 4); addon.fbDownload(this.ctx, fb, plane, out); return out; },
                    // the present pass (display.frag) on the GPU: RGBA8, row 0 = bottom
                    present: (samples) => { const out = new Uint8Array(w * h * 4); addon.present(this.ctx, fb, samples, out); return out; },
@@ -302,7 +314,12 @@ class RenderJobContext {  // RenderJobContext + loadRenderJobContext (LoadRender
 // (The tile loop of the reference, RenderJobExecutor.tsx:148-182, is the precedent for cutting a job's frame.)
 const STRIPE_ROWS = 8;
 class ShardedRenderJobContext {
+  // new ShardedRenderJobContext(devices?, flags?, samplesInFlight?) or new ShardedRenderJobContext({ devices, flags, samplesInFlight, gbuffer })
   constructor(devices = [0], flags = RM.RENDER_STRICT, samplesInFlight = 3) {
+    let gbuffer = "f32";
+    if (devices !== null && typeof devices === "object" && !Array.isArray(devices))
+      ({ devices = [0], flags = RM.RENDER_STRICT, samplesInFlight = 3, gbuffer = "f32" } = devices);
+    this.gbuffer = gbuffer; this.gbufferCode = gbufferCode(gbuffer);
     if (!Array.isArray(devices) || devices.length < 1) throw new TypeError("ShardedRenderJobContext(devices: number[], flags?)");
     this.devices = devices.slice(); this.flags = flags;
     this.ctxs = devices.map((d) => addon.ctxCreate(d));
@@ -329,7 +346,7 @@ class ShardedRenderJobContext {
     if (i >= 0) { const e = this.purgatory.splice(i, 1)[0]; if (e.frameid !== frameid) for (const fb of e.fbs) addon.fbClear(fb); fbs = e.fbs; }
     else {
       fbs = [];
-      try { this.ctxs.forEach((c, p) => fbs.push(addon.fbCreateStriped(c, w, h, STRIPE_ROWS, this.ctxs.length, p))); }
+      try { this.ctxs.forEach((c, p) => fbs.push(addon.fbCreateStriped(c, w, h, STRIPE_ROWS, this.ctxs.length, p, this.gbufferCode))); }
       catch (e) { for (const fb of fbs) addon.fbDestroy(fb); throw e; }
     }
     const info = { fbs, width: w, height: h, frameid, sharded: true, dof: false,

@@ -163,16 +163,16 @@ static napi_value SceneDestroy(napi_env env, napi_callback_info info) {
   return nullptr;
 }
 
-// fbCreate(ctx, width, height, rowBegin, rowCount)
+// fbCreate(ctx, width, height, rowBegin, rowCount[, gbuffer]): gbuffer = RM_GBUFFER_F32 (default) or RM_GBUFFER_F16
 static napi_value FbCreate(napi_env env, napi_callback_info info) {
-  size_t argc = 5;
-  napi_value argv[5];
+  size_t argc = 6;
+  napi_value argv[6];
   NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
   rm_ctx* ctx = get_external<rm_ctx>(env, argv[0]);
-  int32_t v[4] = {0, 0, 0, 0};
-  for (int i = 0; i < 4; i++) napi_get_value_int32(env, argv[1 + i], &v[i]);
+  int32_t v[5] = {0, 0, 0, 0, RM_GBUFFER_F32};
+  for (int i = 0; i < 5 && 1 + i < (int)argc; i++) napi_get_value_int32(env, argv[1 + i], &v[i]);
   rm_fb* fb = nullptr;
-  if (rm_fb_create(ctx, v[0], v[1], v[2], v[3], &fb) != RM_OK) return throw_rm(env, ctx, "rm_fb_create");
+  if (rm_fb_create_fmt(ctx, v[0], v[1], v[2], v[3], v[4], &fb) != RM_OK) return throw_rm(env, ctx, "rm_fb_create");
   return make_external(env, fb);
 }
 
@@ -247,21 +247,21 @@ static napi_value Present(napi_env env, napi_callback_info info) {
   return nullptr;
 }
 
-// fbCreateStriped(ctx, width, height, stripeRows, parts, part): the stripes k with k % parts == part of a width x height image,
+// fbCreateStriped(ctx, width, height, stripeRows, parts, part[, gbuffer]): the stripes k with k % parts == part of a width x height image,
 // planes owned by the library (rm_fb_create_striped) -- what one GPU of a sharded frame holds
 static napi_value FbCreateStriped(napi_env env, napi_callback_info info) {
-  size_t argc = 6;
-  napi_value argv[6];
+  size_t argc = 7;
+  napi_value argv[7];
   NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
   rm_ctx* ctx = get_external<rm_ctx>(env, argv[0]);
   if (!ctx || argc < 6) {
-    napi_throw_type_error(env, nullptr, "fbCreateStriped(ctx, width, height, stripeRows, parts, part)");
+    napi_throw_type_error(env, nullptr, "fbCreateStriped(ctx, width, height, stripeRows, parts, part[, gbuffer])");
     return nullptr;
   }
-  int32_t v[5] = {0, 0, 0, 0, 0};
-  for (int i = 0; i < 5; i++) napi_get_value_int32(env, argv[1 + i], &v[i]);
+  int32_t v[6] = {0, 0, 0, 0, 0, RM_GBUFFER_F32};
+  for (int i = 0; i < 6 && 1 + i < (int)argc; i++) napi_get_value_int32(env, argv[1 + i], &v[i]);
   rm_fb* fb = nullptr;
-  if (rm_fb_create_striped(ctx, v[0], v[1], v[2], v[3], v[4], nullptr, nullptr, nullptr, &fb) != RM_OK) return throw_rm(env, ctx, "rm_fb_create_striped");
+  if (rm_fb_create_striped_fmt(ctx, v[0], v[1], v[2], v[3], v[4], nullptr, nullptr, nullptr, v[5], &fb) != RM_OK) return throw_rm(env, ctx, "rm_fb_create_striped");
   return make_external(env, fb);
 }
 

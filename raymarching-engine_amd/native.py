@@ -33,7 +33,19 @@ EXPORTS = [
     "rm_ctx_set_retire_eps", "rm_ctx_set_samples_in_flight", "rm_ctx_last_warning", "rm_ctx_set_cost_order", "rm_ctx_set_cull_min_pixels", "rm_ctx_set_cull_budget", "rm_ctx_cull_stats", "rm_debug_counters", "rm_device_memory", "rm_sync", "rm_scene_create", "rm_scene_destroy", "rm_fb_create", "rm_fb_create_striped", "rm_fb_rows", "rm_fb_width", "rm_fb_height", "rm_fb_wrap", "rm_fb_clear", "rm_fb_destroy",
     "rm_fb_download", "rm_fb_upload", "rm_fb_device_ptr", "rm_buffer_create", "rm_buffer_destroy", "rm_buffer_download", "rm_buffer_upload", "rm_render_sample", "rm_render_samples", "rm_ctx_set_sample_batch", "rm_ctx_set_gl_stack", "rm_render_timed",
     "rm_probe", "rm_probe_camera", "rm_probe_rng", "rm_probe_math", "rm_assemble_striped", "rm_assemble_striped_bytes", "rm_present", "rm_present_planes", "rm_present_device", "rm_present_rows", "rm_pack_present_rows", "rm_ctx_last_pipeline", "rm_present_sharded", "rm_present_sharded_start", "rm_present_sharded_finish", "rm_present_striped_rows", "rm_debug_cull_cell",
+    "rm_fb_create_fmt", "rm_fb_create_striped_fmt", "rm_fb_wrap_fmt", "rm_fb_gbuffer", "rm_fb_download_raw", "rm_fb_upload_raw",
 ]
+
+# G-buffer formats of a framebuffer (include/hip_raymarch.h RM_GBUFFER_*): "f32" (the default: the software GL stack's planes, which the
+# goldens were rendered on) or "f16" (the reference's RGBA16F normal + DoF radius and albedo + depth planes, LoadRenderJobContext.tsx:81-119)
+GBUFFER_FORMATS = {"f32": abi.RM_GBUFFER_F32, "f16": abi.RM_GBUFFER_F16}
+
+
+def gbuffer_code(gbuffer: str) -> int:
+    """The RM_GBUFFER_* value of a format name; ValueError for anything else."""
+    if not isinstance(gbuffer, str) or gbuffer not in GBUFFER_FORMATS:
+        raise ValueError(f"gbuffer must be one of {sorted(GBUFFER_FORMATS)}, not {gbuffer!r}")
+    return GBUFFER_FORMATS[gbuffer]
 
 
 def cull_cell(scene, centre, radius: float, margin: float = 0.0):
@@ -140,6 +152,12 @@ def load_library(path=None):
         "rm_fb_download": (ip, [vp, ip, fp]),
         "rm_fb_upload": (ip, [vp, ip, fp]),
         "rm_fb_device_ptr": (vp, [vp, ip]),
+        "rm_fb_create_fmt": (ip, [vp, ip, ip, ip, ip, ip, C.POINTER(vp)]),
+        "rm_fb_wrap_fmt": (ip, [vp, ip, ip, ip, ip, vp, vp, vp, ip, C.POINTER(vp)]),
+        "rm_fb_create_striped_fmt": (ip, [vp, ip, ip, ip, ip, ip, vp, vp, vp, ip, C.POINTER(vp)]),
+        "rm_fb_gbuffer": (ip, [vp]),
+        "rm_fb_download_raw": (ip, [vp, ip, vp, C.c_size_t]),
+        "rm_fb_upload_raw": (ip, [vp, ip, vp, C.c_size_t]),
         "rm_render_sample": (ip, [vp, vp, vp, C.POINTER(abi.RmUniforms), C.POINTER(abi.RmRect), ip]),
         "rm_render_samples": (ip, [vp, vp, vp, C.POINTER(abi.RmUniforms), fp, ip, C.POINTER(abi.RmRect), ip]),
         "rm_render_timed": (ip, [vp, vp, vp, C.POINTER(abi.RmUniforms), ip, C.POINTER(abi.RmRect), ip, fp]),
@@ -377,15 +395,17 @@ class Context:
     def create_scene(self, scene: Scene) -> "SceneHandle":
         return SceneHandle(self, scene)
 
-    def create_framebuffer(self, width: int, height: int, row_begin: int = 0, row_count: Optional[int] = None) -> "Framebuffer":
-        return Framebuffer(self, width, height, row_begin, height if row_count is None else row_count)
+    def create_framebuffer(self, width: int, height: int, row_begin: int = 0, row_count: Optional[int] = None, gbuffer: str = "f32") -> "Framebuffer":
+        """gbuffer: "f32" (default) or "f16", the reference's half-precision normal + DoF radius and albedo + depth planes."""
+        return Framebuffer(self, width, height, row_begin, height if row_count is None else row_count, gbuffer=gbuffer)
 
-    def create_striped_framebuffer(self, width, height, stripe_rows, parts, part, color_ptr=None, normal_ptr=None, albedo_ptr=None) -> "Framebuffer":
+    def create_striped_framebuffer(self, width, height, stripe_rows, parts, part, color_ptr=None, normal_ptr=None, albedo_ptr=None,
+                                   gbuffer: str = "f32") -> "Framebuffer":
         """Rows r with (r // stripe_rows) % parts == part, packed (row sharding across GPUs)."""
-        return Framebuffer(self, width, height, 0, 0, striped=(stripe_rows, parts, part, color_ptr, normal_ptr, albedo_ptr))
+        return Framebuffer(self, width, height, 0, 0, striped=(stripe_rows, parts, part, color_ptr, normal_ptr, albedo_ptr), gbuffer=gbuffer)
 
-    def wrap_framebuffer(self, width, height, row_begin, row_count, color_ptr, normal_ptr=None, albedo_ptr=None) -> "Framebuffer":
-        return Framebuffer(self, width, height, row_begin, row_count, wrap=(color_ptr, normal_ptr, albedo_ptr))
+    def wrap_framebuffer(self, width, height, row_begin, row_count, color_ptr, normal_ptr=None, albedo_ptr=None, gbuffer: str = "f32") -> "Framebuffer":
+        return Framebuffer(self, width, height, row_begin, row_count, wrap=(color_ptr, normal_ptr, albedo_ptr), gbuffer=gbuffer)
 
     def render_sample(self, scene: "SceneHandle", fb: "Framebuffer", uniforms: abi.RmUniforms, tile: Optional[abi.RmRect] = None,
                       flags: int = abi.RM_RENDER_STRICT):
@@ -444,21 +464,39 @@ class SceneHandle:
 
 
 class Framebuffer:
-    def __init__(self, ctx: Context, width, height, row_begin, row_count, wrap=None, striped=None):
+    def __init__(self, ctx: Context, width, height, row_begin, row_count, wrap=None, striped=None, gbuffer: str = "f32"):
+        fmt = gbuffer_code(gbuffer)
         self.ctx = ctx
         self.width, self.height, self.row_begin, self.row_count = width, height, row_begin, row_count
+        self.gbuffer = gbuffer
         h = C.c_void_p()
         if striped is not None:
             s, n, r, c0, c1, c2 = striped
-            ctx._check(ctx.lib.rm_fb_create_striped(ctx.h, width, height, s, n, r, C.c_void_p(c0 or 0), C.c_void_p(c1 or 0),
-                                                    C.c_void_p(c2 or 0), C.byref(h)))
+            ctx._check(ctx.lib.rm_fb_create_striped_fmt(ctx.h, width, height, s, n, r, C.c_void_p(c0 or 0), C.c_void_p(c1 or 0),
+                                                        C.c_void_p(c2 or 0), fmt, C.byref(h)))
             self.row_count = int(ctx.lib.rm_fb_rows(h))
         elif wrap is None:
-            ctx._check(ctx.lib.rm_fb_create(ctx.h, width, height, row_begin, row_count, C.byref(h)))
+            ctx._check(ctx.lib.rm_fb_create_fmt(ctx.h, width, height, row_begin, row_count, fmt, C.byref(h)))
         else:
-            ctx._check(ctx.lib.rm_fb_wrap(ctx.h, width, height, row_begin, row_count, C.c_void_p(wrap[0]),
-                                          C.c_void_p(wrap[1] or 0), C.c_void_p(wrap[2] or 0), C.byref(h)))
+            ctx._check(ctx.lib.rm_fb_wrap_fmt(ctx.h, width, height, row_begin, row_count, C.c_void_p(wrap[0]),
+                                              C.c_void_p(wrap[1] or 0), C.c_void_p(wrap[2] or 0), fmt, C.byref(h)))
         self.h = h
+
+    def plane_dtype(self, plane: int):
+        """numpy dtype of a plane as stored: float32, or float16 for the G-buffer planes of an "f16" framebuffer."""
+        return np.float16 if (plane != abi.RM_PLANE_COLOR and self.gbuffer == "f16") else np.float32
+
+    def download_raw(self, plane: int = abi.RM_PLANE_COLOR) -> np.ndarray:
+        """A plane as stored ([rows, W, 4] of plane_dtype(plane)): the half bits of an "f16" G-buffer plane, not widened."""
+        out = np.empty((self.row_count, self.width, 4), self.plane_dtype(plane))
+        self.ctx._check(self.ctx.lib.rm_fb_download_raw(self.h, plane, out.ctypes.data_as(C.c_void_p), out.nbytes))
+        return out
+
+    def upload_raw(self, plane: int, data: np.ndarray):
+        """Stores [rows, W, 4] of plane_dtype(plane) into a plane as they are."""
+        a = np.ascontiguousarray(data, self.plane_dtype(plane))
+        assert a.shape == (self.row_count, self.width, 4)
+        self.ctx._check(self.ctx.lib.rm_fb_upload_raw(self.h, plane, a.ctypes.data_as(C.c_void_p), a.nbytes))
 
     def clear(self):
         self.ctx._check(self.ctx.lib.rm_fb_clear(self.h))
@@ -469,11 +507,13 @@ class Framebuffer:
             self.h = None
 
     def download(self, plane: int = abi.RM_PLANE_COLOR) -> np.ndarray:
+        """A plane as float32 (a half plane widened exactly)."""
         out = np.empty((self.row_count, self.width, 4), np.float32)
         self.ctx._check(self.ctx.lib.rm_fb_download(self.h, plane, _fp(out)))
         return out
 
     def upload(self, plane: int, data: np.ndarray):
+        """float32 data into a plane (a half plane rounds it to nearest even, on the device)."""
         a = np.ascontiguousarray(data, np.float32)
         assert a.shape == (self.row_count, self.width, 4)
         self.ctx._check(self.ctx.lib.rm_fb_upload(self.h, plane, _fp(a)))
