@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define RM_ABI_VERSION 9 /* 9: RM_GBUFFER_F32 / _F16, rm_fb_create_fmt, rm_fb_create_striped_fmt, rm_fb_wrap_fmt, rm_fb_gbuffer, rm_fb_download_raw, rm_fb_upload_raw (additions only); 8: RM_PRIM_TORUS / _CYLINDER / _PLANE, RM_OP_SMOOTH_SUBTRACT / _INTERSECT, rm_probe_math (additions only); 7: rm_present_sharded_finish / rm_present_sharded take the size of the host buffer (a changed signature), rm_ctx_set_cull_min_pixels, rm_ctx_set_cull_budget, rm_ctx_cull_stats; 6: rm_present_striped_rows, rm_present_sharded_start / _finish, rm_ctx_last_warning, RM_PROBE_CAST_SHADOW, RM_PRIM_KIND (additions only); 3: rm_ctx_set_sample_batch, rm_buffer_*; 4: rm_ctx_set_gl_stack; 5: RmSurface / RmSceneDesc.surfaces (the struct grew), rm_pack_present_rows, rm_present_sharded, rm_ctx_last_pipeline, RM_RENDER_NO_FAR_JUMP, RM_RENDER_NO_CULL (additions only) */
+#define RM_ABI_VERSION 9 /* 9: RM_GBUFFER_F32 / _F16, rm_fb_create_fmt, rm_fb_create_striped_fmt, rm_fb_wrap_fmt, rm_fb_gbuffer, rm_fb_download_raw, rm_fb_upload_raw, RmDenoise, rm_denoise_default, rm_denoise, rm_denoise_device, rm_present_denoised (additions only); 8: RM_PRIM_TORUS / _CYLINDER / _PLANE, RM_OP_SMOOTH_SUBTRACT / _INTERSECT, rm_probe_math (additions only); 7: rm_present_sharded_finish / rm_present_sharded take the size of the host buffer (a changed signature), rm_ctx_set_cull_min_pixels, rm_ctx_set_cull_budget, rm_ctx_cull_stats; 6: rm_present_striped_rows, rm_present_sharded_start / _finish, rm_ctx_last_warning, RM_PROBE_CAST_SHADOW, RM_PRIM_KIND (additions only); 3: rm_ctx_set_sample_batch, rm_buffer_*; 4: rm_ctx_set_gl_stack; 5: RmSurface / RmSceneDesc.surfaces (the struct grew), rm_pack_present_rows, rm_present_sharded, rm_ctx_last_pipeline, RM_RENDER_NO_FAR_JUMP, RM_RENDER_NO_CULL (additions only) */
 
 #define RM_MAX_BOUNCES 10 /* raymarchingStepCountsArray[10], raymarcher.frag:31 */
 #define RM_MAX_LIGHTS 10  /* lightPositions[10],             raymarcher.frag:37-39 */
@@ -583,6 +583,40 @@ RM_API int rm_pack_present_rows(rm_ctx* ctx, rm_fb* fb, void* out_float4_device,
  * travels to the GPU that shows the frame.  Asynchronous on hip_stream (NULL = the context's stream). */
 RM_API int rm_present_striped_rows(rm_ctx* ctx, const void* color, const void* normal_dof, int width, int height, int samples, int stripe_rows, int parts, int part,
                             void* out_rgba8_device, void* hip_stream);
+
+/* ---- denoise (opt-in): the edge-avoiding a-trous wavelet filter of Dammertz et al. 2010, guided by the G-buffer ----
+ * The filter display.frag:27-42 sketches, on the three planes after `samples` (= k) samples; INTEGRATION.md "Denoising"
+ * states it in full.  With s = 1.0f / k, per pixel p: modulation m_p = max(albedo.xyz s, 1e-3) per channel, demodulated
+ * colour x_p = colour.rgb s / m_p, normal n_p = normalize(normal.xyz s) (the zero vector when the length is < 1e-6 or
+ * not finite: sky), depth z_p = albedo_depth.w s.  Pass i = 0 .. iterations-1 (step h = 2^i) averages the taps
+ * q = p + h (dx, dy), dx, dy in -2..2 (a tap outside the image is skipped, no wrap), with weights
+ *   b[dx] b[dy] exp(-|x_p - x_q|^2 / (sigma_color^2 4^-i)) exp(-|n_p - n_q|^2 / sigma_normal^2) w_z,  b = (1,4,6,4,1)/16,
+ *   w_z = 1 at the centre or when both depths are non-finite, 0 when exactly one is, else
+ *         exp(-|z_p - z_q| / (sigma_depth max(z_p, 1e-6) h sqrt(dx^2 + dy^2)));
+ * a tap whose x_q is not finite weighs 0 and a pixel whose x_p is not finite keeps it.  Only x changes between passes.
+ * The result is in colour-plane units: (x m_p k, colour.w); iterations = 0 is an exact copy of the colour plane.
+ * The planes of an RM_GBUFFER_F16 framebuffer are widened exactly.  A NULL RmDenoise* means rm_denoise_default.
+ * RM_ERR_INVALID before any device work for a windowed or striped framebuffer (the filter reads neighbouring rows), a
+ * framebuffer of another context or without G-buffer planes, samples < 1, iterations outside 0..8, or a sigma that is
+ * <= 0 or not finite.  The passes run in buffers the context owns (grown on demand, freed with it): one denoise at a
+ * time per context. */
+typedef struct RmDenoise {
+  int iterations;       /* passes L, 0..8 (default 5) */
+  float sigma_color;    /* of the demodulated colour, halved every pass (default 2.5) */
+  float sigma_normal;   /* default 2.0 */
+  float sigma_depth;    /* relative to the centre's depth (default 0.2) */
+  int reserved;         /* 0 */
+} RmDenoise;
+RM_API void rm_denoise_default(RmDenoise* params);
+/* out_host = rm_fb_rows(fb) x width x 4 floats of HOST memory, colour-plane units, row 0 = bottom; waits for the result. */
+RM_API int rm_denoise(rm_ctx* ctx, rm_fb* fb, int samples, const RmDenoise* params, float* out_host);
+/* The same left on the device: out_float4_device = rm_fb_rows(fb) x width float4 of DEVICE memory (16-byte aligned),
+ * enqueued on hip_stream (NULL = the context's stream); no host wait. */
+RM_API int rm_denoise_device(rm_ctx* ctx, rm_fb* fb, int samples, const RmDenoise* params, void* out_float4_device, void* hip_stream);
+/* The denoised colour through exactly rm_present's pass (display.frag, the GL stack's arithmetic under rm_ctx_set_gl_stack,
+ * the framebuffer's own normal + DoF plane): the bytes rm_present gives for a framebuffer whose colour plane holds
+ * rm_denoise's result.  out_rgba8 = height x width x 4 bytes of HOST memory, row 0 = bottom. */
+RM_API int rm_present_denoised(rm_ctx* ctx, rm_fb* fb, int samples, const RmDenoise* params, uint8_t* out_rgba8);
 
 /* The present of a frame that ONE process renders on several GPUs -- the shape of the reference's own host: one
  * thread, one render loop (index.tsx:120), here with a context per GPU, each holding one part of the frame's stripes

@@ -112,4 +112,18 @@ class RmRect(C.Structure):
     _fields_ = [("x", C.c_int32), ("y", C.c_int32), ("w", C.c_int32), ("h", C.c_int32)]
 
 
+class RmDenoise(C.Structure):
+    """Parameters of rm_denoise* (ABI 9): the G-buffer-guided a-trous filter (include/hip_raymarch.h)."""
+    _fields_ = [
+        ("iterations", C.c_int32),
+        ("sigma_color", C.c_float),
+        ("sigma_normal", C.c_float),
+        ("sigma_depth", C.c_float),
+        ("reserved", C.c_int32),
+    ]
+
+
+DENOISE_DEFAULTS = dict(iterations=5, sigma_color=2.5, sigma_normal=2.0, sigma_depth=0.2)  # rm_denoise_default
+
+
 assert C.sizeof(RmPrim) == 32 and C.sizeof(RmSurface) == 48

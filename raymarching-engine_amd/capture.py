@@ -61,7 +61,9 @@ def to_data_url(rgba8: np.ndarray) -> str:
     return "data:image/png;base64," + base64.b64encode(encode_png(rgba8)).decode("ascii")
 
 
-def save_png(framebuffer, samples: int, path: str) -> None:
-    """Present `framebuffer` (rm_present: DoF blur, 1/samples, gamma) and write it as a PNG."""
+def save_png(framebuffer, samples: int, path: str, denoise=None) -> None:
+    """Present `framebuffer` (rm_present: DoF blur, 1/samples, gamma) and write it as a PNG.  `denoise` (True, a dict or
+    abi.RmDenoise) presents the denoised colour instead (rm_present_denoised); None keeps the bytes of rm_present."""
+    rgba8 = framebuffer.present(samples) if denoise is None else framebuffer.present(samples, denoise=denoise)
     with open(path, "wb") as f:
-        f.write(encode_png(framebuffer.present(samples)))
+        f.write(encode_png(rgba8))

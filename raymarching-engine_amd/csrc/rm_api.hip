@@ -105,6 +105,8 @@ struct rm_ctx {
   std::unordered_map<void*, size_t> buffers;  // rm_buffer_create: base address -> bytes
   uchar4* present_buf = nullptr;   // device staging of rm_present / rm_present_planes, grown on demand
   size_t present_cap = 0;          // pixels
+  float4* denoise_buf[3] = {nullptr, nullptr, nullptr};  // rm_denoise*: the two ping-pong buffers of x and the guide, grown on demand
+  size_t denoise_cap = 0;          // pixels
   // rm_present_sharded (one process driving several GPUs): this context's rows of the payload, and on the context that
   // shows the frame the gathered parts and the frame in image order; grown on demand, freed with the context
   void* shard_rows = nullptr;  size_t shard_rows_cap = 0;    // this context's rows of the payload (packed float4 or RGBA8)
@@ -279,6 +281,8 @@ void rm_ctx_destroy(rm_ctx* ctx) {
     if (ctx->sp_stage[s]) (void)hipFree(ctx->sp_stage[s]);
   }
   if (ctx->present_buf) (void)hipFree(ctx->present_buf);
+  for (auto* b : ctx->denoise_buf)
+    if (b) (void)hipFree(b);
   if (ctx->shard_rows) (void)hipFree(ctx->shard_rows);
   if (ctx->shard_recv) (void)hipFree(ctx->shard_recv);
   if (ctx->shard_frame) (void)hipFree(ctx->shard_frame);
@@ -1784,6 +1788,108 @@ int rm_present(rm_ctx* ctx, rm_fb* fb, int samples, uint8_t* out_rgba8) {
   if (fb->stripe_rows > 0 || fb->row_begin != 0 || fb->row_count != fb->height)
     return fail(ctx, RM_ERR_INVALID, "rm_present: the blur reads neighbouring rows, so it needs the whole frame: gather the planes and use rm_present_planes (or rm_present_rows when depth of field is off)");
   return present_planes(ctx, fb->plane[0], fb->plane[1], fb->gbuffer == RM_GBUFFER_F16, fb->width, fb->height, samples, out_rgba8);
+}
+
+// ---- denoise (rm_frame_kernels.inc "denoise") ---------------------------------------------------------
+
+void rm_denoise_default(RmDenoise* p) {
+  if (!p) return;
+  std::memset(p, 0, sizeof *p);
+  p->iterations = 5;
+  p->sigma_color = 2.5f;
+  p->sigma_normal = 2.0f;
+  p->sigma_depth = 0.2f;
+}
+
+// Every check of the denoise entry points, before any device work.
+static int denoise_check(rm_ctx* ctx, rm_fb* fb, int samples, const RmDenoise* params, const char* who) {
+  if (!ctx || !fb) return fail(ctx, RM_ERR_INVALID, std::string(who) + ": NULL argument");
+  if (fb->ctx != ctx) return fail(ctx, RM_ERR_INVALID, std::string(who) + ": framebuffer belongs to another context");
+  if (fb->stripe_rows > 0 || fb->row_begin != 0 || fb->row_count != fb->height)
+    return fail(ctx, RM_ERR_INVALID, std::string(who) + ": the filter reads neighbouring rows, so it needs a framebuffer holding the whole frame");
+  if (!fb->plane[1] || !fb->plane[2]) return fail(ctx, RM_ERR_INVALID, std::string(who) + ": the framebuffer has no G-buffer planes to guide the filter");
+  if (samples < 1) return fail(ctx, RM_ERR_INVALID, std::string(who) + ": samples must be >= 1");
+  if (params) {
+    if (params->iterations < 0 || params->iterations > 8) return fail(ctx, RM_ERR_INVALID, std::string(who) + ": iterations must be in 0..8");
+    const float sg[3] = {params->sigma_color, params->sigma_normal, params->sigma_depth};
+    for (float v : sg)
+      if (!(v > 0.0f && std::isfinite(v))) return fail(ctx, RM_ERR_INVALID, std::string(who) + ": every sigma must be finite and > 0");
+  }
+  return RM_OK;
+}
+
+// Enqueues the passes on `stream`.  out: the result, or NULL for one of the context's buffers; *result = where it is (the
+// colour plane itself for 0 iterations and no `out`).
+static int denoise_enqueue(rm_ctx* ctx, rm_fb* fb, int samples, const RmDenoise* params, float4* out, hipStream_t stream, const float4** result) {
+  RmDenoise d;
+  if (params) d = *params;
+  else rm_denoise_default(&d);
+  RM_HIP(ctx, hipSetDevice(ctx->device));
+  const size_t pixels = (size_t)fb->width * (size_t)fb->height;
+  const int L = d.iterations;
+  if (L == 0) {
+    if (out) RM_HIP(ctx, hipMemcpyAsync(out, fb->plane[0], pixels * sizeof(float4), hipMemcpyDeviceToDevice, stream));
+    *result = out ? out : fb->plane[0];
+    return RM_OK;
+  }
+  if (ctx->denoise_cap < pixels) {  // a live loop denoises every present: the buffers stay with the context
+    RM_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    RM_HIP(ctx, hipStreamSynchronize(stream));
+    for (auto*& b : ctx->denoise_buf) {
+      if (b) (void)hipFree(b);
+      b = nullptr;
+    }
+    ctx->denoise_cap = 0;
+    for (auto*& b : ctx->denoise_buf) RM_HIP(ctx, hipMalloc(reinterpret_cast<void**>(&b), pixels * sizeof(float4)));
+    ctx->denoise_cap = pixels;
+  }
+  DenoisePass P{};
+  P.color = fb->plane[0];
+  P.normal_dof = fb->plane[1];
+  P.albedo_depth = fb->plane[2];
+  P.guide = ctx->denoise_buf[2];
+  P.W = fb->width;
+  P.H = fb->height;
+  P.s = 1.0f / (float)samples;  // present_device's scale
+  P.k = (float)samples;
+  P.inv_normal = 1.0f / (d.sigma_normal * d.sigma_normal);
+  const bool half = fb->gbuffer == RM_GBUFFER_F16;
+  for (int i = 0; i < L; i++) {
+    P.step = 1 << i;
+    P.inv_color = (float)(1 << (2 * i)) / (d.sigma_color * d.sigma_color);  // sigma_c^2 4^-i
+    P.sigma_z_h = d.sigma_depth * (float)P.step;
+    P.x_in = i > 0 ? ctx->denoise_buf[(i - 1) % 2] : nullptr;
+    P.out = (i == L - 1 && out) ? out : ctx->denoise_buf[i % 2];
+    RM_HIP(ctx, rm::launch_denoise_pass(P, half, i == 0, i == L - 1, stream));
+  }
+  *result = P.out;
+  return RM_OK;
+}
+
+int rm_denoise_device(rm_ctx* ctx, rm_fb* fb, int samples, const RmDenoise* params, void* out_float4_device, void* hip_stream) {
+  if (int rc = denoise_check(ctx, fb, samples, params, "rm_denoise_device")) return rc;
+  if (!out_float4_device || (reinterpret_cast<uintptr_t>(out_float4_device) & 15u))
+    return fail(ctx, RM_ERR_INVALID, "rm_denoise_device: the output must be a 16-byte aligned device buffer");
+  const float4* r = nullptr;
+  return denoise_enqueue(ctx, fb, samples, params, static_cast<float4*>(out_float4_device), hip_stream ? static_cast<hipStream_t>(hip_stream) : ctx->stream, &r);
+}
+
+int rm_denoise(rm_ctx* ctx, rm_fb* fb, int samples, const RmDenoise* params, float* out_host) {
+  if (int rc = denoise_check(ctx, fb, samples, params, "rm_denoise")) return rc;
+  if (!out_host) return fail(ctx, RM_ERR_INVALID, "rm_denoise: NULL argument");
+  const float4* r = nullptr;
+  if (int rc = denoise_enqueue(ctx, fb, samples, params, nullptr, ctx->stream, &r)) return rc;
+  RM_HIP(ctx, hipMemcpyAsync(out_host, r, (size_t)fb->width * (size_t)fb->height * sizeof(float4), hipMemcpyDeviceToHost, ctx->stream));
+  RM_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return RM_OK;
+}
+
+int rm_present_denoised(rm_ctx* ctx, rm_fb* fb, int samples, const RmDenoise* params, uint8_t* out_rgba8) {
+  if (int rc = denoise_check(ctx, fb, samples, params, "rm_present_denoised")) return rc;
+  if (!out_rgba8) return fail(ctx, RM_ERR_INVALID, "rm_present_denoised: NULL argument");
+  const float4* r = nullptr;
+  if (int rc = denoise_enqueue(ctx, fb, samples, params, nullptr, ctx->stream, &r)) return rc;
+  return present_planes(ctx, r, fb->plane[1], fb->gbuffer == RM_GBUFFER_F16, fb->width, fb->height, samples, out_rgba8);
 }
 
 // ---- present of a frame sharded over the GPUs of ONE process ----------------------------------------

@@ -277,4 +277,147 @@ hipError_t launch_convert(const void* src, void* dst, long long pixels, bool nar
 }
 #endif
 
+#if !RM_BUILD_FAST && !RM_GL_STACK
+// ---- denoise: edge-avoiding a-trous wavelet filter guided by the G-buffer (Dammertz et al. 2010) --------------------
+// The filter display.frag:27-42 asks for ("How do I account for normals with denoising? ... i might focus more on depth
+// now"), run on the planes after k samples; INTEGRATION.md "Denoising" states it in full, tests/denoise_ref.py restates it
+// in float64.  With s = 1 / k (present_device's scale), per pixel p:
+//   m_p = max(A.xyz s, 1e-3)   x_p = C.rgb s / m_p   n_p = normalize(N.xyz s) (0 when |.| < 1e-6 or not finite)   z_p = A.w s
+// Pass i = 0 .. L-1, step h = 2^i, taps q = p + h (dx, dy), dx, dy in -2..2, taps outside the image skipped:
+//   w = b[dx] b[dy] exp(-|x_p - x_q|^2 / (sigma_c^2 4^-i)) exp(-|n_p - n_q|^2 / sigma_n^2) w_z,   b = (1, 4, 6, 4, 1) / 16
+//   w_z = 1 at the centre or when both depths are non-finite, 0 when one is, else
+//         exp(-|z_p - z_q| / (sigma_z max(z_p, 1e-6) h sqrt(dx^2 + dy^2)));  a tap with a non-finite x_q weighs 0
+//   x'_p = sum w x_q / sum w   (a non-finite x_p keeps its value);  the guides n, z stay those of the input.
+// Output: (x_L m_p k, C.w).  One launch per pass, 16 x 16 pixels per workgroup, one thread per pixel.  Pass 0 computes x and
+// the guide (n.xyz, z) of the pixels it reads from the planes and writes each pixel's guide once; the last pass multiplies
+// the modulation back.  Steps 1 and 2 stage the tile and its halo of 2h pixels in LDS (20^2 or 24^2 pixels x 32 B); wider
+// steps read x and the guide through the caches.  No pixel kernel is touched.
+template <class GB>
+__device__ inline float4 dn_load(const void* plane, size_t i);
+template <>
+__device__ inline float4 dn_load<float4>(const void* plane, size_t i) { return static_cast<const float4*>(plane)[i]; }
+template <>
+__device__ inline float4 dn_load<rm_half4>(const void* plane, size_t i) { return rm_widen(static_cast<const rm_half4*>(plane)[i]); }
+
+__device__ inline float3 dn_modulation(const float4 a, float s) { return make_float3(fmaxf(a.x * s, 1e-3f), fmaxf(a.y * s, 1e-3f), fmaxf(a.z * s, 1e-3f)); }
+__device__ inline bool dn_finite3(const float4 v) { return isfinite(v.x) && isfinite(v.y) && isfinite(v.z); }
+__device__ inline float dn_scaled(float d, float inv) { return d > 0.0f ? d * inv : 0.0f; }  // d * inv, and 0 for d = 0 even when inv = inf
+
+// x (demodulated colour, .w unused) and guide (n.xyz, z) of pixel i, from the planes
+template <class GB>
+__device__ inline void dn_prepare(const DenoisePass& P, size_t i, float4& x, float4& g) {
+  const float4 c = P.color[i], a = dn_load<GB>(P.albedo_depth, i), n = dn_load<GB>(P.normal_dof, i);
+  const float3 m = dn_modulation(a, P.s);
+  x = make_float4(c.x * P.s / m.x, c.y * P.s / m.y, c.z * P.s / m.z, 0.0f);
+  const float nx = n.x * P.s, ny = n.y * P.s, nz = n.z * P.s;
+  const float len = sqrtf(nx * nx + ny * ny + nz * nz);
+  g = (len >= 1e-6f && isfinite(len)) ? make_float4(nx / len, ny / len, nz / len, a.w * P.s) : make_float4(0.0f, 0.0f, 0.0f, a.w * P.s);
+}
+
+// STAGE: the step h of a pass staged in LDS (1 or 2), 0 for a pass that reads through the caches.  PREP: pass 0 (reads the
+// planes).  LAST: the last pass (writes colour-plane units).  GB: float4, or rm_half4 for the planes of a half G-buffer.
+template <int STAGE, bool PREP, bool LAST, class GB>
+__global__ __launch_bounds__(256) void rm_denoise_kernel(const DenoisePass P) {
+  constexpr int HALO = 2 * STAGE, SPAN = 16 + 2 * HALO;
+  __shared__ float4 sx[STAGE > 0 ? SPAN * SPAN : 1], sg[STAGE > 0 ? SPAN * SPAN : 1];
+  const int lx = threadIdx.x % 16, ly = threadIdx.x / 16;
+  const int x = blockIdx.x * 16 + lx, y = blockIdx.y * 16 + ly;
+  const int h = P.step;
+  if (STAGE > 0) {
+    const int x0 = (int)blockIdx.x * 16 - HALO, y0 = (int)blockIdx.y * 16 - HALO;
+    for (int i = threadIdx.x; i < SPAN * SPAN; i += 256) {
+      const int gx = x0 + i % SPAN, gy = y0 + i / SPAN;
+      if (gx < 0 || gx >= P.W || gy < 0 || gy >= P.H) continue;  // never read: a tap outside the image is skipped
+      const size_t q = (size_t)gy * P.W + gx;
+      if (PREP) dn_prepare<GB>(P, q, sx[i], sg[i]);
+      else { sx[i] = P.x_in[q]; sg[i] = P.guide[q]; }
+    }
+    __syncthreads();
+  }
+  if (x >= P.W || y >= P.H) return;
+  const size_t p = (size_t)y * P.W + x;
+  float4 xp, gp;
+  if (STAGE > 0) {
+    const int c = (ly + HALO) * SPAN + lx + HALO;
+    xp = sx[c];
+    gp = sg[c];
+  } else if (PREP) {
+    dn_prepare<GB>(P, p, xp, gp);
+  } else {
+    xp = P.x_in[p];
+    gp = P.guide[p];
+  }
+  if (PREP) P.guide[p] = gp;
+  float4 r = xp;
+  if (dn_finite3(xp)) {
+    constexpr float b[5] = {1.0f / 16.0f, 1.0f / 4.0f, 3.0f / 8.0f, 1.0f / 4.0f, 1.0f / 16.0f};
+    const float zp = gp.w;
+    const bool zp_finite = isfinite(zp);
+    const float inv_z = 1.0f / (P.sigma_z_h * fmaxf(zp, 1e-6f));
+    float ax = 0.0f, ay = 0.0f, az = 0.0f, wsum = 0.0f;
+#pragma unroll
+    for (int dy = -2; dy <= 2; dy++) {
+      const int qy = y + dy * h;
+      if (qy < 0 || qy >= P.H) continue;
+#pragma unroll
+      for (int dx = -2; dx <= 2; dx++) {
+        const int qx = x + dx * h;
+        if (qx < 0 || qx >= P.W) continue;
+        float4 xq, gq;
+        if (STAGE > 0) {
+          const int t = (ly + HALO + dy * STAGE) * SPAN + lx + HALO + dx * STAGE;
+          xq = sx[t];
+          gq = sg[t];
+        } else {
+          const size_t q = (size_t)qy * P.W + qx;
+          xq = P.x_in[q];
+          gq = P.guide[q];
+        }
+        if (!dn_finite3(xq)) continue;
+        const float cx = xp.x - xq.x, cy = xp.y - xq.y, cz = xp.z - xq.z;
+        const float nx = gp.x - gq.x, ny = gp.y - gq.y, nz = gp.z - gq.z;
+        float e = dn_scaled(cx * cx + cy * cy + cz * cz, P.inv_color) + dn_scaled(nx * nx + ny * ny + nz * nz, P.inv_normal);
+        if (dx != 0 || dy != 0) {
+          const bool zq_finite = isfinite(gq.w);
+          if (zq_finite != zp_finite) continue;
+          if (zp_finite) e += dn_scaled(fabsf(zp - gq.w), inv_z * (1.0f / sqrtf((float)(dx * dx + dy * dy))));
+        }
+        const float w = b[dx + 2] * b[dy + 2] * expf(-e);
+        ax += w * xq.x;
+        ay += w * xq.y;
+        az += w * xq.z;
+        wsum += w;
+      }
+    }
+    r = make_float4(ax / wsum, ay / wsum, az / wsum, 0.0f);  // wsum >= b[2]^2: the centre tap weighs (3/8)^2
+  }
+  if (LAST) {
+    const float3 m = dn_modulation(dn_load<GB>(P.albedo_depth, p), P.s);
+    r = make_float4(r.x * m.x * P.k, r.y * m.y * P.k, r.z * m.z * P.k, P.color[p].w);
+  }
+  P.out[p] = r;
+}
+
+hipError_t launch_denoise_pass(const DenoisePass& P, bool half, bool prep, bool last, hipStream_t stream) {
+  const dim3 grid((P.W + 15) / 16, (P.H + 15) / 16);
+#define RM_DENOISE(STAGE, PREP, GB)                                                                                    \
+  do {                                                                                                                 \
+    if (last) hipLaunchKernelGGL((rm_denoise_kernel<STAGE, PREP, true, GB>), grid, dim3(256), 0, stream, P);          \
+    else hipLaunchKernelGGL((rm_denoise_kernel<STAGE, PREP, false, GB>), grid, dim3(256), 0, stream, P);              \
+  } while (0)
+  if (prep) {  // pass 0: h = 1
+    if (half) RM_DENOISE(1, true, rm_half4);
+    else RM_DENOISE(1, true, float4);
+  } else if (P.step == 2) {
+    if (half) RM_DENOISE(2, false, rm_half4);
+    else RM_DENOISE(2, false, float4);
+  } else {
+    if (half) RM_DENOISE(0, false, rm_half4);
+    else RM_DENOISE(0, false, float4);
+  }
+#undef RM_DENOISE
+  return hipGetLastError();
+}
+#endif
+
 }  // namespace rm

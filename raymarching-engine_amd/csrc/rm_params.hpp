@@ -290,6 +290,20 @@ struct ProbeParams {
 };
 // (the probe follows RM_RENDER_NO_CULL through scene.cull.cells, which rm_probe clears)
 
+// One pass of the denoiser (rm_frame_kernels.inc "denoise").  Pass 0 reads color / normal_dof / albedo_depth and writes
+// guide; later passes read x_in and guide; the last pass reads color (.w) and albedo_depth (the modulation) again.
+struct DenoisePass {
+  const float4* color;
+  const void* normal_dof;    // float4 or rm_half4 planes
+  const void* albedo_depth;
+  const float4* x_in;        // the previous pass's demodulated colour (.w unused)
+  float4* guide;             // (n.xyz, z) per pixel
+  float4* out;               // demodulated colour, or on the last pass the result in colour-plane units
+  int W, H, step;            // step h = 2^pass
+  float s, k;                // 1 / samples, samples
+  float inv_color, inv_normal, sigma_z_h;  // 1 / (sigma_c^2 4^-pass), 1 / sigma_n^2, sigma_z h
+};
+
 namespace rm {
 enum {
   WF_POS = 0,   // xyz ray position (march in/out), w = step budget
@@ -346,6 +360,8 @@ hipError_t launch_pack_rows(const float4* color, const void* normal_dof, bool nd
 // one plane between fp32 and half (rm_fb_upload / rm_fb_download of a half plane): narrow = fp32 -> half with rm_narrow, else rm_widen
 hipError_t launch_convert(const void* src, void* dst, long long pixels, bool narrow, hipStream_t stream);
 hipError_t launch_present_rows(const float4* color, long long pixels, float brightness, uchar4* out, hipStream_t stream);
+// one pass of rm_denoise (rm_frame_kernels.inc "denoise"); half: the G-buffer planes hold rm_half4
+hipError_t launch_denoise_pass(const DenoisePass& P, bool half, bool prep, bool last, hipStream_t stream);
 hipError_t launch_present(const float4* color, const void* normal_dof, bool nd_half, int W, int H, float brightness, uchar4* out, hipStream_t stream);
 hipError_t launch_present_striped(const float4* color, const float4* normal_dof, int W, int H, float brightness, uchar4* out, int stripe_rows, int parts, int part,
                                   int local_rows, hipStream_t stream);

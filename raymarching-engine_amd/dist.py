@@ -346,7 +346,10 @@ class ShardedFramebuffer:
         canvas = g8.finish()
         return canvas if gr.rank == g8.dst else None
 
-    def present(self, samples: int, dof: Optional[bool] = None):
+    def present(self, samples: int, dof: Optional[bool] = None, denoise=None):
+        if denoise is not None:  # checked before any collective: every rank raises, none waits for the others
+            raise ValueError("ShardedFramebuffer.present: denoising a sharded frame is not supported (the filter reads rows other "
+                             "ranks hold); present it unsharded with Framebuffer.present(samples, denoise=...)")
         self.start_present(samples, dof)
         canvas = self.finish_present()
         if canvas is None:

@@ -50,11 +50,17 @@ export type RenderJobSchema = {
 };
 export type RenderJobFramebufferInfo = {
   width: number; height: number; frameid: number; download(plane?: 0 | 1 | 2): Float32Array;
-  /** display.frag on the GPU: RGBA8, row 0 = bottom */
-  present(samples: number): Uint8Array;
+  /** display.frag on the GPU: RGBA8, row 0 = bottom; `denoise` presents the denoised colour (rm_present_denoised) */
+  present(samples: number, opts?: { denoise?: true | DenoiseParams }): Uint8Array;
+  /** the colour plane after the G-buffer-guided a-trous filter (rm_denoise): colour-plane units, row 0 = bottom */
+  denoise(samples: number, params?: true | DenoiseParams): Float32Array;
   /** canvas.toDataURL("image/png") of the presented frame (index.tsx:470-476) */
-  toDataURL(samples: number): string;
+  toDataURL(samples: number, opts?: { denoise?: true | DenoiseParams }): string;
 };
+/** RmDenoise (include/hip_raymarch.h): fields left out take DENOISE_DEFAULTS' values */
+export type DenoiseParams = { iterations?: number; sigma_color?: number; sigma_normal?: number; sigma_depth?: number };
+export const DENOISE_DEFAULTS: Required<DenoiseParams>;
+export function denoiseParams(params?: true | DenoiseParams | null): Required<DenoiseParams>;
 export type ShaderError = { type: "vertex" | "fragment" | "program"; infoLog: string };
 /** The G-buffer format of a context's framebuffers: "f32" (default) or "f16", the reference's RGBA16F normal + DoF radius and
  *  albedo + depth planes (accumulated in half precision; the colour plane stays fp32). */
@@ -71,7 +77,8 @@ export class RenderJobContext {
  *  8-row stripes; `present(samples)` of its framebuffer set assembles the canvas on the first GPU (rm_present_sharded). */
 export type ShardedFramebufferInfo = {
   width: number; height: number; frameid: number; sharded: true; dof: boolean; rows(): number[];
-  present(samples: number, dof?: boolean): Uint8Array; toDataURL(samples: number): string;
+  /** throws when asked to denoise: the filter reads rows other GPUs hold */
+  present(samples: number, dof?: boolean, opts?: { denoise?: undefined }): Uint8Array; toDataURL(samples: number): string;
   /** the present in two halves (rm_present_sharded_start / _finish): the frame travels while the next samples render; one at a time */
   startPresent(samples: number, dof?: boolean): void; finishPresent(): Uint8Array; pendingPresent: boolean;
 };

@@ -287,9 +287,16 @@ class RenderJobContext {  // RenderJobContext + loadRenderJobContext (LoadRender
     else fb = addon.fbCreate(this.ctx, w, h, 0, h, this.gbufferCode);
     const info = { fb, width: w, height: h, frameid, download: (plane = 0) => { const out = new Float32Array(w * h * 4); addon.fbDownload(this.ctx, fb, plane, out); return out; },
                    // the present pass (display.frag) on the GPU: RGBA8, row 0 = bottom
-                   present: (samples) => { const out = new Uint8Array(w * h * 4); addon.present(this.ctx, fb, samples, out); return out; },
+                   // opts.denoise (true or the parameters of denoiseParams): the denoised colour through the same pass (rm_present_denoised)
+                   present: (samples, opts = {}) => {
+                     const out = new Uint8Array(w * h * 4);
+                     if (opts.denoise === undefined || opts.denoise === null || opts.denoise === false) addon.present(this.ctx, fb, samples, out);
+                     else addon.presentDenoised(this.ctx, fb, samples, denoiseParams(opts.denoise), out);
+                     return out; },
+                   // the colour plane after the G-buffer-guided a-trous filter (rm_denoise): Float32Array, colour-plane units, row 0 = bottom
+                   denoise: (samples, params) => { const out = new Float32Array(w * h * 4); addon.denoise(this.ctx, fb, samples, denoiseParams(params), out); return out; },
                    // canvas.toDataURL("image/png"), index.tsx:470-476
-                   toDataURL: (samples) => "data:image/png;base64," + encodePng(info.present(samples), w, h).toString("base64") };
+                   toDataURL: (samples, opts = {}) => "data:image/png;base64," + encodePng(info.present(samples, opts), w, h).toString("base64") };
     this.live.set(key, info);
     return info;
   }
@@ -352,7 +359,10 @@ class ShardedRenderJobContext {
     const info = { fbs, width: w, height: h, frameid, sharded: true, dof: false,
                    rows: () => fbs.map((fb) => addon.fbRows(fb)),
                    // the canvas of the assembled frame (display.frag, with its blur when the job has depth of field): RGBA8, row 0 = bottom
-                   present: (samples, dof = info.dof) => { const out = new Uint8Array(w * h * 4); addon.presentSharded(this.ctxs, fbs, samples, !!dof, out); return out; },
+                   present: (samples, dof = info.dof, opts = {}) => {
+                     if (opts.denoise !== undefined || (dof !== null && typeof dof === "object"))
+                       throw new Error("present: denoising a sharded frame is not supported (the filter reads rows other GPUs hold)");
+                     const out = new Uint8Array(w * h * 4); addon.presentSharded(this.ctxs, fbs, samples, !!dof, out); return out; },
                    // the same in two halves (rm_present_sharded_start / _finish): startPresent snapshots and sends and returns at once, so a
                    // `present` callback that calls it lets doRenderJob hand out the next samples while the frame travels; finishPresent
                    // (at the next callback, or whenever the canvas is wanted) returns the canvas of THAT present.  One at a time.
@@ -434,6 +444,24 @@ async function doRenderJob(schema, context) {  // RenderJobExecutor.tsx:77
   };
 }
 
+// ---- denoise parameters (include/hip_raymarch.h RmDenoise, rm_denoise_default) ----
+const DENOISE_DEFAULTS = { iterations: 5, sigma_color: 2.5, sigma_normal: 2.0, sigma_depth: 0.2 };
+// true / undefined / null = the defaults, or an object with some of DENOISE_DEFAULTS' fields; checked as the library checks them
+function denoiseParams(params) {
+  const p = { ...DENOISE_DEFAULTS };
+  if (params !== undefined && params !== null && params !== true) {
+    if (typeof params !== "object") throw new TypeError("denoise: expected true or an object of parameters");
+    for (const [k, v] of Object.entries(params)) {
+      if (!(k in DENOISE_DEFAULTS)) throw new TypeError("denoise: unknown parameter " + k);
+      p[k] = v;
+    }
+  }
+  if (!Number.isInteger(p.iterations) || p.iterations < 0 || p.iterations > 8) throw new RangeError("denoise: iterations must be an integer in 0..8");
+  for (const k of ["sigma_color", "sigma_normal", "sigma_depth"])
+    if (!(typeof p[k] === "number" && Number.isFinite(p[k]) && p[k] > 0)) throw new RangeError("denoise: " + k + " must be finite and > 0");
+  return p;
+}
+
 // ---- PNG capture (index.tsx:470-476 canvas.toDataURL): RGBA8, filter 0, rows flipped to top-down ----
 const zlib = require("zlib");
 const CRC_TABLE = (() => { const t = new Uint32Array(256); for (let n = 0; n < 256; n++) { let c = n; for (let k = 0; k < 8; k++) c = c & 1 ? 0xedb88320 ^ (c >>> 1) : c >>> 1; t[n] = c >>> 0; } return t; })();
@@ -458,4 +486,4 @@ function encodePng(rgba, width, height, bottomUp = true) {
 }
 
 module.exports = { RM, addon, encodePng, Scene, CsgScene, Mandelbulb, singleSphere, DEFAULT_MATERIAL, halton, resetHalton, uniformsFromSchema, packUniforms,
-                   tileRect, RenderJobContext, ShardedRenderJobContext, doRenderJob, U_OFFSET };
+                   tileRect, RenderJobContext, ShardedRenderJobContext, doRenderJob, U_OFFSET, DENOISE_DEFAULTS, denoiseParams };

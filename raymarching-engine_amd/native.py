@@ -6,6 +6,7 @@ raises: there is no Python or CPU fallback for rendering.
 from __future__ import annotations
 
 import ctypes as C
+import math
 from pathlib import Path
 from typing import Optional
 
@@ -34,6 +35,7 @@ EXPORTS = [
     "rm_fb_download", "rm_fb_upload", "rm_fb_device_ptr", "rm_buffer_create", "rm_buffer_destroy", "rm_buffer_download", "rm_buffer_upload", "rm_render_sample", "rm_render_samples", "rm_ctx_set_sample_batch", "rm_ctx_set_gl_stack", "rm_render_timed",
     "rm_probe", "rm_probe_camera", "rm_probe_rng", "rm_probe_math", "rm_assemble_striped", "rm_assemble_striped_bytes", "rm_present", "rm_present_planes", "rm_present_device", "rm_present_rows", "rm_pack_present_rows", "rm_ctx_last_pipeline", "rm_present_sharded", "rm_present_sharded_start", "rm_present_sharded_finish", "rm_present_striped_rows", "rm_debug_cull_cell",
     "rm_fb_create_fmt", "rm_fb_create_striped_fmt", "rm_fb_wrap_fmt", "rm_fb_gbuffer", "rm_fb_download_raw", "rm_fb_upload_raw",
+    "rm_denoise_default", "rm_denoise", "rm_denoise_device", "rm_present_denoised",
 ]
 
 # G-buffer formats of a framebuffer (include/hip_raymarch.h RM_GBUFFER_*): "f32" (the default: the software GL stack's planes, which the
@@ -46,6 +48,31 @@ def gbuffer_code(gbuffer: str) -> int:
     if not isinstance(gbuffer, str) or gbuffer not in GBUFFER_FORMATS:
         raise ValueError(f"gbuffer must be one of {sorted(GBUFFER_FORMATS)}, not {gbuffer!r}")
     return GBUFFER_FORMATS[gbuffer]
+
+
+def denoise_params(params=None) -> abi.RmDenoise:
+    """An abi.RmDenoise from None / True (the defaults, rm_denoise_default), a dict of some of its fields over the defaults, or an
+    abi.RmDenoise.  Checked here as the library checks it (iterations in 0..8, every sigma finite and > 0): ValueError otherwise."""
+    if isinstance(params, abi.RmDenoise):
+        p = params
+    else:
+        if params is None or params is True:
+            fields = {}
+        elif isinstance(params, dict):
+            fields = dict(params)
+        else:
+            raise ValueError(f"denoise: expected True, a dict or abi.RmDenoise, got {params!r}")
+        unknown = set(fields) - set(abi.DENOISE_DEFAULTS)
+        if unknown:
+            raise ValueError(f"denoise: unknown parameter(s) {sorted(unknown)}; known: {sorted(abi.DENOISE_DEFAULTS)}")
+        p = abi.RmDenoise(**{**abi.DENOISE_DEFAULTS, **fields})
+    if not 0 <= p.iterations <= 8:
+        raise ValueError("denoise: iterations must be in 0..8")
+    for name in ("sigma_color", "sigma_normal", "sigma_depth"):
+        v = getattr(p, name)
+        if not (math.isfinite(v) and v > 0.0):
+            raise ValueError(f"denoise: {name} must be finite and > 0")
+    return p
 
 
 def cull_cell(scene, centre, radius: float, margin: float = 0.0):
@@ -177,6 +204,10 @@ def load_library(path=None):
         "rm_present_striped_rows": (ip, [vp, vp, vp, ip, ip, ip, ip, ip, ip, vp, vp]),
         "rm_present": (ip, [vp, vp, ip, C.POINTER(C.c_uint8)]),
         "rm_present_planes": (ip, [vp, vp, vp, ip, ip, ip, C.POINTER(C.c_uint8)]),
+        "rm_denoise_default": (None, [C.POINTER(abi.RmDenoise)]),
+        "rm_denoise": (ip, [vp, vp, ip, C.POINTER(abi.RmDenoise), fp]),
+        "rm_denoise_device": (ip, [vp, vp, ip, C.POINTER(abi.RmDenoise), vp, vp]),
+        "rm_present_denoised": (ip, [vp, vp, ip, C.POINTER(abi.RmDenoise), C.POINTER(C.c_uint8)]),
     }
     for name, (res, args) in sig.items():
         if name.startswith("rm_debug_") and not hasattr(lib, name) and os.environ.get("RM_LIB"):
@@ -346,6 +377,12 @@ class Context:
         (that part's packed rows x width x 4 bytes), asynchronous: each rank's share of a sharded frame's blur."""
         self._check(self.lib.rm_present_striped_rows(self.h, C.c_void_p(color_ptr), C.c_void_p(normal_dof_ptr or 0), width, height, int(samples), stripe_rows,
                                                      parts, part, C.c_void_p(out_ptr), C.c_void_p(stream) if stream else None))
+
+    def denoise_device(self, fb: "Framebuffer", samples: int, out_ptr: int, params=None, stream: Optional[int] = None):
+        """rm_denoise_device: Framebuffer.denoise into rows x W float4 of device memory at out_ptr, enqueued on `stream` (None =
+        the context's); no host wait."""
+        p = denoise_params(params)
+        self._check(self.lib.rm_denoise_device(self.h, fb.h, int(samples), C.byref(p), C.c_void_p(out_ptr), C.c_void_p(stream) if stream else None))
 
     def present_rows(self, fb: "Framebuffer", samples: int, out_ptr: int, stream: Optional[int] = None):
         """Tone-map the rows `fb` holds (no depth of field) into DEVICE memory (rows*width*4 bytes), asynchronous."""
@@ -521,8 +558,21 @@ class Framebuffer:
     def device_ptr(self, plane: int = abi.RM_PLANE_COLOR) -> int:
         return int(self.ctx.lib.rm_fb_device_ptr(self.h, plane) or 0)
 
-    def present(self, samples: int) -> np.ndarray:
-        """Tone-mapped RGBA8 image of the whole frame (display.frag:16-64), row 0 = bottom."""
+    def present(self, samples: int, denoise=None) -> np.ndarray:
+        """Tone-mapped RGBA8 image of the whole frame (display.frag:16-64), row 0 = bottom.  `denoise`: None (the default: the
+        accumulated colour as it is), or True / a dict / abi.RmDenoise to present the denoised colour (rm_present_denoised)."""
         out = np.empty((self.row_count, self.width, 4), np.uint8)
-        self.ctx._check(self.ctx.lib.rm_present(self.ctx.h, self.h, int(samples), out.ctypes.data_as(C.POINTER(C.c_uint8))))
+        if denoise is None:
+            self.ctx._check(self.ctx.lib.rm_present(self.ctx.h, self.h, int(samples), out.ctypes.data_as(C.POINTER(C.c_uint8))))
+        else:
+            p = denoise_params(denoise)
+            self.ctx._check(self.ctx.lib.rm_present_denoised(self.ctx.h, self.h, int(samples), C.byref(p), out.ctypes.data_as(C.POINTER(C.c_uint8))))
+        return out
+
+    def denoise(self, samples: int, params=None) -> np.ndarray:
+        """The colour plane after the G-buffer-guided a-trous filter (rm_denoise): float32 [rows, W, 4] in colour-plane units,
+        row 0 = bottom.  `params`: None / True (the defaults), a dict of some RmDenoise fields, or abi.RmDenoise."""
+        p = denoise_params(params)
+        out = np.empty((self.row_count, self.width, 4), np.float32)
+        self.ctx._check(self.ctx.lib.rm_denoise(self.ctx.h, self.h, int(samples), C.byref(p), _fp(out)))
         return out
