@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define RM_ABI_VERSION 9 /* 9: RM_GBUFFER_F32 / _F16, rm_fb_create_fmt, rm_fb_create_striped_fmt, rm_fb_wrap_fmt, rm_fb_gbuffer, rm_fb_download_raw, rm_fb_upload_raw, RmDenoise, rm_denoise_default, rm_denoise, rm_denoise_device, rm_present_denoised (additions only); 8: RM_PRIM_TORUS / _CYLINDER / _PLANE, RM_OP_SMOOTH_SUBTRACT / _INTERSECT, rm_probe_math (additions only); 7: rm_present_sharded_finish / rm_present_sharded take the size of the host buffer (a changed signature), rm_ctx_set_cull_min_pixels, rm_ctx_set_cull_budget, rm_ctx_cull_stats; 6: rm_present_striped_rows, rm_present_sharded_start / _finish, rm_ctx_last_warning, RM_PROBE_CAST_SHADOW, RM_PRIM_KIND (additions only); 3: rm_ctx_set_sample_batch, rm_buffer_*; 4: rm_ctx_set_gl_stack; 5: RmSurface / RmSceneDesc.surfaces (the struct grew), rm_pack_present_rows, rm_present_sharded, rm_ctx_last_pipeline, RM_RENDER_NO_FAR_JUMP, RM_RENDER_NO_CULL (additions only) */
+#define RM_ABI_VERSION 9 /* 9: RM_GBUFFER_F32 / _F16, rm_fb_create_fmt, rm_fb_create_striped_fmt, rm_fb_wrap_fmt, rm_fb_gbuffer, rm_fb_download_raw, rm_fb_upload_raw, RmDenoise, rm_denoise_default, rm_denoise, rm_denoise_device, rm_present_denoised, RM_FB_MOMENTS, RM_PLANE_MOMENTS, rm_fb_has_moments, RmDenoiseVariance, rm_denoise_variance_default, rm_denoise_variance, rm_denoise_variance_device, rm_present_denoised_variance (additions only); 8: RM_PRIM_TORUS / _CYLINDER / _PLANE, RM_OP_SMOOTH_SUBTRACT / _INTERSECT, rm_probe_math (additions only); 7: rm_present_sharded_finish / rm_present_sharded take the size of the host buffer (a changed signature), rm_ctx_set_cull_min_pixels, rm_ctx_set_cull_budget, rm_ctx_cull_stats; 6: rm_present_striped_rows, rm_present_sharded_start / _finish, rm_ctx_last_warning, RM_PROBE_CAST_SHADOW, RM_PRIM_KIND (additions only); 3: rm_ctx_set_sample_batch, rm_buffer_*; 4: rm_ctx_set_gl_stack; 5: RmSurface / RmSceneDesc.surfaces (the struct grew), rm_pack_present_rows, rm_present_sharded, rm_ctx_last_pipeline, RM_RENDER_NO_FAR_JUMP, RM_RENDER_NO_CULL (additions only) */
 
 #define RM_MAX_BOUNCES 10 /* raymarchingStepCountsArray[10], raymarcher.frag:31 */
 #define RM_MAX_LIGHTS 10  /* lightPositions[10],             raymarcher.frag:37-39 */
@@ -446,6 +446,25 @@ RM_API int rm_fb_gbuffer(const rm_fb* fb);
 RM_API int rm_fb_download_raw(rm_fb* fb, int plane, void* host, size_t bytes);
 RM_API int rm_fb_upload_raw(rm_fb* fb, int plane, const void* host, size_t bytes);
 
+/* (ABI 9) The moments plane (opt-in): RM_FB_MOMENTS OR'ed into rm_fb_create_fmt's `gbuffer` argument gives an owned
+ * framebuffer a fourth plane, RM_PLANE_MOMENTS, of 2 x fp32 per pixel (8 bytes, rows as the other planes) in either
+ * G-buffer format: (sum l, sum l^2), where l is the luminance of one sample's colour contribution (the staged
+ * light * exposure, c), computed in fp32 in exactly this order, every product and sum rounded on its own, no contraction:
+ *   l = (0.2126f * c.r + 0.7152f * c.g) + 0.0722f * c.b
+ * It is blended by the colour plane's rule: (M.x + l, M.y + l * l) in additive mode, and in mix mode
+ * (f * (M.x - l) + l, f * (M.y - l * l) + l * l) with the colour's factor f.  Like the half G-buffer it is written only by
+ * rm_combine_kernel, so a render into a framebuffer with moments that writes the G-buffer (full mode, at least one
+ * bounce, not RM_RENDER_COLOR_ONLY) is always staged (one slot under RM_RENDER_NO_OVERLAP) and fails with RM_ERR_DEVICE
+ * when the staging cannot be allocated; other renders (preview mode, colour only) leave the plane as it is.  Created
+ * zero-filled and cleared by rm_fb_clear.  rm_fb_download_raw / rm_fb_upload_raw take plane 3 with exactly
+ * row_count*width*8 bytes and rm_fb_device_ptr(fb, 3) addresses it; without moments plane 3 is RM_ERR_INVALID / NULL.
+ * rm_fb_download / rm_fb_upload stay planes 0..2.  rm_fb_create_striped_fmt and rm_fb_wrap_fmt refuse the flag
+ * (RM_ERR_INVALID): the variance-guided denoiser, its only reader, needs a whole frame. */
+#define RM_FB_MOMENTS 0x100
+enum { RM_PLANE_MOMENTS = 3 };
+/* 1 when the framebuffer has the moments plane, else 0 (NULL included). */
+RM_API int rm_fb_has_moments(const rm_fb* fb);
+
 /* Raw device memory for hosts that have no allocator of their own: rm_present_rows, rm_present_device and
  * rm_assemble_striped_bytes take DEVICE pointers (in the reference these are textures the GL context owns,
  * LoadRenderJobContext.tsx:43-124; a torch host passes tensor addresses instead).  Created zero-filled; the copies
@@ -617,6 +636,35 @@ RM_API int rm_denoise_device(rm_ctx* ctx, rm_fb* fb, int samples, const RmDenois
  * the framebuffer's own normal + DoF plane): the bytes rm_present gives for a framebuffer whose colour plane holds
  * rm_denoise's result.  out_rgba8 = height x width x 4 bytes of HOST memory, row 0 = bottom. */
 RM_API int rm_present_denoised(rm_ctx* ctx, rm_fb* fb, int samples, const RmDenoise* params, uint8_t* out_rgba8);
+
+/* ---- variance-guided denoise (opt-in): rm_denoise's filter with the colour weight of SVGF (Schied et al. 2017) ----
+ * The same passes, taps, spatial kernel b, normal weight and depth weight as rm_denoise, on a framebuffer with the
+ * moments plane (RM_FB_MOMENTS); INTEGRATION.md "Denoising" states it in full.  With s, m_p, x_p, n_p, z_p as there and
+ * lum(c) = 0.2126 c.r + 0.7152 c.g + 0.0722 c.b, each pixel carries the variance of its demodulated luminance
+ *   v_p = max(0, M.y s - (M.x s)^2) s / max(lum(m_p), 1e-3)^2   (0 where that is not finite).
+ * Before each pass g = the 3x3 Gaussian (1,2,1)^2/16 of v (taps outside the image skipped, renormalised); the colour
+ * weight of the tap q is
+ *   w_l = exp(-|lum(x_p) - lum(x_q)| / (sigma_luminance sqrt(g_p) + eps_p)),   eps_p = max(1e-3 |lum(x_p)|, 1e-6)
+ * in place of rm_denoise's, and the pass filters the variance with the squared weights: v'_p = sum w^2 v_q / (sum w)^2.
+ * A pixel whose variance is 0 keeps its colour up to taps within a few tenths of a percent of its luminance, so the
+ * weights tighten as samples accumulate, while low-sample frames are smoothed (INTEGRATION.md gives the measured
+ * error against converged frames, edges and depth of field included).  The defaults differ from rm_denoise's.  Non-finite colours and depths, sky, the image border,
+ * the output units and iterations = 0 (an exact copy of the colour plane) are rm_denoise's.  RM_ERR_INVALID before any
+ * device work for everything rm_denoise refuses, a framebuffer without the moments plane, and a sigma that is <= 0 or
+ * not finite, or reserved != 0.  The passes use the same context buffers as rm_denoise (one denoise at a time per
+ * context). */
+typedef struct RmDenoiseVariance {
+  int iterations;         /* passes L, 0..8 (default 3) */
+  float sigma_luminance;  /* of the luminance distance, in units of the prefiltered standard deviation (default 4.0) */
+  float sigma_normal;     /* default 1.0 */
+  float sigma_depth;      /* relative to the centre's depth (default 0.2) */
+  int reserved;           /* must be 0 */
+} RmDenoiseVariance;
+RM_API void rm_denoise_variance_default(RmDenoiseVariance* params);
+/* rm_denoise, rm_denoise_device and rm_present_denoised with the variance-guided filter (NULL params = the defaults). */
+RM_API int rm_denoise_variance(rm_ctx* ctx, rm_fb* fb, int samples, const RmDenoiseVariance* params, float* out_host);
+RM_API int rm_denoise_variance_device(rm_ctx* ctx, rm_fb* fb, int samples, const RmDenoiseVariance* params, void* out_float4_device, void* hip_stream);
+RM_API int rm_present_denoised_variance(rm_ctx* ctx, rm_fb* fb, int samples, const RmDenoiseVariance* params, uint8_t* out_rgba8);
 
 /* The present of a frame that ONE process renders on several GPUs -- the shape of the reference's own host: one
  * thread, one render loop (index.tsx:120), here with a context per GPU, each holding one part of the frame's stripes

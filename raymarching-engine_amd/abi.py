@@ -22,6 +22,8 @@ RM_RENDER_NO_CULL = 128
 RM_PIPELINE_NONE, RM_PIPELINE_PIXEL_KERNEL, RM_PIPELINE_WAVEFRONT = 0, 1, 2
 RM_PLANE_COLOR, RM_PLANE_NORMAL_DOF, RM_PLANE_ALBEDO_DEPTH = 0, 1, 2
 RM_GBUFFER_F32, RM_GBUFFER_F16 = 0, 1  # G-buffer formats (ABI 9)
+RM_FB_MOMENTS = 0x100  # OR'ed into rm_fb_create_fmt's format: the moments plane (ABI 9)
+RM_PLANE_MOMENTS = 3
 RM_PROBE_SDF, RM_PROBE_CAST_RAY, RM_PROBE_NORMAL, RM_PROBE_MATERIAL, RM_PROBE_CAST_STEPS, RM_PROBE_CAST_SHADOW = 0, 1, 2, 3, 4, 5
 RM_MATH_FUNCTIONS = ("sin", "cos", "log", "exp", "pow", "acos", "atan2", "tan", "pow_pair_nm1", "pow_pair_n", "sincos_s", "sincos_c", "sqrt", "div")  # RM_MATH_*
 
@@ -124,6 +126,20 @@ class RmDenoise(C.Structure):
 
 
 DENOISE_DEFAULTS = dict(iterations=5, sigma_color=2.5, sigma_normal=2.0, sigma_depth=0.2)  # rm_denoise_default
+
+
+class RmDenoiseVariance(C.Structure):
+    """Parameters of rm_denoise_variance* (ABI 9): the variance-guided filter (include/hip_raymarch.h)."""
+    _fields_ = [
+        ("iterations", C.c_int32),
+        ("sigma_luminance", C.c_float),
+        ("sigma_normal", C.c_float),
+        ("sigma_depth", C.c_float),
+        ("reserved", C.c_int32),
+    ]
+
+
+DENOISE_VARIANCE_DEFAULTS = dict(iterations=3, sigma_luminance=4.0, sigma_normal=1.0, sigma_depth=0.2)  # rm_denoise_variance_default
 
 
 assert C.sizeof(RmPrim) == 32 and C.sizeof(RmSurface) == 48

@@ -63,7 +63,9 @@ def to_data_url(rgba8: np.ndarray) -> str:
 
 def save_png(framebuffer, samples: int, path: str, denoise=None) -> None:
     """Present `framebuffer` (rm_present: DoF blur, 1/samples, gamma) and write it as a PNG.  `denoise` (True, a dict or
-    abi.RmDenoise) presents the denoised colour instead (rm_present_denoised); None keeps the bytes of rm_present."""
+    abi.RmDenoise) presents the denoised colour instead (rm_present_denoised), and "variance" (or abi.RmDenoiseVariance, or a dict
+    with "mode": "variance") the variance-guided filter's (rm_present_denoised_variance), as Framebuffer.present does; None keeps
+    the bytes of rm_present."""
     rgba8 = framebuffer.present(samples) if denoise is None else framebuffer.present(samples, denoise=denoise)
     with open(path, "wb") as f:
         f.write(encode_png(rgba8))

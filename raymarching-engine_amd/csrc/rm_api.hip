@@ -164,11 +164,16 @@ struct rm_fb {
   float4* plane[3] = {nullptr, nullptr, nullptr};  // planes 1 and 2 hold rm_half4 when gbuffer == RM_GBUFFER_F16
   bool owned = false;
   int gbuffer = RM_GBUFFER_F32;
+  float2* moments = nullptr;  // RM_FB_MOMENTS (owned framebuffers only): plane 3, (sum l, sum l^2) per pixel
 };
 
 // bytes per pixel of a plane, and of the whole plane
-static size_t plane_px_bytes(int gbuffer, int plane) { return (plane > 0 && gbuffer == RM_GBUFFER_F16) ? sizeof(rm_half4) : sizeof(float4); }
+static size_t plane_px_bytes(int gbuffer, int plane) {
+  return plane == RM_PLANE_MOMENTS ? sizeof(float2) : (plane > 0 && gbuffer == RM_GBUFFER_F16) ? sizeof(rm_half4) : sizeof(float4);
+}
 static size_t plane_bytes(const rm_fb* fb, int plane) { return plane_px_bytes(fb->gbuffer, plane) * (size_t)fb->width * (size_t)fb->row_count; }
+// device address of plane 0..3 (3: the moments plane, NULL without one)
+static void* plane_ptr(const rm_fb* fb, int plane) { return plane == RM_PLANE_MOMENTS ? static_cast<void*>(fb->moments) : static_cast<void*>(fb->plane[plane]); }
 
 static thread_local std::string g_create_error;
 
@@ -783,6 +788,8 @@ int rm_fb_create(rm_ctx* ctx, int width, int height, int row_begin, int row_coun
 int rm_fb_create_fmt(rm_ctx* ctx, int width, int height, int row_begin, int row_count, int gbuffer, rm_fb** out) {
   if (!ctx || !out) return fail(ctx, RM_ERR_INVALID, "rm_fb_create: NULL argument");
   *out = nullptr;
+  const bool moments = (gbuffer & RM_FB_MOMENTS) != 0;
+  gbuffer &= ~RM_FB_MOMENTS;
   if (int rc = gbuffer_check(ctx, gbuffer, "rm_fb_create")) return rc;
   if (int rc = fb_check(ctx, width, height, row_begin, row_count)) return rc;
   rm_fb* fb = new (std::nothrow) rm_fb();
@@ -799,6 +806,17 @@ int rm_fb_create_fmt(rm_ctx* ctx, int width, int height, int row_begin, int row_
     if (e != hipSuccess) {
       for (int j = 0; j <= i; j++)
         if (fb->plane[j]) (void)hipFree(fb->plane[j]);
+      delete fb;
+      return fail(ctx, RM_ERR_DEVICE, std::string("rm_fb_create: ") + hipGetErrorString(e));
+    }
+  }
+  if (moments) {
+    const size_t bytes = plane_bytes(fb, RM_PLANE_MOMENTS);
+    hipError_t e = hipMalloc(reinterpret_cast<void**>(&fb->moments), bytes);
+    if (e == hipSuccess) e = hipMemsetAsync(fb->moments, 0, bytes, ctx->stream);
+    if (e != hipSuccess) {
+      for (auto* pl : fb->plane) (void)hipFree(pl);
+      if (fb->moments) (void)hipFree(fb->moments);
       delete fb;
       return fail(ctx, RM_ERR_DEVICE, std::string("rm_fb_create: ") + hipGetErrorString(e));
     }
@@ -825,6 +843,7 @@ int rm_fb_create_striped_fmt(rm_ctx* ctx, int width, int height, int stripe_rows
                              void* normal_dof, void* albedo_depth, int gbuffer, rm_fb** out) {
   if (!ctx || !out) return fail(ctx, RM_ERR_INVALID, "rm_fb_create_striped: NULL argument");
   *out = nullptr;
+  if (gbuffer & RM_FB_MOMENTS) return fail(ctx, RM_ERR_INVALID, "rm_fb_create_striped: RM_FB_MOMENTS needs a framebuffer holding the whole frame (rm_fb_create_fmt)");
   if (int rc = gbuffer_check(ctx, gbuffer, "rm_fb_create_striped")) return rc;
   if (int rc = fb_check(ctx, width, height, 0, 1)) return rc;
   if (stripe_rows < 1 || parts < 1 || part < 0 || part >= parts) return fail(ctx, RM_ERR_INVALID, "rm_fb_create_striped: need stripe_rows >= 1 and 0 <= part < parts");
@@ -876,6 +895,7 @@ int rm_fb_wrap_fmt(rm_ctx* ctx, int width, int height, int row_begin, int row_co
                    void* albedo_depth, int gbuffer, rm_fb** out) {
   if (!ctx || !out || !color) return fail(ctx, RM_ERR_INVALID, "rm_fb_wrap: NULL argument");
   *out = nullptr;
+  if (gbuffer & RM_FB_MOMENTS) return fail(ctx, RM_ERR_INVALID, "rm_fb_wrap: RM_FB_MOMENTS is for owned framebuffers (rm_fb_create_fmt)");
   if (int rc = gbuffer_check(ctx, gbuffer, "rm_fb_wrap")) return rc;
   if (int rc = fb_check(ctx, width, height, row_begin, row_count)) return rc;
   if ((normal_dof == nullptr) != (albedo_depth == nullptr)) return fail(ctx, RM_ERR_INVALID, "rm_fb_wrap: give both G-buffer planes or neither");
@@ -895,12 +915,14 @@ int rm_fb_wrap_fmt(rm_ctx* ctx, int width, int height, int row_begin, int row_co
 }
 
 int rm_fb_gbuffer(const rm_fb* fb) { return fb ? fb->gbuffer : RM_GBUFFER_F32; }
+int rm_fb_has_moments(const rm_fb* fb) { return fb && fb->moments ? 1 : 0; }
 
 int rm_fb_clear(rm_fb* fb) {
   if (!fb) return RM_ERR_INVALID;
   rm_ctx* ctx = fb->ctx;
   for (int i = 0; i < 3; i++)
     if (fb->plane[i]) RM_HIP(ctx, hipMemsetAsync(fb->plane[i], 0, plane_bytes(fb, i), ctx->stream));
+  if (fb->moments) RM_HIP(ctx, hipMemsetAsync(fb->moments, 0, plane_bytes(fb, RM_PLANE_MOMENTS), ctx->stream));
   return RM_OK;
 }
 
@@ -911,6 +933,7 @@ void rm_fb_destroy(rm_fb* fb) {
   if (fb->owned)
     for (int i = 0; i < 3; i++)
       if (fb->plane[i]) (void)hipFree(fb->plane[i]);
+  if (fb->moments) (void)hipFree(fb->moments);  // always the library's
   delete fb;
 }
 
@@ -958,8 +981,8 @@ int rm_fb_upload(rm_fb* fb, int plane, const float* host) {
 }
 
 static int raw_check(rm_fb* fb, int plane, const void* host, size_t bytes, const char* what) {
-  if (!fb || !host || plane < 0 || plane > 2) return fb ? fail(fb->ctx, RM_ERR_INVALID, std::string(what) + ": bad argument") : RM_ERR_INVALID;
-  if (!fb->plane[plane]) return fail(fb->ctx, RM_ERR_INVALID, std::string(what) + ": this framebuffer has no such plane");
+  if (!fb || !host || plane < 0 || plane > 3) return fb ? fail(fb->ctx, RM_ERR_INVALID, std::string(what) + ": bad argument") : RM_ERR_INVALID;
+  if (!plane_ptr(fb, plane)) return fail(fb->ctx, RM_ERR_INVALID, std::string(what) + ": this framebuffer has no such plane");
   if (bytes != plane_bytes(fb, plane)) {
     char buf[200];
     std::snprintf(buf, sizeof buf, "%s: plane %d holds %zu bytes (%d x %d pixels of %zu bytes), not %zu", what, plane, plane_bytes(fb, plane), fb->row_count,
@@ -972,7 +995,7 @@ static int raw_check(rm_fb* fb, int plane, const void* host, size_t bytes, const
 int rm_fb_download_raw(rm_fb* fb, int plane, void* host, size_t bytes) {
   if (int rc = raw_check(fb, plane, host, bytes, "rm_fb_download_raw")) return rc;
   rm_ctx* ctx = fb->ctx;
-  RM_HIP(ctx, hipMemcpyAsync(host, fb->plane[plane], bytes, hipMemcpyDeviceToHost, ctx->stream));
+  RM_HIP(ctx, hipMemcpyAsync(host, plane_ptr(fb, plane), bytes, hipMemcpyDeviceToHost, ctx->stream));
   RM_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return RM_OK;
 }
@@ -980,12 +1003,12 @@ int rm_fb_download_raw(rm_fb* fb, int plane, void* host, size_t bytes) {
 int rm_fb_upload_raw(rm_fb* fb, int plane, const void* host, size_t bytes) {
   if (int rc = raw_check(fb, plane, host, bytes, "rm_fb_upload_raw")) return rc;
   rm_ctx* ctx = fb->ctx;
-  RM_HIP(ctx, hipMemcpyAsync(fb->plane[plane], host, bytes, hipMemcpyHostToDevice, ctx->stream));
+  RM_HIP(ctx, hipMemcpyAsync(plane_ptr(fb, plane), host, bytes, hipMemcpyHostToDevice, ctx->stream));
   RM_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return RM_OK;
 }
 
-void* rm_fb_device_ptr(rm_fb* fb, int plane) { return (fb && plane >= 0 && plane <= 2) ? fb->plane[plane] : nullptr; }
+void* rm_fb_device_ptr(rm_fb* fb, int plane) { return (fb && plane >= 0 && plane <= 3) ? plane_ptr(fb, plane) : nullptr; }
 
 // ---- raw device memory for hosts without an allocator of their own ---------------------
 
@@ -1219,6 +1242,7 @@ static int build_params(rm_ctx* ctx, rm_scene* scene, rm_fb* fb, const RmUniform
   P->block_cost = nullptr;
   P->no_far_jump = (flags & RM_RENDER_NO_FAR_JUMP) ? 1 : 0;
   P->gbuffer_half = fb->gbuffer == RM_GBUFFER_F16 ? 1 : 0;
+  P->moments = color_only ? nullptr : fb->moments;  // blended by rm_combine_kernel, so only behind a staged launch (launch)
   if (P->no_far_jump) P->scene.far_end = 0, P->scene.clear_rho = 0.0f;  // the far-field shortcuts inside an evaluation (KIFS tree) read the scene block
   if (flags & RM_RENDER_NO_CULL) P->scene.cull.cells = nullptr;
   return RM_OK;
@@ -1426,7 +1450,7 @@ static bool uses_wavefront(const rm_ctx* ctx, const KParams& P, int flags) {
   if (!RM_WITH_WAVEFRONT) return false;  // the product library (build_params refuses the flag)
   if (ctx->gl_stack && !(flags & RM_RENDER_FAST)) return false;
   if (P.scene.table_flags & (RM_TABLE_HAS_SURFACES | RM_TABLE_HAS_KIND)) return false;
-  if (P.gbuffer_half) return false;  // the half G-buffer is blended by rm_combine_kernel behind the staged pixel kernel only
+  if (P.gbuffer_half || P.moments) return false;  // the half G-buffer and the moments are blended by rm_combine_kernel behind the staged pixel kernel only
   return (flags & RM_RENDER_WAVEFRONT) ? true : (flags & RM_RENDER_MEGAKERNEL) ? false : prefer_wavefront(P, flags);
 }
 
@@ -1604,7 +1628,8 @@ static hipError_t launch(rm_ctx* ctx, const KParams& P, int flags) {
   // exactly as it was -- so a render that writes the G-buffer (full mode, a bounce, the planes asked for: raymarcher.frag:347-351
   // runs at bounce 0) is always staged; with RM_RENDER_NO_OVERLAP on one staging slot, so that a sample's render waits for the
   // previous sample's blend.  No unstaged fallback: without room for the staging of the tile the call fails (render in tiles).
-  if (P.gbuffer_half && P.normal_dof != nullptr && P.u.renderMode == 0 && P.u.reflections > 0.0f)
+  // The moments plane (RM_FB_MOMENTS) is written by rm_combine_kernel only too, under the same rule.
+  if ((P.gbuffer_half || P.moments != nullptr) && P.normal_dof != nullptr && P.u.renderMode == 0 && P.u.reflections > 0.0f)
     return launch_pixels_in_flight(ctx, P, flags, 1, nullptr, (flags & RM_RENDER_NO_OVERLAP) ? 1 : 0);
   // full mode with at least one bounce: the kernel's only use of the planes is the final blend, which can be split off
   if (ctx->samples_in_flight > 1 && !(flags & RM_RENDER_NO_OVERLAP) && P.u.renderMode == 0 && P.u.reflections > 0.0f) {
@@ -1819,8 +1844,9 @@ static int denoise_check(rm_ctx* ctx, rm_fb* fb, int samples, const RmDenoise* p
 }
 
 // Enqueues the passes on `stream`.  out: the result, or NULL for one of the context's buffers; *result = where it is (the
-// colour plane itself for 0 iterations and no `out`).
-static int denoise_enqueue(rm_ctx* ctx, rm_fb* fb, int samples, const RmDenoise* params, float4* out, hipStream_t stream, const float4** result) {
+// colour plane itself for 0 iterations and no `out`).  var: the variance-guided mode, d.sigma_color holding sigma_luminance.
+static int denoise_enqueue(rm_ctx* ctx, rm_fb* fb, int samples, const RmDenoise* params, float4* out, hipStream_t stream, const float4** result,
+                           bool var = false) {
   RmDenoise d;
   if (params) d = *params;
   else rm_denoise_default(&d);
@@ -1853,6 +1879,8 @@ static int denoise_enqueue(rm_ctx* ctx, rm_fb* fb, int samples, const RmDenoise*
   P.s = 1.0f / (float)samples;  // present_device's scale
   P.k = (float)samples;
   P.inv_normal = 1.0f / (d.sigma_normal * d.sigma_normal);
+  P.moments = var ? fb->moments : nullptr;
+  P.sigma_l = d.sigma_color;
   const bool half = fb->gbuffer == RM_GBUFFER_F16;
   for (int i = 0; i < L; i++) {
     P.step = 1 << i;
@@ -1860,7 +1888,7 @@ static int denoise_enqueue(rm_ctx* ctx, rm_fb* fb, int samples, const RmDenoise*
     P.sigma_z_h = d.sigma_depth * (float)P.step;
     P.x_in = i > 0 ? ctx->denoise_buf[(i - 1) % 2] : nullptr;
     P.out = (i == L - 1 && out) ? out : ctx->denoise_buf[i % 2];
-    RM_HIP(ctx, rm::launch_denoise_pass(P, half, i == 0, i == L - 1, stream));
+    RM_HIP(ctx, (var ? rm::launch_denoise_variance_pass : rm::launch_denoise_pass)(P, half, i == 0, i == L - 1, stream));
   }
   *result = P.out;
   return RM_OK;
@@ -1889,6 +1917,60 @@ int rm_present_denoised(rm_ctx* ctx, rm_fb* fb, int samples, const RmDenoise* pa
   if (!out_rgba8) return fail(ctx, RM_ERR_INVALID, "rm_present_denoised: NULL argument");
   const float4* r = nullptr;
   if (int rc = denoise_enqueue(ctx, fb, samples, params, nullptr, ctx->stream, &r)) return rc;
+  return present_planes(ctx, r, fb->plane[1], fb->gbuffer == RM_GBUFFER_F16, fb->width, fb->height, samples, out_rgba8);
+}
+
+// ---- variance-guided denoise (rm_frame_kernels.inc "the variance-guided mode") ------------------------
+
+void rm_denoise_variance_default(RmDenoiseVariance* p) {
+  if (!p) return;
+  std::memset(p, 0, sizeof *p);
+  p->iterations = 3;
+  p->sigma_luminance = 4.0f;
+  p->sigma_normal = 1.0f;
+  p->sigma_depth = 0.2f;
+}
+
+// rm_denoise's checks, the moments plane and the variance parameters; *d = the parameters as denoise_enqueue takes them
+static int denoise_variance_check(rm_ctx* ctx, rm_fb* fb, int samples, const RmDenoiseVariance* params, const char* who, RmDenoise* d) {
+  RmDenoiseVariance v;
+  if (params) v = *params;
+  else rm_denoise_variance_default(&v);
+  if (!ctx || !fb) return fail(ctx, RM_ERR_INVALID, std::string(who) + ": NULL argument");
+  if (params && params->reserved != 0) return fail(ctx, RM_ERR_INVALID, std::string(who) + ": reserved must be 0");
+  if (!(v.sigma_luminance > 0.0f && std::isfinite(v.sigma_luminance))) return fail(ctx, RM_ERR_INVALID, std::string(who) + ": every sigma must be finite and > 0");
+  *d = RmDenoise{v.iterations, v.sigma_luminance, v.sigma_normal, v.sigma_depth, 0};
+  if (int rc = denoise_check(ctx, fb, samples, d, who)) return rc;
+  if (!fb->moments) return fail(ctx, RM_ERR_INVALID, std::string(who) + ": the framebuffer has no moments plane (create it with RM_FB_MOMENTS)");
+  return RM_OK;
+}
+
+int rm_denoise_variance_device(rm_ctx* ctx, rm_fb* fb, int samples, const RmDenoiseVariance* params, void* out_float4_device, void* hip_stream) {
+  RmDenoise d;
+  if (int rc = denoise_variance_check(ctx, fb, samples, params, "rm_denoise_variance_device", &d)) return rc;
+  if (!out_float4_device || (reinterpret_cast<uintptr_t>(out_float4_device) & 15u))
+    return fail(ctx, RM_ERR_INVALID, "rm_denoise_variance_device: the output must be a 16-byte aligned device buffer");
+  const float4* r = nullptr;
+  return denoise_enqueue(ctx, fb, samples, &d, static_cast<float4*>(out_float4_device), hip_stream ? static_cast<hipStream_t>(hip_stream) : ctx->stream, &r, true);
+}
+
+int rm_denoise_variance(rm_ctx* ctx, rm_fb* fb, int samples, const RmDenoiseVariance* params, float* out_host) {
+  RmDenoise d;
+  if (int rc = denoise_variance_check(ctx, fb, samples, params, "rm_denoise_variance", &d)) return rc;
+  if (!out_host) return fail(ctx, RM_ERR_INVALID, "rm_denoise_variance: NULL argument");
+  const float4* r = nullptr;
+  if (int rc = denoise_enqueue(ctx, fb, samples, &d, nullptr, ctx->stream, &r, true)) return rc;
+  RM_HIP(ctx, hipMemcpyAsync(out_host, r, (size_t)fb->width * (size_t)fb->height * sizeof(float4), hipMemcpyDeviceToHost, ctx->stream));
+  RM_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return RM_OK;
+}
+
+int rm_present_denoised_variance(rm_ctx* ctx, rm_fb* fb, int samples, const RmDenoiseVariance* params, uint8_t* out_rgba8) {
+  RmDenoise d;
+  if (int rc = denoise_variance_check(ctx, fb, samples, params, "rm_present_denoised_variance", &d)) return rc;
+  if (!out_rgba8) return fail(ctx, RM_ERR_INVALID, "rm_present_denoised_variance: NULL argument");
+  const float4* r = nullptr;
+  if (int rc = denoise_enqueue(ctx, fb, samples, &d, nullptr, ctx->stream, &r, true)) return rc;
   return present_planes(ctx, r, fb->plane[1], fb->gbuffer == RM_GBUFFER_F16, fb->width, fb->height, samples, out_rgba8);
 }
 

@@ -43,7 +43,10 @@ hipError_t launch_assemble(const void* src, int parts, int max_rows, long long r
 // Exactly the operations the pixel kernel performs when it blends itself, on the values it staged
 // (KParams::stage), so a staged sample leaves the same bits in the planes; the samples of a batch
 // (KParams::batch) are blended one after the other, in sample order, as separate launches would.
-__global__ __launch_bounds__(256) void rm_combine_kernel(const KParams P) {
+// MOMENTS: also the moments plane (RM_FB_MOMENTS, KParams::moments), by the colour's rule, on l = the luminance of the staged
+// colour in the order include/hip_raymarch.h states (this TU is contract-off: every product and sum is rounded on its own).
+template <bool MOMENTS>
+__device__ inline void rm_combine(const KParams& P) {
   const long long total = (long long)P.tw * P.th;
   const RmUniforms& u = P.u;
   const int samples = P.batch > 1 ? P.batch : 1;
@@ -51,6 +54,8 @@ __global__ __launch_bounds__(256) void rm_combine_kernel(const KParams P) {
     const int x = (int)(i % P.tw), y = (int)(i / P.tw);
     const size_t pix = (size_t)(P.ty + y) * (size_t)P.W + (size_t)(P.tx + x);
     float4 col = P.color[pix];
+    float2 mo;
+    if (MOMENTS) mo = P.moments[pix];
     for (int k = 0; k < samples; k++) {
       const float4 s = P.stage[(long long)k * 3ll * P.stage_stride + i], prev = col;  // staged tile-compact: pixel i of the tile
       if (u.blendMode == 0) {
@@ -59,8 +64,18 @@ __global__ __launch_bounds__(256) void rm_combine_kernel(const KParams P) {
       } else {
         col = make_float4(s.x + prev.x, s.y + prev.y, s.z + prev.z, 1.0f + prev.w);
       }
+      if (MOMENTS) {
+        const float l = (0.2126f * s.x + 0.7152f * s.y) + 0.0722f * s.z, l2 = l * l;
+        if (u.blendMode == 0) {
+          const float f = u.blendWithPreviousFactor;
+          mo = make_float2(gmix<PM>(l, mo.x, f), gmix<PM>(l2, mo.y, f));
+        } else {
+          mo = make_float2(mo.x + l, mo.y + l2);
+        }
+      }
     }
     P.color[pix] = col;
+    if (MOMENTS) P.moments[pix] = mo;
     if (P.normal_dof != nullptr && P.gbuffer_half) {  // RGBA16F: rounded to half after EVERY sample, as separate draws would
       rm_half4* const hn = reinterpret_cast<rm_half4*>(P.normal_dof);
       rm_half4* const ha = reinterpret_cast<rm_half4*>(P.albedo_depth);
@@ -88,8 +103,12 @@ __global__ __launch_bounds__(256) void rm_combine_kernel(const KParams P) {
   }
 }
 
+__global__ __launch_bounds__(256) void rm_combine_kernel(const KParams P) { rm_combine<false>(P); }
+__global__ __launch_bounds__(256) void rm_combine_moments_kernel(const KParams P) { rm_combine<true>(P); }
+
 hipError_t launch_combine(const KParams& P, hipStream_t stream) {
-  hipLaunchKernelGGL(rm_combine_kernel, dim3(small_grid((long long)P.tw * P.th)), dim3(256), 0, stream, P);
+  if (P.moments) hipLaunchKernelGGL(rm_combine_moments_kernel, dim3(small_grid((long long)P.tw * P.th)), dim3(256), 0, stream, P);
+  else hipLaunchKernelGGL(rm_combine_kernel, dim3(small_grid((long long)P.tw * P.th)), dim3(256), 0, stream, P);
   return hipGetLastError();
 }
 
@@ -314,10 +333,32 @@ __device__ inline void dn_prepare(const DenoisePass& P, size_t i, float4& x, flo
   g = (len >= 1e-6f && isfinite(len)) ? make_float4(nx / len, ny / len, nz / len, a.w * P.s) : make_float4(0.0f, 0.0f, 0.0f, a.w * P.s);
 }
 
+// ---- the variance-guided mode (rm_denoise_variance; SVGF's colour weight, Schied et al. 2017) ----
+// x.w carries v, the variance of the pixel's demodulated luminance: pass 0 computes it from the moments plane,
+//   v_p = max(0, M.y s - (M.x s)^2) s / max(lum(m_p), 1e-3)^2   (0 where not finite),
+// and every pass filters it with the squared weights, v'_p = sum w^2 v_q / (sum w)^2.  The colour weight of a pass is
+//   w_l = exp(-|lum(x_p) - lum(x_q)| / (sigma_l sqrt(g_p) + eps_p)),   eps_p = max(1e-3 |lum(x_p)|, 1e-6),
+//   g = the 3x3 Gaussian (1,2,1)^2/16 of v
+// (taps outside the image skipped, renormalised), read from the tile in LDS at steps 1 and 2 and through the caches beyond.
+// The normal and depth weights, the spatial kernel, the taps and the remodulation are the mode above's.
+__device__ inline float dn_lum(const float4 v) { return (0.2126f * v.x + 0.7152f * v.y) + 0.0722f * v.z; }
+
+template <class GB>
+__device__ inline void dn_prepare_var(const DenoisePass& P, size_t i, float4& x, float4& g) {
+  dn_prepare<GB>(P, i, x, g);
+  const float3 m = dn_modulation(dn_load<GB>(P.albedo_depth, i), P.s);
+  const float2 M = P.moments[i];
+  const float mu = M.x * P.s, lm = fmaxf((0.2126f * m.x + 0.7152f * m.y) + 0.0722f * m.z, 1e-3f);
+  const float v = fmaxf(0.0f, M.y * P.s - mu * mu) * P.s / (lm * lm);
+  x.w = isfinite(v) ? v : 0.0f;
+}
+
 // STAGE: the step h of a pass staged in LDS (1 or 2), 0 for a pass that reads through the caches.  PREP: pass 0 (reads the
 // planes).  LAST: the last pass (writes colour-plane units).  GB: float4, or rm_half4 for the planes of a half G-buffer.
-template <int STAGE, bool PREP, bool LAST, class GB>
+// VAR: the variance-guided mode (above); false is rm_denoise's filter.
+template <int STAGE, bool PREP, bool LAST, class GB, bool VAR>
 __global__ __launch_bounds__(256) void rm_denoise_kernel(const DenoisePass P) {
+  static_assert(!(VAR && PREP && STAGE == 0), "pass 0 is staged");
   constexpr int HALO = 2 * STAGE, SPAN = 16 + 2 * HALO;
   __shared__ float4 sx[STAGE > 0 ? SPAN * SPAN : 1], sg[STAGE > 0 ? SPAN * SPAN : 1];
   const int lx = threadIdx.x % 16, ly = threadIdx.x / 16;
@@ -329,7 +370,10 @@ __global__ __launch_bounds__(256) void rm_denoise_kernel(const DenoisePass P) {
       const int gx = x0 + i % SPAN, gy = y0 + i / SPAN;
       if (gx < 0 || gx >= P.W || gy < 0 || gy >= P.H) continue;  // never read: a tap outside the image is skipped
       const size_t q = (size_t)gy * P.W + gx;
-      if (PREP) dn_prepare<GB>(P, q, sx[i], sg[i]);
+      if (PREP) {
+        if (VAR) dn_prepare_var<GB>(P, q, sx[i], sg[i]);
+        else dn_prepare<GB>(P, q, sx[i], sg[i]);
+      }
       else { sx[i] = P.x_in[q]; sg[i] = P.guide[q]; }
     }
     __syncthreads();
@@ -342,7 +386,8 @@ __global__ __launch_bounds__(256) void rm_denoise_kernel(const DenoisePass P) {
     xp = sx[c];
     gp = sg[c];
   } else if (PREP) {
-    dn_prepare<GB>(P, p, xp, gp);
+    if (VAR) dn_prepare_var<GB>(P, p, xp, gp);
+    else dn_prepare<GB>(P, p, xp, gp);
   } else {
     xp = P.x_in[p];
     gp = P.guide[p];
@@ -352,6 +397,23 @@ __global__ __launch_bounds__(256) void rm_denoise_kernel(const DenoisePass P) {
   if (dn_finite3(xp)) {
     constexpr float b[5] = {1.0f / 16.0f, 1.0f / 4.0f, 3.0f / 8.0f, 1.0f / 4.0f, 1.0f / 16.0f};
     const float zp = gp.w;
+    float lp = 0.0f, inv_l = 0.0f, av = 0.0f;
+    if (VAR) {  // g_p: the 3x3 prefilter of v around p
+      float gs = 0.0f, gw = 0.0f;
+#pragma unroll
+      for (int dy = -1; dy <= 1; dy++) {
+        if (y + dy < 0 || y + dy >= P.H) continue;
+#pragma unroll
+        for (int dx = -1; dx <= 1; dx++) {
+          if (x + dx < 0 || x + dx >= P.W) continue;
+          const float k = (dy == 0 ? 0.5f : 0.25f) * (dx == 0 ? 0.5f : 0.25f);
+          gs += k * (STAGE > 0 ? sx[(ly + HALO + dy) * SPAN + lx + HALO + dx].w : P.x_in[(size_t)(y + dy) * P.W + (x + dx)].w);
+          gw += k;
+        }
+      }
+      lp = dn_lum(xp);
+      inv_l = 1.0f / (P.sigma_l * sqrtf(gs / gw) + fmaxf(1e-3f * fabsf(lp), 1e-6f));  // eps_p: well above lum's fp32 resolution
+    }
     const bool zp_finite = isfinite(zp);
     const float inv_z = 1.0f / (P.sigma_z_h * fmaxf(zp, 1e-6f));
     float ax = 0.0f, ay = 0.0f, az = 0.0f, wsum = 0.0f;
@@ -376,7 +438,8 @@ __global__ __launch_bounds__(256) void rm_denoise_kernel(const DenoisePass P) {
         if (!dn_finite3(xq)) continue;
         const float cx = xp.x - xq.x, cy = xp.y - xq.y, cz = xp.z - xq.z;
         const float nx = gp.x - gq.x, ny = gp.y - gq.y, nz = gp.z - gq.z;
-        float e = dn_scaled(cx * cx + cy * cy + cz * cz, P.inv_color) + dn_scaled(nx * nx + ny * ny + nz * nz, P.inv_normal);
+        float e = (VAR ? dn_scaled(fabsf(lp - dn_lum(xq)), inv_l) : dn_scaled(cx * cx + cy * cy + cz * cz, P.inv_color)) +
+                  dn_scaled(nx * nx + ny * ny + nz * nz, P.inv_normal);
         if (dx != 0 || dy != 0) {
           const bool zq_finite = isfinite(gq.w);
           if (zq_finite != zp_finite) continue;
@@ -387,9 +450,10 @@ __global__ __launch_bounds__(256) void rm_denoise_kernel(const DenoisePass P) {
         ay += w * xq.y;
         az += w * xq.z;
         wsum += w;
+        if (VAR) av += w * w * xq.w;
       }
     }
-    r = make_float4(ax / wsum, ay / wsum, az / wsum, 0.0f);  // wsum >= b[2]^2: the centre tap weighs (3/8)^2
+    r = make_float4(ax / wsum, ay / wsum, az / wsum, VAR ? av / (wsum * wsum) : 0.0f);  // wsum >= b[2]^2: the centre tap weighs (3/8)^2
   }
   if (LAST) {
     const float3 m = dn_modulation(dn_load<GB>(P.albedo_depth, p), P.s);
@@ -398,12 +462,13 @@ __global__ __launch_bounds__(256) void rm_denoise_kernel(const DenoisePass P) {
   P.out[p] = r;
 }
 
-hipError_t launch_denoise_pass(const DenoisePass& P, bool half, bool prep, bool last, hipStream_t stream) {
+template <bool VAR>
+static hipError_t launch_denoise_pass_t(const DenoisePass& P, bool half, bool prep, bool last, hipStream_t stream) {
   const dim3 grid((P.W + 15) / 16, (P.H + 15) / 16);
 #define RM_DENOISE(STAGE, PREP, GB)                                                                                    \
   do {                                                                                                                 \
-    if (last) hipLaunchKernelGGL((rm_denoise_kernel<STAGE, PREP, true, GB>), grid, dim3(256), 0, stream, P);          \
-    else hipLaunchKernelGGL((rm_denoise_kernel<STAGE, PREP, false, GB>), grid, dim3(256), 0, stream, P);              \
+    if (last) hipLaunchKernelGGL((rm_denoise_kernel<STAGE, PREP, true, GB, VAR>), grid, dim3(256), 0, stream, P);     \
+    else hipLaunchKernelGGL((rm_denoise_kernel<STAGE, PREP, false, GB, VAR>), grid, dim3(256), 0, stream, P);         \
   } while (0)
   if (prep) {  // pass 0: h = 1
     if (half) RM_DENOISE(1, true, rm_half4);
@@ -417,6 +482,13 @@ hipError_t launch_denoise_pass(const DenoisePass& P, bool half, bool prep, bool 
   }
 #undef RM_DENOISE
   return hipGetLastError();
+}
+
+hipError_t launch_denoise_pass(const DenoisePass& P, bool half, bool prep, bool last, hipStream_t stream) {
+  return launch_denoise_pass_t<false>(P, half, prep, last, stream);
+}
+hipError_t launch_denoise_variance_pass(const DenoisePass& P, bool half, bool prep, bool last, hipStream_t stream) {
+  return launch_denoise_pass_t<true>(P, half, prep, last, stream);
 }
 #endif
 

@@ -264,6 +264,8 @@ struct KParams {
   int no_far_jump;  // RM_RENDER_NO_FAR_JUMP: march escaping rays step by step (a measurement / test switch, same bits)
   int gbuffer_half;  // RM_GBUFFER_F16: normal_dof / albedo_depth point at rm_half4 planes -- read by rm_combine_kernel; a launch of
                      // the pixel kernel that would blend into them itself is never made (rm_api.hip launch: always staged)
+  float2* moments;   // RM_FB_MOMENTS: (sum l, sum l^2) per pixel, written by rm_combine_kernel only (like the half planes: a launch
+                     // that writes the G-buffer into a framebuffer with moments is always staged); nullptr = none
 };
 
 // a table long enough for the compacting pixel kernel (rm_device.hpp RM_KIND_TABLE_BIG); launcher and grid computation agree through this
@@ -302,6 +304,9 @@ struct DenoisePass {
   int W, H, step;            // step h = 2^pass
   float s, k;                // 1 / samples, samples
   float inv_color, inv_normal, sigma_z_h;  // 1 / (sigma_c^2 4^-pass), 1 / sigma_n^2, sigma_z h
+  // the variance-guided mode only (rm_denoise_variance): x.w carries the variance v of the demodulated luminance
+  const float2* moments;     // (sum l, sum l^2) per pixel, read by pass 0
+  float sigma_l;             // sigma_luminance
 };
 
 namespace rm {
@@ -362,6 +367,8 @@ hipError_t launch_convert(const void* src, void* dst, long long pixels, bool nar
 hipError_t launch_present_rows(const float4* color, long long pixels, float brightness, uchar4* out, hipStream_t stream);
 // one pass of rm_denoise (rm_frame_kernels.inc "denoise"); half: the G-buffer planes hold rm_half4
 hipError_t launch_denoise_pass(const DenoisePass& P, bool half, bool prep, bool last, hipStream_t stream);
+// one pass of rm_denoise_variance (the same, x.w = the variance; P.moments read by pass 0)
+hipError_t launch_denoise_variance_pass(const DenoisePass& P, bool half, bool prep, bool last, hipStream_t stream);
 hipError_t launch_present(const float4* color, const void* normal_dof, bool nd_half, int W, int H, float brightness, uchar4* out, hipStream_t stream);
 hipError_t launch_present_striped(const float4* color, const float4* normal_dof, int W, int H, float brightness, uchar4* out, int stripe_rows, int parts, int part,
                                   int local_rows, hipStream_t stream);

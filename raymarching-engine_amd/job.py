@@ -219,13 +219,18 @@ class RenderJobContext:
     # the G-buffer format of every framebuffer the context makes: "f32" (the default, the goldens' software GL stack) or "f16" (the
     # reference's RGBA16F normal + DoF radius and albedo + depth planes on a hardware GL, LoadRenderJobContext.tsx:81-119)
     gbuffer = "f32"
+    # every framebuffer the context makes also keeps the luminance moments plane (RM_FB_MOMENTS) the variance-guided denoiser reads
+    moments = False
 
     def __init__(self, device: int = 0, flags: int = abi.RM_RENDER_STRICT, rows: Optional[Tuple[int, int]] = None, group=None,
-                 native_context=None, stripes: Optional[Tuple[int, int]] = None, gbuffer: str = "f32"):
+                 native_context=None, stripes: Optional[Tuple[int, int]] = None, gbuffer: str = "f32", moments: bool = False):
         from . import native
 
         native.gbuffer_code(gbuffer)  # ValueError before any device work
+        if moments and ((group is not None and group.sharded) or stripes is not None):
+            raise ValueError("RenderJobContext: moments=True needs framebuffers holding the whole frame, not a sharded or striped one")
         self.gbuffer = gbuffer
+        self.moments = bool(moments)
         self.native = native_context if native_context is not None else native.Context(device)
         self.flags = flags
         self.rows = rows  # (row_begin, row_count) window of this GPU, None = whole image
@@ -353,6 +358,8 @@ class RenderJobContext:
             fb = self.native.create_striped_framebuffer(width, height, shard.STRIPE_ROWS, self.stripes[0], self.stripes[1], **fmt)
         else:
             rb, rc = self.rows if self.rows is not None else (0, height)
+            if self.moments:
+                fmt["moments"] = True
             fb = self.native.create_framebuffer(width, height, rb, rc, **fmt)
         self._live[key] = fb
         return fb
@@ -464,15 +471,16 @@ def drain(generator) -> dict:
         return stop.value
 
 
-def collect_presents(frames: list) -> Callable:
+def collect_presents(frames: list, denoise=None) -> Callable:
     """A ``present`` callback for drain(): appends (samples, canvas) for every present of the job that has samples to
     show -- the reference presents once BEFORE the first sample too (RenderJobExecutor.tsx:163 at samplesRenderedSoFar
     = 0: the previous job's accumulation; its presenter divides by its own running count, index.tsx:25-39), which has
     no brightness here.  `canvas` = framebuffer.present(samples): RGBA8 [H, W, 4], row 0 = bottom; on a sharded job the
-    call is the ranks' collective and the canvas is None on every rank but 0."""
+    call is the ranks' collective and the canvas is None on every rank but 0.  `denoise`: passed on to framebuffer.present
+    (None: not asked for, the bytes of rm_present)."""
 
     def present(schema, context, fb, samples):
         if samples > 0:
-            frames.append((samples, fb.present(samples)))
+            frames.append((samples, fb.present(samples) if denoise is None else fb.present(samples, denoise=denoise)))
 
     return present

@@ -50,13 +50,21 @@ export type RenderJobSchema = {
 };
 export type RenderJobFramebufferInfo = {
   width: number; height: number; frameid: number; download(plane?: 0 | 1 | 2): Float32Array;
-  /** display.frag on the GPU: RGBA8, row 0 = bottom; `denoise` presents the denoised colour (rm_present_denoised) */
-  present(samples: number, opts?: { denoise?: true | DenoiseParams }): Uint8Array;
+  /** display.frag on the GPU: RGBA8, row 0 = bottom; `denoise` presents the denoised colour (rm_present_denoised), or with
+   *  "variance" / { mode: "variance", ... } the variance-guided filter's (rm_present_denoised_variance; needs { moments: true }) */
+  present(samples: number, opts?: { denoise?: DenoiseOption }): Uint8Array;
+  /** the colour plane after the variance-guided filter (rm_denoise_variance; needs { moments: true }) */
+  denoiseVariance(samples: number, params?: true | "variance" | DenoiseVarianceParams): Float32Array;
   /** the colour plane after the G-buffer-guided a-trous filter (rm_denoise): colour-plane units, row 0 = bottom */
   denoise(samples: number, params?: true | DenoiseParams): Float32Array;
   /** canvas.toDataURL("image/png") of the presented frame (index.tsx:470-476) */
-  toDataURL(samples: number, opts?: { denoise?: true | DenoiseParams }): string;
+  toDataURL(samples: number, opts?: { denoise?: DenoiseOption }): string;
 };
+/** RmDenoiseVariance (include/hip_raymarch.h): fields left out take DENOISE_VARIANCE_DEFAULTS' values */
+export type DenoiseVarianceParams = { iterations?: number; sigma_luminance?: number; sigma_normal?: number; sigma_depth?: number };
+export type DenoiseOption = true | DenoiseParams | (DenoiseParams & { mode: "atrous" }) | "variance" | (DenoiseVarianceParams & { mode: "variance" });
+export const DENOISE_VARIANCE_DEFAULTS: Required<DenoiseVarianceParams>;
+export function denoiseVarianceParams(params?: true | "variance" | (DenoiseVarianceParams & { mode?: "variance" }) | null): Required<DenoiseVarianceParams>;
 /** RmDenoise (include/hip_raymarch.h): fields left out take DENOISE_DEFAULTS' values */
 export type DenoiseParams = { iterations?: number; sigma_color?: number; sigma_normal?: number; sigma_depth?: number };
 export const DENOISE_DEFAULTS: Required<DenoiseParams>;
@@ -67,8 +75,10 @@ export type ShaderError = { type: "vertex" | "fragment" | "program"; infoLog: st
 export type GBufferFormat = "f32" | "f16";
 export class RenderJobContext {
   constructor(device?: number, flags?: number);
-  constructor(options: { device?: number; flags?: number; gbuffer?: GBufferFormat });
+  /** moments: every framebuffer also keeps the luminance moments plane (RM_FB_MOMENTS) the variance-guided denoiser reads */
+  constructor(options: { device?: number; flags?: number; gbuffer?: GBufferFormat; moments?: boolean });
   readonly gbuffer: GBufferFormat;
+  readonly moments: boolean;
   fboCreate(width: number, height: number, frameid: number): RenderJobFramebufferInfo;
   fboDelete(width: number, height: number, frameid: number): void;
   close(): void;

@@ -22,7 +22,7 @@ const RM = {
   PRIM_SPHERE: 0, PRIM_BOX: 1, PRIM_REPEAT: 2, PRIM_FOLD: 3, PRIM_KIND: 4, PRIM_TORUS: 5, PRIM_CYLINDER: 6, PRIM_PLANE: 7,
   OP_UNION: 0, OP_SMOOTH_UNION: 1, OP_SUBTRACT: 2, OP_INTERSECT: 3, OP_SMOOTH_SUBTRACT: 4, OP_SMOOTH_INTERSECT: 5,
   RENDER_STRICT: 0, RENDER_FAST: 1, RENDER_COLOR_ONLY: 2, RENDER_MEGAKERNEL: 4, RENDER_WAVEFRONT: 16, RENDER_NO_OVERLAP: 32, RENDER_NO_FAR_JUMP: 64, RENDER_NO_CULL: 128,
-  GBUFFER_F32: 0, GBUFFER_F16: 1,
+  GBUFFER_F32: 0, GBUFFER_F16: 1, FB_MOMENTS: 0x100, PLANE_MOMENTS: 3,
 };
 // G-buffer formats of a context's framebuffers (include/hip_raymarch.h RM_GBUFFER_*): "f32", the default (the goldens' software GL
 // stack), or "f16", the reference's RGBA16F normal + DoF radius and albedo + depth planes (LoadRenderJobContext.tsx:81-119)
@@ -261,11 +261,13 @@ const scenePins = {  // mixed into both contexts, for hosts that hold handles th
 };
 
 class RenderJobContext {  // RenderJobContext + loadRenderJobContext (LoadRenderJobContext.tsx:162-287)
-  // new RenderJobContext(device?, flags?) or new RenderJobContext({ device, flags, gbuffer })
+  // new RenderJobContext(device?, flags?) or new RenderJobContext({ device, flags, gbuffer, moments })
+  // moments: every framebuffer also keeps the luminance moments plane (RM_FB_MOMENTS) the variance-guided denoiser reads
   constructor(device = 0, flags = RM.RENDER_STRICT) {
-    let gbuffer = "f32";
-    if (device !== null && typeof device === "object") ({ device = 0, flags = RM.RENDER_STRICT, gbuffer = "f32" } = device);
+    let gbuffer = "f32", moments = false;
+    if (device !== null && typeof device === "object") ({ device = 0, flags = RM.RENDER_STRICT, gbuffer = "f32", moments = false } = device);
     this.gbuffer = gbuffer; this.gbufferCode = gbufferCode(gbuffer);  // (before any device work)
+    this.moments = !!moments;
     this.ctx = addon.ctxCreate(device); this.flags = flags; this.scenes = new Map(); this.pins = new Map(); this.live = new Map(); this.purgatory = [];
   }
   evict(keep) { evictScenes(this.scenes, (s) => { if (!(s && s.infoLog)) addon.sceneDestroy(s); }, this.pins, keep); }
@@ -284,15 +286,20 @@ class RenderJobContext {  // RenderJobContext + loadRenderJobContext (LoadRender
     const i = this.purgatory.findIndex((e) => e.w === w && e.h === h);
     let fb;
     if (i >= 0) { const e = this.purgatory.splice(i, 1)[0]; if (e.frameid !== frameid) addon.fbClear(e.fb); fb = e.fb; }
-    else fb = addon.fbCreate(this.ctx, w, h, 0, h, this.gbufferCode);
+    else fb = addon.fbCreate(this.ctx, w, h, 0, h, this.gbufferCode | (this.moments ? RM.FB_MOMENTS : 0));
     const info = { fb, width: w, height: h, frameid, download: (plane = 0) => { const out = new Float32Array(w * h * 4); addon.fbDownload(this.ctx, fb, plane, out); return out; },
                    // the present pass (display.frag) on the GPU: RGBA8, row 0 = bottom
-                   // opts.denoise (true or the parameters of denoiseParams): the denoised colour through the same pass (rm_present_denoised)
+                   // opts.denoise (true or the parameters of denoiseParams): the denoised colour through the same pass (rm_present_denoised);
+                   // "variance" or { mode: "variance", ... } (denoiseVarianceParams): the variance-guided filter's (rm_present_denoised_variance)
                    present: (samples, opts = {}) => {
                      const out = new Uint8Array(w * h * 4);
-                     if (opts.denoise === undefined || opts.denoise === null || opts.denoise === false) addon.present(this.ctx, fb, samples, out);
-                     else addon.presentDenoised(this.ctx, fb, samples, denoiseParams(opts.denoise), out);
+                     const d = opts.denoise;
+                     if (d === undefined || d === null || d === false) addon.present(this.ctx, fb, samples, out);
+                     else if (isVarianceMode(d)) addon.presentDenoisedVariance(this.ctx, fb, samples, denoiseVarianceParams(d), out);
+                     else addon.presentDenoised(this.ctx, fb, samples, denoiseParams(d && d.mode === "atrous" ? withoutMode(d) : d), out);
                      return out; },
+                   // the colour plane after the variance-guided filter (rm_denoise_variance; needs { moments: true }): as denoise
+                   denoiseVariance: (samples, params) => { const out = new Float32Array(w * h * 4); addon.denoiseVariance(this.ctx, fb, samples, denoiseVarianceParams(params), out); return out; },
                    // the colour plane after the G-buffer-guided a-trous filter (rm_denoise): Float32Array, colour-plane units, row 0 = bottom
                    denoise: (samples, params) => { const out = new Float32Array(w * h * 4); addon.denoise(this.ctx, fb, samples, denoiseParams(params), out); return out; },
                    // canvas.toDataURL("image/png"), index.tsx:470-476
@@ -323,10 +330,12 @@ const STRIPE_ROWS = 8;
 class ShardedRenderJobContext {
   // new ShardedRenderJobContext(devices?, flags?, samplesInFlight?) or new ShardedRenderJobContext({ devices, flags, samplesInFlight, gbuffer })
   constructor(devices = [0], flags = RM.RENDER_STRICT, samplesInFlight = 3) {
-    let gbuffer = "f32";
+    let gbuffer = "f32", moments = false;
     if (devices !== null && typeof devices === "object" && !Array.isArray(devices))
-      ({ devices = [0], flags = RM.RENDER_STRICT, samplesInFlight = 3, gbuffer = "f32" } = devices);
+      ({ devices = [0], flags = RM.RENDER_STRICT, samplesInFlight = 3, gbuffer = "f32", moments = false } = devices);
     this.gbuffer = gbuffer; this.gbufferCode = gbufferCode(gbuffer);
+    if (moments)
+      throw new RangeError("ShardedRenderJobContext: moments needs framebuffers holding the whole frame (the denoiser reads rows other GPUs hold)");
     if (!Array.isArray(devices) || devices.length < 1) throw new TypeError("ShardedRenderJobContext(devices: number[], flags?)");
     this.devices = devices.slice(); this.flags = flags;
     this.ctxs = devices.map((d) => addon.ctxCreate(d));
@@ -462,6 +471,28 @@ function denoiseParams(params) {
   return p;
 }
 
+// ---- variance-guided denoise parameters (include/hip_raymarch.h RmDenoiseVariance, rm_denoise_variance_default) ----
+const DENOISE_VARIANCE_DEFAULTS = { iterations: 3, sigma_luminance: 4.0, sigma_normal: 1.0, sigma_depth: 0.2 };
+function isVarianceMode(d) { return d === "variance" || (d !== null && typeof d === "object" && d.mode === "variance"); }
+function withoutMode(d) { const { mode, ...rest } = d; return rest; }
+// true / "variance" / undefined / null = the defaults, or an object with some of DENOISE_VARIANCE_DEFAULTS' fields (and mode: "variance");
+// checked as the library checks them
+function denoiseVarianceParams(params) {
+  const p = { ...DENOISE_VARIANCE_DEFAULTS };
+  if (params !== undefined && params !== null && params !== true && params !== "variance") {
+    if (typeof params !== "object") throw new TypeError("denoise: expected \"variance\" or an object of parameters");
+    for (const [k, v] of Object.entries(params)) {
+      if (k === "mode") { if (v !== "variance") throw new TypeError("denoise: mode " + v + " is not the variance-guided filter"); continue; }
+      if (!(k in DENOISE_VARIANCE_DEFAULTS)) throw new TypeError("denoise: unknown parameter " + k);
+      p[k] = v;
+    }
+  }
+  if (!Number.isInteger(p.iterations) || p.iterations < 0 || p.iterations > 8) throw new RangeError("denoise: iterations must be an integer in 0..8");
+  for (const k of ["sigma_luminance", "sigma_normal", "sigma_depth"])
+    if (!(typeof p[k] === "number" && Number.isFinite(p[k]) && p[k] > 0)) throw new RangeError("denoise: " + k + " must be finite and > 0");
+  return p;
+}
+
 // ---- PNG capture (index.tsx:470-476 canvas.toDataURL): RGBA8, filter 0, rows flipped to top-down ----
 const zlib = require("zlib");
 const CRC_TABLE = (() => { const t = new Uint32Array(256); for (let n = 0; n < 256; n++) { let c = n; for (let k = 0; k < 8; k++) c = c & 1 ? 0xedb88320 ^ (c >>> 1) : c >>> 1; t[n] = c >>> 0; } return t; })();
@@ -486,4 +517,5 @@ function encodePng(rgba, width, height, bottomUp = true) {
 }
 
 module.exports = { RM, addon, encodePng, Scene, CsgScene, Mandelbulb, singleSphere, DEFAULT_MATERIAL, halton, resetHalton, uniformsFromSchema, packUniforms,
-                   tileRect, RenderJobContext, ShardedRenderJobContext, doRenderJob, U_OFFSET, DENOISE_DEFAULTS, denoiseParams };
+                   tileRect, RenderJobContext, ShardedRenderJobContext, doRenderJob, U_OFFSET, DENOISE_DEFAULTS, denoiseParams,
+                   DENOISE_VARIANCE_DEFAULTS, denoiseVarianceParams };

@@ -298,6 +298,57 @@ static napi_value denoise_common(napi_env env, napi_callback_info info, bool pre
 static napi_value Denoise(napi_env env, napi_callback_info info) { return denoise_common(env, info, false); }
 static napi_value PresentDenoised(napi_env env, napi_callback_info info) { return denoise_common(env, info, true); }
 
+// The RmDenoiseVariance of a JS value: null / undefined = rm_denoise_variance_default; an object's iterations, sigma_luminance,
+// sigma_normal and sigma_depth (numbers) over the defaults; other properties are ignored.  The library checks the values.
+static bool get_denoise_variance(napi_env env, napi_value v, RmDenoiseVariance* p) {
+  rm_denoise_variance_default(p);
+  napi_valuetype t;
+  if (napi_typeof(env, v, &t) != napi_ok) return false;
+  if (t == napi_undefined || t == napi_null) return true;
+  if (t != napi_object) return false;
+  const char* names[4] = {"iterations", "sigma_luminance", "sigma_normal", "sigma_depth"};
+  for (int k = 0; k < 4; k++) {
+    bool has = false;
+    napi_value f;
+    if (napi_has_named_property(env, v, names[k], &has) != napi_ok) return false;
+    if (!has) continue;
+    double d = 0.0;
+    if (napi_get_named_property(env, v, names[k], &f) != napi_ok || napi_get_value_double(env, f, &d) != napi_ok) return false;
+    if (k == 0) p->iterations = (d >= -1e9 && d <= 1e9) ? (int)d : -1;
+    else (k == 1 ? p->sigma_luminance : k == 2 ? p->sigma_normal : p->sigma_depth) = (float)d;
+  }
+  return true;
+}
+
+// denoiseVariance(ctx, fb, samples, params, out: Float32Array(width * height * 4)) = rm_denoise_variance
+// presentDenoisedVariance(ctx, fb, samples, params, out: Uint8Array(width * height * 4)) = rm_present_denoised_variance
+static napi_value denoise_variance_common(napi_env env, napi_callback_info info, bool present) {
+  const char* who = present ? "presentDenoisedVariance" : "denoiseVariance";
+  size_t argc = 5;
+  napi_value argv[5];
+  NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+  rm_ctx* ctx = argc == 5 ? get_external<rm_ctx>(env, argv[0]) : nullptr;
+  rm_fb* fb = argc == 5 ? get_external<rm_fb>(env, argv[1]) : nullptr;
+  int32_t samples = 1;
+  RmDenoiseVariance p;
+  void* d = nullptr;
+  size_t n = 0;
+  if (!ctx || !fb || napi_get_value_int32(env, argv[2], &samples) != napi_ok || !get_denoise_variance(env, argv[3], &p) || !get_buffer(env, argv[4], &d, &n)) {
+    napi_throw_type_error(env, nullptr, present ? "presentDenoisedVariance(ctx, fb, samples, params, out: Uint8Array)" : "denoiseVariance(ctx, fb, samples, params, out: Float32Array)");
+    return nullptr;
+  }
+  const size_t need = (size_t)rm_fb_width(fb) * (size_t)rm_fb_rows(fb) * 4 * (present ? 1 : sizeof(float));
+  if (n < need) {
+    napi_throw_range_error(env, nullptr, (std::string(who) + ": out is smaller than the frame").c_str());
+    return nullptr;
+  }
+  const int rc = present ? rm_present_denoised_variance(ctx, fb, samples, &p, static_cast<uint8_t*>(d)) : rm_denoise_variance(ctx, fb, samples, &p, static_cast<float*>(d));
+  if (rc != RM_OK) return throw_rm(env, ctx, present ? "rm_present_denoised_variance" : "rm_denoise_variance");
+  return nullptr;
+}
+static napi_value DenoiseVariance(napi_env env, napi_callback_info info) { return denoise_variance_common(env, info, false); }
+static napi_value PresentDenoisedVariance(napi_env env, napi_callback_info info) { return denoise_variance_common(env, info, true); }
+
 // fbCreateStriped(ctx, width, height, stripeRows, parts, part[, gbuffer]): the stripes k with k % parts == part of a width x height image,
 // planes owned by the library (rm_fb_create_striped) -- what one GPU of a sharded frame holds
 static napi_value FbCreateStriped(napi_env env, napi_callback_info info) {
@@ -491,7 +542,8 @@ static napi_value Sizes(napi_env env, napi_callback_info) {
   NAPI_OK(napi_create_object(env, &o));
   const struct { const char* k; uint32_t v; } items[] = {
       {"RmUniforms", (uint32_t)sizeof(RmUniforms)}, {"RmSceneDesc", (uint32_t)sizeof(RmSceneDesc)}, {"RmPrim", (uint32_t)sizeof(RmPrim)},
-      {"RmMaterial", (uint32_t)sizeof(RmMaterial)}, {"RmRect", (uint32_t)sizeof(RmRect)}, {"RmSurface", (uint32_t)sizeof(RmSurface)}, {"RmDenoise", (uint32_t)sizeof(RmDenoise)}, {"abi", (uint32_t)rm_abi_version()}};
+      {"RmMaterial", (uint32_t)sizeof(RmMaterial)}, {"RmRect", (uint32_t)sizeof(RmRect)}, {"RmSurface", (uint32_t)sizeof(RmSurface)}, {"RmDenoise", (uint32_t)sizeof(RmDenoise)},
+      {"RmDenoiseVariance", (uint32_t)sizeof(RmDenoiseVariance)}, {"abi", (uint32_t)rm_abi_version()}};
   for (const auto& it : items) {
     NAPI_OK(napi_create_uint32(env, it.v, &v));
     NAPI_OK(napi_set_named_property(env, o, it.k, v));
@@ -502,7 +554,7 @@ static napi_value Sizes(napi_env env, napi_callback_info) {
 static napi_value Init(napi_env env, napi_value exports) {
   const struct { const char* name; napi_callback fn; } fns[] = {
       {"ctxCreate", CtxCreate}, {"ctxDestroy", CtxDestroy}, {"sync", Sync}, {"sceneCreate", SceneCreate}, {"sceneDestroy", SceneDestroy},
-      {"fbCreate", FbCreate}, {"fbClear", FbClear}, {"fbDestroy", FbDestroy}, {"fbDownload", FbDownload}, {"present", Present}, {"denoise", Denoise}, {"presentDenoised", PresentDenoised}, {"renderSample", RenderSample}, {"renderSamples", RenderSamples},
+      {"fbCreate", FbCreate}, {"fbClear", FbClear}, {"fbDestroy", FbDestroy}, {"fbDownload", FbDownload}, {"present", Present}, {"denoise", Denoise}, {"presentDenoised", PresentDenoised}, {"denoiseVariance", DenoiseVariance}, {"presentDenoisedVariance", PresentDenoisedVariance}, {"renderSample", RenderSample}, {"renderSamples", RenderSamples},
       {"fbCreateStriped", FbCreateStriped}, {"fbRows", FbRows}, {"setSamplesInFlight", SetSamplesInFlight}, {"presentSharded", PresentSharded}, {"presentShardedStart", PresentShardedStart}, {"presentShardedFinish", PresentShardedFinish},
       {"sizes", Sizes}};
   for (const auto& f : fns) {

@@ -36,6 +36,7 @@ EXPORTS = [
     "rm_probe", "rm_probe_camera", "rm_probe_rng", "rm_probe_math", "rm_assemble_striped", "rm_assemble_striped_bytes", "rm_present", "rm_present_planes", "rm_present_device", "rm_present_rows", "rm_pack_present_rows", "rm_ctx_last_pipeline", "rm_present_sharded", "rm_present_sharded_start", "rm_present_sharded_finish", "rm_present_striped_rows", "rm_debug_cull_cell",
     "rm_fb_create_fmt", "rm_fb_create_striped_fmt", "rm_fb_wrap_fmt", "rm_fb_gbuffer", "rm_fb_download_raw", "rm_fb_upload_raw",
     "rm_denoise_default", "rm_denoise", "rm_denoise_device", "rm_present_denoised",
+    "rm_fb_has_moments", "rm_denoise_variance_default", "rm_denoise_variance", "rm_denoise_variance_device", "rm_present_denoised_variance",
 ]
 
 # G-buffer formats of a framebuffer (include/hip_raymarch.h RM_GBUFFER_*): "f32" (the default: the software GL stack's planes, which the
@@ -73,6 +74,50 @@ def denoise_params(params=None) -> abi.RmDenoise:
         if not (math.isfinite(v) and v > 0.0):
             raise ValueError(f"denoise: {name} must be finite and > 0")
     return p
+
+
+def denoise_variance_params(params=None) -> abi.RmDenoiseVariance:
+    """An abi.RmDenoiseVariance from None / True / "variance" (the defaults, rm_denoise_variance_default), a dict of some of its
+    fields over the defaults (a "mode": "variance" entry allowed), or an abi.RmDenoiseVariance.  Checked as the library checks it
+    (iterations in 0..8, every sigma finite and > 0, reserved 0): ValueError otherwise."""
+    if isinstance(params, abi.RmDenoiseVariance):
+        p = params
+    else:
+        if params is None or params is True or params == "variance":
+            fields = {}
+        elif isinstance(params, dict):
+            fields = {k: v for k, v in params.items() if k != "mode"}
+            if params.get("mode", "variance") != "variance":
+                raise ValueError(f"denoise: mode {params['mode']!r} is not the variance-guided filter")
+        else:
+            raise ValueError(f"denoise: expected True, \"variance\", a dict or abi.RmDenoiseVariance, got {params!r}")
+        unknown = set(fields) - set(abi.DENOISE_VARIANCE_DEFAULTS)
+        if unknown:
+            raise ValueError(f"denoise: unknown parameter(s) {sorted(unknown)}; known: {sorted(abi.DENOISE_VARIANCE_DEFAULTS)}")
+        p = abi.RmDenoiseVariance(**{**abi.DENOISE_VARIANCE_DEFAULTS, **fields})
+    if not 0 <= p.iterations <= 8:
+        raise ValueError("denoise: iterations must be in 0..8")
+    for name in ("sigma_luminance", "sigma_normal", "sigma_depth"):
+        v = getattr(p, name)
+        if not (math.isfinite(v) and v > 0.0):
+            raise ValueError(f"denoise: {name} must be finite and > 0")
+    if p.reserved != 0:
+        raise ValueError("denoise: reserved must be 0")
+    return p
+
+
+def denoise_mode(denoise):
+    """The filter a present's `denoise` asks for: ("variance", abi.RmDenoiseVariance) for "variance", an abi.RmDenoiseVariance or
+    a dict with "mode": "variance"; ("atrous", abi.RmDenoise) for every form denoise_params takes, and a dict with
+    "mode": "atrous"."""
+    if isinstance(denoise, abi.RmDenoiseVariance) or (isinstance(denoise, str) and denoise == "variance") or \
+            (isinstance(denoise, dict) and denoise.get("mode") == "variance"):
+        return "variance", denoise_variance_params(denoise)
+    if isinstance(denoise, dict) and "mode" in denoise:
+        if denoise["mode"] != "atrous":
+            raise ValueError(f"denoise: unknown mode {denoise['mode']!r} (\"atrous\" or \"variance\")")
+        denoise = {k: v for k, v in denoise.items() if k != "mode"}
+    return "atrous", denoise_params(denoise)
 
 
 def cull_cell(scene, centre, radius: float, margin: float = 0.0):
@@ -208,6 +253,11 @@ def load_library(path=None):
         "rm_denoise": (ip, [vp, vp, ip, C.POINTER(abi.RmDenoise), fp]),
         "rm_denoise_device": (ip, [vp, vp, ip, C.POINTER(abi.RmDenoise), vp, vp]),
         "rm_present_denoised": (ip, [vp, vp, ip, C.POINTER(abi.RmDenoise), C.POINTER(C.c_uint8)]),
+        "rm_fb_has_moments": (ip, [vp]),
+        "rm_denoise_variance_default": (None, [C.POINTER(abi.RmDenoiseVariance)]),
+        "rm_denoise_variance": (ip, [vp, vp, ip, C.POINTER(abi.RmDenoiseVariance), fp]),
+        "rm_denoise_variance_device": (ip, [vp, vp, ip, C.POINTER(abi.RmDenoiseVariance), vp, vp]),
+        "rm_present_denoised_variance": (ip, [vp, vp, ip, C.POINTER(abi.RmDenoiseVariance), C.POINTER(C.c_uint8)]),
     }
     for name, (res, args) in sig.items():
         if name.startswith("rm_debug_") and not hasattr(lib, name) and os.environ.get("RM_LIB"):
@@ -384,6 +434,12 @@ class Context:
         p = denoise_params(params)
         self._check(self.lib.rm_denoise_device(self.h, fb.h, int(samples), C.byref(p), C.c_void_p(out_ptr), C.c_void_p(stream) if stream else None))
 
+    def denoise_variance_device(self, fb: "Framebuffer", samples: int, out_ptr: int, params=None, stream: Optional[int] = None):
+        """rm_denoise_variance_device: Framebuffer.denoise_variance into rows x W float4 of device memory at out_ptr, enqueued on
+        `stream` (None = the context's); no host wait."""
+        p = denoise_variance_params(params)
+        self._check(self.lib.rm_denoise_variance_device(self.h, fb.h, int(samples), C.byref(p), C.c_void_p(out_ptr), C.c_void_p(stream) if stream else None))
+
     def present_rows(self, fb: "Framebuffer", samples: int, out_ptr: int, stream: Optional[int] = None):
         """Tone-map the rows `fb` holds (no depth of field) into DEVICE memory (rows*width*4 bytes), asynchronous."""
         self._check(self.lib.rm_present_rows(self.h, fb.h, int(samples), C.c_void_p(out_ptr), C.c_void_p(stream) if stream else None))
@@ -432,9 +488,11 @@ class Context:
     def create_scene(self, scene: Scene) -> "SceneHandle":
         return SceneHandle(self, scene)
 
-    def create_framebuffer(self, width: int, height: int, row_begin: int = 0, row_count: Optional[int] = None, gbuffer: str = "f32") -> "Framebuffer":
-        """gbuffer: "f32" (default) or "f16", the reference's half-precision normal + DoF radius and albedo + depth planes."""
-        return Framebuffer(self, width, height, row_begin, height if row_count is None else row_count, gbuffer=gbuffer)
+    def create_framebuffer(self, width: int, height: int, row_begin: int = 0, row_count: Optional[int] = None, gbuffer: str = "f32",
+                           moments: bool = False) -> "Framebuffer":
+        """gbuffer: "f32" (default) or "f16", the reference's half-precision normal + DoF radius and albedo + depth planes.
+        moments: also keep the per-pixel luminance moments plane (RM_FB_MOMENTS) the variance-guided denoiser reads."""
+        return Framebuffer(self, width, height, row_begin, height if row_count is None else row_count, gbuffer=gbuffer, moments=moments)
 
     def create_striped_framebuffer(self, width, height, stripe_rows, parts, part, color_ptr=None, normal_ptr=None, albedo_ptr=None,
                                    gbuffer: str = "f32") -> "Framebuffer":
@@ -501,8 +559,12 @@ class SceneHandle:
 
 
 class Framebuffer:
-    def __init__(self, ctx: Context, width, height, row_begin, row_count, wrap=None, striped=None, gbuffer: str = "f32"):
+    def __init__(self, ctx: Context, width, height, row_begin, row_count, wrap=None, striped=None, gbuffer: str = "f32", moments: bool = False):
         fmt = gbuffer_code(gbuffer)
+        if moments:
+            if wrap is not None or striped is not None:
+                raise ValueError("moments=True is for framebuffers the library allocates whole (Context.create_framebuffer)")
+            fmt |= abi.RM_FB_MOMENTS
         self.ctx = ctx
         self.width, self.height, self.row_begin, self.row_count = width, height, row_begin, row_count
         self.gbuffer = gbuffer
@@ -519,20 +581,26 @@ class Framebuffer:
                                               C.c_void_p(wrap[1] or 0), C.c_void_p(wrap[2] or 0), fmt, C.byref(h)))
         self.h = h
 
+    @property
+    def moments(self) -> bool:
+        """True when the framebuffer keeps the moments plane (rm_fb_has_moments)."""
+        return bool(self.ctx.lib.rm_fb_has_moments(self.h))
+
     def plane_dtype(self, plane: int):
         """numpy dtype of a plane as stored: float32, or float16 for the G-buffer planes of an "f16" framebuffer."""
-        return np.float16 if (plane != abi.RM_PLANE_COLOR and self.gbuffer == "f16") else np.float32
+        return np.float16 if (plane in (abi.RM_PLANE_NORMAL_DOF, abi.RM_PLANE_ALBEDO_DEPTH) and self.gbuffer == "f16") else np.float32
 
     def download_raw(self, plane: int = abi.RM_PLANE_COLOR) -> np.ndarray:
-        """A plane as stored ([rows, W, 4] of plane_dtype(plane)): the half bits of an "f16" G-buffer plane, not widened."""
-        out = np.empty((self.row_count, self.width, 4), self.plane_dtype(plane))
+        """A plane as stored ([rows, W, 4] of plane_dtype(plane)): the half bits of an "f16" G-buffer plane, not widened.
+        Plane 3 (abi.RM_PLANE_MOMENTS) is [rows, W, 2] float32: (sum l, sum l^2)."""
+        out = np.empty((self.row_count, self.width, 2 if plane == abi.RM_PLANE_MOMENTS else 4), self.plane_dtype(plane))
         self.ctx._check(self.ctx.lib.rm_fb_download_raw(self.h, plane, out.ctypes.data_as(C.c_void_p), out.nbytes))
         return out
 
     def upload_raw(self, plane: int, data: np.ndarray):
         """Stores [rows, W, 4] of plane_dtype(plane) into a plane as they are."""
         a = np.ascontiguousarray(data, self.plane_dtype(plane))
-        assert a.shape == (self.row_count, self.width, 4)
+        assert a.shape == (self.row_count, self.width, 2 if plane == abi.RM_PLANE_MOMENTS else 4)
         self.ctx._check(self.ctx.lib.rm_fb_upload_raw(self.h, plane, a.ctypes.data_as(C.c_void_p), a.nbytes))
 
     def clear(self):
@@ -560,13 +628,16 @@ class Framebuffer:
 
     def present(self, samples: int, denoise=None) -> np.ndarray:
         """Tone-mapped RGBA8 image of the whole frame (display.frag:16-64), row 0 = bottom.  `denoise`: None (the default: the
-        accumulated colour as it is), or True / a dict / abi.RmDenoise to present the denoised colour (rm_present_denoised)."""
+        accumulated colour as it is), or True / a dict / abi.RmDenoise to present the denoised colour (rm_present_denoised); or
+        "variance" / abi.RmDenoiseVariance / a dict with "mode": "variance" for the variance-guided filter
+        (rm_present_denoised_variance; the framebuffer needs moments=True)."""
         out = np.empty((self.row_count, self.width, 4), np.uint8)
         if denoise is None:
             self.ctx._check(self.ctx.lib.rm_present(self.ctx.h, self.h, int(samples), out.ctypes.data_as(C.POINTER(C.c_uint8))))
-        else:
-            p = denoise_params(denoise)
-            self.ctx._check(self.ctx.lib.rm_present_denoised(self.ctx.h, self.h, int(samples), C.byref(p), out.ctypes.data_as(C.POINTER(C.c_uint8))))
+            return out
+        mode, p = denoise_mode(denoise)
+        fn = self.ctx.lib.rm_present_denoised_variance if mode == "variance" else self.ctx.lib.rm_present_denoised
+        self.ctx._check(fn(self.ctx.h, self.h, int(samples), C.byref(p), out.ctypes.data_as(C.POINTER(C.c_uint8))))
         return out
 
     def denoise(self, samples: int, params=None) -> np.ndarray:
@@ -575,4 +646,13 @@ class Framebuffer:
         p = denoise_params(params)
         out = np.empty((self.row_count, self.width, 4), np.float32)
         self.ctx._check(self.ctx.lib.rm_denoise(self.ctx.h, self.h, int(samples), C.byref(p), _fp(out)))
+        return out
+
+    def denoise_variance(self, samples: int, params=None) -> np.ndarray:
+        """The colour plane after the variance-guided filter (rm_denoise_variance; the framebuffer needs moments=True): float32
+        [rows, W, 4] in colour-plane units, row 0 = bottom.  `params`: None / True (the defaults), a dict of some
+        RmDenoiseVariance fields, or abi.RmDenoiseVariance."""
+        p = denoise_variance_params(params)
+        out = np.empty((self.row_count, self.width, 4), np.float32)
+        self.ctx._check(self.ctx.lib.rm_denoise_variance(self.ctx.h, self.h, int(samples), C.byref(p), _fp(out)))
         return out
