@@ -25,7 +25,15 @@ rm_render_samples call.  --yield-interval 1 presents and gathers after every
 sample, like the live loop (index.tsx:158-169).  Total work is fixed => strong
 scaling.
 
-Rank 0 prints ONE JSON line.  `roofline` is the fp32-VALU roofline of the
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the steps,
+writes --dump-outputs and prints the line: everything else it can measure or
+check is behind --full (off by default), which runs what follows and leaves its
+fields null otherwise.  One GPU: the hardware counters of this run
+(live_counters), the kernel time and the `roofline`, the CPU baseline and the
+`workloads` legs.  Sharded: the present-every-sample leg and the frame check
+(--check-frame asks for the check alone).
+
+`roofline` is the fp32-VALU roofline of the
 pixel kernel (the path has no contraction, so no MFMA; HBM traffic is ~100 B
 per ~2e4 flops): achieved = algorithmic flops per launch / HIP-event kernel
 time, the flops instrumented over EVERY row of the frame by the counting oracle
@@ -202,7 +210,7 @@ def counters_entry(key, strict, pipeline, windowed, gl_stack=0):
 
 # ---- hardware counters measured by THIS run (round 6) --------------------------------------------------------------------------
 # Until round 5 `traffic`, `frac_executed`, `valu_issue_busy` and `fma_share` were replayed from the builder's own rocprofv3 passes
-# (profiles/<round>_counters.json).  The default one-GPU invocation now measures them itself, before it touches the GPU: three
+# (profiles/<round>_counters.json).  The one-GPU headline with --full now measures them itself, before it touches the GPU: three
 # child processes -- rocprofv3 --pmc <group> --kernel-trace -- python3 bench.py --counter-child -- each rendering a few frames of
 # the headline and of every `workloads` leg; a --pmc pass carries --kernel-trace only, FETCH_SIZE and WRITE_SIZE have a pass each
 # (MI355X_MICROARCH.md: the TCC block has 4 slots, FETCH_SIZE takes 3, WRITE_SIZE 2), and the gfx950 correction of FETCH_SIZE
@@ -379,6 +387,9 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline, measure and check everything else: on one GPU this run's hardware counters, the kernel time and "
+                         "the roofline, the CPU baseline and the `workloads` legs; sharded, the present-every-sample leg and the frame check")
     ap.add_argument("--workload", default="c3b", choices=list(WORKLOADS))
     ap.add_argument("--rows", default="", help="render only image rows A:B of the frame (e.g. one shard of C4/C5 on one GPU)")
     ap.add_argument("--stripe-of", type=int, default=0, help="one GPU standing in for rank 0 of an N-way split: render its 8-row stripes of the frame (no collective)")
@@ -387,7 +398,7 @@ def main():
                                                                               "reference's bits as SwiftShader renders the unmodified shader); implies --strict --megakernel")
     ap.add_argument("--megakernel", action="store_true", help="force the one-thread-one-pixel kernel (default: the library picks per job)")
     ap.add_argument("--wavefront", action="store_true", help="the wavefront pipeline (the tests' second implementation: loads tests/_xcheck/libhip_raymarch_xcheck.so instead of the product library)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--overlap-leg", action="store_true",
                     help="also time the same K steps with 3 samples in flight on this one GPU (reported as `overlap`, never as `value`)")
     ap.add_argument("--in-flight", type=int, default=0,
@@ -405,17 +416,19 @@ def main():
     ap.add_argument("--no-far-jump", action="store_true", help="RM_RENDER_NO_FAR_JUMP: march escaping rays step by step (measurement switch, same bits)")
     ap.add_argument("--no-cull", action="store_true", help="RM_RENDER_NO_CULL: fold every row of a primitive table at every point (measurement switch, same bits)")
     ap.add_argument("--counter-child", action="store_true", help="(internal) render a few frames of every leg and exit: what live_counters profiles")
-    ap.add_argument("--dump-counters", default="", help="write this run's measured counters to the given file in the format of profiles/<round>_counters.json (what a later run replays when it cannot measure)")
-    ap.add_argument("--no-live-counters", action="store_true", help="do not measure the hardware counters in this run (replay profiles/<round>_counters.json)")
-    ap.add_argument("--no-workloads", action="store_true", help="skip the `workloads` legs (the other BASELINE configurations and the two parity builds of the headline, a few steps each)")
-    ap.add_argument("--no-check-frame", action="store_true", help="sharded runs check the assembled frame by default (see --check-frame); this skips it")
+    ap.add_argument("--dump-counters", default="", help="with --full: write this run's measured counters to the given file in the format of profiles/<round>_counters.json (what a later run replays when it cannot measure)")
+    ap.add_argument("--no-live-counters", action="store_true", help="--full without measuring the hardware counters in this run (replay profiles/<round>_counters.json)")
+    ap.add_argument("--no-workloads", action="store_true", help="--full without the `workloads` legs (the other BASELINE configurations and the two parity builds of the headline, a few steps each)")
+    ap.add_argument("--no-check-frame", action="store_true", help="sharded runs with --full check the assembled frame (see --check-frame); this skips it")
     ap.add_argument("--dump-outputs", default="", metavar="DIR",
                     help="after the timed steps, write the three fp32 planes the job accumulated (what its caller receives) as DIR/<plane>.npy: "
                          "every pixel of this rank's rows, or a fixed seeded sample of DUMP_PIXELS of them (DIR/pixel_index.npy) when they are more")
     ap.add_argument("--check-frame", action="store_true",
                     help="sharded runs: after the timed legs rank 0 renders the same samples on ONE framebuffer, presents it and compares "
-                         "the bytes with the frame it assembled from the gathered rows (reported as `frame_check`)")
+                         "the bytes with the frame it assembled from the gathered rows (reported as `frame_check`; --full does it unless --no-check-frame)")
     args = ap.parse_args()
+    if args.dump_counters and not args.full:
+        ap.error("--dump-counters writes the counters --full measures: give --full as well")
     if args.wavefront and not os.environ.get("RM_LIB"):
         # the wavefront pipeline is not in the product library (round 5): it is timed from the tests' cross-check build of the same sources
         os.environ["RM_LIB"] = os.path.join(ROOT, "tests", "_xcheck", "libhip_raymarch_xcheck.so")
@@ -436,7 +449,7 @@ def main():
     live, live_note = None, None
     default_run = (world == 1 and os.environ.get("RM_BENCH_FORCE_DIST") != "1" and args.workload == "c3b" and not args.strict and not args.rows and args.stripe_of <= 1
                    and not args.wavefront and not args.dof and not args.no_far_jump and not args.no_cull and not args.gl_stack)
-    if default_run and not args.no_live_counters and not under_a_profiler():
+    if args.full and default_run and not args.no_live_counters and not under_a_profiler():
         live, live_note = live_counters()  # child processes, before this one touches the GPU
 
     if live and args.dump_counters:
@@ -601,6 +614,7 @@ def main():
     elapsed = regions[len(regions) // 2]
     if args.dump_outputs and rank == 0:  # before anything below renders into the same framebuffer
         dump_outputs(args.dump_outputs, fb, abi)
+    pipeline = ctx.last_pipeline()  # what the library dispatched for this job (rm_ctx_last_pipeline), not a re-derivation of its rule
 
     px_frame = W * row_count if (rows_window is not None or stripes is not None) else W * H
     ms_per_step = elapsed / args.steps * 1e3
@@ -612,7 +626,7 @@ def main():
     # for information, never `value`: the same K steps with a present + gather after EVERY sample (the live loop's
     # sampleYieldInterval = 1), four single-sample launches in flight
     every_sample = None
-    if sharded and yield_interval > 1:
+    if args.full and sharded and yield_interval > 1:
         ctx.set_samples_in_flight(4)
         run(min(args.warmup, 8) or 1, 1)
         drain()
@@ -624,7 +638,7 @@ def main():
     # --check-frame: the canvas rank 0 was last presented against the same samples rendered and presented on ONE framebuffer
     # here (the accumulation per pixel is in sample order either way: the bytes must be identical)
     frame_check = None
-    if sharded and not args.no_check_frame:  # (on by default since round 6: the first run on a real node proves its own frame)
+    if sharded and (args.check_frame or (args.full and not args.no_check_frame)):  # (the first --full run on a real node proves its own frame)
         fb.start_present(samples[0])
         canvas = fb.finish_present()
         torch.cuda.synchronize()
@@ -653,25 +667,27 @@ def main():
         ctx.set_samples_in_flight(in_flight)
         overlap = {"samples_in_flight": 3, "value": px_frame * args.steps / e1 / 1e6, "ms_per_step": e1 / args.steps * 1e3}
 
-    # kernel time of every rank's launch: HIP events on the launch stream
-    tile = None  # the whole window this rank's framebuffer holds
-    u = J.uniforms_from_schema(schema, (0.5, 1.0 / 3.0))
-    n_timed = max(3, min(args.steps, 20))
-    ctx.render_timed(scene, fb, u, 2, tile, flags | abi.RM_RENDER_NO_OVERLAP)  # let the cost order of this job settle
-    kernel_ms = ctx.render_timed(scene, fb, u, n_timed, tile, flags | abi.RM_RENDER_NO_OVERLAP)
-    pipeline = ctx.last_pipeline()  # what the library dispatched for this job (rm_ctx_last_pipeline), not a re-derivation of its rule
-    kernel_ms_per_rank = [kernel_ms]
-    if world > 1:
-        t = torch.zeros(world, dtype=torch.float64, device=dev)
-        t[rank] = kernel_ms
-        dist.all_reduce(t)
-        kernel_ms_per_rank = [float(v) for v in t.tolist()]
+    # --full: kernel time of every rank's launch, HIP events on the launch stream
+    kernel_ms = None
+    if args.full:
+        tile = None  # the whole window this rank's framebuffer holds
+        u = J.uniforms_from_schema(schema, (0.5, 1.0 / 3.0))
+        n_timed = max(3, min(args.steps, 20))
+        ctx.render_timed(scene, fb, u, 2, tile, flags | abi.RM_RENDER_NO_OVERLAP)  # let the cost order of this job settle
+        kernel_ms = ctx.render_timed(scene, fb, u, n_timed, tile, flags | abi.RM_RENDER_NO_OVERLAP)
+        pipeline = ctx.last_pipeline()
+        kernel_ms_per_rank = [kernel_ms]
+        if world > 1:
+            t = torch.zeros(world, dtype=torch.float64, device=dev)
+            t[rank] = kernel_ms
+            dist.all_reduce(t)
+            kernel_ms_per_rank = [float(v) for v in t.tolist()]
 
-    # The other claims of DESIGN.md section 6 on the same line (default invocation only; a few steps each): the other BASELINE
+    # --full: the other claims of DESIGN.md section 6 on the same line (the one-GPU headline only; a few steps each): the other BASELINE
     # configurations in the fast build, and the headline in the two parity builds -- strict (the oracle's bits) and the GL
     # stack's arithmetic with its own tan (rm_ctx_set_gl_stack(ctx, 2): the reference's bits as SwiftShader renders them).
     workloads = None
-    if (world == 1 and not force_dist and rows_window is None and stripes is None and args.workload == "c3b" and not args.strict
+    if (args.full and world == 1 and not force_dist and rows_window is None and stripes is None and args.workload == "c3b" and not args.strict
             and not args.no_workloads and not args.wavefront and not args.dof):
         workloads = {}
         legs = (("c2", "fast", 0, 8), ("c3a", "fast", 0, 5), ("c4", "fast", 0, 5), ("c5", "fast", 0, 3), ("c3b", "strict", 0, 5), ("c3b", "glstack", 2, 3))
@@ -728,19 +744,17 @@ def main():
                       "payload": payload, "gathered_bytes_per_present": int(fb.gathered_bytes_per_present()) if hasattr(fb, "gathered_bytes_per_present") else None,
                       "frame_check": frame_check, "frame_check_samples": samples[0] if frame_check is not None else None}
 
-    out = None
-    if rank == 0:
+    cpu = roof = None
+    if rank == 0 and args.full:
         rows_held = (np.arange(rows_window[0], rows_window[1]) if rows_window is not None else shard.owned_rows(H, stripes[0], stripes[1]) if stripes is not None
                      else shard.owned_rows(H, world, rank))
         px_launch = len(rows_held) * W
         flops_launch, flops_px, fixture = instrumented_flops(args.workload, rows_held)
         useful_launch, useful_px, useful_fixture = instrumented_flops(args.workload + "_pruned", rows_held)  # ... of the PRUNED algorithm (frac_useful)
-        cpu = None
         if world == 1 and not args.no_cpu_baseline:
             cpu = cpu_baseline(sc, schema)
             cpu["reference_gl"] = reference_gl(args.workload)
         nominal_px = NOMINAL_FLOPS_PX[args.workload]
-        roof = None
         # NOT measured in this run: replayed from the builder's separate rocprofv3 --pmc runs of this command, kept in
         # profiles/<round>_counters.json with the hash of the kernel sources they were measured on (withheld when the sources changed)
         traffic = executed = counters_file = counters_from = issue_busy = fma_share = None
@@ -791,6 +805,8 @@ def main():
                             "valu_issue_busy of the issue slots taken, that is what bounds it.  issue_accounted (round 6) = (VALU + 3.1 TRANS + 2.1 LDS instructions) / kernel time / 1.03e12: the share of the "
                             "kernel's time its instruction stream accounts for at what instructions cost on this chip in such a mix (tools/ubench/fold_rate.hip: a transcendental in a group of four "
                             "4.1 slots, a ds_read_b128 2.1, a dense fp32 stream 1.03e12 slots/s); the rest is waves that are not there to issue"}
+    out = None
+    if rank == 0:
         out = {
             "metric": "Mpixels/sec at 3840x2160 Mandelbulb" if args.workload in ("c3b", "c3a") else "Mpixels/sec",
             "value": value, "unit": "Mpixels/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,

@@ -2340,7 +2340,7 @@ def test_bench_under_the_drivers_launcher_with_one_rank(tmp_path):
         port = s.getsockname()[1]
     env = dict(os.environ, RM_BENCH_FORCE_DIST="1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
-           "--master-port", str(port), os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "2", "--no-cpu-baseline"]
+           "--master-port", str(port), os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "2", "--full", "--no-cpu-baseline"]
     try:
         r = subprocess.run(cmd, capture_output=True, text=True, timeout=500, env=env)
     except subprocess.TimeoutExpired as e:
@@ -2362,15 +2362,15 @@ def test_bench_with_four_ranks_sharing_this_gpu(tmp_path):
     RM_BENCH_BACKEND=gloo (RCCL refuses two ranks on one device; the gathered rows travel through host memory instead).
     Everything else is the N > 1 path as it runs on a node: four processes, the rendezvous, each rank's stripes, sample
     batches, a present and a gather per yield, the assembly on rank 0, the barrier and the max over ranks, the
-    present-every-sample leg, one JSON line from rank 0 -- and the assembled frame is checked against a one-framebuffer
-    render of the same samples (--check-frame)."""
+    present-every-sample leg, one JSON line from rank 0 -- and, with --full, the assembled frame is checked against a
+    one-framebuffer render of the same samples (the frame check)."""
     import json
     import subprocess
     import sys
 
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, RM_BENCH_SHARE_GPU="1", RM_BENCH_BACKEND="gloo")
-    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "4", "--steps", "16", "--warmup", "8", "--no-cpu-baseline"]  # the driver's bare command: no flag asks for the check
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "4", "--steps", "16", "--warmup", "8", "--full", "--no-cpu-baseline"]  # --full: no flag of its own asks for the check
     try:
         r = subprocess.run(cmd, capture_output=True, text=True, timeout=500, env=env)
     except subprocess.TimeoutExpired as e:
@@ -2382,7 +2382,7 @@ def test_bench_with_four_ranks_sharing_this_gpu(tmp_path):
     out = json.loads(lines[0])
     assert out["n_gpus"] == 4 and out["steps"] == 16 and out["value"] > 50.0 and out["config"]["sample_yield_interval"] == 8
     assert out["config"]["rows_per_gpu"] in (536, 544) and out["present_every_sample"]["value"] > 10.0
-    # the frame check runs by default on a sharded run (round 6): the frame rank 0 assembled from the four ranks' gathered rows is,
+    # the frame check runs on a sharded --full run: the frame rank 0 assembled from the four ranks' gathered rows is,
     # byte for byte, the present of the same 48 samples rendered on one framebuffer -- and the line says what the collective saw
     assert out["frame_check"] is True
     c = out["collective"]
@@ -2392,7 +2392,7 @@ def test_bench_with_four_ranks_sharing_this_gpu(tmp_path):
 
 
 def test_bench_default_line_carries_every_workload(tmp_path):
-    """`python bench.py` as the driver runs it at N = 1 (here with fewer steps and without the CPU leg): next to the headline the
+    """`python bench.py --full` at N = 1 (here with fewer steps and without the CPU leg): next to the headline the
     line carries a `workloads` object -- C2, C3a, C4, C5 in the fast build, the headline in the strict build and in the GL stack's
     arithmetic (the reference's bits) -- each leg with its step time, its kernel time and its rate; the ordering of the builds
     is what DESIGN.md section 6 says it is."""
@@ -2401,7 +2401,7 @@ def test_bench_default_line_carries_every_workload(tmp_path):
     import sys
 
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    cmd = [sys.executable, os.path.join(root, "bench.py"), "--steps", "10", "--warmup", "3", "--repeats", "1", "--no-cpu-baseline"]  # (with this run's own rocprofv3 passes: the default)
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--steps", "10", "--warmup", "3", "--repeats", "1", "--full", "--no-cpu-baseline"]  # (with this run's own counter passes: --full's default)
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{") and '"metric"' in ln]
@@ -2431,14 +2431,14 @@ def test_bench_default_line_carries_every_workload(tmp_path):
 
 
 def test_bench_default_line_replays_its_counters_when_it_cannot_measure():
-    """The same default invocation on a box where the counters cannot be measured (forced here: RM_BENCH_FAIL_LIVE_COUNTERS=1): the line replays
+    """The same --full invocation on a box where the counters cannot be measured (forced here: RM_BENCH_FAIL_LIVE_COUNTERS=1): the line replays
     profiles/<round>_counters.json -- valid for these kernel sources by its hash -- and says so, with the reason."""
     import json
     import subprocess
     import sys
 
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    cmd = [sys.executable, os.path.join(root, "bench.py"), "--steps", "6", "--warmup", "2", "--repeats", "1", "--no-cpu-baseline"]
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--steps", "6", "--warmup", "2", "--repeats", "1", "--full", "--no-cpu-baseline"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=dict(os.environ, RM_BENCH_FAIL_LIVE_COUNTERS="1"))
     assert r.returncode == 0, r.stderr[-2000:]
     out = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{") and '"metric"' in ln][-1])
@@ -2447,3 +2447,33 @@ def test_bench_default_line_replays_its_counters_when_it_cannot_measure():
     assert 0.2 < out["roofline"]["frac_executed"] < 0.6 and out["roofline"]["traffic"] > 7e8
     for key, leg in out["workloads"].items():
         assert leg["counters_from"].startswith("profiles/") and leg["frac_executed"] is not None and leg["issue_accounted"] is not None, (key, leg)
+
+
+def test_bench_plain_run_times_the_headline_only(tmp_path):
+    """`python bench.py` without --full: set-up, warm-up, the timed steps, --dump-outputs and the line -- no counter passes, no
+    kernel timing, no CPU baseline, no `workloads` legs -- and the headline fields mean what they do with --full."""
+    import json
+    import subprocess
+    import sys
+    import time
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    steps, warmup = 20, 5
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", str(warmup), "--dump-outputs", str(tmp_path / "out")]
+    t0 = time.perf_counter()
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=300)
+    wall = time.perf_counter() - t0
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{") and '"metric"' in ln]
+    assert len(lines) == 1, r.stdout[-2000:]
+    out = json.loads(lines[0])
+    assert out["metric"] == "Mpixels/sec at 3840x2160 Mandelbulb" and out["unit"] == "Mpixels/s" and out["higher_is_better"] is True and out["dtype"] == "f32"
+    assert out["n_gpus"] == 1 and out["steps"] == steps and out["warmup"] == warmup and out["value"] > 100.0
+    assert abs(out["value"] - 3840 * 2160 / out["ms_per_step"] / 1e3) < 1e-6 * out["value"]
+    assert out["spread"]["regions"] == 3 and out["config"]["pipeline"].startswith(("megakernel", "wavefront"))
+    for key in ("roofline", "cpu_baseline", "workloads", "overlap", "present_every_sample", "frame_check", "collective"):
+        assert out[key] is None, key
+    for name in ("color", "normal_dof", "albedo_depth", "pixel_index"):
+        assert (tmp_path / "out" / (name + ".npy")).exists(), name
+    # what the run spends outside its warm-up and timed steps (start-up, set-up, the first launches, the dump, the exit): at most 30 s
+    assert wall - (steps + warmup) * out["ms_per_step"] * 1e-3 < 30.0, wall

@@ -723,3 +723,13 @@ def test_bench_counters_fall_back_to_the_replay_file_and_that_file_matches_the_s
         assert ent["hbm_bytes_per_pixel"] > 25.0 and 0.4 < ent["lanes_active"] <= 1.0 and ent["sq_insts_valu_per_frame"] > 1e6
         acc = bench.issue_accounted(ent, 1.0)  # (per millisecond of kernel time: a number, not a claim)
         assert acc is not None and acc > 0.0
+
+
+def test_bench_dump_counters_asks_for_full(tmp_path):
+    """A plain bench.py run measures no counters, so --dump-counters without --full is refused before anything runs (and writes nothing)."""
+    import subprocess
+    import sys
+
+    target = tmp_path / "counters.json"
+    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--dump-counters", str(target)], capture_output=True, text=True, timeout=60)
+    assert r.returncode == 2 and "--full" in r.stderr and not target.exists(), r.stderr
