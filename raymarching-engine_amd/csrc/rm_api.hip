@@ -20,7 +20,10 @@
 #include "rm_params.hpp"
 
 #ifndef RM_WITH_WAVEFRONT
-#define RM_WITH_WAVEFRONT 0  // 1: the tests' cross-check build (see "the wavefront pipeline" below)
+#define RM_WITH_WAVEFRONT 0  // 1: the tests' cross-check build (rm_wavefront_host.inc)
+#endif
+#if RM_WITH_WAVEFRONT
+#include "rm_wavefront_host.inc"
 #endif
 
 #define RM_SP_MAX 8
@@ -38,6 +41,126 @@ hipError_t rm_gl_launch_present_rows(const float4* color, long long pixels, floa
 hipError_t rm_gl_set_native_tan(int on, hipStream_t stream);
 }
 
+// Samples in flight (pixel-kernel path, full mode): sample n renders on side stream n % depth into a staging
+// buffer and is blended into the planes, in order, by a small kernel on the context's stream; the next samples
+// render meanwhile.  One sample alone leaves the chip partly idle: a ray is a serial chain of ~2e5 instructions
+// (~1 ms), so every launch ends in a tail and a small shard never fills the SIMDs.
+struct SamplesInFlight {
+  int depth = 3;  // RM_SAMPLES_IN_FLIGHT, rm_ctx_set_samples_in_flight
+  hipStream_t stream[RM_SP_MAX] = {};
+  hipEvent_t done[RM_SP_MAX] = {}, free[RM_SP_MAX] = {};  // slot's render finished; the blend that read its staging finished
+  float4* stage[RM_SP_MAX] = {};
+  size_t elems = 0;  // float4 elements of every slot's staging buffer (3 planes x tile pixels x samples of a batch)
+  unsigned int next = 0;
+  bool ready = false;
+
+  hipError_t ensure_slots(int n) {
+    hipError_t e;
+    // side streams are made as the depth asks for them, not all RM_SP_MAX at once: the HIP runtime deals a process's streams
+    // over a few hardware queues, and streams that share a queue serialise (measured: 0.59 instead of 0.42 ms per sample on a 1/8 shard)
+    for (int s = 0; s < n; s++) {
+      if (stream[s]) continue;
+      if ((e = hipStreamCreateWithFlags(&stream[s], hipStreamNonBlocking)) != hipSuccess) return e;
+      if ((e = hipEventCreateWithFlags(&done[s], hipEventDisableTiming)) != hipSuccess) return e;
+      if ((e = hipEventCreateWithFlags(&free[s], hipEventDisableTiming)) != hipSuccess) return e;
+    }
+    ready = true;
+    return hipSuccess;
+  }
+  // frees the staging buffers (the caller has synchronised the device, or is giving the buffers up)
+  void release_staging() {
+    for (float4*& p : stage) { if (p) (void)hipFree(p); p = nullptr; }
+    elems = 0;
+  }
+  // staging of `need` float4 in each of the first n slots (a larger launch than any before waits for the device and makes them
+  // all anew), and the slot the next launch takes
+  hipError_t reserve(size_t need, int n, int* slot) {
+    hipError_t e;
+    if (elems < need) {
+      if ((e = hipDeviceSynchronize()) != hipSuccess) return e;
+      release_staging();
+      for (int s = 0; s < n; s++)
+        if ((e = hipMalloc(reinterpret_cast<void**>(&stage[s]), sizeof(float4) * need)) != hipSuccess) { release_staging(); return e; }
+      elems = need;
+    }
+    *slot = (int)(next++ % (unsigned int)n);
+    if (stage[*slot]) return hipSuccess;
+    return hipMalloc(reinterpret_cast<void**>(&stage[*slot]), sizeof(float4) * elems);  // the depth was raised after the buffers were made
+  }
+  size_t held_bytes() const {
+    size_t held = 0;
+    for (const float4* p : stage) held += p ? sizeof(float4) * elems : 0;
+    return held;
+  }
+  hipError_t sync_all() {
+    for (int s = 0; s < RM_SP_MAX; s++)
+      if (stream[s]) { const hipError_t e = hipStreamSynchronize(stream[s]); if (e != hipSuccess) return e; }
+    return hipSuccess;
+  }
+  void destroy() {
+    for (int s = 0; s < RM_SP_MAX; s++) {
+      if (stream[s]) { (void)hipStreamSynchronize(stream[s]); (void)hipStreamDestroy(stream[s]); }
+      if (done[s]) (void)hipEventDestroy(done[s]);
+      if (free[s]) (void)hipEventDestroy(free[s]);
+      if (stage[s]) (void)hipFree(stage[s]);
+    }
+  }
+};
+
+// Cost-ordered dispatch of the pixel kernel when samples run one at a time: the tiles of a job in the order of their
+// cost in the previous sample of the same job (same framebuffer window, tile and scene kind), most expensive first.
+// One set per stream the kernel runs on (the side streams of the samples in flight, and the context's stream): a
+// launch orders by the costs the previous launch ON ITS STREAM left, so no ordering between streams is needed.
+struct Lpt {
+  // Off the critical path (the context's own slot) there are two cost / order buffers, used in turn.  The costs of launch n
+  // are sorted on a side stream WHILE launch n + 1 runs, and launch n + 2 starts in that order -- tile costs hardly
+  // change from one sample to the next, so an order that is one sample old is as good, and the sort's two small launches
+  // (one workgroup) no longer stand between two launches.  A sample-in-flight slot uses [0] alone.
+  unsigned int* cost[2] = {nullptr, nullptr};
+  unsigned int* order[2] = {nullptr, nullptr};
+  hipEvent_t rendered[2] = {nullptr, nullptr}, sorted[2] = {nullptr, nullptr};
+  int capacity = 0;   // tiles the buffers hold
+  long long key[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // the job the costs belong to
+  bool have_cost = false;
+  unsigned long long launches = 0;  // of this job (the context's own slot)
+  int to_sort = 0;  // a sample-in-flight slot: tiles whose costs the last render left to sort_slot_costs (0: it recorded none)
+
+  void forget() { have_cost = false; }  // the next launch starts a new job
+  // room for `tiles`, in `sets` sets of buffers; what still uses the old ones runs on `stream` or `sort_stream`
+  hipError_t grow(long long tiles, int sets, hipStream_t stream, hipStream_t sort_stream) {
+    if (capacity >= tiles) return hipSuccess;
+    hipError_t e;
+    if (cost[0]) {
+      (void)hipStreamSynchronize(stream);
+      if (sort_stream) (void)hipStreamSynchronize(sort_stream);
+    }
+    free_buffers();
+    const size_t order_elems = (size_t)tiles + rm::rm_order_scratch_elems(tiles);  // the sort's per-workgroup histograms behind the order
+    for (int k = 0; k < sets; k++) {
+      if ((e = hipMalloc(reinterpret_cast<void**>(&cost[k]), sizeof(unsigned int) * (size_t)tiles)) != hipSuccess) return e;
+      if ((e = hipMalloc(reinterpret_cast<void**>(&order[k]), sizeof(unsigned int) * order_elems)) != hipSuccess) return e;
+    }
+    capacity = (int)tiles;
+    forget();
+    return hipSuccess;
+  }
+  void free_buffers() {
+    for (int k = 0; k < 2; k++) {
+      if (cost[k]) (void)hipFree(cost[k]);
+      if (order[k]) (void)hipFree(order[k]);
+      cost[k] = order[k] = nullptr;
+    }
+    capacity = 0;
+  }
+  void destroy() {
+    free_buffers();
+    for (int k = 0; k < 2; k++) {
+      if (rendered[k]) (void)hipEventDestroy(rendered[k]);
+      if (sorted[k]) (void)hipEventDestroy(sorted[k]);
+    }
+  }
+};
+
 struct rm_ctx {
   int device = 0;
   hipStream_t own_stream = nullptr;
@@ -45,60 +168,15 @@ struct rm_ctx {
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   float retire_eps = 0.0f;  // opt-in (rm_ctx_set_retire_eps): any tolerance brightens lit pixels, see the header
   bool gl_stack = false;    // rm_ctx_set_gl_stack: strict-flag work runs in the GL stack's arithmetic (rm_glstack.hip)
-  int cu_count = 256;
-  // persistent-grid sizes in workgroups per CU, from a sweep on the headline frame (tools/sweep.sh):
-  // the Mandelbulb passes want FEW waves (every wave ends in a tail of a few long rays), the table march wants all slots
-  int pass2_blocks_per_cu = 2;
-  int pass1_blocks_per_cu = 2;
-  int pass2_rounds = 1;  // launches over the parked rays (the last one runs every ray to its end); >1 measured slower
-  int repark = 24;       // a drained pass-2 wave with this many active lanes or fewer hands them to the next round
-  // wavefront pipeline workspace (per-ray state + queue heads), grown on demand
-  float4* ws = nullptr;
-  size_t ws_rays = 0;
-  unsigned int* heads = nullptr;  // 3 counters per march launch: head(pass 0/1), head(pass 2), parked count
-  unsigned int* ws_list = nullptr;  // parked ray ids (two lists, ping-pong between pass-2 rounds)
-  unsigned int* ws_list2 = nullptr;
-  unsigned long long* stats = nullptr;  // 16 counters, filled by RM_WF_STATS builds only
-  hipStream_t wf_stream[4] = {nullptr, nullptr, nullptr, nullptr};  // side streams of the banded wavefront pipeline
-  hipEvent_t wf_join[4] = {nullptr, nullptr, nullptr, nullptr};
-  hipEvent_t wf_fork = nullptr;
-  int wf_bands = 0;  // bands of rows in flight on side streams; 0 = automatic (2 for large tiles: measured best)
-  int wf_blocks_per_cu = 8;
-  int claims_per_wave = 8;
-  // Samples in flight (pixel-kernel path, full mode): sample n renders on side stream n % depth into a staging
-  // buffer and is blended into the planes, in order, by a small kernel on the context's stream; the next samples
-  // render meanwhile.  One sample alone leaves the chip partly idle: a ray is a serial chain of ~2e5 instructions
-  // (~1 ms), so every launch ends in a tail and a small shard never fills the SIMDs.
-  int samples_in_flight = 3;
-  hipStream_t sp_stream[RM_SP_MAX] = {};
-  hipEvent_t sp_done[RM_SP_MAX] = {}, sp_free[RM_SP_MAX] = {};
-  float4* sp_stage[RM_SP_MAX] = {};
-  size_t sp_elems = 0;     // float4 elements of every slot's staging buffer (3 planes x tile pixels x samples of a batch)
+#if RM_WITH_WAVEFRONT
+  WavefrontHost wf;
+#endif
+  SamplesInFlight sp;
   int last_pipeline = 0;   // rm_ctx_last_pipeline: what the last render call dispatched
   // Sample batch of rm_render_samples (KParams::batch): 0 = as many samples per launch as bring it to about
   // RM_BATCH_TARGET_TILES workgroups (a whole 4K frame has 16 320), 1 = one launch per sample, 2..RM_BATCH_MAX = fixed.
   int sample_batch = 0;
-  unsigned int sp_next = 0;
-  bool sp_ready = false;
-  // Cost-ordered dispatch of the pixel kernel when samples run one at a time: the tiles of a job in the order of their
-  // cost in the previous sample of the same job (same framebuffer window, tile and scene kind), most expensive first.
-  // One set per stream the kernel runs on (the side streams of the samples in flight, and the context's stream): a
-  // launch orders by the costs the previous launch ON ITS STREAM left, so no ordering between streams is needed.
-  struct Lpt {
-    unsigned int* cost = nullptr;
-    unsigned int* order = nullptr;
-    int capacity = 0;   // tiles the buffers hold
-    long long key[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // the job the costs belong to
-    bool have_cost = false;
-    // Off the critical path (the context's own slot): two cost / order buffers used in turn.  The costs of launch n
-    // are sorted on a side stream WHILE launch n + 1 runs, and launch n + 2 starts in that order -- tile costs hardly
-    // change from one sample to the next, so an order that is one sample old is as good, and the sort's two small launches
-    // (one workgroup) no longer stand between two launches.
-    unsigned int* cost2 = nullptr;
-    unsigned int* order2 = nullptr;
-    hipEvent_t rendered[2] = {nullptr, nullptr}, sorted[2] = {nullptr, nullptr};
-    unsigned long long launches = 0;  // of this job
-  } lpt[RM_SP_MAX + 1];
+  Lpt lpt[RM_SP_MAX + 1];  // one per stream the kernel runs on: the sample-in-flight slots, and [RM_SP_MAX] the context's own
   hipStream_t lpt_stream = nullptr;
   bool lpt_enabled = true;
   hipEvent_t switch_ev = nullptr;  // orders the old stream before the new one in rm_ctx_set_stream
@@ -232,17 +310,8 @@ int rm_ctx_create(int device, rm_ctx** out) {
     return fail(nullptr, RM_ERR_DEVICE, msg);
   }
   ctx->stream = ctx->own_stream;
-  int cus = 0;
-  if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && cus > 0) ctx->cu_count = cus;
-  if (const char* v = std::getenv("RM_PASS1_BLOCKS_PER_CU")) { int n = std::atoi(v); if (n >= 1 && n <= 8) ctx->pass1_blocks_per_cu = n; }
-  if (const char* v = std::getenv("RM_PASS2_ROUNDS")) { int n = std::atoi(v); if (n >= 1 && n <= 3) ctx->pass2_rounds = n; }
-  if (const char* v = std::getenv("RM_REPARK")) { int n = std::atoi(v); if (n >= 0 && n <= 63) ctx->repark = n; }
   if (const char* v = std::getenv("RM_COST_ORDER")) ctx->lpt_enabled = std::atoi(v) != 0;
-  if (const char* v = std::getenv("RM_SAMPLES_IN_FLIGHT")) { int n = std::atoi(v); if (n >= 1 && n <= RM_SP_MAX) ctx->samples_in_flight = n; }
-  if (const char* v = std::getenv("RM_WF_CLAIMS")) { int n = std::atoi(v); if (n >= 1 && n <= 64) ctx->claims_per_wave = n; }
-  if (const char* v = std::getenv("RM_WF_BLOCKS_PER_CU")) { int n = std::atoi(v); if (n >= 1 && n <= 8) ctx->wf_blocks_per_cu = n; }
-  if (const char* v = std::getenv("RM_WF_BANDS")) { int n = std::atoi(v); if (n >= 1 && n <= 8) ctx->wf_bands = n; }
-  if (const char* v = std::getenv("RM_PASS2_BLOCKS_PER_CU")) { int n = std::atoi(v); if (n >= 1 && n <= 8) ctx->pass2_blocks_per_cu = n; }
+  if (const char* v = std::getenv("RM_SAMPLES_IN_FLIGHT")) { int n = std::atoi(v); if (n >= 1 && n <= RM_SP_MAX) ctx->sp.depth = n; }
   if (const char* v = std::getenv("RM_CULL_MIN_PIXELS")) { long long n = std::atoll(v); if (n >= 0) ctx->cull_min_pixels = n; }  // (the tests: 0, so that small renders go through the grid)
   {  // the culling grids of this context's scenes: a sixteenth of the device's memory, at most 1 GiB (a 256-row table's grid is 126 MB)
     size_t free_b = 0, total_b = 0;
@@ -258,33 +327,12 @@ void rm_ctx_destroy(rm_ctx* ctx) {
   if (!ctx) return;
   (void)hipSetDevice(ctx->device);
   (void)hipStreamSynchronize(ctx->stream);
-  if (ctx->ws) (void)hipFree(ctx->ws);
-  if (ctx->heads) (void)hipFree(ctx->heads);
-  if (ctx->ws_list) (void)hipFree(ctx->ws_list);
-  if (ctx->ws_list2) (void)hipFree(ctx->ws_list2);
-  if (ctx->stats) (void)hipFree(ctx->stats);
-  for (int s = 0; s < 4; s++) {
-    if (ctx->wf_stream[s]) { (void)hipStreamSynchronize(ctx->wf_stream[s]); (void)hipStreamDestroy(ctx->wf_stream[s]); }
-    if (ctx->wf_join[s]) (void)hipEventDestroy(ctx->wf_join[s]);
-  }
-  if (ctx->wf_fork) (void)hipEventDestroy(ctx->wf_fork);
+#if RM_WITH_WAVEFRONT
+  ctx->wf.destroy();
+#endif
   if (ctx->lpt_stream) { (void)hipStreamSynchronize(ctx->lpt_stream); (void)hipStreamDestroy(ctx->lpt_stream); }
-  for (auto& l : ctx->lpt) {
-    if (l.cost) (void)hipFree(l.cost);
-    if (l.order) (void)hipFree(l.order);
-    if (l.cost2) (void)hipFree(l.cost2);
-    if (l.order2) (void)hipFree(l.order2);
-    for (int k = 0; k < 2; k++) {
-      if (l.rendered[k]) (void)hipEventDestroy(l.rendered[k]);
-      if (l.sorted[k]) (void)hipEventDestroy(l.sorted[k]);
-    }
-  }
-  for (int s = 0; s < RM_SP_MAX; s++) {
-    if (ctx->sp_stream[s]) { (void)hipStreamSynchronize(ctx->sp_stream[s]); (void)hipStreamDestroy(ctx->sp_stream[s]); }
-    if (ctx->sp_done[s]) (void)hipEventDestroy(ctx->sp_done[s]);
-    if (ctx->sp_free[s]) (void)hipEventDestroy(ctx->sp_free[s]);
-    if (ctx->sp_stage[s]) (void)hipFree(ctx->sp_stage[s]);
-  }
+  for (auto& l : ctx->lpt) l.destroy();
+  ctx->sp.destroy();
   if (ctx->present_buf) (void)hipFree(ctx->present_buf);
   for (auto* b : ctx->denoise_buf)
     if (b) (void)hipFree(b);
@@ -329,8 +377,8 @@ int rm_ctx_set_stream(rm_ctx* ctx, void* hip_stream) {
 int rm_ctx_set_samples_in_flight(rm_ctx* ctx, int n) {
   if (!ctx) return RM_ERR_INVALID;
   if (n < 1 || n > RM_SP_MAX) return fail(ctx, RM_ERR_INVALID, "rm_ctx_set_samples_in_flight: n must be in 1..8");
-  if (ctx->sp_ready) RM_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  ctx->samples_in_flight = n;
+  if (ctx->sp.ready) RM_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  ctx->sp.depth = n;
   ctx->warning.clear();
   if (n > 1) {
     // every sample in flight renders on a side stream; the HIP runtime maps a process's streams onto GPU_MAX_HW_QUEUES
@@ -352,7 +400,7 @@ const char* rm_ctx_last_warning(const rm_ctx* ctx) { return ctx ? ctx->warning.c
 int rm_ctx_set_cost_order(rm_ctx* ctx, int on) {
   if (!ctx) return RM_ERR_INVALID;
   ctx->lpt_enabled = on != 0;
-  for (auto& l : ctx->lpt) l.have_cost = false;
+  for (auto& l : ctx->lpt) l.forget();
   return RM_OK;
 }
 
@@ -388,10 +436,12 @@ int rm_ctx_set_gl_stack(rm_ctx* ctx, int on) {
 int rm_debug_counters(rm_ctx* ctx, unsigned long long* out16, int reset) {
   if (!ctx || !out16) return RM_ERR_INVALID;
   for (int i = 0; i < 16; i++) out16[i] = 0;
-  if (!ctx->stats) return RM_OK;
+#if RM_WITH_WAVEFRONT  // (the product has no stats: zeros)
+  if (!ctx->wf.stats) return RM_OK;
   RM_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  RM_HIP(ctx, hipMemcpy(out16, ctx->stats, sizeof(unsigned long long) * 16, hipMemcpyDeviceToHost));
-  if (reset) RM_HIP(ctx, hipMemset(ctx->stats, 0, sizeof(unsigned long long) * 16));
+  RM_HIP(ctx, hipMemcpy(out16, ctx->wf.stats, sizeof(unsigned long long) * 16, hipMemcpyDeviceToHost));
+  if (reset) RM_HIP(ctx, hipMemset(ctx->wf.stats, 0, sizeof(unsigned long long) * 16));
+#endif
   return RM_OK;
 }
 
@@ -1170,8 +1220,7 @@ int rm_ctx_set_cull_budget(rm_ctx* ctx, size_t bytes) {
     for (rm_scene* c : ctx->cull_scenes)
       if (c->last_use < victim->last_use) victim = c;
     RM_HIP(ctx, hipStreamSynchronize(ctx->stream));  // (renders that read the grid are followed by their blend on this stream)
-    for (int i = 0; i < RM_SP_MAX; i++)
-      if (ctx->sp_stream[i]) RM_HIP(ctx, hipStreamSynchronize(ctx->sp_stream[i]));
+    RM_HIP(ctx, ctx->sp.sync_all());
     cull_release(ctx, victim, true);
     victim->cull_wanted = true;
     victim->px_seen = 0;
@@ -1190,6 +1239,10 @@ int rm_ctx_cull_stats(const rm_ctx* ctx, unsigned long long* out4) {
 }
 
 // ---- the hot path ---------------------------------------------------------------
+
+// what one sample of a tw x th tile asks of the scene, in pixel-samples of the JOB: a striped framebuffer holds one part of `parts` of the frame, and
+// the other ranks render the rest of it (each with a grid of its own to earn: the threshold is the same for a sharded job as for a whole one)
+static long long job_pixel_samples(const rm_fb* fb, int tw, int th) { return (long long)tw * (long long)th * (fb->stripe_rows > 0 ? (long long)fb->parts : 1ll); }
 
 static int build_params(rm_ctx* ctx, rm_scene* scene, rm_fb* fb, const RmUniforms* u, const RmRect* tile, int flags,
                         KParams* P, bool* empty) {
@@ -1221,9 +1274,7 @@ static int build_params(rm_ctx* ctx, rm_scene* scene, rm_fb* fb, const RmUniform
     l1 = (y1 > fb->row_begin + fb->row_count ? fb->row_begin + fb->row_count : y1) - fb->row_begin;
   }
   *empty = x1 <= x0 || l1 <= l0;
-  // what the scene has been asked for, in pixel-samples of the JOB: a striped framebuffer holds one part of `parts` of the frame, and the
-  // other ranks render the rest of it (each with a grid of its own to earn: the threshold is the same for a sharded job as for a whole one)
-  if (int rc = scene_cull_grid(ctx, scene, flags, *empty ? 0ll : (long long)(x1 - x0) * (long long)(l1 - l0) * (fb->stripe_rows > 0 ? (long long)fb->parts : 1ll))) return rc;
+  if (int rc = scene_cull_grid(ctx, scene, flags, *empty ? 0ll : job_pixel_samples(fb, x1 - x0, l1 - l0))) return rc;
   P->u = *u;
   P->scene = scene->dev;
   P->color = fb->plane[0];
@@ -1250,200 +1301,9 @@ static int build_params(rm_ctx* ctx, rm_scene* scene, rm_fb* fb, const RmUniform
 
 #define RM_BATCH_TARGET_TILES 16384ll  // workgroups a batch launch of rm_render_samples aims for
 
-// ---- the wavefront pipeline (rm_wavefront.inc): compiled into the tests' CROSS-CHECK build only (round 5) ---------------------------
-// The same per-pixel program cut at its marches into queue-driven stages.  Rounds 1-3 the library picked it for some jobs; since round
-// 4 the pixel kernel is the faster one for every measured job in both builds, and it alone grew per-shape surfaces, kind rows and
-// the GL stack's arithmetic.  It stays what it is good for -- a second implementation of the marches, bounces and lights that the
-// tests hold the pixel kernel to, bit for bit -- in tests/_xcheck/libhip_raymarch_xcheck.so (build.py build_crosscheck,
-// -DRM_WITH_WAVEFRONT=1); libhip_raymarch.so, the product, has neither its kernels nor this orchestration, and refuses
-// RM_RENDER_WAVEFRONT.  The product's own cross-check is the stepwise march: RM_RENDER_NO_FAR_JUMP | RM_RENDER_NO_CULL.
-#if RM_WITH_WAVEFRONT
-#define RM_MAX_MARCHES (RM_MAX_BOUNCES * (1 + RM_MAX_LIGHTS))
-#define RM_COUNTERS_PER_MARCH 8  // queue heads and parked counts of the launches of one march
-
-// One sample through the wavefront pipeline (rm_wavefront.inc).
-#define RM_WF_STREAMS 4
-#define RM_WF_MAX_BANDS 8
-
-// One band of rows through the wavefront pipeline (rm_wavefront.inc) on `stream`.
-static hipError_t launch_wavefront_band(rm_ctx* ctx, const KParams& P, int flags, hipStream_t stream, float4* ws,
-                                        unsigned int* list, unsigned int* list2, unsigned int* heads) {
-  const bool fast = (flags & RM_RENDER_FAST) != 0;
-  rm::WfParams W{};
-  W.k = P;
-  W.tiles_x = (P.tw + 7) / 8;
-  const int tiles_y = (P.th + 7) / 8;
-  W.n_rays = W.tiles_x * tiles_y * 64;
-  for (int i = 0; i < rm::WF_ARRAYS; i++) W.a[i] = ws + (size_t)i * (size_t)W.n_rays;
-  W.stats = ctx->stats;
-  hipError_t e;
-  const bool classes = rm::wf_kind_has_cost_classes(P.scene.kind) && !(flags & RM_RENDER_NO_COST_CLASSES);
-  // persistent march grid: every SIMD slot of the chip, or fewer when there are few rays
-  int blocks = ctx->cu_count * ctx->wf_blocks_per_cu;
-  const int needed = (W.n_rays + 255) / 256;
-  if (blocks > needed) blocks = needed;
-  int march = 0;
-  auto do_march = [&](int pos_array, int dir_array, bool preview) -> hipError_t {
-    W.pos_array = pos_array;
-    W.dir_array = dir_array;
-    unsigned int* c = heads + RM_COUNTERS_PER_MARCH * march++;  // [0] head of pass 0/1, [1] parked by pass 1, [2..] heads/counts of the pass-2 rounds
-    auto go = [&](int pass) { return fast ? rm::wf_launch_march_fast(W, preview, pass, blocks, stream) : rm::wf_launch_march_strict(W, preview, pass, blocks, stream); };
-    W.head = c;
-    W.claims_per_wave = ctx->claims_per_wave;
-    W.repark = 0;
-    W.list_in = nullptr;
-    W.list_in_count = nullptr;
-    W.list_out = list;
-    W.list_out_count = c + 1;
-    if (!classes) return go(0);
-    const int saved = blocks;
-    const int pass1 = ctx->cu_count * ctx->pass1_blocks_per_cu;
-    if (blocks > pass1) blocks = pass1;
-    hipError_t e1 = go(1);  // cheap evaluations; parks the rays that need the deep one
-    blocks = saved;
-    if (e1 != hipSuccess) return e1;
-    // The parked rays, compacted, in up to three rounds.  Fewer waves than SIMD
-    // slots on purpose (2 per SIMD keep the VALU of this dependent-chain code
-    // busy), and a round whose queue has drained does not let its waves thin
-    // out to a few never-settling rays each: a wave with <= repark active lanes
-    // parks them again and the next, smaller round re-compacts the survivors.
-    unsigned int* in = list;
-    unsigned int* outl = list2;
-    unsigned int* in_count = c + 1;
-    int round_blocks = ctx->cu_count * ctx->pass2_blocks_per_cu;
-    for (int round = 0; round < ctx->pass2_rounds; round++) {
-      const bool last = round == ctx->pass2_rounds - 1;
-      W.head = c + 2 + 2 * round;
-      W.list_in = in;
-      W.list_in_count = in_count;
-      W.list_out = outl;
-      W.list_out_count = c + 3 + 2 * round;
-      W.repark = last ? 0 : ctx->repark;
-      blocks = round_blocks < saved ? round_blocks : saved;
-      hipError_t e2 = go(2);
-      if (e2 != hipSuccess) { blocks = saved; return e2; }
-      in_count = W.list_out_count;
-      unsigned int* t = in; in = outl; outl = t;
-      round_blocks = round_blocks / 4 > ctx->cu_count / 4 ? round_blocks / 4 : ctx->cu_count / 4;
-    }
-    blocks = saved;
-    return hipSuccess;
-  };
-  if ((e = rm::wf_launch_stage(W, 0, stream)) != hipSuccess) return e;  // setup
-  if (P.u.renderMode == 1) {
-    if ((e = do_march(rm::WF_POS, rm::WF_DIR, true)) != hipSuccess) return e;
-    return rm::wf_launch_stage(W, 1, stream);
-  }
-  int bounces = 0;
-  for (float i = 0.0f; i < P.u.reflections; i += 1.0f) bounces++;
-  if (bounces == 0) return rm::wf_launch_stage(W, 2, stream);
-  for (int b = 0; b < bounces; b++) {
-    W.bounce = b;
-    W.last_bounce = b == bounces - 1;
-    if ((e = do_march(rm::WF_POS, rm::WF_DIR, false)) != hipSuccess) return e;
-    if ((e = fast ? rm::wf_launch_shade_fast(W, stream) : rm::wf_launch_shade_strict(W, stream)) != hipSuccess) return e;
-    for (int j = 0; j < P.u.lightCount; j++) {
-      W.light = j;
-      if ((e = do_march(rm::WF_SPOS, rm::WF_SDIR, false)) != hipSuccess) return e;
-      if ((e = rm::wf_launch_stage(W, 3, stream)) != hipSuccess) return e;  // light
-    }
-  }
-  return hipSuccess;
-}
-
-// One sample through the wavefront pipeline.  A large tile is cut into bands of
-// rows that go down the pipeline on RM_WF_STREAMS side streams: every kernel of
-// the pipeline ends with a tail in which the chip drains (a few long rays, the
-// last workgroups), and the next band's kernels fill those holes.  Bands are
-// independent (every pixel is), so this changes nothing in the results.
-static hipError_t launch_wavefront(rm_ctx* ctx, const KParams& P, int flags) {
-  hipStream_t stream = ctx->stream;
-  const int tiles_x = (P.tw + 7) / 8, tiles_y = (P.th + 7) / 8;
-  int bands = ctx->wf_bands > 0 ? ctx->wf_bands : (tiles_y >= 32 ? 2 : 1);
-  if (bands > RM_WF_MAX_BANDS) bands = RM_WF_MAX_BANDS;
-  if (bands > tiles_y) bands = tiles_y;
-  const size_t total_rays = (size_t)tiles_x * (size_t)tiles_y * 64;
-  hipError_t e;
-  if (!ctx->heads) {
-    if ((e = hipMalloc(reinterpret_cast<void**>(&ctx->heads), sizeof(unsigned int) * RM_COUNTERS_PER_MARCH * RM_MAX_MARCHES * RM_WF_MAX_BANDS)) != hipSuccess) return e;
-    if ((e = hipMalloc(reinterpret_cast<void**>(&ctx->stats), sizeof(unsigned long long) * 16)) != hipSuccess) return e;
-    if ((e = hipMemset(ctx->stats, 0, sizeof(unsigned long long) * 16)) != hipSuccess) return e;
-    for (int s = 0; s < RM_WF_STREAMS; s++) {
-      if ((e = hipStreamCreateWithFlags(&ctx->wf_stream[s], hipStreamNonBlocking)) != hipSuccess) return e;
-      if ((e = hipEventCreateWithFlags(&ctx->wf_join[s], hipEventDisableTiming)) != hipSuccess) return e;
-    }
-    if ((e = hipEventCreateWithFlags(&ctx->wf_fork, hipEventDisableTiming)) != hipSuccess) return e;
-  }
-  if (ctx->ws_rays < total_rays) {
-    if (ctx->ws) {
-      if ((e = hipDeviceSynchronize()) != hipSuccess) return e;
-      (void)hipFree(ctx->ws);
-      (void)hipFree(ctx->ws_list);
-      (void)hipFree(ctx->ws_list2);
-      ctx->ws = nullptr;
-      ctx->ws_list = nullptr;
-      ctx->ws_list2 = nullptr;
-      ctx->ws_rays = 0;
-    }
-    if ((e = hipMalloc(reinterpret_cast<void**>(&ctx->ws), sizeof(float4) * (size_t)rm::WF_ARRAYS * total_rays)) != hipSuccess) {
-      char msg[160];
-      std::snprintf(msg, sizeof msg, "wavefront pipeline: cannot allocate its %.1f GB ray workspace (%zu rays x %d B); render in tiles or use RM_RENDER_MEGAKERNEL",
-                    (double)(sizeof(float4) * (size_t)rm::WF_ARRAYS * total_rays) / 1e9, total_rays, (int)(sizeof(float4) * rm::WF_ARRAYS));
-      ctx->error = msg;
-      return e;
-    }
-    if ((e = hipMalloc(reinterpret_cast<void**>(&ctx->ws_list), sizeof(unsigned int) * total_rays)) != hipSuccess) return e;
-    if ((e = hipMalloc(reinterpret_cast<void**>(&ctx->ws_list2), sizeof(unsigned int) * total_rays)) != hipSuccess) return e;
-    ctx->ws_rays = total_rays;
-  }
-  if ((e = hipMemsetAsync(ctx->heads, 0, sizeof(unsigned int) * RM_COUNTERS_PER_MARCH * RM_MAX_MARCHES * RM_WF_MAX_BANDS, stream)) != hipSuccess) return e;
-  if (bands == 1) return launch_wavefront_band(ctx, P, flags, stream, ctx->ws, ctx->ws_list, ctx->ws_list2, ctx->heads);
-  if ((e = hipEventRecord(ctx->wf_fork, stream)) != hipSuccess) return e;
-  for (int s = 0; s < RM_WF_STREAMS; s++)
-    if ((e = hipStreamWaitEvent(ctx->wf_stream[s], ctx->wf_fork, 0)) != hipSuccess) return e;
-  size_t rays_before = 0;
-  for (int b = 0; b < bands; b++) {
-    const int t0 = (int)((long long)tiles_y * b / bands), t1 = (int)((long long)tiles_y * (b + 1) / bands);
-    KParams B = P;
-    B.ty = P.ty + t0 * 8;
-    B.th = (t1 * 8 < P.th ? t1 * 8 : P.th) - t0 * 8;
-    const size_t band_rays = (size_t)tiles_x * (size_t)(t1 - t0) * 64;
-    if ((e = launch_wavefront_band(ctx, B, flags, ctx->wf_stream[b % RM_WF_STREAMS], ctx->ws + (size_t)rm::WF_ARRAYS * rays_before,
-                                   ctx->ws_list + rays_before, ctx->ws_list2 + rays_before, ctx->heads + (size_t)RM_COUNTERS_PER_MARCH * RM_MAX_MARCHES * b)) != hipSuccess)
-      return e;
-    rays_before += band_rays;
-  }
-  for (int s = 0; s < RM_WF_STREAMS; s++) {
-    if ((e = hipEventRecord(ctx->wf_join[s], ctx->wf_stream[s])) != hipSuccess) return e;
-    if ((e = hipStreamWaitEvent(stream, ctx->wf_join[s], 0)) != hipSuccess) return e;
-  }
-  return hipSuccess;
-}
-
-#endif  // RM_WITH_WAVEFRONT
-
-// Which implementation of the per-pixel program runs a job (same results either way).
-// Measured on MI355X (fast build, ms per sample, pixel kernel / wavefront pipeline).  Round 2:
-//   Mandelbulb 3840x2160 full      2.49 / 4.5         sphere 1080p preview 0.11 / 1.4
-//   CSG-64 4096x512  (2 Mpx)       6.79 / 7.67        CSG-64 4096x4096 (16.8 Mpx)  47.0 / 40.6
-//   CSG-64 8192x1024 (8.4 Mpx)     60.5 / 54.6        CSG-64 8192x8192 (67 Mpx)    467  / 415
-// Round 3, with the far-field jump in both and the compacting pixel kernel for long tables (RM_KIND_TABLE_BIG; tools/r03_table.py):
-//   Mandelbulb 3840x2160 full      1.98 / 4.0
-//   CSG-64 4096^2, rank 0's 1/8    2.33 / 6.33        CSG-64 4096x4096             15.3 / 14.4
-//   CSG-64 8192^2, rank 0's 1/8    31.5 / 33.1        CSG-64 8192x8192             244  / 229
-// and at the end of round 3, with the tighter far field and CSG-64's own pixel kernel (RM_KIND_TABLE_SMOOTH):
-//   CSG-64 4096^2, rank 0's 1/8    2.19 / 5.79        CSG-64 4096x4096             12.9 / 13.2
-//   CSG-64 8192^2, rank 0's 1/8    29.2 / 32.7        CSG-64 8192x8192             225.7 / 225.6
-// The fast build's one-kernel form now wins or ties everywhere -- the pipeline's global ray compaction bought 10-16 % on the two
-// full CSG frames in round 2, 6 % after the pixel kernel compacted its table rays, nothing now -- and it needs no 240 bytes of
-// workspace per pixel: the fast build never picks the pipeline by itself any more (RM_RENDER_WAVEFRONT still forces it; it remains
-// the second implementation the tests hold the pixel kernel to).  Round 4, with the exits, the job-shape variants and the row culling
-// in the parity build too, the same holds there (strict, pixel kernel / pipeline):
-//   CSG-64 4096x4096               26.5 / 29.8        CSG-64 8192^2, rank 0's 1/8    45.2 / 85.7
-// so the library never picks the pipeline by itself.
-static bool prefer_wavefront(const KParams&, int) { return false; }
-
-// The implementation a render call uses.  The GL-stack arithmetic exists as the pixel kernel only, and so do
+// The implementation a render call uses (same results either way).  The pixel kernel is the faster one for every measured job in
+// both builds, so the wavefront pipeline (rm_wavefront.inc, launched by rm_wavefront_host.inc) runs only where a caller of the tests'
+// cross-check build asks for it.  The GL-stack arithmetic exists as the pixel kernel only, and so do
 // position-dependent materials (RM_TABLE_HAS_SURFACES): the pipeline's stages carry one material block per scene -- its light
 // stage has no scene table staged -- so such scenes render with the pixel kernel whatever the flags ask for (same results).
 static bool uses_wavefront(const rm_ctx* ctx, const KParams& P, int flags) {
@@ -1451,18 +1311,24 @@ static bool uses_wavefront(const rm_ctx* ctx, const KParams& P, int flags) {
   if (ctx->gl_stack && !(flags & RM_RENDER_FAST)) return false;
   if (P.scene.table_flags & (RM_TABLE_HAS_SURFACES | RM_TABLE_HAS_KIND)) return false;
   if (P.gbuffer_half || P.moments) return false;  // the half G-buffer and the moments are blended by rm_combine_kernel behind the staged pixel kernel only
-  return (flags & RM_RENDER_WAVEFRONT) ? true : (flags & RM_RENDER_MEGAKERNEL) ? false : prefer_wavefront(P, flags);
+  return (flags & RM_RENDER_WAVEFRONT) != 0;
 }
 
-static hipError_t launch_pixels_ordered(rm_ctx* ctx, const KParams& P, int flags, hipStream_t stream, int slot);
-
-// frees the staging buffers of the samples in flight (the caller has synchronised the device, or is giving the buffers up)
-static void release_staging(rm_ctx* ctx) {
-  for (int s = 0; s < RM_SP_MAX; s++) {
-    if (ctx->sp_stage[s]) (void)hipFree(ctx->sp_stage[s]);
-    ctx->sp_stage[s] = nullptr;
-  }
-  ctx->sp_elems = 0;
+// Whether a job's samples are staged (launch_pixels_in_flight), and over how many slots.
+struct Staging { enum Rule { NEVER, MAY, MUST } rule; int depth; };
+static Staging staging_rule(const rm_ctx* ctx, const KParams& P, int flags) {
+  // full mode with at least one bounce: the kernel's only use of the planes is the final blend, which can be split off
+  if (uses_wavefront(ctx, P, flags) || !(P.u.renderMode == 0 && P.u.reflections > 0.0f)) return {Staging::NEVER, 0};
+  const bool overlap = !(flags & RM_RENDER_NO_OVERLAP);
+  // The half G-buffer (RM_GBUFFER_F16) is blended by rm_combine_kernel only -- the pixel kernel's own blend is the fp32 one, left
+  // exactly as it was -- so a render that writes the G-buffer (the planes asked for: raymarcher.frag:347-351 runs at bounce 0) is
+  // always staged; with RM_RENDER_NO_OVERLAP on one staging slot, so that a sample's render waits for the previous sample's blend.
+  // No unstaged fallback: without room for the staging of the tile the call fails (render in tiles).
+  // The moments plane (RM_FB_MOMENTS) is written by rm_combine_kernel only too, under the same rule.
+  if ((P.gbuffer_half || P.moments != nullptr) && P.normal_dof != nullptr) return {Staging::MUST, overlap ? ctx->sp.depth : 1};
+  // Otherwise staging is there for the overlap: a launch that finds no room for it renders unstaged (same bits).  On ONE slot a
+  // single sample gains nothing from it and launch() leaves it unstaged; a batch of rm_render_samples still saves its launches.
+  return {overlap ? Staging::MAY : Staging::NEVER, ctx->sp.depth};
 }
 
 // Staging the library may hold for a job: a quarter of what the device has free (counting what staging already holds).
@@ -1475,132 +1341,50 @@ static size_t staging_budget(rm_ctx* ctx) {
   }
   size_t free_b = 0, total_b = 0;
   if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) return (size_t)1 << 30;
-  size_t held = 0;
-  for (int s = 0; s < RM_SP_MAX; s++) held += ctx->sp_stage[s] ? sizeof(float4) * ctx->sp_elems : 0;
-  return (free_b + held) / 4;
+  return (free_b + ctx->sp.held_bytes()) / 4;
 }
 
-// The pixel kernel of one sample -- or of a batch of `batch` samples, randNoise pairs in `noise` -- on a side stream,
-// staged, and its blend on the context's stream (see rm_ctx).
-// depth: staging slots to rotate through (0 = the context's samples in flight; 1 = a sample's render waits for the previous blend)
-static hipError_t launch_pixels_in_flight(rm_ctx* ctx, const KParams& P, int flags, int batch = 1, const float* noise = nullptr, int depth = 0) {
-  hipError_t e;
-  if (depth <= 0) depth = ctx->samples_in_flight;
-  // side streams are made as the depth asks for them, not all RM_SP_MAX at once: the HIP runtime deals a process's streams
-  // over a few hardware queues, and streams that share a queue serialise (measured: 0.59 instead of 0.42 ms per sample on a 1/8 shard)
-  for (int s = 0; s < depth; s++) {
-    if (ctx->sp_stream[s]) continue;
-    if ((e = hipStreamCreateWithFlags(&ctx->sp_stream[s], hipStreamNonBlocking)) != hipSuccess) return e;
-    if ((e = hipEventCreateWithFlags(&ctx->sp_done[s], hipEventDisableTiming)) != hipSuccess) return e;
-    if ((e = hipEventCreateWithFlags(&ctx->sp_free[s], hipEventDisableTiming)) != hipSuccess) return e;
-  }
-  ctx->sp_ready = true;
-  // A slot's staging holds the launch's TILE, compact (tile pixel i of sample k at k * 3 * stride + i), so it is sized by the
-  // largest batch x tile a job has used -- not by the frame: a subdivided 8192^2 render stages a tile, not 3.2 GB x batch.
-  // One buffer of `sp_elems` float4 per slot; a launch needs 3 * tw * th * batch of them.
-  const size_t tile_px = (size_t)P.tw * (size_t)P.th;
-  const size_t need = 3 * tile_px * (size_t)batch;
-  if (ctx->sp_elems < need) {
-    if ((e = hipDeviceSynchronize()) != hipSuccess) return e;
-    release_staging(ctx);
-    for (int s = 0; s < depth; s++)
-      if ((e = hipMalloc(reinterpret_cast<void**>(&ctx->sp_stage[s]), sizeof(float4) * need)) != hipSuccess) { release_staging(ctx); return e; }
-    ctx->sp_elems = need;
-  }
-  const int slot = (int)(ctx->sp_next++ % (unsigned int)depth);
-  if (!ctx->sp_stage[slot]) {  // the depth was raised after the buffers were made
-    if ((e = hipMalloc(reinterpret_cast<void**>(&ctx->sp_stage[slot]), sizeof(float4) * ctx->sp_elems)) != hipSuccess) return e;
-  }
-  KParams Q = P;
-  Q.stage = ctx->sp_stage[slot];
-  Q.stage_stride = (long long)tile_px;
-  if (batch > 1) {
-    Q.batch = batch;
-    std::memcpy(Q.batch_noise, noise, sizeof(float) * 2 * (size_t)batch);
-  }
-  hipStream_t side = ctx->sp_stream[slot];
-  // the render reads no plane: it only has to wait until the blend that last used this staging buffer is done
-  if ((e = hipStreamWaitEvent(side, ctx->sp_free[slot], 0)) != hipSuccess) return e;
-  if (ctx->cull_event && (e = hipStreamWaitEvent(side, ctx->cull_event, 0)) != hipSuccess) return e;  // ... and for the scene's culling grid, built on the context's cull_stream (scene_cull_grid records cull_event behind the build)
-  ctx->lpt[slot].launches = 0;
-  if ((e = launch_pixels_ordered(ctx, Q, flags, side, slot)) != hipSuccess) return e;
-  if ((e = hipEventRecord(ctx->sp_done[slot], side)) != hipSuccess) return e;
-  if (ctx->lpt[slot].launches > 0) {  // the launch recorded tile costs: sort them now, behind the completion event
-    rm_ctx::Lpt& Ls = ctx->lpt[slot];
-    if ((e = rm::launch_order(Ls.cost, Ls.order, Ls.order + Ls.capacity, (int)Ls.launches, side)) != hipSuccess) return e;
-  }
-  if ((e = hipStreamWaitEvent(ctx->stream, ctx->sp_done[slot], 0)) != hipSuccess) return e;
-  if ((e = rm::launch_combine(Q, ctx->stream)) != hipSuccess) return e;
-  return hipEventRecord(ctx->sp_free[slot], ctx->stream);
+// the pixel kernel in the build the flags and the context ask for
+static hipError_t launch_pixel_kernel(const rm_ctx* ctx, const KParams& P, int flags, hipStream_t stream) {
+  return (flags & RM_RENDER_FAST) ? rm::launch_pixels_fast(P, stream) : ctx->gl_stack ? rm_gl_launch_pixels(&P, stream) : rm::launch_pixels_strict(P, stream);
 }
 
-// The pixel kernel on `stream`, its tiles in the order of their cost in the previous launch of the same job on that stream
-// (slot = which of the context's streams: a sample-in-flight slot, or RM_SP_MAX for the context's own stream).
-static hipError_t launch_pixels_ordered(rm_ctx* ctx, const KParams& P, int flags, hipStream_t stream, int slot) {
-  const bool fast = (flags & RM_RENDER_FAST) != 0;
-  int gx = 0, gy = 0;
-  rm::pixel_grid(P, &gx, &gy);
-  const long long tiles = (long long)gx * gy;
-  if (!ctx->lpt_enabled || tiles < 512 || tiles > (1ll << 22))  // small jobs end on launch latency, not on a tail
-    return fast ? rm::launch_pixels_fast(P, stream) : ctx->gl_stack ? rm_gl_launch_pixels(&P, stream) : rm::launch_pixels_strict(P, stream);
-  rm_ctx::Lpt& L = ctx->lpt[slot];
+// Cost order on a sample-in-flight slot: the costs are sorted on the slot's own stream right AFTER the render (sort_slot_costs, called once the render's
+// completion event is recorded), so the sort's two small launches sit in the shadow of the other slots' renders instead of in front of this slot's next one
+static hipError_t launch_ordered_on_slot(rm_ctx* ctx, Lpt& L, KParams Q, int flags, hipStream_t stream, long long tiles) {
   hipError_t e;
-  const long long key[8] = {P.W, P.H, ((long long)P.tx << 32) | (unsigned int)P.ty, ((long long)P.tw << 32) | (unsigned int)P.th,
-                            ((long long)P.stripe_rows << 40) | ((long long)P.parts << 20) | P.part, P.row_begin,
-                            ((long long)P.scene.kind << 8) | P.u.renderMode, tiles};
-  const bool async_sort = slot == RM_SP_MAX;  // the context's own stream: sort on a side stream, one sample behind
-  if (L.capacity < tiles) {
-    if (L.cost) {
-      (void)hipStreamSynchronize(stream);
-      if (ctx->lpt_stream) (void)hipStreamSynchronize(ctx->lpt_stream);
-      (void)hipFree(L.cost); (void)hipFree(L.order);
-      if (L.cost2) { (void)hipFree(L.cost2); (void)hipFree(L.order2); }
-    }
-    L.cost = L.order = L.cost2 = L.order2 = nullptr;
-    L.capacity = 0;
-    if ((e = hipMalloc(reinterpret_cast<void**>(&L.cost), sizeof(unsigned int) * (size_t)tiles)) != hipSuccess) return e;
-    const size_t order_elems = (size_t)tiles + rm::rm_order_scratch_elems(tiles);  // the sort's per-workgroup histograms behind the order
-    if ((e = hipMalloc(reinterpret_cast<void**>(&L.order), sizeof(unsigned int) * order_elems)) != hipSuccess) return e;
-    if (async_sort) {
-      if ((e = hipMalloc(reinterpret_cast<void**>(&L.cost2), sizeof(unsigned int) * (size_t)tiles)) != hipSuccess) return e;
-      if ((e = hipMalloc(reinterpret_cast<void**>(&L.order2), sizeof(unsigned int) * order_elems)) != hipSuccess) return e;
-    }
-    L.capacity = (int)tiles;
-    L.have_cost = false;
-  }
-  if (std::memcmp(key, L.key, sizeof key) != 0) {
-    std::memcpy(L.key, key, sizeof key);
-    L.have_cost = false;
-  }
-  KParams Q = P;
-  if (!async_sort) {
-    // a sample-in-flight slot: the costs are sorted on the slot's own stream right AFTER the render (sort_slot_costs,
-    // called once the render's completion event is recorded), so the sort's two small launches sit in the
-    // shadow of the other slots' renders instead of in front of this slot's next one
-    Q.block_cost = L.cost;
-    if (L.have_cost) Q.block_order = L.order;
-    else if ((e = hipMemsetAsync(L.cost, 0, sizeof(unsigned int) * (size_t)tiles, stream)) != hipSuccess) return e;
-    L.have_cost = true;
-    L.launches = (unsigned long long)tiles;  // what sort_slot_costs has to sort
-    return fast ? rm::launch_pixels_fast(Q, stream) : ctx->gl_stack ? rm_gl_launch_pixels(&Q, stream) : rm::launch_pixels_strict(Q, stream);
-  }
-  if (!ctx->lpt_stream) {
-    if ((e = hipStreamCreateWithFlags(&ctx->lpt_stream, hipStreamNonBlocking)) != hipSuccess) return e;
-  }
+  Q.block_cost = L.cost[0];
+  if (L.have_cost) Q.block_order = L.order[0];
+  else if ((e = hipMemsetAsync(L.cost[0], 0, sizeof(unsigned int) * (size_t)tiles, stream)) != hipSuccess) return e;
+  L.have_cost = true;
+  L.to_sort = (int)tiles;
+  return launch_pixel_kernel(ctx, Q, flags, stream);
+}
+
+static hipError_t sort_slot_costs(rm_ctx* ctx, int slot, hipStream_t stream) {
+  Lpt& L = ctx->lpt[slot];
+  return L.to_sort > 0 ? rm::launch_order(L.cost[0], L.order[0], L.order[0] + L.capacity, L.to_sort, stream) : hipSuccess;
+}
+
+// Cost order on the context's own stream: the sort runs on lpt_stream, one sample behind (see Lpt)
+static hipError_t launch_ordered_on_own_stream(rm_ctx* ctx, Lpt& L, KParams Q, int flags, long long tiles) {
+  hipError_t e;
+  hipStream_t stream = ctx->stream;
+  if (!ctx->lpt_stream && (e = hipStreamCreateWithFlags(&ctx->lpt_stream, hipStreamNonBlocking)) != hipSuccess) return e;
   for (int k = 0; k < 2; k++) {
     if (!L.rendered[k] && (e = hipEventCreateWithFlags(&L.rendered[k], hipEventDisableTiming)) != hipSuccess) return e;
     if (!L.sorted[k] && (e = hipEventCreateWithFlags(&L.sorted[k], hipEventDisableTiming)) != hipSuccess) return e;
   }
   if (!L.have_cost) {  // a new job: both cost buffers start from zero, no order yet
     if ((e = hipStreamSynchronize(ctx->lpt_stream)) != hipSuccess) return e;  // sorts of the previous job still use the buffers
-    if ((e = hipMemsetAsync(L.cost, 0, sizeof(unsigned int) * (size_t)tiles, stream)) != hipSuccess) return e;
-    if ((e = hipMemsetAsync(L.cost2, 0, sizeof(unsigned int) * (size_t)tiles, stream)) != hipSuccess) return e;
+    if ((e = hipMemsetAsync(L.cost[0], 0, sizeof(unsigned int) * (size_t)tiles, stream)) != hipSuccess) return e;
+    if ((e = hipMemsetAsync(L.cost[1], 0, sizeof(unsigned int) * (size_t)tiles, stream)) != hipSuccess) return e;
     L.launches = 0;
     L.have_cost = true;
   }
-  const int cur = (int)(L.launches & 1ull), prev = cur ^ 1;
-  unsigned int* cost_cur = cur ? L.cost2 : L.cost;
-  unsigned int* order_cur = cur ? L.order2 : L.order;
+  const int cur = (int)(L.launches & 1ull);
+  unsigned int* cost_cur = L.cost[cur];
+  unsigned int* order_cur = L.order[cur];
   // launch n writes its costs into buffer n % 2 (zeroed by the sort of launch n - 2, which launch n therefore waits
   // for -- it ran during launch n - 1) and starts in the order that sort left in the same buffer's order array
   if (L.launches >= 2) {
@@ -1608,8 +1392,7 @@ static hipError_t launch_pixels_ordered(rm_ctx* ctx, const KParams& P, int flags
     Q.block_order = order_cur;
   }
   Q.block_cost = cost_cur;
-  (void)prev;
-  if ((e = fast ? rm::launch_pixels_fast(Q, stream) : ctx->gl_stack ? rm_gl_launch_pixels(&Q, stream) : rm::launch_pixels_strict(Q, stream)) != hipSuccess) return e;
+  if ((e = launch_pixel_kernel(ctx, Q, flags, stream)) != hipSuccess) return e;
   if ((e = hipEventRecord(L.rendered[cur], stream)) != hipSuccess) return e;
   if ((e = hipStreamWaitEvent(ctx->lpt_stream, L.rendered[cur], 0)) != hipSuccess) return e;
   if ((e = rm::launch_order(cost_cur, order_cur, order_cur + L.capacity, (int)tiles, ctx->lpt_stream)) != hipSuccess) return e;  // sorts and zeroes the costs
@@ -1618,22 +1401,69 @@ static hipError_t launch_pixels_ordered(rm_ctx* ctx, const KParams& P, int flags
   return hipSuccess;
 }
 
+// The pixel kernel on `stream`, its tiles in the order of their cost in the previous launch of the same job on that stream
+// (slot = which of the context's streams: a sample-in-flight slot, or RM_SP_MAX for the context's own stream).
+static hipError_t launch_pixels_ordered(rm_ctx* ctx, const KParams& P, int flags, hipStream_t stream, int slot) {
+  int gx = 0, gy = 0;
+  rm::pixel_grid(P, &gx, &gy);
+  const long long tiles = (long long)gx * gy;
+  if (!ctx->lpt_enabled || tiles < 512 || tiles > (1ll << 22))  // small jobs end on launch latency, not on a tail
+    return launch_pixel_kernel(ctx, P, flags, stream);
+  Lpt& L = ctx->lpt[slot];
+  const long long key[8] = {P.W, P.H, ((long long)P.tx << 32) | (unsigned int)P.ty, ((long long)P.tw << 32) | (unsigned int)P.th,
+                            ((long long)P.stripe_rows << 40) | ((long long)P.parts << 20) | P.part, P.row_begin,
+                            ((long long)P.scene.kind << 8) | P.u.renderMode, tiles};
+  const bool own_stream = slot == RM_SP_MAX;
+  if (hipError_t e = L.grow(tiles, own_stream ? 2 : 1, stream, ctx->lpt_stream)) return e;
+  if (std::memcmp(key, L.key, sizeof key) != 0) {
+    std::memcpy(L.key, key, sizeof key);
+    L.forget();
+  }
+  return own_stream ? launch_ordered_on_own_stream(ctx, L, P, flags, tiles) : launch_ordered_on_slot(ctx, L, P, flags, stream, tiles);
+}
+
+// The pixel kernel of one sample -- or of a batch of `batch` samples, randNoise pairs in `noise` -- on a side stream,
+// staged, and its blend on the context's stream (see SamplesInFlight).
+// depth: staging slots to rotate through (1 = a sample's render waits for the previous blend)
+static hipError_t launch_pixels_in_flight(rm_ctx* ctx, const KParams& P, int flags, int depth, int batch = 1, const float* noise = nullptr) {
+  hipError_t e;
+  SamplesInFlight& S = ctx->sp;
+  if ((e = S.ensure_slots(depth)) != hipSuccess) return e;
+  // A slot's staging holds the launch's TILE, compact (tile pixel i of sample k at k * 3 * stride + i), so it is sized by the
+  // largest batch x tile a job has used -- not by the frame: a subdivided 8192^2 render stages a tile, not 3.2 GB x batch.
+  const size_t tile_px = (size_t)P.tw * (size_t)P.th;
+  int slot = 0;
+  if ((e = S.reserve(3 * tile_px * (size_t)batch, depth, &slot)) != hipSuccess) return e;
+  KParams Q = P;
+  Q.stage = S.stage[slot];
+  Q.stage_stride = (long long)tile_px;
+  if (batch > 1) {
+    Q.batch = batch;
+    std::memcpy(Q.batch_noise, noise, sizeof(float) * 2 * (size_t)batch);
+  }
+  hipStream_t side = S.stream[slot];
+  // the render reads no plane: it only has to wait until the blend that last used this staging buffer is done
+  if ((e = hipStreamWaitEvent(side, S.free[slot], 0)) != hipSuccess) return e;
+  if (ctx->cull_event && (e = hipStreamWaitEvent(side, ctx->cull_event, 0)) != hipSuccess) return e;  // ... and for the scene's culling grid, built on the context's cull_stream (scene_cull_grid records cull_event behind the build)
+  ctx->lpt[slot].to_sort = 0;
+  if ((e = launch_pixels_ordered(ctx, Q, flags, side, slot)) != hipSuccess) return e;
+  if ((e = hipEventRecord(S.done[slot], side)) != hipSuccess) return e;
+  if ((e = sort_slot_costs(ctx, slot, side)) != hipSuccess) return e;  // behind the completion event
+  if ((e = hipStreamWaitEvent(ctx->stream, S.done[slot], 0)) != hipSuccess) return e;
+  if ((e = rm::launch_combine(Q, ctx->stream)) != hipSuccess) return e;
+  return hipEventRecord(S.free[slot], ctx->stream);
+}
+
 static hipError_t launch(rm_ctx* ctx, const KParams& P, int flags) {
   const bool wavefront = uses_wavefront(ctx, P, flags);
   ctx->last_pipeline = wavefront ? RM_PIPELINE_WAVEFRONT : RM_PIPELINE_PIXEL_KERNEL;
 #if RM_WITH_WAVEFRONT
-  if (wavefront) return launch_wavefront(ctx, P, flags);
+  if (wavefront) return launch_wavefront(ctx->wf, P, flags, ctx->stream, &ctx->error);
 #endif
-  // The half G-buffer (RM_GBUFFER_F16) is blended by rm_combine_kernel only -- the pixel kernel's own blend is the fp32 one, left
-  // exactly as it was -- so a render that writes the G-buffer (full mode, a bounce, the planes asked for: raymarcher.frag:347-351
-  // runs at bounce 0) is always staged; with RM_RENDER_NO_OVERLAP on one staging slot, so that a sample's render waits for the
-  // previous sample's blend.  No unstaged fallback: without room for the staging of the tile the call fails (render in tiles).
-  // The moments plane (RM_FB_MOMENTS) is written by rm_combine_kernel only too, under the same rule.
-  if ((P.gbuffer_half || P.moments != nullptr) && P.normal_dof != nullptr && P.u.renderMode == 0 && P.u.reflections > 0.0f)
-    return launch_pixels_in_flight(ctx, P, flags, 1, nullptr, (flags & RM_RENDER_NO_OVERLAP) ? 1 : 0);
-  // full mode with at least one bounce: the kernel's only use of the planes is the final blend, which can be split off
-  if (ctx->samples_in_flight > 1 && !(flags & RM_RENDER_NO_OVERLAP) && P.u.renderMode == 0 && P.u.reflections > 0.0f) {
-    const hipError_t e = launch_pixels_in_flight(ctx, P, flags);
+  const Staging s = staging_rule(ctx, P, flags);
+  if (s.rule == Staging::MUST) return launch_pixels_in_flight(ctx, P, flags, s.depth);
+  if (s.rule == Staging::MAY && s.depth > 1) {
+    const hipError_t e = launch_pixels_in_flight(ctx, P, flags, s.depth);
     if (e != hipErrorOutOfMemory) return e;
     (void)hipGetLastError();  // no room for the staging of this tile: render it unstaged (same bits, no overlap)
   }
@@ -1658,13 +1488,12 @@ int rm_render_samples(rm_ctx* ctx, rm_scene* scene, rm_fb* fb, const RmUniforms*
   if (count < 0 || (count > 0 && !rand_noise_pairs)) return fail(ctx, RM_ERR_INVALID, "rm_render_samples: bad count / NULL randNoise");
   if (empty) return RM_OK;
   if (count > 1 && scene->cull_wanted)  // build_params counted one sample of the tile: the call asks for `count` (the grid, if this earns it, serves the next call)
-    scene->px_seen += (long long)(count - 1) * (long long)P.tw * (long long)P.th * (fb->stripe_rows > 0 ? (long long)fb->parts : 1ll);
+    scene->px_seen += (long long)(count - 1) * job_pixel_samples(fb, P.tw, P.th);
   RM_HIP(ctx, hipSetDevice(ctx->device));
-  // Samples the pixel kernel can stage (the conditions of launch()) go out in batches: one launch per batch.
-  const bool wavefront = uses_wavefront(ctx, P, flags);
-  const bool stageable = !wavefront && !(flags & RM_RENDER_NO_OVERLAP) && P.u.renderMode == 0 && P.u.reflections > 0.0f;
+  // Samples that are staged with overlap go out in batches: one launch per batch.
+  const Staging s = staging_rule(ctx, P, flags);
   int per_launch = 1;
-  if (stageable && ctx->sample_batch != 1) {
+  if (s.rule != Staging::NEVER && !(flags & RM_RENDER_NO_OVERLAP) && ctx->sample_batch != 1) {
     per_launch = ctx->sample_batch;
     if (per_launch == 0) {
       int gx = 0, gy = 0;
@@ -1674,15 +1503,15 @@ int rm_render_samples(rm_ctx* ctx, rm_scene* scene, rm_fb* fb, const RmUniforms*
     }
     per_launch = per_launch < 1 ? 1 : per_launch > RM_BATCH_MAX ? RM_BATCH_MAX : per_launch;
     // the staging of a batch is 48 bytes per tile pixel, sample of the batch and launch in flight: within the budget
-    const size_t per_sample = sizeof(float4) * 3 * (size_t)P.tw * (size_t)P.th * (size_t)ctx->samples_in_flight;
+    const size_t per_sample = sizeof(float4) * 3 * (size_t)P.tw * (size_t)P.th * (size_t)s.depth;
     const size_t fit = staging_budget(ctx) / (per_sample ? per_sample : 1);
     if ((size_t)per_launch > fit) per_launch = fit < 1 ? 1 : (int)fit;
   }
-  ctx->last_pipeline = wavefront ? RM_PIPELINE_WAVEFRONT : RM_PIPELINE_PIXEL_KERNEL;
+  ctx->last_pipeline = uses_wavefront(ctx, P, flags) ? RM_PIPELINE_WAVEFRONT : RM_PIPELINE_PIXEL_KERNEL;
   for (int i = 0; i < count;) {
     int n = count - i < per_launch ? count - i : per_launch;
     if (n > 1) {
-      const hipError_t e = launch_pixels_in_flight(ctx, P, flags, n, rand_noise_pairs + 2 * i);
+      const hipError_t e = launch_pixels_in_flight(ctx, P, flags, s.depth, n, rand_noise_pairs + 2 * i);
       if (e == hipErrorOutOfMemory) {  // the batch's staging does not fit after all: one sample per launch from here on
         (void)hipGetLastError();
         per_launch = 1;

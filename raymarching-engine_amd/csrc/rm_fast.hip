@@ -7,7 +7,7 @@
 #include "rm_kernels.inc"
 #include "rm_frame_kernels.inc"
 #ifndef RM_WITH_WAVEFRONT
-#define RM_WITH_WAVEFRONT 0  // 1: the tests' cross-check build (rm_api.hip "the wavefront pipeline")
+#define RM_WITH_WAVEFRONT 0  // 1: the tests' cross-check build (rm_wavefront_host.inc)
 #endif
 #if RM_WITH_WAVEFRONT
 #include "rm_wavefront.inc"
