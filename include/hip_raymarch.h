@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define RM_ABI_VERSION 9 /* 9: RM_GBUFFER_F32 / _F16, rm_fb_create_fmt, rm_fb_create_striped_fmt, rm_fb_wrap_fmt, rm_fb_gbuffer, rm_fb_download_raw, rm_fb_upload_raw, RmDenoise, rm_denoise_default, rm_denoise, rm_denoise_device, rm_present_denoised, RM_FB_MOMENTS, RM_PLANE_MOMENTS, rm_fb_has_moments, RmDenoiseVariance, rm_denoise_variance_default, rm_denoise_variance, rm_denoise_variance_device, rm_present_denoised_variance (additions only); 8: RM_PRIM_TORUS / _CYLINDER / _PLANE, RM_OP_SMOOTH_SUBTRACT / _INTERSECT, rm_probe_math (additions only); 7: rm_present_sharded_finish / rm_present_sharded take the size of the host buffer (a changed signature), rm_ctx_set_cull_min_pixels, rm_ctx_set_cull_budget, rm_ctx_cull_stats; 6: rm_present_striped_rows, rm_present_sharded_start / _finish, rm_ctx_last_warning, RM_PROBE_CAST_SHADOW, RM_PRIM_KIND (additions only); 3: rm_ctx_set_sample_batch, rm_buffer_*; 4: rm_ctx_set_gl_stack; 5: RmSurface / RmSceneDesc.surfaces (the struct grew), rm_pack_present_rows, rm_present_sharded, rm_ctx_last_pipeline, RM_RENDER_NO_FAR_JUMP, RM_RENDER_NO_CULL (additions only) */
+#define RM_ABI_VERSION 9 /* 9: RM_GBUFFER_F32 / _F16, rm_fb_create_fmt, rm_fb_create_striped_fmt, rm_fb_wrap_fmt, rm_fb_gbuffer, rm_fb_download_raw, rm_fb_upload_raw, RmDenoise, rm_denoise_default, rm_denoise, rm_denoise_device, rm_present_denoised, RM_FB_MOMENTS, RM_PLANE_MOMENTS, rm_fb_has_moments, RmDenoiseVariance, rm_denoise_variance_default, rm_denoise_variance, rm_denoise_variance_device, rm_present_denoised_variance, RmDespeckle, RmFilters, RM_DENOISE_NONE / _ATROUS / _VARIANCE, rm_filters_default, rm_filter, rm_filter_device, rm_present_filtered (additions only); 8: RM_PRIM_TORUS / _CYLINDER / _PLANE, RM_OP_SMOOTH_SUBTRACT / _INTERSECT, rm_probe_math (additions only); 7: rm_present_sharded_finish / rm_present_sharded take the size of the host buffer (a changed signature), rm_ctx_set_cull_min_pixels, rm_ctx_set_cull_budget, rm_ctx_cull_stats; 6: rm_present_striped_rows, rm_present_sharded_start / _finish, rm_ctx_last_warning, RM_PROBE_CAST_SHADOW, RM_PRIM_KIND (additions only); 3: rm_ctx_set_sample_batch, rm_buffer_*; 4: rm_ctx_set_gl_stack; 5: RmSurface / RmSceneDesc.surfaces (the struct grew), rm_pack_present_rows, rm_present_sharded, rm_ctx_last_pipeline, RM_RENDER_NO_FAR_JUMP, RM_RENDER_NO_CULL (additions only) */
 
 #define RM_MAX_BOUNCES 10 /* raymarchingStepCountsArray[10], raymarcher.frag:31 */
 #define RM_MAX_LIGHTS 10  /* lightPositions[10],             raymarcher.frag:37-39 */
@@ -665,6 +665,58 @@ RM_API void rm_denoise_variance_default(RmDenoiseVariance* params);
 RM_API int rm_denoise_variance(rm_ctx* ctx, rm_fb* fb, int samples, const RmDenoiseVariance* params, float* out_host);
 RM_API int rm_denoise_variance_device(rm_ctx* ctx, rm_fb* fb, int samples, const RmDenoiseVariance* params, void* out_float4_device, void* hip_stream);
 RM_API int rm_present_denoised_variance(rm_ctx* ctx, rm_fb* fb, int samples, const RmDenoiseVariance* params, uint8_t* out_rgba8);
+
+/* ---- firefly filter (opt-in): an outlier clamp ahead of the denoisers and the present ----
+ * The direct-light specular term of raymarcher.frag:368-371 reaches 1 / (pi roughness^2) times the light colour in single
+ * pixels, and pow() leaves non-finite ones; both denoisers are edge-avoiding and keep such a pixel (above: "a pixel whose x_p
+ * is not finite keeps it").  This stage dims a pixel whose luminance stands out of its neighbourhood to the neighbourhood's
+ * rank statistic and, optionally, repairs a non-finite one; INTEGRATION.md "Firefly filter" states it in full, with what was
+ * measured.  Input is the colour plane C after `samples` (= k) samples, s = 1.0f / k; all arithmetic is fp32, every product and
+ * sum rounded on its own:
+ *   l_p = (0.2126f * (C.r * s) + 0.7152f * (C.g * s)) + 0.0722f * (C.b * s);      a pixel is VALID iff l_p is finite.
+ * The neighbourhood is the (2 radius + 1)^2 window without the centre, scanned dy = -radius..radius outer, dx inner; taps
+ * outside the image (no wrap) and invalid taps are skipped.  n = the number of valid taps, t = the (rank + 1)-th largest l_q
+ * among them (duplicates counted one by one), T = gain * t + floor (two roundings).
+ *   n <= rank:                     the pixel is unchanged.
+ *   valid centre, l_p <= T:        unchanged, bit for bit.
+ *   valid centre, l_p > T:         out.rgb = C.rgb * f, f = t / l_p: the hue stays, the luminance becomes the rank statistic's.
+ *   invalid centre, repair != 0:   out.rgb = the mean of the taps with l_q <= t: C_q.rgb summed in scan order, sequentially per
+ *                                  channel, divided by (float)count; unchanged if any channel of the result is not finite.
+ *   invalid centre, repair == 0:   unchanged.
+ * out.w = C.w always; the output is in colour-plane units, like rm_denoise's.  A pixel with l_p <= floor is therefore never
+ * changed (floor is in mean-colour, i.e. display, units), and rank = 1 tolerates one bright neighbour.  The filter reads the
+ * colour plane alone: it is the same for both G-buffer formats and runs on framebuffers without G-buffer planes. */
+typedef struct RmDespeckle {
+  int radius;    /* 1 or 2 (default 2) */
+  int rank;      /* 0..3 (default 1) */
+  float gain;    /* finite, >= 1 (default 3.0) */
+  float floor;   /* finite, >= 0 (default 0.1) */
+  int repair;    /* 0 = leave non-finite pixels (default 1) */
+  int reserved;  /* must be 0 */
+} RmDespeckle;
+
+/* The chain ahead of the present: despeckle -> denoise.  The denoise stage reads the despeckled colour where its statement
+ * reads the colour plane (the .w of its result included); its guides and the moments plane are the framebuffer's own.  With the
+ * despeckle stage off the chain is exactly rm_denoise* / rm_denoise_variance*; with both stages off it is an exact copy of the
+ * colour plane.  rm_present_filtered runs rm_present's pass on the result (the GL stack's arithmetic under rm_ctx_set_gl_stack,
+ * the framebuffer's own normal + DoF plane).  The despeckled plane lives in a buffer the context owns (grown on demand, freed
+ * with it): one filter chain at a time per context.  RM_ERR_INVALID before any device work for a NULL argument, a framebuffer of
+ * another context, a windowed or striped framebuffer (the filter reads neighbouring rows), samples < 1, `despeckle` outside
+ * 0 / 1, an unknown denoise mode, a despeckle parameter outside the ranges above (checked only when that stage is on),
+ * everything the selected denoiser refuses, and a misaligned or NULL device output.  Despeckle alone accepts a framebuffer
+ * without G-buffer planes and a wrapped whole-frame one.  Outputs as rm_denoise / rm_denoise_device / rm_present_denoised. */
+enum { RM_DENOISE_NONE = 0, RM_DENOISE_ATROUS = 1, RM_DENOISE_VARIANCE = 2 };
+typedef struct RmFilters {          /* all POD */
+  int despeckle;                    /* 0 off, 1 on */
+  int denoise;                      /* RM_DENOISE_* */
+  RmDespeckle despeckle_params;
+  RmDenoise atrous;
+  RmDenoiseVariance variance;
+} RmFilters;
+RM_API void rm_filters_default(RmFilters* filters);   /* both stages off, every parameter block at its own default */
+RM_API int rm_filter(rm_ctx* ctx, rm_fb* fb, int samples, const RmFilters* filters, float* out_host);
+RM_API int rm_filter_device(rm_ctx* ctx, rm_fb* fb, int samples, const RmFilters* filters, void* out_float4_device, void* hip_stream);
+RM_API int rm_present_filtered(rm_ctx* ctx, rm_fb* fb, int samples, const RmFilters* filters, uint8_t* out_rgba8);
 
 /* The present of a frame that ONE process renders on several GPUs -- the shape of the reference's own host: one
  * thread, one render loop (index.tsx:120), here with a context per GPU, each holding one part of the frame's stripes

@@ -142,4 +142,31 @@ class RmDenoiseVariance(C.Structure):
 DENOISE_VARIANCE_DEFAULTS = dict(iterations=3, sigma_luminance=4.0, sigma_normal=1.0, sigma_depth=0.2)  # rm_denoise_variance_default
 
 
-assert C.sizeof(RmPrim) == 32 and C.sizeof(RmSurface) == 48
+class RmDespeckle(C.Structure):
+    """Parameters of the firefly filter (ABI 9): the outlier clamp ahead of the denoisers (include/hip_raymarch.h)."""
+    _fields_ = [
+        ("radius", C.c_int32),
+        ("rank", C.c_int32),
+        ("gain", C.c_float),
+        ("floor", C.c_float),
+        ("repair", C.c_int32),
+        ("reserved", C.c_int32),
+    ]
+
+
+DESPECKLE_DEFAULTS = dict(radius=2, rank=1, gain=3.0, floor=0.1, repair=1)  # rm_filters_default's despeckle_params
+
+RM_DENOISE_NONE, RM_DENOISE_ATROUS, RM_DENOISE_VARIANCE = 0, 1, 2
+
+
+class RmFilters(C.Structure):
+    """The chain ahead of the present, despeckle -> denoise (ABI 9; rm_filter, rm_filter_device, rm_present_filtered)."""
+    _fields_ = [
+        ("despeckle", C.c_int32),
+        ("denoise", C.c_int32),
+        ("despeckle_params", RmDespeckle),
+        ("atrous", RmDenoise),
+        ("variance", RmDenoiseVariance),
+    ]
+
+assert C.sizeof(RmPrim) == 32 and C.sizeof(RmSurface) == 48 and C.sizeof(RmDespeckle) == 24 and C.sizeof(RmFilters) == 72

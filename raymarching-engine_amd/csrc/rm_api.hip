@@ -185,6 +185,8 @@ struct rm_ctx {
   size_t present_cap = 0;          // pixels
   float4* denoise_buf[3] = {nullptr, nullptr, nullptr};  // rm_denoise*: the two ping-pong buffers of x and the guide, grown on demand
   size_t denoise_cap = 0;          // pixels
+  float4* despeckle_buf = nullptr;  // rm_filter*: the despeckled colour plane the denoise stage reads, grown on demand
+  size_t despeckle_cap = 0;         // pixels
   // rm_present_sharded (one process driving several GPUs): this context's rows of the payload, and on the context that
   // shows the frame the gathered parts and the frame in image order; grown on demand, freed with the context
   void* shard_rows = nullptr;  size_t shard_rows_cap = 0;    // this context's rows of the payload (packed float4 or RGBA8)
@@ -336,6 +338,7 @@ void rm_ctx_destroy(rm_ctx* ctx) {
   if (ctx->present_buf) (void)hipFree(ctx->present_buf);
   for (auto* b : ctx->denoise_buf)
     if (b) (void)hipFree(b);
+  if (ctx->despeckle_buf) (void)hipFree(ctx->despeckle_buf);
   if (ctx->shard_rows) (void)hipFree(ctx->shard_rows);
   if (ctx->shard_recv) (void)hipFree(ctx->shard_recv);
   if (ctx->shard_frame) (void)hipFree(ctx->shard_frame);
@@ -1672,10 +1675,12 @@ static int denoise_check(rm_ctx* ctx, rm_fb* fb, int samples, const RmDenoise* p
   return RM_OK;
 }
 
-// Enqueues the passes on `stream`.  out: the result, or NULL for one of the context's buffers; *result = where it is (the
-// colour plane itself for 0 iterations and no `out`).  var: the variance-guided mode, d.sigma_color holding sigma_luminance.
-static int denoise_enqueue(rm_ctx* ctx, rm_fb* fb, int samples, const RmDenoise* params, float4* out, hipStream_t stream, const float4** result,
-                           bool var = false) {
+// Enqueues the passes on `stream`.  color: the colour the filter reads where the colour plane stands in its statement (the
+// plane itself, or rm_filter's despeckled copy of it); the guides and the moments are the framebuffer's own.  out: the result, or
+// NULL for one of the context's buffers; *result = where it is (`color` itself for 0 iterations and no `out`).  var: the
+// variance-guided mode, d.sigma_color holding sigma_luminance.
+static int denoise_enqueue(rm_ctx* ctx, rm_fb* fb, const float4* color, int samples, const RmDenoise* params, float4* out, hipStream_t stream,
+                           const float4** result, bool var = false) {
   RmDenoise d;
   if (params) d = *params;
   else rm_denoise_default(&d);
@@ -1683,8 +1688,8 @@ static int denoise_enqueue(rm_ctx* ctx, rm_fb* fb, int samples, const RmDenoise*
   const size_t pixels = (size_t)fb->width * (size_t)fb->height;
   const int L = d.iterations;
   if (L == 0) {
-    if (out) RM_HIP(ctx, hipMemcpyAsync(out, fb->plane[0], pixels * sizeof(float4), hipMemcpyDeviceToDevice, stream));
-    *result = out ? out : fb->plane[0];
+    if (out) RM_HIP(ctx, hipMemcpyAsync(out, color, pixels * sizeof(float4), hipMemcpyDeviceToDevice, stream));
+    *result = out ? out : color;
     return RM_OK;
   }
   if (ctx->denoise_cap < pixels) {  // a live loop denoises every present: the buffers stay with the context
@@ -1699,7 +1704,7 @@ static int denoise_enqueue(rm_ctx* ctx, rm_fb* fb, int samples, const RmDenoise*
     ctx->denoise_cap = pixels;
   }
   DenoisePass P{};
-  P.color = fb->plane[0];
+  P.color = color;
   P.normal_dof = fb->plane[1];
   P.albedo_depth = fb->plane[2];
   P.guide = ctx->denoise_buf[2];
@@ -1728,14 +1733,14 @@ int rm_denoise_device(rm_ctx* ctx, rm_fb* fb, int samples, const RmDenoise* para
   if (!out_float4_device || (reinterpret_cast<uintptr_t>(out_float4_device) & 15u))
     return fail(ctx, RM_ERR_INVALID, "rm_denoise_device: the output must be a 16-byte aligned device buffer");
   const float4* r = nullptr;
-  return denoise_enqueue(ctx, fb, samples, params, static_cast<float4*>(out_float4_device), hip_stream ? static_cast<hipStream_t>(hip_stream) : ctx->stream, &r);
+  return denoise_enqueue(ctx, fb, fb->plane[0], samples, params, static_cast<float4*>(out_float4_device), hip_stream ? static_cast<hipStream_t>(hip_stream) : ctx->stream, &r);
 }
 
 int rm_denoise(rm_ctx* ctx, rm_fb* fb, int samples, const RmDenoise* params, float* out_host) {
   if (int rc = denoise_check(ctx, fb, samples, params, "rm_denoise")) return rc;
   if (!out_host) return fail(ctx, RM_ERR_INVALID, "rm_denoise: NULL argument");
   const float4* r = nullptr;
-  if (int rc = denoise_enqueue(ctx, fb, samples, params, nullptr, ctx->stream, &r)) return rc;
+  if (int rc = denoise_enqueue(ctx, fb, fb->plane[0], samples, params, nullptr, ctx->stream, &r)) return rc;
   RM_HIP(ctx, hipMemcpyAsync(out_host, r, (size_t)fb->width * (size_t)fb->height * sizeof(float4), hipMemcpyDeviceToHost, ctx->stream));
   RM_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return RM_OK;
@@ -1745,7 +1750,7 @@ int rm_present_denoised(rm_ctx* ctx, rm_fb* fb, int samples, const RmDenoise* pa
   if (int rc = denoise_check(ctx, fb, samples, params, "rm_present_denoised")) return rc;
   if (!out_rgba8) return fail(ctx, RM_ERR_INVALID, "rm_present_denoised: NULL argument");
   const float4* r = nullptr;
-  if (int rc = denoise_enqueue(ctx, fb, samples, params, nullptr, ctx->stream, &r)) return rc;
+  if (int rc = denoise_enqueue(ctx, fb, fb->plane[0], samples, params, nullptr, ctx->stream, &r)) return rc;
   return present_planes(ctx, r, fb->plane[1], fb->gbuffer == RM_GBUFFER_F16, fb->width, fb->height, samples, out_rgba8);
 }
 
@@ -1780,7 +1785,7 @@ int rm_denoise_variance_device(rm_ctx* ctx, rm_fb* fb, int samples, const RmDeno
   if (!out_float4_device || (reinterpret_cast<uintptr_t>(out_float4_device) & 15u))
     return fail(ctx, RM_ERR_INVALID, "rm_denoise_variance_device: the output must be a 16-byte aligned device buffer");
   const float4* r = nullptr;
-  return denoise_enqueue(ctx, fb, samples, &d, static_cast<float4*>(out_float4_device), hip_stream ? static_cast<hipStream_t>(hip_stream) : ctx->stream, &r, true);
+  return denoise_enqueue(ctx, fb, fb->plane[0], samples, &d, static_cast<float4*>(out_float4_device), hip_stream ? static_cast<hipStream_t>(hip_stream) : ctx->stream, &r, true);
 }
 
 int rm_denoise_variance(rm_ctx* ctx, rm_fb* fb, int samples, const RmDenoiseVariance* params, float* out_host) {
@@ -1788,7 +1793,7 @@ int rm_denoise_variance(rm_ctx* ctx, rm_fb* fb, int samples, const RmDenoiseVari
   if (int rc = denoise_variance_check(ctx, fb, samples, params, "rm_denoise_variance", &d)) return rc;
   if (!out_host) return fail(ctx, RM_ERR_INVALID, "rm_denoise_variance: NULL argument");
   const float4* r = nullptr;
-  if (int rc = denoise_enqueue(ctx, fb, samples, &d, nullptr, ctx->stream, &r, true)) return rc;
+  if (int rc = denoise_enqueue(ctx, fb, fb->plane[0], samples, &d, nullptr, ctx->stream, &r, true)) return rc;
   RM_HIP(ctx, hipMemcpyAsync(out_host, r, (size_t)fb->width * (size_t)fb->height * sizeof(float4), hipMemcpyDeviceToHost, ctx->stream));
   RM_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return RM_OK;
@@ -1799,7 +1804,125 @@ int rm_present_denoised_variance(rm_ctx* ctx, rm_fb* fb, int samples, const RmDe
   if (int rc = denoise_variance_check(ctx, fb, samples, params, "rm_present_denoised_variance", &d)) return rc;
   if (!out_rgba8) return fail(ctx, RM_ERR_INVALID, "rm_present_denoised_variance: NULL argument");
   const float4* r = nullptr;
-  if (int rc = denoise_enqueue(ctx, fb, samples, &d, nullptr, ctx->stream, &r, true)) return rc;
+  if (int rc = denoise_enqueue(ctx, fb, fb->plane[0], samples, &d, nullptr, ctx->stream, &r, true)) return rc;
+  return present_planes(ctx, r, fb->plane[1], fb->gbuffer == RM_GBUFFER_F16, fb->width, fb->height, samples, out_rgba8);
+}
+
+// ---- the filter chain ahead of the present: despeckle -> denoise (rm_frame_kernels.inc "despeckle") ------------------
+
+void rm_filters_default(RmFilters* f) {
+  if (!f) return;
+  std::memset(f, 0, sizeof *f);  // both stages off
+  f->despeckle_params.radius = 2;
+  f->despeckle_params.rank = 1;
+  f->despeckle_params.gain = 3.0f;
+  f->despeckle_params.floor = 0.1f;
+  f->despeckle_params.repair = 1;
+  rm_denoise_default(&f->atrous);
+  rm_denoise_variance_default(&f->variance);
+}
+
+// Every check of the rm_filter entry points, before any device work: the chain's own values first (they need neither a context
+// nor a GPU), then the handles, then what the selected denoiser refuses.  *d = the denoise stage's parameters as denoise_enqueue
+// takes them.
+static int filters_check(rm_ctx* ctx, rm_fb* fb, int samples, const RmFilters* f, const char* who, RmDenoise* d) {
+  if (!f) return fail(ctx, RM_ERR_INVALID, std::string(who) + ": NULL argument");
+  if (f->despeckle != 0 && f->despeckle != 1) return fail(ctx, RM_ERR_INVALID, std::string(who) + ": despeckle must be 0 or 1");
+  if (f->denoise != RM_DENOISE_NONE && f->denoise != RM_DENOISE_ATROUS && f->denoise != RM_DENOISE_VARIANCE)
+    return fail(ctx, RM_ERR_INVALID, std::string(who) + ": unknown denoise mode");
+  if (f->despeckle) {
+    const RmDespeckle& p = f->despeckle_params;
+    if (p.radius != 1 && p.radius != 2) return fail(ctx, RM_ERR_INVALID, std::string(who) + ": despeckle radius must be 1 or 2");
+    if (p.rank < 0 || p.rank > 3) return fail(ctx, RM_ERR_INVALID, std::string(who) + ": despeckle rank must be in 0..3");
+    if (!(std::isfinite(p.gain) && p.gain >= 1.0f)) return fail(ctx, RM_ERR_INVALID, std::string(who) + ": despeckle gain must be finite and >= 1");
+    if (!(std::isfinite(p.floor) && p.floor >= 0.0f)) return fail(ctx, RM_ERR_INVALID, std::string(who) + ": despeckle floor must be finite and >= 0");
+    if (p.reserved != 0) return fail(ctx, RM_ERR_INVALID, std::string(who) + ": despeckle reserved must be 0");
+  }
+  if (!ctx || !fb) return fail(ctx, RM_ERR_INVALID, std::string(who) + ": NULL argument");
+  if (fb->ctx != ctx) return fail(ctx, RM_ERR_INVALID, std::string(who) + ": framebuffer belongs to another context");
+  if (fb->stripe_rows > 0 || fb->row_begin != 0 || fb->row_count != fb->height)
+    return fail(ctx, RM_ERR_INVALID, std::string(who) + ": the filter reads neighbouring rows, so it needs a framebuffer holding the whole frame");
+  if (samples < 1) return fail(ctx, RM_ERR_INVALID, std::string(who) + ": samples must be >= 1");
+  if (f->denoise == RM_DENOISE_ATROUS) {
+    *d = f->atrous;
+    return denoise_check(ctx, fb, samples, d, who);
+  }
+  if (f->denoise == RM_DENOISE_VARIANCE) return denoise_variance_check(ctx, fb, samples, &f->variance, who, d);
+  return RM_OK;
+}
+
+// Enqueues the chain on `stream`.  out: the result, or NULL for one of the context's buffers; *result = where it is (the colour
+// plane itself when both stages are off and there is no `out`).
+static int filters_enqueue(rm_ctx* ctx, rm_fb* fb, int samples, const RmFilters* f, const RmDenoise* d, float4* out, hipStream_t stream,
+                           const float4** result) {
+  const float4* color = fb->plane[0];
+  const size_t pixels = (size_t)fb->width * (size_t)fb->height;
+  if (f->despeckle) {
+    RM_HIP(ctx, hipSetDevice(ctx->device));
+    float4* dst = (f->denoise == RM_DENOISE_NONE && out) ? out : nullptr;
+    if (!dst) {
+      if (ctx->despeckle_cap < pixels) {  // lives with the context like the denoiser's buffers
+        RM_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        RM_HIP(ctx, hipStreamSynchronize(stream));
+        if (ctx->despeckle_buf) (void)hipFree(ctx->despeckle_buf);
+        ctx->despeckle_buf = nullptr;
+        ctx->despeckle_cap = 0;
+        RM_HIP(ctx, hipMalloc(reinterpret_cast<void**>(&ctx->despeckle_buf), pixels * sizeof(float4)));
+        ctx->despeckle_cap = pixels;
+      }
+      dst = ctx->despeckle_buf;
+    }
+    DespecklePass P{};
+    P.color = fb->plane[0];
+    P.out = dst;
+    P.W = fb->width;
+    P.H = fb->height;
+    P.s = 1.0f / (float)samples;  // present_device's scale
+    P.gain = f->despeckle_params.gain;
+    P.floor = f->despeckle_params.floor;
+    P.repair = f->despeckle_params.repair;
+    RM_HIP(ctx, rm::launch_despeckle(P, f->despeckle_params.radius, f->despeckle_params.rank, stream));
+    color = dst;
+    if (f->denoise == RM_DENOISE_NONE) {
+      *result = dst;
+      return RM_OK;
+    }
+  }
+  if (f->denoise == RM_DENOISE_NONE) {  // both stages off: an exact copy of the colour plane
+    RM_HIP(ctx, hipSetDevice(ctx->device));
+    if (out) RM_HIP(ctx, hipMemcpyAsync(out, color, pixels * sizeof(float4), hipMemcpyDeviceToDevice, stream));
+    *result = out ? out : color;
+    return RM_OK;
+  }
+  return denoise_enqueue(ctx, fb, color, samples, d, out, stream, result, f->denoise == RM_DENOISE_VARIANCE);
+}
+
+int rm_filter_device(rm_ctx* ctx, rm_fb* fb, int samples, const RmFilters* filters, void* out_float4_device, void* hip_stream) {
+  RmDenoise d{};
+  if (int rc = filters_check(ctx, fb, samples, filters, "rm_filter_device", &d)) return rc;
+  if (!out_float4_device || (reinterpret_cast<uintptr_t>(out_float4_device) & 15u))
+    return fail(ctx, RM_ERR_INVALID, "rm_filter_device: the output must be a 16-byte aligned device buffer");
+  const float4* r = nullptr;
+  return filters_enqueue(ctx, fb, samples, filters, &d, static_cast<float4*>(out_float4_device), hip_stream ? static_cast<hipStream_t>(hip_stream) : ctx->stream, &r);
+}
+
+int rm_filter(rm_ctx* ctx, rm_fb* fb, int samples, const RmFilters* filters, float* out_host) {
+  RmDenoise d{};
+  if (int rc = filters_check(ctx, fb, samples, filters, "rm_filter", &d)) return rc;
+  if (!out_host) return fail(ctx, RM_ERR_INVALID, "rm_filter: NULL argument");
+  const float4* r = nullptr;
+  if (int rc = filters_enqueue(ctx, fb, samples, filters, &d, nullptr, ctx->stream, &r)) return rc;
+  RM_HIP(ctx, hipMemcpyAsync(out_host, r, (size_t)fb->width * (size_t)fb->height * sizeof(float4), hipMemcpyDeviceToHost, ctx->stream));
+  RM_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return RM_OK;
+}
+
+int rm_present_filtered(rm_ctx* ctx, rm_fb* fb, int samples, const RmFilters* filters, uint8_t* out_rgba8) {
+  RmDenoise d{};
+  if (int rc = filters_check(ctx, fb, samples, filters, "rm_present_filtered", &d)) return rc;
+  if (!out_rgba8) return fail(ctx, RM_ERR_INVALID, "rm_present_filtered: NULL argument");
+  const float4* r = nullptr;
+  if (int rc = filters_enqueue(ctx, fb, samples, filters, &d, nullptr, ctx->stream, &r)) return rc;
   return present_planes(ctx, r, fb->plane[1], fb->gbuffer == RM_GBUFFER_F16, fb->width, fb->height, samples, out_rgba8);
 }
 

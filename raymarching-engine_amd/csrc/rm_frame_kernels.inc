@@ -490,6 +490,111 @@ hipError_t launch_denoise_pass(const DenoisePass& P, bool half, bool prep, bool 
 hipError_t launch_denoise_variance_pass(const DenoisePass& P, bool half, bool prep, bool last, hipStream_t stream) {
   return launch_denoise_pass_t<true>(P, half, prep, last, stream);
 }
+
+// ---- despeckle: the firefly filter ahead of the denoisers and the present (rm_filter*, opt-in) ----------------------
+// An outlier clamp on the colour plane after k samples; include/hip_raymarch.h and INTEGRATION.md "Firefly filter" state it in
+// full, tests/despeckle_ref.py restates it in float32.  With s = 1.0f / k, every product and sum rounded on its own:
+//   l_p = (0.2126f * (C.r * s) + 0.7152f * (C.g * s)) + 0.0722f * (C.b * s);   a pixel is valid iff l_p is finite.
+// Over the (2 radius + 1)^2 window without the centre (dy outer, dx inner; taps outside the image and invalid taps skipped):
+//   n = the number of valid taps,  t = the (rank + 1)-th largest l_q,  T = gain * t + floor.
+//   n <= rank: unchanged.   valid centre: l_p <= T unchanged (bit for bit), else C.rgb * (t / l_p).
+//   invalid centre: with repair the mean of the taps with l_q <= t (summed in scan order, / (float)count; unchanged unless
+//   every channel of it is finite), else unchanged.   .w is always C.w.
+// One launch, 16 x 16 pixels per workgroup, one thread per pixel.  The tile and its halo of RADIUS pixels are staged in LDS as
+// the colour and l (computed once per staged pixel); a slot outside the image is marked invalid (NaN) and never read from
+// memory.  The RANK + 1 largest values stay in registers (unrolled insertion), and only an invalid centre walks the window a
+// second time.  Reads the colour plane alone: 16 B in, 16 B out per pixel, whatever the G-buffer.
+template <int RADIUS, int RANK>
+__global__ __launch_bounds__(256) void rm_despeckle_kernel(const DespecklePass P) {
+  constexpr int SPAN = 16 + 2 * RADIUS;
+  __shared__ float4 sc[SPAN * SPAN];
+  __shared__ float sl[SPAN * SPAN];
+  const int lx = threadIdx.x % 16, ly = threadIdx.x / 16;
+  const int x = blockIdx.x * 16 + lx, y = blockIdx.y * 16 + ly;
+  const int x0 = (int)blockIdx.x * 16 - RADIUS, y0 = (int)blockIdx.y * 16 - RADIUS;
+  for (int i = threadIdx.x; i < SPAN * SPAN; i += 256) {
+    const int gx = x0 + i % SPAN, gy = y0 + i / SPAN;
+    if (gx < 0 || gx >= P.W || gy < 0 || gy >= P.H) {
+      sl[i] = __int_as_float(0x7fc00000);  // invalid: a tap outside the image is skipped
+      continue;
+    }
+    const float4 c = P.color[(size_t)gy * P.W + gx];
+    sc[i] = c;
+    sl[i] = (0.2126f * (c.x * P.s) + 0.7152f * (c.y * P.s)) + 0.0722f * (c.z * P.s);
+  }
+  __syncthreads();
+  if (x >= P.W || y >= P.H) return;
+  const int ci = (ly + RADIUS) * SPAN + lx + RADIUS;
+  const float4 c = sc[ci];
+  const float lp = sl[ci];
+  float top[RANK + 1];  // the RANK + 1 largest valid l_q so far, descending
+#pragma unroll
+  for (int j = 0; j <= RANK; j++) top[j] = -INFINITY;
+  int n = 0;
+#pragma unroll
+  for (int dy = -RADIUS; dy <= RADIUS; dy++) {
+#pragma unroll
+    for (int dx = -RADIUS; dx <= RADIUS; dx++) {
+      if (dx == 0 && dy == 0) continue;
+      float v = sl[ci + dy * SPAN + dx];
+      if (!isfinite(v)) continue;
+      n++;
+#pragma unroll
+      for (int j = 0; j <= RANK; j++) {
+        const float hi = fmaxf(v, top[j]), lo = fminf(v, top[j]);  // both finite or -inf: no NaN reaches here
+        top[j] = hi;
+        v = lo;
+      }
+    }
+  }
+  float4 r = c;
+  if (n > RANK) {
+    const float t = top[RANK];
+    if (isfinite(lp)) {
+      const float T = P.gain * t + P.floor;
+      if (lp > T) {
+        const float f = t / lp;
+        r = make_float4(c.x * f, c.y * f, c.z * f, c.w);
+      }
+    } else if (P.repair) {
+      float ax = 0.0f, ay = 0.0f, az = 0.0f;
+      int count = 0;
+      for (int dy = -RADIUS; dy <= RADIUS; dy++) {
+        for (int dx = -RADIUS; dx <= RADIUS; dx++) {
+          if (dx == 0 && dy == 0) continue;
+          const int q = ci + dy * SPAN + dx;
+          const float v = sl[q];
+          if (!isfinite(v) || !(v <= t)) continue;
+          const float4 cq = sc[q];
+          ax += cq.x;
+          ay += cq.y;
+          az += cq.z;
+          count++;
+        }
+      }
+      const float mx = ax / (float)count, my = ay / (float)count, mz = az / (float)count;  // count >= 1: the tap that gave t
+      if (isfinite(mx) && isfinite(my) && isfinite(mz)) r = make_float4(mx, my, mz, c.w);
+    }
+  }
+  P.out[(size_t)y * P.W + x] = r;
+}
+
+hipError_t launch_despeckle(const DespecklePass& P, int radius, int rank, hipStream_t stream) {
+  const dim3 grid((P.W + 15) / 16, (P.H + 15) / 16);
+#define RM_DESPECKLE(RADIUS)                                                                                   \
+  switch (rank) {                                                                                              \
+    case 0: hipLaunchKernelGGL((rm_despeckle_kernel<RADIUS, 0>), grid, dim3(256), 0, stream, P); break;        \
+    case 1: hipLaunchKernelGGL((rm_despeckle_kernel<RADIUS, 1>), grid, dim3(256), 0, stream, P); break;        \
+    case 2: hipLaunchKernelGGL((rm_despeckle_kernel<RADIUS, 2>), grid, dim3(256), 0, stream, P); break;        \
+    case 3: hipLaunchKernelGGL((rm_despeckle_kernel<RADIUS, 3>), grid, dim3(256), 0, stream, P); break;        \
+    default: return hipErrorInvalidValue;                                                                      \
+  }
+  if (radius == 1) { RM_DESPECKLE(1) }
+  else if (radius == 2) { RM_DESPECKLE(2) }
+  else return hipErrorInvalidValue;
+#undef RM_DESPECKLE
+  return hipGetLastError();
+}
 #endif
 
 }  // namespace rm

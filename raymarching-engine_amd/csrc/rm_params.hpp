@@ -309,6 +309,16 @@ struct DenoisePass {
   float sigma_l;             // sigma_luminance
 };
 
+// The firefly filter's one launch (rm_frame_kernels.inc "despeckle"): colour plane in, despeckled colour out.
+struct DespecklePass {
+  const float4* color;
+  float4* out;
+  int W, H;
+  float s;            // 1 / samples
+  float gain, floor;  // T = gain * t + floor
+  int repair;         // != 0: an invalid centre takes the mean of its ordinary taps
+};
+
 namespace rm {
 enum {
   WF_POS = 0,   // xyz ray position (march in/out), w = step budget
@@ -369,6 +379,8 @@ hipError_t launch_present_rows(const float4* color, long long pixels, float brig
 hipError_t launch_denoise_pass(const DenoisePass& P, bool half, bool prep, bool last, hipStream_t stream);
 // one pass of rm_denoise_variance (the same, x.w = the variance; P.moments read by pass 0)
 hipError_t launch_denoise_variance_pass(const DenoisePass& P, bool half, bool prep, bool last, hipStream_t stream);
+// the firefly filter ahead of the denoisers (rm_filter*); radius 1 or 2, rank 0..3
+hipError_t launch_despeckle(const DespecklePass& P, int radius, int rank, hipStream_t stream);
 hipError_t launch_present(const float4* color, const void* normal_dof, bool nd_half, int W, int H, float brightness, uchar4* out, hipStream_t stream);
 hipError_t launch_present_striped(const float4* color, const float4* normal_dof, int W, int H, float brightness, uchar4* out, int stripe_rows, int parts, int part,
                                   int local_rows, hipStream_t stream);

@@ -51,15 +51,23 @@ export type RenderJobSchema = {
 export type RenderJobFramebufferInfo = {
   width: number; height: number; frameid: number; download(plane?: 0 | 1 | 2): Float32Array;
   /** display.frag on the GPU: RGBA8, row 0 = bottom; `denoise` presents the denoised colour (rm_present_denoised), or with
-   *  "variance" / { mode: "variance", ... } the variance-guided filter's (rm_present_denoised_variance; needs { moments: true }) */
-  present(samples: number, opts?: { denoise?: DenoiseOption }): Uint8Array;
+   *  "variance" / { mode: "variance", ... } the variance-guided filter's (rm_present_denoised_variance; needs { moments: true });
+   *  `despeckle` runs the firefly filter ahead of either (rm_present_filtered); without it the calls are the ones above */
+  present(samples: number, opts?: { denoise?: DenoiseOption; despeckle?: DespeckleOption }): Uint8Array;
+  /** the colour plane after the chain despeckle -> denoise (rm_filter): colour-plane units, row 0 = bottom */
+  filter(samples: number, opts?: { denoise?: DenoiseOption; despeckle?: DespeckleOption }): Float32Array;
   /** the colour plane after the variance-guided filter (rm_denoise_variance; needs { moments: true }) */
   denoiseVariance(samples: number, params?: true | "variance" | DenoiseVarianceParams): Float32Array;
   /** the colour plane after the G-buffer-guided a-trous filter (rm_denoise): colour-plane units, row 0 = bottom */
   denoise(samples: number, params?: true | DenoiseParams): Float32Array;
   /** canvas.toDataURL("image/png") of the presented frame (index.tsx:470-476) */
-  toDataURL(samples: number, opts?: { denoise?: DenoiseOption }): string;
+  toDataURL(samples: number, opts?: { denoise?: DenoiseOption; despeckle?: DespeckleOption }): string;
 };
+/** RmDespeckle (include/hip_raymarch.h): the firefly filter; fields left out take DESPECKLE_DEFAULTS' values */
+export type DespeckleParams = { radius?: 1 | 2; rank?: 0 | 1 | 2 | 3; gain?: number; floor?: number; repair?: number | boolean };
+export type DespeckleOption = true | DespeckleParams;
+export const DESPECKLE_DEFAULTS: { radius: number; rank: number; gain: number; floor: number; repair: number };
+export function despeckleParams(params?: true | DespeckleParams | null): { radius: number; rank: number; gain: number; floor: number; repair: number };
 /** RmDenoiseVariance (include/hip_raymarch.h): fields left out take DENOISE_VARIANCE_DEFAULTS' values */
 export type DenoiseVarianceParams = { iterations?: number; sigma_luminance?: number; sigma_normal?: number; sigma_depth?: number };
 export type DenoiseOption = true | DenoiseParams | (DenoiseParams & { mode: "atrous" }) | "variance" | (DenoiseVarianceParams & { mode: "variance" });
@@ -87,8 +95,8 @@ export class RenderJobContext {
  *  8-row stripes; `present(samples)` of its framebuffer set assembles the canvas on the first GPU (rm_present_sharded). */
 export type ShardedFramebufferInfo = {
   width: number; height: number; frameid: number; sharded: true; dof: boolean; rows(): number[];
-  /** throws when asked to denoise: the filter reads rows other GPUs hold */
-  present(samples: number, dof?: boolean, opts?: { denoise?: undefined }): Uint8Array; toDataURL(samples: number): string;
+  /** throws when asked to denoise or to despeckle: the filters read rows other GPUs hold */
+  present(samples: number, dof?: boolean, opts?: { denoise?: undefined; despeckle?: undefined }): Uint8Array; toDataURL(samples: number): string;
   /** the present in two halves (rm_present_sharded_start / _finish): the frame travels while the next samples render; one at a time */
   startPresent(samples: number, dof?: boolean): void; finishPresent(): Uint8Array; pendingPresent: boolean;
 };

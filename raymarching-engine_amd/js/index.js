@@ -22,7 +22,7 @@ const RM = {
   PRIM_SPHERE: 0, PRIM_BOX: 1, PRIM_REPEAT: 2, PRIM_FOLD: 3, PRIM_KIND: 4, PRIM_TORUS: 5, PRIM_CYLINDER: 6, PRIM_PLANE: 7,
   OP_UNION: 0, OP_SMOOTH_UNION: 1, OP_SUBTRACT: 2, OP_INTERSECT: 3, OP_SMOOTH_SUBTRACT: 4, OP_SMOOTH_INTERSECT: 5,
   RENDER_STRICT: 0, RENDER_FAST: 1, RENDER_COLOR_ONLY: 2, RENDER_MEGAKERNEL: 4, RENDER_WAVEFRONT: 16, RENDER_NO_OVERLAP: 32, RENDER_NO_FAR_JUMP: 64, RENDER_NO_CULL: 128,
-  GBUFFER_F32: 0, GBUFFER_F16: 1, FB_MOMENTS: 0x100, PLANE_MOMENTS: 3,
+  GBUFFER_F32: 0, GBUFFER_F16: 1, FB_MOMENTS: 0x100, PLANE_MOMENTS: 3, DENOISE_NONE: 0, DENOISE_ATROUS: 1, DENOISE_VARIANCE: 2,
 };
 // G-buffer formats of a context's framebuffers (include/hip_raymarch.h RM_GBUFFER_*): "f32", the default (the goldens' software GL
 // stack), or "f16", the reference's RGBA16F normal + DoF radius and albedo + depth planes (LoadRenderJobContext.tsx:81-119)
@@ -291,13 +291,21 @@ class RenderJobContext {  // RenderJobContext + loadRenderJobContext (LoadRender
                    // the present pass (display.frag) on the GPU: RGBA8, row 0 = bottom
                    // opts.denoise (true or the parameters of denoiseParams): the denoised colour through the same pass (rm_present_denoised);
                    // "variance" or { mode: "variance", ... } (denoiseVarianceParams): the variance-guided filter's (rm_present_denoised_variance)
+                   // opts.despeckle (true or the parameters of despeckleParams): the firefly filter ahead of either (rm_present_filtered);
+                   // without it the calls are the ones above
                    present: (samples, opts = {}) => {
                      const out = new Uint8Array(w * h * 4);
                      const d = opts.denoise;
+                     if (opts.despeckle !== undefined && opts.despeckle !== null && opts.despeckle !== false) {
+                       addon.presentFiltered(this.ctx, fb, samples, filters(opts), out);
+                       return out;
+                     }
                      if (d === undefined || d === null || d === false) addon.present(this.ctx, fb, samples, out);
                      else if (isVarianceMode(d)) addon.presentDenoisedVariance(this.ctx, fb, samples, denoiseVarianceParams(d), out);
                      else addon.presentDenoised(this.ctx, fb, samples, denoiseParams(d && d.mode === "atrous" ? withoutMode(d) : d), out);
                      return out; },
+                   // the colour plane after the chain despeckle -> denoise (rm_filter): opts = { despeckle, denoise } as present takes them
+                   filter: (samples, opts = {}) => { const out = new Float32Array(w * h * 4); addon.filter(this.ctx, fb, samples, filters(opts), out); return out; },
                    // the colour plane after the variance-guided filter (rm_denoise_variance; needs { moments: true }): as denoise
                    denoiseVariance: (samples, params) => { const out = new Float32Array(w * h * 4); addon.denoiseVariance(this.ctx, fb, samples, denoiseVarianceParams(params), out); return out; },
                    // the colour plane after the G-buffer-guided a-trous filter (rm_denoise): Float32Array, colour-plane units, row 0 = bottom
@@ -371,6 +379,8 @@ class ShardedRenderJobContext {
                    present: (samples, dof = info.dof, opts = {}) => {
                      if (opts.denoise !== undefined || (dof !== null && typeof dof === "object"))
                        throw new Error("present: denoising a sharded frame is not supported (the filter reads rows other GPUs hold)");
+                     if (opts.despeckle !== undefined)
+                       throw new Error("present: the firefly filter on a sharded frame is not supported (it reads rows other GPUs hold)");
                      const out = new Uint8Array(w * h * 4); addon.presentSharded(this.ctxs, fbs, samples, !!dof, out); return out; },
                    // the same in two halves (rm_present_sharded_start / _finish): startPresent snapshots and sends and returns at once, so a
                    // `present` callback that calls it lets doRenderJob hand out the next samples while the frame travels; finishPresent
@@ -493,6 +503,37 @@ function denoiseVarianceParams(params) {
   return p;
 }
 
+// ---- firefly filter parameters (include/hip_raymarch.h RmDespeckle, rm_filters_default) ----
+const DESPECKLE_DEFAULTS = { radius: 2, rank: 1, gain: 3.0, floor: 0.1, repair: 1 };
+// true / undefined / null = the defaults, or an object with some of DESPECKLE_DEFAULTS' fields; checked as the library checks them
+function despeckleParams(params) {
+  const p = { ...DESPECKLE_DEFAULTS };
+  if (params !== undefined && params !== null && params !== true) {
+    if (typeof params !== "object") throw new TypeError("despeckle: expected true or an object of parameters");
+    for (const [k, v] of Object.entries(params)) {
+      if (!(k in DESPECKLE_DEFAULTS)) throw new TypeError("despeckle: unknown parameter " + k);
+      p[k] = k === "repair" && typeof v === "boolean" ? Number(v) : v;
+    }
+  }
+  if (p.radius !== 1 && p.radius !== 2) throw new RangeError("despeckle: radius must be 1 or 2");
+  if (!Number.isInteger(p.rank) || p.rank < 0 || p.rank > 3) throw new RangeError("despeckle: rank must be an integer in 0..3");
+  if (!(typeof p.gain === "number" && Number.isFinite(p.gain) && p.gain >= 1)) throw new RangeError("despeckle: gain must be finite and >= 1");
+  if (!(typeof p.floor === "number" && Number.isFinite(p.floor) && p.floor >= 0)) throw new RangeError("despeckle: floor must be finite and >= 0");
+  if (!Number.isInteger(p.repair)) throw new RangeError("despeckle: repair must be an integer (0 = off)");
+  return p;
+}
+// the addon's RmFilters of { despeckle, denoise }: a stage that is undefined / null / false is off
+function filters(opts = {}) {
+  const off = (v) => v === undefined || v === null || v === false;
+  const f = { despeckle: off(opts.despeckle) ? null : despeckleParams(opts.despeckle), denoise: RM.DENOISE_NONE, atrous: null, variance: null };
+  const d = opts.denoise;
+  if (!off(d)) {
+    if (isVarianceMode(d)) { f.denoise = RM.DENOISE_VARIANCE; f.variance = denoiseVarianceParams(d); }
+    else { f.denoise = RM.DENOISE_ATROUS; f.atrous = denoiseParams(d && d.mode === "atrous" ? withoutMode(d) : d); }
+  }
+  return f;
+}
+
 // ---- PNG capture (index.tsx:470-476 canvas.toDataURL): RGBA8, filter 0, rows flipped to top-down ----
 const zlib = require("zlib");
 const CRC_TABLE = (() => { const t = new Uint32Array(256); for (let n = 0; n < 256; n++) { let c = n; for (let k = 0; k < 8; k++) c = c & 1 ? 0xedb88320 ^ (c >>> 1) : c >>> 1; t[n] = c >>> 0; } return t; })();
@@ -518,4 +559,4 @@ function encodePng(rgba, width, height, bottomUp = true) {
 
 module.exports = { RM, addon, encodePng, Scene, CsgScene, Mandelbulb, singleSphere, DEFAULT_MATERIAL, halton, resetHalton, uniformsFromSchema, packUniforms,
                    tileRect, RenderJobContext, ShardedRenderJobContext, doRenderJob, U_OFFSET, DENOISE_DEFAULTS, denoiseParams,
-                   DENOISE_VARIANCE_DEFAULTS, denoiseVarianceParams };
+                   DENOISE_VARIANCE_DEFAULTS, denoiseVarianceParams, DESPECKLE_DEFAULTS, despeckleParams };

@@ -349,6 +349,78 @@ static napi_value denoise_variance_common(napi_env env, napi_callback_info info,
 static napi_value DenoiseVariance(napi_env env, napi_callback_info info) { return denoise_variance_common(env, info, false); }
 static napi_value PresentDenoisedVariance(napi_env env, napi_callback_info info) { return denoise_variance_common(env, info, true); }
 
+// The RmFilters of a JS object { despeckle, denoise, atrous, variance }: rm_filters_default, then `despeckle` (null / undefined = the
+// stage off, or an object's radius, rank, gain, floor and repair over the defaults = the stage on), `denoise` (the RM_DENOISE_* number;
+// undefined = none) and the parameter blocks `atrous` / `variance` as denoise / denoiseVariance take them.  The library checks the values.
+static bool get_filters(napi_env env, napi_value v, RmFilters* f) {
+  rm_filters_default(f);
+  napi_valuetype t;
+  if (napi_typeof(env, v, &t) != napi_ok || t != napi_object) return false;
+  napi_value d, m, a, va;
+  if (napi_get_named_property(env, v, "despeckle", &d) != napi_ok || napi_get_named_property(env, v, "denoise", &m) != napi_ok ||
+      napi_get_named_property(env, v, "atrous", &a) != napi_ok || napi_get_named_property(env, v, "variance", &va) != napi_ok)
+    return false;
+  if (napi_typeof(env, d, &t) != napi_ok) return false;
+  if (t == napi_object) {
+    f->despeckle = 1;
+    const char* names[5] = {"radius", "rank", "gain", "floor", "repair"};
+    for (int k = 0; k < 5; k++) {
+      bool has = false;
+      napi_value p;
+      if (napi_has_named_property(env, d, names[k], &has) != napi_ok) return false;
+      if (!has) continue;
+      double x = 0.0;
+      if (napi_get_named_property(env, d, names[k], &p) != napi_ok || napi_get_value_double(env, p, &x) != napi_ok) return false;
+      const int i = (x >= -1e9 && x <= 1e9) ? (int)x : -1;
+      if (k == 0) f->despeckle_params.radius = i;
+      else if (k == 1) f->despeckle_params.rank = i;
+      else if (k == 2) f->despeckle_params.gain = (float)x;
+      else if (k == 3) f->despeckle_params.floor = (float)x;
+      else f->despeckle_params.repair = x != 0.0 ? 1 : 0;
+    }
+  } else if (t != napi_undefined && t != napi_null) {
+    return false;
+  }
+  if (napi_typeof(env, m, &t) != napi_ok) return false;
+  if (t == napi_number) {
+    int32_t mode = 0;
+    if (napi_get_value_int32(env, m, &mode) != napi_ok) return false;
+    f->denoise = mode;
+  } else if (t != napi_undefined && t != napi_null) {
+    return false;
+  }
+  return get_denoise(env, a, &f->atrous) && get_denoise_variance(env, va, &f->variance);
+}
+
+// filter(ctx, fb, samples, filters, out: Float32Array(width * height * 4)) = rm_filter: colour-plane units, row 0 = bottom
+// presentFiltered(ctx, fb, samples, filters, out: Uint8Array(width * height * 4)) = rm_present_filtered
+static napi_value filter_common(napi_env env, napi_callback_info info, bool present) {
+  const char* who = present ? "presentFiltered" : "filter";
+  size_t argc = 5;
+  napi_value argv[5];
+  NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+  rm_ctx* ctx = argc == 5 ? get_external<rm_ctx>(env, argv[0]) : nullptr;
+  rm_fb* fb = argc == 5 ? get_external<rm_fb>(env, argv[1]) : nullptr;
+  int32_t samples = 1;
+  RmFilters f;
+  void* d = nullptr;
+  size_t n = 0;
+  if (!ctx || !fb || napi_get_value_int32(env, argv[2], &samples) != napi_ok || !get_filters(env, argv[3], &f) || !get_buffer(env, argv[4], &d, &n)) {
+    napi_throw_type_error(env, nullptr, present ? "presentFiltered(ctx, fb, samples, filters, out: Uint8Array)" : "filter(ctx, fb, samples, filters, out: Float32Array)");
+    return nullptr;
+  }
+  const size_t need = (size_t)rm_fb_width(fb) * (size_t)rm_fb_rows(fb) * 4 * (present ? 1 : sizeof(float));
+  if (n < need) {
+    napi_throw_range_error(env, nullptr, (std::string(who) + ": out is smaller than the frame").c_str());
+    return nullptr;
+  }
+  const int rc = present ? rm_present_filtered(ctx, fb, samples, &f, static_cast<uint8_t*>(d)) : rm_filter(ctx, fb, samples, &f, static_cast<float*>(d));
+  if (rc != RM_OK) return throw_rm(env, ctx, present ? "rm_present_filtered" : "rm_filter");
+  return nullptr;
+}
+static napi_value Filter(napi_env env, napi_callback_info info) { return filter_common(env, info, false); }
+static napi_value PresentFiltered(napi_env env, napi_callback_info info) { return filter_common(env, info, true); }
+
 // fbCreateStriped(ctx, width, height, stripeRows, parts, part[, gbuffer]): the stripes k with k % parts == part of a width x height image,
 // planes owned by the library (rm_fb_create_striped) -- what one GPU of a sharded frame holds
 static napi_value FbCreateStriped(napi_env env, napi_callback_info info) {
@@ -543,7 +615,7 @@ static napi_value Sizes(napi_env env, napi_callback_info) {
   const struct { const char* k; uint32_t v; } items[] = {
       {"RmUniforms", (uint32_t)sizeof(RmUniforms)}, {"RmSceneDesc", (uint32_t)sizeof(RmSceneDesc)}, {"RmPrim", (uint32_t)sizeof(RmPrim)},
       {"RmMaterial", (uint32_t)sizeof(RmMaterial)}, {"RmRect", (uint32_t)sizeof(RmRect)}, {"RmSurface", (uint32_t)sizeof(RmSurface)}, {"RmDenoise", (uint32_t)sizeof(RmDenoise)},
-      {"RmDenoiseVariance", (uint32_t)sizeof(RmDenoiseVariance)}, {"abi", (uint32_t)rm_abi_version()}};
+      {"RmDenoiseVariance", (uint32_t)sizeof(RmDenoiseVariance)}, {"RmDespeckle", (uint32_t)sizeof(RmDespeckle)}, {"RmFilters", (uint32_t)sizeof(RmFilters)}, {"abi", (uint32_t)rm_abi_version()}};
   for (const auto& it : items) {
     NAPI_OK(napi_create_uint32(env, it.v, &v));
     NAPI_OK(napi_set_named_property(env, o, it.k, v));
@@ -554,7 +626,7 @@ static napi_value Sizes(napi_env env, napi_callback_info) {
 static napi_value Init(napi_env env, napi_value exports) {
   const struct { const char* name; napi_callback fn; } fns[] = {
       {"ctxCreate", CtxCreate}, {"ctxDestroy", CtxDestroy}, {"sync", Sync}, {"sceneCreate", SceneCreate}, {"sceneDestroy", SceneDestroy},
-      {"fbCreate", FbCreate}, {"fbClear", FbClear}, {"fbDestroy", FbDestroy}, {"fbDownload", FbDownload}, {"present", Present}, {"denoise", Denoise}, {"presentDenoised", PresentDenoised}, {"denoiseVariance", DenoiseVariance}, {"presentDenoisedVariance", PresentDenoisedVariance}, {"renderSample", RenderSample}, {"renderSamples", RenderSamples},
+      {"fbCreate", FbCreate}, {"fbClear", FbClear}, {"fbDestroy", FbDestroy}, {"fbDownload", FbDownload}, {"present", Present}, {"denoise", Denoise}, {"presentDenoised", PresentDenoised}, {"denoiseVariance", DenoiseVariance}, {"presentDenoisedVariance", PresentDenoisedVariance}, {"filter", Filter}, {"presentFiltered", PresentFiltered}, {"renderSample", RenderSample}, {"renderSamples", RenderSamples},
       {"fbCreateStriped", FbCreateStriped}, {"fbRows", FbRows}, {"setSamplesInFlight", SetSamplesInFlight}, {"presentSharded", PresentSharded}, {"presentShardedStart", PresentShardedStart}, {"presentShardedFinish", PresentShardedFinish},
       {"sizes", Sizes}};
   for (const auto& f : fns) {

@@ -37,6 +37,7 @@ EXPORTS = [
     "rm_fb_create_fmt", "rm_fb_create_striped_fmt", "rm_fb_wrap_fmt", "rm_fb_gbuffer", "rm_fb_download_raw", "rm_fb_upload_raw",
     "rm_denoise_default", "rm_denoise", "rm_denoise_device", "rm_present_denoised",
     "rm_fb_has_moments", "rm_denoise_variance_default", "rm_denoise_variance", "rm_denoise_variance_device", "rm_present_denoised_variance",
+    "rm_filters_default", "rm_filter", "rm_filter_device", "rm_present_filtered",
 ]
 
 # G-buffer formats of a framebuffer (include/hip_raymarch.h RM_GBUFFER_*): "f32" (the default: the software GL stack's planes, which the
@@ -118,6 +119,61 @@ def denoise_mode(denoise):
             raise ValueError(f"denoise: unknown mode {denoise['mode']!r} (\"atrous\" or \"variance\")")
         denoise = {k: v for k, v in denoise.items() if k != "mode"}
     return "atrous", denoise_params(denoise)
+
+
+def despeckle_params(params=None) -> abi.RmDespeckle:
+    """An abi.RmDespeckle from None / True (the defaults, rm_filters_default's), a dict of some of its fields over the defaults, or
+    an abi.RmDespeckle.  Checked here as the library checks it (radius 1 or 2, rank in 0..3, gain finite and >= 1, floor finite and
+    >= 0, reserved 0): ValueError otherwise."""
+    if isinstance(params, abi.RmDespeckle):
+        p = params
+    else:
+        if params is None or params is True:
+            fields = {}
+        elif isinstance(params, dict):
+            fields = dict(params)
+        else:
+            raise ValueError(f"despeckle: expected True, a dict or abi.RmDespeckle, got {params!r}")
+        unknown = set(fields) - set(abi.DESPECKLE_DEFAULTS)
+        if unknown:
+            raise ValueError(f"despeckle: unknown parameter(s) {sorted(unknown)}; known: {sorted(abi.DESPECKLE_DEFAULTS)}")
+        fields = {**abi.DESPECKLE_DEFAULTS, **fields}
+        for name in ("radius", "rank", "repair"):
+            if isinstance(fields[name], bool):
+                fields[name] = int(fields[name])
+            if not isinstance(fields[name], (int, np.integer)):
+                raise ValueError(f"despeckle: {name} must be an integer")
+        for name in ("gain", "floor"):
+            if isinstance(fields[name], bool) or not isinstance(fields[name], (int, float, np.integer, np.floating)):
+                raise ValueError(f"despeckle: {name} must be a number")
+        p = abi.RmDespeckle(**fields)
+    if p.radius not in (1, 2):
+        raise ValueError("despeckle: radius must be 1 or 2")
+    if not 0 <= p.rank <= 3:
+        raise ValueError("despeckle: rank must be in 0..3")
+    if not (math.isfinite(p.gain) and p.gain >= 1.0):
+        raise ValueError("despeckle: gain must be finite and >= 1")
+    if not (math.isfinite(p.floor) and p.floor >= 0.0):
+        raise ValueError("despeckle: floor must be finite and >= 0")
+    if p.reserved != 0:
+        raise ValueError("despeckle: reserved must be 0")
+    return p
+
+
+def filters(despeckle=None, denoise=None) -> abi.RmFilters:
+    """The abi.RmFilters of a chain: `despeckle` None (stage off) or what despeckle_params takes, `denoise` None (stage off) or what
+    denoise_mode takes.  The blocks of a stage that is off keep their defaults (rm_filters_default)."""
+    f = abi.RmFilters()
+    load_library().rm_filters_default(C.byref(f))
+    if despeckle is not None:
+        f.despeckle, f.despeckle_params = 1, despeckle_params(despeckle)
+    if denoise is not None:
+        mode, p = denoise_mode(denoise)
+        if mode == "variance":
+            f.denoise, f.variance = abi.RM_DENOISE_VARIANCE, p
+        else:
+            f.denoise, f.atrous = abi.RM_DENOISE_ATROUS, p
+    return f
 
 
 def cull_cell(scene, centre, radius: float, margin: float = 0.0):
@@ -258,6 +314,10 @@ def load_library(path=None):
         "rm_denoise_variance": (ip, [vp, vp, ip, C.POINTER(abi.RmDenoiseVariance), fp]),
         "rm_denoise_variance_device": (ip, [vp, vp, ip, C.POINTER(abi.RmDenoiseVariance), vp, vp]),
         "rm_present_denoised_variance": (ip, [vp, vp, ip, C.POINTER(abi.RmDenoiseVariance), C.POINTER(C.c_uint8)]),
+        "rm_filters_default": (None, [C.POINTER(abi.RmFilters)]),
+        "rm_filter": (ip, [vp, vp, ip, C.POINTER(abi.RmFilters), fp]),
+        "rm_filter_device": (ip, [vp, vp, ip, C.POINTER(abi.RmFilters), vp, vp]),
+        "rm_present_filtered": (ip, [vp, vp, ip, C.POINTER(abi.RmFilters), C.POINTER(C.c_uint8)]),
     }
     for name, (res, args) in sig.items():
         if name.startswith("rm_debug_") and not hasattr(lib, name) and os.environ.get("RM_LIB"):
@@ -439,6 +499,12 @@ class Context:
         `stream` (None = the context's); no host wait."""
         p = denoise_variance_params(params)
         self._check(self.lib.rm_denoise_variance_device(self.h, fb.h, int(samples), C.byref(p), C.c_void_p(out_ptr), C.c_void_p(stream) if stream else None))
+
+    def filter_device(self, fb: "Framebuffer", samples: int, out_ptr: int, despeckle=None, denoise=None, stream: Optional[int] = None):
+        """rm_filter_device: Framebuffer.filter into rows x W float4 of device memory at out_ptr, enqueued on `stream` (None = the
+        context's); no host wait."""
+        f = filters(despeckle, denoise)
+        self._check(self.lib.rm_filter_device(self.h, fb.h, int(samples), C.byref(f), C.c_void_p(out_ptr), C.c_void_p(stream) if stream else None))
 
     def present_rows(self, fb: "Framebuffer", samples: int, out_ptr: int, stream: Optional[int] = None):
         """Tone-map the rows `fb` holds (no depth of field) into DEVICE memory (rows*width*4 bytes), asynchronous."""
@@ -626,18 +692,33 @@ class Framebuffer:
     def device_ptr(self, plane: int = abi.RM_PLANE_COLOR) -> int:
         return int(self.ctx.lib.rm_fb_device_ptr(self.h, plane) or 0)
 
-    def present(self, samples: int, denoise=None) -> np.ndarray:
+    def present(self, samples: int, denoise=None, despeckle=None) -> np.ndarray:
         """Tone-mapped RGBA8 image of the whole frame (display.frag:16-64), row 0 = bottom.  `denoise`: None (the default: the
         accumulated colour as it is), or True / a dict / abi.RmDenoise to present the denoised colour (rm_present_denoised); or
         "variance" / abi.RmDenoiseVariance / a dict with "mode": "variance" for the variance-guided filter
-        (rm_present_denoised_variance; the framebuffer needs moments=True)."""
+        (rm_present_denoised_variance; the framebuffer needs moments=True).  `despeckle`: None (the default: no firefly filter, and
+        exactly the calls above), or True / a dict / abi.RmDespeckle to run the firefly filter ahead of the denoiser and the present
+        (rm_present_filtered)."""
         out = np.empty((self.row_count, self.width, 4), np.uint8)
+        if despeckle is not None:
+            f = filters(despeckle, denoise)
+            self.ctx._check(self.ctx.lib.rm_present_filtered(self.ctx.h, self.h, int(samples), C.byref(f), out.ctypes.data_as(C.POINTER(C.c_uint8))))
+            return out
         if denoise is None:
             self.ctx._check(self.ctx.lib.rm_present(self.ctx.h, self.h, int(samples), out.ctypes.data_as(C.POINTER(C.c_uint8))))
             return out
         mode, p = denoise_mode(denoise)
         fn = self.ctx.lib.rm_present_denoised_variance if mode == "variance" else self.ctx.lib.rm_present_denoised
         self.ctx._check(fn(self.ctx.h, self.h, int(samples), C.byref(p), out.ctypes.data_as(C.POINTER(C.c_uint8))))
+        return out
+
+    def filter(self, samples: int, despeckle=None, denoise=None) -> np.ndarray:
+        """The colour plane after the chain despeckle -> denoise (rm_filter): float32 [rows, W, 4] in colour-plane units, row 0 =
+        bottom.  `despeckle`: None (off) or True / a dict / abi.RmDespeckle; `denoise`: None (off) or what present's takes.  With
+        both off it is the colour plane itself."""
+        f = filters(despeckle, denoise)
+        out = np.empty((self.row_count, self.width, 4), np.float32)
+        self.ctx._check(self.ctx.lib.rm_filter(self.ctx.h, self.h, int(samples), C.byref(f), _fp(out)))
         return out
 
     def denoise(self, samples: int, params=None) -> np.ndarray:
