@@ -161,6 +161,21 @@ struct Lpt {
   }
 };
 
+// Device scratch of the present and the frame filters that lives with the context (a live loop presents, and filters, every
+// sample): grown on demand by scratch_reserve, which states the rule, and freed with the context.
+enum {
+  SCRATCH_PRESENT,        // rm_present / rm_present_planes: the RGBA8 image before it goes to the host
+  SCRATCH_DENOISE_X0,     // the denoisers' two ping-pong buffers of x
+  SCRATCH_DENOISE_X1,
+  SCRATCH_DENOISE_GUIDE,  // and their guide
+  SCRATCH_DESPECKLE,      // the despeckled colour plane the denoise stage reads
+  SCRATCH_COUNT
+};
+struct Scratch {
+  void* p = nullptr;
+  size_t bytes = 0;
+};
+
 struct rm_ctx {
   int device = 0;
   hipStream_t own_stream = nullptr;
@@ -181,12 +196,8 @@ struct rm_ctx {
   bool lpt_enabled = true;
   hipEvent_t switch_ev = nullptr;  // orders the old stream before the new one in rm_ctx_set_stream
   std::unordered_map<void*, size_t> buffers;  // rm_buffer_create: base address -> bytes
-  uchar4* present_buf = nullptr;   // device staging of rm_present / rm_present_planes, grown on demand
-  size_t present_cap = 0;          // pixels
-  float4* denoise_buf[3] = {nullptr, nullptr, nullptr};  // rm_denoise*: the two ping-pong buffers of x and the guide, grown on demand
-  size_t denoise_cap = 0;          // pixels
-  float4* despeckle_buf = nullptr;  // rm_filter*: the despeckled colour plane the denoise stage reads, grown on demand
-  size_t despeckle_cap = 0;         // pixels
+  Scratch scratch[SCRATCH_COUNT];  // scratch_reserve
+  template <class T> T* scratch_as(int which) const { return static_cast<T*>(scratch[which].p); }
   // rm_present_sharded (one process driving several GPUs): this context's rows of the payload, and on the context that
   // shows the frame the gathered parts and the frame in image order; grown on demand, freed with the context
   void* shard_rows = nullptr;  size_t shard_rows_cap = 0;    // this context's rows of the payload (packed float4 or RGBA8)
@@ -335,10 +346,8 @@ void rm_ctx_destroy(rm_ctx* ctx) {
   if (ctx->lpt_stream) { (void)hipStreamSynchronize(ctx->lpt_stream); (void)hipStreamDestroy(ctx->lpt_stream); }
   for (auto& l : ctx->lpt) l.destroy();
   ctx->sp.destroy();
-  if (ctx->present_buf) (void)hipFree(ctx->present_buf);
-  for (auto* b : ctx->denoise_buf)
-    if (b) (void)hipFree(b);
-  if (ctx->despeckle_buf) (void)hipFree(ctx->despeckle_buf);
+  for (auto& s : ctx->scratch)
+    if (s.p) (void)hipFree(s.p);
   if (ctx->shard_rows) (void)hipFree(ctx->shard_rows);
   if (ctx->shard_recv) (void)hipFree(ctx->shard_recv);
   if (ctx->shard_frame) (void)hipFree(ctx->shard_frame);
@@ -1615,23 +1624,34 @@ int rm_pack_present_rows(rm_ctx* ctx, rm_fb* fb, void* out_float4_device, void* 
   return RM_OK;
 }
 
+// Room for `bytes` in one of the context's scratch buffers, for work about to be enqueued on `stream`.  The rule, for all of them:
+// with enough capacity there is nothing to do.  Otherwise wait for the context's stream AND for `stream` -- what still reads the
+// old buffer was enqueued on one of them --, free it, and set the capacity to 0 before allocating: a failed hipMalloc then leaves
+// an empty buffer, from which the next call starts over.
+static int scratch_reserve(rm_ctx* ctx, int which, size_t bytes, hipStream_t stream) {
+  Scratch& s = ctx->scratch[which];
+  if (s.bytes >= bytes) return RM_OK;
+  if (s.p) {
+    RM_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (stream != ctx->stream) RM_HIP(ctx, hipStreamSynchronize(stream));
+    (void)hipFree(s.p);
+  }
+  s = Scratch{};
+  void* p = nullptr;
+  RM_HIP(ctx, hipMalloc(&p, bytes));
+  s = Scratch{p, bytes};
+  return RM_OK;
+}
+
 static int present_planes(rm_ctx* ctx, const void* color, const void* normal_dof, bool nd_half, int width, int height, int samples, uint8_t* out_rgba8) {
   if (!ctx || !color || !out_rgba8) return fail(ctx, RM_ERR_INVALID, "rm_present_planes: NULL argument");
   if (width < 1 || height < 1 || samples < 1) return fail(ctx, RM_ERR_INVALID, "rm_present_planes: width, height and samples must be >= 1");
   RM_HIP(ctx, hipSetDevice(ctx->device));
-  const size_t pixels = (size_t)width * (size_t)height;
-  if (ctx->present_cap < pixels) {  // the staging buffer lives with the context: a live loop presents every sample
-    if (ctx->present_buf) {
-      RM_HIP(ctx, hipStreamSynchronize(ctx->stream));
-      (void)hipFree(ctx->present_buf);
-      ctx->present_buf = nullptr;
-      ctx->present_cap = 0;
-    }
-    RM_HIP(ctx, hipMalloc(reinterpret_cast<void**>(&ctx->present_buf), pixels * 4));
-    ctx->present_cap = pixels;
-  }
-  if (int rc = present_device(ctx, color, normal_dof, nd_half, width, height, samples, ctx->present_buf, nullptr)) return rc;
-  RM_HIP(ctx, hipMemcpyAsync(out_rgba8, ctx->present_buf, pixels * 4, hipMemcpyDeviceToHost, ctx->stream));
+  const size_t bytes = (size_t)width * (size_t)height * 4;
+  if (int rc = scratch_reserve(ctx, SCRATCH_PRESENT, bytes, ctx->stream)) return rc;
+  void* rgba8 = ctx->scratch[SCRATCH_PRESENT].p;
+  if (int rc = present_device(ctx, color, normal_dof, nd_half, width, height, samples, rgba8, nullptr)) return rc;
+  RM_HIP(ctx, hipMemcpyAsync(out_rgba8, rgba8, bytes, hipMemcpyDeviceToHost, ctx->stream));
   RM_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return RM_OK;
 }
@@ -1647,7 +1667,10 @@ int rm_present(rm_ctx* ctx, rm_fb* fb, int samples, uint8_t* out_rgba8) {
   return present_planes(ctx, fb->plane[0], fb->plane[1], fb->gbuffer == RM_GBUFFER_F16, fb->width, fb->height, samples, out_rgba8);
 }
 
-// ---- denoise (rm_frame_kernels.inc "denoise") ---------------------------------------------------------
+// ---- frame filters: despeckle -> denoise ahead of the present (rm_frame_kernels.inc "denoise", "the variance-guided mode", "despeckle") ----
+// Nine entry points, one path.  RmFilters states all of them: rm_denoise* is the chain with the a-trous stage alone, rm_denoise_variance*
+// the chain with the variance-guided stage alone.  Each export builds or takes its RmFilters and ends in filter_to_device,
+// filter_to_host or filter_to_rgba8, which check (filters_check), enqueue (filters_enqueue) and deliver.
 
 void rm_denoise_default(RmDenoise* p) {
   if (!p) return;
@@ -1658,104 +1681,6 @@ void rm_denoise_default(RmDenoise* p) {
   p->sigma_depth = 0.2f;
 }
 
-// Every check of the denoise entry points, before any device work.
-static int denoise_check(rm_ctx* ctx, rm_fb* fb, int samples, const RmDenoise* params, const char* who) {
-  if (!ctx || !fb) return fail(ctx, RM_ERR_INVALID, std::string(who) + ": NULL argument");
-  if (fb->ctx != ctx) return fail(ctx, RM_ERR_INVALID, std::string(who) + ": framebuffer belongs to another context");
-  if (fb->stripe_rows > 0 || fb->row_begin != 0 || fb->row_count != fb->height)
-    return fail(ctx, RM_ERR_INVALID, std::string(who) + ": the filter reads neighbouring rows, so it needs a framebuffer holding the whole frame");
-  if (!fb->plane[1] || !fb->plane[2]) return fail(ctx, RM_ERR_INVALID, std::string(who) + ": the framebuffer has no G-buffer planes to guide the filter");
-  if (samples < 1) return fail(ctx, RM_ERR_INVALID, std::string(who) + ": samples must be >= 1");
-  if (params) {
-    if (params->iterations < 0 || params->iterations > 8) return fail(ctx, RM_ERR_INVALID, std::string(who) + ": iterations must be in 0..8");
-    const float sg[3] = {params->sigma_color, params->sigma_normal, params->sigma_depth};
-    for (float v : sg)
-      if (!(v > 0.0f && std::isfinite(v))) return fail(ctx, RM_ERR_INVALID, std::string(who) + ": every sigma must be finite and > 0");
-  }
-  return RM_OK;
-}
-
-// Enqueues the passes on `stream`.  color: the colour the filter reads where the colour plane stands in its statement (the
-// plane itself, or rm_filter's despeckled copy of it); the guides and the moments are the framebuffer's own.  out: the result, or
-// NULL for one of the context's buffers; *result = where it is (`color` itself for 0 iterations and no `out`).  var: the
-// variance-guided mode, d.sigma_color holding sigma_luminance.
-static int denoise_enqueue(rm_ctx* ctx, rm_fb* fb, const float4* color, int samples, const RmDenoise* params, float4* out, hipStream_t stream,
-                           const float4** result, bool var = false) {
-  RmDenoise d;
-  if (params) d = *params;
-  else rm_denoise_default(&d);
-  RM_HIP(ctx, hipSetDevice(ctx->device));
-  const size_t pixels = (size_t)fb->width * (size_t)fb->height;
-  const int L = d.iterations;
-  if (L == 0) {
-    if (out) RM_HIP(ctx, hipMemcpyAsync(out, color, pixels * sizeof(float4), hipMemcpyDeviceToDevice, stream));
-    *result = out ? out : color;
-    return RM_OK;
-  }
-  if (ctx->denoise_cap < pixels) {  // a live loop denoises every present: the buffers stay with the context
-    RM_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    RM_HIP(ctx, hipStreamSynchronize(stream));
-    for (auto*& b : ctx->denoise_buf) {
-      if (b) (void)hipFree(b);
-      b = nullptr;
-    }
-    ctx->denoise_cap = 0;
-    for (auto*& b : ctx->denoise_buf) RM_HIP(ctx, hipMalloc(reinterpret_cast<void**>(&b), pixels * sizeof(float4)));
-    ctx->denoise_cap = pixels;
-  }
-  DenoisePass P{};
-  P.color = color;
-  P.normal_dof = fb->plane[1];
-  P.albedo_depth = fb->plane[2];
-  P.guide = ctx->denoise_buf[2];
-  P.W = fb->width;
-  P.H = fb->height;
-  P.s = 1.0f / (float)samples;  // present_device's scale
-  P.k = (float)samples;
-  P.inv_normal = 1.0f / (d.sigma_normal * d.sigma_normal);
-  P.moments = var ? fb->moments : nullptr;
-  P.sigma_l = d.sigma_color;
-  const bool half = fb->gbuffer == RM_GBUFFER_F16;
-  for (int i = 0; i < L; i++) {
-    P.step = 1 << i;
-    P.inv_color = (float)(1 << (2 * i)) / (d.sigma_color * d.sigma_color);  // sigma_c^2 4^-i
-    P.sigma_z_h = d.sigma_depth * (float)P.step;
-    P.x_in = i > 0 ? ctx->denoise_buf[(i - 1) % 2] : nullptr;
-    P.out = (i == L - 1 && out) ? out : ctx->denoise_buf[i % 2];
-    RM_HIP(ctx, (var ? rm::launch_denoise_variance_pass : rm::launch_denoise_pass)(P, half, i == 0, i == L - 1, stream));
-  }
-  *result = P.out;
-  return RM_OK;
-}
-
-int rm_denoise_device(rm_ctx* ctx, rm_fb* fb, int samples, const RmDenoise* params, void* out_float4_device, void* hip_stream) {
-  if (int rc = denoise_check(ctx, fb, samples, params, "rm_denoise_device")) return rc;
-  if (!out_float4_device || (reinterpret_cast<uintptr_t>(out_float4_device) & 15u))
-    return fail(ctx, RM_ERR_INVALID, "rm_denoise_device: the output must be a 16-byte aligned device buffer");
-  const float4* r = nullptr;
-  return denoise_enqueue(ctx, fb, fb->plane[0], samples, params, static_cast<float4*>(out_float4_device), hip_stream ? static_cast<hipStream_t>(hip_stream) : ctx->stream, &r);
-}
-
-int rm_denoise(rm_ctx* ctx, rm_fb* fb, int samples, const RmDenoise* params, float* out_host) {
-  if (int rc = denoise_check(ctx, fb, samples, params, "rm_denoise")) return rc;
-  if (!out_host) return fail(ctx, RM_ERR_INVALID, "rm_denoise: NULL argument");
-  const float4* r = nullptr;
-  if (int rc = denoise_enqueue(ctx, fb, fb->plane[0], samples, params, nullptr, ctx->stream, &r)) return rc;
-  RM_HIP(ctx, hipMemcpyAsync(out_host, r, (size_t)fb->width * (size_t)fb->height * sizeof(float4), hipMemcpyDeviceToHost, ctx->stream));
-  RM_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return RM_OK;
-}
-
-int rm_present_denoised(rm_ctx* ctx, rm_fb* fb, int samples, const RmDenoise* params, uint8_t* out_rgba8) {
-  if (int rc = denoise_check(ctx, fb, samples, params, "rm_present_denoised")) return rc;
-  if (!out_rgba8) return fail(ctx, RM_ERR_INVALID, "rm_present_denoised: NULL argument");
-  const float4* r = nullptr;
-  if (int rc = denoise_enqueue(ctx, fb, fb->plane[0], samples, params, nullptr, ctx->stream, &r)) return rc;
-  return present_planes(ctx, r, fb->plane[1], fb->gbuffer == RM_GBUFFER_F16, fb->width, fb->height, samples, out_rgba8);
-}
-
-// ---- variance-guided denoise (rm_frame_kernels.inc "the variance-guided mode") ------------------------
-
 void rm_denoise_variance_default(RmDenoiseVariance* p) {
   if (!p) return;
   std::memset(p, 0, sizeof *p);
@@ -1764,51 +1689,6 @@ void rm_denoise_variance_default(RmDenoiseVariance* p) {
   p->sigma_normal = 1.0f;
   p->sigma_depth = 0.2f;
 }
-
-// rm_denoise's checks, the moments plane and the variance parameters; *d = the parameters as denoise_enqueue takes them
-static int denoise_variance_check(rm_ctx* ctx, rm_fb* fb, int samples, const RmDenoiseVariance* params, const char* who, RmDenoise* d) {
-  RmDenoiseVariance v;
-  if (params) v = *params;
-  else rm_denoise_variance_default(&v);
-  if (!ctx || !fb) return fail(ctx, RM_ERR_INVALID, std::string(who) + ": NULL argument");
-  if (params && params->reserved != 0) return fail(ctx, RM_ERR_INVALID, std::string(who) + ": reserved must be 0");
-  if (!(v.sigma_luminance > 0.0f && std::isfinite(v.sigma_luminance))) return fail(ctx, RM_ERR_INVALID, std::string(who) + ": every sigma must be finite and > 0");
-  *d = RmDenoise{v.iterations, v.sigma_luminance, v.sigma_normal, v.sigma_depth, 0};
-  if (int rc = denoise_check(ctx, fb, samples, d, who)) return rc;
-  if (!fb->moments) return fail(ctx, RM_ERR_INVALID, std::string(who) + ": the framebuffer has no moments plane (create it with RM_FB_MOMENTS)");
-  return RM_OK;
-}
-
-int rm_denoise_variance_device(rm_ctx* ctx, rm_fb* fb, int samples, const RmDenoiseVariance* params, void* out_float4_device, void* hip_stream) {
-  RmDenoise d;
-  if (int rc = denoise_variance_check(ctx, fb, samples, params, "rm_denoise_variance_device", &d)) return rc;
-  if (!out_float4_device || (reinterpret_cast<uintptr_t>(out_float4_device) & 15u))
-    return fail(ctx, RM_ERR_INVALID, "rm_denoise_variance_device: the output must be a 16-byte aligned device buffer");
-  const float4* r = nullptr;
-  return denoise_enqueue(ctx, fb, fb->plane[0], samples, &d, static_cast<float4*>(out_float4_device), hip_stream ? static_cast<hipStream_t>(hip_stream) : ctx->stream, &r, true);
-}
-
-int rm_denoise_variance(rm_ctx* ctx, rm_fb* fb, int samples, const RmDenoiseVariance* params, float* out_host) {
-  RmDenoise d;
-  if (int rc = denoise_variance_check(ctx, fb, samples, params, "rm_denoise_variance", &d)) return rc;
-  if (!out_host) return fail(ctx, RM_ERR_INVALID, "rm_denoise_variance: NULL argument");
-  const float4* r = nullptr;
-  if (int rc = denoise_enqueue(ctx, fb, fb->plane[0], samples, &d, nullptr, ctx->stream, &r, true)) return rc;
-  RM_HIP(ctx, hipMemcpyAsync(out_host, r, (size_t)fb->width * (size_t)fb->height * sizeof(float4), hipMemcpyDeviceToHost, ctx->stream));
-  RM_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return RM_OK;
-}
-
-int rm_present_denoised_variance(rm_ctx* ctx, rm_fb* fb, int samples, const RmDenoiseVariance* params, uint8_t* out_rgba8) {
-  RmDenoise d;
-  if (int rc = denoise_variance_check(ctx, fb, samples, params, "rm_present_denoised_variance", &d)) return rc;
-  if (!out_rgba8) return fail(ctx, RM_ERR_INVALID, "rm_present_denoised_variance: NULL argument");
-  const float4* r = nullptr;
-  if (int rc = denoise_enqueue(ctx, fb, fb->plane[0], samples, &d, nullptr, ctx->stream, &r, true)) return rc;
-  return present_planes(ctx, r, fb->plane[1], fb->gbuffer == RM_GBUFFER_F16, fb->width, fb->height, samples, out_rgba8);
-}
-
-// ---- the filter chain ahead of the present: despeckle -> denoise (rm_frame_kernels.inc "despeckle") ------------------
 
 void rm_filters_default(RmFilters* f) {
   if (!f) return;
@@ -1822,59 +1702,82 @@ void rm_filters_default(RmFilters* f) {
   rm_denoise_variance_default(&f->variance);
 }
 
-// Every check of the rm_filter entry points, before any device work: the chain's own values first (they need neither a context
-// nor a GPU), then the handles, then what the selected denoiser refuses.  *d = the denoise stage's parameters as denoise_enqueue
-// takes them.
+// the chains the older entry points stand for: one denoiser, despeckle off; NULL params = that denoiser's defaults
+static RmFilters atrous_chain(const RmDenoise* params) {
+  RmFilters f;
+  rm_filters_default(&f);
+  f.denoise = RM_DENOISE_ATROUS;
+  if (params) f.atrous = *params;
+  return f;
+}
+static RmFilters variance_chain(const RmDenoiseVariance* params) {
+  RmFilters f;
+  rm_filters_default(&f);
+  f.denoise = RM_DENOISE_VARIANCE;
+  if (params) f.variance = *params;
+  return f;
+}
+
+// Every check of the nine entry points but the output's, before any device work, in ONE order: the chain's own values (they need
+// neither a context nor a GPU: a NULL chain, the stage switches, the despeckle block when that stage is on), the handles (NULL,
+// another context's framebuffer, a window or stripes), samples, and then what the selected denoiser refuses: a framebuffer
+// without G-buffer planes, its block (reserved -- the variance block's alone --, iterations, the sigmas), a framebuffer without
+// the moments plane.  A stage that is off is not looked at.  *d = the denoise stage's parameters as filters_enqueue takes them
+// (sigma_color holding the variance-guided mode's sigma_luminance).
 static int filters_check(rm_ctx* ctx, rm_fb* fb, int samples, const RmFilters* f, const char* who, RmDenoise* d) {
-  if (!f) return fail(ctx, RM_ERR_INVALID, std::string(who) + ": NULL argument");
-  if (f->despeckle != 0 && f->despeckle != 1) return fail(ctx, RM_ERR_INVALID, std::string(who) + ": despeckle must be 0 or 1");
-  if (f->denoise != RM_DENOISE_NONE && f->denoise != RM_DENOISE_ATROUS && f->denoise != RM_DENOISE_VARIANCE)
-    return fail(ctx, RM_ERR_INVALID, std::string(who) + ": unknown denoise mode");
+  auto refuse = [&](const char* what) { return fail(ctx, RM_ERR_INVALID, std::string(who) + ": " + what); };
+  if (!f) return refuse("NULL argument");
+  if (f->despeckle != 0 && f->despeckle != 1) return refuse("despeckle must be 0 or 1");
+  if (f->denoise != RM_DENOISE_NONE && f->denoise != RM_DENOISE_ATROUS && f->denoise != RM_DENOISE_VARIANCE) return refuse("unknown denoise mode");
   if (f->despeckle) {
     const RmDespeckle& p = f->despeckle_params;
-    if (p.radius != 1 && p.radius != 2) return fail(ctx, RM_ERR_INVALID, std::string(who) + ": despeckle radius must be 1 or 2");
-    if (p.rank < 0 || p.rank > 3) return fail(ctx, RM_ERR_INVALID, std::string(who) + ": despeckle rank must be in 0..3");
-    if (!(std::isfinite(p.gain) && p.gain >= 1.0f)) return fail(ctx, RM_ERR_INVALID, std::string(who) + ": despeckle gain must be finite and >= 1");
-    if (!(std::isfinite(p.floor) && p.floor >= 0.0f)) return fail(ctx, RM_ERR_INVALID, std::string(who) + ": despeckle floor must be finite and >= 0");
-    if (p.reserved != 0) return fail(ctx, RM_ERR_INVALID, std::string(who) + ": despeckle reserved must be 0");
+    if (p.radius != 1 && p.radius != 2) return refuse("despeckle radius must be 1 or 2");
+    if (p.rank < 0 || p.rank > 3) return refuse("despeckle rank must be in 0..3");
+    if (!(std::isfinite(p.gain) && p.gain >= 1.0f)) return refuse("despeckle gain must be finite and >= 1");
+    if (!(std::isfinite(p.floor) && p.floor >= 0.0f)) return refuse("despeckle floor must be finite and >= 0");
+    if (p.reserved != 0) return refuse("despeckle reserved must be 0");
   }
-  if (!ctx || !fb) return fail(ctx, RM_ERR_INVALID, std::string(who) + ": NULL argument");
-  if (fb->ctx != ctx) return fail(ctx, RM_ERR_INVALID, std::string(who) + ": framebuffer belongs to another context");
+  if (!ctx || !fb) return refuse("NULL argument");
+  if (fb->ctx != ctx) return refuse("framebuffer belongs to another context");
   if (fb->stripe_rows > 0 || fb->row_begin != 0 || fb->row_count != fb->height)
-    return fail(ctx, RM_ERR_INVALID, std::string(who) + ": the filter reads neighbouring rows, so it needs a framebuffer holding the whole frame");
-  if (samples < 1) return fail(ctx, RM_ERR_INVALID, std::string(who) + ": samples must be >= 1");
-  if (f->denoise == RM_DENOISE_ATROUS) {
-    *d = f->atrous;
-    return denoise_check(ctx, fb, samples, d, who);
-  }
-  if (f->denoise == RM_DENOISE_VARIANCE) return denoise_variance_check(ctx, fb, samples, &f->variance, who, d);
+    return refuse("the filter reads neighbouring rows, so it needs a framebuffer holding the whole frame");
+  if (samples < 1) return refuse("samples must be >= 1");
+  if (f->denoise == RM_DENOISE_NONE) return RM_OK;
+  const bool var = f->denoise == RM_DENOISE_VARIANCE;
+  *d = var ? RmDenoise{f->variance.iterations, f->variance.sigma_luminance, f->variance.sigma_normal, f->variance.sigma_depth, 0} : f->atrous;
+  if (!fb->plane[1] || !fb->plane[2]) return refuse("the framebuffer has no G-buffer planes to guide the filter");
+  if (var && f->variance.reserved != 0) return refuse("reserved must be 0");
+  if (d->iterations < 0 || d->iterations > 8) return refuse("iterations must be in 0..8");
+  for (float v : {d->sigma_color, d->sigma_normal, d->sigma_depth})
+    if (!(v > 0.0f && std::isfinite(v))) return refuse("every sigma must be finite and > 0");
+  if (var && !fb->moments) return refuse("the framebuffer has no moments plane (create it with RM_FB_MOMENTS)");
   return RM_OK;
 }
 
-// Enqueues the chain on `stream`.  out: the result, or NULL for one of the context's buffers; *result = where it is (the colour
-// plane itself when both stages are off and there is no `out`).
+// Enqueues the chain on `stream` (after filters_check, whose *d this takes).  out: the result, or NULL for one of the context's
+// buffers; *result = where it is.  The denoise stage reads the despeckled colour where its statement reads the colour plane; the
+// guides and the moments are the framebuffer's own.  With no pass to run -- the denoise stage off, or on with 0 iterations -- the
+// result is the despeckled colour, written straight into `out`, or without that stage the colour plane: copied into `out`, and
+// without an `out` the plane itself.
 static int filters_enqueue(rm_ctx* ctx, rm_fb* fb, int samples, const RmFilters* f, const RmDenoise* d, float4* out, hipStream_t stream,
                            const float4** result) {
+  RM_HIP(ctx, hipSetDevice(ctx->device));
+  const size_t bytes = (size_t)fb->width * (size_t)fb->height * sizeof(float4);
+  const bool var = f->denoise == RM_DENOISE_VARIANCE;
+  const int L = f->denoise == RM_DENOISE_NONE ? 0 : d->iterations;
+  float4* despeckled = (L == 0 && out) ? out : nullptr;
+  if (f->despeckle && !despeckled) {
+    if (int rc = scratch_reserve(ctx, SCRATCH_DESPECKLE, bytes, stream)) return rc;
+    despeckled = ctx->scratch_as<float4>(SCRATCH_DESPECKLE);
+  }
+  if (L > 0)  // a live loop denoises every present: the ping-pong buffers of x and the guide stay with the context
+    for (int b : {SCRATCH_DENOISE_X0, SCRATCH_DENOISE_X1, SCRATCH_DENOISE_GUIDE})
+      if (int rc = scratch_reserve(ctx, b, bytes, stream)) return rc;
   const float4* color = fb->plane[0];
-  const size_t pixels = (size_t)fb->width * (size_t)fb->height;
   if (f->despeckle) {
-    RM_HIP(ctx, hipSetDevice(ctx->device));
-    float4* dst = (f->denoise == RM_DENOISE_NONE && out) ? out : nullptr;
-    if (!dst) {
-      if (ctx->despeckle_cap < pixels) {  // lives with the context like the denoiser's buffers
-        RM_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        RM_HIP(ctx, hipStreamSynchronize(stream));
-        if (ctx->despeckle_buf) (void)hipFree(ctx->despeckle_buf);
-        ctx->despeckle_buf = nullptr;
-        ctx->despeckle_cap = 0;
-        RM_HIP(ctx, hipMalloc(reinterpret_cast<void**>(&ctx->despeckle_buf), pixels * sizeof(float4)));
-        ctx->despeckle_cap = pixels;
-      }
-      dst = ctx->despeckle_buf;
-    }
     DespecklePass P{};
-    P.color = fb->plane[0];
-    P.out = dst;
+    P.color = color;
+    P.out = despeckled;
     P.W = fb->width;
     P.H = fb->height;
     P.s = 1.0f / (float)samples;  // present_device's scale
@@ -1882,48 +1785,105 @@ static int filters_enqueue(rm_ctx* ctx, rm_fb* fb, int samples, const RmFilters*
     P.floor = f->despeckle_params.floor;
     P.repair = f->despeckle_params.repair;
     RM_HIP(ctx, rm::launch_despeckle(P, f->despeckle_params.radius, f->despeckle_params.rank, stream));
-    color = dst;
-    if (f->denoise == RM_DENOISE_NONE) {
-      *result = dst;
-      return RM_OK;
-    }
+    color = despeckled;
   }
-  if (f->denoise == RM_DENOISE_NONE) {  // both stages off: an exact copy of the colour plane
-    RM_HIP(ctx, hipSetDevice(ctx->device));
-    if (out) RM_HIP(ctx, hipMemcpyAsync(out, color, pixels * sizeof(float4), hipMemcpyDeviceToDevice, stream));
+  if (L == 0) {  // nothing (more) to run: an exact copy
+    if (out && color != out) RM_HIP(ctx, hipMemcpyAsync(out, color, bytes, hipMemcpyDeviceToDevice, stream));
     *result = out ? out : color;
     return RM_OK;
   }
-  return denoise_enqueue(ctx, fb, color, samples, d, out, stream, result, f->denoise == RM_DENOISE_VARIANCE);
+  float4* const x[2] = {ctx->scratch_as<float4>(SCRATCH_DENOISE_X0), ctx->scratch_as<float4>(SCRATCH_DENOISE_X1)};
+  DenoisePass P{};
+  P.color = color;
+  P.normal_dof = fb->plane[1];
+  P.albedo_depth = fb->plane[2];
+  P.guide = ctx->scratch_as<float4>(SCRATCH_DENOISE_GUIDE);
+  P.W = fb->width;
+  P.H = fb->height;
+  P.s = 1.0f / (float)samples;  // present_device's scale
+  P.k = (float)samples;
+  P.inv_normal = 1.0f / (d->sigma_normal * d->sigma_normal);
+  P.moments = var ? fb->moments : nullptr;
+  P.sigma_l = d->sigma_color;
+  const bool half = fb->gbuffer == RM_GBUFFER_F16;
+  for (int i = 0; i < L; i++) {
+    P.step = 1 << i;
+    P.inv_color = (float)(1 << (2 * i)) / (d->sigma_color * d->sigma_color);  // sigma_c^2 4^-i
+    P.sigma_z_h = d->sigma_depth * (float)P.step;
+    P.x_in = i > 0 ? x[(i - 1) % 2] : nullptr;
+    P.out = (i == L - 1 && out) ? out : x[i % 2];
+    RM_HIP(ctx, (var ? rm::launch_denoise_variance_pass : rm::launch_denoise_pass)(P, half, i == 0, i == L - 1, stream));
+  }
+  *result = P.out;
+  return RM_OK;
 }
 
-int rm_filter_device(rm_ctx* ctx, rm_fb* fb, int samples, const RmFilters* filters, void* out_float4_device, void* hip_stream) {
+// The three endings.  Onto a caller's device buffer, on the caller's stream (NULL = the context's): no host wait.
+static int filter_to_device(rm_ctx* ctx, rm_fb* fb, int samples, const RmFilters* f, const char* who, void* out_float4_device, void* hip_stream) {
   RmDenoise d{};
-  if (int rc = filters_check(ctx, fb, samples, filters, "rm_filter_device", &d)) return rc;
+  if (int rc = filters_check(ctx, fb, samples, f, who, &d)) return rc;
   if (!out_float4_device || (reinterpret_cast<uintptr_t>(out_float4_device) & 15u))
-    return fail(ctx, RM_ERR_INVALID, "rm_filter_device: the output must be a 16-byte aligned device buffer");
+    return fail(ctx, RM_ERR_INVALID, std::string(who) + ": the output must be a 16-byte aligned device buffer");
   const float4* r = nullptr;
-  return filters_enqueue(ctx, fb, samples, filters, &d, static_cast<float4*>(out_float4_device), hip_stream ? static_cast<hipStream_t>(hip_stream) : ctx->stream, &r);
+  return filters_enqueue(ctx, fb, samples, f, &d, static_cast<float4*>(out_float4_device), hip_stream ? static_cast<hipStream_t>(hip_stream) : ctx->stream, &r);
 }
 
-int rm_filter(rm_ctx* ctx, rm_fb* fb, int samples, const RmFilters* filters, float* out_host) {
+// Into host float4, on the context's stream; returns once it is idle.
+static int filter_to_host(rm_ctx* ctx, rm_fb* fb, int samples, const RmFilters* f, const char* who, float* out_host) {
   RmDenoise d{};
-  if (int rc = filters_check(ctx, fb, samples, filters, "rm_filter", &d)) return rc;
-  if (!out_host) return fail(ctx, RM_ERR_INVALID, "rm_filter: NULL argument");
+  if (int rc = filters_check(ctx, fb, samples, f, who, &d)) return rc;
+  if (!out_host) return fail(ctx, RM_ERR_INVALID, std::string(who) + ": NULL argument");
   const float4* r = nullptr;
-  if (int rc = filters_enqueue(ctx, fb, samples, filters, &d, nullptr, ctx->stream, &r)) return rc;
+  if (int rc = filters_enqueue(ctx, fb, samples, f, &d, nullptr, ctx->stream, &r)) return rc;
   RM_HIP(ctx, hipMemcpyAsync(out_host, r, (size_t)fb->width * (size_t)fb->height * sizeof(float4), hipMemcpyDeviceToHost, ctx->stream));
   RM_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return RM_OK;
 }
 
-int rm_present_filtered(rm_ctx* ctx, rm_fb* fb, int samples, const RmFilters* filters, uint8_t* out_rgba8) {
+// Through rm_present's pass into host RGBA8, likewise.
+static int filter_to_rgba8(rm_ctx* ctx, rm_fb* fb, int samples, const RmFilters* f, const char* who, uint8_t* out_rgba8) {
   RmDenoise d{};
-  if (int rc = filters_check(ctx, fb, samples, filters, "rm_present_filtered", &d)) return rc;
-  if (!out_rgba8) return fail(ctx, RM_ERR_INVALID, "rm_present_filtered: NULL argument");
+  if (int rc = filters_check(ctx, fb, samples, f, who, &d)) return rc;
+  if (!out_rgba8) return fail(ctx, RM_ERR_INVALID, std::string(who) + ": NULL argument");
   const float4* r = nullptr;
-  if (int rc = filters_enqueue(ctx, fb, samples, filters, &d, nullptr, ctx->stream, &r)) return rc;
+  if (int rc = filters_enqueue(ctx, fb, samples, f, &d, nullptr, ctx->stream, &r)) return rc;
   return present_planes(ctx, r, fb->plane[1], fb->gbuffer == RM_GBUFFER_F16, fb->width, fb->height, samples, out_rgba8);
+}
+
+int rm_denoise_device(rm_ctx* ctx, rm_fb* fb, int samples, const RmDenoise* params, void* out_float4_device, void* hip_stream) {
+  const RmFilters f = atrous_chain(params);
+  return filter_to_device(ctx, fb, samples, &f, "rm_denoise_device", out_float4_device, hip_stream);
+}
+int rm_denoise(rm_ctx* ctx, rm_fb* fb, int samples, const RmDenoise* params, float* out_host) {
+  const RmFilters f = atrous_chain(params);
+  return filter_to_host(ctx, fb, samples, &f, "rm_denoise", out_host);
+}
+int rm_present_denoised(rm_ctx* ctx, rm_fb* fb, int samples, const RmDenoise* params, uint8_t* out_rgba8) {
+  const RmFilters f = atrous_chain(params);
+  return filter_to_rgba8(ctx, fb, samples, &f, "rm_present_denoised", out_rgba8);
+}
+
+int rm_denoise_variance_device(rm_ctx* ctx, rm_fb* fb, int samples, const RmDenoiseVariance* params, void* out_float4_device, void* hip_stream) {
+  const RmFilters f = variance_chain(params);
+  return filter_to_device(ctx, fb, samples, &f, "rm_denoise_variance_device", out_float4_device, hip_stream);
+}
+int rm_denoise_variance(rm_ctx* ctx, rm_fb* fb, int samples, const RmDenoiseVariance* params, float* out_host) {
+  const RmFilters f = variance_chain(params);
+  return filter_to_host(ctx, fb, samples, &f, "rm_denoise_variance", out_host);
+}
+int rm_present_denoised_variance(rm_ctx* ctx, rm_fb* fb, int samples, const RmDenoiseVariance* params, uint8_t* out_rgba8) {
+  const RmFilters f = variance_chain(params);
+  return filter_to_rgba8(ctx, fb, samples, &f, "rm_present_denoised_variance", out_rgba8);
+}
+
+int rm_filter_device(rm_ctx* ctx, rm_fb* fb, int samples, const RmFilters* filters, void* out_float4_device, void* hip_stream) {
+  return filter_to_device(ctx, fb, samples, filters, "rm_filter_device", out_float4_device, hip_stream);
+}
+int rm_filter(rm_ctx* ctx, rm_fb* fb, int samples, const RmFilters* filters, float* out_host) {
+  return filter_to_host(ctx, fb, samples, filters, "rm_filter", out_host);
+}
+int rm_present_filtered(rm_ctx* ctx, rm_fb* fb, int samples, const RmFilters* filters, uint8_t* out_rgba8) {
+  return filter_to_rgba8(ctx, fb, samples, filters, "rm_present_filtered", out_rgba8);
 }
 
 // ---- present of a frame sharded over the GPUs of ONE process ----------------------------------------

@@ -463,65 +463,45 @@ async function doRenderJob(schema, context) {  // RenderJobExecutor.tsx:77
   };
 }
 
-// ---- denoise parameters (include/hip_raymarch.h RmDenoise, rm_denoise_default) ----
+// ---- parameters of the frame filters (include/hip_raymarch.h RmDenoise, RmDenoiseVariance, RmDespeckle and their rm_*_default) ----
 const DENOISE_DEFAULTS = { iterations: 5, sigma_color: 2.5, sigma_normal: 2.0, sigma_depth: 0.2 };
-// true / undefined / null = the defaults, or an object with some of DENOISE_DEFAULTS' fields; checked as the library checks them
-function denoiseParams(params) {
-  const p = { ...DENOISE_DEFAULTS };
-  if (params !== undefined && params !== null && params !== true) {
-    if (typeof params !== "object") throw new TypeError("denoise: expected true or an object of parameters");
+const DENOISE_VARIANCE_DEFAULTS = { iterations: 3, sigma_luminance: 4.0, sigma_normal: 1.0, sigma_depth: 0.2 };
+const DESPECKLE_DEFAULTS = { radius: 2, rank: 1, gain: 3.0, floor: 0.1, repair: 1 };
+// One table per block for filterParams: the prefix of its messages, the forms that mean "the defaults" as the refusal of any other
+// form names them, the defaults, the `mode` an object may name, the fields a boolean may set, and the library's own checks in the
+// library's order as field: [holds, text].
+const finite = (v) => typeof v === "number" && Number.isFinite(v);
+const POSITIVE = [(v) => finite(v) && v > 0, "must be finite and > 0"];
+const integerIn = (lo, hi) => [(v) => Number.isInteger(v) && v >= lo && v <= hi, "must be an integer in " + lo + ".." + hi];
+const FILTER_BLOCKS = {
+  atrous: { label: "denoise", forms: "true", defaults: DENOISE_DEFAULTS,
+            checks: { iterations: integerIn(0, 8), sigma_color: POSITIVE, sigma_normal: POSITIVE, sigma_depth: POSITIVE } },
+  variance: { label: "denoise", forms: "\"variance\"", defaults: DENOISE_VARIANCE_DEFAULTS, mode: "variance",
+              checks: { iterations: integerIn(0, 8), sigma_luminance: POSITIVE, sigma_normal: POSITIVE, sigma_depth: POSITIVE } },
+  despeckle: { label: "despeckle", forms: "true", defaults: DESPECKLE_DEFAULTS, flags: ["repair"],
+               checks: { radius: [(v) => v === 1 || v === 2, "must be 1 or 2"], rank: integerIn(0, 3), gain: [(v) => finite(v) && v >= 1, "must be finite and >= 1"],
+                         floor: [(v) => finite(v) && v >= 0, "must be finite and >= 0"], repair: [Number.isInteger, "must be an integer (0 = off)"] } },
+};
+// true / undefined / null / the block's mode = the defaults, or an object with some of the defaults' fields (and the block's mode);
+// checked as the library checks them
+function filterParams({ label, forms, defaults, mode, flags = [], checks }, params) {
+  const p = { ...defaults };
+  if (params !== undefined && params !== null && params !== true && !(mode !== undefined && params === mode)) {
+    if (typeof params !== "object") throw new TypeError(label + ": expected " + forms + " or an object of parameters");
     for (const [k, v] of Object.entries(params)) {
-      if (!(k in DENOISE_DEFAULTS)) throw new TypeError("denoise: unknown parameter " + k);
-      p[k] = v;
+      if (mode !== undefined && k === "mode") { if (v !== mode) throw new TypeError(label + ": mode " + v + " is not the " + mode + "-guided filter"); continue; }
+      if (!(k in defaults)) throw new TypeError(label + ": unknown parameter " + k);
+      p[k] = flags.includes(k) && typeof v === "boolean" ? Number(v) : v;
     }
   }
-  if (!Number.isInteger(p.iterations) || p.iterations < 0 || p.iterations > 8) throw new RangeError("denoise: iterations must be an integer in 0..8");
-  for (const k of ["sigma_color", "sigma_normal", "sigma_depth"])
-    if (!(typeof p[k] === "number" && Number.isFinite(p[k]) && p[k] > 0)) throw new RangeError("denoise: " + k + " must be finite and > 0");
+  for (const [k, [holds, text]] of Object.entries(checks)) if (!holds(p[k])) throw new RangeError(label + ": " + k + " " + text);
   return p;
 }
-
-// ---- variance-guided denoise parameters (include/hip_raymarch.h RmDenoiseVariance, rm_denoise_variance_default) ----
-const DENOISE_VARIANCE_DEFAULTS = { iterations: 3, sigma_luminance: 4.0, sigma_normal: 1.0, sigma_depth: 0.2 };
+function denoiseParams(params) { return filterParams(FILTER_BLOCKS.atrous, params); }
+function denoiseVarianceParams(params) { return filterParams(FILTER_BLOCKS.variance, params); }
+function despeckleParams(params) { return filterParams(FILTER_BLOCKS.despeckle, params); }
 function isVarianceMode(d) { return d === "variance" || (d !== null && typeof d === "object" && d.mode === "variance"); }
 function withoutMode(d) { const { mode, ...rest } = d; return rest; }
-// true / "variance" / undefined / null = the defaults, or an object with some of DENOISE_VARIANCE_DEFAULTS' fields (and mode: "variance");
-// checked as the library checks them
-function denoiseVarianceParams(params) {
-  const p = { ...DENOISE_VARIANCE_DEFAULTS };
-  if (params !== undefined && params !== null && params !== true && params !== "variance") {
-    if (typeof params !== "object") throw new TypeError("denoise: expected \"variance\" or an object of parameters");
-    for (const [k, v] of Object.entries(params)) {
-      if (k === "mode") { if (v !== "variance") throw new TypeError("denoise: mode " + v + " is not the variance-guided filter"); continue; }
-      if (!(k in DENOISE_VARIANCE_DEFAULTS)) throw new TypeError("denoise: unknown parameter " + k);
-      p[k] = v;
-    }
-  }
-  if (!Number.isInteger(p.iterations) || p.iterations < 0 || p.iterations > 8) throw new RangeError("denoise: iterations must be an integer in 0..8");
-  for (const k of ["sigma_luminance", "sigma_normal", "sigma_depth"])
-    if (!(typeof p[k] === "number" && Number.isFinite(p[k]) && p[k] > 0)) throw new RangeError("denoise: " + k + " must be finite and > 0");
-  return p;
-}
-
-// ---- firefly filter parameters (include/hip_raymarch.h RmDespeckle, rm_filters_default) ----
-const DESPECKLE_DEFAULTS = { radius: 2, rank: 1, gain: 3.0, floor: 0.1, repair: 1 };
-// true / undefined / null = the defaults, or an object with some of DESPECKLE_DEFAULTS' fields; checked as the library checks them
-function despeckleParams(params) {
-  const p = { ...DESPECKLE_DEFAULTS };
-  if (params !== undefined && params !== null && params !== true) {
-    if (typeof params !== "object") throw new TypeError("despeckle: expected true or an object of parameters");
-    for (const [k, v] of Object.entries(params)) {
-      if (!(k in DESPECKLE_DEFAULTS)) throw new TypeError("despeckle: unknown parameter " + k);
-      p[k] = k === "repair" && typeof v === "boolean" ? Number(v) : v;
-    }
-  }
-  if (p.radius !== 1 && p.radius !== 2) throw new RangeError("despeckle: radius must be 1 or 2");
-  if (!Number.isInteger(p.rank) || p.rank < 0 || p.rank > 3) throw new RangeError("despeckle: rank must be an integer in 0..3");
-  if (!(typeof p.gain === "number" && Number.isFinite(p.gain) && p.gain >= 1)) throw new RangeError("despeckle: gain must be finite and >= 1");
-  if (!(typeof p.floor === "number" && Number.isFinite(p.floor) && p.floor >= 0)) throw new RangeError("despeckle: floor must be finite and >= 0");
-  if (!Number.isInteger(p.repair)) throw new RangeError("despeckle: repair must be an integer (0 = off)");
-  return p;
-}
 // the addon's RmFilters of { despeckle, denoise }: a stage that is undefined / null / false is off
 function filters(opts = {}) {
   const off = (v) => v === undefined || v === null || v === false;

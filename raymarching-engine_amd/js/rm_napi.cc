@@ -8,6 +8,7 @@
 // ({success:false, why}), RenderJobExecutor.tsx:112-136.
 #include <node_api.h>
 
+#include <cstddef>
 #include <cstdint>
 #include <cstring>
 #include <string>
@@ -247,140 +248,57 @@ static napi_value Present(napi_env env, napi_callback_info info) {
   return nullptr;
 }
 
-// The RmDenoise of a JS value: null / undefined = rm_denoise_default; an object's iterations, sigma_color, sigma_normal and
-// sigma_depth (numbers) over the defaults.  The library checks the values (RM_ERR_INVALID before any device work).
-static bool get_denoise(napi_env env, napi_value v, RmDenoise* p) {
-  rm_denoise_default(p);
+// ---- the frame filters: denoise*, denoiseVariance*, filter* ----
+// A parameter block's fields as JS names them.  INT: a number truncated to int (-1 beyond +-1e9, which every range check refuses);
+// FLAG: 1 for a number other than 0, else 0.  The library checks the values (RM_ERR_INVALID before any device work).
+struct Field {
+  const char* name;
+  enum Kind { INT, FLOAT, FLAG } kind;
+  size_t offset;
+};
+static const Field DENOISE_FIELDS[] = {{"iterations", Field::INT, offsetof(RmDenoise, iterations)}, {"sigma_color", Field::FLOAT, offsetof(RmDenoise, sigma_color)},
+                                       {"sigma_normal", Field::FLOAT, offsetof(RmDenoise, sigma_normal)}, {"sigma_depth", Field::FLOAT, offsetof(RmDenoise, sigma_depth)}};
+static const Field VARIANCE_FIELDS[] = {{"iterations", Field::INT, offsetof(RmDenoiseVariance, iterations)}, {"sigma_luminance", Field::FLOAT, offsetof(RmDenoiseVariance, sigma_luminance)},
+                                        {"sigma_normal", Field::FLOAT, offsetof(RmDenoiseVariance, sigma_normal)}, {"sigma_depth", Field::FLOAT, offsetof(RmDenoiseVariance, sigma_depth)}};
+static const Field DESPECKLE_FIELDS[] = {{"radius", Field::INT, offsetof(RmDespeckle, radius)}, {"rank", Field::INT, offsetof(RmDespeckle, rank)}, {"gain", Field::FLOAT, offsetof(RmDespeckle, gain)},
+                                         {"floor", Field::FLOAT, offsetof(RmDespeckle, floor)}, {"repair", Field::FLAG, offsetof(RmDespeckle, repair)}};
+
+// A parameter block of a JS value, over the defaults the caller has filled in: null / undefined leave them (*given = false); an
+// object's properties named in `fields` (numbers) replace them, its other properties are ignored; anything else is refused.
+template <size_t N>
+static bool get_block(napi_env env, napi_value v, void* block, const Field (&fields)[N], bool* given = nullptr) {
   napi_valuetype t;
   if (napi_typeof(env, v, &t) != napi_ok) return false;
+  if (given) *given = t == napi_object;
   if (t == napi_undefined || t == napi_null) return true;
   if (t != napi_object) return false;
-  const char* names[4] = {"iterations", "sigma_color", "sigma_normal", "sigma_depth"};
-  for (int k = 0; k < 4; k++) {
+  for (const Field& f : fields) {
     bool has = false;
-    napi_value f;
-    if (napi_has_named_property(env, v, names[k], &has) != napi_ok) return false;
+    napi_value x;
+    if (napi_has_named_property(env, v, f.name, &has) != napi_ok) return false;
     if (!has) continue;
     double d = 0.0;
-    if (napi_get_named_property(env, v, names[k], &f) != napi_ok || napi_get_value_double(env, f, &d) != napi_ok) return false;
-    if (k == 0) p->iterations = (d >= -1e9 && d <= 1e9) ? (int)d : -1;
-    else (k == 1 ? p->sigma_color : k == 2 ? p->sigma_normal : p->sigma_depth) = (float)d;
+    if (napi_get_named_property(env, v, f.name, &x) != napi_ok || napi_get_value_double(env, x, &d) != napi_ok) return false;
+    char* at = static_cast<char*>(block) + f.offset;
+    if (f.kind == Field::FLOAT) *reinterpret_cast<float*>(at) = (float)d;
+    else *reinterpret_cast<int*>(at) = f.kind == Field::FLAG ? (d != 0.0 ? 1 : 0) : (d >= -1e9 && d <= 1e9) ? (int)d : -1;
   }
   return true;
 }
 
-// denoise(ctx, fb, samples, params, out: Float32Array(width * height * 4)) = rm_denoise: colour-plane units, row 0 = bottom
-// presentDenoised(ctx, fb, samples, params, out: Uint8Array(width * height * 4)) = rm_present_denoised
-static napi_value denoise_common(napi_env env, napi_callback_info info, bool present) {
-  const char* who = present ? "presentDenoised" : "denoise";
-  size_t argc = 5;
-  napi_value argv[5];
-  NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
-  rm_ctx* ctx = argc == 5 ? get_external<rm_ctx>(env, argv[0]) : nullptr;
-  rm_fb* fb = argc == 5 ? get_external<rm_fb>(env, argv[1]) : nullptr;
-  int32_t samples = 1;
-  RmDenoise p;
-  void* d = nullptr;
-  size_t n = 0;
-  if (!ctx || !fb || napi_get_value_int32(env, argv[2], &samples) != napi_ok || !get_denoise(env, argv[3], &p) || !get_buffer(env, argv[4], &d, &n)) {
-    napi_throw_type_error(env, nullptr, present ? "presentDenoised(ctx, fb, samples, params, out: Uint8Array)" : "denoise(ctx, fb, samples, params, out: Float32Array)");
-    return nullptr;
-  }
-  const size_t need = (size_t)rm_fb_width(fb) * (size_t)rm_fb_rows(fb) * 4 * (present ? 1 : sizeof(float));
-  if (n < need) {
-    napi_throw_range_error(env, nullptr, (std::string(who) + ": out is smaller than the frame").c_str());
-    return nullptr;
-  }
-  const int rc = present ? rm_present_denoised(ctx, fb, samples, &p, static_cast<uint8_t*>(d)) : rm_denoise(ctx, fb, samples, &p, static_cast<float*>(d));
-  if (rc != RM_OK) return throw_rm(env, ctx, present ? "rm_present_denoised" : "rm_denoise");
-  return nullptr;
-}
-static napi_value Denoise(napi_env env, napi_callback_info info) { return denoise_common(env, info, false); }
-static napi_value PresentDenoised(napi_env env, napi_callback_info info) { return denoise_common(env, info, true); }
-
-// The RmDenoiseVariance of a JS value: null / undefined = rm_denoise_variance_default; an object's iterations, sigma_luminance,
-// sigma_normal and sigma_depth (numbers) over the defaults; other properties are ignored.  The library checks the values.
-static bool get_denoise_variance(napi_env env, napi_value v, RmDenoiseVariance* p) {
-  rm_denoise_variance_default(p);
-  napi_valuetype t;
-  if (napi_typeof(env, v, &t) != napi_ok) return false;
-  if (t == napi_undefined || t == napi_null) return true;
-  if (t != napi_object) return false;
-  const char* names[4] = {"iterations", "sigma_luminance", "sigma_normal", "sigma_depth"};
-  for (int k = 0; k < 4; k++) {
-    bool has = false;
-    napi_value f;
-    if (napi_has_named_property(env, v, names[k], &has) != napi_ok) return false;
-    if (!has) continue;
-    double d = 0.0;
-    if (napi_get_named_property(env, v, names[k], &f) != napi_ok || napi_get_value_double(env, f, &d) != napi_ok) return false;
-    if (k == 0) p->iterations = (d >= -1e9 && d <= 1e9) ? (int)d : -1;
-    else (k == 1 ? p->sigma_luminance : k == 2 ? p->sigma_normal : p->sigma_depth) = (float)d;
-  }
-  return true;
-}
-
-// denoiseVariance(ctx, fb, samples, params, out: Float32Array(width * height * 4)) = rm_denoise_variance
-// presentDenoisedVariance(ctx, fb, samples, params, out: Uint8Array(width * height * 4)) = rm_present_denoised_variance
-static napi_value denoise_variance_common(napi_env env, napi_callback_info info, bool present) {
-  const char* who = present ? "presentDenoisedVariance" : "denoiseVariance";
-  size_t argc = 5;
-  napi_value argv[5];
-  NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
-  rm_ctx* ctx = argc == 5 ? get_external<rm_ctx>(env, argv[0]) : nullptr;
-  rm_fb* fb = argc == 5 ? get_external<rm_fb>(env, argv[1]) : nullptr;
-  int32_t samples = 1;
-  RmDenoiseVariance p;
-  void* d = nullptr;
-  size_t n = 0;
-  if (!ctx || !fb || napi_get_value_int32(env, argv[2], &samples) != napi_ok || !get_denoise_variance(env, argv[3], &p) || !get_buffer(env, argv[4], &d, &n)) {
-    napi_throw_type_error(env, nullptr, present ? "presentDenoisedVariance(ctx, fb, samples, params, out: Uint8Array)" : "denoiseVariance(ctx, fb, samples, params, out: Float32Array)");
-    return nullptr;
-  }
-  const size_t need = (size_t)rm_fb_width(fb) * (size_t)rm_fb_rows(fb) * 4 * (present ? 1 : sizeof(float));
-  if (n < need) {
-    napi_throw_range_error(env, nullptr, (std::string(who) + ": out is smaller than the frame").c_str());
-    return nullptr;
-  }
-  const int rc = present ? rm_present_denoised_variance(ctx, fb, samples, &p, static_cast<uint8_t*>(d)) : rm_denoise_variance(ctx, fb, samples, &p, static_cast<float*>(d));
-  if (rc != RM_OK) return throw_rm(env, ctx, present ? "rm_present_denoised_variance" : "rm_denoise_variance");
-  return nullptr;
-}
-static napi_value DenoiseVariance(napi_env env, napi_callback_info info) { return denoise_variance_common(env, info, false); }
-static napi_value PresentDenoisedVariance(napi_env env, napi_callback_info info) { return denoise_variance_common(env, info, true); }
-
-// The RmFilters of a JS object { despeckle, denoise, atrous, variance }: rm_filters_default, then `despeckle` (null / undefined = the
-// stage off, or an object's radius, rank, gain, floor and repair over the defaults = the stage on), `denoise` (the RM_DENOISE_* number;
-// undefined = none) and the parameter blocks `atrous` / `variance` as denoise / denoiseVariance take them.  The library checks the values.
+// The RmFilters (at rm_filters_default) of a JS object { despeckle, denoise, atrous, variance }: `despeckle` (null / undefined = the
+// stage off, an object of its parameters = the stage on), `denoise` (the RM_DENOISE_* number; undefined = none) and the parameter
+// blocks `atrous` / `variance` as denoise / denoiseVariance take them.
 static bool get_filters(napi_env env, napi_value v, RmFilters* f) {
-  rm_filters_default(f);
   napi_valuetype t;
   if (napi_typeof(env, v, &t) != napi_ok || t != napi_object) return false;
   napi_value d, m, a, va;
   if (napi_get_named_property(env, v, "despeckle", &d) != napi_ok || napi_get_named_property(env, v, "denoise", &m) != napi_ok ||
       napi_get_named_property(env, v, "atrous", &a) != napi_ok || napi_get_named_property(env, v, "variance", &va) != napi_ok)
     return false;
-  if (napi_typeof(env, d, &t) != napi_ok) return false;
-  if (t == napi_object) {
-    f->despeckle = 1;
-    const char* names[5] = {"radius", "rank", "gain", "floor", "repair"};
-    for (int k = 0; k < 5; k++) {
-      bool has = false;
-      napi_value p;
-      if (napi_has_named_property(env, d, names[k], &has) != napi_ok) return false;
-      if (!has) continue;
-      double x = 0.0;
-      if (napi_get_named_property(env, d, names[k], &p) != napi_ok || napi_get_value_double(env, p, &x) != napi_ok) return false;
-      const int i = (x >= -1e9 && x <= 1e9) ? (int)x : -1;
-      if (k == 0) f->despeckle_params.radius = i;
-      else if (k == 1) f->despeckle_params.rank = i;
-      else if (k == 2) f->despeckle_params.gain = (float)x;
-      else if (k == 3) f->despeckle_params.floor = (float)x;
-      else f->despeckle_params.repair = x != 0.0 ? 1 : 0;
-    }
-  } else if (t != napi_undefined && t != napi_null) {
-    return false;
-  }
+  bool on = false;
+  if (!get_block(env, d, &f->despeckle_params, DESPECKLE_FIELDS, &on)) return false;
+  f->despeckle = on ? 1 : 0;
   if (napi_typeof(env, m, &t) != napi_ok) return false;
   if (t == napi_number) {
     int32_t mode = 0;
@@ -389,13 +307,19 @@ static bool get_filters(napi_env env, napi_value v, RmFilters* f) {
   } else if (t != napi_undefined && t != napi_null) {
     return false;
   }
-  return get_denoise(env, a, &f->atrous) && get_denoise_variance(env, va, &f->variance);
+  return get_block(env, a, &f->atrous, DENOISE_FIELDS) && get_block(env, va, &f->variance, VARIANCE_FIELDS);
 }
 
-// filter(ctx, fb, samples, filters, out: Float32Array(width * height * 4)) = rm_filter: colour-plane units, row 0 = bottom
-// presentFiltered(ctx, fb, samples, filters, out: Uint8Array(width * height * 4)) = rm_present_filtered
-static napi_value filter_common(napi_env env, napi_callback_info info, bool present) {
-  const char* who = present ? "presentFiltered" : "filter";
+// The six exports, (ctx, fb, samples, params | filters, out), each through its own C entry point.  `out` of the float plane:
+// Float32Array(width * height * 4), colour-plane units; of the present: Uint8Array(width * height * 4); row 0 = bottom.
+//   denoise         = rm_denoise           presentDenoised         = rm_present_denoised            params: RmDenoise's fields, or null
+//   denoiseVariance = rm_denoise_variance  presentDenoisedVariance = rm_present_denoised_variance   params: RmDenoiseVariance's, or null
+//   filter          = rm_filter            presentFiltered         = rm_present_filtered            filters: what get_filters takes
+enum Family { ATROUS, VARIANCE, CHAIN };
+static napi_value filter_common(napi_env env, napi_callback_info info, Family family, bool present) {
+  static const char* const JS_NAME[3][2] = {{"denoise", "presentDenoised"}, {"denoiseVariance", "presentDenoisedVariance"}, {"filter", "presentFiltered"}};
+  static const char* const C_NAME[3][2] = {{"rm_denoise", "rm_present_denoised"}, {"rm_denoise_variance", "rm_present_denoised_variance"}, {"rm_filter", "rm_present_filtered"}};
+  const std::string who = JS_NAME[family][present];
   size_t argc = 5;
   napi_value argv[5];
   NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
@@ -403,23 +327,34 @@ static napi_value filter_common(napi_env env, napi_callback_info info, bool pres
   rm_fb* fb = argc == 5 ? get_external<rm_fb>(env, argv[1]) : nullptr;
   int32_t samples = 1;
   RmFilters f;
+  rm_filters_default(&f);
   void* d = nullptr;
   size_t n = 0;
-  if (!ctx || !fb || napi_get_value_int32(env, argv[2], &samples) != napi_ok || !get_filters(env, argv[3], &f) || !get_buffer(env, argv[4], &d, &n)) {
-    napi_throw_type_error(env, nullptr, present ? "presentFiltered(ctx, fb, samples, filters, out: Uint8Array)" : "filter(ctx, fb, samples, filters, out: Float32Array)");
+  if (!ctx || !fb || napi_get_value_int32(env, argv[2], &samples) != napi_ok ||
+      !(family == ATROUS ? get_block(env, argv[3], &f.atrous, DENOISE_FIELDS) : family == VARIANCE ? get_block(env, argv[3], &f.variance, VARIANCE_FIELDS) : get_filters(env, argv[3], &f)) ||
+      !get_buffer(env, argv[4], &d, &n)) {
+    napi_throw_type_error(env, nullptr, (who + "(ctx, fb, samples, " + (family == CHAIN ? "filters" : "params") + ", out: " + (present ? "Uint8Array" : "Float32Array") + ")").c_str());
     return nullptr;
   }
   const size_t need = (size_t)rm_fb_width(fb) * (size_t)rm_fb_rows(fb) * 4 * (present ? 1 : sizeof(float));
   if (n < need) {
-    napi_throw_range_error(env, nullptr, (std::string(who) + ": out is smaller than the frame").c_str());
+    napi_throw_range_error(env, nullptr, (who + ": out is smaller than the frame").c_str());
     return nullptr;
   }
-  const int rc = present ? rm_present_filtered(ctx, fb, samples, &f, static_cast<uint8_t*>(d)) : rm_filter(ctx, fb, samples, &f, static_cast<float*>(d));
-  if (rc != RM_OK) return throw_rm(env, ctx, present ? "rm_present_filtered" : "rm_filter");
+  uint8_t* rgba8 = static_cast<uint8_t*>(d);
+  float* plane = static_cast<float*>(d);
+  const int rc = family == ATROUS     ? (present ? rm_present_denoised(ctx, fb, samples, &f.atrous, rgba8) : rm_denoise(ctx, fb, samples, &f.atrous, plane))
+                 : family == VARIANCE ? (present ? rm_present_denoised_variance(ctx, fb, samples, &f.variance, rgba8) : rm_denoise_variance(ctx, fb, samples, &f.variance, plane))
+                                      : (present ? rm_present_filtered(ctx, fb, samples, &f, rgba8) : rm_filter(ctx, fb, samples, &f, plane));
+  if (rc != RM_OK) return throw_rm(env, ctx, C_NAME[family][present]);
   return nullptr;
 }
-static napi_value Filter(napi_env env, napi_callback_info info) { return filter_common(env, info, false); }
-static napi_value PresentFiltered(napi_env env, napi_callback_info info) { return filter_common(env, info, true); }
+static napi_value Denoise(napi_env env, napi_callback_info info) { return filter_common(env, info, ATROUS, false); }
+static napi_value PresentDenoised(napi_env env, napi_callback_info info) { return filter_common(env, info, ATROUS, true); }
+static napi_value DenoiseVariance(napi_env env, napi_callback_info info) { return filter_common(env, info, VARIANCE, false); }
+static napi_value PresentDenoisedVariance(napi_env env, napi_callback_info info) { return filter_common(env, info, VARIANCE, true); }
+static napi_value Filter(napi_env env, napi_callback_info info) { return filter_common(env, info, CHAIN, false); }
+static napi_value PresentFiltered(napi_env env, napi_callback_info info) { return filter_common(env, info, CHAIN, true); }
 
 // fbCreateStriped(ctx, width, height, stripeRows, parts, part[, gbuffer]): the stripes k with k % parts == part of a width x height image,
 // planes owned by the library (rm_fb_create_striped) -- what one GPU of a sharded frame holds

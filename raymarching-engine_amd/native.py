@@ -52,59 +52,73 @@ def gbuffer_code(gbuffer: str) -> int:
     return GBUFFER_FORMATS[gbuffer]
 
 
-def denoise_params(params=None) -> abi.RmDenoise:
-    """An abi.RmDenoise from None / True (the defaults, rm_denoise_default), a dict of some of its fields over the defaults, or an
-    abi.RmDenoise.  Checked here as the library checks it (iterations in 0..8, every sigma finite and > 0): ValueError otherwise."""
-    if isinstance(params, abi.RmDenoise):
+# The hosts' parameter blocks (include/hip_raymarch.h), one table each for _params: the prefix of its messages, the forms that mean
+# "the defaults" as the refusal of any other form lists them, the defaults, the dict entry that may name the filter ("mode"), the
+# fields a dict has to give as integers / as numbers, and the library's own checks in the library's order as field: (holds, text)
+# -- `reserved` is listed where it must be 0.
+_POSITIVE = (lambda v: math.isfinite(v) and v > 0.0, "must be finite and > 0")
+_ITERATIONS = (lambda v: 0 <= v <= 8, "must be in 0..8")
+_ZERO = (lambda v: v == 0, "must be 0")
+_BLOCKS = {
+    abi.RmDenoise: dict(label="denoise", forms="True", defaults=abi.DENOISE_DEFAULTS,
+                        checks=dict(iterations=_ITERATIONS, sigma_color=_POSITIVE, sigma_normal=_POSITIVE, sigma_depth=_POSITIVE)),
+    abi.RmDenoiseVariance: dict(label="denoise", forms='True, "variance"', defaults=abi.DENOISE_VARIANCE_DEFAULTS, mode="variance",
+                                checks=dict(iterations=_ITERATIONS, sigma_luminance=_POSITIVE, sigma_normal=_POSITIVE, sigma_depth=_POSITIVE,
+                                            reserved=_ZERO)),
+    abi.RmDespeckle: dict(label="despeckle", forms="True", defaults=abi.DESPECKLE_DEFAULTS, integers=("radius", "rank", "repair"),
+                          numbers=("gain", "floor"),
+                          checks=dict(radius=(lambda v: v in (1, 2), "must be 1 or 2"), rank=(lambda v: 0 <= v <= 3, "must be in 0..3"),
+                                      gain=(lambda v: math.isfinite(v) and v >= 1.0, "must be finite and >= 1"),
+                                      floor=(lambda v: math.isfinite(v) and v >= 0.0, "must be finite and >= 0"), reserved=_ZERO)),
+}
+
+
+def _params(struct, params):
+    """The block `struct` from None / True / its mode's name (the defaults), a dict of some of its fields over the defaults, or a
+    `struct`, which is returned as it is; checked as the library checks it: ValueError otherwise."""
+    b = _BLOCKS[struct]
+    label, mode = b["label"], b.get("mode")
+    if isinstance(params, struct):
         p = params
     else:
-        if params is None or params is True:
+        if params is None or params is True or (mode is not None and params == mode):
             fields = {}
         elif isinstance(params, dict):
             fields = dict(params)
+            if mode is not None and fields.pop("mode", mode) != mode:
+                raise ValueError(f"{label}: mode {params['mode']!r} is not the {mode}-guided filter")
         else:
-            raise ValueError(f"denoise: expected True, a dict or abi.RmDenoise, got {params!r}")
-        unknown = set(fields) - set(abi.DENOISE_DEFAULTS)
+            raise ValueError(f"{label}: expected {b['forms']}, a dict or abi.{struct.__name__}, got {params!r}")
+        unknown = set(fields) - set(b["defaults"])
         if unknown:
-            raise ValueError(f"denoise: unknown parameter(s) {sorted(unknown)}; known: {sorted(abi.DENOISE_DEFAULTS)}")
-        p = abi.RmDenoise(**{**abi.DENOISE_DEFAULTS, **fields})
-    if not 0 <= p.iterations <= 8:
-        raise ValueError("denoise: iterations must be in 0..8")
-    for name in ("sigma_color", "sigma_normal", "sigma_depth"):
-        v = getattr(p, name)
-        if not (math.isfinite(v) and v > 0.0):
-            raise ValueError(f"denoise: {name} must be finite and > 0")
+            raise ValueError(f"{label}: unknown parameter(s) {sorted(unknown)}; known: {sorted(b['defaults'])}")
+        fields = {**b["defaults"], **fields}
+        for name in b.get("integers", ()):
+            if isinstance(fields[name], bool):
+                fields[name] = int(fields[name])
+            if not isinstance(fields[name], (int, np.integer)):
+                raise ValueError(f"{label}: {name} must be an integer")
+        for name in b.get("numbers", ()):
+            if isinstance(fields[name], bool) or not isinstance(fields[name], (int, float, np.integer, np.floating)):
+                raise ValueError(f"{label}: {name} must be a number")
+        p = struct(**fields)
+    for name, (holds, text) in b["checks"].items():
+        if not holds(getattr(p, name)):
+            raise ValueError(f"{label}: {name} {text}")
     return p
+
+
+def denoise_params(params=None) -> abi.RmDenoise:
+    """An abi.RmDenoise from None / True (the defaults, rm_denoise_default), a dict of some of its fields over the defaults, or an
+    abi.RmDenoise.  Checked here as the library checks it (iterations in 0..8, every sigma finite and > 0): ValueError otherwise."""
+    return _params(abi.RmDenoise, params)
 
 
 def denoise_variance_params(params=None) -> abi.RmDenoiseVariance:
     """An abi.RmDenoiseVariance from None / True / "variance" (the defaults, rm_denoise_variance_default), a dict of some of its
     fields over the defaults (a "mode": "variance" entry allowed), or an abi.RmDenoiseVariance.  Checked as the library checks it
     (iterations in 0..8, every sigma finite and > 0, reserved 0): ValueError otherwise."""
-    if isinstance(params, abi.RmDenoiseVariance):
-        p = params
-    else:
-        if params is None or params is True or params == "variance":
-            fields = {}
-        elif isinstance(params, dict):
-            fields = {k: v for k, v in params.items() if k != "mode"}
-            if params.get("mode", "variance") != "variance":
-                raise ValueError(f"denoise: mode {params['mode']!r} is not the variance-guided filter")
-        else:
-            raise ValueError(f"denoise: expected True, \"variance\", a dict or abi.RmDenoiseVariance, got {params!r}")
-        unknown = set(fields) - set(abi.DENOISE_VARIANCE_DEFAULTS)
-        if unknown:
-            raise ValueError(f"denoise: unknown parameter(s) {sorted(unknown)}; known: {sorted(abi.DENOISE_VARIANCE_DEFAULTS)}")
-        p = abi.RmDenoiseVariance(**{**abi.DENOISE_VARIANCE_DEFAULTS, **fields})
-    if not 0 <= p.iterations <= 8:
-        raise ValueError("denoise: iterations must be in 0..8")
-    for name in ("sigma_luminance", "sigma_normal", "sigma_depth"):
-        v = getattr(p, name)
-        if not (math.isfinite(v) and v > 0.0):
-            raise ValueError(f"denoise: {name} must be finite and > 0")
-    if p.reserved != 0:
-        raise ValueError("denoise: reserved must be 0")
-    return p
+    return _params(abi.RmDenoiseVariance, params)
 
 
 def denoise_mode(denoise):
@@ -125,39 +139,7 @@ def despeckle_params(params=None) -> abi.RmDespeckle:
     """An abi.RmDespeckle from None / True (the defaults, rm_filters_default's), a dict of some of its fields over the defaults, or
     an abi.RmDespeckle.  Checked here as the library checks it (radius 1 or 2, rank in 0..3, gain finite and >= 1, floor finite and
     >= 0, reserved 0): ValueError otherwise."""
-    if isinstance(params, abi.RmDespeckle):
-        p = params
-    else:
-        if params is None or params is True:
-            fields = {}
-        elif isinstance(params, dict):
-            fields = dict(params)
-        else:
-            raise ValueError(f"despeckle: expected True, a dict or abi.RmDespeckle, got {params!r}")
-        unknown = set(fields) - set(abi.DESPECKLE_DEFAULTS)
-        if unknown:
-            raise ValueError(f"despeckle: unknown parameter(s) {sorted(unknown)}; known: {sorted(abi.DESPECKLE_DEFAULTS)}")
-        fields = {**abi.DESPECKLE_DEFAULTS, **fields}
-        for name in ("radius", "rank", "repair"):
-            if isinstance(fields[name], bool):
-                fields[name] = int(fields[name])
-            if not isinstance(fields[name], (int, np.integer)):
-                raise ValueError(f"despeckle: {name} must be an integer")
-        for name in ("gain", "floor"):
-            if isinstance(fields[name], bool) or not isinstance(fields[name], (int, float, np.integer, np.floating)):
-                raise ValueError(f"despeckle: {name} must be a number")
-        p = abi.RmDespeckle(**fields)
-    if p.radius not in (1, 2):
-        raise ValueError("despeckle: radius must be 1 or 2")
-    if not 0 <= p.rank <= 3:
-        raise ValueError("despeckle: rank must be in 0..3")
-    if not (math.isfinite(p.gain) and p.gain >= 1.0):
-        raise ValueError("despeckle: gain must be finite and >= 1")
-    if not (math.isfinite(p.floor) and p.floor >= 0.0):
-        raise ValueError("despeckle: floor must be finite and >= 0")
-    if p.reserved != 0:
-        raise ValueError("despeckle: reserved must be 0")
-    return p
+    return _params(abi.RmDespeckle, params)
 
 
 def filters(despeckle=None, denoise=None) -> abi.RmFilters:
