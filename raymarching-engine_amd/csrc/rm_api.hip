@@ -174,6 +174,51 @@ enum {
 struct Scratch {
   void* p = nullptr;
   size_t bytes = 0;
+  bool pinned_host = false;  // page-locked host memory instead of device memory
+  void release() {
+    if (p) (void)(pinned_host ? hipHostFree(p) : hipFree(p));
+    p = nullptr;
+    bytes = 0;
+  }
+};
+
+// rm_present_sharded (one process driving several GPUs): this context's rows of the payload, and on the context that shows the
+// frame -- the root -- the gathered parts and the frame in image order; grown on demand (scratch_reserve), freed with the context.
+struct ShardPresent {
+  enum {
+    ROWS,    // this context's rows of the payload (packed float4 or RGBA8)
+    ROWS8,   // depth of field: this context's rows after ITS blur (RGBA8)
+    ALL,     // depth of field: every part's packed rows (the all-gather's receive side)
+    RECV,    // root: every part's RGBA8 rows
+    FRAME,   // depth of field: the packed frame in image order (every context)
+    CANVAS,  // root: the RGBA8 canvas in image order
+    HOST,    // root: pinned host copy of the canvas (rm_present_sharded_finish reads it)
+    COUNT
+  };
+  Scratch buf[COUNT];
+  hipStream_t stream = nullptr;                         // copies, assembly and blur of a present travel here, next to the renders
+  hipEvent_t snap = nullptr, ev = nullptr, done = nullptr;  // snapshot written; this context's part delivered; root: canvas on the host
+  bool pending = false;                                 // root: a start without its finish
+  int w = 0, h = 0;                                     // root: the canvas of the pending present
+
+  ShardPresent() { buf[HOST].pinned_host = true; }
+  template <class T> T* as(int which) const { return static_cast<T*>(buf[which].p); }
+  // the stream and the events, made with the first present (the caller has selected the device); `done` on the root alone
+  hipError_t ensure(bool root) {
+    hipError_t e = hipSuccess;
+    if (!stream) e = hipStreamCreateWithFlags(&stream, hipStreamNonBlocking);
+    for (hipEvent_t* event : {&snap, &ev, root ? &done : nullptr})
+      if (e == hipSuccess && event && !*event) e = hipEventCreateWithFlags(event, hipEventDisableTiming);
+    return e;
+  }
+  // waits for the present stream before anything it may still write is freed; then the buffers, the stream, the events
+  void destroy() {
+    if (stream) (void)hipStreamSynchronize(stream);
+    for (Scratch& b : buf) b.release();
+    if (stream) (void)hipStreamDestroy(stream);
+    for (hipEvent_t event : {snap, ev, done})
+      if (event) (void)hipEventDestroy(event);
+  }
 };
 
 struct rm_ctx {
@@ -198,19 +243,7 @@ struct rm_ctx {
   std::unordered_map<void*, size_t> buffers;  // rm_buffer_create: base address -> bytes
   Scratch scratch[SCRATCH_COUNT];  // scratch_reserve
   template <class T> T* scratch_as(int which) const { return static_cast<T*>(scratch[which].p); }
-  // rm_present_sharded (one process driving several GPUs): this context's rows of the payload, and on the context that
-  // shows the frame the gathered parts and the frame in image order; grown on demand, freed with the context
-  void* shard_rows = nullptr;  size_t shard_rows_cap = 0;    // this context's rows of the payload (packed float4 or RGBA8)
-  void* shard_rows8 = nullptr; size_t shard_rows8_cap = 0;   // depth of field: this context's rows after ITS blur (RGBA8)
-  void* shard_all = nullptr;   size_t shard_all_cap = 0;     // depth of field: every part's packed rows (the all-gather's receive side)
-  void* shard_recv = nullptr;  size_t shard_recv_cap = 0;    // root: every part's RGBA8 rows
-  void* shard_frame = nullptr; size_t shard_frame_cap = 0;   // depth of field: the packed frame in image order (every context); root: the canvas
-  void* shard_canvas = nullptr; size_t shard_canvas_cap = 0; // root: the RGBA8 canvas in image order
-  void* shard_host = nullptr;  size_t shard_host_cap = 0;    // root: pinned host copy of the canvas (rm_present_sharded_finish reads it)
-  hipStream_t shard_stream = nullptr;                        // copies, assembly and blur of a present travel here, next to the renders
-  hipEvent_t shard_snap = nullptr, shard_ev = nullptr, shard_done = nullptr;  // snapshot written; this context's part delivered; root: canvas on the host
-  bool shard_pending = false;                                // root: a start without its finish
-  int shard_w = 0, shard_h = 0;                              // root: the canvas of the pending present
+  ShardPresent shard;  // rm_present_sharded
   unsigned long long peer_enabled = 0;  // devices this context's GPU has been given peer access to
   // Culling grids of this context's scenes (scene_cull_grid): built once a scene has been asked for cull_min_pixels pixel-samples
   // (rm_ctx_set_cull_min_pixels), held within cull_budget bytes -- the least recently rendered scene gives its grid up first, and
@@ -248,10 +281,12 @@ struct rm_scene {
   unsigned long long last_use = 0; // rm_ctx::use_clock at the last render / probe
 };
 
-struct rm_fb {
-  rm_ctx* ctx = nullptr;
+struct FbGeometry {
   int width = 0, height = 0, row_begin = 0, row_count = 0;  // row_count = rows held by the planes
   int stripe_rows = 0, parts = 1, part = 0;                 // striped window when stripe_rows > 0
+};
+struct rm_fb : FbGeometry {
+  rm_ctx* ctx = nullptr;
   float4* plane[3] = {nullptr, nullptr, nullptr};  // planes 1 and 2 hold rm_half4 when gbuffer == RM_GBUFFER_F16
   bool owned = false;
   int gbuffer = RM_GBUFFER_F32;
@@ -346,19 +381,8 @@ void rm_ctx_destroy(rm_ctx* ctx) {
   if (ctx->lpt_stream) { (void)hipStreamSynchronize(ctx->lpt_stream); (void)hipStreamDestroy(ctx->lpt_stream); }
   for (auto& l : ctx->lpt) l.destroy();
   ctx->sp.destroy();
-  for (auto& s : ctx->scratch)
-    if (s.p) (void)hipFree(s.p);
-  if (ctx->shard_rows) (void)hipFree(ctx->shard_rows);
-  if (ctx->shard_recv) (void)hipFree(ctx->shard_recv);
-  if (ctx->shard_frame) (void)hipFree(ctx->shard_frame);
-  if (ctx->shard_rows8) (void)hipFree(ctx->shard_rows8);
-  if (ctx->shard_all) (void)hipFree(ctx->shard_all);
-  if (ctx->shard_canvas) (void)hipFree(ctx->shard_canvas);
-  if (ctx->shard_host) (void)hipHostFree(ctx->shard_host);
-  if (ctx->shard_stream) { (void)hipStreamSynchronize(ctx->shard_stream); (void)hipStreamDestroy(ctx->shard_stream); }
-  if (ctx->shard_snap) (void)hipEventDestroy(ctx->shard_snap);
-  if (ctx->shard_done) (void)hipEventDestroy(ctx->shard_done);
-  if (ctx->shard_ev) (void)hipEventDestroy(ctx->shard_ev);
+  for (auto& s : ctx->scratch) s.release();
+  ctx->shard.destroy();
   if (ctx->cull_stream) { (void)hipStreamSynchronize(ctx->cull_stream); (void)hipStreamDestroy(ctx->cull_stream); }
   for (auto& b : ctx->cull_pool) (void)hipFree(b.p);
   if (ctx->cull_event) (void)hipEventDestroy(ctx->cull_event);
@@ -843,6 +867,52 @@ static int planes_aligned(const void* color, const void* normal_dof, const void*
   return !((reinterpret_cast<uintptr_t>(color) & 15u) || (reinterpret_cast<uintptr_t>(normal_dof) & g) || (reinterpret_cast<uintptr_t>(albedo_depth) & g));
 }
 
+// Frees the planes the library allocated (the moments plane is always the library's) and the framebuffer itself.
+static void fb_release(rm_fb* fb) {
+  if (fb->owned)
+    for (auto* pl : fb->plane)
+      if (pl) (void)hipFree(pl);
+  if (fb->moments) (void)hipFree(fb->moments);
+  delete fb;
+}
+
+// Allocates the planes the library owns -- 0..2, and 3, the moments plane, when asked for -- and zeroes them on the context's
+// stream.  One way out of a failure: what was allocated is freed, and the framebuffer with it.
+static int fb_allocate(rm_fb* fb, bool moments, const char* who) {
+  rm_ctx* ctx = fb->ctx;
+  (void)hipSetDevice(ctx->device);
+  for (int i = 0; i < (moments ? 4 : 3); i++) {
+    const size_t bytes = plane_bytes(fb, i);
+    void* p = nullptr;
+    hipError_t e = hipMalloc(&p, bytes);
+    if (i == RM_PLANE_MOMENTS) fb->moments = static_cast<float2*>(p);
+    else fb->plane[i] = static_cast<float4*>(p);
+    if (e == hipSuccess) e = hipMemsetAsync(p, 0, bytes, ctx->stream);
+    if (e != hipSuccess) {
+      fb_release(fb);
+      return fail(ctx, RM_ERR_DEVICE, std::string(who) + ": " + hipGetErrorString(e));
+    }
+  }
+  return RM_OK;
+}
+
+// The framebuffer every constructor ends in, after its own checks: over the caller's three planes, or with planes of the
+// library's own (zeroed; with the moments plane when asked for).
+static int fb_make(rm_ctx* ctx, const char* who, const FbGeometry& geometry, int gbuffer, void* const* planes, bool moments, rm_fb** out) {
+  rm_fb* fb = new (std::nothrow) rm_fb();
+  if (!fb) return fail(ctx, RM_ERR_DEVICE, "out of host memory");
+  static_cast<FbGeometry&>(*fb) = geometry;
+  fb->ctx = ctx;
+  fb->gbuffer = gbuffer;
+  fb->owned = planes == nullptr;
+  if (planes)
+    for (int i = 0; i < 3; i++) fb->plane[i] = static_cast<float4*>(planes[i]);
+  else if (int rc = fb_allocate(fb, moments, who))
+    return rc;
+  *out = fb;
+  return RM_OK;
+}
+
 int rm_fb_create(rm_ctx* ctx, int width, int height, int row_begin, int row_count, rm_fb** out) {
   return rm_fb_create_fmt(ctx, width, height, row_begin, row_count, RM_GBUFFER_F32, out);
 }
@@ -854,37 +924,7 @@ int rm_fb_create_fmt(rm_ctx* ctx, int width, int height, int row_begin, int row_
   gbuffer &= ~RM_FB_MOMENTS;
   if (int rc = gbuffer_check(ctx, gbuffer, "rm_fb_create")) return rc;
   if (int rc = fb_check(ctx, width, height, row_begin, row_count)) return rc;
-  rm_fb* fb = new (std::nothrow) rm_fb();
-  if (!fb) return fail(ctx, RM_ERR_DEVICE, "out of host memory");
-  fb->ctx = ctx;
-  fb->width = width; fb->height = height; fb->row_begin = row_begin; fb->row_count = row_count;
-  fb->owned = true;
-  fb->gbuffer = gbuffer;
-  (void)hipSetDevice(ctx->device);
-  for (int i = 0; i < 3; i++) {
-    const size_t bytes = plane_bytes(fb, i);
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&fb->plane[i]), bytes);
-    if (e == hipSuccess) e = hipMemsetAsync(fb->plane[i], 0, bytes, ctx->stream);
-    if (e != hipSuccess) {
-      for (int j = 0; j <= i; j++)
-        if (fb->plane[j]) (void)hipFree(fb->plane[j]);
-      delete fb;
-      return fail(ctx, RM_ERR_DEVICE, std::string("rm_fb_create: ") + hipGetErrorString(e));
-    }
-  }
-  if (moments) {
-    const size_t bytes = plane_bytes(fb, RM_PLANE_MOMENTS);
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&fb->moments), bytes);
-    if (e == hipSuccess) e = hipMemsetAsync(fb->moments, 0, bytes, ctx->stream);
-    if (e != hipSuccess) {
-      for (auto* pl : fb->plane) (void)hipFree(pl);
-      if (fb->moments) (void)hipFree(fb->moments);
-      delete fb;
-      return fail(ctx, RM_ERR_DEVICE, std::string("rm_fb_create: ") + hipGetErrorString(e));
-    }
-  }
-  *out = fb;
-  return RM_OK;
+  return fb_make(ctx, "rm_fb_create", FbGeometry{width, height, row_begin, row_count}, gbuffer, nullptr, moments, out);
 }
 
 // rows r < y owned by a striped framebuffer
@@ -914,34 +954,8 @@ int rm_fb_create_striped_fmt(rm_ctx* ctx, int width, int height, int stripe_rows
     return fail(ctx, RM_ERR_INVALID, "rm_fb_create_striped: planes must be aligned to their pixel (16 bytes; 8 for half G-buffer planes)");
   const int rows = striped_rows_below(height, stripe_rows, parts, part);
   if (rows < 1) return fail(ctx, RM_ERR_INVALID, "rm_fb_create_striped: this part holds no rows");
-  rm_fb* fb = new (std::nothrow) rm_fb();
-  if (!fb) return fail(ctx, RM_ERR_DEVICE, "out of host memory");
-  fb->ctx = ctx;
-  fb->width = width; fb->height = height; fb->row_begin = 0; fb->row_count = rows;
-  fb->stripe_rows = stripe_rows; fb->parts = parts; fb->part = part;
-  fb->gbuffer = gbuffer;
-  if (color) {
-    fb->plane[0] = static_cast<float4*>(color);
-    fb->plane[1] = static_cast<float4*>(normal_dof);
-    fb->plane[2] = static_cast<float4*>(albedo_depth);
-    fb->owned = false;
-  } else {
-    fb->owned = true;
-    (void)hipSetDevice(ctx->device);
-    for (int i = 0; i < 3; i++) {
-      const size_t bytes = plane_bytes(fb, i);
-      hipError_t e = hipMalloc(reinterpret_cast<void**>(&fb->plane[i]), bytes);
-      if (e == hipSuccess) e = hipMemsetAsync(fb->plane[i], 0, bytes, ctx->stream);
-      if (e != hipSuccess) {
-        for (int j = 0; j <= i; j++)
-          if (fb->plane[j]) (void)hipFree(fb->plane[j]);
-        delete fb;
-        return fail(ctx, RM_ERR_DEVICE, std::string("rm_fb_create_striped: ") + hipGetErrorString(e));
-      }
-    }
-  }
-  *out = fb;
-  return RM_OK;
+  void* const planes[3] = {color, normal_dof, albedo_depth};
+  return fb_make(ctx, "rm_fb_create_striped", FbGeometry{width, height, 0, rows, stripe_rows, parts, part}, gbuffer, color ? planes : nullptr, false, out);
 }
 
 int rm_fb_rows(const rm_fb* fb) { return fb ? fb->row_count : 0; }
@@ -963,17 +977,8 @@ int rm_fb_wrap_fmt(rm_ctx* ctx, int width, int height, int row_begin, int row_co
   if ((normal_dof == nullptr) != (albedo_depth == nullptr)) return fail(ctx, RM_ERR_INVALID, "rm_fb_wrap: give both G-buffer planes or neither");
   if (!planes_aligned(color, normal_dof, albedo_depth, gbuffer))
     return fail(ctx, RM_ERR_INVALID, "rm_fb_wrap: planes must be aligned to their pixel (16 bytes; 8 for half G-buffer planes)");
-  rm_fb* fb = new (std::nothrow) rm_fb();
-  if (!fb) return fail(ctx, RM_ERR_DEVICE, "out of host memory");
-  fb->ctx = ctx;
-  fb->width = width; fb->height = height; fb->row_begin = row_begin; fb->row_count = row_count;
-  fb->plane[0] = static_cast<float4*>(color);
-  fb->plane[1] = static_cast<float4*>(normal_dof);
-  fb->plane[2] = static_cast<float4*>(albedo_depth);
-  fb->owned = false;
-  fb->gbuffer = gbuffer;
-  *out = fb;
-  return RM_OK;
+  void* const planes[3] = {color, normal_dof, albedo_depth};
+  return fb_make(ctx, "rm_fb_wrap", FbGeometry{width, height, row_begin, row_count}, gbuffer, planes, false, out);
 }
 
 int rm_fb_gbuffer(const rm_fb* fb) { return fb ? fb->gbuffer : RM_GBUFFER_F32; }
@@ -982,9 +987,9 @@ int rm_fb_has_moments(const rm_fb* fb) { return fb && fb->moments ? 1 : 0; }
 int rm_fb_clear(rm_fb* fb) {
   if (!fb) return RM_ERR_INVALID;
   rm_ctx* ctx = fb->ctx;
-  for (int i = 0; i < 3; i++)
-    if (fb->plane[i]) RM_HIP(ctx, hipMemsetAsync(fb->plane[i], 0, plane_bytes(fb, i), ctx->stream));
-  if (fb->moments) RM_HIP(ctx, hipMemsetAsync(fb->moments, 0, plane_bytes(fb, RM_PLANE_MOMENTS), ctx->stream));
+  RM_HIP(ctx, hipSetDevice(ctx->device));
+  for (int i = 0; i <= RM_PLANE_MOMENTS; i++)
+    if (void* p = plane_ptr(fb, i)) RM_HIP(ctx, hipMemsetAsync(p, 0, plane_bytes(fb, i), ctx->stream));
   return RM_OK;
 }
 
@@ -992,14 +997,19 @@ void rm_fb_destroy(rm_fb* fb) {
   if (!fb) return;
   (void)hipSetDevice(fb->ctx->device);
   (void)hipStreamSynchronize(fb->ctx->stream);
-  if (fb->owned)
-    for (int i = 0; i < 3; i++)
-      if (fb->plane[i]) (void)hipFree(fb->plane[i]);
-  if (fb->moments) (void)hipFree(fb->moments);  // always the library's
-  delete fb;
+  fb_release(fb);
 }
 
-// a half plane through fp32 on the device (rm_narrow / rm_widen, the render kernels' own helpers): a scratch plane of float4
+// The one copy between host memory and the context's device: `bytes` on the context's stream, and back once they have arrived.
+static int copy_and_wait(rm_ctx* ctx, void* dst, const void* src, size_t bytes, hipMemcpyKind kind) {
+  RM_HIP(ctx, hipSetDevice(ctx->device));
+  RM_HIP(ctx, hipMemcpyAsync(dst, src, bytes, kind, ctx->stream));
+  RM_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return RM_OK;
+}
+
+// a half plane through fp32 on the device (rm_narrow / rm_widen, the render kernels' own helpers): a scratch plane of float4,
+// made per call -- kept with the context it would hold 16 bytes per pixel for a conversion a live loop never asks for
 static int convert_half_plane(rm_fb* fb, int plane, void* host, bool upload) {
   rm_ctx* ctx = fb->ctx;
   const long long pixels = (long long)fb->width * (long long)fb->row_count;
@@ -1022,24 +1032,23 @@ static int convert_half_plane(rm_fb* fb, int plane, void* host, bool upload) {
   return RM_OK;
 }
 
-int rm_fb_download(rm_fb* fb, int plane, float* host) {
-  if (!fb || !host || plane < 0 || plane > 2) return fb ? fail(fb->ctx, RM_ERR_INVALID, "rm_fb_download: bad argument") : RM_ERR_INVALID;
-  rm_ctx* ctx = fb->ctx;
-  if (!fb->plane[plane]) return fail(ctx, RM_ERR_INVALID, "rm_fb_download: this framebuffer has no such plane");
-  if (plane_px_bytes(fb->gbuffer, plane) != sizeof(float4)) return convert_half_plane(fb, plane, host, false);
-  RM_HIP(ctx, hipMemcpyAsync(host, fb->plane[plane], plane_bytes(fb, plane), hipMemcpyDeviceToHost, ctx->stream));
-  RM_HIP(ctx, hipStreamSynchronize(ctx->stream));
+// the float entries: planes 0..2 as fp32 whatever the framebuffer stores
+static int float_plane_check(rm_fb* fb, int plane, const float* host, const char* what) {
+  if (!fb || !host || plane < 0 || plane > 2) return fb ? fail(fb->ctx, RM_ERR_INVALID, std::string(what) + ": bad argument") : RM_ERR_INVALID;
+  if (!fb->plane[plane]) return fail(fb->ctx, RM_ERR_INVALID, std::string(what) + ": this framebuffer has no such plane");
   return RM_OK;
 }
 
+int rm_fb_download(rm_fb* fb, int plane, float* host) {
+  if (int rc = float_plane_check(fb, plane, host, "rm_fb_download")) return rc;
+  if (plane_px_bytes(fb->gbuffer, plane) != sizeof(float4)) return convert_half_plane(fb, plane, host, false);
+  return copy_and_wait(fb->ctx, host, fb->plane[plane], plane_bytes(fb, plane), hipMemcpyDeviceToHost);
+}
+
 int rm_fb_upload(rm_fb* fb, int plane, const float* host) {
-  if (!fb || !host || plane < 0 || plane > 2) return fb ? fail(fb->ctx, RM_ERR_INVALID, "rm_fb_upload: bad argument") : RM_ERR_INVALID;
-  rm_ctx* ctx = fb->ctx;
-  if (!fb->plane[plane]) return fail(ctx, RM_ERR_INVALID, "rm_fb_upload: this framebuffer has no such plane");
+  if (int rc = float_plane_check(fb, plane, host, "rm_fb_upload")) return rc;
   if (plane_px_bytes(fb->gbuffer, plane) != sizeof(float4)) return convert_half_plane(fb, plane, const_cast<float*>(host), true);
-  RM_HIP(ctx, hipMemcpyAsync(fb->plane[plane], host, plane_bytes(fb, plane), hipMemcpyHostToDevice, ctx->stream));
-  RM_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return RM_OK;
+  return copy_and_wait(fb->ctx, fb->plane[plane], host, plane_bytes(fb, plane), hipMemcpyHostToDevice);
 }
 
 static int raw_check(rm_fb* fb, int plane, const void* host, size_t bytes, const char* what) {
@@ -1056,18 +1065,12 @@ static int raw_check(rm_fb* fb, int plane, const void* host, size_t bytes, const
 
 int rm_fb_download_raw(rm_fb* fb, int plane, void* host, size_t bytes) {
   if (int rc = raw_check(fb, plane, host, bytes, "rm_fb_download_raw")) return rc;
-  rm_ctx* ctx = fb->ctx;
-  RM_HIP(ctx, hipMemcpyAsync(host, plane_ptr(fb, plane), bytes, hipMemcpyDeviceToHost, ctx->stream));
-  RM_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return RM_OK;
+  return copy_and_wait(fb->ctx, host, plane_ptr(fb, plane), bytes, hipMemcpyDeviceToHost);
 }
 
 int rm_fb_upload_raw(rm_fb* fb, int plane, const void* host, size_t bytes) {
   if (int rc = raw_check(fb, plane, host, bytes, "rm_fb_upload_raw")) return rc;
-  rm_ctx* ctx = fb->ctx;
-  RM_HIP(ctx, hipMemcpyAsync(plane_ptr(fb, plane), host, bytes, hipMemcpyHostToDevice, ctx->stream));
-  RM_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return RM_OK;
+  return copy_and_wait(fb->ctx, plane_ptr(fb, plane), host, bytes, hipMemcpyHostToDevice);
 }
 
 void* rm_fb_device_ptr(rm_fb* fb, int plane) { return (fb && plane >= 0 && plane <= 3) ? plane_ptr(fb, plane) : nullptr; }
@@ -1108,16 +1111,12 @@ static int buffer_check(rm_ctx* ctx, const void* device_ptr, const void* host, s
 
 int rm_buffer_download(rm_ctx* ctx, const void* device_ptr, void* host, size_t bytes) {
   if (int rc = buffer_check(ctx, device_ptr, host, bytes, "rm_buffer_download")) return rc;
-  RM_HIP(ctx, hipMemcpyAsync(host, device_ptr, bytes, hipMemcpyDeviceToHost, ctx->stream));
-  RM_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return RM_OK;
+  return copy_and_wait(ctx, host, device_ptr, bytes, hipMemcpyDeviceToHost);
 }
 
 int rm_buffer_upload(rm_ctx* ctx, void* device_ptr, const void* host, size_t bytes) {
   if (int rc = buffer_check(ctx, device_ptr, host, bytes, "rm_buffer_upload")) return rc;
-  RM_HIP(ctx, hipMemcpyAsync(device_ptr, host, bytes, hipMemcpyHostToDevice, ctx->stream));
-  RM_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return RM_OK;
+  return copy_and_wait(ctx, device_ptr, host, bytes, hipMemcpyHostToDevice);
 }
 
 // The culling grid of a scene that has one coming (rm_scene_create), before a call that reads it (either build; not the GL stack's
@@ -1624,22 +1623,21 @@ int rm_pack_present_rows(rm_ctx* ctx, rm_fb* fb, void* out_float4_device, void* 
   return RM_OK;
 }
 
-// Room for `bytes` in one of the context's scratch buffers, for work about to be enqueued on `stream`.  The rule, for all of them:
-// with enough capacity there is nothing to do.  Otherwise wait for the context's stream AND for `stream` -- what still reads the
-// old buffer was enqueued on one of them --, free it, and set the capacity to 0 before allocating: a failed hipMalloc then leaves
-// an empty buffer, from which the next call starts over.
-static int scratch_reserve(rm_ctx* ctx, int which, size_t bytes, hipStream_t stream) {
-  Scratch& s = ctx->scratch[which];
+// Room for `bytes` in one of the context's buffers (its device has been selected), for work about to be enqueued on `stream`.  The
+// rule, for all of them: with enough capacity there is nothing to do.  Otherwise wait for the context's stream AND for `stream`
+// -- what still uses the old buffer was enqueued on one of them --, free it, and set the capacity to 0 before allocating: a
+// failed allocation then leaves an empty buffer, from which the next call starts over.
+static int scratch_reserve(rm_ctx* ctx, Scratch& s, size_t bytes, hipStream_t stream) {
   if (s.bytes >= bytes) return RM_OK;
   if (s.p) {
     RM_HIP(ctx, hipStreamSynchronize(ctx->stream));
     if (stream != ctx->stream) RM_HIP(ctx, hipStreamSynchronize(stream));
-    (void)hipFree(s.p);
   }
-  s = Scratch{};
+  s.release();
   void* p = nullptr;
-  RM_HIP(ctx, hipMalloc(&p, bytes));
-  s = Scratch{p, bytes};
+  RM_HIP(ctx, s.pinned_host ? hipHostMalloc(&p, bytes, hipHostMallocDefault) : hipMalloc(&p, bytes));
+  s.p = p;
+  s.bytes = bytes;
   return RM_OK;
 }
 
@@ -1648,7 +1646,7 @@ static int present_planes(rm_ctx* ctx, const void* color, const void* normal_dof
   if (width < 1 || height < 1 || samples < 1) return fail(ctx, RM_ERR_INVALID, "rm_present_planes: width, height and samples must be >= 1");
   RM_HIP(ctx, hipSetDevice(ctx->device));
   const size_t bytes = (size_t)width * (size_t)height * 4;
-  if (int rc = scratch_reserve(ctx, SCRATCH_PRESENT, bytes, ctx->stream)) return rc;
+  if (int rc = scratch_reserve(ctx, ctx->scratch[SCRATCH_PRESENT], bytes, ctx->stream)) return rc;
   void* rgba8 = ctx->scratch[SCRATCH_PRESENT].p;
   if (int rc = present_device(ctx, color, normal_dof, nd_half, width, height, samples, rgba8, nullptr)) return rc;
   RM_HIP(ctx, hipMemcpyAsync(out_rgba8, rgba8, bytes, hipMemcpyDeviceToHost, ctx->stream));
@@ -1767,12 +1765,12 @@ static int filters_enqueue(rm_ctx* ctx, rm_fb* fb, int samples, const RmFilters*
   const int L = f->denoise == RM_DENOISE_NONE ? 0 : d->iterations;
   float4* despeckled = (L == 0 && out) ? out : nullptr;
   if (f->despeckle && !despeckled) {
-    if (int rc = scratch_reserve(ctx, SCRATCH_DESPECKLE, bytes, stream)) return rc;
+    if (int rc = scratch_reserve(ctx, ctx->scratch[SCRATCH_DESPECKLE], bytes, stream)) return rc;
     despeckled = ctx->scratch_as<float4>(SCRATCH_DESPECKLE);
   }
   if (L > 0)  // a live loop denoises every present: the ping-pong buffers of x and the guide stay with the context
     for (int b : {SCRATCH_DENOISE_X0, SCRATCH_DENOISE_X1, SCRATCH_DENOISE_GUIDE})
-      if (int rc = scratch_reserve(ctx, b, bytes, stream)) return rc;
+      if (int rc = scratch_reserve(ctx, ctx->scratch[b], bytes, stream)) return rc;
   const float4* color = fb->plane[0];
   if (f->despeckle) {
     DespecklePass P{};
@@ -1888,24 +1886,6 @@ int rm_present_filtered(rm_ctx* ctx, rm_fb* fb, int samples, const RmFilters* fi
 
 // ---- present of a frame sharded over the GPUs of ONE process ----------------------------------------
 
-static int grow(rm_ctx* ctx, void** p, size_t* cap, size_t bytes, bool pinned_host = false) {
-  if (*cap >= bytes) return RM_OK;
-  RM_HIP(ctx, hipSetDevice(ctx->device));
-  if (*p) {
-    RM_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    if (ctx->shard_stream) RM_HIP(ctx, hipStreamSynchronize(ctx->shard_stream));
-    (void)(pinned_host ? hipHostFree(*p) : hipFree(*p));
-    *p = nullptr;
-    *cap = 0;
-  }
-  if ((pinned_host ? hipHostMalloc(p, bytes, hipHostMallocDefault) : hipMalloc(p, bytes)) != hipSuccess) {
-    (void)hipGetLastError();
-    return fail(ctx, RM_ERR_DEVICE, "rm_present_sharded: out of memory");
-  }
-  *cap = bytes;
-  return RM_OK;
-}
-
 int rm_present_striped_rows(rm_ctx* ctx, const void* color, const void* normal_dof, int width, int height, int samples, int stripe_rows, int parts, int part,
                             void* out_rgba8_device, void* hip_stream) {
   if (!ctx || !color || !out_rgba8_device) return fail(ctx, RM_ERR_INVALID, "rm_present_striped_rows: NULL argument");
@@ -1938,7 +1918,8 @@ int rm_present_sharded_start(rm_ctx* const* ctxs, rm_fb* const* fbs, int parts, 
   rm_ctx* root = (ctxs && parts >= 1) ? ctxs[0] : nullptr;
   if (!root || !fbs) return fail(root, RM_ERR_INVALID, "rm_present_sharded: NULL argument");
   if (samples < 1) return fail(root, RM_ERR_INVALID, "rm_present_sharded: samples must be >= 1");
-  if (root->shard_pending) return fail(root, RM_ERR_INVALID, "rm_present_sharded_start: the previous present has not been finished (rm_present_sharded_finish)");
+  if (root->shard.pending) return fail(root, RM_ERR_INVALID, "rm_present_sharded_start: the previous present has not been finished (rm_present_sharded_finish)");
+  using S = ShardPresent;
   const rm_fb* f0 = fbs[0];
   for (int p = 0; p < parts; p++) {
     const rm_fb* f = fbs[p];
@@ -1951,22 +1932,23 @@ int rm_present_sharded_start(rm_ctx* const* ctxs, rm_fb* const* fbs, int parts, 
   const int max_rows = striped_rows_below(H, stripe, parts, 0);  // part 0 holds the most rows
   const size_t part8 = (size_t)max_rows * (size_t)W * sizeof(uchar4), part32 = (size_t)max_rows * (size_t)W * sizeof(float4);
   const size_t canvas_bytes = (size_t)H * (size_t)W * sizeof(uchar4);
-  if (int rc = grow(root, &root->shard_recv, &root->shard_recv_cap, part8 * (size_t)parts)) return rc;
-  if (int rc = grow(root, &root->shard_canvas, &root->shard_canvas_cap, canvas_bytes)) return rc;
-  if (int rc = grow(root, &root->shard_host, &root->shard_host_cap, canvas_bytes, true)) return rc;
+  // every context's present stream first, then its buffers: what may still use a buffer that has to grow runs on that stream
   for (int p = 0; p < parts; p++) {
     rm_ctx* c = ctxs[p];
-    int rc = grow(c, &c->shard_rows, &c->shard_rows_cap, dof ? part32 : part8);
-    if (!rc && dof) rc = grow(c, &c->shard_rows8, &c->shard_rows8_cap, part8);
-    if (!rc && dof) rc = grow(c, &c->shard_all, &c->shard_all_cap, part32 * (size_t)parts);
-    if (!rc && dof) rc = grow(c, &c->shard_frame, &c->shard_frame_cap, (size_t)H * (size_t)W * sizeof(float4));
-    if (rc) return c == root ? rc : fail(root, rc, rm_last_error(c));
+    ShardPresent& s = c->shard;
     RM_HIP(root, hipSetDevice(c->device));
-    if (!c->shard_stream) RM_HIP(root, hipStreamCreateWithFlags(&c->shard_stream, hipStreamNonBlocking));
-    if (!c->shard_snap) RM_HIP(root, hipEventCreateWithFlags(&c->shard_snap, hipEventDisableTiming));
-    if (!c->shard_ev) RM_HIP(root, hipEventCreateWithFlags(&c->shard_ev, hipEventDisableTiming));
+    RM_HIP(root, s.ensure(c == root));
+    auto reserve = [&](int which, size_t bytes) { return scratch_reserve(c, s.buf[which], bytes, s.stream); };
+    int rc = RM_OK;
+    if (c == root) rc = reserve(S::RECV, part8 * (size_t)parts);
+    if (!rc && c == root) rc = reserve(S::CANVAS, canvas_bytes);
+    if (!rc && c == root) rc = reserve(S::HOST, canvas_bytes);
+    if (!rc) rc = reserve(S::ROWS, dof ? part32 : part8);
+    if (!rc && dof) rc = reserve(S::ROWS8, part8);
+    if (!rc && dof) rc = reserve(S::ALL, part32 * (size_t)parts);
+    if (!rc && dof) rc = reserve(S::FRAME, (size_t)H * (size_t)W * sizeof(float4));
+    if (rc) return c == root ? rc : fail(root, rc, rm_last_error(c));
   }
-  if (!root->shard_done) { RM_HIP(root, hipSetDevice(root->device)); RM_HIP(root, hipEventCreateWithFlags(&root->shard_done, hipEventDisableTiming)); }
   // 1. every context snapshots what it holds, on the stream its renders are ordered on: the next samples may start at once (the planes
   //    are accumulated in place).  (The previous present was finished -- checked above -- so its buffers are free.)
   for (int p = 0; p < parts; p++) {
@@ -1974,10 +1956,10 @@ int rm_present_sharded_start(rm_ctx* const* ctxs, rm_fb* const* fbs, int parts, 
     rm_fb* f = fbs[p];
     RM_HIP(root, hipSetDevice(c->device));
     const long long pixels = (long long)W * (long long)f->row_count;
-    if (dof) RM_HIP(root, rm::launch_pack_rows(f->plane[0], f->plane[1], f->gbuffer == RM_GBUFFER_F16, pixels, static_cast<float4*>(c->shard_rows), c->stream));
-    else RM_HIP(root, (c->gl_stack ? rm_gl_launch_present_rows : rm::launch_present_rows)(f->plane[0], pixels, 1.0f / (float)samples, static_cast<uchar4*>(c->shard_rows), c->stream));
-    RM_HIP(root, hipEventRecord(c->shard_snap, c->stream));
-    RM_HIP(root, hipStreamWaitEvent(c->shard_stream, c->shard_snap, 0));
+    if (dof) RM_HIP(root, rm::launch_pack_rows(f->plane[0], f->plane[1], f->gbuffer == RM_GBUFFER_F16, pixels, c->shard.as<float4>(S::ROWS), c->stream));
+    else RM_HIP(root, (c->gl_stack ? rm_gl_launch_present_rows : rm::launch_present_rows)(f->plane[0], pixels, 1.0f / (float)samples, c->shard.as<uchar4>(S::ROWS), c->stream));
+    RM_HIP(root, hipEventRecord(c->shard.snap, c->stream));
+    RM_HIP(root, hipStreamWaitEvent(c->shard.stream, c->shard.snap, 0));
   }
   // 2. everything else travels on the contexts' present streams, beside the renders
   if (dof) {
@@ -1987,60 +1969,60 @@ int rm_present_sharded_start(rm_ctx* const* ctxs, rm_fb* const* fbs, int parts, 
       rm_ctx* c = ctxs[p];
       RM_HIP(root, hipSetDevice(c->device));
       for (int q = 0; q < parts; q++)
-        if (int rc = shard_copy(root, c, ctxs[q], static_cast<char*>(ctxs[q]->shard_all) + part32 * (size_t)p, c->shard_rows, (size_t)fbs[p]->row_count * (size_t)W * sizeof(float4), c->shard_stream)) return rc;
-      RM_HIP(root, hipEventRecord(c->shard_ev, c->shard_stream));
+        if (int rc = shard_copy(root, c, ctxs[q], ctxs[q]->shard.as<char>(S::ALL) + part32 * (size_t)p, c->shard.buf[S::ROWS].p, (size_t)fbs[p]->row_count * (size_t)W * sizeof(float4), c->shard.stream)) return rc;
+      RM_HIP(root, hipEventRecord(c->shard.ev, c->shard.stream));
     }
     // ... then every context puts the frame in image order, blurs and tone-maps ITS stripes (1 / parts of the pass each) and sends
     // the bytes to the root
     for (int q = 0; q < parts; q++) {
       rm_ctx* c = ctxs[q];
       RM_HIP(root, hipSetDevice(c->device));
-      for (int p = 0; p < parts; p++) RM_HIP(root, hipStreamWaitEvent(c->shard_stream, ctxs[p]->shard_ev, 0));
-      RM_HIP(root, rm::launch_assemble(c->shard_all, parts, max_rows, (long long)W * (long long)sizeof(float4), H, stripe, c->shard_frame, c->shard_stream));
-      RM_HIP(root, (c->gl_stack ? rm_gl_launch_present_striped : rm::launch_present_striped)(static_cast<const float4*>(c->shard_frame), static_cast<const float4*>(c->shard_frame), W, H,
-                                                                                                1.0f / (float)samples, static_cast<uchar4*>(c->shard_rows8), stripe, parts, q,
-                                                                                                fbs[q]->row_count, c->shard_stream));
+      for (int p = 0; p < parts; p++) RM_HIP(root, hipStreamWaitEvent(c->shard.stream, ctxs[p]->shard.ev, 0));
+      RM_HIP(root, rm::launch_assemble(c->shard.buf[S::ALL].p, parts, max_rows, (long long)W * (long long)sizeof(float4), H, stripe, c->shard.buf[S::FRAME].p, c->shard.stream));
+      RM_HIP(root, (c->gl_stack ? rm_gl_launch_present_striped : rm::launch_present_striped)(c->shard.as<const float4>(S::FRAME), c->shard.as<const float4>(S::FRAME), W, H,
+                                                                                                1.0f / (float)samples, c->shard.as<uchar4>(S::ROWS8), stripe, parts, q,
+                                                                                                fbs[q]->row_count, c->shard.stream));
     }
     for (int q = 0; q < parts; q++) {
       rm_ctx* c = ctxs[q];
       RM_HIP(root, hipSetDevice(c->device));
-      if (int rc = shard_copy(root, c, root, static_cast<char*>(root->shard_recv) + part8 * (size_t)q, c->shard_rows8, (size_t)fbs[q]->row_count * (size_t)W * sizeof(uchar4), c->shard_stream)) return rc;
-      RM_HIP(root, hipEventRecord(c->shard_ev, c->shard_stream));  // (the root waited for the first record above; this one is the next in stream order)
+      if (int rc = shard_copy(root, c, root, root->shard.as<char>(S::RECV) + part8 * (size_t)q, c->shard.buf[S::ROWS8].p, (size_t)fbs[q]->row_count * (size_t)W * sizeof(uchar4), c->shard.stream)) return rc;
+      RM_HIP(root, hipEventRecord(c->shard.ev, c->shard.stream));  // (the root waited for the first record above; this one is the next in stream order)
     }
   } else {
     for (int p = 0; p < parts; p++) {
       rm_ctx* c = ctxs[p];
       RM_HIP(root, hipSetDevice(c->device));
-      if (int rc = shard_copy(root, c, root, static_cast<char*>(root->shard_recv) + part8 * (size_t)p, c->shard_rows, (size_t)fbs[p]->row_count * (size_t)W * sizeof(uchar4), c->shard_stream)) return rc;
-      RM_HIP(root, hipEventRecord(c->shard_ev, c->shard_stream));
+      if (int rc = shard_copy(root, c, root, root->shard.as<char>(S::RECV) + part8 * (size_t)p, c->shard.buf[S::ROWS].p, (size_t)fbs[p]->row_count * (size_t)W * sizeof(uchar4), c->shard.stream)) return rc;
+      RM_HIP(root, hipEventRecord(c->shard.ev, c->shard.stream));
     }
   }
   // 3. the root puts the bytes in image order and brings the canvas to the host (pinned: the copy is asynchronous)
   RM_HIP(root, hipSetDevice(root->device));
-  for (int p = 0; p < parts; p++) RM_HIP(root, hipStreamWaitEvent(root->shard_stream, ctxs[p]->shard_ev, 0));
-  RM_HIP(root, rm::launch_assemble(root->shard_recv, parts, max_rows, (long long)W * (long long)sizeof(uchar4), H, stripe, root->shard_canvas, root->shard_stream));
-  RM_HIP(root, hipMemcpyAsync(root->shard_host, root->shard_canvas, canvas_bytes, hipMemcpyDeviceToHost, root->shard_stream));
-  RM_HIP(root, hipEventRecord(root->shard_done, root->shard_stream));
-  root->shard_pending = true;
-  root->shard_w = W;
-  root->shard_h = H;
+  for (int p = 0; p < parts; p++) RM_HIP(root, hipStreamWaitEvent(root->shard.stream, ctxs[p]->shard.ev, 0));
+  RM_HIP(root, rm::launch_assemble(root->shard.buf[S::RECV].p, parts, max_rows, (long long)W * (long long)sizeof(uchar4), H, stripe, root->shard.buf[S::CANVAS].p, root->shard.stream));
+  RM_HIP(root, hipMemcpyAsync(root->shard.buf[S::HOST].p, root->shard.buf[S::CANVAS].p, canvas_bytes, hipMemcpyDeviceToHost, root->shard.stream));
+  RM_HIP(root, hipEventRecord(root->shard.done, root->shard.stream));
+  root->shard.pending = true;
+  root->shard.w = W;
+  root->shard.h = H;
   return RM_OK;
 }
 
 int rm_present_sharded_finish(rm_ctx* const* ctxs, int parts, uint8_t* out_rgba8, size_t out_bytes) {
   rm_ctx* root = (ctxs && parts >= 1) ? ctxs[0] : nullptr;
   if (!root || !out_rgba8) return fail(root, RM_ERR_INVALID, "rm_present_sharded_finish: NULL argument");
-  if (!root->shard_pending) return fail(root, RM_ERR_INVALID, "rm_present_sharded_finish: no present was started");
-  const size_t bytes = (size_t)root->shard_h * (size_t)root->shard_w * sizeof(uchar4);
+  if (!root->shard.pending) return fail(root, RM_ERR_INVALID, "rm_present_sharded_finish: no present was started");
+  const size_t bytes = (size_t)root->shard.h * (size_t)root->shard.w * sizeof(uchar4);
   if (out_bytes < bytes) {  // (the present stays pending: the caller can come back with the right buffer)
     char buf[160];
-    std::snprintf(buf, sizeof buf, "rm_present_sharded_finish: the pending present is %d x %d (%zu bytes), the buffer holds %zu", root->shard_w, root->shard_h, bytes, out_bytes);
+    std::snprintf(buf, sizeof buf, "rm_present_sharded_finish: the pending present is %d x %d (%zu bytes), the buffer holds %zu", root->shard.w, root->shard.h, bytes, out_bytes);
     return fail(root, RM_ERR_INVALID, buf);
   }
-  root->shard_pending = false;
+  root->shard.pending = false;
   RM_HIP(root, hipSetDevice(root->device));
-  RM_HIP(root, hipEventSynchronize(root->shard_done));  // the present's own work only: the renders enqueued since go on
-  std::memcpy(out_rgba8, root->shard_host, bytes);
+  RM_HIP(root, hipEventSynchronize(root->shard.done));  // the present's own work only: the renders enqueued since go on
+  std::memcpy(out_rgba8, root->shard.buf[ShardPresent::HOST].p, bytes);
   return RM_OK;
 }
 

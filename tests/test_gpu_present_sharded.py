@@ -130,3 +130,122 @@ def test_present_striped_rows_are_the_rows_of_present(stripe_rows):
                 assert np.array_equal(out.cpu().numpy(), want[rows]), (stripe_rows, parts, part)
     finally:
         ctx.close()
+
+
+class ShardedPair:
+    """`parts` contexts with the striped framebuffers of one frame size each, next to one context holding whole frames: the same
+    samples rendered into both, for canvases that must agree byte for byte.  The contexts live across sizes and modes."""
+
+    def __init__(self, parts):
+        self.parts = parts
+        self.sc = S.Mandelbulb()
+        self.one = native.Context(0)
+        self.ctxs = [native.Context(0) for _ in range(parts)]
+        self.h = self.one.create_scene(self.sc)
+        self.hs = [c.create_scene(self.sc) for c in self.ctxs]
+        self.frames = {}  # (W, H) -> (the whole framebuffer, the striped ones)
+
+    def render(self, W, H, dof, samples=2):
+        """Clears the framebuffers of this size and renders `samples` samples into them; returns rm_present's canvas."""
+        if (W, H) not in self.frames:
+            self.frames[W, H] = (self.one.create_framebuffer(W, H),
+                                 [c.create_striped_framebuffer(W, H, shard.STRIPE_ROWS, self.parts, p) for p, c in enumerate(self.ctxs)])
+        fb, fbs = self.frames[W, H]
+        schema = J.make_schema(self.sc, W, H, counts=(40,), render_mode="full", position=(0, 0, -2.5), lights=GC.LIGHT,
+                               dof_amount=0.03 if dof else 0.0, dof_distance=1.6)
+        for f in [fb] + fbs:
+            f.clear()
+        for nz in GC.halton_pairs(samples):
+            u = J.uniforms_from_schema(schema, nz)
+            self.one.render_sample(self.h, fb, u, None, abi.RM_RENDER_FAST)
+            for c, hh, f in zip(self.ctxs, self.hs, fbs):
+                c.render_sample(hh, f, u, None, abi.RM_RENDER_FAST)
+        want = fb.present(samples)
+        assert int(want[..., :3].max()) > 100
+        return want, fbs, samples
+
+    def close(self):
+        for c in self.ctxs + [self.one]:
+            c.close()
+
+
+def test_present_sharded_buffers_across_sizes_and_modes():
+    """Small without depth of field, large with it, small with it, large without it, on the same live contexts with samples
+    rendered in between: every buffer of the present grows, is reused at a smaller size, and changes its payload between RGBA8
+    rows and packed float4 rows -- and every canvas is rm_present's."""
+    pair = ShardedPair(2)
+    try:
+        for step, (W, H, dof) in enumerate([(40, 24, False), (136, 100, True), (40, 24, True), (136, 100, False)]):
+            want, fbs, samples = pair.render(W, H, dof)
+            got = native.present_sharded(pair.ctxs, fbs, samples, dof)
+            assert got.shape == (H, W, 4) and np.array_equal(got, want), f"present {step} ({W} x {H}, dof {dof}): {int((got != want).sum())} bytes differ"
+    finally:
+        pair.close()
+
+
+@pytest.mark.parametrize("dof", [False, True])
+def test_present_sharded_start_finish_then_a_larger_start(dof):
+    pair = ShardedPair(2)
+    try:
+        for W, H in ((40, 24), (136, 100)):
+            want, fbs, samples = pair.render(W, H, dof)
+            native.present_sharded_start(pair.ctxs, fbs, samples, dof)
+            got = native.present_sharded_finish(pair.ctxs, W, H)
+            assert np.array_equal(got, want), f"{W} x {H}: {int((got != want).sum())} bytes differ"
+    finally:
+        pair.close()
+
+
+def sharded_arrays(ctxs, fbs):
+    import ctypes as C
+
+    n = len(ctxs)
+    return (C.c_void_p * n)(*[c.h for c in ctxs]), (C.c_void_p * n)(*[f.h for f in fbs]), n
+
+
+def test_present_sharded_finish_with_a_buffer_one_byte_short():
+    """Refused with the size of the pending present and both byte counts; the present stays pending, and a finish with the right
+    buffer delivers it."""
+    import ctypes as C
+
+    W, H = 40, 24
+    pair = ShardedPair(2)
+    try:
+        want, fbs, samples = pair.render(W, H, False)
+        cs, fs, n = sharded_arrays(pair.ctxs, fbs)
+        lib, root = pair.ctxs[0].lib, pair.ctxs[0]
+        native.present_sharded_start(pair.ctxs, fbs, samples, False)
+        out = np.full((H, W, 4), 7, np.uint8)
+        assert lib.rm_present_sharded_finish(cs, n, out.ctypes.data_as(C.POINTER(C.c_uint8)), out.nbytes - 1) == abi.RM_ERR_INVALID
+        assert lib.rm_last_error(root.h).decode() == \
+            f"rm_present_sharded_finish: the pending present is {W} x {H} ({W * H * 4} bytes), the buffer holds {W * H * 4 - 1}"
+        assert (out == 7).all()  # nothing was written
+        with pytest.raises(native.RmError):  # still pending: another start is refused
+            native.present_sharded_start(pair.ctxs, fbs, samples, False)
+        assert root.lib.rm_last_error(root.h).decode() == "rm_present_sharded_start: the previous present has not been finished (rm_present_sharded_finish)"
+        assert lib.rm_present_sharded_finish(cs, n, out.ctypes.data_as(C.POINTER(C.c_uint8)), out.nbytes) == abi.RM_OK
+        assert np.array_equal(out, want)
+    finally:
+        pair.close()
+
+
+def test_present_sharded_with_a_short_buffer_starts_nothing():
+    import ctypes as C
+
+    W, H = 40, 24
+    pair = ShardedPair(2)
+    try:
+        want, fbs, samples = pair.render(W, H, False)
+        cs, fs, n = sharded_arrays(pair.ctxs, fbs)
+        lib, root = pair.ctxs[0].lib, pair.ctxs[0]
+        out = np.full((H, W, 4), 7, np.uint8)
+        out_p = out.ctypes.data_as(C.POINTER(C.c_uint8))
+        assert lib.rm_present_sharded(cs, fs, n, samples, 0, out_p, out.nbytes - 1) == abi.RM_ERR_INVALID
+        assert lib.rm_last_error(root.h).decode() == "rm_present_sharded: the buffer is smaller than width * height * 4 bytes"
+        assert (out == 7).all()
+        assert lib.rm_present_sharded_finish(cs, n, out_p, out.nbytes) == abi.RM_ERR_INVALID  # refused before anything started
+        assert lib.rm_last_error(root.h).decode() == "rm_present_sharded_finish: no present was started"
+        assert lib.rm_present_sharded(cs, fs, n, samples, 0, out_p, out.nbytes) == abi.RM_OK
+        assert np.array_equal(out, want)
+    finally:
+        pair.close()
