@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define RM_ABI_VERSION 9 /* 9: RM_GBUFFER_F32 / _F16, rm_fb_create_fmt, rm_fb_create_striped_fmt, rm_fb_wrap_fmt, rm_fb_gbuffer, rm_fb_download_raw, rm_fb_upload_raw, RmDenoise, rm_denoise_default, rm_denoise, rm_denoise_device, rm_present_denoised, RM_FB_MOMENTS, RM_PLANE_MOMENTS, rm_fb_has_moments, RmDenoiseVariance, rm_denoise_variance_default, rm_denoise_variance, rm_denoise_variance_device, rm_present_denoised_variance, RmDespeckle, RmFilters, RM_DENOISE_NONE / _ATROUS / _VARIANCE, rm_filters_default, rm_filter, rm_filter_device, rm_present_filtered (additions only); 8: RM_PRIM_TORUS / _CYLINDER / _PLANE, RM_OP_SMOOTH_SUBTRACT / _INTERSECT, rm_probe_math (additions only); 7: rm_present_sharded_finish / rm_present_sharded take the size of the host buffer (a changed signature), rm_ctx_set_cull_min_pixels, rm_ctx_set_cull_budget, rm_ctx_cull_stats; 6: rm_present_striped_rows, rm_present_sharded_start / _finish, rm_ctx_last_warning, RM_PROBE_CAST_SHADOW, RM_PRIM_KIND (additions only); 3: rm_ctx_set_sample_batch, rm_buffer_*; 4: rm_ctx_set_gl_stack; 5: RmSurface / RmSceneDesc.surfaces (the struct grew), rm_pack_present_rows, rm_present_sharded, rm_ctx_last_pipeline, RM_RENDER_NO_FAR_JUMP, RM_RENDER_NO_CULL (additions only) */
+#define RM_ABI_VERSION 9 /* 9: RM_GBUFFER_F32 / _F16, rm_fb_create_fmt, rm_fb_create_striped_fmt, rm_fb_wrap_fmt, rm_fb_gbuffer, rm_fb_download_raw, rm_fb_upload_raw, RmDenoise, rm_denoise_default, rm_denoise, rm_denoise_device, rm_present_denoised, RM_FB_MOMENTS, RM_PLANE_MOMENTS, rm_fb_has_moments, RmDenoiseVariance, rm_denoise_variance_default, rm_denoise_variance, rm_denoise_variance_device, rm_present_denoised_variance, RmDespeckle, RmFilters, RM_DENOISE_NONE / _ATROUS / _VARIANCE, rm_filters_default, rm_filter, rm_filter_device, rm_present_filtered, RM_STATS_BINS, RmFrameStats, rm_frame_stats, RmAutoExposure, rm_auto_exposure_default, rm_stats_percentile, rm_stats_exposure, RM_TONE_CLIP / _REINHARD / _ACES, RmDisplay, rm_display_default, rm_present_display, rm_present_display_device, rm_present_linear (additions only); 8: RM_PRIM_TORUS / _CYLINDER / _PLANE, RM_OP_SMOOTH_SUBTRACT / _INTERSECT, rm_probe_math (additions only); 7: rm_present_sharded_finish / rm_present_sharded take the size of the host buffer (a changed signature), rm_ctx_set_cull_min_pixels, rm_ctx_set_cull_budget, rm_ctx_cull_stats; 6: rm_present_striped_rows, rm_present_sharded_start / _finish, rm_ctx_last_warning, RM_PROBE_CAST_SHADOW, RM_PRIM_KIND (additions only); 3: rm_ctx_set_sample_batch, rm_buffer_*; 4: rm_ctx_set_gl_stack; 5: RmSurface / RmSceneDesc.surfaces (the struct grew), rm_pack_present_rows, rm_present_sharded, rm_ctx_last_pipeline, RM_RENDER_NO_FAR_JUMP, RM_RENDER_NO_CULL (additions only) */
 
 #define RM_MAX_BOUNCES 10 /* raymarchingStepCountsArray[10], raymarcher.frag:31 */
 #define RM_MAX_LIGHTS 10  /* lightPositions[10],             raymarcher.frag:37-39 */
@@ -717,6 +717,82 @@ RM_API void rm_filters_default(RmFilters* filters);   /* both stages off, every 
 RM_API int rm_filter(rm_ctx* ctx, rm_fb* fb, int samples, const RmFilters* filters, float* out_host);
 RM_API int rm_filter_device(rm_ctx* ctx, rm_fb* fb, int samples, const RmFilters* filters, void* out_float4_device, void* hip_stream);
 RM_API int rm_present_filtered(rm_ctx* ctx, rm_fb* fb, int samples, const RmFilters* filters, uint8_t* out_rgba8);
+
+/* ---- frame statistics and exposure (opt-in) ----
+ * rm_frame_stats reduces a frame to numbers on the device: the histogram of the luminance the firefly filter computes, in the same
+ * order.  With s = 1.0f / samples, fp32, every product and sum rounded on its own:
+ *   l = (0.2126f * (C.r * s) + 0.7152f * (C.g * s)) + 0.0722f * (C.b * s)
+ * and every pixel falls in exactly one class:
+ *   l NaN or +-inf                                            non_finite
+ *   l < 2^-20 (negatives, +-0 and subnormals included)        below
+ *   l >= 2^12                                                 above
+ *   otherwise                                                 hist[(bits(l) >> 19) - 1712]
+ * 16 bins per octave over 32 octaves: bin b covers [lo_b, hi_b), lo_b = the float with the bits (b + 1712) << 19, hi_b = lo_(b+1),
+ * hi_511 = 2^12.  Integer arithmetic on the float's bits: no logarithm on the device, and nothing depends on the order of arrival.
+ * min_l / max_l are the exact minimum and maximum over the finite l (-0 orders below +0); +inf / -inf when no pixel is finite.
+ * filters == NULL: the statistics of the colour plane as it is, of ANY framebuffer of the context -- a window, a striped part, a
+ * wrapped colour-only frame: pixels = rows held x width.  The counts are integers, so the RmFrameStats of a sharded frame's parts add
+ * up exactly to the whole frame's.  filters != NULL: the statistics of the chain's result (rm_filter's), and everything rm_filter
+ * refuses is refused.  RM_ERR_INVALID before any device work for a NULL handle or output, a framebuffer of another context and
+ * samples < 1.  Synchronous; the counters live in a buffer the context owns. */
+#define RM_STATS_BINS 512
+typedef struct RmFrameStats {      /* 4136 bytes */
+  uint64_t pixels, below, above, non_finite;   /* pixels = below + above + non_finite + sum(hist) */
+  float min_l, max_l;
+  uint64_t hist[RM_STATS_BINS];
+} RmFrameStats;
+RM_API int rm_frame_stats(rm_ctx* ctx, rm_fb* fb, int samples, const RmFilters* filters, RmFrameStats* out);
+
+/* Host arithmetic on an RmFrameStats, all in double: no GPU, no context (like rm_debug_cull_cell).  N = sum(hist): only binned pixels
+ * are ranked; C_b = the cumulative count through bin b (C_-1 = 0).
+ *   rm_stats_percentile: *l = hi_b of the bin that holds the r-th smallest binned pixel, r = max(1, ceil(q N)); 0 when N == 0.
+ *     RM_ERR_INVALID for a NULL argument and q outside [0, 1] or not finite.
+ *   rm_stats_exposure: the gain that brings the log-average luminance of the pixels between two percentiles to `key`:
+ *     a = low N, b = high N, w_b = max(0, min(C_b, b) - max(C_(b-1), a)), m = sum(w_b lambda_b) / (b - a) with
+ *     lambda_b = (log2(lo_b) + log2(hi_b)) / 2, *gain = clamp(key / exp2(m), min_gain, max_gain) rounded to fp32; 1 when N == 0.
+ *     params == NULL: the defaults.  RM_ERR_INVALID for a NULL stats or gain, unless 0 <= low < high <= 1, key > 0,
+ *     0 < min_gain <= max_gain, every field finite and reserved == 0 all hold. */
+typedef struct RmAutoExposure {
+  float key;        /* the display value the log-average goes to (default 0.18) */
+  float low, high;  /* the percentiles between which pixels count (default 0.10, 0.95) */
+  float min_gain, max_gain;  /* default 2^-10, 2^10 */
+  int reserved;     /* must be 0 */
+} RmAutoExposure;
+RM_API void rm_auto_exposure_default(RmAutoExposure* params);
+RM_API int rm_stats_percentile(const RmFrameStats* stats, double q, float* l);
+RM_API int rm_stats_exposure(const RmFrameStats* stats, const RmAutoExposure* params, float* gain);
+
+/* ---- the display transform (opt-in): a fourth stage, behind the present pass's blur ----
+ * Let v_c be what rm_present holds per channel in front of its pow (a / count * brightness: the blurred colour x 1 / samples), from
+ * the chain's result as rm_present_filtered feeds it, in the arithmetic rm_present uses on that context (the GL stack's under
+ * rm_ctx_set_gl_stack).  Every operation is fp32 and rounded on its own, with IEEE division, in this order:
+ *   1. e_c = v_c * gain
+ *   2. RM_TONE_CLIP: t_c = e_c
+ *   3. otherwise a channel with !(e_c > 0) (zero, negative, NaN) passes through: t_c = e_c
+ *   4. else E = min(e_c, 1048576.0f) and
+ *        RM_TONE_REINHARD: q = E / w2; a = 1.0f + q; n = E * a; d = 1.0f + E; t = n / d    (w2 = white * white, once, in fp32)
+ *        RM_TONE_ACES (Narkowicz's fit): a = 2.51f * E; a = a + 0.03f; n = E * a; b = 2.43f * E; b = b + 0.59f; b = E * b;
+ *                                        d = b + 0.14f; t = n / d
+ *   5. out_c = unorm8(pow(t_c, 1.0f / 2.2f)), alpha 255
+ * rm_present_linear stops after step 1: (e.r, e.g, e.b, 1.0f), height x width x 4 floats, row 0 = bottom (tone and white are still
+ * checked).  x * 1.0f is x: with the default RmDisplay rm_present_display gives rm_present_filtered's bytes, with the default
+ * filters as well rm_present's.  filters == NULL: both stages off; display == NULL: the default.  RM_ERR_INVALID before any device
+ * work, and before the handles are looked at, for a gain that is not finite or <= 0, an unknown tone, a white that is not finite or
+ * <= 0 (checked for RM_TONE_REINHARD only) and reserved != 0; after those everything rm_present_filtered refuses; the device
+ * output must be non-NULL and 4-byte aligned (height x width x 4 bytes, enqueued on hip_stream, NULL = the context's: no host
+ * wait).  The striped, rows and sharded presents keep the reference's transform. */
+enum { RM_TONE_CLIP = 0, RM_TONE_REINHARD = 1, RM_TONE_ACES = 2 };
+typedef struct RmDisplay {
+  float gain;    /* finite, > 0 (default 1) */
+  int tone;      /* RM_TONE_* (default RM_TONE_CLIP) */
+  float white;   /* RM_TONE_REINHARD: the value that maps to 1; finite, > 0 (default 4) */
+  int reserved;  /* must be 0 */
+} RmDisplay;
+RM_API void rm_display_default(RmDisplay* display);
+RM_API int rm_present_display(rm_ctx* ctx, rm_fb* fb, int samples, const RmFilters* filters, const RmDisplay* display, uint8_t* out_rgba8);
+RM_API int rm_present_display_device(rm_ctx* ctx, rm_fb* fb, int samples, const RmFilters* filters, const RmDisplay* display, void* out_rgba8_device,
+                                     void* hip_stream);
+RM_API int rm_present_linear(rm_ctx* ctx, rm_fb* fb, int samples, const RmFilters* filters, const RmDisplay* display, float* out_float4_host);
 
 /* The present of a frame that ONE process renders on several GPUs -- the shape of the reference's own host: one
  * thread, one render loop (index.tsx:120), here with a context per GPU, each holding one part of the frame's stripes

@@ -170,3 +170,53 @@ class RmFilters(C.Structure):
     ]
 
 assert C.sizeof(RmPrim) == 32 and C.sizeof(RmSurface) == 48 and C.sizeof(RmDespeckle) == 24 and C.sizeof(RmFilters) == 72
+
+
+RM_STATS_BINS = 512
+
+
+class RmFrameStats(C.Structure):
+    """rm_frame_stats' result (ABI 9): the luminance histogram of a frame, 16 bins per octave over [2^-20, 2^12), the three classes
+    outside it and the exact minimum and maximum over the finite luminances (include/hip_raymarch.h)."""
+    _fields_ = [
+        ("pixels", C.c_uint64),
+        ("below", C.c_uint64),
+        ("above", C.c_uint64),
+        ("non_finite", C.c_uint64),
+        ("min_l", C.c_float),
+        ("max_l", C.c_float),
+        ("hist", C.c_uint64 * RM_STATS_BINS),
+    ]
+
+
+class RmAutoExposure(C.Structure):
+    """Parameters of rm_stats_exposure (ABI 9): the gain that brings the log-average between two percentiles to `key`."""
+    _fields_ = [
+        ("key", C.c_float),
+        ("low", C.c_float),
+        ("high", C.c_float),
+        ("min_gain", C.c_float),
+        ("max_gain", C.c_float),
+        ("reserved", C.c_int32),
+    ]
+
+
+AUTO_EXPOSURE_DEFAULTS = dict(key=0.18, low=0.10, high=0.95, min_gain=2.0 ** -10, max_gain=2.0 ** 10)  # rm_auto_exposure_default
+
+RM_TONE_CLIP, RM_TONE_REINHARD, RM_TONE_ACES = 0, 1, 2
+TONE_NAMES = {"clip": RM_TONE_CLIP, "reinhard": RM_TONE_REINHARD, "aces": RM_TONE_ACES}
+
+
+class RmDisplay(C.Structure):
+    """The display transform behind the present pass's blur (ABI 9; rm_present_display, rm_present_display_device, rm_present_linear)."""
+    _fields_ = [
+        ("gain", C.c_float),
+        ("tone", C.c_int32),
+        ("white", C.c_float),
+        ("reserved", C.c_int32),
+    ]
+
+
+DISPLAY_DEFAULTS = dict(gain=1.0, tone=RM_TONE_CLIP, white=4.0)  # rm_display_default
+
+assert C.sizeof(RmFrameStats) == 4136 and C.sizeof(RmAutoExposure) == 24 and C.sizeof(RmDisplay) == 16

@@ -61,13 +61,14 @@ def to_data_url(rgba8: np.ndarray) -> str:
     return "data:image/png;base64," + base64.b64encode(encode_png(rgba8)).decode("ascii")
 
 
-def save_png(framebuffer, samples: int, path: str, denoise=None, despeckle=None) -> None:
+def save_png(framebuffer, samples: int, path: str, denoise=None, despeckle=None, display=None) -> None:
     """Present `framebuffer` (rm_present: DoF blur, 1/samples, gamma) and write it as a PNG.  `denoise` (True, a dict or
     abi.RmDenoise) presents the denoised colour instead (rm_present_denoised), and "variance" (or abi.RmDenoiseVariance, or a dict
     with "mode": "variance") the variance-guided filter's (rm_present_denoised_variance), as Framebuffer.present does; None keeps
     the bytes of rm_present.  `despeckle` (True, a dict or abi.RmDespeckle) runs the firefly filter ahead of either
-    (rm_present_filtered); None is today's calls unchanged."""
-    kw = {k: v for k, v in (("denoise", denoise), ("despeckle", despeckle)) if v is not None}
+    (rm_present_filtered); None is today's calls unchanged.  `display` (a dict, abi.RmDisplay or "auto") is Framebuffer.present's: the
+    display transform behind the blur (rm_present_display); None keeps the reference's."""
+    kw = {k: v for k, v in (("denoise", denoise), ("despeckle", despeckle), ("display", display)) if v is not None}
     rgba8 = framebuffer.present(samples, **kw)
     with open(path, "wb") as f:
         f.write(encode_png(rgba8))

@@ -37,6 +37,8 @@ hipError_t rm_gl_launch_camera_rng(const RmUniforms* u, int W, int H, int what, 
 hipError_t rm_gl_launch_present(const float4* color, const void* normal_dof, bool nd_half, int W, int H, float brightness, uchar4* out, hipStream_t stream);
 hipError_t rm_gl_launch_present_striped(const float4* color, const float4* normal_dof, int W, int H, float brightness, uchar4* out, int stripe_rows, int parts,
                                         int part, int local_rows, hipStream_t stream);
+hipError_t rm_gl_launch_present_display(const float4* color, const void* normal_dof, bool nd_half, int W, int H, float brightness, const DisplayPass* D, bool linear,
+                                        void* out, hipStream_t stream);
 hipError_t rm_gl_launch_present_rows(const float4* color, long long pixels, float brightness, uchar4* out, hipStream_t stream);
 hipError_t rm_gl_set_native_tan(int on, hipStream_t stream);
 }
@@ -169,6 +171,8 @@ enum {
   SCRATCH_DENOISE_X1,
   SCRATCH_DENOISE_GUIDE,  // and their guide
   SCRATCH_DESPECKLE,      // the despeckled colour plane the denoise stage reads
+  SCRATCH_STATS,          // rm_frame_stats: the counters (RM_STATS_BYTES), zeroed on the stream each call
+  SCRATCH_STATS_HOST,     // and their page-locked host copy
   SCRATCH_COUNT
 };
 struct Scratch {
@@ -242,6 +246,7 @@ struct rm_ctx {
   hipEvent_t switch_ev = nullptr;  // orders the old stream before the new one in rm_ctx_set_stream
   std::unordered_map<void*, size_t> buffers;  // rm_buffer_create: base address -> bytes
   Scratch scratch[SCRATCH_COUNT];  // scratch_reserve
+  rm_ctx() { scratch[SCRATCH_STATS_HOST].pinned_host = true; }
   template <class T> T* scratch_as(int which) const { return static_cast<T*>(scratch[which].p); }
   ShardPresent shard;  // rm_present_sharded
   unsigned long long peer_enabled = 0;  // devices this context's GPU has been given peer access to
@@ -1882,6 +1887,193 @@ int rm_filter(rm_ctx* ctx, rm_fb* fb, int samples, const RmFilters* filters, flo
 }
 int rm_present_filtered(rm_ctx* ctx, rm_fb* fb, int samples, const RmFilters* filters, uint8_t* out_rgba8) {
   return filter_to_rgba8(ctx, fb, samples, filters, "rm_present_filtered", out_rgba8);
+}
+
+// ---- the display transform: a fourth stage behind the blur, and a fourth ending (rm_frame_kernels.inc "the display transform") ----
+
+void rm_display_default(RmDisplay* p) {
+  if (!p) return;
+  std::memset(p, 0, sizeof *p);
+  p->gain = 1.0f;
+  p->tone = RM_TONE_CLIP;
+  p->white = 4.0f;
+}
+
+// The display block's own values, ahead of filters_check as that orders its own: they need neither a context nor a GPU.
+// in == NULL: the default.  *D = the block as the kernel takes it.
+static int display_check(rm_ctx* ctx, const RmDisplay* in, const char* who, DisplayPass* D) {
+  auto refuse = [&](const char* what) { return fail(ctx, RM_ERR_INVALID, std::string(who) + ": " + what); };
+  RmDisplay d;
+  rm_display_default(&d);
+  if (in) d = *in;
+  if (!(std::isfinite(d.gain) && d.gain > 0.0f)) return refuse("display gain must be finite and > 0");
+  if (d.tone != RM_TONE_CLIP && d.tone != RM_TONE_REINHARD && d.tone != RM_TONE_ACES) return refuse("display tone must be RM_TONE_CLIP, RM_TONE_REINHARD or RM_TONE_ACES");
+  if (d.tone == RM_TONE_REINHARD && !(std::isfinite(d.white) && d.white > 0.0f)) return refuse("display white must be finite and > 0");
+  if (d.reserved != 0) return refuse("display reserved must be 0");
+  *D = DisplayPass{d.gain, d.tone, d.white * d.white};
+  return RM_OK;
+}
+
+// The chain, then rm_present's pass ending in the display transform, on `stream`: W x H uchar4 into `out`, or W x H float4 with `linear`.
+static int display_enqueue(rm_ctx* ctx, rm_fb* fb, int samples, const RmFilters* f, const RmDenoise* d, const DisplayPass& D, bool linear, void* out,
+                           hipStream_t stream) {
+  const float4* r = nullptr;
+  if (int rc = filters_enqueue(ctx, fb, samples, f, d, nullptr, stream, &r)) return rc;
+  const bool half = fb->gbuffer == RM_GBUFFER_F16;
+  const float brightness = 1.0f / (float)samples;  // present_device's scale
+  RM_HIP(ctx, ctx->gl_stack ? rm_gl_launch_present_display(r, fb->plane[1], half, fb->width, fb->height, brightness, &D, linear, out, stream)
+                            : rm::launch_present_display(r, fb->plane[1], half, fb->width, fb->height, brightness, D, linear, out, stream));
+  return RM_OK;
+}
+
+// Into host memory through the context's present buffer, on the context's stream; returns once it is idle.
+static int display_to_host(rm_ctx* ctx, rm_fb* fb, int samples, const RmFilters* filters, const RmDisplay* display, const char* who, bool linear, void* out_host) {
+  DisplayPass D{};
+  if (int rc = display_check(ctx, display, who, &D)) return rc;
+  RmFilters off;
+  rm_filters_default(&off);
+  const RmFilters* f = filters ? filters : &off;
+  RmDenoise d{};
+  if (int rc = filters_check(ctx, fb, samples, f, who, &d)) return rc;
+  if (!out_host) return fail(ctx, RM_ERR_INVALID, std::string(who) + ": NULL argument");
+  RM_HIP(ctx, hipSetDevice(ctx->device));
+  const size_t bytes = (size_t)fb->width * (size_t)fb->height * (linear ? sizeof(float4) : sizeof(uchar4));
+  if (int rc = scratch_reserve(ctx, ctx->scratch[SCRATCH_PRESENT], bytes, ctx->stream)) return rc;
+  void* image = ctx->scratch[SCRATCH_PRESENT].p;
+  if (int rc = display_enqueue(ctx, fb, samples, f, &d, D, linear, image, ctx->stream)) return rc;
+  RM_HIP(ctx, hipMemcpyAsync(out_host, image, bytes, hipMemcpyDeviceToHost, ctx->stream));
+  RM_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return RM_OK;
+}
+
+int rm_present_display(rm_ctx* ctx, rm_fb* fb, int samples, const RmFilters* filters, const RmDisplay* display, uint8_t* out_rgba8) {
+  return display_to_host(ctx, fb, samples, filters, display, "rm_present_display", false, out_rgba8);
+}
+int rm_present_linear(rm_ctx* ctx, rm_fb* fb, int samples, const RmFilters* filters, const RmDisplay* display, float* out_float4_host) {
+  return display_to_host(ctx, fb, samples, filters, display, "rm_present_linear", true, out_float4_host);
+}
+int rm_present_display_device(rm_ctx* ctx, rm_fb* fb, int samples, const RmFilters* filters, const RmDisplay* display, void* out_rgba8_device, void* hip_stream) {
+  const char* who = "rm_present_display_device";
+  DisplayPass D{};
+  if (int rc = display_check(ctx, display, who, &D)) return rc;
+  RmFilters off;
+  rm_filters_default(&off);
+  const RmFilters* f = filters ? filters : &off;
+  RmDenoise d{};
+  if (int rc = filters_check(ctx, fb, samples, f, who, &d)) return rc;
+  if (!out_rgba8_device || (reinterpret_cast<uintptr_t>(out_rgba8_device) & 3u))
+    return fail(ctx, RM_ERR_INVALID, std::string(who) + ": the output must be a 4-byte aligned device buffer");
+  return display_enqueue(ctx, fb, samples, f, &d, D, false, out_rgba8_device, hip_stream ? static_cast<hipStream_t>(hip_stream) : ctx->stream);
+}
+
+// ---- frame statistics and exposure (rm_frame_kernels.inc "frame statistics") ----------------------------------------------
+
+int rm_frame_stats(rm_ctx* ctx, rm_fb* fb, int samples, const RmFilters* filters, RmFrameStats* out) {
+  const char* who = "rm_frame_stats";
+  RmDenoise d{};
+  if (filters) {
+    if (int rc = filters_check(ctx, fb, samples, filters, who, &d)) return rc;
+    if (!out) return fail(ctx, RM_ERR_INVALID, std::string(who) + ": NULL argument");
+  } else {
+    if (!ctx || !fb || !out) return fail(ctx, RM_ERR_INVALID, std::string(who) + ": NULL argument");
+    if (fb->ctx != ctx) return fail(ctx, RM_ERR_INVALID, std::string(who) + ": framebuffer belongs to another context");
+    if (samples < 1) return fail(ctx, RM_ERR_INVALID, std::string(who) + ": samples must be >= 1");
+  }
+  RM_HIP(ctx, hipSetDevice(ctx->device));
+  if (int rc = scratch_reserve(ctx, ctx->scratch[SCRATCH_STATS], RM_STATS_BYTES, ctx->stream)) return rc;
+  if (int rc = scratch_reserve(ctx, ctx->scratch[SCRATCH_STATS_HOST], RM_STATS_BYTES, ctx->stream)) return rc;
+  unsigned long long* const counters = ctx->scratch_as<unsigned long long>(SCRATCH_STATS);
+  const unsigned long long* const host = ctx->scratch_as<unsigned long long>(SCRATCH_STATS_HOST);
+  const float4* color = fb->plane[0];
+  if (filters)
+    if (int rc = filters_enqueue(ctx, fb, samples, filters, &d, nullptr, ctx->stream, &color)) return rc;
+  const long long pixels = (long long)fb->width * (long long)fb->row_count;
+  RM_HIP(ctx, hipMemsetAsync(counters, 0, RM_STATS_BYTES, ctx->stream));
+  RM_HIP(ctx, rm::launch_frame_stats(color, pixels, 1.0f / (float)samples, counters, ctx->stream));
+  RM_HIP(ctx, hipMemcpyAsync(ctx->scratch[SCRATCH_STATS_HOST].p, counters, RM_STATS_BYTES, hipMemcpyDeviceToHost, ctx->stream));
+  RM_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  std::memset(out, 0, sizeof *out);
+  out->pixels = (uint64_t)pixels;
+  out->below = host[RM_STATS_BELOW];
+  out->above = host[RM_STATS_ABOVE];
+  out->non_finite = host[RM_STATS_NON_FINITE];
+  for (int b = 0; b < RM_STATS_BINS; b++) out->hist[b] = host[b];
+  unsigned int keys[2];  // the complement of the minimum's key, the maximum's key (rm_frame_kernels.inc stats_key)
+  std::memcpy(keys, host + RM_STATS_COUNTERS, sizeof keys);
+  auto unkey = [](unsigned int k) {
+    const unsigned int b = (k & 0x80000000u) ? (k & 0x7fffffffu) : ~k;
+    float v;
+    std::memcpy(&v, &b, sizeof v);
+    return v;
+  };
+  const bool any_finite = out->non_finite < out->pixels;
+  out->min_l = any_finite ? unkey(~keys[0]) : std::numeric_limits<float>::infinity();
+  out->max_l = any_finite ? unkey(keys[1]) : -std::numeric_limits<float>::infinity();
+  return RM_OK;
+}
+
+void rm_auto_exposure_default(RmAutoExposure* p) {
+  if (!p) return;
+  std::memset(p, 0, sizeof *p);
+  p->key = 0.18f;
+  p->low = 0.10f;
+  p->high = 0.95f;
+  p->min_gain = 1.0f / 1024.0f;
+  p->max_gain = 1024.0f;
+}
+
+// lo_b of bin b = 0..RM_STATS_BINS (hi_b = lo_(b+1); lo_512 = 2^12): the float with the bits (b + 1712) << 19
+static float stats_bin_edge(int b) {
+  const uint32_t bits = (uint32_t)(b + 1712) << 19;
+  float v;
+  std::memcpy(&v, &bits, sizeof v);
+  return v;
+}
+
+int rm_stats_percentile(const RmFrameStats* stats, double q, float* l) {
+  if (!stats || !l || !(q >= 0.0 && q <= 1.0)) return RM_ERR_INVALID;
+  uint64_t N = 0;
+  for (uint64_t c : stats->hist) N += c;
+  *l = 0.0f;
+  if (N == 0) return RM_OK;
+  const double r = std::fmax(1.0, std::ceil(q * (double)N));
+  uint64_t C = 0;
+  for (int b = 0; b < RM_STATS_BINS; b++) {
+    C += stats->hist[b];
+    if ((double)C >= r) {
+      *l = stats_bin_edge(b + 1);
+      return RM_OK;
+    }
+  }
+  *l = stats_bin_edge(RM_STATS_BINS);  // not reached: C_511 = N >= r
+  return RM_OK;
+}
+
+int rm_stats_exposure(const RmFrameStats* stats, const RmAutoExposure* params, float* gain) {
+  if (!stats || !gain) return RM_ERR_INVALID;
+  RmAutoExposure p;
+  rm_auto_exposure_default(&p);
+  if (params) p = *params;
+  for (float v : {p.key, p.low, p.high, p.min_gain, p.max_gain})
+    if (!std::isfinite(v)) return RM_ERR_INVALID;
+  if (!(0.0f <= p.low && p.low < p.high && p.high <= 1.0f) || !(p.key > 0.0f) || !(0.0f < p.min_gain && p.min_gain <= p.max_gain) || p.reserved != 0)
+    return RM_ERR_INVALID;
+  uint64_t N = 0;
+  for (uint64_t c : stats->hist) N += c;
+  *gain = 1.0f;
+  if (N == 0) return RM_OK;
+  const double a = (double)p.low * (double)N, b = (double)p.high * (double)N;
+  double sum = 0.0;
+  uint64_t C = 0;
+  for (int i = 0; i < RM_STATS_BINS; i++) {
+    const double before = (double)C;
+    C += stats->hist[i];
+    const double w = std::fmax(0.0, std::fmin((double)C, b) - std::fmax(before, a));
+    if (w > 0.0) sum += w * ((std::log2((double)stats_bin_edge(i)) + std::log2((double)stats_bin_edge(i + 1))) / 2.0);
+  }
+  const double g = (double)p.key / std::exp2(sum / (b - a));
+  *gain = (float)std::fmin(std::fmax(g, (double)p.min_gain), (double)p.max_gain);
+  return RM_OK;
 }
 
 // ---- present of a frame sharded over the GPUs of ONE process ----------------------------------------

@@ -22,6 +22,10 @@ hipError_t rm_gl_launch_camera_rng(const RmUniforms* u, int W, int H, int what, 
 hipError_t rm_gl_launch_present(const float4* color, const void* normal_dof, bool nd_half, int W, int H, float brightness, uchar4* out, hipStream_t stream) {
   return rm_gl::launch_present(color, normal_dof, nd_half, W, H, brightness, out, stream);
 }
+hipError_t rm_gl_launch_present_display(const float4* color, const void* normal_dof, bool nd_half, int W, int H, float brightness, const DisplayPass* D, bool linear,
+                                        void* out, hipStream_t stream) {
+  return rm_gl::launch_present_display(color, normal_dof, nd_half, W, H, brightness, *D, linear, out, stream);
+}
 hipError_t rm_gl_launch_present_striped(const float4* color, const float4* normal_dof, int W, int H, float brightness, uchar4* out, int stripe_rows, int parts,
                                         int part, int local_rows, hipStream_t stream) {
   return rm_gl::launch_present_striped(color, normal_dof, W, H, brightness, out, stripe_rows, parts, part, local_rows, stream);

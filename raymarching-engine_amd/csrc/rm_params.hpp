@@ -319,6 +319,24 @@ struct DespecklePass {
   int repair;         // != 0: an invalid centre takes the mean of its ordinary taps
 };
 
+// The display transform behind the blur (rm_frame_kernels.inc "the display transform"): RmDisplay as the kernel takes it.
+struct DisplayPass {
+  float gain;
+  int tone;   // RM_TONE_*
+  float w2;   // white * white, rounded once on the host (RM_TONE_REINHARD)
+};
+
+// rm_frame_stats' device counters (rm_frame_kernels.inc "frame statistics"): 64-bit, the bins first, then the three other classes,
+// and behind them two 32-bit words: the complement of the minimum's key and the maximum's key.
+enum {
+  RM_STATS_BELOW = RM_STATS_BINS,
+  RM_STATS_ABOVE,
+  RM_STATS_NON_FINITE,
+  RM_STATS_COUNTERS,
+  RM_STATS_BYTES = RM_STATS_COUNTERS * 8 + 8,
+  RM_STATS_GRID = 1024,  // workgroups at most: each adds its non-zero counters to the global ones once
+};
+
 namespace rm {
 enum {
   WF_POS = 0,   // xyz ray position (march in/out), w = step budget
@@ -384,6 +402,11 @@ hipError_t launch_despeckle(const DespecklePass& P, int radius, int rank, hipStr
 hipError_t launch_present(const float4* color, const void* normal_dof, bool nd_half, int W, int H, float brightness, uchar4* out, hipStream_t stream);
 hipError_t launch_present_striped(const float4* color, const float4* normal_dof, int W, int H, float brightness, uchar4* out, int stripe_rows, int parts, int part,
                                   int local_rows, hipStream_t stream);
+// rm_present's pass ending in the display transform: W x H uchar4, or with `linear` W x H float4 (e.rgb, 1)
+hipError_t launch_present_display(const float4* color, const void* normal_dof, bool nd_half, int W, int H, float brightness, const DisplayPass& D, bool linear,
+                                  void* out, hipStream_t stream);
+// the luminance histogram of `pixels` float4 colours into RM_STATS_BYTES of zeroed counters (rm_frame_stats)
+hipError_t launch_frame_stats(const float4* color, long long pixels, float s, unsigned long long* counters, hipStream_t stream);
 hipError_t wf_launch_stage(const WfParams& W, int stage, hipStream_t stream);
 hipError_t launch_pixels_strict(const KParams& P, hipStream_t stream);
 hipError_t launch_pixels_fast(const KParams& P, hipStream_t stream);

@@ -346,13 +346,16 @@ class ShardedFramebuffer:
         canvas = g8.finish()
         return canvas if gr.rank == g8.dst else None
 
-    def present(self, samples: int, dof: Optional[bool] = None, denoise=None, despeckle=None):
+    def present(self, samples: int, dof: Optional[bool] = None, denoise=None, despeckle=None, display=None):
         if denoise is not None:  # checked before any collective: every rank raises, none waits for the others
             raise ValueError("ShardedFramebuffer.present: denoising a sharded frame is not supported (the filter reads rows other "
                              "ranks hold); present it unsharded with Framebuffer.present(samples, denoise=...)")
         if despeckle is not None:
             raise ValueError("ShardedFramebuffer.present: the firefly filter on a sharded frame is not supported (it reads rows other "
                              "ranks hold); present it unsharded with Framebuffer.present(samples, despeckle=...)")
+        if display is not None:
+            raise ValueError("ShardedFramebuffer.present: the display transform on a sharded frame is not supported yet (the sharded "
+                             "presents keep the reference's transform); sum Framebuffer.stats over the parts for its exposure")
         self.start_present(samples, dof)
         canvas = self.finish_present()
         if canvas is None:

@@ -471,14 +471,15 @@ def drain(generator) -> dict:
         return stop.value
 
 
-def collect_presents(frames: list, denoise=None, despeckle=None) -> Callable:
+def collect_presents(frames: list, denoise=None, despeckle=None, display=None) -> Callable:
     """A ``present`` callback for drain(): appends (samples, canvas) for every present of the job that has samples to
     show -- the reference presents once BEFORE the first sample too (RenderJobExecutor.tsx:163 at samplesRenderedSoFar
     = 0: the previous job's accumulation; its presenter divides by its own running count, index.tsx:25-39), which has
     no brightness here.  `canvas` = framebuffer.present(samples): RGBA8 [H, W, 4], row 0 = bottom; on a sharded job the
     call is the ranks' collective and the canvas is None on every rank but 0.  `denoise`: passed on to framebuffer.present
-    (None: not asked for, the bytes of rm_present), and so is `despeckle` (the firefly filter ahead of it)."""
-    kw = {k: v for k, v in (("denoise", denoise), ("despeckle", despeckle)) if v is not None}
+    (None: not asked for, the bytes of rm_present), and so are `despeckle` (the firefly filter ahead of it) and `display` (the
+    display transform behind the blur; "auto" takes the gain from the frame's statistics)."""
+    kw = {k: v for k, v in (("denoise", denoise), ("despeckle", despeckle), ("display", display)) if v is not None}
 
     def present(schema, context, fb, samples):
         if samples > 0:

@@ -53,7 +53,11 @@ export type RenderJobFramebufferInfo = {
   /** display.frag on the GPU: RGBA8, row 0 = bottom; `denoise` presents the denoised colour (rm_present_denoised), or with
    *  "variance" / { mode: "variance", ... } the variance-guided filter's (rm_present_denoised_variance; needs { moments: true });
    *  `despeckle` runs the firefly filter ahead of either (rm_present_filtered); without it the calls are the ones above */
-  present(samples: number, opts?: { denoise?: DenoiseOption; despeckle?: DespeckleOption }): Uint8Array;
+  present(samples: number, opts?: FrameOptions): Uint8Array;
+  /** the blurred, exposed frame as floats (rm_present_linear): (e.r, e.g, e.b, 1) per pixel, row 0 = bottom; the tone is checked, not applied */
+  linear(samples: number, opts?: FrameOptions): Float32Array;
+  /** the luminance statistics (rm_frame_stats) of the colour plane, or with `despeckle` / `denoise` of the chain's result */
+  stats(samples: number, opts?: { denoise?: DenoiseOption; despeckle?: DespeckleOption }): FrameStats;
   /** the colour plane after the chain despeckle -> denoise (rm_filter): colour-plane units, row 0 = bottom */
   filter(samples: number, opts?: { denoise?: DenoiseOption; despeckle?: DespeckleOption }): Float32Array;
   /** the colour plane after the variance-guided filter (rm_denoise_variance; needs { moments: true }) */
@@ -61,8 +65,26 @@ export type RenderJobFramebufferInfo = {
   /** the colour plane after the G-buffer-guided a-trous filter (rm_denoise): colour-plane units, row 0 = bottom */
   denoise(samples: number, params?: true | DenoiseParams): Float32Array;
   /** canvas.toDataURL("image/png") of the presented frame (index.tsx:470-476) */
-  toDataURL(samples: number, opts?: { denoise?: DenoiseOption; despeckle?: DespeckleOption }): string;
+  toDataURL(samples: number, opts?: FrameOptions): string;
 };
+/** `display`: the display transform behind the blur (rm_present_display); without it present's calls are the ones above */
+export type FrameOptions = { denoise?: DenoiseOption; despeckle?: DespeckleOption; display?: DisplayOption };
+/** RmDisplay (include/hip_raymarch.h): e = v * gain, then the tone operator ("clip": none; "reinhard" with `white`; "aces"), then pow and RGBA8 */
+export type DisplayParams = { gain?: number; tone?: "clip" | "reinhard" | "aces"; white?: number };
+/** "auto" / { auto, tone, white }: the gain is statsExposure of the same chain's stats (auto: true or its parameters) */
+export type DisplayOption = DisplayParams | "auto" | { auto: true | AutoExposureParams; tone?: "clip" | "reinhard" | "aces"; white?: number };
+export const DISPLAY_DEFAULTS: Required<DisplayParams>;
+/** checked as the library checks them; `tone` comes back as its RM_TONE_* number */
+export function displayParams(params?: true | DisplayParams | null): { gain: number; tone: number; white: number };
+/** RmFrameStats: 512 bins, 16 per octave over [2^-20, 2^12), the classes outside them, min / max over the finite luminances */
+export type FrameStats = { pixels: number; below: number; above: number; nonFinite: number; min: number; max: number; hist: Float64Array };
+/** RmAutoExposure: fields left out take AUTO_EXPOSURE_DEFAULTS' values */
+export type AutoExposureParams = { key?: number; low?: number; high?: number; min_gain?: number; max_gain?: number };
+export const AUTO_EXPOSURE_DEFAULTS: Required<AutoExposureParams>;
+/** rm_stats_exposure: the gain that brings the log-average luminance between the `low` and `high` percentiles to `key` */
+export function statsExposure(stats: FrameStats, opts?: AutoExposureParams | null): number;
+/** rm_stats_percentile: the upper edge of the bin that holds the ceil(q N)-th smallest binned pixel; 0 when nothing is binned */
+export function statsPercentile(stats: FrameStats, q: number): number;
 /** RmDespeckle (include/hip_raymarch.h): the firefly filter; fields left out take DESPECKLE_DEFAULTS' values */
 export type DespeckleParams = { radius?: 1 | 2; rank?: 0 | 1 | 2 | 3; gain?: number; floor?: number; repair?: number | boolean };
 export type DespeckleOption = true | DespeckleParams;
@@ -95,8 +117,8 @@ export class RenderJobContext {
  *  8-row stripes; `present(samples)` of its framebuffer set assembles the canvas on the first GPU (rm_present_sharded). */
 export type ShardedFramebufferInfo = {
   width: number; height: number; frameid: number; sharded: true; dof: boolean; rows(): number[];
-  /** throws when asked to denoise or to despeckle: the filters read rows other GPUs hold */
-  present(samples: number, dof?: boolean, opts?: { denoise?: undefined; despeckle?: undefined }): Uint8Array; toDataURL(samples: number): string;
+  /** throws when asked to denoise or to despeckle (the filters read rows other GPUs hold) or for a display transform (not carried yet) */
+  present(samples: number, dof?: boolean, opts?: { denoise?: undefined; despeckle?: undefined; display?: undefined }): Uint8Array; toDataURL(samples: number): string;
   /** the present in two halves (rm_present_sharded_start / _finish): the frame travels while the next samples render; one at a time */
   startPresent(samples: number, dof?: boolean): void; finishPresent(): Uint8Array; pendingPresent: boolean;
 };

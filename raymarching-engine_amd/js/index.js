@@ -293,9 +293,16 @@ class RenderJobContext {  // RenderJobContext + loadRenderJobContext (LoadRender
                    // "variance" or { mode: "variance", ... } (denoiseVarianceParams): the variance-guided filter's (rm_present_denoised_variance)
                    // opts.despeckle (true or the parameters of despeckleParams): the firefly filter ahead of either (rm_present_filtered);
                    // without it the calls are the ones above
+                   // opts.display (the parameters of displayParams -- gain, tone "clip" / "reinhard" / "aces", white --, or "auto" /
+                   // { auto: true or statsExposure's parameters, tone, white }: the gain from stats of the same chain): the display
+                   // transform behind the blur (rm_present_display); without it the calls are the ones above
                    present: (samples, opts = {}) => {
                      const out = new Uint8Array(w * h * 4);
                      const d = opts.denoise;
+                     if (opts.display !== undefined && opts.display !== null) {
+                       addon.presentDisplay(this.ctx, fb, samples, filters(opts), info.displayBlock(samples, opts), out);
+                       return out;
+                     }
                      if (opts.despeckle !== undefined && opts.despeckle !== null && opts.despeckle !== false) {
                        addon.presentFiltered(this.ctx, fb, samples, filters(opts), out);
                        return out;
@@ -304,6 +311,22 @@ class RenderJobContext {  // RenderJobContext + loadRenderJobContext (LoadRender
                      else if (isVarianceMode(d)) addon.presentDenoisedVariance(this.ctx, fb, samples, denoiseVarianceParams(d), out);
                      else addon.presentDenoised(this.ctx, fb, samples, denoiseParams(d && d.mode === "atrous" ? withoutMode(d) : d), out);
                      return out; },
+                   // the RmDisplay of opts.display: displayParams', or with "auto" the gain rm_stats_exposure gives for the same chain's statistics
+                   displayBlock: (samples, opts = {}) => {
+                     const disp = opts.display;
+                     if (!displayIsAuto(disp)) return displayParams(disp);
+                     const { auto = true, ...rest } = disp === "auto" ? {} : disp;
+                     if ("gain" in rest) throw new TypeError("display: give either a gain or auto");
+                     const p = displayParams(rest);
+                     p.gain = statsExposure(info.stats(samples, opts), auto === true ? undefined : auto);
+                     return p; },
+                   // the blurred, exposed frame as floats (rm_present_linear): (e.r, e.g, e.b, 1), row 0 = bottom; opts as present takes them
+                   linear: (samples, opts = {}) => { const out = new Float32Array(w * h * 4);
+                     addon.presentLinear(this.ctx, fb, samples, filters(opts), info.displayBlock(samples, opts), out); return out; },
+                   // the luminance statistics (rm_frame_stats) of the colour plane, or with opts.despeckle / opts.denoise of the chain's result
+                   stats: (samples, opts = {}) => { const raw = new ArrayBuffer(addon.sizes().RmFrameStats);
+                     const on = (v) => !(v === undefined || v === null || v === false);
+                     addon.frameStats(this.ctx, fb, samples, on(opts.despeckle) || on(opts.denoise) ? filters(opts) : null, raw); return unpackStats(raw); },
                    // the colour plane after the chain despeckle -> denoise (rm_filter): opts = { despeckle, denoise } as present takes them
                    filter: (samples, opts = {}) => { const out = new Float32Array(w * h * 4); addon.filter(this.ctx, fb, samples, filters(opts), out); return out; },
                    // the colour plane after the variance-guided filter (rm_denoise_variance; needs { moments: true }): as denoise
@@ -381,6 +404,8 @@ class ShardedRenderJobContext {
                        throw new Error("present: denoising a sharded frame is not supported (the filter reads rows other GPUs hold)");
                      if (opts.despeckle !== undefined)
                        throw new Error("present: the firefly filter on a sharded frame is not supported (it reads rows other GPUs hold)");
+                     if (opts.display !== undefined)
+                       throw new Error("present: the display transform on a sharded frame is not supported yet (the sharded presents keep the reference's transform)");
                      const out = new Uint8Array(w * h * 4); addon.presentSharded(this.ctxs, fbs, samples, !!dof, out); return out; },
                    // the same in two halves (rm_present_sharded_start / _finish): startPresent snapshots and sends and returns at once, so a
                    // `present` callback that calls it lets doRenderJob hand out the next samples while the frame travels; finishPresent
@@ -514,6 +539,63 @@ function filters(opts = {}) {
   return f;
 }
 
+// ---- the display transform and the frame statistics (include/hip_raymarch.h RmDisplay, RmFrameStats, RmAutoExposure) ----
+const TONES = { clip: 0, reinhard: 1, aces: 2 };
+const DISPLAY_DEFAULTS = { gain: 1.0, tone: "clip", white: 4.0 };
+const AUTO_EXPOSURE_DEFAULTS = { key: 0.18, low: 0.10, high: 0.95, min_gain: 2 ** -10, max_gain: 2 ** 10 };
+const STATS_BINS = 512;
+// undefined / null / true = the defaults (gain 1, the hard clip), or an object with some of gain, tone ("clip" | "reinhard" | "aces"), white;
+// checked as the library checks them (white for "reinhard" alone); returns { gain, tone: the RM_TONE_* number, white }
+function displayParams(params) {
+  const p = { ...DISPLAY_DEFAULTS };
+  if (params !== undefined && params !== null && params !== true) {
+    if (typeof params !== "object") throw new TypeError("display: expected \"auto\" or an object of parameters");
+    for (const [k, v] of Object.entries(params)) {
+      if (!(k in DISPLAY_DEFAULTS)) throw new TypeError("display: unknown parameter " + k);
+      p[k] = v;
+    }
+  }
+  if (!POSITIVE[0](p.gain)) throw new RangeError("display: gain " + POSITIVE[1]);
+  if (!(typeof p.tone === "string" && Object.prototype.hasOwnProperty.call(TONES, p.tone))) throw new RangeError("display: tone must be \"clip\", \"reinhard\" or \"aces\"");
+  if (p.tone === "reinhard" && !POSITIVE[0](p.white)) throw new RangeError("display: white " + POSITIVE[1]);
+  return { gain: p.gain, tone: TONES[p.tone], white: finite(p.white) ? p.white : DISPLAY_DEFAULTS.white };
+}
+function displayIsAuto(d) { return d === "auto" || (d !== null && typeof d === "object" && "auto" in d); }
+// the RmFrameStats the addon filled, as { pixels, below, above, nonFinite, min, max, hist: Float64Array(512) } (counts stay below 2^53)
+function unpackStats(raw) {
+  const v = new DataView(raw);
+  const u64 = (at) => Number(v.getBigUint64(at, true));
+  const hist = new Float64Array(STATS_BINS);
+  for (let b = 0; b < STATS_BINS; b++) hist[b] = u64(40 + 8 * b);
+  return { pixels: u64(0), below: u64(8), above: u64(16), nonFinite: u64(24), min: v.getFloat32(32, true), max: v.getFloat32(36, true), hist };
+}
+function packStats(stats) {
+  if (stats === null || typeof stats !== "object" || !stats.hist || stats.hist.length !== STATS_BINS) throw new TypeError("stats: expected what fb.stats returns");
+  const raw = new ArrayBuffer(addon.sizes().RmFrameStats), v = new DataView(raw);
+  [stats.pixels, stats.below, stats.above, stats.nonFinite].forEach((n, i) => v.setBigUint64(8 * i, BigInt(n), true));
+  v.setFloat32(32, stats.min, true); v.setFloat32(36, stats.max, true);
+  for (let b = 0; b < STATS_BINS; b++) v.setBigUint64(40 + 8 * b, BigInt(stats.hist[b]), true);
+  return raw;
+}
+// rm_stats_exposure: the gain that brings the log-average luminance between two percentiles to `key`; opts: some of AUTO_EXPOSURE_DEFAULTS' fields
+function statsExposure(stats, opts) {
+  const p = { ...AUTO_EXPOSURE_DEFAULTS };
+  if (opts !== undefined && opts !== null && opts !== true) {
+    if (typeof opts !== "object") throw new TypeError("auto exposure: expected an object of parameters");
+    for (const [k, v] of Object.entries(opts)) {
+      if (!(k in AUTO_EXPOSURE_DEFAULTS)) throw new TypeError("auto exposure: unknown parameter " + k);
+      if (!finite(v)) throw new RangeError("auto exposure: " + k + " must be a finite number");
+      p[k] = v;
+    }
+  }
+  return addon.statsExposure(packStats(stats), p);
+}
+// rm_stats_percentile: the upper edge of the bin that holds the ceil(q N)-th smallest binned pixel
+function statsPercentile(stats, q) {
+  if (!(typeof q === "number" && q >= 0 && q <= 1)) throw new RangeError("statsPercentile: q must be in [0, 1]");
+  return addon.statsPercentile(packStats(stats), q);
+}
+
 // ---- PNG capture (index.tsx:470-476 canvas.toDataURL): RGBA8, filter 0, rows flipped to top-down ----
 const zlib = require("zlib");
 const CRC_TABLE = (() => { const t = new Uint32Array(256); for (let n = 0; n < 256; n++) { let c = n; for (let k = 0; k < 8; k++) c = c & 1 ? 0xedb88320 ^ (c >>> 1) : c >>> 1; t[n] = c >>> 0; } return t; })();
@@ -539,4 +621,5 @@ function encodePng(rgba, width, height, bottomUp = true) {
 
 module.exports = { RM, addon, encodePng, Scene, CsgScene, Mandelbulb, singleSphere, DEFAULT_MATERIAL, halton, resetHalton, uniformsFromSchema, packUniforms,
                    tileRect, RenderJobContext, ShardedRenderJobContext, doRenderJob, U_OFFSET, DENOISE_DEFAULTS, denoiseParams,
-                   DENOISE_VARIANCE_DEFAULTS, denoiseVarianceParams, DESPECKLE_DEFAULTS, despeckleParams };
+                   DENOISE_VARIANCE_DEFAULTS, denoiseVarianceParams, DESPECKLE_DEFAULTS, despeckleParams, DISPLAY_DEFAULTS, AUTO_EXPOSURE_DEFAULTS,
+                   displayParams, statsExposure, statsPercentile };

@@ -356,6 +356,97 @@ static napi_value PresentDenoisedVariance(napi_env env, napi_callback_info info)
 static napi_value Filter(napi_env env, napi_callback_info info) { return filter_common(env, info, CHAIN, false); }
 static napi_value PresentFiltered(napi_env env, napi_callback_info info) { return filter_common(env, info, CHAIN, true); }
 
+// ---- the display transform and the frame statistics: presentDisplay, presentLinear, frameStats, statsExposure, statsPercentile ----
+static const Field DISPLAY_FIELDS[] = {{"gain", Field::FLOAT, offsetof(RmDisplay, gain)}, {"tone", Field::INT, offsetof(RmDisplay, tone)}, {"white", Field::FLOAT, offsetof(RmDisplay, white)}};
+static const Field AUTO_EXPOSURE_FIELDS[] = {{"key", Field::FLOAT, offsetof(RmAutoExposure, key)}, {"low", Field::FLOAT, offsetof(RmAutoExposure, low)}, {"high", Field::FLOAT, offsetof(RmAutoExposure, high)},
+                                             {"min_gain", Field::FLOAT, offsetof(RmAutoExposure, min_gain)}, {"max_gain", Field::FLOAT, offsetof(RmAutoExposure, max_gain)}};
+
+// presentDisplay(ctx, fb, samples, filters, display, out: Uint8Array(width * height * 4))   = rm_present_display
+// presentLinear(ctx, fb, samples, filters, display, out: Float32Array(width * height * 4))  = rm_present_linear
+// filters: what get_filters takes; display: { gain, tone (the RM_TONE_* number), white } or null (the default)
+static napi_value display_common(napi_env env, napi_callback_info info, bool linear) {
+  const std::string who = linear ? "presentLinear" : "presentDisplay";
+  size_t argc = 6;
+  napi_value argv[6];
+  NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+  rm_ctx* ctx = argc == 6 ? get_external<rm_ctx>(env, argv[0]) : nullptr;
+  rm_fb* fb = argc == 6 ? get_external<rm_fb>(env, argv[1]) : nullptr;
+  int32_t samples = 1;
+  RmFilters f;
+  rm_filters_default(&f);
+  RmDisplay disp;
+  rm_display_default(&disp);
+  void* d = nullptr;
+  size_t n = 0;
+  if (!ctx || !fb || napi_get_value_int32(env, argv[2], &samples) != napi_ok || !get_filters(env, argv[3], &f) || !get_block(env, argv[4], &disp, DISPLAY_FIELDS) ||
+      !get_buffer(env, argv[5], &d, &n)) {
+    napi_throw_type_error(env, nullptr, (who + "(ctx, fb, samples, filters, display, out: " + (linear ? "Float32Array" : "Uint8Array") + ")").c_str());
+    return nullptr;
+  }
+  if (n < (size_t)rm_fb_width(fb) * (size_t)rm_fb_height(fb) * 4 * (linear ? sizeof(float) : 1)) {
+    napi_throw_range_error(env, nullptr, (who + ": out is smaller than the frame").c_str());
+    return nullptr;
+  }
+  const int rc = linear ? rm_present_linear(ctx, fb, samples, &f, &disp, static_cast<float*>(d)) : rm_present_display(ctx, fb, samples, &f, &disp, static_cast<uint8_t*>(d));
+  if (rc != RM_OK) return throw_rm(env, ctx, linear ? "rm_present_linear" : "rm_present_display");
+  return nullptr;
+}
+static napi_value PresentDisplay(napi_env env, napi_callback_info info) { return display_common(env, info, false); }
+static napi_value PresentLinear(napi_env env, napi_callback_info info) { return display_common(env, info, true); }
+
+// frameStats(ctx, fb, samples, filters | null, out: ArrayBuffer(sizeof(RmFrameStats))) = rm_frame_stats: the struct as it is
+static napi_value FrameStats(napi_env env, napi_callback_info info) {
+  size_t argc = 5;
+  napi_value argv[5];
+  NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+  rm_ctx* ctx = argc == 5 ? get_external<rm_ctx>(env, argv[0]) : nullptr;
+  rm_fb* fb = argc == 5 ? get_external<rm_fb>(env, argv[1]) : nullptr;
+  int32_t samples = 1;
+  RmFilters f;
+  rm_filters_default(&f);
+  napi_valuetype t = napi_undefined;
+  void* d = nullptr;
+  size_t n = 0;
+  if (!ctx || !fb || napi_get_value_int32(env, argv[2], &samples) != napi_ok || napi_typeof(env, argv[3], &t) != napi_ok ||
+      !(t == napi_null || t == napi_undefined || get_filters(env, argv[3], &f)) || !get_buffer(env, argv[4], &d, &n) || n != sizeof(RmFrameStats)) {
+    napi_throw_type_error(env, nullptr, "frameStats(ctx, fb, samples, filters | null, out: ArrayBuffer of sizeof(RmFrameStats) bytes)");
+    return nullptr;
+  }
+  RmFrameStats st;
+  if (rm_frame_stats(ctx, fb, samples, (t == napi_null || t == napi_undefined) ? nullptr : &f, &st) != RM_OK) return throw_rm(env, ctx, "rm_frame_stats");
+  std::memcpy(d, &st, sizeof st);
+  return nullptr;
+}
+
+// statsExposure(stats: ArrayBuffer(sizeof(RmFrameStats)), params | null) = rm_stats_exposure; statsPercentile(stats, q) = rm_stats_percentile
+static napi_value stats_host(napi_env env, napi_callback_info info, bool exposure) {
+  size_t argc = 2;
+  napi_value argv[2];
+  NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+  void* d = nullptr;
+  size_t n = 0;
+  RmAutoExposure p;
+  rm_auto_exposure_default(&p);
+  double q = 0.0;
+  if (argc != 2 || !get_buffer(env, argv[0], &d, &n) || n != sizeof(RmFrameStats) ||
+      !(exposure ? get_block(env, argv[1], &p, AUTO_EXPOSURE_FIELDS) : napi_get_value_double(env, argv[1], &q) == napi_ok)) {
+    napi_throw_type_error(env, nullptr, exposure ? "statsExposure(stats: ArrayBuffer of sizeof(RmFrameStats) bytes, params | null)" : "statsPercentile(stats: ArrayBuffer of sizeof(RmFrameStats) bytes, q: number)");
+    return nullptr;
+  }
+  RmFrameStats st;
+  std::memcpy(&st, d, sizeof st);
+  float r = 0.0f;
+  if ((exposure ? rm_stats_exposure(&st, &p, &r) : rm_stats_percentile(&st, q, &r)) != RM_OK) {
+    napi_throw_range_error(env, nullptr, exposure ? "statsExposure: refused by rm_stats_exposure (0 <= low < high <= 1, key > 0, 0 < min_gain <= max_gain, all finite)" : "statsPercentile: q must be in [0, 1]");
+    return nullptr;
+  }
+  napi_value out;
+  NAPI_OK(napi_create_double(env, (double)r, &out));
+  return out;
+}
+static napi_value StatsExposure(napi_env env, napi_callback_info info) { return stats_host(env, info, true); }
+static napi_value StatsPercentile(napi_env env, napi_callback_info info) { return stats_host(env, info, false); }
+
 // fbCreateStriped(ctx, width, height, stripeRows, parts, part[, gbuffer]): the stripes k with k % parts == part of a width x height image,
 // planes owned by the library (rm_fb_create_striped) -- what one GPU of a sharded frame holds
 static napi_value FbCreateStriped(napi_env env, napi_callback_info info) {
@@ -550,7 +641,8 @@ static napi_value Sizes(napi_env env, napi_callback_info) {
   const struct { const char* k; uint32_t v; } items[] = {
       {"RmUniforms", (uint32_t)sizeof(RmUniforms)}, {"RmSceneDesc", (uint32_t)sizeof(RmSceneDesc)}, {"RmPrim", (uint32_t)sizeof(RmPrim)},
       {"RmMaterial", (uint32_t)sizeof(RmMaterial)}, {"RmRect", (uint32_t)sizeof(RmRect)}, {"RmSurface", (uint32_t)sizeof(RmSurface)}, {"RmDenoise", (uint32_t)sizeof(RmDenoise)},
-      {"RmDenoiseVariance", (uint32_t)sizeof(RmDenoiseVariance)}, {"RmDespeckle", (uint32_t)sizeof(RmDespeckle)}, {"RmFilters", (uint32_t)sizeof(RmFilters)}, {"abi", (uint32_t)rm_abi_version()}};
+      {"RmDenoiseVariance", (uint32_t)sizeof(RmDenoiseVariance)}, {"RmDespeckle", (uint32_t)sizeof(RmDespeckle)}, {"RmFilters", (uint32_t)sizeof(RmFilters)}, {"RmFrameStats", (uint32_t)sizeof(RmFrameStats)},
+      {"RmAutoExposure", (uint32_t)sizeof(RmAutoExposure)}, {"RmDisplay", (uint32_t)sizeof(RmDisplay)}, {"abi", (uint32_t)rm_abi_version()}};
   for (const auto& it : items) {
     NAPI_OK(napi_create_uint32(env, it.v, &v));
     NAPI_OK(napi_set_named_property(env, o, it.k, v));
@@ -561,7 +653,7 @@ static napi_value Sizes(napi_env env, napi_callback_info) {
 static napi_value Init(napi_env env, napi_value exports) {
   const struct { const char* name; napi_callback fn; } fns[] = {
       {"ctxCreate", CtxCreate}, {"ctxDestroy", CtxDestroy}, {"sync", Sync}, {"sceneCreate", SceneCreate}, {"sceneDestroy", SceneDestroy},
-      {"fbCreate", FbCreate}, {"fbClear", FbClear}, {"fbDestroy", FbDestroy}, {"fbDownload", FbDownload}, {"present", Present}, {"denoise", Denoise}, {"presentDenoised", PresentDenoised}, {"denoiseVariance", DenoiseVariance}, {"presentDenoisedVariance", PresentDenoisedVariance}, {"filter", Filter}, {"presentFiltered", PresentFiltered}, {"renderSample", RenderSample}, {"renderSamples", RenderSamples},
+      {"fbCreate", FbCreate}, {"fbClear", FbClear}, {"fbDestroy", FbDestroy}, {"fbDownload", FbDownload}, {"present", Present}, {"denoise", Denoise}, {"presentDenoised", PresentDenoised}, {"denoiseVariance", DenoiseVariance}, {"presentDenoisedVariance", PresentDenoisedVariance}, {"filter", Filter}, {"presentFiltered", PresentFiltered}, {"presentDisplay", PresentDisplay}, {"presentLinear", PresentLinear}, {"frameStats", FrameStats}, {"statsExposure", StatsExposure}, {"statsPercentile", StatsPercentile}, {"renderSample", RenderSample}, {"renderSamples", RenderSamples},
       {"fbCreateStriped", FbCreateStriped}, {"fbRows", FbRows}, {"setSamplesInFlight", SetSamplesInFlight}, {"presentSharded", PresentSharded}, {"presentShardedStart", PresentShardedStart}, {"presentShardedFinish", PresentShardedFinish},
       {"sizes", Sizes}};
   for (const auto& f : fns) {

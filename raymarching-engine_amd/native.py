@@ -38,6 +38,8 @@ EXPORTS = [
     "rm_denoise_default", "rm_denoise", "rm_denoise_device", "rm_present_denoised",
     "rm_fb_has_moments", "rm_denoise_variance_default", "rm_denoise_variance", "rm_denoise_variance_device", "rm_present_denoised_variance",
     "rm_filters_default", "rm_filter", "rm_filter_device", "rm_present_filtered",
+    "rm_frame_stats", "rm_auto_exposure_default", "rm_stats_percentile", "rm_stats_exposure",
+    "rm_display_default", "rm_present_display", "rm_present_display_device", "rm_present_linear",
 ]
 
 # G-buffer formats of a framebuffer (include/hip_raymarch.h RM_GBUFFER_*): "f32" (the default: the software GL stack's planes, which the
@@ -70,6 +72,14 @@ _BLOCKS = {
                           checks=dict(radius=(lambda v: v in (1, 2), "must be 1 or 2"), rank=(lambda v: 0 <= v <= 3, "must be in 0..3"),
                                       gain=(lambda v: math.isfinite(v) and v >= 1.0, "must be finite and >= 1"),
                                       floor=(lambda v: math.isfinite(v) and v >= 0.0, "must be finite and >= 0"), reserved=_ZERO)),
+    # white is checked for the operator that reads it alone (display_params), as the library does
+    abi.RmDisplay: dict(label="display", forms="True", defaults=abi.DISPLAY_DEFAULTS, integers=("tone",), numbers=("gain", "white"),
+                        checks=dict(gain=_POSITIVE, tone=(lambda v: v in abi.TONE_NAMES.values(), 'must be "clip", "reinhard" or "aces"'),
+                                    reserved=_ZERO)),
+    abi.RmAutoExposure: dict(label="auto exposure", forms="True", defaults=abi.AUTO_EXPOSURE_DEFAULTS,
+                             numbers=("key", "low", "high", "min_gain", "max_gain"),
+                             checks=dict(key=_POSITIVE, low=(lambda v: 0.0 <= v < 1.0, "must be in [0, 1)"), high=(lambda v: 0.0 < v <= 1.0, "must be in (0, 1]"),
+                                         min_gain=_POSITIVE, max_gain=_POSITIVE, reserved=_ZERO)),
 }
 
 
@@ -156,6 +166,83 @@ def filters(despeckle=None, denoise=None) -> abi.RmFilters:
         else:
             f.denoise, f.atrous = abi.RM_DENOISE_ATROUS, p
     return f
+
+
+def display_params(display=None) -> abi.RmDisplay:
+    """An abi.RmDisplay from None / True (the defaults, rm_display_default: gain 1, the hard clip), a dict of some of its fields over
+    the defaults -- `tone` as "clip" / "reinhard" / "aces" or its RM_TONE_* value -- or an abi.RmDisplay.  Checked here as the
+    library checks it (gain finite and > 0, a known tone, white finite and > 0 for "reinhard", reserved 0): ValueError otherwise."""
+    if isinstance(display, dict) and isinstance(display.get("tone"), str):
+        if display["tone"] not in abi.TONE_NAMES:
+            raise ValueError(f"display: unknown tone {display['tone']!r}; known: {sorted(abi.TONE_NAMES)}")
+        display = {**display, "tone": abi.TONE_NAMES[display["tone"]]}
+    p = _params(abi.RmDisplay, display)
+    if p.tone == abi.RM_TONE_REINHARD and not _POSITIVE[0](p.white):
+        raise ValueError(f"display: white {_POSITIVE[1]}")
+    return p
+
+
+def auto_exposure_params(params=None) -> abi.RmAutoExposure:
+    """An abi.RmAutoExposure from None / True (rm_auto_exposure_default's values), a dict of some of its fields over them, or an
+    abi.RmAutoExposure; checked as rm_stats_exposure checks it: ValueError otherwise."""
+    p = _params(abi.RmAutoExposure, params)
+    if not p.low < p.high:
+        raise ValueError("auto exposure: low must be below high")
+    if not p.min_gain <= p.max_gain:
+        raise ValueError("auto exposure: min_gain must not exceed max_gain")
+    return p
+
+
+def display_is_auto(display) -> bool:
+    """True for the forms of `display` whose gain comes from the frame's statistics: "auto", or a dict with an "auto" entry."""
+    return (isinstance(display, str) and display == "auto") or (isinstance(display, dict) and "auto" in display)
+
+
+class FrameStats:
+    """An abi.RmFrameStats (rm_frame_stats): `hist` is a numpy view of its 512 bins, the other fields are attributes; the statistics
+    of the parts of a frame add up (`+`: counts summed, min / max taken).  percentile and exposure are the library's host
+    arithmetic (rm_stats_percentile, rm_stats_exposure)."""
+
+    def __init__(self, raw: Optional[abi.RmFrameStats] = None):
+        self.raw = raw if raw is not None else abi.RmFrameStats(min_l=math.inf, max_l=-math.inf)
+
+    pixels = property(lambda self: int(self.raw.pixels))
+    below = property(lambda self: int(self.raw.below))
+    above = property(lambda self: int(self.raw.above))
+    non_finite = property(lambda self: int(self.raw.non_finite))
+    min = property(lambda self: float(self.raw.min_l))
+    max = property(lambda self: float(self.raw.max_l))
+
+    @property
+    def hist(self) -> np.ndarray:
+        return np.ctypeslib.as_array(self.raw.hist)
+
+    def __add__(self, other: "FrameStats") -> "FrameStats":
+        if not isinstance(other, FrameStats):
+            return NotImplemented
+        r = abi.RmFrameStats()
+        for name in ("pixels", "below", "above", "non_finite"):
+            setattr(r, name, getattr(self.raw, name) + getattr(other.raw, name))
+        r.min_l, r.max_l = min(self.raw.min_l, other.raw.min_l), max(self.raw.max_l, other.raw.max_l)
+        out = FrameStats(r)
+        out.hist[:] = self.hist + other.hist
+        return out
+
+    def percentile(self, q: float) -> float:
+        """hi_b of the bin that holds the ceil(q N)-th smallest binned pixel (0 when nothing is binned)."""
+        l = C.c_float()
+        if load_library().rm_stats_percentile(C.byref(self.raw), float(q), C.byref(l)) != abi.RM_OK:
+            raise ValueError(f"percentile: q must be in [0, 1], not {q!r}")
+        return float(l.value)
+
+    def exposure(self, **fields) -> float:
+        """The gain that brings the log-average luminance between the `low` and `high` percentiles to `key` (rm_stats_exposure;
+        fields left out take rm_auto_exposure_default's values)."""
+        p = auto_exposure_params(fields or None)
+        g = C.c_float()
+        if load_library().rm_stats_exposure(C.byref(self.raw), C.byref(p), C.byref(g)) != abi.RM_OK:
+            raise ValueError("exposure: refused by rm_stats_exposure")
+        return float(g.value)
 
 
 def cull_cell(scene, centre, radius: float, margin: float = 0.0):
@@ -300,6 +387,14 @@ def load_library(path=None):
         "rm_filter": (ip, [vp, vp, ip, C.POINTER(abi.RmFilters), fp]),
         "rm_filter_device": (ip, [vp, vp, ip, C.POINTER(abi.RmFilters), vp, vp]),
         "rm_present_filtered": (ip, [vp, vp, ip, C.POINTER(abi.RmFilters), C.POINTER(C.c_uint8)]),
+        "rm_frame_stats": (ip, [vp, vp, ip, C.POINTER(abi.RmFilters), C.POINTER(abi.RmFrameStats)]),
+        "rm_auto_exposure_default": (None, [C.POINTER(abi.RmAutoExposure)]),
+        "rm_stats_percentile": (ip, [C.POINTER(abi.RmFrameStats), C.c_double, fp]),
+        "rm_stats_exposure": (ip, [C.POINTER(abi.RmFrameStats), C.POINTER(abi.RmAutoExposure), fp]),
+        "rm_display_default": (None, [C.POINTER(abi.RmDisplay)]),
+        "rm_present_display": (ip, [vp, vp, ip, C.POINTER(abi.RmFilters), C.POINTER(abi.RmDisplay), C.POINTER(C.c_uint8)]),
+        "rm_present_display_device": (ip, [vp, vp, ip, C.POINTER(abi.RmFilters), C.POINTER(abi.RmDisplay), vp, vp]),
+        "rm_present_linear": (ip, [vp, vp, ip, C.POINTER(abi.RmFilters), C.POINTER(abi.RmDisplay), fp]),
     }
     for name, (res, args) in sig.items():
         if name.startswith("rm_debug_") and not hasattr(lib, name) and os.environ.get("RM_LIB"):
@@ -488,6 +583,15 @@ class Context:
         f = filters(despeckle, denoise)
         self._check(self.lib.rm_filter_device(self.h, fb.h, int(samples), C.byref(f), C.c_void_p(out_ptr), C.c_void_p(stream) if stream else None))
 
+    def present_display_device(self, fb: "Framebuffer", samples: int, out_ptr: int, denoise=None, despeckle=None, display=None,
+                               stream: Optional[int] = None):
+        """rm_present_display_device: Framebuffer.present(..., display=...) into rows x W x 4 bytes of device memory at out_ptr,
+        enqueued on `stream` (None = the context's); no host wait."""
+        d = fb.display_block(samples, denoise, despeckle, display)
+        f = filters(despeckle, denoise)
+        self._check(self.lib.rm_present_display_device(self.h, fb.h, int(samples), C.byref(f), C.byref(d), C.c_void_p(out_ptr),
+                                                       C.c_void_p(stream) if stream else None))
+
     def present_rows(self, fb: "Framebuffer", samples: int, out_ptr: int, stream: Optional[int] = None):
         """Tone-map the rows `fb` holds (no depth of field) into DEVICE memory (rows*width*4 bytes), asynchronous."""
         self._check(self.lib.rm_present_rows(self.h, fb.h, int(samples), C.c_void_p(out_ptr), C.c_void_p(stream) if stream else None))
@@ -674,14 +778,53 @@ class Framebuffer:
     def device_ptr(self, plane: int = abi.RM_PLANE_COLOR) -> int:
         return int(self.ctx.lib.rm_fb_device_ptr(self.h, plane) or 0)
 
-    def present(self, samples: int, denoise=None, despeckle=None) -> np.ndarray:
+    def stats(self, samples: int, despeckle=None, denoise=None) -> FrameStats:
+        """The luminance statistics of the rows this framebuffer holds (rm_frame_stats): of the colour plane as it is, or with
+        `despeckle` / `denoise` (what filter takes) of the chain's result -- what will be shown once the fireflies are gone."""
+        out = abi.RmFrameStats()
+        f = filters(despeckle, denoise) if (despeckle is not None or denoise is not None) else None
+        self.ctx._check(self.ctx.lib.rm_frame_stats(self.ctx.h, self.h, int(samples), C.byref(f) if f is not None else None, C.byref(out)))
+        return FrameStats(out)
+
+    def display_block(self, samples: int, denoise=None, despeckle=None, display=None) -> abi.RmDisplay:
+        """The abi.RmDisplay of a present's `display`: what display_params takes, or "auto" / a dict with an "auto" entry (True or
+        the fields of rm_stats_exposure's block) next to `tone` and `white`: the gain then comes from `stats` of the same chain."""
+        if not display_is_auto(display):
+            return display_params(display)
+        fields = {} if isinstance(display, str) else dict(display)
+        auto = fields.pop("auto", True)
+        if "gain" in fields:
+            raise ValueError("display: give either a gain or \"auto\"")
+        d = display_params(fields)
+        p = auto_exposure_params(None if auto is True else auto)
+        d.gain = self.stats(samples, despeckle=despeckle, denoise=denoise).exposure(**{k: getattr(p, k) for k in abi.AUTO_EXPOSURE_DEFAULTS})
+        return d
+
+    def linear(self, samples: int, denoise=None, despeckle=None, display=None) -> np.ndarray:
+        """The blurred, exposed frame as floats (rm_present_linear): what present holds in front of its tone operator and pow,
+        (e.r, e.g, e.b, 1) as float32 [H, W, 4], row 0 = bottom.  `display` as present takes it (its tone is checked, not applied)."""
+        d = self.display_block(samples, denoise, despeckle, display)
+        f = filters(despeckle, denoise)
+        out = np.empty((self.row_count, self.width, 4), np.float32)
+        self.ctx._check(self.ctx.lib.rm_present_linear(self.ctx.h, self.h, int(samples), C.byref(f), C.byref(d), _fp(out)))
+        return out
+
+    def present(self, samples: int, denoise=None, despeckle=None, display=None) -> np.ndarray:
         """Tone-mapped RGBA8 image of the whole frame (display.frag:16-64), row 0 = bottom.  `denoise`: None (the default: the
         accumulated colour as it is), or True / a dict / abi.RmDenoise to present the denoised colour (rm_present_denoised); or
         "variance" / abi.RmDenoiseVariance / a dict with "mode": "variance" for the variance-guided filter
         (rm_present_denoised_variance; the framebuffer needs moments=True).  `despeckle`: None (the default: no firefly filter, and
         exactly the calls above), or True / a dict / abi.RmDespeckle to run the firefly filter ahead of the denoiser and the present
-        (rm_present_filtered)."""
+        (rm_present_filtered).  `display`: None (the default: the reference's transform, and exactly the calls above), or a dict /
+        abi.RmDisplay -- gain, tone ("clip", "reinhard", "aces"), white -- for the display transform behind the blur
+        (rm_present_display); "auto" or {"auto": True or rm_stats_exposure's fields, "tone": ...} takes the gain from the
+        statistics of the same chain (stats, FrameStats.exposure)."""
         out = np.empty((self.row_count, self.width, 4), np.uint8)
+        if display is not None:
+            d = self.display_block(samples, denoise, despeckle, display)
+            f = filters(despeckle, denoise)
+            self.ctx._check(self.ctx.lib.rm_present_display(self.ctx.h, self.h, int(samples), C.byref(f), C.byref(d), out.ctypes.data_as(C.POINTER(C.c_uint8))))
+            return out
         if despeckle is not None:
             f = filters(despeckle, denoise)
             self.ctx._check(self.ctx.lib.rm_present_filtered(self.ctx.h, self.h, int(samples), C.byref(f), out.ctypes.data_as(C.POINTER(C.c_uint8))))
