@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define RM_ABI_VERSION 9 /* 9: RM_GBUFFER_F32 / _F16, rm_fb_create_fmt, rm_fb_create_striped_fmt, rm_fb_wrap_fmt, rm_fb_gbuffer, rm_fb_download_raw, rm_fb_upload_raw, RmDenoise, rm_denoise_default, rm_denoise, rm_denoise_device, rm_present_denoised, RM_FB_MOMENTS, RM_PLANE_MOMENTS, rm_fb_has_moments, RmDenoiseVariance, rm_denoise_variance_default, rm_denoise_variance, rm_denoise_variance_device, rm_present_denoised_variance, RmDespeckle, RmFilters, RM_DENOISE_NONE / _ATROUS / _VARIANCE, rm_filters_default, rm_filter, rm_filter_device, rm_present_filtered, RM_STATS_BINS, RmFrameStats, rm_frame_stats, RmAutoExposure, rm_auto_exposure_default, rm_stats_percentile, rm_stats_exposure, RM_TONE_CLIP / _REINHARD / _ACES, RmDisplay, rm_display_default, rm_present_display, rm_present_display_device, rm_present_linear (additions only); 8: RM_PRIM_TORUS / _CYLINDER / _PLANE, RM_OP_SMOOTH_SUBTRACT / _INTERSECT, rm_probe_math (additions only); 7: rm_present_sharded_finish / rm_present_sharded take the size of the host buffer (a changed signature), rm_ctx_set_cull_min_pixels, rm_ctx_set_cull_budget, rm_ctx_cull_stats; 6: rm_present_striped_rows, rm_present_sharded_start / _finish, rm_ctx_last_warning, RM_PROBE_CAST_SHADOW, RM_PRIM_KIND (additions only); 3: rm_ctx_set_sample_batch, rm_buffer_*; 4: rm_ctx_set_gl_stack; 5: RmSurface / RmSceneDesc.surfaces (the struct grew), rm_pack_present_rows, rm_present_sharded, rm_ctx_last_pipeline, RM_RENDER_NO_FAR_JUMP, RM_RENDER_NO_CULL (additions only) */
+#define RM_ABI_VERSION 9 /* 9: RM_GBUFFER_F32 / _F16, rm_fb_create_fmt, rm_fb_create_striped_fmt, rm_fb_wrap_fmt, rm_fb_gbuffer, rm_fb_download_raw, rm_fb_upload_raw, RmDenoise, rm_denoise_default, rm_denoise, rm_denoise_device, rm_present_denoised, RM_FB_MOMENTS, RM_PLANE_MOMENTS, rm_fb_has_moments, RmDenoiseVariance, rm_denoise_variance_default, rm_denoise_variance, rm_denoise_variance_device, rm_present_denoised_variance, RmDespeckle, RmFilters, RM_DENOISE_NONE / _ATROUS / _VARIANCE, rm_filters_default, rm_filter, rm_filter_device, rm_present_filtered, RM_STATS_BINS, RmFrameStats, rm_frame_stats, RmAutoExposure, rm_auto_exposure_default, rm_stats_percentile, rm_stats_exposure, RM_TONE_CLIP / _REINHARD / _ACES, RmDisplay, rm_display_default, rm_present_display, rm_present_display_device, rm_present_linear, RmGrid, rm_grid_axis, rm_sdf_grid, rm_sdf_grid_device, RmMeshParams, rm_mesh_params_default, rm_mesh, rm_mesh_extract, rm_mesh_from_values, rm_mesh_counts, rm_mesh_timings, RM_MESH_POSITIONS / _NORMALS / _COLOURS / _TRIANGLES / _CELLS, rm_mesh_download, rm_mesh_device_ptr, rm_mesh_destroy (additions only); 8: RM_PRIM_TORUS / _CYLINDER / _PLANE, RM_OP_SMOOTH_SUBTRACT / _INTERSECT, rm_probe_math (additions only); 7: rm_present_sharded_finish / rm_present_sharded take the size of the host buffer (a changed signature), rm_ctx_set_cull_min_pixels, rm_ctx_set_cull_budget, rm_ctx_cull_stats; 6: rm_present_striped_rows, rm_present_sharded_start / _finish, rm_ctx_last_warning, RM_PROBE_CAST_SHADOW, RM_PRIM_KIND (additions only); 3: rm_ctx_set_sample_batch, rm_buffer_*; 4: rm_ctx_set_gl_stack; 5: RmSurface / RmSceneDesc.surfaces (the struct grew), rm_pack_present_rows, rm_present_sharded, rm_ctx_last_pipeline, RM_RENDER_NO_FAR_JUMP, RM_RENDER_NO_CULL (additions only) */
 
 #define RM_MAX_BOUNCES 10 /* raymarchingStepCountsArray[10], raymarcher.frag:31 */
 #define RM_MAX_LIGHTS 10  /* lightPositions[10],             raymarcher.frag:37-39 */
@@ -817,6 +817,76 @@ RM_API int rm_present_linear(rm_ctx* ctx, rm_fb* fb, int samples, const RmFilter
 RM_API int rm_present_sharded_start(rm_ctx* const* ctxs, rm_fb* const* fbs, int parts, int samples, int dof);
 RM_API int rm_present_sharded_finish(rm_ctx* const* ctxs, int parts, uint8_t* out_rgba8, size_t out_bytes);
 RM_API int rm_present_sharded(rm_ctx* const* ctxs, rm_fb* const* fbs, int parts, int samples, int dof, uint8_t* out_rgba8, size_t out_bytes);
+
+/* ---- mesh extraction (opt-in): the surface of a scene as triangles ----
+ * The scenes are signed distance fields; these entries sample one on a regular grid and mesh the level set `iso` with surface nets,
+ * on the device.  No render kernel, entry point or result above changes.
+ *
+ * The grid.  n = CELLS per axis, so an axis has n + 1 corners; corner i of axis a lies at  lo[a] + (float)i * h[a]  with
+ * h[a] = (hi[a] - lo[a]) / (float)n[a], everything fp32: the difference, the IEEE division, the product and the sum each rounded on
+ * their own, no contraction.  The kernels compute the same bits; rm_grid_axis is the host statement of them (out = n[axis] + 1 floats;
+ * host arithmetic, no GPU and no context, like rm_stats_percentile).  A grid is valid iff every lo, hi and h is finite and h > 0,
+ * 1 <= n[a] <= 1024, (n0 + 1)(n1 + 1)(n2 + 1) <= 2^28 and reserved == 0.  Values are stored x fastest:
+ * v[(k * (ny + 1) + j) * (nx + 1) + i]. */
+typedef struct RmGrid { float lo[3], hi[3]; int32_t n[3]; int32_t reserved; } RmGrid; /* 40 bytes */
+RM_API int rm_grid_axis(const RmGrid* grid, int axis, float* out);
+
+/* The scene's distance at every corner: out[corner] is bit for bit what rm_probe(RM_PROBE_SDF) returns at that corner's position with
+ * the same flags on the same context -- the same kind selection (kind rows; the long tables' evaluation from 16 rows), the same scene
+ * block and culling grid, RM_RENDER_FAST the fast build, otherwise the GL stack's arithmetic on a context with rm_ctx_set_gl_stack,
+ * else the strict build.  flags: 0, RM_RENDER_FAST, RM_RENDER_NO_CULL, alone or together; anything else is RM_ERR_INVALID.
+ * rm_sdf_grid: out_host = corners floats of HOST memory, synchronous.  rm_sdf_grid_device: out_device = corners floats of DEVICE
+ * memory (4-byte aligned), enqueued on hip_stream (NULL = the context's stream), no allocation and no host wait.  On a stream of the
+ * caller's the context's own stream is made to wait, on the device, behind the launch: whatever the context does later with the scene
+ * or its culling grid (a rebuild, rm_scene_destroy) is ordered behind this reader as it is behind the context's own work. */
+RM_API int rm_sdf_grid(rm_ctx* ctx, rm_scene* scene, const RmGrid* grid, int flags, float* out_host);
+RM_API int rm_sdf_grid_device(rm_ctx* ctx, rm_scene* scene, const RmGrid* grid, int flags, void* out_device, void* hip_stream);
+
+/* The mesher: surface nets (no case table).  With e = v - iso (one fp32 subtraction) a corner is INSIDE iff e < 0 -- NaN, +0 and -0
+ * are outside -- and a cell is ACTIVE iff its 8 corners are not all alike.
+ *   The vertex of an active cell (i, j, k): walk its 12 edges, axis a = x, then y, then z with (a, b, c) cyclic -- (x, y, z), (y, z, x),
+ *   (z, x, y) -- and within an axis the four edges along a at offsets (ob, oc) = (0,0), (1,0), (0,1), (1,1) from the cell's low corner.
+ *   For an edge from corner c0 to c1 = c0 + 1 along a whose ends differ in `inside`:  t = e0 / (e0 - e1);  if !(t >= 0 && t <= 1) t = 0.5f;
+ *   the crossing point has c0's coordinates except along a:  p0 + t * (p1 - p0)  (three roundings).  The points are summed per
+ *   component, sequentially, in that edge order, and the vertex is  sum / (float)m  (IEEE division), m = the number of such edges.
+ *   Vertices come in ascending linear cell index (k * ny + j) * nx + i.
+ *   Faces: cells in the same order, within a cell a = x, y, z: the edge from the cell's low corner along a emits a quad iff its ends
+ *   differ in `inside` and the cell's index along b and along c is >= 1 (edges on the grid's boundary emit nothing).  The quad's
+ *   vertices q0..q3 belong to the cells at (b, c) offsets (-1,-1), (0,-1), (0,0), (-1,0); a low corner that is inside emits the
+ *   triangles (q0,q1,q2), (q0,q2,q3), otherwise (q0,q3,q2), (q0,q2,q1): counter-clockwise seen from outside, towards increasing
+ *   distance.  Degenerate triangles are kept.  Indices are uint32.
+ * The order is exactly this one on every run (a prefix scan over per-cell counts places the output; no arrival-order atomics).
+ *
+ * rm_mesh_extract: rm_sdf_grid's values, which never leave the device, then the mesher.  params == NULL: the defaults (iso 0,
+ *   normals 1, normal_delta 1e-5f, colours 0, flags 0 -- flags as rm_sdf_grid takes them).
+ * rm_mesh_from_values: the mesher on the caller's field (corners floats of HOST memory, x fastest).
+ * Arrays of a mesh (rm_mesh_download: `bytes` must be the array's exact size, else RM_ERR_INVALID; rm_mesh_device_ptr: NULL for an
+ * absent or empty array):
+ *   RM_MESH_POSITIONS  V x 3 fp32       RM_MESH_TRIANGLES  T x 3 uint32       RM_MESH_CELLS  V uint32, each vertex's linear cell index
+ *   RM_MESH_NORMALS    V x 3 fp32, RM_MESH_COLOURS  V x 3 fp32: only when asked for, only from rm_mesh_extract: what
+ *     rm_probe(RM_PROBE_NORMAL, param = normal_delta) and the first three outputs of rm_probe(RM_PROBE_MATERIAL) give at the vertex
+ *     positions with the same flags (the probe kernel itself, on the mesh's arrays).
+ * rm_mesh_counts: out2 = {vertices, triangles}.  An empty mesh is valid: 0 / 0, and downloads of 0 bytes succeed.  A mesh owns its
+ * arrays; the sampler's and the mesher's scratch is freed before the call returns; a failed allocation is RM_ERR_DEVICE with
+ * nothing leaked.  Like a scene, a mesh belongs to its context and is destroyed before it.  Synchronous.
+ * rm_mesh_timings: out_ms3 = {sampling, meshing, attributes} in milliseconds, from events on the context's stream round the kernels of
+ * each stage of the call that made the mesh: the sampler; count + scan, and emit (the totals' way to the host and the allocation of the
+ * arrays between the two are not in it); the normals and colours probes.  0 for a stage that did not run.
+ * RM_ERR_INVALID before any device work -- and, as for rm_present_display, before the handles are looked at -- for an invalid grid,
+ * an iso that is not finite, normals or colours outside 0 / 1, a normal_delta that is not finite or <= 0 when normals are on, flags
+ * outside rm_sdf_grid's set and reserved != 0; then for NULL handles or outputs, a scene of another context, an unknown `what` and a
+ * wrong `bytes`. */
+typedef struct RmMeshParams { float iso; int32_t normals; float normal_delta; int32_t colours; int32_t flags; int32_t reserved; } RmMeshParams; /* 24 bytes */
+RM_API void rm_mesh_params_default(RmMeshParams* params);
+typedef struct rm_mesh rm_mesh;
+RM_API int rm_mesh_extract(rm_ctx* ctx, rm_scene* scene, const RmGrid* grid, const RmMeshParams* params, rm_mesh** out);
+RM_API int rm_mesh_from_values(rm_ctx* ctx, const RmGrid* grid, const float* values_host, float iso, rm_mesh** out);
+RM_API int rm_mesh_counts(const rm_mesh* mesh, unsigned long long* out2);
+RM_API int rm_mesh_timings(const rm_mesh* mesh, float* out_ms3);
+enum { RM_MESH_POSITIONS = 0, RM_MESH_NORMALS = 1, RM_MESH_COLOURS = 2, RM_MESH_TRIANGLES = 3, RM_MESH_CELLS = 4 };
+RM_API int rm_mesh_download(rm_mesh* mesh, int what, void* host, size_t bytes);
+RM_API void* rm_mesh_device_ptr(rm_mesh* mesh, int what);
+RM_API void rm_mesh_destroy(rm_mesh* mesh);
 
 #ifdef __cplusplus
 }

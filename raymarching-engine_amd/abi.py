@@ -220,3 +220,33 @@ class RmDisplay(C.Structure):
 DISPLAY_DEFAULTS = dict(gain=1.0, tone=RM_TONE_CLIP, white=4.0)  # rm_display_default
 
 assert C.sizeof(RmFrameStats) == 4136 and C.sizeof(RmAutoExposure) == 24 and C.sizeof(RmDisplay) == 16
+
+
+RM_MESH_POSITIONS, RM_MESH_NORMALS, RM_MESH_COLOURS, RM_MESH_TRIANGLES, RM_MESH_CELLS = 0, 1, 2, 3, 4
+
+
+class RmGrid(C.Structure):
+    """The grid of rm_sdf_grid / rm_mesh_* (ABI 9): n CELLS per axis, n + 1 corners at lo + i * (hi - lo) / n (include/hip_raymarch.h)."""
+    _fields_ = [
+        ("lo", C.c_float * 3),
+        ("hi", C.c_float * 3),
+        ("n", C.c_int32 * 3),
+        ("reserved", C.c_int32),
+    ]
+
+
+class RmMeshParams(C.Structure):
+    """Parameters of rm_mesh_extract (ABI 9): the level, and which per-vertex arrays the scene's probes add (include/hip_raymarch.h)."""
+    _fields_ = [
+        ("iso", C.c_float),
+        ("normals", C.c_int32),
+        ("normal_delta", C.c_float),
+        ("colours", C.c_int32),
+        ("flags", C.c_int32),
+        ("reserved", C.c_int32),
+    ]
+
+
+MESH_DEFAULTS = dict(iso=0.0, normals=1, normal_delta=1e-5, colours=0, flags=0)  # rm_mesh_params_default
+
+assert C.sizeof(RmGrid) == 40 and C.sizeof(RmMeshParams) == 24

@@ -32,6 +32,7 @@
 extern "C" {
 hipError_t rm_gl_launch_pixels(const void* kparams, hipStream_t stream);
 hipError_t rm_gl_launch_probe(const void* probe_params, hipStream_t stream);
+hipError_t rm_gl_launch_sdf_grid(const void* grid_params, hipStream_t stream);
 hipError_t rm_gl_launch_math_probe(int fn, const float* a, const float* b, int n, float* out, hipStream_t stream);
 hipError_t rm_gl_launch_camera_rng(const RmUniforms* u, int W, int H, int what, int count, float* out, hipStream_t stream);
 hipError_t rm_gl_launch_present(const float4* color, const void* normal_dof, bool nd_half, int W, int H, float brightness, uchar4* out, hipStream_t stream);
@@ -244,6 +245,8 @@ struct rm_ctx {
   hipStream_t lpt_stream = nullptr;
   bool lpt_enabled = true;
   hipEvent_t switch_ev = nullptr;  // orders the old stream before the new one in rm_ctx_set_stream
+  hipEvent_t mesh_ev[7] = {};      // rm_mesh_extract / rm_mesh_from_values: the marks between their stages (rm_mesh_timings), made with the first mesh
+  hipEvent_t mesh_order = nullptr; // rm_sdf_grid_device on a caller's stream: the context's stream waits behind that launch (sdf_grid_enqueue)
   std::unordered_map<void*, size_t> buffers;  // rm_buffer_create: base address -> bytes
   Scratch scratch[SCRATCH_COUNT];  // scratch_reserve
   rm_ctx() { scratch[SCRATCH_STATS_HOST].pinned_host = true; }
@@ -394,6 +397,9 @@ void rm_ctx_destroy(rm_ctx* ctx) {
   if (ctx->cull_order) (void)hipEventDestroy(ctx->cull_order);
   for (auto& b : ctx->buffers) (void)hipFree(b.first);  // rm_buffer_create'd memory the host did not destroy
   if (ctx->switch_ev) (void)hipEventDestroy(ctx->switch_ev);
+  for (hipEvent_t e : ctx->mesh_ev)
+    if (e) (void)hipEventDestroy(e);
+  if (ctx->mesh_order) (void)hipEventDestroy(ctx->mesh_order);
   if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);
   if (ctx->ev1) (void)hipEventDestroy(ctx->ev1);
   if (ctx->own_stream) (void)hipStreamDestroy(ctx->own_stream);
@@ -2229,6 +2235,15 @@ int rm_present_sharded(rm_ctx* const* ctxs, rm_fb* const* fbs, int parts, int sa
 
 // ---- probes ----------------------------------------------------------------------
 
+// One probe launch on device arrays: the scene block as the flags shape it, and the unit the flags and the context select.  rm_probe's, and
+// the mesh entries' for the normals and colours of a mesh (rm_mesh_host.inc).
+static hipError_t probe_enqueue(rm_ctx* ctx, rm_scene* scene, int what, const float* d_in, float* d_out, int n, float param, int flags, hipStream_t stream) {
+  ProbeParams P{scene->dev, d_in, d_out, n, what, param, (flags & RM_RENDER_FAST) ? ctx->retire_eps : 0.0f, (flags & RM_RENDER_NO_FAR_JUMP) ? 1 : 0};
+  if (P.no_far_jump) P.scene.far_end = 0, P.scene.clear_rho = 0.0f;
+  if (flags & RM_RENDER_NO_CULL) P.scene.cull.cells = nullptr;
+  return (flags & RM_RENDER_FAST) ? rm::launch_probe_fast(P, stream) : ctx->gl_stack ? rm_gl_launch_probe(&P, stream) : rm::launch_probe_strict(P, stream);
+}
+
 int rm_probe(rm_ctx* ctx, rm_scene* scene, int what, const float* in, int n, float param, int flags, float* out) {
   if (!ctx || !scene || !in || !out) return fail(ctx, RM_ERR_INVALID, "rm_probe: NULL argument");
   if (scene->ctx != ctx) return fail(ctx, RM_ERR_INVALID, "rm_probe: the scene belongs to another context");
@@ -2242,12 +2257,7 @@ int rm_probe(rm_ctx* ctx, rm_scene* scene, int what, const float* in, int n, flo
   hipError_t e = hipMalloc(reinterpret_cast<void**>(&d_out), out_bytes);
   if (e == hipSuccess) e = hipMemcpyAsync(d_in, in, in_bytes, hipMemcpyHostToDevice, ctx->stream);
   if (e == hipSuccess && scene_cull_grid(ctx, scene, flags, 1ll << 40) != RM_OK) e = hipErrorUnknown;  // (a probe is a test's call: with the grid)
-  if (e == hipSuccess) {
-    ProbeParams P{scene->dev, d_in, d_out, n, what, param, (flags & RM_RENDER_FAST) ? ctx->retire_eps : 0.0f, (flags & RM_RENDER_NO_FAR_JUMP) ? 1 : 0};
-    if (P.no_far_jump) P.scene.far_end = 0, P.scene.clear_rho = 0.0f;
-    if (flags & RM_RENDER_NO_CULL) P.scene.cull.cells = nullptr;
-    e = (flags & RM_RENDER_FAST) ? rm::launch_probe_fast(P, ctx->stream) : ctx->gl_stack ? rm_gl_launch_probe(&P, ctx->stream) : rm::launch_probe_strict(P, ctx->stream);
-  }
+  if (e == hipSuccess) e = probe_enqueue(ctx, scene, what, d_in, d_out, n, param, flags, ctx->stream);
   if (e == hipSuccess) e = hipMemcpyAsync(out, d_out, out_bytes, hipMemcpyDeviceToHost, ctx->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
   (void)hipFree(d_in);
@@ -2297,5 +2307,7 @@ int rm_probe_camera(rm_ctx* ctx, const RmUniforms* uniforms, int width, int heig
 int rm_probe_rng(rm_ctx* ctx, const RmUniforms* uniforms, int width, int height, int count, float* out) {
   return camera_rng(ctx, uniforms, width, height, 1, count, out);
 }
+
+#include "rm_mesh_host.inc"
 
 }  // extern "C"

@@ -1,0 +1,240 @@
+// Mesh extraction (include/hip_raymarch.h "mesh extraction"): a scene's distance on a grid of corners, in this unit's arithmetic,
+// and -- in the strict unit only, it has no arithmetic of a policy's own -- the surface-nets mesher over such a grid.  Included by
+// rm_strict.hip / rm_fast.hip / rm_glstack.hip behind rm_kernels.inc.
+namespace rm {
+
+// ---- the sampler: rm_probe's RM_PROBE_SDF with the point made from the corner's indices -------------------------------------
+// One thread per corner, x fastest, so a wave's stores are one run of a row.  Lanes beyond the last corner evaluate the last corner
+// and store nothing: the evaluators ballot and branch wave-uniformly (rm_probe_kernel keeps whole waves alive the same way).
+template <int KIND, bool FAST>
+__global__ __launch_bounds__(256) void rm_sdf_grid_kernel(const SdfGridParams P) {
+  using MM = typename std::conditional<FAST, FM, PM>::type;
+  __shared__ SceneLds lds;
+  const GridDims& g = P.grid;
+  const int gi = blockIdx.x * blockDim.x + threadIdx.x;
+  const int c = gi < g.corners ? gi : g.corners - 1;
+  const int i = c % g.nc[0], row = c / g.nc[0];
+  const v3 p = V(rm_grid_coord(g, 0, i), rm_grid_coord(g, 1, row % g.nc[1]), rm_grid_coord(g, 2, row / g.nc[1]));
+  enter_math_mode<KIND, FAST>();
+  Sdf<KIND>::stage(P.scene, lds);
+  __syncthreads();
+  const float d = Sdf<KIND>::template eval<MM>(P.scene, lds, p);
+  if (gi < g.corners) P.out[c] = d;
+}
+
+#ifndef RM_ONLY_KERNELS
+// the kind selection is launch_probe's, row for row: a corner's value has to be the probe's at that point
+hipError_t RM_LAUNCH(launch_sdf_grid)(const SdfGridParams& P, hipStream_t stream) {
+  const dim3 grid((unsigned int)((P.grid.corners + 255) / 256));
+#define RM_GRID_CASE(K) case K: hipLaunchKernelGGL((rm_sdf_grid_kernel<K, kFast>), grid, dim3(256), 0, stream, P); break;
+  if (P.scene.kind == RM_SCENE_TABLE && (P.scene.table_flags & RM_TABLE_HAS_KIND)) {
+    hipLaunchKernelGGL((rm_sdf_grid_kernel<RM_KIND_TABLE_KINDS, kFast>), grid, dim3(256), 0, stream, P);
+    return hipGetLastError();
+  }
+  if (P.scene.kind == RM_SCENE_TABLE && P.scene.nprims >= RM_TABLE_BIG_ROWS) {
+    hipLaunchKernelGGL((rm_sdf_grid_kernel<RM_KIND_TABLE_BIG, kFast>), grid, dim3(256), 0, stream, P);
+    return hipGetLastError();
+  }
+  switch (P.scene.kind) {
+    RM_GRID_CASE(RM_SCENE_TABLE)
+    RM_GRID_CASE(RM_SCENE_MANDELBULB)
+    RM_GRID_CASE(RM_SCENE_SPHERE_GRID)
+    RM_GRID_CASE(RM_SCENE_SPHERE_LATTICE)
+    RM_GRID_CASE(RM_SCENE_MENGER)
+    RM_GRID_CASE(RM_SCENE_KIFS_TREE)
+    RM_GRID_CASE(RM_SCENE_KIFS_BOX)
+    default: return hipErrorInvalidValue;
+  }
+#undef RM_GRID_CASE
+  return hipGetLastError();
+}
+#endif
+
+#if !RM_BUILD_FAST && !RM_GL_STACK
+// ---- the mesher: surface nets ---------------------------------------------------------------------------------------------------
+// A corner is inside iff v - iso < 0 (NaN, +0, -0 are outside); a cell is active iff its 8 corners are not all alike and then owns
+// one vertex, the mean of its edges' crossing points; an edge whose ends differ, away from the grid's boundary, owns one quad
+// between the four cells round it.  Three steps: count per cell, scan, emit -- so vertices and faces come out in ascending cell
+// order on every run, with no atomics.  One thread per cell; a cell reads its 8 corners (two runs of a row per wave and pair of rows).
+
+struct MeshCell {
+  int idx[3];      // the cell's indices
+  int cell;        // (k * ny + j) * nx + i
+  float e[8];      // v - iso of corner dx | dy << 1 | dz << 2
+  unsigned int inside;  // bit per corner
+};
+
+__device__ inline MeshCell mesh_cell(const MeshParams& P, int cell) {
+  const GridDims& g = P.grid;
+  const int nx = g.nc[0] - 1, ny = g.nc[1] - 1;
+  MeshCell c;
+  c.cell = cell;
+  c.idx[0] = cell % nx;
+  c.idx[1] = (cell / nx) % ny;
+  c.idx[2] = cell / (nx * ny);
+  const size_t base = ((size_t)c.idx[2] * g.nc[1] + c.idx[1]) * g.nc[0] + c.idx[0];
+  c.inside = 0u;
+#pragma unroll
+  for (int k = 0; k < 8; k++) {
+    const size_t at = base + (size_t)(k & 1) + (size_t)((k >> 1) & 1) * g.nc[0] + (size_t)(k >> 2) * g.nc[0] * g.nc[1];
+    c.e[k] = P.values[at] - P.iso;
+    c.inside |= (c.e[k] < 0.0f ? 1u : 0u) << k;
+  }
+  return c;
+}
+
+// the quads the cell's three low edges own, as a mask over the axes
+__device__ inline unsigned int mesh_quads(const MeshCell& c) {
+  unsigned int q = 0u;
+#pragma unroll
+  for (int a = 0; a < 3; a++) {
+    const int b = (a + 1) % 3, cc = (a + 2) % 3;
+    const bool crosses = ((c.inside ^ (c.inside >> (1 << a))) & 1u) != 0u;
+    if (crosses && c.idx[b] >= 1 && c.idx[cc] >= 1) q |= 1u << a;
+  }
+  return q;
+}
+
+__global__ __launch_bounds__(256) void rm_mesh_count_kernel(const MeshParams P, int cells) {
+  const int cell = blockIdx.x * blockDim.x + threadIdx.x;
+  if (cell >= cells) return;
+  const MeshCell c = mesh_cell(P, cell);
+  const unsigned long long active = (c.inside != 0u && c.inside != 0xFFu) ? 1ull : 0ull;
+  P.counts[cell] = active | ((unsigned long long)__popc(mesh_quads(c)) << 32);
+}
+
+// Exclusive scan of 64-bit words (two 32-bit sums side by side: neither reaches 2^32), 256 per workgroup: every element becomes the sum
+// of those before it IN ITS WORKGROUP and sums[workgroup] the workgroup's total; the totals are scanned the same way (launch_mesh_scan)
+// and added back.  n is a long long: 2^28 cells at most, but the words are addressed with it.
+__global__ __launch_bounds__(256) void rm_mesh_scan_kernel(unsigned long long* data, long long n, unsigned long long* sums) {
+  __shared__ unsigned long long s[256];
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  const unsigned long long v = i < n ? data[i] : 0ull;
+  s[threadIdx.x] = v;
+  __syncthreads();
+  for (int off = 1; off < 256; off <<= 1) {
+    const unsigned long long u = (int)threadIdx.x >= off ? s[threadIdx.x - off] : 0ull;
+    __syncthreads();
+    s[threadIdx.x] += u;
+    __syncthreads();
+  }
+  if (i < n) data[i] = s[threadIdx.x] - v;
+  if (threadIdx.x == 255) sums[blockIdx.x] = s[255];
+}
+__global__ __launch_bounds__(256) void rm_mesh_scan_add_kernel(unsigned long long* data, long long n, const unsigned long long* sums) {
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i < n) data[i] += sums[blockIdx.x];
+}
+
+__global__ __launch_bounds__(256) void rm_mesh_emit_kernel(const MeshParams P, int cells) {
+  const int cell = blockIdx.x * blockDim.x + threadIdx.x;
+  if (cell >= cells) return;
+  const MeshCell c = mesh_cell(P, cell);
+  if (c.inside == 0u || c.inside == 0xFFu) return;  // (an edge that owns a quad crosses: its cell is active)
+  const GridDims& g = P.grid;
+  const unsigned long long first = P.counts[cell];
+  float pc[3][2];  // the corners' coordinates
+#pragma unroll
+  for (int a = 0; a < 3; a++) { pc[a][0] = rm_grid_coord(g, a, c.idx[a]); pc[a][1] = rm_grid_coord(g, a, c.idx[a] + 1); }
+  float sum[3] = {0.0f, 0.0f, 0.0f};
+  int m = 0;
+#pragma unroll
+  for (int a = 0; a < 3; a++) {
+    const int b = (a + 1) % 3, cc = (a + 2) % 3;
+#pragma unroll
+    for (int o = 0; o < 4; o++) {
+      const int ob = o & 1, oc = o >> 1, k0 = (ob << b) | (oc << cc), k1 = k0 | (1 << a);
+      if ((((c.inside >> k0) ^ (c.inside >> k1)) & 1u) == 0u) continue;
+      float t = c.e[k0] / (c.e[k0] - c.e[k1]);
+      if (!(t >= 0.0f && t <= 1.0f)) t = 0.5f;
+      const float span = pc[a][1] - pc[a][0], step = t * span;
+      float p[3];
+      p[a] = pc[a][0] + step;
+      p[b] = pc[b][ob];
+      p[cc] = pc[cc][oc];
+      sum[0] += p[0]; sum[1] += p[1]; sum[2] += p[2];
+      m++;
+    }
+  }
+  const unsigned int vertex = (unsigned int)first;
+  const float fm = (float)m;
+  P.positions[3 * (size_t)vertex] = sum[0] / fm;
+  P.positions[3 * (size_t)vertex + 1] = sum[1] / fm;
+  P.positions[3 * (size_t)vertex + 2] = sum[2] / fm;
+  P.cells[vertex] = (unsigned int)cell;
+  // the quads: vertices of the cells at (b, c) offsets (-1,-1), (0,-1), (0,0), (-1,0); counter-clockwise seen from outside
+  const unsigned int quads = mesh_quads(c);
+  const int stride[3] = {1, g.nc[0] - 1, (g.nc[0] - 1) * (g.nc[1] - 1)};
+  size_t tri = 2 * (size_t)(first >> 32);
+#pragma unroll
+  for (int a = 0; a < 3; a++) {
+    if (!((quads >> a) & 1u)) continue;
+    const int sb = stride[(a + 1) % 3], sc = stride[(a + 2) % 3];
+    const unsigned int q0 = (unsigned int)P.counts[cell - sb - sc], q1 = (unsigned int)P.counts[cell - sc], q2 = vertex, q3 = (unsigned int)P.counts[cell - sb];
+    unsigned int* t = P.triangles + 3 * tri;
+    if (c.inside & 1u) { t[0] = q0; t[1] = q1; t[2] = q2; t[3] = q0; t[4] = q2; t[5] = q3; }
+    else { t[0] = q0; t[1] = q3; t[2] = q2; t[3] = q0; t[4] = q2; t[5] = q1; }
+    tri += 2;
+  }
+}
+
+// the first three of every twelve floats: the diffuse colour out of the material probe's records
+// (the name matters to an existing test: tests/test_gbuffer_half_cpu.py runs llvm-objdump -D over the code objects, data sections included, and
+// that tool faults on some symbol-table offsets read as instructions; kernel names shift those offsets -- rerun that test after renaming one)
+__global__ __launch_bounds__(256) void rm_mesh_take3_kernel(const float* material, float* colours, long long n3) {
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i < n3) colours[i] = material[(i / 3) * 12 + i % 3];
+}
+
+#ifndef RM_ONLY_KERNELS
+static inline long long mesh_cells(const GridDims& g) { return (long long)(g.nc[0] - 1) * (g.nc[1] - 1) * (g.nc[2] - 1); }
+
+hipError_t launch_mesh_count(const MeshParams& P, hipStream_t stream) {
+  const long long cells = mesh_cells(P.grid);
+  hipLaunchKernelGGL(rm_mesh_count_kernel, dim3((unsigned int)((cells + 255) / 256)), dim3(256), 0, stream, P, (int)cells);
+  return hipGetLastError();
+}
+
+// the workgroup totals of every level but the last, one level behind the other
+size_t rm_mesh_scan_scratch_elems(long long cells) {
+  size_t elems = 0;
+  for (long long n = (cells + 255) / 256; n > 1; n = (n + 255) / 256) elems += (size_t)n;
+  return elems;
+}
+
+// counts[0 .. cells) -> the exclusive scan, in place; *total (device) = the sum of all of them
+hipError_t launch_mesh_scan(unsigned long long* counts, long long cells, unsigned long long* scratch, unsigned long long* total, hipStream_t stream) {
+  unsigned long long* data[8];
+  long long n[8];
+  int levels = 0;
+  data[0] = counts;
+  n[0] = cells;
+  for (;;) {  // down: 2^28 cells make four levels
+    const long long groups = (n[levels] + 255) / 256;
+    unsigned long long* sums = groups == 1 ? total : scratch;
+    hipLaunchKernelGGL(rm_mesh_scan_kernel, dim3((unsigned int)groups), dim3(256), 0, stream, data[levels], n[levels], sums);
+    if (groups == 1) break;
+    scratch += groups;
+    levels++;
+    data[levels] = sums;
+    n[levels] = groups;
+  }
+  for (int l = levels - 1; l >= 0; l--)  // and up
+    hipLaunchKernelGGL(rm_mesh_scan_add_kernel, dim3((unsigned int)((n[l] + 255) / 256)), dim3(256), 0, stream, data[l], n[l], data[l + 1]);
+  return hipGetLastError();
+}
+
+hipError_t launch_mesh_colours(const float* material, float* colours, long long vertices, hipStream_t stream) {
+  hipLaunchKernelGGL(rm_mesh_take3_kernel, dim3((unsigned int)((3 * vertices + 255) / 256)), dim3(256), 0, stream, material, colours, 3 * vertices);
+  return hipGetLastError();
+}
+
+hipError_t launch_mesh_emit(const MeshParams& P, hipStream_t stream) {
+  const long long cells = mesh_cells(P.grid);
+  hipLaunchKernelGGL(rm_mesh_emit_kernel, dim3((unsigned int)((cells + 255) / 256)), dim3(256), 0, stream, P, (int)cells);
+  return hipGetLastError();
+}
+#endif
+#endif  // !RM_BUILD_FAST && !RM_GL_STACK
+
+}  // namespace rm

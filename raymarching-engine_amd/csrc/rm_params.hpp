@@ -292,6 +292,36 @@ struct ProbeParams {
 };
 // (the probe follows RM_RENDER_NO_CULL through scene.cull.cells, which rm_probe clears)
 
+// A grid of corners as the mesh kernels take it (rm_mesh_kernels.inc; RmGrid checked, h divided once on the host): corner i of axis a
+// lies at lo[a] + (float)i * h[a], each operation rounded on its own; nc = corners per axis (cells + 1), x fastest in memory.
+struct GridDims {
+  float lo[3], h[3];
+  int nc[3];
+  int corners;  // nc[0] * nc[1] * nc[2] <= 2^28
+};
+__host__ __device__ inline float rm_grid_coord(const GridDims& g, int axis, int i) {
+#pragma clang fp contract(off)  // (the host unit is not built contract-off)
+  const float step = (float)i * g.h[axis];
+  return g.lo[axis] + step;
+}
+// rm_sdf_grid: Sdf<KIND>::eval at every corner, with the probe's scene block
+struct SdfGridParams {
+  DevScene scene;
+  GridDims grid;
+  float* out;
+};
+// The surface-nets mesher over a grid of values.  counts: per cell (vertex flag) | (quads << 32), scanned in place into the cell's
+// first vertex | first quad; the emit pass reads a neighbour's vertex index from there (every cell round a crossing edge is active).
+struct MeshParams {
+  GridDims grid;
+  const float* values;
+  float iso;
+  unsigned long long* counts;  // cells entries
+  float* positions;            // emit: V x 3
+  unsigned int* cells;         // emit: V
+  unsigned int* triangles;     // emit: T x 3
+};
+
 // One pass of the denoiser (rm_frame_kernels.inc "denoise").  Pass 0 reads color / normal_dof / albedo_depth and writes
 // guide; later passes read x_in and guide; the last pass reads color (.w) and albedo_depth (the modulation) again.
 struct DenoisePass {
@@ -412,6 +442,14 @@ hipError_t launch_pixels_strict(const KParams& P, hipStream_t stream);
 hipError_t launch_pixels_fast(const KParams& P, hipStream_t stream);
 hipError_t launch_probe_strict(const ProbeParams& P, hipStream_t stream);
 hipError_t launch_probe_fast(const ProbeParams& P, hipStream_t stream);
+// rm_mesh_kernels.inc: the grid sampler in each unit's arithmetic; the mesher's three steps (strict unit only, arithmetic-independent)
+hipError_t launch_sdf_grid_strict(const SdfGridParams& P, hipStream_t stream);
+hipError_t launch_sdf_grid_fast(const SdfGridParams& P, hipStream_t stream);
+size_t rm_mesh_scan_scratch_elems(long long cells);  // 64-bit words of scratch launch_mesh_scan needs behind the counts
+hipError_t launch_mesh_count(const MeshParams& P, hipStream_t stream);
+hipError_t launch_mesh_scan(unsigned long long* counts, long long cells, unsigned long long* scratch, unsigned long long* total, hipStream_t stream);
+hipError_t launch_mesh_emit(const MeshParams& P, hipStream_t stream);
+hipError_t launch_mesh_colours(const float* material, float* colours, long long vertices, hipStream_t stream);  // 12 floats per vertex -> the first 3
 hipError_t launch_camera_rng(const RmUniforms& u, int W, int H, int what, int count, float* out, hipStream_t stream);
 hipError_t launch_math_probe(int fn, const float* a, const float* b, int n, float* out, hipStream_t stream);
 }  // namespace rm

@@ -4,6 +4,7 @@
 #include <type_traits>
 #include "rm_device.hpp"
 #include "rm_kernels.inc"
+#include "rm_mesh_kernels.inc"
 #include "rm_frame_kernels.inc"
 #ifndef RM_WITH_WAVEFRONT
 #define RM_WITH_WAVEFRONT 0  // 1: the tests' cross-check build (rm_wavefront_host.inc)

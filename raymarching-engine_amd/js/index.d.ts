@@ -111,6 +111,12 @@ export class RenderJobContext {
   readonly moments: boolean;
   fboCreate(width: number, height: number, frameid: number): RenderJobFramebufferInfo;
   fboDelete(width: number, height: number, frameid: number): void;
+  /** the scene's distance at every corner of the grid, x fastest (rm_sdf_grid): rm_probe's RM_PROBE_SDF at the corners, bit for bit */
+  sdfGrid(scene: Scene, grid: MeshGrid, flags?: number): Float32Array;
+  /** the level set `iso` of the scene on the grid as triangles (rm_mesh_extract: sampled and meshed with surface nets on the GPU) */
+  extractMesh(scene: Scene, grid: MeshGrid, params?: MeshParams | null): Mesh;
+  /** the mesher alone on the caller's field (rm_mesh_from_values) */
+  meshFromValues(grid: MeshGrid, values: Float32Array, iso?: number): Mesh;
   close(): void;
 }
 /** A frame sharded over several GPUs by this one process: a native context per device, each holding one part of the frame's
@@ -139,3 +145,12 @@ export function halton(base: number): Generator<number, never, unknown>;
 export function resetHalton(): void;
 export function encodePng(rgba: Uint8Array, width: number, height: number, bottomUp?: boolean): Buffer;
 export const RM: { [name: string]: number };
+/** mesh extraction (include/hip_raymarch.h "mesh extraction"): n = CELLS per axis between the corners lo and hi */
+export interface MeshGrid { lo: [number, number, number]; hi: [number, number, number]; n: [number, number, number] }
+export interface MeshParams { iso?: number; normals?: boolean | 0 | 1; normalDelta?: number; colours?: boolean | 0 | 1; flags?: number }
+export interface Mesh { positions: Float32Array; normals: Float32Array | null; colours: Float32Array | null; triangles: Uint32Array; cells: Uint32Array; /** ms of sampling, meshing, attributes (rm_mesh_timings) */ timings: [number, number, number] }
+export const MESH_DEFAULTS: { iso: number; normals: 0 | 1; normalDelta: number; colours: 0 | 1; flags: number };
+export function meshGrid(lo: number[], hi: number[], n: number[]): MeshGrid;
+export function meshParams(params?: MeshParams | null): { iso: number; normals: 0 | 1; normalDelta: number; colours: 0 | 1; flags: number };
+/** binary little-endian PLY (normals and uchar colours when present): the bytes the Python host's write_ply writes */
+export function encodePly(mesh: { positions: Float32Array; triangles: Uint32Array; normals?: Float32Array | null; colours?: Float32Array | null }): Buffer;

@@ -345,6 +345,22 @@ class RenderJobContext {  // RenderJobContext + loadRenderJobContext (LoadRender
     this.purgatory.push({ w, h, frameid, fb: info.fb });
     while (this.purgatory.length > 3) addon.fbDestroy(this.purgatory.shift().fb);
   }
+  // ---- mesh extraction (include/hip_raymarch.h "mesh extraction"); scene: a composer object, through the scene cache ----
+  sceneHandle(scene) { const h = this.getScene(scene); if (h && h.infoLog) throw new Error("scene: " + h.infoLog); return h; }
+  // the scene's distance at every corner of grid (meshGrid): Float32Array, x fastest -- rm_probe's RM_PROBE_SDF at the corners, bit for bit
+  sdfGrid(scene, grid, flags = 0) {
+    const out = new Float32Array((grid.n[0] + 1) * (grid.n[1] + 1) * (grid.n[2] + 1));
+    addon.sdfGrid(this.ctx, this.sceneHandle(scene), grid, flags, out);
+    return out;
+  }
+  // the level set opts.iso as { positions, normals | null, colours | null, triangles, cells } (rm_mesh_extract); opts: meshParams'
+  extractMesh(scene, grid, opts) { return addon.extractMesh(this.ctx, this.sceneHandle(scene), grid, meshParams(opts)); }
+  // the mesher alone on the caller's field: values Float32Array of the grid's corners, x fastest (rm_mesh_from_values)
+  meshFromValues(grid, values, iso = 0) {
+    if (!(values instanceof Float32Array)) throw new TypeError("meshFromValues: values must be a Float32Array");
+    if (!finite(iso)) throw new RangeError("mesh: iso must be a finite number");
+    return addon.meshFromValues(this.ctx, grid, values, iso);
+  }
   close() { for (const e of this.purgatory) addon.fbDestroy(e.fb); for (const v of this.live.values()) addon.fbDestroy(v.fb);
             for (const s of this.scenes.values()) if (!(s && s.infoLog)) addon.sceneDestroy(s); addon.ctxDestroy(this.ctx); }
 }
@@ -596,6 +612,64 @@ function statsPercentile(stats, q) {
   return addon.statsPercentile(packStats(stats), q);
 }
 
+// ---- mesh extraction: the grid, the parameters and the PLY writer (include/hip_raymarch.h RmGrid, RmMeshParams) ----
+const MESH_DEFAULTS = { iso: 0.0, normals: 1, normalDelta: 1e-5, colours: 0, flags: 0 };
+// { lo, hi, n }: n = CELLS per axis between the corners lo and hi; checked as the library checks an RmGrid
+function meshGrid(lo, hi, n) {
+  const three = (a) => Array.isArray(a) && a.length === 3 && a.every((v) => typeof v === "number");
+  if (!three(lo) || !three(hi) || !three(n)) throw new TypeError("grid: lo, hi and n take three numbers each");
+  if (!n.every((v) => Number.isInteger(v) && v >= 1 && v <= 1024)) throw new RangeError("grid: n must be integers in 1..1024 cells per axis");
+  for (let a = 0; a < 3; a++) {
+    const l = Math.fround(lo[a]), h = Math.fround(hi[a]), step = Math.fround(Math.fround(h - l) / n[a]);
+    if (!finite(l) || !finite(h) || !finite(step) || !(step > 0)) throw new RangeError("grid: lo, hi and the cell size (hi - lo) / n must be finite, the cell size > 0");
+  }
+  if ((n[0] + 1) * (n[1] + 1) * (n[2] + 1) > 2 ** 28) throw new RangeError("grid: at most 2^28 corners");
+  return { lo: lo.slice(), hi: hi.slice(), n: n.slice() };
+}
+// undefined / null = the defaults, or an object with some of iso, normals, normalDelta, colours, flags (RM.RENDER_FAST, RM.RENDER_NO_CULL);
+// checked as the library checks an RmMeshParams; returns { iso, normals: 0 | 1, normalDelta, colours: 0 | 1, flags }
+function meshParams(opts) {
+  const p = { ...MESH_DEFAULTS };
+  if (opts !== undefined && opts !== null) {
+    if (typeof opts !== "object") throw new TypeError("mesh: expected an object of parameters");
+    for (const [k, v] of Object.entries(opts)) {
+      if (!(k in MESH_DEFAULTS)) throw new TypeError("mesh: unknown parameter " + k);
+      p[k] = v;
+    }
+  }
+  const flag = (v) => v === true || v === 1 ? 1 : v === false || v === 0 ? 0 : -1;
+  if (!finite(p.iso) || !finite(Math.fround(p.iso))) throw new RangeError("mesh: iso must be a finite number");
+  p.normals = flag(p.normals); p.colours = flag(p.colours);
+  if (p.normals < 0 || p.colours < 0) throw new RangeError("mesh: normals and colours must be true or false");
+  if (p.normals && !POSITIVE[0](p.normalDelta)) throw new RangeError("mesh: normalDelta " + POSITIVE[1]);
+  if (!Number.isInteger(p.flags) || (p.flags & ~(RM.RENDER_FAST | RM.RENDER_NO_CULL)) !== 0) throw new RangeError("mesh: flags must be 0, RM.RENDER_FAST, RM.RENDER_NO_CULL or both");
+  return p;
+}
+// binary little-endian PLY of { positions, triangles, normals?, colours? }: x y z, then nx ny nz, then uchar red green blue
+// (floor(clamp(c, 0, 1) * 255 + 0.5), NaN as 0); faces as a uchar count and uint indices -- the bytes the Python host writes
+function encodePly(mesh) {
+  const V = mesh.positions.length / 3, T = mesh.triangles.length / 3, nrm = mesh.normals || null, col = mesh.colours || null;
+  const header = ["ply", "format binary_little_endian 1.0", "comment hip_raymarch mesh", "element vertex " + V, "property float x", "property float y", "property float z"];
+  if (nrm) header.push("property float nx", "property float ny", "property float nz");
+  if (col) header.push("property uchar red", "property uchar green", "property uchar blue");
+  header.push("element face " + T, "property list uchar uint vertex_indices", "end_header");
+  const head = Buffer.from(header.join("\n") + "\n", "ascii"), stride = 12 + (nrm ? 12 : 0) + (col ? 3 : 0);
+  const out = Buffer.alloc(head.length + V * stride + T * 13);
+  head.copy(out, 0);
+  let at = head.length;
+  const byte = (c) => { const x = Number.isNaN(c) ? 0 : Math.min(Math.max(c, 0), 1); return Math.floor(x * 255 + 0.5); };
+  for (let v = 0; v < V; v++) {
+    for (let k = 0; k < 3; k++) { out.writeFloatLE(mesh.positions[3 * v + k], at); at += 4; }
+    if (nrm) for (let k = 0; k < 3; k++) { out.writeFloatLE(nrm[3 * v + k], at); at += 4; }
+    if (col) for (let k = 0; k < 3; k++) out[at++] = byte(col[3 * v + k]);
+  }
+  for (let t = 0; t < T; t++) {
+    out[at++] = 3;
+    for (let k = 0; k < 3; k++) { out.writeUInt32LE(mesh.triangles[3 * t + k], at); at += 4; }
+  }
+  return out;
+}
+
 // ---- PNG capture (index.tsx:470-476 canvas.toDataURL): RGBA8, filter 0, rows flipped to top-down ----
 const zlib = require("zlib");
 const CRC_TABLE = (() => { const t = new Uint32Array(256); for (let n = 0; n < 256; n++) { let c = n; for (let k = 0; k < 8; k++) c = c & 1 ? 0xedb88320 ^ (c >>> 1) : c >>> 1; t[n] = c >>> 0; } return t; })();
@@ -622,4 +696,4 @@ function encodePng(rgba, width, height, bottomUp = true) {
 module.exports = { RM, addon, encodePng, Scene, CsgScene, Mandelbulb, singleSphere, DEFAULT_MATERIAL, halton, resetHalton, uniformsFromSchema, packUniforms,
                    tileRect, RenderJobContext, ShardedRenderJobContext, doRenderJob, U_OFFSET, DENOISE_DEFAULTS, denoiseParams,
                    DENOISE_VARIANCE_DEFAULTS, denoiseVarianceParams, DESPECKLE_DEFAULTS, despeckleParams, DISPLAY_DEFAULTS, AUTO_EXPOSURE_DEFAULTS,
-                   displayParams, statsExposure, statsPercentile };
+                   displayParams, statsExposure, statsPercentile, MESH_DEFAULTS, meshGrid, meshParams, encodePly };

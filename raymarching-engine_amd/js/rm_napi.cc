@@ -447,6 +447,186 @@ static napi_value stats_host(napi_env env, napi_callback_info info, bool exposur
 static napi_value StatsExposure(napi_env env, napi_callback_info info) { return stats_host(env, info, true); }
 static napi_value StatsPercentile(napi_env env, napi_callback_info info) { return stats_host(env, info, false); }
 
+// ---- mesh extraction: meshBlocks, sdfGrid, extractMesh, meshFromValues (include/hip_raymarch.h "mesh extraction") ----
+static const Field MESH_FIELDS[] = {{"iso", Field::FLOAT, offsetof(RmMeshParams, iso)}, {"normals", Field::INT, offsetof(RmMeshParams, normals)},
+                                    {"normalDelta", Field::FLOAT, offsetof(RmMeshParams, normal_delta)}, {"colours", Field::INT, offsetof(RmMeshParams, colours)},
+                                    {"flags", Field::INT, offsetof(RmMeshParams, flags)}};
+
+// The RmGrid of { lo: [x, y, z], hi: [x, y, z], n: [nx, ny, nz] } (numbers; n truncated as an INT field is).  The library checks the values.
+static bool get_grid(napi_env env, napi_value v, RmGrid* g) {
+  napi_valuetype t;
+  if (napi_typeof(env, v, &t) != napi_ok || t != napi_object) return false;
+  std::memset(g, 0, sizeof *g);
+  static const char* const NAMES[3] = {"lo", "hi", "n"};
+  for (int k = 0; k < 3; k++) {
+    napi_value a;
+    uint32_t len = 0;
+    bool is_array = false;
+    if (napi_get_named_property(env, v, NAMES[k], &a) != napi_ok || napi_is_array(env, a, &is_array) != napi_ok || !is_array ||
+        napi_get_array_length(env, a, &len) != napi_ok || len != 3)
+      return false;
+    for (uint32_t i = 0; i < 3; i++) {
+      napi_value x;
+      double d = 0.0;
+      if (napi_get_element(env, a, i, &x) != napi_ok || napi_get_value_double(env, x, &d) != napi_ok) return false;
+      if (k == 0) g->lo[i] = (float)d;
+      else if (k == 1) g->hi[i] = (float)d;
+      else g->n[i] = (d >= -1e9 && d <= 1e9) ? (int32_t)d : -1;
+    }
+  }
+  return true;
+}
+
+static bool get_mesh_params(napi_env env, napi_value v, RmMeshParams* p) {
+  rm_mesh_params_default(p);
+  return get_block(env, v, p, MESH_FIELDS);
+}
+
+static napi_value make_array(napi_env env, napi_typedarray_type type, size_t count, void** data) {
+  napi_value ab, out;
+  if (napi_create_arraybuffer(env, count * 4, data, &ab) != napi_ok || napi_create_typedarray(env, type, count, ab, 0, &out) != napi_ok) return nullptr;
+  return out;
+}
+
+// meshBlocks(grid, params | null) -> { grid: ArrayBuffer(RmGrid), params: ArrayBuffer(RmMeshParams) }: the bytes the calls below hand to the library
+static napi_value MeshBlocks(napi_env env, napi_callback_info info) {
+  size_t argc = 2;
+  napi_value argv[2];
+  NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+  RmGrid g;
+  RmMeshParams p;
+  if (argc != 2 || !get_grid(env, argv[0], &g) || !get_mesh_params(env, argv[1], &p)) {
+    napi_throw_type_error(env, nullptr, "meshBlocks(grid: { lo, hi, n }, params | null)");
+    return nullptr;
+  }
+  napi_value o, gb, pb;
+  void *gd = nullptr, *pd = nullptr;
+  NAPI_OK(napi_create_object(env, &o));
+  NAPI_OK(napi_create_arraybuffer(env, sizeof g, &gd, &gb));
+  NAPI_OK(napi_create_arraybuffer(env, sizeof p, &pd, &pb));
+  std::memcpy(gd, &g, sizeof g);
+  std::memcpy(pd, &p, sizeof p);
+  NAPI_OK(napi_set_named_property(env, o, "grid", gb));
+  NAPI_OK(napi_set_named_property(env, o, "params", pb));
+  return o;
+}
+
+// sdfGrid(ctx, scene, grid, flags, out: Float32Array(corners)) = rm_sdf_grid
+static napi_value SdfGrid(napi_env env, napi_callback_info info) {
+  size_t argc = 5;
+  napi_value argv[5];
+  NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+  rm_ctx* ctx = argc == 5 ? get_external<rm_ctx>(env, argv[0]) : nullptr;
+  rm_scene* scene = argc == 5 ? get_external<rm_scene>(env, argv[1]) : nullptr;
+  RmGrid g;
+  int32_t flags = 0;
+  void* d = nullptr;
+  size_t n = 0;
+  if (!ctx || !scene || !get_grid(env, argv[2], &g) || napi_get_value_int32(env, argv[3], &flags) != napi_ok || !get_buffer(env, argv[4], &d, &n)) {
+    napi_throw_type_error(env, nullptr, "sdfGrid(ctx, scene, grid, flags, out: Float32Array)");
+    return nullptr;
+  }
+  float probe[1025];
+  if (rm_grid_axis(&g, 0, probe) != RM_OK) return throw_rm(env, nullptr, "rm_sdf_grid");  // (the size below is a valid grid's)
+  if (n != (size_t)(g.n[0] + 1) * (size_t)(g.n[1] + 1) * (size_t)(g.n[2] + 1) * sizeof(float)) {
+    napi_throw_range_error(env, nullptr, "sdfGrid: out must hold (nx + 1)(ny + 1)(nz + 1) floats");
+    return nullptr;
+  }
+  if (rm_sdf_grid(ctx, scene, &g, flags, static_cast<float*>(d)) != RM_OK) return throw_rm(env, ctx, "rm_sdf_grid");
+  return nullptr;
+}
+
+// the mesh as { positions, normals | null, colours | null: Float32Array(3 V), triangles: Uint32Array(3 T), cells: Uint32Array(V), timings: [sampling,
+// meshing, attributes] in ms (rm_mesh_timings) }; normals / colours: whether the call asked for them; the handle is destroyed
+static napi_value mesh_result(napi_env env, rm_ctx* ctx, rm_mesh* mesh, bool normals, bool colours) {
+  unsigned long long counts[2] = {0, 0};
+  rm_mesh_counts(mesh, counts);
+  static const struct { const char* name; int what; napi_typedarray_type type; int per_vertex, per_triangle; } ARRAYS[] = {
+      {"positions", RM_MESH_POSITIONS, napi_float32_array, 3, 0}, {"normals", RM_MESH_NORMALS, napi_float32_array, 3, 0}, {"colours", RM_MESH_COLOURS, napi_float32_array, 3, 0},
+      {"triangles", RM_MESH_TRIANGLES, napi_uint32_array, 0, 3}, {"cells", RM_MESH_CELLS, napi_uint32_array, 1, 0}};
+  napi_value o = nullptr;
+  bool ok = napi_create_object(env, &o) == napi_ok;
+  bool refused = false;
+  for (const auto& a : ARRAYS) {
+    if (!ok) break;
+    napi_value v = nullptr;
+    if ((a.what == RM_MESH_NORMALS && !normals) || (a.what == RM_MESH_COLOURS && !colours)) {
+      ok = napi_get_null(env, &v) == napi_ok;  // the mesh was made without this array
+    } else {
+      const size_t count = (size_t)counts[0] * a.per_vertex + (size_t)counts[1] * a.per_triangle;
+      void* data = nullptr;
+      v = make_array(env, a.type, count, &data);
+      ok = v != nullptr;
+      if (!ok) break;
+      if (rm_mesh_download(mesh, a.what, data, count * 4) != RM_OK) { refused = true; break; }
+    }
+    ok = ok && napi_set_named_property(env, o, a.name, v) == napi_ok;
+  }
+  float ms[3] = {0.0f, 0.0f, 0.0f};
+  rm_mesh_timings(mesh, ms);
+  napi_value timings = nullptr;
+  ok = ok && !refused && napi_create_array_with_length(env, 3, &timings) == napi_ok;
+  for (uint32_t k = 0; ok && k < 3; k++) {
+    napi_value x;
+    ok = napi_create_double(env, (double)ms[k], &x) == napi_ok && napi_set_element(env, timings, k, x) == napi_ok;
+  }
+  ok = refused || (ok && napi_set_named_property(env, o, "timings", timings) == napi_ok);
+  if (refused) {
+    napi_value r = throw_rm(env, ctx, "rm_mesh_download");
+    rm_mesh_destroy(mesh);
+    return r;
+  }
+  rm_mesh_destroy(mesh);
+  if (!ok) {
+    napi_throw_error(env, nullptr, "N-API call failed while the mesh was copied");
+    return nullptr;
+  }
+  return o;
+}
+
+// extractMesh(ctx, scene, grid, params | null) = rm_mesh_extract, then the arrays
+static napi_value ExtractMesh(napi_env env, napi_callback_info info) {
+  size_t argc = 4;
+  napi_value argv[4];
+  NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+  rm_ctx* ctx = argc == 4 ? get_external<rm_ctx>(env, argv[0]) : nullptr;
+  rm_scene* scene = argc == 4 ? get_external<rm_scene>(env, argv[1]) : nullptr;
+  RmGrid g;
+  RmMeshParams p;
+  if (!ctx || !scene || !get_grid(env, argv[2], &g) || !get_mesh_params(env, argv[3], &p)) {
+    napi_throw_type_error(env, nullptr, "extractMesh(ctx, scene, grid, params | null)");
+    return nullptr;
+  }
+  rm_mesh* mesh = nullptr;
+  if (rm_mesh_extract(ctx, scene, &g, &p, &mesh) != RM_OK) return throw_rm(env, ctx, "rm_mesh_extract");
+  return mesh_result(env, ctx, mesh, p.normals != 0, p.colours != 0);
+}
+
+// meshFromValues(ctx, grid, values: Float32Array(corners), iso) = rm_mesh_from_values, then the arrays
+static napi_value MeshFromValues(napi_env env, napi_callback_info info) {
+  size_t argc = 4;
+  napi_value argv[4];
+  NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+  rm_ctx* ctx = argc == 4 ? get_external<rm_ctx>(env, argv[0]) : nullptr;
+  RmGrid g;
+  double iso = 0.0;
+  void* d = nullptr;
+  size_t n = 0;
+  if (!ctx || !get_grid(env, argv[1], &g) || !get_buffer(env, argv[2], &d, &n) || napi_get_value_double(env, argv[3], &iso) != napi_ok) {
+    napi_throw_type_error(env, nullptr, "meshFromValues(ctx, grid, values: Float32Array, iso)");
+    return nullptr;
+  }
+  float probe[1025];
+  if (rm_grid_axis(&g, 0, probe) != RM_OK) return throw_rm(env, nullptr, "rm_mesh_from_values");
+  if (n != (size_t)(g.n[0] + 1) * (size_t)(g.n[1] + 1) * (size_t)(g.n[2] + 1) * sizeof(float)) {
+    napi_throw_range_error(env, nullptr, "meshFromValues: values must hold (nx + 1)(ny + 1)(nz + 1) floats");
+    return nullptr;
+  }
+  rm_mesh* mesh = nullptr;
+  if (rm_mesh_from_values(ctx, &g, static_cast<const float*>(d), (float)iso, &mesh) != RM_OK) return throw_rm(env, ctx, "rm_mesh_from_values");
+  return mesh_result(env, ctx, mesh, false, false);
+}
+
 // fbCreateStriped(ctx, width, height, stripeRows, parts, part[, gbuffer]): the stripes k with k % parts == part of a width x height image,
 // planes owned by the library (rm_fb_create_striped) -- what one GPU of a sharded frame holds
 static napi_value FbCreateStriped(napi_env env, napi_callback_info info) {
@@ -642,7 +822,8 @@ static napi_value Sizes(napi_env env, napi_callback_info) {
       {"RmUniforms", (uint32_t)sizeof(RmUniforms)}, {"RmSceneDesc", (uint32_t)sizeof(RmSceneDesc)}, {"RmPrim", (uint32_t)sizeof(RmPrim)},
       {"RmMaterial", (uint32_t)sizeof(RmMaterial)}, {"RmRect", (uint32_t)sizeof(RmRect)}, {"RmSurface", (uint32_t)sizeof(RmSurface)}, {"RmDenoise", (uint32_t)sizeof(RmDenoise)},
       {"RmDenoiseVariance", (uint32_t)sizeof(RmDenoiseVariance)}, {"RmDespeckle", (uint32_t)sizeof(RmDespeckle)}, {"RmFilters", (uint32_t)sizeof(RmFilters)}, {"RmFrameStats", (uint32_t)sizeof(RmFrameStats)},
-      {"RmAutoExposure", (uint32_t)sizeof(RmAutoExposure)}, {"RmDisplay", (uint32_t)sizeof(RmDisplay)}, {"abi", (uint32_t)rm_abi_version()}};
+      {"RmAutoExposure", (uint32_t)sizeof(RmAutoExposure)}, {"RmDisplay", (uint32_t)sizeof(RmDisplay)}, {"RmGrid", (uint32_t)sizeof(RmGrid)},
+      {"RmMeshParams", (uint32_t)sizeof(RmMeshParams)}, {"abi", (uint32_t)rm_abi_version()}};
   for (const auto& it : items) {
     NAPI_OK(napi_create_uint32(env, it.v, &v));
     NAPI_OK(napi_set_named_property(env, o, it.k, v));
@@ -655,7 +836,7 @@ static napi_value Init(napi_env env, napi_value exports) {
       {"ctxCreate", CtxCreate}, {"ctxDestroy", CtxDestroy}, {"sync", Sync}, {"sceneCreate", SceneCreate}, {"sceneDestroy", SceneDestroy},
       {"fbCreate", FbCreate}, {"fbClear", FbClear}, {"fbDestroy", FbDestroy}, {"fbDownload", FbDownload}, {"present", Present}, {"denoise", Denoise}, {"presentDenoised", PresentDenoised}, {"denoiseVariance", DenoiseVariance}, {"presentDenoisedVariance", PresentDenoisedVariance}, {"filter", Filter}, {"presentFiltered", PresentFiltered}, {"presentDisplay", PresentDisplay}, {"presentLinear", PresentLinear}, {"frameStats", FrameStats}, {"statsExposure", StatsExposure}, {"statsPercentile", StatsPercentile}, {"renderSample", RenderSample}, {"renderSamples", RenderSamples},
       {"fbCreateStriped", FbCreateStriped}, {"fbRows", FbRows}, {"setSamplesInFlight", SetSamplesInFlight}, {"presentSharded", PresentSharded}, {"presentShardedStart", PresentShardedStart}, {"presentShardedFinish", PresentShardedFinish},
-      {"sizes", Sizes}};
+      {"meshBlocks", MeshBlocks}, {"sdfGrid", SdfGrid}, {"extractMesh", ExtractMesh}, {"meshFromValues", MeshFromValues}, {"sizes", Sizes}};
   for (const auto& f : fns) {
     napi_value fn;
     if (napi_create_function(env, f.name, NAPI_AUTO_LENGTH, f.fn, nullptr, &fn) != napi_ok) return nullptr;

@@ -1,0 +1,147 @@
+"""Mesh extraction, the Python host: the grid and the mesh of Context.sdf_grid / extract_mesh / mesh_from_values
+(include/hip_raymarch.h "mesh extraction"), and writers for the two formats other tools read."""
+from __future__ import annotations
+
+import math
+from dataclasses import dataclass
+from typing import Optional
+
+import numpy as np
+
+from . import abi
+
+
+class Grid:
+    """`n` = (nx, ny, nz) CELLS between the corners `lo` and `hi`: an axis has n + 1 corners.  Checked as the library checks an RmGrid."""
+
+    def __init__(self, lo, hi, n):
+        self.lo, self.hi = tuple(float(v) for v in lo), tuple(float(v) for v in hi)
+        self.n = tuple(int(v) for v in n)
+        if not (len(self.lo) == len(self.hi) == len(self.n) == 3):
+            raise ValueError("grid: lo, hi and n take three values each")
+        if any(isinstance(v, bool) or int(v) != v for v in n):
+            raise ValueError("grid: n must be integers")
+        if not all(1 <= v <= 1024 for v in self.n):
+            raise ValueError("grid: n must be in 1..1024 cells per axis")
+        f = np.float32
+        with np.errstate(all="ignore"):
+            h = [(f(b) - f(a)) / f(k) for a, b, k in zip(self.lo, self.hi, self.n)]
+        if not all(math.isfinite(f(v)) for v in self.lo + self.hi) or not all(math.isfinite(v) and v > 0 for v in h):
+            raise ValueError("grid: lo, hi and the cell size (hi - lo) / n must be finite, the cell size > 0")
+        if self.corners > 1 << 28:
+            raise ValueError("grid: at most 2^28 corners")
+
+    @property
+    def shape(self):
+        """Of the corner values: (nz + 1, ny + 1, nx + 1), x fastest."""
+        return (self.n[2] + 1, self.n[1] + 1, self.n[0] + 1)
+
+    @property
+    def corners(self) -> int:
+        return (self.n[0] + 1) * (self.n[1] + 1) * (self.n[2] + 1)
+
+    @property
+    def cells(self) -> int:
+        return self.n[0] * self.n[1] * self.n[2]
+
+    def to_c(self) -> abi.RmGrid:
+        return abi.RmGrid(lo=(abi.C.c_float * 3)(*self.lo), hi=(abi.C.c_float * 3)(*self.hi), n=(abi.C.c_int32 * 3)(*self.n), reserved=0)
+
+    def axis(self, a: int) -> np.ndarray:
+        """The n[a] + 1 corner coordinates of axis a (rm_grid_axis: the library's host arithmetic)."""
+        from . import native
+
+        out = np.empty(self.n[a] + 1, np.float32)
+        if native.load_library().rm_grid_axis(abi.C.byref(self.to_c()), int(a), native._fp(out)) != abi.RM_OK:
+            raise ValueError("grid: refused by rm_grid_axis")
+        return out
+
+
+def mesh_params(iso=0.0, normals=True, colours=False, flags=0, normal_delta=1e-5) -> abi.RmMeshParams:
+    """The abi.RmMeshParams of an extraction, checked as the library checks it: ValueError otherwise."""
+    for name, v in (("iso", iso), ("normal_delta", normal_delta)):
+        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)):
+            raise ValueError(f"mesh: {name} must be a number")
+    if not math.isfinite(np.float32(iso)):
+        raise ValueError("mesh: iso must be finite")
+    for name, v in (("normals", normals), ("colours", colours)):
+        if not (isinstance(v, (bool, int, np.integer)) and int(v) in (0, 1)):
+            raise ValueError(f"mesh: {name} must be True or False")
+    if normals and not (math.isfinite(np.float32(normal_delta)) and np.float32(normal_delta) > 0):
+        raise ValueError("mesh: normal_delta must be finite and > 0")
+    if isinstance(flags, bool) or not isinstance(flags, (int, np.integer)) or int(flags) & ~(abi.RM_RENDER_FAST | abi.RM_RENDER_NO_CULL):
+        raise ValueError("mesh: flags must be 0, RM_RENDER_FAST, RM_RENDER_NO_CULL or both")
+    return abi.RmMeshParams(iso=float(iso), normals=int(normals), normal_delta=float(normal_delta), colours=int(colours), flags=int(flags), reserved=0)
+
+
+@dataclass
+class Mesh:
+    """A triangle mesh as numpy arrays: positions [V, 3] float32, triangles [T, 3] uint32 (counter-clockwise seen from outside), cells
+    [V] uint32 (each vertex's linear cell index in `grid`), and normals / colours [V, 3] float32 or None."""
+    positions: np.ndarray
+    triangles: np.ndarray
+    cells: Optional[np.ndarray] = None
+    normals: Optional[np.ndarray] = None
+    colours: Optional[np.ndarray] = None
+    grid: Optional[Grid] = None
+    timings: Optional[dict] = None  # rm_mesh_timings: milliseconds of sampling, meshing, attributes (device events)
+
+    @property
+    def vertices(self) -> int:
+        return len(self.positions)
+
+
+def _number(v) -> str:
+    return "%.9g" % float(v)  # nine digits give every float32 back
+
+
+def write_obj(mesh: Mesh, path) -> None:
+    """Wavefront OBJ: `v` lines, `vn` lines when the mesh has normals, faces 1-based (`f a//a b//b c//c` with normals)."""
+    lines = ["# hip_raymarch mesh: %d vertices, %d triangles" % (mesh.vertices, len(mesh.triangles))]
+    lines += ["v " + " ".join(_number(c) for c in p) for p in mesh.positions]
+    if mesh.normals is not None:
+        lines += ["vn " + " ".join(_number(c) for c in n) for n in mesh.normals]
+    face = "f {0}//{0} {1}//{1} {2}//{2}" if mesh.normals is not None else "f {0} {1} {2}"
+    lines += [face.format(*(int(i) + 1 for i in t)) for t in mesh.triangles]
+    with open(path, "w") as f:
+        f.write("\n".join(lines) + "\n")
+
+
+def colour_bytes(colours: np.ndarray) -> np.ndarray:
+    """Colours as the PLY stores them: floor(clamp(c, 0, 1) * 255 + 0.5) in double, NaN as 0."""
+    c = np.nan_to_num(np.asarray(colours, np.float64), nan=0.0, posinf=1.0, neginf=0.0)
+    return np.floor(np.clip(c, 0.0, 1.0) * 255.0 + 0.5).astype(np.uint8)
+
+
+def encode_ply(mesh: Mesh) -> bytes:
+    """Binary little-endian PLY: x y z, then nx ny nz when the mesh has normals, then uchar red green blue when it has colours;
+    faces as a uchar count and uint indices."""
+    fields = [("x", "<f4"), ("y", "<f4"), ("z", "<f4")]
+    header = ["ply", "format binary_little_endian 1.0", "comment hip_raymarch mesh", "element vertex %d" % mesh.vertices,
+              "property float x", "property float y", "property float z"]
+    if mesh.normals is not None:
+        fields += [("nx", "<f4"), ("ny", "<f4"), ("nz", "<f4")]
+        header += ["property float nx", "property float ny", "property float nz"]
+    if mesh.colours is not None:
+        fields += [("red", "u1"), ("green", "u1"), ("blue", "u1")]
+        header += ["property uchar red", "property uchar green", "property uchar blue"]
+    header += ["element face %d" % len(mesh.triangles), "property list uchar uint vertex_indices", "end_header"]
+    v = np.zeros(mesh.vertices, np.dtype(fields))
+    for k, name in enumerate("xyz"):
+        v[name] = mesh.positions[:, k]
+        if mesh.normals is not None:
+            v["n" + name] = mesh.normals[:, k]
+    if mesh.colours is not None:
+        rgb = colour_bytes(mesh.colours)
+        for k, name in enumerate(("red", "green", "blue")):
+            v[name] = rgb[:, k]
+    f = np.zeros(len(mesh.triangles), np.dtype([("count", "u1"), ("a", "<u4"), ("b", "<u4"), ("c", "<u4")]))
+    f["count"] = 3
+    for k, name in enumerate("abc"):
+        f[name] = mesh.triangles[:, k]
+    return ("\n".join(header) + "\n").encode("ascii") + v.tobytes() + f.tobytes()
+
+
+def write_ply(mesh: Mesh, path) -> None:
+    with open(path, "wb") as f:
+        f.write(encode_ply(mesh))

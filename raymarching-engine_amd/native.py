@@ -40,6 +40,8 @@ EXPORTS = [
     "rm_filters_default", "rm_filter", "rm_filter_device", "rm_present_filtered",
     "rm_frame_stats", "rm_auto_exposure_default", "rm_stats_percentile", "rm_stats_exposure",
     "rm_display_default", "rm_present_display", "rm_present_display_device", "rm_present_linear",
+    "rm_grid_axis", "rm_sdf_grid", "rm_sdf_grid_device", "rm_mesh_params_default", "rm_mesh_extract", "rm_mesh_from_values", "rm_mesh_counts", "rm_mesh_timings",
+    "rm_mesh_download", "rm_mesh_device_ptr", "rm_mesh_destroy",
 ]
 
 # G-buffer formats of a framebuffer (include/hip_raymarch.h RM_GBUFFER_*): "f32" (the default: the software GL stack's planes, which the
@@ -395,6 +397,17 @@ def load_library(path=None):
         "rm_present_display": (ip, [vp, vp, ip, C.POINTER(abi.RmFilters), C.POINTER(abi.RmDisplay), C.POINTER(C.c_uint8)]),
         "rm_present_display_device": (ip, [vp, vp, ip, C.POINTER(abi.RmFilters), C.POINTER(abi.RmDisplay), vp, vp]),
         "rm_present_linear": (ip, [vp, vp, ip, C.POINTER(abi.RmFilters), C.POINTER(abi.RmDisplay), fp]),
+        "rm_grid_axis": (ip, [C.POINTER(abi.RmGrid), ip, fp]),
+        "rm_sdf_grid": (ip, [vp, vp, C.POINTER(abi.RmGrid), ip, fp]),
+        "rm_sdf_grid_device": (ip, [vp, vp, C.POINTER(abi.RmGrid), ip, vp, vp]),
+        "rm_mesh_params_default": (None, [C.POINTER(abi.RmMeshParams)]),
+        "rm_mesh_extract": (ip, [vp, vp, C.POINTER(abi.RmGrid), C.POINTER(abi.RmMeshParams), C.POINTER(vp)]),
+        "rm_mesh_from_values": (ip, [vp, C.POINTER(abi.RmGrid), fp, C.c_float, C.POINTER(vp)]),
+        "rm_mesh_counts": (ip, [vp, C.POINTER(C.c_ulonglong)]),
+        "rm_mesh_timings": (ip, [vp, fp]),
+        "rm_mesh_download": (ip, [vp, ip, vp, C.c_size_t]),
+        "rm_mesh_device_ptr": (vp, [vp, ip]),
+        "rm_mesh_destroy": (None, [vp]),
     }
     for name, (res, args) in sig.items():
         if name.startswith("rm_debug_") and not hasattr(lib, name) and os.environ.get("RM_LIB"):
@@ -676,6 +689,65 @@ class Context:
         out = np.empty((len(a), out_w), np.float32)
         self._check(self.lib.rm_probe(self.h, scene.h, what, _fp(a), len(a), float(param), flags, _fp(out)))
         return out[:, 0] if out_w == 1 else out
+
+    def sdf_grid(self, scene: "SceneHandle", grid, flags: int = abi.RM_RENDER_STRICT) -> np.ndarray:
+        """The scene's distance at every corner of `grid` (mesh.Grid), float32 [nz + 1, ny + 1, nx + 1]: what probe(RM_PROBE_SDF) gives
+        at the corners' positions with the same flags, bit for bit (rm_sdf_grid)."""
+        g = grid.to_c()
+        out = np.empty(grid.shape, np.float32)
+        self._check(self.lib.rm_sdf_grid(self.h, scene.h, C.byref(g), int(flags), _fp(out)))
+        return out
+
+    def sdf_grid_device(self, scene: "SceneHandle", grid, out_ptr: int, flags: int = abi.RM_RENDER_STRICT, stream: Optional[int] = None):
+        """rm_sdf_grid_device: sdf_grid into grid.corners floats of device memory at out_ptr, enqueued on `stream` (None = the
+        context's); no allocation, no host wait."""
+        g = grid.to_c()
+        self._check(self.lib.rm_sdf_grid_device(self.h, scene.h, C.byref(g), int(flags), C.c_void_p(out_ptr), C.c_void_p(stream) if stream else None))
+
+    def _take_mesh(self, handle, grid, normals=False, colours=False):
+        """The arrays of a mesh handle as a mesh.Mesh (normals / colours: whether the call that made it asked for them); destroys the handle."""
+        from .mesh import Mesh
+
+        try:
+            counts, ms = (C.c_ulonglong * 2)(), (C.c_float * 3)()
+            self._check(self.lib.rm_mesh_counts(handle, counts))
+            self._check(self.lib.rm_mesh_timings(handle, ms))
+            v, t = int(counts[0]), int(counts[1])
+            arrays = {}
+            present = {abi.RM_MESH_NORMALS: bool(normals), abi.RM_MESH_COLOURS: bool(colours)}
+            for name, what, shape, dtype in (("positions", abi.RM_MESH_POSITIONS, (v, 3), np.float32), ("normals", abi.RM_MESH_NORMALS, (v, 3), np.float32),
+                                             ("colours", abi.RM_MESH_COLOURS, (v, 3), np.float32), ("triangles", abi.RM_MESH_TRIANGLES, (t, 3), np.uint32),
+                                             ("cells", abi.RM_MESH_CELLS, (v,), np.uint32)):
+                if not present.get(what, True):
+                    arrays[name] = None  # the mesh was made without this array
+                    continue
+                a = np.empty(shape, dtype)
+                self._check(self.lib.rm_mesh_download(handle, what, a.ctypes.data_as(C.c_void_p), a.nbytes))
+                arrays[name] = a
+            return Mesh(grid=grid, timings=dict(sampling=float(ms[0]), meshing=float(ms[1]), attributes=float(ms[2])), **arrays)
+        finally:
+            self.lib.rm_mesh_destroy(handle)
+
+    def extract_mesh(self, scene: "SceneHandle", grid, iso: float = 0.0, normals: bool = True, colours: bool = False, flags: int = 0,
+                     normal_delta: float = 1e-5):
+        """The level set `iso` of the scene on `grid` (mesh.Grid) as a mesh.Mesh: rm_mesh_extract -- the distances sampled and meshed
+        (surface nets) on the device, with per-vertex normals / diffuse colours from the scene's probes when asked for."""
+        from .mesh import mesh_params
+
+        g, p = grid.to_c(), mesh_params(iso=iso, normals=normals, colours=colours, flags=flags, normal_delta=normal_delta)
+        h = C.c_void_p()
+        self._check(self.lib.rm_mesh_extract(self.h, scene.h, C.byref(g), C.byref(p), C.byref(h)))
+        return self._take_mesh(h, grid, normals=p.normals, colours=p.colours)
+
+    def mesh_from_values(self, grid, values: np.ndarray, iso: float = 0.0):
+        """The mesher alone on the caller's field: `values` float32 [nz + 1, ny + 1, nx + 1] (rm_mesh_from_values)."""
+        g = grid.to_c()
+        v = np.ascontiguousarray(values, np.float32)
+        if v.shape != grid.shape:
+            raise ValueError(f"values must have the shape {grid.shape} of the grid's corners, not {v.shape}")
+        h = C.c_void_p()
+        self._check(self.lib.rm_mesh_from_values(self.h, C.byref(g), _fp(v), float(iso), C.byref(h)))
+        return self._take_mesh(h, grid)
 
     def probe_camera(self, uniforms: abi.RmUniforms, width: int, height: int) -> np.ndarray:
         out = np.empty((height, width, 8), np.float32)
