@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define RM_ABI_VERSION 9 /* 9: RM_GBUFFER_F32 / _F16, rm_fb_create_fmt, rm_fb_create_striped_fmt, rm_fb_wrap_fmt, rm_fb_gbuffer, rm_fb_download_raw, rm_fb_upload_raw, RmDenoise, rm_denoise_default, rm_denoise, rm_denoise_device, rm_present_denoised, RM_FB_MOMENTS, RM_PLANE_MOMENTS, rm_fb_has_moments, RmDenoiseVariance, rm_denoise_variance_default, rm_denoise_variance, rm_denoise_variance_device, rm_present_denoised_variance, RmDespeckle, RmFilters, RM_DENOISE_NONE / _ATROUS / _VARIANCE, rm_filters_default, rm_filter, rm_filter_device, rm_present_filtered, RM_STATS_BINS, RmFrameStats, rm_frame_stats, RmAutoExposure, rm_auto_exposure_default, rm_stats_percentile, rm_stats_exposure, RM_TONE_CLIP / _REINHARD / _ACES, RmDisplay, rm_display_default, rm_present_display, rm_present_display_device, rm_present_linear, RmGrid, rm_grid_axis, rm_sdf_grid, rm_sdf_grid_device, RmMeshParams, rm_mesh_params_default, rm_mesh, rm_mesh_extract, rm_mesh_from_values, rm_mesh_counts, rm_mesh_timings, RM_MESH_POSITIONS / _NORMALS / _COLOURS / _TRIANGLES / _CELLS, rm_mesh_download, rm_mesh_device_ptr, rm_mesh_destroy (additions only); 8: RM_PRIM_TORUS / _CYLINDER / _PLANE, RM_OP_SMOOTH_SUBTRACT / _INTERSECT, rm_probe_math (additions only); 7: rm_present_sharded_finish / rm_present_sharded take the size of the host buffer (a changed signature), rm_ctx_set_cull_min_pixels, rm_ctx_set_cull_budget, rm_ctx_cull_stats; 6: rm_present_striped_rows, rm_present_sharded_start / _finish, rm_ctx_last_warning, RM_PROBE_CAST_SHADOW, RM_PRIM_KIND (additions only); 3: rm_ctx_set_sample_batch, rm_buffer_*; 4: rm_ctx_set_gl_stack; 5: RmSurface / RmSceneDesc.surfaces (the struct grew), rm_pack_present_rows, rm_present_sharded, rm_ctx_last_pipeline, RM_RENDER_NO_FAR_JUMP, RM_RENDER_NO_CULL (additions only) */
+#define RM_ABI_VERSION 9 /* 9: RM_GBUFFER_F32 / _F16, rm_fb_create_fmt, rm_fb_create_striped_fmt, rm_fb_wrap_fmt, rm_fb_gbuffer, rm_fb_download_raw, rm_fb_upload_raw, RmDenoise, rm_denoise_default, rm_denoise, rm_denoise_device, rm_present_denoised, RM_FB_MOMENTS, RM_PLANE_MOMENTS, rm_fb_has_moments, RmDenoiseVariance, rm_denoise_variance_default, rm_denoise_variance, rm_denoise_variance_device, rm_present_denoised_variance, RmDespeckle, RmFilters, RM_DENOISE_NONE / _ATROUS / _VARIANCE, rm_filters_default, rm_filter, rm_filter_device, rm_present_filtered, RM_STATS_BINS, RmFrameStats, rm_frame_stats, RmAutoExposure, rm_auto_exposure_default, rm_stats_percentile, rm_stats_exposure, RM_TONE_CLIP / _REINHARD / _ACES, RmDisplay, rm_display_default, rm_present_display, rm_present_display_device, rm_present_linear, RmGrid, rm_grid_axis, rm_sdf_grid, rm_sdf_grid_device, RmMeshParams, rm_mesh_params_default, rm_mesh, rm_mesh_extract, rm_mesh_from_values, rm_mesh_counts, rm_mesh_timings, RM_MESH_POSITIONS / _NORMALS / _COLOURS / _TRIANGLES / _CELLS, rm_mesh_download, rm_mesh_device_ptr, rm_mesh_destroy, RmMeshSharp, rm_mesh_sharp_default, rm_mesh_extract_sharp (additions only); 8: RM_PRIM_TORUS / _CYLINDER / _PLANE, RM_OP_SMOOTH_SUBTRACT / _INTERSECT, rm_probe_math (additions only); 7: rm_present_sharded_finish / rm_present_sharded take the size of the host buffer (a changed signature), rm_ctx_set_cull_min_pixels, rm_ctx_set_cull_budget, rm_ctx_cull_stats; 6: rm_present_striped_rows, rm_present_sharded_start / _finish, rm_ctx_last_warning, RM_PROBE_CAST_SHADOW, RM_PRIM_KIND (additions only); 3: rm_ctx_set_sample_batch, rm_buffer_*; 4: rm_ctx_set_gl_stack; 5: RmSurface / RmSceneDesc.surfaces (the struct grew), rm_pack_present_rows, rm_present_sharded, rm_ctx_last_pipeline, RM_RENDER_NO_FAR_JUMP, RM_RENDER_NO_CULL (additions only) */
 
 #define RM_MAX_BOUNCES 10 /* raymarchingStepCountsArray[10], raymarcher.frag:31 */
 #define RM_MAX_LIGHTS 10  /* lightPositions[10],             raymarcher.frag:37-39 */
@@ -887,6 +887,50 @@ enum { RM_MESH_POSITIONS = 0, RM_MESH_NORMALS = 1, RM_MESH_COLOURS = 2, RM_MESH_
 RM_API int rm_mesh_download(rm_mesh* mesh, int what, void* host, size_t bytes);
 RM_API void* rm_mesh_device_ptr(rm_mesh* mesh, int what);
 RM_API void rm_mesh_destroy(rm_mesh* mesh);
+
+/* ---- sharp vertices (opt-in): dual contouring over the surface-nets mesh ----
+ * Surface nets puts a cell's vertex at the mean of its edge crossings, which bevels every edge and corner of a scene by about half a cell.
+ * rm_mesh_extract_sharp keeps that mesh -- RM_MESH_TRIANGLES, RM_MESH_CELLS, the vertex count and order are bit for bit those of
+ * rm_mesh_extract with the same grid and params -- and moves each vertex to the minimiser of a quadratic error function (QEF) of the
+ * surface's tangent planes at the cell's edge crossings.  Normals and colours, when asked for, are the probes at the NEW positions, with
+ * params.normal_delta as before.  The result is an ordinary rm_mesh.  params == NULL and sharp == NULL: the defaults (refine 6, normal_delta
+ * 0x1p-10f, threshold 0.1f).  rm_mesh_extract and rm_mesh_from_values are unchanged (a field has no normals: no sharp variant of the latter).
+ *
+ * All arithmetic below is fp32, every operation rounded on its own, no contraction, division and square root IEEE, in the strict build
+ * whatever params.flags say: the flags select only the unit whose probe kernel evaluates the scene, as in rm_mesh_extract.
+ *   1. Sample, count, scan, emit: rm_mesh_extract's.
+ *   2. Crossings.  A vertex has 12 slots, its cell's edges in the mesher's order (axis a = x, y, z; offsets (0,0), (1,0), (0,1), (1,1)).  A slot
+ *      is LIVE iff its edge's ends differ in `inside` and then holds a bracket (x0, e0, x1, e1): the ends' coordinates along a and their
+ *      v - iso.  `refine` times:  xm = x0 + 0.5f * (x1 - x0);  em = sdf(the edge's point with xm along a) - iso;  if (em < 0) == (e0 < 0) then
+ *      (x0, e0) = (xm, em) else (x1, e1) = (xm, em)  (a NaN is outside, as in the mesher).  Then  t = e0 / (e0 - e1);  if !(t >= 0 && t <= 1)
+ *      t = 0.5f;  the crossing lies at  x0 + t * (x1 - x0)  along a (difference, product, sum), its other coordinates are the edge's.  sdf is
+ *      rm_probe's RM_PROBE_SDF launch with params.flags over all slots at once, one launch per round; a dead slot holds the cell's
+ *      surface-nets vertex, so that the probes evaluate a defined point, and contributes nothing.  With refine == 0 the crossings are the
+ *      mesher's own.
+ *   3. Mass point.  c = the live crossings summed per component, sequentially in slot order, each sum divided by (float)m, m = their number.
+ *   4. Normals.  One RM_PROBE_NORMAL launch with param = sharp.normal_delta and params.flags at the slots' points.  A live slot CONTRIBUTES
+ *      iff its normal's three components are finite and not all zero.
+ *   5. QEF.  With d = p - c per contributing slot (p its crossing, n its normal), sequentially in slot order:  A = sum n n^T  as six sums
+ *      a00 += nx nx, a01 += nx ny, a02 += nx nz, a11 += ny ny, a12 += ny nz, a22 += nz nz  and  b += n * nd,  nd = (nx dx + ny dy) + nz dz.
+ *      Eigenvectors by cyclic Jacobi: V = I, then 5 sweeps over the pairs (p, q) = (0,1), (0,2), (1,2), r the third index; a pair with
+ *      a_pq == 0 is skipped, otherwise
+ *        theta = (a_qq - a_pp) / (2 a_pq);   t = copysign(1, theta) / (|theta| + sqrt(theta theta + 1));
+ *        cr = 1 / sqrt(t t + 1);   sr = t cr;   h = t a_pq;
+ *        a_pp = a_pp - h;   a_qq = a_qq + h;   a_pq = 0;
+ *        (a_rp, a_rq) = (cr a_rp - sr a_rq,  sr a_rp + cr a_rq)      -- both from the old pair, each product rounded, then the sum
+ *        (v_kp, v_kq) = (cr v_kp - sr v_kq,  sr v_kp + cr v_kq)      for the rows k = 0, 1, 2 of V
+ *      lambda_i = a_ii, its vector column i of V.  lmax = lambda_0; if (lambda_1 > lmax) lmax = lambda_1; likewise lambda_2.  Pair i is KEPT
+ *      iff lambda_i > 0 and lambda_i > threshold * lmax.  o = 0; for i = 0, 1, 2, if kept:  w = ((v_0i b_0 + v_1i b_1) + v_2i b_2) / lambda_i,
+ *      o_k = o_k + v_ki w.  x = c + o.  If no slot contributes or a component of x is not finite, x = c.  Finally each component is clamped
+ *      to its cell's own corner coordinates (if x < lo then lo; if x > hi then hi): a vertex never leaves its cell, so the connectivity stays valid.
+ * The scratch is 12 slots of (bracket, point, probe output) per vertex and a mask word, freed before the call returns; a failed allocation
+ * is RM_ERR_DEVICE with nothing leaked, and so is a mesh with 12 V > INT_MAX (the probe's count is an int).  The time of steps 2-5 is added
+ * to the meshing slot of rm_mesh_timings.  RM_ERR_INVALID, in this order: everything rm_mesh_extract refuses before the handles are looked
+ * at; at that same point refine outside 0..16, a normal_delta that is not finite or <= 0, a threshold that is not finite or outside [0, 1),
+ * reserved != 0; then NULL handles or outputs and a scene of another context. */
+typedef struct RmMeshSharp { int32_t refine; float normal_delta; float threshold; int32_t reserved; } RmMeshSharp; /* 16 bytes */
+RM_API void rm_mesh_sharp_default(RmMeshSharp* sharp);
+RM_API int rm_mesh_extract_sharp(rm_ctx* ctx, rm_scene* scene, const RmGrid* grid, const RmMeshParams* params, const RmMeshSharp* sharp, rm_mesh** out);
 
 #ifdef __cplusplus
 }

@@ -250,3 +250,19 @@ class RmMeshParams(C.Structure):
 MESH_DEFAULTS = dict(iso=0.0, normals=1, normal_delta=1e-5, colours=0, flags=0)  # rm_mesh_params_default
 
 assert C.sizeof(RmGrid) == 40 and C.sizeof(RmMeshParams) == 24
+
+
+class RmMeshSharp(C.Structure):
+    """Parameters of rm_mesh_extract_sharp (ABI 9): the bisection rounds of an edge crossing, the step of the normals at the crossings and the
+    relative eigenvalue below which the QEF is truncated (include/hip_raymarch.h "sharp vertices")."""
+    _fields_ = [
+        ("refine", C.c_int32),
+        ("normal_delta", C.c_float),
+        ("threshold", C.c_float),
+        ("reserved", C.c_int32),
+    ]
+
+
+MESH_SHARP_DEFAULTS = dict(refine=6, normal_delta=2.0 ** -10, threshold=0.1)  # rm_mesh_sharp_default
+
+assert C.sizeof(RmMeshSharp) == 16

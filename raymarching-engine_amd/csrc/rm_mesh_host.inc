@@ -78,8 +78,10 @@ void rm_mesh_params_default(RmMeshParams* params) {
 }
 
 // The marks between the stages of an extraction, on the context's stream (timing events the context keeps): 0 | sampler | 1 | count, scan | 2
-// ... the totals come to the host, the arrays are allocated ... 3 | emit | 4, 5 | normals, colours | 6.
-enum { MESH_MARK_BEGIN, MESH_MARK_SAMPLED, MESH_MARK_SCANNED, MESH_MARK_EMIT, MESH_MARK_EMITTED, MESH_MARK_ATTRIBUTES, MESH_MARK_END };
+// ... the totals come to the host, the arrays are allocated ... 3 | emit | 4, 5 | normals, colours | 6.  rm_mesh_extract_sharp has, between 4
+// and 5 and behind the allocation of its scratch, 7 | crossings, rounds, normals, QEF | 8.
+enum { MESH_MARK_BEGIN, MESH_MARK_SAMPLED, MESH_MARK_SCANNED, MESH_MARK_EMIT, MESH_MARK_EMITTED, MESH_MARK_ATTRIBUTES, MESH_MARK_END, MESH_MARK_SHARPEN,
+       MESH_MARK_SHARPENED, MESH_MARKS };
 static hipError_t mesh_mark(rm_ctx* ctx, int k) {
   if (!ctx->mesh_ev[k]) {
     const hipError_t e = hipEventCreate(&ctx->mesh_ev[k]);
@@ -228,12 +230,67 @@ static int mesh_attributes(rm_ctx* ctx, rm_scene* scene, const RmMeshParams& p, 
   return RM_OK;
 }
 
-int rm_mesh_extract(rm_ctx* ctx, rm_scene* scene, const RmGrid* grid, const RmMeshParams* params, rm_mesh** out) {
-  const char* who = "rm_mesh_extract";
+// Sharp vertices (the header's "sharp vertices"): the emitted mesh's positions become the QEF's.  Per vertex 12 slots of bracket, point and
+// probe output, owned here and gone when this returns; the scene is evaluated by the probe kernel on the slot arrays, one launch per round
+// and one for the normals.  Waits for the stream: the scratch is freed behind the last kernel that reads it.
+static int mesh_sharpen(rm_ctx* ctx, rm_scene* scene, const GridDims& G, const float* d_values, const RmMeshParams& p, const RmMeshSharp& sharp, rm_mesh* mesh,
+                        const char* who) {
+  if (mesh->vertices > (unsigned long long)INT_MAX / 12ull)
+    return fail(ctx, RM_ERR_DEVICE, std::string(who) + ": the mesh has more vertices than the probe's int count holds twelve slots of (12 V > INT_MAX)");
+  const size_t slots = 12u * (size_t)mesh->vertices;
+  MeshBuffer state, points, probed, live;
+  RM_HIP(ctx, state.reserve(sizeof(float4) * slots));
+  RM_HIP(ctx, points.reserve(sizeof(float) * 3u * slots));
+  RM_HIP(ctx, probed.reserve(sizeof(float) * 3u * slots));
+  RM_HIP(ctx, live.reserve(sizeof(unsigned int) * (size_t)mesh->vertices));
+  MeshSharpParams P{};
+  P.mesh = MeshParams{G, d_values, p.iso, nullptr, static_cast<float*>(mesh->array[RM_MESH_POSITIONS]), static_cast<unsigned int*>(mesh->array[RM_MESH_CELLS]), nullptr};
+  P.vertices = (int)mesh->vertices;
+  P.state = static_cast<float4*>(state.p);
+  P.points = points.f32();
+  P.probed = probed.f32();
+  P.live = live.u32();
+  P.threshold = sharp.threshold;
+  RM_HIP(ctx, mesh_mark(ctx, MESH_MARK_SHARPEN));
+  RM_HIP(ctx, rm::launch_mesh_cross(P, 1, 0, sharp.refine == 0, ctx->stream));
+  for (int round = 0; round < sharp.refine; round++) {
+    RM_HIP(ctx, probe_enqueue(ctx, scene, RM_PROBE_SDF, points.f32(), probed.f32(), (int)slots, 0.0f, p.flags, ctx->stream));
+    RM_HIP(ctx, rm::launch_mesh_cross(P, 0, 1, round == sharp.refine - 1, ctx->stream));
+  }
+  RM_HIP(ctx, probe_enqueue(ctx, scene, RM_PROBE_NORMAL, points.f32(), probed.f32(), (int)slots, sharp.normal_delta, p.flags, ctx->stream));
+  RM_HIP(ctx, rm::launch_mesh_qef(P, ctx->stream));
+  RM_HIP(ctx, mesh_mark(ctx, MESH_MARK_SHARPENED));
+  RM_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  mesh->ms[1] += mesh_between(ctx, MESH_MARK_SHARPEN, MESH_MARK_SHARPENED);
+  return RM_OK;
+}
+
+void rm_mesh_sharp_default(RmMeshSharp* sharp) {
+  if (!sharp) return;
+  *sharp = RmMeshSharp{6, 0x1p-10f, 0.1f, 0};
+}
+
+static int mesh_sharp_check(rm_ctx* ctx, const RmMeshSharp* in, const char* who, RmMeshSharp* s) {
+  auto refuse = [&](const char* what) { return fail(ctx, RM_ERR_INVALID, std::string(who) + ": " + what); };
+  rm_mesh_sharp_default(s);
+  if (in) *s = *in;
+  if (s->refine < 0 || s->refine > 16) return refuse("sharp refine must be in 0..16");
+  if (!(std::isfinite(s->normal_delta) && s->normal_delta > 0.0f)) return refuse("sharp normal_delta must be finite and > 0");
+  if (!(std::isfinite(s->threshold) && s->threshold >= 0.0f && s->threshold < 1.0f)) return refuse("sharp threshold must be finite and in [0, 1)");
+  if (s->reserved != 0) return refuse("sharp reserved must be 0");
+  return RM_OK;
+}
+
+// rm_mesh_extract and rm_mesh_extract_sharp: `sharpen` tells them apart, `sharp` (NULL = the defaults) is looked at only with it
+static int mesh_extract(rm_ctx* ctx, rm_scene* scene, const RmGrid* grid, const RmMeshParams* params, bool sharpen, const RmMeshSharp* sharp, rm_mesh** out,
+                        const char* who) {
   GridDims G{};
   RmMeshParams p;
+  RmMeshSharp s{};
   if (int rc = grid_check(ctx, grid, who, &G)) return rc;
   if (int rc = mesh_params_check(ctx, params, who, &p)) return rc;
+  if (sharpen)
+    if (int rc = mesh_sharp_check(ctx, sharp, who, &s)) return rc;
   if (!ctx || !scene || !out) return fail(ctx, RM_ERR_INVALID, std::string(who) + ": NULL argument");
   if (scene->ctx != ctx) return fail(ctx, RM_ERR_INVALID, std::string(who) + ": the scene belongs to another context");
   *out = nullptr;
@@ -248,6 +305,7 @@ int rm_mesh_extract(rm_ctx* ctx, rm_scene* scene, const RmGrid* grid, const RmMe
   mesh->has[RM_MESH_NORMALS] = p.normals != 0;
   mesh->has[RM_MESH_COLOURS] = p.colours != 0;
   int rc = mesh_build(ctx, G, values.f32(), p.iso, mesh);
+  if (rc == RM_OK && sharpen && mesh->vertices > 0) rc = mesh_sharpen(ctx, scene, G, values.f32(), p, s, mesh, who);
   const bool attributes = rc == RM_OK && mesh->vertices > 0 && (p.normals || p.colours);
   if (attributes) rc = mesh_attributes(ctx, scene, p, mesh, material);
   if (rc == RM_OK && hipStreamSynchronize(ctx->stream) != hipSuccess) rc = fail(ctx, RM_ERR_DEVICE, std::string(who) + ": the stream failed");
@@ -256,6 +314,14 @@ int rm_mesh_extract(rm_ctx* ctx, rm_scene* scene, const RmGrid* grid, const RmMe
   if (attributes) mesh->ms[2] = mesh_between(ctx, MESH_MARK_ATTRIBUTES, MESH_MARK_END);
   *out = mesh;
   return RM_OK;
+}
+
+int rm_mesh_extract(rm_ctx* ctx, rm_scene* scene, const RmGrid* grid, const RmMeshParams* params, rm_mesh** out) {
+  return mesh_extract(ctx, scene, grid, params, false, nullptr, out, "rm_mesh_extract");
+}
+
+int rm_mesh_extract_sharp(rm_ctx* ctx, rm_scene* scene, const RmGrid* grid, const RmMeshParams* params, const RmMeshSharp* sharp, rm_mesh** out) {
+  return mesh_extract(ctx, scene, grid, params, true, sharp, out, "rm_mesh_extract_sharp");
 }
 
 int rm_mesh_counts(const rm_mesh* mesh, unsigned long long* out2) {

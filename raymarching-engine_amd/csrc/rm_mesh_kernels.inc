@@ -1,5 +1,6 @@
 // Mesh extraction (include/hip_raymarch.h "mesh extraction"): a scene's distance on a grid of corners, in this unit's arithmetic,
-// and -- in the strict unit only, it has no arithmetic of a policy's own -- the surface-nets mesher over such a grid.  Included by
+// and -- in the strict unit only, they have no arithmetic of a policy's own -- the surface-nets mesher over such a grid and the two
+// kernels that move its vertices to their cells' QEF minimisers (rm_mesh_extract_sharp).  Included by
 // rm_strict.hip / rm_fast.hip / rm_glstack.hip behind rm_kernels.inc.
 namespace rm {
 
@@ -186,6 +187,164 @@ __global__ __launch_bounds__(256) void rm_mesh_take3_kernel(const float* materia
   if (i < n3) colours[i] = material[(i / 3) * 12 + i % 3];
 }
 
+// ---- sharp vertices: dual contouring over the emitted mesh (include/hip_raymarch.h "sharp vertices") ----------------------------------
+// One thread per vertex, the cell through RM_MESH_CELLS.  The scene is evaluated by the probe kernel between these launches (rm_mesh_host.inc
+// mesh_sharpen); these two only prepare its input and consume its output, in this unit's plain fp32: every operation rounded on its own.
+
+// The 12 slots of a vertex: a slot is live iff its edge's ends differ in `inside`, and then carries a bracket (x0, e0, x1, e1) along its axis.
+// init: the bracket is the edge itself, and a dead slot's point becomes the surface-nets vertex.  consume: the probe's value at the bracket's
+// midpoint replaces the end it agrees with in `inside`.  last: the point is the bracket's linear crossing and the live mask is written;
+// otherwise the point is the bracket's midpoint, for the next round, and the bracket is kept.
+__global__ __launch_bounds__(256) void rm_mesh_cross_kernel(const MeshSharpParams P, int init, int consume, int last) {
+  const int v = blockIdx.x * blockDim.x + threadIdx.x;
+  if (v >= P.vertices) return;
+  const size_t V = (size_t)P.vertices;
+  const GridDims& g = P.mesh.grid;
+  const MeshCell c = mesh_cell(P.mesh, (int)P.mesh.cells[v]);
+  float pc[3][2];
+#pragma unroll
+  for (int a = 0; a < 3; a++) { pc[a][0] = rm_grid_coord(g, a, c.idx[a]); pc[a][1] = rm_grid_coord(g, a, c.idx[a] + 1); }
+  float nets[3] = {0.0f, 0.0f, 0.0f};
+  if (init) { nets[0] = P.mesh.positions[3 * (size_t)v]; nets[1] = P.mesh.positions[3 * (size_t)v + 1]; nets[2] = P.mesh.positions[3 * (size_t)v + 2]; }
+  unsigned int live = 0u;
+#pragma unroll
+  for (int a = 0; a < 3; a++) {
+    const int b = (a + 1) % 3, cc = (a + 2) % 3;
+#pragma unroll
+    for (int o = 0; o < 4; o++) {
+      const int ob = o & 1, oc = o >> 1, k0 = (ob << b) | (oc << cc), k1 = k0 | (1 << a);
+      const size_t at = (size_t)(4 * a + o) * V + (size_t)v;
+      float* point = P.points + 3 * at;
+      if ((((c.inside >> k0) ^ (c.inside >> k1)) & 1u) == 0u) {
+        if (init) { point[0] = nets[0]; point[1] = nets[1]; point[2] = nets[2]; }
+        continue;
+      }
+      live |= 1u << (4 * a + o);
+      float x0, e0, x1, e1;
+      if (init) {
+        x0 = pc[a][0]; e0 = c.e[k0]; x1 = pc[a][1]; e1 = c.e[k1];
+      } else {
+        const float4 s = P.state[at];
+        x0 = s.x; e0 = s.y; x1 = s.z; e1 = s.w;
+      }
+      if (consume) {
+        const float half = 0.5f * (x1 - x0), xm = x0 + half;  // (the point this round's probe evaluated)
+        const float em = P.probed[at] - P.mesh.iso;
+        if ((em < 0.0f) == (e0 < 0.0f)) { x0 = xm; e0 = em; }
+        else { x1 = xm; e1 = em; }
+      }
+      float t = 0.5f;
+      if (last) {
+        t = e0 / (e0 - e1);
+        if (!(t >= 0.0f && t <= 1.0f)) t = 0.5f;
+      } else {
+        P.state[at] = make_float4(x0, e0, x1, e1);
+      }
+      const float span = x1 - x0, step = t * span;
+      float p[3];
+      p[a] = x0 + step;
+      p[b] = pc[b][ob];
+      p[cc] = pc[cc][oc];
+      point[0] = p[0]; point[1] = p[1]; point[2] = p[2];
+    }
+  }
+  if (last) P.live[v] = live;
+}
+
+// one Jacobi rotation of the pair (p, q) of a symmetric 3 x 3 matrix, r the third index, and of the columns p and q of V (the header's text)
+__device__ inline void mesh_jacobi(float& app, float& aqq, float& apq, float& arp, float& arq, float& v0p, float& v0q, float& v1p, float& v1q, float& v2p,
+                                   float& v2q) {
+  if (apq == 0.0f) return;
+  const float theta = (aqq - app) / (2.0f * apq);
+  const float t = copysignf(1.0f, theta) / (fabsf(theta) + sqrtf(theta * theta + 1.0f));
+  const float cr = 1.0f / sqrtf(t * t + 1.0f), sr = t * cr, h = t * apq;
+  app = app - h;
+  aqq = aqq + h;
+  apq = 0.0f;
+  const float rp = cr * arp - sr * arq, rq = sr * arp + cr * arq;
+  arp = rp; arq = rq;
+  const float w0p = cr * v0p - sr * v0q, w0q = sr * v0p + cr * v0q;
+  v0p = w0p; v0q = w0q;
+  const float w1p = cr * v1p - sr * v1q, w1q = sr * v1p + cr * v1q;
+  v1p = w1p; v1q = w1q;
+  const float w2p = cr * v2p - sr * v2q, w2q = sr * v2p + cr * v2q;
+  v2p = w2p; v2q = w2q;
+}
+
+// The vertex of the quadratic error function of the live slots' planes (point, normal), about their mass point, its small eigenvalues
+// truncated, kept inside the cell.  Everything is named scalars: the 3 x 3 state stays in registers.
+__global__ __launch_bounds__(256) void rm_mesh_qef_kernel(const MeshSharpParams P) {
+  const int v = blockIdx.x * blockDim.x + threadIdx.x;
+  if (v >= P.vertices) return;
+  const size_t V = (size_t)P.vertices;
+  const unsigned int live = P.live[v];
+  float sx = 0.0f, sy = 0.0f, sz = 0.0f;
+  int m = 0;
+#pragma unroll
+  for (int s = 0; s < 12; s++) {
+    if (!((live >> s) & 1u)) continue;
+    const float* p = P.points + 3 * ((size_t)s * V + (size_t)v);
+    sx += p[0]; sy += p[1]; sz += p[2];
+    m++;
+  }
+  const float fm = (float)m;
+  const float cx = sx / fm, cy = sy / fm, cz = sz / fm;
+  float a00 = 0.0f, a01 = 0.0f, a02 = 0.0f, a11 = 0.0f, a12 = 0.0f, a22 = 0.0f, b0 = 0.0f, b1 = 0.0f, b2 = 0.0f;
+  int planes = 0;
+#pragma unroll
+  for (int s = 0; s < 12; s++) {
+    if (!((live >> s) & 1u)) continue;
+    const size_t at = 3 * ((size_t)s * V + (size_t)v);
+    const float nx = P.probed[at], ny = P.probed[at + 1], nz = P.probed[at + 2];
+    if (!(isfinite(nx) && isfinite(ny) && isfinite(nz)) || (nx == 0.0f && ny == 0.0f && nz == 0.0f)) continue;
+    const float dx = P.points[at] - cx, dy = P.points[at + 1] - cy, dz = P.points[at + 2] - cz;
+    const float nd = nx * dx + ny * dy + nz * dz;
+    a00 += nx * nx; a01 += nx * ny; a02 += nx * nz; a11 += ny * ny; a12 += ny * nz; a22 += nz * nz;
+    b0 += nx * nd; b1 += ny * nd; b2 += nz * nd;
+    planes++;
+  }
+  float v00 = 1.0f, v01 = 0.0f, v02 = 0.0f, v10 = 0.0f, v11 = 1.0f, v12 = 0.0f, v20 = 0.0f, v21 = 0.0f, v22 = 1.0f;
+#pragma unroll
+  for (int sweep = 0; sweep < 5; sweep++) {
+    mesh_jacobi(a00, a11, a01, a02, a12, v00, v01, v10, v11, v20, v21);  // (0, 1), r = 2
+    mesh_jacobi(a00, a22, a02, a01, a12, v00, v02, v10, v12, v20, v22);  // (0, 2), r = 1
+    mesh_jacobi(a11, a22, a12, a01, a02, v01, v02, v11, v12, v21, v22);  // (1, 2), r = 0
+  }
+  float lmax = a00;
+  if (a11 > lmax) lmax = a11;
+  if (a22 > lmax) lmax = a22;
+  const float bar = P.threshold * lmax;
+  float ox = 0.0f, oy = 0.0f, oz = 0.0f;
+  if (a00 > 0.0f && a00 > bar) {
+    const float w = (v00 * b0 + v10 * b1 + v20 * b2) / a00;
+    ox += v00 * w; oy += v10 * w; oz += v20 * w;
+  }
+  if (a11 > 0.0f && a11 > bar) {
+    const float w = (v01 * b0 + v11 * b1 + v21 * b2) / a11;
+    ox += v01 * w; oy += v11 * w; oz += v21 * w;
+  }
+  if (a22 > 0.0f && a22 > bar) {
+    const float w = (v02 * b0 + v12 * b1 + v22 * b2) / a22;
+    ox += v02 * w; oy += v12 * w; oz += v22 * w;
+  }
+  float x = cx + ox, y = cy + oy, z = cz + oz;
+  if (planes == 0 || !(isfinite(x) && isfinite(y) && isfinite(z))) { x = cx; y = cy; z = cz; }
+  const GridDims& g = P.mesh.grid;
+  const int cells_x = g.nc[0] - 1, cells_y = g.nc[1] - 1, cell = (int)P.mesh.cells[v];
+  const int i = cell % cells_x, j = (cell / cells_x) % cells_y, k = cell / (cells_x * cells_y);
+  const float lx = rm_grid_coord(g, 0, i), hx = rm_grid_coord(g, 0, i + 1), ly = rm_grid_coord(g, 1, j), hy = rm_grid_coord(g, 1, j + 1);
+  const float lz = rm_grid_coord(g, 2, k), hz = rm_grid_coord(g, 2, k + 1);
+  if (x < lx) x = lx;
+  if (x > hx) x = hx;
+  if (y < ly) y = ly;
+  if (y > hy) y = hy;
+  if (z < lz) z = lz;
+  if (z > hz) z = hz;
+  P.mesh.positions[3 * (size_t)v] = x;
+  P.mesh.positions[3 * (size_t)v + 1] = y;
+  P.mesh.positions[3 * (size_t)v + 2] = z;
+}
+
 #ifndef RM_ONLY_KERNELS
 static inline long long mesh_cells(const GridDims& g) { return (long long)(g.nc[0] - 1) * (g.nc[1] - 1) * (g.nc[2] - 1); }
 
@@ -226,6 +385,16 @@ hipError_t launch_mesh_scan(unsigned long long* counts, long long cells, unsigne
 
 hipError_t launch_mesh_colours(const float* material, float* colours, long long vertices, hipStream_t stream) {
   hipLaunchKernelGGL(rm_mesh_take3_kernel, dim3((unsigned int)((3 * vertices + 255) / 256)), dim3(256), 0, stream, material, colours, 3 * vertices);
+  return hipGetLastError();
+}
+
+hipError_t launch_mesh_cross(const MeshSharpParams& P, int init, int consume, int last, hipStream_t stream) {
+  hipLaunchKernelGGL(rm_mesh_cross_kernel, dim3((unsigned int)((P.vertices + 255) / 256)), dim3(256), 0, stream, P, init, consume, last);
+  return hipGetLastError();
+}
+
+hipError_t launch_mesh_qef(const MeshSharpParams& P, hipStream_t stream) {
+  hipLaunchKernelGGL(rm_mesh_qef_kernel, dim3((unsigned int)((P.vertices + 255) / 256)), dim3(256), 0, stream, P);
   return hipGetLastError();
 }
 

@@ -321,6 +321,18 @@ struct MeshParams {
   unsigned int* cells;         // emit: V
   unsigned int* triangles;     // emit: T x 3
 };
+// The sharp vertices of rm_mesh_extract_sharp over an emitted mesh: 12 slots per vertex, the cell's edges in the mesher's order.  Slot s of
+// vertex v lies at s * vertices + v in every slot array, so a wave's accesses to one slot are one run.  mesh.positions holds the surface-nets
+// vertices on the way in (the point of a dead slot) and the QEF's on the way out; mesh.counts and mesh.triangles are not used.
+struct MeshSharpParams {
+  MeshParams mesh;
+  int vertices;
+  float4* state;        // 12 V: (x0, e0, x1, e1) of a live slot's bracket
+  float* points;        // 12 V x 3: what the probes evaluate -- a round's midpoints, at the end the crossings
+  const float* probed;  // 12 V x 3 floats of room: a round's RM_PROBE_SDF output (12 V floats), then the RM_PROBE_NORMAL output
+  unsigned int* live;   // V: bit s = slot s is live
+  float threshold;
+};
 
 // One pass of the denoiser (rm_frame_kernels.inc "denoise").  Pass 0 reads color / normal_dof / albedo_depth and writes
 // guide; later passes read x_in and guide; the last pass reads color (.w) and albedo_depth (the modulation) again.
@@ -450,6 +462,10 @@ hipError_t launch_mesh_count(const MeshParams& P, hipStream_t stream);
 hipError_t launch_mesh_scan(unsigned long long* counts, long long cells, unsigned long long* scratch, unsigned long long* total, hipStream_t stream);
 hipError_t launch_mesh_emit(const MeshParams& P, hipStream_t stream);
 hipError_t launch_mesh_colours(const float* material, float* colours, long long vertices, hipStream_t stream);  // 12 floats per vertex -> the first 3
+// rm_mesh_extract_sharp's two kernels.  cross: `init` makes the brackets from the corner values (else they are read), `consume` takes a round's
+// probe output in, `last` writes the crossings and the live mask (else the next round's midpoints and the brackets).  qef: the vertex positions.
+hipError_t launch_mesh_cross(const MeshSharpParams& P, int init, int consume, int last, hipStream_t stream);
+hipError_t launch_mesh_qef(const MeshSharpParams& P, hipStream_t stream);
 hipError_t launch_camera_rng(const RmUniforms& u, int W, int H, int what, int count, float* out, hipStream_t stream);
 hipError_t launch_math_probe(int fn, const float* a, const float* b, int n, float* out, hipStream_t stream);
 }  // namespace rm

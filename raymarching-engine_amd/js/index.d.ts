@@ -115,6 +115,8 @@ export class RenderJobContext {
   sdfGrid(scene: Scene, grid: MeshGrid, flags?: number): Float32Array;
   /** the level set `iso` of the scene on the grid as triangles (rm_mesh_extract: sampled and meshed with surface nets on the GPU) */
   extractMesh(scene: Scene, grid: MeshGrid, params?: MeshParams | null): Mesh;
+  /** with `sharp` (true = the defaults): rm_mesh_extract_sharp, the same triangles with every vertex at its cell's QEF minimiser, so hard edges and corners stay sharp */
+  extractMesh(scene: Scene, grid: MeshGrid, params: MeshParams | null | undefined, sharp: MeshSharp | true | null): Mesh;
   /** the mesher alone on the caller's field (rm_mesh_from_values) */
   meshFromValues(grid: MeshGrid, values: Float32Array, iso?: number): Mesh;
   close(): void;
@@ -152,5 +154,9 @@ export interface Mesh { positions: Float32Array; normals: Float32Array | null; c
 export const MESH_DEFAULTS: { iso: number; normals: 0 | 1; normalDelta: number; colours: 0 | 1; flags: number };
 export function meshGrid(lo: number[], hi: number[], n: number[]): MeshGrid;
 export function meshParams(params?: MeshParams | null): { iso: number; normals: 0 | 1; normalDelta: number; colours: 0 | 1; flags: number };
+/** the sharp block of extractMesh (RmMeshSharp): bisection rounds per edge crossing (0..16), the step of the normals at the crossings (> 0), the relative eigenvalue below which the QEF is truncated ([0, 1)) */
+export interface MeshSharp { refine?: number; normalDelta?: number; threshold?: number }
+export const MESH_SHARP_DEFAULTS: { refine: number; normalDelta: number; threshold: number };
+export function meshSharp(sharp?: MeshSharp | null): { refine: number; normalDelta: number; threshold: number };
 /** binary little-endian PLY (normals and uchar colours when present): the bytes the Python host's write_ply writes */
 export function encodePly(mesh: { positions: Float32Array; triangles: Uint32Array; normals?: Float32Array | null; colours?: Float32Array | null }): Buffer;

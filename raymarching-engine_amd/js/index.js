@@ -354,7 +354,12 @@ class RenderJobContext {  // RenderJobContext + loadRenderJobContext (LoadRender
     return out;
   }
   // the level set opts.iso as { positions, normals | null, colours | null, triangles, cells } (rm_mesh_extract); opts: meshParams'
-  extractMesh(scene, grid, opts) { return addon.extractMesh(this.ctx, this.sceneHandle(scene), grid, meshParams(opts)); }
+  // sharp: undefined / null = that call; true or meshSharp's options = rm_mesh_extract_sharp, the same triangles with each vertex at its cell's
+  // QEF minimiser (hard edges and corners stay sharp)
+  extractMesh(scene, grid, opts, sharp) {
+    if (sharp === undefined || sharp === null) return addon.extractMesh(this.ctx, this.sceneHandle(scene), grid, meshParams(opts));
+    return addon.extractMesh(this.ctx, this.sceneHandle(scene), grid, meshParams(opts), meshSharp(sharp === true ? undefined : sharp));
+  }
   // the mesher alone on the caller's field: values Float32Array of the grid's corners, x fastest (rm_mesh_from_values)
   meshFromValues(grid, values, iso = 0) {
     if (!(values instanceof Float32Array)) throw new TypeError("meshFromValues: values must be a Float32Array");
@@ -645,6 +650,23 @@ function meshParams(opts) {
   if (!Number.isInteger(p.flags) || (p.flags & ~(RM.RENDER_FAST | RM.RENDER_NO_CULL)) !== 0) throw new RangeError("mesh: flags must be 0, RM.RENDER_FAST, RM.RENDER_NO_CULL or both");
   return p;
 }
+// the sharp block of extractMesh (include/hip_raymarch.h RmMeshSharp): undefined / null = the defaults, or an object with some of refine,
+// normalDelta, threshold; checked as the library checks it; returns { refine, normalDelta, threshold }
+const MESH_SHARP_DEFAULTS = { refine: 6, normalDelta: 2 ** -10, threshold: 0.1 };
+function meshSharp(opts) {
+  const p = { ...MESH_SHARP_DEFAULTS };
+  if (opts !== undefined && opts !== null) {
+    if (typeof opts !== "object") throw new TypeError("mesh: expected an object of sharp parameters");
+    for (const [k, v] of Object.entries(opts)) {
+      if (!(k in MESH_SHARP_DEFAULTS)) throw new TypeError("mesh: unknown sharp parameter " + k);
+      p[k] = v;
+    }
+  }
+  if (!Number.isInteger(p.refine) || p.refine < 0 || p.refine > 16) throw new RangeError("mesh: sharp refine must be an integer in 0..16");
+  if (!POSITIVE[0](p.normalDelta) || !POSITIVE[0](Math.fround(p.normalDelta))) throw new RangeError("mesh: sharp normalDelta " + POSITIVE[1]);
+  if (!finite(p.threshold) || !(Math.fround(p.threshold) >= 0 && Math.fround(p.threshold) < 1)) throw new RangeError("mesh: sharp threshold must be finite and in [0, 1)");
+  return p;
+}
 // binary little-endian PLY of { positions, triangles, normals?, colours? }: x y z, then nx ny nz, then uchar red green blue
 // (floor(clamp(c, 0, 1) * 255 + 0.5), NaN as 0); faces as a uchar count and uint indices -- the bytes the Python host writes
 function encodePly(mesh) {
@@ -696,4 +718,4 @@ function encodePng(rgba, width, height, bottomUp = true) {
 module.exports = { RM, addon, encodePng, Scene, CsgScene, Mandelbulb, singleSphere, DEFAULT_MATERIAL, halton, resetHalton, uniformsFromSchema, packUniforms,
                    tileRect, RenderJobContext, ShardedRenderJobContext, doRenderJob, U_OFFSET, DENOISE_DEFAULTS, denoiseParams,
                    DENOISE_VARIANCE_DEFAULTS, denoiseVarianceParams, DESPECKLE_DEFAULTS, despeckleParams, DISPLAY_DEFAULTS, AUTO_EXPOSURE_DEFAULTS,
-                   displayParams, statsExposure, statsPercentile, MESH_DEFAULTS, meshGrid, meshParams, encodePly };
+                   displayParams, statsExposure, statsPercentile, MESH_DEFAULTS, meshGrid, meshParams, MESH_SHARP_DEFAULTS, meshSharp, encodePly };

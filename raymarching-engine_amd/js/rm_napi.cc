@@ -482,6 +482,32 @@ static bool get_mesh_params(napi_env env, napi_value v, RmMeshParams* p) {
   return get_block(env, v, p, MESH_FIELDS);
 }
 
+static const Field MESH_SHARP_FIELDS[] = {{"refine", Field::INT, offsetof(RmMeshSharp, refine)}, {"normalDelta", Field::FLOAT, offsetof(RmMeshSharp, normal_delta)},
+                                          {"threshold", Field::FLOAT, offsetof(RmMeshSharp, threshold)}};
+// the sharp block of extractMesh: null / undefined = none (*given = false), an object = rm_mesh_extract_sharp with its fields over the defaults
+static bool get_mesh_sharp(napi_env env, napi_value v, RmMeshSharp* s, bool* given) {
+  rm_mesh_sharp_default(s);
+  return get_block(env, v, s, MESH_SHARP_FIELDS, given);
+}
+
+// meshSharpBlock(sharp | null) -> ArrayBuffer(RmMeshSharp): the bytes extractMesh hands to the library (null: the defaults)
+static napi_value MeshSharpBlock(napi_env env, napi_callback_info info) {
+  size_t argc = 1;
+  napi_value argv[1];
+  NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+  RmMeshSharp s;
+  bool given = false;
+  if (argc != 1 || !get_mesh_sharp(env, argv[0], &s, &given)) {
+    napi_throw_type_error(env, nullptr, "meshSharpBlock(sharp | null)");
+    return nullptr;
+  }
+  napi_value b;
+  void* d = nullptr;
+  NAPI_OK(napi_create_arraybuffer(env, sizeof s, &d, &b));
+  std::memcpy(d, &s, sizeof s);
+  return b;
+}
+
 static napi_value make_array(napi_env env, napi_typedarray_type type, size_t count, void** data) {
   napi_value ab, out;
   if (napi_create_arraybuffer(env, count * 4, data, &ab) != napi_ok || napi_create_typedarray(env, type, count, ab, 0, &out) != napi_ok) return nullptr;
@@ -584,21 +610,26 @@ static napi_value mesh_result(napi_env env, rm_ctx* ctx, rm_mesh* mesh, bool nor
   return o;
 }
 
-// extractMesh(ctx, scene, grid, params | null) = rm_mesh_extract, then the arrays
+// extractMesh(ctx, scene, grid, params | null[, sharp | null]) = rm_mesh_extract, or with a sharp block rm_mesh_extract_sharp; then the arrays
 static napi_value ExtractMesh(napi_env env, napi_callback_info info) {
-  size_t argc = 4;
-  napi_value argv[4];
+  size_t argc = 5;
+  napi_value argv[5];
   NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
-  rm_ctx* ctx = argc == 4 ? get_external<rm_ctx>(env, argv[0]) : nullptr;
-  rm_scene* scene = argc == 4 ? get_external<rm_scene>(env, argv[1]) : nullptr;
+  const bool counted = argc == 4 || argc == 5;
+  rm_ctx* ctx = counted ? get_external<rm_ctx>(env, argv[0]) : nullptr;
+  rm_scene* scene = counted ? get_external<rm_scene>(env, argv[1]) : nullptr;
   RmGrid g;
   RmMeshParams p;
-  if (!ctx || !scene || !get_grid(env, argv[2], &g) || !get_mesh_params(env, argv[3], &p)) {
-    napi_throw_type_error(env, nullptr, "extractMesh(ctx, scene, grid, params | null)");
+  RmMeshSharp s;
+  bool sharp = false;
+  if (!ctx || !scene || !get_grid(env, argv[2], &g) || !get_mesh_params(env, argv[3], &p) || (argc == 5 && !get_mesh_sharp(env, argv[4], &s, &sharp))) {
+    napi_throw_type_error(env, nullptr, "extractMesh(ctx, scene, grid, params | null[, sharp | null])");
     return nullptr;
   }
   rm_mesh* mesh = nullptr;
-  if (rm_mesh_extract(ctx, scene, &g, &p, &mesh) != RM_OK) return throw_rm(env, ctx, "rm_mesh_extract");
+  if (sharp) {
+    if (rm_mesh_extract_sharp(ctx, scene, &g, &p, &s, &mesh) != RM_OK) return throw_rm(env, ctx, "rm_mesh_extract_sharp");
+  } else if (rm_mesh_extract(ctx, scene, &g, &p, &mesh) != RM_OK) return throw_rm(env, ctx, "rm_mesh_extract");
   return mesh_result(env, ctx, mesh, p.normals != 0, p.colours != 0);
 }
 
@@ -823,7 +854,7 @@ static napi_value Sizes(napi_env env, napi_callback_info) {
       {"RmMaterial", (uint32_t)sizeof(RmMaterial)}, {"RmRect", (uint32_t)sizeof(RmRect)}, {"RmSurface", (uint32_t)sizeof(RmSurface)}, {"RmDenoise", (uint32_t)sizeof(RmDenoise)},
       {"RmDenoiseVariance", (uint32_t)sizeof(RmDenoiseVariance)}, {"RmDespeckle", (uint32_t)sizeof(RmDespeckle)}, {"RmFilters", (uint32_t)sizeof(RmFilters)}, {"RmFrameStats", (uint32_t)sizeof(RmFrameStats)},
       {"RmAutoExposure", (uint32_t)sizeof(RmAutoExposure)}, {"RmDisplay", (uint32_t)sizeof(RmDisplay)}, {"RmGrid", (uint32_t)sizeof(RmGrid)},
-      {"RmMeshParams", (uint32_t)sizeof(RmMeshParams)}, {"abi", (uint32_t)rm_abi_version()}};
+      {"RmMeshParams", (uint32_t)sizeof(RmMeshParams)}, {"RmMeshSharp", (uint32_t)sizeof(RmMeshSharp)}, {"abi", (uint32_t)rm_abi_version()}};
   for (const auto& it : items) {
     NAPI_OK(napi_create_uint32(env, it.v, &v));
     NAPI_OK(napi_set_named_property(env, o, it.k, v));
@@ -836,7 +867,7 @@ static napi_value Init(napi_env env, napi_value exports) {
       {"ctxCreate", CtxCreate}, {"ctxDestroy", CtxDestroy}, {"sync", Sync}, {"sceneCreate", SceneCreate}, {"sceneDestroy", SceneDestroy},
       {"fbCreate", FbCreate}, {"fbClear", FbClear}, {"fbDestroy", FbDestroy}, {"fbDownload", FbDownload}, {"present", Present}, {"denoise", Denoise}, {"presentDenoised", PresentDenoised}, {"denoiseVariance", DenoiseVariance}, {"presentDenoisedVariance", PresentDenoisedVariance}, {"filter", Filter}, {"presentFiltered", PresentFiltered}, {"presentDisplay", PresentDisplay}, {"presentLinear", PresentLinear}, {"frameStats", FrameStats}, {"statsExposure", StatsExposure}, {"statsPercentile", StatsPercentile}, {"renderSample", RenderSample}, {"renderSamples", RenderSamples},
       {"fbCreateStriped", FbCreateStriped}, {"fbRows", FbRows}, {"setSamplesInFlight", SetSamplesInFlight}, {"presentSharded", PresentSharded}, {"presentShardedStart", PresentShardedStart}, {"presentShardedFinish", PresentShardedFinish},
-      {"meshBlocks", MeshBlocks}, {"sdfGrid", SdfGrid}, {"extractMesh", ExtractMesh}, {"meshFromValues", MeshFromValues}, {"sizes", Sizes}};
+      {"meshBlocks", MeshBlocks}, {"meshSharpBlock", MeshSharpBlock}, {"sdfGrid", SdfGrid}, {"extractMesh", ExtractMesh}, {"meshFromValues", MeshFromValues}, {"sizes", Sizes}};
   for (const auto& f : fns) {
     napi_value fn;
     if (napi_create_function(env, f.name, NAPI_AUTO_LENGTH, f.fn, nullptr, &fn) != napi_ok) return nullptr;

@@ -74,6 +74,29 @@ def mesh_params(iso=0.0, normals=True, colours=False, flags=0, normal_delta=1e-5
     return abi.RmMeshParams(iso=float(iso), normals=int(normals), normal_delta=float(normal_delta), colours=int(colours), flags=int(flags), reserved=0)
 
 
+def mesh_sharp(**fields) -> abi.RmMeshSharp:
+    """The abi.RmMeshSharp of Context.extract_mesh(..., sharp=...), over abi.MESH_SHARP_DEFAULTS: refine (bisection rounds per edge crossing,
+    0..16), normal_delta (the step of the normals at the crossings, > 0) and threshold (eigenvalues at or below threshold * the largest are
+    dropped from the QEF, in [0, 1)).  Checked as the library checks it: ValueError otherwise, and for unknown keys."""
+    unknown = set(fields) - set(abi.MESH_SHARP_DEFAULTS)
+    if unknown:
+        raise ValueError(f"mesh: unknown sharp parameter {sorted(unknown)[0]}")
+    p = {**abi.MESH_SHARP_DEFAULTS, **fields}
+    refine = p["refine"]
+    if isinstance(refine, bool) or not isinstance(refine, (int, np.integer)) or not 0 <= int(refine) <= 16:
+        raise ValueError("mesh: sharp refine must be an integer in 0..16")
+    for name in ("normal_delta", "threshold"):
+        if isinstance(p[name], bool) or not isinstance(p[name], (int, float, np.integer, np.floating)):
+            raise ValueError(f"mesh: sharp {name} must be a number")
+    with np.errstate(over="ignore"):
+        delta, threshold = np.float32(p["normal_delta"]), np.float32(p["threshold"])
+    if not (math.isfinite(delta) and delta > 0):
+        raise ValueError("mesh: sharp normal_delta must be finite and > 0")
+    if not (math.isfinite(threshold) and 0 <= threshold < 1):
+        raise ValueError("mesh: sharp threshold must be finite and in [0, 1)")
+    return abi.RmMeshSharp(refine=int(refine), normal_delta=float(p["normal_delta"]), threshold=float(p["threshold"]), reserved=0)
+
+
 @dataclass
 class Mesh:
     """A triangle mesh as numpy arrays: positions [V, 3] float32, triangles [T, 3] uint32 (counter-clockwise seen from outside), cells

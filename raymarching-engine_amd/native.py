@@ -41,7 +41,7 @@ EXPORTS = [
     "rm_frame_stats", "rm_auto_exposure_default", "rm_stats_percentile", "rm_stats_exposure",
     "rm_display_default", "rm_present_display", "rm_present_display_device", "rm_present_linear",
     "rm_grid_axis", "rm_sdf_grid", "rm_sdf_grid_device", "rm_mesh_params_default", "rm_mesh_extract", "rm_mesh_from_values", "rm_mesh_counts", "rm_mesh_timings",
-    "rm_mesh_download", "rm_mesh_device_ptr", "rm_mesh_destroy",
+    "rm_mesh_download", "rm_mesh_device_ptr", "rm_mesh_destroy", "rm_mesh_sharp_default", "rm_mesh_extract_sharp",
 ]
 
 # G-buffer formats of a framebuffer (include/hip_raymarch.h RM_GBUFFER_*): "f32" (the default: the software GL stack's planes, which the
@@ -408,6 +408,8 @@ def load_library(path=None):
         "rm_mesh_download": (ip, [vp, ip, vp, C.c_size_t]),
         "rm_mesh_device_ptr": (vp, [vp, ip]),
         "rm_mesh_destroy": (None, [vp]),
+        "rm_mesh_sharp_default": (None, [C.POINTER(abi.RmMeshSharp)]),
+        "rm_mesh_extract_sharp": (ip, [vp, vp, C.POINTER(abi.RmGrid), C.POINTER(abi.RmMeshParams), C.POINTER(abi.RmMeshSharp), C.POINTER(vp)]),
     }
     for name, (res, args) in sig.items():
         if name.startswith("rm_debug_") and not hasattr(lib, name) and os.environ.get("RM_LIB"):
@@ -729,14 +731,28 @@ class Context:
             self.lib.rm_mesh_destroy(handle)
 
     def extract_mesh(self, scene: "SceneHandle", grid, iso: float = 0.0, normals: bool = True, colours: bool = False, flags: int = 0,
-                     normal_delta: float = 1e-5):
+                     normal_delta: float = 1e-5, sharp=None):
         """The level set `iso` of the scene on `grid` (mesh.Grid) as a mesh.Mesh: rm_mesh_extract -- the distances sampled and meshed
-        (surface nets) on the device, with per-vertex normals / diffuse colours from the scene's probes when asked for."""
-        from .mesh import mesh_params
+        (surface nets) on the device, with per-vertex normals / diffuse colours from the scene's probes when asked for.  `sharp`: None is
+        that call; True (the defaults), a dict of mesh.mesh_sharp's arguments or an abi.RmMeshSharp is rm_mesh_extract_sharp -- the same
+        triangles with every vertex at its cell's QEF minimiser, which keeps the edges and corners of hard-edged scenes."""
+        from .mesh import mesh_params, mesh_sharp
 
         g, p = grid.to_c(), mesh_params(iso=iso, normals=normals, colours=colours, flags=flags, normal_delta=normal_delta)
         h = C.c_void_p()
-        self._check(self.lib.rm_mesh_extract(self.h, scene.h, C.byref(g), C.byref(p), C.byref(h)))
+        if sharp is None:
+            self._check(self.lib.rm_mesh_extract(self.h, scene.h, C.byref(g), C.byref(p), C.byref(h)))
+        else:
+            if isinstance(sharp, abi.RmMeshSharp):
+                s = mesh_sharp(refine=sharp.refine, normal_delta=sharp.normal_delta, threshold=sharp.threshold)
+                s.reserved = sharp.reserved  # (the library's to refuse)
+            elif sharp is True:
+                s = mesh_sharp()
+            elif isinstance(sharp, dict):
+                s = mesh_sharp(**sharp)
+            else:
+                raise ValueError("mesh: sharp must be None, True, a dict of mesh_sharp's arguments or an abi.RmMeshSharp")
+            self._check(self.lib.rm_mesh_extract_sharp(self.h, scene.h, C.byref(g), C.byref(p), C.byref(s), C.byref(h)))
         return self._take_mesh(h, grid, normals=p.normals, colours=p.colours)
 
     def mesh_from_values(self, grid, values: np.ndarray, iso: float = 0.0):
