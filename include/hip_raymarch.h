@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define RM_ABI_VERSION 9 /* 9: RM_GBUFFER_F32 / _F16, rm_fb_create_fmt, rm_fb_create_striped_fmt, rm_fb_wrap_fmt, rm_fb_gbuffer, rm_fb_download_raw, rm_fb_upload_raw, RmDenoise, rm_denoise_default, rm_denoise, rm_denoise_device, rm_present_denoised, RM_FB_MOMENTS, RM_PLANE_MOMENTS, rm_fb_has_moments, RmDenoiseVariance, rm_denoise_variance_default, rm_denoise_variance, rm_denoise_variance_device, rm_present_denoised_variance, RmDespeckle, RmFilters, RM_DENOISE_NONE / _ATROUS / _VARIANCE, rm_filters_default, rm_filter, rm_filter_device, rm_present_filtered, RM_STATS_BINS, RmFrameStats, rm_frame_stats, RmAutoExposure, rm_auto_exposure_default, rm_stats_percentile, rm_stats_exposure, RM_TONE_CLIP / _REINHARD / _ACES, RmDisplay, rm_display_default, rm_present_display, rm_present_display_device, rm_present_linear, RmGrid, rm_grid_axis, rm_sdf_grid, rm_sdf_grid_device, RmMeshParams, rm_mesh_params_default, rm_mesh, rm_mesh_extract, rm_mesh_from_values, rm_mesh_counts, rm_mesh_timings, RM_MESH_POSITIONS / _NORMALS / _COLOURS / _TRIANGLES / _CELLS, rm_mesh_download, rm_mesh_device_ptr, rm_mesh_destroy, RmMeshSharp, rm_mesh_sharp_default, rm_mesh_extract_sharp (additions only); 8: RM_PRIM_TORUS / _CYLINDER / _PLANE, RM_OP_SMOOTH_SUBTRACT / _INTERSECT, rm_probe_math (additions only); 7: rm_present_sharded_finish / rm_present_sharded take the size of the host buffer (a changed signature), rm_ctx_set_cull_min_pixels, rm_ctx_set_cull_budget, rm_ctx_cull_stats; 6: rm_present_striped_rows, rm_present_sharded_start / _finish, rm_ctx_last_warning, RM_PROBE_CAST_SHADOW, RM_PRIM_KIND (additions only); 3: rm_ctx_set_sample_batch, rm_buffer_*; 4: rm_ctx_set_gl_stack; 5: RmSurface / RmSceneDesc.surfaces (the struct grew), rm_pack_present_rows, rm_present_sharded, rm_ctx_last_pipeline, RM_RENDER_NO_FAR_JUMP, RM_RENDER_NO_CULL (additions only) */
+#define RM_ABI_VERSION 9 /* 9: RM_GBUFFER_F32 / _F16, rm_fb_create_fmt, rm_fb_create_striped_fmt, rm_fb_wrap_fmt, rm_fb_gbuffer, rm_fb_download_raw, rm_fb_upload_raw, RmDenoise, rm_denoise_default, rm_denoise, rm_denoise_device, rm_present_denoised, RM_FB_MOMENTS, RM_PLANE_MOMENTS, rm_fb_has_moments, RmDenoiseVariance, rm_denoise_variance_default, rm_denoise_variance, rm_denoise_variance_device, rm_present_denoised_variance, RmDespeckle, RmFilters, RM_DENOISE_NONE / _ATROUS / _VARIANCE, rm_filters_default, rm_filter, rm_filter_device, rm_present_filtered, RM_STATS_BINS, RmFrameStats, rm_frame_stats, RmAutoExposure, rm_auto_exposure_default, rm_stats_percentile, rm_stats_exposure, RM_TONE_CLIP / _REINHARD / _ACES, RmDisplay, rm_display_default, rm_present_display, rm_present_display_device, rm_present_linear, RmGrid, rm_grid_axis, rm_sdf_grid, rm_sdf_grid_device, RmMeshParams, rm_mesh_params_default, rm_mesh, rm_mesh_extract, rm_mesh_from_values, rm_mesh_counts, rm_mesh_timings, RM_MESH_POSITIONS / _NORMALS / _COLOURS / _TRIANGLES / _CELLS, rm_mesh_download, rm_mesh_device_ptr, rm_mesh_destroy, RmMeshSharp, rm_mesh_sharp_default, rm_mesh_extract_sharp, RmMeshKeep, rm_mesh_keep_default, rm_mesh_components, RM_MESH_PART_LABELS / _SIZES, rm_mesh_components_download, rm_mesh_filter (additions only); 8: RM_PRIM_TORUS / _CYLINDER / _PLANE, RM_OP_SMOOTH_SUBTRACT / _INTERSECT, rm_probe_math (additions only); 7: rm_present_sharded_finish / rm_present_sharded take the size of the host buffer (a changed signature), rm_ctx_set_cull_min_pixels, rm_ctx_set_cull_budget, rm_ctx_cull_stats; 6: rm_present_striped_rows, rm_present_sharded_start / _finish, rm_ctx_last_warning, RM_PROBE_CAST_SHADOW, RM_PRIM_KIND (additions only); 3: rm_ctx_set_sample_batch, rm_buffer_*; 4: rm_ctx_set_gl_stack; 5: RmSurface / RmSceneDesc.surfaces (the struct grew), rm_pack_present_rows, rm_present_sharded, rm_ctx_last_pipeline, RM_RENDER_NO_FAR_JUMP, RM_RENDER_NO_CULL (additions only) */
 
 #define RM_MAX_BOUNCES 10 /* raymarchingStepCountsArray[10], raymarcher.frag:31 */
 #define RM_MAX_LIGHTS 10  /* lightPositions[10],             raymarcher.frag:37-39 */
@@ -931,6 +931,49 @@ RM_API void rm_mesh_destroy(rm_mesh* mesh);
 typedef struct RmMeshSharp { int32_t refine; float normal_delta; float threshold; int32_t reserved; } RmMeshSharp; /* 16 bytes */
 RM_API void rm_mesh_sharp_default(RmMeshSharp* sharp);
 RM_API int rm_mesh_extract_sharp(rm_ctx* ctx, rm_scene* scene, const RmGrid* grid, const RmMeshParams* params, const RmMeshSharp* sharp, rm_mesh** out);
+
+/* ---- components and islands (opt-in): what hangs together, and a mesh of the parts worth keeping ----
+ * A level set of a fractal scene is one body in a cloud of detached specks, and a cell that is active only on the grid's boundary yields a vertex
+ * that no triangle references.  These entries label a mesh's connected components and compact the kept ones into a new mesh, on the device.  They
+ * work on any rm_mesh (rm_mesh_extract, _sharp, _from_values, an earlier rm_mesh_filter) and change nothing of it.  For V vertices and T triangles:
+ *   Connected.  Two vertices are connected iff a chain of triangles links them: two vertices of one triangle are linked (degenerate triangles
+ *     count: their indices are distinct).  A vertex in no triangle is a component of its own with 0 triangles.
+ *   Component index.  The components are numbered 0 .. C-1 in ascending order of their smallest vertex index.
+ *   RM_MESH_PART_LABELS  V uint32: labels[v] is the index of v's component.
+ *   RM_MESH_PART_SIZES   C x 2 uint32: (vertices, triangles) of component c.  A triangle belongs to the component of its vertices.
+ *   Keep rule (RmMeshKeep: rm_mesh_keep_default gives min_triangles 1, largest 0).  A component PASSES iff triangles >= min_triangles.  With
+ *     largest == 0 every passing component is kept.  With largest = k > 0 only the first k passing components are kept, in the order (triangles
+ *     descending, component index ascending).  The defaults therefore drop exactly the unreferenced vertices.
+ *   Filtered mesh.  An ordinary rm_mesh of the same context: the kept vertices in their original relative order, the kept triangles in theirs,
+ *     indices renumbered, and positions, cells (still the linear cell index in the source's grid), and normals and colours when the source has
+ *     them, carried bit for bit.  An array the source was made without is absent from the result too.  A kept component is kept whole, so
+ *     filtering a filtered mesh by the same rule gives the same arrays.  An empty source or an empty selection gives a valid empty mesh (0 / 0).
+ * Every output is defined without reference to the order in which the device's threads arrive: it is the same on every run.
+ * Procedure (rm_mesh_kernels.inc "components and islands": integer kernels, the same in every build):
+ *   1. Labelling.  parent[v] = v, then rounds of HOOK (one thread per triangle: find the roots of an edge's ends, atomicMin the larger root's
+ *      parent to the smaller) and FLATTEN (parent[v] = root(v)).  parent[x] <= x holds at every instant, so a root chase strictly descends and
+ *      ends by itself: no thread waits for another.  The hook pass sets a word when it met two roots.  The host reads it behind each round and
+ *      stops at the first round that left it 0, a whole pass that found every edge inside one tree.  At most 64 rounds: reaching that is a
+ *      defect, RM_ERR_DEVICE "did not converge".
+ *   2. The roots (parent[v] == v) are numbered by the mesher's scan, labels[v] = the number of parent[v], and the sizes are integer atomic adds.
+ *   3. rm_mesh_filter: the C pairs come to the host, the keep rule is applied there, a mask per component goes back.  The vertex and the triangle
+ *      keep flags are scanned, one kernel gathers the vertex arrays, one writes the renumbered triangles.
+ * rm_mesh_components: labels the mesh once and keeps the result with it (4 V + 8 C bytes of device memory, freed by rm_mesh_destroy: a mesh's
+ *   arrays never change, so it stays valid).  Later calls, rm_mesh_components_download and rm_mesh_filter reuse it.  *out_count = C.  Synchronous,
+ *   on the stream of the mesh's context.  A filtered mesh starts without a labelling of its own.
+ * rm_mesh_components_download: `bytes` must be exactly 4 V (labels) or 8 C (sizes).  It labels the mesh if nobody has.  host may be NULL only with
+ *   0 bytes.
+ * rm_mesh_filter: keep == NULL is the defaults.  rm_mesh_timings of the result is {0, the milliseconds of the labelling (if this call ran it) and of
+ *   the compaction kernels between events on the stream, 0}.  rm_mesh_download and rm_mesh_device_ptr serve the result as they serve any mesh.
+ * RM_ERR_INVALID, in this order (the text through rm_last_error(NULL) when no context is known): before the handles are looked at, keep
+ * min_triangles < 0, keep largest < 0, a non-zero keep reserved.  Then a NULL mesh, out or out_count ("NULL argument").  Then an unknown `what`.
+ * Then a wrong `bytes` ("exact size").  RM_ERR_DEVICE: a mesh with T >= 2^32 (the sizes are uint32), a failed allocation (nothing leaked). */
+typedef struct RmMeshKeep { int32_t min_triangles; int32_t largest; int32_t reserved[2]; } RmMeshKeep; /* 16 bytes */
+RM_API void rm_mesh_keep_default(RmMeshKeep* keep);
+RM_API int rm_mesh_components(rm_mesh* mesh, unsigned long long* out_count);
+enum { RM_MESH_PART_LABELS = 0, RM_MESH_PART_SIZES = 1 };
+RM_API int rm_mesh_components_download(rm_mesh* mesh, int what, void* host, size_t bytes);
+RM_API int rm_mesh_filter(rm_mesh* mesh, const RmMeshKeep* keep, rm_mesh** out);
 
 #ifdef __cplusplus
 }

@@ -266,3 +266,21 @@ class RmMeshSharp(C.Structure):
 MESH_SHARP_DEFAULTS = dict(refine=6, normal_delta=2.0 ** -10, threshold=0.1)  # rm_mesh_sharp_default
 
 assert C.sizeof(RmMeshSharp) == 16
+
+
+RM_MESH_PART_LABELS, RM_MESH_PART_SIZES = 0, 1
+
+
+class RmMeshKeep(C.Structure):
+    """The keep rule of rm_mesh_filter (ABI 9): a component passes with at least min_triangles triangles; largest = k > 0 keeps only the k
+    passing components with the most triangles (include/hip_raymarch.h "components and islands")."""
+    _fields_ = [
+        ("min_triangles", C.c_int32),
+        ("largest", C.c_int32),
+        ("reserved", C.c_int32 * 2),
+    ]
+
+
+MESH_KEEP_DEFAULTS = dict(min_triangles=1, largest=0)  # rm_mesh_keep_default
+
+assert C.sizeof(RmMeshKeep) == 16

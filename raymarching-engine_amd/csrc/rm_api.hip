@@ -5,6 +5,7 @@
 // RM_ERR_NO_DEVICE and nothing else can be called.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -245,7 +246,7 @@ struct rm_ctx {
   hipStream_t lpt_stream = nullptr;
   bool lpt_enabled = true;
   hipEvent_t switch_ev = nullptr;  // orders the old stream before the new one in rm_ctx_set_stream
-  hipEvent_t mesh_ev[9] = {};      // rm_mesh_extract(_sharp) / rm_mesh_from_values: the marks between their stages (rm_mesh_timings), made with the first mesh
+  hipEvent_t mesh_ev[15] = {};      // rm_mesh_extract(_sharp) / rm_mesh_from_values: the marks between their stages (rm_mesh_timings), made with the first mesh
   hipEvent_t mesh_order = nullptr; // rm_sdf_grid_device on a caller's stream: the context's stream waits behind that launch (sdf_grid_enqueue)
   std::unordered_map<void*, size_t> buffers;  // rm_buffer_create: base address -> bytes
   Scratch scratch[SCRATCH_COUNT];  // scratch_reserve

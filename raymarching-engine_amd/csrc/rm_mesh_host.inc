@@ -7,6 +7,11 @@ struct rm_mesh {
   void* array[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};  // RM_MESH_*; NULL when absent or empty
   bool has[5] = {true, false, false, true, true};                   // normals and colours: when rm_mesh_extract was asked for them
   float ms[3] = {0.0f, 0.0f, 0.0f};                                 // rm_mesh_timings: sampling, meshing, attributes
+  // rm_mesh_components' result, kept once made (the arrays above never change): V labels, `components` pairs of sizes; NULL when empty
+  bool labelled = false;
+  unsigned long long components = 0;
+  void* labels = nullptr;
+  void* sizes = nullptr;
 };
 
 // device memory that is freed when the call that made it returns, unless the mesh has taken it
@@ -80,8 +85,11 @@ void rm_mesh_params_default(RmMeshParams* params) {
 // The marks between the stages of an extraction, on the context's stream (timing events the context keeps): 0 | sampler | 1 | count, scan | 2
 // ... the totals come to the host, the arrays are allocated ... 3 | emit | 4, 5 | normals, colours | 6.  rm_mesh_extract_sharp has, between 4
 // and 5 and behind the allocation of its scratch, 7 | crossings, rounds, normals, QEF | 8.
+// rm_mesh_components and rm_mesh_filter have marks of their own: 9 | init, rounds, scan, labels, sizes | 10, and 11 | keep flags, scans | 12 ...
+// the totals come to the host, the arrays are allocated ... 13 | gathers | 14.
 enum { MESH_MARK_BEGIN, MESH_MARK_SAMPLED, MESH_MARK_SCANNED, MESH_MARK_EMIT, MESH_MARK_EMITTED, MESH_MARK_ATTRIBUTES, MESH_MARK_END, MESH_MARK_SHARPEN,
-       MESH_MARK_SHARPENED, MESH_MARKS };
+       MESH_MARK_SHARPENED, MESH_MARK_LABEL, MESH_MARK_LABELLED, MESH_MARK_FLAG, MESH_MARK_FLAGGED, MESH_MARK_GATHER, MESH_MARK_GATHERED, MESH_MARKS };
+static_assert(MESH_MARKS == sizeof(rm_ctx::mesh_ev) / sizeof(hipEvent_t), "rm_ctx::mesh_ev holds one event per mark");
 static hipError_t mesh_mark(rm_ctx* ctx, int k) {
   if (!ctx->mesh_ev[k]) {
     const hipError_t e = hipEventCreate(&ctx->mesh_ev[k]);
@@ -185,6 +193,8 @@ void rm_mesh_destroy(rm_mesh* mesh) {
   (void)hipStreamSynchronize(mesh->ctx->stream);
   for (void* p : mesh->array)
     if (p) (void)hipFree(p);
+  if (mesh->labels) (void)hipFree(mesh->labels);
+  if (mesh->sizes) (void)hipFree(mesh->sizes);
   delete mesh;
 }
 
@@ -352,4 +362,181 @@ int rm_mesh_download(rm_mesh* mesh, int what, void* host, size_t bytes) {
 void* rm_mesh_device_ptr(rm_mesh* mesh, int what) {
   if (!mesh || what < RM_MESH_POSITIONS || what > RM_MESH_CELLS) return nullptr;
   return mesh->array[what];
+}
+
+// ---- components and islands (include/hip_raymarch.h "components and islands") --------------------------------------------------------
+
+void rm_mesh_keep_default(RmMeshKeep* keep) {
+  if (!keep) return;
+  *keep = RmMeshKeep{1, 0, {0, 0}};
+}
+
+// The labelling, once per mesh: a forest over the vertices by rounds of hook + flatten until a hook pass met no two roots, the roots numbered
+// by the scan, the sizes counted.  On the context's stream; waits for it.  *ms (when given) gains the time between its marks if it ran.
+static int mesh_label(rm_mesh* mesh, const char* who, float* ms) {
+  if (mesh->labelled) return RM_OK;
+  rm_ctx* ctx = mesh->ctx;
+  const unsigned long long V = mesh->vertices, T = mesh->triangles;
+  if (T >= (1ull << 32)) return fail(ctx, RM_ERR_DEVICE, std::string(who) + ": the mesh has more triangles than a uint32 size holds (T >= 2^32)");
+  RM_HIP(ctx, hipSetDevice(ctx->device));
+  if (V == 0) {
+    mesh->labelled = true;
+    return RM_OK;
+  }
+  const size_t scratch_elems = rm::rm_mesh_scan_scratch_elems((long long)V) + 2;  // ... the total, and the word the hook pass sets, behind the levels
+  MeshBuffer parent, words, scratch, labels, sizes;
+  RM_HIP(ctx, parent.reserve(sizeof(unsigned int) * (size_t)V));
+  RM_HIP(ctx, words.reserve(sizeof(unsigned long long) * (size_t)V));
+  RM_HIP(ctx, scratch.reserve(sizeof(unsigned long long) * scratch_elems));
+  RM_HIP(ctx, labels.reserve(sizeof(unsigned int) * (size_t)V));
+  unsigned long long* d_total = scratch.u64() + (scratch_elems - 2);
+  unsigned int* d_changed = reinterpret_cast<unsigned int*>(scratch.u64() + (scratch_elems - 1));
+  const unsigned int* triangles = static_cast<const unsigned int*>(mesh->array[RM_MESH_TRIANGLES]);
+  RM_HIP(ctx, mesh_mark(ctx, MESH_MARK_LABEL));
+  RM_HIP(ctx, rm::launch_mesh_link_init(parent.u32(), (long long)V, ctx->stream));
+  const int max_rounds = 64;
+  int round = 0;
+  for (unsigned int changed = T > 0 ? 1u : 0u; changed != 0u; round++) {
+    if (round == max_rounds) return fail(ctx, RM_ERR_DEVICE, std::string(who) + ": the labelling did not converge in 64 rounds");
+    RM_HIP(ctx, hipMemsetAsync(d_changed, 0, sizeof(unsigned long long), ctx->stream));
+    RM_HIP(ctx, rm::launch_mesh_link_hook(parent.u32(), triangles, (long long)V, (long long)T, d_changed, ctx->stream));
+    RM_HIP(ctx, rm::launch_mesh_link_flatten(parent.u32(), (long long)V, ctx->stream));
+    if (int rc = copy_and_wait(ctx, &changed, d_changed, sizeof changed, hipMemcpyDeviceToHost)) return rc;
+  }
+  RM_HIP(ctx, rm::launch_mesh_roots(parent.u32(), words.u64(), (long long)V, ctx->stream));
+  RM_HIP(ctx, rm::launch_mesh_scan(words.u64(), (long long)V, scratch.u64(), d_total, ctx->stream));
+  RM_HIP(ctx, rm::launch_mesh_labels(parent.u32(), words.u64(), labels.u32(), (long long)V, ctx->stream));
+  unsigned long long total = 0;
+  if (int rc = copy_and_wait(ctx, &total, d_total, sizeof total, hipMemcpyDeviceToHost)) return rc;
+  RM_HIP(ctx, sizes.reserve(sizeof(unsigned int) * 2u * (size_t)total));
+  RM_HIP(ctx, hipMemsetAsync(sizes.p, 0, sizeof(unsigned int) * 2u * (size_t)total, ctx->stream));
+  RM_HIP(ctx, rm::launch_mesh_part_sizes(labels.u32(), nullptr, (long long)V, sizes.u32(), 0, ctx->stream));
+  RM_HIP(ctx, rm::launch_mesh_part_sizes(labels.u32(), triangles, (long long)T, sizes.u32(), 1, ctx->stream));
+  RM_HIP(ctx, mesh_mark(ctx, MESH_MARK_LABELLED));
+  RM_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  if (ms) *ms += mesh_between(ctx, MESH_MARK_LABEL, MESH_MARK_LABELLED);
+  mesh->components = total;
+  mesh->labels = labels.release();
+  mesh->sizes = sizes.release();
+  mesh->labelled = true;
+  return RM_OK;
+}
+
+int rm_mesh_components(rm_mesh* mesh, unsigned long long* out_count) {
+  if (!mesh || !out_count) return fail(mesh ? mesh->ctx : nullptr, RM_ERR_INVALID, "rm_mesh_components: NULL argument");
+  if (int rc = mesh_label(mesh, "rm_mesh_components", nullptr)) return rc;
+  *out_count = mesh->components;
+  return RM_OK;
+}
+
+int rm_mesh_components_download(rm_mesh* mesh, int what, void* host, size_t bytes) {
+  const char* who = "rm_mesh_components_download";
+  if (!mesh) return fail(nullptr, RM_ERR_INVALID, std::string(who) + ": NULL argument");
+  rm_ctx* ctx = mesh->ctx;
+  if (what != RM_MESH_PART_LABELS && what != RM_MESH_PART_SIZES) return fail(ctx, RM_ERR_INVALID, std::string(who) + ": unknown array");
+  if (int rc = mesh_label(mesh, who, nullptr)) return rc;
+  const size_t size = what == RM_MESH_PART_LABELS ? (size_t)mesh->vertices * 4u : (size_t)mesh->components * 8u;
+  if (bytes != size) return fail(ctx, RM_ERR_INVALID, std::string(who) + ": bytes must be the array's exact size");
+  if (bytes == 0) return RM_OK;
+  if (!host) return fail(ctx, RM_ERR_INVALID, std::string(who) + ": NULL argument");
+  return copy_and_wait(ctx, host, what == RM_MESH_PART_LABELS ? mesh->labels : mesh->sizes, bytes, hipMemcpyDeviceToHost);
+}
+
+// The keep rule, stated once: a component passes iff triangles >= min_triangles; with largest == 0 every passing one is kept, else the first
+// `largest` of them in the order (triangles descending, component index ascending).  sizes: (vertices, triangles) pairs.
+static std::vector<unsigned int> mesh_keep_mask(const std::vector<unsigned int>& sizes, const RmMeshKeep& k) {
+  const size_t C = sizes.size() / 2;
+  std::vector<unsigned int> keep(C, 0u), passing;
+  for (size_t c = 0; c < C; c++)
+    if ((unsigned long long)sizes[2 * c + 1] >= (unsigned long long)k.min_triangles) passing.push_back((unsigned int)c);
+  if (k.largest > 0) {
+    std::stable_sort(passing.begin(), passing.end(), [&](unsigned int a, unsigned int b) { return sizes[2 * (size_t)a + 1] > sizes[2 * (size_t)b + 1]; });
+    if (passing.size() > (size_t)k.largest) passing.resize((size_t)k.largest);
+  }
+  for (unsigned int c : passing) keep[c] = 1u;
+  return keep;
+}
+
+int rm_mesh_filter(rm_mesh* mesh, const RmMeshKeep* keep, rm_mesh** out) {
+  const char* who = "rm_mesh_filter";
+  rm_ctx* ctx = mesh ? mesh->ctx : nullptr;
+  auto refuse = [&](const char* what) { return fail(ctx, RM_ERR_INVALID, std::string(who) + ": " + what); };
+  RmMeshKeep k;
+  rm_mesh_keep_default(&k);
+  if (keep) k = *keep;
+  if (k.min_triangles < 0) return refuse("keep min_triangles must be >= 0");
+  if (k.largest < 0) return refuse("keep largest must be >= 0");
+  if (k.reserved[0] != 0 || k.reserved[1] != 0) return refuse("keep reserved must be 0");
+  if (!mesh || !out) return refuse("NULL argument");
+  *out = nullptr;
+  float ms = 0.0f;
+  if (int rc = mesh_label(mesh, who, &ms)) return rc;
+  RM_HIP(ctx, hipSetDevice(ctx->device));
+  rm_mesh* made = new (std::nothrow) rm_mesh;
+  if (!made) return fail(ctx, RM_ERR_DEVICE, std::string(who) + ": out of host memory");
+  made->ctx = ctx;
+  for (int a = 0; a < 5; a++) made->has[a] = mesh->has[a];
+  // everything below returns through here: a refused step gives the half-made mesh up (its arrays are still the MeshBuffers')
+  auto build = [&]() -> int {
+    const unsigned long long V = mesh->vertices, T = mesh->triangles, C = mesh->components;
+    if (V == 0) return RM_OK;
+    std::vector<unsigned int> sizes(2 * (size_t)C);
+    if (int rc = copy_and_wait(ctx, sizes.data(), mesh->sizes, sizeof(unsigned int) * sizes.size(), hipMemcpyDeviceToHost)) return rc;
+    const std::vector<unsigned int> mask = mesh_keep_mask(sizes, k);
+    const size_t vertex_scratch = rm::rm_mesh_scan_scratch_elems((long long)V), triangle_scratch = rm::rm_mesh_scan_scratch_elems((long long)T);
+    MeshBuffer d_keep, vertex_at, triangle_at, scratch, arrays[5];
+    RM_HIP(ctx, d_keep.reserve(sizeof(unsigned int) * (size_t)C));
+    RM_HIP(ctx, vertex_at.reserve(sizeof(unsigned long long) * (size_t)V));
+    RM_HIP(ctx, triangle_at.reserve(sizeof(unsigned long long) * (size_t)T));
+    RM_HIP(ctx, scratch.reserve(sizeof(unsigned long long) * (vertex_scratch + triangle_scratch + 2)));
+    unsigned long long* d_totals = scratch.u64() + vertex_scratch + triangle_scratch;
+    const unsigned int* labels = static_cast<const unsigned int*>(mesh->labels);
+    const unsigned int* triangles = static_cast<const unsigned int*>(mesh->array[RM_MESH_TRIANGLES]);
+    RM_HIP(ctx, hipMemcpyAsync(d_keep.p, mask.data(), sizeof(unsigned int) * (size_t)C, hipMemcpyHostToDevice, ctx->stream));
+    RM_HIP(ctx, hipMemsetAsync(d_totals, 0, 2 * sizeof(unsigned long long), ctx->stream));  // (a mesh without triangles scans nothing)
+    RM_HIP(ctx, mesh_mark(ctx, MESH_MARK_FLAG));
+    RM_HIP(ctx, rm::launch_mesh_keep_flags(labels, nullptr, d_keep.u32(), (long long)V, vertex_at.u64(), ctx->stream));
+    RM_HIP(ctx, rm::launch_mesh_scan(vertex_at.u64(), (long long)V, scratch.u64(), d_totals, ctx->stream));
+    if (T > 0) {
+      RM_HIP(ctx, rm::launch_mesh_keep_flags(labels, triangles, d_keep.u32(), (long long)T, triangle_at.u64(), ctx->stream));
+      RM_HIP(ctx, rm::launch_mesh_scan(triangle_at.u64(), (long long)T, scratch.u64() + vertex_scratch, d_totals + 1, ctx->stream));
+    }
+    RM_HIP(ctx, mesh_mark(ctx, MESH_MARK_FLAGGED));
+    unsigned long long totals[2] = {0, 0};
+    if (int rc = copy_and_wait(ctx, totals, d_totals, sizeof totals, hipMemcpyDeviceToHost)) return rc;  // (the mask's upload is done too)
+    ms += mesh_between(ctx, MESH_MARK_FLAG, MESH_MARK_FLAGGED);
+    made->vertices = totals[0];
+    made->triangles = totals[1];
+    if (made->vertices == 0) return RM_OK;
+    rm::MeshGather G{};
+    G.labels = labels;
+    G.keep = d_keep.u32();
+    G.vertex_at = vertex_at.u64();
+    const int order[4] = {RM_MESH_POSITIONS, RM_MESH_NORMALS, RM_MESH_COLOURS, RM_MESH_CELLS};
+    for (int a = 0; a < 4; a++) {
+      const int what = order[a];
+      if (!mesh->array[what]) continue;  // (absent; a mesh with vertices has the others)
+      RM_HIP(ctx, arrays[what].reserve(mesh_array_bytes(made, what)));
+      G.src[a] = static_cast<const unsigned int*>(mesh->array[what]);
+      G.dst[a] = arrays[what].u32();
+    }
+    RM_HIP(ctx, arrays[RM_MESH_TRIANGLES].reserve(mesh_array_bytes(made, RM_MESH_TRIANGLES)));
+    RM_HIP(ctx, mesh_mark(ctx, MESH_MARK_GATHER));
+    RM_HIP(ctx, rm::launch_mesh_gather_vertices(G, (long long)V, ctx->stream));
+    if (made->triangles > 0)
+      RM_HIP(ctx, rm::launch_mesh_gather_triangles(G, triangles, triangle_at.u64(), (long long)T, arrays[RM_MESH_TRIANGLES].u32(), ctx->stream));
+    RM_HIP(ctx, mesh_mark(ctx, MESH_MARK_GATHERED));
+    RM_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    ms += mesh_between(ctx, MESH_MARK_GATHER, MESH_MARK_GATHERED);
+    for (int a = 0; a < 5; a++) made->array[a] = arrays[a].release();
+    return RM_OK;
+  };
+  if (int rc = build()) {
+    (void)hipStreamSynchronize(ctx->stream);  // (the scratch is freed behind whatever was enqueued)
+    rm_mesh_destroy(made);
+    return rc;
+  }
+  made->ms[1] = ms;
+  *out = made;
+  return RM_OK;
 }

@@ -1,6 +1,7 @@
 // Mesh extraction (include/hip_raymarch.h "mesh extraction"): a scene's distance on a grid of corners, in this unit's arithmetic,
-// and -- in the strict unit only, they have no arithmetic of a policy's own -- the surface-nets mesher over such a grid and the two
-// kernels that move its vertices to their cells' QEF minimisers (rm_mesh_extract_sharp).  Included by
+// and -- in the strict unit only, they have no arithmetic of a policy's own -- the surface-nets mesher over such a grid, the two
+// kernels that move its vertices to their cells' QEF minimisers (rm_mesh_extract_sharp), and the integer kernels that label a mesh's
+// connected components and compact the kept ones (rm_mesh_components, rm_mesh_filter).  Included by
 // rm_strict.hip / rm_fast.hip / rm_glstack.hip behind rm_kernels.inc.
 namespace rm {
 
@@ -345,6 +346,132 @@ __global__ __launch_bounds__(256) void rm_mesh_qef_kernel(const MeshSharpParams 
   P.mesh.positions[3 * (size_t)v + 2] = z;
 }
 
+// ---- components and islands (include/hip_raymarch.h "components and islands") ---------------------------------------------------------
+// A forest over the vertices, parent[v] <= v at every instant: a root is its own parent, and the least vertex of a finished tree.  Parents are
+// read with relaxed agent-scope atomic loads -- other workgroups lower them while this one reads -- and only ever lowered, by atomicMin, to a
+// vertex of the same component: a stale parent is an older, larger ancestor, so a chase strictly descends and ends by itself.  No thread waits
+// for another.  The host repeats hook + flatten until a hook pass met no two roots (rm_mesh_host.inc mesh_label).
+
+__device__ inline unsigned int mesh_link_root(const unsigned int* parent, unsigned int v) {
+  for (;;) {
+    const unsigned int p = __hip_atomic_load(parent + v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (p >= v) return v;  // (p > v never happens; it would end the chase all the same)
+    v = p;
+  }
+}
+
+// Unite the trees of a and b: the larger root's parent is lowered to the smaller root.  When the larger was no root any more (old != hi), its
+// parent is now min(old, lo) and the link to the other of the two may be gone, so old and lo are united in its place: hi is below one of
+// them and both are smaller than hi, so this descends too.  Returns whether a and b were in different trees.
+__device__ inline bool mesh_link_unite(unsigned int* parent, unsigned int a, unsigned int b) {
+  bool met = false;
+  for (;;) {
+    a = mesh_link_root(parent, a);
+    b = mesh_link_root(parent, b);
+    if (a == b) return met;
+    met = true;
+    const unsigned int hi = a > b ? a : b, lo = a > b ? b : a;
+    const unsigned int old = atomicMin(parent + hi, lo);
+    if (old == hi) return met;
+    a = old;
+    b = lo;
+  }
+}
+
+__global__ __launch_bounds__(256) void rm_mesh_link_init_kernel(unsigned int* parent, long long vertices) {
+  const long long v = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (v < vertices) parent[v] = (unsigned int)v;
+}
+
+// one thread per triangle; two of its edges connect its three vertices.  A triangle with an index beyond the mesh links nothing.
+__global__ __launch_bounds__(256) void rm_mesh_link_hook_kernel(unsigned int* parent, const unsigned int* triangles, long long vertices, long long n,
+                                                                unsigned int* changed) {
+  const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
+  bool met = false;
+  if (t < n) {
+    const unsigned int a = triangles[3 * t], b = triangles[3 * t + 1], c = triangles[3 * t + 2];
+    if (a < vertices && b < vertices && c < vertices) {
+      met = mesh_link_unite(parent, a, b);
+      met = mesh_link_unite(parent, b, c) || met;
+    }
+  }
+  const unsigned long long any = __ballot(met);  // one store per wave that met two roots
+  if (any != 0ull && (int)(threadIdx.x & 63u) == __ffsll((long long)any) - 1) *changed = 1u;
+}
+
+__global__ __launch_bounds__(256) void rm_mesh_link_flatten_kernel(unsigned int* parent, long long vertices) {
+  const long long v = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (v >= vertices) return;
+  const unsigned int r = mesh_link_root(parent, (unsigned int)v);
+  if (r != (unsigned int)v) __hip_atomic_store(parent + v, r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // (roots stay roots in this pass)
+}
+
+__global__ __launch_bounds__(256) void rm_mesh_roots_kernel(const unsigned int* parent, unsigned long long* words, long long vertices) {
+  const long long v = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (v < vertices) words[v] = parent[v] == (unsigned int)v ? 1ull : 0ull;
+}
+
+__global__ __launch_bounds__(256) void rm_mesh_labels_kernel(const unsigned int* parent, const unsigned long long* scanned, unsigned int* labels,
+                                                             long long vertices) {
+  const long long v = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (v < vertices) labels[v] = (unsigned int)scanned[parent[v]];
+}
+
+// the component of vertex i (triangles == NULL) or of triangle i: that of its first vertex
+__device__ inline unsigned int mesh_part_of(const unsigned int* labels, const unsigned int* triangles, long long i) {
+  return labels[triangles ? triangles[3 * i] : (unsigned int)i];
+}
+
+// sizes[2 c + slot] += 1 per element.  Integer adds: any order gives the same sums.  Most of a wave's elements usually lie in one component:
+// where all of them do, one lane adds their count.
+__global__ __launch_bounds__(256) void rm_mesh_part_sizes_kernel(const unsigned int* labels, const unsigned int* triangles, long long n, unsigned int* sizes,
+                                                                 int slot) {
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  const bool valid = i < n;
+  const unsigned int c = valid ? mesh_part_of(labels, triangles, i) : 0u;
+  const unsigned long long lanes = __ballot(valid);
+  if (lanes == 0ull) return;
+  const int lead = __ffsll((long long)lanes) - 1;
+  const unsigned int first = (unsigned int)__shfl((int)c, lead);
+  if (__ballot(valid && c == first) == lanes) {
+    if ((int)(threadIdx.x & 63u) == lead) atomicAdd(sizes + 2 * (size_t)first + slot, (unsigned int)__popcll(lanes));
+  } else if (valid) {
+    atomicAdd(sizes + 2 * (size_t)c + slot, 1u);
+  }
+}
+
+__global__ __launch_bounds__(256) void rm_mesh_keep_flags_kernel(const unsigned int* labels, const unsigned int* triangles, const unsigned int* keep, long long n,
+                                                                 unsigned long long* words) {
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i < n) words[i] = keep[mesh_part_of(labels, triangles, i)] ? 1ull : 0ull;
+}
+
+// one thread per source vertex: a kept one copies its rows, as words, to its place among the kept
+__global__ __launch_bounds__(256) void rm_mesh_gather_vertices_kernel(const MeshGather G, long long vertices) {
+  const long long v = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (v >= vertices || !G.keep[G.labels[v]]) return;
+  const size_t to = (size_t)G.vertex_at[v];
+#pragma unroll
+  for (int a = 0; a < 3; a++) {
+    if (!G.src[a]) continue;
+    G.dst[a][3 * to] = G.src[a][3 * v];
+    G.dst[a][3 * to + 1] = G.src[a][3 * v + 1];
+    G.dst[a][3 * to + 2] = G.src[a][3 * v + 2];
+  }
+  G.dst[3][to] = G.src[3][v];
+}
+
+// one thread per source triangle: a kept one (its vertices are kept with it) goes to its place with its indices renumbered
+__global__ __launch_bounds__(256) void rm_mesh_gather_triangles_kernel(const MeshGather G, const unsigned int* triangles, const unsigned long long* triangle_at,
+                                                                       long long n, unsigned int* out) {
+  const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (t >= n || !G.keep[G.labels[triangles[3 * t]]]) return;
+  const size_t to = (size_t)triangle_at[t];
+  out[3 * to] = (unsigned int)G.vertex_at[triangles[3 * t]];
+  out[3 * to + 1] = (unsigned int)G.vertex_at[triangles[3 * t + 1]];
+  out[3 * to + 2] = (unsigned int)G.vertex_at[triangles[3 * t + 2]];
+}
+
 #ifndef RM_ONLY_KERNELS
 static inline long long mesh_cells(const GridDims& g) { return (long long)(g.nc[0] - 1) * (g.nc[1] - 1) * (g.nc[2] - 1); }
 
@@ -397,6 +524,44 @@ hipError_t launch_mesh_qef(const MeshSharpParams& P, hipStream_t stream) {
   hipLaunchKernelGGL(rm_mesh_qef_kernel, dim3((unsigned int)((P.vertices + 255) / 256)), dim3(256), 0, stream, P);
   return hipGetLastError();
 }
+
+// components and islands: n < 2^32 elements, one thread each, workgroups of 256; nothing is launched for n == 0
+#define RM_MESH_PARTS_LAUNCH(kernel, n, ...)                                                                            \
+  do {                                                                                                                  \
+    if ((n) > 0) hipLaunchKernelGGL(kernel, dim3((unsigned int)(((n) + 255) / 256)), dim3(256), 0, stream, __VA_ARGS__); \
+    return hipGetLastError();                                                                                           \
+  } while (0)
+
+hipError_t launch_mesh_link_init(unsigned int* parent, long long vertices, hipStream_t stream) {
+  RM_MESH_PARTS_LAUNCH(rm_mesh_link_init_kernel, vertices, parent, vertices);
+}
+hipError_t launch_mesh_link_hook(unsigned int* parent, const unsigned int* triangles, long long vertices, long long n, unsigned int* changed, hipStream_t stream) {
+  RM_MESH_PARTS_LAUNCH(rm_mesh_link_hook_kernel, n, parent, triangles, vertices, n, changed);
+}
+hipError_t launch_mesh_link_flatten(unsigned int* parent, long long vertices, hipStream_t stream) {
+  RM_MESH_PARTS_LAUNCH(rm_mesh_link_flatten_kernel, vertices, parent, vertices);
+}
+hipError_t launch_mesh_roots(const unsigned int* parent, unsigned long long* words, long long vertices, hipStream_t stream) {
+  RM_MESH_PARTS_LAUNCH(rm_mesh_roots_kernel, vertices, parent, words, vertices);
+}
+hipError_t launch_mesh_labels(const unsigned int* parent, const unsigned long long* scanned, unsigned int* labels, long long vertices, hipStream_t stream) {
+  RM_MESH_PARTS_LAUNCH(rm_mesh_labels_kernel, vertices, parent, scanned, labels, vertices);
+}
+hipError_t launch_mesh_part_sizes(const unsigned int* labels, const unsigned int* triangles, long long n, unsigned int* sizes, int slot, hipStream_t stream) {
+  RM_MESH_PARTS_LAUNCH(rm_mesh_part_sizes_kernel, n, labels, triangles, n, sizes, slot);
+}
+hipError_t launch_mesh_keep_flags(const unsigned int* labels, const unsigned int* triangles, const unsigned int* keep, long long n, unsigned long long* words,
+                                  hipStream_t stream) {
+  RM_MESH_PARTS_LAUNCH(rm_mesh_keep_flags_kernel, n, labels, triangles, keep, n, words);
+}
+hipError_t launch_mesh_gather_vertices(const MeshGather& G, long long vertices, hipStream_t stream) {
+  RM_MESH_PARTS_LAUNCH(rm_mesh_gather_vertices_kernel, vertices, G, vertices);
+}
+hipError_t launch_mesh_gather_triangles(const MeshGather& G, const unsigned int* triangles, const unsigned long long* triangle_at, long long n,
+                                        unsigned int* out, hipStream_t stream) {
+  RM_MESH_PARTS_LAUNCH(rm_mesh_gather_triangles_kernel, n, G, triangles, triangle_at, n, out);
+}
+#undef RM_MESH_PARTS_LAUNCH
 
 hipError_t launch_mesh_emit(const MeshParams& P, hipStream_t stream) {
   const long long cells = mesh_cells(P.grid);

@@ -466,6 +466,29 @@ hipError_t launch_mesh_colours(const float* material, float* colours, long long 
 // probe output in, `last` writes the crossings and the live mask (else the next round's midpoints and the brackets).  qef: the vertex positions.
 hipError_t launch_mesh_cross(const MeshSharpParams& P, int init, int consume, int last, hipStream_t stream);
 hipError_t launch_mesh_qef(const MeshSharpParams& P, hipStream_t stream);
+// Components and islands (rm_mesh_components, rm_mesh_filter): integer kernels over a mesh's vertices (n = V) and triangles (n = T).
+// link_init: parent[v] = v.  link_hook: every triangle unites its vertices' trees, *changed = 1 when it met two roots.  link_flatten: parent[v]
+// = root(v).  roots: words[v] = (parent[v] == v), for the scan; labels: labels[v] = scanned words[parent[v]].  part_sizes: sizes[2 c + slot]
+// += 1 per vertex (triangles == NULL, slot 0) or per triangle (slot 1) of component c.  keep_flags: words[i] = keep[component of vertex or
+// triangle i].  gather_vertices / gather_triangles: the kept rows to their scanned places, the triangles' indices remapped.
+struct MeshGather {
+  const unsigned int* labels;
+  const unsigned int* keep;            // per component: 0 or 1
+  const unsigned long long* vertex_at;  // the scanned vertex keep flags
+  const unsigned int* src[4];           // positions, normals, colours (3 words per vertex; NULL when absent), cells (1 word)
+  unsigned int* dst[4];
+};
+hipError_t launch_mesh_link_init(unsigned int* parent, long long vertices, hipStream_t stream);
+hipError_t launch_mesh_link_hook(unsigned int* parent, const unsigned int* triangles, long long vertices, long long n, unsigned int* changed, hipStream_t stream);
+hipError_t launch_mesh_link_flatten(unsigned int* parent, long long vertices, hipStream_t stream);
+hipError_t launch_mesh_roots(const unsigned int* parent, unsigned long long* words, long long vertices, hipStream_t stream);
+hipError_t launch_mesh_labels(const unsigned int* parent, const unsigned long long* scanned, unsigned int* labels, long long vertices, hipStream_t stream);
+hipError_t launch_mesh_part_sizes(const unsigned int* labels, const unsigned int* triangles, long long n, unsigned int* sizes, int slot, hipStream_t stream);
+hipError_t launch_mesh_keep_flags(const unsigned int* labels, const unsigned int* triangles, const unsigned int* keep, long long n, unsigned long long* words,
+                                  hipStream_t stream);
+hipError_t launch_mesh_gather_vertices(const MeshGather& G, long long vertices, hipStream_t stream);
+hipError_t launch_mesh_gather_triangles(const MeshGather& G, const unsigned int* triangles, const unsigned long long* triangle_at, long long n,
+                                        unsigned int* out, hipStream_t stream);
 hipError_t launch_camera_rng(const RmUniforms& u, int W, int H, int what, int count, float* out, hipStream_t stream);
 hipError_t launch_math_probe(int fn, const float* a, const float* b, int n, float* out, hipStream_t stream);
 }  // namespace rm

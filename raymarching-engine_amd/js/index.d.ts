@@ -117,8 +117,10 @@ export class RenderJobContext {
   extractMesh(scene: Scene, grid: MeshGrid, params?: MeshParams | null): Mesh;
   /** with `sharp` (true = the defaults): rm_mesh_extract_sharp, the same triangles with every vertex at its cell's QEF minimiser, so hard edges and corners stay sharp */
   extractMesh(scene: Scene, grid: MeshGrid, params: MeshParams | null | undefined, sharp: MeshSharp | true | null): Mesh;
+  /** with `keep` (true = the defaults, which drop unreferenced vertices): the mesh's connected components filtered on the GPU before anything is copied (rm_mesh_filter); `components`: the result carries labels and componentSizes (rm_mesh_components) */
+  extractMesh(scene: Scene, grid: MeshGrid, params: MeshParams | null | undefined, sharp: MeshSharp | true | null | undefined, keep: MeshKeep | true | null | undefined, components?: boolean): Mesh;
   /** the mesher alone on the caller's field (rm_mesh_from_values) */
-  meshFromValues(grid: MeshGrid, values: Float32Array, iso?: number): Mesh;
+  meshFromValues(grid: MeshGrid, values: Float32Array, iso?: number, keep?: MeshKeep | true | null, components?: boolean): Mesh;
   close(): void;
 }
 /** A frame sharded over several GPUs by this one process: a native context per device, each holding one part of the frame's
@@ -150,7 +152,7 @@ export const RM: { [name: string]: number };
 /** mesh extraction (include/hip_raymarch.h "mesh extraction"): n = CELLS per axis between the corners lo and hi */
 export interface MeshGrid { lo: [number, number, number]; hi: [number, number, number]; n: [number, number, number] }
 export interface MeshParams { iso?: number; normals?: boolean | 0 | 1; normalDelta?: number; colours?: boolean | 0 | 1; flags?: number }
-export interface Mesh { positions: Float32Array; normals: Float32Array | null; colours: Float32Array | null; triangles: Uint32Array; cells: Uint32Array; /** ms of sampling, meshing, attributes (rm_mesh_timings) */ timings: [number, number, number] }
+export interface Mesh { positions: Float32Array; normals: Float32Array | null; colours: Float32Array | null; triangles: Uint32Array; cells: Uint32Array; /** ms of sampling, meshing, attributes (rm_mesh_timings) */ timings: [number, number, number]; /** only when components were asked for: each vertex's component, and (vertices, triangles) per component */ labels?: Uint32Array; componentSizes?: Uint32Array }
 export const MESH_DEFAULTS: { iso: number; normals: 0 | 1; normalDelta: number; colours: 0 | 1; flags: number };
 export function meshGrid(lo: number[], hi: number[], n: number[]): MeshGrid;
 export function meshParams(params?: MeshParams | null): { iso: number; normals: 0 | 1; normalDelta: number; colours: 0 | 1; flags: number };
@@ -158,5 +160,9 @@ export function meshParams(params?: MeshParams | null): { iso: number; normals: 
 export interface MeshSharp { refine?: number; normalDelta?: number; threshold?: number }
 export const MESH_SHARP_DEFAULTS: { refine: number; normalDelta: number; threshold: number };
 export function meshSharp(sharp?: MeshSharp | null): { refine: number; normalDelta: number; threshold: number };
+/** the keep block of extractMesh / meshFromValues (RmMeshKeep): a component passes with at least minTriangles triangles; largest = k > 0 keeps only the k passing components with the most triangles (the lower component index first among equals), 0 keeps every passing one */
+export interface MeshKeep { minTriangles?: number; largest?: number }
+export const MESH_KEEP_DEFAULTS: { minTriangles: number; largest: number };
+export function meshKeep(keep?: MeshKeep | null): { minTriangles: number; largest: number };
 /** binary little-endian PLY (normals and uchar colours when present): the bytes the Python host's write_ply writes */
 export function encodePly(mesh: { positions: Float32Array; triangles: Uint32Array; normals?: Float32Array | null; colours?: Float32Array | null }): Buffer;

@@ -356,15 +356,25 @@ class RenderJobContext {  // RenderJobContext + loadRenderJobContext (LoadRender
   // the level set opts.iso as { positions, normals | null, colours | null, triangles, cells } (rm_mesh_extract); opts: meshParams'
   // sharp: undefined / null = that call; true or meshSharp's options = rm_mesh_extract_sharp, the same triangles with each vertex at its cell's
   // QEF minimiser (hard edges and corners stay sharp)
-  extractMesh(scene, grid, opts, sharp) {
-    if (sharp === undefined || sharp === null) return addon.extractMesh(this.ctx, this.sceneHandle(scene), grid, meshParams(opts));
-    return addon.extractMesh(this.ctx, this.sceneHandle(scene), grid, meshParams(opts), meshSharp(sharp === true ? undefined : sharp));
+  // keep: undefined / null = that mesh; true or meshKeep's options = its connected components filtered on the GPU before anything is copied
+  // (rm_mesh_filter; the defaults drop the unreferenced vertices).  components: truthy adds labels (Uint32Array(V)) and componentSizes
+  // (Uint32Array(2 C): vertices, triangles per component) of the mesh that is returned (rm_mesh_components)
+  extractMesh(scene, grid, opts, sharp, keep, components) {
+    const plain = (keep === undefined || keep === null) && !components;
+    if (plain && (sharp === undefined || sharp === null)) return addon.extractMesh(this.ctx, this.sceneHandle(scene), grid, meshParams(opts));
+    const s = sharp === undefined || sharp === null ? null : meshSharp(sharp === true ? undefined : sharp);
+    if (plain) return addon.extractMesh(this.ctx, this.sceneHandle(scene), grid, meshParams(opts), s);
+    const k = keep === undefined || keep === null ? null : meshKeep(keep === true ? undefined : keep);
+    return addon.extractMesh(this.ctx, this.sceneHandle(scene), grid, meshParams(opts), s, k, !!components);
   }
   // the mesher alone on the caller's field: values Float32Array of the grid's corners, x fastest (rm_mesh_from_values)
-  meshFromValues(grid, values, iso = 0) {
+  // keep, components: as in extractMesh
+  meshFromValues(grid, values, iso = 0, keep, components) {
     if (!(values instanceof Float32Array)) throw new TypeError("meshFromValues: values must be a Float32Array");
     if (!finite(iso)) throw new RangeError("mesh: iso must be a finite number");
-    return addon.meshFromValues(this.ctx, grid, values, iso);
+    if ((keep === undefined || keep === null) && !components) return addon.meshFromValues(this.ctx, grid, values, iso);
+    const k = keep === undefined || keep === null ? null : meshKeep(keep === true ? undefined : keep);
+    return addon.meshFromValues(this.ctx, grid, values, iso, k, !!components);
   }
   close() { for (const e of this.purgatory) addon.fbDestroy(e.fb); for (const v of this.live.values()) addon.fbDestroy(v.fb);
             for (const s of this.scenes.values()) if (!(s && s.infoLog)) addon.sceneDestroy(s); addon.ctxDestroy(this.ctx); }
@@ -667,6 +677,25 @@ function meshSharp(opts) {
   if (!finite(p.threshold) || !(Math.fround(p.threshold) >= 0 && Math.fround(p.threshold) < 1)) throw new RangeError("mesh: sharp threshold must be finite and in [0, 1)");
   return p;
 }
+
+// the keep block of extractMesh / meshFromValues (include/hip_raymarch.h RmMeshKeep): undefined / null = the defaults, or an object with some of
+// minTriangles (a component passes with at least that many triangles) and largest (0 = every passing component, k > 0 = only the k with the
+// most triangles, the lower component index first among equals); integers in 0..1e9, what the addon's integer fields hold
+const MESH_KEEP_DEFAULTS = { minTriangles: 1, largest: 0 };
+function meshKeep(opts) {
+  const p = { ...MESH_KEEP_DEFAULTS };
+  if (opts !== undefined && opts !== null) {
+    if (typeof opts !== "object") throw new TypeError("mesh: expected an object of keep parameters");
+    for (const k of Object.keys(opts)) {
+      if (!(k in MESH_KEEP_DEFAULTS)) throw new TypeError("mesh: unknown keep parameter " + k);
+      p[k] = opts[k];
+    }
+  }
+  for (const k of Object.keys(MESH_KEEP_DEFAULTS))
+    if (typeof p[k] !== "number" || !Number.isInteger(p[k]) || p[k] < 0 || p[k] > 1e9) throw new RangeError("mesh: keep " + k + " must be an integer in 0..1e9");
+  return p;
+}
+
 // binary little-endian PLY of { positions, triangles, normals?, colours? }: x y z, then nx ny nz, then uchar red green blue
 // (floor(clamp(c, 0, 1) * 255 + 0.5), NaN as 0); faces as a uchar count and uint indices -- the bytes the Python host writes
 function encodePly(mesh) {
@@ -718,4 +747,5 @@ function encodePng(rgba, width, height, bottomUp = true) {
 module.exports = { RM, addon, encodePng, Scene, CsgScene, Mandelbulb, singleSphere, DEFAULT_MATERIAL, halton, resetHalton, uniformsFromSchema, packUniforms,
                    tileRect, RenderJobContext, ShardedRenderJobContext, doRenderJob, U_OFFSET, DENOISE_DEFAULTS, denoiseParams,
                    DENOISE_VARIANCE_DEFAULTS, denoiseVarianceParams, DESPECKLE_DEFAULTS, despeckleParams, DISPLAY_DEFAULTS, AUTO_EXPOSURE_DEFAULTS,
-                   displayParams, statsExposure, statsPercentile, MESH_DEFAULTS, meshGrid, meshParams, MESH_SHARP_DEFAULTS, meshSharp, encodePly };
+                   displayParams, statsExposure, statsPercentile, MESH_DEFAULTS, meshGrid, meshParams, MESH_SHARP_DEFAULTS, meshSharp, MESH_KEEP_DEFAULTS, meshKeep,
+                   encodePly };

@@ -508,6 +508,37 @@ static napi_value MeshSharpBlock(napi_env env, napi_callback_info info) {
   return b;
 }
 
+// any value as its truth (JavaScript's ToBoolean)
+static bool get_bool(napi_env env, napi_value v, bool* out) {
+  napi_value b;
+  return napi_coerce_to_bool(env, v, &b) == napi_ok && napi_get_value_bool(env, b, out) == napi_ok;
+}
+
+static const Field MESH_KEEP_FIELDS[] = {{"minTriangles", Field::INT, offsetof(RmMeshKeep, min_triangles)}, {"largest", Field::INT, offsetof(RmMeshKeep, largest)}};
+// the keep block of extractMesh / meshFromValues: null / undefined = none (*given = false), an object = rm_mesh_filter with its fields over the defaults
+static bool get_mesh_keep(napi_env env, napi_value v, RmMeshKeep* k, bool* given) {
+  rm_mesh_keep_default(k);
+  return get_block(env, v, k, MESH_KEEP_FIELDS, given);
+}
+
+// meshKeepBlock(keep | null) -> ArrayBuffer(RmMeshKeep): the bytes the mesh calls hand to rm_mesh_filter (null: the defaults)
+static napi_value MeshKeepBlock(napi_env env, napi_callback_info info) {
+  size_t argc = 1;
+  napi_value argv[1];
+  NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+  RmMeshKeep k;
+  bool given = false;
+  if (argc != 1 || !get_mesh_keep(env, argv[0], &k, &given)) {
+    napi_throw_type_error(env, nullptr, "meshKeepBlock(keep | null)");
+    return nullptr;
+  }
+  napi_value b;
+  void* d = nullptr;
+  NAPI_OK(napi_create_arraybuffer(env, sizeof k, &d, &b));
+  std::memcpy(d, &k, sizeof k);
+  return b;
+}
+
 static napi_value make_array(napi_env env, napi_typedarray_type type, size_t count, void** data) {
   napi_value ab, out;
   if (napi_create_arraybuffer(env, count * 4, data, &ab) != napi_ok || napi_create_typedarray(env, type, count, ab, 0, &out) != napi_ok) return nullptr;
@@ -563,8 +594,18 @@ static napi_value SdfGrid(napi_env env, napi_callback_info info) {
 }
 
 // the mesh as { positions, normals | null, colours | null: Float32Array(3 V), triangles: Uint32Array(3 T), cells: Uint32Array(V), timings: [sampling,
-// meshing, attributes] in ms (rm_mesh_timings) }; normals / colours: whether the call asked for them; the handle is destroyed
-static napi_value mesh_result(napi_env env, rm_ctx* ctx, rm_mesh* mesh, bool normals, bool colours) {
+// meshing, attributes] in ms (rm_mesh_timings) }; normals / colours: whether the call asked for them; the handle is destroyed.  keep: the mesh is
+// first filtered on the device (rm_mesh_filter) and the filtered one is what is copied; components: labels: Uint32Array(V) and componentSizes:
+// Uint32Array(2 C) come with it (rm_mesh_components)
+static napi_value mesh_result(napi_env env, rm_ctx* ctx, rm_mesh* mesh, bool normals, bool colours, const RmMeshKeep* keep = nullptr, bool components = false) {
+  if (keep) {
+    rm_mesh* filtered = nullptr;
+    const int rc = rm_mesh_filter(mesh, keep, &filtered);
+    napi_value r = rc != RM_OK ? throw_rm(env, ctx, "rm_mesh_filter") : nullptr;
+    rm_mesh_destroy(mesh);
+    if (rc != RM_OK) return r;
+    mesh = filtered;
+  }
   unsigned long long counts[2] = {0, 0};
   rm_mesh_counts(mesh, counts);
   static const struct { const char* name; int what; napi_typedarray_type type; int per_vertex, per_triangle; } ARRAYS[] = {
@@ -588,6 +629,21 @@ static napi_value mesh_result(napi_env env, rm_ctx* ctx, rm_mesh* mesh, bool nor
     }
     ok = ok && napi_set_named_property(env, o, a.name, v) == napi_ok;
   }
+  if (components && ok && !refused) {
+    unsigned long long parts = 0;
+    refused = rm_mesh_components(mesh, &parts) != RM_OK;
+    static const struct { const char* name; int what; } PARTS[] = {{"labels", RM_MESH_PART_LABELS}, {"componentSizes", RM_MESH_PART_SIZES}};
+    for (const auto& a : PARTS) {
+      if (!ok || refused) break;
+      const size_t count = a.what == RM_MESH_PART_LABELS ? (size_t)counts[0] : 2u * (size_t)parts;
+      void* data = nullptr;
+      napi_value v = make_array(env, napi_uint32_array, count, &data);
+      ok = v != nullptr;
+      if (!ok) break;
+      if (rm_mesh_components_download(mesh, a.what, data, count * 4) != RM_OK) { refused = true; break; }
+      ok = napi_set_named_property(env, o, a.name, v) == napi_ok;
+    }
+  }
   float ms[3] = {0.0f, 0.0f, 0.0f};
   rm_mesh_timings(mesh, ms);
   napi_value timings = nullptr;
@@ -610,41 +666,48 @@ static napi_value mesh_result(napi_env env, rm_ctx* ctx, rm_mesh* mesh, bool nor
   return o;
 }
 
-// extractMesh(ctx, scene, grid, params | null[, sharp | null]) = rm_mesh_extract, or with a sharp block rm_mesh_extract_sharp; then the arrays
+// extractMesh(ctx, scene, grid, params | null[, sharp | null[, keep | null[, components]]]) = rm_mesh_extract, or with a sharp block
+// rm_mesh_extract_sharp; with a keep block rm_mesh_filter behind it; then the arrays
 static napi_value ExtractMesh(napi_env env, napi_callback_info info) {
-  size_t argc = 5;
-  napi_value argv[5];
+  size_t argc = 7;
+  napi_value argv[7];
   NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
-  const bool counted = argc == 4 || argc == 5;
+  const bool counted = argc >= 4 && argc <= 7;
   rm_ctx* ctx = counted ? get_external<rm_ctx>(env, argv[0]) : nullptr;
   rm_scene* scene = counted ? get_external<rm_scene>(env, argv[1]) : nullptr;
   RmGrid g;
   RmMeshParams p;
   RmMeshSharp s;
-  bool sharp = false;
-  if (!ctx || !scene || !get_grid(env, argv[2], &g) || !get_mesh_params(env, argv[3], &p) || (argc == 5 && !get_mesh_sharp(env, argv[4], &s, &sharp))) {
-    napi_throw_type_error(env, nullptr, "extractMesh(ctx, scene, grid, params | null[, sharp | null])");
+  RmMeshKeep k;
+  bool sharp = false, keep = false, components = false;
+  if (!ctx || !scene || !get_grid(env, argv[2], &g) || !get_mesh_params(env, argv[3], &p) || (argc >= 5 && !get_mesh_sharp(env, argv[4], &s, &sharp)) ||
+      (argc >= 6 && !get_mesh_keep(env, argv[5], &k, &keep)) || (argc == 7 && !get_bool(env, argv[6], &components))) {
+    napi_throw_type_error(env, nullptr, "extractMesh(ctx, scene, grid, params | null[, sharp | null[, keep | null[, components]]])");
     return nullptr;
   }
   rm_mesh* mesh = nullptr;
   if (sharp) {
     if (rm_mesh_extract_sharp(ctx, scene, &g, &p, &s, &mesh) != RM_OK) return throw_rm(env, ctx, "rm_mesh_extract_sharp");
   } else if (rm_mesh_extract(ctx, scene, &g, &p, &mesh) != RM_OK) return throw_rm(env, ctx, "rm_mesh_extract");
-  return mesh_result(env, ctx, mesh, p.normals != 0, p.colours != 0);
+  return mesh_result(env, ctx, mesh, p.normals != 0, p.colours != 0, keep ? &k : nullptr, components);
 }
 
-// meshFromValues(ctx, grid, values: Float32Array(corners), iso) = rm_mesh_from_values, then the arrays
+// meshFromValues(ctx, grid, values: Float32Array(corners), iso[, keep | null[, components]]) = rm_mesh_from_values, with a keep block
+// rm_mesh_filter behind it, then the arrays
 static napi_value MeshFromValues(napi_env env, napi_callback_info info) {
-  size_t argc = 4;
-  napi_value argv[4];
+  size_t argc = 6;
+  napi_value argv[6];
   NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
-  rm_ctx* ctx = argc == 4 ? get_external<rm_ctx>(env, argv[0]) : nullptr;
+  rm_ctx* ctx = argc >= 4 && argc <= 6 ? get_external<rm_ctx>(env, argv[0]) : nullptr;
+  RmMeshKeep k;
+  bool keep = false, components = false;
   RmGrid g;
   double iso = 0.0;
   void* d = nullptr;
   size_t n = 0;
-  if (!ctx || !get_grid(env, argv[1], &g) || !get_buffer(env, argv[2], &d, &n) || napi_get_value_double(env, argv[3], &iso) != napi_ok) {
-    napi_throw_type_error(env, nullptr, "meshFromValues(ctx, grid, values: Float32Array, iso)");
+  if (!ctx || !get_grid(env, argv[1], &g) || !get_buffer(env, argv[2], &d, &n) || napi_get_value_double(env, argv[3], &iso) != napi_ok ||
+      (argc >= 5 && !get_mesh_keep(env, argv[4], &k, &keep)) || (argc == 6 && !get_bool(env, argv[5], &components))) {
+    napi_throw_type_error(env, nullptr, "meshFromValues(ctx, grid, values: Float32Array, iso[, keep | null[, components]])");
     return nullptr;
   }
   float probe[1025];
@@ -655,7 +718,7 @@ static napi_value MeshFromValues(napi_env env, napi_callback_info info) {
   }
   rm_mesh* mesh = nullptr;
   if (rm_mesh_from_values(ctx, &g, static_cast<const float*>(d), (float)iso, &mesh) != RM_OK) return throw_rm(env, ctx, "rm_mesh_from_values");
-  return mesh_result(env, ctx, mesh, false, false);
+  return mesh_result(env, ctx, mesh, false, false, keep ? &k : nullptr, components);
 }
 
 // fbCreateStriped(ctx, width, height, stripeRows, parts, part[, gbuffer]): the stripes k with k % parts == part of a width x height image,
@@ -854,7 +917,7 @@ static napi_value Sizes(napi_env env, napi_callback_info) {
       {"RmMaterial", (uint32_t)sizeof(RmMaterial)}, {"RmRect", (uint32_t)sizeof(RmRect)}, {"RmSurface", (uint32_t)sizeof(RmSurface)}, {"RmDenoise", (uint32_t)sizeof(RmDenoise)},
       {"RmDenoiseVariance", (uint32_t)sizeof(RmDenoiseVariance)}, {"RmDespeckle", (uint32_t)sizeof(RmDespeckle)}, {"RmFilters", (uint32_t)sizeof(RmFilters)}, {"RmFrameStats", (uint32_t)sizeof(RmFrameStats)},
       {"RmAutoExposure", (uint32_t)sizeof(RmAutoExposure)}, {"RmDisplay", (uint32_t)sizeof(RmDisplay)}, {"RmGrid", (uint32_t)sizeof(RmGrid)},
-      {"RmMeshParams", (uint32_t)sizeof(RmMeshParams)}, {"RmMeshSharp", (uint32_t)sizeof(RmMeshSharp)}, {"abi", (uint32_t)rm_abi_version()}};
+      {"RmMeshParams", (uint32_t)sizeof(RmMeshParams)}, {"RmMeshSharp", (uint32_t)sizeof(RmMeshSharp)}, {"RmMeshKeep", (uint32_t)sizeof(RmMeshKeep)}, {"abi", (uint32_t)rm_abi_version()}};
   for (const auto& it : items) {
     NAPI_OK(napi_create_uint32(env, it.v, &v));
     NAPI_OK(napi_set_named_property(env, o, it.k, v));
@@ -867,7 +930,7 @@ static napi_value Init(napi_env env, napi_value exports) {
       {"ctxCreate", CtxCreate}, {"ctxDestroy", CtxDestroy}, {"sync", Sync}, {"sceneCreate", SceneCreate}, {"sceneDestroy", SceneDestroy},
       {"fbCreate", FbCreate}, {"fbClear", FbClear}, {"fbDestroy", FbDestroy}, {"fbDownload", FbDownload}, {"present", Present}, {"denoise", Denoise}, {"presentDenoised", PresentDenoised}, {"denoiseVariance", DenoiseVariance}, {"presentDenoisedVariance", PresentDenoisedVariance}, {"filter", Filter}, {"presentFiltered", PresentFiltered}, {"presentDisplay", PresentDisplay}, {"presentLinear", PresentLinear}, {"frameStats", FrameStats}, {"statsExposure", StatsExposure}, {"statsPercentile", StatsPercentile}, {"renderSample", RenderSample}, {"renderSamples", RenderSamples},
       {"fbCreateStriped", FbCreateStriped}, {"fbRows", FbRows}, {"setSamplesInFlight", SetSamplesInFlight}, {"presentSharded", PresentSharded}, {"presentShardedStart", PresentShardedStart}, {"presentShardedFinish", PresentShardedFinish},
-      {"meshBlocks", MeshBlocks}, {"meshSharpBlock", MeshSharpBlock}, {"sdfGrid", SdfGrid}, {"extractMesh", ExtractMesh}, {"meshFromValues", MeshFromValues}, {"sizes", Sizes}};
+      {"meshBlocks", MeshBlocks}, {"meshSharpBlock", MeshSharpBlock}, {"meshKeepBlock", MeshKeepBlock}, {"sdfGrid", SdfGrid}, {"extractMesh", ExtractMesh}, {"meshFromValues", MeshFromValues}, {"sizes", Sizes}};
   for (const auto& f : fns) {
     napi_value fn;
     if (napi_create_function(env, f.name, NAPI_AUTO_LENGTH, f.fn, nullptr, &fn) != napi_ok) return nullptr;

@@ -97,10 +97,26 @@ def mesh_sharp(**fields) -> abi.RmMeshSharp:
     return abi.RmMeshSharp(refine=int(refine), normal_delta=float(p["normal_delta"]), threshold=float(p["threshold"]), reserved=0)
 
 
+def mesh_keep(**fields) -> abi.RmMeshKeep:
+    """The abi.RmMeshKeep of Context.extract_mesh(..., keep=...) / mesh_from_values(..., keep=...), over abi.MESH_KEEP_DEFAULTS: min_triangles (a
+    component passes with at least that many triangles, >= 0) and largest (0 keeps every passing component, k > 0 only the k with the most
+    triangles, the lower component index first among equals).  Checked as the library checks it: ValueError otherwise, and for unknown keys."""
+    unknown = set(fields) - set(abi.MESH_KEEP_DEFAULTS)
+    if unknown:
+        raise ValueError(f"mesh: unknown keep parameter {sorted(unknown)[0]}")
+    p = {**abi.MESH_KEEP_DEFAULTS, **fields}
+    for name in ("min_triangles", "largest"):
+        v = p[name]
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 0 <= int(v) <= 0x7FFFFFFF:
+            raise ValueError(f"mesh: keep {name} must be an integer in 0..2^31 - 1")
+    return abi.RmMeshKeep(min_triangles=int(p["min_triangles"]), largest=int(p["largest"]))
+
+
 @dataclass
 class Mesh:
     """A triangle mesh as numpy arrays: positions [V, 3] float32, triangles [T, 3] uint32 (counter-clockwise seen from outside), cells
-    [V] uint32 (each vertex's linear cell index in `grid`), and normals / colours [V, 3] float32 or None."""
+    [V] uint32 (each vertex's linear cell index in `grid`), and normals / colours [V, 3] float32 or None.  labels [V] uint32 (each vertex's
+    connected component) and component_sizes [C, 2] uint32 ((vertices, triangles) per component) only when the call asked for components."""
     positions: np.ndarray
     triangles: np.ndarray
     cells: Optional[np.ndarray] = None
@@ -108,6 +124,8 @@ class Mesh:
     colours: Optional[np.ndarray] = None
     grid: Optional[Grid] = None
     timings: Optional[dict] = None  # rm_mesh_timings: milliseconds of sampling, meshing, attributes (device events)
+    labels: Optional[np.ndarray] = None
+    component_sizes: Optional[np.ndarray] = None
 
     @property
     def vertices(self) -> int:

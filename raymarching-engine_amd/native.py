@@ -42,6 +42,7 @@ EXPORTS = [
     "rm_display_default", "rm_present_display", "rm_present_display_device", "rm_present_linear",
     "rm_grid_axis", "rm_sdf_grid", "rm_sdf_grid_device", "rm_mesh_params_default", "rm_mesh_extract", "rm_mesh_from_values", "rm_mesh_counts", "rm_mesh_timings",
     "rm_mesh_download", "rm_mesh_device_ptr", "rm_mesh_destroy", "rm_mesh_sharp_default", "rm_mesh_extract_sharp",
+    "rm_mesh_keep_default", "rm_mesh_components", "rm_mesh_components_download", "rm_mesh_filter",
 ]
 
 # G-buffer formats of a framebuffer (include/hip_raymarch.h RM_GBUFFER_*): "f32" (the default: the software GL stack's planes, which the
@@ -410,6 +411,10 @@ def load_library(path=None):
         "rm_mesh_destroy": (None, [vp]),
         "rm_mesh_sharp_default": (None, [C.POINTER(abi.RmMeshSharp)]),
         "rm_mesh_extract_sharp": (ip, [vp, vp, C.POINTER(abi.RmGrid), C.POINTER(abi.RmMeshParams), C.POINTER(abi.RmMeshSharp), C.POINTER(vp)]),
+        "rm_mesh_keep_default": (None, [C.POINTER(abi.RmMeshKeep)]),
+        "rm_mesh_components": (ip, [vp, C.POINTER(C.c_ulonglong)]),
+        "rm_mesh_components_download": (ip, [vp, ip, vp, C.c_size_t]),
+        "rm_mesh_filter": (ip, [vp, C.POINTER(abi.RmMeshKeep), C.POINTER(vp)]),
     }
     for name, (res, args) in sig.items():
         if name.startswith("rm_debug_") and not hasattr(lib, name) and os.environ.get("RM_LIB"):
@@ -706,11 +711,19 @@ class Context:
         g = grid.to_c()
         self._check(self.lib.rm_sdf_grid_device(self.h, scene.h, C.byref(g), int(flags), C.c_void_p(out_ptr), C.c_void_p(stream) if stream else None))
 
-    def _take_mesh(self, handle, grid, normals=False, colours=False):
-        """The arrays of a mesh handle as a mesh.Mesh (normals / colours: whether the call that made it asked for them); destroys the handle."""
+    def _take_mesh(self, handle, grid, normals=False, colours=False, keep=None, components=False):
+        """The arrays of a mesh handle as a mesh.Mesh (normals / colours: whether the call that made it asked for them); destroys the handle.
+        keep (an abi.RmMeshKeep): the mesh is first filtered on the device (rm_mesh_filter) and the filtered one is what is downloaded; components: its labels and
+        component sizes come with it."""
         from .mesh import Mesh
 
+        handles = [handle]
         try:
+            if keep is not None:
+                filtered = C.c_void_p()
+                self._check(self.lib.rm_mesh_filter(handle, C.byref(keep), C.byref(filtered)))
+                handles.append(filtered)
+                handle = filtered
             counts, ms = (C.c_ulonglong * 2)(), (C.c_float * 3)()
             self._check(self.lib.rm_mesh_counts(handle, counts))
             self._check(self.lib.rm_mesh_timings(handle, ms))
@@ -726,18 +739,47 @@ class Context:
                 a = np.empty(shape, dtype)
                 self._check(self.lib.rm_mesh_download(handle, what, a.ctypes.data_as(C.c_void_p), a.nbytes))
                 arrays[name] = a
+            if components:
+                count = C.c_ulonglong()
+                self._check(self.lib.rm_mesh_components(handle, C.byref(count)))
+                for name, what, shape in (("labels", abi.RM_MESH_PART_LABELS, (v,)), ("component_sizes", abi.RM_MESH_PART_SIZES, (int(count.value), 2))):
+                    a = np.empty(shape, np.uint32)
+                    self._check(self.lib.rm_mesh_components_download(handle, what, a.ctypes.data_as(C.c_void_p), a.nbytes))
+                    arrays[name] = a
             return Mesh(grid=grid, timings=dict(sampling=float(ms[0]), meshing=float(ms[1]), attributes=float(ms[2])), **arrays)
         finally:
-            self.lib.rm_mesh_destroy(handle)
+            for h in reversed(handles):
+                self.lib.rm_mesh_destroy(h)
+
+    @staticmethod
+    def _mesh_keep(keep) -> abi.RmMeshKeep:
+        """The `keep` of extract_mesh / mesh_from_values as an abi.RmMeshKeep: True (the defaults), a dict of mesh.mesh_keep's arguments or an
+        abi.RmMeshKeep."""
+        from .mesh import mesh_keep
+
+        if isinstance(keep, abi.RmMeshKeep):
+            k = mesh_keep(min_triangles=keep.min_triangles, largest=keep.largest)
+            k.reserved[0], k.reserved[1] = keep.reserved[0], keep.reserved[1]  # (the library's to refuse)
+            return k
+        if keep is True:
+            return mesh_keep()
+        if isinstance(keep, dict):
+            return mesh_keep(**keep)
+        raise ValueError("mesh: keep must be None, True, a dict of mesh_keep's arguments or an abi.RmMeshKeep")
 
     def extract_mesh(self, scene: "SceneHandle", grid, iso: float = 0.0, normals: bool = True, colours: bool = False, flags: int = 0,
-                     normal_delta: float = 1e-5, sharp=None):
+                     normal_delta: float = 1e-5, sharp=None, *, keep=None, components: bool = False):
         """The level set `iso` of the scene on `grid` (mesh.Grid) as a mesh.Mesh: rm_mesh_extract -- the distances sampled and meshed
         (surface nets) on the device, with per-vertex normals / diffuse colours from the scene's probes when asked for.  `sharp`: None is
         that call; True (the defaults), a dict of mesh.mesh_sharp's arguments or an abi.RmMeshSharp is rm_mesh_extract_sharp -- the same
-        triangles with every vertex at its cell's QEF minimiser, which keeps the edges and corners of hard-edged scenes."""
+        triangles with every vertex at its cell's QEF minimiser, which keeps the edges and corners of hard-edged scenes.  `keep`: None
+        is that mesh; True (the defaults: drop unreferenced vertices), a dict of mesh.mesh_keep's arguments or an abi.RmMeshKeep filters its
+        connected components on the device before anything is downloaded (rm_mesh_filter).  `components`: the returned mesh carries
+        labels and component_sizes (rm_mesh_components)."""
         from .mesh import mesh_params, mesh_sharp
 
+        if keep is not None:
+            keep = self._mesh_keep(keep)  # (refused before anything runs)
         g, p = grid.to_c(), mesh_params(iso=iso, normals=normals, colours=colours, flags=flags, normal_delta=normal_delta)
         h = C.c_void_p()
         if sharp is None:
@@ -753,17 +795,20 @@ class Context:
             else:
                 raise ValueError("mesh: sharp must be None, True, a dict of mesh_sharp's arguments or an abi.RmMeshSharp")
             self._check(self.lib.rm_mesh_extract_sharp(self.h, scene.h, C.byref(g), C.byref(p), C.byref(s), C.byref(h)))
-        return self._take_mesh(h, grid, normals=p.normals, colours=p.colours)
+        return self._take_mesh(h, grid, normals=p.normals, colours=p.colours, keep=keep, components=components)
 
-    def mesh_from_values(self, grid, values: np.ndarray, iso: float = 0.0):
-        """The mesher alone on the caller's field: `values` float32 [nz + 1, ny + 1, nx + 1] (rm_mesh_from_values)."""
+    def mesh_from_values(self, grid, values: np.ndarray, iso: float = 0.0, *, keep=None, components: bool = False):
+        """The mesher alone on the caller's field: `values` float32 [nz + 1, ny + 1, nx + 1] (rm_mesh_from_values).  keep and components:
+        as in extract_mesh."""
+        if keep is not None:
+            keep = self._mesh_keep(keep)
         g = grid.to_c()
         v = np.ascontiguousarray(values, np.float32)
         if v.shape != grid.shape:
             raise ValueError(f"values must have the shape {grid.shape} of the grid's corners, not {v.shape}")
         h = C.c_void_p()
         self._check(self.lib.rm_mesh_from_values(self.h, C.byref(g), _fp(v), float(iso), C.byref(h)))
-        return self._take_mesh(h, grid)
+        return self._take_mesh(h, grid, keep=keep, components=components)
 
     def probe_camera(self, uniforms: abi.RmUniforms, width: int, height: int) -> np.ndarray:
         out = np.empty((height, width, 8), np.float32)
