@@ -11,6 +11,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <limits>
+#include <memory>
 #include <mutex>
 #include <new>
 #include <string>
@@ -188,6 +189,43 @@ struct Scratch {
   }
 };
 
+// Device memory that one call, or one mesh, owns: freed with its owner.  Waiting for the stream before memory that a kernel may still
+// read goes is the owner's business (rm_mesh_destroy; the waits of the probe and mesh entries).
+struct DeviceArray {
+  void* p = nullptr;
+  DeviceArray() = default;
+  DeviceArray(DeviceArray&& o) noexcept : p(o.p) { o.p = nullptr; }  // moves, never copies: one owner
+  ~DeviceArray() { release(); }
+  void release() { if (p) (void)hipFree(p); p = nullptr; }
+  hipError_t reserve(size_t bytes) { release(); return bytes ? hipMalloc(&p, bytes) : hipSuccess; }  // (0 bytes: NULL)
+  float* f32() const { return static_cast<float*>(p); }
+  unsigned int* u32() const { return static_cast<unsigned int*>(p); }
+  unsigned long long* u64() const { return static_cast<unsigned long long*>(p); }
+};
+
+// Stage timing of the mesh entries (rm_mesh_timings): a span is a pair of events on the context's stream, made with the first mesh
+// that runs the stage.
+struct MeshSpans {
+  enum { SAMPLE, COUNT_SCAN, EMIT, SHARPEN, ATTRIBUTES, LABEL, KEEP_FLAGS, GATHER, COUNT };
+  hipEvent_t ev[COUNT][2] = {};
+  hipError_t begin(int span, hipStream_t stream) { return record(ev[span][0], stream); }
+  hipError_t end(int span, hipStream_t stream) { return record(ev[span][1], stream); }
+  // milliseconds of a span that the stream has passed; 0 when the runtime cannot tell
+  float ms(int span) const {
+    float t = 0.0f;
+    return hipEventElapsedTime(&t, ev[span][0], ev[span][1]) == hipSuccess ? t : 0.0f;
+  }
+  void destroy() {
+    for (auto& pair : ev)
+      for (hipEvent_t e : pair)
+        if (e) (void)hipEventDestroy(e);
+  }
+  static hipError_t record(hipEvent_t& e, hipStream_t stream) {
+    const hipError_t made = e ? hipSuccess : hipEventCreate(&e);
+    return made != hipSuccess ? made : hipEventRecord(e, stream);
+  }
+};
+
 // rm_present_sharded (one process driving several GPUs): this context's rows of the payload, and on the context that shows the
 // frame -- the root -- the gathered parts and the frame in image order; grown on demand (scratch_reserve), freed with the context.
 struct ShardPresent {
@@ -246,7 +284,7 @@ struct rm_ctx {
   hipStream_t lpt_stream = nullptr;
   bool lpt_enabled = true;
   hipEvent_t switch_ev = nullptr;  // orders the old stream before the new one in rm_ctx_set_stream
-  hipEvent_t mesh_ev[15] = {};      // rm_mesh_extract(_sharp) / rm_mesh_from_values: the marks between their stages (rm_mesh_timings), made with the first mesh
+  MeshSpans mesh_spans;             // the mesh entries' stages (rm_mesh_timings)
   hipEvent_t mesh_order = nullptr; // rm_sdf_grid_device on a caller's stream: the context's stream waits behind that launch (sdf_grid_enqueue)
   std::unordered_map<void*, size_t> buffers;  // rm_buffer_create: base address -> bytes
   Scratch scratch[SCRATCH_COUNT];  // scratch_reserve
@@ -324,6 +362,26 @@ static int fail(rm_ctx* ctx, int code, const std::string& msg) {
     if (e_ != hipSuccess) return fail(ctx, RM_ERR_DEVICE, std::string(#expr ": ") + hipGetErrorString(e_)); \
   } while (0)
 
+// An entry's refusals, with its name in front of the text: RM_ERR_INVALID unless the code says otherwise.
+struct Refuse {
+  rm_ctx* ctx;
+  const char* who;
+  int operator()(const char* what, int code = RM_ERR_INVALID) const { return fail(ctx, code, std::string(who) + ": " + what); }
+};
+// ... and RM_HIP for the entries that put their name, not the expression, in front of the runtime's text
+#define RM_HIP_AS(refuse, expr)                                                   \
+  do {                                                                            \
+    hipError_t e_ = (expr);                                                       \
+    if (e_ != hipSuccess) return refuse(hipGetErrorString(e_), RM_ERR_DEVICE);    \
+  } while (0)
+
+// The pair (context, scene) of an entry that takes both; `others`: whether the entry's further pointers, part of the same test, are there.
+static int scene_check(const Refuse& refuse, const rm_scene* scene, bool others) {
+  if (!refuse.ctx || !scene || !others) return refuse("NULL argument");
+  if (scene->ctx != refuse.ctx) return refuse("the scene belongs to another context");
+  return RM_OK;
+}
+
 extern "C" {
 
 int rm_abi_version(void) { return RM_ABI_VERSION; }
@@ -398,8 +456,7 @@ void rm_ctx_destroy(rm_ctx* ctx) {
   if (ctx->cull_order) (void)hipEventDestroy(ctx->cull_order);
   for (auto& b : ctx->buffers) (void)hipFree(b.first);  // rm_buffer_create'd memory the host did not destroy
   if (ctx->switch_ev) (void)hipEventDestroy(ctx->switch_ev);
-  for (hipEvent_t e : ctx->mesh_ev)
-    if (e) (void)hipEventDestroy(e);
+  ctx->mesh_spans.destroy();
   if (ctx->mesh_order) (void)hipEventDestroy(ctx->mesh_order);
   if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);
   if (ctx->ev1) (void)hipEventDestroy(ctx->ev1);
@@ -2246,58 +2303,54 @@ static hipError_t probe_enqueue(rm_ctx* ctx, rm_scene* scene, int what, const fl
 }
 
 int rm_probe(rm_ctx* ctx, rm_scene* scene, int what, const float* in, int n, float param, int flags, float* out) {
-  if (!ctx || !scene || !in || !out) return fail(ctx, RM_ERR_INVALID, "rm_probe: NULL argument");
-  if (scene->ctx != ctx) return fail(ctx, RM_ERR_INVALID, "rm_probe: the scene belongs to another context");
-  if (what < RM_PROBE_SDF || what > RM_PROBE_CAST_SHADOW) return fail(ctx, RM_ERR_INVALID, "rm_probe: unknown probe");
+  const Refuse refuse{ctx, "rm_probe"};
+  if (int rc = scene_check(refuse, scene, in && out)) return rc;
+  if (what < RM_PROBE_SDF || what > RM_PROBE_CAST_SHADOW) return refuse("unknown probe");
   if (n <= 0) return RM_OK;
   static const int in_w[6] = {3, 6, 3, 3, 6, 9}, out_w[6] = {1, 3, 3, 12, 1, 1};
   RM_HIP(ctx, hipSetDevice(ctx->device));
-  float *d_in = nullptr, *d_out = nullptr;
+  DeviceArray d_in, d_out;  // (freed behind the wait below; a call that fails before it leaves that wait to hipFree)
   const size_t in_bytes = sizeof(float) * (size_t)in_w[what] * (size_t)n, out_bytes = sizeof(float) * (size_t)out_w[what] * (size_t)n;
-  RM_HIP(ctx, hipMalloc(reinterpret_cast<void**>(&d_in), in_bytes));
-  hipError_t e = hipMalloc(reinterpret_cast<void**>(&d_out), out_bytes);
-  if (e == hipSuccess) e = hipMemcpyAsync(d_in, in, in_bytes, hipMemcpyHostToDevice, ctx->stream);
-  if (e == hipSuccess && scene_cull_grid(ctx, scene, flags, 1ll << 40) != RM_OK) e = hipErrorUnknown;  // (a probe is a test's call: with the grid)
-  if (e == hipSuccess) e = probe_enqueue(ctx, scene, what, d_in, d_out, n, param, flags, ctx->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(out, d_out, out_bytes, hipMemcpyDeviceToHost, ctx->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-  (void)hipFree(d_in);
-  if (d_out) (void)hipFree(d_out);
-  if (e != hipSuccess) return fail(ctx, RM_ERR_DEVICE, std::string("rm_probe: ") + hipGetErrorString(e));
+  RM_HIP(ctx, d_in.reserve(in_bytes));
+  RM_HIP_AS(refuse, d_out.reserve(out_bytes));
+  RM_HIP_AS(refuse, hipMemcpyAsync(d_in.p, in, in_bytes, hipMemcpyHostToDevice, ctx->stream));
+  if (int rc = scene_cull_grid(ctx, scene, flags, 1ll << 40)) return rc;  // (a probe is a test's call: with the grid)
+  RM_HIP_AS(refuse, probe_enqueue(ctx, scene, what, d_in.f32(), d_out.f32(), n, param, flags, ctx->stream));
+  RM_HIP_AS(refuse, hipMemcpyAsync(out, d_out.p, out_bytes, hipMemcpyDeviceToHost, ctx->stream));
+  RM_HIP_AS(refuse, hipStreamSynchronize(ctx->stream));
   return RM_OK;
 }
 
 static int camera_rng(rm_ctx* ctx, const RmUniforms* u, int width, int height, int what, int count, float* out) {
-  if (!ctx || !u || !out || width < 1 || height < 1 || count < 1) return fail(ctx, RM_ERR_INVALID, "probe: bad argument");
+  const Refuse refuse{ctx, "probe"};
+  if (!ctx || !u || !out || width < 1 || height < 1 || count < 1) return refuse("bad argument");
   RM_HIP(ctx, hipSetDevice(ctx->device));
-  float* d_out = nullptr;
+  DeviceArray d_out;
   const size_t bytes = sizeof(float) * (size_t)width * (size_t)height * (size_t)(what == 1 ? count : 8);
-  RM_HIP(ctx, hipMalloc(reinterpret_cast<void**>(&d_out), bytes));
-  hipError_t e = ctx->gl_stack ? rm_gl_launch_camera_rng(u, width, height, what, count, d_out, ctx->stream) : rm::launch_camera_rng(*u, width, height, what, count, d_out, ctx->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(out, d_out, bytes, hipMemcpyDeviceToHost, ctx->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-  (void)hipFree(d_out);
-  if (e != hipSuccess) return fail(ctx, RM_ERR_DEVICE, std::string("probe: ") + hipGetErrorString(e));
+  RM_HIP(ctx, d_out.reserve(bytes));
+  RM_HIP_AS(refuse, ctx->gl_stack ? rm_gl_launch_camera_rng(u, width, height, what, count, d_out.f32(), ctx->stream)
+                                  : rm::launch_camera_rng(*u, width, height, what, count, d_out.f32(), ctx->stream));
+  RM_HIP_AS(refuse, hipMemcpyAsync(out, d_out.p, bytes, hipMemcpyDeviceToHost, ctx->stream));
+  RM_HIP_AS(refuse, hipStreamSynchronize(ctx->stream));
   return RM_OK;
 }
 
 int rm_probe_math(rm_ctx* ctx, int fn, const float* a, const float* b, int n, float* out) {
-  if (!ctx || !a || !out || n < 1 || fn < 0 || fn >= RM_MATH_COUNT) return fail(ctx, RM_ERR_INVALID, "rm_probe_math: bad argument");
+  const Refuse refuse{ctx, "rm_probe_math"};
+  if (!ctx || !a || !out || n < 1 || fn < 0 || fn >= RM_MATH_COUNT) return refuse("bad argument");
   const bool two = fn == RM_MATH_POW || fn == RM_MATH_ATAN2 || fn == RM_MATH_POW_PAIR_NM1 || fn == RM_MATH_POW_PAIR_N || fn == RM_MATH_DIV;
-  if (two && !b) return fail(ctx, RM_ERR_INVALID, "rm_probe_math: this function takes two arguments");
+  if (two && !b) return refuse("this function takes two arguments");
   RM_HIP(ctx, hipSetDevice(ctx->device));
-  float* d = nullptr;  // a | b | out
+  DeviceArray abo;  // a | b | out
   const size_t bytes = sizeof(float) * (size_t)n;
-  RM_HIP(ctx, hipMalloc(reinterpret_cast<void**>(&d), 3 * bytes));
-  hipError_t e = hipMemcpyAsync(d, a, bytes, hipMemcpyHostToDevice, ctx->stream);
-  if (e == hipSuccess && two) e = hipMemcpyAsync(d + n, b, bytes, hipMemcpyHostToDevice, ctx->stream);
-  if (e == hipSuccess)
-    e = ctx->gl_stack ? rm_gl_launch_math_probe(fn, d, two ? d + n : nullptr, n, d + 2 * (size_t)n, ctx->stream)
-                      : rm::launch_math_probe(fn, d, two ? d + n : nullptr, n, d + 2 * (size_t)n, ctx->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(out, d + 2 * (size_t)n, bytes, hipMemcpyDeviceToHost, ctx->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-  (void)hipFree(d);
-  if (e != hipSuccess) return fail(ctx, RM_ERR_DEVICE, std::string("rm_probe_math: ") + hipGetErrorString(e));
+  RM_HIP(ctx, abo.reserve(3 * bytes));
+  float* d = abo.f32();
+  RM_HIP_AS(refuse, hipMemcpyAsync(d, a, bytes, hipMemcpyHostToDevice, ctx->stream));
+  if (two) RM_HIP_AS(refuse, hipMemcpyAsync(d + n, b, bytes, hipMemcpyHostToDevice, ctx->stream));
+  RM_HIP_AS(refuse, ctx->gl_stack ? rm_gl_launch_math_probe(fn, d, two ? d + n : nullptr, n, d + 2 * (size_t)n, ctx->stream)
+                                  : rm::launch_math_probe(fn, d, two ? d + n : nullptr, n, d + 2 * (size_t)n, ctx->stream));
+  RM_HIP_AS(refuse, hipMemcpyAsync(out, d + 2 * (size_t)n, bytes, hipMemcpyDeviceToHost, ctx->stream));
+  RM_HIP_AS(refuse, hipStreamSynchronize(ctx->stream));
   return RM_OK;
 }
 

@@ -598,71 +598,56 @@ static napi_value SdfGrid(napi_env env, napi_callback_info info) {
 // first filtered on the device (rm_mesh_filter) and the filtered one is what is copied; components: labels: Uint32Array(V) and componentSizes:
 // Uint32Array(2 C) come with it (rm_mesh_components)
 static napi_value mesh_result(napi_env env, rm_ctx* ctx, rm_mesh* mesh, bool normals, bool colours, const RmMeshKeep* keep = nullptr, bool components = false) {
+  struct Guard {  // the handle in hand is destroyed on every way out
+    rm_mesh* h;
+    ~Guard() { rm_mesh_destroy(h); }
+  } guard{mesh};
+  const auto napi_failed = [&]() -> napi_value {
+    napi_throw_error(env, nullptr, "N-API call failed while the mesh was copied");
+    return nullptr;
+  };
   if (keep) {
     rm_mesh* filtered = nullptr;
-    const int rc = rm_mesh_filter(mesh, keep, &filtered);
-    napi_value r = rc != RM_OK ? throw_rm(env, ctx, "rm_mesh_filter") : nullptr;
+    if (rm_mesh_filter(mesh, keep, &filtered) != RM_OK) return throw_rm(env, ctx, "rm_mesh_filter");
     rm_mesh_destroy(mesh);
-    if (rc != RM_OK) return r;
-    mesh = filtered;
+    guard.h = mesh = filtered;
   }
-  unsigned long long counts[2] = {0, 0};
+  unsigned long long counts[2] = {0, 0}, parts = 0;
   rm_mesh_counts(mesh, counts);
-  static const struct { const char* name; int what; napi_typedarray_type type; int per_vertex, per_triangle; } ARRAYS[] = {
-      {"positions", RM_MESH_POSITIONS, napi_float32_array, 3, 0}, {"normals", RM_MESH_NORMALS, napi_float32_array, 3, 0}, {"colours", RM_MESH_COLOURS, napi_float32_array, 3, 0},
-      {"triangles", RM_MESH_TRIANGLES, napi_uint32_array, 0, 3}, {"cells", RM_MESH_CELLS, napi_uint32_array, 1, 0}};
+  enum { ALWAYS, NORMALS, COLOURS, COMPONENTS };  // when an array is there: with every mesh, or when the call asked for it
+  static const struct { const char* name; int what; napi_typedarray_type type; int when, per_vertex, per_triangle, per_part; } ARRAYS[] = {
+      {"positions", RM_MESH_POSITIONS, napi_float32_array, ALWAYS, 3, 0, 0},  {"normals", RM_MESH_NORMALS, napi_float32_array, NORMALS, 3, 0, 0},
+      {"colours", RM_MESH_COLOURS, napi_float32_array, COLOURS, 3, 0, 0},     {"triangles", RM_MESH_TRIANGLES, napi_uint32_array, ALWAYS, 0, 3, 0},
+      {"cells", RM_MESH_CELLS, napi_uint32_array, ALWAYS, 1, 0, 0},           {"labels", RM_MESH_PART_LABELS, napi_uint32_array, COMPONENTS, 1, 0, 0},
+      {"componentSizes", RM_MESH_PART_SIZES, napi_uint32_array, COMPONENTS, 0, 0, 2}};
   napi_value o = nullptr;
-  bool ok = napi_create_object(env, &o) == napi_ok;
-  bool refused = false;
+  if (napi_create_object(env, &o) != napi_ok) return napi_failed();
   for (const auto& a : ARRAYS) {
-    if (!ok) break;
     napi_value v = nullptr;
-    if ((a.what == RM_MESH_NORMALS && !normals) || (a.what == RM_MESH_COLOURS && !colours)) {
-      ok = napi_get_null(env, &v) == napi_ok;  // the mesh was made without this array
+    if (a.when == COMPONENTS) {
+      if (!components) continue;  // (no property at all)
+      if (rm_mesh_components(mesh, &parts) != RM_OK) return throw_rm(env, ctx, "rm_mesh_download");  // (labelled once, behind the five arrays)
+    }
+    if ((a.when == NORMALS && !normals) || (a.when == COLOURS && !colours)) {
+      if (napi_get_null(env, &v) != napi_ok) return napi_failed();  // the mesh was made without this array
     } else {
-      const size_t count = (size_t)counts[0] * a.per_vertex + (size_t)counts[1] * a.per_triangle;
+      const size_t count = (size_t)counts[0] * a.per_vertex + (size_t)counts[1] * a.per_triangle + (size_t)parts * a.per_part;
       void* data = nullptr;
-      v = make_array(env, a.type, count, &data);
-      ok = v != nullptr;
-      if (!ok) break;
-      if (rm_mesh_download(mesh, a.what, data, count * 4) != RM_OK) { refused = true; break; }
+      if (!(v = make_array(env, a.type, count, &data))) return napi_failed();
+      const int rc = a.when == COMPONENTS ? rm_mesh_components_download(mesh, a.what, data, count * 4) : rm_mesh_download(mesh, a.what, data, count * 4);
+      if (rc != RM_OK) return throw_rm(env, ctx, "rm_mesh_download");
     }
-    ok = ok && napi_set_named_property(env, o, a.name, v) == napi_ok;
-  }
-  if (components && ok && !refused) {
-    unsigned long long parts = 0;
-    refused = rm_mesh_components(mesh, &parts) != RM_OK;
-    static const struct { const char* name; int what; } PARTS[] = {{"labels", RM_MESH_PART_LABELS}, {"componentSizes", RM_MESH_PART_SIZES}};
-    for (const auto& a : PARTS) {
-      if (!ok || refused) break;
-      const size_t count = a.what == RM_MESH_PART_LABELS ? (size_t)counts[0] : 2u * (size_t)parts;
-      void* data = nullptr;
-      napi_value v = make_array(env, napi_uint32_array, count, &data);
-      ok = v != nullptr;
-      if (!ok) break;
-      if (rm_mesh_components_download(mesh, a.what, data, count * 4) != RM_OK) { refused = true; break; }
-      ok = napi_set_named_property(env, o, a.name, v) == napi_ok;
-    }
+    if (napi_set_named_property(env, o, a.name, v) != napi_ok) return napi_failed();
   }
   float ms[3] = {0.0f, 0.0f, 0.0f};
   rm_mesh_timings(mesh, ms);
   napi_value timings = nullptr;
-  ok = ok && !refused && napi_create_array_with_length(env, 3, &timings) == napi_ok;
-  for (uint32_t k = 0; ok && k < 3; k++) {
+  if (napi_create_array_with_length(env, 3, &timings) != napi_ok) return napi_failed();
+  for (uint32_t k = 0; k < 3; k++) {
     napi_value x;
-    ok = napi_create_double(env, (double)ms[k], &x) == napi_ok && napi_set_element(env, timings, k, x) == napi_ok;
+    if (napi_create_double(env, (double)ms[k], &x) != napi_ok || napi_set_element(env, timings, k, x) != napi_ok) return napi_failed();
   }
-  ok = refused || (ok && napi_set_named_property(env, o, "timings", timings) == napi_ok);
-  if (refused) {
-    napi_value r = throw_rm(env, ctx, "rm_mesh_download");
-    rm_mesh_destroy(mesh);
-    return r;
-  }
-  rm_mesh_destroy(mesh);
-  if (!ok) {
-    napi_throw_error(env, nullptr, "N-API call failed while the mesh was copied");
-    return nullptr;
-  }
+  if (napi_set_named_property(env, o, "timings", timings) != napi_ok) return napi_failed();
   return o;
 }
 

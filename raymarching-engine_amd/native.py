@@ -752,20 +752,27 @@ class Context:
                 self.lib.rm_mesh_destroy(h)
 
     @staticmethod
-    def _mesh_keep(keep) -> abi.RmMeshKeep:
-        """The `keep` of extract_mesh / mesh_from_values as an abi.RmMeshKeep: True (the defaults), a dict of mesh.mesh_keep's arguments or an
-        abi.RmMeshKeep."""
-        from .mesh import mesh_keep
+    def _mesh_block(name: str, value, struct):
+        """The `sharp` / `keep` of extract_mesh / mesh_from_values as its struct, through mesh.mesh_<name>'s checks: None stays None, True is
+        the defaults, a dict that function's arguments, a struct its fields -- whose `reserved` is left for the library to refuse."""
+        from . import mesh
 
-        if isinstance(keep, abi.RmMeshKeep):
-            k = mesh_keep(min_triangles=keep.min_triangles, largest=keep.largest)
-            k.reserved[0], k.reserved[1] = keep.reserved[0], keep.reserved[1]  # (the library's to refuse)
-            return k
-        if keep is True:
-            return mesh_keep()
-        if isinstance(keep, dict):
-            return mesh_keep(**keep)
-        raise ValueError("mesh: keep must be None, True, a dict of mesh_keep's arguments or an abi.RmMeshKeep")
+        make = getattr(mesh, "mesh_" + name)
+        if value is None:
+            return None
+        if isinstance(value, struct):
+            block = make(**{f: getattr(value, f) for f, _ in struct._fields_ if f != "reserved"})
+            block.reserved = value.reserved
+            return block
+        if value is True:
+            return make()
+        if isinstance(value, dict):
+            return make(**value)
+        raise ValueError(f"mesh: {name} must be None, True, a dict of mesh_{name}'s arguments or an abi.{struct.__name__}")
+
+    @staticmethod
+    def _mesh_keep(keep):
+        return Context._mesh_block("keep", keep, abi.RmMeshKeep)
 
     def extract_mesh(self, scene: "SceneHandle", grid, iso: float = 0.0, normals: bool = True, colours: bool = False, flags: int = 0,
                      normal_delta: float = 1e-5, sharp=None, *, keep=None, components: bool = False):
@@ -776,32 +783,22 @@ class Context:
         is that mesh; True (the defaults: drop unreferenced vertices), a dict of mesh.mesh_keep's arguments or an abi.RmMeshKeep filters its
         connected components on the device before anything is downloaded (rm_mesh_filter).  `components`: the returned mesh carries
         labels and component_sizes (rm_mesh_components)."""
-        from .mesh import mesh_params, mesh_sharp
+        from .mesh import mesh_params
 
-        if keep is not None:
-            keep = self._mesh_keep(keep)  # (refused before anything runs)
+        keep = self._mesh_keep(keep)  # (refused before anything runs)
         g, p = grid.to_c(), mesh_params(iso=iso, normals=normals, colours=colours, flags=flags, normal_delta=normal_delta)
         h = C.c_void_p()
-        if sharp is None:
+        s = self._mesh_block("sharp", sharp, abi.RmMeshSharp)
+        if s is None:
             self._check(self.lib.rm_mesh_extract(self.h, scene.h, C.byref(g), C.byref(p), C.byref(h)))
         else:
-            if isinstance(sharp, abi.RmMeshSharp):
-                s = mesh_sharp(refine=sharp.refine, normal_delta=sharp.normal_delta, threshold=sharp.threshold)
-                s.reserved = sharp.reserved  # (the library's to refuse)
-            elif sharp is True:
-                s = mesh_sharp()
-            elif isinstance(sharp, dict):
-                s = mesh_sharp(**sharp)
-            else:
-                raise ValueError("mesh: sharp must be None, True, a dict of mesh_sharp's arguments or an abi.RmMeshSharp")
             self._check(self.lib.rm_mesh_extract_sharp(self.h, scene.h, C.byref(g), C.byref(p), C.byref(s), C.byref(h)))
         return self._take_mesh(h, grid, normals=p.normals, colours=p.colours, keep=keep, components=components)
 
     def mesh_from_values(self, grid, values: np.ndarray, iso: float = 0.0, *, keep=None, components: bool = False):
         """The mesher alone on the caller's field: `values` float32 [nz + 1, ny + 1, nx + 1] (rm_mesh_from_values).  keep and components:
         as in extract_mesh."""
-        if keep is not None:
-            keep = self._mesh_keep(keep)
+        keep = self._mesh_keep(keep)
         g = grid.to_c()
         v = np.ascontiguousarray(values, np.float32)
         if v.shape != grid.shape:

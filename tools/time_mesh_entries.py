@@ -1,0 +1,111 @@
+"""Times the probe and mesh entry points on the host's clock.
+
+  python tools/time_mesh_entries.py [--runs N] [--reps N] [--n N]
+
+On the csg64 golden scene (tests/golden_cases.py) and a grid of n^3 cells (default 64) over its bounds, [-2, 2]^3 (centres within
+1.5 of the origin, radii up to 0.45, smooth unions): rm_probe of 65 536 SDF points, rm_sdf_grid, rm_mesh_extract with normals and
+colours, rm_mesh_extract_sharp with the same, rm_mesh_from_values on the downloaded field, rm_mesh_components on a fresh mesh, and
+rm_mesh_filter with largest = 1 on a labelled mesh.  Every call returns with its work done, so the host's clock is the measure:
+`runs` runs of `reps` calls each after a warm-up run, and the min / median / max of the per-call time over the runs.  Each call
+that makes a mesh has its rm_mesh_destroy inside the timed span; what a call needs made for it (the fresh mesh of rm_mesh_components)
+is made and destroyed outside it.  The host buffers are allocated once, outside the timed calls.
+RM_LIB selects another build of the library to time against (raymarching-engine_amd/native.py)."""
+import argparse
+import ctypes as C
+import json
+import sys
+import time
+from pathlib import Path
+
+import numpy as np
+
+ROOT = Path(__file__).resolve().parent.parent
+sys.path.insert(0, str(ROOT))
+sys.path.insert(0, str(ROOT / "tests"))
+
+
+def spread(xs):
+    xs = sorted(xs)
+    return {"min": round(xs[0], 4), "median": round(xs[len(xs) // 2], 4), "max": round(xs[-1], 4)}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--runs", type=int, default=7)
+    ap.add_argument("--reps", type=int, default=8)
+    ap.add_argument("--n", type=int, default=64)
+    args = ap.parse_args()
+
+    import golden_cases as GC
+    from raymarching_engine_amd import abi, mesh as M, native
+
+    ctx = native.Context(0)
+    lib = ctx.lib
+    scene = ctx.create_scene(GC.build_scene("csg64"))
+    grid = M.Grid((-2.0, -2.0, -2.0), (2.0, 2.0, 2.0), (args.n,) * 3)
+    g = grid.to_c()
+    plain, full = M.mesh_params(normals=False, colours=False), M.mesh_params(normals=True, colours=True)
+    largest = M.mesh_keep(largest=1)
+
+    def timed(what, call, before=None, after=None, **extra):
+        """`before` makes what one call takes and `after` gives it up, both outside the timed span."""
+        runs = []
+        for r in range(args.runs + 1):  # the first run is the warm-up
+            spent = 0.0
+            for _ in range(args.reps):
+                arg = before() if before else None
+                t0 = time.perf_counter()
+                call(arg)
+                spent += time.perf_counter() - t0
+                if after:
+                    after(arg)
+            if r:
+                runs.append(spent * 1e3 / args.reps)
+        print(json.dumps({"what": what, **extra, "n": args.n, "runs": args.runs, "reps": args.reps, "ms": spread(runs)}), flush=True)
+
+    def extract(params, sharp=False):
+        h = C.c_void_p()
+        if sharp:
+            ctx._check(lib.rm_mesh_extract_sharp(ctx.h, scene.h, C.byref(g), C.byref(params), None, C.byref(h)))
+        else:
+            ctx._check(lib.rm_mesh_extract(ctx.h, scene.h, C.byref(g), C.byref(params), C.byref(h)))
+        return h
+
+    points = np.random.default_rng(0).uniform(-2.0, 2.0, (65536, 3)).astype(np.float32)
+    distances = np.empty(len(points), np.float32)
+    timed("rm_probe", lambda _: ctx._check(lib.rm_probe(ctx.h, scene.h, abi.RM_PROBE_SDF, native._fp(points), len(points), 0.0, 0, native._fp(distances))), points=len(points))
+
+    field = np.empty(grid.shape, np.float32)
+    timed("rm_sdf_grid", lambda _: ctx._check(lib.rm_sdf_grid(ctx.h, scene.h, C.byref(g), 0, native._fp(field))))
+    timed("rm_mesh_extract + destroy", lambda _: lib.rm_mesh_destroy(extract(full)), normals=True, colours=True)
+    timed("rm_mesh_extract_sharp + destroy", lambda _: lib.rm_mesh_destroy(extract(full, sharp=True)), normals=True, colours=True)
+
+    def from_values(_):
+        h = C.c_void_p()
+        ctx._check(lib.rm_mesh_from_values(ctx.h, C.byref(g), native._fp(field), 0.0, C.byref(h)))
+        lib.rm_mesh_destroy(h)
+
+    timed("rm_mesh_from_values + destroy", from_values)
+
+    count = C.c_ulonglong()
+    timed("rm_mesh_components", lambda h: ctx._check(lib.rm_mesh_components(h, C.byref(count))), before=lambda: extract(plain), after=lib.rm_mesh_destroy, mesh="fresh")
+
+    labelled = extract(full)
+    ctx._check(lib.rm_mesh_components(labelled, C.byref(count)))
+
+    def filter_largest(_):
+        h = C.c_void_p()
+        ctx._check(lib.rm_mesh_filter(labelled, C.byref(largest), C.byref(h)))
+        lib.rm_mesh_destroy(h)
+
+    timed("rm_mesh_filter + destroy", filter_largest, largest=1, mesh="labelled")
+    counts = (C.c_ulonglong * 2)()
+    ctx._check(lib.rm_mesh_counts(labelled, counts))
+    print(json.dumps({"what": "mesh", "vertices": int(counts[0]), "triangles": int(counts[1]), "components": int(count.value)}))
+    lib.rm_mesh_destroy(labelled)
+    scene.destroy()
+    ctx.close()
+
+
+if __name__ == "__main__":
+    main()
