@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define RM_ABI_VERSION 9 /* 9: RM_GBUFFER_F32 / _F16, rm_fb_create_fmt, rm_fb_create_striped_fmt, rm_fb_wrap_fmt, rm_fb_gbuffer, rm_fb_download_raw, rm_fb_upload_raw, RmDenoise, rm_denoise_default, rm_denoise, rm_denoise_device, rm_present_denoised, RM_FB_MOMENTS, RM_PLANE_MOMENTS, rm_fb_has_moments, RmDenoiseVariance, rm_denoise_variance_default, rm_denoise_variance, rm_denoise_variance_device, rm_present_denoised_variance, RmDespeckle, RmFilters, RM_DENOISE_NONE / _ATROUS / _VARIANCE, rm_filters_default, rm_filter, rm_filter_device, rm_present_filtered, RM_STATS_BINS, RmFrameStats, rm_frame_stats, RmAutoExposure, rm_auto_exposure_default, rm_stats_percentile, rm_stats_exposure, RM_TONE_CLIP / _REINHARD / _ACES, RmDisplay, rm_display_default, rm_present_display, rm_present_display_device, rm_present_linear, RmGrid, rm_grid_axis, rm_sdf_grid, rm_sdf_grid_device, RmMeshParams, rm_mesh_params_default, rm_mesh, rm_mesh_extract, rm_mesh_from_values, rm_mesh_counts, rm_mesh_timings, RM_MESH_POSITIONS / _NORMALS / _COLOURS / _TRIANGLES / _CELLS, rm_mesh_download, rm_mesh_device_ptr, rm_mesh_destroy, RmMeshSharp, rm_mesh_sharp_default, rm_mesh_extract_sharp, RmMeshKeep, rm_mesh_keep_default, rm_mesh_components, RM_MESH_PART_LABELS / _SIZES, rm_mesh_components_download, rm_mesh_filter (additions only); 8: RM_PRIM_TORUS / _CYLINDER / _PLANE, RM_OP_SMOOTH_SUBTRACT / _INTERSECT, rm_probe_math (additions only); 7: rm_present_sharded_finish / rm_present_sharded take the size of the host buffer (a changed signature), rm_ctx_set_cull_min_pixels, rm_ctx_set_cull_budget, rm_ctx_cull_stats; 6: rm_present_striped_rows, rm_present_sharded_start / _finish, rm_ctx_last_warning, RM_PROBE_CAST_SHADOW, RM_PRIM_KIND (additions only); 3: rm_ctx_set_sample_batch, rm_buffer_*; 4: rm_ctx_set_gl_stack; 5: RmSurface / RmSceneDesc.surfaces (the struct grew), rm_pack_present_rows, rm_present_sharded, rm_ctx_last_pipeline, RM_RENDER_NO_FAR_JUMP, RM_RENDER_NO_CULL (additions only) */
+#define RM_ABI_VERSION 9 /* 9: RM_GBUFFER_F32 / _F16, rm_fb_create_fmt, rm_fb_create_striped_fmt, rm_fb_wrap_fmt, rm_fb_gbuffer, rm_fb_download_raw, rm_fb_upload_raw, RmDenoise, rm_denoise_default, rm_denoise, rm_denoise_device, rm_present_denoised, RM_FB_MOMENTS, RM_PLANE_MOMENTS, rm_fb_has_moments, RmDenoiseVariance, rm_denoise_variance_default, rm_denoise_variance, rm_denoise_variance_device, rm_present_denoised_variance, RmDespeckle, RmFilters, RM_DENOISE_NONE / _ATROUS / _VARIANCE, rm_filters_default, rm_filter, rm_filter_device, rm_present_filtered, RM_STATS_BINS, RmFrameStats, rm_frame_stats, RmAutoExposure, rm_auto_exposure_default, rm_stats_percentile, rm_stats_exposure, RM_TONE_CLIP / _REINHARD / _ACES, RmDisplay, rm_display_default, rm_present_display, rm_present_display_device, rm_present_linear, RmGrid, rm_grid_axis, rm_sdf_grid, rm_sdf_grid_device, RmMeshParams, rm_mesh_params_default, rm_mesh, rm_mesh_extract, rm_mesh_from_values, rm_mesh_counts, rm_mesh_timings, RM_MESH_POSITIONS / _NORMALS / _COLOURS / _TRIANGLES / _CELLS, rm_mesh_download, rm_mesh_device_ptr, rm_mesh_destroy, RmMeshSharp, rm_mesh_sharp_default, rm_mesh_extract_sharp, RmMeshKeep, rm_mesh_keep_default, rm_mesh_components, RM_MESH_PART_LABELS / _SIZES, rm_mesh_components_download, rm_mesh_filter, RmMeshSimplify, rm_mesh_simplify_default, rm_mesh_simplify (additions only); 8: RM_PRIM_TORUS / _CYLINDER / _PLANE, RM_OP_SMOOTH_SUBTRACT / _INTERSECT, rm_probe_math (additions only); 7: rm_present_sharded_finish / rm_present_sharded take the size of the host buffer (a changed signature), rm_ctx_set_cull_min_pixels, rm_ctx_set_cull_budget, rm_ctx_cull_stats; 6: rm_present_striped_rows, rm_present_sharded_start / _finish, rm_ctx_last_warning, RM_PROBE_CAST_SHADOW, RM_PRIM_KIND (additions only); 3: rm_ctx_set_sample_batch, rm_buffer_*; 4: rm_ctx_set_gl_stack; 5: RmSurface / RmSceneDesc.surfaces (the struct grew), rm_pack_present_rows, rm_present_sharded, rm_ctx_last_pipeline, RM_RENDER_NO_FAR_JUMP, RM_RENDER_NO_CULL (additions only) */
 
 #define RM_MAX_BOUNCES 10 /* raymarchingStepCountsArray[10], raymarcher.frag:31 */
 #define RM_MAX_LIGHTS 10  /* lightPositions[10],             raymarcher.frag:37-39 */
@@ -974,6 +974,53 @@ RM_API int rm_mesh_components(rm_mesh* mesh, unsigned long long* out_count);
 enum { RM_MESH_PART_LABELS = 0, RM_MESH_PART_SIZES = 1 };
 RM_API int rm_mesh_components_download(rm_mesh* mesh, int what, void* host, size_t bytes);
 RM_API int rm_mesh_filter(rm_mesh* mesh, const RmMeshKeep* keep, rm_mesh** out);
+
+/* ---- simplification (opt-in): vertex clustering, a lighter mesh that averages the fine one ----
+ * Every stage above keeps the triangle count its sampling grid dictates.  rm_mesh_simplify lays a second grid, `clusters`, over a mesh, merges
+ * the vertices of each of its cells into one, and drops the triangles that collapse or repeat.  It works on any rm_mesh (rm_mesh_extract, _sharp,
+ * _from_values, rm_mesh_filter, an earlier rm_mesh_simplify) and changes nothing of it; the result is an ordinary rm_mesh of the same context, which
+ * every mesh entry serves.  `clusters` is valid by RmGrid's rule and need not be related to the grid the mesh was sampled on; n[a] cells of
+ * h[a] = (hi[a] - lo[a]) / (float)n[a] per axis, as everywhere.  There are no error quadrics and no care for manifoldness: a cluster's vertex
+ * is the mean of its vertices, and thin sheets closer than a cluster cell merge.
+ * Arithmetic: fp32 unless it says double, every operation rounded on its own (no contraction), IEEE division and square root, the same whatever
+ * build made the source.  Q20(x) = (long long)rintf(x * 1048576.0f).  For V vertices and T triangles:
+ *   1. Cluster of a vertex p.  Per axis a: u = (p[a] - lo[a]) / h[a]; i = 0 if !(u >= 0) (NaN too), i = n[a] - 1 if u >= (float)n[a], else
+ *      i = min((int)floorf(u), n[a] - 1).  key = (k * ny + j) * nx + i.  The fraction f = u - (float)i, then 0 if !(f >= 0), 1 if f > 1 (a vertex
+ *      outside `clusters` lands on its boundary cell's face), and q[a] = Q20(f) in 0 .. 2^20.
+ *   2. Vertices.  One per occupied cluster, in ascending key; RM_MESH_CELLS of the result is that key, the linear cell index in `clusters`.  With m
+ *      the cluster's vertex count and S[a] the integer sum of its q[a]: g = (float)((double)S[a] / ((double)m * 1048576.0)) (one double division),
+ *      position[a] = lo[a] + ((float)i + g) * h[a] (a sum, a product, a sum).
+ *   3. Normals and colours, when the source has them (an array the source lacks is absent from the result).  Per component x: a non-finite x
+ *      counts as 0, x is clamped to [-1024, 1024], Q20(x) is summed per cluster as a signed 64-bit integer S, mean = (float)((double)S /
+ *      ((double)m * 1048576.0)).  A colour is that mean.  A normal is the mean renormalised: len = sqrtf((x * x + y * y) + z * z), each component
+ *      divided by len; (0, 0, 0) if len is 0 or not finite.
+ *   4. Triangles.  Corners are mapped to the new indices.  A triangle with two equal corners is dropped.  Unless keep_duplicates, among the
+ *      surviving triangles of one canonical form only the one with the smallest source index is kept; the canonical form rotates the smallest
+ *      index to the front and preserves the cyclic order, so (a, b, c) and (a, c, b) are different triangles.  The kept triangles stand in their
+ *      source order and are stored as mapped, not rotated.  A cluster whose triangles all vanished keeps its vertex: rm_mesh_filter with the
+ *      defaults, applied to the result, removes exactly those (simplify first, then filter).
+ *   5. An empty source gives a valid empty mesh.  The result starts without a labelling of its own.
+ * Every output is a function of integer sums, minima and scans: it is the same on every run, whatever order the device's threads arrive in.
+ * Procedure (rm_mesh_kernels.inc "simplification": in the strict unit, the same for every source).  No thread waits for another and every loop
+ * is bounded.
+ *   1. One thread per vertex marks its cluster's word in a dense array of 8 bytes per cluster cell; the mesher's scan numbers the occupied ones.
+ *   2. One thread per vertex adds its q, its Q20 attributes and 1 to its cluster's row of 64-bit integers (atomic adds: they commute; a run of
+ *      neighbouring lanes with one cluster is summed in the wave first and adds once); one thread per output vertex divides, renormalises
+ *      and places.
+ *   3. One thread per triangle maps it.  Unless keep_duplicates, every survivor enters an open-addressing table of triangle indices (a power of
+ *      two >= 2 T slots, hashed over the canonical triple): atomicCAS on an empty slot; where the occupant's canonical triple equals its own,
+ *      atomicMin; otherwise the next slot.  A slot's class never changes once claimed, so it ends holding the smallest index of its class, and a
+ *      triangle is kept iff its slot holds its own index.  A probe that went round the whole table sets an error word: RM_ERR_DEVICE.
+ *   4. The keep flags are scanned and the kept triangles gathered.
+ * rm_mesh_simplify: params == NULL is the defaults.  Synchronous, on the stream of the mesh's context.  rm_mesh_timings of the result is {0, the
+ *   milliseconds of these kernels between events on the stream, 0}.  The scratch (8 bytes per cluster cell, one row per output vertex, 4 V + 20 T
+ *   bytes and the table) is freed before the call returns.
+ * RM_ERR_INVALID, in this order (the text through rm_last_error(NULL) when no context is known): before the handles are looked at, a NULL or
+ * invalid `clusters` (RmGrid's texts), keep_duplicates outside 0 / 1, a non-zero reserved.  Then a NULL mesh or out ("NULL argument").
+ * RM_ERR_DEVICE: a mesh with T >= 2^32, a failed allocation (nothing leaked). */
+typedef struct RmMeshSimplify { int32_t keep_duplicates; int32_t reserved[3]; } RmMeshSimplify; /* 16 bytes */
+RM_API void rm_mesh_simplify_default(RmMeshSimplify* params);
+RM_API int rm_mesh_simplify(rm_mesh* mesh, const RmGrid* clusters, const RmMeshSimplify* params, rm_mesh** out);
 
 #ifdef __cplusplus
 }

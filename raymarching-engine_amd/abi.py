@@ -284,3 +284,17 @@ class RmMeshKeep(C.Structure):
 MESH_KEEP_DEFAULTS = dict(min_triangles=1, largest=0)  # rm_mesh_keep_default
 
 assert C.sizeof(RmMeshKeep) == 16
+
+
+class RmMeshSimplify(C.Structure):
+    """Parameters of rm_mesh_simplify (ABI 9): keep_duplicates = 1 keeps every surviving triangle, 0 only the first of each canonical form
+    (include/hip_raymarch.h "simplification")."""
+    _fields_ = [
+        ("keep_duplicates", C.c_int32),
+        ("reserved", C.c_int32 * 3),
+    ]
+
+
+MESH_SIMPLIFY_DEFAULTS = dict(keep_duplicates=0)  # rm_mesh_simplify_default
+
+assert C.sizeof(RmMeshSimplify) == 16

@@ -206,7 +206,7 @@ struct DeviceArray {
 // Stage timing of the mesh entries (rm_mesh_timings): a span is a pair of events on the context's stream, made with the first mesh
 // that runs the stage.
 struct MeshSpans {
-  enum { SAMPLE, COUNT_SCAN, EMIT, SHARPEN, ATTRIBUTES, LABEL, KEEP_FLAGS, GATHER, COUNT };
+  enum { SAMPLE, COUNT_SCAN, EMIT, SHARPEN, ATTRIBUTES, LABEL, KEEP_FLAGS, GATHER, CLUSTER_NUMBER, CLUSTER_MERGE, CLUSTER_GATHER, COUNT };
   hipEvent_t ev[COUNT][2] = {};
   hipError_t begin(int span, hipStream_t stream) { return record(ev[span][0], stream); }
   hipError_t end(int span, hipStream_t stream) { return record(ev[span][1], stream); }

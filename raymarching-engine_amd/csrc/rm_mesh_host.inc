@@ -501,3 +501,126 @@ int rm_mesh_filter(rm_mesh* mesh, const RmMeshKeep* keep, rm_mesh** out) {
   *out = made.release();
   return RM_OK;
 }
+
+// ---- simplification (include/hip_raymarch.h "simplification") -----------------------------------------------------------------------------
+
+void rm_mesh_simplify_default(RmMeshSimplify* params) {
+  if (!params) return;
+  *params = RmMeshSimplify{0, {0, 0, 0}};
+}
+
+// what a simplification needs beside its result: owned by rm_mesh_simplify, declared before the mesh it makes
+struct SimplifyScratch {
+  DeviceArray marks, levels, sums, vertex_to, mapped, words, table;
+};
+
+// `mesh` (with vertices) clustered on G into `made`: number the occupied clusters, read V'; sum, place, map and deduplicate, read T' and the
+// error word; gather.  On the context's stream; returns with it idle.  made->ms[1] is the time of its three spans.
+static int mesh_cluster(const Refuse& refuse, const rm_mesh* mesh, const GridDims& G, bool keep_duplicates, SimplifyScratch& tmp, rm_mesh* made) {
+  rm_ctx* ctx = mesh->ctx;
+  MeshSpans& spans = ctx->mesh_spans;
+  const unsigned long long V = mesh->vertices, T = mesh->triangles;
+  const long long cells = (long long)(G.nc[0] - 1) * (G.nc[1] - 1) * (G.nc[2] - 1);
+  const size_t cell_levels = rm::rm_mesh_scan_scratch_elems(cells), triangle_levels = rm::rm_mesh_scan_scratch_elems((long long)T + 1);
+  RM_HIP(ctx, tmp.marks.reserve(sizeof(unsigned long long) * (size_t)cells));
+  RM_HIP(ctx, tmp.levels.reserve(sizeof(unsigned long long) * (cell_levels + triangle_levels + 3)));  // ... V', T' and the error word behind the levels
+  unsigned long long* d_totals = tmp.levels.u64() + cell_levels + triangle_levels;
+  rm::MeshSimplify S{};
+  S.grid = G;
+  S.vertices = (long long)V;
+  S.triangles = (long long)T;
+  S.positions = mesh->array[RM_MESH_POSITIONS].f32();
+  S.normals = mesh->array[RM_MESH_NORMALS].f32();
+  S.colours = mesh->array[RM_MESH_COLOURS].f32();
+  S.source_triangles = mesh->array[RM_MESH_TRIANGLES].u32();
+  S.marks = tmp.marks.u64();
+  S.error = reinterpret_cast<unsigned int*>(d_totals + 2);
+  RM_HIP(ctx, spans.begin(MeshSpans::CLUSTER_NUMBER, ctx->stream));
+  RM_HIP(ctx, hipMemsetAsync(tmp.marks.p, 0, sizeof(unsigned long long) * (size_t)cells, ctx->stream));
+  RM_HIP(ctx, hipMemsetAsync(d_totals, 0, 3 * sizeof(unsigned long long), ctx->stream));
+  RM_HIP(ctx, rm::launch_mesh_simplify_mark(S, ctx->stream));
+  RM_HIP(ctx, rm::launch_mesh_scan(S.marks, cells, tmp.levels.u64(), d_totals, ctx->stream));
+  RM_HIP(ctx, spans.end(MeshSpans::CLUSTER_NUMBER, ctx->stream));
+  unsigned long long totals[3] = {0, 0, 0};
+  if (int rc = copy_and_wait(ctx, totals, d_totals, sizeof totals[0], hipMemcpyDeviceToHost)) return rc;
+  float ms = spans.ms(MeshSpans::CLUSTER_NUMBER);
+  made->vertices = totals[0];
+  S.out_vertices = (long long)made->vertices;
+  S.row = 4 + (S.normals ? 3 : 0) + (S.colours ? 3 : 0);
+  const size_t sums_bytes = sizeof(unsigned long long) * (size_t)S.row * (size_t)made->vertices;
+  RM_HIP(ctx, tmp.sums.reserve(sums_bytes));
+  RM_HIP(ctx, tmp.vertex_to.reserve(sizeof(unsigned int) * (size_t)V));
+  for (int what : {RM_MESH_POSITIONS, RM_MESH_NORMALS, RM_MESH_COLOURS, RM_MESH_CELLS})
+    if (mesh->array[what].p) RM_HIP(ctx, made->array[what].reserve(mesh_array_bytes(made, what)));
+  S.sums = tmp.sums.u64();
+  S.vertex_to = tmp.vertex_to.u32();
+  S.out_positions = made->array[RM_MESH_POSITIONS].f32();
+  S.out_normals = made->array[RM_MESH_NORMALS].f32();
+  S.out_colours = made->array[RM_MESH_COLOURS].f32();
+  S.out_cells = made->array[RM_MESH_CELLS].u32();
+  if (T > 0) {
+    RM_HIP(ctx, tmp.mapped.reserve(sizeof(unsigned int) * 3u * (size_t)T));
+    RM_HIP(ctx, tmp.words.reserve(sizeof(unsigned long long) * ((size_t)T + 1)));
+    S.mapped = tmp.mapped.u32();
+    S.words = tmp.words.u64();
+    if (!keep_duplicates) {
+      S.slots = 1ull;
+      while (S.slots < 2ull * T) S.slots <<= 1;
+      RM_HIP(ctx, tmp.table.reserve(sizeof(unsigned int) * (size_t)S.slots));
+      S.table = tmp.table.u32();
+    }
+  }
+  RM_HIP(ctx, spans.begin(MeshSpans::CLUSTER_MERGE, ctx->stream));
+  RM_HIP(ctx, hipMemsetAsync(tmp.sums.p, 0, sums_bytes, ctx->stream));
+  RM_HIP(ctx, rm::launch_mesh_simplify_sums(S, ctx->stream));
+  RM_HIP(ctx, rm::launch_mesh_simplify_place(S, ctx->stream));
+  if (T > 0) {
+    RM_HIP(ctx, rm::launch_mesh_simplify_map(S, ctx->stream));
+    if (!keep_duplicates) {
+      RM_HIP(ctx, hipMemsetAsync(tmp.table.p, 0xFF, sizeof(unsigned int) * (size_t)S.slots, ctx->stream));
+      RM_HIP(ctx, rm::launch_mesh_simplify_insert(S, ctx->stream));
+      RM_HIP(ctx, rm::launch_mesh_simplify_keep(S, ctx->stream));
+    }
+    RM_HIP(ctx, rm::launch_mesh_scan(S.words, (long long)T + 1, tmp.levels.u64() + cell_levels, d_totals + 1, ctx->stream));
+  }
+  RM_HIP(ctx, spans.end(MeshSpans::CLUSTER_MERGE, ctx->stream));
+  if (int rc = copy_and_wait(ctx, totals + 1, d_totals + 1, 2 * sizeof totals[0], hipMemcpyDeviceToHost)) return rc;
+  ms += spans.ms(MeshSpans::CLUSTER_MERGE);
+  if ((unsigned int)totals[2] != 0u) return refuse("a triangle found no slot in the table", RM_ERR_DEVICE);
+  made->triangles = totals[1];
+  if (made->triangles > 0) {
+    RM_HIP(ctx, made->array[RM_MESH_TRIANGLES].reserve(mesh_array_bytes(made, RM_MESH_TRIANGLES)));
+    S.out_triangles = made->array[RM_MESH_TRIANGLES].u32();
+    RM_HIP(ctx, spans.begin(MeshSpans::CLUSTER_GATHER, ctx->stream));
+    RM_HIP(ctx, rm::launch_mesh_simplify_gather(S, ctx->stream));
+    RM_HIP(ctx, spans.end(MeshSpans::CLUSTER_GATHER, ctx->stream));
+    RM_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    ms += spans.ms(MeshSpans::CLUSTER_GATHER);
+  }
+  made->ms[1] = ms;
+  return RM_OK;
+}
+
+int rm_mesh_simplify(rm_mesh* mesh, const RmGrid* clusters, const RmMeshSimplify* params, rm_mesh** out) {
+  rm_ctx* ctx = mesh ? mesh->ctx : nullptr;
+  const Refuse refuse{ctx, "rm_mesh_simplify"};
+  GridDims G{};
+  RmMeshSimplify p;
+  rm_mesh_simplify_default(&p);
+  if (params) p = *params;
+  if (int rc = grid_check(refuse, clusters, &G)) return rc;
+  if (p.keep_duplicates != 0 && p.keep_duplicates != 1) return refuse("keep_duplicates must be 0 or 1");
+  if (p.reserved[0] != 0 || p.reserved[1] != 0 || p.reserved[2] != 0) return refuse("simplify reserved must be 0");
+  if (!mesh || !out) return refuse("NULL argument");
+  *out = nullptr;
+  if (mesh->triangles >= (1ull << 32)) return refuse("the mesh has more triangles than a uint32 index holds (T >= 2^32)", RM_ERR_DEVICE);
+  RM_HIP(ctx, hipSetDevice(ctx->device));
+  SimplifyScratch tmp;  // (before the mesh: freed behind the wait of whatever gives the mesh up)
+  MeshPtr made(new (std::nothrow) rm_mesh(ctx), rm_mesh_destroy);
+  if (!made) return refuse("out of host memory", RM_ERR_DEVICE);
+  for (int a = 0; a < 5; a++) made->has[a] = mesh->has[a];
+  if (mesh->vertices > 0)
+    if (int rc = mesh_cluster(refuse, mesh, G, p.keep_duplicates != 0, tmp, made.get())) return rc;
+  *out = made.release();
+  return RM_OK;
+}

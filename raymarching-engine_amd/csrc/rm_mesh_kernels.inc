@@ -1,7 +1,7 @@
 // Mesh extraction (include/hip_raymarch.h "mesh extraction"): a scene's distance on a grid of corners, in this unit's arithmetic,
 // and -- in the strict unit only, they have no arithmetic of a policy's own -- the surface-nets mesher over such a grid, the two
 // kernels that move its vertices to their cells' QEF minimisers (rm_mesh_extract_sharp), and the integer kernels that label a mesh's
-// connected components and compact the kept ones (rm_mesh_components, rm_mesh_filter).  Included by
+// connected components and compact the kept ones (rm_mesh_components, rm_mesh_filter), and the vertex clustering of rm_mesh_simplify.  Included by
 // rm_strict.hip / rm_fast.hip / rm_glstack.hip behind rm_kernels.inc.
 namespace rm {
 
@@ -472,6 +472,225 @@ __global__ __launch_bounds__(256) void rm_mesh_gather_triangles_kernel(const Mes
   out[3 * to + 2] = (unsigned int)G.vertex_at[triangles[3 * t + 2]];
 }
 
+// ---- simplification: vertex clustering (include/hip_raymarch.h "simplification") ------------------------------------------------------------
+// Everything a run can differ in is an integer: the means are sums of Q20 integers (atomic adds commute), the survivor of a class of equal
+// triangles is a minimum.  The fp32 around them is this unit's plain arithmetic, every operation rounded on its own.  No thread waits for
+// another; the one loop, the table's probe, is bounded by the table's size.
+
+__device__ inline long long mesh_q20(float x) { return (long long)rintf(x * 1048576.0f); }
+
+// a normal's or a colour's component as it is summed: non-finite counts as 0, clamped to [-1024, 1024]
+__device__ inline unsigned long long mesh_q20_attribute(float x) {
+  if (!isfinite(x)) x = 0.0f;
+  if (x < -1024.0f) x = -1024.0f;
+  if (x > 1024.0f) x = 1024.0f;
+  return (unsigned long long)mesh_q20(x);  // (two's complement: the row's unsigned adds sum it as a signed value)
+}
+
+struct MeshCluster {
+  unsigned int key;   // (k * ny + j) * nx + i
+  unsigned int q[3];  // the position inside the cluster cell, 0 .. 2^20 per axis
+};
+
+__device__ inline MeshCluster mesh_cluster(const GridDims& g, const float* p) {
+  MeshCluster c;
+  int idx[3];
+#pragma unroll
+  for (int a = 0; a < 3; a++) {
+    const int n = g.nc[a] - 1;
+    const float d = p[a] - g.lo[a], u = d / g.h[a];
+    int i;
+    if (!(u >= 0.0f)) i = 0;  // (NaN too)
+    else if (u >= (float)n) i = n - 1;
+    else {
+      i = (int)floorf(u);
+      if (i > n - 1) i = n - 1;
+    }
+    float f = u - (float)i;
+    if (!(f >= 0.0f)) f = 0.0f;
+    if (f > 1.0f) f = 1.0f;
+    idx[a] = i;
+    c.q[a] = (unsigned int)mesh_q20(f);
+  }
+  c.key = (unsigned int)((idx[2] * (g.nc[1] - 1) + idx[1]) * (g.nc[0] - 1) + idx[0]);
+  return c;
+}
+
+__global__ __launch_bounds__(256) void rm_mesh_simplify_mark_kernel(const MeshSimplify S) {
+  const long long v = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (v < S.vertices) S.marks[mesh_cluster(S.grid, S.positions + 3 * v).key] = 1ull;  // (every writer of a word writes the same)
+}
+
+// Behind the scan: marks[key] is the cluster's output vertex.  Vertices stand in ascending source cell order, so neighbouring lanes often share
+// a cluster: every run of consecutive lanes with one cluster is summed in the wave first (a segmented shuffle reduction; integer sums, so the
+// totals are what one add per vertex gives) and the run's first lane makes the adds.  Every lane of a wave stays to the end: the shuffles read
+// all of them; a lane beyond the last vertex is a run of its own that adds nothing.
+__global__ __launch_bounds__(256) void rm_mesh_simplify_sums_kernel(const MeshSimplify S) {
+  const long long v = (long long)blockIdx.x * 256 + threadIdx.x;
+  const int lane = (int)(threadIdx.x & 63u);
+  const bool valid = v < S.vertices;
+  MeshCluster c{};
+  unsigned int to = 0xFFFFFFFFu;
+  if (valid) {
+    c = mesh_cluster(S.grid, S.positions + 3 * v);
+    to = (unsigned int)S.marks[c.key];
+    S.vertex_to[v] = to;
+  }
+  const unsigned int before = (unsigned int)__shfl_up((int)to, 1);
+  const bool head = lane == 0 || before != to;
+  const unsigned long long heads = __ballot(head), above = lane == 63 ? 0ull : heads >> (lane + 1);
+  const int last = above != 0ull ? lane + __ffsll((long long)above) - 1 : 63;  // the last lane of this lane's run
+  // the count and the q sums of a run fit 32 bits (64 lanes of at most 2^20); the attributes' do not
+  unsigned int n = valid ? 1u : 0u, q[3] = {c.q[0], c.q[1], c.q[2]};
+  unsigned long long w[6] = {0ull, 0ull, 0ull, 0ull, 0ull, 0ull};
+  if (valid && S.normals) {
+#pragma unroll
+    for (int a = 0; a < 3; a++) w[a] = mesh_q20_attribute(S.normals[3 * v + a]);
+  }
+  if (valid && S.colours) {
+#pragma unroll
+    for (int a = 0; a < 3; a++) w[3 + a] = mesh_q20_attribute(S.colours[3 * v + a]);
+  }
+  const bool wide = S.normals != nullptr || S.colours != nullptr;  // (uniform)
+#pragma unroll
+  for (int off = 1; off < 64; off <<= 1) {
+    const bool mine = lane + off <= last;
+    const unsigned int dn = (unsigned int)__shfl_down((int)n, off);
+    if (mine) n += dn;
+#pragma unroll
+    for (int a = 0; a < 3; a++) {
+      const unsigned int dq = (unsigned int)__shfl_down((int)q[a], off);
+      if (mine) q[a] += dq;
+    }
+    if (wide) {
+#pragma unroll
+      for (int a = 0; a < 6; a++) {
+        const unsigned long long dw = __shfl_down(w[a], off);
+        if (mine) w[a] += dw;
+      }
+    }
+  }
+  if (!head || !valid) return;
+  S.out_cells[to] = c.key;  // (the same from every run of the cluster)
+  unsigned long long* row = S.sums + (size_t)to * (size_t)S.row;
+  atomicAdd(row, (unsigned long long)n);
+#pragma unroll
+  for (int a = 0; a < 3; a++) atomicAdd(row + 1 + a, (unsigned long long)q[a]);
+  int at = 4;
+  if (S.normals) {
+#pragma unroll
+    for (int a = 0; a < 3; a++) atomicAdd(row + at + a, w[a]);
+    at += 3;
+  }
+  if (S.colours) {
+#pragma unroll
+    for (int a = 0; a < 3; a++) atomicAdd(row + at + a, w[3 + a]);
+  }
+}
+
+__device__ inline float mesh_q20_mean(unsigned long long sum, double count_q20) { return (float)((double)(long long)sum / count_q20); }
+
+__global__ __launch_bounds__(256) void rm_mesh_simplify_place_kernel(const MeshSimplify S) {
+  const long long o = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (o >= S.out_vertices) return;
+  const GridDims& g = S.grid;
+  const unsigned long long* row = S.sums + (size_t)o * (size_t)S.row;
+  const double m = (double)row[0] * 1048576.0;
+  const int nx = g.nc[0] - 1, ny = g.nc[1] - 1, key = (int)S.out_cells[o];
+  const int idx[3] = {key % nx, (key / nx) % ny, key / (nx * ny)};
+#pragma unroll
+  for (int a = 0; a < 3; a++) {
+    const float s = (float)idx[a] + mesh_q20_mean(row[1 + a], m), step = s * g.h[a];
+    S.out_positions[3 * o + a] = g.lo[a] + step;
+  }
+  int at = 4;
+  if (S.out_normals) {
+    const float x = mesh_q20_mean(row[at], m), y = mesh_q20_mean(row[at + 1], m), z = mesh_q20_mean(row[at + 2], m);
+    const float xx = x * x, yy = y * y, zz = z * z, xy = xx + yy, len = sqrtf(xy + zz);
+    const bool none = len == 0.0f || !isfinite(len);
+    S.out_normals[3 * o] = none ? 0.0f : x / len;
+    S.out_normals[3 * o + 1] = none ? 0.0f : y / len;
+    S.out_normals[3 * o + 2] = none ? 0.0f : z / len;
+    at += 3;
+  }
+  if (S.out_colours) {
+#pragma unroll
+    for (int a = 0; a < 3; a++) S.out_colours[3 * o + a] = mesh_q20_mean(row[at + a], m);
+  }
+}
+
+// one thread per triangle, and one more for the word behind the last: the scan's total lands there, so "kept" reads as words[t + 1] != words[t].
+// A triangle with an index beyond the mesh (none of this library's has one) is dropped.
+__global__ __launch_bounds__(256) void rm_mesh_simplify_map_kernel(const MeshSimplify S) {
+  const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (t > S.triangles) return;
+  if (t == S.triangles) { S.words[t] = 0ull; return; }
+  const unsigned int a = S.source_triangles[3 * t], b = S.source_triangles[3 * t + 1], c = S.source_triangles[3 * t + 2];
+  const bool valid = a < S.vertices && b < S.vertices && c < S.vertices;
+  const unsigned int ma = valid ? S.vertex_to[a] : 0u, mb = valid ? S.vertex_to[b] : 0u, mc = valid ? S.vertex_to[c] : 0u;
+  S.mapped[3 * t] = ma;
+  S.mapped[3 * t + 1] = mb;
+  S.mapped[3 * t + 2] = mc;
+  S.words[t] = (ma != mb && mb != mc && ma != mc) ? 1ull : 0ull;
+}
+
+// the smallest index in front, the cyclic order kept (the three differ)
+struct MeshTriple {
+  unsigned int a, b, c;
+};
+__device__ inline MeshTriple mesh_canonical(const unsigned int* m) {
+  const unsigned int x = m[0], y = m[1], z = m[2];
+  if (x < y && x < z) return MeshTriple{x, y, z};
+  if (y < z) return MeshTriple{y, z, x};
+  return MeshTriple{z, x, y};
+}
+
+__global__ __launch_bounds__(256) void rm_mesh_simplify_insert_kernel(const MeshSimplify S) {
+  const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (t >= S.triangles || S.words[t] == 0ull) return;
+  const MeshTriple mine = mesh_canonical(S.mapped + 3 * t);
+  unsigned long long h = (mine.a * 0x9E3779B97F4A7C15ull) ^ (mine.b * 0xC2B2AE3D27D4EB4Full) ^ (mine.c * 0x165667B19E3779F9ull);
+  h ^= h >> 29;
+  h *= 0xBF58476D1CE4E5B9ull;
+  h ^= h >> 32;
+  const unsigned long long mask = S.slots - 1ull;
+  unsigned long long slot = h & mask;
+  for (unsigned long long probe = 0; probe < S.slots; probe++, slot = (slot + 1ull) & mask) {
+    unsigned int held = __hip_atomic_load(S.table + slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (held == 0xFFFFFFFFu) {
+      held = atomicCAS(S.table + slot, 0xFFFFFFFFu, (unsigned int)t);
+      if (held == 0xFFFFFFFFu) { S.words[t] = slot + 1ull; return; }
+    }
+    // whoever holds the slot is of the class that claimed it: any of them tells which
+    const MeshTriple theirs = mesh_canonical(S.mapped + 3 * (size_t)held);
+    if (theirs.a == mine.a && theirs.b == mine.b && theirs.c == mine.c) {
+      atomicMin(S.table + slot, (unsigned int)t);
+      S.words[t] = slot + 1ull;
+      return;
+    }
+  }
+  S.words[t] = 0ull;
+  *S.error = 1u;
+}
+
+__global__ __launch_bounds__(256) void rm_mesh_simplify_keep_kernel(const MeshSimplify S) {
+  const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (t >= S.triangles) return;
+  const unsigned long long at = S.words[t];
+  S.words[t] = (at != 0ull && S.table[at - 1ull] == (unsigned int)t) ? 1ull : 0ull;
+}
+
+// (named with rm_mesh_take3_kernel's caution: the lengths of the kernel names decide whether llvm-objdump -D reads this code object whole)
+__global__ __launch_bounds__(256) void rm_mesh_simplify_take_kernel(const MeshSimplify S) {
+  const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (t >= S.triangles) return;
+  const size_t to = (size_t)S.words[t];
+  if (S.words[t + 1] == to) return;
+  S.out_triangles[3 * to] = S.mapped[3 * t];
+  S.out_triangles[3 * to + 1] = S.mapped[3 * t + 1];
+  S.out_triangles[3 * to + 2] = S.mapped[3 * t + 2];
+}
+
 #ifndef RM_ONLY_KERNELS
 static inline long long mesh_cells(const GridDims& g) { return (long long)(g.nc[0] - 1) * (g.nc[1] - 1) * (g.nc[2] - 1); }
 
@@ -561,6 +780,15 @@ hipError_t launch_mesh_gather_triangles(const MeshGather& G, const unsigned int*
                                         unsigned int* out, hipStream_t stream) {
   RM_MESH_PARTS_LAUNCH(rm_mesh_gather_triangles_kernel, n, G, triangles, triangle_at, n, out);
 }
+
+// simplification: one thread per source vertex, output vertex or source triangle (map: and one more)
+hipError_t launch_mesh_simplify_mark(const MeshSimplify& S, hipStream_t stream) { RM_MESH_PARTS_LAUNCH(rm_mesh_simplify_mark_kernel, S.vertices, S); }
+hipError_t launch_mesh_simplify_sums(const MeshSimplify& S, hipStream_t stream) { RM_MESH_PARTS_LAUNCH(rm_mesh_simplify_sums_kernel, S.vertices, S); }
+hipError_t launch_mesh_simplify_place(const MeshSimplify& S, hipStream_t stream) { RM_MESH_PARTS_LAUNCH(rm_mesh_simplify_place_kernel, S.out_vertices, S); }
+hipError_t launch_mesh_simplify_map(const MeshSimplify& S, hipStream_t stream) { RM_MESH_PARTS_LAUNCH(rm_mesh_simplify_map_kernel, S.triangles + 1, S); }
+hipError_t launch_mesh_simplify_insert(const MeshSimplify& S, hipStream_t stream) { RM_MESH_PARTS_LAUNCH(rm_mesh_simplify_insert_kernel, S.triangles, S); }
+hipError_t launch_mesh_simplify_keep(const MeshSimplify& S, hipStream_t stream) { RM_MESH_PARTS_LAUNCH(rm_mesh_simplify_keep_kernel, S.triangles, S); }
+hipError_t launch_mesh_simplify_gather(const MeshSimplify& S, hipStream_t stream) { RM_MESH_PARTS_LAUNCH(rm_mesh_simplify_take_kernel, S.triangles, S); }
 #undef RM_MESH_PARTS_LAUNCH
 
 hipError_t launch_mesh_emit(const MeshParams& P, hipStream_t stream) {

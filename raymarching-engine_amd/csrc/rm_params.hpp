@@ -489,6 +489,42 @@ hipError_t launch_mesh_keep_flags(const unsigned int* labels, const unsigned int
 hipError_t launch_mesh_gather_vertices(const MeshGather& G, long long vertices, hipStream_t stream);
 hipError_t launch_mesh_gather_triangles(const MeshGather& G, const unsigned int* triangles, const unsigned long long* triangle_at, long long n,
                                         unsigned int* out, hipStream_t stream);
+// Simplification (rm_mesh_simplify): vertex clustering over a mesh's arrays.  grid: the CLUSTER grid (nc = cells + 1 per axis).  sums: one row of
+// `row` 64-bit words per output vertex -- the count, the three q sums, then the Q20 sums of the normals and of the colours where the source has
+// them.  simplify_mark: marks[key of v] = 1.  simplify_sums (behind the scan of the marks): vertex_to[v] = the scanned mark, the row's atomic
+// adds, cells[that] = key.  simplify_place: one thread per output vertex, the rows into positions / normals / colours.  simplify_map: mapped[t]
+// = the triangle's corners through vertex_to, words[t] = 1 if no two are equal, else 0.  simplify_insert: every survivor into `table` (slots of
+// 0xFFFFFFFF, a power of two of them), words[t] = its slot + 1; *error = 1 where a probe went round.  simplify_keep: words[t] = 1 iff the slot
+// holds t.  simplify_gather (behind the scan of words[0 .. T], words[T] = 0): the kept triangles, those whose scanned word differs from the next.
+struct MeshSimplify {
+  GridDims grid;
+  long long vertices, out_vertices, triangles;
+  const float* positions;              // the source's: V x 3
+  const float* normals;                // V x 3 or NULL
+  const float* colours;                // V x 3 or NULL
+  const unsigned int* source_triangles;  // T x 3
+  unsigned long long* marks;           // per cluster cell
+  unsigned long long* sums;            // out_vertices x row
+  int row;                             // 4, 7 or 10
+  unsigned int* vertex_to;             // V
+  float* out_positions;                // out_vertices x 3
+  float* out_normals;
+  float* out_colours;
+  unsigned int* out_cells;
+  unsigned int* mapped;                // T x 3
+  unsigned long long* words;           // T + 1
+  unsigned int* table;
+  unsigned long long slots;            // a power of two
+  unsigned int* error;
+  unsigned int* out_triangles;
+};
+hipError_t launch_mesh_simplify_mark(const MeshSimplify& S, hipStream_t stream);
+hipError_t launch_mesh_simplify_sums(const MeshSimplify& S, hipStream_t stream);
+hipError_t launch_mesh_simplify_place(const MeshSimplify& S, hipStream_t stream);
+hipError_t launch_mesh_simplify_map(const MeshSimplify& S, hipStream_t stream);
+hipError_t launch_mesh_simplify_insert(const MeshSimplify& S, hipStream_t stream);
+hipError_t launch_mesh_simplify_keep(const MeshSimplify& S, hipStream_t stream);
+hipError_t launch_mesh_simplify_gather(const MeshSimplify& S, hipStream_t stream);
 hipError_t launch_camera_rng(const RmUniforms& u, int W, int H, int what, int count, float* out, hipStream_t stream);
 hipError_t launch_math_probe(int fn, const float* a, const float* b, int n, float* out, hipStream_t stream);
 }  // namespace rm

@@ -119,8 +119,10 @@ export class RenderJobContext {
   extractMesh(scene: Scene, grid: MeshGrid, params: MeshParams | null | undefined, sharp: MeshSharp | true | null): Mesh;
   /** with `keep` (true = the defaults, which drop unreferenced vertices): the mesh's connected components filtered on the GPU before anything is copied (rm_mesh_filter); `components`: the result carries labels and componentSizes (rm_mesh_components) */
   extractMesh(scene: Scene, grid: MeshGrid, params: MeshParams | null | undefined, sharp: MeshSharp | true | null | undefined, keep: MeshKeep | true | null | undefined, components?: boolean): Mesh;
-  /** the mesher alone on the caller's field (rm_mesh_from_values) */
-  meshFromValues(grid: MeshGrid, values: Float32Array, iso?: number, keep?: MeshKeep | true | null, components?: boolean): Mesh;
+  /** with `simplify`: the vertices of every cell of a second grid of clusters merged into one on the GPU (rm_mesh_simplify) before `keep` and `components` are applied, so one filter also removes the vertices the clustering left without triangles; the result's cells index the cluster grid */
+  extractMesh(scene: Scene, grid: MeshGrid, params: MeshParams | null | undefined, sharp: MeshSharp | true | null | undefined, keep: MeshKeep | true | null | undefined, components: boolean | undefined, simplify: MeshSimplify | null): Mesh;
+  /** the mesher alone on the caller's field (rm_mesh_from_values); keep, components and simplify as in extractMesh */
+  meshFromValues(grid: MeshGrid, values: Float32Array, iso?: number, keep?: MeshKeep | true | null, components?: boolean, simplify?: MeshSimplify | null): Mesh;
   close(): void;
 }
 /** A frame sharded over several GPUs by this one process: a native context per device, each holding one part of the frame's
@@ -164,5 +166,9 @@ export function meshSharp(sharp?: MeshSharp | null): { refine: number; normalDel
 export interface MeshKeep { minTriangles?: number; largest?: number }
 export const MESH_KEEP_DEFAULTS: { minTriangles: number; largest: number };
 export function meshKeep(keep?: MeshKeep | null): { minTriangles: number; largest: number };
+/** the simplify block of extractMesh / meshFromValues (RmMeshSimplify and its RmGrid of clusters): one output vertex per occupied cell of `grid`, the mean of the cell's vertices; keepDuplicates keeps the triangles that repeat an earlier one */
+export interface MeshSimplify { grid: MeshGrid; keepDuplicates?: boolean | 0 | 1 }
+export const MESH_SIMPLIFY_DEFAULTS: { keepDuplicates: 0 | 1 };
+export function meshSimplify(simplify: MeshSimplify): { grid: MeshGrid; keepDuplicates: 0 | 1 };
 /** binary little-endian PLY (normals and uchar colours when present): the bytes the Python host's write_ply writes */
 export function encodePly(mesh: { positions: Float32Array; triangles: Uint32Array; normals?: Float32Array | null; colours?: Float32Array | null }): Buffer;

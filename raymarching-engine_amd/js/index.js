@@ -359,7 +359,14 @@ class RenderJobContext {  // RenderJobContext + loadRenderJobContext (LoadRender
   // keep: undefined / null = that mesh; true or meshKeep's options = its connected components filtered on the GPU before anything is copied
   // (rm_mesh_filter; the defaults drop the unreferenced vertices).  components: truthy adds labels (Uint32Array(V)) and componentSizes
   // (Uint32Array(2 C): vertices, triangles per component) of the mesh that is returned (rm_mesh_components)
-  extractMesh(scene, grid, opts, sharp, keep, components) {
+  // simplify: undefined / null = that mesh; meshSimplify's options ({ grid, keepDuplicates }) = the vertices of every cell of that grid of clusters
+  // merged into one on the GPU (rm_mesh_simplify) before keep and components are applied; the result's cells index the cluster grid
+  extractMesh(scene, grid, opts, sharp, keep, components, simplify = null) {
+    if (simplify !== undefined && simplify !== null) {
+      const s = sharp === undefined || sharp === null ? null : meshSharp(sharp === true ? undefined : sharp);
+      const k = keep === undefined || keep === null ? null : meshKeep(keep === true ? undefined : keep);
+      return addon.extractMesh(this.ctx, this.sceneHandle(scene), grid, meshParams(opts), s, k, !!components, meshSimplify(simplify));
+    }
     const plain = (keep === undefined || keep === null) && !components;
     if (plain && (sharp === undefined || sharp === null)) return addon.extractMesh(this.ctx, this.sceneHandle(scene), grid, meshParams(opts));
     const s = sharp === undefined || sharp === null ? null : meshSharp(sharp === true ? undefined : sharp);
@@ -368,10 +375,14 @@ class RenderJobContext {  // RenderJobContext + loadRenderJobContext (LoadRender
     return addon.extractMesh(this.ctx, this.sceneHandle(scene), grid, meshParams(opts), s, k, !!components);
   }
   // the mesher alone on the caller's field: values Float32Array of the grid's corners, x fastest (rm_mesh_from_values)
-  // keep, components: as in extractMesh
-  meshFromValues(grid, values, iso = 0, keep, components) {
+  // keep, components, simplify: as in extractMesh
+  meshFromValues(grid, values, iso = 0, keep, components, simplify) {
     if (!(values instanceof Float32Array)) throw new TypeError("meshFromValues: values must be a Float32Array");
     if (!finite(iso)) throw new RangeError("mesh: iso must be a finite number");
+    if (simplify !== undefined && simplify !== null) {
+      const k = keep === undefined || keep === null ? null : meshKeep(keep === true ? undefined : keep);
+      return addon.meshFromValues(this.ctx, grid, values, iso, k, !!components, meshSimplify(simplify));
+    }
     if ((keep === undefined || keep === null) && !components) return addon.meshFromValues(this.ctx, grid, values, iso);
     const k = keep === undefined || keep === null ? null : meshKeep(keep === true ? undefined : keep);
     return addon.meshFromValues(this.ctx, grid, values, iso, k, !!components);
@@ -696,6 +707,22 @@ function meshKeep(opts) {
   return p;
 }
 
+// the simplify block of extractMesh / meshFromValues (include/hip_raymarch.h RmMeshSimplify and the RmGrid of clusters): an object with grid (a
+// meshGrid: one output vertex per occupied cell; it need not be related to the sampling grid) and, optionally, keepDuplicates (keep the triangles
+// that repeat an earlier one); checked as the library checks them; returns { grid, keepDuplicates: 0 | 1 }
+const MESH_SIMPLIFY_DEFAULTS = { keepDuplicates: 0 };
+function meshSimplify(opts) {
+  if (opts === undefined || opts === null || typeof opts !== "object") throw new TypeError("mesh: expected an object of simplify parameters");
+  for (const k of Object.keys(opts))
+    if (k !== "grid" && !(k in MESH_SIMPLIFY_DEFAULTS)) throw new TypeError("mesh: unknown simplify parameter " + k);
+  const g = opts.grid;
+  if (g === undefined || g === null || typeof g !== "object") throw new TypeError("mesh: simplify needs a grid { lo, hi, n }");
+  const d = "keepDuplicates" in opts ? opts.keepDuplicates : MESH_SIMPLIFY_DEFAULTS.keepDuplicates;
+  const flag = d === true || d === 1 ? 1 : d === false || d === 0 ? 0 : -1;
+  if (flag < 0) throw new RangeError("mesh: simplify keepDuplicates must be true or false");
+  return { grid: meshGrid(g.lo, g.hi, g.n), keepDuplicates: flag };
+}
+
 // binary little-endian PLY of { positions, triangles, normals?, colours? }: x y z, then nx ny nz, then uchar red green blue
 // (floor(clamp(c, 0, 1) * 255 + 0.5), NaN as 0); faces as a uchar count and uint indices -- the bytes the Python host writes
 function encodePly(mesh) {
@@ -748,4 +775,4 @@ module.exports = { RM, addon, encodePng, Scene, CsgScene, Mandelbulb, singleSphe
                    tileRect, RenderJobContext, ShardedRenderJobContext, doRenderJob, U_OFFSET, DENOISE_DEFAULTS, denoiseParams,
                    DENOISE_VARIANCE_DEFAULTS, denoiseVarianceParams, DESPECKLE_DEFAULTS, despeckleParams, DISPLAY_DEFAULTS, AUTO_EXPOSURE_DEFAULTS,
                    displayParams, statsExposure, statsPercentile, MESH_DEFAULTS, meshGrid, meshParams, MESH_SHARP_DEFAULTS, meshSharp, MESH_KEEP_DEFAULTS, meshKeep,
-                   encodePly };
+                   MESH_SIMPLIFY_DEFAULTS, meshSimplify, encodePly };

@@ -539,6 +539,45 @@ static napi_value MeshKeepBlock(napi_env env, napi_callback_info info) {
   return b;
 }
 
+static const Field MESH_SIMPLIFY_FIELDS[] = {{"keepDuplicates", Field::FLAG, offsetof(RmMeshSimplify, keep_duplicates)}};
+// the simplify block of extractMesh / meshFromValues: null / undefined = none (*given = false), an object { grid: { lo, hi, n }, keepDuplicates } =
+// rm_mesh_simplify on that grid of clusters
+struct MeshSimplifyBlock {
+  RmGrid clusters;
+  RmMeshSimplify params;
+};
+static bool get_mesh_simplify(napi_env env, napi_value v, MeshSimplifyBlock* s, bool* given) {
+  rm_mesh_simplify_default(&s->params);
+  std::memset(&s->clusters, 0, sizeof s->clusters);
+  if (!get_block(env, v, &s->params, MESH_SIMPLIFY_FIELDS, given)) return false;
+  if (!*given) return true;
+  napi_value g;
+  return napi_get_named_property(env, v, "grid", &g) == napi_ok && get_grid(env, g, &s->clusters);
+}
+
+// meshSimplifyBlock(simplify) -> { grid: ArrayBuffer(RmGrid), params: ArrayBuffer(RmMeshSimplify) }: the bytes the mesh calls hand to rm_mesh_simplify
+static napi_value MeshSimplifyBlockOf(napi_env env, napi_callback_info info) {
+  size_t argc = 1;
+  napi_value argv[1];
+  NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+  MeshSimplifyBlock s;
+  bool given = false;
+  if (argc != 1 || !get_mesh_simplify(env, argv[0], &s, &given) || !given) {
+    napi_throw_type_error(env, nullptr, "meshSimplifyBlock(simplify: { grid: { lo, hi, n }, keepDuplicates })");
+    return nullptr;
+  }
+  napi_value o, gb, pb;
+  void *gd = nullptr, *pd = nullptr;
+  NAPI_OK(napi_create_object(env, &o));
+  NAPI_OK(napi_create_arraybuffer(env, sizeof s.clusters, &gd, &gb));
+  NAPI_OK(napi_create_arraybuffer(env, sizeof s.params, &pd, &pb));
+  std::memcpy(gd, &s.clusters, sizeof s.clusters);
+  std::memcpy(pd, &s.params, sizeof s.params);
+  NAPI_OK(napi_set_named_property(env, o, "grid", gb));
+  NAPI_OK(napi_set_named_property(env, o, "params", pb));
+  return o;
+}
+
 static napi_value make_array(napi_env env, napi_typedarray_type type, size_t count, void** data) {
   napi_value ab, out;
   if (napi_create_arraybuffer(env, count * 4, data, &ab) != napi_ok || napi_create_typedarray(env, type, count, ab, 0, &out) != napi_ok) return nullptr;
@@ -596,8 +635,10 @@ static napi_value SdfGrid(napi_env env, napi_callback_info info) {
 // the mesh as { positions, normals | null, colours | null: Float32Array(3 V), triangles: Uint32Array(3 T), cells: Uint32Array(V), timings: [sampling,
 // meshing, attributes] in ms (rm_mesh_timings) }; normals / colours: whether the call asked for them; the handle is destroyed.  keep: the mesh is
 // first filtered on the device (rm_mesh_filter) and the filtered one is what is copied; components: labels: Uint32Array(V) and componentSizes:
-// Uint32Array(2 C) come with it (rm_mesh_components)
-static napi_value mesh_result(napi_env env, rm_ctx* ctx, rm_mesh* mesh, bool normals, bool colours, const RmMeshKeep* keep = nullptr, bool components = false) {
+// Uint32Array(2 C) come with it (rm_mesh_components).  simplify: before either, the mesh is clustered on the device (rm_mesh_simplify), so one
+// filter also removes the vertices the clustering left without triangles
+static napi_value mesh_result(napi_env env, rm_ctx* ctx, rm_mesh* mesh, bool normals, bool colours, const RmMeshKeep* keep = nullptr, bool components = false,
+                              const MeshSimplifyBlock* simplify = nullptr) {
   struct Guard {  // the handle in hand is destroyed on every way out
     rm_mesh* h;
     ~Guard() { rm_mesh_destroy(h); }
@@ -606,6 +647,12 @@ static napi_value mesh_result(napi_env env, rm_ctx* ctx, rm_mesh* mesh, bool nor
     napi_throw_error(env, nullptr, "N-API call failed while the mesh was copied");
     return nullptr;
   };
+  if (simplify) {
+    rm_mesh* simplified = nullptr;
+    if (rm_mesh_simplify(mesh, &simplify->clusters, &simplify->params, &simplified) != RM_OK) return throw_rm(env, ctx, "rm_mesh_simplify");
+    rm_mesh_destroy(mesh);
+    guard.h = mesh = simplified;
+  }
   if (keep) {
     rm_mesh* filtered = nullptr;
     if (rm_mesh_filter(mesh, keep, &filtered) != RM_OK) return throw_rm(env, ctx, "rm_mesh_filter");
@@ -651,48 +698,52 @@ static napi_value mesh_result(napi_env env, rm_ctx* ctx, rm_mesh* mesh, bool nor
   return o;
 }
 
-// extractMesh(ctx, scene, grid, params | null[, sharp | null[, keep | null[, components]]]) = rm_mesh_extract, or with a sharp block
-// rm_mesh_extract_sharp; with a keep block rm_mesh_filter behind it; then the arrays
+// extractMesh(ctx, scene, grid, params | null[, sharp | null[, keep | null[, components[, simplify | null]]]]) = rm_mesh_extract, or with a sharp
+// block rm_mesh_extract_sharp; with a simplify block rm_mesh_simplify behind it; with a keep block rm_mesh_filter behind that; then the arrays
 static napi_value ExtractMesh(napi_env env, napi_callback_info info) {
-  size_t argc = 7;
-  napi_value argv[7];
+  size_t argc = 8;
+  napi_value argv[8];
   NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
-  const bool counted = argc >= 4 && argc <= 7;
+  const bool counted = argc >= 4 && argc <= 8;
   rm_ctx* ctx = counted ? get_external<rm_ctx>(env, argv[0]) : nullptr;
   rm_scene* scene = counted ? get_external<rm_scene>(env, argv[1]) : nullptr;
   RmGrid g;
   RmMeshParams p;
   RmMeshSharp s;
   RmMeshKeep k;
-  bool sharp = false, keep = false, components = false;
+  MeshSimplifyBlock c;
+  bool sharp = false, keep = false, components = false, simplify = false;
   if (!ctx || !scene || !get_grid(env, argv[2], &g) || !get_mesh_params(env, argv[3], &p) || (argc >= 5 && !get_mesh_sharp(env, argv[4], &s, &sharp)) ||
-      (argc >= 6 && !get_mesh_keep(env, argv[5], &k, &keep)) || (argc == 7 && !get_bool(env, argv[6], &components))) {
-    napi_throw_type_error(env, nullptr, "extractMesh(ctx, scene, grid, params | null[, sharp | null[, keep | null[, components]]])");
+      (argc >= 6 && !get_mesh_keep(env, argv[5], &k, &keep)) || (argc >= 7 && !get_bool(env, argv[6], &components)) ||
+      (argc == 8 && !get_mesh_simplify(env, argv[7], &c, &simplify))) {
+    napi_throw_type_error(env, nullptr, "extractMesh(ctx, scene, grid, params | null[, sharp | null[, keep | null[, components[, simplify | null]]]])");
     return nullptr;
   }
   rm_mesh* mesh = nullptr;
   if (sharp) {
     if (rm_mesh_extract_sharp(ctx, scene, &g, &p, &s, &mesh) != RM_OK) return throw_rm(env, ctx, "rm_mesh_extract_sharp");
   } else if (rm_mesh_extract(ctx, scene, &g, &p, &mesh) != RM_OK) return throw_rm(env, ctx, "rm_mesh_extract");
-  return mesh_result(env, ctx, mesh, p.normals != 0, p.colours != 0, keep ? &k : nullptr, components);
+  return mesh_result(env, ctx, mesh, p.normals != 0, p.colours != 0, keep ? &k : nullptr, components, simplify ? &c : nullptr);
 }
 
-// meshFromValues(ctx, grid, values: Float32Array(corners), iso[, keep | null[, components]]) = rm_mesh_from_values, with a keep block
-// rm_mesh_filter behind it, then the arrays
+// meshFromValues(ctx, grid, values: Float32Array(corners), iso[, keep | null[, components[, simplify | null]]]) = rm_mesh_from_values, with a
+// simplify block rm_mesh_simplify behind it, with a keep block rm_mesh_filter behind that, then the arrays
 static napi_value MeshFromValues(napi_env env, napi_callback_info info) {
-  size_t argc = 6;
-  napi_value argv[6];
+  size_t argc = 7;
+  napi_value argv[7];
   NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
-  rm_ctx* ctx = argc >= 4 && argc <= 6 ? get_external<rm_ctx>(env, argv[0]) : nullptr;
+  rm_ctx* ctx = argc >= 4 && argc <= 7 ? get_external<rm_ctx>(env, argv[0]) : nullptr;
   RmMeshKeep k;
-  bool keep = false, components = false;
+  MeshSimplifyBlock c;
+  bool keep = false, components = false, simplify = false;
   RmGrid g;
   double iso = 0.0;
   void* d = nullptr;
   size_t n = 0;
   if (!ctx || !get_grid(env, argv[1], &g) || !get_buffer(env, argv[2], &d, &n) || napi_get_value_double(env, argv[3], &iso) != napi_ok ||
-      (argc >= 5 && !get_mesh_keep(env, argv[4], &k, &keep)) || (argc == 6 && !get_bool(env, argv[5], &components))) {
-    napi_throw_type_error(env, nullptr, "meshFromValues(ctx, grid, values: Float32Array, iso[, keep | null[, components]])");
+      (argc >= 5 && !get_mesh_keep(env, argv[4], &k, &keep)) || (argc >= 6 && !get_bool(env, argv[5], &components)) ||
+      (argc == 7 && !get_mesh_simplify(env, argv[6], &c, &simplify))) {
+    napi_throw_type_error(env, nullptr, "meshFromValues(ctx, grid, values: Float32Array, iso[, keep | null[, components[, simplify | null]]])");
     return nullptr;
   }
   float probe[1025];
@@ -703,7 +754,7 @@ static napi_value MeshFromValues(napi_env env, napi_callback_info info) {
   }
   rm_mesh* mesh = nullptr;
   if (rm_mesh_from_values(ctx, &g, static_cast<const float*>(d), (float)iso, &mesh) != RM_OK) return throw_rm(env, ctx, "rm_mesh_from_values");
-  return mesh_result(env, ctx, mesh, false, false, keep ? &k : nullptr, components);
+  return mesh_result(env, ctx, mesh, false, false, keep ? &k : nullptr, components, simplify ? &c : nullptr);
 }
 
 // fbCreateStriped(ctx, width, height, stripeRows, parts, part[, gbuffer]): the stripes k with k % parts == part of a width x height image,
@@ -902,7 +953,7 @@ static napi_value Sizes(napi_env env, napi_callback_info) {
       {"RmMaterial", (uint32_t)sizeof(RmMaterial)}, {"RmRect", (uint32_t)sizeof(RmRect)}, {"RmSurface", (uint32_t)sizeof(RmSurface)}, {"RmDenoise", (uint32_t)sizeof(RmDenoise)},
       {"RmDenoiseVariance", (uint32_t)sizeof(RmDenoiseVariance)}, {"RmDespeckle", (uint32_t)sizeof(RmDespeckle)}, {"RmFilters", (uint32_t)sizeof(RmFilters)}, {"RmFrameStats", (uint32_t)sizeof(RmFrameStats)},
       {"RmAutoExposure", (uint32_t)sizeof(RmAutoExposure)}, {"RmDisplay", (uint32_t)sizeof(RmDisplay)}, {"RmGrid", (uint32_t)sizeof(RmGrid)},
-      {"RmMeshParams", (uint32_t)sizeof(RmMeshParams)}, {"RmMeshSharp", (uint32_t)sizeof(RmMeshSharp)}, {"RmMeshKeep", (uint32_t)sizeof(RmMeshKeep)}, {"abi", (uint32_t)rm_abi_version()}};
+      {"RmMeshParams", (uint32_t)sizeof(RmMeshParams)}, {"RmMeshSharp", (uint32_t)sizeof(RmMeshSharp)}, {"RmMeshKeep", (uint32_t)sizeof(RmMeshKeep)}, {"RmMeshSimplify", (uint32_t)sizeof(RmMeshSimplify)}, {"abi", (uint32_t)rm_abi_version()}};
   for (const auto& it : items) {
     NAPI_OK(napi_create_uint32(env, it.v, &v));
     NAPI_OK(napi_set_named_property(env, o, it.k, v));
@@ -915,7 +966,7 @@ static napi_value Init(napi_env env, napi_value exports) {
       {"ctxCreate", CtxCreate}, {"ctxDestroy", CtxDestroy}, {"sync", Sync}, {"sceneCreate", SceneCreate}, {"sceneDestroy", SceneDestroy},
       {"fbCreate", FbCreate}, {"fbClear", FbClear}, {"fbDestroy", FbDestroy}, {"fbDownload", FbDownload}, {"present", Present}, {"denoise", Denoise}, {"presentDenoised", PresentDenoised}, {"denoiseVariance", DenoiseVariance}, {"presentDenoisedVariance", PresentDenoisedVariance}, {"filter", Filter}, {"presentFiltered", PresentFiltered}, {"presentDisplay", PresentDisplay}, {"presentLinear", PresentLinear}, {"frameStats", FrameStats}, {"statsExposure", StatsExposure}, {"statsPercentile", StatsPercentile}, {"renderSample", RenderSample}, {"renderSamples", RenderSamples},
       {"fbCreateStriped", FbCreateStriped}, {"fbRows", FbRows}, {"setSamplesInFlight", SetSamplesInFlight}, {"presentSharded", PresentSharded}, {"presentShardedStart", PresentShardedStart}, {"presentShardedFinish", PresentShardedFinish},
-      {"meshBlocks", MeshBlocks}, {"meshSharpBlock", MeshSharpBlock}, {"meshKeepBlock", MeshKeepBlock}, {"sdfGrid", SdfGrid}, {"extractMesh", ExtractMesh}, {"meshFromValues", MeshFromValues}, {"sizes", Sizes}};
+      {"meshBlocks", MeshBlocks}, {"meshSharpBlock", MeshSharpBlock}, {"meshKeepBlock", MeshKeepBlock}, {"meshSimplifyBlock", MeshSimplifyBlockOf}, {"sdfGrid", SdfGrid}, {"extractMesh", ExtractMesh}, {"meshFromValues", MeshFromValues}, {"sizes", Sizes}};
   for (const auto& f : fns) {
     napi_value fn;
     if (napi_create_function(env, f.name, NAPI_AUTO_LENGTH, f.fn, nullptr, &fn) != napi_ok) return nullptr;

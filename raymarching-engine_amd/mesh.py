@@ -112,6 +112,17 @@ def mesh_keep(**fields) -> abi.RmMeshKeep:
     return abi.RmMeshKeep(min_triangles=int(p["min_triangles"]), largest=int(p["largest"]))
 
 
+def mesh_simplify(grid, keep_duplicates=False) -> tuple:
+    """The (abi.RmGrid, abi.RmMeshSimplify) of Context.extract_mesh(..., simplify=...) / mesh_from_values(..., simplify=...): `grid` is the
+    Grid of clusters (one output vertex per occupied cell, it need not be related to the sampling grid), keep_duplicates keeps the triangles
+    that repeat an earlier one.  Checked as the library checks them: ValueError otherwise."""
+    if not isinstance(grid, Grid):
+        raise ValueError("mesh: simplify grid must be a mesh.Grid")
+    if not (isinstance(keep_duplicates, (bool, int, np.integer)) and int(keep_duplicates) in (0, 1)):
+        raise ValueError("mesh: simplify keep_duplicates must be True or False")
+    return grid.to_c(), abi.RmMeshSimplify(keep_duplicates=int(keep_duplicates))
+
+
 @dataclass
 class Mesh:
     """A triangle mesh as numpy arrays: positions [V, 3] float32, triangles [T, 3] uint32 (counter-clockwise seen from outside), cells

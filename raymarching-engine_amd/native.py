@@ -43,6 +43,7 @@ EXPORTS = [
     "rm_grid_axis", "rm_sdf_grid", "rm_sdf_grid_device", "rm_mesh_params_default", "rm_mesh_extract", "rm_mesh_from_values", "rm_mesh_counts", "rm_mesh_timings",
     "rm_mesh_download", "rm_mesh_device_ptr", "rm_mesh_destroy", "rm_mesh_sharp_default", "rm_mesh_extract_sharp",
     "rm_mesh_keep_default", "rm_mesh_components", "rm_mesh_components_download", "rm_mesh_filter",
+    "rm_mesh_simplify_default", "rm_mesh_simplify",
 ]
 
 # G-buffer formats of a framebuffer (include/hip_raymarch.h RM_GBUFFER_*): "f32" (the default: the software GL stack's planes, which the
@@ -415,6 +416,8 @@ def load_library(path=None):
         "rm_mesh_components": (ip, [vp, C.POINTER(C.c_ulonglong)]),
         "rm_mesh_components_download": (ip, [vp, ip, vp, C.c_size_t]),
         "rm_mesh_filter": (ip, [vp, C.POINTER(abi.RmMeshKeep), C.POINTER(vp)]),
+        "rm_mesh_simplify_default": (None, [C.POINTER(abi.RmMeshSimplify)]),
+        "rm_mesh_simplify": (ip, [vp, C.POINTER(abi.RmGrid), C.POINTER(abi.RmMeshSimplify), C.POINTER(vp)]),
     }
     for name, (res, args) in sig.items():
         if name.startswith("rm_debug_") and not hasattr(lib, name) and os.environ.get("RM_LIB"):
@@ -711,14 +714,21 @@ class Context:
         g = grid.to_c()
         self._check(self.lib.rm_sdf_grid_device(self.h, scene.h, C.byref(g), int(flags), C.c_void_p(out_ptr), C.c_void_p(stream) if stream else None))
 
-    def _take_mesh(self, handle, grid, normals=False, colours=False, keep=None, components=False):
+    def _take_mesh(self, handle, grid, normals=False, colours=False, keep=None, components=False, simplify=None):
         """The arrays of a mesh handle as a mesh.Mesh (normals / colours: whether the call that made it asked for them); destroys the handle.
-        keep (an abi.RmMeshKeep): the mesh is first filtered on the device (rm_mesh_filter) and the filtered one is what is downloaded; components: its labels and
-        component sizes come with it."""
+        simplify (_mesh_simplify's triple): the mesh is first clustered on the device (rm_mesh_simplify) and the Mesh's grid is the cluster grid,
+        which its cells then index; keep (an abi.RmMeshKeep): that mesh is filtered on the device (rm_mesh_filter), which also removes the vertices
+        simplification left without triangles; the last of them is what is downloaded.  components: its labels and component sizes come with it."""
         from .mesh import Mesh
 
         handles = [handle]
         try:
+            if simplify is not None:
+                grid, clusters, params = simplify
+                simplified = C.c_void_p()
+                self._check(self.lib.rm_mesh_simplify(handle, C.byref(clusters), C.byref(params), C.byref(simplified)))
+                handles.append(simplified)
+                handle = simplified
             if keep is not None:
                 filtered = C.c_void_p()
                 self._check(self.lib.rm_mesh_filter(handle, C.byref(keep), C.byref(filtered)))
@@ -774,18 +784,43 @@ class Context:
     def _mesh_keep(keep):
         return Context._mesh_block("keep", keep, abi.RmMeshKeep)
 
+    @staticmethod
+    def _mesh_simplify(simplify):
+        """The `simplify` of extract_mesh / mesh_from_values as (mesh.Grid of the clusters, abi.RmGrid, abi.RmMeshSimplify), through
+        mesh.mesh_simplify's checks: None stays None; a mesh.Grid is that grid with the defaults, a dict mesh_simplify's arguments, a pair
+        (abi.RmGrid, abi.RmMeshSimplify) its fields -- whose `reserved` are left for the library to refuse."""
+        from . import mesh
+
+        if simplify is None:
+            return None
+        if isinstance(simplify, mesh.Grid):
+            return (simplify,) + mesh.mesh_simplify(simplify)
+        if isinstance(simplify, dict):
+            unknown = set(simplify) - {"grid", "keep_duplicates"}
+            if unknown or "grid" not in simplify:
+                raise ValueError(f"mesh: unknown simplify parameter {sorted(unknown)[0]}" if unknown else "mesh: simplify needs a grid")
+            return (simplify["grid"],) + mesh.mesh_simplify(**simplify)
+        if isinstance(simplify, tuple) and len(simplify) == 2 and isinstance(simplify[0], abi.RmGrid) and isinstance(simplify[1], abi.RmMeshSimplify):
+            g, p = simplify
+            grid = mesh.Grid(tuple(g.lo), tuple(g.hi), tuple(g.n))
+            mesh.mesh_simplify(grid, p.keep_duplicates)
+            return grid, g, p
+        raise ValueError("mesh: simplify must be None, a mesh.Grid, a dict of mesh_simplify's arguments or its (abi.RmGrid, abi.RmMeshSimplify)")
+
     def extract_mesh(self, scene: "SceneHandle", grid, iso: float = 0.0, normals: bool = True, colours: bool = False, flags: int = 0,
-                     normal_delta: float = 1e-5, sharp=None, *, keep=None, components: bool = False):
+                     normal_delta: float = 1e-5, sharp=None, *, keep=None, components: bool = False, simplify=None):
         """The level set `iso` of the scene on `grid` (mesh.Grid) as a mesh.Mesh: rm_mesh_extract -- the distances sampled and meshed
         (surface nets) on the device, with per-vertex normals / diffuse colours from the scene's probes when asked for.  `sharp`: None is
         that call; True (the defaults), a dict of mesh.mesh_sharp's arguments or an abi.RmMeshSharp is rm_mesh_extract_sharp -- the same
         triangles with every vertex at its cell's QEF minimiser, which keeps the edges and corners of hard-edged scenes.  `keep`: None
         is that mesh; True (the defaults: drop unreferenced vertices), a dict of mesh.mesh_keep's arguments or an abi.RmMeshKeep filters its
         connected components on the device before anything is downloaded (rm_mesh_filter).  `components`: the returned mesh carries
-        labels and component_sizes (rm_mesh_components)."""
+        labels and component_sizes (rm_mesh_components).  `simplify`: None is that mesh; a mesh.Grid of clusters, a dict of
+        mesh.mesh_simplify's arguments or its pair merges the vertices of every cluster cell into one on the device (rm_mesh_simplify) before
+        `keep` and `components` are applied, and the returned mesh's grid is the cluster grid."""
         from .mesh import mesh_params
 
-        keep = self._mesh_keep(keep)  # (refused before anything runs)
+        keep, simplify = self._mesh_keep(keep), self._mesh_simplify(simplify)  # (refused before anything runs)
         g, p = grid.to_c(), mesh_params(iso=iso, normals=normals, colours=colours, flags=flags, normal_delta=normal_delta)
         h = C.c_void_p()
         s = self._mesh_block("sharp", sharp, abi.RmMeshSharp)
@@ -793,19 +828,19 @@ class Context:
             self._check(self.lib.rm_mesh_extract(self.h, scene.h, C.byref(g), C.byref(p), C.byref(h)))
         else:
             self._check(self.lib.rm_mesh_extract_sharp(self.h, scene.h, C.byref(g), C.byref(p), C.byref(s), C.byref(h)))
-        return self._take_mesh(h, grid, normals=p.normals, colours=p.colours, keep=keep, components=components)
+        return self._take_mesh(h, grid, normals=p.normals, colours=p.colours, keep=keep, components=components, simplify=simplify)
 
-    def mesh_from_values(self, grid, values: np.ndarray, iso: float = 0.0, *, keep=None, components: bool = False):
-        """The mesher alone on the caller's field: `values` float32 [nz + 1, ny + 1, nx + 1] (rm_mesh_from_values).  keep and components:
-        as in extract_mesh."""
-        keep = self._mesh_keep(keep)
+    def mesh_from_values(self, grid, values: np.ndarray, iso: float = 0.0, *, keep=None, components: bool = False, simplify=None):
+        """The mesher alone on the caller's field: `values` float32 [nz + 1, ny + 1, nx + 1] (rm_mesh_from_values).  keep, components and
+        simplify: as in extract_mesh."""
+        keep, simplify = self._mesh_keep(keep), self._mesh_simplify(simplify)
         g = grid.to_c()
         v = np.ascontiguousarray(values, np.float32)
         if v.shape != grid.shape:
             raise ValueError(f"values must have the shape {grid.shape} of the grid's corners, not {v.shape}")
         h = C.c_void_p()
         self._check(self.lib.rm_mesh_from_values(self.h, C.byref(g), _fp(v), float(iso), C.byref(h)))
-        return self._take_mesh(h, grid, keep=keep, components=components)
+        return self._take_mesh(h, grid, keep=keep, components=components, simplify=simplify)
 
     def probe_camera(self, uniforms: abi.RmUniforms, width: int, height: int) -> np.ndarray:
         out = np.empty((height, width, 8), np.float32)
