@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define RM_ABI_VERSION 9 /* 9: RM_GBUFFER_F32 / _F16, rm_fb_create_fmt, rm_fb_create_striped_fmt, rm_fb_wrap_fmt, rm_fb_gbuffer, rm_fb_download_raw, rm_fb_upload_raw, RmDenoise, rm_denoise_default, rm_denoise, rm_denoise_device, rm_present_denoised, RM_FB_MOMENTS, RM_PLANE_MOMENTS, rm_fb_has_moments, RmDenoiseVariance, rm_denoise_variance_default, rm_denoise_variance, rm_denoise_variance_device, rm_present_denoised_variance, RmDespeckle, RmFilters, RM_DENOISE_NONE / _ATROUS / _VARIANCE, rm_filters_default, rm_filter, rm_filter_device, rm_present_filtered, RM_STATS_BINS, RmFrameStats, rm_frame_stats, RmAutoExposure, rm_auto_exposure_default, rm_stats_percentile, rm_stats_exposure, RM_TONE_CLIP / _REINHARD / _ACES, RmDisplay, rm_display_default, rm_present_display, rm_present_display_device, rm_present_linear, RmGrid, rm_grid_axis, rm_sdf_grid, rm_sdf_grid_device, RmMeshParams, rm_mesh_params_default, rm_mesh, rm_mesh_extract, rm_mesh_from_values, rm_mesh_counts, rm_mesh_timings, RM_MESH_POSITIONS / _NORMALS / _COLOURS / _TRIANGLES / _CELLS, rm_mesh_download, rm_mesh_device_ptr, rm_mesh_destroy, RmMeshSharp, rm_mesh_sharp_default, rm_mesh_extract_sharp, RmMeshKeep, rm_mesh_keep_default, rm_mesh_components, RM_MESH_PART_LABELS / _SIZES, rm_mesh_components_download, rm_mesh_filter, RmMeshSimplify, rm_mesh_simplify_default, rm_mesh_simplify (additions only); 8: RM_PRIM_TORUS / _CYLINDER / _PLANE, RM_OP_SMOOTH_SUBTRACT / _INTERSECT, rm_probe_math (additions only); 7: rm_present_sharded_finish / rm_present_sharded take the size of the host buffer (a changed signature), rm_ctx_set_cull_min_pixels, rm_ctx_set_cull_budget, rm_ctx_cull_stats; 6: rm_present_striped_rows, rm_present_sharded_start / _finish, rm_ctx_last_warning, RM_PROBE_CAST_SHADOW, RM_PRIM_KIND (additions only); 3: rm_ctx_set_sample_batch, rm_buffer_*; 4: rm_ctx_set_gl_stack; 5: RmSurface / RmSceneDesc.surfaces (the struct grew), rm_pack_present_rows, rm_present_sharded, rm_ctx_last_pipeline, RM_RENDER_NO_FAR_JUMP, RM_RENDER_NO_CULL (additions only) */
+#define RM_ABI_VERSION 9 /* 9: RM_GBUFFER_F32 / _F16, rm_fb_create_fmt, rm_fb_create_striped_fmt, rm_fb_wrap_fmt, rm_fb_gbuffer, rm_fb_download_raw, rm_fb_upload_raw, RmDenoise, rm_denoise_default, rm_denoise, rm_denoise_device, rm_present_denoised, RM_FB_MOMENTS, RM_PLANE_MOMENTS, rm_fb_has_moments, RmDenoiseVariance, rm_denoise_variance_default, rm_denoise_variance, rm_denoise_variance_device, rm_present_denoised_variance, RmDespeckle, RmFilters, RM_DENOISE_NONE / _ATROUS / _VARIANCE, rm_filters_default, rm_filter, rm_filter_device, rm_present_filtered, RM_STATS_BINS, RmFrameStats, rm_frame_stats, RmAutoExposure, rm_auto_exposure_default, rm_stats_percentile, rm_stats_exposure, RM_TONE_CLIP / _REINHARD / _ACES, RmDisplay, rm_display_default, rm_present_display, rm_present_display_device, rm_present_linear, RmGrid, rm_grid_axis, rm_sdf_grid, rm_sdf_grid_device, RmMeshParams, rm_mesh_params_default, rm_mesh, rm_mesh_extract, rm_mesh_from_values, rm_mesh_counts, rm_mesh_timings, RM_MESH_POSITIONS / _NORMALS / _COLOURS / _TRIANGLES / _CELLS, rm_mesh_download, rm_mesh_device_ptr, rm_mesh_destroy, RmMeshSharp, rm_mesh_sharp_default, rm_mesh_extract_sharp, RmMeshKeep, rm_mesh_keep_default, rm_mesh_components, RM_MESH_PART_LABELS / _SIZES, rm_mesh_components_download, rm_mesh_filter, RmMeshSimplify, rm_mesh_simplify_default, rm_mesh_simplify, RmMeshQuadric, rm_mesh_quadric_default, rm_mesh_simplify_quadric (additions only); 8: RM_PRIM_TORUS / _CYLINDER / _PLANE, RM_OP_SMOOTH_SUBTRACT / _INTERSECT, rm_probe_math (additions only); 7: rm_present_sharded_finish / rm_present_sharded take the size of the host buffer (a changed signature), rm_ctx_set_cull_min_pixels, rm_ctx_set_cull_budget, rm_ctx_cull_stats; 6: rm_present_striped_rows, rm_present_sharded_start / _finish, rm_ctx_last_warning, RM_PROBE_CAST_SHADOW, RM_PRIM_KIND (additions only); 3: rm_ctx_set_sample_batch, rm_buffer_*; 4: rm_ctx_set_gl_stack; 5: RmSurface / RmSceneDesc.surfaces (the struct grew), rm_pack_present_rows, rm_present_sharded, rm_ctx_last_pipeline, RM_RENDER_NO_FAR_JUMP, RM_RENDER_NO_CULL (additions only) */
 
 #define RM_MAX_BOUNCES 10 /* raymarchingStepCountsArray[10], raymarcher.frag:31 */
 #define RM_MAX_LIGHTS 10  /* lightPositions[10],             raymarcher.frag:37-39 */
@@ -980,8 +980,8 @@ RM_API int rm_mesh_filter(rm_mesh* mesh, const RmMeshKeep* keep, rm_mesh** out);
  * the vertices of each of its cells into one, and drops the triangles that collapse or repeat.  It works on any rm_mesh (rm_mesh_extract, _sharp,
  * _from_values, rm_mesh_filter, an earlier rm_mesh_simplify) and changes nothing of it; the result is an ordinary rm_mesh of the same context, which
  * every mesh entry serves.  `clusters` is valid by RmGrid's rule and need not be related to the grid the mesh was sampled on; n[a] cells of
- * h[a] = (hi[a] - lo[a]) / (float)n[a] per axis, as everywhere.  There are no error quadrics and no care for manifoldness: a cluster's vertex
- * is the mean of its vertices, and thin sheets closer than a cluster cell merge.
+ * h[a] = (hi[a] - lo[a]) / (float)n[a] per axis, as everywhere.  There is no care for manifoldness: a cluster's vertex
+ * is the mean of its vertices (rm_mesh_simplify_quadric below places it by error quadrics), and thin sheets closer than a cluster cell merge.
  * Arithmetic: fp32 unless it says double, every operation rounded on its own (no contraction), IEEE division and square root, the same whatever
  * build made the source.  Q20(x) = (long long)rintf(x * 1048576.0f).  For V vertices and T triangles:
  *   1. Cluster of a vertex p.  Per axis a: u = (p[a] - lo[a]) / h[a]; i = 0 if !(u >= 0) (NaN too), i = n[a] - 1 if u >= (float)n[a], else
@@ -1021,6 +1021,53 @@ RM_API int rm_mesh_filter(rm_mesh* mesh, const RmMeshKeep* keep, rm_mesh** out);
 typedef struct RmMeshSimplify { int32_t keep_duplicates; int32_t reserved[3]; } RmMeshSimplify; /* 16 bytes */
 RM_API void rm_mesh_simplify_default(RmMeshSimplify* params);
 RM_API int rm_mesh_simplify(rm_mesh* mesh, const RmGrid* clusters, const RmMeshSimplify* params, rm_mesh** out);
+
+/* ---- quadric placement (opt-in): a cluster's vertex where it best keeps the surface ----
+ * rm_mesh_simplify puts a cluster's vertex at the mean of its vertices, which bevels every edge and corner inside a cluster by a fraction of a
+ * CLUSTER cell -- what rm_mesh_extract_sharp had won back on the fine grid.  rm_mesh_simplify_quadric is to rm_mesh_simplify what
+ * rm_mesh_extract_sharp is to rm_mesh_extract: the same mesh, with every vertex moved to the minimiser of the summed plane quadrics of the source
+ * triangles that touch its cluster (Lindstrom, "Out-of-core simplification of large polygonal models", 2000).  Only the positions move.  The
+ * source is unchanged; the result is an ordinary rm_mesh of the same context, which every mesh entry serves.  rm_mesh_simplify, its struct and
+ * its refusals are as they were.  params == NULL and quadric == NULL: the defaults (keep_duplicates 0; threshold 0.1f).
+ * Arithmetic: fp32 unless it says double, every operation rounded on its own (no contraction), IEEE division and square root, the same whatever
+ * build made the source.  Let S be the result of rm_mesh_simplify(mesh, clusters, params): it gives, for every source vertex v, its output vertex
+ * o(v) and its clamped quantised fractions q_v[a] (step 1 there), and for every output vertex its cell indices i[a] and mean fractions g[a] (step
+ * 2 there).  Q24(x) = (long long)rintf(x * 16777216.0f).  For V vertices and T triangles of the source:
+ *   0. Every array of the result except RM_MESH_POSITIONS is bit for bit the corresponding array of S: the vertex count and order, RM_MESH_CELLS,
+ *      RM_MESH_TRIANGLES (both settings of keep_duplicates), and normals and colours when the source has them -- those stay the cluster means, a
+ *      mesh has no scene to probe again.  The result starts without a labelling.
+ *   1. Axis scale.  hmax = h[0]; if (h[1] > hmax) hmax = h[1]; if (h[2] > hmax) hmax = h[2];  s[a] = h[a] / hmax.
+ *   2. Planes.  Every source triangle (i0, i1, i2) whose three indices are < V takes part, whether or not it survives in S (collapsed and
+ *      duplicate triangles count too).  e1 = p1 - p0, e2 = p2 - p0;  c = (e1y e2z - e1z e2y,  e1z e2x - e1x e2z,  e1x e2y - e1y e2x), each
+ *      product rounded, then the difference;  len = sqrtf((cx cx + cy cy) + cz cz).  If !(len > 0) or len is not finite the triangle contributes
+ *      nothing.  n = c / len (three divisions);  m[a] = n[a] * s[a]: the plane's normal in cluster-cell coordinates, scaled so that |m| <= 1
+ *      and residuals stay proportional to world distances.
+ *   3. Sums.  For each corner k = 0, 1, 2 of a contributing triangle, with v = i_k and o = o(v):  f[a] = (float)q_v[a] / 1048576.0f (exact);
+ *      d[a] = f[a] - g_o[a];  md = (m0 d0 + m1 d1) + m2 d2.  Cluster o gains  A00 += Q24(m0 m0), A01 += Q24(m0 m1), A02 += Q24(m0 m2),
+ *      A11 += Q24(m1 m1), A12 += Q24(m1 m2), A22 += Q24(m2 m2),  B[a] += Q24(m[a] md)  and  planes += 1.  The sums are signed 64-bit integers:
+ *      every term is below 2^26 and there are at most 3 * 2^32 of them, so nothing overflows.  A triangle with several corners in one cluster adds
+ *      once per corner.
+ *   4. Solve, per output vertex with planes > 0.  a_ij = (float)((double)A_ij / 16777216.0), b likewise.  Then exactly step 5 of "sharp vertices"
+ *      from its Jacobi on: V = I, the 5 sweeps over the pairs (0,1), (0,2), (1,2); lmax; pair i is kept iff lambda_i > 0 and lambda_i > threshold *
+ *      lmax; the truncated solve, which gives the offset w (o there).  x[a] = g[a] + w[a]; if a component of x is not finite, x = g.  Clamp:
+ *      if (x[a] < 0) x[a] = 0; if (x[a] > 1) x[a] = 1 -- a vertex never leaves its cluster cell.  position[a] = lo[a] + ((float)i[a] + x[a]) *
+ *      h[a] (simplify's own sum, product, sum).  With planes == 0 the position is S's, bit for bit.
+ *   5. An empty source gives a valid empty mesh.  rm_mesh_timings of the result is {0, the milliseconds of all kernels of the call between
+ *      events on the stream, 0}.
+ * Every output is a function of integer sums: the same bytes on every run.  Triangles may fold where a minimiser is clamped, and manifoldness is
+ * no more preserved than by rm_mesh_simplify.  Quadrics are not weighted by area; there are no boundary or feature constraints.
+ * Procedure (rm_mesh_kernels.inc "quadric placement", in the strict unit).  rm_mesh_simplify's kernels run as they are.  Behind its place kernel,
+ * one thread per source triangle computes the plane once and adds to a second scratch of ten 64-bit words per output vertex (integer atomic adds:
+ * they commute); the corners of a triangle that share a cluster are merged in registers first, which leaves one to three slots, and for each slot
+ * runs of neighbouring lanes with one cluster are summed in the wave and add once.  Then one thread per output vertex converts, solves, clamps
+ * and overwrites the position.  No thread waits for another and no loop is unbounded.  The scratch is freed before the call returns.
+ * RM_ERR_INVALID, in this order (the text through rm_last_error(NULL) when no context is known): everything rm_mesh_simplify refuses before the
+ * handles are looked at, in its order and with its texts (a NULL or invalid `clusters`, keep_duplicates outside 0 / 1, a non-zero simplify
+ * reserved); a threshold that is not finite or outside [0, 1); a non-zero quadric reserved; then a NULL mesh or out ("NULL argument").
+ * RM_ERR_DEVICE: as rm_mesh_simplify (T >= 2^32, a failed allocation with nothing leaked). */
+typedef struct RmMeshQuadric { float threshold; int32_t reserved[3]; } RmMeshQuadric; /* 16 bytes */
+RM_API void rm_mesh_quadric_default(RmMeshQuadric* q);
+RM_API int rm_mesh_simplify_quadric(rm_mesh* mesh, const RmGrid* clusters, const RmMeshSimplify* params, const RmMeshQuadric* quadric, rm_mesh** out);
 
 #ifdef __cplusplus
 }

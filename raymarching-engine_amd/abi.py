@@ -298,3 +298,17 @@ class RmMeshSimplify(C.Structure):
 MESH_SIMPLIFY_DEFAULTS = dict(keep_duplicates=0)  # rm_mesh_simplify_default
 
 assert C.sizeof(RmMeshSimplify) == 16
+
+
+class RmMeshQuadric(C.Structure):
+    """Parameters of rm_mesh_simplify_quadric (ABI 9): eigenvalues at or below threshold * the largest are dropped from a cluster's solve
+    (include/hip_raymarch.h "quadric placement")."""
+    _fields_ = [
+        ("threshold", C.c_float),
+        ("reserved", C.c_int32 * 3),
+    ]
+
+
+MESH_QUADRIC_DEFAULTS = dict(threshold=0.1)  # rm_mesh_quadric_default
+
+assert C.sizeof(RmMeshQuadric) == 16

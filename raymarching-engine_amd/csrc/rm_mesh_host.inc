@@ -511,12 +511,15 @@ void rm_mesh_simplify_default(RmMeshSimplify* params) {
 
 // what a simplification needs beside its result: owned by rm_mesh_simplify, declared before the mesh it makes
 struct SimplifyScratch {
-  DeviceArray marks, levels, sums, vertex_to, mapped, words, table;
+  DeviceArray marks, levels, sums, vertex_to, mapped, words, table, quadrics;
 };
 
 // `mesh` (with vertices) clustered on G into `made`: number the occupied clusters, read V'; sum, place, map and deduplicate, read T' and the
-// error word; gather.  On the context's stream; returns with it idle.  made->ms[1] is the time of its three spans.
-static int mesh_cluster(const Refuse& refuse, const rm_mesh* mesh, const GridDims& G, bool keep_duplicates, SimplifyScratch& tmp, rm_mesh* made) {
+// error word; gather.  On the context's stream; returns with it idle.  made->ms[1] is the time of its three spans.  quadric (NULL: the cluster
+// means stay): behind the place kernel, inside its span, the source triangles' plane quadrics are summed per cluster and the positions of the
+// output vertices that have planes are moved to the minimisers (rm_mesh_simplify_quadric).
+static int mesh_cluster(const Refuse& refuse, const rm_mesh* mesh, const GridDims& G, bool keep_duplicates, const RmMeshQuadric* quadric,
+                        SimplifyScratch& tmp, rm_mesh* made) {
   rm_ctx* ctx = mesh->ctx;
   MeshSpans& spans = ctx->mesh_spans;
   const unsigned long long V = mesh->vertices, T = mesh->triangles;
@@ -525,7 +528,7 @@ static int mesh_cluster(const Refuse& refuse, const rm_mesh* mesh, const GridDim
   RM_HIP(ctx, tmp.marks.reserve(sizeof(unsigned long long) * (size_t)cells));
   RM_HIP(ctx, tmp.levels.reserve(sizeof(unsigned long long) * (cell_levels + triangle_levels + 3)));  // ... V', T' and the error word behind the levels
   unsigned long long* d_totals = tmp.levels.u64() + cell_levels + triangle_levels;
-  rm::MeshSimplify S{};
+  rm::MeshQuadric S{};  // (the simplification's own fields, and the placement's behind them)
   S.grid = G;
   S.vertices = (long long)V;
   S.triangles = (long long)T;
@@ -570,10 +573,26 @@ static int mesh_cluster(const Refuse& refuse, const rm_mesh* mesh, const GridDim
       S.table = tmp.table.u32();
     }
   }
+  const bool planes = quadric != nullptr && T > 0 && made->vertices > 0;
+  const size_t quadrics_bytes = sizeof(unsigned long long) * 10u * (size_t)made->vertices;
+  if (planes) {
+    RM_HIP(ctx, tmp.quadrics.reserve(quadrics_bytes));
+    S.quadrics = tmp.quadrics.u64();
+    float hmax = G.h[0];
+    if (G.h[1] > hmax) hmax = G.h[1];
+    if (G.h[2] > hmax) hmax = G.h[2];
+    for (int a = 0; a < 3; a++) S.scale[a] = G.h[a] / hmax;
+    S.threshold = quadric->threshold;
+  }
   RM_HIP(ctx, spans.begin(MeshSpans::CLUSTER_MERGE, ctx->stream));
   RM_HIP(ctx, hipMemsetAsync(tmp.sums.p, 0, sums_bytes, ctx->stream));
   RM_HIP(ctx, rm::launch_mesh_simplify_sums(S, ctx->stream));
   RM_HIP(ctx, rm::launch_mesh_simplify_place(S, ctx->stream));
+  if (planes) {
+    RM_HIP(ctx, hipMemsetAsync(tmp.quadrics.p, 0, quadrics_bytes, ctx->stream));
+    RM_HIP(ctx, rm::launch_mesh_quadric_sums(S, ctx->stream));
+    RM_HIP(ctx, rm::launch_mesh_quadric_place(S, ctx->stream));
+  }
   if (T > 0) {
     RM_HIP(ctx, rm::launch_mesh_simplify_map(S, ctx->stream));
     if (!keep_duplicates) {
@@ -601,16 +620,26 @@ static int mesh_cluster(const Refuse& refuse, const rm_mesh* mesh, const GridDim
   return RM_OK;
 }
 
-int rm_mesh_simplify(rm_mesh* mesh, const RmGrid* clusters, const RmMeshSimplify* params, rm_mesh** out) {
+// rm_mesh_simplify (quadric NULL and unasked) and rm_mesh_simplify_quadric (asked; a NULL block is the defaults): one path, the checks in the
+// header's order
+static int mesh_simplify_entry(const char* who, rm_mesh* mesh, const RmGrid* clusters, const RmMeshSimplify* params, bool asked,
+                               const RmMeshQuadric* quadric, rm_mesh** out) {
   rm_ctx* ctx = mesh ? mesh->ctx : nullptr;
-  const Refuse refuse{ctx, "rm_mesh_simplify"};
+  const Refuse refuse{ctx, who};
   GridDims G{};
   RmMeshSimplify p;
   rm_mesh_simplify_default(&p);
   if (params) p = *params;
+  RmMeshQuadric q;
+  rm_mesh_quadric_default(&q);
+  if (quadric) q = *quadric;
   if (int rc = grid_check(refuse, clusters, &G)) return rc;
   if (p.keep_duplicates != 0 && p.keep_duplicates != 1) return refuse("keep_duplicates must be 0 or 1");
   if (p.reserved[0] != 0 || p.reserved[1] != 0 || p.reserved[2] != 0) return refuse("simplify reserved must be 0");
+  if (asked) {
+    if (!(std::isfinite(q.threshold) && q.threshold >= 0.0f && q.threshold < 1.0f)) return refuse("quadric threshold must be finite and in [0, 1)");
+    if (q.reserved[0] != 0 || q.reserved[1] != 0 || q.reserved[2] != 0) return refuse("quadric reserved must be 0");
+  }
   if (!mesh || !out) return refuse("NULL argument");
   *out = nullptr;
   if (mesh->triangles >= (1ull << 32)) return refuse("the mesh has more triangles than a uint32 index holds (T >= 2^32)", RM_ERR_DEVICE);
@@ -620,7 +649,22 @@ int rm_mesh_simplify(rm_mesh* mesh, const RmGrid* clusters, const RmMeshSimplify
   if (!made) return refuse("out of host memory", RM_ERR_DEVICE);
   for (int a = 0; a < 5; a++) made->has[a] = mesh->has[a];
   if (mesh->vertices > 0)
-    if (int rc = mesh_cluster(refuse, mesh, G, p.keep_duplicates != 0, tmp, made.get())) return rc;
+    if (int rc = mesh_cluster(refuse, mesh, G, p.keep_duplicates != 0, asked ? &q : nullptr, tmp, made.get())) return rc;
   *out = made.release();
   return RM_OK;
+}
+
+int rm_mesh_simplify(rm_mesh* mesh, const RmGrid* clusters, const RmMeshSimplify* params, rm_mesh** out) {
+  return mesh_simplify_entry("rm_mesh_simplify", mesh, clusters, params, false, nullptr, out);
+}
+
+// ---- quadric placement (include/hip_raymarch.h "quadric placement") ---------------------------------------------------------------------------
+
+void rm_mesh_quadric_default(RmMeshQuadric* q) {
+  if (!q) return;
+  *q = RmMeshQuadric{0.1f, {0, 0, 0}};
+}
+
+int rm_mesh_simplify_quadric(rm_mesh* mesh, const RmGrid* clusters, const RmMeshSimplify* params, const RmMeshQuadric* quadric, rm_mesh** out) {
+  return mesh_simplify_entry("rm_mesh_simplify_quadric", mesh, clusters, params, true, quadric, out);
 }

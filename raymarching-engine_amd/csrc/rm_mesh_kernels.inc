@@ -1,7 +1,8 @@
 // Mesh extraction (include/hip_raymarch.h "mesh extraction"): a scene's distance on a grid of corners, in this unit's arithmetic,
 // and -- in the strict unit only, they have no arithmetic of a policy's own -- the surface-nets mesher over such a grid, the two
 // kernels that move its vertices to their cells' QEF minimisers (rm_mesh_extract_sharp), and the integer kernels that label a mesh's
-// connected components and compact the kept ones (rm_mesh_components, rm_mesh_filter), and the vertex clustering of rm_mesh_simplify.  Included by
+// connected components and compact the kept ones (rm_mesh_components, rm_mesh_filter), and the vertex clustering of rm_mesh_simplify with the quadric placement of
+// rm_mesh_simplify_quadric.  Included by
 // rm_strict.hip / rm_fast.hip / rm_glstack.hip behind rm_kernels.inc.
 namespace rm {
 
@@ -691,6 +692,170 @@ __global__ __launch_bounds__(256) void rm_mesh_simplify_take_kernel(const MeshSi
   S.out_triangles[3 * to + 2] = S.mapped[3 * t + 2];
 }
 
+// ---- quadric placement (include/hip_raymarch.h "quadric placement") ---------------------------------------------------------------------------
+// Behind the sums and the place kernel: vertex_to and the rows of the means are final.  Again everything a run can differ in is an integer: the
+// plane quadrics are sums of Q24 integers per cluster, ten 64-bit words a row (a00 a01 a02 a11 a12 a22 b0 b1 b2 planes).
+
+__device__ inline long long mesh_q24(float x) { return (long long)rintf(x * 16777216.0f); }
+
+// One corner slot of every lane of a wave into the rows: `to` is the slot's output vertex (0xFFFFFFFF: an empty slot), `planes` the corners it
+// stands for, r.. the Q24 terms times that count.  Source triangles stand in cell order, so neighbouring lanes often meet in a cluster: every run
+// of consecutive lanes with one `to` is summed in the wave first (the segmented shuffle reduction of the sums kernel; integer sums, so the totals
+// are what one add per corner gives) and the run's first lane makes the ten adds.  Of a run of at most 64 lanes the six sums of A and the count
+// fit 32 bits (|m_i m_j| <= 1: 192 terms of at most 2^24, the mixed ones signed and at most half that); the sums of b do not.  Every lane of
+// the wave calls this and stays to the end of the shuffles.
+__device__ inline void mesh_quadric_run_add(unsigned long long* quadrics, int lane, unsigned int to, unsigned int planes, unsigned int r00, int r01, int r02,
+                                            unsigned int r11, int r12, unsigned int r22, long long rb0, long long rb1, long long rb2) {
+  const unsigned int before = (unsigned int)__shfl_up((int)to, 1);
+  const bool head = lane == 0 || before != to;
+  const unsigned long long heads = __ballot(head), above = lane == 63 ? 0ull : heads >> (lane + 1);
+  const int last = above != 0ull ? lane + __ffsll((long long)above) - 1 : 63;  // the last lane of this lane's run
+#pragma unroll
+  for (int off = 1; off < 64; off <<= 1) {
+    const bool mine = lane + off <= last;
+    const unsigned int dn = (unsigned int)__shfl_down((int)planes, off);
+    const unsigned int d00 = (unsigned int)__shfl_down((int)r00, off), d11 = (unsigned int)__shfl_down((int)r11, off);
+    const unsigned int d22 = (unsigned int)__shfl_down((int)r22, off);
+    const int d01 = __shfl_down(r01, off), d02 = __shfl_down(r02, off), d12 = __shfl_down(r12, off);
+    const long long db0 = __shfl_down(rb0, off), db1 = __shfl_down(rb1, off), db2 = __shfl_down(rb2, off);
+    if (mine) {
+      planes += dn; r00 += d00; r11 += d11; r22 += d22;
+      r01 += d01; r02 += d02; r12 += d12;
+      rb0 += db0; rb1 += db1; rb2 += db2;
+    }
+  }
+  if (!head || to == 0xFFFFFFFFu) return;
+  unsigned long long* row = quadrics + (size_t)to * 10u;
+  atomicAdd(row, (unsigned long long)r00);
+  atomicAdd(row + 1, (unsigned long long)(long long)r01);  // (two's complement: the unsigned adds sum signed values)
+  atomicAdd(row + 2, (unsigned long long)(long long)r02);
+  atomicAdd(row + 3, (unsigned long long)r11);
+  atomicAdd(row + 4, (unsigned long long)(long long)r12);
+  atomicAdd(row + 5, (unsigned long long)r22);
+  atomicAdd(row + 6, (unsigned long long)rb0);
+  atomicAdd(row + 7, (unsigned long long)rb1);
+  atomicAdd(row + 8, (unsigned long long)rb2);
+  atomicAdd(row + 9, (unsigned long long)planes);
+}
+
+// One thread per source triangle: its plane once, then one term per corner for the corner's cluster.  The corners that share a cluster are merged
+// in registers first, which leaves one to three slots (cluster, corners, sums of b); then the wave merges each slot with its neighbours'.  A lane
+// beyond the last triangle, or with a triangle that contributes nothing, has three empty slots.
+// (rm_mesh_take3_kernel's caution holds here too: these kernels' mangled names, their parameter type included, decide whether llvm-objdump -D
+// reads this code object whole)
+__global__ __launch_bounds__(256) void rm_mesh_quadric_sums_kernel(const MeshQuadric S) {
+  const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
+  const int lane = (int)(threadIdx.x & 63u);
+  bool contributes = false;
+  unsigned int o[3] = {0u, 0u, 0u};
+  unsigned int a00 = 0u, a11 = 0u, a22 = 0u;
+  int a01 = 0, a02 = 0, a12 = 0;
+  long long b[3][3] = {{0ll, 0ll, 0ll}, {0ll, 0ll, 0ll}, {0ll, 0ll, 0ll}};
+  if (t < S.triangles) {
+    const unsigned int i[3] = {S.source_triangles[3 * t], S.source_triangles[3 * t + 1], S.source_triangles[3 * t + 2]};
+    if (i[0] < S.vertices && i[1] < S.vertices && i[2] < S.vertices) {
+      const float* p0 = S.positions + 3 * (size_t)i[0];
+      const float* p1 = S.positions + 3 * (size_t)i[1];
+      const float* p2 = S.positions + 3 * (size_t)i[2];
+      const float e1x = p1[0] - p0[0], e1y = p1[1] - p0[1], e1z = p1[2] - p0[2];
+      const float e2x = p2[0] - p0[0], e2y = p2[1] - p0[1], e2z = p2[2] - p0[2];
+      const float cx = e1y * e2z - e1z * e2y, cy = e1z * e2x - e1x * e2z, cz = e1x * e2y - e1y * e2x;
+      const float len = sqrtf((cx * cx + cy * cy) + cz * cz);
+      if (len > 0.0f && isfinite(len)) {
+        contributes = true;
+        const float m0 = (cx / len) * S.scale[0], m1 = (cy / len) * S.scale[1], m2 = (cz / len) * S.scale[2];
+        a00 = (unsigned int)mesh_q24(m0 * m0); a11 = (unsigned int)mesh_q24(m1 * m1); a22 = (unsigned int)mesh_q24(m2 * m2);
+        a01 = (int)mesh_q24(m0 * m1); a02 = (int)mesh_q24(m0 * m2); a12 = (int)mesh_q24(m1 * m2);
+#pragma unroll
+        for (int k = 0; k < 3; k++) {
+          const MeshCluster c = mesh_cluster(S.grid, S.positions + 3 * (size_t)i[k]);
+          o[k] = S.vertex_to[i[k]];
+          const unsigned long long* row = S.sums + (size_t)o[k] * (size_t)S.row;
+          const double count = (double)row[0] * 1048576.0;
+          const float d0 = (float)c.q[0] / 1048576.0f - mesh_q20_mean(row[1], count);
+          const float d1 = (float)c.q[1] / 1048576.0f - mesh_q20_mean(row[2], count);
+          const float d2 = (float)c.q[2] / 1048576.0f - mesh_q20_mean(row[3], count);
+          const float md = (m0 * d0 + m1 * d1) + m2 * d2;
+          b[k][0] = mesh_q24(m0 * md); b[k][1] = mesh_q24(m1 * md); b[k][2] = mesh_q24(m2 * md);
+        }
+      }
+    }
+  }
+  // corners of one cluster: corner 1 into 0, corner 2 into 0 or 1; n[k] = the corners that row k now stands for
+  unsigned int n[3] = {contributes ? 1u : 0u, contributes ? 1u : 0u, contributes ? 1u : 0u};
+  if (contributes && o[1] == o[0]) {
+    b[0][0] += b[1][0]; b[0][1] += b[1][1]; b[0][2] += b[1][2];
+    n[0] += 1u; n[1] = 0u;
+  }
+  if (contributes && o[2] == o[0]) {
+    b[0][0] += b[2][0]; b[0][1] += b[2][1]; b[0][2] += b[2][2];
+    n[0] += 1u; n[2] = 0u;
+  } else if (contributes && n[1] != 0u && o[2] == o[1]) {
+    b[1][0] += b[2][0]; b[1][1] += b[2][1]; b[1][2] += b[2][2];
+    n[1] += 1u; n[2] = 0u;
+  }
+#pragma unroll
+  for (int k = 0; k < 3; k++) {
+    const unsigned int times = n[k];
+    mesh_quadric_run_add(S.quadrics, lane, times != 0u ? o[k] : 0xFFFFFFFFu, times, times * a00, (int)times * a01, (int)times * a02, times * a11, (int)times * a12,
+                         times * a22, b[k][0], b[k][1], b[k][2]);
+  }
+}
+
+__device__ inline float mesh_q24_value(unsigned long long sum) { return (float)((double)(long long)sum / 16777216.0); }
+
+// One thread per output vertex with planes: the truncated solve of "sharp vertices" step 5 on the cluster's sums, about the mean fractions g that
+// the place kernel used, clamped to the cluster cell; the position is overwritten.  A vertex without planes keeps the place kernel's.  The 3 x 3
+// state is named scalars, as in rm_mesh_qef_kernel.
+__global__ __launch_bounds__(256) void rm_mesh_quadric_place_kernel(const MeshQuadric S) {
+  const long long o = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (o >= S.out_vertices) return;
+  const unsigned long long* sums = S.quadrics + (size_t)o * 10u;
+  if (sums[9] == 0ull) return;
+  float a00 = mesh_q24_value(sums[0]), a01 = mesh_q24_value(sums[1]), a02 = mesh_q24_value(sums[2]);
+  float a11 = mesh_q24_value(sums[3]), a12 = mesh_q24_value(sums[4]), a22 = mesh_q24_value(sums[5]);
+  const float b0 = mesh_q24_value(sums[6]), b1 = mesh_q24_value(sums[7]), b2 = mesh_q24_value(sums[8]);
+  float v00 = 1.0f, v01 = 0.0f, v02 = 0.0f, v10 = 0.0f, v11 = 1.0f, v12 = 0.0f, v20 = 0.0f, v21 = 0.0f, v22 = 1.0f;
+#pragma unroll
+  for (int sweep = 0; sweep < 5; sweep++) {
+    mesh_jacobi(a00, a11, a01, a02, a12, v00, v01, v10, v11, v20, v21);  // (0, 1), r = 2
+    mesh_jacobi(a00, a22, a02, a01, a12, v00, v02, v10, v12, v20, v22);  // (0, 2), r = 1
+    mesh_jacobi(a11, a22, a12, a01, a02, v01, v02, v11, v12, v21, v22);  // (1, 2), r = 0
+  }
+  float lmax = a00;
+  if (a11 > lmax) lmax = a11;
+  if (a22 > lmax) lmax = a22;
+  const float bar = S.threshold * lmax;
+  float w0 = 0.0f, w1 = 0.0f, w2 = 0.0f;
+  if (a00 > 0.0f && a00 > bar) {
+    const float w = (v00 * b0 + v10 * b1 + v20 * b2) / a00;
+    w0 += v00 * w; w1 += v10 * w; w2 += v20 * w;
+  }
+  if (a11 > 0.0f && a11 > bar) {
+    const float w = (v01 * b0 + v11 * b1 + v21 * b2) / a11;
+    w0 += v01 * w; w1 += v11 * w; w2 += v21 * w;
+  }
+  if (a22 > 0.0f && a22 > bar) {
+    const float w = (v02 * b0 + v12 * b1 + v22 * b2) / a22;
+    w0 += v02 * w; w1 += v12 * w; w2 += v22 * w;
+  }
+  const GridDims& g = S.grid;
+  const unsigned long long* row = S.sums + (size_t)o * (size_t)S.row;
+  const double count = (double)row[0] * 1048576.0;
+  const float g0 = mesh_q20_mean(row[1], count), g1 = mesh_q20_mean(row[2], count), g2 = mesh_q20_mean(row[3], count);
+  float x[3] = {g0 + w0, g1 + w1, g2 + w2};
+  if (!(isfinite(x[0]) && isfinite(x[1]) && isfinite(x[2]))) { x[0] = g0; x[1] = g1; x[2] = g2; }
+  const int nx = g.nc[0] - 1, ny = g.nc[1] - 1, key = (int)S.out_cells[o];
+  const int idx[3] = {key % nx, (key / nx) % ny, key / (nx * ny)};
+#pragma unroll
+  for (int a = 0; a < 3; a++) {
+    if (x[a] < 0.0f) x[a] = 0.0f;
+    if (x[a] > 1.0f) x[a] = 1.0f;
+    const float s = (float)idx[a] + x[a], step = s * g.h[a];
+    S.out_positions[3 * o + a] = g.lo[a] + step;
+  }
+}
+
 #ifndef RM_ONLY_KERNELS
 static inline long long mesh_cells(const GridDims& g) { return (long long)(g.nc[0] - 1) * (g.nc[1] - 1) * (g.nc[2] - 1); }
 
@@ -789,6 +954,8 @@ hipError_t launch_mesh_simplify_map(const MeshSimplify& S, hipStream_t stream) {
 hipError_t launch_mesh_simplify_insert(const MeshSimplify& S, hipStream_t stream) { RM_MESH_PARTS_LAUNCH(rm_mesh_simplify_insert_kernel, S.triangles, S); }
 hipError_t launch_mesh_simplify_keep(const MeshSimplify& S, hipStream_t stream) { RM_MESH_PARTS_LAUNCH(rm_mesh_simplify_keep_kernel, S.triangles, S); }
 hipError_t launch_mesh_simplify_gather(const MeshSimplify& S, hipStream_t stream) { RM_MESH_PARTS_LAUNCH(rm_mesh_simplify_take_kernel, S.triangles, S); }
+hipError_t launch_mesh_quadric_sums(const MeshQuadric& S, hipStream_t stream) { RM_MESH_PARTS_LAUNCH(rm_mesh_quadric_sums_kernel, S.triangles, S); }
+hipError_t launch_mesh_quadric_place(const MeshQuadric& S, hipStream_t stream) { RM_MESH_PARTS_LAUNCH(rm_mesh_quadric_place_kernel, S.out_vertices, S); }
 #undef RM_MESH_PARTS_LAUNCH
 
 hipError_t launch_mesh_emit(const MeshParams& P, hipStream_t stream) {

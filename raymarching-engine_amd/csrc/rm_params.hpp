@@ -518,6 +518,14 @@ struct MeshSimplify {
   unsigned int* error;
   unsigned int* out_triangles;
 };
+// Quadric placement (rm_mesh_simplify_quadric) on top of a simplification: quadric_sums (behind simplify_place) adds every source triangle's
+// plane to the rows of its corners' clusters, ten 64-bit words each (a00 a01 a02 a11 a12 a22 b0 b1 b2 in Q24, planes); quadric_place
+// overwrites the positions of the output vertices that have planes.
+struct MeshQuadric : MeshSimplify {
+  unsigned long long* quadrics;  // out_vertices x 10
+  float scale[3];                // h[a] / max h
+  float threshold;
+};
 hipError_t launch_mesh_simplify_mark(const MeshSimplify& S, hipStream_t stream);
 hipError_t launch_mesh_simplify_sums(const MeshSimplify& S, hipStream_t stream);
 hipError_t launch_mesh_simplify_place(const MeshSimplify& S, hipStream_t stream);
@@ -525,6 +533,8 @@ hipError_t launch_mesh_simplify_map(const MeshSimplify& S, hipStream_t stream);
 hipError_t launch_mesh_simplify_insert(const MeshSimplify& S, hipStream_t stream);
 hipError_t launch_mesh_simplify_keep(const MeshSimplify& S, hipStream_t stream);
 hipError_t launch_mesh_simplify_gather(const MeshSimplify& S, hipStream_t stream);
+hipError_t launch_mesh_quadric_sums(const MeshQuadric& S, hipStream_t stream);
+hipError_t launch_mesh_quadric_place(const MeshQuadric& S, hipStream_t stream);
 hipError_t launch_camera_rng(const RmUniforms& u, int W, int H, int what, int count, float* out, hipStream_t stream);
 hipError_t launch_math_probe(int fn, const float* a, const float* b, int n, float* out, hipStream_t stream);
 }  // namespace rm

@@ -121,8 +121,12 @@ export class RenderJobContext {
   extractMesh(scene: Scene, grid: MeshGrid, params: MeshParams | null | undefined, sharp: MeshSharp | true | null | undefined, keep: MeshKeep | true | null | undefined, components?: boolean): Mesh;
   /** with `simplify`: the vertices of every cell of a second grid of clusters merged into one on the GPU (rm_mesh_simplify) before `keep` and `components` are applied, so one filter also removes the vertices the clustering left without triangles; the result's cells index the cluster grid */
   extractMesh(scene: Scene, grid: MeshGrid, params: MeshParams | null | undefined, sharp: MeshSharp | true | null | undefined, keep: MeshKeep | true | null | undefined, components: boolean | undefined, simplify: MeshSimplify | null): Mesh;
+  /** with `quadric` (true = the defaults; only with `simplify`): every cluster's vertex at the minimiser of the plane quadrics of the source triangles that touch the cluster instead of at the mean of its vertices (rm_mesh_simplify_quadric), which keeps the edges and corners inside a cluster; only the positions differ */
+  extractMesh(scene: Scene, grid: MeshGrid, params: MeshParams | null | undefined, sharp: MeshSharp | true | null | undefined, keep: MeshKeep | true | null | undefined, components: boolean | undefined, simplify: MeshSimplify, quadric: MeshQuadric | true | null): Mesh;
   /** the mesher alone on the caller's field (rm_mesh_from_values); keep, components and simplify as in extractMesh */
   meshFromValues(grid: MeshGrid, values: Float32Array, iso?: number, keep?: MeshKeep | true | null, components?: boolean, simplify?: MeshSimplify | null): Mesh;
+  /** quadric as in extractMesh */
+  meshFromValues(grid: MeshGrid, values: Float32Array, iso: number | undefined, keep: MeshKeep | true | null | undefined, components: boolean | undefined, simplify: MeshSimplify, quadric: MeshQuadric | true | null): Mesh;
   close(): void;
 }
 /** A frame sharded over several GPUs by this one process: a native context per device, each holding one part of the frame's
@@ -170,5 +174,9 @@ export function meshKeep(keep?: MeshKeep | null): { minTriangles: number; larges
 export interface MeshSimplify { grid: MeshGrid; keepDuplicates?: boolean | 0 | 1 }
 export const MESH_SIMPLIFY_DEFAULTS: { keepDuplicates: 0 | 1 };
 export function meshSimplify(simplify: MeshSimplify): { grid: MeshGrid; keepDuplicates: 0 | 1 };
+/** the quadric block of extractMesh / meshFromValues (RmMeshQuadric): eigenvalues at or below threshold * the largest are dropped from a cluster's solve, in [0, 1) */
+export interface MeshQuadric { threshold?: number }
+export const MESH_QUADRIC_DEFAULTS: { threshold: number };
+export function meshQuadric(quadric?: MeshQuadric | null): { threshold: number };
 /** binary little-endian PLY (normals and uchar colours when present): the bytes the Python host's write_ply writes */
 export function encodePly(mesh: { positions: Float32Array; triangles: Uint32Array; normals?: Float32Array | null; colours?: Float32Array | null }): Buffer;

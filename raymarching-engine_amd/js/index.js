@@ -361,10 +361,15 @@ class RenderJobContext {  // RenderJobContext + loadRenderJobContext (LoadRender
   // (Uint32Array(2 C): vertices, triangles per component) of the mesh that is returned (rm_mesh_components)
   // simplify: undefined / null = that mesh; meshSimplify's options ({ grid, keepDuplicates }) = the vertices of every cell of that grid of clusters
   // merged into one on the GPU (rm_mesh_simplify) before keep and components are applied; the result's cells index the cluster grid
-  extractMesh(scene, grid, opts, sharp, keep, components, simplify = null) {
+  // quadric (with simplify only): undefined / null = that call; true or meshQuadric's options = rm_mesh_simplify_quadric, the same mesh with every
+  // cluster's vertex at the minimiser of its plane quadrics
+  extractMesh(scene, grid, opts, sharp, keep, components, simplify = null, quadric = null) {
+    const q = quadric === undefined || quadric === null ? null : meshQuadric(quadric === true ? undefined : quadric);
+    if (q !== null && (simplify === undefined || simplify === null)) throw new TypeError("mesh: quadric places the vertices of a simplification: give simplify as well");
     if (simplify !== undefined && simplify !== null) {
       const s = sharp === undefined || sharp === null ? null : meshSharp(sharp === true ? undefined : sharp);
       const k = keep === undefined || keep === null ? null : meshKeep(keep === true ? undefined : keep);
+      if (q !== null) return addon.extractMesh(this.ctx, this.sceneHandle(scene), grid, meshParams(opts), s, k, !!components, meshSimplify(simplify), q);
       return addon.extractMesh(this.ctx, this.sceneHandle(scene), grid, meshParams(opts), s, k, !!components, meshSimplify(simplify));
     }
     const plain = (keep === undefined || keep === null) && !components;
@@ -375,12 +380,15 @@ class RenderJobContext {  // RenderJobContext + loadRenderJobContext (LoadRender
     return addon.extractMesh(this.ctx, this.sceneHandle(scene), grid, meshParams(opts), s, k, !!components);
   }
   // the mesher alone on the caller's field: values Float32Array of the grid's corners, x fastest (rm_mesh_from_values)
-  // keep, components, simplify: as in extractMesh
-  meshFromValues(grid, values, iso = 0, keep, components, simplify) {
+  // keep, components, simplify, quadric: as in extractMesh
+  meshFromValues(grid, values, iso = 0, keep, components, simplify, quadric) {
     if (!(values instanceof Float32Array)) throw new TypeError("meshFromValues: values must be a Float32Array");
     if (!finite(iso)) throw new RangeError("mesh: iso must be a finite number");
+    const q = quadric === undefined || quadric === null ? null : meshQuadric(quadric === true ? undefined : quadric);
+    if (q !== null && (simplify === undefined || simplify === null)) throw new TypeError("mesh: quadric places the vertices of a simplification: give simplify as well");
     if (simplify !== undefined && simplify !== null) {
       const k = keep === undefined || keep === null ? null : meshKeep(keep === true ? undefined : keep);
+      if (q !== null) return addon.meshFromValues(this.ctx, grid, values, iso, k, !!components, meshSimplify(simplify), q);
       return addon.meshFromValues(this.ctx, grid, values, iso, k, !!components, meshSimplify(simplify));
     }
     if ((keep === undefined || keep === null) && !components) return addon.meshFromValues(this.ctx, grid, values, iso);
@@ -723,6 +731,22 @@ function meshSimplify(opts) {
   return { grid: meshGrid(g.lo, g.hi, g.n), keepDuplicates: flag };
 }
 
+// the quadric block of extractMesh / meshFromValues (include/hip_raymarch.h RmMeshQuadric): undefined / null = the defaults, or an object with
+// threshold (eigenvalues at or below threshold * the largest are dropped from a cluster's solve, in [0, 1))
+const MESH_QUADRIC_DEFAULTS = { threshold: 0.1 };
+function meshQuadric(opts) {
+  const p = { ...MESH_QUADRIC_DEFAULTS };
+  if (opts !== undefined && opts !== null) {
+    if (typeof opts !== "object") throw new TypeError("mesh: expected an object of quadric parameters");
+    for (const [k, v] of Object.entries(opts)) {
+      if (!(k in MESH_QUADRIC_DEFAULTS)) throw new TypeError("mesh: unknown quadric parameter " + k);
+      p[k] = v;
+    }
+  }
+  if (!finite(p.threshold) || !(Math.fround(p.threshold) >= 0 && Math.fround(p.threshold) < 1)) throw new RangeError("mesh: quadric threshold must be finite and in [0, 1)");
+  return p;
+}
+
 // binary little-endian PLY of { positions, triangles, normals?, colours? }: x y z, then nx ny nz, then uchar red green blue
 // (floor(clamp(c, 0, 1) * 255 + 0.5), NaN as 0); faces as a uchar count and uint indices -- the bytes the Python host writes
 function encodePly(mesh) {
@@ -775,4 +799,4 @@ module.exports = { RM, addon, encodePng, Scene, CsgScene, Mandelbulb, singleSphe
                    tileRect, RenderJobContext, ShardedRenderJobContext, doRenderJob, U_OFFSET, DENOISE_DEFAULTS, denoiseParams,
                    DENOISE_VARIANCE_DEFAULTS, denoiseVarianceParams, DESPECKLE_DEFAULTS, despeckleParams, DISPLAY_DEFAULTS, AUTO_EXPOSURE_DEFAULTS,
                    displayParams, statsExposure, statsPercentile, MESH_DEFAULTS, meshGrid, meshParams, MESH_SHARP_DEFAULTS, meshSharp, MESH_KEEP_DEFAULTS, meshKeep,
-                   MESH_SIMPLIFY_DEFAULTS, meshSimplify, encodePly };
+                   MESH_SIMPLIFY_DEFAULTS, meshSimplify, MESH_QUADRIC_DEFAULTS, meshQuadric, encodePly };

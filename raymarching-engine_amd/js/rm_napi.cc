@@ -578,6 +578,32 @@ static napi_value MeshSimplifyBlockOf(napi_env env, napi_callback_info info) {
   return o;
 }
 
+static const Field MESH_QUADRIC_FIELDS[] = {{"threshold", Field::FLOAT, offsetof(RmMeshQuadric, threshold)}};
+// the quadric block of extractMesh / meshFromValues: null / undefined = none (*given = false), an object = rm_mesh_simplify_quadric in place of
+// rm_mesh_simplify, with its fields over the defaults
+static bool get_mesh_quadric(napi_env env, napi_value v, RmMeshQuadric* q, bool* given) {
+  rm_mesh_quadric_default(q);
+  return get_block(env, v, q, MESH_QUADRIC_FIELDS, given);
+}
+
+// meshQuadricBlock(quadric | null) -> ArrayBuffer(RmMeshQuadric): the bytes the mesh calls hand to rm_mesh_simplify_quadric (null: the defaults)
+static napi_value MeshQuadricBlock(napi_env env, napi_callback_info info) {
+  size_t argc = 1;
+  napi_value argv[1];
+  NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+  RmMeshQuadric q;
+  bool given = false;
+  if (argc != 1 || !get_mesh_quadric(env, argv[0], &q, &given)) {
+    napi_throw_type_error(env, nullptr, "meshQuadricBlock(quadric | null)");
+    return nullptr;
+  }
+  napi_value b;
+  void* d = nullptr;
+  NAPI_OK(napi_create_arraybuffer(env, sizeof q, &d, &b));
+  std::memcpy(d, &q, sizeof q);
+  return b;
+}
+
 static napi_value make_array(napi_env env, napi_typedarray_type type, size_t count, void** data) {
   napi_value ab, out;
   if (napi_create_arraybuffer(env, count * 4, data, &ab) != napi_ok || napi_create_typedarray(env, type, count, ab, 0, &out) != napi_ok) return nullptr;
@@ -636,9 +662,9 @@ static napi_value SdfGrid(napi_env env, napi_callback_info info) {
 // meshing, attributes] in ms (rm_mesh_timings) }; normals / colours: whether the call asked for them; the handle is destroyed.  keep: the mesh is
 // first filtered on the device (rm_mesh_filter) and the filtered one is what is copied; components: labels: Uint32Array(V) and componentSizes:
 // Uint32Array(2 C) come with it (rm_mesh_components).  simplify: before either, the mesh is clustered on the device (rm_mesh_simplify), so one
-// filter also removes the vertices the clustering left without triangles
+// filter also removes the vertices the clustering left without triangles; with quadric by rm_mesh_simplify_quadric
 static napi_value mesh_result(napi_env env, rm_ctx* ctx, rm_mesh* mesh, bool normals, bool colours, const RmMeshKeep* keep = nullptr, bool components = false,
-                              const MeshSimplifyBlock* simplify = nullptr) {
+                              const MeshSimplifyBlock* simplify = nullptr, const RmMeshQuadric* quadric = nullptr) {
   struct Guard {  // the handle in hand is destroyed on every way out
     rm_mesh* h;
     ~Guard() { rm_mesh_destroy(h); }
@@ -649,7 +675,9 @@ static napi_value mesh_result(napi_env env, rm_ctx* ctx, rm_mesh* mesh, bool nor
   };
   if (simplify) {
     rm_mesh* simplified = nullptr;
-    if (rm_mesh_simplify(mesh, &simplify->clusters, &simplify->params, &simplified) != RM_OK) return throw_rm(env, ctx, "rm_mesh_simplify");
+    if (quadric) {
+      if (rm_mesh_simplify_quadric(mesh, &simplify->clusters, &simplify->params, quadric, &simplified) != RM_OK) return throw_rm(env, ctx, "rm_mesh_simplify_quadric");
+    } else if (rm_mesh_simplify(mesh, &simplify->clusters, &simplify->params, &simplified) != RM_OK) return throw_rm(env, ctx, "rm_mesh_simplify");
     rm_mesh_destroy(mesh);
     guard.h = mesh = simplified;
   }
@@ -698,13 +726,14 @@ static napi_value mesh_result(napi_env env, rm_ctx* ctx, rm_mesh* mesh, bool nor
   return o;
 }
 
-// extractMesh(ctx, scene, grid, params | null[, sharp | null[, keep | null[, components[, simplify | null]]]]) = rm_mesh_extract, or with a sharp
-// block rm_mesh_extract_sharp; with a simplify block rm_mesh_simplify behind it; with a keep block rm_mesh_filter behind that; then the arrays
+// extractMesh(ctx, scene, grid, params | null[, sharp | null[, keep | null[, components[, simplify | null[, quadric | null]]]]]) = rm_mesh_extract, or
+// with a sharp block rm_mesh_extract_sharp; with a simplify block rm_mesh_simplify behind it (with a quadric block too: rm_mesh_simplify_quadric);
+// with a keep block rm_mesh_filter behind that; then the arrays.  A quadric block without a simplify block is refused.
 static napi_value ExtractMesh(napi_env env, napi_callback_info info) {
-  size_t argc = 8;
-  napi_value argv[8];
+  size_t argc = 9;
+  napi_value argv[9];
   NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
-  const bool counted = argc >= 4 && argc <= 8;
+  const bool counted = argc >= 4 && argc <= 9;
   rm_ctx* ctx = counted ? get_external<rm_ctx>(env, argv[0]) : nullptr;
   rm_scene* scene = counted ? get_external<rm_scene>(env, argv[1]) : nullptr;
   RmGrid g;
@@ -712,38 +741,41 @@ static napi_value ExtractMesh(napi_env env, napi_callback_info info) {
   RmMeshSharp s;
   RmMeshKeep k;
   MeshSimplifyBlock c;
-  bool sharp = false, keep = false, components = false, simplify = false;
+  RmMeshQuadric q;
+  bool sharp = false, keep = false, components = false, simplify = false, quadric = false;
   if (!ctx || !scene || !get_grid(env, argv[2], &g) || !get_mesh_params(env, argv[3], &p) || (argc >= 5 && !get_mesh_sharp(env, argv[4], &s, &sharp)) ||
       (argc >= 6 && !get_mesh_keep(env, argv[5], &k, &keep)) || (argc >= 7 && !get_bool(env, argv[6], &components)) ||
-      (argc == 8 && !get_mesh_simplify(env, argv[7], &c, &simplify))) {
-    napi_throw_type_error(env, nullptr, "extractMesh(ctx, scene, grid, params | null[, sharp | null[, keep | null[, components[, simplify | null]]]])");
+      (argc >= 8 && !get_mesh_simplify(env, argv[7], &c, &simplify)) || (argc == 9 && !get_mesh_quadric(env, argv[8], &q, &quadric)) || (quadric && !simplify)) {
+    napi_throw_type_error(env, nullptr, "extractMesh(ctx, scene, grid, params | null[, sharp | null[, keep | null[, components[, simplify | null[, quadric | null]]]]])");
     return nullptr;
   }
   rm_mesh* mesh = nullptr;
   if (sharp) {
     if (rm_mesh_extract_sharp(ctx, scene, &g, &p, &s, &mesh) != RM_OK) return throw_rm(env, ctx, "rm_mesh_extract_sharp");
   } else if (rm_mesh_extract(ctx, scene, &g, &p, &mesh) != RM_OK) return throw_rm(env, ctx, "rm_mesh_extract");
-  return mesh_result(env, ctx, mesh, p.normals != 0, p.colours != 0, keep ? &k : nullptr, components, simplify ? &c : nullptr);
+  return mesh_result(env, ctx, mesh, p.normals != 0, p.colours != 0, keep ? &k : nullptr, components, simplify ? &c : nullptr, quadric ? &q : nullptr);
 }
 
-// meshFromValues(ctx, grid, values: Float32Array(corners), iso[, keep | null[, components[, simplify | null]]]) = rm_mesh_from_values, with a
-// simplify block rm_mesh_simplify behind it, with a keep block rm_mesh_filter behind that, then the arrays
+// meshFromValues(ctx, grid, values: Float32Array(corners), iso[, keep | null[, components[, simplify | null[, quadric | null]]]]) = rm_mesh_from_values,
+// with a simplify block rm_mesh_simplify (with a quadric block too: rm_mesh_simplify_quadric) behind it, with a keep block rm_mesh_filter behind
+// that, then the arrays
 static napi_value MeshFromValues(napi_env env, napi_callback_info info) {
-  size_t argc = 7;
-  napi_value argv[7];
+  size_t argc = 8;
+  napi_value argv[8];
   NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
-  rm_ctx* ctx = argc >= 4 && argc <= 7 ? get_external<rm_ctx>(env, argv[0]) : nullptr;
+  rm_ctx* ctx = argc >= 4 && argc <= 8 ? get_external<rm_ctx>(env, argv[0]) : nullptr;
   RmMeshKeep k;
   MeshSimplifyBlock c;
-  bool keep = false, components = false, simplify = false;
+  RmMeshQuadric q;
+  bool keep = false, components = false, simplify = false, quadric = false;
   RmGrid g;
   double iso = 0.0;
   void* d = nullptr;
   size_t n = 0;
   if (!ctx || !get_grid(env, argv[1], &g) || !get_buffer(env, argv[2], &d, &n) || napi_get_value_double(env, argv[3], &iso) != napi_ok ||
       (argc >= 5 && !get_mesh_keep(env, argv[4], &k, &keep)) || (argc >= 6 && !get_bool(env, argv[5], &components)) ||
-      (argc == 7 && !get_mesh_simplify(env, argv[6], &c, &simplify))) {
-    napi_throw_type_error(env, nullptr, "meshFromValues(ctx, grid, values: Float32Array, iso[, keep | null[, components[, simplify | null]]])");
+      (argc >= 7 && !get_mesh_simplify(env, argv[6], &c, &simplify)) || (argc == 8 && !get_mesh_quadric(env, argv[7], &q, &quadric)) || (quadric && !simplify)) {
+    napi_throw_type_error(env, nullptr, "meshFromValues(ctx, grid, values: Float32Array, iso[, keep | null[, components[, simplify | null[, quadric | null]]]])");
     return nullptr;
   }
   float probe[1025];
@@ -754,7 +786,7 @@ static napi_value MeshFromValues(napi_env env, napi_callback_info info) {
   }
   rm_mesh* mesh = nullptr;
   if (rm_mesh_from_values(ctx, &g, static_cast<const float*>(d), (float)iso, &mesh) != RM_OK) return throw_rm(env, ctx, "rm_mesh_from_values");
-  return mesh_result(env, ctx, mesh, false, false, keep ? &k : nullptr, components, simplify ? &c : nullptr);
+  return mesh_result(env, ctx, mesh, false, false, keep ? &k : nullptr, components, simplify ? &c : nullptr, quadric ? &q : nullptr);
 }
 
 // fbCreateStriped(ctx, width, height, stripeRows, parts, part[, gbuffer]): the stripes k with k % parts == part of a width x height image,
@@ -953,7 +985,7 @@ static napi_value Sizes(napi_env env, napi_callback_info) {
       {"RmMaterial", (uint32_t)sizeof(RmMaterial)}, {"RmRect", (uint32_t)sizeof(RmRect)}, {"RmSurface", (uint32_t)sizeof(RmSurface)}, {"RmDenoise", (uint32_t)sizeof(RmDenoise)},
       {"RmDenoiseVariance", (uint32_t)sizeof(RmDenoiseVariance)}, {"RmDespeckle", (uint32_t)sizeof(RmDespeckle)}, {"RmFilters", (uint32_t)sizeof(RmFilters)}, {"RmFrameStats", (uint32_t)sizeof(RmFrameStats)},
       {"RmAutoExposure", (uint32_t)sizeof(RmAutoExposure)}, {"RmDisplay", (uint32_t)sizeof(RmDisplay)}, {"RmGrid", (uint32_t)sizeof(RmGrid)},
-      {"RmMeshParams", (uint32_t)sizeof(RmMeshParams)}, {"RmMeshSharp", (uint32_t)sizeof(RmMeshSharp)}, {"RmMeshKeep", (uint32_t)sizeof(RmMeshKeep)}, {"RmMeshSimplify", (uint32_t)sizeof(RmMeshSimplify)}, {"abi", (uint32_t)rm_abi_version()}};
+      {"RmMeshParams", (uint32_t)sizeof(RmMeshParams)}, {"RmMeshSharp", (uint32_t)sizeof(RmMeshSharp)}, {"RmMeshKeep", (uint32_t)sizeof(RmMeshKeep)}, {"RmMeshSimplify", (uint32_t)sizeof(RmMeshSimplify)}, {"RmMeshQuadric", (uint32_t)sizeof(RmMeshQuadric)}, {"abi", (uint32_t)rm_abi_version()}};
   for (const auto& it : items) {
     NAPI_OK(napi_create_uint32(env, it.v, &v));
     NAPI_OK(napi_set_named_property(env, o, it.k, v));
@@ -966,7 +998,7 @@ static napi_value Init(napi_env env, napi_value exports) {
       {"ctxCreate", CtxCreate}, {"ctxDestroy", CtxDestroy}, {"sync", Sync}, {"sceneCreate", SceneCreate}, {"sceneDestroy", SceneDestroy},
       {"fbCreate", FbCreate}, {"fbClear", FbClear}, {"fbDestroy", FbDestroy}, {"fbDownload", FbDownload}, {"present", Present}, {"denoise", Denoise}, {"presentDenoised", PresentDenoised}, {"denoiseVariance", DenoiseVariance}, {"presentDenoisedVariance", PresentDenoisedVariance}, {"filter", Filter}, {"presentFiltered", PresentFiltered}, {"presentDisplay", PresentDisplay}, {"presentLinear", PresentLinear}, {"frameStats", FrameStats}, {"statsExposure", StatsExposure}, {"statsPercentile", StatsPercentile}, {"renderSample", RenderSample}, {"renderSamples", RenderSamples},
       {"fbCreateStriped", FbCreateStriped}, {"fbRows", FbRows}, {"setSamplesInFlight", SetSamplesInFlight}, {"presentSharded", PresentSharded}, {"presentShardedStart", PresentShardedStart}, {"presentShardedFinish", PresentShardedFinish},
-      {"meshBlocks", MeshBlocks}, {"meshSharpBlock", MeshSharpBlock}, {"meshKeepBlock", MeshKeepBlock}, {"meshSimplifyBlock", MeshSimplifyBlockOf}, {"sdfGrid", SdfGrid}, {"extractMesh", ExtractMesh}, {"meshFromValues", MeshFromValues}, {"sizes", Sizes}};
+      {"meshBlocks", MeshBlocks}, {"meshSharpBlock", MeshSharpBlock}, {"meshKeepBlock", MeshKeepBlock}, {"meshSimplifyBlock", MeshSimplifyBlockOf}, {"meshQuadricBlock", MeshQuadricBlock}, {"sdfGrid", SdfGrid}, {"extractMesh", ExtractMesh}, {"meshFromValues", MeshFromValues}, {"sizes", Sizes}};
   for (const auto& f : fns) {
     napi_value fn;
     if (napi_create_function(env, f.name, NAPI_AUTO_LENGTH, f.fn, nullptr, &fn) != napi_ok) return nullptr;

@@ -123,6 +123,19 @@ def mesh_simplify(grid, keep_duplicates=False) -> tuple:
     return grid.to_c(), abi.RmMeshSimplify(keep_duplicates=int(keep_duplicates))
 
 
+def mesh_quadric(threshold=abi.MESH_QUADRIC_DEFAULTS["threshold"]) -> abi.RmMeshQuadric:
+    """The abi.RmMeshQuadric of Context.extract_mesh(..., simplify=..., quadric=...) / mesh_from_values(..., simplify=..., quadric=...): the
+    cluster vertices are placed at the minimisers of their clusters' plane quadrics (rm_mesh_simplify_quadric); eigenvalues at or below
+    threshold * the largest are dropped from the solve, in [0, 1).  Checked as the library checks it: ValueError otherwise."""
+    if isinstance(threshold, bool) or not isinstance(threshold, (int, float, np.integer, np.floating)):
+        raise ValueError("mesh: quadric threshold must be a number")
+    with np.errstate(over="ignore"):
+        t = np.float32(threshold)
+    if not (math.isfinite(t) and 0 <= t < 1):
+        raise ValueError("mesh: quadric threshold must be finite and in [0, 1)")
+    return abi.RmMeshQuadric(threshold=float(threshold))
+
+
 @dataclass
 class Mesh:
     """A triangle mesh as numpy arrays: positions [V, 3] float32, triangles [T, 3] uint32 (counter-clockwise seen from outside), cells

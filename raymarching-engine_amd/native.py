@@ -43,7 +43,7 @@ EXPORTS = [
     "rm_grid_axis", "rm_sdf_grid", "rm_sdf_grid_device", "rm_mesh_params_default", "rm_mesh_extract", "rm_mesh_from_values", "rm_mesh_counts", "rm_mesh_timings",
     "rm_mesh_download", "rm_mesh_device_ptr", "rm_mesh_destroy", "rm_mesh_sharp_default", "rm_mesh_extract_sharp",
     "rm_mesh_keep_default", "rm_mesh_components", "rm_mesh_components_download", "rm_mesh_filter",
-    "rm_mesh_simplify_default", "rm_mesh_simplify",
+    "rm_mesh_simplify_default", "rm_mesh_simplify", "rm_mesh_quadric_default", "rm_mesh_simplify_quadric",
 ]
 
 # G-buffer formats of a framebuffer (include/hip_raymarch.h RM_GBUFFER_*): "f32" (the default: the software GL stack's planes, which the
@@ -418,6 +418,8 @@ def load_library(path=None):
         "rm_mesh_filter": (ip, [vp, C.POINTER(abi.RmMeshKeep), C.POINTER(vp)]),
         "rm_mesh_simplify_default": (None, [C.POINTER(abi.RmMeshSimplify)]),
         "rm_mesh_simplify": (ip, [vp, C.POINTER(abi.RmGrid), C.POINTER(abi.RmMeshSimplify), C.POINTER(vp)]),
+        "rm_mesh_quadric_default": (None, [C.POINTER(abi.RmMeshQuadric)]),
+        "rm_mesh_simplify_quadric": (ip, [vp, C.POINTER(abi.RmGrid), C.POINTER(abi.RmMeshSimplify), C.POINTER(abi.RmMeshQuadric), C.POINTER(vp)]),
     }
     for name, (res, args) in sig.items():
         if name.startswith("rm_debug_") and not hasattr(lib, name) and os.environ.get("RM_LIB"):
@@ -714,10 +716,10 @@ class Context:
         g = grid.to_c()
         self._check(self.lib.rm_sdf_grid_device(self.h, scene.h, C.byref(g), int(flags), C.c_void_p(out_ptr), C.c_void_p(stream) if stream else None))
 
-    def _take_mesh(self, handle, grid, normals=False, colours=False, keep=None, components=False, simplify=None):
+    def _take_mesh(self, handle, grid, normals=False, colours=False, keep=None, components=False, simplify=None, quadric=None):
         """The arrays of a mesh handle as a mesh.Mesh (normals / colours: whether the call that made it asked for them); destroys the handle.
         simplify (_mesh_simplify's triple): the mesh is first clustered on the device (rm_mesh_simplify) and the Mesh's grid is the cluster grid,
-        which its cells then index; keep (an abi.RmMeshKeep): that mesh is filtered on the device (rm_mesh_filter), which also removes the vertices
+        which its cells then index -- with quadric (an abi.RmMeshQuadric) by rm_mesh_simplify_quadric; keep (an abi.RmMeshKeep): that mesh is filtered on the device (rm_mesh_filter), which also removes the vertices
         simplification left without triangles; the last of them is what is downloaded.  components: its labels and component sizes come with it."""
         from .mesh import Mesh
 
@@ -726,7 +728,10 @@ class Context:
             if simplify is not None:
                 grid, clusters, params = simplify
                 simplified = C.c_void_p()
-                self._check(self.lib.rm_mesh_simplify(handle, C.byref(clusters), C.byref(params), C.byref(simplified)))
+                if quadric is None:
+                    self._check(self.lib.rm_mesh_simplify(handle, C.byref(clusters), C.byref(params), C.byref(simplified)))
+                else:
+                    self._check(self.lib.rm_mesh_simplify_quadric(handle, C.byref(clusters), C.byref(params), C.byref(quadric), C.byref(simplified)))
                 handles.append(simplified)
                 handle = simplified
             if keep is not None:
@@ -785,6 +790,17 @@ class Context:
         return Context._mesh_block("keep", keep, abi.RmMeshKeep)
 
     @staticmethod
+    def _mesh_quadric(quadric, simplify):
+        """The `quadric` of extract_mesh / mesh_from_values as an abi.RmMeshQuadric (_mesh_block's rules); without `simplify` there is nothing
+        to place: ValueError."""
+        if isinstance(quadric, dict) and set(quadric) - set(abi.MESH_QUADRIC_DEFAULTS):
+            raise ValueError(f"mesh: unknown quadric parameter {sorted(set(quadric) - set(abi.MESH_QUADRIC_DEFAULTS))[0]}")
+        block = Context._mesh_block("quadric", quadric, abi.RmMeshQuadric)
+        if block is not None and simplify is None:
+            raise ValueError("mesh: quadric places the vertices of a simplification: give simplify as well")
+        return block
+
+    @staticmethod
     def _mesh_simplify(simplify):
         """The `simplify` of extract_mesh / mesh_from_values as (mesh.Grid of the clusters, abi.RmGrid, abi.RmMeshSimplify), through
         mesh.mesh_simplify's checks: None stays None; a mesh.Grid is that grid with the defaults, a dict mesh_simplify's arguments, a pair
@@ -808,7 +824,7 @@ class Context:
         raise ValueError("mesh: simplify must be None, a mesh.Grid, a dict of mesh_simplify's arguments or its (abi.RmGrid, abi.RmMeshSimplify)")
 
     def extract_mesh(self, scene: "SceneHandle", grid, iso: float = 0.0, normals: bool = True, colours: bool = False, flags: int = 0,
-                     normal_delta: float = 1e-5, sharp=None, *, keep=None, components: bool = False, simplify=None):
+                     normal_delta: float = 1e-5, sharp=None, *, keep=None, components: bool = False, simplify=None, quadric=None):
         """The level set `iso` of the scene on `grid` (mesh.Grid) as a mesh.Mesh: rm_mesh_extract -- the distances sampled and meshed
         (surface nets) on the device, with per-vertex normals / diffuse colours from the scene's probes when asked for.  `sharp`: None is
         that call; True (the defaults), a dict of mesh.mesh_sharp's arguments or an abi.RmMeshSharp is rm_mesh_extract_sharp -- the same
@@ -817,10 +833,12 @@ class Context:
         connected components on the device before anything is downloaded (rm_mesh_filter).  `components`: the returned mesh carries
         labels and component_sizes (rm_mesh_components).  `simplify`: None is that mesh; a mesh.Grid of clusters, a dict of
         mesh.mesh_simplify's arguments or its pair merges the vertices of every cluster cell into one on the device (rm_mesh_simplify) before
-        `keep` and `components` are applied, and the returned mesh's grid is the cluster grid."""
+        `keep` and `components` are applied, and the returned mesh's grid is the cluster grid.  `quadric` (with `simplify` only): None is
+        that call; True (the defaults), a dict of mesh.mesh_quadric's arguments or an abi.RmMeshQuadric is rm_mesh_simplify_quadric -- the same
+        mesh with every cluster's vertex at the minimiser of its plane quadrics, which keeps the edges and corners inside a cluster."""
         from .mesh import mesh_params
 
-        keep, simplify = self._mesh_keep(keep), self._mesh_simplify(simplify)  # (refused before anything runs)
+        keep, simplify, quadric = self._mesh_keep(keep), self._mesh_simplify(simplify), self._mesh_quadric(quadric, simplify)  # (refused before anything runs)
         g, p = grid.to_c(), mesh_params(iso=iso, normals=normals, colours=colours, flags=flags, normal_delta=normal_delta)
         h = C.c_void_p()
         s = self._mesh_block("sharp", sharp, abi.RmMeshSharp)
@@ -828,19 +846,19 @@ class Context:
             self._check(self.lib.rm_mesh_extract(self.h, scene.h, C.byref(g), C.byref(p), C.byref(h)))
         else:
             self._check(self.lib.rm_mesh_extract_sharp(self.h, scene.h, C.byref(g), C.byref(p), C.byref(s), C.byref(h)))
-        return self._take_mesh(h, grid, normals=p.normals, colours=p.colours, keep=keep, components=components, simplify=simplify)
+        return self._take_mesh(h, grid, normals=p.normals, colours=p.colours, keep=keep, components=components, simplify=simplify, quadric=quadric)
 
-    def mesh_from_values(self, grid, values: np.ndarray, iso: float = 0.0, *, keep=None, components: bool = False, simplify=None):
-        """The mesher alone on the caller's field: `values` float32 [nz + 1, ny + 1, nx + 1] (rm_mesh_from_values).  keep, components and
-        simplify: as in extract_mesh."""
-        keep, simplify = self._mesh_keep(keep), self._mesh_simplify(simplify)
+    def mesh_from_values(self, grid, values: np.ndarray, iso: float = 0.0, *, keep=None, components: bool = False, simplify=None, quadric=None):
+        """The mesher alone on the caller's field: `values` float32 [nz + 1, ny + 1, nx + 1] (rm_mesh_from_values).  keep, components,
+        simplify and quadric: as in extract_mesh."""
+        keep, simplify, quadric = self._mesh_keep(keep), self._mesh_simplify(simplify), self._mesh_quadric(quadric, simplify)
         g = grid.to_c()
         v = np.ascontiguousarray(values, np.float32)
         if v.shape != grid.shape:
             raise ValueError(f"values must have the shape {grid.shape} of the grid's corners, not {v.shape}")
         h = C.c_void_p()
         self._check(self.lib.rm_mesh_from_values(self.h, C.byref(g), _fp(v), float(iso), C.byref(h)))
-        return self._take_mesh(h, grid, keep=keep, components=components, simplify=simplify)
+        return self._take_mesh(h, grid, keep=keep, components=components, simplify=simplify, quadric=quadric)
 
     def probe_camera(self, uniforms: abi.RmUniforms, width: int, height: int) -> np.ndarray:
         out = np.empty((height, width, 8), np.float32)
