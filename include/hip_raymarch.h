@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define RM_ABI_VERSION 9 /* 9: RM_GBUFFER_F32 / _F16, rm_fb_create_fmt, rm_fb_create_striped_fmt, rm_fb_wrap_fmt, rm_fb_gbuffer, rm_fb_download_raw, rm_fb_upload_raw, RmDenoise, rm_denoise_default, rm_denoise, rm_denoise_device, rm_present_denoised, RM_FB_MOMENTS, RM_PLANE_MOMENTS, rm_fb_has_moments, RmDenoiseVariance, rm_denoise_variance_default, rm_denoise_variance, rm_denoise_variance_device, rm_present_denoised_variance, RmDespeckle, RmFilters, RM_DENOISE_NONE / _ATROUS / _VARIANCE, rm_filters_default, rm_filter, rm_filter_device, rm_present_filtered, RM_STATS_BINS, RmFrameStats, rm_frame_stats, RmAutoExposure, rm_auto_exposure_default, rm_stats_percentile, rm_stats_exposure, RM_TONE_CLIP / _REINHARD / _ACES, RmDisplay, rm_display_default, rm_present_display, rm_present_display_device, rm_present_linear, RmGrid, rm_grid_axis, rm_sdf_grid, rm_sdf_grid_device, RmMeshParams, rm_mesh_params_default, rm_mesh, rm_mesh_extract, rm_mesh_from_values, rm_mesh_counts, rm_mesh_timings, RM_MESH_POSITIONS / _NORMALS / _COLOURS / _TRIANGLES / _CELLS, rm_mesh_download, rm_mesh_device_ptr, rm_mesh_destroy, RmMeshSharp, rm_mesh_sharp_default, rm_mesh_extract_sharp, RmMeshKeep, rm_mesh_keep_default, rm_mesh_components, RM_MESH_PART_LABELS / _SIZES, rm_mesh_components_download, rm_mesh_filter, RmMeshSimplify, rm_mesh_simplify_default, rm_mesh_simplify, RmMeshQuadric, rm_mesh_quadric_default, rm_mesh_simplify_quadric (additions only); 8: RM_PRIM_TORUS / _CYLINDER / _PLANE, RM_OP_SMOOTH_SUBTRACT / _INTERSECT, rm_probe_math (additions only); 7: rm_present_sharded_finish / rm_present_sharded take the size of the host buffer (a changed signature), rm_ctx_set_cull_min_pixels, rm_ctx_set_cull_budget, rm_ctx_cull_stats; 6: rm_present_striped_rows, rm_present_sharded_start / _finish, rm_ctx_last_warning, RM_PROBE_CAST_SHADOW, RM_PRIM_KIND (additions only); 3: rm_ctx_set_sample_batch, rm_buffer_*; 4: rm_ctx_set_gl_stack; 5: RmSurface / RmSceneDesc.surfaces (the struct grew), rm_pack_present_rows, rm_present_sharded, rm_ctx_last_pipeline, RM_RENDER_NO_FAR_JUMP, RM_RENDER_NO_CULL (additions only) */
+#define RM_ABI_VERSION 9 /* 9: RM_GBUFFER_F32 / _F16, rm_fb_create_fmt, rm_fb_create_striped_fmt, rm_fb_wrap_fmt, rm_fb_gbuffer, rm_fb_download_raw, rm_fb_upload_raw, RmDenoise, rm_denoise_default, rm_denoise, rm_denoise_device, rm_present_denoised, RM_FB_MOMENTS, RM_PLANE_MOMENTS, rm_fb_has_moments, RmDenoiseVariance, rm_denoise_variance_default, rm_denoise_variance, rm_denoise_variance_device, rm_present_denoised_variance, RmDespeckle, RmFilters, RM_DENOISE_NONE / _ATROUS / _VARIANCE, rm_filters_default, rm_filter, rm_filter_device, rm_present_filtered, RM_STATS_BINS, RmFrameStats, rm_frame_stats, RmAutoExposure, rm_auto_exposure_default, rm_stats_percentile, rm_stats_exposure, RM_TONE_CLIP / _REINHARD / _ACES, RmDisplay, rm_display_default, rm_present_display, rm_present_display_device, rm_present_linear, RmGrid, rm_grid_axis, rm_sdf_grid, rm_sdf_grid_device, RmMeshParams, rm_mesh_params_default, rm_mesh, rm_mesh_extract, rm_mesh_from_values, rm_mesh_counts, rm_mesh_timings, RM_MESH_POSITIONS / _NORMALS / _COLOURS / _TRIANGLES / _CELLS, rm_mesh_download, rm_mesh_device_ptr, rm_mesh_destroy, RmMeshSharp, rm_mesh_sharp_default, rm_mesh_extract_sharp, RmMeshKeep, rm_mesh_keep_default, rm_mesh_components, RM_MESH_PART_LABELS / _SIZES, rm_mesh_components_download, rm_mesh_filter, RmMeshSimplify, rm_mesh_simplify_default, rm_mesh_simplify, RmMeshQuadric, rm_mesh_quadric_default, rm_mesh_simplify_quadric, RmMeshOcclusion, rm_mesh_occlusion_default, rm_mesh_occlusion_directions, rm_mesh_occlusion (additions only); 8: RM_PRIM_TORUS / _CYLINDER / _PLANE, RM_OP_SMOOTH_SUBTRACT / _INTERSECT, rm_probe_math (additions only); 7: rm_present_sharded_finish / rm_present_sharded take the size of the host buffer (a changed signature), rm_ctx_set_cull_min_pixels, rm_ctx_set_cull_budget, rm_ctx_cull_stats; 6: rm_present_striped_rows, rm_present_sharded_start / _finish, rm_ctx_last_warning, RM_PROBE_CAST_SHADOW, RM_PRIM_KIND (additions only); 3: rm_ctx_set_sample_batch, rm_buffer_*; 4: rm_ctx_set_gl_stack; 5: RmSurface / RmSceneDesc.surfaces (the struct grew), rm_pack_present_rows, rm_present_sharded, rm_ctx_last_pipeline, RM_RENDER_NO_FAR_JUMP, RM_RENDER_NO_CULL (additions only) */
 
 #define RM_MAX_BOUNCES 10 /* raymarchingStepCountsArray[10], raymarcher.frag:31 */
 #define RM_MAX_LIGHTS 10  /* lightPositions[10],             raymarcher.frag:37-39 */
@@ -1068,6 +1068,58 @@ RM_API int rm_mesh_simplify(rm_mesh* mesh, const RmGrid* clusters, const RmMeshS
 typedef struct RmMeshQuadric { float threshold; int32_t reserved[3]; } RmMeshQuadric; /* 16 bytes */
 RM_API void rm_mesh_quadric_default(RmMeshQuadric* q);
 RM_API int rm_mesh_simplify_quadric(rm_mesh* mesh, const RmGrid* clusters, const RmMeshSimplify* params, const RmMeshQuadric* quadric, rm_mesh** out);
+
+/* ---- ambient occlusion (opt-in): how open the scene is over every vertex, from the distance field ----
+ * The mesh entries end with positions, normals and a flat diffuse colour; the cavities and creases that make a scene legible are a property of
+ * the SCENE, which nothing downstream of the mesh can add.  rm_mesh_occlusion bakes them per vertex from the exact distance field (Evans,
+ * "Fast approximations for global illumination on dynamic scenes", 2006; Quilez's distance-field occlusion): a fixed fan of K directions over
+ * the surface, J taps along each, and at every tap the distance the scene has against the distance an open half-space would have.  No ray is
+ * cast and the triangles are not read.  It works on any rm_mesh (rm_mesh_extract, _sharp, _from_values, rm_mesh_filter, rm_mesh_simplify,
+ * _quadric) with any scene of the mesh's context, and changes nothing of the mesh: the occlusion is not one of its arrays (rm_mesh_download
+ * serves `what` 0..4 as before), it goes to the caller's V floats.  1 means open.  The result is a function of (scene, positions, params)
+ * only -- the mesh's stored normals are not used.
+ * params == NULL: the defaults (radius 0.25f, directions 16, taps 4, normal_delta 0x1p-10f -- the sharp vertices' default, for the same
+ * reason --, strength 1, flags 0).  A block is valid iff radius is finite and in [0x1p-64f, 0x1p64f], directions K is one of 1, 2, 4, 8, 16,
+ * 32, 64, taps J is one of 1, 2, 4, 8, normal_delta is finite and > 0, strength is finite and in [0, 4], flags are of rm_sdf_grid's set and
+ * reserved is 0.
+ * Arithmetic: fp32 unless it says double, every operation rounded on its own (no contraction), IEEE division.
+ *   1. Direction table, on the host in double (rm_mesh_occlusion_directions writes it: K x 4 floats, no GPU and no context, like rm_grid_axis).
+ *      For k = 0 .. K-1:  u = (k + 0.5) / K;  phi = k * (pi * (3 - sqrt(5)));  z = sqrt(1 - u);  r = sqrt(u);  x = r cos(phi);  y = r sin(phi).
+ *      Each of x, y, z is rounded to float; the fourth float is (float)(1.0 / (double)z_float).  Every direction has z > 0: a cosine-weighted
+ *      fan over the hemisphere.  The device gets this table from the host and recomputes nothing of it.
+ *   2. Per vertex with position p:  n = what rm_probe(RM_PROBE_NORMAL, param = normal_delta, flags) gives at p;  d0 = what
+ *      rm_probe(RM_PROBE_SDF, flags) gives at p.
+ *   3. Frame (Duff et al., "Building an orthonormal basis, revisited", 2017).  s = copysignf(1, n.z);  a = -1.0f / (s + n.z);
+ *      b = (n.x * n.y) * a;  t = (1 + ((s * n.x) * n.x) * a,  s * b,  (-s) * n.x);  bt = (b,  s + (n.y * n.y) * a,  -n.y).
+ *      Direction k, per component c:  w[c] = ((x * t[c]) + (y * bt[c])) + (z * n[c]).
+ *   4. Taps j = 0 .. J-1.  t_j = radius * 2^-j;  inv_t_j = inv_radius * 2^j with inv_radius = 1.0f / radius (both scalings exact);
+ *      q[c] = p[c] + w[c] * t_j;  d = the scene's distance at q, RM_PROBE_SDF's bits for these flags on this context;  e = z * t_j;
+ *      ie = (1 / z) * inv_t_j (the table's fourth float);  o = ((d0 + e) - d) * ie;  if (!(o >= 0)) o = 0;  if (o > 1) o = 1 (NaN gives 0);
+ *      quantum = (uint32)(o * 65536.0f + 0.5f), truncating.  Over a flat open surface d = d0 + e, and over a convex one d is larger: o = 0.
+ *      d0 takes out, to first order, the fraction of a cell by which a surface-nets vertex sits off the surface.
+ *   5. S = the integer sum of the K * J quanta (at most 2^25; no order).  occ = (float)S * 2^-(16 + log2 K + log2 J) (the scale is exact);
+ *      ao = 1 - strength * occ;  if (!(ao <= 1)) ao = 1;  if (ao < 0) ao = 0.
+ * The same bytes on every run.
+ * Procedure (rm_mesh_kernels.inc "ambient occlusion", in all three units: it calls the scene's evaluator).  Two probe launches on the mesh's
+ * positions make n and d0 in scratch, as the attribute pass does; then one lane per (vertex, direction) -- a vertex's K lanes are neighbours
+ * in one wave -- sets its J points up, evaluates them, and the K integer sums are added across the lanes; the first of them stores.  No atomics.
+ * The call is synchronous on the context's stream and frees its scratch before it returns.  out_ms2 (may be NULL) receives the milliseconds
+ * between events on the stream of {the two probes, the taps}; an empty mesh succeeds, writes nothing to out_host and {0, 0} to out_ms2.
+ * RM_ERR_INVALID, in this order (the text through rm_last_error(NULL) when no context is known): an invalid block, one text per field, before
+ * the handles are looked at; a NULL mesh, scene or out_host ("NULL argument"); a scene of another context than the mesh's.
+ * RM_ERR_DEVICE: V * directions >= 2^31; a failed allocation, with nothing leaked. */
+typedef struct RmMeshOcclusion {
+  float radius;        /* the first tap's distance along its direction; tap j lies at radius * 2^-j */
+  int32_t directions;  /* K */
+  int32_t taps;        /* J */
+  float normal_delta;  /* of the RM_PROBE_NORMAL that gives the frame */
+  float strength;      /* ao = 1 - strength * occ, clamped to [0, 1] */
+  int32_t flags;       /* 0, RM_RENDER_FAST, RM_RENDER_NO_CULL or both, as rm_sdf_grid */
+  int32_t reserved[2];
+} RmMeshOcclusion; /* 32 bytes */
+RM_API void rm_mesh_occlusion_default(RmMeshOcclusion* params);
+RM_API int rm_mesh_occlusion_directions(int directions, float* out);
+RM_API int rm_mesh_occlusion(rm_mesh* mesh, rm_scene* scene, const RmMeshOcclusion* params, float* out_host, float* out_ms2);
 
 #ifdef __cplusplus
 }

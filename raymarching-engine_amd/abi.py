@@ -312,3 +312,22 @@ class RmMeshQuadric(C.Structure):
 MESH_QUADRIC_DEFAULTS = dict(threshold=0.1)  # rm_mesh_quadric_default
 
 assert C.sizeof(RmMeshQuadric) == 16
+
+
+class RmMeshOcclusion(C.Structure):
+    """Parameters of rm_mesh_occlusion (ABI 9): `directions` directions over every vertex, `taps` taps along each, the first at `radius`
+    (include/hip_raymarch.h "ambient occlusion")."""
+    _fields_ = [
+        ("radius", C.c_float),
+        ("directions", C.c_int32),
+        ("taps", C.c_int32),
+        ("normal_delta", C.c_float),
+        ("strength", C.c_float),
+        ("flags", C.c_int32),
+        ("reserved", C.c_int32 * 2),
+    ]
+
+
+MESH_OCCLUSION_DEFAULTS = dict(radius=0.25, directions=16, taps=4, normal_delta=2.0 ** -10, strength=1.0, flags=0)  # rm_mesh_occlusion_default
+
+assert C.sizeof(RmMeshOcclusion) == 32

@@ -35,6 +35,7 @@ extern "C" {
 hipError_t rm_gl_launch_pixels(const void* kparams, hipStream_t stream);
 hipError_t rm_gl_launch_probe(const void* probe_params, hipStream_t stream);
 hipError_t rm_gl_launch_sdf_grid(const void* grid_params, hipStream_t stream);
+hipError_t rm_gl_launch_mesh_occlusion(const void* occlusion_params, hipStream_t stream);
 hipError_t rm_gl_launch_math_probe(int fn, const float* a, const float* b, int n, float* out, hipStream_t stream);
 hipError_t rm_gl_launch_camera_rng(const RmUniforms* u, int W, int H, int what, int count, float* out, hipStream_t stream);
 hipError_t rm_gl_launch_present(const float4* color, const void* normal_dof, bool nd_half, int W, int H, float brightness, uchar4* out, hipStream_t stream);
@@ -206,7 +207,8 @@ struct DeviceArray {
 // Stage timing of the mesh entries (rm_mesh_timings): a span is a pair of events on the context's stream, made with the first mesh
 // that runs the stage.
 struct MeshSpans {
-  enum { SAMPLE, COUNT_SCAN, EMIT, SHARPEN, ATTRIBUTES, LABEL, KEEP_FLAGS, GATHER, CLUSTER_NUMBER, CLUSTER_MERGE, CLUSTER_GATHER, COUNT };
+  enum { SAMPLE, COUNT_SCAN, EMIT, SHARPEN, ATTRIBUTES, LABEL, KEEP_FLAGS, GATHER, CLUSTER_NUMBER, CLUSTER_MERGE, CLUSTER_GATHER, OCCLUSION_PROBES, OCCLUSION_TAPS,
+         COUNT };
   hipEvent_t ev[COUNT][2] = {};
   hipError_t begin(int span, hipStream_t stream) { return record(ev[span][0], stream); }
   hipError_t end(int span, hipStream_t stream) { return record(ev[span][1], stream); }

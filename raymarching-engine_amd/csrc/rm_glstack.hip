@@ -18,6 +18,9 @@ extern "C" {
 hipError_t rm_gl_launch_pixels(const void* kparams, hipStream_t stream) { return rm_gl::launch_pixels_strict(*static_cast<const KParams*>(kparams), stream); }
 hipError_t rm_gl_launch_probe(const void* probe_params, hipStream_t stream) { return rm_gl::launch_probe_strict(*static_cast<const ProbeParams*>(probe_params), stream); }
 hipError_t rm_gl_launch_sdf_grid(const void* grid_params, hipStream_t stream) { return rm_gl::launch_sdf_grid_strict(*static_cast<const SdfGridParams*>(grid_params), stream); }
+hipError_t rm_gl_launch_mesh_occlusion(const void* occlusion_params, hipStream_t stream) {
+  return rm_gl::launch_mesh_occlusion_strict(*static_cast<const MeshOcclusionPass*>(occlusion_params), stream);
+}
 hipError_t rm_gl_launch_camera_rng(const RmUniforms* u, int W, int H, int what, int count, float* out, hipStream_t stream) {
   return rm_gl::launch_camera_rng(*u, W, H, what, count, out, stream);
 }

@@ -668,3 +668,109 @@ void rm_mesh_quadric_default(RmMeshQuadric* q) {
 int rm_mesh_simplify_quadric(rm_mesh* mesh, const RmGrid* clusters, const RmMeshSimplify* params, const RmMeshQuadric* quadric, rm_mesh** out) {
   return mesh_simplify_entry("rm_mesh_simplify_quadric", mesh, clusters, params, true, quadric, out);
 }
+
+// ---- ambient occlusion (include/hip_raymarch.h "ambient occlusion") ----------------------------------------------------------------------------
+
+void rm_mesh_occlusion_default(RmMeshOcclusion* params) {
+  if (!params) return;
+  *params = RmMeshOcclusion{0.25f, 16, 4, 0x1p-10f, 1.0f, 0, {0, 0}};
+}
+
+// log2 of a power of two in 1..limit, -1 for anything else
+static int occlusion_log2(int n, int limit) {
+  for (int l = 0; (1 << l) <= limit; l++)
+    if (n == (1 << l)) return l;
+  return -1;
+}
+
+// the table in double, every output rounded once (the header's "direction table")
+static void occlusion_directions(int K, float* out) {
+  const double golden = M_PI * (3.0 - std::sqrt(5.0));
+  for (int k = 0; k < K; k++) {
+    const double u = ((double)k + 0.5) / (double)K;
+    const double phi = (double)k * golden;
+    const double r = std::sqrt(u);
+    const float z = (float)std::sqrt(1.0 - u);
+    out[4 * k] = (float)(r * std::cos(phi));
+    out[4 * k + 1] = (float)(r * std::sin(phi));
+    out[4 * k + 2] = z;
+    out[4 * k + 3] = (float)(1.0 / (double)z);
+  }
+}
+
+int rm_mesh_occlusion_directions(int directions, float* out) {
+  const Refuse refuse{nullptr, "rm_mesh_occlusion_directions"};
+  if (occlusion_log2(directions, 64) < 0) return refuse("directions must be 1, 2, 4, 8, 16, 32 or 64");
+  if (!out) return refuse("NULL argument");
+  occlusion_directions(directions, out);
+  return RM_OK;
+}
+
+static int mesh_occlusion_check(const Refuse& refuse, const RmMeshOcclusion* in, RmMeshOcclusion* p) {
+  rm_mesh_occlusion_default(p);
+  if (in) *p = *in;
+  if (!(std::isfinite(p->radius) && p->radius >= 0x1p-64f && p->radius <= 0x1p64f)) return refuse("occlusion radius must be finite and in [2^-64, 2^64]");
+  if (occlusion_log2(p->directions, 64) < 0) return refuse("occlusion directions must be 1, 2, 4, 8, 16, 32 or 64");
+  if (occlusion_log2(p->taps, 8) < 0) return refuse("occlusion taps must be 1, 2, 4 or 8");
+  if (!(std::isfinite(p->normal_delta) && p->normal_delta > 0.0f)) return refuse("occlusion normal_delta must be finite and > 0");
+  if (!(std::isfinite(p->strength) && p->strength >= 0.0f && p->strength <= 4.0f)) return refuse("occlusion strength must be finite and in [0, 4]");
+  if (int rc = sdf_flags_check(refuse, p->flags)) return rc;
+  if (p->reserved[0] != 0 || p->reserved[1] != 0) return refuse("occlusion reserved must be 0");
+  return RM_OK;
+}
+
+int rm_mesh_occlusion(rm_mesh* mesh, rm_scene* scene, const RmMeshOcclusion* params, float* out_host, float* out_ms2) {
+  rm_ctx* ctx = mesh ? mesh->ctx : nullptr;
+  const Refuse refuse{ctx, "rm_mesh_occlusion"};
+  RmMeshOcclusion p;
+  if (int rc = mesh_occlusion_check(refuse, params, &p)) return rc;
+  if (int rc = scene_check(refuse, scene, out_host != nullptr)) return rc;  // (a NULL mesh is a NULL context there)
+  if (out_ms2) out_ms2[0] = out_ms2[1] = 0.0f;
+  if (mesh->vertices == 0) return RM_OK;
+  const int log2_k = occlusion_log2(p.directions, 64), log2_j = occlusion_log2(p.taps, 8);
+  if ((mesh->vertices << log2_k) >= (1ull << 31))
+    return refuse("the mesh has more vertices than the kernel's index holds rays of (V * directions >= 2^31)", RM_ERR_DEVICE);
+  const size_t V = (size_t)mesh->vertices;
+  float table[64 * 4];
+  occlusion_directions(p.directions, table);
+  RM_HIP(ctx, hipSetDevice(ctx->device));
+  DeviceArray normals, d0, directions, ao;  // (freed behind the wait of the copy below; a call that fails before it leaves that wait to hipFree)
+  RM_HIP_AS(refuse, normals.reserve(sizeof(float) * 3u * V));
+  RM_HIP_AS(refuse, d0.reserve(sizeof(float) * V));
+  RM_HIP_AS(refuse, directions.reserve(sizeof(float) * 4u * (size_t)p.directions));
+  RM_HIP_AS(refuse, ao.reserve(sizeof(float) * V));
+  if (int rc = scene_cull_grid(ctx, scene, p.flags, 1ll << 40)) return rc;  // (with the grid, as rm_probe obtains it)
+  const float* positions = mesh->array[RM_MESH_POSITIONS].f32();
+  MeshOcclusionPass P{};
+  P.scene = scene->dev;
+  if (p.flags & RM_RENDER_NO_CULL) P.scene.cull.cells = nullptr;
+  P.positions = positions;
+  P.normals = normals.f32();
+  P.d0 = d0.f32();
+  P.directions = static_cast<const float4*>(directions.p);
+  P.out = ao.f32();
+  P.vertices = (int)V;
+  P.log2_directions = log2_k;
+  P.taps = p.taps;
+  P.radius = p.radius;
+  P.inv_radius = 1.0f / p.radius;
+  P.strength = p.strength;
+  P.scale = std::ldexp(1.0f, -(16 + log2_k + log2_j));
+  MeshSpans& spans = ctx->mesh_spans;
+  RM_HIP_AS(refuse, hipMemcpyAsync(directions.p, table, sizeof(float) * 4u * (size_t)p.directions, hipMemcpyHostToDevice, ctx->stream));
+  RM_HIP_AS(refuse, spans.begin(MeshSpans::OCCLUSION_PROBES, ctx->stream));
+  RM_HIP_AS(refuse, probe_enqueue(ctx, scene, RM_PROBE_NORMAL, positions, normals.f32(), (int)V, p.normal_delta, p.flags, ctx->stream));
+  RM_HIP_AS(refuse, probe_enqueue(ctx, scene, RM_PROBE_SDF, positions, d0.f32(), (int)V, 0.0f, p.flags, ctx->stream));
+  RM_HIP_AS(refuse, spans.end(MeshSpans::OCCLUSION_PROBES, ctx->stream));
+  RM_HIP_AS(refuse, spans.begin(MeshSpans::OCCLUSION_TAPS, ctx->stream));
+  RM_HIP_AS(refuse, (p.flags & RM_RENDER_FAST) ? rm::launch_mesh_occlusion_fast(P, ctx->stream)
+                    : ctx->gl_stack           ? rm_gl_launch_mesh_occlusion(&P, ctx->stream)
+                                              : rm::launch_mesh_occlusion_strict(P, ctx->stream));
+  RM_HIP_AS(refuse, spans.end(MeshSpans::OCCLUSION_TAPS, ctx->stream));
+  if (int rc = copy_and_wait(ctx, out_host, ao.p, sizeof(float) * V, hipMemcpyDeviceToHost)) return rc;
+  if (out_ms2) {
+    out_ms2[0] = spans.ms(MeshSpans::OCCLUSION_PROBES);
+    out_ms2[1] = spans.ms(MeshSpans::OCCLUSION_TAPS);
+  }
+  return RM_OK;
+}

@@ -53,6 +53,108 @@ hipError_t RM_LAUNCH(launch_sdf_grid)(const SdfGridParams& P, hipStream_t stream
 }
 #endif
 
+// ---- ambient occlusion: the scene's distance at a fixed fan of taps over every vertex (the header's "ambient occlusion") -----------
+// One lane per (vertex, direction): a vertex's K lanes are consecutive, and K divides 64, so they sit in one wave.  A lane builds the
+// frame of its vertex's probed normal, turns its direction into it and makes all its taps' points BEFORE enter_math_mode (the fast
+// Mandelbulb flushes denormals: what can go subnormal behind it reaches only the quantiser, where it is 0 either way).  The points
+// wait in LDS, [tap][component][thread], and that is what holds the order: the compiler orders no floating-point operation against a
+// write of the mode register (with the points in registers the fast Mandelbulb's code had the switch ahead of the whole set-up), but
+// the stores that take them lie ahead of a barrier, and the switch behind it.  It also spares the evaluator 24 registers.  Then the
+// lane evaluates its taps one after the other and sums its quanta; the K integer sums are added across the vertex's lanes (any order
+// gives the same sum), and lane k = 0 scales, shades and stores.  Lanes beyond V * K repeat the last ray and store nothing: the
+// evaluators ballot and branch wave-uniformly, as above.  The triangles are not read.
+template <int KIND, bool FAST>
+__global__ __launch_bounds__(256) void rm_mesh_occlusion_kernel(const MeshOcclusionPass P) {
+  using MM = typename std::conditional<FAST, FM, PM>::type;
+  __shared__ SceneLds lds;
+  __shared__ float taps[8][3][256];  // a lane's points: only that lane reads them back
+  const unsigned int rays = (unsigned int)P.vertices << P.log2_directions;  // < 2^31 (rm_mesh_occlusion)
+  const unsigned int gi = blockIdx.x * blockDim.x + threadIdx.x;
+  const unsigned int ray = gi < rays ? gi : rays - 1u;
+  const unsigned int v = ray >> P.log2_directions, k = ray & ((1u << P.log2_directions) - 1u);
+  const float* const pv = P.positions + 3 * (size_t)v;
+  const float* const nv = P.normals + 3 * (size_t)v;
+  const float px = pv[0], py = pv[1], pz = pv[2];
+  const float nx = nv[0], ny = nv[1], nz = nv[2];
+  const float d0 = P.d0[v];
+  const float4 dir = P.directions[k];  // (x, y, z, 1 / z) in the frame
+  // the frame (Duff et al. 2017) and the direction in it
+  const float s = copysignf(1.0f, nz);
+  const float a = -1.0f / (s + nz);
+  const float b = (nx * ny) * a;
+  const float tx = 1.0f + ((s * nx) * nx) * a, ty = s * b, tz = (-s) * nx;
+  const float bx = b, by = s + (ny * ny) * a, bz = -ny;
+  const float wx = ((dir.x * tx) + (dir.y * bx)) + (dir.z * nx);
+  const float wy = ((dir.x * ty) + (dir.y * by)) + (dir.z * ny);
+  const float wz = ((dir.x * tz) + (dir.y * bz)) + (dir.z * nz);
+  {
+    float t = P.radius;
+#pragma unroll
+    for (int j = 0; j < 8; j++) {  // (taps beyond J are made and never evaluated)
+      taps[j][0][threadIdx.x] = px + wx * t;
+      taps[j][1][threadIdx.x] = py + wy * t;
+      taps[j][2][threadIdx.x] = pz + wz * t;
+      t *= 0.5f;
+    }
+  }
+  __syncthreads();
+  enter_math_mode<KIND, FAST>();
+  Sdf<KIND>::stage(P.scene, lds);
+  __syncthreads();
+  unsigned int sum = 0;
+  float t = P.radius, it = P.inv_radius;
+  for (int j = 0; j < P.taps; j++) {
+    const float d = Sdf<KIND>::template eval<MM>(P.scene, lds, V(taps[j][0][threadIdx.x], taps[j][1][threadIdx.x], taps[j][2][threadIdx.x]));
+    const float e = dir.z * t;
+    const float ie = dir.w * it;
+    float o = ((d0 + e) - d) * ie;
+    if (!(o >= 0.0f)) o = 0.0f;
+    if (o > 1.0f) o = 1.0f;
+    sum += (unsigned int)(o * 65536.0f + 0.5f);
+    t *= 0.5f;
+    it *= 2.0f;
+  }
+#pragma unroll
+  for (int m = 1; m < 64; m <<= 1)
+    if (m < (1 << P.log2_directions)) sum += (unsigned int)__shfl_xor((int)sum, m);
+  if (gi < rays && k == 0) {
+    const float occ = (float)sum * P.scale;
+    float ao = 1.0f - P.strength * occ;
+    if (!(ao <= 1.0f)) ao = 1.0f;
+    if (ao < 0.0f) ao = 0.0f;
+    P.out[v] = ao;
+  }
+}
+
+#ifndef RM_ONLY_KERNELS
+// the kind selection is launch_sdf_grid's, row for row: a tap's distance has to be the probe's at that point
+hipError_t RM_LAUNCH(launch_mesh_occlusion)(const MeshOcclusionPass& P, hipStream_t stream) {
+  const long long rays = (long long)P.vertices << P.log2_directions;
+  const dim3 grid((unsigned int)((rays + 255) / 256));
+#define RM_OCCLUSION_CASE(K) case K: hipLaunchKernelGGL((rm_mesh_occlusion_kernel<K, kFast>), grid, dim3(256), 0, stream, P); break;
+  if (P.scene.kind == RM_SCENE_TABLE && (P.scene.table_flags & RM_TABLE_HAS_KIND)) {
+    hipLaunchKernelGGL((rm_mesh_occlusion_kernel<RM_KIND_TABLE_KINDS, kFast>), grid, dim3(256), 0, stream, P);
+    return hipGetLastError();
+  }
+  if (P.scene.kind == RM_SCENE_TABLE && P.scene.nprims >= RM_TABLE_BIG_ROWS) {
+    hipLaunchKernelGGL((rm_mesh_occlusion_kernel<RM_KIND_TABLE_BIG, kFast>), grid, dim3(256), 0, stream, P);
+    return hipGetLastError();
+  }
+  switch (P.scene.kind) {
+    RM_OCCLUSION_CASE(RM_SCENE_TABLE)
+    RM_OCCLUSION_CASE(RM_SCENE_MANDELBULB)
+    RM_OCCLUSION_CASE(RM_SCENE_SPHERE_GRID)
+    RM_OCCLUSION_CASE(RM_SCENE_SPHERE_LATTICE)
+    RM_OCCLUSION_CASE(RM_SCENE_MENGER)
+    RM_OCCLUSION_CASE(RM_SCENE_KIFS_TREE)
+    RM_OCCLUSION_CASE(RM_SCENE_KIFS_BOX)
+    default: return hipErrorInvalidValue;
+  }
+#undef RM_OCCLUSION_CASE
+  return hipGetLastError();
+}
+#endif
+
 #if !RM_BUILD_FAST && !RM_GL_STACK
 // ---- the mesher: surface nets ---------------------------------------------------------------------------------------------------
 // A corner is inside iff v - iso < 0 (NaN, +0, -0 are outside); a cell is active iff its 8 corners are not all alike and then owns

@@ -310,6 +310,22 @@ struct SdfGridParams {
   GridDims grid;
   float* out;
 };
+// rm_mesh_occlusion: one lane per (vertex, direction), Sdf<KIND>::eval at its taps, with the probe's scene block.  normals and d0 are
+// the probes' outputs at the positions (RM_PROBE_NORMAL, RM_PROBE_SDF); directions is the host's table (rm_mesh_occlusion_directions).
+struct MeshOcclusionPass {
+  DevScene scene;
+  const float* positions;    // V x 3
+  const float* normals;      // V x 3
+  const float* d0;           // V
+  const float4* directions;  // K x (x, y, z, 1 / z)
+  float* out;                // V
+  int vertices;              // V << log2_directions < 2^31
+  int log2_directions;       // K = 1 << log2_directions <= 64
+  int taps;                  // J in 1..8
+  float radius, inv_radius;  // inv_radius = 1.0f / radius, divided once on the host
+  float strength;
+  float scale;               // 2^-(16 + log2 K + log2 J)
+};
 // The surface-nets mesher over a grid of values.  counts: per cell (vertex flag) | (quads << 32), scanned in place into the cell's
 // first vertex | first quad; the emit pass reads a neighbour's vertex index from there (every cell round a crossing edge is active).
 struct MeshParams {
@@ -457,6 +473,8 @@ hipError_t launch_probe_fast(const ProbeParams& P, hipStream_t stream);
 // rm_mesh_kernels.inc: the grid sampler in each unit's arithmetic; the mesher's three steps (strict unit only, arithmetic-independent)
 hipError_t launch_sdf_grid_strict(const SdfGridParams& P, hipStream_t stream);
 hipError_t launch_sdf_grid_fast(const SdfGridParams& P, hipStream_t stream);
+hipError_t launch_mesh_occlusion_strict(const MeshOcclusionPass& P, hipStream_t stream);
+hipError_t launch_mesh_occlusion_fast(const MeshOcclusionPass& P, hipStream_t stream);
 size_t rm_mesh_scan_scratch_elems(long long cells);  // 64-bit words of scratch launch_mesh_scan needs behind the counts
 hipError_t launch_mesh_count(const MeshParams& P, hipStream_t stream);
 hipError_t launch_mesh_scan(unsigned long long* counts, long long cells, unsigned long long* scratch, unsigned long long* total, hipStream_t stream);

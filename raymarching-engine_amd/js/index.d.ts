@@ -123,6 +123,8 @@ export class RenderJobContext {
   extractMesh(scene: Scene, grid: MeshGrid, params: MeshParams | null | undefined, sharp: MeshSharp | true | null | undefined, keep: MeshKeep | true | null | undefined, components: boolean | undefined, simplify: MeshSimplify | null): Mesh;
   /** with `quadric` (true = the defaults; only with `simplify`): every cluster's vertex at the minimiser of the plane quadrics of the source triangles that touch the cluster instead of at the mean of its vertices (rm_mesh_simplify_quadric), which keeps the edges and corners inside a cluster; only the positions differ */
   extractMesh(scene: Scene, grid: MeshGrid, params: MeshParams | null | undefined, sharp: MeshSharp | true | null | undefined, keep: MeshKeep | true | null | undefined, components: boolean | undefined, simplify: MeshSimplify, quadric: MeshQuadric | true | null): Mesh;
+  /** with `occlusion` (true = the defaults): the scene's ambient occlusion at the vertices of the mesh that is returned, behind simplify, keep and components (rm_mesh_occlusion), as Mesh.occlusion; timings gains a fourth entry, its milliseconds */
+  extractMesh(scene: Scene, grid: MeshGrid, params: MeshParams | null | undefined, sharp: MeshSharp | true | null | undefined, keep: MeshKeep | true | null | undefined, components: boolean | undefined, simplify: MeshSimplify | null | undefined, quadric: MeshQuadric | true | null | undefined, occlusion: MeshOcclusion | true | null): Mesh;
   /** the mesher alone on the caller's field (rm_mesh_from_values); keep, components and simplify as in extractMesh */
   meshFromValues(grid: MeshGrid, values: Float32Array, iso?: number, keep?: MeshKeep | true | null, components?: boolean, simplify?: MeshSimplify | null): Mesh;
   /** quadric as in extractMesh */
@@ -158,7 +160,7 @@ export const RM: { [name: string]: number };
 /** mesh extraction (include/hip_raymarch.h "mesh extraction"): n = CELLS per axis between the corners lo and hi */
 export interface MeshGrid { lo: [number, number, number]; hi: [number, number, number]; n: [number, number, number] }
 export interface MeshParams { iso?: number; normals?: boolean | 0 | 1; normalDelta?: number; colours?: boolean | 0 | 1; flags?: number }
-export interface Mesh { positions: Float32Array; normals: Float32Array | null; colours: Float32Array | null; triangles: Uint32Array; cells: Uint32Array; /** ms of sampling, meshing, attributes (rm_mesh_timings) */ timings: [number, number, number]; /** only when components were asked for: each vertex's component, and (vertices, triangles) per component */ labels?: Uint32Array; componentSizes?: Uint32Array }
+export interface Mesh { positions: Float32Array; normals: Float32Array | null; colours: Float32Array | null; triangles: Uint32Array; cells: Uint32Array; /** ms of sampling, meshing, attributes (rm_mesh_timings); with an occlusion a fourth entry, its probes and taps */ timings: [number, number, number] | [number, number, number, number]; /** only when components were asked for: each vertex's component, and (vertices, triangles) per component */ labels?: Uint32Array; componentSizes?: Uint32Array; /** only when an occlusion was asked for: 1 = open, per vertex (rm_mesh_occlusion) */ occlusion?: Float32Array }
 export const MESH_DEFAULTS: { iso: number; normals: 0 | 1; normalDelta: number; colours: 0 | 1; flags: number };
 export function meshGrid(lo: number[], hi: number[], n: number[]): MeshGrid;
 export function meshParams(params?: MeshParams | null): { iso: number; normals: 0 | 1; normalDelta: number; colours: 0 | 1; flags: number };
@@ -178,5 +180,9 @@ export function meshSimplify(simplify: MeshSimplify): { grid: MeshGrid; keepDupl
 export interface MeshQuadric { threshold?: number }
 export const MESH_QUADRIC_DEFAULTS: { threshold: number };
 export function meshQuadric(quadric?: MeshQuadric | null): { threshold: number };
-/** binary little-endian PLY (normals and uchar colours when present): the bytes the Python host's write_ply writes */
-export function encodePly(mesh: { positions: Float32Array; triangles: Uint32Array; normals?: Float32Array | null; colours?: Float32Array | null }): Buffer;
+/** the occlusion block of extractMesh (RmMeshOcclusion): `directions` (1, 2, 4 ... 64) directions over every vertex, `taps` (1, 2, 4, 8) taps along each, the first at `radius`; ao = 1 - strength * occlusion */
+export interface MeshOcclusion { radius?: number; directions?: number; taps?: number; normalDelta?: number; strength?: number; flags?: number }
+export const MESH_OCCLUSION_DEFAULTS: { radius: number; directions: number; taps: number; normalDelta: number; strength: number; flags: number };
+export function meshOcclusion(occlusion?: MeshOcclusion | null): { radius: number; directions: number; taps: number; normalDelta: number; strength: number; flags: number };
+/** binary little-endian PLY (normals, uchar colours and a float `quality` -- the occlusion -- when present): the bytes the Python host's write_ply writes */
+export function encodePly(mesh: { positions: Float32Array; triangles: Uint32Array; normals?: Float32Array | null; colours?: Float32Array | null; occlusion?: Float32Array | null }): Buffer;

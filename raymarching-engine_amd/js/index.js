@@ -363,9 +363,18 @@ class RenderJobContext {  // RenderJobContext + loadRenderJobContext (LoadRender
   // merged into one on the GPU (rm_mesh_simplify) before keep and components are applied; the result's cells index the cluster grid
   // quadric (with simplify only): undefined / null = that call; true or meshQuadric's options = rm_mesh_simplify_quadric, the same mesh with every
   // cluster's vertex at the minimiser of its plane quadrics
-  extractMesh(scene, grid, opts, sharp, keep, components, simplify = null, quadric = null) {
+  // occlusion: undefined / null = that mesh; true or meshOcclusion's options = occlusion (Float32Array(V), 1 = open) of the mesh that is returned,
+  // baked from the scene's distance field behind simplify, keep and components (rm_mesh_occlusion); its milliseconds are timings[3]
+  extractMesh(scene, grid, opts, sharp, keep, components, simplify = null, quadric = null, occlusion = null) {
     const q = quadric === undefined || quadric === null ? null : meshQuadric(quadric === true ? undefined : quadric);
     if (q !== null && (simplify === undefined || simplify === null)) throw new TypeError("mesh: quadric places the vertices of a simplification: give simplify as well");
+    if (occlusion !== undefined && occlusion !== null) {
+      const o = meshOcclusion(occlusion === true ? undefined : occlusion);
+      const s = sharp === undefined || sharp === null ? null : meshSharp(sharp === true ? undefined : sharp);
+      const k = keep === undefined || keep === null ? null : meshKeep(keep === true ? undefined : keep);
+      const c = simplify === undefined || simplify === null ? null : meshSimplify(simplify);
+      return addon.extractMesh(this.ctx, this.sceneHandle(scene), grid, meshParams(opts), s, k, !!components, c, q, o);
+    }
     if (simplify !== undefined && simplify !== null) {
       const s = sharp === undefined || sharp === null ? null : meshSharp(sharp === true ? undefined : sharp);
       const k = keep === undefined || keep === null ? null : meshKeep(keep === true ? undefined : keep);
@@ -747,15 +756,39 @@ function meshQuadric(opts) {
   return p;
 }
 
-// binary little-endian PLY of { positions, triangles, normals?, colours? }: x y z, then nx ny nz, then uchar red green blue
-// (floor(clamp(c, 0, 1) * 255 + 0.5), NaN as 0); faces as a uchar count and uint indices -- the bytes the Python host writes
+// the occlusion block of extractMesh (include/hip_raymarch.h RmMeshOcclusion): undefined / null = the defaults, or an object with some of radius
+// (the first tap's distance, in [2^-64, 2^64]), directions (1, 2, 4, ... 64), taps (1, 2, 4, 8), normalDelta (> 0), strength (in [0, 4]) and flags
+// (RM.RENDER_FAST, RM.RENDER_NO_CULL); checked as the library checks it
+const MESH_OCCLUSION_DEFAULTS = { radius: 0.25, directions: 16, taps: 4, normalDelta: 2 ** -10, strength: 1, flags: 0 };
+function meshOcclusion(opts) {
+  const p = { ...MESH_OCCLUSION_DEFAULTS };
+  if (opts !== undefined && opts !== null) {
+    if (typeof opts !== "object") throw new TypeError("mesh: expected an object of occlusion parameters");
+    for (const [k, v] of Object.entries(opts)) {
+      if (!(k in MESH_OCCLUSION_DEFAULTS)) throw new TypeError("mesh: unknown occlusion parameter " + k);
+      p[k] = v;
+    }
+  }
+  if (!finite(p.radius) || !(Math.fround(p.radius) >= 2 ** -64 && Math.fround(p.radius) <= 2 ** 64)) throw new RangeError("mesh: occlusion radius must be finite and in [2^-64, 2^64]");
+  if (![1, 2, 4, 8, 16, 32, 64].includes(p.directions)) throw new RangeError("mesh: occlusion directions must be one of 1, 2, 4, 8, 16, 32, 64");
+  if (![1, 2, 4, 8].includes(p.taps)) throw new RangeError("mesh: occlusion taps must be one of 1, 2, 4, 8");
+  if (!POSITIVE[0](p.normalDelta) || !POSITIVE[0](Math.fround(p.normalDelta))) throw new RangeError("mesh: occlusion normalDelta " + POSITIVE[1]);
+  if (!finite(p.strength) || !(Math.fround(p.strength) >= 0 && Math.fround(p.strength) <= 4)) throw new RangeError("mesh: occlusion strength must be finite and in [0, 4]");
+  if (!Number.isInteger(p.flags) || (p.flags & ~(RM.RENDER_FAST | RM.RENDER_NO_CULL)) !== 0) throw new RangeError("mesh: occlusion flags must be 0, RM.RENDER_FAST, RM.RENDER_NO_CULL or both");
+  return p;
+}
+
+// binary little-endian PLY of { positions, triangles, normals?, colours?, occlusion? }: x y z, then nx ny nz, then uchar red green blue
+// (floor(clamp(c, 0, 1) * 255 + 0.5), NaN as 0), then float quality (the occlusion); faces as a uchar count and uint indices -- the bytes the
+// Python host writes
 function encodePly(mesh) {
-  const V = mesh.positions.length / 3, T = mesh.triangles.length / 3, nrm = mesh.normals || null, col = mesh.colours || null;
+  const V = mesh.positions.length / 3, T = mesh.triangles.length / 3, nrm = mesh.normals || null, col = mesh.colours || null, occ = mesh.occlusion || null;
   const header = ["ply", "format binary_little_endian 1.0", "comment hip_raymarch mesh", "element vertex " + V, "property float x", "property float y", "property float z"];
   if (nrm) header.push("property float nx", "property float ny", "property float nz");
   if (col) header.push("property uchar red", "property uchar green", "property uchar blue");
+  if (occ) header.push("property float quality");
   header.push("element face " + T, "property list uchar uint vertex_indices", "end_header");
-  const head = Buffer.from(header.join("\n") + "\n", "ascii"), stride = 12 + (nrm ? 12 : 0) + (col ? 3 : 0);
+  const head = Buffer.from(header.join("\n") + "\n", "ascii"), stride = 12 + (nrm ? 12 : 0) + (col ? 3 : 0) + (occ ? 4 : 0);
   const out = Buffer.alloc(head.length + V * stride + T * 13);
   head.copy(out, 0);
   let at = head.length;
@@ -764,6 +797,7 @@ function encodePly(mesh) {
     for (let k = 0; k < 3; k++) { out.writeFloatLE(mesh.positions[3 * v + k], at); at += 4; }
     if (nrm) for (let k = 0; k < 3; k++) { out.writeFloatLE(nrm[3 * v + k], at); at += 4; }
     if (col) for (let k = 0; k < 3; k++) out[at++] = byte(col[3 * v + k]);
+    if (occ) { out.writeFloatLE(occ[v], at); at += 4; }
   }
   for (let t = 0; t < T; t++) {
     out[at++] = 3;
@@ -799,4 +833,4 @@ module.exports = { RM, addon, encodePng, Scene, CsgScene, Mandelbulb, singleSphe
                    tileRect, RenderJobContext, ShardedRenderJobContext, doRenderJob, U_OFFSET, DENOISE_DEFAULTS, denoiseParams,
                    DENOISE_VARIANCE_DEFAULTS, denoiseVarianceParams, DESPECKLE_DEFAULTS, despeckleParams, DISPLAY_DEFAULTS, AUTO_EXPOSURE_DEFAULTS,
                    displayParams, statsExposure, statsPercentile, MESH_DEFAULTS, meshGrid, meshParams, MESH_SHARP_DEFAULTS, meshSharp, MESH_KEEP_DEFAULTS, meshKeep,
-                   MESH_SIMPLIFY_DEFAULTS, meshSimplify, MESH_QUADRIC_DEFAULTS, meshQuadric, encodePly };
+                   MESH_SIMPLIFY_DEFAULTS, meshSimplify, MESH_QUADRIC_DEFAULTS, meshQuadric, MESH_OCCLUSION_DEFAULTS, meshOcclusion, encodePly };

@@ -604,6 +604,34 @@ static napi_value MeshQuadricBlock(napi_env env, napi_callback_info info) {
   return b;
 }
 
+static const Field MESH_OCCLUSION_FIELDS[] = {{"radius", Field::FLOAT, offsetof(RmMeshOcclusion, radius)}, {"directions", Field::INT, offsetof(RmMeshOcclusion, directions)},
+                                              {"taps", Field::INT, offsetof(RmMeshOcclusion, taps)}, {"normalDelta", Field::FLOAT, offsetof(RmMeshOcclusion, normal_delta)},
+                                              {"strength", Field::FLOAT, offsetof(RmMeshOcclusion, strength)}, {"flags", Field::INT, offsetof(RmMeshOcclusion, flags)}};
+// the occlusion block of extractMesh: null / undefined = none (*given = false), an object = rm_mesh_occlusion on the mesh that is returned, with
+// its fields over the defaults
+static bool get_mesh_occlusion(napi_env env, napi_value v, RmMeshOcclusion* o, bool* given) {
+  rm_mesh_occlusion_default(o);
+  return get_block(env, v, o, MESH_OCCLUSION_FIELDS, given);
+}
+
+// meshOcclusionBlock(occlusion | null) -> ArrayBuffer(RmMeshOcclusion): the bytes extractMesh hands to rm_mesh_occlusion (null: the defaults)
+static napi_value MeshOcclusionBlock(napi_env env, napi_callback_info info) {
+  size_t argc = 1;
+  napi_value argv[1];
+  NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+  RmMeshOcclusion o;
+  bool given = false;
+  if (argc != 1 || !get_mesh_occlusion(env, argv[0], &o, &given)) {
+    napi_throw_type_error(env, nullptr, "meshOcclusionBlock(occlusion | null)");
+    return nullptr;
+  }
+  napi_value b;
+  void* d = nullptr;
+  NAPI_OK(napi_create_arraybuffer(env, sizeof o, &d, &b));
+  std::memcpy(d, &o, sizeof o);
+  return b;
+}
+
 static napi_value make_array(napi_env env, napi_typedarray_type type, size_t count, void** data) {
   napi_value ab, out;
   if (napi_create_arraybuffer(env, count * 4, data, &ab) != napi_ok || napi_create_typedarray(env, type, count, ab, 0, &out) != napi_ok) return nullptr;
@@ -662,9 +690,11 @@ static napi_value SdfGrid(napi_env env, napi_callback_info info) {
 // meshing, attributes] in ms (rm_mesh_timings) }; normals / colours: whether the call asked for them; the handle is destroyed.  keep: the mesh is
 // first filtered on the device (rm_mesh_filter) and the filtered one is what is copied; components: labels: Uint32Array(V) and componentSizes:
 // Uint32Array(2 C) come with it (rm_mesh_components).  simplify: before either, the mesh is clustered on the device (rm_mesh_simplify), so one
-// filter also removes the vertices the clustering left without triangles; with quadric by rm_mesh_simplify_quadric
+// filter also removes the vertices the clustering left without triangles; with quadric by rm_mesh_simplify_quadric.  occlusion (with the scene):
+// occlusion: Float32Array(V) of the mesh that is returned comes with it (rm_mesh_occlusion), and its milliseconds (probes + taps) as timings[3]
 static napi_value mesh_result(napi_env env, rm_ctx* ctx, rm_mesh* mesh, bool normals, bool colours, const RmMeshKeep* keep = nullptr, bool components = false,
-                              const MeshSimplifyBlock* simplify = nullptr, const RmMeshQuadric* quadric = nullptr) {
+                              const MeshSimplifyBlock* simplify = nullptr, const RmMeshQuadric* quadric = nullptr, rm_scene* scene = nullptr,
+                              const RmMeshOcclusion* occlusion = nullptr) {
   struct Guard {  // the handle in hand is destroyed on every way out
     rm_mesh* h;
     ~Guard() { rm_mesh_destroy(h); }
@@ -714,11 +744,21 @@ static napi_value mesh_result(napi_env env, rm_ctx* ctx, rm_mesh* mesh, bool nor
     }
     if (napi_set_named_property(env, o, a.name, v) != napi_ok) return napi_failed();
   }
-  float ms[3] = {0.0f, 0.0f, 0.0f};
+  float ms[4] = {0.0f, 0.0f, 0.0f, 0.0f};
   rm_mesh_timings(mesh, ms);
+  if (occlusion) {
+    napi_value v = nullptr;
+    void* data = nullptr;
+    float ms2[2] = {0.0f, 0.0f};
+    if (!(v = make_array(env, napi_float32_array, (size_t)counts[0], &data))) return napi_failed();
+    if (rm_mesh_occlusion(mesh, scene, occlusion, static_cast<float*>(data), ms2) != RM_OK) return throw_rm(env, ctx, "rm_mesh_occlusion");
+    if (napi_set_named_property(env, o, "occlusion", v) != napi_ok) return napi_failed();
+    ms[3] = ms2[0] + ms2[1];
+  }
+  const uint32_t spans = occlusion ? 4u : 3u;
   napi_value timings = nullptr;
-  if (napi_create_array_with_length(env, 3, &timings) != napi_ok) return napi_failed();
-  for (uint32_t k = 0; k < 3; k++) {
+  if (napi_create_array_with_length(env, spans, &timings) != napi_ok) return napi_failed();
+  for (uint32_t k = 0; k < spans; k++) {
     napi_value x;
     if (napi_create_double(env, (double)ms[k], &x) != napi_ok || napi_set_element(env, timings, k, x) != napi_ok) return napi_failed();
   }
@@ -726,14 +766,15 @@ static napi_value mesh_result(napi_env env, rm_ctx* ctx, rm_mesh* mesh, bool nor
   return o;
 }
 
-// extractMesh(ctx, scene, grid, params | null[, sharp | null[, keep | null[, components[, simplify | null[, quadric | null]]]]]) = rm_mesh_extract, or
+// extractMesh(ctx, scene, grid, params | null[, sharp | null[, keep | null[, components[, simplify | null[, quadric | null[, occlusion | null]]]]]]) = rm_mesh_extract, or
 // with a sharp block rm_mesh_extract_sharp; with a simplify block rm_mesh_simplify behind it (with a quadric block too: rm_mesh_simplify_quadric);
-// with a keep block rm_mesh_filter behind that; then the arrays.  A quadric block without a simplify block is refused.
+// with a keep block rm_mesh_filter behind that; then the arrays, with an occlusion block rm_mesh_occlusion on that last mesh.  A quadric block
+// without a simplify block is refused.
 static napi_value ExtractMesh(napi_env env, napi_callback_info info) {
-  size_t argc = 9;
-  napi_value argv[9];
+  size_t argc = 10;
+  napi_value argv[10];
   NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
-  const bool counted = argc >= 4 && argc <= 9;
+  const bool counted = argc >= 4 && argc <= 10;
   rm_ctx* ctx = counted ? get_external<rm_ctx>(env, argv[0]) : nullptr;
   rm_scene* scene = counted ? get_external<rm_scene>(env, argv[1]) : nullptr;
   RmGrid g;
@@ -742,18 +783,20 @@ static napi_value ExtractMesh(napi_env env, napi_callback_info info) {
   RmMeshKeep k;
   MeshSimplifyBlock c;
   RmMeshQuadric q;
-  bool sharp = false, keep = false, components = false, simplify = false, quadric = false;
+  RmMeshOcclusion ao;
+  bool sharp = false, keep = false, components = false, simplify = false, quadric = false, occlusion = false;
   if (!ctx || !scene || !get_grid(env, argv[2], &g) || !get_mesh_params(env, argv[3], &p) || (argc >= 5 && !get_mesh_sharp(env, argv[4], &s, &sharp)) ||
       (argc >= 6 && !get_mesh_keep(env, argv[5], &k, &keep)) || (argc >= 7 && !get_bool(env, argv[6], &components)) ||
-      (argc >= 8 && !get_mesh_simplify(env, argv[7], &c, &simplify)) || (argc == 9 && !get_mesh_quadric(env, argv[8], &q, &quadric)) || (quadric && !simplify)) {
-    napi_throw_type_error(env, nullptr, "extractMesh(ctx, scene, grid, params | null[, sharp | null[, keep | null[, components[, simplify | null[, quadric | null]]]]])");
+      (argc >= 8 && !get_mesh_simplify(env, argv[7], &c, &simplify)) || (argc >= 9 && !get_mesh_quadric(env, argv[8], &q, &quadric)) || (argc == 10 && !get_mesh_occlusion(env, argv[9], &ao, &occlusion)) || (quadric && !simplify)) {
+    napi_throw_type_error(env, nullptr, "extractMesh(ctx, scene, grid, params | null[, sharp | null[, keep | null[, components[, simplify | null[, quadric | null[, occlusion | null]]]]]])");
     return nullptr;
   }
   rm_mesh* mesh = nullptr;
   if (sharp) {
     if (rm_mesh_extract_sharp(ctx, scene, &g, &p, &s, &mesh) != RM_OK) return throw_rm(env, ctx, "rm_mesh_extract_sharp");
   } else if (rm_mesh_extract(ctx, scene, &g, &p, &mesh) != RM_OK) return throw_rm(env, ctx, "rm_mesh_extract");
-  return mesh_result(env, ctx, mesh, p.normals != 0, p.colours != 0, keep ? &k : nullptr, components, simplify ? &c : nullptr, quadric ? &q : nullptr);
+  return mesh_result(env, ctx, mesh, p.normals != 0, p.colours != 0, keep ? &k : nullptr, components, simplify ? &c : nullptr, quadric ? &q : nullptr, scene,
+                     occlusion ? &ao : nullptr);
 }
 
 // meshFromValues(ctx, grid, values: Float32Array(corners), iso[, keep | null[, components[, simplify | null[, quadric | null]]]]) = rm_mesh_from_values,
@@ -985,7 +1028,7 @@ static napi_value Sizes(napi_env env, napi_callback_info) {
       {"RmMaterial", (uint32_t)sizeof(RmMaterial)}, {"RmRect", (uint32_t)sizeof(RmRect)}, {"RmSurface", (uint32_t)sizeof(RmSurface)}, {"RmDenoise", (uint32_t)sizeof(RmDenoise)},
       {"RmDenoiseVariance", (uint32_t)sizeof(RmDenoiseVariance)}, {"RmDespeckle", (uint32_t)sizeof(RmDespeckle)}, {"RmFilters", (uint32_t)sizeof(RmFilters)}, {"RmFrameStats", (uint32_t)sizeof(RmFrameStats)},
       {"RmAutoExposure", (uint32_t)sizeof(RmAutoExposure)}, {"RmDisplay", (uint32_t)sizeof(RmDisplay)}, {"RmGrid", (uint32_t)sizeof(RmGrid)},
-      {"RmMeshParams", (uint32_t)sizeof(RmMeshParams)}, {"RmMeshSharp", (uint32_t)sizeof(RmMeshSharp)}, {"RmMeshKeep", (uint32_t)sizeof(RmMeshKeep)}, {"RmMeshSimplify", (uint32_t)sizeof(RmMeshSimplify)}, {"RmMeshQuadric", (uint32_t)sizeof(RmMeshQuadric)}, {"abi", (uint32_t)rm_abi_version()}};
+      {"RmMeshParams", (uint32_t)sizeof(RmMeshParams)}, {"RmMeshSharp", (uint32_t)sizeof(RmMeshSharp)}, {"RmMeshKeep", (uint32_t)sizeof(RmMeshKeep)}, {"RmMeshSimplify", (uint32_t)sizeof(RmMeshSimplify)}, {"RmMeshQuadric", (uint32_t)sizeof(RmMeshQuadric)}, {"RmMeshOcclusion", (uint32_t)sizeof(RmMeshOcclusion)}, {"abi", (uint32_t)rm_abi_version()}};
   for (const auto& it : items) {
     NAPI_OK(napi_create_uint32(env, it.v, &v));
     NAPI_OK(napi_set_named_property(env, o, it.k, v));
@@ -998,7 +1041,7 @@ static napi_value Init(napi_env env, napi_value exports) {
       {"ctxCreate", CtxCreate}, {"ctxDestroy", CtxDestroy}, {"sync", Sync}, {"sceneCreate", SceneCreate}, {"sceneDestroy", SceneDestroy},
       {"fbCreate", FbCreate}, {"fbClear", FbClear}, {"fbDestroy", FbDestroy}, {"fbDownload", FbDownload}, {"present", Present}, {"denoise", Denoise}, {"presentDenoised", PresentDenoised}, {"denoiseVariance", DenoiseVariance}, {"presentDenoisedVariance", PresentDenoisedVariance}, {"filter", Filter}, {"presentFiltered", PresentFiltered}, {"presentDisplay", PresentDisplay}, {"presentLinear", PresentLinear}, {"frameStats", FrameStats}, {"statsExposure", StatsExposure}, {"statsPercentile", StatsPercentile}, {"renderSample", RenderSample}, {"renderSamples", RenderSamples},
       {"fbCreateStriped", FbCreateStriped}, {"fbRows", FbRows}, {"setSamplesInFlight", SetSamplesInFlight}, {"presentSharded", PresentSharded}, {"presentShardedStart", PresentShardedStart}, {"presentShardedFinish", PresentShardedFinish},
-      {"meshBlocks", MeshBlocks}, {"meshSharpBlock", MeshSharpBlock}, {"meshKeepBlock", MeshKeepBlock}, {"meshSimplifyBlock", MeshSimplifyBlockOf}, {"meshQuadricBlock", MeshQuadricBlock}, {"sdfGrid", SdfGrid}, {"extractMesh", ExtractMesh}, {"meshFromValues", MeshFromValues}, {"sizes", Sizes}};
+      {"meshBlocks", MeshBlocks}, {"meshSharpBlock", MeshSharpBlock}, {"meshKeepBlock", MeshKeepBlock}, {"meshSimplifyBlock", MeshSimplifyBlockOf}, {"meshQuadricBlock", MeshQuadricBlock}, {"meshOcclusionBlock", MeshOcclusionBlock}, {"sdfGrid", SdfGrid}, {"extractMesh", ExtractMesh}, {"meshFromValues", MeshFromValues}, {"sizes", Sizes}};
   for (const auto& f : fns) {
     napi_value fn;
     if (napi_create_function(env, f.name, NAPI_AUTO_LENGTH, f.fn, nullptr, &fn) != napi_ok) return nullptr;

@@ -3,7 +3,7 @@
 from __future__ import annotations
 
 import math
-from dataclasses import dataclass
+from dataclasses import dataclass, replace
 from typing import Optional
 
 import numpy as np
@@ -136,11 +136,43 @@ def mesh_quadric(threshold=abi.MESH_QUADRIC_DEFAULTS["threshold"]) -> abi.RmMesh
     return abi.RmMeshQuadric(threshold=float(threshold))
 
 
+def mesh_occlusion(**fields) -> abi.RmMeshOcclusion:
+    """The abi.RmMeshOcclusion of Context.extract_mesh(..., occlusion=...), over abi.MESH_OCCLUSION_DEFAULTS: radius (the first tap's distance,
+    in [2^-64, 2^64]), directions (1, 2, 4, ... 64 over every vertex), taps (1, 2, 4 or 8 along each, halving the distance), normal_delta (the
+    step of the normal that gives the frame, > 0), strength (ao = 1 - strength * occlusion, in [0, 4]) and flags (rm_sdf_grid's).  Checked as
+    the library checks it: ValueError otherwise, and for unknown keys."""
+    unknown = set(fields) - set(abi.MESH_OCCLUSION_DEFAULTS)
+    if unknown:
+        raise ValueError(f"mesh: unknown occlusion parameter {sorted(unknown)[0]}")
+    p = {**abi.MESH_OCCLUSION_DEFAULTS, **fields}
+    for name in ("radius", "normal_delta", "strength"):
+        if isinstance(p[name], bool) or not isinstance(p[name], (int, float, np.integer, np.floating)):
+            raise ValueError(f"mesh: occlusion {name} must be a number")
+    with np.errstate(over="ignore"):
+        radius, delta, strength = np.float32(p["radius"]), np.float32(p["normal_delta"]), np.float32(p["strength"])
+    if not (math.isfinite(radius) and 2.0 ** -64 <= radius <= 2.0 ** 64):
+        raise ValueError("mesh: occlusion radius must be finite and in [2^-64, 2^64]")
+    for name, allowed in (("directions", (1, 2, 4, 8, 16, 32, 64)), ("taps", (1, 2, 4, 8))):
+        v = p[name]
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or int(v) not in allowed:
+            raise ValueError(f"mesh: occlusion {name} must be one of {', '.join(str(a) for a in allowed)}")
+    if not (math.isfinite(delta) and delta > 0):
+        raise ValueError("mesh: occlusion normal_delta must be finite and > 0")
+    if not (math.isfinite(strength) and 0 <= strength <= 4):
+        raise ValueError("mesh: occlusion strength must be finite and in [0, 4]")
+    flags = p["flags"]
+    if isinstance(flags, bool) or not isinstance(flags, (int, np.integer)) or int(flags) & ~(abi.RM_RENDER_FAST | abi.RM_RENDER_NO_CULL):
+        raise ValueError("mesh: occlusion flags must be 0, RM_RENDER_FAST, RM_RENDER_NO_CULL or both")
+    return abi.RmMeshOcclusion(radius=float(p["radius"]), directions=int(p["directions"]), taps=int(p["taps"]), normal_delta=float(p["normal_delta"]),
+                               strength=float(p["strength"]), flags=int(flags))
+
+
 @dataclass
 class Mesh:
     """A triangle mesh as numpy arrays: positions [V, 3] float32, triangles [T, 3] uint32 (counter-clockwise seen from outside), cells
     [V] uint32 (each vertex's linear cell index in `grid`), and normals / colours [V, 3] float32 or None.  labels [V] uint32 (each vertex's
-    connected component) and component_sizes [C, 2] uint32 ((vertices, triangles) per component) only when the call asked for components."""
+    connected component) and component_sizes [C, 2] uint32 ((vertices, triangles) per component) only when the call asked for components.
+    occlusion [V] float32 (1 = open; rm_mesh_occlusion) only when the call asked for it."""
     positions: np.ndarray
     triangles: np.ndarray
     cells: Optional[np.ndarray] = None
@@ -150,10 +182,33 @@ class Mesh:
     timings: Optional[dict] = None  # rm_mesh_timings: milliseconds of sampling, meshing, attributes (device events)
     labels: Optional[np.ndarray] = None
     component_sizes: Optional[np.ndarray] = None
+    occlusion = None  # Optional[np.ndarray]; an attribute that the constructor takes by keyword (below): the dataclass's own fields stay as they were
 
     @property
     def vertices(self) -> int:
         return len(self.positions)
+
+
+def _with_occlusion(init):
+    def __init__(self, *args, occlusion=None, **fields):
+        init(self, *args, **fields)
+        self.occlusion = occlusion
+
+    __init__.__doc__, __init__.__wrapped__ = init.__doc__, init
+    return __init__
+
+
+Mesh.__init__ = _with_occlusion(Mesh.__init__)
+
+
+def shaded(mesh: Mesh) -> Mesh:
+    """A copy of the mesh whose colours are multiplied by its occlusion (fp32); a mesh without colours gets grey: the occlusion in all
+    three channels.  ValueError for a mesh without an occlusion."""
+    if mesh.occlusion is None:
+        raise ValueError("mesh: shaded needs a mesh with an occlusion (extract_mesh(..., occlusion=...))")
+    ao = np.asarray(mesh.occlusion, np.float32)[:, None]
+    base = np.ones((mesh.vertices, 3), np.float32) if mesh.colours is None else np.asarray(mesh.colours, np.float32)
+    return replace(mesh, colours=base * ao, occlusion=mesh.occlusion)
 
 
 def _number(v) -> str:
@@ -179,8 +234,8 @@ def colour_bytes(colours: np.ndarray) -> np.ndarray:
 
 
 def encode_ply(mesh: Mesh) -> bytes:
-    """Binary little-endian PLY: x y z, then nx ny nz when the mesh has normals, then uchar red green blue when it has colours;
-    faces as a uchar count and uint indices."""
+    """Binary little-endian PLY: x y z, then nx ny nz when the mesh has normals, then uchar red green blue when it has colours, then
+    float quality when it has an occlusion; faces as a uchar count and uint indices."""
     fields = [("x", "<f4"), ("y", "<f4"), ("z", "<f4")]
     header = ["ply", "format binary_little_endian 1.0", "comment hip_raymarch mesh", "element vertex %d" % mesh.vertices,
               "property float x", "property float y", "property float z"]
@@ -190,6 +245,9 @@ def encode_ply(mesh: Mesh) -> bytes:
     if mesh.colours is not None:
         fields += [("red", "u1"), ("green", "u1"), ("blue", "u1")]
         header += ["property uchar red", "property uchar green", "property uchar blue"]
+    if mesh.occlusion is not None:
+        fields += [("quality", "<f4")]
+        header += ["property float quality"]
     header += ["element face %d" % len(mesh.triangles), "property list uchar uint vertex_indices", "end_header"]
     v = np.zeros(mesh.vertices, np.dtype(fields))
     for k, name in enumerate("xyz"):
@@ -200,6 +258,8 @@ def encode_ply(mesh: Mesh) -> bytes:
         rgb = colour_bytes(mesh.colours)
         for k, name in enumerate(("red", "green", "blue")):
             v[name] = rgb[:, k]
+    if mesh.occlusion is not None:
+        v["quality"] = mesh.occlusion
     f = np.zeros(len(mesh.triangles), np.dtype([("count", "u1"), ("a", "<u4"), ("b", "<u4"), ("c", "<u4")]))
     f["count"] = 3
     for k, name in enumerate("abc"):

@@ -44,6 +44,7 @@ EXPORTS = [
     "rm_mesh_download", "rm_mesh_device_ptr", "rm_mesh_destroy", "rm_mesh_sharp_default", "rm_mesh_extract_sharp",
     "rm_mesh_keep_default", "rm_mesh_components", "rm_mesh_components_download", "rm_mesh_filter",
     "rm_mesh_simplify_default", "rm_mesh_simplify", "rm_mesh_quadric_default", "rm_mesh_simplify_quadric",
+    "rm_mesh_occlusion_default", "rm_mesh_occlusion_directions", "rm_mesh_occlusion",
 ]
 
 # G-buffer formats of a framebuffer (include/hip_raymarch.h RM_GBUFFER_*): "f32" (the default: the software GL stack's planes, which the
@@ -420,6 +421,9 @@ def load_library(path=None):
         "rm_mesh_simplify": (ip, [vp, C.POINTER(abi.RmGrid), C.POINTER(abi.RmMeshSimplify), C.POINTER(vp)]),
         "rm_mesh_quadric_default": (None, [C.POINTER(abi.RmMeshQuadric)]),
         "rm_mesh_simplify_quadric": (ip, [vp, C.POINTER(abi.RmGrid), C.POINTER(abi.RmMeshSimplify), C.POINTER(abi.RmMeshQuadric), C.POINTER(vp)]),
+        "rm_mesh_occlusion_default": (None, [C.POINTER(abi.RmMeshOcclusion)]),
+        "rm_mesh_occlusion_directions": (ip, [ip, fp]),
+        "rm_mesh_occlusion": (ip, [vp, vp, C.POINTER(abi.RmMeshOcclusion), fp, fp]),
     }
     for name, (res, args) in sig.items():
         if name.startswith("rm_debug_") and not hasattr(lib, name) and os.environ.get("RM_LIB"):
@@ -716,11 +720,13 @@ class Context:
         g = grid.to_c()
         self._check(self.lib.rm_sdf_grid_device(self.h, scene.h, C.byref(g), int(flags), C.c_void_p(out_ptr), C.c_void_p(stream) if stream else None))
 
-    def _take_mesh(self, handle, grid, normals=False, colours=False, keep=None, components=False, simplify=None, quadric=None):
+    def _take_mesh(self, handle, grid, normals=False, colours=False, keep=None, components=False, simplify=None, quadric=None, scene=None, occlusion=None):
         """The arrays of a mesh handle as a mesh.Mesh (normals / colours: whether the call that made it asked for them); destroys the handle.
         simplify (_mesh_simplify's triple): the mesh is first clustered on the device (rm_mesh_simplify) and the Mesh's grid is the cluster grid,
         which its cells then index -- with quadric (an abi.RmMeshQuadric) by rm_mesh_simplify_quadric; keep (an abi.RmMeshKeep): that mesh is filtered on the device (rm_mesh_filter), which also removes the vertices
-        simplification left without triangles; the last of them is what is downloaded.  components: its labels and component sizes come with it."""
+        simplification left without triangles; the last of them is what is downloaded.  components: its labels and component sizes come with it.
+        occlusion (an abi.RmMeshOcclusion, with the scene): that last mesh's ambient occlusion comes with it (rm_mesh_occlusion), and the
+        timings gain "occlusion", the milliseconds of its probes and taps."""
         from .mesh import Mesh
 
         handles = [handle]
@@ -761,7 +767,13 @@ class Context:
                     a = np.empty(shape, np.uint32)
                     self._check(self.lib.rm_mesh_components_download(handle, what, a.ctypes.data_as(C.c_void_p), a.nbytes))
                     arrays[name] = a
-            return Mesh(grid=grid, timings=dict(sampling=float(ms[0]), meshing=float(ms[1]), attributes=float(ms[2])), **arrays)
+            timings = dict(sampling=float(ms[0]), meshing=float(ms[1]), attributes=float(ms[2]))
+            if occlusion is not None:
+                ao, ms2 = np.empty(v, np.float32), (C.c_float * 2)()
+                self._check(self.lib.rm_mesh_occlusion(handle, scene.h, C.byref(occlusion), _fp(ao), ms2))
+                arrays["occlusion"] = ao
+                timings["occlusion"] = float(ms2[0]) + float(ms2[1])
+            return Mesh(grid=grid, timings=timings, **arrays)
         finally:
             for h in reversed(handles):
                 self.lib.rm_mesh_destroy(h)
@@ -788,6 +800,11 @@ class Context:
     @staticmethod
     def _mesh_keep(keep):
         return Context._mesh_block("keep", keep, abi.RmMeshKeep)
+
+    @staticmethod
+    def _mesh_occlusion(occlusion):
+        """The `occlusion` of extract_mesh as an abi.RmMeshOcclusion (_mesh_block's rules)."""
+        return Context._mesh_block("occlusion", occlusion, abi.RmMeshOcclusion)
 
     @staticmethod
     def _mesh_quadric(quadric, simplify):
@@ -824,7 +841,7 @@ class Context:
         raise ValueError("mesh: simplify must be None, a mesh.Grid, a dict of mesh_simplify's arguments or its (abi.RmGrid, abi.RmMeshSimplify)")
 
     def extract_mesh(self, scene: "SceneHandle", grid, iso: float = 0.0, normals: bool = True, colours: bool = False, flags: int = 0,
-                     normal_delta: float = 1e-5, sharp=None, *, keep=None, components: bool = False, simplify=None, quadric=None):
+                     normal_delta: float = 1e-5, sharp=None, *, keep=None, components: bool = False, simplify=None, quadric=None, occlusion=None):
         """The level set `iso` of the scene on `grid` (mesh.Grid) as a mesh.Mesh: rm_mesh_extract -- the distances sampled and meshed
         (surface nets) on the device, with per-vertex normals / diffuse colours from the scene's probes when asked for.  `sharp`: None is
         that call; True (the defaults), a dict of mesh.mesh_sharp's arguments or an abi.RmMeshSharp is rm_mesh_extract_sharp -- the same
@@ -835,10 +852,14 @@ class Context:
         mesh.mesh_simplify's arguments or its pair merges the vertices of every cluster cell into one on the device (rm_mesh_simplify) before
         `keep` and `components` are applied, and the returned mesh's grid is the cluster grid.  `quadric` (with `simplify` only): None is
         that call; True (the defaults), a dict of mesh.mesh_quadric's arguments or an abi.RmMeshQuadric is rm_mesh_simplify_quadric -- the same
-        mesh with every cluster's vertex at the minimiser of its plane quadrics, which keeps the edges and corners inside a cluster."""
+        mesh with every cluster's vertex at the minimiser of its plane quadrics, which keeps the edges and corners inside a cluster.
+        `occlusion`: None is that mesh; True (the defaults), a dict of mesh.mesh_occlusion's arguments or an abi.RmMeshOcclusion bakes the
+        scene's ambient occlusion at the vertices of the mesh that is returned -- behind `simplify`, `keep` and `components` -- into
+        Mesh.occlusion (rm_mesh_occlusion; 1 = open), which encode_ply writes as `quality` and mesh.shaded multiplies into the colours."""
         from .mesh import mesh_params
 
         keep, simplify, quadric = self._mesh_keep(keep), self._mesh_simplify(simplify), self._mesh_quadric(quadric, simplify)  # (refused before anything runs)
+        occlusion = self._mesh_occlusion(occlusion)
         g, p = grid.to_c(), mesh_params(iso=iso, normals=normals, colours=colours, flags=flags, normal_delta=normal_delta)
         h = C.c_void_p()
         s = self._mesh_block("sharp", sharp, abi.RmMeshSharp)
@@ -846,7 +867,8 @@ class Context:
             self._check(self.lib.rm_mesh_extract(self.h, scene.h, C.byref(g), C.byref(p), C.byref(h)))
         else:
             self._check(self.lib.rm_mesh_extract_sharp(self.h, scene.h, C.byref(g), C.byref(p), C.byref(s), C.byref(h)))
-        return self._take_mesh(h, grid, normals=p.normals, colours=p.colours, keep=keep, components=components, simplify=simplify, quadric=quadric)
+        return self._take_mesh(h, grid, normals=p.normals, colours=p.colours, keep=keep, components=components, simplify=simplify, quadric=quadric,
+                               scene=scene, occlusion=occlusion)
 
     def mesh_from_values(self, grid, values: np.ndarray, iso: float = 0.0, *, keep=None, components: bool = False, simplify=None, quadric=None):
         """The mesher alone on the caller's field: `values` float32 [nz + 1, ny + 1, nx + 1] (rm_mesh_from_values).  keep, components,
