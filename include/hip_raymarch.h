@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define RM_ABI_VERSION 9 /* 9: RM_GBUFFER_F32 / _F16, rm_fb_create_fmt, rm_fb_create_striped_fmt, rm_fb_wrap_fmt, rm_fb_gbuffer, rm_fb_download_raw, rm_fb_upload_raw, RmDenoise, rm_denoise_default, rm_denoise, rm_denoise_device, rm_present_denoised, RM_FB_MOMENTS, RM_PLANE_MOMENTS, rm_fb_has_moments, RmDenoiseVariance, rm_denoise_variance_default, rm_denoise_variance, rm_denoise_variance_device, rm_present_denoised_variance, RmDespeckle, RmFilters, RM_DENOISE_NONE / _ATROUS / _VARIANCE, rm_filters_default, rm_filter, rm_filter_device, rm_present_filtered, RM_STATS_BINS, RmFrameStats, rm_frame_stats, RmAutoExposure, rm_auto_exposure_default, rm_stats_percentile, rm_stats_exposure, RM_TONE_CLIP / _REINHARD / _ACES, RmDisplay, rm_display_default, rm_present_display, rm_present_display_device, rm_present_linear, RmGrid, rm_grid_axis, rm_sdf_grid, rm_sdf_grid_device, RmMeshParams, rm_mesh_params_default, rm_mesh, rm_mesh_extract, rm_mesh_from_values, rm_mesh_counts, rm_mesh_timings, RM_MESH_POSITIONS / _NORMALS / _COLOURS / _TRIANGLES / _CELLS, rm_mesh_download, rm_mesh_device_ptr, rm_mesh_destroy, RmMeshSharp, rm_mesh_sharp_default, rm_mesh_extract_sharp, RmMeshKeep, rm_mesh_keep_default, rm_mesh_components, RM_MESH_PART_LABELS / _SIZES, rm_mesh_components_download, rm_mesh_filter, RmMeshSimplify, rm_mesh_simplify_default, rm_mesh_simplify, RmMeshQuadric, rm_mesh_quadric_default, rm_mesh_simplify_quadric, RmMeshOcclusion, rm_mesh_occlusion_default, rm_mesh_occlusion_directions, rm_mesh_occlusion (additions only); 8: RM_PRIM_TORUS / _CYLINDER / _PLANE, RM_OP_SMOOTH_SUBTRACT / _INTERSECT, rm_probe_math (additions only); 7: rm_present_sharded_finish / rm_present_sharded take the size of the host buffer (a changed signature), rm_ctx_set_cull_min_pixels, rm_ctx_set_cull_budget, rm_ctx_cull_stats; 6: rm_present_striped_rows, rm_present_sharded_start / _finish, rm_ctx_last_warning, RM_PROBE_CAST_SHADOW, RM_PRIM_KIND (additions only); 3: rm_ctx_set_sample_batch, rm_buffer_*; 4: rm_ctx_set_gl_stack; 5: RmSurface / RmSceneDesc.surfaces (the struct grew), rm_pack_present_rows, rm_present_sharded, rm_ctx_last_pipeline, RM_RENDER_NO_FAR_JUMP, RM_RENDER_NO_CULL (additions only) */
+#define RM_ABI_VERSION 9 /* 9: RM_GBUFFER_F32 / _F16, rm_fb_create_fmt, rm_fb_create_striped_fmt, rm_fb_wrap_fmt, rm_fb_gbuffer, rm_fb_download_raw, rm_fb_upload_raw, RmDenoise, rm_denoise_default, rm_denoise, rm_denoise_device, rm_present_denoised, RM_FB_MOMENTS, RM_PLANE_MOMENTS, rm_fb_has_moments, RmDenoiseVariance, rm_denoise_variance_default, rm_denoise_variance, rm_denoise_variance_device, rm_present_denoised_variance, RmDespeckle, RmFilters, RM_DENOISE_NONE / _ATROUS / _VARIANCE, rm_filters_default, rm_filter, rm_filter_device, rm_present_filtered, RM_STATS_BINS, RmFrameStats, rm_frame_stats, RmAutoExposure, rm_auto_exposure_default, rm_stats_percentile, rm_stats_exposure, RM_TONE_CLIP / _REINHARD / _ACES, RmDisplay, rm_display_default, rm_present_display, rm_present_display_device, rm_present_linear, RmGrid, rm_grid_axis, rm_sdf_grid, rm_sdf_grid_device, RmMeshParams, rm_mesh_params_default, rm_mesh, rm_mesh_extract, rm_mesh_from_values, rm_mesh_counts, rm_mesh_timings, RM_MESH_POSITIONS / _NORMALS / _COLOURS / _TRIANGLES / _CELLS, rm_mesh_download, rm_mesh_device_ptr, rm_mesh_destroy, RmMeshSharp, rm_mesh_sharp_default, rm_mesh_extract_sharp, RmMeshKeep, rm_mesh_keep_default, rm_mesh_components, RM_MESH_PART_LABELS / _SIZES, rm_mesh_components_download, rm_mesh_filter, RmMeshSimplify, rm_mesh_simplify_default, rm_mesh_simplify, RmMeshQuadric, rm_mesh_quadric_default, rm_mesh_simplify_quadric, RmMeshOcclusion, rm_mesh_occlusion_default, rm_mesh_occlusion_directions, rm_mesh_occlusion, RmMeshMeasures, rm_mesh_measure, rm_mesh_measure_components (additions only); 8: RM_PRIM_TORUS / _CYLINDER / _PLANE, RM_OP_SMOOTH_SUBTRACT / _INTERSECT, rm_probe_math (additions only); 7: rm_present_sharded_finish / rm_present_sharded take the size of the host buffer (a changed signature), rm_ctx_set_cull_min_pixels, rm_ctx_set_cull_budget, rm_ctx_cull_stats; 6: rm_present_striped_rows, rm_present_sharded_start / _finish, rm_ctx_last_warning, RM_PROBE_CAST_SHADOW, RM_PRIM_KIND (additions only); 3: rm_ctx_set_sample_batch, rm_buffer_*; 4: rm_ctx_set_gl_stack; 5: RmSurface / RmSceneDesc.surfaces (the struct grew), rm_pack_present_rows, rm_present_sharded, rm_ctx_last_pipeline, RM_RENDER_NO_FAR_JUMP, RM_RENDER_NO_CULL (additions only) */
 
 #define RM_MAX_BOUNCES 10 /* raymarchingStepCountsArray[10], raymarcher.frag:31 */
 #define RM_MAX_LIGHTS 10  /* lightPositions[10],             raymarcher.frag:37-39 */
@@ -1120,6 +1120,74 @@ typedef struct RmMeshOcclusion {
 RM_API void rm_mesh_occlusion_default(RmMeshOcclusion* params);
 RM_API int rm_mesh_occlusion_directions(int directions, float* out);
 RM_API int rm_mesh_occlusion(rm_mesh* mesh, rm_scene* scene, const RmMeshOcclusion* params, float* out_host, float* out_ms2);
+
+/* ---- measures and edge topology (opt-in): is the mesh closed and oriented, how many edges are open, its area, volume and extent ----
+ * What a caller who exports a mesh asks of it: rm_mesh_simplify has "no care for manifoldness", an extraction whose grid cuts the surface
+ * leaves open borders, a fractal level set is one body plus specks.  rm_mesh_measure answers on the device, without a download.  It works
+ * on any rm_mesh (rm_mesh_extract, _sharp, _from_values, rm_mesh_filter, rm_mesh_simplify, _quadric) and changes nothing of the mesh; the
+ * result is kept with the mesh once made, as the labelling is (a mesh's arrays never change): a second call returns the stored bytes.
+ * For V vertices and T triangles:
+ *   Participating triangles.  A triangle PARTICIPATES iff its three indices are < V and pairwise distinct; skipped_triangles counts the
+ *     others (no mesh of this library has one; the kernels read nothing but the three indices of such a triangle).  P = the participating ones.
+ *   Edges.  A participating triangle (a, b, c) uses the directed edges a->b, b->c, c->a.  The undirected edge {x, y}, x < y, has f uses as
+ *     x->y and r uses as y->x.  edges = E = the undirected edges with f + r >= 1.  An edge is BOUNDARY iff f + r = 1; REGULAR iff f = 1 and
+ *     r = 1; otherwise IRREGULAR (three or more uses, or two in the same direction).  It is UNBALANCED iff f + r >= 2 and f != r: the places
+ *     where the orientation disagrees, a subset of the irregular edges.  boundary + regular + irregular = E.
+ *   Topology.  used_vertices counts the vertices named by at least one participating triangle.  euler = used_vertices - E + P.
+ *     closed = 1 iff P >= 1, boundary_edges = 0 and irregular_edges = 0: every edge is then shared by exactly two triangles in opposite
+ *     directions -- a closed, consistently oriented surface without non-manifold edges.  Non-manifold VERTICES (two fans that meet in a
+ *     point) are not examined.
+ *   Components.  components = C of rm_mesh_components; the call labels the mesh if nobody has, and the labelling stays with the mesh.  An
+ *     edge belongs to the component of its ends.  rm_mesh_measure_components gives per component c, in rm_mesh_components' numbering, four
+ *     uint64: (edges, boundary, irregular, unbalanced); `bytes` must be exactly 32 C, `host` may be NULL only with 0 bytes; it measures the
+ *     mesh if nobody has.  closed_components counts the components that have at least one participating triangle and whose edges are all
+ *     regular.
+ *   Extent.  finite_vertices counts the vertices whose three coordinates are finite, referenced or not; lo[a] is the minimum and hi[a] the
+ *     maximum of their coordinate a, and 0.0f is added to each of the six floats at the end, so a zero is stored as +0 whatever order the
+ *     device compares in.  With no finite vertex lo = hi = 0.
+ *   Area and volume, in double: every operation rounded on its own (no contraction), IEEE division and square root.  o[a] = (double)lo[a].
+ *     A participating triangle is MEASURED iff its nine coordinates are finite; unmeasured_triangles counts the participating ones that are
+ *     not.  For a measured triangle with p0, p1, p2 converted to double:  a = p0 - o, b = p1 - o, c = p2 - o;  e1 = b - a, e2 = c - a;
+ *     n = (e1y e2z - e1z e2y,  e1z e2x - e1x e2z,  e1x e2y - e1y e2x), each product rounded, then the difference;
+ *     area_t = 0.5 * sqrt((nx nx + ny ny) + nz nz);  m = the same cross product of b and c;  vol_t = ((ax mx + ay my) + az mz) / 6.0.
+ *     Every other triangle has area_t = vol_t = +0.0 at its place.  area and volume are the FIXED-TREE sums of the T terms in triangle
+ *     order: pad the list with +0.0 to a multiple of 256; each group of 256 becomes one value by `for off = 128, 64, .., 1: s[i] = s[i] +
+ *     s[i + off] for i < off`; the group values, in group order, are the next list; repeat until one value is left (an empty list sums to
+ *     +0.0).  volume is signed, positive for the mesher's outward orientation, and means an enclosed volume only when `closed`.
+ * Determinism: every output is a function of integer sums, minima and maxima, and of that fixed tree: the same bytes on every run.
+ * Procedure (rm_mesh_kernels.inc "measures and edge topology", strict unit only: no scene arithmetic).  Topology: the labelling if the mesh
+ * has none; then one thread per triangle inserts its three edges into an open-addressing table of 64-bit keys x << 32 | y (all-ones is the
+ * empty word, and no key since x < y; a power of two of slots, the first >= 4 T) -- atomicCAS on an empty slot, the next slot on a foreign
+ * key -- and makes one 64-bit atomicAdd on the slot's count word, 1 for a use x->y and 1 << 32 for y->x (both halves stay below 2^32 since
+ * T < 2^32); it also sets its corners' flags.  A probe that went round the whole table sets an error word: RM_ERR_DEVICE.  One thread per slot
+ * classifies its edge; totals and component rows are integer atomic adds, summed in the wave first where its edges lie in one component;
+ * one thread per vertex counts the flags.  Geometry: one thread per vertex for the extent (integer atomicMin / atomicMax on an
+ * order-preserving code of the floats, reduced in the wave first), then one thread per triangle computes its two terms and its workgroup
+ * makes the first level of the tree in LDS; every further level is one launch.  No floating-point atomics, no thread waits for another, every
+ * loop is bounded.  Scratch, freed before the call returns: 16 bytes per slot (at most 128 T), 4 V bytes of flags, 32 C bytes of rows,
+ * 16 ceil(T / 256) bytes of group sums and 1/255 of that for the levels behind, 120 bytes of totals.
+ * The call is synchronous on the context's stream.  out_ms2 (may be NULL) receives the milliseconds between events on the stream of
+ * {topology, including the labelling if this call ran it; geometry}, and {0, 0} when the stored result is returned.  An empty mesh succeeds:
+ * all zero, closed 0, 0 rows.
+ * RM_ERR_INVALID (the text through rm_last_error(NULL) when no context is known): a NULL mesh or out ("NULL argument"); for
+ * rm_mesh_measure_components a NULL mesh ("NULL argument"), then a wrong `bytes` ("exact size"), then a NULL host with bytes > 0.
+ * RM_ERR_DEVICE: T >= 2^32; a failed allocation, with nothing leaked. */
+typedef struct RmMeshMeasures {            /* 160 bytes */
+  uint64_t vertices, triangles;            /*   0,   8: V, T as rm_mesh_counts */
+  uint64_t used_vertices;                  /*  16 */
+  uint64_t skipped_triangles;              /*  24 */
+  uint64_t unmeasured_triangles;           /*  32 */
+  uint64_t finite_vertices;                /*  40 */
+  uint64_t edges, boundary_edges, regular_edges, irregular_edges, unbalanced_edges; /* 48, 56, 64, 72, 80 */
+  int64_t  euler;                          /*  88 */
+  uint64_t components, closed_components;  /*  96, 104 */
+  double   area, volume;                   /* 112, 120 */
+  float    lo[3], hi[3];                   /* 128, 140 */
+  int32_t  closed;                         /* 152 */
+  int32_t  reserved;                       /* 156: written as 0 */
+} RmMeshMeasures;
+RM_API int rm_mesh_measure(rm_mesh* mesh, RmMeshMeasures* out, float* out_ms2);
+RM_API int rm_mesh_measure_components(rm_mesh* mesh, void* host, size_t bytes);
 
 #ifdef __cplusplus
 }

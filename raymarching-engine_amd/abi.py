@@ -331,3 +331,40 @@ class RmMeshOcclusion(C.Structure):
 MESH_OCCLUSION_DEFAULTS = dict(radius=0.25, directions=16, taps=4, normal_delta=2.0 ** -10, strength=1.0, flags=0)  # rm_mesh_occlusion_default
 
 assert C.sizeof(RmMeshOcclusion) == 32
+
+
+class RmMeshMeasures(C.Structure):
+    """What rm_mesh_measure says of a mesh (ABI 9): counts of vertices, triangles and edge classes, the Euler characteristic, components,
+    area, signed volume and extent (include/hip_raymarch.h "measures and edge topology")."""
+    _fields_ = [
+        ("vertices", C.c_uint64),
+        ("triangles", C.c_uint64),
+        ("used_vertices", C.c_uint64),
+        ("skipped_triangles", C.c_uint64),
+        ("unmeasured_triangles", C.c_uint64),
+        ("finite_vertices", C.c_uint64),
+        ("edges", C.c_uint64),
+        ("boundary_edges", C.c_uint64),
+        ("regular_edges", C.c_uint64),
+        ("irregular_edges", C.c_uint64),
+        ("unbalanced_edges", C.c_uint64),
+        ("euler", C.c_int64),
+        ("components", C.c_uint64),
+        ("closed_components", C.c_uint64),
+        ("area", C.c_double),
+        ("volume", C.c_double),
+        ("lo", C.c_float * 3),
+        ("hi", C.c_float * 3),
+        ("closed", C.c_int32),
+        ("reserved", C.c_int32),
+    ]
+
+
+assert C.sizeof(RmMeshMeasures) == 160
+
+
+def mesh_measures_dict(m: "RmMeshMeasures") -> dict:
+    """The struct's fields as a dict: lo and hi as tuples, `closed` as bool, `reserved` left out."""
+    d = {name: getattr(m, name) for name, _ in RmMeshMeasures._fields_ if name != "reserved"}
+    d["lo"], d["hi"], d["closed"] = tuple(float(x) for x in m.lo), tuple(float(x) for x in m.hi), bool(m.closed)
+    return d

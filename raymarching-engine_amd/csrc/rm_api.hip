@@ -208,7 +208,7 @@ struct DeviceArray {
 // that runs the stage.
 struct MeshSpans {
   enum { SAMPLE, COUNT_SCAN, EMIT, SHARPEN, ATTRIBUTES, LABEL, KEEP_FLAGS, GATHER, CLUSTER_NUMBER, CLUSTER_MERGE, CLUSTER_GATHER, OCCLUSION_PROBES, OCCLUSION_TAPS,
-         COUNT };
+         MEASURE_TOPOLOGY, MEASURE_GEOMETRY, COUNT };
   hipEvent_t ev[COUNT][2] = {};
   hipError_t begin(int span, hipStream_t stream) { return record(ev[span][0], stream); }
   hipError_t end(int span, hipStream_t stream) { return record(ev[span][1], stream); }

@@ -1,7 +1,7 @@
 // ---- mesh extraction (include/hip_raymarch.h "mesh extraction"; kernels: rm_mesh_kernels.inc) ------------------------------------
 // Included by rm_api.hip inside its extern "C" block, behind the probes.
 
-enum { MESH_LABELS = 5, MESH_SIZES = 6, MESH_ARRAYS = 7 };  // rm_mesh_components' two arrays, behind the five of RM_MESH_*
+enum { MESH_LABELS = 5, MESH_SIZES = 6, MESH_ARRAYS = 7 };  // rm_mesh_components' two arrays, behind the five of RM_MESH_* (rm_mesh_measure's result lives on the host)
 
 struct rm_mesh {
   explicit rm_mesh(rm_ctx* of) : ctx(of) {}
@@ -13,6 +13,10 @@ struct rm_mesh {
   // rm_mesh_components' result, kept once made (the five arrays never change): V labels, `components` pairs of sizes
   bool labelled = false;
   unsigned long long components = 0;
+  // rm_mesh_measure's result, kept once made for the same reason: the struct, and `components` rows of four counts
+  bool measured = false;
+  RmMeshMeasures measures{};
+  std::vector<unsigned long long> edge_rows;
 };
 
 // A mesh under construction: given up through rm_mesh_destroy, which waits for the stream before it frees -- so the scratch of the call
@@ -772,5 +776,161 @@ int rm_mesh_occlusion(rm_mesh* mesh, rm_scene* scene, const RmMeshOcclusion* par
     out_ms2[0] = spans.ms(MeshSpans::OCCLUSION_PROBES);
     out_ms2[1] = spans.ms(MeshSpans::OCCLUSION_TAPS);
   }
+  return RM_OK;
+}
+
+// ---- measures and edge topology (include/hip_raymarch.h "measures and edge topology") ----------------------------------------------------------
+
+// a coordinate out of the extent kernel's code, with the header's + 0.0f
+static float measure_extent_float(unsigned int code) {
+  const unsigned int bits = (code & 0x80000000u) ? (code & 0x7FFFFFFFu) : ~code;
+  float f;
+  std::memcpy(&f, &bits, sizeof f);
+  return f + 0.0f;
+}
+
+// The measures, once per mesh: the labelling if the mesh has none, the edge table, its classes and the used vertices; the extent, the terms
+// and the levels of their tree.  Everything is allocated before the first launch; on the context's stream, and waits for it: the scratch goes
+// when this returns.  ms2 (when given): the two spans' milliseconds, {0, 0} when the stored result stands.
+static int mesh_measure(const Refuse& refuse, rm_mesh* mesh, float* ms2) {
+  if (ms2) ms2[0] = ms2[1] = 0.0f;
+  if (mesh->measured) return RM_OK;
+  rm_ctx* ctx = mesh->ctx;
+  const unsigned long long V = mesh->vertices, T = mesh->triangles;
+  if (T >= (1ull << 32)) return refuse("the mesh has more triangles than a uint32 count holds (T >= 2^32)", RM_ERR_DEVICE);
+  float ms[2] = {0.0f, 0.0f};
+  if (int rc = mesh_label(refuse, mesh, &ms[0])) return rc;
+  RM_HIP(ctx, hipSetDevice(ctx->device));
+  const unsigned long long C = mesh->components;
+  RmMeshMeasures m{};
+  m.vertices = V;
+  m.triangles = T;
+  m.components = C;
+  std::vector<unsigned long long> rows;
+  if (V == 0) {
+    m.skipped_triangles = T;  // (no index is < 0 vertices)
+  } else {
+    try {
+      rows.resize(4 * (size_t)C);
+    } catch (const std::bad_alloc&) {
+      return refuse("out of host memory", RM_ERR_DEVICE);
+    }
+    unsigned long long slots = 0;
+    if (T > 0)
+      for (slots = 1ull; slots < 4ull * T; slots <<= 1) {}
+    // the tree's levels behind the first: groups[k] values each of area and volume; the level of one value is the totals' own two words
+    std::vector<long long> groups;
+    size_t level_elems = 0;
+    for (long long g = ((long long)T + 255) / 256; T > 0; g = (g + 255) / 256) {
+      groups.push_back(g);
+      if (g == 1) break;
+      level_elems += (size_t)g;
+    }
+    DeviceArray keys, counts, used, totals, d_rows, levels;
+    RM_HIP_AS(refuse, keys.reserve(sizeof(unsigned long long) * (size_t)slots));
+    RM_HIP_AS(refuse, counts.reserve(sizeof(unsigned long long) * (size_t)slots));
+    RM_HIP_AS(refuse, used.reserve(sizeof(unsigned int) * (size_t)V));
+    RM_HIP_AS(refuse, totals.reserve(sizeof(unsigned long long) * rm::RM_MEASURE_WORDS));
+    RM_HIP_AS(refuse, d_rows.reserve(sizeof(unsigned long long) * 4u * (size_t)C));
+    RM_HIP_AS(refuse, levels.reserve(sizeof(double) * 2u * level_elems));
+    unsigned long long first[rm::RM_MEASURE_WORDS] = {};
+    const unsigned int identities[6] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0u, 0u, 0u};
+    std::memcpy(first + rm::RM_MEASURE_EXTENT, identities, sizeof identities);
+    rm::MeshMeasure M{};
+    M.vertices = (long long)V;
+    M.triangles = (long long)T;
+    M.positions = mesh->array[RM_MESH_POSITIONS].f32();
+    M.corners = mesh->array[RM_MESH_TRIANGLES].u32();
+    M.labels = mesh->array[MESH_LABELS].u32();
+    M.keys = keys.u64();
+    M.counts = counts.u64();
+    M.slots = slots;
+    M.used = used.u32();
+    M.totals = totals.u64();
+    M.rows = d_rows.u64();
+    double* const d_area = reinterpret_cast<double*>(M.totals + rm::RM_MEASURE_AREA);
+    double* const d_volume = reinterpret_cast<double*>(M.totals + rm::RM_MEASURE_VOLUME);
+    MeshSpans& spans = ctx->mesh_spans;
+    RM_HIP_AS(refuse, hipMemcpyAsync(totals.p, first, sizeof first, hipMemcpyHostToDevice, ctx->stream));
+    RM_HIP_AS(refuse, spans.begin(MeshSpans::MEASURE_TOPOLOGY, ctx->stream));
+    RM_HIP_AS(refuse, hipMemsetAsync(used.p, 0, sizeof(unsigned int) * (size_t)V, ctx->stream));
+    RM_HIP_AS(refuse, hipMemsetAsync(d_rows.p, 0, sizeof(unsigned long long) * 4u * (size_t)C, ctx->stream));
+    if (T > 0) {
+      RM_HIP_AS(refuse, hipMemsetAsync(keys.p, 0xFF, sizeof(unsigned long long) * (size_t)slots, ctx->stream));
+      RM_HIP_AS(refuse, hipMemsetAsync(counts.p, 0, sizeof(unsigned long long) * (size_t)slots, ctx->stream));
+      RM_HIP_AS(refuse, rm::launch_mesh_measure_edges(M, ctx->stream));
+      RM_HIP_AS(refuse, rm::launch_mesh_measure_classes(M, ctx->stream));
+    }
+    RM_HIP_AS(refuse, rm::launch_mesh_measure_used(M, ctx->stream));
+    RM_HIP_AS(refuse, spans.end(MeshSpans::MEASURE_TOPOLOGY, ctx->stream));
+    RM_HIP_AS(refuse, spans.begin(MeshSpans::MEASURE_GEOMETRY, ctx->stream));
+    RM_HIP_AS(refuse, rm::launch_mesh_measure_extent(M, ctx->stream));
+    if (T > 0) {
+      double* from = static_cast<double*>(levels.p);  // a level's area values, its volume values behind them
+      const bool only = groups[0] == 1;
+      RM_HIP_AS(refuse, rm::launch_mesh_measure_terms(M, only ? d_area : from, only ? d_volume : from + groups[0], ctx->stream));
+      for (size_t k = 1; k < groups.size(); k++) {
+        const bool last = groups[k] == 1;
+        double* to = from + 2 * groups[k - 1];
+        RM_HIP_AS(refuse, rm::launch_mesh_measure_sum(from, from + groups[k - 1], groups[k - 1], last ? d_area : to, last ? d_volume : to + groups[k], ctx->stream));
+        from = to;
+      }
+    }
+    RM_HIP_AS(refuse, spans.end(MeshSpans::MEASURE_GEOMETRY, ctx->stream));
+    unsigned long long got[rm::RM_MEASURE_WORDS] = {};
+    if (C > 0)
+      if (int rc = copy_and_wait(ctx, rows.data(), d_rows.p, sizeof(unsigned long long) * rows.size(), hipMemcpyDeviceToHost)) return rc;
+    if (int rc = copy_and_wait(ctx, got, totals.p, sizeof got, hipMemcpyDeviceToHost)) return rc;
+    ms[0] += spans.ms(MeshSpans::MEASURE_TOPOLOGY);
+    ms[1] = spans.ms(MeshSpans::MEASURE_GEOMETRY);
+    if (got[rm::RM_MEASURE_ERROR] != 0ull) return refuse("an edge found no slot in the table", RM_ERR_DEVICE);
+    m.skipped_triangles = got[rm::RM_MEASURE_SKIPPED];
+    m.used_vertices = got[rm::RM_MEASURE_USED];
+    m.unmeasured_triangles = got[rm::RM_MEASURE_UNMEASURED];
+    m.finite_vertices = got[rm::RM_MEASURE_FINITE];
+    m.edges = got[rm::RM_MEASURE_EDGES];
+    m.boundary_edges = got[rm::RM_MEASURE_BOUNDARY];
+    m.regular_edges = got[rm::RM_MEASURE_REGULAR];
+    m.irregular_edges = got[rm::RM_MEASURE_IRREGULAR];
+    m.unbalanced_edges = got[rm::RM_MEASURE_UNBALANCED];
+    std::memcpy(&m.area, got + rm::RM_MEASURE_AREA, sizeof m.area);
+    std::memcpy(&m.volume, got + rm::RM_MEASURE_VOLUME, sizeof m.volume);
+    if (m.finite_vertices > 0) {
+      unsigned int extent[6];
+      std::memcpy(extent, got + rm::RM_MEASURE_EXTENT, sizeof extent);
+      for (int a = 0; a < 3; a++) {
+        m.lo[a] = measure_extent_float(extent[a]);
+        m.hi[a] = measure_extent_float(extent[3 + a]);
+      }
+    }
+  }
+  const unsigned long long P = T - m.skipped_triangles;
+  m.euler = (long long)m.used_vertices - (long long)m.edges + (long long)P;
+  m.closed = P >= 1 && m.boundary_edges == 0 && m.irregular_edges == 0 ? 1 : 0;
+  for (size_t c = 0; c < rows.size() / 4; c++)
+    if (rows[4 * c] > 0 && rows[4 * c + 1] == 0 && rows[4 * c + 2] == 0) m.closed_components++;
+  mesh->measures = m;
+  mesh->edge_rows = std::move(rows);
+  mesh->measured = true;
+  if (ms2) { ms2[0] = ms[0]; ms2[1] = ms[1]; }
+  return RM_OK;
+}
+
+int rm_mesh_measure(rm_mesh* mesh, RmMeshMeasures* out, float* out_ms2) {
+  const Refuse refuse{mesh ? mesh->ctx : nullptr, "rm_mesh_measure"};
+  if (!mesh || !out) return refuse("NULL argument");
+  if (int rc = mesh_measure(refuse, mesh, out_ms2)) return rc;
+  *out = mesh->measures;
+  return RM_OK;
+}
+
+int rm_mesh_measure_components(rm_mesh* mesh, void* host, size_t bytes) {
+  const Refuse refuse{mesh ? mesh->ctx : nullptr, "rm_mesh_measure_components"};
+  if (!mesh) return refuse("NULL argument");
+  if (int rc = mesh_measure(refuse, mesh, nullptr)) return rc;
+  if (bytes != sizeof(unsigned long long) * mesh->edge_rows.size()) return refuse("bytes must be the rows' exact size (32 per component)");
+  if (bytes == 0) return RM_OK;
+  if (!host) return refuse("NULL argument");
+  std::memcpy(host, mesh->edge_rows.data(), bytes);
   return RM_OK;
 }

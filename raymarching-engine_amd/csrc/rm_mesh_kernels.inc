@@ -2,7 +2,7 @@
 // and -- in the strict unit only, they have no arithmetic of a policy's own -- the surface-nets mesher over such a grid, the two
 // kernels that move its vertices to their cells' QEF minimisers (rm_mesh_extract_sharp), and the integer kernels that label a mesh's
 // connected components and compact the kept ones (rm_mesh_components, rm_mesh_filter), and the vertex clustering of rm_mesh_simplify with the quadric placement of
-// rm_mesh_simplify_quadric.  Included by
+// rm_mesh_simplify_quadric, and the edge table, classes, extent and fixed-tree sums of rm_mesh_measure.  Included by
 // rm_strict.hip / rm_fast.hip / rm_glstack.hip behind rm_kernels.inc.
 namespace rm {
 
@@ -958,6 +958,213 @@ __global__ __launch_bounds__(256) void rm_mesh_quadric_place_kernel(const MeshQu
   }
 }
 
+// ---- measures and edge topology (include/hip_raymarch.h "measures and edge topology") -------------------------------------------------------
+// Everything a run can differ in is an integer sum, a minimum or a maximum; the doubles are summed by a tree whose shape depends on T alone.
+// No thread waits for another; the one loop, the table's probe, is bounded by the table's size.  A triangle with a repeated index or one beyond
+// the mesh is looked at no further than its three indices.
+
+// lanes of this wave for which `flag` holds, added to *word by the wave's first lane (every lane of the wave calls this)
+__device__ inline void mesh_measure_count(unsigned long long* word, bool flag) {
+  const unsigned long long lanes = __ballot(flag);
+  if (lanes != 0ull && (threadIdx.x & 63u) == 0u) atomicAdd(word, (unsigned long long)__popcll(lanes));
+}
+
+// one use of the directed edge from -> to
+__device__ inline void mesh_measure_edge(const MeshMeasure& M, unsigned int from, unsigned int to) {
+  const bool forward = from < to;
+  const unsigned long long key = forward ? ((unsigned long long)from << 32 | to) : ((unsigned long long)to << 32 | from);
+  unsigned long long h = key * 0x9E3779B97F4A7C15ull;
+  h ^= h >> 29;
+  h *= 0xBF58476D1CE4E5B9ull;
+  h ^= h >> 32;
+  const unsigned long long mask = M.slots - 1ull;
+  unsigned long long slot = h & mask;
+  for (unsigned long long probe = 0; probe < M.slots; probe++, slot = (slot + 1ull) & mask) {
+    unsigned long long held = __hip_atomic_load(M.keys + slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (held == ~0ull) {
+      held = atomicCAS(M.keys + slot, ~0ull, key);
+      if (held == ~0ull) held = key;
+    }
+    if (held == key) {
+      atomicAdd(M.counts + slot, forward ? 1ull : 1ull << 32);
+      return;
+    }
+  }
+  M.totals[RM_MEASURE_ERROR] = 1ull;  // (every writer writes the same)
+}
+
+__global__ __launch_bounds__(256) void rm_mesh_measure_edges_kernel(const MeshMeasure M) {
+  const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
+  const bool valid = t < M.triangles;
+  unsigned int a = 0u, b = 0u, c = 0u;
+  if (valid) { a = M.corners[3 * t]; b = M.corners[3 * t + 1]; c = M.corners[3 * t + 2]; }
+  const bool takes_part = valid && a < M.vertices && b < M.vertices && c < M.vertices && a != b && b != c && a != c;
+  mesh_measure_count(M.totals + RM_MEASURE_SKIPPED, valid && !takes_part);
+  if (!takes_part) return;
+  M.used[a] = 1u;  // (every writer of a flag writes the same)
+  M.used[b] = 1u;
+  M.used[c] = 1u;
+  mesh_measure_edge(M, a, b);
+  mesh_measure_edge(M, b, c);
+  mesh_measure_edge(M, c, a);
+}
+
+// One thread per slot.  The five totals are counted over the wave and added once; the component rows too where all the wave's edges lie in
+// one component (a mesh of one body: every wave), else every edge adds to its own row.
+__global__ __launch_bounds__(256) void rm_mesh_measure_classes_kernel(const MeshMeasure M) {
+  const unsigned long long slot = (unsigned long long)blockIdx.x * 256 + threadIdx.x;
+  const unsigned long long key = slot < M.slots ? M.keys[slot] : ~0ull;
+  const bool edge = key != ~0ull;
+  const unsigned long long lanes = __ballot(edge);
+  if (lanes == 0ull) return;
+  unsigned int part = 0u;
+  bool boundary = false, regular = false, irregular = false, unbalanced = false;
+  if (edge) {
+    const unsigned long long uses = M.counts[slot];
+    const unsigned long long f = uses & 0xFFFFFFFFull, r = uses >> 32;
+    boundary = f + r == 1ull;
+    regular = f == 1ull && r == 1ull;
+    irregular = !boundary && !regular;
+    unbalanced = f + r >= 2ull && f != r;
+    part = M.labels[(unsigned int)(key >> 32)];
+  }
+  const unsigned long long n_boundary = (unsigned long long)__popcll(__ballot(boundary)), n_regular = (unsigned long long)__popcll(__ballot(regular));
+  const unsigned long long n_irregular = (unsigned long long)__popcll(__ballot(irregular)), n_unbalanced = (unsigned long long)__popcll(__ballot(unbalanced));
+  const int lane = (int)(threadIdx.x & 63u), lead = __ffsll((long long)lanes) - 1;
+  const unsigned int first = (unsigned int)__shfl((int)part, lead);
+  const bool together = __ballot(edge && part == first) == lanes;
+  if (lane == lead) {
+    atomicAdd(M.totals + RM_MEASURE_EDGES, (unsigned long long)__popcll(lanes));
+    if (n_boundary) atomicAdd(M.totals + RM_MEASURE_BOUNDARY, n_boundary);
+    if (n_regular) atomicAdd(M.totals + RM_MEASURE_REGULAR, n_regular);
+    if (n_irregular) atomicAdd(M.totals + RM_MEASURE_IRREGULAR, n_irregular);
+    if (n_unbalanced) atomicAdd(M.totals + RM_MEASURE_UNBALANCED, n_unbalanced);
+  }
+  unsigned long long* row = M.rows + 4 * (size_t)part;
+  if (together) {
+    if (lane != lead) return;
+    atomicAdd(row, (unsigned long long)__popcll(lanes));
+    if (n_boundary) atomicAdd(row + 1, n_boundary);
+    if (n_irregular) atomicAdd(row + 2, n_irregular);
+    if (n_unbalanced) atomicAdd(row + 3, n_unbalanced);
+  } else if (edge) {
+    atomicAdd(row, 1ull);
+    if (boundary) atomicAdd(row + 1, 1ull);
+    if (irregular) atomicAdd(row + 2, 1ull);
+    if (unbalanced) atomicAdd(row + 3, 1ull);
+  }
+}
+
+__global__ __launch_bounds__(256) void rm_mesh_measure_used_kernel(const MeshMeasure M) {
+  const long long v = (long long)blockIdx.x * 256 + threadIdx.x;
+  mesh_measure_count(M.totals + RM_MEASURE_USED, v < M.vertices && M.used[v] != 0u);
+}
+
+// a float's bits as an unsigned integer that orders as the floats do (-0 below +0; NaN is never coded), and back
+__device__ inline unsigned int mesh_measure_code(float x) {
+  const unsigned int u = __float_as_uint(x);
+  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ inline float mesh_measure_decode(unsigned int c) { return __uint_as_float((c & 0x80000000u) ? (c & 0x7FFFFFFFu) : ~c); }
+
+// One thread per vertex: the finite ones are counted, and their coordinates' codes reduced over the wave by integer minima and maxima, then one
+// atomicMin / atomicMax per wave and word.  A lane without a finite vertex holds the identities.
+__global__ __launch_bounds__(256) void rm_mesh_measure_extent_kernel(const MeshMeasure M) {
+  const long long v = (long long)blockIdx.x * 256 + threadIdx.x;
+  unsigned int lo[3] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu}, hi[3] = {0u, 0u, 0u};
+  bool finite = false;
+  if (v < M.vertices) {
+    const float x = M.positions[3 * v], y = M.positions[3 * v + 1], z = M.positions[3 * v + 2];
+    finite = isfinite(x) && isfinite(y) && isfinite(z);
+    if (finite) {
+      lo[0] = hi[0] = mesh_measure_code(x);
+      lo[1] = hi[1] = mesh_measure_code(y);
+      lo[2] = hi[2] = mesh_measure_code(z);
+    }
+  }
+  const unsigned long long lanes = __ballot(finite);
+  if (lanes == 0ull) return;
+#pragma unroll
+  for (int m = 1; m < 64; m <<= 1) {
+#pragma unroll
+    for (int a = 0; a < 3; a++) {
+      const unsigned int l = (unsigned int)__shfl_xor((int)lo[a], m), h = (unsigned int)__shfl_xor((int)hi[a], m);
+      if (l < lo[a]) lo[a] = l;
+      if (h > hi[a]) hi[a] = h;
+    }
+  }
+  if ((threadIdx.x & 63u) != 0u) return;
+  atomicAdd(M.totals + RM_MEASURE_FINITE, (unsigned long long)__popcll(lanes));
+  unsigned int* extent = reinterpret_cast<unsigned int*>(M.totals + RM_MEASURE_EXTENT);
+#pragma unroll
+  for (int a = 0; a < 3; a++) {
+    atomicMin(extent + a, lo[a]);
+    atomicMax(extent + 3 + a, hi[a]);
+  }
+}
+
+// the stated tree over a workgroup's 256 values of each list: for off = 128 .. 1, s[i] = s[i] + s[i + off] for i < off; s[0] holds the sum
+__device__ inline void mesh_measure_tree(double (*s)[256]) {
+  for (int off = 128; off >= 1; off >>= 1) {
+    __syncthreads();
+    if ((int)threadIdx.x < off) {
+      s[0][threadIdx.x] = s[0][threadIdx.x] + s[0][threadIdx.x + off];
+      s[1][threadIdx.x] = s[1][threadIdx.x] + s[1][threadIdx.x + off];
+    }
+  }
+}
+
+// One thread per triangle: its two terms in double, every operation rounded on its own (this unit is built without contraction; '/' and sqrt
+// are IEEE in double), +0.0 for a triangle that is not measured and for the places behind the last; then the first level of the tree.
+__global__ __launch_bounds__(256) void rm_mesh_measure_terms_kernel(const MeshMeasure M, double* area, double* volume) {
+  __shared__ double s[2][256];
+  const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
+  double area_t = 0.0, volume_t = 0.0;
+  bool unmeasured = false;
+  if (t < M.triangles) {
+    const unsigned int i0 = M.corners[3 * t], i1 = M.corners[3 * t + 1], i2 = M.corners[3 * t + 2];
+    if (i0 < M.vertices && i1 < M.vertices && i2 < M.vertices && i0 != i1 && i1 != i2 && i0 != i2) {
+      const float* p0 = M.positions + 3 * (size_t)i0;
+      const float* p1 = M.positions + 3 * (size_t)i1;
+      const float* p2 = M.positions + 3 * (size_t)i2;
+      const float q[9] = {p0[0], p0[1], p0[2], p1[0], p1[1], p1[2], p2[0], p2[1], p2[2]};
+      bool finite = true;
+#pragma unroll
+      for (int k = 0; k < 9; k++) finite = finite && isfinite(q[k]);
+      unmeasured = !finite;
+      if (finite) {
+        // (a measured triangle has finite vertices: the extent is there)
+        const unsigned int* extent = reinterpret_cast<const unsigned int*>(M.totals + RM_MEASURE_EXTENT);
+        const double ox = (double)(mesh_measure_decode(extent[0]) + 0.0f), oy = (double)(mesh_measure_decode(extent[1]) + 0.0f);
+        const double oz = (double)(mesh_measure_decode(extent[2]) + 0.0f);
+        const double ax = (double)q[0] - ox, ay = (double)q[1] - oy, az = (double)q[2] - oz;
+        const double bx = (double)q[3] - ox, by = (double)q[4] - oy, bz = (double)q[5] - oz;
+        const double cx = (double)q[6] - ox, cy = (double)q[7] - oy, cz = (double)q[8] - oz;
+        const double e1x = bx - ax, e1y = by - ay, e1z = bz - az, e2x = cx - ax, e2y = cy - ay, e2z = cz - az;
+        const double nx = e1y * e2z - e1z * e2y, ny = e1z * e2x - e1x * e2z, nz = e1x * e2y - e1y * e2x;
+        area_t = 0.5 * sqrt((nx * nx + ny * ny) + nz * nz);
+        const double mx = by * cz - bz * cy, my = bz * cx - bx * cz, mz = bx * cy - by * cx;
+        volume_t = ((ax * mx + ay * my) + az * mz) / 6.0;
+      }
+    }
+  }
+  mesh_measure_count(M.totals + RM_MEASURE_UNMEASURED, unmeasured);
+  s[0][threadIdx.x] = area_t;
+  s[1][threadIdx.x] = volume_t;
+  mesh_measure_tree(s);
+  if (threadIdx.x == 0u) { area[blockIdx.x] = s[0][0]; volume[blockIdx.x] = s[1][0]; }
+}
+
+// one further level: workgroup g sums values [256 g, 256 g + 256) of each list, +0.0 behind the last
+__global__ __launch_bounds__(256) void rm_mesh_measure_sum_kernel(const double* area, const double* volume, long long n, double* out_area, double* out_volume) {
+  __shared__ double s[2][256];
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  s[0][threadIdx.x] = i < n ? area[i] : 0.0;
+  s[1][threadIdx.x] = i < n ? volume[i] : 0.0;
+  mesh_measure_tree(s);
+  if (threadIdx.x == 0u) { out_area[blockIdx.x] = s[0][0]; out_volume[blockIdx.x] = s[1][0]; }
+}
+
 #ifndef RM_ONLY_KERNELS
 static inline long long mesh_cells(const GridDims& g) { return (long long)(g.nc[0] - 1) * (g.nc[1] - 1) * (g.nc[2] - 1); }
 
@@ -1058,6 +1265,17 @@ hipError_t launch_mesh_simplify_keep(const MeshSimplify& S, hipStream_t stream) 
 hipError_t launch_mesh_simplify_gather(const MeshSimplify& S, hipStream_t stream) { RM_MESH_PARTS_LAUNCH(rm_mesh_simplify_take_kernel, S.triangles, S); }
 hipError_t launch_mesh_quadric_sums(const MeshQuadric& S, hipStream_t stream) { RM_MESH_PARTS_LAUNCH(rm_mesh_quadric_sums_kernel, S.triangles, S); }
 hipError_t launch_mesh_quadric_place(const MeshQuadric& S, hipStream_t stream) { RM_MESH_PARTS_LAUNCH(rm_mesh_quadric_place_kernel, S.out_vertices, S); }
+// measures: one thread per triangle, slot or vertex; the sums one workgroup per 256 values
+hipError_t launch_mesh_measure_edges(const MeshMeasure& M, hipStream_t stream) { RM_MESH_PARTS_LAUNCH(rm_mesh_measure_edges_kernel, M.triangles, M); }
+hipError_t launch_mesh_measure_classes(const MeshMeasure& M, hipStream_t stream) { RM_MESH_PARTS_LAUNCH(rm_mesh_measure_classes_kernel, (long long)M.slots, M); }
+hipError_t launch_mesh_measure_used(const MeshMeasure& M, hipStream_t stream) { RM_MESH_PARTS_LAUNCH(rm_mesh_measure_used_kernel, M.vertices, M); }
+hipError_t launch_mesh_measure_extent(const MeshMeasure& M, hipStream_t stream) { RM_MESH_PARTS_LAUNCH(rm_mesh_measure_extent_kernel, M.vertices, M); }
+hipError_t launch_mesh_measure_terms(const MeshMeasure& M, double* area, double* volume, hipStream_t stream) {
+  RM_MESH_PARTS_LAUNCH(rm_mesh_measure_terms_kernel, M.triangles, M, area, volume);
+}
+hipError_t launch_mesh_measure_sum(const double* area, const double* volume, long long n, double* out_area, double* out_volume, hipStream_t stream) {
+  RM_MESH_PARTS_LAUNCH(rm_mesh_measure_sum_kernel, n, area, volume, n, out_area, out_volume);
+}
 #undef RM_MESH_PARTS_LAUNCH
 
 hipError_t launch_mesh_emit(const MeshParams& P, hipStream_t stream) {

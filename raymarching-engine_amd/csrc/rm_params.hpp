@@ -553,6 +553,40 @@ hipError_t launch_mesh_simplify_keep(const MeshSimplify& S, hipStream_t stream);
 hipError_t launch_mesh_simplify_gather(const MeshSimplify& S, hipStream_t stream);
 hipError_t launch_mesh_quadric_sums(const MeshQuadric& S, hipStream_t stream);
 hipError_t launch_mesh_quadric_place(const MeshQuadric& S, hipStream_t stream);
+// Measures and edge topology (rm_mesh_measure): integer kernels over a mesh's triangles, the slots of an edge table and its vertices, and the
+// double-precision terms of area and volume with their fixed-tree sums.  totals: RM_MEASURE_WORDS 64-bit words, set by the host before the
+// first launch (the extent's six words to the identities of min and max, everything else 0).  measure_edges: one thread per triangle, its
+// three edges into the table (keys of all-ones, a power of two of them; counts of 0), used[v] = 1 for its corners.  measure_classes: one thread
+// per slot.  measure_used: one thread per vertex, counts the flags.  measure_extent: one thread per vertex.  measure_terms (behind
+// measure_extent: it reads the extent's low corner): one thread per triangle, and the first level of the tree; measure_sum: one further level,
+// n values of each of the two lists into ceil(n / 256).
+enum {
+  RM_MEASURE_SKIPPED, RM_MEASURE_USED, RM_MEASURE_EDGES, RM_MEASURE_BOUNDARY, RM_MEASURE_REGULAR, RM_MEASURE_IRREGULAR, RM_MEASURE_UNBALANCED,
+  RM_MEASURE_UNMEASURED, RM_MEASURE_FINITE, RM_MEASURE_ERROR,
+  RM_MEASURE_EXTENT,                         // three words: six uint32, lo[3] then hi[3], floats in an order-preserving integer code
+  RM_MEASURE_AREA = RM_MEASURE_EXTENT + 3,   // the two sums, as doubles
+  RM_MEASURE_VOLUME,
+  RM_MEASURE_WORDS
+};
+struct MeshMeasure {
+  long long vertices, triangles;
+  const float* positions;         // V x 3
+  const unsigned int* corners;    // T x 3
+  const unsigned int* labels;     // V
+  unsigned long long* keys;       // slots
+  unsigned long long* counts;     // slots: uses x -> y in the low half, y -> x in the high half
+  unsigned long long slots;       // a power of two
+  unsigned int* used;             // V
+  unsigned long long* totals;     // RM_MEASURE_WORDS
+  unsigned long long* rows;       // components x 4: edges, boundary, irregular, unbalanced
+};
+hipError_t launch_mesh_measure_edges(const MeshMeasure& M, hipStream_t stream);
+hipError_t launch_mesh_measure_classes(const MeshMeasure& M, hipStream_t stream);
+hipError_t launch_mesh_measure_used(const MeshMeasure& M, hipStream_t stream);
+hipError_t launch_mesh_measure_extent(const MeshMeasure& M, hipStream_t stream);
+// area[g], volume[g] = the tree sums of group g's 256 triangles
+hipError_t launch_mesh_measure_terms(const MeshMeasure& M, double* area, double* volume, hipStream_t stream);
+hipError_t launch_mesh_measure_sum(const double* area, const double* volume, long long n, double* out_area, double* out_volume, hipStream_t stream);
 hipError_t launch_camera_rng(const RmUniforms& u, int W, int H, int what, int count, float* out, hipStream_t stream);
 hipError_t launch_math_probe(int fn, const float* a, const float* b, int n, float* out, hipStream_t stream);
 }  // namespace rm

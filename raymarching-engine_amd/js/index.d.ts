@@ -125,10 +125,14 @@ export class RenderJobContext {
   extractMesh(scene: Scene, grid: MeshGrid, params: MeshParams | null | undefined, sharp: MeshSharp | true | null | undefined, keep: MeshKeep | true | null | undefined, components: boolean | undefined, simplify: MeshSimplify, quadric: MeshQuadric | true | null): Mesh;
   /** with `occlusion` (true = the defaults): the scene's ambient occlusion at the vertices of the mesh that is returned, behind simplify, keep and components (rm_mesh_occlusion), as Mesh.occlusion; timings gains a fourth entry, its milliseconds */
   extractMesh(scene: Scene, grid: MeshGrid, params: MeshParams | null | undefined, sharp: MeshSharp | true | null | undefined, keep: MeshKeep | true | null | undefined, components: boolean | undefined, simplify: MeshSimplify | null | undefined, quadric: MeshQuadric | true | null | undefined, occlusion: MeshOcclusion | true | null): Mesh;
+  /** with `measures`: the mesh that is returned is measured on the GPU behind simplify and keep, before anything is copied (rm_mesh_measure), as Mesh.measures */
+  extractMesh(scene: Scene, grid: MeshGrid, params: MeshParams | null | undefined, sharp: MeshSharp | true | null | undefined, keep: MeshKeep | true | null | undefined, components: boolean | undefined, simplify: MeshSimplify | null | undefined, quadric: MeshQuadric | true | null | undefined, occlusion: MeshOcclusion | true | null | undefined, measures: boolean): Mesh;
   /** the mesher alone on the caller's field (rm_mesh_from_values); keep, components and simplify as in extractMesh */
   meshFromValues(grid: MeshGrid, values: Float32Array, iso?: number, keep?: MeshKeep | true | null, components?: boolean, simplify?: MeshSimplify | null): Mesh;
   /** quadric as in extractMesh */
   meshFromValues(grid: MeshGrid, values: Float32Array, iso: number | undefined, keep: MeshKeep | true | null | undefined, components: boolean | undefined, simplify: MeshSimplify, quadric: MeshQuadric | true | null): Mesh;
+  /** measures as in extractMesh */
+  meshFromValues(grid: MeshGrid, values: Float32Array, iso: number | undefined, keep: MeshKeep | true | null | undefined, components: boolean | undefined, simplify: MeshSimplify | null | undefined, quadric: MeshQuadric | true | null | undefined, measures: boolean): Mesh;
   close(): void;
 }
 /** A frame sharded over several GPUs by this one process: a native context per device, each holding one part of the frame's
@@ -160,7 +164,9 @@ export const RM: { [name: string]: number };
 /** mesh extraction (include/hip_raymarch.h "mesh extraction"): n = CELLS per axis between the corners lo and hi */
 export interface MeshGrid { lo: [number, number, number]; hi: [number, number, number]; n: [number, number, number] }
 export interface MeshParams { iso?: number; normals?: boolean | 0 | 1; normalDelta?: number; colours?: boolean | 0 | 1; flags?: number }
-export interface Mesh { positions: Float32Array; normals: Float32Array | null; colours: Float32Array | null; triangles: Uint32Array; cells: Uint32Array; /** ms of sampling, meshing, attributes (rm_mesh_timings); with an occlusion a fourth entry, its probes and taps */ timings: [number, number, number] | [number, number, number, number]; /** only when components were asked for: each vertex's component, and (vertices, triangles) per component */ labels?: Uint32Array; componentSizes?: Uint32Array; /** only when an occlusion was asked for: 1 = open, per vertex (rm_mesh_occlusion) */ occlusion?: Float32Array }
+export interface Mesh { positions: Float32Array; normals: Float32Array | null; colours: Float32Array | null; triangles: Uint32Array; cells: Uint32Array; /** ms of sampling, meshing, attributes (rm_mesh_timings); with an occlusion a fourth entry, its probes and taps */ timings: [number, number, number] | [number, number, number, number]; /** only when components were asked for: each vertex's component, and (vertices, triangles) per component */ labels?: Uint32Array; componentSizes?: Uint32Array; /** only when an occlusion was asked for: 1 = open, per vertex (rm_mesh_occlusion) */ occlusion?: Float32Array; /** only when measures were asked for (rm_mesh_measure) */ measures?: MeshMeasures }
+/** what rm_mesh_measure says of a mesh (RmMeshMeasures, include/hip_raymarch.h "measures and edge topology"): the counts as Numbers (all below 2^53), lo / hi of the finite vertices, closed = no boundary and no irregular edge; componentEdges: 4 uint64 per component (edges, boundary, irregular, unbalanced; rm_mesh_measure_components); milliseconds of topology and geometry */
+export interface MeshMeasures { vertices: number; triangles: number; usedVertices: number; skippedTriangles: number; unmeasuredTriangles: number; finiteVertices: number; edges: number; boundaryEdges: number; regularEdges: number; irregularEdges: number; unbalancedEdges: number; euler: number; components: number; closedComponents: number; area: number; volume: number; lo: [number, number, number]; hi: [number, number, number]; closed: boolean; componentEdges: BigUint64Array; milliseconds: [number, number] }
 export const MESH_DEFAULTS: { iso: number; normals: 0 | 1; normalDelta: number; colours: 0 | 1; flags: number };
 export function meshGrid(lo: number[], hi: number[], n: number[]): MeshGrid;
 export function meshParams(params?: MeshParams | null): { iso: number; normals: 0 | 1; normalDelta: number; colours: 0 | 1; flags: number };
@@ -185,4 +191,6 @@ export interface MeshOcclusion { radius?: number; directions?: number; taps?: nu
 export const MESH_OCCLUSION_DEFAULTS: { radius: number; directions: number; taps: number; normalDelta: number; strength: number; flags: number };
 export function meshOcclusion(occlusion?: MeshOcclusion | null): { radius: number; directions: number; taps: number; normalDelta: number; strength: number; flags: number };
 /** binary little-endian PLY (normals, uchar colours and a float `quality` -- the occlusion -- when present): the bytes the Python host's write_ply writes */
+/** binary STL of the triangles, facet normals computed in double from the float32 positions: the bytes the Python host's mesh.encode_stl writes */
+export function encodeStl(mesh: { positions: Float32Array; triangles: Uint32Array }): Buffer;
 export function encodePly(mesh: { positions: Float32Array; triangles: Uint32Array; normals?: Float32Array | null; colours?: Float32Array | null; occlusion?: Float32Array | null }): Buffer;

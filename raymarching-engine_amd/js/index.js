@@ -365,9 +365,20 @@ class RenderJobContext {  // RenderJobContext + loadRenderJobContext (LoadRender
   // cluster's vertex at the minimiser of its plane quadrics
   // occlusion: undefined / null = that mesh; true or meshOcclusion's options = occlusion (Float32Array(V), 1 = open) of the mesh that is returned,
   // baked from the scene's distance field behind simplify, keep and components (rm_mesh_occlusion); its milliseconds are timings[3]
-  extractMesh(scene, grid, opts, sharp, keep, components, simplify = null, quadric = null, occlusion = null) {
+  // measures: truthy = the mesh that is returned is measured on the GPU behind simplify and keep, before anything is copied (rm_mesh_measure), as
+  // measures: RmMeshMeasures' fields in camel case -- the counts as Numbers (all below 2^53: V, T < 2^32 and E <= 3 T), closed as a boolean,
+  // lo / hi as arrays --, componentEdges: BigUint64Array(4 C) of (edges, boundary, irregular, unbalanced) per component as the raw uint64 rows, and
+  // milliseconds: [topology, geometry].  timings is as without it.
+  extractMesh(scene, grid, opts, sharp, keep, components, simplify = null, quadric = null, occlusion = null, measures = false) {
     const q = quadric === undefined || quadric === null ? null : meshQuadric(quadric === true ? undefined : quadric);
     if (q !== null && (simplify === undefined || simplify === null)) throw new TypeError("mesh: quadric places the vertices of a simplification: give simplify as well");
+    if (measures) {
+      const o = occlusion === undefined || occlusion === null ? null : meshOcclusion(occlusion === true ? undefined : occlusion);
+      const s = sharp === undefined || sharp === null ? null : meshSharp(sharp === true ? undefined : sharp);
+      const k = keep === undefined || keep === null ? null : meshKeep(keep === true ? undefined : keep);
+      const c = simplify === undefined || simplify === null ? null : meshSimplify(simplify);
+      return addon.extractMesh(this.ctx, this.sceneHandle(scene), grid, meshParams(opts), s, k, !!components, c, q, o, true);
+    }
     if (occlusion !== undefined && occlusion !== null) {
       const o = meshOcclusion(occlusion === true ? undefined : occlusion);
       const s = sharp === undefined || sharp === null ? null : meshSharp(sharp === true ? undefined : sharp);
@@ -389,12 +400,17 @@ class RenderJobContext {  // RenderJobContext + loadRenderJobContext (LoadRender
     return addon.extractMesh(this.ctx, this.sceneHandle(scene), grid, meshParams(opts), s, k, !!components);
   }
   // the mesher alone on the caller's field: values Float32Array of the grid's corners, x fastest (rm_mesh_from_values)
-  // keep, components, simplify, quadric: as in extractMesh
-  meshFromValues(grid, values, iso = 0, keep, components, simplify, quadric) {
+  // keep, components, simplify, quadric, measures: as in extractMesh
+  meshFromValues(grid, values, iso = 0, keep, components, simplify, quadric, measures) {
     if (!(values instanceof Float32Array)) throw new TypeError("meshFromValues: values must be a Float32Array");
     if (!finite(iso)) throw new RangeError("mesh: iso must be a finite number");
     const q = quadric === undefined || quadric === null ? null : meshQuadric(quadric === true ? undefined : quadric);
     if (q !== null && (simplify === undefined || simplify === null)) throw new TypeError("mesh: quadric places the vertices of a simplification: give simplify as well");
+    if (measures) {
+      const k = keep === undefined || keep === null ? null : meshKeep(keep === true ? undefined : keep);
+      const c = simplify === undefined || simplify === null ? null : meshSimplify(simplify);
+      return addon.meshFromValues(this.ctx, grid, values, iso, k, !!components, c, q, true);
+    }
     if (simplify !== undefined && simplify !== null) {
       const k = keep === undefined || keep === null ? null : meshKeep(keep === true ? undefined : keep);
       if (q !== null) return addon.meshFromValues(this.ctx, grid, values, iso, k, !!components, meshSimplify(simplify), q);
@@ -781,6 +797,31 @@ function meshOcclusion(opts) {
 // binary little-endian PLY of { positions, triangles, normals?, colours?, occlusion? }: x y z, then nx ny nz, then uchar red green blue
 // (floor(clamp(c, 0, 1) * 255 + 0.5), NaN as 0), then float quality (the occlusion); faces as a uchar count and uint indices -- the bytes the
 // Python host writes
+// Binary STL of { positions, triangles }: 80 header bytes (`hip_raymarch mesh`, zero padded), uint32 T, then per triangle the facet normal, p0, p1,
+// p2 as little-endian float32 and a uint16 0.  The normal in double from the float32 coordinates, every operation rounded on its own: e1 = p1 - p0,
+// e2 = p2 - p0, c = e1 x e2, len = sqrt((cx cx + cy cy) + cz cz), c / len rounded to float32; (0, 0, 0) where len is not > 0 or not finite -- the
+// bytes the Python host's mesh.encode_stl writes
+function encodeStl(mesh) {
+  const p = mesh.positions, t = mesh.triangles, T = t.length / 3;
+  const out = Buffer.alloc(84 + 50 * T);
+  out.write("hip_raymarch mesh", 0, "ascii");
+  out.writeUInt32LE(T, 80);
+  let at = 84;
+  for (let i = 0; i < T; i++) {
+    const a = 3 * t[3 * i], b = 3 * t[3 * i + 1], c = 3 * t[3 * i + 2];
+    if (a + 2 >= p.length || b + 2 >= p.length || c + 2 >= p.length) throw new RangeError("encodeStl: a triangle names a vertex beyond the positions");
+    const e1x = p[b] - p[a], e1y = p[b + 1] - p[a + 1], e1z = p[b + 2] - p[a + 2];
+    const e2x = p[c] - p[a], e2y = p[c + 1] - p[a + 1], e2z = p[c + 2] - p[a + 2];
+    const cx = e1y * e2z - e1z * e2y, cy = e1z * e2x - e1x * e2z, cz = e1x * e2y - e1y * e2x;
+    const len = Math.sqrt((cx * cx + cy * cy) + cz * cz), good = len > 0 && Number.isFinite(len);
+    out.writeFloatLE(good ? cx / len : 0, at); out.writeFloatLE(good ? cy / len : 0, at + 4); out.writeFloatLE(good ? cz / len : 0, at + 8);
+    at += 12;
+    for (const v of [a, b, c]) for (let k = 0; k < 3; k++, at += 4) out.writeFloatLE(p[v + k], at);
+    at += 2;  // (the attribute count: 0)
+  }
+  return out;
+}
+
 function encodePly(mesh) {
   const V = mesh.positions.length / 3, T = mesh.triangles.length / 3, nrm = mesh.normals || null, col = mesh.colours || null, occ = mesh.occlusion || null;
   const header = ["ply", "format binary_little_endian 1.0", "comment hip_raymarch mesh", "element vertex " + V, "property float x", "property float y", "property float z"];
@@ -833,4 +874,4 @@ module.exports = { RM, addon, encodePng, Scene, CsgScene, Mandelbulb, singleSphe
                    tileRect, RenderJobContext, ShardedRenderJobContext, doRenderJob, U_OFFSET, DENOISE_DEFAULTS, denoiseParams,
                    DENOISE_VARIANCE_DEFAULTS, denoiseVarianceParams, DESPECKLE_DEFAULTS, despeckleParams, DISPLAY_DEFAULTS, AUTO_EXPOSURE_DEFAULTS,
                    displayParams, statsExposure, statsPercentile, MESH_DEFAULTS, meshGrid, meshParams, MESH_SHARP_DEFAULTS, meshSharp, MESH_KEEP_DEFAULTS, meshKeep,
-                   MESH_SIMPLIFY_DEFAULTS, meshSimplify, MESH_QUADRIC_DEFAULTS, meshQuadric, MESH_OCCLUSION_DEFAULTS, meshOcclusion, encodePly };
+                   MESH_SIMPLIFY_DEFAULTS, meshSimplify, MESH_QUADRIC_DEFAULTS, meshQuadric, MESH_OCCLUSION_DEFAULTS, meshOcclusion, encodePly, encodeStl };

@@ -692,9 +692,45 @@ static napi_value SdfGrid(napi_env env, napi_callback_info info) {
 // Uint32Array(2 C) come with it (rm_mesh_components).  simplify: before either, the mesh is clustered on the device (rm_mesh_simplify), so one
 // filter also removes the vertices the clustering left without triangles; with quadric by rm_mesh_simplify_quadric.  occlusion (with the scene):
 // occlusion: Float32Array(V) of the mesh that is returned comes with it (rm_mesh_occlusion), and its milliseconds (probes + taps) as timings[3]
+// measures: that mesh is measured before anything is copied (rm_mesh_measure) and `measures` comes with it: RmMeshMeasures' fields in camel case,
+// the counts as Numbers (all below 2^53: V, T < 2^32, E <= 3 T), lo / hi as arrays of three, closed as a boolean, componentEdges:
+// BigUint64Array(4 C) (rm_mesh_measure_components), milliseconds: [topology, geometry]
+static napi_value measures_object(napi_env env, const RmMeshMeasures& m, const float* ms2, rm_mesh* mesh, bool* rm_failed) {
+  *rm_failed = false;
+  napi_value o = nullptr, v = nullptr;
+  if (napi_create_object(env, &o) != napi_ok) return nullptr;
+  const struct { const char* name; double value; } NUMBERS[] = {
+      {"vertices", (double)m.vertices}, {"triangles", (double)m.triangles}, {"usedVertices", (double)m.used_vertices}, {"skippedTriangles", (double)m.skipped_triangles},
+      {"unmeasuredTriangles", (double)m.unmeasured_triangles}, {"finiteVertices", (double)m.finite_vertices}, {"edges", (double)m.edges},
+      {"boundaryEdges", (double)m.boundary_edges}, {"regularEdges", (double)m.regular_edges}, {"irregularEdges", (double)m.irregular_edges},
+      {"unbalancedEdges", (double)m.unbalanced_edges}, {"euler", (double)m.euler}, {"components", (double)m.components},
+      {"closedComponents", (double)m.closed_components}, {"area", m.area}, {"volume", m.volume}};
+  for (const auto& n : NUMBERS)
+    if (napi_create_double(env, n.value, &v) != napi_ok || napi_set_named_property(env, o, n.name, v) != napi_ok) return nullptr;
+  const struct { const char* name; const float* values; uint32_t count; } TRIPLES[] = {{"lo", m.lo, 3}, {"hi", m.hi, 3}, {"milliseconds", ms2, 2}};
+  for (const auto& t : TRIPLES) {
+    napi_value a = nullptr;
+    if (napi_create_array_with_length(env, t.count, &a) != napi_ok) return nullptr;
+    for (uint32_t k = 0; k < t.count; k++)
+      if (napi_create_double(env, (double)t.values[k], &v) != napi_ok || napi_set_element(env, a, k, v) != napi_ok) return nullptr;
+    if (napi_set_named_property(env, o, t.name, a) != napi_ok) return nullptr;
+  }
+  if (napi_get_boolean(env, m.closed != 0, &v) != napi_ok || napi_set_named_property(env, o, "closed", v) != napi_ok) return nullptr;
+  napi_value ab = nullptr, rows = nullptr;
+  void* data = nullptr;
+  const size_t words = 4u * (size_t)m.components;
+  if (napi_create_arraybuffer(env, words * 8u, &data, &ab) != napi_ok || napi_create_typedarray(env, napi_biguint64_array, words, ab, 0, &rows) != napi_ok) return nullptr;
+  if (rm_mesh_measure_components(mesh, data, words * 8u) != RM_OK) {
+    *rm_failed = true;
+    return nullptr;
+  }
+  if (napi_set_named_property(env, o, "componentEdges", rows) != napi_ok) return nullptr;
+  return o;
+}
+
 static napi_value mesh_result(napi_env env, rm_ctx* ctx, rm_mesh* mesh, bool normals, bool colours, const RmMeshKeep* keep = nullptr, bool components = false,
                               const MeshSimplifyBlock* simplify = nullptr, const RmMeshQuadric* quadric = nullptr, rm_scene* scene = nullptr,
-                              const RmMeshOcclusion* occlusion = nullptr) {
+                              const RmMeshOcclusion* occlusion = nullptr, bool measures = false) {
   struct Guard {  // the handle in hand is destroyed on every way out
     rm_mesh* h;
     ~Guard() { rm_mesh_destroy(h); }
@@ -717,6 +753,9 @@ static napi_value mesh_result(napi_env env, rm_ctx* ctx, rm_mesh* mesh, bool nor
     rm_mesh_destroy(mesh);
     guard.h = mesh = filtered;
   }
+  RmMeshMeasures measured{};
+  float measured_ms[2] = {0.0f, 0.0f};
+  if (measures && rm_mesh_measure(mesh, &measured, measured_ms) != RM_OK) return throw_rm(env, ctx, "rm_mesh_measure");
   unsigned long long counts[2] = {0, 0}, parts = 0;
   rm_mesh_counts(mesh, counts);
   enum { ALWAYS, NORMALS, COLOURS, COMPONENTS };  // when an array is there: with every mesh, or when the call asked for it
@@ -763,18 +802,24 @@ static napi_value mesh_result(napi_env env, rm_ctx* ctx, rm_mesh* mesh, bool nor
     if (napi_create_double(env, (double)ms[k], &x) != napi_ok || napi_set_element(env, timings, k, x) != napi_ok) return napi_failed();
   }
   if (napi_set_named_property(env, o, "timings", timings) != napi_ok) return napi_failed();
+  if (measures) {
+    bool rm_failed = false;
+    napi_value v = measures_object(env, measured, measured_ms, mesh, &rm_failed);
+    if (!v) return rm_failed ? throw_rm(env, ctx, "rm_mesh_measure_components") : napi_failed();
+    if (napi_set_named_property(env, o, "measures", v) != napi_ok) return napi_failed();
+  }
   return o;
 }
 
-// extractMesh(ctx, scene, grid, params | null[, sharp | null[, keep | null[, components[, simplify | null[, quadric | null[, occlusion | null]]]]]]) = rm_mesh_extract, or
+// extractMesh(ctx, scene, grid, params | null[, sharp | null[, keep | null[, components[, simplify | null[, quadric | null[, occlusion | null[, measures]]]]]]]) = rm_mesh_extract, or
 // with a sharp block rm_mesh_extract_sharp; with a simplify block rm_mesh_simplify behind it (with a quadric block too: rm_mesh_simplify_quadric);
-// with a keep block rm_mesh_filter behind that; then the arrays, with an occlusion block rm_mesh_occlusion on that last mesh.  A quadric block
-// without a simplify block is refused.
+// with a keep block rm_mesh_filter behind that; with measures rm_mesh_measure on that last mesh; then the arrays, with an occlusion block
+// rm_mesh_occlusion on that last mesh.  A quadric block without a simplify block is refused.
 static napi_value ExtractMesh(napi_env env, napi_callback_info info) {
-  size_t argc = 10;
-  napi_value argv[10];
+  size_t argc = 11;
+  napi_value argv[11];
   NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
-  const bool counted = argc >= 4 && argc <= 10;
+  const bool counted = argc >= 4 && argc <= 11;
   rm_ctx* ctx = counted ? get_external<rm_ctx>(env, argv[0]) : nullptr;
   rm_scene* scene = counted ? get_external<rm_scene>(env, argv[1]) : nullptr;
   RmGrid g;
@@ -784,11 +829,11 @@ static napi_value ExtractMesh(napi_env env, napi_callback_info info) {
   MeshSimplifyBlock c;
   RmMeshQuadric q;
   RmMeshOcclusion ao;
-  bool sharp = false, keep = false, components = false, simplify = false, quadric = false, occlusion = false;
+  bool sharp = false, keep = false, components = false, simplify = false, quadric = false, occlusion = false, measures = false;
   if (!ctx || !scene || !get_grid(env, argv[2], &g) || !get_mesh_params(env, argv[3], &p) || (argc >= 5 && !get_mesh_sharp(env, argv[4], &s, &sharp)) ||
       (argc >= 6 && !get_mesh_keep(env, argv[5], &k, &keep)) || (argc >= 7 && !get_bool(env, argv[6], &components)) ||
-      (argc >= 8 && !get_mesh_simplify(env, argv[7], &c, &simplify)) || (argc >= 9 && !get_mesh_quadric(env, argv[8], &q, &quadric)) || (argc == 10 && !get_mesh_occlusion(env, argv[9], &ao, &occlusion)) || (quadric && !simplify)) {
-    napi_throw_type_error(env, nullptr, "extractMesh(ctx, scene, grid, params | null[, sharp | null[, keep | null[, components[, simplify | null[, quadric | null[, occlusion | null]]]]]])");
+      (argc >= 8 && !get_mesh_simplify(env, argv[7], &c, &simplify)) || (argc >= 9 && !get_mesh_quadric(env, argv[8], &q, &quadric)) || (argc >= 10 && !get_mesh_occlusion(env, argv[9], &ao, &occlusion)) || (argc == 11 && !get_bool(env, argv[10], &measures)) || (quadric && !simplify)) {
+    napi_throw_type_error(env, nullptr, "extractMesh(ctx, scene, grid, params | null[, sharp | null[, keep | null[, components[, simplify | null[, quadric | null[, occlusion | null[, measures]]]]]]])");
     return nullptr;
   }
   rm_mesh* mesh = nullptr;
@@ -796,29 +841,29 @@ static napi_value ExtractMesh(napi_env env, napi_callback_info info) {
     if (rm_mesh_extract_sharp(ctx, scene, &g, &p, &s, &mesh) != RM_OK) return throw_rm(env, ctx, "rm_mesh_extract_sharp");
   } else if (rm_mesh_extract(ctx, scene, &g, &p, &mesh) != RM_OK) return throw_rm(env, ctx, "rm_mesh_extract");
   return mesh_result(env, ctx, mesh, p.normals != 0, p.colours != 0, keep ? &k : nullptr, components, simplify ? &c : nullptr, quadric ? &q : nullptr, scene,
-                     occlusion ? &ao : nullptr);
+                     occlusion ? &ao : nullptr, measures);
 }
 
-// meshFromValues(ctx, grid, values: Float32Array(corners), iso[, keep | null[, components[, simplify | null[, quadric | null]]]]) = rm_mesh_from_values,
+// meshFromValues(ctx, grid, values: Float32Array(corners), iso[, keep | null[, components[, simplify | null[, quadric | null[, measures]]]]]) = rm_mesh_from_values,
 // with a simplify block rm_mesh_simplify (with a quadric block too: rm_mesh_simplify_quadric) behind it, with a keep block rm_mesh_filter behind
-// that, then the arrays
+// that, with measures rm_mesh_measure on that last mesh, then the arrays
 static napi_value MeshFromValues(napi_env env, napi_callback_info info) {
-  size_t argc = 8;
-  napi_value argv[8];
+  size_t argc = 9;
+  napi_value argv[9];
   NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
-  rm_ctx* ctx = argc >= 4 && argc <= 8 ? get_external<rm_ctx>(env, argv[0]) : nullptr;
+  rm_ctx* ctx = argc >= 4 && argc <= 9 ? get_external<rm_ctx>(env, argv[0]) : nullptr;
   RmMeshKeep k;
   MeshSimplifyBlock c;
   RmMeshQuadric q;
-  bool keep = false, components = false, simplify = false, quadric = false;
+  bool keep = false, components = false, simplify = false, quadric = false, measures = false;
   RmGrid g;
   double iso = 0.0;
   void* d = nullptr;
   size_t n = 0;
   if (!ctx || !get_grid(env, argv[1], &g) || !get_buffer(env, argv[2], &d, &n) || napi_get_value_double(env, argv[3], &iso) != napi_ok ||
       (argc >= 5 && !get_mesh_keep(env, argv[4], &k, &keep)) || (argc >= 6 && !get_bool(env, argv[5], &components)) ||
-      (argc >= 7 && !get_mesh_simplify(env, argv[6], &c, &simplify)) || (argc == 8 && !get_mesh_quadric(env, argv[7], &q, &quadric)) || (quadric && !simplify)) {
-    napi_throw_type_error(env, nullptr, "meshFromValues(ctx, grid, values: Float32Array, iso[, keep | null[, components[, simplify | null[, quadric | null]]]])");
+      (argc >= 7 && !get_mesh_simplify(env, argv[6], &c, &simplify)) || (argc >= 8 && !get_mesh_quadric(env, argv[7], &q, &quadric)) || (argc == 9 && !get_bool(env, argv[8], &measures)) || (quadric && !simplify)) {
+    napi_throw_type_error(env, nullptr, "meshFromValues(ctx, grid, values: Float32Array, iso[, keep | null[, components[, simplify | null[, quadric | null[, measures]]]]])");
     return nullptr;
   }
   float probe[1025];
@@ -829,7 +874,7 @@ static napi_value MeshFromValues(napi_env env, napi_callback_info info) {
   }
   rm_mesh* mesh = nullptr;
   if (rm_mesh_from_values(ctx, &g, static_cast<const float*>(d), (float)iso, &mesh) != RM_OK) return throw_rm(env, ctx, "rm_mesh_from_values");
-  return mesh_result(env, ctx, mesh, false, false, keep ? &k : nullptr, components, simplify ? &c : nullptr, quadric ? &q : nullptr);
+  return mesh_result(env, ctx, mesh, false, false, keep ? &k : nullptr, components, simplify ? &c : nullptr, quadric ? &q : nullptr, nullptr, nullptr, measures);
 }
 
 // fbCreateStriped(ctx, width, height, stripeRows, parts, part[, gbuffer]): the stripes k with k % parts == part of a width x height image,
@@ -1028,7 +1073,7 @@ static napi_value Sizes(napi_env env, napi_callback_info) {
       {"RmMaterial", (uint32_t)sizeof(RmMaterial)}, {"RmRect", (uint32_t)sizeof(RmRect)}, {"RmSurface", (uint32_t)sizeof(RmSurface)}, {"RmDenoise", (uint32_t)sizeof(RmDenoise)},
       {"RmDenoiseVariance", (uint32_t)sizeof(RmDenoiseVariance)}, {"RmDespeckle", (uint32_t)sizeof(RmDespeckle)}, {"RmFilters", (uint32_t)sizeof(RmFilters)}, {"RmFrameStats", (uint32_t)sizeof(RmFrameStats)},
       {"RmAutoExposure", (uint32_t)sizeof(RmAutoExposure)}, {"RmDisplay", (uint32_t)sizeof(RmDisplay)}, {"RmGrid", (uint32_t)sizeof(RmGrid)},
-      {"RmMeshParams", (uint32_t)sizeof(RmMeshParams)}, {"RmMeshSharp", (uint32_t)sizeof(RmMeshSharp)}, {"RmMeshKeep", (uint32_t)sizeof(RmMeshKeep)}, {"RmMeshSimplify", (uint32_t)sizeof(RmMeshSimplify)}, {"RmMeshQuadric", (uint32_t)sizeof(RmMeshQuadric)}, {"RmMeshOcclusion", (uint32_t)sizeof(RmMeshOcclusion)}, {"abi", (uint32_t)rm_abi_version()}};
+      {"RmMeshParams", (uint32_t)sizeof(RmMeshParams)}, {"RmMeshSharp", (uint32_t)sizeof(RmMeshSharp)}, {"RmMeshKeep", (uint32_t)sizeof(RmMeshKeep)}, {"RmMeshSimplify", (uint32_t)sizeof(RmMeshSimplify)}, {"RmMeshQuadric", (uint32_t)sizeof(RmMeshQuadric)}, {"RmMeshOcclusion", (uint32_t)sizeof(RmMeshOcclusion)}, {"RmMeshMeasures", (uint32_t)sizeof(RmMeshMeasures)}, {"abi", (uint32_t)rm_abi_version()}};
   for (const auto& it : items) {
     NAPI_OK(napi_create_uint32(env, it.v, &v));
     NAPI_OK(napi_set_named_property(env, o, it.k, v));

@@ -172,7 +172,8 @@ class Mesh:
     """A triangle mesh as numpy arrays: positions [V, 3] float32, triangles [T, 3] uint32 (counter-clockwise seen from outside), cells
     [V] uint32 (each vertex's linear cell index in `grid`), and normals / colours [V, 3] float32 or None.  labels [V] uint32 (each vertex's
     connected component) and component_sizes [C, 2] uint32 ((vertices, triangles) per component) only when the call asked for components.
-    occlusion [V] float32 (1 = open; rm_mesh_occlusion) only when the call asked for it."""
+    occlusion [V] float32 (1 = open; rm_mesh_occlusion) only when the call asked for it.  measures (rm_mesh_measure; only when the call asked
+    for them): a dict of abi.RmMeshMeasures' fields plus component_edges, [C, 4] uint64 (edges, boundary, irregular, unbalanced)."""
     positions: np.ndarray
     triangles: np.ndarray
     cells: Optional[np.ndarray] = None
@@ -183,6 +184,7 @@ class Mesh:
     labels: Optional[np.ndarray] = None
     component_sizes: Optional[np.ndarray] = None
     occlusion = None  # Optional[np.ndarray]; an attribute that the constructor takes by keyword (below): the dataclass's own fields stay as they were
+    measures = None  # Optional[dict]; taken the same way
 
     @property
     def vertices(self) -> int:
@@ -190,9 +192,10 @@ class Mesh:
 
 
 def _with_occlusion(init):
-    def __init__(self, *args, occlusion=None, **fields):
+    def __init__(self, *args, occlusion=None, measures=None, **fields):
         init(self, *args, **fields)
         self.occlusion = occlusion
+        self.measures = measures
 
     __init__.__doc__, __init__.__wrapped__ = init.__doc__, init
     return __init__
@@ -270,3 +273,32 @@ def encode_ply(mesh: Mesh) -> bytes:
 def write_ply(mesh: Mesh, path) -> None:
     with open(path, "wb") as f:
         f.write(encode_ply(mesh))
+
+
+def encode_stl(mesh: Mesh) -> bytes:
+    """Binary STL: 80 header bytes (`hip_raymarch mesh`, zero padded), uint32 T, then per triangle the facet normal, p0, p1, p2 as
+    little-endian float32 and a uint16 0.  The normal is computed in double from the float32 coordinates, every operation rounded on its
+    own: e1 = p1 - p0, e2 = p2 - p0, c = e1 x e2, len = sqrt((cx cx + cy cy) + cz cz), c / len rounded to float32 -- and (0, 0, 0) where
+    len is not > 0 or not finite.  js/index.js encodeStl gives the same bytes."""
+    p = np.asarray(mesh.positions, np.float32).reshape(-1, 3)
+    t = np.asarray(mesh.triangles, np.uint32).reshape(-1, 3)
+    if len(t) >= 2 ** 32:
+        raise ValueError("mesh: an STL file holds fewer than 2^32 triangles")
+    corners = p[t.astype(np.int64)]  # [T, 3, 3]
+    d = corners.astype(np.float64)
+    e1, e2 = d[:, 1] - d[:, 0], d[:, 2] - d[:, 0]
+    with np.errstate(all="ignore"):
+        c = np.stack([e1[:, 1] * e2[:, 2] - e1[:, 2] * e2[:, 1], e1[:, 2] * e2[:, 0] - e1[:, 0] * e2[:, 2], e1[:, 0] * e2[:, 1] - e1[:, 1] * e2[:, 0]], axis=1)
+        length = np.sqrt((c[:, 0] * c[:, 0] + c[:, 1] * c[:, 1]) + c[:, 2] * c[:, 2])
+        good = (length > 0) & np.isfinite(length)
+        normal = np.where(good[:, None], c / np.where(good, length, 1.0)[:, None], 0.0).astype(np.float32)
+    facets = np.zeros(len(t), np.dtype([("normal", "<f4", 3), ("corners", "<f4", (3, 3)), ("attribute", "<u2")]))
+    facets["normal"] = normal
+    facets["corners"] = corners
+    header = b"hip_raymarch mesh".ljust(80, b"\0")
+    return header + np.uint32(len(t)).astype("<u4").tobytes() + facets.tobytes()
+
+
+def write_stl(mesh: Mesh, path) -> None:
+    with open(path, "wb") as f:
+        f.write(encode_stl(mesh))

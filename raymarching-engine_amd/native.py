@@ -45,6 +45,7 @@ EXPORTS = [
     "rm_mesh_keep_default", "rm_mesh_components", "rm_mesh_components_download", "rm_mesh_filter",
     "rm_mesh_simplify_default", "rm_mesh_simplify", "rm_mesh_quadric_default", "rm_mesh_simplify_quadric",
     "rm_mesh_occlusion_default", "rm_mesh_occlusion_directions", "rm_mesh_occlusion",
+    "rm_mesh_measure", "rm_mesh_measure_components",
 ]
 
 # G-buffer formats of a framebuffer (include/hip_raymarch.h RM_GBUFFER_*): "f32" (the default: the software GL stack's planes, which the
@@ -424,6 +425,8 @@ def load_library(path=None):
         "rm_mesh_occlusion_default": (None, [C.POINTER(abi.RmMeshOcclusion)]),
         "rm_mesh_occlusion_directions": (ip, [ip, fp]),
         "rm_mesh_occlusion": (ip, [vp, vp, C.POINTER(abi.RmMeshOcclusion), fp, fp]),
+        "rm_mesh_measure": (ip, [vp, C.POINTER(abi.RmMeshMeasures), fp]),
+        "rm_mesh_measure_components": (ip, [vp, vp, C.c_size_t]),
     }
     for name, (res, args) in sig.items():
         if name.startswith("rm_debug_") and not hasattr(lib, name) and os.environ.get("RM_LIB"):
@@ -720,13 +723,14 @@ class Context:
         g = grid.to_c()
         self._check(self.lib.rm_sdf_grid_device(self.h, scene.h, C.byref(g), int(flags), C.c_void_p(out_ptr), C.c_void_p(stream) if stream else None))
 
-    def _take_mesh(self, handle, grid, normals=False, colours=False, keep=None, components=False, simplify=None, quadric=None, scene=None, occlusion=None):
+    def _take_mesh(self, handle, grid, normals=False, colours=False, keep=None, components=False, simplify=None, quadric=None, scene=None, occlusion=None, measures=False):
         """The arrays of a mesh handle as a mesh.Mesh (normals / colours: whether the call that made it asked for them); destroys the handle.
         simplify (_mesh_simplify's triple): the mesh is first clustered on the device (rm_mesh_simplify) and the Mesh's grid is the cluster grid,
         which its cells then index -- with quadric (an abi.RmMeshQuadric) by rm_mesh_simplify_quadric; keep (an abi.RmMeshKeep): that mesh is filtered on the device (rm_mesh_filter), which also removes the vertices
         simplification left without triangles; the last of them is what is downloaded.  components: its labels and component sizes come with it.
         occlusion (an abi.RmMeshOcclusion, with the scene): that last mesh's ambient occlusion comes with it (rm_mesh_occlusion), and the
-        timings gain "occlusion", the milliseconds of its probes and taps."""
+        timings gain "occlusion", the milliseconds of its probes and taps.  measures: that last mesh is measured before anything is downloaded
+        (rm_mesh_measure, rm_mesh_measure_components): Mesh.measures, and the timings gain "measures", the milliseconds of topology and geometry."""
         from .mesh import Mesh
 
         handles = [handle]
@@ -745,6 +749,13 @@ class Context:
                 self._check(self.lib.rm_mesh_filter(handle, C.byref(keep), C.byref(filtered)))
                 handles.append(filtered)
                 handle = filtered
+            measured = None
+            if measures:
+                block, measure_ms = abi.RmMeshMeasures(), (C.c_float * 2)()
+                self._check(self.lib.rm_mesh_measure(handle, C.byref(block), measure_ms))
+                rows = np.empty((int(block.components), 4), np.uint64)
+                self._check(self.lib.rm_mesh_measure_components(handle, rows.ctypes.data_as(C.c_void_p), rows.nbytes))
+                measured = dict(abi.mesh_measures_dict(block), component_edges=rows)
             counts, ms = (C.c_ulonglong * 2)(), (C.c_float * 3)()
             self._check(self.lib.rm_mesh_counts(handle, counts))
             self._check(self.lib.rm_mesh_timings(handle, ms))
@@ -773,6 +784,9 @@ class Context:
                 self._check(self.lib.rm_mesh_occlusion(handle, scene.h, C.byref(occlusion), _fp(ao), ms2))
                 arrays["occlusion"] = ao
                 timings["occlusion"] = float(ms2[0]) + float(ms2[1])
+            if measured is not None:
+                arrays["measures"] = measured
+                timings["measures"] = float(measure_ms[0]) + float(measure_ms[1])
             return Mesh(grid=grid, timings=timings, **arrays)
         finally:
             for h in reversed(handles):
@@ -841,7 +855,8 @@ class Context:
         raise ValueError("mesh: simplify must be None, a mesh.Grid, a dict of mesh_simplify's arguments or its (abi.RmGrid, abi.RmMeshSimplify)")
 
     def extract_mesh(self, scene: "SceneHandle", grid, iso: float = 0.0, normals: bool = True, colours: bool = False, flags: int = 0,
-                     normal_delta: float = 1e-5, sharp=None, *, keep=None, components: bool = False, simplify=None, quadric=None, occlusion=None):
+                     normal_delta: float = 1e-5, sharp=None, *, keep=None, components: bool = False, simplify=None, quadric=None,
+                     measures: bool = False, occlusion=None):
         """The level set `iso` of the scene on `grid` (mesh.Grid) as a mesh.Mesh: rm_mesh_extract -- the distances sampled and meshed
         (surface nets) on the device, with per-vertex normals / diffuse colours from the scene's probes when asked for.  `sharp`: None is
         that call; True (the defaults), a dict of mesh.mesh_sharp's arguments or an abi.RmMeshSharp is rm_mesh_extract_sharp -- the same
@@ -855,7 +870,10 @@ class Context:
         mesh with every cluster's vertex at the minimiser of its plane quadrics, which keeps the edges and corners inside a cluster.
         `occlusion`: None is that mesh; True (the defaults), a dict of mesh.mesh_occlusion's arguments or an abi.RmMeshOcclusion bakes the
         scene's ambient occlusion at the vertices of the mesh that is returned -- behind `simplify`, `keep` and `components` -- into
-        Mesh.occlusion (rm_mesh_occlusion; 1 = open), which encode_ply writes as `quality` and mesh.shaded multiplies into the colours."""
+        Mesh.occlusion (rm_mesh_occlusion; 1 = open), which encode_ply writes as `quality` and mesh.shaded multiplies into the colours.
+        `measures`: True measures the mesh that is returned on the device -- behind `simplify` and `keep`, before the download -- into
+        Mesh.measures (rm_mesh_measure): a dict of abi.RmMeshMeasures' fields (lo and hi as tuples, closed as bool) plus component_edges,
+        [C, 4] uint64 rows of (edges, boundary, irregular, unbalanced) per component."""
         from .mesh import mesh_params
 
         keep, simplify, quadric = self._mesh_keep(keep), self._mesh_simplify(simplify), self._mesh_quadric(quadric, simplify)  # (refused before anything runs)
@@ -868,11 +886,12 @@ class Context:
         else:
             self._check(self.lib.rm_mesh_extract_sharp(self.h, scene.h, C.byref(g), C.byref(p), C.byref(s), C.byref(h)))
         return self._take_mesh(h, grid, normals=p.normals, colours=p.colours, keep=keep, components=components, simplify=simplify, quadric=quadric,
-                               scene=scene, occlusion=occlusion)
+                               scene=scene, occlusion=occlusion, measures=measures)
 
-    def mesh_from_values(self, grid, values: np.ndarray, iso: float = 0.0, *, keep=None, components: bool = False, simplify=None, quadric=None):
+    def mesh_from_values(self, grid, values: np.ndarray, iso: float = 0.0, *, keep=None, components: bool = False, simplify=None, quadric=None,
+                         measures: bool = False):
         """The mesher alone on the caller's field: `values` float32 [nz + 1, ny + 1, nx + 1] (rm_mesh_from_values).  keep, components,
-        simplify and quadric: as in extract_mesh."""
+        simplify, quadric and measures: as in extract_mesh."""
         keep, simplify, quadric = self._mesh_keep(keep), self._mesh_simplify(simplify), self._mesh_quadric(quadric, simplify)
         g = grid.to_c()
         v = np.ascontiguousarray(values, np.float32)
@@ -880,7 +899,7 @@ class Context:
             raise ValueError(f"values must have the shape {grid.shape} of the grid's corners, not {v.shape}")
         h = C.c_void_p()
         self._check(self.lib.rm_mesh_from_values(self.h, C.byref(g), _fp(v), float(iso), C.byref(h)))
-        return self._take_mesh(h, grid, keep=keep, components=components, simplify=simplify, quadric=quadric)
+        return self._take_mesh(h, grid, keep=keep, components=components, simplify=simplify, quadric=quadric, measures=measures)
 
     def probe_camera(self, uniforms: abi.RmUniforms, width: int, height: int) -> np.ndarray:
         out = np.empty((height, width, 8), np.float32)
