@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define RM_ABI_VERSION 9 /* 9: RM_GBUFFER_F32 / _F16, rm_fb_create_fmt, rm_fb_create_striped_fmt, rm_fb_wrap_fmt, rm_fb_gbuffer, rm_fb_download_raw, rm_fb_upload_raw, RmDenoise, rm_denoise_default, rm_denoise, rm_denoise_device, rm_present_denoised, RM_FB_MOMENTS, RM_PLANE_MOMENTS, rm_fb_has_moments, RmDenoiseVariance, rm_denoise_variance_default, rm_denoise_variance, rm_denoise_variance_device, rm_present_denoised_variance, RmDespeckle, RmFilters, RM_DENOISE_NONE / _ATROUS / _VARIANCE, rm_filters_default, rm_filter, rm_filter_device, rm_present_filtered, RM_STATS_BINS, RmFrameStats, rm_frame_stats, RmAutoExposure, rm_auto_exposure_default, rm_stats_percentile, rm_stats_exposure, RM_TONE_CLIP / _REINHARD / _ACES, RmDisplay, rm_display_default, rm_present_display, rm_present_display_device, rm_present_linear, RmGrid, rm_grid_axis, rm_sdf_grid, rm_sdf_grid_device, RmMeshParams, rm_mesh_params_default, rm_mesh, rm_mesh_extract, rm_mesh_from_values, rm_mesh_counts, rm_mesh_timings, RM_MESH_POSITIONS / _NORMALS / _COLOURS / _TRIANGLES / _CELLS, rm_mesh_download, rm_mesh_device_ptr, rm_mesh_destroy, RmMeshSharp, rm_mesh_sharp_default, rm_mesh_extract_sharp, RmMeshKeep, rm_mesh_keep_default, rm_mesh_components, RM_MESH_PART_LABELS / _SIZES, rm_mesh_components_download, rm_mesh_filter, RmMeshSimplify, rm_mesh_simplify_default, rm_mesh_simplify, RmMeshQuadric, rm_mesh_quadric_default, rm_mesh_simplify_quadric, RmMeshOcclusion, rm_mesh_occlusion_default, rm_mesh_occlusion_directions, rm_mesh_occlusion, RmMeshMeasures, rm_mesh_measure, rm_mesh_measure_components (additions only); 8: RM_PRIM_TORUS / _CYLINDER / _PLANE, RM_OP_SMOOTH_SUBTRACT / _INTERSECT, rm_probe_math (additions only); 7: rm_present_sharded_finish / rm_present_sharded take the size of the host buffer (a changed signature), rm_ctx_set_cull_min_pixels, rm_ctx_set_cull_budget, rm_ctx_cull_stats; 6: rm_present_striped_rows, rm_present_sharded_start / _finish, rm_ctx_last_warning, RM_PROBE_CAST_SHADOW, RM_PRIM_KIND (additions only); 3: rm_ctx_set_sample_batch, rm_buffer_*; 4: rm_ctx_set_gl_stack; 5: RmSurface / RmSceneDesc.surfaces (the struct grew), rm_pack_present_rows, rm_present_sharded, rm_ctx_last_pipeline, RM_RENDER_NO_FAR_JUMP, RM_RENDER_NO_CULL (additions only) */
+#define RM_ABI_VERSION 9 /* 9: RM_GBUFFER_F32 / _F16, rm_fb_create_fmt, rm_fb_create_striped_fmt, rm_fb_wrap_fmt, rm_fb_gbuffer, rm_fb_download_raw, rm_fb_upload_raw, RmDenoise, rm_denoise_default, rm_denoise, rm_denoise_device, rm_present_denoised, RM_FB_MOMENTS, RM_PLANE_MOMENTS, rm_fb_has_moments, RmDenoiseVariance, rm_denoise_variance_default, rm_denoise_variance, rm_denoise_variance_device, rm_present_denoised_variance, RmDespeckle, RmFilters, RM_DENOISE_NONE / _ATROUS / _VARIANCE, rm_filters_default, rm_filter, rm_filter_device, rm_present_filtered, RM_STATS_BINS, RmFrameStats, rm_frame_stats, RmAutoExposure, rm_auto_exposure_default, rm_stats_percentile, rm_stats_exposure, RM_TONE_CLIP / _REINHARD / _ACES, RmDisplay, rm_display_default, rm_present_display, rm_present_display_device, rm_present_linear, RmGrid, rm_grid_axis, rm_sdf_grid, rm_sdf_grid_device, RmMeshParams, rm_mesh_params_default, rm_mesh, rm_mesh_extract, rm_mesh_from_values, rm_mesh_counts, rm_mesh_timings, RM_MESH_POSITIONS / _NORMALS / _COLOURS / _TRIANGLES / _CELLS, rm_mesh_download, rm_mesh_device_ptr, rm_mesh_destroy, RmMeshSharp, rm_mesh_sharp_default, rm_mesh_extract_sharp, RmMeshKeep, rm_mesh_keep_default, rm_mesh_components, RM_MESH_PART_LABELS / _SIZES, rm_mesh_components_download, rm_mesh_filter, RmMeshSimplify, rm_mesh_simplify_default, rm_mesh_simplify, RmMeshQuadric, rm_mesh_quadric_default, rm_mesh_simplify_quadric, RmMeshOcclusion, rm_mesh_occlusion_default, rm_mesh_occlusion_directions, rm_mesh_occlusion, RmMeshMeasures, rm_mesh_measure, rm_mesh_measure_components, RmMeshSlabs, rm_mesh_slabs_default, rm_mesh_extract_slabs, rm_mesh_extract_sharp_slabs, rm_mesh_from_values_slabs (additions only); 8: RM_PRIM_TORUS / _CYLINDER / _PLANE, RM_OP_SMOOTH_SUBTRACT / _INTERSECT, rm_probe_math (additions only); 7: rm_present_sharded_finish / rm_present_sharded take the size of the host buffer (a changed signature), rm_ctx_set_cull_min_pixels, rm_ctx_set_cull_budget, rm_ctx_cull_stats; 6: rm_present_striped_rows, rm_present_sharded_start / _finish, rm_ctx_last_warning, RM_PROBE_CAST_SHADOW, RM_PRIM_KIND (additions only); 3: rm_ctx_set_sample_batch, rm_buffer_*; 4: rm_ctx_set_gl_stack; 5: RmSurface / RmSceneDesc.surfaces (the struct grew), rm_pack_present_rows, rm_present_sharded, rm_ctx_last_pipeline, RM_RENDER_NO_FAR_JUMP, RM_RENDER_NO_CULL (additions only) */
 
 #define RM_MAX_BOUNCES 10 /* raymarchingStepCountsArray[10], raymarcher.frag:31 */
 #define RM_MAX_LIGHTS 10  /* lightPositions[10],             raymarcher.frag:37-39 */
@@ -1188,6 +1188,49 @@ typedef struct RmMeshMeasures {            /* 160 bytes */
 } RmMeshMeasures;
 RM_API int rm_mesh_measure(rm_mesh* mesh, RmMeshMeasures* out, float* out_ms2);
 RM_API int rm_mesh_measure_components(rm_mesh* mesh, void* host, size_t bytes);
+
+/* ---- slabbed extraction (opt-in): grids beyond 2^28 corners, meshed in windows of z layers ----
+ * rm_mesh_extract, _sharp and _from_values hold the whole corner field at once and refuse more than 2^28 corners (about 645^3).  The three
+ * entries below walk the grid in SLABS of cell layers, hold one window of values at a time, and give one ordinary rm_mesh: every later
+ * stage (components, filter, simplify, quadric, occlusion, measure, the downloads) serves it unchanged, so a labelling runs across slabs.
+ * Contract: wherever the unslabbed entry runs, all arrays of the result (RM_MESH_POSITIONS, _TRIANGLES, _CELLS, and _NORMALS / _COLOURS
+ * when asked for) and rm_mesh_counts are byte for byte that entry's, for every scene, flag combination and admissible `layers`; `layers`
+ * never changes a byte of a result.
+ * Grid rule (these three entries only): RmGrid's rule without the bound on the corners -- 1 <= n[a] <= 1024 stays, so a grid has at most
+ *   2^30 cells, and RM_MESH_CELLS (the linear cell index in the WHOLE grid) and the uint32 vertex indices still hold.  Totals are 64-bit.
+ * Window.  slabs == NULL: the defaults (layers 0).  layers = L >= 1 is the number of cell layers per slab; above nz it is nz.  Slab s owns
+ *   the layers s L .. min(nz, (s + 1) L) - 1.  The window of a slab that starts at layer k0 > 0 also covers the HALO layer k0 - 1: corner
+ *   planes k0 - 1 .. k0 + L.  (L + 2) (nx + 1) (ny + 1) must not exceed 2^28, so every index inside a window is an int.  layers == 0: the
+ *   largest L whose (L + 2) (nx + 1) (ny + 1) stays within 2^26 corners (profiles/mesh_slabs.txt), at least 1.
+ * Procedure (rm_mesh_kernels.inc "slabbed extraction"), two passes over the slabs; a window's values are indexed from its first plane:
+ *   1. Tally.  Per slab: its own planes k0 .. k0 + L are filled -- by the sampler of rm_sdf_grid with the plane's index in the whole grid
+ *      (z = lo[2] + (float)k * h[2]: the dense sampler's bits), or for rm_mesh_from_values_slabs by a copy of those planes -- and one
+ *      thread per own cell evaluates the mesher's (active, quads); the words are summed in the wave, in the workgroup, and by one 64-bit
+ *      integer atomic add per workgroup into the slab's total.  Integer sums: the same on every run.  One read of the totals gives every
+ *      slab's vertex and triangle base and the sizes of the three arrays, which are allocated once.
+ *   2. Emit.  Per slab with at least one vertex (the others are skipped, their second sampling saved): the window is filled again, halo
+ *      plane included (the planes two windows share are sampled again, not kept); count over the window's cells, the halo's first; the
+ *      scan of rm_mesh_extract; emit, where halo cells emit nothing, a cell's vertex index is scanned[cell] - scanned[first own cell] +
+ *      the slab's vertex base (its neighbours' likewise), RM_MESH_CELLS is the cell's index in the whole grid, and the boundary rule of
+ *      the quads uses the indices in the whole grid.
+ *   3. rm_mesh_extract_sharp_slabs: the kernels of "sharp vertices" run per slab behind its emit, on the slab's run of vertices, while the
+ *      window's values are resident; "12 V > INT_MAX" applies per slab.
+ *   4. Normals and colours: the probes of rm_mesh_extract, once, on the finished arrays.
+ * rm_mesh_timings: {sampling or upload, both passes; tally, count, scan, emit and sharpening; attributes}, summed over the windows.
+ * Memory: (L + 2)(nx + 1)(ny + 1) floats and (L + 1) nx ny 64-bit counts, allocated once per call, beside the mesh itself.
+ * Refused (RM_ERR_INVALID), in this order and before the handles are looked at: the grid; params; sharp; then slabs -- layers < 0, reserved
+ * != 0, "slab window ..." above 2^28 corners (rm_mesh_from_values_slabs: the grid, iso, slabs).  Then a NULL handle or out ("NULL
+ * argument") and a scene of another context.  RM_ERR_DEVICE: a failed allocation, with nothing leaked; a slab whose second sampling does not
+ * count what its first counted (the host compares the scan's total with the tally before the emit writes anything). */
+typedef struct RmMeshSlabs {  /* 8 bytes */
+  int32_t layers;             /* cell layers per slab; 0 = chosen by the library */
+  int32_t reserved;           /* must be 0 */
+} RmMeshSlabs;
+RM_API void rm_mesh_slabs_default(RmMeshSlabs* slabs);
+RM_API int rm_mesh_extract_slabs(rm_ctx* ctx, rm_scene* scene, const RmGrid* grid, const RmMeshParams* params, const RmMeshSlabs* slabs, rm_mesh** out);
+RM_API int rm_mesh_extract_sharp_slabs(rm_ctx* ctx, rm_scene* scene, const RmGrid* grid, const RmMeshParams* params, const RmMeshSharp* sharp,
+                                       const RmMeshSlabs* slabs, rm_mesh** out);
+RM_API int rm_mesh_from_values_slabs(rm_ctx* ctx, const RmGrid* grid, const float* values_host, float iso, const RmMeshSlabs* slabs, rm_mesh** out);
 
 #ifdef __cplusplus
 }

@@ -363,6 +363,20 @@ class RmMeshMeasures(C.Structure):
 assert C.sizeof(RmMeshMeasures) == 160
 
 
+class RmMeshSlabs(C.Structure):
+    """The window of rm_mesh_extract_slabs / _sharp_slabs / rm_mesh_from_values_slabs (ABI 9): cell layers per slab, 0 = chosen by the library
+    (include/hip_raymarch.h "slabbed extraction")."""
+    _fields_ = [
+        ("layers", C.c_int32),
+        ("reserved", C.c_int32),
+    ]
+
+
+MESH_SLABS_DEFAULTS = dict(layers=0)  # rm_mesh_slabs_default
+
+assert C.sizeof(RmMeshSlabs) == 8
+
+
 def mesh_measures_dict(m: "RmMeshMeasures") -> dict:
     """The struct's fields as a dict: lo and hi as tuples, `closed` as bool, `reserved` left out."""
     d = {name: getattr(m, name) for name, _ in RmMeshMeasures._fields_ if name != "reserved"}

@@ -30,8 +30,9 @@ static size_t mesh_array_bytes(const rm_mesh* m, int which) {
   return (size_t)m->vertices * (which == RM_MESH_CELLS || which == MESH_LABELS ? 4u : 12u);
 }
 
-// RmGrid's rule, and the grid as the kernels take it
-static int grid_check(const Refuse& refuse, const RmGrid* grid, GridDims* G) {
+// RmGrid's rule, and the grid as the kernels take it.  capped = false (the slabbed entries alone): without the bound on the corners, and then
+// G->corners, which cannot hold them, is 0 -- those entries work on windows with corner counts of their own.
+static int grid_check(const Refuse& refuse, const RmGrid* grid, GridDims* G, bool capped = true) {
   if (!grid) return refuse("NULL grid");
   long long corners = 1;
   for (int a = 0; a < 3; a++) {
@@ -45,9 +46,9 @@ static int grid_check(const Refuse& refuse, const RmGrid* grid, GridDims* G) {
     G->nc[a] = grid->n[a] + 1;
     corners *= grid->n[a] + 1;
   }
-  if (corners > (1ll << 28)) return refuse("grid must have at most 2^28 corners");
+  if (capped && corners > (1ll << 28)) return refuse("grid must have at most 2^28 corners");
   if (grid->reserved != 0) return refuse("grid reserved must be 0");
-  G->corners = (int)corners;
+  G->corners = corners > (1ll << 28) ? 0 : (int)corners;
   return RM_OK;
 }
 
@@ -82,14 +83,14 @@ void rm_mesh_params_default(RmMeshParams* params) {
   *params = RmMeshParams{0.0f, 1, 1e-5f, 0, 0, 0};
 }
 
-// the sampler on `stream`, with the culling grid as rm_probe obtains it
-static int sdf_grid_enqueue(const Refuse& refuse, rm_scene* scene, const GridDims& G, int flags, float* d_out, hipStream_t stream) {
+// the sampler on `stream`, with the culling grid as rm_probe obtains it; plane0 > 0: G is a window of a grid's z planes that begins there
+static int sdf_grid_enqueue(const Refuse& refuse, rm_scene* scene, const GridDims& G, int flags, float* d_out, hipStream_t stream, int plane0 = 0) {
   rm_ctx* ctx = refuse.ctx;
   RM_HIP(ctx, hipSetDevice(ctx->device));
   if (int rc = scene_cull_grid(ctx, scene, flags, 1ll << 40)) return rc;
   const bool foreign = stream != ctx->stream;
   if (foreign && ctx->cull_event) RM_HIP(ctx, hipStreamWaitEvent(stream, ctx->cull_event, 0));  // (the grid is built on a stream of its own)
-  SdfGridParams P{scene->dev, G, d_out};
+  SdfGridParams P{scene->dev, G, d_out, plane0};
   if (flags & RM_RENDER_NO_CULL) P.scene.cull.cells = nullptr;
   RM_HIP_AS(refuse, (flags & RM_RENDER_FAST) ? rm::launch_sdf_grid_fast(P, stream) : ctx->gl_stack ? rm_gl_launch_sdf_grid(&P, stream) : rm::launch_sdf_grid_strict(P, stream));
   if (foreign) {
@@ -208,25 +209,41 @@ static int mesh_attributes(rm_ctx* ctx, rm_scene* scene, const RmMeshParams& p, 
 }
 
 // Sharp vertices (the header's "sharp vertices"): the emitted mesh's positions become the QEF's.  Per vertex 12 slots of bracket, point and
-// probe output, owned here and gone when this returns; the scene is evaluated by the probe kernel on the slot arrays, one launch per round
-// and one for the normals.  Waits for the stream: the scratch is freed behind the last kernel that reads it.
-static int mesh_sharpen(const Refuse& refuse, rm_scene* scene, const GridDims& G, const float* d_values, const RmMeshParams& p, const RmMeshSharp& sharp, rm_mesh* mesh) {
-  rm_ctx* ctx = refuse.ctx;
-  if (mesh->vertices > (unsigned long long)INT_MAX / 12ull)
-    return refuse("the mesh has more vertices than the probe's int count holds twelve slots of (12 V > INT_MAX)", RM_ERR_DEVICE);
-  const size_t slots = 12u * (size_t)mesh->vertices;
+// probe output, the caller's (SharpScratch, reserved for at least `count` vertices); the scene is evaluated by the probe kernel on the slot
+// arrays, one launch per round and one for the normals.  Waits for the stream: the scratch may be freed, or used again, when this returns.
+// The vertices are `count` from `first` on, and d_values begins at the grid's plane `plane0`: the whole mesh over the whole grid (0, 0,
+// mesh->vertices), or one slab's run of vertices over its window (mesh_build_slabs).
+struct SharpScratch {
   DeviceArray state, points, probed, live;
-  RM_HIP(ctx, state.reserve(sizeof(float4) * slots));
-  RM_HIP(ctx, points.reserve(sizeof(float) * 3u * slots));
-  RM_HIP(ctx, probed.reserve(sizeof(float) * 3u * slots));
-  RM_HIP(ctx, live.reserve(sizeof(unsigned int) * (size_t)mesh->vertices));
+  hipError_t reserve(size_t vertices) {
+    const size_t slots = 12u * vertices;
+    hipError_t e = state.reserve(sizeof(float4) * slots);
+    if (e == hipSuccess) e = points.reserve(sizeof(float) * 3u * slots);
+    if (e == hipSuccess) e = probed.reserve(sizeof(float) * 3u * slots);
+    if (e == hipSuccess) e = live.reserve(sizeof(unsigned int) * vertices);
+    return e;
+  }
+};
+
+static int mesh_sharp_fits(const Refuse& refuse, unsigned long long vertices) {
+  if (vertices > (unsigned long long)INT_MAX / 12ull)
+    return refuse("the mesh has more vertices than the probe's int count holds twelve slots of (12 V > INT_MAX)", RM_ERR_DEVICE);
+  return RM_OK;
+}
+
+static int mesh_sharpen(const Refuse& refuse, rm_scene* scene, const GridDims& G, const float* d_values, int plane0, const RmMeshParams& p,
+                        const RmMeshSharp& sharp, rm_mesh* mesh, unsigned long long first, unsigned long long count, const SharpScratch& tmp) {
+  rm_ctx* ctx = refuse.ctx;
+  const size_t slots = 12u * (size_t)count;
+  const DeviceArray &points = tmp.points, &probed = tmp.probed;
   MeshSharpParams P{};
-  P.mesh = MeshParams{G, d_values, p.iso, nullptr, mesh->array[RM_MESH_POSITIONS].f32(), mesh->array[RM_MESH_CELLS].u32(), nullptr};
-  P.vertices = (int)mesh->vertices;
-  P.state = static_cast<float4*>(state.p);
+  P.mesh = MeshParams{G, d_values, p.iso, nullptr, mesh->array[RM_MESH_POSITIONS].f32() + 3u * (size_t)first, mesh->array[RM_MESH_CELLS].u32() + (size_t)first,
+                      nullptr, plane0};
+  P.vertices = (int)count;
+  P.state = static_cast<float4*>(tmp.state.p);
   P.points = points.f32();
   P.probed = probed.f32();
-  P.live = live.u32();
+  P.live = tmp.live.u32();
   P.threshold = sharp.threshold;
   RM_HIP(ctx, ctx->mesh_spans.begin(MeshSpans::SHARPEN, ctx->stream));
   RM_HIP(ctx, rm::launch_mesh_cross(P, 1, 0, sharp.refine == 0, ctx->stream));
@@ -271,6 +288,7 @@ static int mesh_extract(const Refuse& refuse, rm_scene* scene, const RmGrid* gri
   *out = nullptr;
   RM_HIP(ctx, hipSetDevice(ctx->device));
   DeviceArray values, material;  // (before the mesh: freed behind the wait of whatever gives the mesh up, or the one below)
+  SharpScratch sharp_tmp;
   RM_HIP(ctx, values.reserve(sizeof(float) * (size_t)G.corners));
   RM_HIP(ctx, ctx->mesh_spans.begin(MeshSpans::SAMPLE, ctx->stream));
   if (int rc = sdf_grid_enqueue(refuse, scene, G, p.flags, values.f32(), ctx->stream)) return rc;
@@ -280,8 +298,11 @@ static int mesh_extract(const Refuse& refuse, rm_scene* scene, const RmGrid* gri
   made->has[RM_MESH_NORMALS] = p.normals != 0;
   made->has[RM_MESH_COLOURS] = p.colours != 0;
   if (int rc = mesh_build(ctx, G, values.f32(), p.iso, made.get())) return rc;
-  if (sharpen && made->vertices > 0)
-    if (int rc = mesh_sharpen(refuse, scene, G, values.f32(), p, s, made.get())) return rc;
+  if (sharpen && made->vertices > 0) {
+    if (int rc = mesh_sharp_fits(refuse, made->vertices)) return rc;
+    RM_HIP(ctx, sharp_tmp.reserve((size_t)made->vertices));
+    if (int rc = mesh_sharpen(refuse, scene, G, values.f32(), 0, p, s, made.get(), 0, made->vertices, sharp_tmp)) return rc;
+  }
   const bool attributes = made->vertices > 0 && (p.normals || p.colours);
   if (attributes)
     if (int rc = mesh_attributes(ctx, scene, p, made.get(), material)) return rc;
@@ -298,6 +319,203 @@ int rm_mesh_extract(rm_ctx* ctx, rm_scene* scene, const RmGrid* grid, const RmMe
 
 int rm_mesh_extract_sharp(rm_ctx* ctx, rm_scene* scene, const RmGrid* grid, const RmMeshParams* params, const RmMeshSharp* sharp, rm_mesh** out) {
   return mesh_extract(Refuse{ctx, "rm_mesh_extract_sharp"}, scene, grid, params, true, sharp, out);
+}
+
+// ---- slabbed extraction (include/hip_raymarch.h "slabbed extraction") ------------------------------------------------------------------
+
+static const long long kMeshSlabWindow = 1ll << 26;  // the default budget of window corners (profiles/mesh_slabs.txt)
+
+void rm_mesh_slabs_default(RmMeshSlabs* slabs) {
+  if (!slabs) return;
+  *slabs = RmMeshSlabs{0, 0};
+}
+
+// RmMeshSlabs' rule on a checked grid: *layers = the cell layers per slab, in 1..nz
+static int mesh_slabs_check(const Refuse& refuse, const RmMeshSlabs* in, const GridDims& G, int* layers) {
+  RmMeshSlabs s;
+  rm_mesh_slabs_default(&s);
+  if (in) s = *in;
+  if (s.layers < 0) return refuse("slabs layers must be >= 0");
+  if (s.reserved != 0) return refuse("slabs reserved must be 0");
+  const long long plane = (long long)G.nc[0] * G.nc[1];
+  const int nz = G.nc[2] - 1;
+  long long L = s.layers;
+  if (L == 0) L = kMeshSlabWindow / plane - 2;
+  if (L < 1) L = 1;
+  if (L > nz) L = nz;
+  if ((L + 2) * plane > (1ll << 28)) return refuse("slab window (layers + 2) * (nx + 1) * (ny + 1) must be at most 2^28 corners");
+  *layers = (int)L;
+  return RM_OK;
+}
+
+// The slabbed mesher on the context's stream, into the mesh's three arrays: the tally pass over every slab, the totals read once, the emit
+// pass over the slabs that have vertices, each sharpened behind its emit when `sharp` is given.  A window is filled by the sampler (scene) or
+// from values_host; the planes two windows share are filled again, not kept.  Returns with the stream idle; mesh->ms[0] and ms[1] are the
+// sums over the windows.  The window buffers are the caller's `tmp`, declared before the mesh.
+struct SlabScratch {
+  DeviceArray values, counts, levels, totals;
+  SharpScratch sharp;
+};
+
+static int mesh_build_slabs(const Refuse& refuse, rm_scene* scene, const float* values_host, const GridDims& G, int L, const RmMeshParams& p,
+                            const RmMeshSharp* sharp, SlabScratch& tmp, rm_mesh* mesh) {
+  rm_ctx* ctx = refuse.ctx;
+  MeshSpans& spans = ctx->mesh_spans;
+  const int nz = G.nc[2] - 1, slabs = (nz + L - 1) / L;
+  const size_t plane = (size_t)G.nc[0] * G.nc[1], layer = (size_t)(G.nc[0] - 1) * (G.nc[1] - 1);
+  const int halo = slabs > 1 ? 1 : 0;  // (only a slab behind the first has one)
+  const long long window_cells = (long long)(L + halo) * (long long)layer;
+  const size_t level_elems = rm::rm_mesh_scan_scratch_elems(window_cells) + 1;  // ... and the scan's total behind the levels
+  RM_HIP(ctx, tmp.values.reserve(sizeof(float) * (size_t)(L + halo + 1) * plane));
+  RM_HIP(ctx, tmp.counts.reserve(sizeof(unsigned long long) * (size_t)window_cells));
+  RM_HIP(ctx, tmp.levels.reserve(sizeof(unsigned long long) * level_elems));
+  RM_HIP(ctx, tmp.totals.reserve(sizeof(unsigned long long) * (size_t)slabs));
+  RM_HIP(ctx, hipMemsetAsync(tmp.totals.p, 0, sizeof(unsigned long long) * (size_t)slabs, ctx->stream));
+  float* d_values = tmp.values.f32();
+  unsigned long long* d_scan_total = tmp.levels.u64() + (level_elems - 1);
+
+  // planes plane0 .. plane0 + planes - 1 into the window, in the SAMPLE span
+  const auto fill = [&](int plane0, int planes) -> int {
+    RM_HIP(ctx, spans.begin(MeshSpans::SAMPLE, ctx->stream));
+    if (values_host) {
+      RM_HIP(ctx, hipMemcpyAsync(d_values, values_host + (size_t)plane0 * plane, sizeof(float) * (size_t)planes * plane, hipMemcpyHostToDevice, ctx->stream));
+    } else {
+      GridDims W = G;
+      W.nc[2] = planes;
+      W.corners = (int)((size_t)planes * plane);
+      if (int rc = sdf_grid_enqueue(refuse, scene, W, p.flags, d_values, ctx->stream, plane0)) return rc;
+    }
+    RM_HIP(ctx, spans.end(MeshSpans::SAMPLE, ctx->stream));
+    return RM_OK;
+  };
+
+  MeshSlab S{};
+  S.mesh = MeshParams{G, d_values, p.iso, nullptr, nullptr, nullptr, nullptr, 0};
+  for (int s = 0; s < slabs; s++) {  // the tally pass: a slab's own planes are enough
+    S.own0 = S.mesh.plane0 = s * L;
+    S.layers = nz - S.own0 < L ? nz - S.own0 : L;
+    S.total = tmp.totals.u64() + s;
+    if (int rc = fill(S.own0, S.layers + 1)) return rc;
+    RM_HIP(ctx, spans.begin(MeshSpans::COUNT_SCAN, ctx->stream));
+    RM_HIP(ctx, rm::launch_mesh_slab_tally(S, ctx->stream));
+    RM_HIP(ctx, spans.end(MeshSpans::COUNT_SCAN, ctx->stream));
+    RM_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    mesh->ms[0] += spans.ms(MeshSpans::SAMPLE);
+    mesh->ms[1] += spans.ms(MeshSpans::COUNT_SCAN);
+  }
+  std::vector<unsigned long long> totals((size_t)slabs);
+  if (int rc = copy_and_wait(ctx, totals.data(), tmp.totals.p, sizeof(unsigned long long) * totals.size(), hipMemcpyDeviceToHost)) return rc;
+  unsigned long long vertices = 0, quads = 0, most = 0;
+  for (unsigned long long t : totals) {
+    vertices += t & 0xFFFFFFFFull;
+    quads += t >> 32;
+    if ((t & 0xFFFFFFFFull) > most) most = t & 0xFFFFFFFFull;
+  }
+  mesh->vertices = vertices;
+  mesh->triangles = 2ull * quads;
+  if (vertices == 0) return RM_OK;
+  if (sharp) {
+    if (int rc = mesh_sharp_fits(refuse, most)) return rc;  // (per slab: a slab's vertices are one run of the probe)
+    RM_HIP(ctx, tmp.sharp.reserve((size_t)most));
+  }
+  for (int what : {RM_MESH_POSITIONS, RM_MESH_CELLS, RM_MESH_TRIANGLES}) RM_HIP(ctx, mesh->array[what].reserve(mesh_array_bytes(mesh, what)));
+  S.mesh.counts = tmp.counts.u64();
+  S.mesh.positions = mesh->array[RM_MESH_POSITIONS].f32();
+  S.mesh.cells = mesh->array[RM_MESH_CELLS].u32();
+  S.mesh.triangles = mesh->array[RM_MESH_TRIANGLES].u32();
+  S.total = nullptr;
+  S.vertex_base = S.quad_base = 0;
+  for (int s = 0; s < slabs; s++) {  // the emit pass
+    const unsigned long long own_vertices = totals[(size_t)s] & 0xFFFFFFFFull, own_quads = totals[(size_t)s] >> 32;
+    if (own_vertices == 0) continue;  // (and no quads: the cell that owns one is active)
+    S.own0 = s * L;
+    S.mesh.plane0 = S.own0 > 0 ? S.own0 - 1 : 0;
+    S.layers = nz - S.own0 < L ? nz - S.own0 : L;
+    const int layers = S.own0 - S.mesh.plane0 + S.layers;  // (with the halo)
+    if (int rc = fill(S.mesh.plane0, layers + 1)) return rc;
+    RM_HIP(ctx, spans.begin(MeshSpans::COUNT_SCAN, ctx->stream));
+    RM_HIP(ctx, rm::launch_mesh_slab_count(S, ctx->stream));
+    RM_HIP(ctx, rm::launch_mesh_scan(S.mesh.counts, (long long)layers * (long long)layer, tmp.levels.u64(), d_scan_total, ctx->stream));
+    RM_HIP(ctx, spans.end(MeshSpans::COUNT_SCAN, ctx->stream));
+    // The emit writes at the tally's bases: what the scan counted of the slab's own cells has to be what the tally counted, or nothing is written.
+    unsigned long long all = 0, before = 0;
+    if (int rc = copy_and_wait(ctx, &all, d_scan_total, sizeof all, hipMemcpyDeviceToHost)) return rc;
+    if (int rc = copy_and_wait(ctx, &before, S.mesh.counts + (size_t)(S.own0 - S.mesh.plane0) * layer, sizeof before, hipMemcpyDeviceToHost)) return rc;
+    if (all - before != totals[(size_t)s]) return refuse("the two samplings of a slab disagree", RM_ERR_DEVICE);
+    RM_HIP(ctx, spans.begin(MeshSpans::EMIT, ctx->stream));
+    RM_HIP(ctx, rm::launch_mesh_slab_emit(S, ctx->stream));
+    RM_HIP(ctx, spans.end(MeshSpans::EMIT, ctx->stream));
+    RM_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    mesh->ms[0] += spans.ms(MeshSpans::SAMPLE);
+    mesh->ms[1] += spans.ms(MeshSpans::COUNT_SCAN) + spans.ms(MeshSpans::EMIT);
+    if (sharp)
+      if (int rc = mesh_sharpen(refuse, scene, G, d_values, S.mesh.plane0, p, *sharp, mesh, S.vertex_base, own_vertices, tmp.sharp)) return rc;
+    S.vertex_base += own_vertices;
+    S.quad_base += own_quads;
+  }
+  return RM_OK;
+}
+
+// rm_mesh_extract_slabs and rm_mesh_extract_sharp_slabs: mesh_extract's checks with the slabs' behind them, then mesh_build_slabs
+static int mesh_extract_slabs(const Refuse& refuse, rm_scene* scene, const RmGrid* grid, const RmMeshParams* params, bool sharpen, const RmMeshSharp* sharp,
+                              const RmMeshSlabs* slabs, rm_mesh** out) {
+  rm_ctx* ctx = refuse.ctx;
+  GridDims G{};
+  RmMeshParams p;
+  RmMeshSharp s{};
+  int layers = 0;
+  if (int rc = grid_check(refuse, grid, &G, false)) return rc;
+  if (int rc = mesh_params_check(refuse, params, &p)) return rc;
+  if (sharpen)
+    if (int rc = mesh_sharp_check(refuse, sharp, &s)) return rc;
+  if (int rc = mesh_slabs_check(refuse, slabs, G, &layers)) return rc;
+  if (int rc = scene_check(refuse, scene, out != nullptr)) return rc;
+  *out = nullptr;
+  RM_HIP(ctx, hipSetDevice(ctx->device));
+  SlabScratch tmp;  // (before the mesh: freed behind the wait of whatever gives the mesh up, or the one below)
+  DeviceArray material;
+  MeshPtr made(new (std::nothrow) rm_mesh(ctx), rm_mesh_destroy);
+  if (!made) return refuse("out of host memory", RM_ERR_DEVICE);
+  made->has[RM_MESH_NORMALS] = p.normals != 0;
+  made->has[RM_MESH_COLOURS] = p.colours != 0;
+  if (int rc = mesh_build_slabs(refuse, scene, nullptr, G, layers, p, sharpen ? &s : nullptr, tmp, made.get())) return rc;
+  const bool attributes = made->vertices > 0 && (p.normals || p.colours);
+  if (attributes)
+    if (int rc = mesh_attributes(ctx, scene, p, made.get(), material)) return rc;
+  if (hipStreamSynchronize(ctx->stream) != hipSuccess) return refuse("the stream failed", RM_ERR_DEVICE);
+  if (attributes) made->ms[2] = ctx->mesh_spans.ms(MeshSpans::ATTRIBUTES);
+  *out = made.release();
+  return RM_OK;
+}
+
+int rm_mesh_extract_slabs(rm_ctx* ctx, rm_scene* scene, const RmGrid* grid, const RmMeshParams* params, const RmMeshSlabs* slabs, rm_mesh** out) {
+  return mesh_extract_slabs(Refuse{ctx, "rm_mesh_extract_slabs"}, scene, grid, params, false, nullptr, slabs, out);
+}
+
+int rm_mesh_extract_sharp_slabs(rm_ctx* ctx, rm_scene* scene, const RmGrid* grid, const RmMeshParams* params, const RmMeshSharp* sharp,
+                                const RmMeshSlabs* slabs, rm_mesh** out) {
+  return mesh_extract_slabs(Refuse{ctx, "rm_mesh_extract_sharp_slabs"}, scene, grid, params, true, sharp, slabs, out);
+}
+
+int rm_mesh_from_values_slabs(rm_ctx* ctx, const RmGrid* grid, const float* values_host, float iso, const RmMeshSlabs* slabs, rm_mesh** out) {
+  const Refuse refuse{ctx, "rm_mesh_from_values_slabs"};
+  GridDims G{};
+  int layers = 0;
+  if (int rc = grid_check(refuse, grid, &G, false)) return rc;
+  if (!std::isfinite(iso)) return refuse("iso must be finite");
+  if (int rc = mesh_slabs_check(refuse, slabs, G, &layers)) return rc;
+  if (!ctx || !values_host || !out) return refuse("NULL argument");
+  *out = nullptr;
+  RM_HIP(ctx, hipSetDevice(ctx->device));
+  RmMeshParams p;
+  rm_mesh_params_default(&p);
+  p.iso = iso;
+  SlabScratch tmp;
+  MeshPtr made(new (std::nothrow) rm_mesh(ctx), rm_mesh_destroy);
+  if (!made) return refuse("out of host memory", RM_ERR_DEVICE);
+  if (int rc = mesh_build_slabs(refuse, nullptr, values_host, G, layers, p, nullptr, tmp, made.get())) return rc;
+  *out = made.release();
+  return RM_OK;
 }
 
 int rm_mesh_counts(const rm_mesh* mesh, unsigned long long* out2) {

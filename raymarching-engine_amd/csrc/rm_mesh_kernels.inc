@@ -17,7 +17,7 @@ __global__ __launch_bounds__(256) void rm_sdf_grid_kernel(const SdfGridParams P)
   const int gi = blockIdx.x * blockDim.x + threadIdx.x;
   const int c = gi < g.corners ? gi : g.corners - 1;
   const int i = c % g.nc[0], row = c / g.nc[0];
-  const v3 p = V(rm_grid_coord(g, 0, i), rm_grid_coord(g, 1, row % g.nc[1]), rm_grid_coord(g, 2, row / g.nc[1]));
+  const v3 p = V(rm_grid_coord(g, 0, i), rm_grid_coord(g, 1, row % g.nc[1]), rm_grid_coord(g, 2, row / g.nc[1] + P.plane0));  // (a window's plane by its index in the whole grid)
   enter_math_mode<KIND, FAST>();
   Sdf<KIND>::stage(P.scene, lds);
   __syncthreads();
@@ -177,7 +177,7 @@ __device__ inline MeshCell mesh_cell(const MeshParams& P, int cell) {
   c.idx[0] = cell % nx;
   c.idx[1] = (cell / nx) % ny;
   c.idx[2] = cell / (nx * ny);
-  const size_t base = ((size_t)c.idx[2] * g.nc[1] + c.idx[1]) * g.nc[0] + c.idx[0];
+  const size_t base = ((size_t)(c.idx[2] - P.plane0) * g.nc[1] + c.idx[1]) * g.nc[0] + c.idx[0];  // (the values begin at plane P.plane0)
   c.inside = 0u;
 #pragma unroll
   for (int k = 0; k < 8; k++) {
@@ -231,13 +231,8 @@ __global__ __launch_bounds__(256) void rm_mesh_scan_add_kernel(unsigned long lon
   if (i < n) data[i] += sums[blockIdx.x];
 }
 
-__global__ __launch_bounds__(256) void rm_mesh_emit_kernel(const MeshParams P, int cells) {
-  const int cell = blockIdx.x * blockDim.x + threadIdx.x;
-  if (cell >= cells) return;
-  const MeshCell c = mesh_cell(P, cell);
-  if (c.inside == 0u || c.inside == 0xFFu) return;  // (an edge that owns a quad crosses: its cell is active)
-  const GridDims& g = P.grid;
-  const unsigned long long first = P.counts[cell];
+// the vertex of an active cell: the mean of its edges' crossing points
+__device__ inline void mesh_vertex(const GridDims& g, const MeshCell& c, float* out) {
   float pc[3][2];  // the corners' coordinates
 #pragma unroll
   for (int a = 0; a < 3; a++) { pc[a][0] = rm_grid_coord(g, a, c.idx[a]); pc[a][1] = rm_grid_coord(g, a, c.idx[a] + 1); }
@@ -261,26 +256,91 @@ __global__ __launch_bounds__(256) void rm_mesh_emit_kernel(const MeshParams P, i
       m++;
     }
   }
-  const unsigned int vertex = (unsigned int)first;
   const float fm = (float)m;
-  P.positions[3 * (size_t)vertex] = sum[0] / fm;
-  P.positions[3 * (size_t)vertex + 1] = sum[1] / fm;
-  P.positions[3 * (size_t)vertex + 2] = sum[2] / fm;
-  P.cells[vertex] = (unsigned int)cell;
-  // the quads: vertices of the cells at (b, c) offsets (-1,-1), (0,-1), (0,0), (-1,0); counter-clockwise seen from outside
+  out[0] = sum[0] / fm;
+  out[1] = sum[1] / fm;
+  out[2] = sum[2] / fm;
+}
+
+// The cell's quads from triangle `tri` on: vertices of the cells at (b, c) offsets (-1,-1), (0,-1), (0,0), (-1,0); counter-clockwise seen
+// from outside.  vertex_of(d): the vertex of the cell d cells before this one.
+template <class VertexOf>
+__device__ inline void mesh_write_quads(const GridDims& g, const MeshCell& c, unsigned int vertex, size_t tri, unsigned int* triangles, VertexOf vertex_of) {
   const unsigned int quads = mesh_quads(c);
   const int stride[3] = {1, g.nc[0] - 1, (g.nc[0] - 1) * (g.nc[1] - 1)};
-  size_t tri = 2 * (size_t)(first >> 32);
 #pragma unroll
   for (int a = 0; a < 3; a++) {
     if (!((quads >> a) & 1u)) continue;
     const int sb = stride[(a + 1) % 3], sc = stride[(a + 2) % 3];
-    const unsigned int q0 = (unsigned int)P.counts[cell - sb - sc], q1 = (unsigned int)P.counts[cell - sc], q2 = vertex, q3 = (unsigned int)P.counts[cell - sb];
-    unsigned int* t = P.triangles + 3 * tri;
+    const unsigned int q0 = vertex_of(sb + sc), q1 = vertex_of(sc), q2 = vertex, q3 = vertex_of(sb);
+    unsigned int* t = triangles + 3 * tri;
     if (c.inside & 1u) { t[0] = q0; t[1] = q1; t[2] = q2; t[3] = q0; t[4] = q2; t[5] = q3; }
     else { t[0] = q0; t[1] = q3; t[2] = q2; t[3] = q0; t[4] = q2; t[5] = q1; }
     tri += 2;
   }
+}
+
+__global__ __launch_bounds__(256) void rm_mesh_emit_kernel(const MeshParams P, int cells) {
+  const int cell = blockIdx.x * blockDim.x + threadIdx.x;
+  if (cell >= cells) return;
+  const MeshCell c = mesh_cell(P, cell);
+  if (c.inside == 0u || c.inside == 0xFFu) return;  // (an edge that owns a quad crosses: its cell is active)
+  const unsigned long long first = P.counts[cell];
+  const unsigned int vertex = (unsigned int)first;
+  mesh_vertex(P.grid, c, P.positions + 3 * (size_t)vertex);
+  P.cells[vertex] = (unsigned int)cell;
+  mesh_write_quads(P.grid, c, vertex, 2 * (size_t)(first >> 32), P.triangles, [&](int d) { return (unsigned int)P.counts[cell - d]; });
+}
+
+// ---- slabbed extraction (include/hip_raymarch.h "slabbed extraction") ------------------------------------------------------------------
+// The mesher over a window of z planes.  Cell indices are those of the whole grid (at most 2^30: an int), so mesh_cell, mesh_quads' boundary
+// rule and RM_MESH_CELLS are the dense mesher's; only the values and the counts are addressed from the window's first plane.
+
+// The tally pass: one thread per cell of the slab's own layers, the words (active) | (quads << 32) summed in the wave, then in the
+// workgroup, then by one 64-bit atomic add per workgroup.  Integer sums: the same on every run.
+__global__ __launch_bounds__(256) void rm_mesh_slab_tally_kernel(const MeshSlab S, int first, int cells) {
+  __shared__ unsigned long long waves[4];
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  unsigned long long word = 0ull;
+  if (t < cells) {
+    const MeshCell c = mesh_cell(S.mesh, first + t);
+    const unsigned long long active = (c.inside != 0u && c.inside != 0xFFu) ? 1ull : 0ull;
+    word = active | ((unsigned long long)__popc(mesh_quads(c)) << 32);
+  }
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) word += __shfl_down(word, off, 64);
+  if ((threadIdx.x & 63u) == 0u) waves[threadIdx.x >> 6] = word;
+  __syncthreads();
+  if (threadIdx.x == 0u) {
+    const unsigned long long sum = (waves[0] + waves[1]) + (waves[2] + waves[3]);
+    if (sum != 0ull) atomicAdd(S.total, sum);
+  }
+}
+
+// The emit pass's count: one thread per cell of the window, the halo layer's first.
+__global__ __launch_bounds__(256) void rm_mesh_slab_count_kernel(const MeshSlab S, int first, int cells) {
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= cells) return;
+  const MeshCell c = mesh_cell(S.mesh, first + t);
+  const unsigned long long active = (c.inside != 0u && c.inside != 0xFFu) ? 1ull : 0ull;
+  S.mesh.counts[t] = active | ((unsigned long long)__popc(mesh_quads(c)) << 32);
+}
+
+// ... and its emit, over the scanned counts: the halo's cells emit nothing (they are the slab's before); what the scan counted of them,
+// its value at the slab's first own cell, goes off every index, and the slabs' bases on.
+__global__ __launch_bounds__(256) void rm_mesh_slab_emit_kernel(const MeshSlab S, int first, int halo, int cells) {
+  const int t = halo + blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= cells) return;
+  const MeshCell c = mesh_cell(S.mesh, first + t);
+  if (c.inside == 0u || c.inside == 0xFFu) return;
+  const unsigned long long* counts = S.mesh.counts;
+  const unsigned long long before = counts[halo], at = counts[t];
+  const unsigned int shift = (unsigned int)S.vertex_base - (unsigned int)before;  // (mod 2^32: every index it meets is below 2^32)
+  const unsigned int vertex = (unsigned int)at + shift;
+  mesh_vertex(S.mesh.grid, c, S.mesh.positions + 3 * (size_t)vertex);
+  S.mesh.cells[vertex] = (unsigned int)c.cell;
+  const size_t tri = 2 * (size_t)(S.quad_base + ((at >> 32) - (before >> 32)));
+  mesh_write_quads(S.mesh.grid, c, vertex, tri, S.mesh.triangles, [&](int d) { return (unsigned int)counts[t - d] + shift; });
 }
 
 // the first three of every twelve floats: the diffuse colour out of the material probe's records
@@ -1281,6 +1341,25 @@ hipError_t launch_mesh_measure_sum(const double* area, const double* volume, lon
 hipError_t launch_mesh_emit(const MeshParams& P, hipStream_t stream) {
   const long long cells = mesh_cells(P.grid);
   hipLaunchKernelGGL(rm_mesh_emit_kernel, dim3((unsigned int)((cells + 255) / 256)), dim3(256), 0, stream, P, (int)cells);
+  return hipGetLastError();
+}
+
+// slabbed extraction: a layer has at most 2^20 cells and a window at most 2^28 corners, so every count here is an int
+static inline int mesh_layer_cells(const GridDims& g) { return (g.nc[0] - 1) * (g.nc[1] - 1); }
+
+hipError_t launch_mesh_slab_tally(const MeshSlab& S, hipStream_t stream) {
+  const int layer = mesh_layer_cells(S.mesh.grid), cells = S.layers * layer;
+  hipLaunchKernelGGL(rm_mesh_slab_tally_kernel, dim3((unsigned int)((cells + 255) / 256)), dim3(256), 0, stream, S, S.own0 * layer, cells);
+  return hipGetLastError();
+}
+hipError_t launch_mesh_slab_count(const MeshSlab& S, hipStream_t stream) {
+  const int layer = mesh_layer_cells(S.mesh.grid), cells = (S.own0 - S.mesh.plane0 + S.layers) * layer;
+  hipLaunchKernelGGL(rm_mesh_slab_count_kernel, dim3((unsigned int)((cells + 255) / 256)), dim3(256), 0, stream, S, S.mesh.plane0 * layer, cells);
+  return hipGetLastError();
+}
+hipError_t launch_mesh_slab_emit(const MeshSlab& S, hipStream_t stream) {
+  const int layer = mesh_layer_cells(S.mesh.grid), halo = (S.own0 - S.mesh.plane0) * layer, cells = halo + S.layers * layer;
+  hipLaunchKernelGGL(rm_mesh_slab_emit_kernel, dim3((unsigned int)((cells - halo + 255) / 256)), dim3(256), 0, stream, S, S.mesh.plane0 * layer, halo, cells);
   return hipGetLastError();
 }
 #endif

@@ -309,6 +309,7 @@ struct SdfGridParams {
   DevScene scene;
   GridDims grid;
   float* out;
+  int plane0;  // a window of z planes (slabbed extraction): grid.nc[2] and grid.corners are the window's, out[0] is corner (0, 0, plane0); 0 = the whole grid
 };
 // rm_mesh_occlusion: one lane per (vertex, direction), Sdf<KIND>::eval at its taps, with the probe's scene block.  normals and d0 are
 // the probes' outputs at the positions (RM_PROBE_NORMAL, RM_PROBE_SDF); directions is the host's table (rm_mesh_occlusion_directions).
@@ -336,6 +337,16 @@ struct MeshParams {
   float* positions;            // emit: V x 3
   unsigned int* cells;         // emit: V
   unsigned int* triangles;     // emit: T x 3
+  int plane0;                  // values[0] is corner (0, 0, plane0) of the grid: a window of z planes (slabbed extraction); 0 = the whole grid
+};
+// One slab of rm_mesh_extract_slabs (the header's "slabbed extraction").  mesh.grid is the WHOLE grid and cell indices are global; mesh.values
+// holds the window's planes from mesh.plane0 on, mesh.counts the window's cells: those of layer mesh.plane0 first, which is the halo layer
+// when own0 > plane0.  The slab's own cells are layers own0 .. own0 + layers - 1.
+struct MeshSlab {
+  MeshParams mesh;
+  int own0, layers;
+  unsigned long long vertex_base, quad_base;  // emit: the vertices and quads of the slabs before this one
+  unsigned long long* total;                  // tally: this slab's (vertices) | (quads << 32), summed by atomics
 };
 // The sharp vertices of rm_mesh_extract_sharp over an emitted mesh: 12 slots per vertex, the cell's edges in the mesher's order.  Slot s of
 // vertex v lies at s * vertices + v in every slot array, so a wave's accesses to one slot are one run.  mesh.positions holds the surface-nets
@@ -479,6 +490,9 @@ size_t rm_mesh_scan_scratch_elems(long long cells);  // 64-bit words of scratch 
 hipError_t launch_mesh_count(const MeshParams& P, hipStream_t stream);
 hipError_t launch_mesh_scan(unsigned long long* counts, long long cells, unsigned long long* scratch, unsigned long long* total, hipStream_t stream);
 hipError_t launch_mesh_emit(const MeshParams& P, hipStream_t stream);
+hipError_t launch_mesh_slab_tally(const MeshSlab& S, hipStream_t stream);
+hipError_t launch_mesh_slab_count(const MeshSlab& S, hipStream_t stream);
+hipError_t launch_mesh_slab_emit(const MeshSlab& S, hipStream_t stream);
 hipError_t launch_mesh_colours(const float* material, float* colours, long long vertices, hipStream_t stream);  // 12 floats per vertex -> the first 3
 // rm_mesh_extract_sharp's two kernels.  cross: `init` makes the brackets from the corner values (else they are read), `consume` takes a round's
 // probe output in, `last` writes the crossings and the live mask (else the next round's midpoints and the brackets).  qef: the vertex positions.

@@ -127,12 +127,16 @@ export class RenderJobContext {
   extractMesh(scene: Scene, grid: MeshGrid, params: MeshParams | null | undefined, sharp: MeshSharp | true | null | undefined, keep: MeshKeep | true | null | undefined, components: boolean | undefined, simplify: MeshSimplify | null | undefined, quadric: MeshQuadric | true | null | undefined, occlusion: MeshOcclusion | true | null): Mesh;
   /** with `measures`: the mesh that is returned is measured on the GPU behind simplify and keep, before anything is copied (rm_mesh_measure), as Mesh.measures */
   extractMesh(scene: Scene, grid: MeshGrid, params: MeshParams | null | undefined, sharp: MeshSharp | true | null | undefined, keep: MeshKeep | true | null | undefined, components: boolean | undefined, simplify: MeshSimplify | null | undefined, quadric: MeshQuadric | true | null | undefined, occlusion: MeshOcclusion | true | null | undefined, measures: boolean): Mesh;
+  /** with `slabs` (true = the defaults, a number = the cell layers per slab): rm_mesh_extract_slabs / rm_mesh_extract_sharp_slabs, the same mesh byte for byte, made from one window of z layers at a time; it also takes a meshGrid(lo, hi, n, { slabs: true }) beyond 2^28 corners */
+  extractMesh(scene: Scene, grid: MeshGrid, params: MeshParams | null | undefined, sharp: MeshSharp | true | null | undefined, keep: MeshKeep | true | null | undefined, components: boolean | undefined, simplify: MeshSimplify | null | undefined, quadric: MeshQuadric | true | null | undefined, occlusion: MeshOcclusion | true | null | undefined, measures: boolean | undefined, slabs: MeshSlabs | number | true | null): Mesh;
   /** the mesher alone on the caller's field (rm_mesh_from_values); keep, components and simplify as in extractMesh */
   meshFromValues(grid: MeshGrid, values: Float32Array, iso?: number, keep?: MeshKeep | true | null, components?: boolean, simplify?: MeshSimplify | null): Mesh;
   /** quadric as in extractMesh */
   meshFromValues(grid: MeshGrid, values: Float32Array, iso: number | undefined, keep: MeshKeep | true | null | undefined, components: boolean | undefined, simplify: MeshSimplify, quadric: MeshQuadric | true | null): Mesh;
   /** measures as in extractMesh */
   meshFromValues(grid: MeshGrid, values: Float32Array, iso: number | undefined, keep: MeshKeep | true | null | undefined, components: boolean | undefined, simplify: MeshSimplify | null | undefined, quadric: MeshQuadric | true | null | undefined, measures: boolean): Mesh;
+  /** slabs as in extractMesh (rm_mesh_from_values_slabs) */
+  meshFromValues(grid: MeshGrid, values: Float32Array, iso: number | undefined, keep: MeshKeep | true | null | undefined, components: boolean | undefined, simplify: MeshSimplify | null | undefined, quadric: MeshQuadric | true | null | undefined, measures: boolean | undefined, slabs: MeshSlabs | number | true | null): Mesh;
   close(): void;
 }
 /** A frame sharded over several GPUs by this one process: a native context per device, each holding one part of the frame's
@@ -162,18 +166,24 @@ export function resetHalton(): void;
 export function encodePng(rgba: Uint8Array, width: number, height: number, bottomUp?: boolean): Buffer;
 export const RM: { [name: string]: number };
 /** mesh extraction (include/hip_raymarch.h "mesh extraction"): n = CELLS per axis between the corners lo and hi */
-export interface MeshGrid { lo: [number, number, number]; hi: [number, number, number]; n: [number, number, number] }
+export interface MeshGrid { lo: [number, number, number]; hi: [number, number, number]; n: [number, number, number]; slabs?: true }
 export interface MeshParams { iso?: number; normals?: boolean | 0 | 1; normalDelta?: number; colours?: boolean | 0 | 1; flags?: number }
 export interface Mesh { positions: Float32Array; normals: Float32Array | null; colours: Float32Array | null; triangles: Uint32Array; cells: Uint32Array; /** ms of sampling, meshing, attributes (rm_mesh_timings); with an occlusion a fourth entry, its probes and taps */ timings: [number, number, number] | [number, number, number, number]; /** only when components were asked for: each vertex's component, and (vertices, triangles) per component */ labels?: Uint32Array; componentSizes?: Uint32Array; /** only when an occlusion was asked for: 1 = open, per vertex (rm_mesh_occlusion) */ occlusion?: Float32Array; /** only when measures were asked for (rm_mesh_measure) */ measures?: MeshMeasures }
 /** what rm_mesh_measure says of a mesh (RmMeshMeasures, include/hip_raymarch.h "measures and edge topology"): the counts as Numbers (all below 2^53), lo / hi of the finite vertices, closed = no boundary and no irregular edge; componentEdges: 4 uint64 per component (edges, boundary, irregular, unbalanced; rm_mesh_measure_components); milliseconds of topology and geometry */
 export interface MeshMeasures { vertices: number; triangles: number; usedVertices: number; skippedTriangles: number; unmeasuredTriangles: number; finiteVertices: number; edges: number; boundaryEdges: number; regularEdges: number; irregularEdges: number; unbalancedEdges: number; euler: number; components: number; closedComponents: number; area: number; volume: number; lo: [number, number, number]; hi: [number, number, number]; closed: boolean; componentEdges: BigUint64Array; milliseconds: [number, number] }
 export const MESH_DEFAULTS: { iso: number; normals: 0 | 1; normalDelta: number; colours: 0 | 1; flags: number };
 export function meshGrid(lo: number[], hi: number[], n: number[]): MeshGrid;
+/** with { slabs: true }: without the bound of 2^28 corners -- a grid for extractMesh / meshFromValues with `slabs` */
+export function meshGrid(lo: number[], hi: number[], n: number[], opts: { slabs?: boolean } | null): MeshGrid;
 export function meshParams(params?: MeshParams | null): { iso: number; normals: 0 | 1; normalDelta: number; colours: 0 | 1; flags: number };
 /** the sharp block of extractMesh (RmMeshSharp): bisection rounds per edge crossing (0..16), the step of the normals at the crossings (> 0), the relative eigenvalue below which the QEF is truncated ([0, 1)) */
 export interface MeshSharp { refine?: number; normalDelta?: number; threshold?: number }
 export const MESH_SHARP_DEFAULTS: { refine: number; normalDelta: number; threshold: number };
 export function meshSharp(sharp?: MeshSharp | null): { refine: number; normalDelta: number; threshold: number };
+/** the slabs block of extractMesh / meshFromValues (RmMeshSlabs): the cell layers per slab, 0 = chosen by the library; above the grid's nz it means nz */
+export interface MeshSlabs { layers?: number }
+export const MESH_SLABS_DEFAULTS: { layers: number };
+export function meshSlabs(slabs?: MeshSlabs | null): { layers: number };
 /** the keep block of extractMesh / meshFromValues (RmMeshKeep): a component passes with at least minTriangles triangles; largest = k > 0 keeps only the k passing components with the most triangles (the lower component index first among equals), 0 keeps every passing one */
 export interface MeshKeep { minTriangles?: number; largest?: number }
 export const MESH_KEEP_DEFAULTS: { minTriangles: number; largest: number };

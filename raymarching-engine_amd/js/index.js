@@ -369,9 +369,20 @@ class RenderJobContext {  // RenderJobContext + loadRenderJobContext (LoadRender
   // measures: RmMeshMeasures' fields in camel case -- the counts as Numbers (all below 2^53: V, T < 2^32 and E <= 3 T), closed as a boolean,
   // lo / hi as arrays --, componentEdges: BigUint64Array(4 C) of (edges, boundary, irregular, unbalanced) per component as the raw uint64 rows, and
   // milliseconds: [topology, geometry].  timings is as without it.
-  extractMesh(scene, grid, opts, sharp, keep, components, simplify = null, quadric = null, occlusion = null, measures = false) {
+  // slabs: undefined / null = those calls; true, a number of cell layers or meshSlabs' options = rm_mesh_extract_slabs / _sharp_slabs, the same
+  // mesh byte for byte, made from one window of z layers at a time -- which also takes a meshGrid(lo, hi, n, { slabs: true }) beyond 2^28 corners
+  extractMesh(scene, grid, opts, sharp, keep, components, simplify = null, quadric = null, occlusion = null, measures = false, slabs = null) {
     const q = quadric === undefined || quadric === null ? null : meshQuadric(quadric === true ? undefined : quadric);
     if (q !== null && (simplify === undefined || simplify === null)) throw new TypeError("mesh: quadric places the vertices of a simplification: give simplify as well");
+    if (slabs !== undefined && slabs !== null) {
+      const w = meshSlabs(slabs === true ? undefined : typeof slabs === "number" ? { layers: slabs } : slabs);
+      const o = occlusion === undefined || occlusion === null ? null : meshOcclusion(occlusion === true ? undefined : occlusion);
+      const s = sharp === undefined || sharp === null ? null : meshSharp(sharp === true ? undefined : sharp);
+      const k = keep === undefined || keep === null ? null : meshKeep(keep === true ? undefined : keep);
+      const c = simplify === undefined || simplify === null ? null : meshSimplify(simplify);
+      return addon.extractMeshSlabs(this.ctx, this.sceneHandle(scene), grid, w, meshParams(opts), s, k, !!components, c, q, o, !!measures);
+    }
+    if (grid && grid.slabs) throw new TypeError("mesh: a grid made with slabs: true is extracted in slabs: give slabs as well");
     if (measures) {
       const o = occlusion === undefined || occlusion === null ? null : meshOcclusion(occlusion === true ? undefined : occlusion);
       const s = sharp === undefined || sharp === null ? null : meshSharp(sharp === true ? undefined : sharp);
@@ -401,11 +412,18 @@ class RenderJobContext {  // RenderJobContext + loadRenderJobContext (LoadRender
   }
   // the mesher alone on the caller's field: values Float32Array of the grid's corners, x fastest (rm_mesh_from_values)
   // keep, components, simplify, quadric, measures: as in extractMesh
-  meshFromValues(grid, values, iso = 0, keep, components, simplify, quadric, measures) {
+  meshFromValues(grid, values, iso = 0, keep, components, simplify, quadric, measures, slabs) {
     if (!(values instanceof Float32Array)) throw new TypeError("meshFromValues: values must be a Float32Array");
     if (!finite(iso)) throw new RangeError("mesh: iso must be a finite number");
     const q = quadric === undefined || quadric === null ? null : meshQuadric(quadric === true ? undefined : quadric);
     if (q !== null && (simplify === undefined || simplify === null)) throw new TypeError("mesh: quadric places the vertices of a simplification: give simplify as well");
+    if (slabs !== undefined && slabs !== null) {  // (rm_mesh_from_values_slabs; slabs as in extractMesh)
+      const w = meshSlabs(slabs === true ? undefined : typeof slabs === "number" ? { layers: slabs } : slabs);
+      const k = keep === undefined || keep === null ? null : meshKeep(keep === true ? undefined : keep);
+      const c = simplify === undefined || simplify === null ? null : meshSimplify(simplify);
+      return addon.meshFromValuesSlabs(this.ctx, grid, values, iso, w, k, !!components, c, q, !!measures);
+    }
+    if (grid && grid.slabs) throw new TypeError("mesh: a grid made with slabs: true is extracted in slabs: give slabs as well");
     if (measures) {
       const k = keep === undefined || keep === null ? null : meshKeep(keep === true ? undefined : keep);
       const c = simplify === undefined || simplify === null ? null : meshSimplify(simplify);
@@ -673,8 +691,10 @@ function statsPercentile(stats, q) {
 
 // ---- mesh extraction: the grid, the parameters and the PLY writer (include/hip_raymarch.h RmGrid, RmMeshParams) ----
 const MESH_DEFAULTS = { iso: 0.0, normals: 1, normalDelta: 1e-5, colours: 0, flags: 0 };
-// { lo, hi, n }: n = CELLS per axis between the corners lo and hi; checked as the library checks an RmGrid
-function meshGrid(lo, hi, n) {
+// { lo, hi, n }: n = CELLS per axis between the corners lo and hi; checked as the library checks an RmGrid.  opts.slabs: true lifts the bound of
+// 2^28 corners and nothing else ({ lo, hi, n, slabs: true }): a grid for extractMesh / meshFromValues with slabs
+function meshGrid(lo, hi, n, opts) {
+  const slabs = !!(opts && opts.slabs);
   const three = (a) => Array.isArray(a) && a.length === 3 && a.every((v) => typeof v === "number");
   if (!three(lo) || !three(hi) || !three(n)) throw new TypeError("grid: lo, hi and n take three numbers each");
   if (!n.every((v) => Number.isInteger(v) && v >= 1 && v <= 1024)) throw new RangeError("grid: n must be integers in 1..1024 cells per axis");
@@ -682,8 +702,8 @@ function meshGrid(lo, hi, n) {
     const l = Math.fround(lo[a]), h = Math.fround(hi[a]), step = Math.fround(Math.fround(h - l) / n[a]);
     if (!finite(l) || !finite(h) || !finite(step) || !(step > 0)) throw new RangeError("grid: lo, hi and the cell size (hi - lo) / n must be finite, the cell size > 0");
   }
-  if ((n[0] + 1) * (n[1] + 1) * (n[2] + 1) > 2 ** 28) throw new RangeError("grid: at most 2^28 corners");
-  return { lo: lo.slice(), hi: hi.slice(), n: n.slice() };
+  if (!slabs && (n[0] + 1) * (n[1] + 1) * (n[2] + 1) > 2 ** 28) throw new RangeError("grid: at most 2^28 corners");
+  return slabs ? { lo: lo.slice(), hi: hi.slice(), n: n.slice(), slabs: true } : { lo: lo.slice(), hi: hi.slice(), n: n.slice() };
 }
 // undefined / null = the defaults, or an object with some of iso, normals, normalDelta, colours, flags (RM.RENDER_FAST, RM.RENDER_NO_CULL);
 // checked as the library checks an RmMeshParams; returns { iso, normals: 0 | 1, normalDelta, colours: 0 | 1, flags }
@@ -737,6 +757,22 @@ function meshKeep(opts) {
   }
   for (const k of Object.keys(MESH_KEEP_DEFAULTS))
     if (typeof p[k] !== "number" || !Number.isInteger(p[k]) || p[k] < 0 || p[k] > 1e9) throw new RangeError("mesh: keep " + k + " must be an integer in 0..1e9");
+  return p;
+}
+
+// the slabs block of extractMesh / meshFromValues (include/hip_raymarch.h RmMeshSlabs): undefined / null = the defaults, or an object with layers
+// (the cell layers per slab, 0 = chosen by the library; above the grid's nz it means nz); an integer in 0..1e9, what the addon's integer fields hold
+const MESH_SLABS_DEFAULTS = { layers: 0 };
+function meshSlabs(opts) {
+  const p = { ...MESH_SLABS_DEFAULTS };
+  if (opts !== undefined && opts !== null) {
+    if (typeof opts !== "object") throw new TypeError("mesh: expected an object of slabs parameters");
+    for (const k of Object.keys(opts)) {
+      if (!(k in MESH_SLABS_DEFAULTS)) throw new TypeError("mesh: unknown slabs parameter " + k);
+      p[k] = opts[k];
+    }
+  }
+  if (typeof p.layers !== "number" || !Number.isInteger(p.layers) || p.layers < 0 || p.layers > 1e9) throw new RangeError("mesh: slabs layers must be an integer in 0..1e9");
   return p;
 }
 
@@ -873,5 +909,5 @@ function encodePng(rgba, width, height, bottomUp = true) {
 module.exports = { RM, addon, encodePng, Scene, CsgScene, Mandelbulb, singleSphere, DEFAULT_MATERIAL, halton, resetHalton, uniformsFromSchema, packUniforms,
                    tileRect, RenderJobContext, ShardedRenderJobContext, doRenderJob, U_OFFSET, DENOISE_DEFAULTS, denoiseParams,
                    DENOISE_VARIANCE_DEFAULTS, denoiseVarianceParams, DESPECKLE_DEFAULTS, despeckleParams, DISPLAY_DEFAULTS, AUTO_EXPOSURE_DEFAULTS,
-                   displayParams, statsExposure, statsPercentile, MESH_DEFAULTS, meshGrid, meshParams, MESH_SHARP_DEFAULTS, meshSharp, MESH_KEEP_DEFAULTS, meshKeep,
+                   displayParams, statsExposure, statsPercentile, MESH_DEFAULTS, meshGrid, meshParams, MESH_SHARP_DEFAULTS, meshSharp, MESH_KEEP_DEFAULTS, meshKeep, MESH_SLABS_DEFAULTS, meshSlabs,
                    MESH_SIMPLIFY_DEFAULTS, meshSimplify, MESH_QUADRIC_DEFAULTS, meshQuadric, MESH_OCCLUSION_DEFAULTS, meshOcclusion, encodePly, encodeStl };

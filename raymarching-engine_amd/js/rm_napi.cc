@@ -877,6 +877,100 @@ static napi_value MeshFromValues(napi_env env, napi_callback_info info) {
   return mesh_result(env, ctx, mesh, false, false, keep ? &k : nullptr, components, simplify ? &c : nullptr, quadric ? &q : nullptr, nullptr, nullptr, measures);
 }
 
+// ---- slabbed extraction: meshSlabsBlock, extractMeshSlabs, meshFromValuesSlabs (include/hip_raymarch.h "slabbed extraction") ----
+static const Field MESH_SLABS_FIELDS[] = {{"layers", Field::INT, offsetof(RmMeshSlabs, layers)}};
+// the slabs block: null / undefined = the defaults, an object = its fields over them
+static bool get_mesh_slabs(napi_env env, napi_value v, RmMeshSlabs* w) {
+  rm_mesh_slabs_default(w);
+  bool given = false;
+  return get_block(env, v, w, MESH_SLABS_FIELDS, &given);
+}
+
+// meshSlabsBlock(slabs | null) -> ArrayBuffer(RmMeshSlabs): the bytes the slabbed mesh calls hand to the library (null: the defaults)
+static napi_value MeshSlabsBlock(napi_env env, napi_callback_info info) {
+  size_t argc = 1;
+  napi_value argv[1];
+  NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+  RmMeshSlabs w;
+  if (argc != 1 || !get_mesh_slabs(env, argv[0], &w)) {
+    napi_throw_type_error(env, nullptr, "meshSlabsBlock(slabs | null)");
+    return nullptr;
+  }
+  napi_value b;
+  void* d = nullptr;
+  NAPI_OK(napi_create_arraybuffer(env, sizeof w, &d, &b));
+  std::memcpy(d, &w, sizeof w);
+  return b;
+}
+
+// extractMeshSlabs(ctx, scene, grid, slabs | null, params | null, sharp | null, keep | null, components, simplify | null, quadric | null, occlusion | null,
+// measures): extractMesh with rm_mesh_extract_slabs / rm_mesh_extract_sharp_slabs in place of rm_mesh_extract / _sharp; every argument is given
+static napi_value ExtractMeshSlabs(napi_env env, napi_callback_info info) {
+  size_t argc = 12;
+  napi_value argv[12];
+  NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+  rm_ctx* ctx = argc == 12 ? get_external<rm_ctx>(env, argv[0]) : nullptr;
+  rm_scene* scene = argc == 12 ? get_external<rm_scene>(env, argv[1]) : nullptr;
+  RmGrid g;
+  RmMeshSlabs w;
+  RmMeshParams p;
+  RmMeshSharp s;
+  RmMeshKeep k;
+  MeshSimplifyBlock c;
+  RmMeshQuadric q;
+  RmMeshOcclusion ao;
+  bool sharp = false, keep = false, components = false, simplify = false, quadric = false, occlusion = false, measures = false;
+  if (!ctx || !scene || !get_grid(env, argv[2], &g) || !get_mesh_slabs(env, argv[3], &w) || !get_mesh_params(env, argv[4], &p) ||
+      !get_mesh_sharp(env, argv[5], &s, &sharp) || !get_mesh_keep(env, argv[6], &k, &keep) || !get_bool(env, argv[7], &components) ||
+      !get_mesh_simplify(env, argv[8], &c, &simplify) || !get_mesh_quadric(env, argv[9], &q, &quadric) || !get_mesh_occlusion(env, argv[10], &ao, &occlusion) ||
+      !get_bool(env, argv[11], &measures) || (quadric && !simplify)) {
+    napi_throw_type_error(env, nullptr, "extractMeshSlabs(ctx, scene, grid, slabs | null, params | null, sharp | null, keep | null, components, simplify | null, quadric | null, occlusion | null, measures)");
+    return nullptr;
+  }
+  rm_mesh* mesh = nullptr;
+  if (sharp) {
+    if (rm_mesh_extract_sharp_slabs(ctx, scene, &g, &p, &s, &w, &mesh) != RM_OK) return throw_rm(env, ctx, "rm_mesh_extract_sharp_slabs");
+  } else if (rm_mesh_extract_slabs(ctx, scene, &g, &p, &w, &mesh) != RM_OK) return throw_rm(env, ctx, "rm_mesh_extract_slabs");
+  return mesh_result(env, ctx, mesh, p.normals != 0, p.colours != 0, keep ? &k : nullptr, components, simplify ? &c : nullptr, quadric ? &q : nullptr, scene,
+                     occlusion ? &ao : nullptr, measures);
+}
+
+// meshFromValuesSlabs(ctx, grid, values: Float32Array(corners), iso, slabs | null, keep | null, components, simplify | null, quadric | null, measures):
+// meshFromValues with rm_mesh_from_values_slabs in place of rm_mesh_from_values; every argument is given
+static napi_value MeshFromValuesSlabs(napi_env env, napi_callback_info info) {
+  size_t argc = 10;
+  napi_value argv[10];
+  NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+  rm_ctx* ctx = argc == 10 ? get_external<rm_ctx>(env, argv[0]) : nullptr;
+  RmMeshSlabs w;
+  RmMeshKeep k;
+  MeshSimplifyBlock c;
+  RmMeshQuadric q;
+  bool keep = false, components = false, simplify = false, quadric = false, measures = false;
+  RmGrid g;
+  double iso = 0.0;
+  void* d = nullptr;
+  size_t n = 0;
+  if (!ctx || !get_grid(env, argv[1], &g) || !get_buffer(env, argv[2], &d, &n) || napi_get_value_double(env, argv[3], &iso) != napi_ok ||
+      !get_mesh_slabs(env, argv[4], &w) || !get_mesh_keep(env, argv[5], &k, &keep) || !get_bool(env, argv[6], &components) ||
+      !get_mesh_simplify(env, argv[7], &c, &simplify) || !get_mesh_quadric(env, argv[8], &q, &quadric) || !get_bool(env, argv[9], &measures) || (quadric && !simplify)) {
+    napi_throw_type_error(env, nullptr, "meshFromValuesSlabs(ctx, grid, values: Float32Array, iso, slabs | null, keep | null, components, simplify | null, quadric | null, measures)");
+    return nullptr;
+  }
+  for (int a = 0; a < 3; a++)  // (the size below needs sane counts; the library checks the rest of the grid)
+    if (g.n[a] < 1 || g.n[a] > 1024) {
+      napi_throw_range_error(env, nullptr, "meshFromValuesSlabs: grid n must be in 1..1024 cells per axis");
+      return nullptr;
+    }
+  if (n != (size_t)(g.n[0] + 1) * (size_t)(g.n[1] + 1) * (size_t)(g.n[2] + 1) * sizeof(float)) {
+    napi_throw_range_error(env, nullptr, "meshFromValuesSlabs: values must hold (nx + 1)(ny + 1)(nz + 1) floats");
+    return nullptr;
+  }
+  rm_mesh* mesh = nullptr;
+  if (rm_mesh_from_values_slabs(ctx, &g, static_cast<const float*>(d), (float)iso, &w, &mesh) != RM_OK) return throw_rm(env, ctx, "rm_mesh_from_values_slabs");
+  return mesh_result(env, ctx, mesh, false, false, keep ? &k : nullptr, components, simplify ? &c : nullptr, quadric ? &q : nullptr, nullptr, nullptr, measures);
+}
+
 // fbCreateStriped(ctx, width, height, stripeRows, parts, part[, gbuffer]): the stripes k with k % parts == part of a width x height image,
 // planes owned by the library (rm_fb_create_striped) -- what one GPU of a sharded frame holds
 static napi_value FbCreateStriped(napi_env env, napi_callback_info info) {
@@ -1073,7 +1167,7 @@ static napi_value Sizes(napi_env env, napi_callback_info) {
       {"RmMaterial", (uint32_t)sizeof(RmMaterial)}, {"RmRect", (uint32_t)sizeof(RmRect)}, {"RmSurface", (uint32_t)sizeof(RmSurface)}, {"RmDenoise", (uint32_t)sizeof(RmDenoise)},
       {"RmDenoiseVariance", (uint32_t)sizeof(RmDenoiseVariance)}, {"RmDespeckle", (uint32_t)sizeof(RmDespeckle)}, {"RmFilters", (uint32_t)sizeof(RmFilters)}, {"RmFrameStats", (uint32_t)sizeof(RmFrameStats)},
       {"RmAutoExposure", (uint32_t)sizeof(RmAutoExposure)}, {"RmDisplay", (uint32_t)sizeof(RmDisplay)}, {"RmGrid", (uint32_t)sizeof(RmGrid)},
-      {"RmMeshParams", (uint32_t)sizeof(RmMeshParams)}, {"RmMeshSharp", (uint32_t)sizeof(RmMeshSharp)}, {"RmMeshKeep", (uint32_t)sizeof(RmMeshKeep)}, {"RmMeshSimplify", (uint32_t)sizeof(RmMeshSimplify)}, {"RmMeshQuadric", (uint32_t)sizeof(RmMeshQuadric)}, {"RmMeshOcclusion", (uint32_t)sizeof(RmMeshOcclusion)}, {"RmMeshMeasures", (uint32_t)sizeof(RmMeshMeasures)}, {"abi", (uint32_t)rm_abi_version()}};
+      {"RmMeshParams", (uint32_t)sizeof(RmMeshParams)}, {"RmMeshSharp", (uint32_t)sizeof(RmMeshSharp)}, {"RmMeshKeep", (uint32_t)sizeof(RmMeshKeep)}, {"RmMeshSimplify", (uint32_t)sizeof(RmMeshSimplify)}, {"RmMeshQuadric", (uint32_t)sizeof(RmMeshQuadric)}, {"RmMeshOcclusion", (uint32_t)sizeof(RmMeshOcclusion)}, {"RmMeshMeasures", (uint32_t)sizeof(RmMeshMeasures)}, {"RmMeshSlabs", (uint32_t)sizeof(RmMeshSlabs)}, {"abi", (uint32_t)rm_abi_version()}};
   for (const auto& it : items) {
     NAPI_OK(napi_create_uint32(env, it.v, &v));
     NAPI_OK(napi_set_named_property(env, o, it.k, v));
@@ -1086,7 +1180,7 @@ static napi_value Init(napi_env env, napi_value exports) {
       {"ctxCreate", CtxCreate}, {"ctxDestroy", CtxDestroy}, {"sync", Sync}, {"sceneCreate", SceneCreate}, {"sceneDestroy", SceneDestroy},
       {"fbCreate", FbCreate}, {"fbClear", FbClear}, {"fbDestroy", FbDestroy}, {"fbDownload", FbDownload}, {"present", Present}, {"denoise", Denoise}, {"presentDenoised", PresentDenoised}, {"denoiseVariance", DenoiseVariance}, {"presentDenoisedVariance", PresentDenoisedVariance}, {"filter", Filter}, {"presentFiltered", PresentFiltered}, {"presentDisplay", PresentDisplay}, {"presentLinear", PresentLinear}, {"frameStats", FrameStats}, {"statsExposure", StatsExposure}, {"statsPercentile", StatsPercentile}, {"renderSample", RenderSample}, {"renderSamples", RenderSamples},
       {"fbCreateStriped", FbCreateStriped}, {"fbRows", FbRows}, {"setSamplesInFlight", SetSamplesInFlight}, {"presentSharded", PresentSharded}, {"presentShardedStart", PresentShardedStart}, {"presentShardedFinish", PresentShardedFinish},
-      {"meshBlocks", MeshBlocks}, {"meshSharpBlock", MeshSharpBlock}, {"meshKeepBlock", MeshKeepBlock}, {"meshSimplifyBlock", MeshSimplifyBlockOf}, {"meshQuadricBlock", MeshQuadricBlock}, {"meshOcclusionBlock", MeshOcclusionBlock}, {"sdfGrid", SdfGrid}, {"extractMesh", ExtractMesh}, {"meshFromValues", MeshFromValues}, {"sizes", Sizes}};
+      {"meshBlocks", MeshBlocks}, {"meshSharpBlock", MeshSharpBlock}, {"meshKeepBlock", MeshKeepBlock}, {"meshSimplifyBlock", MeshSimplifyBlockOf}, {"meshQuadricBlock", MeshQuadricBlock}, {"meshOcclusionBlock", MeshOcclusionBlock}, {"sdfGrid", SdfGrid}, {"extractMesh", ExtractMesh}, {"meshFromValues", MeshFromValues}, {"meshSlabsBlock", MeshSlabsBlock}, {"extractMeshSlabs", ExtractMeshSlabs}, {"meshFromValuesSlabs", MeshFromValuesSlabs}, {"sizes", Sizes}};
   for (const auto& f : fns) {
     napi_value fn;
     if (napi_create_function(env, f.name, NAPI_AUTO_LENGTH, f.fn, nullptr, &fn) != napi_ok) return nullptr;

@@ -12,9 +12,12 @@ from . import abi
 
 
 class Grid:
-    """`n` = (nx, ny, nz) CELLS between the corners `lo` and `hi`: an axis has n + 1 corners.  Checked as the library checks an RmGrid."""
+    """`n` = (nx, ny, nz) CELLS between the corners `lo` and `hi`: an axis has n + 1 corners.  Checked as the library checks an RmGrid.
+    slabs=True lifts the bound of 2^28 corners, and nothing else: such a grid is for extract_mesh / mesh_from_values with `slabs`
+    (include/hip_raymarch.h "slabbed extraction")."""
 
-    def __init__(self, lo, hi, n):
+    def __init__(self, lo, hi, n, slabs=False):
+        self.slabs = bool(slabs)
         self.lo, self.hi = tuple(float(v) for v in lo), tuple(float(v) for v in hi)
         self.n = tuple(int(v) for v in n)
         if not (len(self.lo) == len(self.hi) == len(self.n) == 3):
@@ -28,7 +31,7 @@ class Grid:
             h = [(f(b) - f(a)) / f(k) for a, b, k in zip(self.lo, self.hi, self.n)]
         if not all(math.isfinite(f(v)) for v in self.lo + self.hi) or not all(math.isfinite(v) and v > 0 for v in h):
             raise ValueError("grid: lo, hi and the cell size (hi - lo) / n must be finite, the cell size > 0")
-        if self.corners > 1 << 28:
+        if not self.slabs and self.corners > 1 << 28:
             raise ValueError("grid: at most 2^28 corners")
 
     @property
@@ -52,7 +55,12 @@ class Grid:
         from . import native
 
         out = np.empty(self.n[a] + 1, np.float32)
-        if native.load_library().rm_grid_axis(abi.C.byref(self.to_c()), int(a), native._fp(out)) != abi.RM_OK:
+        g = self.to_c()
+        if self.slabs:  # (rm_grid_axis keeps the bound on the corners; an axis depends on nothing but itself)
+            for other in range(3):
+                if other != int(a):
+                    g.n[other] = 1
+        if native.load_library().rm_grid_axis(abi.C.byref(g), int(a), native._fp(out)) != abi.RM_OK:
             raise ValueError("grid: refused by rm_grid_axis")
         return out
 
@@ -95,6 +103,15 @@ def mesh_sharp(**fields) -> abi.RmMeshSharp:
     if not (math.isfinite(threshold) and 0 <= threshold < 1):
         raise ValueError("mesh: sharp threshold must be finite and in [0, 1)")
     return abi.RmMeshSharp(refine=int(refine), normal_delta=float(p["normal_delta"]), threshold=float(p["threshold"]), reserved=0)
+
+
+def mesh_slabs(layers=0) -> abi.RmMeshSlabs:
+    """The abi.RmMeshSlabs of Context.extract_mesh(..., slabs=...) / mesh_from_values(..., slabs=...): the cell layers per slab, 0 = chosen by
+    the library; above the grid's nz it means nz.  Checked as the library checks it, but for the window's size, which needs the grid:
+    ValueError otherwise."""
+    if isinstance(layers, bool) or not isinstance(layers, (int, np.integer)) or not 0 <= int(layers) <= 0x7FFFFFFF:
+        raise ValueError("mesh: slabs layers must be an integer >= 0")
+    return abi.RmMeshSlabs(layers=int(layers), reserved=0)
 
 
 def mesh_keep(**fields) -> abi.RmMeshKeep:

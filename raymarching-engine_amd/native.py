@@ -46,6 +46,7 @@ EXPORTS = [
     "rm_mesh_simplify_default", "rm_mesh_simplify", "rm_mesh_quadric_default", "rm_mesh_simplify_quadric",
     "rm_mesh_occlusion_default", "rm_mesh_occlusion_directions", "rm_mesh_occlusion",
     "rm_mesh_measure", "rm_mesh_measure_components",
+    "rm_mesh_slabs_default", "rm_mesh_extract_slabs", "rm_mesh_extract_sharp_slabs", "rm_mesh_from_values_slabs",
 ]
 
 # G-buffer formats of a framebuffer (include/hip_raymarch.h RM_GBUFFER_*): "f32" (the default: the software GL stack's planes, which the
@@ -427,6 +428,11 @@ def load_library(path=None):
         "rm_mesh_occlusion": (ip, [vp, vp, C.POINTER(abi.RmMeshOcclusion), fp, fp]),
         "rm_mesh_measure": (ip, [vp, C.POINTER(abi.RmMeshMeasures), fp]),
         "rm_mesh_measure_components": (ip, [vp, vp, C.c_size_t]),
+        "rm_mesh_slabs_default": (None, [C.POINTER(abi.RmMeshSlabs)]),
+        "rm_mesh_extract_slabs": (ip, [vp, vp, C.POINTER(abi.RmGrid), C.POINTER(abi.RmMeshParams), C.POINTER(abi.RmMeshSlabs), C.POINTER(vp)]),
+        "rm_mesh_extract_sharp_slabs": (ip, [vp, vp, C.POINTER(abi.RmGrid), C.POINTER(abi.RmMeshParams), C.POINTER(abi.RmMeshSharp), C.POINTER(abi.RmMeshSlabs),
+                                             C.POINTER(vp)]),
+        "rm_mesh_from_values_slabs": (ip, [vp, C.POINTER(abi.RmGrid), fp, C.c_float, C.POINTER(abi.RmMeshSlabs), C.POINTER(vp)]),
     }
     for name, (res, args) in sig.items():
         if name.startswith("rm_debug_") and not hasattr(lib, name) and os.environ.get("RM_LIB"):
@@ -854,9 +860,22 @@ class Context:
             return grid, g, p
         raise ValueError("mesh: simplify must be None, a mesh.Grid, a dict of mesh_simplify's arguments or its (abi.RmGrid, abi.RmMeshSimplify)")
 
+    @staticmethod
+    def _mesh_slabs(slabs, grid):
+        """The `slabs` of extract_mesh / mesh_from_values as an abi.RmMeshSlabs (_mesh_block's rules, and an int is `layers`); a grid made with
+        slabs=True can only be extracted in slabs: ValueError without them."""
+        if isinstance(slabs, (int, np.integer)) and not isinstance(slabs, bool):
+            slabs = dict(layers=slabs)
+        if isinstance(slabs, dict) and set(slabs) - set(abi.MESH_SLABS_DEFAULTS):
+            raise ValueError(f"mesh: unknown slabs parameter {sorted(set(slabs) - set(abi.MESH_SLABS_DEFAULTS))[0]}")
+        block = Context._mesh_block("slabs", slabs, abi.RmMeshSlabs)
+        if block is None and getattr(grid, "slabs", False):
+            raise ValueError("mesh: a grid made with slabs=True is extracted in slabs: give slabs as well")
+        return block
+
     def extract_mesh(self, scene: "SceneHandle", grid, iso: float = 0.0, normals: bool = True, colours: bool = False, flags: int = 0,
                      normal_delta: float = 1e-5, sharp=None, *, keep=None, components: bool = False, simplify=None, quadric=None,
-                     measures: bool = False, occlusion=None):
+                     measures: bool = False, slabs=None, occlusion=None):
         """The level set `iso` of the scene on `grid` (mesh.Grid) as a mesh.Mesh: rm_mesh_extract -- the distances sampled and meshed
         (surface nets) on the device, with per-vertex normals / diffuse colours from the scene's probes when asked for.  `sharp`: None is
         that call; True (the defaults), a dict of mesh.mesh_sharp's arguments or an abi.RmMeshSharp is rm_mesh_extract_sharp -- the same
@@ -873,7 +892,10 @@ class Context:
         Mesh.occlusion (rm_mesh_occlusion; 1 = open), which encode_ply writes as `quality` and mesh.shaded multiplies into the colours.
         `measures`: True measures the mesh that is returned on the device -- behind `simplify` and `keep`, before the download -- into
         Mesh.measures (rm_mesh_measure): a dict of abi.RmMeshMeasures' fields (lo and hi as tuples, closed as bool) plus component_edges,
-        [C, 4] uint64 rows of (edges, boundary, irregular, unbalanced) per component."""
+        [C, 4] uint64 rows of (edges, boundary, irregular, unbalanced) per component.
+        `slabs`: None is that call; True (the defaults), an int (the cell layers per slab), a dict of mesh.mesh_slabs' arguments or an
+        abi.RmMeshSlabs is rm_mesh_extract_slabs / rm_mesh_extract_sharp_slabs -- the same mesh, byte for byte, made from one window of z
+        layers at a time, which also takes a grid beyond 2^28 corners (mesh.Grid(..., slabs=True)).  Every other setting composes with it."""
         from .mesh import mesh_params
 
         keep, simplify, quadric = self._mesh_keep(keep), self._mesh_simplify(simplify), self._mesh_quadric(quadric, simplify)  # (refused before anything runs)
@@ -881,24 +903,33 @@ class Context:
         g, p = grid.to_c(), mesh_params(iso=iso, normals=normals, colours=colours, flags=flags, normal_delta=normal_delta)
         h = C.c_void_p()
         s = self._mesh_block("sharp", sharp, abi.RmMeshSharp)
-        if s is None:
+        w = self._mesh_slabs(slabs, grid)
+        if s is None and w is None:
             self._check(self.lib.rm_mesh_extract(self.h, scene.h, C.byref(g), C.byref(p), C.byref(h)))
-        else:
+        elif w is None:
             self._check(self.lib.rm_mesh_extract_sharp(self.h, scene.h, C.byref(g), C.byref(p), C.byref(s), C.byref(h)))
+        elif s is None:
+            self._check(self.lib.rm_mesh_extract_slabs(self.h, scene.h, C.byref(g), C.byref(p), C.byref(w), C.byref(h)))
+        else:
+            self._check(self.lib.rm_mesh_extract_sharp_slabs(self.h, scene.h, C.byref(g), C.byref(p), C.byref(s), C.byref(w), C.byref(h)))
         return self._take_mesh(h, grid, normals=p.normals, colours=p.colours, keep=keep, components=components, simplify=simplify, quadric=quadric,
                                scene=scene, occlusion=occlusion, measures=measures)
 
     def mesh_from_values(self, grid, values: np.ndarray, iso: float = 0.0, *, keep=None, components: bool = False, simplify=None, quadric=None,
-                         measures: bool = False):
+                         measures: bool = False, slabs=None):
         """The mesher alone on the caller's field: `values` float32 [nz + 1, ny + 1, nx + 1] (rm_mesh_from_values).  keep, components,
-        simplify, quadric and measures: as in extract_mesh."""
+        simplify, quadric, measures and slabs (rm_mesh_from_values_slabs): as in extract_mesh."""
         keep, simplify, quadric = self._mesh_keep(keep), self._mesh_simplify(simplify), self._mesh_quadric(quadric, simplify)
+        w = self._mesh_slabs(slabs, grid)
         g = grid.to_c()
         v = np.ascontiguousarray(values, np.float32)
         if v.shape != grid.shape:
             raise ValueError(f"values must have the shape {grid.shape} of the grid's corners, not {v.shape}")
         h = C.c_void_p()
-        self._check(self.lib.rm_mesh_from_values(self.h, C.byref(g), _fp(v), float(iso), C.byref(h)))
+        if w is None:
+            self._check(self.lib.rm_mesh_from_values(self.h, C.byref(g), _fp(v), float(iso), C.byref(h)))
+        else:
+            self._check(self.lib.rm_mesh_from_values_slabs(self.h, C.byref(g), _fp(v), float(iso), C.byref(w), C.byref(h)))
         return self._take_mesh(h, grid, keep=keep, components=components, simplify=simplify, quadric=quadric, measures=measures)
 
     def probe_camera(self, uniforms: abi.RmUniforms, width: int, height: int) -> np.ndarray:
