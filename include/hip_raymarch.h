@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define RM_ABI_VERSION 9 /* 9: RM_GBUFFER_F32 / _F16, rm_fb_create_fmt, rm_fb_create_striped_fmt, rm_fb_wrap_fmt, rm_fb_gbuffer, rm_fb_download_raw, rm_fb_upload_raw, RmDenoise, rm_denoise_default, rm_denoise, rm_denoise_device, rm_present_denoised, RM_FB_MOMENTS, RM_PLANE_MOMENTS, rm_fb_has_moments, RmDenoiseVariance, rm_denoise_variance_default, rm_denoise_variance, rm_denoise_variance_device, rm_present_denoised_variance, RmDespeckle, RmFilters, RM_DENOISE_NONE / _ATROUS / _VARIANCE, rm_filters_default, rm_filter, rm_filter_device, rm_present_filtered, RM_STATS_BINS, RmFrameStats, rm_frame_stats, RmAutoExposure, rm_auto_exposure_default, rm_stats_percentile, rm_stats_exposure, RM_TONE_CLIP / _REINHARD / _ACES, RmDisplay, rm_display_default, rm_present_display, rm_present_display_device, rm_present_linear, RmGrid, rm_grid_axis, rm_sdf_grid, rm_sdf_grid_device, RmMeshParams, rm_mesh_params_default, rm_mesh, rm_mesh_extract, rm_mesh_from_values, rm_mesh_counts, rm_mesh_timings, RM_MESH_POSITIONS / _NORMALS / _COLOURS / _TRIANGLES / _CELLS, rm_mesh_download, rm_mesh_device_ptr, rm_mesh_destroy, RmMeshSharp, rm_mesh_sharp_default, rm_mesh_extract_sharp, RmMeshKeep, rm_mesh_keep_default, rm_mesh_components, RM_MESH_PART_LABELS / _SIZES, rm_mesh_components_download, rm_mesh_filter, RmMeshSimplify, rm_mesh_simplify_default, rm_mesh_simplify, RmMeshQuadric, rm_mesh_quadric_default, rm_mesh_simplify_quadric, RmMeshOcclusion, rm_mesh_occlusion_default, rm_mesh_occlusion_directions, rm_mesh_occlusion, RmMeshMeasures, rm_mesh_measure, rm_mesh_measure_components, RmMeshSlabs, rm_mesh_slabs_default, rm_mesh_extract_slabs, rm_mesh_extract_sharp_slabs, rm_mesh_from_values_slabs (additions only); 8: RM_PRIM_TORUS / _CYLINDER / _PLANE, RM_OP_SMOOTH_SUBTRACT / _INTERSECT, rm_probe_math (additions only); 7: rm_present_sharded_finish / rm_present_sharded take the size of the host buffer (a changed signature), rm_ctx_set_cull_min_pixels, rm_ctx_set_cull_budget, rm_ctx_cull_stats; 6: rm_present_striped_rows, rm_present_sharded_start / _finish, rm_ctx_last_warning, RM_PROBE_CAST_SHADOW, RM_PRIM_KIND (additions only); 3: rm_ctx_set_sample_batch, rm_buffer_*; 4: rm_ctx_set_gl_stack; 5: RmSurface / RmSceneDesc.surfaces (the struct grew), rm_pack_present_rows, rm_present_sharded, rm_ctx_last_pipeline, RM_RENDER_NO_FAR_JUMP, RM_RENDER_NO_CULL (additions only) */
+#define RM_ABI_VERSION 9 /* 9: RM_GBUFFER_F32 / _F16, rm_fb_create_fmt, rm_fb_create_striped_fmt, rm_fb_wrap_fmt, rm_fb_gbuffer, rm_fb_download_raw, rm_fb_upload_raw, RmDenoise, rm_denoise_default, rm_denoise, rm_denoise_device, rm_present_denoised, RM_FB_MOMENTS, RM_PLANE_MOMENTS, rm_fb_has_moments, RmDenoiseVariance, rm_denoise_variance_default, rm_denoise_variance, rm_denoise_variance_device, rm_present_denoised_variance, RmDespeckle, RmFilters, RM_DENOISE_NONE / _ATROUS / _VARIANCE, rm_filters_default, rm_filter, rm_filter_device, rm_present_filtered, RM_STATS_BINS, RmFrameStats, rm_frame_stats, RmAutoExposure, rm_auto_exposure_default, rm_stats_percentile, rm_stats_exposure, RM_TONE_CLIP / _REINHARD / _ACES, RmDisplay, rm_display_default, rm_present_display, rm_present_display_device, rm_present_linear, RmGrid, rm_grid_axis, rm_sdf_grid, rm_sdf_grid_device, RmMeshParams, rm_mesh_params_default, rm_mesh, rm_mesh_extract, rm_mesh_from_values, rm_mesh_counts, rm_mesh_timings, RM_MESH_POSITIONS / _NORMALS / _COLOURS / _TRIANGLES / _CELLS, rm_mesh_download, rm_mesh_device_ptr, rm_mesh_destroy, RmMeshSharp, rm_mesh_sharp_default, rm_mesh_extract_sharp, RmMeshKeep, rm_mesh_keep_default, rm_mesh_components, RM_MESH_PART_LABELS / _SIZES, rm_mesh_components_download, rm_mesh_filter, RmMeshSimplify, rm_mesh_simplify_default, rm_mesh_simplify, RmMeshQuadric, rm_mesh_quadric_default, rm_mesh_simplify_quadric, RmMeshOcclusion, rm_mesh_occlusion_default, rm_mesh_occlusion_directions, rm_mesh_occlusion, RmMeshMeasures, rm_mesh_measure, rm_mesh_measure_components, RmMeshSlabs, rm_mesh_slabs_default, rm_mesh_extract_slabs, rm_mesh_extract_sharp_slabs, rm_mesh_from_values_slabs, RmMeshProject, RmMeshProjection, rm_mesh_project_default, rm_mesh_project (additions only); 8: RM_PRIM_TORUS / _CYLINDER / _PLANE, RM_OP_SMOOTH_SUBTRACT / _INTERSECT, rm_probe_math (additions only); 7: rm_present_sharded_finish / rm_present_sharded take the size of the host buffer (a changed signature), rm_ctx_set_cull_min_pixels, rm_ctx_set_cull_budget, rm_ctx_cull_stats; 6: rm_present_striped_rows, rm_present_sharded_start / _finish, rm_ctx_last_warning, RM_PROBE_CAST_SHADOW, RM_PRIM_KIND (additions only); 3: rm_ctx_set_sample_batch, rm_buffer_*; 4: rm_ctx_set_gl_stack; 5: RmSurface / RmSceneDesc.surfaces (the struct grew), rm_pack_present_rows, rm_present_sharded, rm_ctx_last_pipeline, RM_RENDER_NO_FAR_JUMP, RM_RENDER_NO_CULL (additions only) */
 
 #define RM_MAX_BOUNCES 10 /* raymarchingStepCountsArray[10], raymarcher.frag:31 */
 #define RM_MAX_LIGHTS 10  /* lightPositions[10],             raymarcher.frag:37-39 */
@@ -1231,6 +1231,77 @@ RM_API int rm_mesh_extract_slabs(rm_ctx* ctx, rm_scene* scene, const RmGrid* gri
 RM_API int rm_mesh_extract_sharp_slabs(rm_ctx* ctx, rm_scene* scene, const RmGrid* grid, const RmMeshParams* params, const RmMeshSharp* sharp,
                                        const RmMeshSlabs* slabs, rm_mesh** out);
 RM_API int rm_mesh_from_values_slabs(rm_ctx* ctx, const RmGrid* grid, const float* values_host, float iso, const RmMeshSlabs* slabs, rm_mesh** out);
+
+/* ---- projection onto the surface (opt-in): Newton steps of a mesh's vertices onto a level set of a scene ----
+ * Every stage that moves a vertex leaves it off the level set it came from: surface nets averages edge crossings, rm_mesh_simplify averages
+ * vertices, rm_mesh_simplify_quadric minimises against the source triangles.  rm_mesh_project puts the vertices back with the exact distance
+ * field, p <- p - n (d - iso), and reports on the device how far off they were and are.  It works on any rm_mesh (rm_mesh_extract, _sharp,
+ * _from_values, rm_mesh_filter, rm_mesh_simplify, _quadric, the slabbed entries, an earlier projection) with any scene of the mesh's context.
+ * The source is unchanged; the result is an ordinary rm_mesh of the same context that every later stage serves.  RM_MESH_TRIANGLES and
+ * RM_MESH_CELLS are carried bit for bit, RM_MESH_COLOURS too when the source has them; RM_MESH_NORMALS exist iff the source has them and are
+ * then rm_probe(RM_PROBE_NORMAL, param = normal_delta, flags) at the final positions.  The result starts without a labelling or measures;
+ * rm_mesh_download serves `what` 0..4 as before.  Only the VERTICES come to lie on the level set: triangles still chord it, and a vertex inside
+ * a corner goes to the nearest face, not to the corner -- the stage complements "sharp vertices" and "quadric placement", it replaces neither.
+ * params == NULL: the defaults (iso 0, rounds 4, relax 1, tolerance 0, reach 0, normal_delta 0x1p-10f, flags 0).  A block is valid iff iso is
+ * finite, rounds is in 1..16, relax is finite and in (0, 1], tolerance is finite and >= 0, reach is finite and >= 0, normal_delta is finite
+ * and > 0, flags are of rm_sdf_grid's set and reserved is 0.
+ * Arithmetic: fp32, every operation rounded on its own (no contraction), IEEE division, whatever the flags are: they select only the unit that
+ * evaluates the scene.  Per vertex with source position p0, p = p0, and for round r = 0, 1, ..:
+ *   1. d = RM_PROBE_SDF's bits at p for these flags on this context;  e = d - iso.  Round 0's e is e_before.
+ *   2. If e is not finite or |e| <= tolerance the vertex does not move this round.  Otherwise n = RM_PROBE_NORMAL's bits at p (param =
+ *      normal_delta); if a component of n is not finite or all three are zero the vertex is UNDIRECTED and does not move.
+ *   3. s = e * relax;  q[c] = p[c] - n[c] * s (one product, one difference).  With reach > 0: lo = p0[c] - reach, hi = p0[c] + reach;
+ *      if (q[c] < lo) q[c] = lo;  if (q[c] > hi) q[c] = hi; the vertex is CLAMPED if either test changed q.  If a component of q is not finite
+ *      the vertex does not move; otherwise p = q.  The round's `moved` counts the vertices whose p changed in bits.
+ *   4. The host reads `moved` behind each round and stops after the first round that moved nobody (every later round would repeat it, so the
+ *      result does not depend on the stop) or after `rounds` rounds.  rounds_run is the number of rounds evaluated.
+ *   5. e_after = RM_PROBE_SDF at the final p, minus iso.  Where the last round moved nobody these are that round's values.
+ *   6. Report.  Counts are integer sums.  max and worst come from one 64-bit atomicMax per wave on the key bits(|e|) << 32 | (0xFFFFFFFF - v)
+ *      over the finite e: the largest |e|, and among equals the smallest vertex.  mean = sum / count, rms = sqrt(sum2 / count) in double over
+ *      the finite e, where sum and sum2 are the FIXED-TREE sums of "measures and edge topology" of the V terms (double)|e| and (double)e *
+ *      (double)e in vertex order, +0.0 for a non-finite e.  With no finite e: worst, max, mean and rms are 0.
+ *   7. Flipped triangles.  Only triangles whose three indices are < V are examined.  c0, c1 = the cross product of "quadric placement" step 2
+ *      on the source and on the final positions;  dot = (c0x c1x + c0y c1y) + c0z c1z;  flipped iff dot < 0 (a NaN is not).
+ * Every output is a function of scene bits, integer sums and maxima, and that fixed tree: the same bytes on every run.
+ * Procedure (rm_mesh_kernels.inc "projection").  A round is two launches.  Evaluate, in all three units with launch_sdf_grid's kind selection:
+ * one lane per vertex stages the scene and enters the math mode as the probe kernel does, evaluates d, and evaluates the normal only when its
+ * wave has a lane with a finite e above the tolerance -- the evaluators branch wave-uniformly, so whole waves stop paying for normals as their
+ * vertices settle.  (A unit that runs with fp32 denormals flushed decides this on integers and, where d, iso or e is subnormal, for the
+ * normals; the step below decides for itself.)  Step, in the strict unit: the arithmetic of 1 - 3, a flags word per vertex, `moved` reduced in
+ * the wave, and in round 0 and behind the last round the report's terms with the first level of the tree.  One launch per triangle counts the
+ * flips.  No thread waits for another, no loop is unbounded, there are no floating-point atomics.  Scratch, freed before the call returns:
+ * 24 V bytes of d, n, flags and residual, 16 ceil(V / 256) bytes of group sums and 1/255 of that behind, 240 bytes of totals.
+ * The call is synchronous on the context's stream.  rm_mesh_timings of the result is {0, the rounds and the report between events on the
+ * stream, the normals' probe}.  report (may be NULL) receives the struct below; residual_host (may be NULL) V floats, e_after.  An empty mesh
+ * gives a valid empty mesh, an all-zero report (rounds_run 0) and nothing in residual_host.
+ * RM_ERR_INVALID, in this order (the text through rm_last_error(NULL) when no context is known): an invalid block, one text per field, before
+ * the handles are looked at; a NULL mesh, scene or out ("NULL argument"); a scene of another context than the mesh's ("the scene belongs to
+ * another context").  No refusal writes to out, report or residual_host.
+ * RM_ERR_DEVICE: V > INT_MAX; a failed allocation, with nothing leaked. */
+typedef struct RmMeshProject {   /* 32 bytes */
+  float iso;           /* the level to project onto (a mesh does not remember its own) */
+  int32_t rounds;      /* 1..16 */
+  float relax;         /* step = relax * (d - iso); finite, in (0, 1] */
+  float tolerance;     /* a vertex with |d - iso| <= tolerance does not move; finite, >= 0 */
+  float reach;         /* per axis, how far a vertex may end from where it started; finite, >= 0; 0 = no limit */
+  float normal_delta;  /* of the RM_PROBE_NORMAL that gives the direction; finite, > 0 */
+  int32_t flags;       /* 0, RM_RENDER_FAST, RM_RENDER_NO_CULL or both, as rm_sdf_grid */
+  int32_t reserved;    /* must be 0 */
+} RmMeshProject;
+typedef struct RmMeshProjection {  /* 144 bytes */
+  uint64_t vertices, triangles;                       /*   0,   8 */
+  uint64_t moved_vertices;                            /*  16: final position bits != source bits */
+  uint64_t settled_before, settled_after;             /*  24,  32: e finite and |e| <= tolerance */
+  uint64_t nonfinite_before, nonfinite_after;         /*  40,  48 */
+  uint64_t clamped_vertices, undirected_vertices;     /*  56,  64: in at least one round the reach clamp changed q / the normal was unusable */
+  uint64_t flipped_triangles;                         /*  72 */
+  uint64_t worst_before, worst_after;                 /*  80,  88: vertex index of the max, smallest index among ties; 0 with no finite e */
+  double mean_before, rms_before, mean_after, rms_after; /* 96..120: of |e| over the finite ones; 0 with none */
+  float max_before, max_after;                        /* 128, 132 */
+  int32_t rounds_run, reserved;                       /* 136, 140: reserved is written as 0 */
+} RmMeshProjection;
+RM_API void rm_mesh_project_default(RmMeshProject* params);
+RM_API int rm_mesh_project(rm_mesh* mesh, rm_scene* scene, const RmMeshProject* params, rm_mesh** out, RmMeshProjection* report, float* residual_host);
 
 #ifdef __cplusplus
 }

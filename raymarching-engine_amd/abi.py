@@ -377,6 +377,60 @@ MESH_SLABS_DEFAULTS = dict(layers=0)  # rm_mesh_slabs_default
 assert C.sizeof(RmMeshSlabs) == 8
 
 
+class RmMeshProject(C.Structure):
+    """Parameters of rm_mesh_project (ABI 9): up to `rounds` Newton steps p <- p - n * relax * (d - iso) of every vertex, at most `reach` per
+    axis from where it started (include/hip_raymarch.h "projection onto the surface")."""
+    _fields_ = [
+        ("iso", C.c_float),
+        ("rounds", C.c_int32),
+        ("relax", C.c_float),
+        ("tolerance", C.c_float),
+        ("reach", C.c_float),
+        ("normal_delta", C.c_float),
+        ("flags", C.c_int32),
+        ("reserved", C.c_int32),
+    ]
+
+
+MESH_PROJECT_DEFAULTS = dict(iso=0.0, rounds=4, relax=1.0, tolerance=0.0, reach=0.0, normal_delta=2.0 ** -10, flags=0)  # rm_mesh_project_default
+
+assert C.sizeof(RmMeshProject) == 32
+
+
+class RmMeshProjection(C.Structure):
+    """What rm_mesh_project says of its work (ABI 9): how far off the level set the vertices were and are, and what the steps met."""
+    _fields_ = [
+        ("vertices", C.c_uint64),
+        ("triangles", C.c_uint64),
+        ("moved_vertices", C.c_uint64),
+        ("settled_before", C.c_uint64),
+        ("settled_after", C.c_uint64),
+        ("nonfinite_before", C.c_uint64),
+        ("nonfinite_after", C.c_uint64),
+        ("clamped_vertices", C.c_uint64),
+        ("undirected_vertices", C.c_uint64),
+        ("flipped_triangles", C.c_uint64),
+        ("worst_before", C.c_uint64),
+        ("worst_after", C.c_uint64),
+        ("mean_before", C.c_double),
+        ("rms_before", C.c_double),
+        ("mean_after", C.c_double),
+        ("rms_after", C.c_double),
+        ("max_before", C.c_float),
+        ("max_after", C.c_float),
+        ("rounds_run", C.c_int32),
+        ("reserved", C.c_int32),
+    ]
+
+
+assert C.sizeof(RmMeshProjection) == 144
+
+
+def mesh_projection_dict(r: "RmMeshProjection") -> dict:
+    """The struct's fields as a dict, `reserved` left out."""
+    return {name: getattr(r, name) for name, _ in RmMeshProjection._fields_ if name != "reserved"}
+
+
 def mesh_measures_dict(m: "RmMeshMeasures") -> dict:
     """The struct's fields as a dict: lo and hi as tuples, `closed` as bool, `reserved` left out."""
     d = {name: getattr(m, name) for name, _ in RmMeshMeasures._fields_ if name != "reserved"}

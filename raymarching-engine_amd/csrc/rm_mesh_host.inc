@@ -1152,3 +1152,180 @@ int rm_mesh_measure_components(rm_mesh* mesh, void* host, size_t bytes) {
   std::memcpy(host, mesh->edge_rows.data(), bytes);
   return RM_OK;
 }
+
+// ---- projection onto the surface (include/hip_raymarch.h "projection onto the surface") -----------------------------------------------------------
+
+void rm_mesh_project_default(RmMeshProject* params) {
+  if (!params) return;
+  *params = RmMeshProject{0.0f, 4, 1.0f, 0.0f, 0.0f, 0x1p-10f, 0, 0};
+}
+
+static int mesh_project_check(const Refuse& refuse, const RmMeshProject* in, RmMeshProject* p) {
+  rm_mesh_project_default(p);
+  if (in) *p = *in;
+  if (!std::isfinite(p->iso)) return refuse("project iso must be finite");
+  if (p->rounds < 1 || p->rounds > 16) return refuse("project rounds must be in 1..16");
+  if (!(std::isfinite(p->relax) && p->relax > 0.0f && p->relax <= 1.0f)) return refuse("project relax must be finite and in (0, 1]");
+  if (!(std::isfinite(p->tolerance) && p->tolerance >= 0.0f)) return refuse("project tolerance must be finite and >= 0");
+  if (!(std::isfinite(p->reach) && p->reach >= 0.0f)) return refuse("project reach must be finite and >= 0");
+  if (!(std::isfinite(p->normal_delta) && p->normal_delta > 0.0f)) return refuse("project normal_delta must be finite and > 0");
+  if (int rc = sdf_flags_check(refuse, p->flags)) return rc;
+  if (p->reserved != 0) return refuse("project reserved must be 0");
+  return RM_OK;
+}
+
+int rm_mesh_project(rm_mesh* mesh, rm_scene* scene, const RmMeshProject* params, rm_mesh** out, RmMeshProjection* report, float* residual_host) {
+  rm_ctx* ctx = mesh ? mesh->ctx : nullptr;
+  const Refuse refuse{ctx, "rm_mesh_project"};
+  RmMeshProject p;
+  if (int rc = mesh_project_check(refuse, params, &p)) return rc;
+  if (int rc = scene_check(refuse, scene, out != nullptr)) return rc;  // (a NULL mesh is a NULL context there)
+  const unsigned long long V = mesh->vertices, T = mesh->triangles;
+  if (V > (unsigned long long)INT_MAX) return refuse("the mesh has more vertices than the kernels' int index holds (V > INT_MAX)", RM_ERR_DEVICE);
+  *out = nullptr;
+  RM_HIP(ctx, hipSetDevice(ctx->device));
+  DeviceArray d, normals, flags, residual, totals, levels;  // (before the mesh: freed behind the wait of whatever gives the mesh up, or the last one below)
+  MeshPtr made(new (std::nothrow) rm_mesh(ctx), rm_mesh_destroy);
+  if (!made) return refuse("out of host memory", RM_ERR_DEVICE);
+  for (int a = 0; a < 5; a++) made->has[a] = mesh->has[a];
+  RmMeshProjection r{};
+  if (V == 0) {
+    if (report) *report = r;
+    *out = made.release();
+    return RM_OK;
+  }
+  made->vertices = V;
+  made->triangles = T;
+  // the tree's levels behind the first, as rm_mesh_measure lays them out: groups[k] values each of the two lists
+  std::vector<long long> groups;
+  size_t level_elems = 0;
+  for (long long g = ((long long)V + 255) / 256;; g = (g + 255) / 256) {
+    groups.push_back(g);
+    if (g == 1) break;
+    level_elems += (size_t)g;
+  }
+  for (int what : {RM_MESH_POSITIONS, RM_MESH_NORMALS, RM_MESH_COLOURS, RM_MESH_TRIANGLES, RM_MESH_CELLS})
+    if (mesh->array[what].p) RM_HIP_AS(refuse, made->array[what].reserve(mesh_array_bytes(made.get(), what)));
+  RM_HIP_AS(refuse, d.reserve(sizeof(float) * (size_t)V));
+  RM_HIP_AS(refuse, normals.reserve(sizeof(float) * 3u * (size_t)V));
+  RM_HIP_AS(refuse, flags.reserve(sizeof(unsigned int) * (size_t)V));
+  RM_HIP_AS(refuse, residual.reserve(sizeof(float) * (size_t)V));
+  RM_HIP_AS(refuse, totals.reserve(sizeof(unsigned long long) * rm::RM_PROJECT_WORDS));
+  RM_HIP_AS(refuse, levels.reserve(sizeof(double) * 2u * level_elems));
+  if (int rc = scene_cull_grid(ctx, scene, p.flags, 1ll << 40)) return rc;  // (with the grid, as rm_probe obtains it)
+  for (int what : {RM_MESH_POSITIONS, RM_MESH_COLOURS, RM_MESH_TRIANGLES, RM_MESH_CELLS})
+    if (mesh->array[what].p)
+      RM_HIP_AS(refuse, hipMemcpyAsync(made->array[what].p, mesh->array[what].p, mesh_array_bytes(made.get(), what), hipMemcpyDeviceToDevice, ctx->stream));
+  float* positions = made->array[RM_MESH_POSITIONS].f32();
+  MeshProjectEval E{};
+  E.scene = scene->dev;
+  if (p.flags & RM_RENDER_NO_CULL) E.scene.cull.cells = nullptr;
+  E.positions = positions;
+  E.d = d.f32();
+  E.normals = normals.f32();
+  E.vertices = (int)V;
+  E.iso = p.iso;
+  E.tolerance = p.tolerance;
+  E.normal_delta = p.normal_delta;
+  rm::MeshProject S{};
+  S.vertices = (long long)V;
+  S.triangles = (long long)T;
+  S.source = mesh->array[RM_MESH_POSITIONS].f32();
+  S.positions = positions;
+  S.d = d.f32();
+  S.normals = normals.f32();
+  S.residual = residual.f32();
+  S.flags = flags.u32();
+  S.corners = made->array[RM_MESH_TRIANGLES].u32();
+  S.totals = totals.u64();
+  S.iso = p.iso;
+  S.relax = p.relax;
+  S.tolerance = p.tolerance;
+  S.reach = p.reach;
+  // a half of the report: the step kernel's first level, then the further levels into the half's two words of the totals
+  const auto report_half = [&](int round, int word) -> int {
+    double* const d_sum = reinterpret_cast<double*>(S.totals + word);
+    double* from = static_cast<double*>(levels.p);
+    const bool only = groups[0] == 1;
+    RM_HIP_AS(refuse, rm::launch_mesh_project_step(S, round, only ? d_sum : from, only ? d_sum + 1 : from + groups[0], ctx->stream));
+    for (size_t k = 1; k < groups.size(); k++) {
+      const bool last = groups[k] == 1;
+      double* to = from + 2 * groups[k - 1];
+      RM_HIP_AS(refuse, rm::launch_mesh_measure_sum(from, from + groups[k - 1], groups[k - 1], last ? d_sum : to, last ? d_sum + 1 : to + groups[k], ctx->stream));
+      from = to;
+    }
+    return RM_OK;
+  };
+  MeshSpans& spans = ctx->mesh_spans;
+  RM_HIP_AS(refuse, hipMemsetAsync(totals.p, 0, sizeof(unsigned long long) * rm::RM_PROJECT_WORDS, ctx->stream));
+  RM_HIP_AS(refuse, hipMemsetAsync(flags.p, 0, sizeof(unsigned int) * (size_t)V, ctx->stream));
+  RM_HIP_AS(refuse, spans.begin(MeshSpans::PROJECT_ROUNDS, ctx->stream));
+  unsigned long long moved = 0;
+  int rounds_run = 0;
+  for (int round = 0; round < p.rounds; round++) {
+    RM_HIP_AS(refuse, (p.flags & RM_RENDER_FAST) ? rm::launch_mesh_project_eval_fast(E, ctx->stream)
+                      : ctx->gl_stack           ? rm_gl_launch_mesh_project_eval(&E, ctx->stream)
+                                                : rm::launch_mesh_project_eval_strict(E, ctx->stream));
+    if (round == 0) {
+      if (int rc = report_half(0, rm::RM_PROJECT_SUM_BEFORE)) return rc;
+    } else {
+      RM_HIP_AS(refuse, rm::launch_mesh_project_step(S, round, nullptr, nullptr, ctx->stream));
+    }
+    rounds_run = round + 1;
+    if (int rc = copy_and_wait(ctx, &moved, S.totals + rm::RM_PROJECT_MOVED + round, sizeof moved, hipMemcpyDeviceToHost)) return rc;
+    if (moved == 0) break;  // (every later round would repeat this one)
+  }
+  // the residual after: where the last round moved nobody, d is already the distance at the final positions
+  if (moved != 0) RM_HIP_AS(refuse, probe_enqueue(ctx, scene, RM_PROBE_SDF, positions, d.f32(), (int)V, 0.0f, p.flags, ctx->stream));
+  if (int rc = report_half(-1, rm::RM_PROJECT_SUM_AFTER)) return rc;
+  RM_HIP_AS(refuse, rm::launch_mesh_project_flips(S, ctx->stream));
+  RM_HIP_AS(refuse, spans.end(MeshSpans::PROJECT_ROUNDS, ctx->stream));
+  const bool with_normals = made->array[RM_MESH_NORMALS].p != nullptr;
+  if (with_normals) {
+    RM_HIP_AS(refuse, spans.begin(MeshSpans::PROJECT_NORMALS, ctx->stream));
+    RM_HIP_AS(refuse, probe_enqueue(ctx, scene, RM_PROBE_NORMAL, positions, made->array[RM_MESH_NORMALS].f32(), (int)V, p.normal_delta, p.flags, ctx->stream));
+    RM_HIP_AS(refuse, spans.end(MeshSpans::PROJECT_NORMALS, ctx->stream));
+  }
+  unsigned long long got[rm::RM_PROJECT_WORDS] = {};
+  std::vector<float> e_after;
+  if (residual_host) {  // (through a buffer of the call's own: a refusal below writes nothing of the caller's)
+    try {
+      e_after.resize((size_t)V);
+    } catch (const std::bad_alloc&) {
+      return refuse("out of host memory", RM_ERR_DEVICE);
+    }
+    RM_HIP_AS(refuse, hipMemcpyAsync(e_after.data(), residual.p, sizeof(float) * (size_t)V, hipMemcpyDeviceToHost, ctx->stream));
+  }
+  if (int rc = copy_and_wait(ctx, got, totals.p, sizeof got, hipMemcpyDeviceToHost)) return rc;
+  made->ms[1] = spans.ms(MeshSpans::PROJECT_ROUNDS);
+  if (with_normals) made->ms[2] = spans.ms(MeshSpans::PROJECT_NORMALS);
+  r.vertices = V;
+  r.triangles = T;
+  r.moved_vertices = got[rm::RM_PROJECT_MOVED_VERTICES];
+  r.settled_before = got[rm::RM_PROJECT_SETTLED_BEFORE];
+  r.settled_after = got[rm::RM_PROJECT_SETTLED_AFTER];
+  r.nonfinite_before = got[rm::RM_PROJECT_NONFINITE_BEFORE];
+  r.nonfinite_after = got[rm::RM_PROJECT_NONFINITE_AFTER];
+  r.clamped_vertices = got[rm::RM_PROJECT_CLAMPED];
+  r.undirected_vertices = got[rm::RM_PROJECT_UNDIRECTED];
+  r.flipped_triangles = got[rm::RM_PROJECT_FLIPPED];
+  r.rounds_run = rounds_run;
+  const auto half = [&](int key_word, int sum_word, unsigned long long nonfinite, uint64_t* worst, float* max, double* mean, double* rms) {
+    const unsigned long long key = got[key_word], count = V - nonfinite;
+    if (key == 0ull || count == 0ull) return;  // no finite e: everything stays 0
+    const unsigned int bits = (unsigned int)(key >> 32);
+    std::memcpy(max, &bits, sizeof bits);
+    *worst = 0xFFFFFFFFull - (key & 0xFFFFFFFFull);
+    double sum, sum2;
+    std::memcpy(&sum, got + sum_word, sizeof sum);
+    std::memcpy(&sum2, got + sum_word + 1, sizeof sum2);
+    *mean = sum / (double)count;
+    *rms = std::sqrt(sum2 / (double)count);
+  };
+  half(rm::RM_PROJECT_KEY_BEFORE, rm::RM_PROJECT_SUM_BEFORE, r.nonfinite_before, &r.worst_before, &r.max_before, &r.mean_before, &r.rms_before);
+  half(rm::RM_PROJECT_KEY_AFTER, rm::RM_PROJECT_SUM_AFTER, r.nonfinite_after, &r.worst_after, &r.max_after, &r.mean_after, &r.rms_after);
+  if (report) *report = r;
+  if (residual_host) std::memcpy(residual_host, e_after.data(), sizeof(float) * (size_t)V);
+  *out = made.release();
+  return RM_OK;
+}

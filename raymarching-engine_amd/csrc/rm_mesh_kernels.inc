@@ -2,7 +2,7 @@
 // and -- in the strict unit only, they have no arithmetic of a policy's own -- the surface-nets mesher over such a grid, the two
 // kernels that move its vertices to their cells' QEF minimisers (rm_mesh_extract_sharp), and the integer kernels that label a mesh's
 // connected components and compact the kept ones (rm_mesh_components, rm_mesh_filter), and the vertex clustering of rm_mesh_simplify with the quadric placement of
-// rm_mesh_simplify_quadric, and the edge table, classes, extent and fixed-tree sums of rm_mesh_measure.  Included by
+// rm_mesh_simplify_quadric, and the edge table, classes, extent and fixed-tree sums of rm_mesh_measure, and the step and report of rm_mesh_project, whose evaluating kernel is in every unit.  Included by
 // rm_strict.hip / rm_fast.hip / rm_glstack.hip behind rm_kernels.inc.
 namespace rm {
 
@@ -151,6 +151,83 @@ hipError_t RM_LAUNCH(launch_mesh_occlusion)(const MeshOcclusionPass& P, hipStrea
     default: return hipErrorInvalidValue;
   }
 #undef RM_OCCLUSION_CASE
+  return hipGetLastError();
+}
+#endif
+
+// ---- projection: the scene's distance and normal at every vertex (the header's "projection onto the surface") ------------------------------
+// Whether a lane's vertex may step this round: e = d - iso is finite and |e| > tolerance.  The step kernel decides that for itself, in plain
+// IEEE; this copy only tells the evaluating kernel whether the wave needs normals, so it may say yes too often and never too seldom.  In a
+// kernel that runs with fp32 denormals flushed (enter_math_mode) the subtraction reads a subnormal operand as zero and writes a subnormal
+// result as zero, so everything behind it is integer: with a subnormal d or iso the answer is yes unless their bits agree; a difference of
+// zero is a true zero only where d == iso, and otherwise a flushed subnormal, which a tolerance below the normals cannot be told to cover.
+template <bool FLUSHED>
+__device__ inline bool mesh_project_wants(float d, float iso, float tolerance) {
+  if (!FLUSHED) {
+    const float e = d - iso;
+    return isfinite(e) && fabsf(e) > tolerance;
+  }
+  const unsigned int bd = __float_as_uint(d), bi = __float_as_uint(iso), bt = __float_as_uint(tolerance) & 0x7FFFFFFFu;
+  const unsigned int ad = bd & 0x7FFFFFFFu, ai = bi & 0x7FFFFFFFu;
+  if (ad >= 0x7F800000u) return false;       // (iso is finite: e is not)
+  if (bd == bi || (ad | ai) == 0u) return false;  // e is a zero
+  if ((ad != 0u && ad < 0x00800000u) || (ai != 0u && ai < 0x00800000u)) return true;
+  const unsigned int ae = __float_as_uint(d - iso) & 0x7FFFFFFFu;
+  if (ae >= 0x7F800000u) return false;
+  if (ae < 0x00800000u) return bt < 0x00800000u;  // a flushed subnormal
+  return ae > bt;
+}
+
+// One lane per vertex.  The scene is staged and the math mode entered as the probe kernel does, and d and the normal are that kernel's
+// RM_PROBE_SDF and RM_PROBE_NORMAL at the vertex: the same calls on the same policies.  A wave none of whose lanes wants a normal leaves
+// before scene_normal's four evaluations, whole: the evaluators ballot and branch wave-uniformly, so no single lane may.  Lanes beyond V
+// repeat the last vertex, which changes no ballot, and store nothing.
+template <int KIND, bool FAST>
+__global__ __launch_bounds__(256) void rm_mesh_project_eval_kernel(const MeshProjectEval P) {
+  using MM = typename std::conditional<FAST, FM, PM>::type;
+  constexpr bool kFlushed = FAST && (KIND == RM_SCENE_MANDELBULB || KIND == RM_KIND_BULB8 || KIND == RM_KIND_TABLE_KINDS);  // enter_math_mode's rule
+  __shared__ SceneLds lds;
+  const long long gi = (long long)blockIdx.x * 256 + threadIdx.x;  // (V goes up to INT_MAX: the last workgroup's indices pass it)
+  const int v = gi < P.vertices ? (int)gi : P.vertices - 1;
+  const v3 p = V(P.positions[3 * (size_t)v], P.positions[3 * (size_t)v + 1], P.positions[3 * (size_t)v + 2]);
+  enter_math_mode<KIND, FAST>();
+  Sdf<KIND>::stage(P.scene, lds);
+  __syncthreads();
+  const float d = Sdf<KIND>::template eval<MM>(P.scene, lds, p);
+  if (gi < P.vertices) P.d[v] = d;
+  if (__ballot(mesh_project_wants<kFlushed>(d, P.iso, P.tolerance)) == 0ull) return;
+  const v3 n = scene_normal<KIND>(P.scene, lds, p, P.normal_delta);
+  if (gi < P.vertices) {
+    P.normals[3 * (size_t)v] = n.x;
+    P.normals[3 * (size_t)v + 1] = n.y;
+    P.normals[3 * (size_t)v + 2] = n.z;
+  }
+}
+
+#ifndef RM_ONLY_KERNELS
+// the kind selection is launch_sdf_grid's, row for row: the bits have to be the probes' at that point
+hipError_t RM_LAUNCH(launch_mesh_project_eval)(const MeshProjectEval& P, hipStream_t stream) {
+  const dim3 grid((unsigned int)(((long long)P.vertices + 255) / 256));
+#define RM_PROJECT_CASE(K) case K: hipLaunchKernelGGL((rm_mesh_project_eval_kernel<K, kFast>), grid, dim3(256), 0, stream, P); break;
+  if (P.scene.kind == RM_SCENE_TABLE && (P.scene.table_flags & RM_TABLE_HAS_KIND)) {
+    hipLaunchKernelGGL((rm_mesh_project_eval_kernel<RM_KIND_TABLE_KINDS, kFast>), grid, dim3(256), 0, stream, P);
+    return hipGetLastError();
+  }
+  if (P.scene.kind == RM_SCENE_TABLE && P.scene.nprims >= RM_TABLE_BIG_ROWS) {
+    hipLaunchKernelGGL((rm_mesh_project_eval_kernel<RM_KIND_TABLE_BIG, kFast>), grid, dim3(256), 0, stream, P);
+    return hipGetLastError();
+  }
+  switch (P.scene.kind) {
+    RM_PROJECT_CASE(RM_SCENE_TABLE)
+    RM_PROJECT_CASE(RM_SCENE_MANDELBULB)
+    RM_PROJECT_CASE(RM_SCENE_SPHERE_GRID)
+    RM_PROJECT_CASE(RM_SCENE_SPHERE_LATTICE)
+    RM_PROJECT_CASE(RM_SCENE_MENGER)
+    RM_PROJECT_CASE(RM_SCENE_KIFS_TREE)
+    RM_PROJECT_CASE(RM_SCENE_KIFS_BOX)
+    default: return hipErrorInvalidValue;
+  }
+#undef RM_PROJECT_CASE
   return hipGetLastError();
 }
 #endif
@@ -1225,6 +1302,114 @@ __global__ __launch_bounds__(256) void rm_mesh_measure_sum_kernel(const double* 
   if (threadIdx.x == 0u) { out_area[blockIdx.x] = s[0][0]; out_volume[blockIdx.x] = s[1][0]; }
 }
 
+// ---- projection: the step and the report (include/hip_raymarch.h "projection onto the surface") ---------------------------------------------
+// The scene is evaluated by rm_mesh_project_eval_kernel between these launches (rm_mesh_host.inc rm_mesh_project); this kernel only consumes
+// its output, in this unit's plain fp32: every operation rounded on its own.  One thread per vertex, and every thread of a workgroup stays to
+// the end: the ballots and the tree read all of them.  What a run can differ in is an integer sum or a maximum; the doubles go through the
+// measures' fixed tree.
+__global__ __launch_bounds__(256) void rm_mesh_project_step_kernel(const MeshProject S, int round, double* sum, double* sum2) {
+  __shared__ double s[2][256];
+  const long long v = (long long)blockIdx.x * 256 + threadIdx.x;
+  const bool valid = v < S.vertices;
+  float e = 0.0f;
+  bool finite = false, moved = false;
+  if (valid) {
+    e = S.d[v] - S.iso;
+    finite = isfinite(e);
+  }
+  if (round >= 0) {
+    if (valid && finite && fabsf(e) > S.tolerance) {
+      const float nx = S.normals[3 * v], ny = S.normals[3 * v + 1], nz = S.normals[3 * v + 2];
+      unsigned int flags = 0u;
+      if (!(isfinite(nx) && isfinite(ny) && isfinite(nz)) || (nx == 0.0f && ny == 0.0f && nz == 0.0f)) {
+        flags = RM_PROJECT_FLAG_UNDIRECTED;
+      } else {
+        const float step = e * S.relax;
+        const float n[3] = {nx, ny, nz};
+        float p[3], q[3];
+        bool clamped = false;
+#pragma unroll
+        for (int c = 0; c < 3; c++) {
+          p[c] = S.positions[3 * v + c];
+          const float along = n[c] * step;
+          q[c] = p[c] - along;
+          if (S.reach > 0.0f) {
+            const float p0 = S.source[3 * v + c], lo = p0 - S.reach, hi = p0 + S.reach;
+            if (q[c] < lo) { q[c] = lo; clamped = true; }
+            if (q[c] > hi) { q[c] = hi; clamped = true; }
+          }
+        }
+        if (clamped) flags = RM_PROJECT_FLAG_CLAMPED;
+        if (isfinite(q[0]) && isfinite(q[1]) && isfinite(q[2])) {
+#pragma unroll
+          for (int c = 0; c < 3; c++) {
+            moved = moved || __float_as_uint(q[c]) != __float_as_uint(p[c]);
+            S.positions[3 * v + c] = q[c];
+          }
+        }
+      }
+      if (flags != 0u) S.flags[v] |= flags;  // (the vertex is this thread's alone)
+    }
+    mesh_measure_count(S.totals + RM_PROJECT_MOVED + round, moved);
+    if (round > 0) return;  // (the whole workgroup)
+  } else {
+    unsigned int flags = 0u;
+    if (valid) {
+      S.residual[v] = e;
+      flags = S.flags[v];
+      moved = __float_as_uint(S.positions[3 * v]) != __float_as_uint(S.source[3 * v]) ||
+              __float_as_uint(S.positions[3 * v + 1]) != __float_as_uint(S.source[3 * v + 1]) ||
+              __float_as_uint(S.positions[3 * v + 2]) != __float_as_uint(S.source[3 * v + 2]);
+    }
+    mesh_measure_count(S.totals + RM_PROJECT_CLAMPED, (flags & RM_PROJECT_FLAG_CLAMPED) != 0u);
+    mesh_measure_count(S.totals + RM_PROJECT_UNDIRECTED, (flags & RM_PROJECT_FLAG_UNDIRECTED) != 0u);
+    mesh_measure_count(S.totals + RM_PROJECT_MOVED_VERTICES, moved);
+  }
+  // a half of the report: round 0 the one before, round -1 the one after
+  const int after = round < 0 ? 1 : 0;
+  mesh_measure_count(S.totals + RM_PROJECT_SETTLED_BEFORE + after, valid && finite && fabsf(e) <= S.tolerance);
+  mesh_measure_count(S.totals + RM_PROJECT_NONFINITE_BEFORE + after, valid && !finite);
+  unsigned long long key = valid && finite ? ((unsigned long long)__float_as_uint(fabsf(e)) << 32 | (0xFFFFFFFFull - (unsigned long long)v)) : 0ull;
+#pragma unroll
+  for (int m = 1; m < 64; m <<= 1) {
+    const unsigned long long other = __shfl_xor(key, m);
+    if (other > key) key = other;
+  }
+  if ((threadIdx.x & 63u) == 0u && key != 0ull) atomicMax(S.totals + RM_PROJECT_KEY_BEFORE + after, key);
+  s[0][threadIdx.x] = valid && finite ? (double)fabsf(e) : 0.0;
+  s[1][threadIdx.x] = valid && finite ? (double)e * (double)e : 0.0;
+  mesh_measure_tree(s);
+  if (threadIdx.x == 0u) { sum[blockIdx.x] = s[0][0]; sum2[blockIdx.x] = s[1][0]; }
+}
+
+// One thread per triangle with three indices < V: the cross products of "quadric placement" step 2 on the source and on the final positions;
+// flipped iff their dot product is < 0 (a NaN is not).
+__device__ inline void mesh_project_cross(const float* positions, unsigned int i0, unsigned int i1, unsigned int i2, float* c) {
+  const float* p0 = positions + 3 * (size_t)i0;
+  const float* p1 = positions + 3 * (size_t)i1;
+  const float* p2 = positions + 3 * (size_t)i2;
+  const float e1x = p1[0] - p0[0], e1y = p1[1] - p0[1], e1z = p1[2] - p0[2];
+  const float e2x = p2[0] - p0[0], e2y = p2[1] - p0[1], e2z = p2[2] - p0[2];
+  c[0] = e1y * e2z - e1z * e2y;
+  c[1] = e1z * e2x - e1x * e2z;
+  c[2] = e1x * e2y - e1y * e2x;
+}
+__global__ __launch_bounds__(256) void rm_mesh_project_flips_kernel(const MeshProject S) {
+  const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
+  bool flipped = false;
+  if (t < S.triangles) {
+    const unsigned int i0 = S.corners[3 * t], i1 = S.corners[3 * t + 1], i2 = S.corners[3 * t + 2];
+    if (i0 < S.vertices && i1 < S.vertices && i2 < S.vertices) {
+      float c0[3], c1[3];
+      mesh_project_cross(S.source, i0, i1, i2, c0);
+      mesh_project_cross(S.positions, i0, i1, i2, c1);
+      const float dot = (c0[0] * c1[0] + c0[1] * c1[1]) + c0[2] * c1[2];
+      flipped = dot < 0.0f;
+    }
+  }
+  mesh_measure_count(S.totals + RM_PROJECT_FLIPPED, flipped);
+}
+
 #ifndef RM_ONLY_KERNELS
 static inline long long mesh_cells(const GridDims& g) { return (long long)(g.nc[0] - 1) * (g.nc[1] - 1) * (g.nc[2] - 1); }
 
@@ -1336,6 +1521,11 @@ hipError_t launch_mesh_measure_terms(const MeshMeasure& M, double* area, double*
 hipError_t launch_mesh_measure_sum(const double* area, const double* volume, long long n, double* out_area, double* out_volume, hipStream_t stream) {
   RM_MESH_PARTS_LAUNCH(rm_mesh_measure_sum_kernel, n, area, volume, n, out_area, out_volume);
 }
+// projection: one thread per vertex or triangle
+hipError_t launch_mesh_project_step(const MeshProject& S, int round, double* sum, double* sum2, hipStream_t stream) {
+  RM_MESH_PARTS_LAUNCH(rm_mesh_project_step_kernel, S.vertices, S, round, sum, sum2);
+}
+hipError_t launch_mesh_project_flips(const MeshProject& S, hipStream_t stream) { RM_MESH_PARTS_LAUNCH(rm_mesh_project_flips_kernel, S.triangles, S); }
 #undef RM_MESH_PARTS_LAUNCH
 
 hipError_t launch_mesh_emit(const MeshParams& P, hipStream_t stream) {

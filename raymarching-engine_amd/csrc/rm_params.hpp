@@ -327,6 +327,16 @@ struct MeshOcclusionPass {
   float strength;
   float scale;               // 2^-(16 + log2 K + log2 J)
 };
+// rm_mesh_project's evaluating launch: one lane per vertex, Sdf<KIND>::eval at its position with the probe's scene block, and scene_normal
+// there in the waves that have a lane with a finite d - iso above the tolerance (the other waves leave their normals as they are).
+struct MeshProjectEval {
+  DevScene scene;
+  const float* positions;  // V x 3: the round's p
+  float* d;                // V
+  float* normals;          // V x 3
+  int vertices;
+  float iso, tolerance, normal_delta;
+};
 // The surface-nets mesher over a grid of values.  counts: per cell (vertex flag) | (quads << 32), scanned in place into the cell's
 // first vertex | first quad; the emit pass reads a neighbour's vertex index from there (every cell round a crossing edge is active).
 struct MeshParams {
@@ -601,6 +611,37 @@ hipError_t launch_mesh_measure_extent(const MeshMeasure& M, hipStream_t stream);
 // area[g], volume[g] = the tree sums of group g's 256 triangles
 hipError_t launch_mesh_measure_terms(const MeshMeasure& M, double* area, double* volume, hipStream_t stream);
 hipError_t launch_mesh_measure_sum(const double* area, const double* volume, long long n, double* out_area, double* out_volume, hipStream_t stream);
+// Projection (rm_mesh_project).  project_eval, in each unit's arithmetic: d and, where a wave needs them, the normals at the round's positions.
+// project_step (strict unit: plain fp32): round r >= 0 takes one step of every vertex from (d, normals), counts the moved ones into
+// totals[RM_PROJECT_MOVED + r], keeps the flags, and in round 0 makes the report's "before" half; round -1 moves nothing: d is the distance at
+// the final positions, and it writes the residual, the report's "after" half and the counts over the flags.  A report half: the counts, the
+// key of the maximum, and the first level of the two fixed-tree sums into sum[g], sum2[g] (launch_mesh_measure_sum makes the further levels).
+// project_flips: one thread per triangle.  totals: RM_PROJECT_WORDS 64-bit words, zeroed by the host before the first launch.
+enum {
+  RM_PROJECT_SETTLED_BEFORE, RM_PROJECT_SETTLED_AFTER, RM_PROJECT_NONFINITE_BEFORE, RM_PROJECT_NONFINITE_AFTER, RM_PROJECT_MOVED_VERTICES,
+  RM_PROJECT_CLAMPED, RM_PROJECT_UNDIRECTED, RM_PROJECT_FLIPPED,
+  RM_PROJECT_KEY_BEFORE, RM_PROJECT_KEY_AFTER,  // bits(|e|) << 32 | (0xFFFFFFFF - v), maximised; 0: no finite e
+  RM_PROJECT_SUM_BEFORE, RM_PROJECT_SUM2_BEFORE, RM_PROJECT_SUM_AFTER, RM_PROJECT_SUM2_AFTER,  // doubles
+  RM_PROJECT_MOVED,                             // 16 words: the vertices that round r moved
+  RM_PROJECT_WORDS = RM_PROJECT_MOVED + 16
+};
+enum { RM_PROJECT_FLAG_CLAMPED = 1, RM_PROJECT_FLAG_UNDIRECTED = 2 };
+struct MeshProject {
+  long long vertices, triangles;
+  const float* source;          // V x 3: p0
+  float* positions;             // V x 3: p
+  const float* d;               // V
+  const float* normals;         // V x 3
+  float* residual;              // V: written by round -1
+  unsigned int* flags;          // V
+  const unsigned int* corners;  // T x 3
+  unsigned long long* totals;   // RM_PROJECT_WORDS
+  float iso, relax, tolerance, reach;
+};
+hipError_t launch_mesh_project_eval_strict(const MeshProjectEval& P, hipStream_t stream);
+hipError_t launch_mesh_project_eval_fast(const MeshProjectEval& P, hipStream_t stream);
+hipError_t launch_mesh_project_step(const MeshProject& S, int round, double* sum, double* sum2, hipStream_t stream);
+hipError_t launch_mesh_project_flips(const MeshProject& S, hipStream_t stream);
 hipError_t launch_camera_rng(const RmUniforms& u, int W, int H, int what, int count, float* out, hipStream_t stream);
 hipError_t launch_math_probe(int fn, const float* a, const float* b, int n, float* out, hipStream_t stream);
 }  // namespace rm

@@ -129,6 +129,8 @@ export class RenderJobContext {
   extractMesh(scene: Scene, grid: MeshGrid, params: MeshParams | null | undefined, sharp: MeshSharp | true | null | undefined, keep: MeshKeep | true | null | undefined, components: boolean | undefined, simplify: MeshSimplify | null | undefined, quadric: MeshQuadric | true | null | undefined, occlusion: MeshOcclusion | true | null | undefined, measures: boolean): Mesh;
   /** with `slabs` (true = the defaults, a number = the cell layers per slab): rm_mesh_extract_slabs / rm_mesh_extract_sharp_slabs, the same mesh byte for byte, made from one window of z layers at a time; it also takes a meshGrid(lo, hi, n, { slabs: true }) beyond 2^28 corners */
   extractMesh(scene: Scene, grid: MeshGrid, params: MeshParams | null | undefined, sharp: MeshSharp | true | null | undefined, keep: MeshKeep | true | null | undefined, components: boolean | undefined, simplify: MeshSimplify | null | undefined, quadric: MeshQuadric | true | null | undefined, occlusion: MeshOcclusion | true | null | undefined, measures: boolean | undefined, slabs: MeshSlabs | number | true | null): Mesh;
+  /** project: the vertices of the returned mesh are moved onto the scene's level set (rm_mesh_project) behind simplify, quadric and keep, before components, occlusion and measures; iso defaults to params.iso, reach to meshProjectReach of the grid the mesh lies on; the result carries `projection` and `residual` */
+  extractMesh(scene: Scene, grid: MeshGrid, params: MeshParams | null | undefined, sharp: MeshSharp | true | null | undefined, keep: MeshKeep | true | null | undefined, components: boolean | undefined, simplify: MeshSimplify | null | undefined, quadric: MeshQuadric | true | null | undefined, occlusion: MeshOcclusion | true | null | undefined, measures: boolean | undefined, slabs: MeshSlabs | number | true | null | undefined, project: MeshProject | true | null): Mesh;
   /** the mesher alone on the caller's field (rm_mesh_from_values); keep, components and simplify as in extractMesh */
   meshFromValues(grid: MeshGrid, values: Float32Array, iso?: number, keep?: MeshKeep | true | null, components?: boolean, simplify?: MeshSimplify | null): Mesh;
   /** quadric as in extractMesh */
@@ -168,7 +170,7 @@ export const RM: { [name: string]: number };
 /** mesh extraction (include/hip_raymarch.h "mesh extraction"): n = CELLS per axis between the corners lo and hi */
 export interface MeshGrid { lo: [number, number, number]; hi: [number, number, number]; n: [number, number, number]; slabs?: true }
 export interface MeshParams { iso?: number; normals?: boolean | 0 | 1; normalDelta?: number; colours?: boolean | 0 | 1; flags?: number }
-export interface Mesh { positions: Float32Array; normals: Float32Array | null; colours: Float32Array | null; triangles: Uint32Array; cells: Uint32Array; /** ms of sampling, meshing, attributes (rm_mesh_timings); with an occlusion a fourth entry, its probes and taps */ timings: [number, number, number] | [number, number, number, number]; /** only when components were asked for: each vertex's component, and (vertices, triangles) per component */ labels?: Uint32Array; componentSizes?: Uint32Array; /** only when an occlusion was asked for: 1 = open, per vertex (rm_mesh_occlusion) */ occlusion?: Float32Array; /** only when measures were asked for (rm_mesh_measure) */ measures?: MeshMeasures }
+export interface Mesh { positions: Float32Array; normals: Float32Array | null; colours: Float32Array | null; triangles: Uint32Array; cells: Uint32Array; /** ms of sampling, meshing, attributes (rm_mesh_timings); with an occlusion a fourth entry, its probes and taps */ timings: [number, number, number] | [number, number, number, number]; /** only when components were asked for: each vertex's component, and (vertices, triangles) per component */ labels?: Uint32Array; componentSizes?: Uint32Array; /** only when an occlusion was asked for: 1 = open, per vertex (rm_mesh_occlusion) */ occlusion?: Float32Array; /** only when measures were asked for (rm_mesh_measure) */ measures?: MeshMeasures; /** only with `project`: what rm_mesh_project reports, and the distance minus iso at the projected vertices */ projection?: MeshProjection; residual?: Float32Array }
 /** what rm_mesh_measure says of a mesh (RmMeshMeasures, include/hip_raymarch.h "measures and edge topology"): the counts as Numbers (all below 2^53), lo / hi of the finite vertices, closed = no boundary and no irregular edge; componentEdges: 4 uint64 per component (edges, boundary, irregular, unbalanced; rm_mesh_measure_components); milliseconds of topology and geometry */
 export interface MeshMeasures { vertices: number; triangles: number; usedVertices: number; skippedTriangles: number; unmeasuredTriangles: number; finiteVertices: number; edges: number; boundaryEdges: number; regularEdges: number; irregularEdges: number; unbalancedEdges: number; euler: number; components: number; closedComponents: number; area: number; volume: number; lo: [number, number, number]; hi: [number, number, number]; closed: boolean; componentEdges: BigUint64Array; milliseconds: [number, number] }
 export const MESH_DEFAULTS: { iso: number; normals: 0 | 1; normalDelta: number; colours: 0 | 1; flags: number };
@@ -200,6 +202,14 @@ export function meshQuadric(quadric?: MeshQuadric | null): { threshold: number }
 export interface MeshOcclusion { radius?: number; directions?: number; taps?: number; normalDelta?: number; strength?: number; flags?: number }
 export const MESH_OCCLUSION_DEFAULTS: { radius: number; directions: number; taps: number; normalDelta: number; strength: number; flags: number };
 export function meshOcclusion(occlusion?: MeshOcclusion | null): { radius: number; directions: number; taps: number; normalDelta: number; strength: number; flags: number };
+/** the block of rm_mesh_project (RmMeshProject): up to `rounds` (1..16) Newton steps of every vertex onto the level `iso` of the scene, `relax` (in (0, 1]) of each step taken, at most `reach` per axis from where the vertex started (0 = no limit); a vertex within `tolerance` of the level does not move */
+export interface MeshProject { iso?: number; rounds?: number; relax?: number; tolerance?: number; reach?: number; normalDelta?: number; flags?: number }
+export const MESH_PROJECT_DEFAULTS: Required<MeshProject>;
+export function meshProject(project?: MeshProject | null): Required<MeshProject>;
+/** the reach extractMesh takes when `project` names none: half the smallest cell side of the grid, in fp32 */
+export function meshProjectReach(grid: MeshGrid): number;
+/** what rm_mesh_project says of its work (RmMeshProjection): how far off the level set the vertices were and are (|distance - iso|: worst vertex, max, mean, rms), the vertices the reach clamped or that had no usable normal, the triangles whose orientation flipped, the rounds evaluated; milliseconds: the rounds and the normals */
+export interface MeshProjection { vertices: number; triangles: number; movedVertices: number; settledBefore: number; settledAfter: number; nonfiniteBefore: number; nonfiniteAfter: number; clampedVertices: number; undirectedVertices: number; flippedTriangles: number; worstBefore: number; worstAfter: number; meanBefore: number; rmsBefore: number; meanAfter: number; rmsAfter: number; maxBefore: number; maxAfter: number; roundsRun: number; milliseconds: number }
 /** binary little-endian PLY (normals, uchar colours and a float `quality` -- the occlusion -- when present): the bytes the Python host's write_ply writes */
 /** binary STL of the triangles, facet normals computed in double from the float32 positions: the bytes the Python host's mesh.encode_stl writes */
 export function encodeStl(mesh: { positions: Float32Array; triangles: Uint32Array }): Buffer;

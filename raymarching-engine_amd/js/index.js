@@ -371,9 +371,30 @@ class RenderJobContext {  // RenderJobContext + loadRenderJobContext (LoadRender
   // milliseconds: [topology, geometry].  timings is as without it.
   // slabs: undefined / null = those calls; true, a number of cell layers or meshSlabs' options = rm_mesh_extract_slabs / _sharp_slabs, the same
   // mesh byte for byte, made from one window of z layers at a time -- which also takes a meshGrid(lo, hi, n, { slabs: true }) beyond 2^28 corners
-  extractMesh(scene, grid, opts, sharp, keep, components, simplify = null, quadric = null, occlusion = null, measures = false, slabs = null) {
+  // project: undefined / null = that mesh; true or meshProject's options = the vertices of the mesh that is returned moved onto the scene's level set
+  // by Newton steps on the GPU (rm_mesh_project) behind simplify, quadric and keep, before components, occlusion and measures, which then see the
+  // projected mesh.  iso, where not given, is the extraction's; reach, where not given, is meshProjectReach of the grid the returned mesh lies on (the
+  // cluster grid with simplify, else the sampling grid).  The result carries projection (RmMeshProjection's fields in camel case, and milliseconds:
+  // the rounds and the normals) and residual (Float32Array(V): the distance minus iso at the new vertices); timings stays the producing mesh's
+  extractMesh(scene, grid, opts, sharp, keep, components, simplify = null, quadric = null, occlusion = null, measures = false, slabs = null, project = null) {
     const q = quadric === undefined || quadric === null ? null : meshQuadric(quadric === true ? undefined : quadric);
     if (q !== null && (simplify === undefined || simplify === null)) throw new TypeError("mesh: quadric places the vertices of a simplification: give simplify as well");
+    if (project !== undefined && project !== null) {  // (every argument is given: the project block is the last)
+      const params = meshParams(opts);
+      const c = simplify === undefined || simplify === null ? null : meshSimplify(simplify);
+      const given = project === true ? {} : project;
+      if (typeof given !== "object") throw new TypeError("mesh: expected true or an object of project parameters");
+      const pr = meshProject({ iso: params.iso, reach: meshProjectReach(c !== null ? c.grid : grid), ...given });
+      const o = occlusion === undefined || occlusion === null ? null : meshOcclusion(occlusion === true ? undefined : occlusion);
+      const s = sharp === undefined || sharp === null ? null : meshSharp(sharp === true ? undefined : sharp);
+      const k = keep === undefined || keep === null ? null : meshKeep(keep === true ? undefined : keep);
+      if (slabs !== undefined && slabs !== null) {
+        const w = meshSlabs(slabs === true ? undefined : typeof slabs === "number" ? { layers: slabs } : slabs);
+        return addon.extractMeshSlabs(this.ctx, this.sceneHandle(scene), grid, w, params, s, k, !!components, c, q, o, !!measures, pr);
+      }
+      if (grid && grid.slabs) throw new TypeError("mesh: a grid made with slabs: true is extracted in slabs: give slabs as well");
+      return addon.extractMesh(this.ctx, this.sceneHandle(scene), grid, params, s, k, !!components, c, q, o, !!measures, pr);
+    }
     if (slabs !== undefined && slabs !== null) {
       const w = meshSlabs(slabs === true ? undefined : typeof slabs === "number" ? { layers: slabs } : slabs);
       const o = occlusion === undefined || occlusion === null ? null : meshOcclusion(occlusion === true ? undefined : occlusion);
@@ -830,6 +851,36 @@ function meshOcclusion(opts) {
   return p;
 }
 
+// the projection block of rm_mesh_project (include/hip_raymarch.h RmMeshProject): undefined / null = the defaults, or an object with some of iso
+// (the level to project onto), rounds (1..16), relax (in (0, 1]), tolerance (>= 0), reach (>= 0; 0 = no limit), normalDelta (> 0) and flags
+// (RM.RENDER_FAST, RM.RENDER_NO_CULL); checked as the library checks it
+const MESH_PROJECT_DEFAULTS = { iso: 0, rounds: 4, relax: 1, tolerance: 0, reach: 0, normalDelta: 2 ** -10, flags: 0 };
+function meshProject(opts) {
+  const p = { ...MESH_PROJECT_DEFAULTS };
+  if (opts !== undefined && opts !== null) {
+    if (typeof opts !== "object") throw new TypeError("mesh: expected an object of project parameters");
+    for (const [k, v] of Object.entries(opts)) {
+      if (!(k in MESH_PROJECT_DEFAULTS)) throw new TypeError("mesh: unknown project parameter " + k);
+      p[k] = v;
+    }
+  }
+  if (!finite(p.iso) || !finite(Math.fround(p.iso))) throw new RangeError("mesh: project iso must be finite");
+  if (!Number.isInteger(p.rounds) || p.rounds < 1 || p.rounds > 16) throw new RangeError("mesh: project rounds must be an integer in 1..16");
+  if (!finite(p.relax) || !(Math.fround(p.relax) > 0 && Math.fround(p.relax) <= 1)) throw new RangeError("mesh: project relax must be finite and in (0, 1]");
+  if (!finite(p.tolerance) || !finite(Math.fround(p.tolerance)) || !(p.tolerance >= 0)) throw new RangeError("mesh: project tolerance must be finite and >= 0");
+  if (!finite(p.reach) || !finite(Math.fround(p.reach)) || !(p.reach >= 0)) throw new RangeError("mesh: project reach must be finite and >= 0");
+  if (!POSITIVE[0](p.normalDelta) || !POSITIVE[0](Math.fround(p.normalDelta))) throw new RangeError("mesh: project normalDelta " + POSITIVE[1]);
+  if (!Number.isInteger(p.flags) || (p.flags & ~(RM.RENDER_FAST | RM.RENDER_NO_CULL)) !== 0) throw new RangeError("mesh: project flags must be 0, RM.RENDER_FAST, RM.RENDER_NO_CULL or both");
+  return p;
+}
+
+// the reach extractMesh(..., project) takes when none is given: half the smallest cell side of the grid, 0.5f * min h[a] with h in fp32 by RmGrid's rule
+function meshProjectReach(grid) {
+  let least = Infinity;
+  for (let a = 0; a < 3; a++) least = Math.min(least, Math.fround(Math.fround(Math.fround(grid.hi[a]) - Math.fround(grid.lo[a])) / Math.fround(grid.n[a])));
+  return Math.fround(0.5 * least);
+}
+
 // binary little-endian PLY of { positions, triangles, normals?, colours?, occlusion? }: x y z, then nx ny nz, then uchar red green blue
 // (floor(clamp(c, 0, 1) * 255 + 0.5), NaN as 0), then float quality (the occlusion); faces as a uchar count and uint indices -- the bytes the
 // Python host writes
@@ -910,4 +961,4 @@ module.exports = { RM, addon, encodePng, Scene, CsgScene, Mandelbulb, singleSphe
                    tileRect, RenderJobContext, ShardedRenderJobContext, doRenderJob, U_OFFSET, DENOISE_DEFAULTS, denoiseParams,
                    DENOISE_VARIANCE_DEFAULTS, denoiseVarianceParams, DESPECKLE_DEFAULTS, despeckleParams, DISPLAY_DEFAULTS, AUTO_EXPOSURE_DEFAULTS,
                    displayParams, statsExposure, statsPercentile, MESH_DEFAULTS, meshGrid, meshParams, MESH_SHARP_DEFAULTS, meshSharp, MESH_KEEP_DEFAULTS, meshKeep, MESH_SLABS_DEFAULTS, meshSlabs,
-                   MESH_SIMPLIFY_DEFAULTS, meshSimplify, MESH_QUADRIC_DEFAULTS, meshQuadric, MESH_OCCLUSION_DEFAULTS, meshOcclusion, encodePly, encodeStl };
+                   MESH_SIMPLIFY_DEFAULTS, meshSimplify, MESH_QUADRIC_DEFAULTS, meshQuadric, MESH_OCCLUSION_DEFAULTS, meshOcclusion, MESH_PROJECT_DEFAULTS, meshProject, meshProjectReach, encodePly, encodeStl };

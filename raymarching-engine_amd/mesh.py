@@ -184,6 +184,47 @@ def mesh_occlusion(**fields) -> abi.RmMeshOcclusion:
                                strength=float(p["strength"]), flags=int(flags))
 
 
+def mesh_project(**fields) -> abi.RmMeshProject:
+    """The abi.RmMeshProject of Context.extract_mesh(..., project=...), over abi.MESH_PROJECT_DEFAULTS: iso (the level to project onto), rounds
+    (1..16), relax (the fraction of the Newton step taken, in (0, 1]), tolerance (a vertex within it of the level does not move, >= 0), reach
+    (per axis, how far a vertex may end from where it started, >= 0; 0 = no limit), normal_delta (the step of the normal that gives the
+    direction, > 0) and flags (rm_sdf_grid's).  Checked as the library checks it: ValueError otherwise, and for unknown keys."""
+    unknown = set(fields) - set(abi.MESH_PROJECT_DEFAULTS)
+    if unknown:
+        raise ValueError(f"mesh: unknown project parameter {sorted(unknown)[0]}")
+    p = {**abi.MESH_PROJECT_DEFAULTS, **fields}
+    for name in ("iso", "relax", "tolerance", "reach", "normal_delta"):
+        if isinstance(p[name], bool) or not isinstance(p[name], (int, float, np.integer, np.floating)):
+            raise ValueError(f"mesh: project {name} must be a number")
+    with np.errstate(over="ignore"):
+        iso, relax, tolerance, reach, delta = (np.float32(p[name]) for name in ("iso", "relax", "tolerance", "reach", "normal_delta"))
+    if not math.isfinite(iso):
+        raise ValueError("mesh: project iso must be finite")
+    rounds = p["rounds"]
+    if isinstance(rounds, bool) or not isinstance(rounds, (int, np.integer)) or not 1 <= int(rounds) <= 16:
+        raise ValueError("mesh: project rounds must be an integer in 1..16")
+    if not (math.isfinite(relax) and 0 < relax <= 1):
+        raise ValueError("mesh: project relax must be finite and in (0, 1]")
+    if not (math.isfinite(tolerance) and tolerance >= 0):
+        raise ValueError("mesh: project tolerance must be finite and >= 0")
+    if not (math.isfinite(reach) and reach >= 0):
+        raise ValueError("mesh: project reach must be finite and >= 0")
+    if not (math.isfinite(delta) and delta > 0):
+        raise ValueError("mesh: project normal_delta must be finite and > 0")
+    flags = p["flags"]
+    if isinstance(flags, bool) or not isinstance(flags, (int, np.integer)) or int(flags) & ~(abi.RM_RENDER_FAST | abi.RM_RENDER_NO_CULL):
+        raise ValueError("mesh: project flags must be 0, RM_RENDER_FAST, RM_RENDER_NO_CULL or both")
+    return abi.RmMeshProject(iso=float(p["iso"]), rounds=int(rounds), relax=float(p["relax"]), tolerance=float(p["tolerance"]), reach=float(p["reach"]),
+                             normal_delta=float(p["normal_delta"]), flags=int(flags), reserved=0)
+
+
+def project_reach(grid: Grid) -> float:
+    """The reach extract_mesh(..., project=...) takes when none is given: half the smallest cell side of `grid`, 0.5f * min h[a] with h in
+    fp32 by RmGrid's rule."""
+    f = np.float32
+    return float(f(0.5) * min((f(b) - f(a)) / f(k) for a, b, k in zip(grid.lo, grid.hi, grid.n)))
+
+
 @dataclass
 class Mesh:
     """A triangle mesh as numpy arrays: positions [V, 3] float32, triangles [T, 3] uint32 (counter-clockwise seen from outside), cells
@@ -202,6 +243,8 @@ class Mesh:
     component_sizes: Optional[np.ndarray] = None
     occlusion = None  # Optional[np.ndarray]; an attribute that the constructor takes by keyword (below): the dataclass's own fields stay as they were
     measures = None  # Optional[dict]; taken the same way
+    projection = None  # Optional[dict]: abi.RmMeshProjection's fields (rm_mesh_project), only when the call asked for a projection; taken the same way
+    residual = None  # Optional[np.ndarray]: [V] float32, the distance minus iso at the projected vertices; with `projection`
 
     @property
     def vertices(self) -> int:
@@ -209,10 +252,12 @@ class Mesh:
 
 
 def _with_occlusion(init):
-    def __init__(self, *args, occlusion=None, measures=None, **fields):
+    def __init__(self, *args, occlusion=None, measures=None, projection=None, residual=None, **fields):
         init(self, *args, **fields)
         self.occlusion = occlusion
         self.measures = measures
+        self.projection = projection
+        self.residual = residual
 
     __init__.__doc__, __init__.__wrapped__ = init.__doc__, init
     return __init__

@@ -47,6 +47,7 @@ EXPORTS = [
     "rm_mesh_occlusion_default", "rm_mesh_occlusion_directions", "rm_mesh_occlusion",
     "rm_mesh_measure", "rm_mesh_measure_components",
     "rm_mesh_slabs_default", "rm_mesh_extract_slabs", "rm_mesh_extract_sharp_slabs", "rm_mesh_from_values_slabs",
+    "rm_mesh_project_default", "rm_mesh_project",
 ]
 
 # G-buffer formats of a framebuffer (include/hip_raymarch.h RM_GBUFFER_*): "f32" (the default: the software GL stack's planes, which the
@@ -433,6 +434,8 @@ def load_library(path=None):
         "rm_mesh_extract_sharp_slabs": (ip, [vp, vp, C.POINTER(abi.RmGrid), C.POINTER(abi.RmMeshParams), C.POINTER(abi.RmMeshSharp), C.POINTER(abi.RmMeshSlabs),
                                              C.POINTER(vp)]),
         "rm_mesh_from_values_slabs": (ip, [vp, C.POINTER(abi.RmGrid), fp, C.c_float, C.POINTER(abi.RmMeshSlabs), C.POINTER(vp)]),
+        "rm_mesh_project_default": (None, [C.POINTER(abi.RmMeshProject)]),
+        "rm_mesh_project": (ip, [vp, vp, C.POINTER(abi.RmMeshProject), C.POINTER(vp), C.POINTER(abi.RmMeshProjection), fp]),
     }
     for name, (res, args) in sig.items():
         if name.startswith("rm_debug_") and not hasattr(lib, name) and os.environ.get("RM_LIB"):
@@ -729,14 +732,19 @@ class Context:
         g = grid.to_c()
         self._check(self.lib.rm_sdf_grid_device(self.h, scene.h, C.byref(g), int(flags), C.c_void_p(out_ptr), C.c_void_p(stream) if stream else None))
 
-    def _take_mesh(self, handle, grid, normals=False, colours=False, keep=None, components=False, simplify=None, quadric=None, scene=None, occlusion=None, measures=False):
+    def _take_mesh(self, handle, grid, normals=False, colours=False, keep=None, components=False, simplify=None, quadric=None, scene=None, occlusion=None, measures=False,
+                   project=None):
         """The arrays of a mesh handle as a mesh.Mesh (normals / colours: whether the call that made it asked for them); destroys the handle.
         simplify (_mesh_simplify's triple): the mesh is first clustered on the device (rm_mesh_simplify) and the Mesh's grid is the cluster grid,
         which its cells then index -- with quadric (an abi.RmMeshQuadric) by rm_mesh_simplify_quadric; keep (an abi.RmMeshKeep): that mesh is filtered on the device (rm_mesh_filter), which also removes the vertices
         simplification left without triangles; the last of them is what is downloaded.  components: its labels and component sizes come with it.
         occlusion (an abi.RmMeshOcclusion, with the scene): that last mesh's ambient occlusion comes with it (rm_mesh_occlusion), and the
         timings gain "occlusion", the milliseconds of its probes and taps.  measures: that last mesh is measured before anything is downloaded
-        (rm_mesh_measure, rm_mesh_measure_components): Mesh.measures, and the timings gain "measures", the milliseconds of topology and geometry."""
+        (rm_mesh_measure, rm_mesh_measure_components): Mesh.measures, and the timings gain "measures", the milliseconds of topology and geometry.
+        project (_mesh_project's function of the grid the mesh lies on, with the scene): behind simplify and keep, that mesh's vertices are
+        projected onto the scene's level set (rm_mesh_project) and everything after sees the projected mesh: Mesh.projection, Mesh.residual,
+        and the timings gain "projection", the milliseconds of its rounds and its normals; sampling, meshing and attributes stay those of the
+        mesh that was projected, so nothing is counted twice."""
         from .mesh import Mesh
 
         handles = [handle]
@@ -755,6 +763,17 @@ class Context:
                 self._check(self.lib.rm_mesh_filter(handle, C.byref(keep), C.byref(filtered)))
                 handles.append(filtered)
                 handle = filtered
+            projected = None
+            if project is not None:
+                block, moved, report = project(grid), C.c_void_p(), abi.RmMeshProjection()
+                counts, produced_ms = (C.c_ulonglong * 2)(), (C.c_float * 3)()
+                self._check(self.lib.rm_mesh_counts(handle, counts))
+                self._check(self.lib.rm_mesh_timings(handle, produced_ms))  # (the producing mesh's three slots stay the result's)
+                residual = np.empty(int(counts[0]), np.float32)
+                self._check(self.lib.rm_mesh_project(handle, scene.h, C.byref(block), C.byref(moved), C.byref(report), _fp(residual)))
+                handles.append(moved)
+                handle = moved
+                projected = (abi.mesh_projection_dict(report), residual, produced_ms)
             measured = None
             if measures:
                 block, measure_ms = abi.RmMeshMeasures(), (C.c_float * 2)()
@@ -785,6 +804,10 @@ class Context:
                     self._check(self.lib.rm_mesh_components_download(handle, what, a.ctypes.data_as(C.c_void_p), a.nbytes))
                     arrays[name] = a
             timings = dict(sampling=float(ms[0]), meshing=float(ms[1]), attributes=float(ms[2]))
+            if projected is not None:  # (the handle is the projection's: its meshing slot is the rounds, its attributes slot the normals)
+                arrays["projection"], arrays["residual"], produced_ms = projected
+                timings = dict(sampling=float(produced_ms[0]), meshing=float(produced_ms[1]), attributes=float(produced_ms[2]),
+                               projection=float(ms[1]) + float(ms[2]))
             if occlusion is not None:
                 ao, ms2 = np.empty(v, np.float32), (C.c_float * 2)()
                 self._check(self.lib.rm_mesh_occlusion(handle, scene.h, C.byref(occlusion), _fp(ao), ms2))
@@ -825,6 +848,26 @@ class Context:
     def _mesh_occlusion(occlusion):
         """The `occlusion` of extract_mesh as an abi.RmMeshOcclusion (_mesh_block's rules)."""
         return Context._mesh_block("occlusion", occlusion, abi.RmMeshOcclusion)
+
+    @staticmethod
+    def _mesh_project(project, iso):
+        """The `project` of extract_mesh as a function of the mesh.Grid the projected mesh lies on, which gives the abi.RmMeshProject
+        (_mesh_block's rules); None stays None.  True and a dict take the extraction's iso where they name none, and mesh.project_reach of that
+        grid where they name no reach; a struct is taken as it stands."""
+        from . import mesh
+
+        if project is None:
+            return None
+        if isinstance(project, abi.RmMeshProject):
+            block = Context._mesh_block("project", project, abi.RmMeshProject)
+            return lambda grid: block
+        if project is True:
+            project = {}
+        if not isinstance(project, dict):
+            raise ValueError("mesh: project must be None, True, a dict of mesh_project's arguments or an abi.RmMeshProject")
+        fields = {"iso": iso, **project}
+        mesh.mesh_project(**{"reach": 0.0, **fields})  # (refused before anything runs)
+        return lambda grid: mesh.mesh_project(**{"reach": mesh.project_reach(grid), **fields})
 
     @staticmethod
     def _mesh_quadric(quadric, simplify):
@@ -875,7 +918,7 @@ class Context:
 
     def extract_mesh(self, scene: "SceneHandle", grid, iso: float = 0.0, normals: bool = True, colours: bool = False, flags: int = 0,
                      normal_delta: float = 1e-5, sharp=None, *, keep=None, components: bool = False, simplify=None, quadric=None,
-                     measures: bool = False, slabs=None, occlusion=None):
+                     measures: bool = False, slabs=None, project=None, occlusion=None):
         """The level set `iso` of the scene on `grid` (mesh.Grid) as a mesh.Mesh: rm_mesh_extract -- the distances sampled and meshed
         (surface nets) on the device, with per-vertex normals / diffuse colours from the scene's probes when asked for.  `sharp`: None is
         that call; True (the defaults), a dict of mesh.mesh_sharp's arguments or an abi.RmMeshSharp is rm_mesh_extract_sharp -- the same
@@ -895,11 +938,18 @@ class Context:
         [C, 4] uint64 rows of (edges, boundary, irregular, unbalanced) per component.
         `slabs`: None is that call; True (the defaults), an int (the cell layers per slab), a dict of mesh.mesh_slabs' arguments or an
         abi.RmMeshSlabs is rm_mesh_extract_slabs / rm_mesh_extract_sharp_slabs -- the same mesh, byte for byte, made from one window of z
-        layers at a time, which also takes a grid beyond 2^28 corners (mesh.Grid(..., slabs=True)).  Every other setting composes with it."""
+        layers at a time, which also takes a grid beyond 2^28 corners (mesh.Grid(..., slabs=True)).  Every other setting composes with it.
+        `project`: None is that mesh; True (the defaults), a dict of mesh.mesh_project's arguments or an abi.RmMeshProject moves the vertices of
+        the mesh that is returned onto the scene's level set by Newton steps on the device (rm_mesh_project) -- behind `simplify`, `quadric`
+        and `keep`, before `components`, `occlusion` and `measures`, which then see the projected mesh.  iso, where not given, is the
+        extraction's; reach, where not given, is half the smallest cell side of the grid the returned mesh lies on (the cluster grid with
+        `simplify`, else the sampling grid).  The mesh carries Mesh.projection (a dict of abi.RmMeshProjection's fields), Mesh.residual ([V]
+        float32: the distance minus iso at the new vertices) and timings["projection"], the milliseconds of the rounds and the normals; the
+        other three timings stay those of the mesh that was projected."""
         from .mesh import mesh_params
 
         keep, simplify, quadric = self._mesh_keep(keep), self._mesh_simplify(simplify), self._mesh_quadric(quadric, simplify)  # (refused before anything runs)
-        occlusion = self._mesh_occlusion(occlusion)
+        occlusion, project = self._mesh_occlusion(occlusion), self._mesh_project(project, iso)
         g, p = grid.to_c(), mesh_params(iso=iso, normals=normals, colours=colours, flags=flags, normal_delta=normal_delta)
         h = C.c_void_p()
         s = self._mesh_block("sharp", sharp, abi.RmMeshSharp)
@@ -913,7 +963,7 @@ class Context:
         else:
             self._check(self.lib.rm_mesh_extract_sharp_slabs(self.h, scene.h, C.byref(g), C.byref(p), C.byref(s), C.byref(w), C.byref(h)))
         return self._take_mesh(h, grid, normals=p.normals, colours=p.colours, keep=keep, components=components, simplify=simplify, quadric=quadric,
-                               scene=scene, occlusion=occlusion, measures=measures)
+                               scene=scene, occlusion=occlusion, measures=measures, project=project)
 
     def mesh_from_values(self, grid, values: np.ndarray, iso: float = 0.0, *, keep=None, components: bool = False, simplify=None, quadric=None,
                          measures: bool = False, slabs=None):
