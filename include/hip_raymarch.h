@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define RM_ABI_VERSION 9 /* 9: RM_GBUFFER_F32 / _F16, rm_fb_create_fmt, rm_fb_create_striped_fmt, rm_fb_wrap_fmt, rm_fb_gbuffer, rm_fb_download_raw, rm_fb_upload_raw, RmDenoise, rm_denoise_default, rm_denoise, rm_denoise_device, rm_present_denoised, RM_FB_MOMENTS, RM_PLANE_MOMENTS, rm_fb_has_moments, RmDenoiseVariance, rm_denoise_variance_default, rm_denoise_variance, rm_denoise_variance_device, rm_present_denoised_variance, RmDespeckle, RmFilters, RM_DENOISE_NONE / _ATROUS / _VARIANCE, rm_filters_default, rm_filter, rm_filter_device, rm_present_filtered, RM_STATS_BINS, RmFrameStats, rm_frame_stats, RmAutoExposure, rm_auto_exposure_default, rm_stats_percentile, rm_stats_exposure, RM_TONE_CLIP / _REINHARD / _ACES, RmDisplay, rm_display_default, rm_present_display, rm_present_display_device, rm_present_linear, RmGrid, rm_grid_axis, rm_sdf_grid, rm_sdf_grid_device, RmMeshParams, rm_mesh_params_default, rm_mesh, rm_mesh_extract, rm_mesh_from_values, rm_mesh_counts, rm_mesh_timings, RM_MESH_POSITIONS / _NORMALS / _COLOURS / _TRIANGLES / _CELLS, rm_mesh_download, rm_mesh_device_ptr, rm_mesh_destroy, RmMeshSharp, rm_mesh_sharp_default, rm_mesh_extract_sharp, RmMeshKeep, rm_mesh_keep_default, rm_mesh_components, RM_MESH_PART_LABELS / _SIZES, rm_mesh_components_download, rm_mesh_filter, RmMeshSimplify, rm_mesh_simplify_default, rm_mesh_simplify, RmMeshQuadric, rm_mesh_quadric_default, rm_mesh_simplify_quadric, RmMeshOcclusion, rm_mesh_occlusion_default, rm_mesh_occlusion_directions, rm_mesh_occlusion, RmMeshMeasures, rm_mesh_measure, rm_mesh_measure_components, RmMeshSlabs, rm_mesh_slabs_default, rm_mesh_extract_slabs, rm_mesh_extract_sharp_slabs, rm_mesh_from_values_slabs, RmMeshProject, RmMeshProjection, rm_mesh_project_default, rm_mesh_project (additions only); 8: RM_PRIM_TORUS / _CYLINDER / _PLANE, RM_OP_SMOOTH_SUBTRACT / _INTERSECT, rm_probe_math (additions only); 7: rm_present_sharded_finish / rm_present_sharded take the size of the host buffer (a changed signature), rm_ctx_set_cull_min_pixels, rm_ctx_set_cull_budget, rm_ctx_cull_stats; 6: rm_present_striped_rows, rm_present_sharded_start / _finish, rm_ctx_last_warning, RM_PROBE_CAST_SHADOW, RM_PRIM_KIND (additions only); 3: rm_ctx_set_sample_batch, rm_buffer_*; 4: rm_ctx_set_gl_stack; 5: RmSurface / RmSceneDesc.surfaces (the struct grew), rm_pack_present_rows, rm_present_sharded, rm_ctx_last_pipeline, RM_RENDER_NO_FAR_JUMP, RM_RENDER_NO_CULL (additions only) */
+#define RM_ABI_VERSION 9 /* 9: RM_GBUFFER_F32 / _F16, rm_fb_create_fmt, rm_fb_create_striped_fmt, rm_fb_wrap_fmt, rm_fb_gbuffer, rm_fb_download_raw, rm_fb_upload_raw, RmDenoise, rm_denoise_default, rm_denoise, rm_denoise_device, rm_present_denoised, RM_FB_MOMENTS, RM_PLANE_MOMENTS, rm_fb_has_moments, RmDenoiseVariance, rm_denoise_variance_default, rm_denoise_variance, rm_denoise_variance_device, rm_present_denoised_variance, RmDespeckle, RmFilters, RM_DENOISE_NONE / _ATROUS / _VARIANCE, rm_filters_default, rm_filter, rm_filter_device, rm_present_filtered, RM_STATS_BINS, RmFrameStats, rm_frame_stats, RmAutoExposure, rm_auto_exposure_default, rm_stats_percentile, rm_stats_exposure, RM_TONE_CLIP / _REINHARD / _ACES, RmDisplay, rm_display_default, rm_present_display, rm_present_display_device, rm_present_linear, RmGrid, rm_grid_axis, rm_sdf_grid, rm_sdf_grid_device, RmMeshParams, rm_mesh_params_default, rm_mesh, rm_mesh_extract, rm_mesh_from_values, rm_mesh_counts, rm_mesh_timings, RM_MESH_POSITIONS / _NORMALS / _COLOURS / _TRIANGLES / _CELLS, rm_mesh_download, rm_mesh_device_ptr, rm_mesh_destroy, RmMeshSharp, rm_mesh_sharp_default, rm_mesh_extract_sharp, RmMeshKeep, rm_mesh_keep_default, rm_mesh_components, RM_MESH_PART_LABELS / _SIZES, rm_mesh_components_download, rm_mesh_filter, RmMeshSimplify, rm_mesh_simplify_default, rm_mesh_simplify, RmMeshQuadric, rm_mesh_quadric_default, rm_mesh_simplify_quadric, RmMeshOcclusion, rm_mesh_occlusion_default, rm_mesh_occlusion_directions, rm_mesh_occlusion, RmMeshMeasures, rm_mesh_measure, rm_mesh_measure_components, RmMeshSlabs, rm_mesh_slabs_default, rm_mesh_extract_slabs, rm_mesh_extract_sharp_slabs, rm_mesh_from_values_slabs, RmMeshProject, RmMeshProjection, rm_mesh_project_default, rm_mesh_project, RmMeshDeviation, RmMeshDeviationReport, rm_mesh_deviation_default, rm_mesh_deviation_weights, rm_mesh_deviation (additions only); 8: RM_PRIM_TORUS / _CYLINDER / _PLANE, RM_OP_SMOOTH_SUBTRACT / _INTERSECT, rm_probe_math (additions only); 7: rm_present_sharded_finish / rm_present_sharded take the size of the host buffer (a changed signature), rm_ctx_set_cull_min_pixels, rm_ctx_set_cull_budget, rm_ctx_cull_stats; 6: rm_present_striped_rows, rm_present_sharded_start / _finish, rm_ctx_last_warning, RM_PROBE_CAST_SHADOW, RM_PRIM_KIND (additions only); 3: rm_ctx_set_sample_batch, rm_buffer_*; 4: rm_ctx_set_gl_stack; 5: RmSurface / RmSceneDesc.surfaces (the struct grew), rm_pack_present_rows, rm_present_sharded, rm_ctx_last_pipeline, RM_RENDER_NO_FAR_JUMP, RM_RENDER_NO_CULL (additions only) */
 
 #define RM_MAX_BOUNCES 10 /* raymarchingStepCountsArray[10], raymarcher.frag:31 */
 #define RM_MAX_LIGHTS 10  /* lightPositions[10],             raymarcher.frag:37-39 */
@@ -1302,6 +1302,86 @@ typedef struct RmMeshProjection {  /* 144 bytes */
 } RmMeshProjection;
 RM_API void rm_mesh_project_default(RmMeshProject* params);
 RM_API int rm_mesh_project(rm_mesh* mesh, rm_scene* scene, const RmMeshProject* params, rm_mesh** out, RmMeshProjection* report, float* residual_host);
+
+/* ---- deviation (opt-in): how far a mesh's triangles lie off a level set of a scene ----
+ * Every stage above says of its result that only the vertices come to lie on the surface and that triangles still chord it.  rm_mesh_deviation
+ * says by how much: it evaluates the scene's distance field at S = n * n fixed points inside every triangle and returns, per triangle, the
+ * largest |d - iso| it met, and an area-weighted report.  It works on any rm_mesh (rm_mesh_extract, _sharp, _from_values, rm_mesh_filter,
+ * rm_mesh_simplify, _quadric, the slabbed entries, rm_mesh_project) with any scene of the mesh's context.  It changes nothing of the mesh and
+ * is not one of its arrays: rm_mesh_download serves `what` 0..4 as before.  The measure is ONE-SIDED, mesh to surface, and taken at S samples:
+ * a lower bound of the triangle's true maximum, in the field's own units (a distance ESTIMATE such as the Mandelbulb's is no metric distance),
+ * and it says nothing of parts of the surface that no triangle lies near.
+ * params == NULL: the defaults (iso 0, order 4, tolerance 0, flags 0).  A block is valid iff iso is finite, order is 1, 2, 4 or 8, tolerance is
+ * finite and >= 0, flags are of rm_sdf_grid's set and reserved is 0.
+ * Arithmetic: fp32 unless it says double, every operation rounded on its own (no contraction), IEEE division and square root, whatever the
+ * flags are: they select only the unit that evaluates the scene.  For V vertices, T triangles, n = order, S = n * n:
+ *   1. Sample table (rm_mesh_deviation_weights: host arithmetic in double; the device gets the table from the host).  The samples are the
+ *      centroids of the n * n congruent sub-triangles.  For s = 0 .. S - 1:  r = floor(sqrt(s)), c = s - r * r (row r has 2 r + 1
+ *      sub-triangles).  c even, m = c / 2:  A = 3 (r - m) + 1, B = 3 m + 1.  c odd, m = (c - 1) / 2:  A = 3 (r - m) - 1, B = 3 m + 2.
+ *      w1 = A / (3 n), w2 = B / (3 n), w0 = (3 n - A - B) / (3 n): integers divided in double, each quotient rounded once to float.
+ *      out[4 s .. 4 s + 3] = (w0, w1, w2, 0).  All weights are > 0; the S samples carry equal area, so a plain mean over them is the
+ *      triangle's area mean.
+ *   2. Points.  For triangle t with corners p0, p1, p2 and sample s:  q[c] = ((w0 * p0[c]) + (w1 * p1[c])) + (w2 * p2[c]).
+ *   3. Field.  d = RM_PROBE_SDF's bits at q for these flags on this context;  e = d - iso.
+ *   4. Per triangle.  A triangle is SKIPPED iff one of its indices is >= V (the kernels read nothing but its three indices): +0 in
+ *      triangles_host, and it contributes nowhere.  Otherwise F = the number of samples whose e is finite; max_t = the maximum of |e| over
+ *      those samples (on the bits: any order gives the same), +0 with F = 0; it goes to triangles_host[t].  s1, s2 = the sums of (double)e and
+ *      (double)e * (double)e over the S samples, +0.0 for a non-finite e, summed by the butterfly `for m = 1, 2, 4, .. < S: x[i] = x[i] +
+ *      x[i xor m]` (a balanced tree, neighbours first).  The triangle is EVALUATED iff F == S; then mean_t = s1 / S and ms_t = s2 / S.
+ *      area_t in double: e1 = p1 - p0, e2 = p2 - p0 with the corners converted to double,  n = (e1y e2z - e1z e2y,  e1z e2x - e1x e2z,
+ *      e1x e2y - e1y e2x), each product rounded, then the difference;  area_t = 0.5 * sqrt((nx nx + ny ny) + nz nz)  (the area of "measures
+ *      and edge topology" without its shift of the origin).  The triangle is OVER iff it is evaluated and max_t > tolerance.
+ *   5. Report.  Counts are integer sums; nonfinite_samples runs over the triangles that are not skipped.  area, over_area, A1 = sum of
+ *      area_t * mean_t and A2 = sum of area_t * ms_t are the FIXED-TREE sums of "measures and edge topology" over the T terms in triangle
+ *      order, +0.0 for a triangle that is not evaluated (for over_area: not over).  mean_signed = A1 / area, rms = sqrt(A2 / area), both 0
+ *      when area == 0.  max and worst_triangle come from one 64-bit atomicMax per wave on the key bits(max_t) << 32 | (0xFFFFFFFF - t) over
+ *      the evaluated triangles: the largest max_t, and among equals the smallest triangle; both 0 with no evaluated triangle.
+ * Every output is a function of scene bits, integer sums and maxima, and that fixed tree: the same bytes on every run.
+ * Procedure (rm_mesh_kernels.inc "deviation").  Evaluate, in all three units with launch_sdf_grid's kind selection: one lane per (triangle,
+ * sample) -- S divides 64, so a triangle's lanes are neighbours in one wave -- reads its triangle's indices and corners, makes q, parks it in
+ * LDS ahead of a barrier (so that the point provably precedes the unit's math mode, as in "ambient occlusion"), stages the scene, evaluates
+ * and stores d, 4 bytes per sample.  Lanes beyond T * S repeat the last sample and store nothing; lanes of a skipped triangle evaluate vertex
+ * 0's position.  Reduce, in the strict unit (plain fp32 and double, whatever unit evaluated): one lane per sample makes e, the finite flag and
+ * the two squares' terms, the butterflies run over the triangle's S lanes, and the triangle's first lane computes area_t, writes max_t and the
+ * four double terms and takes part in the wave's counts and atomicMax.  The tree's first level is made in LDS per workgroup of 256 terms,
+ * every further level is one launch (the kernels of "measures and edge topology").  No floating-point atomics, no thread waits for another,
+ * every loop is bounded.  Scratch, freed before the call returns: 4 T S bytes of d, 36 T bytes of max_t and terms, 32 ceil(T / 256) bytes of
+ * group sums and 1/255 of that behind, 16 S bytes of table, 20 KiB of totals (256 copies of the counts and the key, a workgroup's atomics
+ * going to the copy of its number mod 256, so that T S / 64 waves do not queue on one address; the host adds the counts and takes the largest
+ * key, which any order gives alike).
+ * The call is synchronous on the context's stream.  report (may be NULL) receives the struct below; triangles_host (may be NULL) T floats,
+ * max_t; out_ms2 (may be NULL) the milliseconds between events on the stream of {evaluate; reduce and report}.  A mesh with V = 0 or T = 0
+ * succeeds: a report that is zero but for vertices, triangles, samples and, with V = 0, skipped_triangles = T; nothing is written to
+ * triangles_host; out_ms2 = {0, 0}.
+ * RM_ERR_INVALID, in this order (the text through rm_last_error(NULL) when no context is known): an invalid block, one text per field, before
+ * the handles are looked at; a NULL mesh or scene ("NULL argument"); a scene of another context than the mesh's ("the scene belongs to
+ * another context").  rm_mesh_deviation_weights: an order that is not 1, 2, 4 or 8, then a NULL out.  No refusal writes to report,
+ * triangles_host or out_ms2.
+ * RM_ERR_DEVICE: T * S >= 2^31; a failed allocation, with nothing leaked. */
+typedef struct RmMeshDeviation {     /* 32 bytes */
+  float   iso;         /* the level the mesh stands for (a mesh does not remember its own); finite */
+  int32_t order;       /* n: 1, 2, 4 or 8; S = n * n samples per triangle */
+  float   tolerance;   /* a triangle is OVER iff its max |e| > tolerance; finite, >= 0 */
+  int32_t flags;       /* 0, RM_RENDER_FAST, RM_RENDER_NO_CULL or both, as rm_sdf_grid */
+  int32_t reserved[4]; /* must be 0 */
+} RmMeshDeviation;
+typedef struct RmMeshDeviationReport { /* 112 bytes */
+  uint64_t vertices, triangles;        /*  0,  8 */
+  uint64_t skipped_triangles;          /* 16: an index >= V */
+  uint64_t unevaluated_triangles;      /* 24: not skipped, at least one sample's e not finite */
+  uint64_t nonfinite_samples;          /* 32: over the triangles that are not skipped */
+  uint64_t over_triangles;             /* 40 */
+  uint64_t worst_triangle;             /* 48: of max, smallest index among ties; 0 with none */
+  double   area, over_area;            /* 56, 64: of the evaluated / the over triangles */
+  double   mean_signed, rms;           /* 72, 80: area-weighted over the evaluated triangles; 0 when area == 0 */
+  float    max;                        /* 88 */
+  int32_t  samples;                    /* 92: S */
+  int32_t  reserved[4];                /* 96: written as 0 */
+} RmMeshDeviationReport;
+RM_API void rm_mesh_deviation_default(RmMeshDeviation* params);
+RM_API int rm_mesh_deviation_weights(int order, float* out); /* S x 4 floats; host arithmetic, no GPU, no context */
+RM_API int rm_mesh_deviation(rm_mesh* mesh, rm_scene* scene, const RmMeshDeviation* params, RmMeshDeviationReport* report, float* triangles_host,
+                             float* out_ms2);
 
 #ifdef __cplusplus
 }

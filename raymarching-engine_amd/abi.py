@@ -431,6 +431,51 @@ def mesh_projection_dict(r: "RmMeshProjection") -> dict:
     return {name: getattr(r, name) for name, _ in RmMeshProjection._fields_ if name != "reserved"}
 
 
+class RmMeshDeviation(C.Structure):
+    """Parameters of rm_mesh_deviation (ABI 9): the scene's distance minus `iso` at order * order fixed points inside every triangle
+    (include/hip_raymarch.h "deviation")."""
+    _fields_ = [
+        ("iso", C.c_float),
+        ("order", C.c_int32),
+        ("tolerance", C.c_float),
+        ("flags", C.c_int32),
+        ("reserved", C.c_int32 * 4),
+    ]
+
+
+MESH_DEVIATION_DEFAULTS = dict(iso=0.0, order=4, tolerance=0.0, flags=0)  # rm_mesh_deviation_default
+
+assert C.sizeof(RmMeshDeviation) == 32
+
+
+class RmMeshDeviationReport(C.Structure):
+    """What rm_mesh_deviation says of a mesh (ABI 9): how far its triangles lie off the level set at their samples, area-weighted."""
+    _fields_ = [
+        ("vertices", C.c_uint64),
+        ("triangles", C.c_uint64),
+        ("skipped_triangles", C.c_uint64),
+        ("unevaluated_triangles", C.c_uint64),
+        ("nonfinite_samples", C.c_uint64),
+        ("over_triangles", C.c_uint64),
+        ("worst_triangle", C.c_uint64),
+        ("area", C.c_double),
+        ("over_area", C.c_double),
+        ("mean_signed", C.c_double),
+        ("rms", C.c_double),
+        ("max", C.c_float),
+        ("samples", C.c_int32),
+        ("reserved", C.c_int32 * 4),
+    ]
+
+
+assert C.sizeof(RmMeshDeviationReport) == 112
+
+
+def mesh_deviation_dict(r: "RmMeshDeviationReport") -> dict:
+    """The struct's fields as a dict, `reserved` left out."""
+    return {name: getattr(r, name) for name, _ in RmMeshDeviationReport._fields_ if name != "reserved"}
+
+
 def mesh_measures_dict(m: "RmMeshMeasures") -> dict:
     """The struct's fields as a dict: lo and hi as tuples, `closed` as bool, `reserved` left out."""
     d = {name: getattr(m, name) for name, _ in RmMeshMeasures._fields_ if name != "reserved"}

@@ -37,6 +37,7 @@ hipError_t rm_gl_launch_probe(const void* probe_params, hipStream_t stream);
 hipError_t rm_gl_launch_sdf_grid(const void* grid_params, hipStream_t stream);
 hipError_t rm_gl_launch_mesh_occlusion(const void* occlusion_params, hipStream_t stream);
 hipError_t rm_gl_launch_mesh_project_eval(const void* eval_params, hipStream_t stream);
+hipError_t rm_gl_launch_mesh_deviation_eval(const void* eval_params, hipStream_t stream);
 hipError_t rm_gl_launch_math_probe(int fn, const float* a, const float* b, int n, float* out, hipStream_t stream);
 hipError_t rm_gl_launch_camera_rng(const RmUniforms* u, int W, int H, int what, int count, float* out, hipStream_t stream);
 hipError_t rm_gl_launch_present(const float4* color, const void* normal_dof, bool nd_half, int W, int H, float brightness, uchar4* out, hipStream_t stream);
@@ -209,7 +210,7 @@ struct DeviceArray {
 // that runs the stage.
 struct MeshSpans {
   enum { SAMPLE, COUNT_SCAN, EMIT, SHARPEN, ATTRIBUTES, LABEL, KEEP_FLAGS, GATHER, CLUSTER_NUMBER, CLUSTER_MERGE, CLUSTER_GATHER, OCCLUSION_PROBES, OCCLUSION_TAPS,
-         MEASURE_TOPOLOGY, MEASURE_GEOMETRY, PROJECT_ROUNDS, PROJECT_NORMALS, COUNT };
+         MEASURE_TOPOLOGY, MEASURE_GEOMETRY, PROJECT_ROUNDS, PROJECT_NORMALS, DEVIATION_EVALUATE, DEVIATION_REDUCE, COUNT };
   hipEvent_t ev[COUNT][2] = {};
   hipError_t begin(int span, hipStream_t stream) { return record(ev[span][0], stream); }
   hipError_t end(int span, hipStream_t stream) { return record(ev[span][1], stream); }

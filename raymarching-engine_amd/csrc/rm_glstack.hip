@@ -24,6 +24,9 @@ hipError_t rm_gl_launch_mesh_occlusion(const void* occlusion_params, hipStream_t
 hipError_t rm_gl_launch_mesh_project_eval(const void* eval_params, hipStream_t stream) {
   return rm_gl::launch_mesh_project_eval_strict(*static_cast<const MeshProjectEval*>(eval_params), stream);
 }
+hipError_t rm_gl_launch_mesh_deviation_eval(const void* eval_params, hipStream_t stream) {
+  return rm_gl::launch_mesh_deviation_eval_strict(*static_cast<const MeshDeviationSdf*>(eval_params), stream);
+}
 hipError_t rm_gl_launch_camera_rng(const RmUniforms* u, int W, int H, int what, int count, float* out, hipStream_t stream) {
   return rm_gl::launch_camera_rng(*u, W, H, what, count, out, stream);
 }

@@ -1329,3 +1329,190 @@ int rm_mesh_project(rm_mesh* mesh, rm_scene* scene, const RmMeshProject* params,
   *out = made.release();
   return RM_OK;
 }
+
+// ---- deviation (include/hip_raymarch.h "deviation") ------------------------------------------------------------------------------------------------
+
+void rm_mesh_deviation_default(RmMeshDeviation* params) {
+  if (!params) return;
+  *params = RmMeshDeviation{0.0f, 4, 0.0f, 0, {0, 0, 0, 0}};
+}
+
+// log2 of the samples per triangle, S = order * order, for an order of 1, 2, 4 or 8; -1 for anything else
+static int deviation_log2_samples(int order) {
+  for (int l = 0; l <= 3; l++)
+    if (order == (1 << l)) return 2 * l;
+  return -1;
+}
+
+// the table in double, every weight rounded once (the header's "sample table")
+static void deviation_weights(int n, float* out) {
+  const double denominator = (double)(3 * n);
+  for (int s = 0, r = 0; s < n * n; s++) {
+    if ((r + 1) * (r + 1) <= s) r++;  // r = floor(sqrt(s))
+    const int c = s - r * r, m = c / 2;
+    const int A = (c & 1) ? 3 * (r - m) - 1 : 3 * (r - m) + 1;
+    const int B = (c & 1) ? 3 * m + 2 : 3 * m + 1;
+    out[4 * s] = (float)((double)(3 * n - A - B) / denominator);
+    out[4 * s + 1] = (float)((double)A / denominator);
+    out[4 * s + 2] = (float)((double)B / denominator);
+    out[4 * s + 3] = 0.0f;
+  }
+}
+
+int rm_mesh_deviation_weights(int order, float* out) {
+  const Refuse refuse{nullptr, "rm_mesh_deviation_weights"};
+  if (deviation_log2_samples(order) < 0) return refuse("order must be 1, 2, 4 or 8");
+  if (!out) return refuse("NULL argument");
+  deviation_weights(order, out);
+  return RM_OK;
+}
+
+static int mesh_deviation_check(const Refuse& refuse, const RmMeshDeviation* in, RmMeshDeviation* p) {
+  rm_mesh_deviation_default(p);
+  if (in) *p = *in;
+  if (!std::isfinite(p->iso)) return refuse("deviation iso must be finite");
+  if (deviation_log2_samples(p->order) < 0) return refuse("deviation order must be 1, 2, 4 or 8");
+  if (!(std::isfinite(p->tolerance) && p->tolerance >= 0.0f)) return refuse("deviation tolerance must be finite and >= 0");
+  if (int rc = sdf_flags_check(refuse, p->flags)) return rc;
+  for (int r : p->reserved)
+    if (r != 0) return refuse("deviation reserved must be 0");
+  return RM_OK;
+}
+
+int rm_mesh_deviation(rm_mesh* mesh, rm_scene* scene, const RmMeshDeviation* params, RmMeshDeviationReport* report, float* triangles_host, float* out_ms2) {
+  rm_ctx* ctx = mesh ? mesh->ctx : nullptr;
+  const Refuse refuse{ctx, "rm_mesh_deviation"};
+  RmMeshDeviation p;
+  if (int rc = mesh_deviation_check(refuse, params, &p)) return rc;
+  if (int rc = scene_check(refuse, scene, true)) return rc;  // (a NULL mesh is a NULL context there)
+  const unsigned long long V = mesh->vertices, T = mesh->triangles;
+  const int log2_s = deviation_log2_samples(p.order), S = 1 << log2_s;
+  RmMeshDeviationReport r{};
+  r.vertices = V;
+  r.triangles = T;
+  r.samples = S;
+  if (V == 0 || T == 0) {
+    if (V == 0) r.skipped_triangles = T;  // (no index is < 0 vertices)
+    if (report) *report = r;
+    if (out_ms2) out_ms2[0] = out_ms2[1] = 0.0f;
+    return RM_OK;
+  }
+  if (T >= (1ull << (31 - log2_s)))
+    return refuse("the mesh has more triangles than the kernels' index holds samples of (T * S >= 2^31)", RM_ERR_DEVICE);
+  float table[64 * 4];
+  deviation_weights(p.order, table);
+  // the levels of the two pairs' trees behind the terms: groups[k] values of each list; the level of one value is the totals' own words
+  std::vector<long long> groups;
+  size_t level_elems = 0;
+  for (long long g = ((long long)T + 255) / 256;; g = (g + 255) / 256) {
+    groups.push_back(g);
+    if (g == 1) break;
+    level_elems += (size_t)g;
+  }
+  std::vector<float> max_host;
+  if (triangles_host) {  // (through a buffer of the call's own: a refusal below writes nothing of the caller's)
+    try {
+      max_host.resize((size_t)T);
+    } catch (const std::bad_alloc&) {
+      return refuse("out of host memory", RM_ERR_DEVICE);
+    }
+  }
+  RM_HIP(ctx, hipSetDevice(ctx->device));
+  DeviceArray d, weights, triangle_max, terms, levels, totals;  // (freed behind the wait of the copy below; a call that fails before it leaves that wait to hipFree)
+  RM_HIP_AS(refuse, d.reserve(sizeof(float) * ((size_t)T << log2_s)));
+  RM_HIP_AS(refuse, weights.reserve(sizeof(float) * 4u * (size_t)S));
+  RM_HIP_AS(refuse, triangle_max.reserve(sizeof(float) * (size_t)T));
+  RM_HIP_AS(refuse, terms.reserve(sizeof(double) * 4u * (size_t)T));
+  RM_HIP_AS(refuse, levels.reserve(sizeof(double) * 4u * level_elems));
+  constexpr size_t kTotalsWords = (size_t)rm::RM_DEVIATION_COPIES * rm::RM_DEVIATION_WORDS;
+  RM_HIP_AS(refuse, totals.reserve(sizeof(unsigned long long) * kTotalsWords));
+  if (int rc = scene_cull_grid(ctx, scene, p.flags, 1ll << 40)) return rc;  // (with the grid, as rm_probe obtains it)
+  MeshDeviationSdf E{};
+  E.scene = scene->dev;
+  if (p.flags & RM_RENDER_NO_CULL) E.scene.cull.cells = nullptr;
+  E.positions = mesh->array[RM_MESH_POSITIONS].f32();
+  E.corners = mesh->array[RM_MESH_TRIANGLES].u32();
+  E.weights = static_cast<const float4*>(weights.p);
+  E.d = d.f32();
+  E.vertices = (long long)V;
+  E.triangles = (int)T;
+  E.log2_samples = log2_s;
+  rm::MeshDeviation D{};
+  D.vertices = (long long)V;
+  D.triangles = (int)T;
+  D.log2_samples = log2_s;
+  D.positions = E.positions;
+  D.corners = E.corners;
+  D.d = d.f32();
+  D.triangle_max = triangle_max.f32();
+  D.terms = static_cast<double*>(terms.p);
+  D.totals = totals.u64();
+  D.iso = p.iso;
+  D.tolerance = p.tolerance;
+  // one pair of lists through every level of the fixed tree, into two neighbouring words of the totals
+  const auto tree = [&](const double* list, double* level, int word) -> int {
+    double* const out = reinterpret_cast<double*>(D.totals + word);
+    const double *from0 = list, *from1 = list + (size_t)T;
+    long long n = (long long)T;
+    for (size_t k = 0; k < groups.size(); k++) {
+      const bool last = groups[k] == 1;
+      double* to0 = last ? out : level;
+      double* to1 = last ? out + 1 : level + groups[k];
+      RM_HIP_AS(refuse, rm::launch_mesh_measure_sum(from0, from1, n, to0, to1, ctx->stream));
+      from0 = to0;
+      from1 = to1;
+      n = groups[k];
+      level += 2 * groups[k];
+    }
+    return RM_OK;
+  };
+  MeshSpans& spans = ctx->mesh_spans;
+  RM_HIP_AS(refuse, hipMemcpyAsync(weights.p, table, sizeof(float) * 4u * (size_t)S, hipMemcpyHostToDevice, ctx->stream));
+  RM_HIP_AS(refuse, hipMemsetAsync(totals.p, 0, sizeof(unsigned long long) * kTotalsWords, ctx->stream));
+  RM_HIP_AS(refuse, spans.begin(MeshSpans::DEVIATION_EVALUATE, ctx->stream));
+  RM_HIP_AS(refuse, (p.flags & RM_RENDER_FAST) ? rm::launch_mesh_deviation_eval_fast(E, ctx->stream)
+                    : ctx->gl_stack           ? rm_gl_launch_mesh_deviation_eval(&E, ctx->stream)
+                                              : rm::launch_mesh_deviation_eval_strict(E, ctx->stream));
+  RM_HIP_AS(refuse, spans.end(MeshSpans::DEVIATION_EVALUATE, ctx->stream));
+  RM_HIP_AS(refuse, spans.begin(MeshSpans::DEVIATION_REDUCE, ctx->stream));
+  RM_HIP_AS(refuse, rm::launch_mesh_deviation_reduce(D, ctx->stream));
+  if (int rc = tree(D.terms, static_cast<double*>(levels.p), rm::RM_DEVIATION_AREA)) return rc;
+  if (int rc = tree(D.terms + 2 * (size_t)T, static_cast<double*>(levels.p) + 2 * level_elems, rm::RM_DEVIATION_SUM1)) return rc;
+  RM_HIP_AS(refuse, spans.end(MeshSpans::DEVIATION_REDUCE, ctx->stream));
+  if (triangles_host) RM_HIP_AS(refuse, hipMemcpyAsync(max_host.data(), triangle_max.p, sizeof(float) * (size_t)T, hipMemcpyDeviceToHost, ctx->stream));
+  static_assert(kTotalsWords * sizeof(unsigned long long) <= 32768, "the copies are read into the stack");
+  unsigned long long copies[kTotalsWords] = {};
+  if (int rc = copy_and_wait(ctx, copies, totals.p, sizeof copies, hipMemcpyDeviceToHost)) return rc;
+  unsigned long long got[rm::RM_DEVIATION_WORDS] = {};  // the copies' counts added, the largest of their keys, copy 0's four sums
+  for (int k = rm::RM_DEVIATION_AREA; k < rm::RM_DEVIATION_WORDS; k++) got[k] = copies[k];
+  for (int copy = 0; copy < rm::RM_DEVIATION_COPIES; copy++) {
+    const unsigned long long* row = copies + (size_t)copy * rm::RM_DEVIATION_WORDS;
+    for (int k = rm::RM_DEVIATION_SKIPPED; k <= rm::RM_DEVIATION_OVER; k++) got[k] += row[k];
+    if (row[rm::RM_DEVIATION_KEY] > got[rm::RM_DEVIATION_KEY]) got[rm::RM_DEVIATION_KEY] = row[rm::RM_DEVIATION_KEY];
+  }
+  r.skipped_triangles = got[rm::RM_DEVIATION_SKIPPED];
+  r.unevaluated_triangles = got[rm::RM_DEVIATION_UNEVALUATED];
+  r.nonfinite_samples = got[rm::RM_DEVIATION_NONFINITE];
+  r.over_triangles = got[rm::RM_DEVIATION_OVER];
+  if (const unsigned long long key = got[rm::RM_DEVIATION_KEY]) {  // (0: no evaluated triangle, max and worst stay 0)
+    const unsigned int bits = (unsigned int)(key >> 32);
+    std::memcpy(&r.max, &bits, sizeof bits);
+    r.worst_triangle = 0xFFFFFFFFull - (key & 0xFFFFFFFFull);
+  }
+  double sum1, sum2;
+  std::memcpy(&r.area, got + rm::RM_DEVIATION_AREA, sizeof r.area);
+  std::memcpy(&r.over_area, got + rm::RM_DEVIATION_OVER_AREA, sizeof r.over_area);
+  std::memcpy(&sum1, got + rm::RM_DEVIATION_SUM1, sizeof sum1);
+  std::memcpy(&sum2, got + rm::RM_DEVIATION_SUM2, sizeof sum2);
+  if (r.area != 0.0) {
+    r.mean_signed = sum1 / r.area;
+    r.rms = std::sqrt(sum2 / r.area);
+  }
+  if (report) *report = r;
+  if (triangles_host) std::memcpy(triangles_host, max_host.data(), sizeof(float) * (size_t)T);
+  if (out_ms2) {
+    out_ms2[0] = spans.ms(MeshSpans::DEVIATION_EVALUATE);
+    out_ms2[1] = spans.ms(MeshSpans::DEVIATION_REDUCE);
+  }
+  return RM_OK;
+}

@@ -2,7 +2,7 @@
 // and -- in the strict unit only, they have no arithmetic of a policy's own -- the surface-nets mesher over such a grid, the two
 // kernels that move its vertices to their cells' QEF minimisers (rm_mesh_extract_sharp), and the integer kernels that label a mesh's
 // connected components and compact the kept ones (rm_mesh_components, rm_mesh_filter), and the vertex clustering of rm_mesh_simplify with the quadric placement of
-// rm_mesh_simplify_quadric, and the edge table, classes, extent and fixed-tree sums of rm_mesh_measure, and the step and report of rm_mesh_project, whose evaluating kernel is in every unit.  Included by
+// rm_mesh_simplify_quadric, and the edge table, classes, extent and fixed-tree sums of rm_mesh_measure, and the step and report of rm_mesh_project, whose evaluating kernel is in every unit, and likewise the reducer of rm_mesh_deviation behind its evaluating kernel.  Included by
 // rm_strict.hip / rm_fast.hip / rm_glstack.hip behind rm_kernels.inc.
 namespace rm {
 
@@ -228,6 +228,67 @@ hipError_t RM_LAUNCH(launch_mesh_project_eval)(const MeshProjectEval& P, hipStre
     default: return hipErrorInvalidValue;
   }
 #undef RM_PROJECT_CASE
+  return hipGetLastError();
+}
+#endif
+
+// ---- deviation: the scene's distance at fixed points inside every triangle (the header's "deviation") -----------------------------------------
+// One lane per (triangle, sample): a triangle's S lanes are consecutive, and S divides 64, so they sit in one wave.  A lane reads its
+// triangle's indices and corners and makes its point BEFORE enter_math_mode; the point waits in LDS, [component][thread], ahead of a barrier,
+// and the switch lies behind it -- the ordering rm_mesh_occlusion_kernel documents: the compiler orders no floating-point operation against a
+// write of the mode register, and the fast Mandelbulb flushes denormals.  Lanes beyond T * S repeat the last sample and store nothing: the
+// evaluators ballot and branch wave-uniformly.  A lane of a skipped triangle (an index >= V) reads nothing out of range: it evaluates vertex
+// 0's position, and the reducer ignores what it stores.
+template <int KIND, bool FAST>
+__global__ __launch_bounds__(256) void rm_mesh_deviation_eval_kernel(const MeshDeviationSdf P) {
+  using MM = typename std::conditional<FAST, FM, PM>::type;
+  __shared__ SceneLds lds;
+  __shared__ float point[3][256];  // a lane's point: only that lane reads it back
+  const unsigned int lanes = (unsigned int)P.triangles << P.log2_samples;  // < 2^31 (rm_mesh_deviation)
+  const unsigned int gi = blockIdx.x * blockDim.x + threadIdx.x;
+  const unsigned int i = gi < lanes ? gi : lanes - 1u;
+  const unsigned int t = i >> P.log2_samples, s = i & ((1u << P.log2_samples) - 1u);
+  unsigned int i0 = P.corners[3 * (size_t)t], i1 = P.corners[3 * (size_t)t + 1], i2 = P.corners[3 * (size_t)t + 2];
+  if (!((long long)i0 < P.vertices && (long long)i1 < P.vertices && (long long)i2 < P.vertices)) i0 = i1 = i2 = 0u;
+  const float* const p0 = P.positions + 3 * (size_t)i0;
+  const float* const p1 = P.positions + 3 * (size_t)i1;
+  const float* const p2 = P.positions + 3 * (size_t)i2;
+  const float4 w = P.weights[s];  // (w0, w1, w2, 0)
+#pragma unroll
+  for (int c = 0; c < 3; c++) point[c][threadIdx.x] = ((w.x * p0[c]) + (w.y * p1[c])) + (w.z * p2[c]);
+  __syncthreads();
+  enter_math_mode<KIND, FAST>();
+  Sdf<KIND>::stage(P.scene, lds);
+  __syncthreads();
+  const float d = Sdf<KIND>::template eval<MM>(P.scene, lds, V(point[0][threadIdx.x], point[1][threadIdx.x], point[2][threadIdx.x]));
+  if (gi < lanes) P.d[gi] = d;
+}
+
+#ifndef RM_ONLY_KERNELS
+// the kind selection is launch_sdf_grid's, row for row: a sample's distance has to be the probe's at that point
+hipError_t RM_LAUNCH(launch_mesh_deviation_eval)(const MeshDeviationSdf& P, hipStream_t stream) {
+  const long long lanes = (long long)P.triangles << P.log2_samples;
+  const dim3 grid((unsigned int)((lanes + 255) / 256));
+#define RM_DEVIATION_CASE(K) case K: hipLaunchKernelGGL((rm_mesh_deviation_eval_kernel<K, kFast>), grid, dim3(256), 0, stream, P); break;
+  if (P.scene.kind == RM_SCENE_TABLE && (P.scene.table_flags & RM_TABLE_HAS_KIND)) {
+    hipLaunchKernelGGL((rm_mesh_deviation_eval_kernel<RM_KIND_TABLE_KINDS, kFast>), grid, dim3(256), 0, stream, P);
+    return hipGetLastError();
+  }
+  if (P.scene.kind == RM_SCENE_TABLE && P.scene.nprims >= RM_TABLE_BIG_ROWS) {
+    hipLaunchKernelGGL((rm_mesh_deviation_eval_kernel<RM_KIND_TABLE_BIG, kFast>), grid, dim3(256), 0, stream, P);
+    return hipGetLastError();
+  }
+  switch (P.scene.kind) {
+    RM_DEVIATION_CASE(RM_SCENE_TABLE)
+    RM_DEVIATION_CASE(RM_SCENE_MANDELBULB)
+    RM_DEVIATION_CASE(RM_SCENE_SPHERE_GRID)
+    RM_DEVIATION_CASE(RM_SCENE_SPHERE_LATTICE)
+    RM_DEVIATION_CASE(RM_SCENE_MENGER)
+    RM_DEVIATION_CASE(RM_SCENE_KIFS_TREE)
+    RM_DEVIATION_CASE(RM_SCENE_KIFS_BOX)
+    default: return hipErrorInvalidValue;
+  }
+#undef RM_DEVIATION_CASE
   return hipGetLastError();
 }
 #endif
@@ -1410,6 +1471,87 @@ __global__ __launch_bounds__(256) void rm_mesh_project_flips_kernel(const MeshPr
   mesh_measure_count(S.totals + RM_PROJECT_FLIPPED, flipped);
 }
 
+// ---- deviation: per triangle and the report's terms (include/hip_raymarch.h "deviation") -------------------------------------------------------
+// The scene is evaluated by rm_mesh_deviation_eval_kernel ahead of this launch; this kernel only consumes d, in this unit's plain fp32 and
+// double, so that no unit's denormal mode touches e, |e| or the squares.  One lane per sample, the eval kernel's lanes; every lane stays to the
+// end: the butterflies over a triangle's S lanes and the wave's ballots read all of them.  The triangle's first lane computes the area, writes
+// max_t and the four terms (the fixed tree is rm_mesh_measure_sum_kernel's, launched by the host) and holds the key of the wave's maximum.
+__global__ __launch_bounds__(256) void rm_mesh_deviation_reduce_kernel(const MeshDeviation D) {
+  const unsigned int lanes = (unsigned int)D.triangles << D.log2_samples;  // < 2^31
+  const unsigned int S = 1u << D.log2_samples;
+  const unsigned int gi = blockIdx.x * blockDim.x + threadIdx.x;
+  const bool valid = gi < lanes;
+  const unsigned int t = valid ? gi >> D.log2_samples : 0u;
+  const bool first = valid && (gi & (S - 1u)) == 0u;
+  unsigned int i0 = 0u, i1 = 0u, i2 = 0u;
+  bool live = false;
+  if (valid) {
+    i0 = D.corners[3 * (size_t)t];
+    i1 = D.corners[3 * (size_t)t + 1];
+    i2 = D.corners[3 * (size_t)t + 2];
+    live = (long long)i0 < D.vertices && (long long)i1 < D.vertices && (long long)i2 < D.vertices;
+  }
+  float e = 0.0f;
+  bool finite = false;
+  if (live) {
+    e = D.d[gi] - D.iso;
+    finite = isfinite(e);
+  }
+  unsigned int largest = finite ? __float_as_uint(fabsf(e)) : 0u;  // (the bits of non-negative floats order as the floats do)
+  double s1 = finite ? (double)e : 0.0, s2 = finite ? (double)e * (double)e : 0.0;
+  unsigned int F = finite ? 1u : 0u;
+#pragma unroll
+  for (unsigned int m = 1u; m < 64u; m <<= 1) {
+    if (m < S) {  // (the same for every lane)
+      const unsigned int other = (unsigned int)__shfl_xor((int)largest, (int)m);
+      if (other > largest) largest = other;
+      s1 = s1 + __shfl_xor(s1, (int)m);
+      s2 = s2 + __shfl_xor(s2, (int)m);
+      F += (unsigned int)__shfl_xor((int)F, (int)m);
+    }
+  }
+  const bool evaluated = first && live && F == S;
+  bool over = false;
+  unsigned long long key = 0ull;
+  if (first) {
+    double area_t = 0.0;
+    const float max_t = live ? __uint_as_float(largest) : 0.0f;
+    if (evaluated) {
+      const float* p0 = D.positions + 3 * (size_t)i0;
+      const float* p1 = D.positions + 3 * (size_t)i1;
+      const float* p2 = D.positions + 3 * (size_t)i2;
+      const double ax = (double)p0[0], ay = (double)p0[1], az = (double)p0[2];
+      const double e1x = (double)p1[0] - ax, e1y = (double)p1[1] - ay, e1z = (double)p1[2] - az;
+      const double e2x = (double)p2[0] - ax, e2y = (double)p2[1] - ay, e2z = (double)p2[2] - az;
+      const double nx = e1y * e2z - e1z * e2y, ny = e1z * e2x - e1x * e2z, nz = e1x * e2y - e1y * e2x;
+      area_t = 0.5 * sqrt((nx * nx + ny * ny) + nz * nz);
+      over = max_t > D.tolerance;
+      key = (unsigned long long)largest << 32 | (0xFFFFFFFFull - (unsigned long long)t);
+    }
+    const double mean_t = s1 / (double)S, ms_t = s2 / (double)S;
+    const size_t T = (size_t)D.triangles;
+    D.triangle_max[t] = max_t;
+    D.terms[t] = evaluated ? area_t : 0.0;
+    D.terms[T + t] = over ? area_t : 0.0;
+    D.terms[2 * T + t] = evaluated ? area_t * mean_t : 0.0;
+    D.terms[3 * T + t] = evaluated ? area_t * ms_t : 0.0;
+  }
+  // a wave's atomics go to one of RM_DEVIATION_COPIES copies of the words, chosen by the workgroup: T S / 64 waves on one address would
+  // queue behind each other for longer than the evaluation takes.  The host adds the copies' counts and takes the largest key: any order
+  // gives the same.
+  unsigned long long* const totals = D.totals + (size_t)(blockIdx.x % RM_DEVIATION_COPIES) * RM_DEVIATION_WORDS;
+  mesh_measure_count(totals + RM_DEVIATION_SKIPPED, first && !live);
+  mesh_measure_count(totals + RM_DEVIATION_UNEVALUATED, first && live && !evaluated);
+  mesh_measure_count(totals + RM_DEVIATION_NONFINITE, live && !finite);
+  mesh_measure_count(totals + RM_DEVIATION_OVER, over);
+#pragma unroll
+  for (int m = 1; m < 64; m <<= 1) {
+    const unsigned long long other = __shfl_xor(key, m);
+    if (other > key) key = other;
+  }
+  if ((threadIdx.x & 63u) == 0u && key != 0ull) atomicMax(totals + RM_DEVIATION_KEY, key);
+}
+
 #ifndef RM_ONLY_KERNELS
 static inline long long mesh_cells(const GridDims& g) { return (long long)(g.nc[0] - 1) * (g.nc[1] - 1) * (g.nc[2] - 1); }
 
@@ -1526,6 +1668,10 @@ hipError_t launch_mesh_project_step(const MeshProject& S, int round, double* sum
   RM_MESH_PARTS_LAUNCH(rm_mesh_project_step_kernel, S.vertices, S, round, sum, sum2);
 }
 hipError_t launch_mesh_project_flips(const MeshProject& S, hipStream_t stream) { RM_MESH_PARTS_LAUNCH(rm_mesh_project_flips_kernel, S.triangles, S); }
+// deviation: one thread per (triangle, sample)
+hipError_t launch_mesh_deviation_reduce(const MeshDeviation& D, hipStream_t stream) {
+  RM_MESH_PARTS_LAUNCH(rm_mesh_deviation_reduce_kernel, (long long)D.triangles << D.log2_samples, D);
+}
 #undef RM_MESH_PARTS_LAUNCH
 
 hipError_t launch_mesh_emit(const MeshParams& P, hipStream_t stream) {

@@ -337,6 +337,18 @@ struct MeshProjectEval {
   int vertices;
   float iso, tolerance, normal_delta;
 };
+// rm_mesh_deviation's evaluating launch: one lane per (triangle, sample), Sdf<KIND>::eval at the sample's point with the probe's scene block.
+// weights is the host's table (rm_mesh_deviation_weights).
+struct MeshDeviationSdf {
+  DevScene scene;
+  const float* positions;       // V x 3
+  const unsigned int* corners;  // T x 3
+  const float4* weights;        // S x (w0, w1, w2, 0)
+  float* d;                     // T x S
+  long long vertices;           // V >= 1
+  int triangles;                // T >= 1, T << log2_samples < 2^31
+  int log2_samples;             // S = 1 << log2_samples <= 64
+};
 // The surface-nets mesher over a grid of values.  counts: per cell (vertex flag) | (quads << 32), scanned in place into the cell's
 // first vertex | first quad; the emit pass reads a neighbour's vertex index from there (every cell round a crossing edge is active).
 struct MeshParams {
@@ -642,6 +654,33 @@ hipError_t launch_mesh_project_eval_strict(const MeshProjectEval& P, hipStream_t
 hipError_t launch_mesh_project_eval_fast(const MeshProjectEval& P, hipStream_t stream);
 hipError_t launch_mesh_project_step(const MeshProject& S, int round, double* sum, double* sum2, hipStream_t stream);
 hipError_t launch_mesh_project_flips(const MeshProject& S, hipStream_t stream);
+// Deviation (rm_mesh_deviation).  deviation_eval, in each unit's arithmetic: d at every (triangle, sample).  deviation_reduce (strict unit:
+// plain fp32 and double): one lane per sample; per triangle max_t into triangle_max[t] and the four terms into terms[k * T + t] (k = area,
+// over_area, area * mean, area * ms), the counts and the key of the maximum into totals.  launch_mesh_measure_sum makes every level of the
+// two pairs' trees.  totals: RM_DEVIATION_COPIES x RM_DEVIATION_WORDS 64-bit words, zeroed by the host before the launch: workgroup b adds its
+// counts and its key to copy b % RM_DEVIATION_COPIES, the host combines the copies; the trees' four sums are in copy 0.
+enum {
+  RM_DEVIATION_SKIPPED, RM_DEVIATION_UNEVALUATED, RM_DEVIATION_NONFINITE, RM_DEVIATION_OVER,
+  RM_DEVIATION_KEY,  // bits(max_t) << 32 | (0xFFFFFFFF - t), maximised over the evaluated triangles; 0: none
+  RM_DEVIATION_AREA, RM_DEVIATION_OVER_AREA, RM_DEVIATION_SUM1, RM_DEVIATION_SUM2,  // doubles
+  RM_DEVIATION_WORDS = 10,
+  RM_DEVIATION_COPIES = 256
+};
+struct MeshDeviation {
+  long long vertices;
+  int triangles;                // T << log2_samples < 2^31
+  int log2_samples;
+  const float* positions;       // V x 3
+  const unsigned int* corners;  // T x 3
+  const float* d;               // T x S
+  float* triangle_max;          // T
+  double* terms;                // 4 x T
+  unsigned long long* totals;   // RM_DEVIATION_COPIES x RM_DEVIATION_WORDS
+  float iso, tolerance;
+};
+hipError_t launch_mesh_deviation_eval_strict(const MeshDeviationSdf& P, hipStream_t stream);
+hipError_t launch_mesh_deviation_eval_fast(const MeshDeviationSdf& P, hipStream_t stream);
+hipError_t launch_mesh_deviation_reduce(const MeshDeviation& D, hipStream_t stream);
 hipError_t launch_camera_rng(const RmUniforms& u, int W, int H, int what, int count, float* out, hipStream_t stream);
 hipError_t launch_math_probe(int fn, const float* a, const float* b, int n, float* out, hipStream_t stream);
 }  // namespace rm

@@ -131,6 +131,8 @@ export class RenderJobContext {
   extractMesh(scene: Scene, grid: MeshGrid, params: MeshParams | null | undefined, sharp: MeshSharp | true | null | undefined, keep: MeshKeep | true | null | undefined, components: boolean | undefined, simplify: MeshSimplify | null | undefined, quadric: MeshQuadric | true | null | undefined, occlusion: MeshOcclusion | true | null | undefined, measures: boolean | undefined, slabs: MeshSlabs | number | true | null): Mesh;
   /** project: the vertices of the returned mesh are moved onto the scene's level set (rm_mesh_project) behind simplify, quadric and keep, before components, occlusion and measures; iso defaults to params.iso, reach to meshProjectReach of the grid the mesh lies on; the result carries `projection` and `residual` */
   extractMesh(scene: Scene, grid: MeshGrid, params: MeshParams | null | undefined, sharp: MeshSharp | true | null | undefined, keep: MeshKeep | true | null | undefined, components: boolean | undefined, simplify: MeshSimplify | null | undefined, quadric: MeshQuadric | true | null | undefined, occlusion: MeshOcclusion | true | null | undefined, measures: boolean | undefined, slabs: MeshSlabs | number | true | null | undefined, project: MeshProject | true | null): Mesh;
+  /** deviation: how far the triangles of the returned mesh lie off the scene's level set (rm_mesh_deviation), measured behind every other stage, project included; iso defaults to params.iso; the result carries `deviation` and `triangleDeviation` */
+  extractMesh(scene: Scene, grid: MeshGrid, params: MeshParams | null | undefined, sharp: MeshSharp | true | null | undefined, keep: MeshKeep | true | null | undefined, components: boolean | undefined, simplify: MeshSimplify | null | undefined, quadric: MeshQuadric | true | null | undefined, occlusion: MeshOcclusion | true | null | undefined, measures: boolean | undefined, slabs: MeshSlabs | number | true | null | undefined, project: MeshProject | true | null | undefined, deviation: MeshDeviation | true | null): Mesh;
   /** the mesher alone on the caller's field (rm_mesh_from_values); keep, components and simplify as in extractMesh */
   meshFromValues(grid: MeshGrid, values: Float32Array, iso?: number, keep?: MeshKeep | true | null, components?: boolean, simplify?: MeshSimplify | null): Mesh;
   /** quadric as in extractMesh */
@@ -170,7 +172,7 @@ export const RM: { [name: string]: number };
 /** mesh extraction (include/hip_raymarch.h "mesh extraction"): n = CELLS per axis between the corners lo and hi */
 export interface MeshGrid { lo: [number, number, number]; hi: [number, number, number]; n: [number, number, number]; slabs?: true }
 export interface MeshParams { iso?: number; normals?: boolean | 0 | 1; normalDelta?: number; colours?: boolean | 0 | 1; flags?: number }
-export interface Mesh { positions: Float32Array; normals: Float32Array | null; colours: Float32Array | null; triangles: Uint32Array; cells: Uint32Array; /** ms of sampling, meshing, attributes (rm_mesh_timings); with an occlusion a fourth entry, its probes and taps */ timings: [number, number, number] | [number, number, number, number]; /** only when components were asked for: each vertex's component, and (vertices, triangles) per component */ labels?: Uint32Array; componentSizes?: Uint32Array; /** only when an occlusion was asked for: 1 = open, per vertex (rm_mesh_occlusion) */ occlusion?: Float32Array; /** only when measures were asked for (rm_mesh_measure) */ measures?: MeshMeasures; /** only with `project`: what rm_mesh_project reports, and the distance minus iso at the projected vertices */ projection?: MeshProjection; residual?: Float32Array }
+export interface Mesh { positions: Float32Array; normals: Float32Array | null; colours: Float32Array | null; triangles: Uint32Array; cells: Uint32Array; /** ms of sampling, meshing, attributes (rm_mesh_timings); with an occlusion a fourth entry, its probes and taps */ timings: [number, number, number] | [number, number, number, number]; /** only when components were asked for: each vertex's component, and (vertices, triangles) per component */ labels?: Uint32Array; componentSizes?: Uint32Array; /** only when an occlusion was asked for: 1 = open, per vertex (rm_mesh_occlusion) */ occlusion?: Float32Array; /** only when measures were asked for (rm_mesh_measure) */ measures?: MeshMeasures; /** only with `project`: what rm_mesh_project reports, and the distance minus iso at the projected vertices */ projection?: MeshProjection; residual?: Float32Array; /** only with `deviation`: what rm_mesh_deviation reports, and each triangle's largest |distance - iso| over its samples */ deviation?: MeshDeviationReport; triangleDeviation?: Float32Array }
 /** what rm_mesh_measure says of a mesh (RmMeshMeasures, include/hip_raymarch.h "measures and edge topology"): the counts as Numbers (all below 2^53), lo / hi of the finite vertices, closed = no boundary and no irregular edge; componentEdges: 4 uint64 per component (edges, boundary, irregular, unbalanced; rm_mesh_measure_components); milliseconds of topology and geometry */
 export interface MeshMeasures { vertices: number; triangles: number; usedVertices: number; skippedTriangles: number; unmeasuredTriangles: number; finiteVertices: number; edges: number; boundaryEdges: number; regularEdges: number; irregularEdges: number; unbalancedEdges: number; euler: number; components: number; closedComponents: number; area: number; volume: number; lo: [number, number, number]; hi: [number, number, number]; closed: boolean; componentEdges: BigUint64Array; milliseconds: [number, number] }
 export const MESH_DEFAULTS: { iso: number; normals: 0 | 1; normalDelta: number; colours: 0 | 1; flags: number };
@@ -210,6 +212,12 @@ export function meshProject(project?: MeshProject | null): Required<MeshProject>
 export function meshProjectReach(grid: MeshGrid): number;
 /** what rm_mesh_project says of its work (RmMeshProjection): how far off the level set the vertices were and are (|distance - iso|: worst vertex, max, mean, rms), the vertices the reach clamped or that had no usable normal, the triangles whose orientation flipped, the rounds evaluated; milliseconds: the rounds and the normals */
 export interface MeshProjection { vertices: number; triangles: number; movedVertices: number; settledBefore: number; settledAfter: number; nonfiniteBefore: number; nonfiniteAfter: number; clampedVertices: number; undirectedVertices: number; flippedTriangles: number; worstBefore: number; worstAfter: number; meanBefore: number; rmsBefore: number; meanAfter: number; rmsAfter: number; maxBefore: number; maxAfter: number; roundsRun: number; milliseconds: number }
+/** the block of rm_mesh_deviation (RmMeshDeviation): the scene's distance minus `iso` at order * order (order 1, 2, 4 or 8) fixed samples inside every triangle; a triangle whose largest |distance - iso| exceeds `tolerance` counts as over */
+export interface MeshDeviation { iso?: number; order?: number; tolerance?: number; flags?: number }
+export const MESH_DEVIATION_DEFAULTS: Required<MeshDeviation>;
+export function meshDeviation(deviation?: MeshDeviation | null): Required<MeshDeviation>;
+/** what rm_mesh_deviation says of a mesh (RmMeshDeviationReport): one-sided, mesh to surface, at `samples` fixed points per triangle -- a lower bound of the true maximum; area, meanSigned and rms are area-weighted over the evaluated triangles; milliseconds: evaluation and reduction */
+export interface MeshDeviationReport { vertices: number; triangles: number; skippedTriangles: number; unevaluatedTriangles: number; nonfiniteSamples: number; overTriangles: number; worstTriangle: number; area: number; overArea: number; meanSigned: number; rms: number; max: number; samples: number; milliseconds: number }
 /** binary little-endian PLY (normals, uchar colours and a float `quality` -- the occlusion -- when present): the bytes the Python host's write_ply writes */
 /** binary STL of the triangles, facet normals computed in double from the float32 positions: the bytes the Python host's mesh.encode_stl writes */
 export function encodeStl(mesh: { positions: Float32Array; triangles: Uint32Array }): Buffer;

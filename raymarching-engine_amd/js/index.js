@@ -376,9 +376,35 @@ class RenderJobContext {  // RenderJobContext + loadRenderJobContext (LoadRender
   // projected mesh.  iso, where not given, is the extraction's; reach, where not given, is meshProjectReach of the grid the returned mesh lies on (the
   // cluster grid with simplify, else the sampling grid).  The result carries projection (RmMeshProjection's fields in camel case, and milliseconds:
   // the rounds and the normals) and residual (Float32Array(V): the distance minus iso at the new vertices); timings stays the producing mesh's
-  extractMesh(scene, grid, opts, sharp, keep, components, simplify = null, quadric = null, occlusion = null, measures = false, slabs = null, project = null) {
+  // deviation: undefined / null = that mesh; true or meshDeviation's options = how far the triangles of the mesh that is returned -- behind every
+  // stage above, project included -- lie off the scene's level set at order * order fixed samples each, measured on the GPU (rm_mesh_deviation).
+  // iso, where not given, is the extraction's.  The result carries deviation (RmMeshDeviationReport's fields in camel case, and milliseconds) and
+  // triangleDeviation (Float32Array(T): each triangle's largest |distance - iso| over its samples); timings is as without it
+  extractMesh(scene, grid, opts, sharp, keep, components, simplify = null, quadric = null, occlusion = null, measures = false, slabs = null, project = null, deviation = null) {
     const q = quadric === undefined || quadric === null ? null : meshQuadric(quadric === true ? undefined : quadric);
     if (q !== null && (simplify === undefined || simplify === null)) throw new TypeError("mesh: quadric places the vertices of a simplification: give simplify as well");
+    if (deviation !== undefined && deviation !== null) {  // (every argument is given: the deviation block is the last)
+      const params = meshParams(opts);
+      const c = simplify === undefined || simplify === null ? null : meshSimplify(simplify);
+      const asked = deviation === true ? {} : deviation;
+      if (typeof asked !== "object") throw new TypeError("mesh: expected true or an object of deviation parameters");
+      const dv = meshDeviation({ iso: params.iso, ...asked });
+      let pr = null;
+      if (project !== undefined && project !== null) {
+        const given = project === true ? {} : project;
+        if (typeof given !== "object") throw new TypeError("mesh: expected true or an object of project parameters");
+        pr = meshProject({ iso: params.iso, reach: meshProjectReach(c !== null ? c.grid : grid), ...given });
+      }
+      const o = occlusion === undefined || occlusion === null ? null : meshOcclusion(occlusion === true ? undefined : occlusion);
+      const s = sharp === undefined || sharp === null ? null : meshSharp(sharp === true ? undefined : sharp);
+      const k = keep === undefined || keep === null ? null : meshKeep(keep === true ? undefined : keep);
+      if (slabs !== undefined && slabs !== null) {
+        const w = meshSlabs(slabs === true ? undefined : typeof slabs === "number" ? { layers: slabs } : slabs);
+        return addon.extractMeshSlabs(this.ctx, this.sceneHandle(scene), grid, w, params, s, k, !!components, c, q, o, !!measures, pr, dv);
+      }
+      if (grid && grid.slabs) throw new TypeError("mesh: a grid made with slabs: true is extracted in slabs: give slabs as well");
+      return addon.extractMesh(this.ctx, this.sceneHandle(scene), grid, params, s, k, !!components, c, q, o, !!measures, pr, dv);
+    }
     if (project !== undefined && project !== null) {  // (every argument is given: the project block is the last)
       const params = meshParams(opts);
       const c = simplify === undefined || simplify === null ? null : meshSimplify(simplify);
@@ -881,6 +907,26 @@ function meshProjectReach(grid) {
   return Math.fround(0.5 * least);
 }
 
+// the block of rm_mesh_deviation (include/hip_raymarch.h RmMeshDeviation): undefined / null = the defaults, or an object with some of iso (the
+// level the mesh stands for), order (n = 1, 2, 4 or 8: n * n samples per triangle), tolerance (>= 0: a triangle whose largest |distance - iso|
+// exceeds it counts as over) and flags (RM.RENDER_FAST, RM.RENDER_NO_CULL); checked as the library checks it
+const MESH_DEVIATION_DEFAULTS = { iso: 0, order: 4, tolerance: 0, flags: 0 };
+function meshDeviation(opts) {
+  const p = { ...MESH_DEVIATION_DEFAULTS };
+  if (opts !== undefined && opts !== null) {
+    if (typeof opts !== "object") throw new TypeError("mesh: expected an object of deviation parameters");
+    for (const [k, v] of Object.entries(opts)) {
+      if (!(k in MESH_DEVIATION_DEFAULTS)) throw new TypeError("mesh: unknown deviation parameter " + k);
+      p[k] = v;
+    }
+  }
+  if (!finite(p.iso) || !finite(Math.fround(p.iso))) throw new RangeError("mesh: deviation iso must be finite");
+  if (![1, 2, 4, 8].includes(p.order)) throw new RangeError("mesh: deviation order must be 1, 2, 4 or 8");
+  if (!finite(p.tolerance) || !finite(Math.fround(p.tolerance)) || !(p.tolerance >= 0)) throw new RangeError("mesh: deviation tolerance must be finite and >= 0");
+  if (!Number.isInteger(p.flags) || (p.flags & ~(RM.RENDER_FAST | RM.RENDER_NO_CULL)) !== 0) throw new RangeError("mesh: deviation flags must be 0, RM.RENDER_FAST, RM.RENDER_NO_CULL or both");
+  return p;
+}
+
 // binary little-endian PLY of { positions, triangles, normals?, colours?, occlusion? }: x y z, then nx ny nz, then uchar red green blue
 // (floor(clamp(c, 0, 1) * 255 + 0.5), NaN as 0), then float quality (the occlusion); faces as a uchar count and uint indices -- the bytes the
 // Python host writes
@@ -961,4 +1007,4 @@ module.exports = { RM, addon, encodePng, Scene, CsgScene, Mandelbulb, singleSphe
                    tileRect, RenderJobContext, ShardedRenderJobContext, doRenderJob, U_OFFSET, DENOISE_DEFAULTS, denoiseParams,
                    DENOISE_VARIANCE_DEFAULTS, denoiseVarianceParams, DESPECKLE_DEFAULTS, despeckleParams, DISPLAY_DEFAULTS, AUTO_EXPOSURE_DEFAULTS,
                    displayParams, statsExposure, statsPercentile, MESH_DEFAULTS, meshGrid, meshParams, MESH_SHARP_DEFAULTS, meshSharp, MESH_KEEP_DEFAULTS, meshKeep, MESH_SLABS_DEFAULTS, meshSlabs,
-                   MESH_SIMPLIFY_DEFAULTS, meshSimplify, MESH_QUADRIC_DEFAULTS, meshQuadric, MESH_OCCLUSION_DEFAULTS, meshOcclusion, MESH_PROJECT_DEFAULTS, meshProject, meshProjectReach, encodePly, encodeStl };
+                   MESH_SIMPLIFY_DEFAULTS, meshSimplify, MESH_QUADRIC_DEFAULTS, meshQuadric, MESH_OCCLUSION_DEFAULTS, meshOcclusion, MESH_PROJECT_DEFAULTS, meshProject, meshProjectReach, MESH_DEVIATION_DEFAULTS, meshDeviation, encodePly, encodeStl };

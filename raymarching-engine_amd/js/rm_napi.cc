@@ -642,6 +642,32 @@ static napi_value MeshProjectBlock(napi_env env, napi_callback_info info) {
   return b;
 }
 
+static const Field MESH_DEVIATION_FIELDS[] = {{"iso", Field::FLOAT, offsetof(RmMeshDeviation, iso)}, {"order", Field::INT, offsetof(RmMeshDeviation, order)},
+                                              {"tolerance", Field::FLOAT, offsetof(RmMeshDeviation, tolerance)}, {"flags", Field::INT, offsetof(RmMeshDeviation, flags)}};
+// the block of rm_mesh_deviation: null / undefined = none (*given = false), an object = its fields over the defaults
+static bool get_mesh_deviation(napi_env env, napi_value v, RmMeshDeviation* p, bool* given) {
+  rm_mesh_deviation_default(p);
+  return get_block(env, v, p, MESH_DEVIATION_FIELDS, given);
+}
+
+// meshDeviationBlock(deviation | null) -> ArrayBuffer(RmMeshDeviation): the bytes a host hands to rm_mesh_deviation (null: the defaults)
+static napi_value MeshDeviationBlock(napi_env env, napi_callback_info info) {
+  size_t argc = 1;
+  napi_value argv[1];
+  NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+  RmMeshDeviation p;
+  bool given = false;
+  if (argc != 1 || !get_mesh_deviation(env, argv[0], &p, &given)) {
+    napi_throw_type_error(env, nullptr, "meshDeviationBlock(deviation | null)");
+    return nullptr;
+  }
+  napi_value b;
+  void* d = nullptr;
+  NAPI_OK(napi_create_arraybuffer(env, sizeof p, &d, &b));
+  std::memcpy(d, &p, sizeof p);
+  return b;
+}
+
 // meshOcclusionBlock(occlusion | null) -> ArrayBuffer(RmMeshOcclusion): the bytes extractMesh hands to rm_mesh_occlusion (null: the defaults)
 static napi_value MeshOcclusionBlock(napi_env env, napi_callback_info info) {
   size_t argc = 1;
@@ -758,7 +784,8 @@ static napi_value measures_object(napi_env env, const RmMeshMeasures& m, const f
 
 static napi_value mesh_result(napi_env env, rm_ctx* ctx, rm_mesh* mesh, bool normals, bool colours, const RmMeshKeep* keep = nullptr, bool components = false,
                               const MeshSimplifyBlock* simplify = nullptr, const RmMeshQuadric* quadric = nullptr, rm_scene* scene = nullptr,
-                              const RmMeshOcclusion* occlusion = nullptr, bool measures = false, const RmMeshProject* project = nullptr) {
+                              const RmMeshOcclusion* occlusion = nullptr, bool measures = false, const RmMeshProject* project = nullptr,
+                              const RmMeshDeviation* deviation = nullptr) {
   struct Guard {  // the handle in hand is destroyed on every way out
     rm_mesh* h;
     ~Guard() { rm_mesh_destroy(h); }
@@ -856,6 +883,24 @@ static napi_value mesh_result(napi_env env, rm_ctx* ctx, rm_mesh* mesh, bool nor
     if (napi_set_named_property(env, o, "occlusion", v) != napi_ok) return napi_failed();
     ms[3] = ms2[0] + ms2[1];
   }
+  if (deviation) {  // RmMeshDeviationReport's fields in camel case, the counts as Numbers (all below 2^53), the milliseconds of both spans; max_t per triangle
+    napi_value r = nullptr, v = nullptr, worst = nullptr;
+    void* data = nullptr;
+    RmMeshDeviationReport report{};
+    float ms2[2] = {0.0f, 0.0f};
+    if (!(worst = make_array(env, napi_float32_array, (size_t)counts[1], &data))) return napi_failed();
+    if (rm_mesh_deviation(mesh, scene, deviation, &report, static_cast<float*>(data), ms2) != RM_OK) return throw_rm(env, ctx, "rm_mesh_deviation");
+    if (napi_create_object(env, &r) != napi_ok) return napi_failed();
+    const struct { const char* name; double value; } NUMBERS[] = {
+        {"vertices", (double)report.vertices}, {"triangles", (double)report.triangles}, {"skippedTriangles", (double)report.skipped_triangles},
+        {"unevaluatedTriangles", (double)report.unevaluated_triangles}, {"nonfiniteSamples", (double)report.nonfinite_samples},
+        {"overTriangles", (double)report.over_triangles}, {"worstTriangle", (double)report.worst_triangle}, {"area", report.area},
+        {"overArea", report.over_area}, {"meanSigned", report.mean_signed}, {"rms", report.rms}, {"max", (double)report.max},
+        {"samples", (double)report.samples}, {"milliseconds", (double)(ms2[0] + ms2[1])}};
+    for (const auto& n : NUMBERS)
+      if (napi_create_double(env, n.value, &v) != napi_ok || napi_set_named_property(env, r, n.name, v) != napi_ok) return napi_failed();
+    if (napi_set_named_property(env, o, "deviation", r) != napi_ok || napi_set_named_property(env, o, "triangleDeviation", worst) != napi_ok) return napi_failed();
+  }
   const uint32_t spans = occlusion ? 4u : 3u;
   napi_value timings = nullptr;
   if (napi_create_array_with_length(env, spans, &timings) != napi_ok) return napi_failed();
@@ -877,12 +922,13 @@ static napi_value mesh_result(napi_env env, rm_ctx* ctx, rm_mesh* mesh, bool nor
 // with a sharp block rm_mesh_extract_sharp; with a simplify block rm_mesh_simplify behind it (with a quadric block too: rm_mesh_simplify_quadric);
 // with a keep block rm_mesh_filter behind that; with measures rm_mesh_measure on that last mesh; then the arrays, with an occlusion block
 // rm_mesh_occlusion on that last mesh.  A quadric block without a simplify block is refused.  With a project block rm_mesh_project behind
-// simplify and keep, before the measures, the components and the occlusion: `projection` and `residual` come with the result.
+// simplify and keep, before the measures, the components and the occlusion: `projection` and `residual` come with the result.  With a
+// deviation block rm_mesh_deviation on the mesh that is returned: `deviation` and `triangleDeviation` come with the result.
 static napi_value ExtractMesh(napi_env env, napi_callback_info info) {
-  size_t argc = 12;
-  napi_value argv[12];
+  size_t argc = 13;
+  napi_value argv[13];
   NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
-  const bool counted = argc >= 4 && argc <= 12;
+  const bool counted = argc >= 4 && argc <= 13;
   rm_ctx* ctx = counted ? get_external<rm_ctx>(env, argv[0]) : nullptr;
   rm_scene* scene = counted ? get_external<rm_scene>(env, argv[1]) : nullptr;
   RmGrid g;
@@ -893,11 +939,12 @@ static napi_value ExtractMesh(napi_env env, napi_callback_info info) {
   RmMeshQuadric q;
   RmMeshOcclusion ao;
   RmMeshProject pr;
-  bool sharp = false, keep = false, components = false, simplify = false, quadric = false, occlusion = false, measures = false, project = false;
+  RmMeshDeviation dv;
+  bool sharp = false, keep = false, components = false, simplify = false, quadric = false, occlusion = false, measures = false, project = false, deviation = false;
   if (!ctx || !scene || !get_grid(env, argv[2], &g) || !get_mesh_params(env, argv[3], &p) || (argc >= 5 && !get_mesh_sharp(env, argv[4], &s, &sharp)) ||
       (argc >= 6 && !get_mesh_keep(env, argv[5], &k, &keep)) || (argc >= 7 && !get_bool(env, argv[6], &components)) ||
-      (argc >= 8 && !get_mesh_simplify(env, argv[7], &c, &simplify)) || (argc >= 9 && !get_mesh_quadric(env, argv[8], &q, &quadric)) || (argc >= 10 && !get_mesh_occlusion(env, argv[9], &ao, &occlusion)) || (argc >= 11 && !get_bool(env, argv[10], &measures)) || (argc == 12 && !get_mesh_project(env, argv[11], &pr, &project)) || (quadric && !simplify)) {
-    napi_throw_type_error(env, nullptr, "extractMesh(ctx, scene, grid, params | null[, sharp | null[, keep | null[, components[, simplify | null[, quadric | null[, occlusion | null[, measures[, project | null]]]]]]]])");
+      (argc >= 8 && !get_mesh_simplify(env, argv[7], &c, &simplify)) || (argc >= 9 && !get_mesh_quadric(env, argv[8], &q, &quadric)) || (argc >= 10 && !get_mesh_occlusion(env, argv[9], &ao, &occlusion)) || (argc >= 11 && !get_bool(env, argv[10], &measures)) || (argc >= 12 && !get_mesh_project(env, argv[11], &pr, &project)) || (argc == 13 && !get_mesh_deviation(env, argv[12], &dv, &deviation)) || (quadric && !simplify)) {
+    napi_throw_type_error(env, nullptr, "extractMesh(ctx, scene, grid, params | null[, sharp | null[, keep | null[, components[, simplify | null[, quadric | null[, occlusion | null[, measures[, project | null[, deviation | null]]]]]]]]])");
     return nullptr;
   }
   rm_mesh* mesh = nullptr;
@@ -905,7 +952,7 @@ static napi_value ExtractMesh(napi_env env, napi_callback_info info) {
     if (rm_mesh_extract_sharp(ctx, scene, &g, &p, &s, &mesh) != RM_OK) return throw_rm(env, ctx, "rm_mesh_extract_sharp");
   } else if (rm_mesh_extract(ctx, scene, &g, &p, &mesh) != RM_OK) return throw_rm(env, ctx, "rm_mesh_extract");
   return mesh_result(env, ctx, mesh, p.normals != 0, p.colours != 0, keep ? &k : nullptr, components, simplify ? &c : nullptr, quadric ? &q : nullptr, scene,
-                     occlusion ? &ao : nullptr, measures, project ? &pr : nullptr);
+                     occlusion ? &ao : nullptr, measures, project ? &pr : nullptr, deviation ? &dv : nullptr);
 }
 
 // meshFromValues(ctx, grid, values: Float32Array(corners), iso[, keep | null[, components[, simplify | null[, quadric | null[, measures]]]]]) = rm_mesh_from_values,
@@ -970,10 +1017,10 @@ static napi_value MeshSlabsBlock(napi_env env, napi_callback_info info) {
 // extractMeshSlabs(ctx, scene, grid, slabs | null, params | null, sharp | null, keep | null, components, simplify | null, quadric | null, occlusion | null,
 // measures): extractMesh with rm_mesh_extract_slabs / rm_mesh_extract_sharp_slabs in place of rm_mesh_extract / _sharp; every argument is given
 static napi_value ExtractMeshSlabs(napi_env env, napi_callback_info info) {
-  size_t argc = 13;
-  napi_value argv[13];
+  size_t argc = 14;
+  napi_value argv[14];
   NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
-  const bool counted = argc == 12 || argc == 13;  // (the thirteenth: a project block, as extractMesh's twelfth)
+  const bool counted = argc >= 12 && argc <= 14;  // (the thirteenth: a project block, as extractMesh's twelfth; the fourteenth: a deviation block)
   rm_ctx* ctx = counted ? get_external<rm_ctx>(env, argv[0]) : nullptr;
   rm_scene* scene = counted ? get_external<rm_scene>(env, argv[1]) : nullptr;
   RmGrid g;
@@ -985,12 +1032,13 @@ static napi_value ExtractMeshSlabs(napi_env env, napi_callback_info info) {
   RmMeshQuadric q;
   RmMeshOcclusion ao;
   RmMeshProject pr;
-  bool sharp = false, keep = false, components = false, simplify = false, quadric = false, occlusion = false, measures = false, project = false;
+  RmMeshDeviation dv;
+  bool sharp = false, keep = false, components = false, simplify = false, quadric = false, occlusion = false, measures = false, project = false, deviation = false;
   if (!ctx || !scene || !get_grid(env, argv[2], &g) || !get_mesh_slabs(env, argv[3], &w) || !get_mesh_params(env, argv[4], &p) ||
       !get_mesh_sharp(env, argv[5], &s, &sharp) || !get_mesh_keep(env, argv[6], &k, &keep) || !get_bool(env, argv[7], &components) ||
       !get_mesh_simplify(env, argv[8], &c, &simplify) || !get_mesh_quadric(env, argv[9], &q, &quadric) || !get_mesh_occlusion(env, argv[10], &ao, &occlusion) ||
-      !get_bool(env, argv[11], &measures) || (argc == 13 && !get_mesh_project(env, argv[12], &pr, &project)) || (quadric && !simplify)) {
-    napi_throw_type_error(env, nullptr, "extractMeshSlabs(ctx, scene, grid, slabs | null, params | null, sharp | null, keep | null, components, simplify | null, quadric | null, occlusion | null, measures[, project | null])");
+      !get_bool(env, argv[11], &measures) || (argc >= 13 && !get_mesh_project(env, argv[12], &pr, &project)) || (argc == 14 && !get_mesh_deviation(env, argv[13], &dv, &deviation)) || (quadric && !simplify)) {
+    napi_throw_type_error(env, nullptr, "extractMeshSlabs(ctx, scene, grid, slabs | null, params | null, sharp | null, keep | null, components, simplify | null, quadric | null, occlusion | null, measures[, project | null[, deviation | null]])");
     return nullptr;
   }
   rm_mesh* mesh = nullptr;
@@ -998,7 +1046,7 @@ static napi_value ExtractMeshSlabs(napi_env env, napi_callback_info info) {
     if (rm_mesh_extract_sharp_slabs(ctx, scene, &g, &p, &s, &w, &mesh) != RM_OK) return throw_rm(env, ctx, "rm_mesh_extract_sharp_slabs");
   } else if (rm_mesh_extract_slabs(ctx, scene, &g, &p, &w, &mesh) != RM_OK) return throw_rm(env, ctx, "rm_mesh_extract_slabs");
   return mesh_result(env, ctx, mesh, p.normals != 0, p.colours != 0, keep ? &k : nullptr, components, simplify ? &c : nullptr, quadric ? &q : nullptr, scene,
-                     occlusion ? &ao : nullptr, measures, project ? &pr : nullptr);
+                     occlusion ? &ao : nullptr, measures, project ? &pr : nullptr, deviation ? &dv : nullptr);
 }
 
 // meshFromValuesSlabs(ctx, grid, values: Float32Array(corners), iso, slabs | null, keep | null, components, simplify | null, quadric | null, measures):
@@ -1233,7 +1281,7 @@ static napi_value Sizes(napi_env env, napi_callback_info) {
       {"RmMaterial", (uint32_t)sizeof(RmMaterial)}, {"RmRect", (uint32_t)sizeof(RmRect)}, {"RmSurface", (uint32_t)sizeof(RmSurface)}, {"RmDenoise", (uint32_t)sizeof(RmDenoise)},
       {"RmDenoiseVariance", (uint32_t)sizeof(RmDenoiseVariance)}, {"RmDespeckle", (uint32_t)sizeof(RmDespeckle)}, {"RmFilters", (uint32_t)sizeof(RmFilters)}, {"RmFrameStats", (uint32_t)sizeof(RmFrameStats)},
       {"RmAutoExposure", (uint32_t)sizeof(RmAutoExposure)}, {"RmDisplay", (uint32_t)sizeof(RmDisplay)}, {"RmGrid", (uint32_t)sizeof(RmGrid)},
-      {"RmMeshParams", (uint32_t)sizeof(RmMeshParams)}, {"RmMeshSharp", (uint32_t)sizeof(RmMeshSharp)}, {"RmMeshKeep", (uint32_t)sizeof(RmMeshKeep)}, {"RmMeshSimplify", (uint32_t)sizeof(RmMeshSimplify)}, {"RmMeshQuadric", (uint32_t)sizeof(RmMeshQuadric)}, {"RmMeshOcclusion", (uint32_t)sizeof(RmMeshOcclusion)}, {"RmMeshMeasures", (uint32_t)sizeof(RmMeshMeasures)}, {"RmMeshSlabs", (uint32_t)sizeof(RmMeshSlabs)}, {"RmMeshProject", (uint32_t)sizeof(RmMeshProject)}, {"RmMeshProjection", (uint32_t)sizeof(RmMeshProjection)}, {"abi", (uint32_t)rm_abi_version()}};
+      {"RmMeshParams", (uint32_t)sizeof(RmMeshParams)}, {"RmMeshSharp", (uint32_t)sizeof(RmMeshSharp)}, {"RmMeshKeep", (uint32_t)sizeof(RmMeshKeep)}, {"RmMeshSimplify", (uint32_t)sizeof(RmMeshSimplify)}, {"RmMeshQuadric", (uint32_t)sizeof(RmMeshQuadric)}, {"RmMeshOcclusion", (uint32_t)sizeof(RmMeshOcclusion)}, {"RmMeshMeasures", (uint32_t)sizeof(RmMeshMeasures)}, {"RmMeshSlabs", (uint32_t)sizeof(RmMeshSlabs)}, {"RmMeshProject", (uint32_t)sizeof(RmMeshProject)}, {"RmMeshProjection", (uint32_t)sizeof(RmMeshProjection)}, {"RmMeshDeviation", (uint32_t)sizeof(RmMeshDeviation)}, {"RmMeshDeviationReport", (uint32_t)sizeof(RmMeshDeviationReport)}, {"abi", (uint32_t)rm_abi_version()}};
   for (const auto& it : items) {
     NAPI_OK(napi_create_uint32(env, it.v, &v));
     NAPI_OK(napi_set_named_property(env, o, it.k, v));
@@ -1246,7 +1294,7 @@ static napi_value Init(napi_env env, napi_value exports) {
       {"ctxCreate", CtxCreate}, {"ctxDestroy", CtxDestroy}, {"sync", Sync}, {"sceneCreate", SceneCreate}, {"sceneDestroy", SceneDestroy},
       {"fbCreate", FbCreate}, {"fbClear", FbClear}, {"fbDestroy", FbDestroy}, {"fbDownload", FbDownload}, {"present", Present}, {"denoise", Denoise}, {"presentDenoised", PresentDenoised}, {"denoiseVariance", DenoiseVariance}, {"presentDenoisedVariance", PresentDenoisedVariance}, {"filter", Filter}, {"presentFiltered", PresentFiltered}, {"presentDisplay", PresentDisplay}, {"presentLinear", PresentLinear}, {"frameStats", FrameStats}, {"statsExposure", StatsExposure}, {"statsPercentile", StatsPercentile}, {"renderSample", RenderSample}, {"renderSamples", RenderSamples},
       {"fbCreateStriped", FbCreateStriped}, {"fbRows", FbRows}, {"setSamplesInFlight", SetSamplesInFlight}, {"presentSharded", PresentSharded}, {"presentShardedStart", PresentShardedStart}, {"presentShardedFinish", PresentShardedFinish},
-      {"meshBlocks", MeshBlocks}, {"meshSharpBlock", MeshSharpBlock}, {"meshKeepBlock", MeshKeepBlock}, {"meshSimplifyBlock", MeshSimplifyBlockOf}, {"meshQuadricBlock", MeshQuadricBlock}, {"meshOcclusionBlock", MeshOcclusionBlock}, {"meshProjectBlock", MeshProjectBlock}, {"sdfGrid", SdfGrid}, {"extractMesh", ExtractMesh}, {"meshFromValues", MeshFromValues}, {"meshSlabsBlock", MeshSlabsBlock}, {"extractMeshSlabs", ExtractMeshSlabs}, {"meshFromValuesSlabs", MeshFromValuesSlabs}, {"sizes", Sizes}};
+      {"meshBlocks", MeshBlocks}, {"meshSharpBlock", MeshSharpBlock}, {"meshKeepBlock", MeshKeepBlock}, {"meshSimplifyBlock", MeshSimplifyBlockOf}, {"meshQuadricBlock", MeshQuadricBlock}, {"meshOcclusionBlock", MeshOcclusionBlock}, {"meshProjectBlock", MeshProjectBlock}, {"meshDeviationBlock", MeshDeviationBlock}, {"sdfGrid", SdfGrid}, {"extractMesh", ExtractMesh}, {"meshFromValues", MeshFromValues}, {"meshSlabsBlock", MeshSlabsBlock}, {"extractMeshSlabs", ExtractMeshSlabs}, {"meshFromValuesSlabs", MeshFromValuesSlabs}, {"sizes", Sizes}};
   for (const auto& f : fns) {
     napi_value fn;
     if (napi_create_function(env, f.name, NAPI_AUTO_LENGTH, f.fn, nullptr, &fn) != napi_ok) return nullptr;

@@ -218,6 +218,32 @@ def mesh_project(**fields) -> abi.RmMeshProject:
                              normal_delta=float(p["normal_delta"]), flags=int(flags), reserved=0)
 
 
+def mesh_deviation(**fields) -> abi.RmMeshDeviation:
+    """The abi.RmMeshDeviation of Context.extract_mesh(..., deviation=...), over abi.MESH_DEVIATION_DEFAULTS: iso (the level the mesh stands
+    for), order (n = 1, 2, 4 or 8: n * n samples per triangle), tolerance (a triangle whose largest |distance - iso| exceeds it is counted as
+    over, >= 0) and flags (rm_sdf_grid's).  Checked as the library checks it: ValueError otherwise, and for unknown keys."""
+    unknown = set(fields) - set(abi.MESH_DEVIATION_DEFAULTS)
+    if unknown:
+        raise ValueError(f"mesh: unknown deviation parameter {sorted(unknown)[0]}")
+    p = {**abi.MESH_DEVIATION_DEFAULTS, **fields}
+    for name in ("iso", "tolerance"):
+        if isinstance(p[name], bool) or not isinstance(p[name], (int, float, np.integer, np.floating)):
+            raise ValueError(f"mesh: deviation {name} must be a number")
+    with np.errstate(over="ignore"):
+        iso, tolerance = np.float32(p["iso"]), np.float32(p["tolerance"])
+    if not math.isfinite(iso):
+        raise ValueError("mesh: deviation iso must be finite")
+    order = p["order"]
+    if isinstance(order, bool) or not isinstance(order, (int, np.integer)) or int(order) not in (1, 2, 4, 8):
+        raise ValueError("mesh: deviation order must be 1, 2, 4 or 8")
+    if not (math.isfinite(tolerance) and tolerance >= 0):
+        raise ValueError("mesh: deviation tolerance must be finite and >= 0")
+    flags = p["flags"]
+    if isinstance(flags, bool) or not isinstance(flags, (int, np.integer)) or int(flags) & ~(abi.RM_RENDER_FAST | abi.RM_RENDER_NO_CULL):
+        raise ValueError("mesh: deviation flags must be 0, RM_RENDER_FAST, RM_RENDER_NO_CULL or both")
+    return abi.RmMeshDeviation(iso=float(p["iso"]), order=int(order), tolerance=float(p["tolerance"]), flags=int(flags))
+
+
 def project_reach(grid: Grid) -> float:
     """The reach extract_mesh(..., project=...) takes when none is given: half the smallest cell side of `grid`, 0.5f * min h[a] with h in
     fp32 by RmGrid's rule."""
@@ -245,6 +271,8 @@ class Mesh:
     measures = None  # Optional[dict]; taken the same way
     projection = None  # Optional[dict]: abi.RmMeshProjection's fields (rm_mesh_project), only when the call asked for a projection; taken the same way
     residual = None  # Optional[np.ndarray]: [V] float32, the distance minus iso at the projected vertices; with `projection`
+    deviation = None  # Optional[dict]: abi.RmMeshDeviationReport's fields (rm_mesh_deviation), only when the call asked for a deviation; taken the same way
+    triangle_deviation = None  # Optional[np.ndarray]: [T] float32, each triangle's largest |distance - iso| over its samples; with `deviation`
 
     @property
     def vertices(self) -> int:
@@ -252,12 +280,14 @@ class Mesh:
 
 
 def _with_occlusion(init):
-    def __init__(self, *args, occlusion=None, measures=None, projection=None, residual=None, **fields):
+    def __init__(self, *args, occlusion=None, measures=None, projection=None, residual=None, deviation=None, triangle_deviation=None, **fields):
         init(self, *args, **fields)
         self.occlusion = occlusion
         self.measures = measures
         self.projection = projection
         self.residual = residual
+        self.deviation = deviation
+        self.triangle_deviation = triangle_deviation
 
     __init__.__doc__, __init__.__wrapped__ = init.__doc__, init
     return __init__

@@ -48,6 +48,7 @@ EXPORTS = [
     "rm_mesh_measure", "rm_mesh_measure_components",
     "rm_mesh_slabs_default", "rm_mesh_extract_slabs", "rm_mesh_extract_sharp_slabs", "rm_mesh_from_values_slabs",
     "rm_mesh_project_default", "rm_mesh_project",
+    "rm_mesh_deviation_default", "rm_mesh_deviation_weights", "rm_mesh_deviation",
 ]
 
 # G-buffer formats of a framebuffer (include/hip_raymarch.h RM_GBUFFER_*): "f32" (the default: the software GL stack's planes, which the
@@ -436,6 +437,9 @@ def load_library(path=None):
         "rm_mesh_from_values_slabs": (ip, [vp, C.POINTER(abi.RmGrid), fp, C.c_float, C.POINTER(abi.RmMeshSlabs), C.POINTER(vp)]),
         "rm_mesh_project_default": (None, [C.POINTER(abi.RmMeshProject)]),
         "rm_mesh_project": (ip, [vp, vp, C.POINTER(abi.RmMeshProject), C.POINTER(vp), C.POINTER(abi.RmMeshProjection), fp]),
+        "rm_mesh_deviation_default": (None, [C.POINTER(abi.RmMeshDeviation)]),
+        "rm_mesh_deviation_weights": (ip, [ip, fp]),
+        "rm_mesh_deviation": (ip, [vp, vp, C.POINTER(abi.RmMeshDeviation), C.POINTER(abi.RmMeshDeviationReport), fp, fp]),
     }
     for name, (res, args) in sig.items():
         if name.startswith("rm_debug_") and not hasattr(lib, name) and os.environ.get("RM_LIB"):
@@ -733,7 +737,7 @@ class Context:
         self._check(self.lib.rm_sdf_grid_device(self.h, scene.h, C.byref(g), int(flags), C.c_void_p(out_ptr), C.c_void_p(stream) if stream else None))
 
     def _take_mesh(self, handle, grid, normals=False, colours=False, keep=None, components=False, simplify=None, quadric=None, scene=None, occlusion=None, measures=False,
-                   project=None):
+                   project=None, deviation=None):
         """The arrays of a mesh handle as a mesh.Mesh (normals / colours: whether the call that made it asked for them); destroys the handle.
         simplify (_mesh_simplify's triple): the mesh is first clustered on the device (rm_mesh_simplify) and the Mesh's grid is the cluster grid,
         which its cells then index -- with quadric (an abi.RmMeshQuadric) by rm_mesh_simplify_quadric; keep (an abi.RmMeshKeep): that mesh is filtered on the device (rm_mesh_filter), which also removes the vertices
@@ -744,7 +748,9 @@ class Context:
         project (_mesh_project's function of the grid the mesh lies on, with the scene): behind simplify and keep, that mesh's vertices are
         projected onto the scene's level set (rm_mesh_project) and everything after sees the projected mesh: Mesh.projection, Mesh.residual,
         and the timings gain "projection", the milliseconds of its rounds and its normals; sampling, meshing and attributes stay those of the
-        mesh that was projected, so nothing is counted twice."""
+        mesh that was projected, so nothing is counted twice.  deviation (an abi.RmMeshDeviation, with the scene): how far the triangles of
+        the mesh that is returned lie off the scene's level set (rm_mesh_deviation): Mesh.deviation, Mesh.triangle_deviation, and the timings
+        gain "deviation", the milliseconds of its evaluation and its reduction."""
         from .mesh import Mesh
 
         handles = [handle]
@@ -813,6 +819,11 @@ class Context:
                 self._check(self.lib.rm_mesh_occlusion(handle, scene.h, C.byref(occlusion), _fp(ao), ms2))
                 arrays["occlusion"] = ao
                 timings["occlusion"] = float(ms2[0]) + float(ms2[1])
+            if deviation is not None:
+                report, worst, ms2 = abi.RmMeshDeviationReport(), np.empty(t, np.float32), (C.c_float * 2)()
+                self._check(self.lib.rm_mesh_deviation(handle, scene.h, C.byref(deviation), C.byref(report), _fp(worst), ms2))
+                arrays["deviation"], arrays["triangle_deviation"] = abi.mesh_deviation_dict(report), worst
+                timings["deviation"] = float(ms2[0]) + float(ms2[1])
             if measured is not None:
                 arrays["measures"] = measured
                 timings["measures"] = float(measure_ms[0]) + float(measure_ms[1])
@@ -870,6 +881,16 @@ class Context:
         return lambda grid: mesh.mesh_project(**{"reach": mesh.project_reach(grid), **fields})
 
     @staticmethod
+    def _mesh_deviation(deviation, iso):
+        """The `deviation` of extract_mesh as an abi.RmMeshDeviation (_mesh_block's rules); None stays None.  True and a dict take the
+        extraction's iso where they name none; a struct is taken as it stands."""
+        if deviation is True:
+            deviation = {}
+        if isinstance(deviation, dict):
+            deviation = {"iso": iso, **deviation}
+        return Context._mesh_block("deviation", deviation, abi.RmMeshDeviation)
+
+    @staticmethod
     def _mesh_quadric(quadric, simplify):
         """The `quadric` of extract_mesh / mesh_from_values as an abi.RmMeshQuadric (_mesh_block's rules); without `simplify` there is nothing
         to place: ValueError."""
@@ -918,7 +939,7 @@ class Context:
 
     def extract_mesh(self, scene: "SceneHandle", grid, iso: float = 0.0, normals: bool = True, colours: bool = False, flags: int = 0,
                      normal_delta: float = 1e-5, sharp=None, *, keep=None, components: bool = False, simplify=None, quadric=None,
-                     measures: bool = False, slabs=None, project=None, occlusion=None):
+                     measures: bool = False, slabs=None, deviation=None, project=None, occlusion=None):
         """The level set `iso` of the scene on `grid` (mesh.Grid) as a mesh.Mesh: rm_mesh_extract -- the distances sampled and meshed
         (surface nets) on the device, with per-vertex normals / diffuse colours from the scene's probes when asked for.  `sharp`: None is
         that call; True (the defaults), a dict of mesh.mesh_sharp's arguments or an abi.RmMeshSharp is rm_mesh_extract_sharp -- the same
@@ -945,11 +966,17 @@ class Context:
         extraction's; reach, where not given, is half the smallest cell side of the grid the returned mesh lies on (the cluster grid with
         `simplify`, else the sampling grid).  The mesh carries Mesh.projection (a dict of abi.RmMeshProjection's fields), Mesh.residual ([V]
         float32: the distance minus iso at the new vertices) and timings["projection"], the milliseconds of the rounds and the normals; the
-        other three timings stay those of the mesh that was projected."""
+        other three timings stay those of the mesh that was projected.
+        `deviation`: None is that mesh; True (the defaults), a dict of mesh.mesh_deviation's arguments or an abi.RmMeshDeviation measures on the
+        device how far the triangles of the mesh that is returned -- behind every stage above, `project` included -- lie off the scene's level
+        set at order * order fixed samples each (rm_mesh_deviation).  iso, where not given, is the extraction's.  The mesh carries
+        Mesh.deviation (a dict of abi.RmMeshDeviationReport's fields), Mesh.triangle_deviation ([T] float32: each triangle's largest
+        |distance - iso| over its samples) and timings["deviation"]."""
         from .mesh import mesh_params
 
         keep, simplify, quadric = self._mesh_keep(keep), self._mesh_simplify(simplify), self._mesh_quadric(quadric, simplify)  # (refused before anything runs)
         occlusion, project = self._mesh_occlusion(occlusion), self._mesh_project(project, iso)
+        deviation = self._mesh_deviation(deviation, iso)
         g, p = grid.to_c(), mesh_params(iso=iso, normals=normals, colours=colours, flags=flags, normal_delta=normal_delta)
         h = C.c_void_p()
         s = self._mesh_block("sharp", sharp, abi.RmMeshSharp)
@@ -963,7 +990,7 @@ class Context:
         else:
             self._check(self.lib.rm_mesh_extract_sharp_slabs(self.h, scene.h, C.byref(g), C.byref(p), C.byref(s), C.byref(w), C.byref(h)))
         return self._take_mesh(h, grid, normals=p.normals, colours=p.colours, keep=keep, components=components, simplify=simplify, quadric=quadric,
-                               scene=scene, occlusion=occlusion, measures=measures, project=project)
+                               scene=scene, occlusion=occlusion, measures=measures, project=project, deviation=deviation)
 
     def mesh_from_values(self, grid, values: np.ndarray, iso: float = 0.0, *, keep=None, components: bool = False, simplify=None, quadric=None,
                          measures: bool = False, slabs=None):
