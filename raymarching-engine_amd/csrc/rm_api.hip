@@ -30,14 +30,22 @@
 
 #define RM_SP_MAX 8
 
-// rm_glstack.hip: the parity build in the GL stack's arithmetic, behind C entry points (its types live in another namespace)
+// rm_glstack.hip: the parity build in the GL stack's arithmetic.  Its scene passes are rm_params.hpp's launchers in namespace rm_gl (their
+// parameter blocks are global types); what takes types of namespace rm, or no block at all, sits behind C entry points.
+namespace rm_gl {
+hipError_t launch_pixels_strict(const KParams& P, hipStream_t stream);
+hipError_t launch_probe_strict(const ProbeParams& P, hipStream_t stream);
+hipError_t launch_sdf_grid_strict(const SdfGridParams& P, hipStream_t stream);
+hipError_t launch_mesh_occlusion_strict(const MeshOcclusionPass& P, hipStream_t stream);
+hipError_t launch_mesh_project_eval_strict(const MeshProjectEval& P, hipStream_t stream);
+hipError_t launch_mesh_deviation_eval_strict(const MeshDeviationSdf& P, hipStream_t stream);
+}  // namespace rm_gl
+// A scene pass `name` in the unit the flags and the context select: the fast build, the GL stack's arithmetic, or the parity build.
+#define RM_SCENE_PASS(ctx, flags, name, P, stream)              \
+  (((flags) & RM_RENDER_FAST) ? rm::name##_fast(P, stream)      \
+   : (ctx)->gl_stack          ? rm_gl::name##_strict(P, stream) \
+                              : rm::name##_strict(P, stream))
 extern "C" {
-hipError_t rm_gl_launch_pixels(const void* kparams, hipStream_t stream);
-hipError_t rm_gl_launch_probe(const void* probe_params, hipStream_t stream);
-hipError_t rm_gl_launch_sdf_grid(const void* grid_params, hipStream_t stream);
-hipError_t rm_gl_launch_mesh_occlusion(const void* occlusion_params, hipStream_t stream);
-hipError_t rm_gl_launch_mesh_project_eval(const void* eval_params, hipStream_t stream);
-hipError_t rm_gl_launch_mesh_deviation_eval(const void* eval_params, hipStream_t stream);
 hipError_t rm_gl_launch_math_probe(int fn, const float* a, const float* b, int n, float* out, hipStream_t stream);
 hipError_t rm_gl_launch_camera_rng(const RmUniforms* u, int W, int H, int what, int count, float* out, hipStream_t stream);
 hipError_t rm_gl_launch_present(const float4* color, const void* normal_dof, bool nd_half, int W, int H, float brightness, uchar4* out, hipStream_t stream);
@@ -384,6 +392,18 @@ static int scene_check(const Refuse& refuse, const rm_scene* scene, bool others)
   if (!refuse.ctx || !scene || !others) return refuse("NULL argument");
   if (scene->ctx != refuse.ctx) return refuse("the scene belongs to another context");
   return RM_OK;
+}
+
+// A host vector of the call's own that a mesh entry (rm_mesh_host.inc) reads its work back into, so that a refusal writes nothing of the
+// caller's: sized before anything is enqueued; false when the host has no memory for it.
+template <class T>
+static bool host_staging(std::vector<T>& v, size_t n) {
+  try {
+    v.resize(n);
+  } catch (const std::bad_alloc&) {
+    return false;
+  }
+  return true;
 }
 
 extern "C" {
@@ -1287,6 +1307,14 @@ static int scene_cull_grid(rm_ctx* ctx, rm_scene* s, int flags, long long pixels
   return RM_OK;
 }
 
+// The scene block a pass gets for its flags (behind scene_cull_grid, where the pass obtains the grid): the scene's own, without the culling
+// grid's cells under RM_RENDER_NO_CULL.
+static DevScene scene_view(const rm_scene* scene, int flags) {
+  DevScene view = scene->dev;
+  if (flags & RM_RENDER_NO_CULL) view.cull.cells = nullptr;
+  return view;
+}
+
 int rm_ctx_set_cull_min_pixels(rm_ctx* ctx, long long pixels) {
   if (!ctx) return RM_ERR_INVALID;
   if (pixels < 0) return fail(ctx, RM_ERR_INVALID, "rm_ctx_set_cull_min_pixels: pixels must be >= 0");
@@ -1360,7 +1388,7 @@ static int build_params(rm_ctx* ctx, rm_scene* scene, rm_fb* fb, const RmUniform
   *empty = x1 <= x0 || l1 <= l0;
   if (int rc = scene_cull_grid(ctx, scene, flags, *empty ? 0ll : job_pixel_samples(fb, x1 - x0, l1 - l0))) return rc;
   P->u = *u;
-  P->scene = scene->dev;
+  P->scene = scene_view(scene, flags);
   P->color = fb->plane[0];
   P->normal_dof = color_only ? nullptr : fb->plane[1];
   P->albedo_depth = color_only ? nullptr : fb->plane[2];
@@ -1379,7 +1407,6 @@ static int build_params(rm_ctx* ctx, rm_scene* scene, rm_fb* fb, const RmUniform
   P->gbuffer_half = fb->gbuffer == RM_GBUFFER_F16 ? 1 : 0;
   P->moments = color_only ? nullptr : fb->moments;  // blended by rm_combine_kernel, so only behind a staged launch (launch)
   if (P->no_far_jump) P->scene.far_end = 0, P->scene.clear_rho = 0.0f;  // the far-field shortcuts inside an evaluation (KIFS tree) read the scene block
-  if (flags & RM_RENDER_NO_CULL) P->scene.cull.cells = nullptr;
   return RM_OK;
 }
 
@@ -1430,7 +1457,7 @@ static size_t staging_budget(rm_ctx* ctx) {
 
 // the pixel kernel in the build the flags and the context ask for
 static hipError_t launch_pixel_kernel(const rm_ctx* ctx, const KParams& P, int flags, hipStream_t stream) {
-  return (flags & RM_RENDER_FAST) ? rm::launch_pixels_fast(P, stream) : ctx->gl_stack ? rm_gl_launch_pixels(&P, stream) : rm::launch_pixels_strict(P, stream);
+  return RM_SCENE_PASS(ctx, flags, launch_pixels, P, stream);
 }
 
 // Cost order on a sample-in-flight slot: the costs are sorted on the slot's own stream right AFTER the render (sort_slot_costs, called once the render's
@@ -2297,13 +2324,12 @@ int rm_present_sharded(rm_ctx* const* ctxs, rm_fb* const* fbs, int parts, int sa
 
 // ---- probes ----------------------------------------------------------------------
 
-// One probe launch on device arrays: the scene block as the flags shape it, and the unit the flags and the context select.  rm_probe's, and
-// the mesh entries' for the normals and colours of a mesh (rm_mesh_host.inc).
+// One probe launch on device arrays: the scene as the flags shape it, in the unit the flags and the context select.  rm_probe's, and the
+// mesh entries' for the normals and colours of a mesh (rm_mesh_host.inc).
 static hipError_t probe_enqueue(rm_ctx* ctx, rm_scene* scene, int what, const float* d_in, float* d_out, int n, float param, int flags, hipStream_t stream) {
-  ProbeParams P{scene->dev, d_in, d_out, n, what, param, (flags & RM_RENDER_FAST) ? ctx->retire_eps : 0.0f, (flags & RM_RENDER_NO_FAR_JUMP) ? 1 : 0};
+  ProbeParams P{scene_view(scene, flags), d_in, d_out, n, what, param, (flags & RM_RENDER_FAST) ? ctx->retire_eps : 0.0f, (flags & RM_RENDER_NO_FAR_JUMP) ? 1 : 0};
   if (P.no_far_jump) P.scene.far_end = 0, P.scene.clear_rho = 0.0f;
-  if (flags & RM_RENDER_NO_CULL) P.scene.cull.cells = nullptr;
-  return (flags & RM_RENDER_FAST) ? rm::launch_probe_fast(P, stream) : ctx->gl_stack ? rm_gl_launch_probe(&P, stream) : rm::launch_probe_strict(P, stream);
+  return RM_SCENE_PASS(ctx, flags, launch_probe, P, stream);
 }
 
 int rm_probe(rm_ctx* ctx, rm_scene* scene, int what, const float* in, int n, float param, int flags, float* out) {

@@ -2,7 +2,8 @@
 // (rm_device.hpp RM_GL_STACK: that stack's transcendental functions, rm_ss_math.hpp, and its min / max / fract / unorm
 // conventions; none of the IEEE-derived exact shortcuts).  Selected per context by rm_ctx_set_gl_stack; with it
 // rm_render_sample / rm_probe* / rm_present* on the strict flags reproduce tests/golden/ bit for bit on the GPU.
-// Everything of this unit lives in namespace rm_gl (the same sources as rm_strict.hip, renamed), behind C entry points.
+// Everything of this unit lives in namespace rm_gl (the same sources as rm_strict.hip, renamed).  rm_api.hip calls the scene passes'
+// launchers there directly (launch_pixels_strict, launch_probe_strict, ...); the rest sits behind the C entry points below.
 #define RM_BUILD_FAST 0
 #define RM_GL_STACK 1
 #undef RM_NORMAL_POLICY
@@ -15,18 +16,6 @@
 #undef rm
 
 extern "C" {
-hipError_t rm_gl_launch_pixels(const void* kparams, hipStream_t stream) { return rm_gl::launch_pixels_strict(*static_cast<const KParams*>(kparams), stream); }
-hipError_t rm_gl_launch_probe(const void* probe_params, hipStream_t stream) { return rm_gl::launch_probe_strict(*static_cast<const ProbeParams*>(probe_params), stream); }
-hipError_t rm_gl_launch_sdf_grid(const void* grid_params, hipStream_t stream) { return rm_gl::launch_sdf_grid_strict(*static_cast<const SdfGridParams*>(grid_params), stream); }
-hipError_t rm_gl_launch_mesh_occlusion(const void* occlusion_params, hipStream_t stream) {
-  return rm_gl::launch_mesh_occlusion_strict(*static_cast<const MeshOcclusionPass*>(occlusion_params), stream);
-}
-hipError_t rm_gl_launch_mesh_project_eval(const void* eval_params, hipStream_t stream) {
-  return rm_gl::launch_mesh_project_eval_strict(*static_cast<const MeshProjectEval*>(eval_params), stream);
-}
-hipError_t rm_gl_launch_mesh_deviation_eval(const void* eval_params, hipStream_t stream) {
-  return rm_gl::launch_mesh_deviation_eval_strict(*static_cast<const MeshDeviationSdf*>(eval_params), stream);
-}
 hipError_t rm_gl_launch_camera_rng(const RmUniforms* u, int W, int H, int what, int count, float* out, hipStream_t stream) {
   return rm_gl::launch_camera_rng(*u, W, H, what, count, out, stream);
 }

@@ -1190,29 +1190,32 @@ hipError_t launch_cull_build(const CullBuild& B, hipStream_t stream) {
 }
 #endif
 
-hipError_t RM_LAUNCH(launch_probe)(const ProbeParams& P, hipStream_t stream) {
-  const dim3 grid((P.n + 255) / 256);
-#define RM_PROBE_CASE(K) case K: hipLaunchKernelGGL((rm_probe_kernel<K, kFast>), grid, dim3(256), 0, stream, P); break;
-  if (P.scene.kind == RM_SCENE_TABLE && (P.scene.table_flags & RM_TABLE_HAS_KIND)) {
-    hipLaunchKernelGGL((rm_probe_kernel<RM_KIND_TABLE_KINDS, kFast>), grid, dim3(256), 0, stream, P);
-    return hipGetLastError();
-  }
-  if (P.scene.kind == RM_SCENE_TABLE && P.scene.nprims >= RM_TABLE_BIG_ROWS) {  // the march of the long tables' pixel kernels (their finer far-field exits)
-    hipLaunchKernelGGL((rm_probe_kernel<RM_KIND_TABLE_BIG, kFast>), grid, dim3(256), 0, stream, P);
-    return hipGetLastError();
-  }
-  switch (P.scene.kind) {
-    RM_PROBE_CASE(RM_SCENE_TABLE)
-    RM_PROBE_CASE(RM_SCENE_MANDELBULB)
-    RM_PROBE_CASE(RM_SCENE_SPHERE_GRID)
-    RM_PROBE_CASE(RM_SCENE_SPHERE_LATTICE)
-    RM_PROBE_CASE(RM_SCENE_MENGER)
-    RM_PROBE_CASE(RM_SCENE_KIFS_TREE)
-    RM_PROBE_CASE(RM_SCENE_KIFS_BOX)
+// The kind a kernel that evaluates the scene at points of its own runs as, stated once: the probe's, and so that of the mesh passes
+// (rm_mesh_kernels.inc), whose distances have to be the probe's at the same point.  `launch` is a generic lambda that starts its kernel for
+// the kind it is handed as a PointKind<K>.  (launch_pixels selects otherwise: RM_KIND_TABLE_SMOOTH, RM_KIND_BULB8 and the preview are its own.)
+template <int K>
+using PointKind = std::integral_constant<int, K>;
+template <class Launch>
+static hipError_t launch_point_kind(const DevScene& scene, Launch&& launch) {
+  const bool table = scene.kind == RM_SCENE_TABLE;
+  if (table && (scene.table_flags & RM_TABLE_HAS_KIND)) launch(PointKind<RM_KIND_TABLE_KINDS>{});
+  else if (table && scene.nprims >= RM_TABLE_BIG_ROWS) launch(PointKind<RM_KIND_TABLE_BIG>{});  // the march of the long tables' pixel kernels (their finer far-field exits)
+  else switch (scene.kind) {
+    case RM_SCENE_TABLE: launch(PointKind<RM_SCENE_TABLE>{}); break;
+    case RM_SCENE_MANDELBULB: launch(PointKind<RM_SCENE_MANDELBULB>{}); break;
+    case RM_SCENE_SPHERE_GRID: launch(PointKind<RM_SCENE_SPHERE_GRID>{}); break;
+    case RM_SCENE_SPHERE_LATTICE: launch(PointKind<RM_SCENE_SPHERE_LATTICE>{}); break;
+    case RM_SCENE_MENGER: launch(PointKind<RM_SCENE_MENGER>{}); break;
+    case RM_SCENE_KIFS_TREE: launch(PointKind<RM_SCENE_KIFS_TREE>{}); break;
+    case RM_SCENE_KIFS_BOX: launch(PointKind<RM_SCENE_KIFS_BOX>{}); break;
     default: return hipErrorInvalidValue;
   }
-#undef RM_PROBE_CASE
   return hipGetLastError();
+}
+
+hipError_t RM_LAUNCH(launch_probe)(const ProbeParams& P, hipStream_t stream) {
+  const dim3 grid((P.n + 255) / 256);
+  return launch_point_kind(P.scene, [&](auto kind) { hipLaunchKernelGGL((rm_probe_kernel<decltype(kind)::value, kFast>), grid, dim3(256), 0, stream, P); });
 }
 
 #if !RM_BUILD_FAST

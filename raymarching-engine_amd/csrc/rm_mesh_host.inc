@@ -24,6 +24,47 @@ struct rm_mesh {
 // `*out = made.release()` hands a finished one over.
 using MeshPtr = std::unique_ptr<rm_mesh, void (*)(rm_mesh*)>;
 
+// a max / worst key of the reports, bits(value) << 32 | (0xFFFFFFFF - index), maximised: the value, and the lowest index that has it
+static void mesh_key_decode(unsigned long long key, float* max, uint64_t* worst) {
+  const unsigned int bits = (unsigned int)(key >> 32);
+  std::memcpy(max, &bits, sizeof bits);
+  *worst = 0xFFFFFFFFull - (key & 0xFFFFFFFFull);
+}
+
+// The fixed tree of sums over n > 0 values of each of two lists (rm_mesh_measure, rm_mesh_project, rm_mesh_deviation), 256 to a group: level k
+// holds groups[k] values of each list, the last level one.  The levels of more than one value lie in scratch, one behind the other, a level's
+// first list and then its second: `elems` values per list, 2 * elems doubles per tree.  The level of one value is two neighbouring words, `out`.
+struct SumTree {
+  long long groups[8];  // (256^8 = 2^64)
+  size_t levels = 0, elems = 0;
+  explicit SumTree(long long n) {
+    for (long long g = (n + 255) / 256; n > 0; g = (g + 255) / 256) {
+      groups[levels++] = g;
+      if (g == 1) break;
+      elems += (size_t)g;
+    }
+  }
+  struct Lists { double *first, *second; };
+  Lists level(size_t k, double* scratch, double* out) const {
+    if (groups[k] == 1) return {out, out + 1};
+    for (size_t j = 0; j < k; j++) scratch += 2 * groups[j];
+    return {scratch, scratch + groups[k]};
+  }
+  // the lists (a, b) of n values each into level k, and on through every further level.  k = 0: from lists of the caller's own; k = 1: a
+  // kernel of the caller's has written level 0 itself, at level(0, ...).
+  hipError_t run(size_t k, const double* a, const double* b, long long n, double* scratch, double* out, hipStream_t stream) const {
+    for (; k < levels; k++) {
+      const Lists to = level(k, scratch, out);
+      const hipError_t e = rm::launch_mesh_measure_sum(a, b, n, to.first, to.second, stream);
+      if (e != hipSuccess) return e;
+      a = to.first;
+      b = to.second;
+      n = groups[k];
+    }
+    return hipSuccess;
+  }
+};
+
 static size_t mesh_array_bytes(const rm_mesh* m, int which) {
   if (which == MESH_SIZES) return (size_t)m->components * 8u;
   if (which == RM_MESH_TRIANGLES) return (size_t)m->triangles * 12u;
@@ -83,16 +124,15 @@ void rm_mesh_params_default(RmMeshParams* params) {
   *params = RmMeshParams{0.0f, 1, 1e-5f, 0, 0, 0};
 }
 
-// the sampler on `stream`, with the culling grid as rm_probe obtains it; plane0 > 0: G is a window of a grid's z planes that begins there
+// the sampler on `stream`, with the culling grid obtained as every scene pass obtains it; plane0 > 0: G is a window of a grid's z planes that begins there
 static int sdf_grid_enqueue(const Refuse& refuse, rm_scene* scene, const GridDims& G, int flags, float* d_out, hipStream_t stream, int plane0 = 0) {
   rm_ctx* ctx = refuse.ctx;
   RM_HIP(ctx, hipSetDevice(ctx->device));
   if (int rc = scene_cull_grid(ctx, scene, flags, 1ll << 40)) return rc;
   const bool foreign = stream != ctx->stream;
   if (foreign && ctx->cull_event) RM_HIP(ctx, hipStreamWaitEvent(stream, ctx->cull_event, 0));  // (the grid is built on a stream of its own)
-  SdfGridParams P{scene->dev, G, d_out, plane0};
-  if (flags & RM_RENDER_NO_CULL) P.scene.cull.cells = nullptr;
-  RM_HIP_AS(refuse, (flags & RM_RENDER_FAST) ? rm::launch_sdf_grid_fast(P, stream) : ctx->gl_stack ? rm_gl_launch_sdf_grid(&P, stream) : rm::launch_sdf_grid_strict(P, stream));
+  const SdfGridParams P{scene_view(scene, flags), G, d_out, plane0};
+  RM_HIP_AS(refuse, RM_SCENE_PASS(ctx, flags, launch_sdf_grid, P, stream));
   if (foreign) {
     // Everything that gives a scene's table or culling grid up -- rm_scene_destroy, the grids' budget (cull_release, cull_order) -- orders itself
     // behind the CONTEXT's stream: so that stream waits behind this launch, on the device, and the caller's stream needs no care of the host's.
@@ -274,53 +314,6 @@ static int mesh_sharp_check(const Refuse& refuse, const RmMeshSharp* in, RmMeshS
   return RM_OK;
 }
 
-// rm_mesh_extract and rm_mesh_extract_sharp: `sharpen` tells them apart, `sharp` (NULL = the defaults) is looked at only with it
-static int mesh_extract(const Refuse& refuse, rm_scene* scene, const RmGrid* grid, const RmMeshParams* params, bool sharpen, const RmMeshSharp* sharp, rm_mesh** out) {
-  rm_ctx* ctx = refuse.ctx;
-  GridDims G{};
-  RmMeshParams p;
-  RmMeshSharp s{};
-  if (int rc = grid_check(refuse, grid, &G)) return rc;
-  if (int rc = mesh_params_check(refuse, params, &p)) return rc;
-  if (sharpen)
-    if (int rc = mesh_sharp_check(refuse, sharp, &s)) return rc;
-  if (int rc = scene_check(refuse, scene, out != nullptr)) return rc;
-  *out = nullptr;
-  RM_HIP(ctx, hipSetDevice(ctx->device));
-  DeviceArray values, material;  // (before the mesh: freed behind the wait of whatever gives the mesh up, or the one below)
-  SharpScratch sharp_tmp;
-  RM_HIP(ctx, values.reserve(sizeof(float) * (size_t)G.corners));
-  RM_HIP(ctx, ctx->mesh_spans.begin(MeshSpans::SAMPLE, ctx->stream));
-  if (int rc = sdf_grid_enqueue(refuse, scene, G, p.flags, values.f32(), ctx->stream)) return rc;
-  RM_HIP(ctx, ctx->mesh_spans.end(MeshSpans::SAMPLE, ctx->stream));
-  MeshPtr made(new (std::nothrow) rm_mesh(ctx), rm_mesh_destroy);
-  if (!made) return refuse("out of host memory", RM_ERR_DEVICE);
-  made->has[RM_MESH_NORMALS] = p.normals != 0;
-  made->has[RM_MESH_COLOURS] = p.colours != 0;
-  if (int rc = mesh_build(ctx, G, values.f32(), p.iso, made.get())) return rc;
-  if (sharpen && made->vertices > 0) {
-    if (int rc = mesh_sharp_fits(refuse, made->vertices)) return rc;
-    RM_HIP(ctx, sharp_tmp.reserve((size_t)made->vertices));
-    if (int rc = mesh_sharpen(refuse, scene, G, values.f32(), 0, p, s, made.get(), 0, made->vertices, sharp_tmp)) return rc;
-  }
-  const bool attributes = made->vertices > 0 && (p.normals || p.colours);
-  if (attributes)
-    if (int rc = mesh_attributes(ctx, scene, p, made.get(), material)) return rc;
-  if (hipStreamSynchronize(ctx->stream) != hipSuccess) return refuse("the stream failed", RM_ERR_DEVICE);
-  made->ms[0] = ctx->mesh_spans.ms(MeshSpans::SAMPLE);
-  if (attributes) made->ms[2] = ctx->mesh_spans.ms(MeshSpans::ATTRIBUTES);
-  *out = made.release();
-  return RM_OK;
-}
-
-int rm_mesh_extract(rm_ctx* ctx, rm_scene* scene, const RmGrid* grid, const RmMeshParams* params, rm_mesh** out) {
-  return mesh_extract(Refuse{ctx, "rm_mesh_extract"}, scene, grid, params, false, nullptr, out);
-}
-
-int rm_mesh_extract_sharp(rm_ctx* ctx, rm_scene* scene, const RmGrid* grid, const RmMeshParams* params, const RmMeshSharp* sharp, rm_mesh** out) {
-  return mesh_extract(Refuse{ctx, "rm_mesh_extract_sharp"}, scene, grid, params, true, sharp, out);
-}
-
 // ---- slabbed extraction (include/hip_raymarch.h "slabbed extraction") ------------------------------------------------------------------
 
 static const long long kMeshSlabWindow = 1ll << 26;  // the default budget of window corners (profiles/mesh_slabs.txt)
@@ -456,45 +449,72 @@ static int mesh_build_slabs(const Refuse& refuse, rm_scene* scene, const float* 
   return RM_OK;
 }
 
-// rm_mesh_extract_slabs and rm_mesh_extract_sharp_slabs: mesh_extract's checks with the slabs' behind them, then mesh_build_slabs
-static int mesh_extract_slabs(const Refuse& refuse, rm_scene* scene, const RmGrid* grid, const RmMeshParams* params, bool sharpen, const RmMeshSharp* sharp,
-                              const RmMeshSlabs* slabs, rm_mesh** out) {
+// rm_mesh_extract and rm_mesh_extract_sharp, and with `slabbed` rm_mesh_extract_slabs and rm_mesh_extract_sharp_slabs.  `sharpen` tells the
+// sharp ones apart; `sharp` and `slabs` (NULL = the defaults) are looked at only with their flags.  Slabbed: the grid's corners are not
+// bounded, the slabs' check stands behind the others', and mesh_build_slabs samples, meshes and sharpens window by window.
+static int mesh_extract(const Refuse& refuse, rm_scene* scene, const RmGrid* grid, const RmMeshParams* params, bool sharpen, const RmMeshSharp* sharp,
+                        bool slabbed, const RmMeshSlabs* slabs, rm_mesh** out) {
   rm_ctx* ctx = refuse.ctx;
   GridDims G{};
   RmMeshParams p;
   RmMeshSharp s{};
   int layers = 0;
-  if (int rc = grid_check(refuse, grid, &G, false)) return rc;
+  if (int rc = grid_check(refuse, grid, &G, !slabbed)) return rc;
   if (int rc = mesh_params_check(refuse, params, &p)) return rc;
   if (sharpen)
     if (int rc = mesh_sharp_check(refuse, sharp, &s)) return rc;
-  if (int rc = mesh_slabs_check(refuse, slabs, G, &layers)) return rc;
+  if (slabbed)
+    if (int rc = mesh_slabs_check(refuse, slabs, G, &layers)) return rc;
   if (int rc = scene_check(refuse, scene, out != nullptr)) return rc;
   *out = nullptr;
   RM_HIP(ctx, hipSetDevice(ctx->device));
-  SlabScratch tmp;  // (before the mesh: freed behind the wait of whatever gives the mesh up, or the one below)
+  SlabScratch tmp;  // (before the mesh: freed behind the wait of whatever gives the mesh up, or the one below); unslabbed: its values and sharp alone
   DeviceArray material;
+  if (!slabbed) {
+    RM_HIP(ctx, tmp.values.reserve(sizeof(float) * (size_t)G.corners));
+    RM_HIP(ctx, ctx->mesh_spans.begin(MeshSpans::SAMPLE, ctx->stream));
+    if (int rc = sdf_grid_enqueue(refuse, scene, G, p.flags, tmp.values.f32(), ctx->stream)) return rc;
+    RM_HIP(ctx, ctx->mesh_spans.end(MeshSpans::SAMPLE, ctx->stream));
+  }
   MeshPtr made(new (std::nothrow) rm_mesh(ctx), rm_mesh_destroy);
   if (!made) return refuse("out of host memory", RM_ERR_DEVICE);
   made->has[RM_MESH_NORMALS] = p.normals != 0;
   made->has[RM_MESH_COLOURS] = p.colours != 0;
-  if (int rc = mesh_build_slabs(refuse, scene, nullptr, G, layers, p, sharpen ? &s : nullptr, tmp, made.get())) return rc;
+  if (slabbed) {
+    if (int rc = mesh_build_slabs(refuse, scene, nullptr, G, layers, p, sharpen ? &s : nullptr, tmp, made.get())) return rc;
+  } else {
+    if (int rc = mesh_build(ctx, G, tmp.values.f32(), p.iso, made.get())) return rc;
+    if (sharpen && made->vertices > 0) {
+      if (int rc = mesh_sharp_fits(refuse, made->vertices)) return rc;
+      RM_HIP(ctx, tmp.sharp.reserve((size_t)made->vertices));
+      if (int rc = mesh_sharpen(refuse, scene, G, tmp.values.f32(), 0, p, s, made.get(), 0, made->vertices, tmp.sharp)) return rc;
+    }
+  }
   const bool attributes = made->vertices > 0 && (p.normals || p.colours);
   if (attributes)
     if (int rc = mesh_attributes(ctx, scene, p, made.get(), material)) return rc;
   if (hipStreamSynchronize(ctx->stream) != hipSuccess) return refuse("the stream failed", RM_ERR_DEVICE);
+  if (!slabbed) made->ms[0] = ctx->mesh_spans.ms(MeshSpans::SAMPLE);  // (slabbed: mesh_build_slabs has summed its windows')
   if (attributes) made->ms[2] = ctx->mesh_spans.ms(MeshSpans::ATTRIBUTES);
   *out = made.release();
   return RM_OK;
 }
 
+int rm_mesh_extract(rm_ctx* ctx, rm_scene* scene, const RmGrid* grid, const RmMeshParams* params, rm_mesh** out) {
+  return mesh_extract(Refuse{ctx, "rm_mesh_extract"}, scene, grid, params, false, nullptr, false, nullptr, out);
+}
+
+int rm_mesh_extract_sharp(rm_ctx* ctx, rm_scene* scene, const RmGrid* grid, const RmMeshParams* params, const RmMeshSharp* sharp, rm_mesh** out) {
+  return mesh_extract(Refuse{ctx, "rm_mesh_extract_sharp"}, scene, grid, params, true, sharp, false, nullptr, out);
+}
+
 int rm_mesh_extract_slabs(rm_ctx* ctx, rm_scene* scene, const RmGrid* grid, const RmMeshParams* params, const RmMeshSlabs* slabs, rm_mesh** out) {
-  return mesh_extract_slabs(Refuse{ctx, "rm_mesh_extract_slabs"}, scene, grid, params, false, nullptr, slabs, out);
+  return mesh_extract(Refuse{ctx, "rm_mesh_extract_slabs"}, scene, grid, params, false, nullptr, true, slabs, out);
 }
 
 int rm_mesh_extract_sharp_slabs(rm_ctx* ctx, rm_scene* scene, const RmGrid* grid, const RmMeshParams* params, const RmMeshSharp* sharp,
                                 const RmMeshSlabs* slabs, rm_mesh** out) {
-  return mesh_extract_slabs(Refuse{ctx, "rm_mesh_extract_sharp_slabs"}, scene, grid, params, true, sharp, slabs, out);
+  return mesh_extract(Refuse{ctx, "rm_mesh_extract_sharp_slabs"}, scene, grid, params, true, sharp, true, slabs, out);
 }
 
 int rm_mesh_from_values_slabs(rm_ctx* ctx, const RmGrid* grid, const float* values_host, float iso, const RmMeshSlabs* slabs, rm_mesh** out) {
@@ -961,11 +981,10 @@ int rm_mesh_occlusion(rm_mesh* mesh, rm_scene* scene, const RmMeshOcclusion* par
   RM_HIP_AS(refuse, d0.reserve(sizeof(float) * V));
   RM_HIP_AS(refuse, directions.reserve(sizeof(float) * 4u * (size_t)p.directions));
   RM_HIP_AS(refuse, ao.reserve(sizeof(float) * V));
-  if (int rc = scene_cull_grid(ctx, scene, p.flags, 1ll << 40)) return rc;  // (with the grid, as rm_probe obtains it)
+  if (int rc = scene_cull_grid(ctx, scene, p.flags, 1ll << 40)) return rc;
   const float* positions = mesh->array[RM_MESH_POSITIONS].f32();
   MeshOcclusionPass P{};
-  P.scene = scene->dev;
-  if (p.flags & RM_RENDER_NO_CULL) P.scene.cull.cells = nullptr;
+  P.scene = scene_view(scene, p.flags);
   P.positions = positions;
   P.normals = normals.f32();
   P.d0 = d0.f32();
@@ -985,9 +1004,7 @@ int rm_mesh_occlusion(rm_mesh* mesh, rm_scene* scene, const RmMeshOcclusion* par
   RM_HIP_AS(refuse, probe_enqueue(ctx, scene, RM_PROBE_SDF, positions, d0.f32(), (int)V, 0.0f, p.flags, ctx->stream));
   RM_HIP_AS(refuse, spans.end(MeshSpans::OCCLUSION_PROBES, ctx->stream));
   RM_HIP_AS(refuse, spans.begin(MeshSpans::OCCLUSION_TAPS, ctx->stream));
-  RM_HIP_AS(refuse, (p.flags & RM_RENDER_FAST) ? rm::launch_mesh_occlusion_fast(P, ctx->stream)
-                    : ctx->gl_stack           ? rm_gl_launch_mesh_occlusion(&P, ctx->stream)
-                                              : rm::launch_mesh_occlusion_strict(P, ctx->stream));
+  RM_HIP_AS(refuse, RM_SCENE_PASS(ctx, p.flags, launch_mesh_occlusion, P, ctx->stream));
   RM_HIP_AS(refuse, spans.end(MeshSpans::OCCLUSION_TAPS, ctx->stream));
   if (int rc = copy_and_wait(ctx, out_host, ao.p, sizeof(float) * V, hipMemcpyDeviceToHost)) return rc;
   if (out_ms2) {
@@ -1028,29 +1045,18 @@ static int mesh_measure(const Refuse& refuse, rm_mesh* mesh, float* ms2) {
   if (V == 0) {
     m.skipped_triangles = T;  // (no index is < 0 vertices)
   } else {
-    try {
-      rows.resize(4 * (size_t)C);
-    } catch (const std::bad_alloc&) {
-      return refuse("out of host memory", RM_ERR_DEVICE);
-    }
+    if (!host_staging(rows, 4 * (size_t)C)) return refuse("out of host memory", RM_ERR_DEVICE);
     unsigned long long slots = 0;
     if (T > 0)
       for (slots = 1ull; slots < 4ull * T; slots <<= 1) {}
-    // the tree's levels behind the first: groups[k] values each of area and volume; the level of one value is the totals' own two words
-    std::vector<long long> groups;
-    size_t level_elems = 0;
-    for (long long g = ((long long)T + 255) / 256; T > 0; g = (g + 255) / 256) {
-      groups.push_back(g);
-      if (g == 1) break;
-      level_elems += (size_t)g;
-    }
+    const SumTree tree((long long)T);  // of area and volume: the terms kernel writes level 0, the level of one value is the totals' own two words
     DeviceArray keys, counts, used, totals, d_rows, levels;
     RM_HIP_AS(refuse, keys.reserve(sizeof(unsigned long long) * (size_t)slots));
     RM_HIP_AS(refuse, counts.reserve(sizeof(unsigned long long) * (size_t)slots));
     RM_HIP_AS(refuse, used.reserve(sizeof(unsigned int) * (size_t)V));
     RM_HIP_AS(refuse, totals.reserve(sizeof(unsigned long long) * rm::RM_MEASURE_WORDS));
     RM_HIP_AS(refuse, d_rows.reserve(sizeof(unsigned long long) * 4u * (size_t)C));
-    RM_HIP_AS(refuse, levels.reserve(sizeof(double) * 2u * level_elems));
+    RM_HIP_AS(refuse, levels.reserve(sizeof(double) * 2u * tree.elems));
     unsigned long long first[rm::RM_MEASURE_WORDS] = {};
     const unsigned int identities[6] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0u, 0u, 0u};
     std::memcpy(first + rm::RM_MEASURE_EXTENT, identities, sizeof identities);
@@ -1066,8 +1072,8 @@ static int mesh_measure(const Refuse& refuse, rm_mesh* mesh, float* ms2) {
     M.used = used.u32();
     M.totals = totals.u64();
     M.rows = d_rows.u64();
-    double* const d_area = reinterpret_cast<double*>(M.totals + rm::RM_MEASURE_AREA);
-    double* const d_volume = reinterpret_cast<double*>(M.totals + rm::RM_MEASURE_VOLUME);
+    static_assert(rm::RM_MEASURE_VOLUME == rm::RM_MEASURE_AREA + 1, "the tree's two sums are neighbours");
+    double* const d_sums = reinterpret_cast<double*>(M.totals + rm::RM_MEASURE_AREA);
     MeshSpans& spans = ctx->mesh_spans;
     RM_HIP_AS(refuse, hipMemcpyAsync(totals.p, first, sizeof first, hipMemcpyHostToDevice, ctx->stream));
     RM_HIP_AS(refuse, spans.begin(MeshSpans::MEASURE_TOPOLOGY, ctx->stream));
@@ -1084,15 +1090,9 @@ static int mesh_measure(const Refuse& refuse, rm_mesh* mesh, float* ms2) {
     RM_HIP_AS(refuse, spans.begin(MeshSpans::MEASURE_GEOMETRY, ctx->stream));
     RM_HIP_AS(refuse, rm::launch_mesh_measure_extent(M, ctx->stream));
     if (T > 0) {
-      double* from = static_cast<double*>(levels.p);  // a level's area values, its volume values behind them
-      const bool only = groups[0] == 1;
-      RM_HIP_AS(refuse, rm::launch_mesh_measure_terms(M, only ? d_area : from, only ? d_volume : from + groups[0], ctx->stream));
-      for (size_t k = 1; k < groups.size(); k++) {
-        const bool last = groups[k] == 1;
-        double* to = from + 2 * groups[k - 1];
-        RM_HIP_AS(refuse, rm::launch_mesh_measure_sum(from, from + groups[k - 1], groups[k - 1], last ? d_area : to, last ? d_volume : to + groups[k], ctx->stream));
-        from = to;
-      }
+      const SumTree::Lists terms = tree.level(0, static_cast<double*>(levels.p), d_sums);
+      RM_HIP_AS(refuse, rm::launch_mesh_measure_terms(M, terms.first, terms.second, ctx->stream));
+      RM_HIP_AS(refuse, tree.run(1, terms.first, terms.second, tree.groups[0], static_cast<double*>(levels.p), d_sums, ctx->stream));
     }
     RM_HIP_AS(refuse, spans.end(MeshSpans::MEASURE_GEOMETRY, ctx->stream));
     unsigned long long got[rm::RM_MEASURE_WORDS] = {};
@@ -1196,14 +1196,7 @@ int rm_mesh_project(rm_mesh* mesh, rm_scene* scene, const RmMeshProject* params,
   }
   made->vertices = V;
   made->triangles = T;
-  // the tree's levels behind the first, as rm_mesh_measure lays them out: groups[k] values each of the two lists
-  std::vector<long long> groups;
-  size_t level_elems = 0;
-  for (long long g = ((long long)V + 255) / 256;; g = (g + 255) / 256) {
-    groups.push_back(g);
-    if (g == 1) break;
-    level_elems += (size_t)g;
-  }
+  const SumTree tree((long long)V);  // of a report half's two sums: the step kernel writes level 0
   for (int what : {RM_MESH_POSITIONS, RM_MESH_NORMALS, RM_MESH_COLOURS, RM_MESH_TRIANGLES, RM_MESH_CELLS})
     if (mesh->array[what].p) RM_HIP_AS(refuse, made->array[what].reserve(mesh_array_bytes(made.get(), what)));
   RM_HIP_AS(refuse, d.reserve(sizeof(float) * (size_t)V));
@@ -1211,15 +1204,14 @@ int rm_mesh_project(rm_mesh* mesh, rm_scene* scene, const RmMeshProject* params,
   RM_HIP_AS(refuse, flags.reserve(sizeof(unsigned int) * (size_t)V));
   RM_HIP_AS(refuse, residual.reserve(sizeof(float) * (size_t)V));
   RM_HIP_AS(refuse, totals.reserve(sizeof(unsigned long long) * rm::RM_PROJECT_WORDS));
-  RM_HIP_AS(refuse, levels.reserve(sizeof(double) * 2u * level_elems));
-  if (int rc = scene_cull_grid(ctx, scene, p.flags, 1ll << 40)) return rc;  // (with the grid, as rm_probe obtains it)
+  RM_HIP_AS(refuse, levels.reserve(sizeof(double) * 2u * tree.elems));
+  if (int rc = scene_cull_grid(ctx, scene, p.flags, 1ll << 40)) return rc;
   for (int what : {RM_MESH_POSITIONS, RM_MESH_COLOURS, RM_MESH_TRIANGLES, RM_MESH_CELLS})
     if (mesh->array[what].p)
       RM_HIP_AS(refuse, hipMemcpyAsync(made->array[what].p, mesh->array[what].p, mesh_array_bytes(made.get(), what), hipMemcpyDeviceToDevice, ctx->stream));
   float* positions = made->array[RM_MESH_POSITIONS].f32();
   MeshProjectEval E{};
-  E.scene = scene->dev;
-  if (p.flags & RM_RENDER_NO_CULL) E.scene.cull.cells = nullptr;
+  E.scene = scene_view(scene, p.flags);
   E.positions = positions;
   E.d = d.f32();
   E.normals = normals.f32();
@@ -1244,16 +1236,10 @@ int rm_mesh_project(rm_mesh* mesh, rm_scene* scene, const RmMeshProject* params,
   S.reach = p.reach;
   // a half of the report: the step kernel's first level, then the further levels into the half's two words of the totals
   const auto report_half = [&](int round, int word) -> int {
-    double* const d_sum = reinterpret_cast<double*>(S.totals + word);
-    double* from = static_cast<double*>(levels.p);
-    const bool only = groups[0] == 1;
-    RM_HIP_AS(refuse, rm::launch_mesh_project_step(S, round, only ? d_sum : from, only ? d_sum + 1 : from + groups[0], ctx->stream));
-    for (size_t k = 1; k < groups.size(); k++) {
-      const bool last = groups[k] == 1;
-      double* to = from + 2 * groups[k - 1];
-      RM_HIP_AS(refuse, rm::launch_mesh_measure_sum(from, from + groups[k - 1], groups[k - 1], last ? d_sum : to, last ? d_sum + 1 : to + groups[k], ctx->stream));
-      from = to;
-    }
+    double* const d_sums = reinterpret_cast<double*>(S.totals + word);
+    const SumTree::Lists sums = tree.level(0, static_cast<double*>(levels.p), d_sums);
+    RM_HIP_AS(refuse, rm::launch_mesh_project_step(S, round, sums.first, sums.second, ctx->stream));
+    RM_HIP_AS(refuse, tree.run(1, sums.first, sums.second, tree.groups[0], static_cast<double*>(levels.p), d_sums, ctx->stream));
     return RM_OK;
   };
   MeshSpans& spans = ctx->mesh_spans;
@@ -1263,9 +1249,7 @@ int rm_mesh_project(rm_mesh* mesh, rm_scene* scene, const RmMeshProject* params,
   unsigned long long moved = 0;
   int rounds_run = 0;
   for (int round = 0; round < p.rounds; round++) {
-    RM_HIP_AS(refuse, (p.flags & RM_RENDER_FAST) ? rm::launch_mesh_project_eval_fast(E, ctx->stream)
-                      : ctx->gl_stack           ? rm_gl_launch_mesh_project_eval(&E, ctx->stream)
-                                                : rm::launch_mesh_project_eval_strict(E, ctx->stream));
+    RM_HIP_AS(refuse, RM_SCENE_PASS(ctx, p.flags, launch_mesh_project_eval, E, ctx->stream));
     if (round == 0) {
       if (int rc = report_half(0, rm::RM_PROJECT_SUM_BEFORE)) return rc;
     } else {
@@ -1289,11 +1273,7 @@ int rm_mesh_project(rm_mesh* mesh, rm_scene* scene, const RmMeshProject* params,
   unsigned long long got[rm::RM_PROJECT_WORDS] = {};
   std::vector<float> e_after;
   if (residual_host) {  // (through a buffer of the call's own: a refusal below writes nothing of the caller's)
-    try {
-      e_after.resize((size_t)V);
-    } catch (const std::bad_alloc&) {
-      return refuse("out of host memory", RM_ERR_DEVICE);
-    }
+    if (!host_staging(e_after, (size_t)V)) return refuse("out of host memory", RM_ERR_DEVICE);
     RM_HIP_AS(refuse, hipMemcpyAsync(e_after.data(), residual.p, sizeof(float) * (size_t)V, hipMemcpyDeviceToHost, ctx->stream));
   }
   if (int rc = copy_and_wait(ctx, got, totals.p, sizeof got, hipMemcpyDeviceToHost)) return rc;
@@ -1313,9 +1293,7 @@ int rm_mesh_project(rm_mesh* mesh, rm_scene* scene, const RmMeshProject* params,
   const auto half = [&](int key_word, int sum_word, unsigned long long nonfinite, uint64_t* worst, float* max, double* mean, double* rms) {
     const unsigned long long key = got[key_word], count = V - nonfinite;
     if (key == 0ull || count == 0ull) return;  // no finite e: everything stays 0
-    const unsigned int bits = (unsigned int)(key >> 32);
-    std::memcpy(max, &bits, sizeof bits);
-    *worst = 0xFFFFFFFFull - (key & 0xFFFFFFFFull);
+    mesh_key_decode(key, max, worst);
     double sum, sum2;
     std::memcpy(&sum, got + sum_word, sizeof sum);
     std::memcpy(&sum2, got + sum_word + 1, sizeof sum2);
@@ -1401,21 +1379,10 @@ int rm_mesh_deviation(rm_mesh* mesh, rm_scene* scene, const RmMeshDeviation* par
     return refuse("the mesh has more triangles than the kernels' index holds samples of (T * S >= 2^31)", RM_ERR_DEVICE);
   float table[64 * 4];
   deviation_weights(p.order, table);
-  // the levels of the two pairs' trees behind the terms: groups[k] values of each list; the level of one value is the totals' own words
-  std::vector<long long> groups;
-  size_t level_elems = 0;
-  for (long long g = ((long long)T + 255) / 256;; g = (g + 255) / 256) {
-    groups.push_back(g);
-    if (g == 1) break;
-    level_elems += (size_t)g;
-  }
+  const SumTree tree((long long)T);  // of each of the two pairs of terms, from the reducer's lists on
   std::vector<float> max_host;
   if (triangles_host) {  // (through a buffer of the call's own: a refusal below writes nothing of the caller's)
-    try {
-      max_host.resize((size_t)T);
-    } catch (const std::bad_alloc&) {
-      return refuse("out of host memory", RM_ERR_DEVICE);
-    }
+    if (!host_staging(max_host, (size_t)T)) return refuse("out of host memory", RM_ERR_DEVICE);
   }
   RM_HIP(ctx, hipSetDevice(ctx->device));
   DeviceArray d, weights, triangle_max, terms, levels, totals;  // (freed behind the wait of the copy below; a call that fails before it leaves that wait to hipFree)
@@ -1423,13 +1390,12 @@ int rm_mesh_deviation(rm_mesh* mesh, rm_scene* scene, const RmMeshDeviation* par
   RM_HIP_AS(refuse, weights.reserve(sizeof(float) * 4u * (size_t)S));
   RM_HIP_AS(refuse, triangle_max.reserve(sizeof(float) * (size_t)T));
   RM_HIP_AS(refuse, terms.reserve(sizeof(double) * 4u * (size_t)T));
-  RM_HIP_AS(refuse, levels.reserve(sizeof(double) * 4u * level_elems));
+  RM_HIP_AS(refuse, levels.reserve(sizeof(double) * 4u * tree.elems));
   constexpr size_t kTotalsWords = (size_t)rm::RM_DEVIATION_COPIES * rm::RM_DEVIATION_WORDS;
   RM_HIP_AS(refuse, totals.reserve(sizeof(unsigned long long) * kTotalsWords));
-  if (int rc = scene_cull_grid(ctx, scene, p.flags, 1ll << 40)) return rc;  // (with the grid, as rm_probe obtains it)
+  if (int rc = scene_cull_grid(ctx, scene, p.flags, 1ll << 40)) return rc;
   MeshDeviationSdf E{};
-  E.scene = scene->dev;
-  if (p.flags & RM_RENDER_NO_CULL) E.scene.cull.cells = nullptr;
+  E.scene = scene_view(scene, p.flags);
   E.positions = mesh->array[RM_MESH_POSITIONS].f32();
   E.corners = mesh->array[RM_MESH_TRIANGLES].u32();
   E.weights = static_cast<const float4*>(weights.p);
@@ -1449,35 +1415,21 @@ int rm_mesh_deviation(rm_mesh* mesh, rm_scene* scene, const RmMeshDeviation* par
   D.totals = totals.u64();
   D.iso = p.iso;
   D.tolerance = p.tolerance;
-  // one pair of lists through every level of the fixed tree, into two neighbouring words of the totals
-  const auto tree = [&](const double* list, double* level, int word) -> int {
-    double* const out = reinterpret_cast<double*>(D.totals + word);
-    const double *from0 = list, *from1 = list + (size_t)T;
-    long long n = (long long)T;
-    for (size_t k = 0; k < groups.size(); k++) {
-      const bool last = groups[k] == 1;
-      double* to0 = last ? out : level;
-      double* to1 = last ? out + 1 : level + groups[k];
-      RM_HIP_AS(refuse, rm::launch_mesh_measure_sum(from0, from1, n, to0, to1, ctx->stream));
-      from0 = to0;
-      from1 = to1;
-      n = groups[k];
-      level += 2 * groups[k];
-    }
-    return RM_OK;
+  // one pair of the reducer's lists through every level of the tree, into two neighbouring words of copy 0 of the totals
+  const auto sum_pair = [&](int pair, int word) {
+    return tree.run(0, D.terms + 2 * (size_t)pair * (size_t)T, D.terms + (2 * (size_t)pair + 1) * (size_t)T, (long long)T,
+                    static_cast<double*>(levels.p) + 2 * (size_t)pair * tree.elems, reinterpret_cast<double*>(D.totals + word), ctx->stream);
   };
   MeshSpans& spans = ctx->mesh_spans;
   RM_HIP_AS(refuse, hipMemcpyAsync(weights.p, table, sizeof(float) * 4u * (size_t)S, hipMemcpyHostToDevice, ctx->stream));
   RM_HIP_AS(refuse, hipMemsetAsync(totals.p, 0, sizeof(unsigned long long) * kTotalsWords, ctx->stream));
   RM_HIP_AS(refuse, spans.begin(MeshSpans::DEVIATION_EVALUATE, ctx->stream));
-  RM_HIP_AS(refuse, (p.flags & RM_RENDER_FAST) ? rm::launch_mesh_deviation_eval_fast(E, ctx->stream)
-                    : ctx->gl_stack           ? rm_gl_launch_mesh_deviation_eval(&E, ctx->stream)
-                                              : rm::launch_mesh_deviation_eval_strict(E, ctx->stream));
+  RM_HIP_AS(refuse, RM_SCENE_PASS(ctx, p.flags, launch_mesh_deviation_eval, E, ctx->stream));
   RM_HIP_AS(refuse, spans.end(MeshSpans::DEVIATION_EVALUATE, ctx->stream));
   RM_HIP_AS(refuse, spans.begin(MeshSpans::DEVIATION_REDUCE, ctx->stream));
   RM_HIP_AS(refuse, rm::launch_mesh_deviation_reduce(D, ctx->stream));
-  if (int rc = tree(D.terms, static_cast<double*>(levels.p), rm::RM_DEVIATION_AREA)) return rc;
-  if (int rc = tree(D.terms + 2 * (size_t)T, static_cast<double*>(levels.p) + 2 * level_elems, rm::RM_DEVIATION_SUM1)) return rc;
+  RM_HIP_AS(refuse, sum_pair(0, rm::RM_DEVIATION_AREA));
+  RM_HIP_AS(refuse, sum_pair(1, rm::RM_DEVIATION_SUM1));
   RM_HIP_AS(refuse, spans.end(MeshSpans::DEVIATION_REDUCE, ctx->stream));
   if (triangles_host) RM_HIP_AS(refuse, hipMemcpyAsync(max_host.data(), triangle_max.p, sizeof(float) * (size_t)T, hipMemcpyDeviceToHost, ctx->stream));
   static_assert(kTotalsWords * sizeof(unsigned long long) <= 32768, "the copies are read into the stack");
@@ -1495,9 +1447,7 @@ int rm_mesh_deviation(rm_mesh* mesh, rm_scene* scene, const RmMeshDeviation* par
   r.nonfinite_samples = got[rm::RM_DEVIATION_NONFINITE];
   r.over_triangles = got[rm::RM_DEVIATION_OVER];
   if (const unsigned long long key = got[rm::RM_DEVIATION_KEY]) {  // (0: no evaluated triangle, max and worst stay 0)
-    const unsigned int bits = (unsigned int)(key >> 32);
-    std::memcpy(&r.max, &bits, sizeof bits);
-    r.worst_triangle = 0xFFFFFFFFull - (key & 0xFFFFFFFFull);
+    mesh_key_decode(key, &r.max, &r.worst_triangle);
   }
   double sum1, sum2;
   std::memcpy(&r.area, got + rm::RM_DEVIATION_AREA, sizeof r.area);

@@ -1,9 +1,18 @@
-// Mesh extraction (include/hip_raymarch.h "mesh extraction"): a scene's distance on a grid of corners, in this unit's arithmetic,
-// and -- in the strict unit only, they have no arithmetic of a policy's own -- the surface-nets mesher over such a grid, the two
-// kernels that move its vertices to their cells' QEF minimisers (rm_mesh_extract_sharp), and the integer kernels that label a mesh's
-// connected components and compact the kept ones (rm_mesh_components, rm_mesh_filter), and the vertex clustering of rm_mesh_simplify with the quadric placement of
-// rm_mesh_simplify_quadric, and the edge table, classes, extent and fixed-tree sums of rm_mesh_measure, and the step and report of rm_mesh_project, whose evaluating kernel is in every unit, and likewise the reducer of rm_mesh_deviation behind its evaluating kernel.  Included by
-// rm_strict.hip / rm_fast.hip / rm_glstack.hip behind rm_kernels.inc.
+// Mesh kernels (include/hip_raymarch.h "mesh extraction" and the sections behind it).  Included by rm_strict.hip / rm_fast.hip /
+// rm_glstack.hip behind rm_kernels.inc.
+//
+// In every unit, in that unit's arithmetic -- the kernels that evaluate the scene, each launched by launch_point_kind (rm_kernels.inc):
+//   - the sampler: a scene's distance on a grid of corners                                  (rm_sdf_grid, rm_mesh_extract*)
+//   - ambient occlusion: the distance at a fan of taps over every vertex                    (rm_mesh_occlusion)
+//   - projection: the distance and, where wanted, the normal at every vertex                (rm_mesh_project)
+//   - deviation: the distance at fixed points inside every triangle                         (rm_mesh_deviation)
+// In the strict unit only -- they have no arithmetic of a policy's own:
+//   - the mesher: surface nets over such a grid, whole or in z-slabs                        (rm_mesh_extract*, rm_mesh_from_values*)
+//   - sharp vertices: the two kernels that move vertices to their cells' QEF minimisers     (rm_mesh_extract_sharp*)
+//   - components and islands: the integer kernels that label and compact                    (rm_mesh_components, rm_mesh_filter)
+//   - simplification: vertex clustering, and the quadric placement on top of it             (rm_mesh_simplify, rm_mesh_simplify_quadric)
+//   - measures: the edge table, classes, extent and the fixed-tree sums                     (rm_mesh_measure)
+//   - projection's step and report, deviation's reducer                                     (behind their evaluating kernels)
 namespace rm {
 
 // ---- the sampler: rm_probe's RM_PROBE_SDF with the point made from the corner's indices -------------------------------------
@@ -26,30 +35,10 @@ __global__ __launch_bounds__(256) void rm_sdf_grid_kernel(const SdfGridParams P)
 }
 
 #ifndef RM_ONLY_KERNELS
-// the kind selection is launch_probe's, row for row: a corner's value has to be the probe's at that point
+// (launch_point_kind: a corner's value has to be the probe's at that point)
 hipError_t RM_LAUNCH(launch_sdf_grid)(const SdfGridParams& P, hipStream_t stream) {
   const dim3 grid((unsigned int)((P.grid.corners + 255) / 256));
-#define RM_GRID_CASE(K) case K: hipLaunchKernelGGL((rm_sdf_grid_kernel<K, kFast>), grid, dim3(256), 0, stream, P); break;
-  if (P.scene.kind == RM_SCENE_TABLE && (P.scene.table_flags & RM_TABLE_HAS_KIND)) {
-    hipLaunchKernelGGL((rm_sdf_grid_kernel<RM_KIND_TABLE_KINDS, kFast>), grid, dim3(256), 0, stream, P);
-    return hipGetLastError();
-  }
-  if (P.scene.kind == RM_SCENE_TABLE && P.scene.nprims >= RM_TABLE_BIG_ROWS) {
-    hipLaunchKernelGGL((rm_sdf_grid_kernel<RM_KIND_TABLE_BIG, kFast>), grid, dim3(256), 0, stream, P);
-    return hipGetLastError();
-  }
-  switch (P.scene.kind) {
-    RM_GRID_CASE(RM_SCENE_TABLE)
-    RM_GRID_CASE(RM_SCENE_MANDELBULB)
-    RM_GRID_CASE(RM_SCENE_SPHERE_GRID)
-    RM_GRID_CASE(RM_SCENE_SPHERE_LATTICE)
-    RM_GRID_CASE(RM_SCENE_MENGER)
-    RM_GRID_CASE(RM_SCENE_KIFS_TREE)
-    RM_GRID_CASE(RM_SCENE_KIFS_BOX)
-    default: return hipErrorInvalidValue;
-  }
-#undef RM_GRID_CASE
-  return hipGetLastError();
+  return launch_point_kind(P.scene, [&](auto kind) { hipLaunchKernelGGL((rm_sdf_grid_kernel<decltype(kind)::value, kFast>), grid, dim3(256), 0, stream, P); });
 }
 #endif
 
@@ -127,31 +116,10 @@ __global__ __launch_bounds__(256) void rm_mesh_occlusion_kernel(const MeshOcclus
 }
 
 #ifndef RM_ONLY_KERNELS
-// the kind selection is launch_sdf_grid's, row for row: a tap's distance has to be the probe's at that point
 hipError_t RM_LAUNCH(launch_mesh_occlusion)(const MeshOcclusionPass& P, hipStream_t stream) {
   const long long rays = (long long)P.vertices << P.log2_directions;
   const dim3 grid((unsigned int)((rays + 255) / 256));
-#define RM_OCCLUSION_CASE(K) case K: hipLaunchKernelGGL((rm_mesh_occlusion_kernel<K, kFast>), grid, dim3(256), 0, stream, P); break;
-  if (P.scene.kind == RM_SCENE_TABLE && (P.scene.table_flags & RM_TABLE_HAS_KIND)) {
-    hipLaunchKernelGGL((rm_mesh_occlusion_kernel<RM_KIND_TABLE_KINDS, kFast>), grid, dim3(256), 0, stream, P);
-    return hipGetLastError();
-  }
-  if (P.scene.kind == RM_SCENE_TABLE && P.scene.nprims >= RM_TABLE_BIG_ROWS) {
-    hipLaunchKernelGGL((rm_mesh_occlusion_kernel<RM_KIND_TABLE_BIG, kFast>), grid, dim3(256), 0, stream, P);
-    return hipGetLastError();
-  }
-  switch (P.scene.kind) {
-    RM_OCCLUSION_CASE(RM_SCENE_TABLE)
-    RM_OCCLUSION_CASE(RM_SCENE_MANDELBULB)
-    RM_OCCLUSION_CASE(RM_SCENE_SPHERE_GRID)
-    RM_OCCLUSION_CASE(RM_SCENE_SPHERE_LATTICE)
-    RM_OCCLUSION_CASE(RM_SCENE_MENGER)
-    RM_OCCLUSION_CASE(RM_SCENE_KIFS_TREE)
-    RM_OCCLUSION_CASE(RM_SCENE_KIFS_BOX)
-    default: return hipErrorInvalidValue;
-  }
-#undef RM_OCCLUSION_CASE
-  return hipGetLastError();
+  return launch_point_kind(P.scene, [&](auto kind) { hipLaunchKernelGGL((rm_mesh_occlusion_kernel<decltype(kind)::value, kFast>), grid, dim3(256), 0, stream, P); });
 }
 #endif
 
@@ -205,30 +173,9 @@ __global__ __launch_bounds__(256) void rm_mesh_project_eval_kernel(const MeshPro
 }
 
 #ifndef RM_ONLY_KERNELS
-// the kind selection is launch_sdf_grid's, row for row: the bits have to be the probes' at that point
 hipError_t RM_LAUNCH(launch_mesh_project_eval)(const MeshProjectEval& P, hipStream_t stream) {
   const dim3 grid((unsigned int)(((long long)P.vertices + 255) / 256));
-#define RM_PROJECT_CASE(K) case K: hipLaunchKernelGGL((rm_mesh_project_eval_kernel<K, kFast>), grid, dim3(256), 0, stream, P); break;
-  if (P.scene.kind == RM_SCENE_TABLE && (P.scene.table_flags & RM_TABLE_HAS_KIND)) {
-    hipLaunchKernelGGL((rm_mesh_project_eval_kernel<RM_KIND_TABLE_KINDS, kFast>), grid, dim3(256), 0, stream, P);
-    return hipGetLastError();
-  }
-  if (P.scene.kind == RM_SCENE_TABLE && P.scene.nprims >= RM_TABLE_BIG_ROWS) {
-    hipLaunchKernelGGL((rm_mesh_project_eval_kernel<RM_KIND_TABLE_BIG, kFast>), grid, dim3(256), 0, stream, P);
-    return hipGetLastError();
-  }
-  switch (P.scene.kind) {
-    RM_PROJECT_CASE(RM_SCENE_TABLE)
-    RM_PROJECT_CASE(RM_SCENE_MANDELBULB)
-    RM_PROJECT_CASE(RM_SCENE_SPHERE_GRID)
-    RM_PROJECT_CASE(RM_SCENE_SPHERE_LATTICE)
-    RM_PROJECT_CASE(RM_SCENE_MENGER)
-    RM_PROJECT_CASE(RM_SCENE_KIFS_TREE)
-    RM_PROJECT_CASE(RM_SCENE_KIFS_BOX)
-    default: return hipErrorInvalidValue;
-  }
-#undef RM_PROJECT_CASE
-  return hipGetLastError();
+  return launch_point_kind(P.scene, [&](auto kind) { hipLaunchKernelGGL((rm_mesh_project_eval_kernel<decltype(kind)::value, kFast>), grid, dim3(256), 0, stream, P); });
 }
 #endif
 
@@ -265,31 +212,10 @@ __global__ __launch_bounds__(256) void rm_mesh_deviation_eval_kernel(const MeshD
 }
 
 #ifndef RM_ONLY_KERNELS
-// the kind selection is launch_sdf_grid's, row for row: a sample's distance has to be the probe's at that point
 hipError_t RM_LAUNCH(launch_mesh_deviation_eval)(const MeshDeviationSdf& P, hipStream_t stream) {
   const long long lanes = (long long)P.triangles << P.log2_samples;
   const dim3 grid((unsigned int)((lanes + 255) / 256));
-#define RM_DEVIATION_CASE(K) case K: hipLaunchKernelGGL((rm_mesh_deviation_eval_kernel<K, kFast>), grid, dim3(256), 0, stream, P); break;
-  if (P.scene.kind == RM_SCENE_TABLE && (P.scene.table_flags & RM_TABLE_HAS_KIND)) {
-    hipLaunchKernelGGL((rm_mesh_deviation_eval_kernel<RM_KIND_TABLE_KINDS, kFast>), grid, dim3(256), 0, stream, P);
-    return hipGetLastError();
-  }
-  if (P.scene.kind == RM_SCENE_TABLE && P.scene.nprims >= RM_TABLE_BIG_ROWS) {
-    hipLaunchKernelGGL((rm_mesh_deviation_eval_kernel<RM_KIND_TABLE_BIG, kFast>), grid, dim3(256), 0, stream, P);
-    return hipGetLastError();
-  }
-  switch (P.scene.kind) {
-    RM_DEVIATION_CASE(RM_SCENE_TABLE)
-    RM_DEVIATION_CASE(RM_SCENE_MANDELBULB)
-    RM_DEVIATION_CASE(RM_SCENE_SPHERE_GRID)
-    RM_DEVIATION_CASE(RM_SCENE_SPHERE_LATTICE)
-    RM_DEVIATION_CASE(RM_SCENE_MENGER)
-    RM_DEVIATION_CASE(RM_SCENE_KIFS_TREE)
-    RM_DEVIATION_CASE(RM_SCENE_KIFS_BOX)
-    default: return hipErrorInvalidValue;
-  }
-#undef RM_DEVIATION_CASE
-  return hipGetLastError();
+  return launch_point_kind(P.scene, [&](auto kind) { hipLaunchKernelGGL((rm_mesh_deviation_eval_kernel<decltype(kind)::value, kFast>), grid, dim3(256), 0, stream, P); });
 }
 #endif
 

@@ -4,8 +4,9 @@
 
 On the csg64 golden scene (tests/golden_cases.py) and a grid of n^3 cells (default 64) over its bounds, [-2, 2]^3 (centres within
 1.5 of the origin, radii up to 0.45, smooth unions): rm_probe of 65 536 SDF points, rm_sdf_grid, rm_mesh_extract with normals and
-colours, rm_mesh_extract_sharp with the same, rm_mesh_from_values on the downloaded field, rm_mesh_components on a fresh mesh, and
-rm_mesh_filter with largest = 1 on a labelled mesh.  Every call returns with its work done, so the host's clock is the measure:
+colours, rm_mesh_extract_sharp with the same, rm_mesh_from_values on the downloaded field, rm_mesh_components on a fresh mesh,
+rm_mesh_filter with largest = 1 on a labelled mesh, and, with their default blocks on that mesh and scene, rm_mesh_occlusion, rm_mesh_measure
+(on a fresh mesh: a mesh keeps its measures), rm_mesh_project and rm_mesh_deviation.  Every call returns with its work done, so the host's clock is the measure:
 `runs` runs of `reps` calls each after a warm-up run, and the min / median / max of the per-call time over the runs.  Each call
 that makes a mesh has its rm_mesh_destroy inside the timed span; what a call needs made for it (the fresh mesh of rm_mesh_components)
 is made and destroyed outside it.  The host buffers are allocated once, outside the timed calls.
@@ -101,6 +102,20 @@ def main():
     timed("rm_mesh_filter + destroy", filter_largest, largest=1, mesh="labelled")
     counts = (C.c_ulonglong * 2)()
     ctx._check(lib.rm_mesh_counts(labelled, counts))
+
+    occlusion = np.empty(int(counts[0]), np.float32)
+    timed("rm_mesh_occlusion", lambda _: ctx._check(lib.rm_mesh_occlusion(labelled, scene.h, None, native._fp(occlusion), None)), mesh="labelled")
+    measures = abi.RmMeshMeasures()
+    timed("rm_mesh_measure", lambda h: ctx._check(lib.rm_mesh_measure(h, C.byref(measures), None)), before=lambda: extract(plain), after=lib.rm_mesh_destroy, mesh="fresh")
+
+    def project(_):
+        h = C.c_void_p()
+        ctx._check(lib.rm_mesh_project(labelled, scene.h, None, C.byref(h), None, None))
+        lib.rm_mesh_destroy(h)
+
+    timed("rm_mesh_project + destroy", project, mesh="labelled")
+    report = abi.RmMeshDeviationReport()
+    timed("rm_mesh_deviation", lambda _: ctx._check(lib.rm_mesh_deviation(labelled, scene.h, None, C.byref(report), None, None)), mesh="labelled")
     print(json.dumps({"what": "mesh", "vertices": int(counts[0]), "triangles": int(counts[1]), "components": int(count.value)}))
     lib.rm_mesh_destroy(labelled)
     scene.destroy()
