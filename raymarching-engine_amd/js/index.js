@@ -353,137 +353,43 @@ class RenderJobContext {  // RenderJobContext + loadRenderJobContext (LoadRender
     addon.sdfGrid(this.ctx, this.sceneHandle(scene), grid, flags, out);
     return out;
   }
-  // the level set opts.iso as { positions, normals | null, colours | null, triangles, cells } (rm_mesh_extract); opts: meshParams'
-  // sharp: undefined / null = that call; true or meshSharp's options = rm_mesh_extract_sharp, the same triangles with each vertex at its cell's
-  // QEF minimiser (hard edges and corners stay sharp)
-  // keep: undefined / null = that mesh; true or meshKeep's options = its connected components filtered on the GPU before anything is copied
-  // (rm_mesh_filter; the defaults drop the unreferenced vertices).  components: truthy adds labels (Uint32Array(V)) and componentSizes
-  // (Uint32Array(2 C): vertices, triangles per component) of the mesh that is returned (rm_mesh_components)
-  // simplify: undefined / null = that mesh; meshSimplify's options ({ grid, keepDuplicates }) = the vertices of every cell of that grid of clusters
-  // merged into one on the GPU (rm_mesh_simplify) before keep and components are applied; the result's cells index the cluster grid
-  // quadric (with simplify only): undefined / null = that call; true or meshQuadric's options = rm_mesh_simplify_quadric, the same mesh with every
-  // cluster's vertex at the minimiser of its plane quadrics
-  // occlusion: undefined / null = that mesh; true or meshOcclusion's options = occlusion (Float32Array(V), 1 = open) of the mesh that is returned,
-  // baked from the scene's distance field behind simplify, keep and components (rm_mesh_occlusion); its milliseconds are timings[3]
-  // measures: truthy = the mesh that is returned is measured on the GPU behind simplify and keep, before anything is copied (rm_mesh_measure), as
-  // measures: RmMeshMeasures' fields in camel case -- the counts as Numbers (all below 2^53: V, T < 2^32 and E <= 3 T), closed as a boolean,
-  // lo / hi as arrays --, componentEdges: BigUint64Array(4 C) of (edges, boundary, irregular, unbalanced) per component as the raw uint64 rows, and
-  // milliseconds: [topology, geometry].  timings is as without it.
-  // slabs: undefined / null = those calls; true, a number of cell layers or meshSlabs' options = rm_mesh_extract_slabs / _sharp_slabs, the same
-  // mesh byte for byte, made from one window of z layers at a time -- which also takes a meshGrid(lo, hi, n, { slabs: true }) beyond 2^28 corners
-  // project: undefined / null = that mesh; true or meshProject's options = the vertices of the mesh that is returned moved onto the scene's level set
-  // by Newton steps on the GPU (rm_mesh_project) behind simplify, quadric and keep, before components, occlusion and measures, which then see the
-  // projected mesh.  iso, where not given, is the extraction's; reach, where not given, is meshProjectReach of the grid the returned mesh lies on (the
-  // cluster grid with simplify, else the sampling grid).  The result carries projection (RmMeshProjection's fields in camel case, and milliseconds:
-  // the rounds and the normals) and residual (Float32Array(V): the distance minus iso at the new vertices); timings stays the producing mesh's
-  // deviation: undefined / null = that mesh; true or meshDeviation's options = how far the triangles of the mesh that is returned -- behind every
-  // stage above, project included -- lie off the scene's level set at order * order fixed samples each, measured on the GPU (rm_mesh_deviation).
-  // iso, where not given, is the extraction's.  The result carries deviation (RmMeshDeviationReport's fields in camel case, and milliseconds) and
-  // triangleDeviation (Float32Array(T): each triangle's largest |distance - iso| over its samples); timings is as without it
+  // the level set opts.iso as { positions, normals | null, colours | null, triangles, cells, timings } (opts: meshParams'), through a pipeline on
+  // the GPU whose stages are all opt-in -- undefined / null = the stage is off, true = its defaults, else its block's options -- in this order:
+  // extract: rm_mesh_extract; with sharp (meshSharp's) rm_mesh_extract_sharp, the same triangles with each vertex at its cell's QEF minimiser
+  //   (hard edges and corners stay sharp); with slabs (true, a number of cell layers or meshSlabs') rm_mesh_extract_slabs / _sharp_slabs, the same
+  //   mesh byte for byte, made from one window of z layers at a time -- which also takes a meshGrid(lo, hi, n, { slabs: true }) beyond 2^28 corners
+  // simplify (meshSimplify's { grid, keepDuplicates }; no `true`): the vertices of every cell of that grid of clusters merged into one
+  //   (rm_mesh_simplify); the result's cells index the cluster grid.  With quadric (meshQuadric's; with simplify only) rm_mesh_simplify_quadric, the
+  //   same mesh with every cluster's vertex at the minimiser of its plane quadrics
+  // keep (meshKeep's): the connected components filtered before anything is copied (rm_mesh_filter; the defaults drop the unreferenced vertices)
+  // project (meshProject's): the vertices moved onto the scene's level set by Newton steps (rm_mesh_project); every later stage sees the projected
+  //   mesh.  iso, where not given, is the extraction's; reach, where not given, is meshProjectReach of the grid the mesh lies on (the cluster grid
+  //   with simplify, else the sampling grid).  Adds projection (RmMeshProjection's fields in camel case, and milliseconds: the rounds and the
+  //   normals) and residual (Float32Array(V): the distance minus iso at the new vertices); timings stays the producing mesh's
+  // measures (truthy): the mesh is measured before anything is copied (rm_mesh_measure).  Adds measures: RmMeshMeasures' fields in camel case --
+  //   the counts as Numbers (all below 2^53: V, T < 2^32 and E <= 3 T), closed as a boolean, lo / hi as arrays --, componentEdges:
+  //   BigUint64Array(4 C) of (edges, boundary, irregular, unbalanced) per component as the raw uint64 rows, and milliseconds: [topology, geometry]
+  // components (truthy): adds labels (Uint32Array(V)) and componentSizes (Uint32Array(2 C): vertices, triangles per component) (rm_mesh_components)
+  // occlusion (meshOcclusion's): adds occlusion (Float32Array(V), 1 = open), baked from the scene's distance field (rm_mesh_occlusion); its
+  //   milliseconds are timings[3], which is there only with it
+  // deviation (meshDeviation's): how far the triangles lie off the scene's level set at order * order fixed samples each (rm_mesh_deviation).  iso,
+  //   where not given, is the extraction's.  Adds deviation (RmMeshDeviationReport's fields in camel case, and milliseconds) and triangleDeviation
+  //   (Float32Array(T): each triangle's largest |distance - iso| over its samples)
   extractMesh(scene, grid, opts, sharp, keep, components, simplify = null, quadric = null, occlusion = null, measures = false, slabs = null, project = null, deviation = null) {
-    const q = quadric === undefined || quadric === null ? null : meshQuadric(quadric === true ? undefined : quadric);
-    if (q !== null && (simplify === undefined || simplify === null)) throw new TypeError("mesh: quadric places the vertices of a simplification: give simplify as well");
-    if (deviation !== undefined && deviation !== null) {  // (every argument is given: the deviation block is the last)
-      const params = meshParams(opts);
-      const c = simplify === undefined || simplify === null ? null : meshSimplify(simplify);
-      const asked = deviation === true ? {} : deviation;
-      if (typeof asked !== "object") throw new TypeError("mesh: expected true or an object of deviation parameters");
-      const dv = meshDeviation({ iso: params.iso, ...asked });
-      let pr = null;
-      if (project !== undefined && project !== null) {
-        const given = project === true ? {} : project;
-        if (typeof given !== "object") throw new TypeError("mesh: expected true or an object of project parameters");
-        pr = meshProject({ iso: params.iso, reach: meshProjectReach(c !== null ? c.grid : grid), ...given });
-      }
-      const o = occlusion === undefined || occlusion === null ? null : meshOcclusion(occlusion === true ? undefined : occlusion);
-      const s = sharp === undefined || sharp === null ? null : meshSharp(sharp === true ? undefined : sharp);
-      const k = keep === undefined || keep === null ? null : meshKeep(keep === true ? undefined : keep);
-      if (slabs !== undefined && slabs !== null) {
-        const w = meshSlabs(slabs === true ? undefined : typeof slabs === "number" ? { layers: slabs } : slabs);
-        return addon.extractMeshSlabs(this.ctx, this.sceneHandle(scene), grid, w, params, s, k, !!components, c, q, o, !!measures, pr, dv);
-      }
-      if (grid && grid.slabs) throw new TypeError("mesh: a grid made with slabs: true is extracted in slabs: give slabs as well");
-      return addon.extractMesh(this.ctx, this.sceneHandle(scene), grid, params, s, k, !!components, c, q, o, !!measures, pr, dv);
-    }
-    if (project !== undefined && project !== null) {  // (every argument is given: the project block is the last)
-      const params = meshParams(opts);
-      const c = simplify === undefined || simplify === null ? null : meshSimplify(simplify);
-      const given = project === true ? {} : project;
-      if (typeof given !== "object") throw new TypeError("mesh: expected true or an object of project parameters");
-      const pr = meshProject({ iso: params.iso, reach: meshProjectReach(c !== null ? c.grid : grid), ...given });
-      const o = occlusion === undefined || occlusion === null ? null : meshOcclusion(occlusion === true ? undefined : occlusion);
-      const s = sharp === undefined || sharp === null ? null : meshSharp(sharp === true ? undefined : sharp);
-      const k = keep === undefined || keep === null ? null : meshKeep(keep === true ? undefined : keep);
-      if (slabs !== undefined && slabs !== null) {
-        const w = meshSlabs(slabs === true ? undefined : typeof slabs === "number" ? { layers: slabs } : slabs);
-        return addon.extractMeshSlabs(this.ctx, this.sceneHandle(scene), grid, w, params, s, k, !!components, c, q, o, !!measures, pr);
-      }
-      if (grid && grid.slabs) throw new TypeError("mesh: a grid made with slabs: true is extracted in slabs: give slabs as well");
-      return addon.extractMesh(this.ctx, this.sceneHandle(scene), grid, params, s, k, !!components, c, q, o, !!measures, pr);
-    }
-    if (slabs !== undefined && slabs !== null) {
-      const w = meshSlabs(slabs === true ? undefined : typeof slabs === "number" ? { layers: slabs } : slabs);
-      const o = occlusion === undefined || occlusion === null ? null : meshOcclusion(occlusion === true ? undefined : occlusion);
-      const s = sharp === undefined || sharp === null ? null : meshSharp(sharp === true ? undefined : sharp);
-      const k = keep === undefined || keep === null ? null : meshKeep(keep === true ? undefined : keep);
-      const c = simplify === undefined || simplify === null ? null : meshSimplify(simplify);
-      return addon.extractMeshSlabs(this.ctx, this.sceneHandle(scene), grid, w, meshParams(opts), s, k, !!components, c, q, o, !!measures);
-    }
-    if (grid && grid.slabs) throw new TypeError("mesh: a grid made with slabs: true is extracted in slabs: give slabs as well");
-    if (measures) {
-      const o = occlusion === undefined || occlusion === null ? null : meshOcclusion(occlusion === true ? undefined : occlusion);
-      const s = sharp === undefined || sharp === null ? null : meshSharp(sharp === true ? undefined : sharp);
-      const k = keep === undefined || keep === null ? null : meshKeep(keep === true ? undefined : keep);
-      const c = simplify === undefined || simplify === null ? null : meshSimplify(simplify);
-      return addon.extractMesh(this.ctx, this.sceneHandle(scene), grid, meshParams(opts), s, k, !!components, c, q, o, true);
-    }
-    if (occlusion !== undefined && occlusion !== null) {
-      const o = meshOcclusion(occlusion === true ? undefined : occlusion);
-      const s = sharp === undefined || sharp === null ? null : meshSharp(sharp === true ? undefined : sharp);
-      const k = keep === undefined || keep === null ? null : meshKeep(keep === true ? undefined : keep);
-      const c = simplify === undefined || simplify === null ? null : meshSimplify(simplify);
-      return addon.extractMesh(this.ctx, this.sceneHandle(scene), grid, meshParams(opts), s, k, !!components, c, q, o);
-    }
-    if (simplify !== undefined && simplify !== null) {
-      const s = sharp === undefined || sharp === null ? null : meshSharp(sharp === true ? undefined : sharp);
-      const k = keep === undefined || keep === null ? null : meshKeep(keep === true ? undefined : keep);
-      if (q !== null) return addon.extractMesh(this.ctx, this.sceneHandle(scene), grid, meshParams(opts), s, k, !!components, meshSimplify(simplify), q);
-      return addon.extractMesh(this.ctx, this.sceneHandle(scene), grid, meshParams(opts), s, k, !!components, meshSimplify(simplify));
-    }
-    const plain = (keep === undefined || keep === null) && !components;
-    if (plain && (sharp === undefined || sharp === null)) return addon.extractMesh(this.ctx, this.sceneHandle(scene), grid, meshParams(opts));
-    const s = sharp === undefined || sharp === null ? null : meshSharp(sharp === true ? undefined : sharp);
-    if (plain) return addon.extractMesh(this.ctx, this.sceneHandle(scene), grid, meshParams(opts), s);
-    const k = keep === undefined || keep === null ? null : meshKeep(keep === true ? undefined : keep);
-    return addon.extractMesh(this.ctx, this.sceneHandle(scene), grid, meshParams(opts), s, k, !!components);
+    const o = meshOptions(grid, opts, { sharp, keep, components, simplify, quadric, occlusion, measures, slabs, project, deviation });
+    const stages = [o.sharp, o.keep, o.components, o.simplify, o.quadric, o.occlusion, o.measures, o.project, o.deviation], h = this.sceneHandle(scene);
+    if (o.slabs !== null) return addon.extractMeshSlabs(...meshArguments([this.ctx, h, grid, o.slabs, o.params, ...stages], 12));
+    return addon.extractMesh(...meshArguments([this.ctx, h, grid, o.params, ...stages], 4, 5));
   }
-  // the mesher alone on the caller's field: values Float32Array of the grid's corners, x fastest (rm_mesh_from_values)
-  // keep, components, simplify, quadric, measures: as in extractMesh
+  // the mesher alone on the caller's field: values Float32Array of the grid's corners, x fastest (rm_mesh_from_values; with slabs
+  // rm_mesh_from_values_slabs); keep, components, simplify, quadric, measures, slabs: as in extractMesh
   meshFromValues(grid, values, iso = 0, keep, components, simplify, quadric, measures, slabs) {
     if (!(values instanceof Float32Array)) throw new TypeError("meshFromValues: values must be a Float32Array");
     if (!finite(iso)) throw new RangeError("mesh: iso must be a finite number");
-    const q = quadric === undefined || quadric === null ? null : meshQuadric(quadric === true ? undefined : quadric);
-    if (q !== null && (simplify === undefined || simplify === null)) throw new TypeError("mesh: quadric places the vertices of a simplification: give simplify as well");
-    if (slabs !== undefined && slabs !== null) {  // (rm_mesh_from_values_slabs; slabs as in extractMesh)
-      const w = meshSlabs(slabs === true ? undefined : typeof slabs === "number" ? { layers: slabs } : slabs);
-      const k = keep === undefined || keep === null ? null : meshKeep(keep === true ? undefined : keep);
-      const c = simplify === undefined || simplify === null ? null : meshSimplify(simplify);
-      return addon.meshFromValuesSlabs(this.ctx, grid, values, iso, w, k, !!components, c, q, !!measures);
-    }
-    if (grid && grid.slabs) throw new TypeError("mesh: a grid made with slabs: true is extracted in slabs: give slabs as well");
-    if (measures) {
-      const k = keep === undefined || keep === null ? null : meshKeep(keep === true ? undefined : keep);
-      const c = simplify === undefined || simplify === null ? null : meshSimplify(simplify);
-      return addon.meshFromValues(this.ctx, grid, values, iso, k, !!components, c, q, true);
-    }
-    if (simplify !== undefined && simplify !== null) {
-      const k = keep === undefined || keep === null ? null : meshKeep(keep === true ? undefined : keep);
-      if (q !== null) return addon.meshFromValues(this.ctx, grid, values, iso, k, !!components, meshSimplify(simplify), q);
-      return addon.meshFromValues(this.ctx, grid, values, iso, k, !!components, meshSimplify(simplify));
-    }
-    if ((keep === undefined || keep === null) && !components) return addon.meshFromValues(this.ctx, grid, values, iso);
-    const k = keep === undefined || keep === null ? null : meshKeep(keep === true ? undefined : keep);
-    return addon.meshFromValues(this.ctx, grid, values, iso, k, !!components);
+    const o = meshOptions(grid, undefined, { keep, components, simplify, quadric, measures, slabs });
+    const stages = [o.keep, o.components, o.simplify, o.quadric, o.measures];
+    if (o.slabs !== null) return addon.meshFromValuesSlabs(...meshArguments([this.ctx, grid, values, iso, o.slabs, ...stages], 10));
+    return addon.meshFromValues(...meshArguments([this.ctx, grid, values, iso, ...stages], 4, 4));
   }
   close() { for (const e of this.purgatory) addon.fbDestroy(e.fb); for (const v of this.live.values()) addon.fbDestroy(v.fb);
             for (const s of this.scenes.values()) if (!(s && s.infoLog)) addon.sceneDestroy(s); addon.ctxDestroy(this.ctx); }
@@ -637,7 +543,7 @@ const DESPECKLE_DEFAULTS = { radius: 2, rank: 1, gain: 3.0, floor: 0.1, repair: 
 // library's order as field: [holds, text].
 const finite = (v) => typeof v === "number" && Number.isFinite(v);
 const POSITIVE = [(v) => finite(v) && v > 0, "must be finite and > 0"];
-const integerIn = (lo, hi) => [(v) => Number.isInteger(v) && v >= lo && v <= hi, "must be an integer in " + lo + ".." + hi];
+const integerIn = (lo, hi, shown = hi) => [(v) => Number.isInteger(v) && v >= lo && v <= hi, "must be an integer in " + lo + ".." + shown];
 const FILTER_BLOCKS = {
   atrous: { label: "denoise", forms: "true", defaults: DENOISE_DEFAULTS,
             checks: { iterations: integerIn(0, 8), sigma_color: POSITIVE, sigma_normal: POSITIVE, sigma_depth: POSITIVE } },
@@ -752,76 +658,80 @@ function meshGrid(lo, hi, n, opts) {
   if (!slabs && (n[0] + 1) * (n[1] + 1) * (n[2] + 1) > 2 ** 28) throw new RangeError("grid: at most 2^28 corners");
   return slabs ? { lo: lo.slice(), hi: hi.slice(), n: n.slice(), slabs: true } : { lo: lo.slice(), hi: hi.slice(), n: n.slice() };
 }
-// undefined / null = the defaults, or an object with some of iso, normals, normalDelta, colours, flags (RM.RENDER_FAST, RM.RENDER_NO_CULL);
-// checked as the library checks an RmMeshParams; returns { iso, normals: 0 | 1, normalDelta, colours: 0 | 1, flags }
-function meshParams(opts) {
-  const p = { ...MESH_DEFAULTS };
-  if (opts !== undefined && opts !== null) {
-    if (typeof opts !== "object") throw new TypeError("mesh: expected an object of parameters");
-    for (const [k, v] of Object.entries(opts)) {
-      if (!(k in MESH_DEFAULTS)) throw new TypeError("mesh: unknown parameter " + k);
-      p[k] = v;
-    }
-  }
-  const flag = (v) => v === true || v === 1 ? 1 : v === false || v === 0 ? 0 : -1;
-  if (!finite(p.iso) || !finite(Math.fround(p.iso))) throw new RangeError("mesh: iso must be a finite number");
-  p.normals = flag(p.normals); p.colours = flag(p.colours);
-  if (p.normals < 0 || p.colours < 0) throw new RangeError("mesh: normals and colours must be true or false");
-  if (p.normals && !POSITIVE[0](p.normalDelta)) throw new RangeError("mesh: normalDelta " + POSITIVE[1]);
-  if (!Number.isInteger(p.flags) || (p.flags & ~(RM.RENDER_FAST | RM.RENDER_NO_CULL)) !== 0) throw new RangeError("mesh: flags must be 0, RM.RENDER_FAST, RM.RENDER_NO_CULL or both");
-  return p;
-}
-// the sharp block of extractMesh (include/hip_raymarch.h RmMeshSharp): undefined / null = the defaults, or an object with some of refine,
-// normalDelta, threshold; checked as the library checks it; returns { refine, normalDelta, threshold }
+// ---- the parameter blocks of the mesh calls (include/hip_raymarch.h RmMeshParams, RmMeshSharp, ... RmMeshDeviation) ----
+// Every block but simplify: undefined / null = the defaults, or an object with some of the defaults' fields; checked as the library checks it.
+// params: iso, normals, normalDelta, colours, flags (RM.RENDER_FAST, RM.RENDER_NO_CULL); returns { iso, normals: 0 | 1, normalDelta, colours: 0 | 1, flags }
+// sharp (extractMesh): refine, normalDelta, threshold
 const MESH_SHARP_DEFAULTS = { refine: 6, normalDelta: 2 ** -10, threshold: 0.1 };
-function meshSharp(opts) {
-  const p = { ...MESH_SHARP_DEFAULTS };
+// keep (extractMesh / meshFromValues): minTriangles (a component passes with at least that many triangles) and largest (0 = every passing
+// component, k > 0 = only the k with the most triangles, the lower component index first among equals); integers in 0..1e9, what the addon's
+// integer fields hold
+const MESH_KEEP_DEFAULTS = { minTriangles: 1, largest: 0 };
+// slabs (extractMesh / meshFromValues): layers (the cell layers per slab, 0 = chosen by the library; above the grid's nz it means nz); an integer
+// in 0..1e9
+const MESH_SLABS_DEFAULTS = { layers: 0 };
+// quadric (extractMesh / meshFromValues): threshold (eigenvalues at or below threshold * the largest are dropped from a cluster's solve, in [0, 1))
+const MESH_QUADRIC_DEFAULTS = { threshold: 0.1 };
+// occlusion (extractMesh): radius (the first tap's distance, in [2^-64, 2^64]), directions (1, 2, 4, ... 64), taps (1, 2, 4, 8), normalDelta (> 0),
+// strength (in [0, 4]) and flags (RM.RENDER_FAST, RM.RENDER_NO_CULL)
+const MESH_OCCLUSION_DEFAULTS = { radius: 0.25, directions: 16, taps: 4, normalDelta: 2 ** -10, strength: 1, flags: 0 };
+// project (rm_mesh_project): iso (the level to project onto), rounds (1..16), relax (in (0, 1]), tolerance (>= 0), reach (>= 0; 0 = no limit),
+// normalDelta (> 0) and flags
+const MESH_PROJECT_DEFAULTS = { iso: 0, rounds: 4, relax: 1, tolerance: 0, reach: 0, normalDelta: 2 ** -10, flags: 0 };
+// deviation (rm_mesh_deviation): iso (the level the mesh stands for), order (n = 1, 2, 4 or 8: n * n samples per triangle), tolerance (>= 0: a
+// triangle whose largest |distance - iso| exceeds it counts as over) and flags
+const MESH_DEVIATION_DEFAULTS = { iso: 0, order: 4, tolerance: 0, flags: 0 };
+// The checks' predicates as [holds(value, block), text]; `32`: the value must also hold as the float32 the addon stores.
+const toFlag = (v) => v === true || v === 1 ? 1 : v === false || v === 0 ? 0 : -1;
+const finite32 = (text) => [(v) => finite(v) && finite(Math.fround(v)), text];
+const within32 = (holds, interval) => [(v) => finite(v) && holds(Math.fround(v)), "must be finite and in " + interval];
+const POSITIVE32 = [(v) => POSITIVE[0](v) && POSITIVE[0](Math.fround(v)), POSITIVE[1]];
+const NOT_NEGATIVE32 = [(v) => finite(v) && finite(Math.fround(v)) && v >= 0, "must be finite and >= 0"];
+const BELOW_ONE32 = within32((f) => f >= 0 && f < 1, "[0, 1)");
+const COUNT = integerIn(0, 1e9, "1e9");
+const oneOf = (set, text) => [(v) => set.includes(v), text];
+const RENDER_FLAGS = [(v) => Number.isInteger(v) && (v & ~(RM.RENDER_FAST | RM.RENDER_NO_CULL)) === 0, "must be 0, RM.RENDER_FAST, RM.RENDER_NO_CULL or both"];
+// One row per block for meshBlock: the label its messages carry, the defaults, the fields true / false may set (0 | 1 in the result), and the
+// library's own checks in the library's order as [what the message names, [holds, text]].
+const MESH_BLOCKS = {
+  params: { label: "", defaults: MESH_DEFAULTS, flags: ["normals", "colours"],
+            checks: [["iso", finite32("must be a finite number")], ["normals and colours", [(v, p) => p.normals >= 0 && p.colours >= 0, "must be true or false"]],
+                     ["normalDelta", [(v, p) => !p.normals || POSITIVE[0](v), POSITIVE[1]]], ["flags", RENDER_FLAGS]] },
+  sharp: { label: "sharp", defaults: MESH_SHARP_DEFAULTS, checks: [["refine", integerIn(0, 16)], ["normalDelta", POSITIVE32], ["threshold", BELOW_ONE32]] },
+  keep: { label: "keep", defaults: MESH_KEEP_DEFAULTS, checks: [["minTriangles", COUNT], ["largest", COUNT]] },
+  slabs: { label: "slabs", defaults: MESH_SLABS_DEFAULTS, checks: [["layers", COUNT]] },
+  quadric: { label: "quadric", defaults: MESH_QUADRIC_DEFAULTS, checks: [["threshold", BELOW_ONE32]] },
+  occlusion: { label: "occlusion", defaults: MESH_OCCLUSION_DEFAULTS,
+               checks: [["radius", within32((f) => f >= 2 ** -64 && f <= 2 ** 64, "[2^-64, 2^64]")], ["directions", oneOf([1, 2, 4, 8, 16, 32, 64], "must be one of 1, 2, 4, 8, 16, 32, 64")],
+                        ["taps", oneOf([1, 2, 4, 8], "must be one of 1, 2, 4, 8")], ["normalDelta", POSITIVE32], ["strength", within32((f) => f >= 0 && f <= 4, "[0, 4]")],
+                        ["flags", RENDER_FLAGS]] },
+  project: { label: "project", defaults: MESH_PROJECT_DEFAULTS,
+             checks: [["iso", finite32("must be finite")], ["rounds", integerIn(1, 16)], ["relax", within32((f) => f > 0 && f <= 1, "(0, 1]")], ["tolerance", NOT_NEGATIVE32],
+                      ["reach", NOT_NEGATIVE32], ["normalDelta", POSITIVE32], ["flags", RENDER_FLAGS]] },
+  deviation: { label: "deviation", defaults: MESH_DEVIATION_DEFAULTS,
+               checks: [["iso", finite32("must be finite")], ["order", oneOf([1, 2, 4, 8], "must be 1, 2, 4 or 8")], ["tolerance", NOT_NEGATIVE32], ["flags", RENDER_FLAGS]] },
+};
+function meshBlock({ label, defaults, flags = [], checks }, opts) {
+  const of = label && label + " ", p = { ...defaults };
   if (opts !== undefined && opts !== null) {
-    if (typeof opts !== "object") throw new TypeError("mesh: expected an object of sharp parameters");
+    if (typeof opts !== "object") throw new TypeError("mesh: expected an object of " + of + "parameters");
     for (const [k, v] of Object.entries(opts)) {
-      if (!(k in MESH_SHARP_DEFAULTS)) throw new TypeError("mesh: unknown sharp parameter " + k);
+      if (!(k in defaults)) throw new TypeError("mesh: unknown " + of + "parameter " + k);
       p[k] = v;
     }
   }
-  if (!Number.isInteger(p.refine) || p.refine < 0 || p.refine > 16) throw new RangeError("mesh: sharp refine must be an integer in 0..16");
-  if (!POSITIVE[0](p.normalDelta) || !POSITIVE[0](Math.fround(p.normalDelta))) throw new RangeError("mesh: sharp normalDelta " + POSITIVE[1]);
-  if (!finite(p.threshold) || !(Math.fround(p.threshold) >= 0 && Math.fround(p.threshold) < 1)) throw new RangeError("mesh: sharp threshold must be finite and in [0, 1)");
+  for (const k of flags) p[k] = toFlag(p[k]);
+  for (const [k, [holds, text]] of checks) if (!holds(p[k], p)) throw new RangeError("mesh: " + of + k + " " + text);
   return p;
 }
-
-// the keep block of extractMesh / meshFromValues (include/hip_raymarch.h RmMeshKeep): undefined / null = the defaults, or an object with some of
-// minTriangles (a component passes with at least that many triangles) and largest (0 = every passing component, k > 0 = only the k with the
-// most triangles, the lower component index first among equals); integers in 0..1e9, what the addon's integer fields hold
-const MESH_KEEP_DEFAULTS = { minTriangles: 1, largest: 0 };
-function meshKeep(opts) {
-  const p = { ...MESH_KEEP_DEFAULTS };
-  if (opts !== undefined && opts !== null) {
-    if (typeof opts !== "object") throw new TypeError("mesh: expected an object of keep parameters");
-    for (const k of Object.keys(opts)) {
-      if (!(k in MESH_KEEP_DEFAULTS)) throw new TypeError("mesh: unknown keep parameter " + k);
-      p[k] = opts[k];
-    }
-  }
-  for (const k of Object.keys(MESH_KEEP_DEFAULTS))
-    if (typeof p[k] !== "number" || !Number.isInteger(p[k]) || p[k] < 0 || p[k] > 1e9) throw new RangeError("mesh: keep " + k + " must be an integer in 0..1e9");
-  return p;
-}
-
-// the slabs block of extractMesh / meshFromValues (include/hip_raymarch.h RmMeshSlabs): undefined / null = the defaults, or an object with layers
-// (the cell layers per slab, 0 = chosen by the library; above the grid's nz it means nz); an integer in 0..1e9, what the addon's integer fields hold
-const MESH_SLABS_DEFAULTS = { layers: 0 };
-function meshSlabs(opts) {
-  const p = { ...MESH_SLABS_DEFAULTS };
-  if (opts !== undefined && opts !== null) {
-    if (typeof opts !== "object") throw new TypeError("mesh: expected an object of slabs parameters");
-    for (const k of Object.keys(opts)) {
-      if (!(k in MESH_SLABS_DEFAULTS)) throw new TypeError("mesh: unknown slabs parameter " + k);
-      p[k] = opts[k];
-    }
-  }
-  if (typeof p.layers !== "number" || !Number.isInteger(p.layers) || p.layers < 0 || p.layers > 1e9) throw new RangeError("mesh: slabs layers must be an integer in 0..1e9");
-  return p;
-}
+function meshParams(opts) { return meshBlock(MESH_BLOCKS.params, opts); }
+function meshSharp(opts) { return meshBlock(MESH_BLOCKS.sharp, opts); }
+function meshKeep(opts) { return meshBlock(MESH_BLOCKS.keep, opts); }
+function meshSlabs(opts) { return meshBlock(MESH_BLOCKS.slabs, opts); }
+function meshQuadric(opts) { return meshBlock(MESH_BLOCKS.quadric, opts); }
+function meshOcclusion(opts) { return meshBlock(MESH_BLOCKS.occlusion, opts); }
+function meshProject(opts) { return meshBlock(MESH_BLOCKS.project, opts); }
+function meshDeviation(opts) { return meshBlock(MESH_BLOCKS.deviation, opts); }
 
 // the simplify block of extractMesh / meshFromValues (include/hip_raymarch.h RmMeshSimplify and the RmGrid of clusters): an object with grid (a
 // meshGrid: one output vertex per occupied cell; it need not be related to the sampling grid) and, optionally, keepDuplicates (keep the triangles
@@ -833,71 +743,9 @@ function meshSimplify(opts) {
     if (k !== "grid" && !(k in MESH_SIMPLIFY_DEFAULTS)) throw new TypeError("mesh: unknown simplify parameter " + k);
   const g = opts.grid;
   if (g === undefined || g === null || typeof g !== "object") throw new TypeError("mesh: simplify needs a grid { lo, hi, n }");
-  const d = "keepDuplicates" in opts ? opts.keepDuplicates : MESH_SIMPLIFY_DEFAULTS.keepDuplicates;
-  const flag = d === true || d === 1 ? 1 : d === false || d === 0 ? 0 : -1;
+  const flag = toFlag("keepDuplicates" in opts ? opts.keepDuplicates : MESH_SIMPLIFY_DEFAULTS.keepDuplicates);
   if (flag < 0) throw new RangeError("mesh: simplify keepDuplicates must be true or false");
   return { grid: meshGrid(g.lo, g.hi, g.n), keepDuplicates: flag };
-}
-
-// the quadric block of extractMesh / meshFromValues (include/hip_raymarch.h RmMeshQuadric): undefined / null = the defaults, or an object with
-// threshold (eigenvalues at or below threshold * the largest are dropped from a cluster's solve, in [0, 1))
-const MESH_QUADRIC_DEFAULTS = { threshold: 0.1 };
-function meshQuadric(opts) {
-  const p = { ...MESH_QUADRIC_DEFAULTS };
-  if (opts !== undefined && opts !== null) {
-    if (typeof opts !== "object") throw new TypeError("mesh: expected an object of quadric parameters");
-    for (const [k, v] of Object.entries(opts)) {
-      if (!(k in MESH_QUADRIC_DEFAULTS)) throw new TypeError("mesh: unknown quadric parameter " + k);
-      p[k] = v;
-    }
-  }
-  if (!finite(p.threshold) || !(Math.fround(p.threshold) >= 0 && Math.fround(p.threshold) < 1)) throw new RangeError("mesh: quadric threshold must be finite and in [0, 1)");
-  return p;
-}
-
-// the occlusion block of extractMesh (include/hip_raymarch.h RmMeshOcclusion): undefined / null = the defaults, or an object with some of radius
-// (the first tap's distance, in [2^-64, 2^64]), directions (1, 2, 4, ... 64), taps (1, 2, 4, 8), normalDelta (> 0), strength (in [0, 4]) and flags
-// (RM.RENDER_FAST, RM.RENDER_NO_CULL); checked as the library checks it
-const MESH_OCCLUSION_DEFAULTS = { radius: 0.25, directions: 16, taps: 4, normalDelta: 2 ** -10, strength: 1, flags: 0 };
-function meshOcclusion(opts) {
-  const p = { ...MESH_OCCLUSION_DEFAULTS };
-  if (opts !== undefined && opts !== null) {
-    if (typeof opts !== "object") throw new TypeError("mesh: expected an object of occlusion parameters");
-    for (const [k, v] of Object.entries(opts)) {
-      if (!(k in MESH_OCCLUSION_DEFAULTS)) throw new TypeError("mesh: unknown occlusion parameter " + k);
-      p[k] = v;
-    }
-  }
-  if (!finite(p.radius) || !(Math.fround(p.radius) >= 2 ** -64 && Math.fround(p.radius) <= 2 ** 64)) throw new RangeError("mesh: occlusion radius must be finite and in [2^-64, 2^64]");
-  if (![1, 2, 4, 8, 16, 32, 64].includes(p.directions)) throw new RangeError("mesh: occlusion directions must be one of 1, 2, 4, 8, 16, 32, 64");
-  if (![1, 2, 4, 8].includes(p.taps)) throw new RangeError("mesh: occlusion taps must be one of 1, 2, 4, 8");
-  if (!POSITIVE[0](p.normalDelta) || !POSITIVE[0](Math.fround(p.normalDelta))) throw new RangeError("mesh: occlusion normalDelta " + POSITIVE[1]);
-  if (!finite(p.strength) || !(Math.fround(p.strength) >= 0 && Math.fround(p.strength) <= 4)) throw new RangeError("mesh: occlusion strength must be finite and in [0, 4]");
-  if (!Number.isInteger(p.flags) || (p.flags & ~(RM.RENDER_FAST | RM.RENDER_NO_CULL)) !== 0) throw new RangeError("mesh: occlusion flags must be 0, RM.RENDER_FAST, RM.RENDER_NO_CULL or both");
-  return p;
-}
-
-// the projection block of rm_mesh_project (include/hip_raymarch.h RmMeshProject): undefined / null = the defaults, or an object with some of iso
-// (the level to project onto), rounds (1..16), relax (in (0, 1]), tolerance (>= 0), reach (>= 0; 0 = no limit), normalDelta (> 0) and flags
-// (RM.RENDER_FAST, RM.RENDER_NO_CULL); checked as the library checks it
-const MESH_PROJECT_DEFAULTS = { iso: 0, rounds: 4, relax: 1, tolerance: 0, reach: 0, normalDelta: 2 ** -10, flags: 0 };
-function meshProject(opts) {
-  const p = { ...MESH_PROJECT_DEFAULTS };
-  if (opts !== undefined && opts !== null) {
-    if (typeof opts !== "object") throw new TypeError("mesh: expected an object of project parameters");
-    for (const [k, v] of Object.entries(opts)) {
-      if (!(k in MESH_PROJECT_DEFAULTS)) throw new TypeError("mesh: unknown project parameter " + k);
-      p[k] = v;
-    }
-  }
-  if (!finite(p.iso) || !finite(Math.fround(p.iso))) throw new RangeError("mesh: project iso must be finite");
-  if (!Number.isInteger(p.rounds) || p.rounds < 1 || p.rounds > 16) throw new RangeError("mesh: project rounds must be an integer in 1..16");
-  if (!finite(p.relax) || !(Math.fround(p.relax) > 0 && Math.fround(p.relax) <= 1)) throw new RangeError("mesh: project relax must be finite and in (0, 1]");
-  if (!finite(p.tolerance) || !finite(Math.fround(p.tolerance)) || !(p.tolerance >= 0)) throw new RangeError("mesh: project tolerance must be finite and >= 0");
-  if (!finite(p.reach) || !finite(Math.fround(p.reach)) || !(p.reach >= 0)) throw new RangeError("mesh: project reach must be finite and >= 0");
-  if (!POSITIVE[0](p.normalDelta) || !POSITIVE[0](Math.fround(p.normalDelta))) throw new RangeError("mesh: project normalDelta " + POSITIVE[1]);
-  if (!Number.isInteger(p.flags) || (p.flags & ~(RM.RENDER_FAST | RM.RENDER_NO_CULL)) !== 0) throw new RangeError("mesh: project flags must be 0, RM.RENDER_FAST, RM.RENDER_NO_CULL or both");
-  return p;
 }
 
 // the reach extractMesh(..., project) takes when none is given: half the smallest cell side of the grid, 0.5f * min h[a] with h in fp32 by RmGrid's rule
@@ -907,24 +755,39 @@ function meshProjectReach(grid) {
   return Math.fround(0.5 * least);
 }
 
-// the block of rm_mesh_deviation (include/hip_raymarch.h RmMeshDeviation): undefined / null = the defaults, or an object with some of iso (the
-// level the mesh stands for), order (n = 1, 2, 4 or 8: n * n samples per triangle), tolerance (>= 0: a triangle whose largest |distance - iso|
-// exceeds it counts as over) and flags (RM.RENDER_FAST, RM.RENDER_NO_CULL); checked as the library checks it
-const MESH_DEVIATION_DEFAULTS = { iso: 0, order: 4, tolerance: 0, flags: 0 };
-function meshDeviation(opts) {
-  const p = { ...MESH_DEVIATION_DEFAULTS };
-  if (opts !== undefined && opts !== null) {
-    if (typeof opts !== "object") throw new TypeError("mesh: expected an object of deviation parameters");
-    for (const [k, v] of Object.entries(opts)) {
-      if (!(k in MESH_DEVIATION_DEFAULTS)) throw new TypeError("mesh: unknown deviation parameter " + k);
-      p[k] = v;
-    }
-  }
-  if (!finite(p.iso) || !finite(Math.fround(p.iso))) throw new RangeError("mesh: deviation iso must be finite");
-  if (![1, 2, 4, 8].includes(p.order)) throw new RangeError("mesh: deviation order must be 1, 2, 4 or 8");
-  if (!finite(p.tolerance) || !finite(Math.fround(p.tolerance)) || !(p.tolerance >= 0)) throw new RangeError("mesh: deviation tolerance must be finite and >= 0");
-  if (!Number.isInteger(p.flags) || (p.flags & ~(RM.RENDER_FAST | RM.RENDER_NO_CULL)) !== 0) throw new RangeError("mesh: deviation flags must be 0, RM.RENDER_FAST, RM.RENDER_NO_CULL or both");
-  return p;
+// Every option of extractMesh / meshFromValues as the addon takes it, each normalised once: a block that is undefined / null is null, true is the
+// block's defaults, slabs as a number is { layers }; project and deviation take true as {} and get the extraction's iso (project also the reach
+// of the grid the mesh lies on) where theirs is not given; components and measures are booleans.  When several options are wrong, the first in
+// this order speaks.
+function meshOptions(grid, opts, given) {
+  const absent = (v) => v === undefined || v === null;
+  const block = (make, v) => absent(v) ? null : make(v === true ? undefined : v);
+  const scenePass = (make, label, v, filled) => {
+    if (absent(v)) return null;
+    const asked = v === true ? {} : v;
+    if (typeof asked !== "object") throw new TypeError("mesh: expected true or an object of " + label + " parameters");
+    return make({ ...filled(), ...asked });
+  };
+  const o = { components: !!given.components, measures: !!given.measures };
+  o.quadric = block(meshQuadric, given.quadric);
+  if (o.quadric !== null && absent(given.simplify)) throw new TypeError("mesh: quadric places the vertices of a simplification: give simplify as well");
+  o.params = meshParams(opts);
+  o.simplify = absent(given.simplify) ? null : meshSimplify(given.simplify);
+  o.deviation = scenePass(meshDeviation, "deviation", given.deviation, () => ({ iso: o.params.iso }));
+  o.project = scenePass(meshProject, "project", given.project, () => ({ iso: o.params.iso, reach: meshProjectReach(o.simplify !== null ? o.simplify.grid : grid) }));
+  o.occlusion = block(meshOcclusion, given.occlusion);
+  o.sharp = block(meshSharp, given.sharp);
+  o.keep = block(meshKeep, given.keep);
+  o.slabs = block(meshSlabs, typeof given.slabs === "number" ? { layers: given.slabs } : given.slabs);
+  if (o.slabs === null && grid && grid.slabs) throw new TypeError("mesh: a grid made with slabs: true is extracted in slabs: give slabs as well");
+  return o;
+}
+// The addon's argument list of a mesh call, cut as the addon's optional arguments allow: the trailing entries that are null or false are
+// dropped, never below the `fixed` leading ones; the components flag (behind `keepAt`) travels with its keep block.
+function meshArguments(args, fixed, keepAt) {
+  let n = args.length;
+  while (n > fixed && (args[n - 1] === null || args[n - 1] === false)) n--;
+  return args.slice(0, n === keepAt + 1 ? n + 1 : n);
 }
 
 // binary little-endian PLY of { positions, triangles, normals?, colours?, occlusion? }: x y z, then nx ny nz, then uchar red green blue

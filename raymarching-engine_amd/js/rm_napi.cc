@@ -477,35 +477,41 @@ static bool get_grid(napi_env env, napi_value v, RmGrid* g) {
   return true;
 }
 
-static bool get_mesh_params(napi_env env, napi_value v, RmMeshParams* p) {
-  rm_mesh_params_default(p);
-  return get_block(env, v, p, MESH_FIELDS);
-}
-
 static const Field MESH_SHARP_FIELDS[] = {{"refine", Field::INT, offsetof(RmMeshSharp, refine)}, {"normalDelta", Field::FLOAT, offsetof(RmMeshSharp, normal_delta)},
                                           {"threshold", Field::FLOAT, offsetof(RmMeshSharp, threshold)}};
-// the sharp block of extractMesh: null / undefined = none (*given = false), an object = rm_mesh_extract_sharp with its fields over the defaults
-static bool get_mesh_sharp(napi_env env, napi_value v, RmMeshSharp* s, bool* given) {
-  rm_mesh_sharp_default(s);
-  return get_block(env, v, s, MESH_SHARP_FIELDS, given);
+static const Field MESH_KEEP_FIELDS[] = {{"minTriangles", Field::INT, offsetof(RmMeshKeep, min_triangles)}, {"largest", Field::INT, offsetof(RmMeshKeep, largest)}};
+static const Field MESH_SIMPLIFY_FIELDS[] = {{"keepDuplicates", Field::FLAG, offsetof(RmMeshSimplify, keep_duplicates)}};
+static const Field MESH_QUADRIC_FIELDS[] = {{"threshold", Field::FLOAT, offsetof(RmMeshQuadric, threshold)}};
+static const Field MESH_OCCLUSION_FIELDS[] = {{"radius", Field::FLOAT, offsetof(RmMeshOcclusion, radius)}, {"directions", Field::INT, offsetof(RmMeshOcclusion, directions)},
+                                              {"taps", Field::INT, offsetof(RmMeshOcclusion, taps)}, {"normalDelta", Field::FLOAT, offsetof(RmMeshOcclusion, normal_delta)},
+                                              {"strength", Field::FLOAT, offsetof(RmMeshOcclusion, strength)}, {"flags", Field::INT, offsetof(RmMeshOcclusion, flags)}};
+static const Field MESH_PROJECT_FIELDS[] = {{"iso", Field::FLOAT, offsetof(RmMeshProject, iso)}, {"rounds", Field::INT, offsetof(RmMeshProject, rounds)},
+                                            {"relax", Field::FLOAT, offsetof(RmMeshProject, relax)}, {"tolerance", Field::FLOAT, offsetof(RmMeshProject, tolerance)},
+                                            {"reach", Field::FLOAT, offsetof(RmMeshProject, reach)}, {"normalDelta", Field::FLOAT, offsetof(RmMeshProject, normal_delta)},
+                                            {"flags", Field::INT, offsetof(RmMeshProject, flags)}};
+static const Field MESH_DEVIATION_FIELDS[] = {{"iso", Field::FLOAT, offsetof(RmMeshDeviation, iso)}, {"order", Field::INT, offsetof(RmMeshDeviation, order)},
+                                              {"tolerance", Field::FLOAT, offsetof(RmMeshDeviation, tolerance)}, {"flags", Field::INT, offsetof(RmMeshDeviation, flags)}};
+static const Field MESH_SLABS_FIELDS[] = {{"layers", Field::INT, offsetof(RmMeshSlabs, layers)}};
+
+// A block of the mesh calls of a JS value: the library's defaults, then get_block's rules (null / undefined = the defaults and *given = false,
+// an object = its fields over them)
+template <class T, size_t N>
+static bool get_mesh_block(napi_env env, napi_value v, T* block, const Field (&fields)[N], void (*defaults)(T*), bool* given = nullptr) {
+  defaults(block);
+  return get_block(env, v, block, fields, given);
 }
 
-// meshSharpBlock(sharp | null) -> ArrayBuffer(RmMeshSharp): the bytes extractMesh hands to the library (null: the defaults)
-static napi_value MeshSharpBlock(napi_env env, napi_callback_info info) {
-  size_t argc = 1;
-  napi_value argv[1];
-  NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
-  RmMeshSharp s;
-  bool given = false;
-  if (argc != 1 || !get_mesh_sharp(env, argv[0], &s, &given)) {
-    napi_throw_type_error(env, nullptr, "meshSharpBlock(sharp | null)");
-    return nullptr;
-  }
-  napi_value b;
-  void* d = nullptr;
-  NAPI_OK(napi_create_arraybuffer(env, sizeof s, &d, &b));
-  std::memcpy(d, &s, sizeof s);
-  return b;
+// the simplify block: an object { grid: { lo, hi, n }, keepDuplicates } = rm_mesh_simplify on that grid of clusters
+struct MeshSimplifyBlock {
+  RmGrid clusters;
+  RmMeshSimplify params;
+};
+static bool get_mesh_simplify(napi_env env, napi_value v, MeshSimplifyBlock* s, bool* given) {
+  std::memset(&s->clusters, 0, sizeof s->clusters);
+  if (!get_mesh_block(env, v, &s->params, MESH_SIMPLIFY_FIELDS, rm_mesh_simplify_default, given)) return false;
+  if (!*given) return true;
+  napi_value g;
+  return napi_get_named_property(env, v, "grid", &g) == napi_ok && get_grid(env, g, &s->clusters);
 }
 
 // any value as its truth (JavaScript's ToBoolean)
@@ -514,195 +520,40 @@ static bool get_bool(napi_env env, napi_value v, bool* out) {
   return napi_coerce_to_bool(env, v, &b) == napi_ok && napi_get_value_bool(env, b, out) == napi_ok;
 }
 
-static const Field MESH_KEEP_FIELDS[] = {{"minTriangles", Field::INT, offsetof(RmMeshKeep, min_triangles)}, {"largest", Field::INT, offsetof(RmMeshKeep, largest)}};
-// the keep block of extractMesh / meshFromValues: null / undefined = none (*given = false), an object = rm_mesh_filter with its fields over the defaults
-static bool get_mesh_keep(napi_env env, napi_value v, RmMeshKeep* k, bool* given) {
-  rm_mesh_keep_default(k);
-  return get_block(env, v, k, MESH_KEEP_FIELDS, given);
-}
-
-// meshKeepBlock(keep | null) -> ArrayBuffer(RmMeshKeep): the bytes the mesh calls hand to rm_mesh_filter (null: the defaults)
-static napi_value MeshKeepBlock(napi_env env, napi_callback_info info) {
-  size_t argc = 1;
-  napi_value argv[1];
-  NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
-  RmMeshKeep k;
-  bool given = false;
-  if (argc != 1 || !get_mesh_keep(env, argv[0], &k, &given)) {
-    napi_throw_type_error(env, nullptr, "meshKeepBlock(keep | null)");
-    return nullptr;
-  }
-  napi_value b;
-  void* d = nullptr;
-  NAPI_OK(napi_create_arraybuffer(env, sizeof k, &d, &b));
-  std::memcpy(d, &k, sizeof k);
-  return b;
-}
-
-static const Field MESH_SIMPLIFY_FIELDS[] = {{"keepDuplicates", Field::FLAG, offsetof(RmMeshSimplify, keep_duplicates)}};
-// the simplify block of extractMesh / meshFromValues: null / undefined = none (*given = false), an object { grid: { lo, hi, n }, keepDuplicates } =
-// rm_mesh_simplify on that grid of clusters
-struct MeshSimplifyBlock {
-  RmGrid clusters;
-  RmMeshSimplify params;
-};
-static bool get_mesh_simplify(napi_env env, napi_value v, MeshSimplifyBlock* s, bool* given) {
-  rm_mesh_simplify_default(&s->params);
-  std::memset(&s->clusters, 0, sizeof s->clusters);
-  if (!get_block(env, v, &s->params, MESH_SIMPLIFY_FIELDS, given)) return false;
-  if (!*given) return true;
-  napi_value g;
-  return napi_get_named_property(env, v, "grid", &g) == napi_ok && get_grid(env, g, &s->clusters);
-}
-
-// meshSimplifyBlock(simplify) -> { grid: ArrayBuffer(RmGrid), params: ArrayBuffer(RmMeshSimplify) }: the bytes the mesh calls hand to rm_mesh_simplify
-static napi_value MeshSimplifyBlockOf(napi_env env, napi_callback_info info) {
-  size_t argc = 1;
-  napi_value argv[1];
-  NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
-  MeshSimplifyBlock s;
-  bool given = false;
-  if (argc != 1 || !get_mesh_simplify(env, argv[0], &s, &given) || !given) {
-    napi_throw_type_error(env, nullptr, "meshSimplifyBlock(simplify: { grid: { lo, hi, n }, keepDuplicates })");
-    return nullptr;
-  }
-  napi_value o, gb, pb;
-  void *gd = nullptr, *pd = nullptr;
-  NAPI_OK(napi_create_object(env, &o));
-  NAPI_OK(napi_create_arraybuffer(env, sizeof s.clusters, &gd, &gb));
-  NAPI_OK(napi_create_arraybuffer(env, sizeof s.params, &pd, &pb));
-  std::memcpy(gd, &s.clusters, sizeof s.clusters);
-  std::memcpy(pd, &s.params, sizeof s.params);
-  NAPI_OK(napi_set_named_property(env, o, "grid", gb));
-  NAPI_OK(napi_set_named_property(env, o, "params", pb));
-  return o;
-}
-
-static const Field MESH_QUADRIC_FIELDS[] = {{"threshold", Field::FLOAT, offsetof(RmMeshQuadric, threshold)}};
-// the quadric block of extractMesh / meshFromValues: null / undefined = none (*given = false), an object = rm_mesh_simplify_quadric in place of
-// rm_mesh_simplify, with its fields over the defaults
-static bool get_mesh_quadric(napi_env env, napi_value v, RmMeshQuadric* q, bool* given) {
-  rm_mesh_quadric_default(q);
-  return get_block(env, v, q, MESH_QUADRIC_FIELDS, given);
-}
-
-// meshQuadricBlock(quadric | null) -> ArrayBuffer(RmMeshQuadric): the bytes the mesh calls hand to rm_mesh_simplify_quadric (null: the defaults)
-static napi_value MeshQuadricBlock(napi_env env, napi_callback_info info) {
-  size_t argc = 1;
-  napi_value argv[1];
-  NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
-  RmMeshQuadric q;
-  bool given = false;
-  if (argc != 1 || !get_mesh_quadric(env, argv[0], &q, &given)) {
-    napi_throw_type_error(env, nullptr, "meshQuadricBlock(quadric | null)");
-    return nullptr;
-  }
-  napi_value b;
-  void* d = nullptr;
-  NAPI_OK(napi_create_arraybuffer(env, sizeof q, &d, &b));
-  std::memcpy(d, &q, sizeof q);
-  return b;
-}
-
-static const Field MESH_OCCLUSION_FIELDS[] = {{"radius", Field::FLOAT, offsetof(RmMeshOcclusion, radius)}, {"directions", Field::INT, offsetof(RmMeshOcclusion, directions)},
-                                              {"taps", Field::INT, offsetof(RmMeshOcclusion, taps)}, {"normalDelta", Field::FLOAT, offsetof(RmMeshOcclusion, normal_delta)},
-                                              {"strength", Field::FLOAT, offsetof(RmMeshOcclusion, strength)}, {"flags", Field::INT, offsetof(RmMeshOcclusion, flags)}};
-// the occlusion block of extractMesh: null / undefined = none (*given = false), an object = rm_mesh_occlusion on the mesh that is returned, with
-// its fields over the defaults
-static bool get_mesh_occlusion(napi_env env, napi_value v, RmMeshOcclusion* o, bool* given) {
-  rm_mesh_occlusion_default(o);
-  return get_block(env, v, o, MESH_OCCLUSION_FIELDS, given);
-}
-
-static const Field MESH_PROJECT_FIELDS[] = {{"iso", Field::FLOAT, offsetof(RmMeshProject, iso)}, {"rounds", Field::INT, offsetof(RmMeshProject, rounds)},
-                                            {"relax", Field::FLOAT, offsetof(RmMeshProject, relax)}, {"tolerance", Field::FLOAT, offsetof(RmMeshProject, tolerance)},
-                                            {"reach", Field::FLOAT, offsetof(RmMeshProject, reach)}, {"normalDelta", Field::FLOAT, offsetof(RmMeshProject, normal_delta)},
-                                            {"flags", Field::INT, offsetof(RmMeshProject, flags)}};
-// the block of rm_mesh_project: null / undefined = none (*given = false), an object = its fields over the defaults
-static bool get_mesh_project(napi_env env, napi_value v, RmMeshProject* p, bool* given) {
-  rm_mesh_project_default(p);
-  return get_block(env, v, p, MESH_PROJECT_FIELDS, given);
-}
-
-// meshProjectBlock(project | null) -> ArrayBuffer(RmMeshProject): the bytes a host hands to rm_mesh_project (null: the defaults)
-static napi_value MeshProjectBlock(napi_env env, napi_callback_info info) {
-  size_t argc = 1;
-  napi_value argv[1];
-  NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
-  RmMeshProject p;
-  bool given = false;
-  if (argc != 1 || !get_mesh_project(env, argv[0], &p, &given)) {
-    napi_throw_type_error(env, nullptr, "meshProjectBlock(project | null)");
-    return nullptr;
-  }
-  napi_value b;
-  void* d = nullptr;
-  NAPI_OK(napi_create_arraybuffer(env, sizeof p, &d, &b));
-  std::memcpy(d, &p, sizeof p);
-  return b;
-}
-
-static const Field MESH_DEVIATION_FIELDS[] = {{"iso", Field::FLOAT, offsetof(RmMeshDeviation, iso)}, {"order", Field::INT, offsetof(RmMeshDeviation, order)},
-                                              {"tolerance", Field::FLOAT, offsetof(RmMeshDeviation, tolerance)}, {"flags", Field::INT, offsetof(RmMeshDeviation, flags)}};
-// the block of rm_mesh_deviation: null / undefined = none (*given = false), an object = its fields over the defaults
-static bool get_mesh_deviation(napi_env env, napi_value v, RmMeshDeviation* p, bool* given) {
-  rm_mesh_deviation_default(p);
-  return get_block(env, v, p, MESH_DEVIATION_FIELDS, given);
-}
-
-// meshDeviationBlock(deviation | null) -> ArrayBuffer(RmMeshDeviation): the bytes a host hands to rm_mesh_deviation (null: the defaults)
-static napi_value MeshDeviationBlock(napi_env env, napi_callback_info info) {
-  size_t argc = 1;
-  napi_value argv[1];
-  NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
-  RmMeshDeviation p;
-  bool given = false;
-  if (argc != 1 || !get_mesh_deviation(env, argv[0], &p, &given)) {
-    napi_throw_type_error(env, nullptr, "meshDeviationBlock(deviation | null)");
-    return nullptr;
-  }
-  napi_value b;
-  void* d = nullptr;
-  NAPI_OK(napi_create_arraybuffer(env, sizeof p, &d, &b));
-  std::memcpy(d, &p, sizeof p);
-  return b;
-}
-
-// meshOcclusionBlock(occlusion | null) -> ArrayBuffer(RmMeshOcclusion): the bytes extractMesh hands to rm_mesh_occlusion (null: the defaults)
-static napi_value MeshOcclusionBlock(napi_env env, napi_callback_info info) {
-  size_t argc = 1;
-  napi_value argv[1];
-  NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
-  RmMeshOcclusion o;
-  bool given = false;
-  if (argc != 1 || !get_mesh_occlusion(env, argv[0], &o, &given)) {
-    napi_throw_type_error(env, nullptr, "meshOcclusionBlock(occlusion | null)");
-    return nullptr;
-  }
-  napi_value b;
-  void* d = nullptr;
-  NAPI_OK(napi_create_arraybuffer(env, sizeof o, &d, &b));
-  std::memcpy(d, &o, sizeof o);
-  return b;
-}
-
 static napi_value make_array(napi_env env, napi_typedarray_type type, size_t count, void** data) {
   napi_value ab, out;
   if (napi_create_arraybuffer(env, count * 4, data, &ab) != napi_ok || napi_create_typedarray(env, type, count, ab, 0, &out) != napi_ok) return nullptr;
   return out;
 }
 
-// meshBlocks(grid, params | null) -> { grid: ArrayBuffer(RmGrid), params: ArrayBuffer(RmMeshParams) }: the bytes the calls below hand to the library
-static napi_value MeshBlocks(napi_env env, napi_callback_info info) {
-  size_t argc = 2;
-  napi_value argv[2];
+// The seven exports mesh<Name>Block(block | null) -> ArrayBuffer(the block's struct): the bytes the mesh calls hand to the library (null: the defaults)
+template <class T, size_t N>
+static napi_value mesh_block_bytes(napi_env env, napi_callback_info info, const Field (&fields)[N], void (*defaults)(T*), const char* usage) {
+  size_t argc = 1;
+  napi_value argv[1];
   NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
-  RmGrid g;
-  RmMeshParams p;
-  if (argc != 2 || !get_grid(env, argv[0], &g) || !get_mesh_params(env, argv[1], &p)) {
-    napi_throw_type_error(env, nullptr, "meshBlocks(grid: { lo, hi, n }, params | null)");
+  T block;
+  if (argc != 1 || !get_mesh_block(env, argv[0], &block, fields, defaults)) {
+    napi_throw_type_error(env, nullptr, usage);
     return nullptr;
   }
+  napi_value b;
+  void* d = nullptr;
+  NAPI_OK(napi_create_arraybuffer(env, sizeof block, &d, &b));
+  std::memcpy(d, &block, sizeof block);
+  return b;
+}
+static napi_value MeshSharpBlock(napi_env env, napi_callback_info info) { return mesh_block_bytes(env, info, MESH_SHARP_FIELDS, rm_mesh_sharp_default, "meshSharpBlock(sharp | null)"); }
+static napi_value MeshKeepBlock(napi_env env, napi_callback_info info) { return mesh_block_bytes(env, info, MESH_KEEP_FIELDS, rm_mesh_keep_default, "meshKeepBlock(keep | null)"); }
+static napi_value MeshQuadricBlock(napi_env env, napi_callback_info info) { return mesh_block_bytes(env, info, MESH_QUADRIC_FIELDS, rm_mesh_quadric_default, "meshQuadricBlock(quadric | null)"); }
+static napi_value MeshOcclusionBlock(napi_env env, napi_callback_info info) { return mesh_block_bytes(env, info, MESH_OCCLUSION_FIELDS, rm_mesh_occlusion_default, "meshOcclusionBlock(occlusion | null)"); }
+static napi_value MeshProjectBlock(napi_env env, napi_callback_info info) { return mesh_block_bytes(env, info, MESH_PROJECT_FIELDS, rm_mesh_project_default, "meshProjectBlock(project | null)"); }
+static napi_value MeshDeviationBlock(napi_env env, napi_callback_info info) { return mesh_block_bytes(env, info, MESH_DEVIATION_FIELDS, rm_mesh_deviation_default, "meshDeviationBlock(deviation | null)"); }
+static napi_value MeshSlabsBlock(napi_env env, napi_callback_info info) { return mesh_block_bytes(env, info, MESH_SLABS_FIELDS, rm_mesh_slabs_default, "meshSlabsBlock(slabs | null)"); }
+
+// { grid: ArrayBuffer(RmGrid), params: ArrayBuffer(the block's struct) }: what meshBlocks and meshSimplifyBlock return
+template <class T>
+static napi_value grid_and_params(napi_env env, const RmGrid& g, const T& p) {
   napi_value o, gb, pb;
   void *gd = nullptr, *pd = nullptr;
   NAPI_OK(napi_create_object(env, &o));
@@ -713,6 +564,34 @@ static napi_value MeshBlocks(napi_env env, napi_callback_info info) {
   NAPI_OK(napi_set_named_property(env, o, "grid", gb));
   NAPI_OK(napi_set_named_property(env, o, "params", pb));
   return o;
+}
+
+// meshSimplifyBlock(simplify) -> the bytes the mesh calls hand to rm_mesh_simplify; there is no default grid, so a block must be given
+static napi_value MeshSimplifyBlockOf(napi_env env, napi_callback_info info) {
+  size_t argc = 1;
+  napi_value argv[1];
+  NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+  MeshSimplifyBlock s;
+  bool given = false;
+  if (argc != 1 || !get_mesh_simplify(env, argv[0], &s, &given) || !given) {
+    napi_throw_type_error(env, nullptr, "meshSimplifyBlock(simplify: { grid: { lo, hi, n }, keepDuplicates })");
+    return nullptr;
+  }
+  return grid_and_params(env, s.clusters, s.params);
+}
+
+// meshBlocks(grid, params | null) -> the bytes the calls below hand to the library
+static napi_value MeshBlocks(napi_env env, napi_callback_info info) {
+  size_t argc = 2;
+  napi_value argv[2];
+  NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+  RmGrid g;
+  RmMeshParams p;
+  if (argc != 2 || !get_grid(env, argv[0], &g) || !get_mesh_block(env, argv[1], &p, MESH_FIELDS, rm_mesh_params_default)) {
+    napi_throw_type_error(env, nullptr, "meshBlocks(grid: { lo, hi, n }, params | null)");
+    return nullptr;
+  }
+  return grid_and_params(env, g, p);
 }
 
 // sdfGrid(ctx, scene, grid, flags, out: Float32Array(corners)) = rm_sdf_grid
@@ -740,35 +619,43 @@ static napi_value SdfGrid(napi_env env, napi_callback_info info) {
   return nullptr;
 }
 
-// the mesh as { positions, normals | null, colours | null: Float32Array(3 V), triangles: Uint32Array(3 T), cells: Uint32Array(V), timings: [sampling,
-// meshing, attributes] in ms (rm_mesh_timings) }; normals / colours: whether the call asked for them; the handle is destroyed.  keep: the mesh is
-// first filtered on the device (rm_mesh_filter) and the filtered one is what is copied; components: labels: Uint32Array(V) and componentSizes:
-// Uint32Array(2 C) come with it (rm_mesh_components).  simplify: before either, the mesh is clustered on the device (rm_mesh_simplify), so one
-// filter also removes the vertices the clustering left without triangles; with quadric by rm_mesh_simplify_quadric.  occlusion (with the scene):
-// occlusion: Float32Array(V) of the mesh that is returned comes with it (rm_mesh_occlusion), and its milliseconds (probes + taps) as timings[3]
-// measures: that mesh is measured before anything is copied (rm_mesh_measure) and `measures` comes with it: RmMeshMeasures' fields in camel case,
-// the counts as Numbers (all below 2^53: V, T < 2^32, E <= 3 T), lo / hi as arrays of three, closed as a boolean, componentEdges:
-// BigUint64Array(4 C) (rm_mesh_measure_components), milliseconds: [topology, geometry]
+struct Number {
+  const char* name;
+  double value;
+};
+// a table of names and numbers as properties of o
+template <size_t N>
+static bool set_numbers(napi_env env, napi_value o, const Number (&table)[N]) {
+  napi_value v = nullptr;
+  for (const Number& n : table)
+    if (napi_create_double(env, n.value, &v) != napi_ok || napi_set_named_property(env, o, n.name, v) != napi_ok) return false;
+  return true;
+}
+// floats as a JS array of Numbers, or nullptr
+static napi_value float_array(napi_env env, const float* values, uint32_t count) {
+  napi_value a = nullptr, v = nullptr;
+  if (napi_create_array_with_length(env, count, &a) != napi_ok) return nullptr;
+  for (uint32_t k = 0; k < count; k++)
+    if (napi_create_double(env, (double)values[k], &v) != napi_ok || napi_set_element(env, a, k, v) != napi_ok) return nullptr;
+  return a;
+}
+
+// the `measures` of a mesh result: RmMeshMeasures' fields in camel case, the counts as Numbers (all below 2^53: V, T < 2^32, E <= 3 T), lo / hi as
+// arrays of three, closed as a boolean, componentEdges: BigUint64Array(4 C) (rm_mesh_measure_components), milliseconds: [topology, geometry]
 static napi_value measures_object(napi_env env, const RmMeshMeasures& m, const float* ms2, rm_mesh* mesh, bool* rm_failed) {
   *rm_failed = false;
   napi_value o = nullptr, v = nullptr;
   if (napi_create_object(env, &o) != napi_ok) return nullptr;
-  const struct { const char* name; double value; } NUMBERS[] = {
+  const Number NUMBERS[] = {
       {"vertices", (double)m.vertices}, {"triangles", (double)m.triangles}, {"usedVertices", (double)m.used_vertices}, {"skippedTriangles", (double)m.skipped_triangles},
       {"unmeasuredTriangles", (double)m.unmeasured_triangles}, {"finiteVertices", (double)m.finite_vertices}, {"edges", (double)m.edges},
       {"boundaryEdges", (double)m.boundary_edges}, {"regularEdges", (double)m.regular_edges}, {"irregularEdges", (double)m.irregular_edges},
       {"unbalancedEdges", (double)m.unbalanced_edges}, {"euler", (double)m.euler}, {"components", (double)m.components},
       {"closedComponents", (double)m.closed_components}, {"area", m.area}, {"volume", m.volume}};
-  for (const auto& n : NUMBERS)
-    if (napi_create_double(env, n.value, &v) != napi_ok || napi_set_named_property(env, o, n.name, v) != napi_ok) return nullptr;
+  if (!set_numbers(env, o, NUMBERS)) return nullptr;
   const struct { const char* name; const float* values; uint32_t count; } TRIPLES[] = {{"lo", m.lo, 3}, {"hi", m.hi, 3}, {"milliseconds", ms2, 2}};
-  for (const auto& t : TRIPLES) {
-    napi_value a = nullptr;
-    if (napi_create_array_with_length(env, t.count, &a) != napi_ok) return nullptr;
-    for (uint32_t k = 0; k < t.count; k++)
-      if (napi_create_double(env, (double)t.values[k], &v) != napi_ok || napi_set_element(env, a, k, v) != napi_ok) return nullptr;
-    if (napi_set_named_property(env, o, t.name, a) != napi_ok) return nullptr;
-  }
+  for (const auto& t : TRIPLES)
+    if (!(v = float_array(env, t.values, t.count)) || napi_set_named_property(env, o, t.name, v) != napi_ok) return nullptr;
   if (napi_get_boolean(env, m.closed != 0, &v) != napi_ok || napi_set_named_property(env, o, "closed", v) != napi_ok) return nullptr;
   napi_value ab = nullptr, rows = nullptr;
   void* data = nullptr;
@@ -782,10 +669,55 @@ static napi_value measures_object(napi_env env, const RmMeshMeasures& m, const f
   return o;
 }
 
-static napi_value mesh_result(napi_env env, rm_ctx* ctx, rm_mesh* mesh, bool normals, bool colours, const RmMeshKeep* keep = nullptr, bool components = false,
-                              const MeshSimplifyBlock* simplify = nullptr, const RmMeshQuadric* quadric = nullptr, rm_scene* scene = nullptr,
-                              const RmMeshOcclusion* occlusion = nullptr, bool measures = false, const RmMeshProject* project = nullptr,
-                              const RmMeshDeviation* deviation = nullptr) {
+// Every stage a mesh call may run behind its extraction: the blocks, whether each was given, and the scene the scene passes evaluate
+struct MeshStages {
+  RmMeshSharp sharp;
+  RmMeshKeep keep;
+  MeshSimplifyBlock simplify;
+  RmMeshQuadric quadric;
+  RmMeshOcclusion occlusion;
+  RmMeshProject project;
+  RmMeshDeviation deviation;
+  bool has_sharp = false, has_keep = false, components = false, has_simplify = false, has_quadric = false, has_occlusion = false, measures = false,
+       has_project = false, has_deviation = false;
+  bool normals = false, colours = false;  // whether the extraction was asked for them
+  rm_scene* scene = nullptr;
+};
+// the stages as the entries' arguments list them: extractMesh / extractMeshSlabs take all nine, meshFromValues / meshFromValuesSlabs the five without a scene
+enum class Stage { SHARP, KEEP, COMPONENTS, SIMPLIFY, QUADRIC, OCCLUSION, MEASURES, PROJECT, DEVIATION };
+static const Stage SCENE_STAGES[] = {Stage::SHARP, Stage::KEEP, Stage::COMPONENTS, Stage::SIMPLIFY, Stage::QUADRIC, Stage::OCCLUSION, Stage::MEASURES, Stage::PROJECT, Stage::DEVIATION};
+static const Stage VALUES_STAGES[] = {Stage::KEEP, Stage::COMPONENTS, Stage::SIMPLIFY, Stage::QUADRIC, Stage::MEASURES};
+// argv[at ...] as the `accepted` stages (an argument the caller left out is undefined: the stage is off); a quadric block without a simplify block is refused
+template <size_t N>
+static bool get_mesh_stages(napi_env env, const napi_value* argv, size_t at, const Stage (&accepted)[N], MeshStages* m) {
+  for (size_t i = 0; i < N; i++) {
+    const napi_value v = argv[at + i];
+    bool ok = false;
+    switch (accepted[i]) {
+      case Stage::SHARP: ok = get_mesh_block(env, v, &m->sharp, MESH_SHARP_FIELDS, rm_mesh_sharp_default, &m->has_sharp); break;
+      case Stage::KEEP: ok = get_mesh_block(env, v, &m->keep, MESH_KEEP_FIELDS, rm_mesh_keep_default, &m->has_keep); break;
+      case Stage::COMPONENTS: ok = get_bool(env, v, &m->components); break;
+      case Stage::SIMPLIFY: ok = get_mesh_simplify(env, v, &m->simplify, &m->has_simplify); break;
+      case Stage::QUADRIC: ok = get_mesh_block(env, v, &m->quadric, MESH_QUADRIC_FIELDS, rm_mesh_quadric_default, &m->has_quadric); break;
+      case Stage::OCCLUSION: ok = get_mesh_block(env, v, &m->occlusion, MESH_OCCLUSION_FIELDS, rm_mesh_occlusion_default, &m->has_occlusion); break;
+      case Stage::MEASURES: ok = get_bool(env, v, &m->measures); break;
+      case Stage::PROJECT: ok = get_mesh_block(env, v, &m->project, MESH_PROJECT_FIELDS, rm_mesh_project_default, &m->has_project); break;
+      case Stage::DEVIATION: ok = get_mesh_block(env, v, &m->deviation, MESH_DEVIATION_FIELDS, rm_mesh_deviation_default, &m->has_deviation); break;
+    }
+    if (!ok) return false;
+  }
+  return !m->has_quadric || m->has_simplify;
+}
+
+// The mesh behind the stages that were given, as { positions, normals | null, colours | null: Float32Array(3 V), triangles: Uint32Array(3 T), cells:
+// Uint32Array(V), timings: [sampling, meshing, attributes] in ms (rm_mesh_timings) }; every handle is destroyed as soon as the next one exists, the
+// last on the way out.  On the device, in this order: simplify (rm_mesh_simplify, with quadric rm_mesh_simplify_quadric), keep (rm_mesh_filter,
+// which also removes the vertices the clustering left without triangles), project (rm_mesh_project: `projection` and `residual`), measures
+// (rm_mesh_measure: `measures`); then the arrays are copied, with components `labels`: Uint32Array(V) and `componentSizes`: Uint32Array(2 C)
+// (rm_mesh_components); then on the mesh that is returned occlusion (rm_mesh_occlusion: `occlusion`: Float32Array(V), its milliseconds as
+// timings[3]) and deviation (rm_mesh_deviation: `deviation` and `triangleDeviation`: Float32Array(T)).
+static napi_value mesh_result(napi_env env, rm_ctx* ctx, rm_mesh* mesh, const MeshStages& m) {
+  rm_scene* const scene = m.scene;
   struct Guard {  // the handle in hand is destroyed on every way out
     rm_mesh* h;
     ~Guard() { rm_mesh_destroy(h); }
@@ -794,17 +726,17 @@ static napi_value mesh_result(napi_env env, rm_ctx* ctx, rm_mesh* mesh, bool nor
     napi_throw_error(env, nullptr, "N-API call failed while the mesh was copied");
     return nullptr;
   };
-  if (simplify) {
+  if (m.has_simplify) {
     rm_mesh* simplified = nullptr;
-    if (quadric) {
-      if (rm_mesh_simplify_quadric(mesh, &simplify->clusters, &simplify->params, quadric, &simplified) != RM_OK) return throw_rm(env, ctx, "rm_mesh_simplify_quadric");
-    } else if (rm_mesh_simplify(mesh, &simplify->clusters, &simplify->params, &simplified) != RM_OK) return throw_rm(env, ctx, "rm_mesh_simplify");
+    if (m.has_quadric) {
+      if (rm_mesh_simplify_quadric(mesh, &m.simplify.clusters, &m.simplify.params, &m.quadric, &simplified) != RM_OK) return throw_rm(env, ctx, "rm_mesh_simplify_quadric");
+    } else if (rm_mesh_simplify(mesh, &m.simplify.clusters, &m.simplify.params, &simplified) != RM_OK) return throw_rm(env, ctx, "rm_mesh_simplify");
     rm_mesh_destroy(mesh);
     guard.h = mesh = simplified;
   }
-  if (keep) {
+  if (m.has_keep) {
     rm_mesh* filtered = nullptr;
-    if (rm_mesh_filter(mesh, keep, &filtered) != RM_OK) return throw_rm(env, ctx, "rm_mesh_filter");
+    if (rm_mesh_filter(mesh, &m.keep, &filtered) != RM_OK) return throw_rm(env, ctx, "rm_mesh_filter");
     rm_mesh_destroy(mesh);
     guard.h = mesh = filtered;
   }
@@ -815,13 +747,13 @@ static napi_value mesh_result(napi_env env, rm_ctx* ctx, rm_mesh* mesh, bool nor
   RmMeshProjection projected{};
   float projected_ms = 0.0f;
   napi_value residual = nullptr;
-  if (project) {
+  if (m.has_project) {
     unsigned long long before[2] = {0, 0};
     rm_mesh_counts(mesh, before);
     void* data = nullptr;
     if (!(residual = make_array(env, napi_float32_array, (size_t)before[0], &data))) return napi_failed();
     rm_mesh* moved = nullptr;
-    if (rm_mesh_project(mesh, scene, project, &moved, &projected, static_cast<float*>(data)) != RM_OK) return throw_rm(env, ctx, "rm_mesh_project");
+    if (rm_mesh_project(mesh, scene, &m.project, &moved, &projected, static_cast<float*>(data)) != RM_OK) return throw_rm(env, ctx, "rm_mesh_project");
     rm_mesh_destroy(mesh);
     guard.h = mesh = moved;
     float slots[3] = {0.0f, 0.0f, 0.0f};
@@ -830,7 +762,7 @@ static napi_value mesh_result(napi_env env, rm_ctx* ctx, rm_mesh* mesh, bool nor
   }
   RmMeshMeasures measured{};
   float measured_ms[2] = {0.0f, 0.0f};
-  if (measures && rm_mesh_measure(mesh, &measured, measured_ms) != RM_OK) return throw_rm(env, ctx, "rm_mesh_measure");
+  if (m.measures && rm_mesh_measure(mesh, &measured, measured_ms) != RM_OK) return throw_rm(env, ctx, "rm_mesh_measure");
   unsigned long long counts[2] = {0, 0}, parts = 0;
   rm_mesh_counts(mesh, counts);
   enum { ALWAYS, NORMALS, COLOURS, COMPONENTS };  // when an array is there: with every mesh, or when the call asked for it
@@ -844,10 +776,10 @@ static napi_value mesh_result(napi_env env, rm_ctx* ctx, rm_mesh* mesh, bool nor
   for (const auto& a : ARRAYS) {
     napi_value v = nullptr;
     if (a.when == COMPONENTS) {
-      if (!components) continue;  // (no property at all)
+      if (!m.components) continue;  // (no property at all)
       if (rm_mesh_components(mesh, &parts) != RM_OK) return throw_rm(env, ctx, "rm_mesh_download");  // (labelled once, behind the five arrays)
     }
-    if ((a.when == NORMALS && !normals) || (a.when == COLOURS && !colours)) {
+    if ((a.when == NORMALS && !m.normals) || (a.when == COLOURS && !m.colours)) {
       if (napi_get_null(env, &v) != napi_ok) return napi_failed();  // the mesh was made without this array
     } else {
       const size_t count = (size_t)counts[0] * a.per_vertex + (size_t)counts[1] * a.per_triangle + (size_t)parts * a.per_part;
@@ -858,10 +790,10 @@ static napi_value mesh_result(napi_env env, rm_ctx* ctx, rm_mesh* mesh, bool nor
     }
     if (napi_set_named_property(env, o, a.name, v) != napi_ok) return napi_failed();
   }
-  if (project) {  // RmMeshProjection's fields in camel case, the counts as Numbers (all below 2^53), and the milliseconds of the rounds and the normals
-    napi_value r = nullptr, v = nullptr;
+  if (m.has_project) {  // RmMeshProjection's fields in camel case, the counts as Numbers (all below 2^53), and the milliseconds of the rounds and the normals
+    napi_value r = nullptr;
     if (napi_create_object(env, &r) != napi_ok) return napi_failed();
-    const struct { const char* name; double value; } NUMBERS[] = {
+    const Number NUMBERS[] = {
         {"vertices", (double)projected.vertices}, {"triangles", (double)projected.triangles}, {"movedVertices", (double)projected.moved_vertices},
         {"settledBefore", (double)projected.settled_before}, {"settledAfter", (double)projected.settled_after},
         {"nonfiniteBefore", (double)projected.nonfinite_before}, {"nonfiniteAfter", (double)projected.nonfinite_after},
@@ -870,46 +802,36 @@ static napi_value mesh_result(napi_env env, rm_ctx* ctx, rm_mesh* mesh, bool nor
         {"meanBefore", projected.mean_before}, {"rmsBefore", projected.rms_before}, {"meanAfter", projected.mean_after}, {"rmsAfter", projected.rms_after},
         {"maxBefore", (double)projected.max_before}, {"maxAfter", (double)projected.max_after}, {"roundsRun", (double)projected.rounds_run},
         {"milliseconds", (double)projected_ms}};
-    for (const auto& n : NUMBERS)
-      if (napi_create_double(env, n.value, &v) != napi_ok || napi_set_named_property(env, r, n.name, v) != napi_ok) return napi_failed();
-    if (napi_set_named_property(env, o, "projection", r) != napi_ok || napi_set_named_property(env, o, "residual", residual) != napi_ok) return napi_failed();
+    if (!set_numbers(env, r, NUMBERS) || napi_set_named_property(env, o, "projection", r) != napi_ok || napi_set_named_property(env, o, "residual", residual) != napi_ok) return napi_failed();
   }
-  if (occlusion) {
+  if (m.has_occlusion) {
     napi_value v = nullptr;
     void* data = nullptr;
     float ms2[2] = {0.0f, 0.0f};
     if (!(v = make_array(env, napi_float32_array, (size_t)counts[0], &data))) return napi_failed();
-    if (rm_mesh_occlusion(mesh, scene, occlusion, static_cast<float*>(data), ms2) != RM_OK) return throw_rm(env, ctx, "rm_mesh_occlusion");
+    if (rm_mesh_occlusion(mesh, scene, &m.occlusion, static_cast<float*>(data), ms2) != RM_OK) return throw_rm(env, ctx, "rm_mesh_occlusion");
     if (napi_set_named_property(env, o, "occlusion", v) != napi_ok) return napi_failed();
     ms[3] = ms2[0] + ms2[1];
   }
-  if (deviation) {  // RmMeshDeviationReport's fields in camel case, the counts as Numbers (all below 2^53), the milliseconds of both spans; max_t per triangle
-    napi_value r = nullptr, v = nullptr, worst = nullptr;
+  if (m.has_deviation) {  // RmMeshDeviationReport's fields in camel case, the counts as Numbers (all below 2^53), the milliseconds of both spans; max_t per triangle
+    napi_value r = nullptr, worst = nullptr;
     void* data = nullptr;
     RmMeshDeviationReport report{};
     float ms2[2] = {0.0f, 0.0f};
     if (!(worst = make_array(env, napi_float32_array, (size_t)counts[1], &data))) return napi_failed();
-    if (rm_mesh_deviation(mesh, scene, deviation, &report, static_cast<float*>(data), ms2) != RM_OK) return throw_rm(env, ctx, "rm_mesh_deviation");
+    if (rm_mesh_deviation(mesh, scene, &m.deviation, &report, static_cast<float*>(data), ms2) != RM_OK) return throw_rm(env, ctx, "rm_mesh_deviation");
     if (napi_create_object(env, &r) != napi_ok) return napi_failed();
-    const struct { const char* name; double value; } NUMBERS[] = {
+    const Number NUMBERS[] = {
         {"vertices", (double)report.vertices}, {"triangles", (double)report.triangles}, {"skippedTriangles", (double)report.skipped_triangles},
         {"unevaluatedTriangles", (double)report.unevaluated_triangles}, {"nonfiniteSamples", (double)report.nonfinite_samples},
         {"overTriangles", (double)report.over_triangles}, {"worstTriangle", (double)report.worst_triangle}, {"area", report.area},
         {"overArea", report.over_area}, {"meanSigned", report.mean_signed}, {"rms", report.rms}, {"max", (double)report.max},
         {"samples", (double)report.samples}, {"milliseconds", (double)(ms2[0] + ms2[1])}};
-    for (const auto& n : NUMBERS)
-      if (napi_create_double(env, n.value, &v) != napi_ok || napi_set_named_property(env, r, n.name, v) != napi_ok) return napi_failed();
-    if (napi_set_named_property(env, o, "deviation", r) != napi_ok || napi_set_named_property(env, o, "triangleDeviation", worst) != napi_ok) return napi_failed();
+    if (!set_numbers(env, r, NUMBERS) || napi_set_named_property(env, o, "deviation", r) != napi_ok || napi_set_named_property(env, o, "triangleDeviation", worst) != napi_ok) return napi_failed();
   }
-  const uint32_t spans = occlusion ? 4u : 3u;
-  napi_value timings = nullptr;
-  if (napi_create_array_with_length(env, spans, &timings) != napi_ok) return napi_failed();
-  for (uint32_t k = 0; k < spans; k++) {
-    napi_value x;
-    if (napi_create_double(env, (double)ms[k], &x) != napi_ok || napi_set_element(env, timings, k, x) != napi_ok) return napi_failed();
-  }
-  if (napi_set_named_property(env, o, "timings", timings) != napi_ok) return napi_failed();
-  if (measures) {
+  napi_value timings = float_array(env, ms, m.has_occlusion ? 4u : 3u);
+  if (!timings || napi_set_named_property(env, o, "timings", timings) != napi_ok) return napi_failed();
+  if (m.measures) {
     bool rm_failed = false;
     napi_value v = measures_object(env, measured, measured_ms, mesh, &rm_failed);
     if (!v) return rm_failed ? throw_rm(env, ctx, "rm_mesh_measure_components") : napi_failed();
@@ -918,172 +840,86 @@ static napi_value mesh_result(napi_env env, rm_ctx* ctx, rm_mesh* mesh, bool nor
   return o;
 }
 
-// extractMesh(ctx, scene, grid, params | null[, sharp | null[, keep | null[, components[, simplify | null[, quadric | null[, occlusion | null[, measures]]]]]]]) = rm_mesh_extract, or
-// with a sharp block rm_mesh_extract_sharp; with a simplify block rm_mesh_simplify behind it (with a quadric block too: rm_mesh_simplify_quadric);
-// with a keep block rm_mesh_filter behind that; with measures rm_mesh_measure on that last mesh; then the arrays, with an occlusion block
-// rm_mesh_occlusion on that last mesh.  A quadric block without a simplify block is refused.  With a project block rm_mesh_project behind
-// simplify and keep, before the measures, the components and the occlusion: `projection` and `residual` come with the result.  With a
-// deviation block rm_mesh_deviation on the mesh that is returned: `deviation` and `triangleDeviation` come with the result.
-static napi_value ExtractMesh(napi_env env, napi_callback_info info) {
-  size_t argc = 13;
-  napi_value argv[13];
-  NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
-  const bool counted = argc >= 4 && argc <= 13;
-  rm_ctx* ctx = counted ? get_external<rm_ctx>(env, argv[0]) : nullptr;
-  rm_scene* scene = counted ? get_external<rm_scene>(env, argv[1]) : nullptr;
-  RmGrid g;
-  RmMeshParams p;
-  RmMeshSharp s;
-  RmMeshKeep k;
-  MeshSimplifyBlock c;
-  RmMeshQuadric q;
-  RmMeshOcclusion ao;
-  RmMeshProject pr;
-  RmMeshDeviation dv;
-  bool sharp = false, keep = false, components = false, simplify = false, quadric = false, occlusion = false, measures = false, project = false, deviation = false;
-  if (!ctx || !scene || !get_grid(env, argv[2], &g) || !get_mesh_params(env, argv[3], &p) || (argc >= 5 && !get_mesh_sharp(env, argv[4], &s, &sharp)) ||
-      (argc >= 6 && !get_mesh_keep(env, argv[5], &k, &keep)) || (argc >= 7 && !get_bool(env, argv[6], &components)) ||
-      (argc >= 8 && !get_mesh_simplify(env, argv[7], &c, &simplify)) || (argc >= 9 && !get_mesh_quadric(env, argv[8], &q, &quadric)) || (argc >= 10 && !get_mesh_occlusion(env, argv[9], &ao, &occlusion)) || (argc >= 11 && !get_bool(env, argv[10], &measures)) || (argc >= 12 && !get_mesh_project(env, argv[11], &pr, &project)) || (argc == 13 && !get_mesh_deviation(env, argv[12], &dv, &deviation)) || (quadric && !simplify)) {
-    napi_throw_type_error(env, nullptr, "extractMesh(ctx, scene, grid, params | null[, sharp | null[, keep | null[, components[, simplify | null[, quadric | null[, occlusion | null[, measures[, project | null[, deviation | null]]]]]]]]])");
-    return nullptr;
-  }
-  rm_mesh* mesh = nullptr;
-  if (sharp) {
-    if (rm_mesh_extract_sharp(ctx, scene, &g, &p, &s, &mesh) != RM_OK) return throw_rm(env, ctx, "rm_mesh_extract_sharp");
-  } else if (rm_mesh_extract(ctx, scene, &g, &p, &mesh) != RM_OK) return throw_rm(env, ctx, "rm_mesh_extract");
-  return mesh_result(env, ctx, mesh, p.normals != 0, p.colours != 0, keep ? &k : nullptr, components, simplify ? &c : nullptr, quadric ? &q : nullptr, scene,
-                     occlusion ? &ao : nullptr, measures, project ? &pr : nullptr, deviation ? &dv : nullptr);
-}
-
-// meshFromValues(ctx, grid, values: Float32Array(corners), iso[, keep | null[, components[, simplify | null[, quadric | null[, measures]]]]]) = rm_mesh_from_values,
-// with a simplify block rm_mesh_simplify (with a quadric block too: rm_mesh_simplify_quadric) behind it, with a keep block rm_mesh_filter behind
-// that, with measures rm_mesh_measure on that last mesh, then the arrays
-static napi_value MeshFromValues(napi_env env, napi_callback_info info) {
-  size_t argc = 9;
-  napi_value argv[9];
-  NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
-  rm_ctx* ctx = argc >= 4 && argc <= 9 ? get_external<rm_ctx>(env, argv[0]) : nullptr;
-  RmMeshKeep k;
-  MeshSimplifyBlock c;
-  RmMeshQuadric q;
-  bool keep = false, components = false, simplify = false, quadric = false, measures = false;
-  RmGrid g;
-  double iso = 0.0;
-  void* d = nullptr;
-  size_t n = 0;
-  if (!ctx || !get_grid(env, argv[1], &g) || !get_buffer(env, argv[2], &d, &n) || napi_get_value_double(env, argv[3], &iso) != napi_ok ||
-      (argc >= 5 && !get_mesh_keep(env, argv[4], &k, &keep)) || (argc >= 6 && !get_bool(env, argv[5], &components)) ||
-      (argc >= 7 && !get_mesh_simplify(env, argv[6], &c, &simplify)) || (argc >= 8 && !get_mesh_quadric(env, argv[7], &q, &quadric)) || (argc == 9 && !get_bool(env, argv[8], &measures)) || (quadric && !simplify)) {
-    napi_throw_type_error(env, nullptr, "meshFromValues(ctx, grid, values: Float32Array, iso[, keep | null[, components[, simplify | null[, quadric | null[, measures]]]]])");
-    return nullptr;
-  }
-  float probe[1025];
-  if (rm_grid_axis(&g, 0, probe) != RM_OK) return throw_rm(env, nullptr, "rm_mesh_from_values");
-  if (n != (size_t)(g.n[0] + 1) * (size_t)(g.n[1] + 1) * (size_t)(g.n[2] + 1) * sizeof(float)) {
-    napi_throw_range_error(env, nullptr, "meshFromValues: values must hold (nx + 1)(ny + 1)(nz + 1) floats");
-    return nullptr;
-  }
-  rm_mesh* mesh = nullptr;
-  if (rm_mesh_from_values(ctx, &g, static_cast<const float*>(d), (float)iso, &mesh) != RM_OK) return throw_rm(env, ctx, "rm_mesh_from_values");
-  return mesh_result(env, ctx, mesh, false, false, keep ? &k : nullptr, components, simplify ? &c : nullptr, quadric ? &q : nullptr, nullptr, nullptr, measures);
-}
-
-// ---- slabbed extraction: meshSlabsBlock, extractMeshSlabs, meshFromValuesSlabs (include/hip_raymarch.h "slabbed extraction") ----
-static const Field MESH_SLABS_FIELDS[] = {{"layers", Field::INT, offsetof(RmMeshSlabs, layers)}};
-// the slabs block: null / undefined = the defaults, an object = its fields over them
-static bool get_mesh_slabs(napi_env env, napi_value v, RmMeshSlabs* w) {
-  rm_mesh_slabs_default(w);
-  bool given = false;
-  return get_block(env, v, w, MESH_SLABS_FIELDS, &given);
-}
-
-// meshSlabsBlock(slabs | null) -> ArrayBuffer(RmMeshSlabs): the bytes the slabbed mesh calls hand to the library (null: the defaults)
-static napi_value MeshSlabsBlock(napi_env env, napi_callback_info info) {
-  size_t argc = 1;
-  napi_value argv[1];
-  NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
-  RmMeshSlabs w;
-  if (argc != 1 || !get_mesh_slabs(env, argv[0], &w)) {
-    napi_throw_type_error(env, nullptr, "meshSlabsBlock(slabs | null)");
-    return nullptr;
-  }
-  napi_value b;
-  void* d = nullptr;
-  NAPI_OK(napi_create_arraybuffer(env, sizeof w, &d, &b));
-  std::memcpy(d, &w, sizeof w);
-  return b;
-}
-
+// The four mesh entries: each checks its argument count, parses its own leading arguments and then the stages (get_mesh_stages), extracts, and
+// hands the mesh to mesh_result.
+// extractMesh(ctx, scene, grid, params | null[, sharp | null[, keep | null[, components[, simplify | null[, quadric | null[, occlusion | null[, measures[,
+// project | null[, deviation | null]]]]]]]]]) = rm_mesh_extract, or with a sharp block rm_mesh_extract_sharp
 // extractMeshSlabs(ctx, scene, grid, slabs | null, params | null, sharp | null, keep | null, components, simplify | null, quadric | null, occlusion | null,
-// measures): extractMesh with rm_mesh_extract_slabs / rm_mesh_extract_sharp_slabs in place of rm_mesh_extract / _sharp; every argument is given
-static napi_value ExtractMeshSlabs(napi_env env, napi_callback_info info) {
+// measures[, project | null[, deviation | null]]) = rm_mesh_extract_slabs / rm_mesh_extract_sharp_slabs: the first twelve arguments are all given
+static napi_value extract_common(napi_env env, napi_callback_info info, bool slabbed) {
   size_t argc = 14;
   napi_value argv[14];
   NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
-  const bool counted = argc >= 12 && argc <= 14;  // (the thirteenth: a project block, as extractMesh's twelfth; the fourteenth: a deviation block)
+  const bool counted = slabbed ? argc >= 12 && argc <= 14 : argc >= 4 && argc <= 13;
+  const size_t at = slabbed ? 4 : 3;  // where the parameters stand: behind the slabs block, or behind the grid
   rm_ctx* ctx = counted ? get_external<rm_ctx>(env, argv[0]) : nullptr;
-  rm_scene* scene = counted ? get_external<rm_scene>(env, argv[1]) : nullptr;
+  MeshStages m;
+  m.scene = counted ? get_external<rm_scene>(env, argv[1]) : nullptr;
   RmGrid g;
   RmMeshSlabs w;
   RmMeshParams p;
-  RmMeshSharp s;
-  RmMeshKeep k;
-  MeshSimplifyBlock c;
-  RmMeshQuadric q;
-  RmMeshOcclusion ao;
-  RmMeshProject pr;
-  RmMeshDeviation dv;
-  bool sharp = false, keep = false, components = false, simplify = false, quadric = false, occlusion = false, measures = false, project = false, deviation = false;
-  if (!ctx || !scene || !get_grid(env, argv[2], &g) || !get_mesh_slabs(env, argv[3], &w) || !get_mesh_params(env, argv[4], &p) ||
-      !get_mesh_sharp(env, argv[5], &s, &sharp) || !get_mesh_keep(env, argv[6], &k, &keep) || !get_bool(env, argv[7], &components) ||
-      !get_mesh_simplify(env, argv[8], &c, &simplify) || !get_mesh_quadric(env, argv[9], &q, &quadric) || !get_mesh_occlusion(env, argv[10], &ao, &occlusion) ||
-      !get_bool(env, argv[11], &measures) || (argc >= 13 && !get_mesh_project(env, argv[12], &pr, &project)) || (argc == 14 && !get_mesh_deviation(env, argv[13], &dv, &deviation)) || (quadric && !simplify)) {
-    napi_throw_type_error(env, nullptr, "extractMeshSlabs(ctx, scene, grid, slabs | null, params | null, sharp | null, keep | null, components, simplify | null, quadric | null, occlusion | null, measures[, project | null[, deviation | null]])");
+  if (!ctx || !m.scene || !get_grid(env, argv[2], &g) || (slabbed && !get_mesh_block(env, argv[3], &w, MESH_SLABS_FIELDS, rm_mesh_slabs_default)) ||
+      !get_mesh_block(env, argv[at], &p, MESH_FIELDS, rm_mesh_params_default) || !get_mesh_stages(env, argv, at + 1, SCENE_STAGES, &m)) {
+    napi_throw_type_error(env, nullptr, slabbed ? "extractMeshSlabs(ctx, scene, grid, slabs | null, params | null, sharp | null, keep | null, components, simplify | null, quadric | null, occlusion | null, measures[, project | null[, deviation | null]])"
+                                                : "extractMesh(ctx, scene, grid, params | null[, sharp | null[, keep | null[, components[, simplify | null[, quadric | null[, occlusion | null[, measures[, project | null[, deviation | null]]]]]]]]])");
     return nullptr;
   }
+  m.normals = p.normals != 0;
+  m.colours = p.colours != 0;
   rm_mesh* mesh = nullptr;
-  if (sharp) {
-    if (rm_mesh_extract_sharp_slabs(ctx, scene, &g, &p, &s, &w, &mesh) != RM_OK) return throw_rm(env, ctx, "rm_mesh_extract_sharp_slabs");
-  } else if (rm_mesh_extract_slabs(ctx, scene, &g, &p, &w, &mesh) != RM_OK) return throw_rm(env, ctx, "rm_mesh_extract_slabs");
-  return mesh_result(env, ctx, mesh, p.normals != 0, p.colours != 0, keep ? &k : nullptr, components, simplify ? &c : nullptr, quadric ? &q : nullptr, scene,
-                     occlusion ? &ao : nullptr, measures, project ? &pr : nullptr, deviation ? &dv : nullptr);
+  if (slabbed) {
+    if (m.has_sharp) {
+      if (rm_mesh_extract_sharp_slabs(ctx, m.scene, &g, &p, &m.sharp, &w, &mesh) != RM_OK) return throw_rm(env, ctx, "rm_mesh_extract_sharp_slabs");
+    } else if (rm_mesh_extract_slabs(ctx, m.scene, &g, &p, &w, &mesh) != RM_OK) return throw_rm(env, ctx, "rm_mesh_extract_slabs");
+  } else if (m.has_sharp) {
+    if (rm_mesh_extract_sharp(ctx, m.scene, &g, &p, &m.sharp, &mesh) != RM_OK) return throw_rm(env, ctx, "rm_mesh_extract_sharp");
+  } else if (rm_mesh_extract(ctx, m.scene, &g, &p, &mesh) != RM_OK) return throw_rm(env, ctx, "rm_mesh_extract");
+  return mesh_result(env, ctx, mesh, m);
 }
+static napi_value ExtractMesh(napi_env env, napi_callback_info info) { return extract_common(env, info, false); }
+static napi_value ExtractMeshSlabs(napi_env env, napi_callback_info info) { return extract_common(env, info, true); }
 
-// meshFromValuesSlabs(ctx, grid, values: Float32Array(corners), iso, slabs | null, keep | null, components, simplify | null, quadric | null, measures):
-// meshFromValues with rm_mesh_from_values_slabs in place of rm_mesh_from_values; every argument is given
-static napi_value MeshFromValuesSlabs(napi_env env, napi_callback_info info) {
+// meshFromValues(ctx, grid, values: Float32Array(corners), iso[, keep | null[, components[, simplify | null[, quadric | null[, measures]]]]]) = rm_mesh_from_values
+// meshFromValuesSlabs(ctx, grid, values, iso, slabs | null, keep | null, components, simplify | null, quadric | null, measures) = rm_mesh_from_values_slabs:
+// every argument is given
+static napi_value values_common(napi_env env, napi_callback_info info, bool slabbed) {
   size_t argc = 10;
   napi_value argv[10];
   NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
-  rm_ctx* ctx = argc == 10 ? get_external<rm_ctx>(env, argv[0]) : nullptr;
-  RmMeshSlabs w;
-  RmMeshKeep k;
-  MeshSimplifyBlock c;
-  RmMeshQuadric q;
-  bool keep = false, components = false, simplify = false, quadric = false, measures = false;
+  rm_ctx* ctx = (slabbed ? argc == 10 : argc >= 4 && argc <= 9) ? get_external<rm_ctx>(env, argv[0]) : nullptr;
+  MeshStages m;
   RmGrid g;
+  RmMeshSlabs w;
   double iso = 0.0;
   void* d = nullptr;
   size_t n = 0;
   if (!ctx || !get_grid(env, argv[1], &g) || !get_buffer(env, argv[2], &d, &n) || napi_get_value_double(env, argv[3], &iso) != napi_ok ||
-      !get_mesh_slabs(env, argv[4], &w) || !get_mesh_keep(env, argv[5], &k, &keep) || !get_bool(env, argv[6], &components) ||
-      !get_mesh_simplify(env, argv[7], &c, &simplify) || !get_mesh_quadric(env, argv[8], &q, &quadric) || !get_bool(env, argv[9], &measures) || (quadric && !simplify)) {
-    napi_throw_type_error(env, nullptr, "meshFromValuesSlabs(ctx, grid, values: Float32Array, iso, slabs | null, keep | null, components, simplify | null, quadric | null, measures)");
+      (slabbed && !get_mesh_block(env, argv[4], &w, MESH_SLABS_FIELDS, rm_mesh_slabs_default)) || !get_mesh_stages(env, argv, slabbed ? 5 : 4, VALUES_STAGES, &m)) {
+    napi_throw_type_error(env, nullptr, slabbed ? "meshFromValuesSlabs(ctx, grid, values: Float32Array, iso, slabs | null, keep | null, components, simplify | null, quadric | null, measures)"
+                                                : "meshFromValues(ctx, grid, values: Float32Array, iso[, keep | null[, components[, simplify | null[, quadric | null[, measures]]]]])");
     return nullptr;
   }
-  for (int a = 0; a < 3; a++)  // (the size below needs sane counts; the library checks the rest of the grid)
-    if (g.n[a] < 1 || g.n[a] > 1024) {
-      napi_throw_range_error(env, nullptr, "meshFromValuesSlabs: grid n must be in 1..1024 cells per axis");
-      return nullptr;
-    }
-  if (n != (size_t)(g.n[0] + 1) * (size_t)(g.n[1] + 1) * (size_t)(g.n[2] + 1) * sizeof(float)) {
-    napi_throw_range_error(env, nullptr, "meshFromValuesSlabs: values must hold (nx + 1)(ny + 1)(nz + 1) floats");
+  // the size below needs sane counts: the whole grid is checked where 2^28 corners bound it, the counts alone where slabs lift that bound (the
+  // library checks the rest of such a grid)
+  float probe[1025];
+  if (!slabbed) {
+    if (rm_grid_axis(&g, 0, probe) != RM_OK) return throw_rm(env, nullptr, "rm_mesh_from_values");
+  } else if (g.n[0] < 1 || g.n[0] > 1024 || g.n[1] < 1 || g.n[1] > 1024 || g.n[2] < 1 || g.n[2] > 1024) {
+    napi_throw_range_error(env, nullptr, "meshFromValuesSlabs: grid n must be in 1..1024 cells per axis");
+    return nullptr;
+  }
+  if (n !=(size_t)(g.n[0] + 1) * (size_t)(g.n[1] + 1) * (size_t)(g.n[2] + 1) * sizeof(float)) {
+    napi_throw_range_error(env, nullptr, slabbed ? "meshFromValuesSlabs: values must hold (nx + 1)(ny + 1)(nz + 1) floats" : "meshFromValues: values must hold (nx + 1)(ny + 1)(nz + 1) floats");
     return nullptr;
   }
   rm_mesh* mesh = nullptr;
-  if (rm_mesh_from_values_slabs(ctx, &g, static_cast<const float*>(d), (float)iso, &w, &mesh) != RM_OK) return throw_rm(env, ctx, "rm_mesh_from_values_slabs");
-  return mesh_result(env, ctx, mesh, false, false, keep ? &k : nullptr, components, simplify ? &c : nullptr, quadric ? &q : nullptr, nullptr, nullptr, measures);
+  if (slabbed) {
+    if (rm_mesh_from_values_slabs(ctx, &g, static_cast<const float*>(d), (float)iso, &w, &mesh) != RM_OK) return throw_rm(env, ctx, "rm_mesh_from_values_slabs");
+  } else if (rm_mesh_from_values(ctx, &g, static_cast<const float*>(d), (float)iso, &mesh) != RM_OK) return throw_rm(env, ctx, "rm_mesh_from_values");
+  return mesh_result(env, ctx, mesh, m);
 }
+static napi_value MeshFromValues(napi_env env, napi_callback_info info) { return values_common(env, info, false); }
+static napi_value MeshFromValuesSlabs(napi_env env, napi_callback_info info) { return values_common(env, info, true); }
 
 // fbCreateStriped(ctx, width, height, stripeRows, parts, part[, gbuffer]): the stripes k with k % parts == part of a width x height image,
 // planes owned by the library (rm_fb_create_striped) -- what one GPU of a sharded frame holds
