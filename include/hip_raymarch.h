@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define RM_ABI_VERSION 9 /* 9: RM_GBUFFER_F32 / _F16, rm_fb_create_fmt, rm_fb_create_striped_fmt, rm_fb_wrap_fmt, rm_fb_gbuffer, rm_fb_download_raw, rm_fb_upload_raw, RmDenoise, rm_denoise_default, rm_denoise, rm_denoise_device, rm_present_denoised, RM_FB_MOMENTS, RM_PLANE_MOMENTS, rm_fb_has_moments, RmDenoiseVariance, rm_denoise_variance_default, rm_denoise_variance, rm_denoise_variance_device, rm_present_denoised_variance, RmDespeckle, RmFilters, RM_DENOISE_NONE / _ATROUS / _VARIANCE, rm_filters_default, rm_filter, rm_filter_device, rm_present_filtered, RM_STATS_BINS, RmFrameStats, rm_frame_stats, RmAutoExposure, rm_auto_exposure_default, rm_stats_percentile, rm_stats_exposure, RM_TONE_CLIP / _REINHARD / _ACES, RmDisplay, rm_display_default, rm_present_display, rm_present_display_device, rm_present_linear, RmGrid, rm_grid_axis, rm_sdf_grid, rm_sdf_grid_device, RmMeshParams, rm_mesh_params_default, rm_mesh, rm_mesh_extract, rm_mesh_from_values, rm_mesh_counts, rm_mesh_timings, RM_MESH_POSITIONS / _NORMALS / _COLOURS / _TRIANGLES / _CELLS, rm_mesh_download, rm_mesh_device_ptr, rm_mesh_destroy, RmMeshSharp, rm_mesh_sharp_default, rm_mesh_extract_sharp, RmMeshKeep, rm_mesh_keep_default, rm_mesh_components, RM_MESH_PART_LABELS / _SIZES, rm_mesh_components_download, rm_mesh_filter, RmMeshSimplify, rm_mesh_simplify_default, rm_mesh_simplify, RmMeshQuadric, rm_mesh_quadric_default, rm_mesh_simplify_quadric, RmMeshOcclusion, rm_mesh_occlusion_default, rm_mesh_occlusion_directions, rm_mesh_occlusion, RmMeshMeasures, rm_mesh_measure, rm_mesh_measure_components, RmMeshSlabs, rm_mesh_slabs_default, rm_mesh_extract_slabs, rm_mesh_extract_sharp_slabs, rm_mesh_from_values_slabs, RmMeshProject, RmMeshProjection, rm_mesh_project_default, rm_mesh_project, RmMeshDeviation, RmMeshDeviationReport, rm_mesh_deviation_default, rm_mesh_deviation_weights, rm_mesh_deviation (additions only); 8: RM_PRIM_TORUS / _CYLINDER / _PLANE, RM_OP_SMOOTH_SUBTRACT / _INTERSECT, rm_probe_math (additions only); 7: rm_present_sharded_finish / rm_present_sharded take the size of the host buffer (a changed signature), rm_ctx_set_cull_min_pixels, rm_ctx_set_cull_budget, rm_ctx_cull_stats; 6: rm_present_striped_rows, rm_present_sharded_start / _finish, rm_ctx_last_warning, RM_PROBE_CAST_SHADOW, RM_PRIM_KIND (additions only); 3: rm_ctx_set_sample_batch, rm_buffer_*; 4: rm_ctx_set_gl_stack; 5: RmSurface / RmSceneDesc.surfaces (the struct grew), rm_pack_present_rows, rm_present_sharded, rm_ctx_last_pipeline, RM_RENDER_NO_FAR_JUMP, RM_RENDER_NO_CULL (additions only) */
+#define RM_ABI_VERSION 9 /* 9: RM_GBUFFER_F32 / _F16, rm_fb_create_fmt, rm_fb_create_striped_fmt, rm_fb_wrap_fmt, rm_fb_gbuffer, rm_fb_download_raw, rm_fb_upload_raw, RmDenoise, rm_denoise_default, rm_denoise, rm_denoise_device, rm_present_denoised, RM_FB_MOMENTS, RM_PLANE_MOMENTS, rm_fb_has_moments, RmDenoiseVariance, rm_denoise_variance_default, rm_denoise_variance, rm_denoise_variance_device, rm_present_denoised_variance, RmDespeckle, RmFilters, RM_DENOISE_NONE / _ATROUS / _VARIANCE, rm_filters_default, rm_filter, rm_filter_device, rm_present_filtered, RM_STATS_BINS, RmFrameStats, rm_frame_stats, RmAutoExposure, rm_auto_exposure_default, rm_stats_percentile, rm_stats_exposure, RM_TONE_CLIP / _REINHARD / _ACES, RmDisplay, rm_display_default, rm_present_display, rm_present_display_device, rm_present_linear, RmGrid, rm_grid_axis, rm_sdf_grid, rm_sdf_grid_device, RmMeshParams, rm_mesh_params_default, rm_mesh, rm_mesh_extract, rm_mesh_from_values, rm_mesh_counts, rm_mesh_timings, RM_MESH_POSITIONS / _NORMALS / _COLOURS / _TRIANGLES / _CELLS, rm_mesh_download, rm_mesh_device_ptr, rm_mesh_destroy, RmMeshSharp, rm_mesh_sharp_default, rm_mesh_extract_sharp, RmMeshKeep, rm_mesh_keep_default, rm_mesh_components, RM_MESH_PART_LABELS / _SIZES, rm_mesh_components_download, rm_mesh_filter, RmMeshSimplify, rm_mesh_simplify_default, rm_mesh_simplify, RmMeshQuadric, rm_mesh_quadric_default, rm_mesh_simplify_quadric, RmMeshOcclusion, rm_mesh_occlusion_default, rm_mesh_occlusion_directions, rm_mesh_occlusion, RmMeshMeasures, rm_mesh_measure, rm_mesh_measure_components, RmMeshSlabs, rm_mesh_slabs_default, rm_mesh_extract_slabs, rm_mesh_extract_sharp_slabs, rm_mesh_from_values_slabs, RmMeshProject, RmMeshProjection, rm_mesh_project_default, rm_mesh_project, RmMeshDeviation, RmMeshDeviationReport, rm_mesh_deviation_default, rm_mesh_deviation_weights, rm_mesh_deviation, RmMeshRefine, RmMeshRefinement, rm_mesh_refine_default, rm_mesh_refine (additions only); 8: RM_PRIM_TORUS / _CYLINDER / _PLANE, RM_OP_SMOOTH_SUBTRACT / _INTERSECT, rm_probe_math (additions only); 7: rm_present_sharded_finish / rm_present_sharded take the size of the host buffer (a changed signature), rm_ctx_set_cull_min_pixels, rm_ctx_set_cull_budget, rm_ctx_cull_stats; 6: rm_present_striped_rows, rm_present_sharded_start / _finish, rm_ctx_last_warning, RM_PROBE_CAST_SHADOW, RM_PRIM_KIND (additions only); 3: rm_ctx_set_sample_batch, rm_buffer_*; 4: rm_ctx_set_gl_stack; 5: RmSurface / RmSceneDesc.surfaces (the struct grew), rm_pack_present_rows, rm_present_sharded, rm_ctx_last_pipeline, RM_RENDER_NO_FAR_JUMP, RM_RENDER_NO_CULL (additions only) */
 
 #define RM_MAX_BOUNCES 10 /* raymarchingStepCountsArray[10], raymarcher.frag:31 */
 #define RM_MAX_LIGHTS 10  /* lightPositions[10],             raymarcher.frag:37-39 */
@@ -1382,6 +1382,85 @@ RM_API void rm_mesh_deviation_default(RmMeshDeviation* params);
 RM_API int rm_mesh_deviation_weights(int order, float* out); /* S x 4 floats; host arithmetic, no GPU, no context */
 RM_API int rm_mesh_deviation(rm_mesh* mesh, rm_scene* scene, const RmMeshDeviation* params, RmMeshDeviationReport* report, float* triangles_host,
                              float* out_ms2);
+
+/* ---- refinement (opt-in): split the edges that chord a level set of a scene ----
+ * rm_mesh_deviation measures how far triangles lie off the level set; the only lever against it used to be a finer grid everywhere.
+ * rm_mesh_refine is adaptive: it splits only the edges whose MIDPOINT is off the surface, puts the new vertices on the surface (with
+ * rm_mesh_project's arithmetic, when a project block is given) and repeats.  It works on any rm_mesh with any scene of the mesh's context.  The
+ * source is unchanged and may be destroyed first; the result is an ordinary rm_mesh of the same context that every later stage serves.
+ * The criterion looks at edge midpoints only: a triangle's interior can still lie further off than `tolerance`, so rm_mesh_deviation remains
+ * the judge of the result.  d is in the field's own units, as for deviation (a distance ESTIMATE such as the Mandelbulb's is no metric distance).
+ * params == NULL: the defaults (iso 0, tolerance 0, min_edge 0, rounds 1, max_triangles 0, flags 0).  A block is valid iff iso is finite,
+ * tolerance and min_edge are finite and >= 0, rounds is in 1..8, flags are of rm_sdf_grid's set and reserved is 0.  project == NULL: the
+ * midpoints stay where they are; otherwise a block that rm_mesh_project accepts (its own iso, flags and normal_delta apply to it).
+ * Arithmetic: fp32, every operation rounded on its own (no contraction), whatever the flags are: they select only the unit that evaluates the
+ * scene.  One round on a mesh of V vertices and T triangles:
+ *   1. Edge table.  The triangles that TAKE PART are rm_mesh_measure's: all three indices < V and pairwise different.  Every other triangle is
+ *      carried unchanged and takes no part.  Using slot u = 3 t + s is the edge of triangle t from corner s to corner (s + 1) % 3.  Every
+ *      undirected edge (lo, hi) of a participating triangle is entered into a lock-free 64-bit table (the measures' key lo << 32 | hi and
+ *      hash) with an atomicMin of u: the edge's OWNER is its lowest using slot.  The unique edges are numbered in ascending owner order (a flag
+ *      per using slot, the mesher's scan); E is their count.
+ *   2. Evaluation.  For edge e:  m[c] = 0.5f * (p_lo[c] + p_hi[c]);  d[e] = RM_PROBE_SDF's bits at m for these flags on this context.
+ *   3. Marking.  err = d[e] - iso;  dx, dy, dz = p_hi - p_lo;  len2 = (dx * dx + dy * dy) + dz * dz.  The edge is MARKED iff err is finite,
+ *      |err| > tolerance and len2 > min_edge * min_edge (one product).  The marked edges get the new vertex indices V + k, k counting the marked
+ *      edges in edge order (scan).
+ *   4. New vertices.  Position m; colour 0.5f * (c_lo[c] + c_hi[c]) where the mesh has colours; cell that of lo.  Normals are not interpolated
+ *      (see "end of call").  The V old vertices keep their indices and their bits.
+ *   5. Emit.  mask has bit s set iff edge s of the triangle is marked; m_s is that edge's new vertex.  The children keep the parent's
+ *      orientation and stand, in this order, at the triangle's scanned offset (a triangle that takes no part: itself).  r is the rotation of the
+ *      corners (v_i = corner (i + r) % 3, m_i likewise) that brings a single marked edge to e0, and two marked edges to e0 and e1:
+ *        mask 0:  (v0, v1, v2)
+ *        one:     (v0, m0, v2), (m0, v1, v2)
+ *        two:     (m0, v1, m1), then if the index m0 < m1:  (v0, m0, v2), (m0, m1, v2)   else:  (v0, m0, m1), (v0, m1, v2)
+ *        mask 7:  (v0, m0, m2), (m0, v1, m1), (m2, m1, v2), (m0, m1, m2)
+ *      The diagonal of "two" is an integer rule: no float ties.  Every triangle at an edge sees the same mark, so no T-junction can arise, at
+ *      irregular edges (used three times or more) too.
+ *   6. Budget and projection.  V' = V + marked and T' = T + the sum of the masks' bit counts are known before anything is emitted.  If no edge
+ *      is marked the call ends (stopped 1).  If T' > max_triangles -- max_triangles == 0: the kernels' own limit, 3 T' < 2^31 -- the round is not
+ *      applied and the call ends (stopped 2).  Otherwise the round's mesh is made, and with project != NULL ALL its vertices go through
+ *      rm_mesh_project's steps 1 - 7 (the same kernels); the next round marks on the projected positions.
+ * Rounds: at most `rounds`; stopped 0 when they were all applied.  rounds_run counts the rounds that were evaluated (steps 1 - 3), applied or not.
+ * End of call.  RM_MESH_NORMALS exist iff the source has them and are then rm_probe(RM_PROBE_NORMAL, param = project's normal_delta, or 0x1p-10f
+ * with project == NULL, flags = project's, or params' with project == NULL) at every vertex of the result -- also when no round was applied.
+ * RM_MESH_COLOURS and RM_MESH_CELLS exist iff the source has them.  The result starts without a labelling or measures.
+ * Report: integers and maxima only, the same bytes on every run.  max_first / max_last: the largest finite |err| over the midpoints of the first
+ * / the last round evaluated (+0 with none).  flipped_triangles: the sum of the projections' flipped_triangles.
+ * Procedure (rm_mesh_kernels.inc "refinement").  Per round: insert (one thread per triangle), flags (one per using slot), scan, E to the host,
+ * number (one per using slot: every slot learns its edge, the owner writes the ends), evaluate -- in all three units with launch_sdf_grid's
+ * kind selection, one lane per edge; the midpoint is made and parked in LDS ahead of a barrier so that it provably precedes the unit's math
+ * mode, as in "deviation"; lanes beyond E repeat the last edge and store nothing -- mark (plain fp32), children per triangle, two scans, one
+ * read of (marked, T') by the host, then the new vertices (one thread per edge) and the children (one per triangle).  No thread waits for
+ * another, every loop is bounded, there are no floating-point atomics.
+ * The call is synchronous on the context's stream.  rm_mesh_timings of the result is {0, the split rounds, the projections and the normals}.
+ * report (may be NULL) receives the struct below.  An empty mesh, or one without triangles, gives a copy and stopped 1 with rounds_run 0.
+ * RM_ERR_INVALID, in this order (the text through rm_last_error(NULL) when no context is known): an invalid block, one text per field, then an
+ * invalid project block (rm_mesh_project's texts), before the handles are looked at; a NULL mesh, scene or out ("NULL argument"); a scene of
+ * another context than the mesh's.  No refusal writes to out or report.
+ * RM_ERR_DEVICE: 3 T >= 2^31; V' > INT_MAX; an edge that found no slot; a failed allocation, with nothing leaked. */
+typedef struct RmMeshRefine {    /* 32 bytes */
+  float iso;              /* the level the mesh stands for (a mesh does not remember its own); finite */
+  float tolerance;        /* an edge is split iff |d(midpoint) - iso| > tolerance; finite, >= 0 */
+  float min_edge;         /* ... and its length > min_edge; finite, >= 0 */
+  int32_t rounds;         /* 1..8 */
+  uint64_t max_triangles; /* a round that would give more is not applied; 0 = the kernels' own limit */
+  int32_t flags;          /* 0, RM_RENDER_FAST, RM_RENDER_NO_CULL or both, as rm_sdf_grid */
+  int32_t reserved;       /* must be 0 */
+} RmMeshRefine;
+typedef struct RmMeshRefinement { /* 256 bytes */
+  uint64_t vertices_before, triangles_before;  /*   0,   8 */
+  uint64_t vertices, triangles;                /*  16,  24: of the result */
+  uint64_t edges[8];                           /*  32: per round evaluated, the unique edges examined */
+  uint64_t split_edges[8];                     /*  96: ... of them marked (also in a round the budget did not apply) */
+  uint64_t nonfinite_midpoints[8];             /* 160: ... whose d - iso is not finite */
+  uint64_t flipped_triangles;                  /* 224: the sum of the projections' */
+  float max_first, max_last;                   /* 232, 236 */
+  int32_t rounds_run;                          /* 240 */
+  int32_t stopped;                             /* 244: 0 rounds done, 1 nothing to split, 2 budget */
+  int32_t reserved[2];                         /* 248: written as 0 */
+} RmMeshRefinement;
+RM_API void rm_mesh_refine_default(RmMeshRefine* params);
+RM_API int rm_mesh_refine(rm_mesh* mesh, rm_scene* scene, const RmMeshRefine* params, const RmMeshProject* project, rm_mesh** out,
+                          RmMeshRefinement* report);
 
 #ifdef __cplusplus
 }

@@ -476,6 +476,56 @@ def mesh_deviation_dict(r: "RmMeshDeviationReport") -> dict:
     return {name: getattr(r, name) for name, _ in RmMeshDeviationReport._fields_ if name != "reserved"}
 
 
+class RmMeshRefine(C.Structure):
+    """Parameters of rm_mesh_refine (ABI 9): split the edges whose midpoint lies further than `tolerance` off the level `iso`
+    (include/hip_raymarch.h "refinement")."""
+    _fields_ = [
+        ("iso", C.c_float),
+        ("tolerance", C.c_float),
+        ("min_edge", C.c_float),
+        ("rounds", C.c_int32),
+        ("max_triangles", C.c_uint64),
+        ("flags", C.c_int32),
+        ("reserved", C.c_int32),
+    ]
+
+
+MESH_REFINE_DEFAULTS = dict(iso=0.0, tolerance=0.0, min_edge=0.0, rounds=1, max_triangles=0, flags=0)  # rm_mesh_refine_default
+
+assert C.sizeof(RmMeshRefine) == 32
+
+
+class RmMeshRefinement(C.Structure):
+    """What rm_mesh_refine says of its work (ABI 9): the sizes before and after, per round the edges examined, split and without a finite
+    distance, the projections' flips, the largest |distance - iso| of the first and the last round, and why it stopped."""
+    _fields_ = [
+        ("vertices_before", C.c_uint64),
+        ("triangles_before", C.c_uint64),
+        ("vertices", C.c_uint64),
+        ("triangles", C.c_uint64),
+        ("edges", C.c_uint64 * 8),
+        ("split_edges", C.c_uint64 * 8),
+        ("nonfinite_midpoints", C.c_uint64 * 8),
+        ("flipped_triangles", C.c_uint64),
+        ("max_first", C.c_float),
+        ("max_last", C.c_float),
+        ("rounds_run", C.c_int32),
+        ("stopped", C.c_int32),
+        ("reserved", C.c_int32 * 2),
+    ]
+
+
+assert C.sizeof(RmMeshRefinement) == 256
+
+
+def mesh_refinement_dict(r: "RmMeshRefinement") -> dict:
+    """The struct's fields as a dict: the per-round arrays as tuples of eight, `reserved` left out."""
+    d = {name: getattr(r, name) for name, _ in RmMeshRefinement._fields_ if name != "reserved"}
+    for name in ("edges", "split_edges", "nonfinite_midpoints"):
+        d[name] = tuple(int(x) for x in d[name])
+    return d
+
+
 def mesh_measures_dict(m: "RmMeshMeasures") -> dict:
     """The struct's fields as a dict: lo and hi as tuples, `closed` as bool, `reserved` left out."""
     d = {name: getattr(m, name) for name, _ in RmMeshMeasures._fields_ if name != "reserved"}

@@ -39,6 +39,7 @@ hipError_t launch_sdf_grid_strict(const SdfGridParams& P, hipStream_t stream);
 hipError_t launch_mesh_occlusion_strict(const MeshOcclusionPass& P, hipStream_t stream);
 hipError_t launch_mesh_project_eval_strict(const MeshProjectEval& P, hipStream_t stream);
 hipError_t launch_mesh_deviation_eval_strict(const MeshDeviationSdf& P, hipStream_t stream);
+hipError_t launch_mesh_refine_eval_strict(const MeshRefineMidpoints& P, hipStream_t stream);
 }  // namespace rm_gl
 // A scene pass `name` in the unit the flags and the context select: the fast build, the GL stack's arithmetic, or the parity build.
 #define RM_SCENE_PASS(ctx, flags, name, P, stream)              \
@@ -218,7 +219,7 @@ struct DeviceArray {
 // that runs the stage.
 struct MeshSpans {
   enum { SAMPLE, COUNT_SCAN, EMIT, SHARPEN, ATTRIBUTES, LABEL, KEEP_FLAGS, GATHER, CLUSTER_NUMBER, CLUSTER_MERGE, CLUSTER_GATHER, OCCLUSION_PROBES, OCCLUSION_TAPS,
-         MEASURE_TOPOLOGY, MEASURE_GEOMETRY, PROJECT_ROUNDS, PROJECT_NORMALS, DEVIATION_EVALUATE, DEVIATION_REDUCE, COUNT };
+         MEASURE_TOPOLOGY, MEASURE_GEOMETRY, PROJECT_ROUNDS, PROJECT_NORMALS, DEVIATION_EVALUATE, DEVIATION_REDUCE, REFINE_SPLIT, REFINE_NORMALS, COUNT };
   hipEvent_t ev[COUNT][2] = {};
   hipError_t begin(int span, hipStream_t stream) { return record(ev[span][0], stream); }
   hipError_t end(int span, hipStream_t stream) { return record(ev[span][1], stream); }

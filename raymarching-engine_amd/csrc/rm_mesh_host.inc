@@ -1174,12 +1174,11 @@ static int mesh_project_check(const Refuse& refuse, const RmMeshProject* in, RmM
   return RM_OK;
 }
 
-int rm_mesh_project(rm_mesh* mesh, rm_scene* scene, const RmMeshProject* params, rm_mesh** out, RmMeshProjection* report, float* residual_host) {
-  rm_ctx* ctx = mesh ? mesh->ctx : nullptr;
-  const Refuse refuse{ctx, "rm_mesh_project"};
-  RmMeshProject p;
-  if (int rc = mesh_project_check(refuse, params, &p)) return rc;
-  if (int rc = scene_check(refuse, scene, out != nullptr)) return rc;  // (a NULL mesh is a NULL context there)
+// The projection of a checked block on checked handles, for rm_mesh_project and for rm_mesh_refine's rounds (`refuse` names the entry).
+// probe_normals = false (the rounds: the normals are probed once, at the end of that call): the result has no RM_MESH_NORMALS array yet.
+static int mesh_project_run(const Refuse& refuse, rm_mesh* mesh, rm_scene* scene, const RmMeshProject& p, bool probe_normals, rm_mesh** out,
+                            RmMeshProjection* report, float* residual_host) {
+  rm_ctx* ctx = mesh->ctx;
   const unsigned long long V = mesh->vertices, T = mesh->triangles;
   if (V > (unsigned long long)INT_MAX) return refuse("the mesh has more vertices than the kernels' int index holds (V > INT_MAX)", RM_ERR_DEVICE);
   *out = nullptr;
@@ -1198,7 +1197,7 @@ int rm_mesh_project(rm_mesh* mesh, rm_scene* scene, const RmMeshProject* params,
   made->triangles = T;
   const SumTree tree((long long)V);  // of a report half's two sums: the step kernel writes level 0
   for (int what : {RM_MESH_POSITIONS, RM_MESH_NORMALS, RM_MESH_COLOURS, RM_MESH_TRIANGLES, RM_MESH_CELLS})
-    if (mesh->array[what].p) RM_HIP_AS(refuse, made->array[what].reserve(mesh_array_bytes(made.get(), what)));
+    if (mesh->array[what].p && (probe_normals || what != RM_MESH_NORMALS)) RM_HIP_AS(refuse, made->array[what].reserve(mesh_array_bytes(made.get(), what)));
   RM_HIP_AS(refuse, d.reserve(sizeof(float) * (size_t)V));
   RM_HIP_AS(refuse, normals.reserve(sizeof(float) * 3u * (size_t)V));
   RM_HIP_AS(refuse, flags.reserve(sizeof(unsigned int) * (size_t)V));
@@ -1306,6 +1305,14 @@ int rm_mesh_project(rm_mesh* mesh, rm_scene* scene, const RmMeshProject* params,
   if (residual_host) std::memcpy(residual_host, e_after.data(), sizeof(float) * (size_t)V);
   *out = made.release();
   return RM_OK;
+}
+
+int rm_mesh_project(rm_mesh* mesh, rm_scene* scene, const RmMeshProject* params, rm_mesh** out, RmMeshProjection* report, float* residual_host) {
+  const Refuse refuse{mesh ? mesh->ctx : nullptr, "rm_mesh_project"};
+  RmMeshProject p;
+  if (int rc = mesh_project_check(refuse, params, &p)) return rc;
+  if (int rc = scene_check(refuse, scene, out != nullptr)) return rc;  // (a NULL mesh is a NULL context there)
+  return mesh_project_run(refuse, mesh, scene, p, true, out, report, residual_host);
 }
 
 // ---- deviation (include/hip_raymarch.h "deviation") ------------------------------------------------------------------------------------------------
@@ -1464,5 +1471,222 @@ int rm_mesh_deviation(rm_mesh* mesh, rm_scene* scene, const RmMeshDeviation* par
     out_ms2[0] = spans.ms(MeshSpans::DEVIATION_EVALUATE);
     out_ms2[1] = spans.ms(MeshSpans::DEVIATION_REDUCE);
   }
+  return RM_OK;
+}
+
+// ---- refinement (include/hip_raymarch.h "refinement") ------------------------------------------------------------------------------------------------
+
+void rm_mesh_refine_default(RmMeshRefine* params) {
+  if (!params) return;
+  *params = RmMeshRefine{0.0f, 0.0f, 0.0f, 1, 0ull, 0, 0};
+}
+
+static int mesh_refine_check(const Refuse& refuse, const RmMeshRefine* in, RmMeshRefine* p) {
+  rm_mesh_refine_default(p);
+  if (in) *p = *in;
+  if (!std::isfinite(p->iso)) return refuse("refine iso must be finite");
+  if (!(std::isfinite(p->tolerance) && p->tolerance >= 0.0f)) return refuse("refine tolerance must be finite and >= 0");
+  if (!(std::isfinite(p->min_edge) && p->min_edge >= 0.0f)) return refuse("refine min_edge must be finite and >= 0");
+  if (p->rounds < 1 || p->rounds > 8) return refuse("refine rounds must be in 1..8");
+  if (int rc = sdf_flags_check(refuse, p->flags)) return rc;
+  if (p->reserved != 0) return refuse("refine reserved must be 0");
+  return RM_OK;
+}
+
+static const unsigned long long kRefineTriangles = 0x7FFFFFFFull / 3ull;  // the kernels' own limit: a using slot 3 t + s is below 2^31
+
+// what a round says of itself: the unique edges, the marked ones, the non-finite midpoints, the largest finite |d - iso|
+struct RefineRound {
+  unsigned long long edges = 0, split = 0, nonfinite = 0;
+  float max = 0.0f;
+};
+
+// One round on `cur` (V > 0, 0 < T <= kRefineTriangles): steps 1 - 3, and, where an edge is marked and the round's T' is within `limit`, steps 4
+// and 5 into *next -- which otherwise stays empty.  On the context's stream; returns with the stream idle, so the scratch goes with it.  *ms
+// gains the round's spans.
+static int mesh_refine_round(const Refuse& refuse, rm_scene* scene, const RmMeshRefine& p, unsigned long long limit, const rm_mesh* cur, MeshPtr& next,
+                             RefineRound* said, float* ms) {
+  rm_ctx* ctx = refuse.ctx;
+  MeshSpans& spans = ctx->mesh_spans;
+  const unsigned long long V = cur->vertices, T = cur->triangles;
+  unsigned long long slots = 1ull;
+  while (slots < 4ull * T) slots <<= 1;
+  DeviceArray keys, owners, words, edge_of, levels, totals, ends, d, marked, marks;
+  RM_HIP_AS(refuse, keys.reserve(sizeof(unsigned long long) * (size_t)slots));
+  RM_HIP_AS(refuse, owners.reserve(sizeof(unsigned long long) * (size_t)slots));
+  RM_HIP_AS(refuse, words.reserve(sizeof(unsigned long long) * 3u * (size_t)T));
+  RM_HIP_AS(refuse, edge_of.reserve(sizeof(unsigned int) * 3u * (size_t)T));
+  RM_HIP_AS(refuse, levels.reserve(sizeof(unsigned long long) * (rm::rm_mesh_scan_scratch_elems(3ll * (long long)T) + 1)));  // (every scan here is of 3 T words at most)
+  RM_HIP_AS(refuse, totals.reserve(sizeof(unsigned long long) * rm::RM_REFINE_WORDS));
+  rm::MeshRefine R{};
+  R.vertices = (long long)V;
+  R.triangles = (long long)T;
+  R.positions = cur->array[RM_MESH_POSITIONS].f32();
+  R.colours = cur->array[RM_MESH_COLOURS].f32();
+  R.cells = cur->array[RM_MESH_CELLS].u32();
+  R.corners = cur->array[RM_MESH_TRIANGLES].u32();
+  R.keys = keys.u64();
+  R.owners = owners.u64();
+  R.slots = slots;
+  R.words = words.u64();
+  R.edge_of = edge_of.u32();
+  R.totals = totals.u64();
+  R.iso = p.iso;
+  R.tolerance = p.tolerance;
+  R.min_edge2 = p.min_edge * p.min_edge;
+  unsigned long long got[rm::RM_REFINE_WORDS] = {};
+  // 1: the table, the owners' flags, their scan
+  RM_HIP_AS(refuse, hipMemsetAsync(totals.p, 0, sizeof got, ctx->stream));
+  RM_HIP_AS(refuse, spans.begin(MeshSpans::REFINE_SPLIT, ctx->stream));
+  RM_HIP_AS(refuse, hipMemsetAsync(keys.p, 0xFF, sizeof(unsigned long long) * (size_t)slots, ctx->stream));
+  RM_HIP_AS(refuse, hipMemsetAsync(owners.p, 0xFF, sizeof(unsigned long long) * (size_t)slots, ctx->stream));
+  RM_HIP_AS(refuse, rm::launch_mesh_refine_edges(R, ctx->stream));
+  RM_HIP_AS(refuse, rm::launch_mesh_refine_flags(R, ctx->stream));
+  RM_HIP_AS(refuse, rm::launch_mesh_scan(R.words, 3ll * (long long)T, levels.u64(), R.totals + rm::RM_REFINE_EDGES, ctx->stream));
+  RM_HIP_AS(refuse, spans.end(MeshSpans::REFINE_SPLIT, ctx->stream));
+  if (int rc = copy_and_wait(ctx, got, totals.p, sizeof got, hipMemcpyDeviceToHost)) return rc;
+  *ms += spans.ms(MeshSpans::REFINE_SPLIT);
+  if (got[rm::RM_REFINE_ERROR] != 0ull) return refuse("an edge found no slot in the table", RM_ERR_DEVICE);
+  const unsigned long long E = got[rm::RM_REFINE_EDGES];
+  said->edges = E;
+  if (E == 0) return RM_OK;  // (no triangle takes part)
+  // 2, 3: the edges' numbers and ends, d at the midpoints, the marks, the children; two scans, one read
+  RM_HIP_AS(refuse, ends.reserve(sizeof(unsigned int) * 2u * (size_t)E));
+  RM_HIP_AS(refuse, d.reserve(sizeof(float) * (size_t)E));
+  RM_HIP_AS(refuse, marked.reserve(sizeof(unsigned int) * (size_t)E));
+  RM_HIP_AS(refuse, marks.reserve(sizeof(unsigned long long) * (size_t)E));
+  if (int rc = scene_cull_grid(ctx, scene, p.flags, 1ll << 40)) return rc;
+  R.edges = (long long)E;
+  R.ends = ends.u32();
+  R.d = d.f32();
+  R.marked = marked.u32();
+  R.marks = marks.u64();
+  MeshRefineMidpoints Q{};
+  Q.scene = scene_view(scene, p.flags);
+  Q.positions = R.positions;
+  Q.ends = R.ends;
+  Q.d = d.f32();
+  Q.edges = (int)E;
+  RM_HIP_AS(refuse, spans.begin(MeshSpans::REFINE_SPLIT, ctx->stream));
+  RM_HIP_AS(refuse, rm::launch_mesh_refine_number(R, ctx->stream));
+  RM_HIP_AS(refuse, RM_SCENE_PASS(ctx, p.flags, launch_mesh_refine_eval, Q, ctx->stream));
+  RM_HIP_AS(refuse, rm::launch_mesh_refine_mark(R, ctx->stream));
+  RM_HIP_AS(refuse, rm::launch_mesh_refine_count(R, ctx->stream));
+  RM_HIP_AS(refuse, rm::launch_mesh_scan(R.marks, (long long)E, levels.u64(), R.totals + rm::RM_REFINE_SPLIT, ctx->stream));
+  RM_HIP_AS(refuse, rm::launch_mesh_scan(R.words, (long long)T, levels.u64(), R.totals + rm::RM_REFINE_CHILDREN, ctx->stream));
+  RM_HIP_AS(refuse, spans.end(MeshSpans::REFINE_SPLIT, ctx->stream));
+  if (int rc = copy_and_wait(ctx, got, totals.p, sizeof got, hipMemcpyDeviceToHost)) return rc;
+  *ms += spans.ms(MeshSpans::REFINE_SPLIT);
+  const unsigned long long K = got[rm::RM_REFINE_SPLIT], T2 = got[rm::RM_REFINE_CHILDREN];
+  said->split = K;
+  said->nonfinite = got[rm::RM_REFINE_NONFINITE];
+  const unsigned int most = (unsigned int)got[rm::RM_REFINE_MAX];
+  std::memcpy(&said->max, &most, sizeof most);
+  if (K == 0 || T2 > limit) return RM_OK;
+  if (V + K > (unsigned long long)INT_MAX)
+    return refuse("the refined mesh has more vertices than the kernels' int index holds (V' > INT_MAX)", RM_ERR_DEVICE);
+  // 4, 5: the round's mesh
+  MeshPtr made(new (std::nothrow) rm_mesh(ctx), rm_mesh_destroy);
+  if (!made) return refuse("out of host memory", RM_ERR_DEVICE);
+  for (int a = 0; a < 5; a++) made->has[a] = cur->has[a];
+  made->vertices = V + K;
+  made->triangles = T2;
+  for (int what : {RM_MESH_POSITIONS, RM_MESH_COLOURS, RM_MESH_TRIANGLES, RM_MESH_CELLS})
+    if (cur->array[what].p) RM_HIP_AS(refuse, made->array[what].reserve(mesh_array_bytes(made.get(), what)));
+  R.out_positions = made->array[RM_MESH_POSITIONS].f32();
+  R.out_colours = made->array[RM_MESH_COLOURS].f32();
+  R.out_cells = made->array[RM_MESH_CELLS].u32();
+  R.out_corners = made->array[RM_MESH_TRIANGLES].u32();
+  RM_HIP_AS(refuse, spans.begin(MeshSpans::REFINE_SPLIT, ctx->stream));
+  for (int what : {RM_MESH_POSITIONS, RM_MESH_COLOURS, RM_MESH_CELLS})
+    if (cur->array[what].p)
+      RM_HIP_AS(refuse, hipMemcpyAsync(made->array[what].p, cur->array[what].p, mesh_array_bytes(cur, what), hipMemcpyDeviceToDevice, ctx->stream));
+  RM_HIP_AS(refuse, rm::launch_mesh_refine_vertices(R, ctx->stream));
+  RM_HIP_AS(refuse, rm::launch_mesh_refine_emit(R, ctx->stream));
+  RM_HIP_AS(refuse, spans.end(MeshSpans::REFINE_SPLIT, ctx->stream));
+  RM_HIP_AS(refuse, hipStreamSynchronize(ctx->stream));
+  *ms += spans.ms(MeshSpans::REFINE_SPLIT);
+  next = std::move(made);
+  return RM_OK;
+}
+
+int rm_mesh_refine(rm_mesh* mesh, rm_scene* scene, const RmMeshRefine* params, const RmMeshProject* project, rm_mesh** out, RmMeshRefinement* report) {
+  rm_ctx* ctx = mesh ? mesh->ctx : nullptr;
+  const Refuse refuse{ctx, "rm_mesh_refine"};
+  RmMeshRefine p;
+  RmMeshProject q;
+  if (int rc = mesh_refine_check(refuse, params, &p)) return rc;
+  if (int rc = mesh_project_check(refuse, project, &q)) return rc;  // (NULL: the defaults, of which the normals' delta alone is used)
+  if (!project) q.flags = p.flags;
+  if (int rc = scene_check(refuse, scene, out != nullptr)) return rc;  // (a NULL mesh is a NULL context there)
+  const unsigned long long V = mesh->vertices, T = mesh->triangles;
+  if (T > kRefineTriangles) return refuse("the mesh has more triangles than the kernels' index holds edge slots of (3 T >= 2^31)", RM_ERR_DEVICE);
+  if (V > (unsigned long long)INT_MAX) return refuse("the mesh has more vertices than the kernels' int index holds (V > INT_MAX)", RM_ERR_DEVICE);
+  *out = nullptr;
+  RM_HIP(ctx, hipSetDevice(ctx->device));
+  const unsigned long long limit = p.max_triangles != 0ull && p.max_triangles < kRefineTriangles ? p.max_triangles : kRefineTriangles;
+  RmMeshRefinement r{};
+  r.vertices_before = V;
+  r.triangles_before = T;
+  r.stopped = 1;
+  float ms_split = 0.0f, ms_project = 0.0f;
+  MeshPtr made(nullptr, rm_mesh_destroy);  // the last round applied; none: the source stands
+  const rm_mesh* at = mesh;
+  if (V > 0 && T > 0) {
+    r.stopped = 0;
+    for (int round = 0; round < p.rounds; round++) {
+      MeshPtr next(nullptr, rm_mesh_destroy);
+      RefineRound said;
+      if (int rc = mesh_refine_round(refuse, scene, p, limit, at, next, &said, &ms_split)) return rc;
+      r.edges[round] = said.edges;
+      r.split_edges[round] = said.split;
+      r.nonfinite_midpoints[round] = said.nonfinite;
+      r.rounds_run = round + 1;
+      r.max_last = said.max;
+      if (round == 0) r.max_first = said.max;
+      if (!next) {
+        r.stopped = said.split == 0 ? 1 : 2;
+        break;
+      }
+      if (project) {
+        rm_mesh* moved = nullptr;
+        RmMeshProjection projection{};
+        if (int rc = mesh_project_run(refuse, next.get(), scene, q, false, &moved, &projection, nullptr)) return rc;
+        next.reset(moved);
+        r.flipped_triangles += projection.flipped_triangles;
+        ms_project += moved->ms[1];
+      }
+      made = std::move(next);
+      at = made.get();
+    }
+  }
+  if (!made) {  // no round was applied: the source's arrays, but for the normals
+    made.reset(new (std::nothrow) rm_mesh(ctx));
+    if (!made) return refuse("out of host memory", RM_ERR_DEVICE);
+    made->vertices = V;
+    made->triangles = T;
+    for (int what : {RM_MESH_POSITIONS, RM_MESH_COLOURS, RM_MESH_TRIANGLES, RM_MESH_CELLS})
+      if (mesh->array[what].p) {
+        RM_HIP_AS(refuse, made->array[what].reserve(mesh_array_bytes(mesh, what)));
+        RM_HIP_AS(refuse, hipMemcpyAsync(made->array[what].p, mesh->array[what].p, mesh_array_bytes(mesh, what), hipMemcpyDeviceToDevice, ctx->stream));
+      }
+  }
+  for (int a = 0; a < 5; a++) made->has[a] = mesh->has[a];
+  const bool with_normals = mesh->array[RM_MESH_NORMALS].p != nullptr && made->vertices > 0;
+  if (with_normals) {
+    RM_HIP_AS(refuse, made->array[RM_MESH_NORMALS].reserve(mesh_array_bytes(made.get(), RM_MESH_NORMALS)));
+    RM_HIP_AS(refuse, ctx->mesh_spans.begin(MeshSpans::REFINE_NORMALS, ctx->stream));
+    RM_HIP_AS(refuse, probe_enqueue(ctx, scene, RM_PROBE_NORMAL, made->array[RM_MESH_POSITIONS].f32(), made->array[RM_MESH_NORMALS].f32(), (int)made->vertices,
+                                    q.normal_delta, q.flags, ctx->stream));
+    RM_HIP_AS(refuse, ctx->mesh_spans.end(MeshSpans::REFINE_NORMALS, ctx->stream));
+  }
+  if (hipStreamSynchronize(ctx->stream) != hipSuccess) return refuse("the stream failed", RM_ERR_DEVICE);
+  made->ms[0] = 0.0f;
+  made->ms[1] = ms_split;
+  made->ms[2] = ms_project + (with_normals ? ctx->mesh_spans.ms(MeshSpans::REFINE_NORMALS) : 0.0f);
+  r.vertices = made->vertices;
+  r.triangles = made->triangles;
+  if (report) *report = r;
+  *out = made.release();
   return RM_OK;
 }

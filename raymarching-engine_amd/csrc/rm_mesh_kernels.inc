@@ -6,6 +6,7 @@
 //   - ambient occlusion: the distance at a fan of taps over every vertex                    (rm_mesh_occlusion)
 //   - projection: the distance and, where wanted, the normal at every vertex                (rm_mesh_project)
 //   - deviation: the distance at fixed points inside every triangle                         (rm_mesh_deviation)
+//   - refinement: the distance at every unique edge's midpoint                              (rm_mesh_refine)
 // In the strict unit only -- they have no arithmetic of a policy's own:
 //   - the mesher: surface nets over such a grid, whole or in z-slabs                        (rm_mesh_extract*, rm_mesh_from_values*)
 //   - sharp vertices: the two kernels that move vertices to their cells' QEF minimisers     (rm_mesh_extract_sharp*)
@@ -13,6 +14,7 @@
 //   - simplification: vertex clustering, and the quadric placement on top of it             (rm_mesh_simplify, rm_mesh_simplify_quadric)
 //   - measures: the edge table, classes, extent and the fixed-tree sums                     (rm_mesh_measure)
 //   - projection's step and report, deviation's reducer                                     (behind their evaluating kernels)
+//   - refinement's edge table, marks, new vertices and children                             (around its evaluating kernel)
 namespace rm {
 
 // ---- the sampler: rm_probe's RM_PROBE_SDF with the point made from the corner's indices -------------------------------------
@@ -216,6 +218,38 @@ hipError_t RM_LAUNCH(launch_mesh_deviation_eval)(const MeshDeviationSdf& P, hipS
   const long long lanes = (long long)P.triangles << P.log2_samples;
   const dim3 grid((unsigned int)((lanes + 255) / 256));
   return launch_point_kind(P.scene, [&](auto kind) { hipLaunchKernelGGL((rm_mesh_deviation_eval_kernel<decltype(kind)::value, kFast>), grid, dim3(256), 0, stream, P); });
+}
+#endif
+
+// ---- refinement: the scene's distance at every unique edge's midpoint (the header's "refinement") ---------------------------------------------
+// One lane per edge.  A lane reads its edge's ends and makes the midpoint BEFORE enter_math_mode; the point waits in LDS, [component][thread],
+// ahead of a barrier, and the switch lies behind it -- the ordering rm_mesh_deviation_eval_kernel documents, and for the same reason: the
+// compiler orders no floating-point operation against a write of the mode register, and the fast Mandelbulb flushes denormals.  Lanes beyond E
+// repeat the last edge and store nothing: the evaluators ballot and branch wave-uniformly.  An edge's ends are < V (refine_number wrote them).
+template <int KIND, bool FAST>
+__global__ __launch_bounds__(256) void rm_mesh_refine_eval_kernel(const MeshRefineMidpoints P) {
+  using MM = typename std::conditional<FAST, FM, PM>::type;
+  __shared__ SceneLds lds;
+  __shared__ float point[3][256];  // a lane's point: only that lane reads it back
+  const unsigned int edges = (unsigned int)P.edges;
+  const unsigned int gi = blockIdx.x * blockDim.x + threadIdx.x;
+  const unsigned int e = gi < edges ? gi : edges - 1u;
+  const float* const a = P.positions + 3 * (size_t)P.ends[2 * (size_t)e];
+  const float* const b = P.positions + 3 * (size_t)P.ends[2 * (size_t)e + 1];
+#pragma unroll
+  for (int c = 0; c < 3; c++) point[c][threadIdx.x] = 0.5f * (a[c] + b[c]);
+  __syncthreads();
+  enter_math_mode<KIND, FAST>();
+  Sdf<KIND>::stage(P.scene, lds);
+  __syncthreads();
+  const float d = Sdf<KIND>::template eval<MM>(P.scene, lds, V(point[0][threadIdx.x], point[1][threadIdx.x], point[2][threadIdx.x]));
+  if (gi < edges) P.d[gi] = d;
+}
+
+#ifndef RM_ONLY_KERNELS
+hipError_t RM_LAUNCH(launch_mesh_refine_eval)(const MeshRefineMidpoints& P, hipStream_t stream) {
+  const dim3 grid((unsigned int)(((long long)P.edges + 255) / 256));
+  return launch_point_kind(P.scene, [&](auto kind) { hipLaunchKernelGGL((rm_mesh_refine_eval_kernel<decltype(kind)::value, kFast>), grid, dim3(256), 0, stream, P); });
 }
 #endif
 
@@ -1478,6 +1512,192 @@ __global__ __launch_bounds__(256) void rm_mesh_deviation_reduce_kernel(const Mes
   if ((threadIdx.x & 63u) == 0u && key != 0ull) atomicMax(totals + RM_DEVIATION_KEY, key);
 }
 
+// ---- refinement: the edge table, the marks and the children (include/hip_raymarch.h "refinement") ------------------------------------------------
+// The scene is evaluated by rm_mesh_refine_eval_kernel between these launches (rm_mesh_host.inc rm_mesh_refine); these kernels are integer but
+// for the mark's plain fp32.  The table is the measures': the same key, the same hash, linear probing bounded by the table's size; what it
+// holds per edge is the lowest using slot 3 t + s, an atomicMin, so owner and numbering are the same on every run.  No thread waits for another.
+
+// the table's slot of the undirected edge {a, b}: with `insert` the key is entered where it is missing; all-ones when the table has no room
+// (insert) or not the key (lookup: only behind an insertion that failed)
+template <bool INSERT>
+__device__ inline unsigned long long mesh_refine_slot(const MeshRefine& R, unsigned int a, unsigned int b) {
+  const unsigned long long key = a < b ? ((unsigned long long)a << 32 | b) : ((unsigned long long)b << 32 | a);
+  unsigned long long h = key * 0x9E3779B97F4A7C15ull;
+  h ^= h >> 29;
+  h *= 0xBF58476D1CE4E5B9ull;
+  h ^= h >> 32;
+  const unsigned long long mask = R.slots - 1ull;
+  unsigned long long slot = h & mask;
+  for (unsigned long long probe = 0; probe < R.slots; probe++, slot = (slot + 1ull) & mask) {
+    unsigned long long held = INSERT ? __hip_atomic_load(R.keys + slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : R.keys[slot];
+    if (INSERT && held == ~0ull) {
+      held = atomicCAS(R.keys + slot, ~0ull, key);
+      if (held == ~0ull) held = key;
+    }
+    if (held == key) return slot;
+    if (!INSERT && held == ~0ull) break;
+  }
+  return ~0ull;
+}
+
+// the triangle's corners; whether it takes part: all three < V and pairwise different (rm_mesh_measure's rule)
+__device__ inline bool mesh_refine_corners(const MeshRefine& R, long long t, unsigned int* c) {
+  c[0] = R.corners[3 * t];
+  c[1] = R.corners[3 * t + 1];
+  c[2] = R.corners[3 * t + 2];
+  return c[0] < R.vertices && c[1] < R.vertices && c[2] < R.vertices && c[0] != c[1] && c[1] != c[2] && c[0] != c[2];
+}
+
+__global__ __launch_bounds__(256) void rm_mesh_refine_edges_kernel(const MeshRefine R) {
+  const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
+  unsigned int c[3];
+  if (t >= R.triangles || !mesh_refine_corners(R, t, c)) return;
+#pragma unroll
+  for (int s = 0; s < 3; s++) {
+    const unsigned long long slot = mesh_refine_slot<true>(R, c[s], c[(s + 1) % 3]);
+    if (slot == ~0ull) R.totals[RM_REFINE_ERROR] = 1ull;  // (every writer writes the same)
+    else atomicMin(R.owners + slot, (unsigned long long)(3 * t + s));
+  }
+}
+
+// One thread per using slot u = 3 t + s.  NUMBER = false: words[u] = 1 iff u is its edge's owner.  NUMBER = true, behind the scan of the words:
+// edge_of[u] = the edge's number, and the owner writes the edge's ends (lo, hi).
+template <bool NUMBER>
+__global__ __launch_bounds__(256) void rm_mesh_refine_slots_kernel(const MeshRefine R) {
+  const long long u = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (u >= 3 * R.triangles) return;
+  const long long t = u / 3;
+  const int s = (int)(u - 3 * t);
+  unsigned int c[3];
+  unsigned long long owner = ~0ull;
+  if (mesh_refine_corners(R, t, c)) {
+    const unsigned long long slot = mesh_refine_slot<false>(R, c[s], c[(s + 1) % 3]);
+    if (slot != ~0ull) owner = R.owners[slot];
+  }
+  if (!NUMBER) {
+    R.words[u] = owner == (unsigned long long)u ? 1ull : 0ull;
+    return;
+  }
+  if (owner == ~0ull) {
+    R.edge_of[u] = 0xFFFFFFFFu;
+    return;
+  }
+  const unsigned int e = (unsigned int)R.words[owner];
+  R.edge_of[u] = e;
+  if (owner == (unsigned long long)u) {
+    const unsigned int a = c[s], b = c[(s + 1) % 3];
+    R.ends[2 * (size_t)e] = a < b ? a : b;
+    R.ends[2 * (size_t)e + 1] = a < b ? b : a;
+  }
+}
+
+// One thread per edge, and every thread of a wave stays to the end: the counts and the maximum read all of them.
+__global__ __launch_bounds__(256) void rm_mesh_refine_mark_kernel(const MeshRefine R) {
+  const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
+  const bool valid = e < R.edges;
+  bool finite = false, marked = false;
+  float err = 0.0f;
+  if (valid) {
+    const float* const a = R.positions + 3 * (size_t)R.ends[2 * e];
+    const float* const b = R.positions + 3 * (size_t)R.ends[2 * e + 1];
+    const float dx = b[0] - a[0], dy = b[1] - a[1], dz = b[2] - a[2];
+    const float len2 = (dx * dx + dy * dy) + dz * dz;
+    err = R.d[e] - R.iso;
+    finite = isfinite(err);
+    marked = finite && fabsf(err) > R.tolerance && len2 > R.min_edge2;
+    R.marked[e] = marked ? 1u : 0u;
+    R.marks[e] = marked ? 1ull : 0ull;
+  }
+  mesh_measure_count(R.totals + RM_REFINE_NONFINITE, valid && !finite);
+  unsigned int most = valid && finite ? __float_as_uint(fabsf(err)) : 0u;
+#pragma unroll
+  for (int m = 1; m < 64; m <<= 1) {
+    const unsigned int other = (unsigned int)__shfl_xor((int)most, m);
+    if (other > most) most = other;
+  }
+  if ((threadIdx.x & 63u) == 0u && most != 0u) atomicMax(R.totals + RM_REFINE_MAX, (unsigned long long)most);
+}
+
+// the new vertex on edge e of a triangle that takes part: all-ones where the edge is not marked
+__device__ inline unsigned int mesh_refine_midpoint(const MeshRefine& R, long long u) {
+  const unsigned int e = R.edge_of[u];
+  if (e == 0xFFFFFFFFu || R.marked[e] == 0u) return 0xFFFFFFFFu;  // (no number: only behind an insertion that failed)
+  return (unsigned int)((unsigned long long)R.vertices + R.marks[e]);
+}
+
+__global__ __launch_bounds__(256) void rm_mesh_refine_count_kernel(const MeshRefine R) {
+  const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (t >= R.triangles) return;
+  unsigned int c[3];
+  unsigned long long children = 1ull;
+  if (mesh_refine_corners(R, t, c))
+    for (int s = 0; s < 3; s++)
+      if (mesh_refine_midpoint(R, 3 * t + s) != 0xFFFFFFFFu) children++;  // (ahead of the scan of the marks: only whether there is one)
+  R.words[t] = children;
+}
+
+__global__ __launch_bounds__(256) void rm_mesh_refine_vertices_kernel(const MeshRefine R) {
+  const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (e >= R.edges || R.marked[e] == 0u) return;
+  const unsigned int lo = R.ends[2 * e], hi = R.ends[2 * e + 1];
+  const size_t k = (size_t)R.vertices + (size_t)R.marks[e];
+#pragma unroll
+  for (int c = 0; c < 3; c++) {
+    R.out_positions[3 * k + c] = 0.5f * (R.positions[3 * (size_t)lo + c] + R.positions[3 * (size_t)hi + c]);
+    if (R.out_colours) R.out_colours[3 * k + c] = 0.5f * (R.colours[3 * (size_t)lo + c] + R.colours[3 * (size_t)hi + c]);
+  }
+  if (R.out_cells) R.out_cells[k] = R.cells[lo];
+}
+
+__device__ inline void mesh_refine_child(unsigned int* out, unsigned int a, unsigned int b, unsigned int c) {
+  out[0] = a;
+  out[1] = b;
+  out[2] = c;
+}
+
+// One thread per triangle: its children at its scanned offset, in the header's order, the parent's orientation kept.
+__global__ __launch_bounds__(256) void rm_mesh_refine_emit_kernel(const MeshRefine R) {
+  const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (t >= R.triangles) return;
+  unsigned int c[3], mid[3] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu};
+  unsigned int* out = R.out_corners + 3 * (size_t)R.words[t];
+  int mask = 0;
+  if (mesh_refine_corners(R, t, c))
+    for (int s = 0; s < 3; s++) {
+      mid[s] = mesh_refine_midpoint(R, 3 * t + s);
+      if (mid[s] != 0xFFFFFFFFu) mask |= 1 << s;
+    }
+  // the rotation that brings the pattern to its form: the one marked edge to e0; two marked edges to e0 and e1
+  const int r = mask == 2 || mask == 6 ? 1 : mask == 4 || mask == 5 ? 2 : 0;
+  const unsigned int v0 = c[r], v1 = c[(r + 1) % 3], v2 = c[(r + 2) % 3];
+  const unsigned int m0 = mid[r], m1 = mid[(r + 1) % 3], m2 = mid[(r + 2) % 3];
+  switch (__popc((unsigned int)mask)) {
+    case 0:
+      mesh_refine_child(out, v0, v1, v2);
+      break;
+    case 1:
+      mesh_refine_child(out, v0, m0, v2);
+      mesh_refine_child(out + 3, m0, v1, v2);
+      break;
+    case 2:
+      mesh_refine_child(out, m0, v1, m1);
+      if (m0 < m1) {
+        mesh_refine_child(out + 3, v0, m0, v2);
+        mesh_refine_child(out + 6, m0, m1, v2);
+      } else {
+        mesh_refine_child(out + 3, v0, m0, m1);
+        mesh_refine_child(out + 6, v0, m1, v2);
+      }
+      break;
+    default:
+      mesh_refine_child(out, v0, m0, m2);
+      mesh_refine_child(out + 3, m0, v1, m1);
+      mesh_refine_child(out + 6, m2, m1, v2);
+      mesh_refine_child(out + 9, m0, m1, m2);
+      break;
+  }
+}
+
 #ifndef RM_ONLY_KERNELS
 static inline long long mesh_cells(const GridDims& g) { return (long long)(g.nc[0] - 1) * (g.nc[1] - 1) * (g.nc[2] - 1); }
 
@@ -1598,6 +1818,14 @@ hipError_t launch_mesh_project_flips(const MeshProject& S, hipStream_t stream) {
 hipError_t launch_mesh_deviation_reduce(const MeshDeviation& D, hipStream_t stream) {
   RM_MESH_PARTS_LAUNCH(rm_mesh_deviation_reduce_kernel, (long long)D.triangles << D.log2_samples, D);
 }
+// refinement: one thread per triangle, using slot or edge
+hipError_t launch_mesh_refine_edges(const MeshRefine& R, hipStream_t stream) { RM_MESH_PARTS_LAUNCH(rm_mesh_refine_edges_kernel, R.triangles, R); }
+hipError_t launch_mesh_refine_flags(const MeshRefine& R, hipStream_t stream) { RM_MESH_PARTS_LAUNCH(rm_mesh_refine_slots_kernel<false>, 3 * R.triangles, R); }
+hipError_t launch_mesh_refine_number(const MeshRefine& R, hipStream_t stream) { RM_MESH_PARTS_LAUNCH(rm_mesh_refine_slots_kernel<true>, 3 * R.triangles, R); }
+hipError_t launch_mesh_refine_mark(const MeshRefine& R, hipStream_t stream) { RM_MESH_PARTS_LAUNCH(rm_mesh_refine_mark_kernel, R.edges, R); }
+hipError_t launch_mesh_refine_count(const MeshRefine& R, hipStream_t stream) { RM_MESH_PARTS_LAUNCH(rm_mesh_refine_count_kernel, R.triangles, R); }
+hipError_t launch_mesh_refine_vertices(const MeshRefine& R, hipStream_t stream) { RM_MESH_PARTS_LAUNCH(rm_mesh_refine_vertices_kernel, R.edges, R); }
+hipError_t launch_mesh_refine_emit(const MeshRefine& R, hipStream_t stream) { RM_MESH_PARTS_LAUNCH(rm_mesh_refine_emit_kernel, R.triangles, R); }
 #undef RM_MESH_PARTS_LAUNCH
 
 hipError_t launch_mesh_emit(const MeshParams& P, hipStream_t stream) {

@@ -349,6 +349,14 @@ struct MeshDeviationSdf {
   int triangles;                // T >= 1, T << log2_samples < 2^31
   int log2_samples;             // S = 1 << log2_samples <= 64
 };
+// rm_mesh_refine's evaluating launch: one lane per unique edge, Sdf<KIND>::eval at the edge's midpoint with the probe's scene block.
+struct MeshRefineMidpoints {
+  DevScene scene;
+  const float* positions;     // V x 3
+  const unsigned int* ends;   // E x (lo, hi)
+  float* d;                   // E
+  int edges;                  // E >= 1
+};
 // The surface-nets mesher over a grid of values.  counts: per cell (vertex flag) | (quads << 32), scanned in place into the cell's
 // first vertex | first quad; the emit pass reads a neighbour's vertex index from there (every cell round a crossing edge is active).
 struct MeshParams {
@@ -681,6 +689,46 @@ struct MeshDeviation {
 hipError_t launch_mesh_deviation_eval_strict(const MeshDeviationSdf& P, hipStream_t stream);
 hipError_t launch_mesh_deviation_eval_fast(const MeshDeviationSdf& P, hipStream_t stream);
 hipError_t launch_mesh_deviation_reduce(const MeshDeviation& D, hipStream_t stream);
+// Refinement (rm_mesh_refine), one round.  refine_edges: one thread per triangle, its three edges into the table (the measures' key and hash;
+// keys and owners of all-ones, a power of two of them), atomicMin of the using slot 3 t + s into the edge's owner.  refine_flags: one thread per
+// using slot, words[u] = 1 iff u owns its edge; the host scans the words.  refine_number: one thread per using slot, edge_of[u] = the scanned
+// word of its edge's owner (all-ones for a slot of a triangle that takes no part), and the owner writes the edge's ends.  refine_eval, in each
+// unit's arithmetic: d at every edge's midpoint.  refine_mark (plain fp32): marked[e], marks[e] (for the scan), the counts and the maximum.
+// refine_count: one thread per triangle, words[t] = its number of children; the host scans marks and words.  refine_vertices: one thread per
+// edge, a marked edge writes its vertex.  refine_emit: one thread per triangle.  totals: RM_REFINE_WORDS 64-bit words, zeroed by the host.
+enum { RM_REFINE_EDGES, RM_REFINE_SPLIT, RM_REFINE_CHILDREN, RM_REFINE_NONFINITE, RM_REFINE_MAX, RM_REFINE_ERROR, RM_REFINE_WORDS };
+struct MeshRefine {
+  long long vertices, triangles;
+  long long edges;                // E: known behind the first scan
+  const float* positions;         // V x 3
+  const float* colours;           // V x 3 or NULL
+  const unsigned int* cells;      // V
+  const unsigned int* corners;    // T x 3
+  unsigned long long* keys;       // slots
+  unsigned long long* owners;     // slots
+  unsigned long long slots;       // a power of two
+  unsigned long long* words;      // 3 T: the owner flags and their scan; then T: the children and their scan
+  unsigned int* edge_of;          // 3 T
+  unsigned int* ends;             // E x 2
+  const float* d;                 // E
+  unsigned int* marked;           // E
+  unsigned long long* marks;      // E: marked, and its scan
+  unsigned long long* totals;     // RM_REFINE_WORDS
+  float* out_positions;           // V' x 3
+  float* out_colours;             // V' x 3 or NULL
+  unsigned int* out_cells;        // V'
+  unsigned int* out_corners;      // T' x 3
+  float iso, tolerance, min_edge2;  // min_edge2 = min_edge * min_edge, rounded once on the host
+};
+hipError_t launch_mesh_refine_edges(const MeshRefine& R, hipStream_t stream);
+hipError_t launch_mesh_refine_flags(const MeshRefine& R, hipStream_t stream);
+hipError_t launch_mesh_refine_number(const MeshRefine& R, hipStream_t stream);
+hipError_t launch_mesh_refine_eval_strict(const MeshRefineMidpoints& P, hipStream_t stream);
+hipError_t launch_mesh_refine_eval_fast(const MeshRefineMidpoints& P, hipStream_t stream);
+hipError_t launch_mesh_refine_mark(const MeshRefine& R, hipStream_t stream);
+hipError_t launch_mesh_refine_count(const MeshRefine& R, hipStream_t stream);
+hipError_t launch_mesh_refine_vertices(const MeshRefine& R, hipStream_t stream);
+hipError_t launch_mesh_refine_emit(const MeshRefine& R, hipStream_t stream);
 hipError_t launch_camera_rng(const RmUniforms& u, int W, int H, int what, int count, float* out, hipStream_t stream);
 hipError_t launch_math_probe(int fn, const float* a, const float* b, int n, float* out, hipStream_t stream);
 }  // namespace rm

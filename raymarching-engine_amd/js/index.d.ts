@@ -132,7 +132,9 @@ export class RenderJobContext {
   /** project: the vertices of the returned mesh are moved onto the scene's level set (rm_mesh_project) behind simplify, quadric and keep, before components, occlusion and measures; iso defaults to params.iso, reach to meshProjectReach of the grid the mesh lies on; the result carries `projection` and `residual` */
   extractMesh(scene: Scene, grid: MeshGrid, params: MeshParams | null | undefined, sharp: MeshSharp | true | null | undefined, keep: MeshKeep | true | null | undefined, components: boolean | undefined, simplify: MeshSimplify | null | undefined, quadric: MeshQuadric | true | null | undefined, occlusion: MeshOcclusion | true | null | undefined, measures: boolean | undefined, slabs: MeshSlabs | number | true | null | undefined, project: MeshProject | true | null): Mesh;
   /** deviation: how far the triangles of the returned mesh lie off the scene's level set (rm_mesh_deviation), measured behind every other stage, project included; iso defaults to params.iso; the result carries `deviation` and `triangleDeviation` */
+  /** refine: behind project and before measures, components, occlusion and deviation, the edges whose midpoint lies further than `tolerance` off the scene's level set are split for `rounds` rounds (rm_mesh_refine), every round's mesh projected with the project block or its defaults; iso defaults to params.iso, tolerance to meshRefineTolerance of the grid the mesh lies on; the criterion looks at edge midpoints only, `deviation` remains the judge; the result carries `refinement` */
   extractMesh(scene: Scene, grid: MeshGrid, params: MeshParams | null | undefined, sharp: MeshSharp | true | null | undefined, keep: MeshKeep | true | null | undefined, components: boolean | undefined, simplify: MeshSimplify | null | undefined, quadric: MeshQuadric | true | null | undefined, occlusion: MeshOcclusion | true | null | undefined, measures: boolean | undefined, slabs: MeshSlabs | number | true | null | undefined, project: MeshProject | true | null | undefined, deviation: MeshDeviation | true | null): Mesh;
+  extractMesh(scene: Scene, grid: MeshGrid, params: MeshParams | null | undefined, sharp: MeshSharp | true | null | undefined, keep: MeshKeep | true | null | undefined, components: boolean | undefined, simplify: MeshSimplify | null | undefined, quadric: MeshQuadric | true | null | undefined, occlusion: MeshOcclusion | true | null | undefined, measures: boolean | undefined, slabs: MeshSlabs | number | true | null | undefined, project: MeshProject | true | null | undefined, deviation: MeshDeviation | true | null | undefined, refine: MeshRefine | true | null): Mesh;
   /** the mesher alone on the caller's field (rm_mesh_from_values); keep, components and simplify as in extractMesh */
   meshFromValues(grid: MeshGrid, values: Float32Array, iso?: number, keep?: MeshKeep | true | null, components?: boolean, simplify?: MeshSimplify | null): Mesh;
   /** quadric as in extractMesh */
@@ -172,7 +174,7 @@ export const RM: { [name: string]: number };
 /** mesh extraction (include/hip_raymarch.h "mesh extraction"): n = CELLS per axis between the corners lo and hi */
 export interface MeshGrid { lo: [number, number, number]; hi: [number, number, number]; n: [number, number, number]; slabs?: true }
 export interface MeshParams { iso?: number; normals?: boolean | 0 | 1; normalDelta?: number; colours?: boolean | 0 | 1; flags?: number }
-export interface Mesh { positions: Float32Array; normals: Float32Array | null; colours: Float32Array | null; triangles: Uint32Array; cells: Uint32Array; /** ms of sampling, meshing, attributes (rm_mesh_timings); with an occlusion a fourth entry, its probes and taps */ timings: [number, number, number] | [number, number, number, number]; /** only when components were asked for: each vertex's component, and (vertices, triangles) per component */ labels?: Uint32Array; componentSizes?: Uint32Array; /** only when an occlusion was asked for: 1 = open, per vertex (rm_mesh_occlusion) */ occlusion?: Float32Array; /** only when measures were asked for (rm_mesh_measure) */ measures?: MeshMeasures; /** only with `project`: what rm_mesh_project reports, and the distance minus iso at the projected vertices */ projection?: MeshProjection; residual?: Float32Array; /** only with `deviation`: what rm_mesh_deviation reports, and each triangle's largest |distance - iso| over its samples */ deviation?: MeshDeviationReport; triangleDeviation?: Float32Array }
+export interface Mesh { positions: Float32Array; normals: Float32Array | null; colours: Float32Array | null; triangles: Uint32Array; cells: Uint32Array; /** ms of sampling, meshing, attributes (rm_mesh_timings); with an occlusion a fourth entry, its probes and taps */ timings: [number, number, number] | [number, number, number, number]; /** only when components were asked for: each vertex's component, and (vertices, triangles) per component */ labels?: Uint32Array; componentSizes?: Uint32Array; /** only when an occlusion was asked for: 1 = open, per vertex (rm_mesh_occlusion) */ occlusion?: Float32Array; /** only when measures were asked for (rm_mesh_measure) */ measures?: MeshMeasures; /** only with `project`: what rm_mesh_project reports, and the distance minus iso at the projected vertices */ projection?: MeshProjection; residual?: Float32Array; /** only with `deviation`: what rm_mesh_deviation reports, and each triangle's largest |distance - iso| over its samples */ deviation?: MeshDeviationReport; triangleDeviation?: Float32Array; /** only with `refine`: what rm_mesh_refine reports */ refinement?: MeshRefinement }
 /** what rm_mesh_measure says of a mesh (RmMeshMeasures, include/hip_raymarch.h "measures and edge topology"): the counts as Numbers (all below 2^53), lo / hi of the finite vertices, closed = no boundary and no irregular edge; componentEdges: 4 uint64 per component (edges, boundary, irregular, unbalanced; rm_mesh_measure_components); milliseconds of topology and geometry */
 export interface MeshMeasures { vertices: number; triangles: number; usedVertices: number; skippedTriangles: number; unmeasuredTriangles: number; finiteVertices: number; edges: number; boundaryEdges: number; regularEdges: number; irregularEdges: number; unbalancedEdges: number; euler: number; components: number; closedComponents: number; area: number; volume: number; lo: [number, number, number]; hi: [number, number, number]; closed: boolean; componentEdges: BigUint64Array; milliseconds: [number, number] }
 export const MESH_DEFAULTS: { iso: number; normals: 0 | 1; normalDelta: number; colours: 0 | 1; flags: number };
@@ -216,6 +218,14 @@ export interface MeshProjection { vertices: number; triangles: number; movedVert
 export interface MeshDeviation { iso?: number; order?: number; tolerance?: number; flags?: number }
 export const MESH_DEVIATION_DEFAULTS: Required<MeshDeviation>;
 export function meshDeviation(deviation?: MeshDeviation | null): Required<MeshDeviation>;
+/** the block of rm_mesh_refine (RmMeshRefine): an edge is split iff its midpoint's |distance - iso| exceeds `tolerance` and its length exceeds `minEdge`; `rounds` in 1..8; a round that would give more than `maxTriangles` triangles is not applied (0 = the kernels' own limit) */
+export interface MeshRefine { iso?: number; tolerance?: number; minEdge?: number; rounds?: number; maxTriangles?: number; flags?: number }
+export const MESH_REFINE_DEFAULTS: Required<MeshRefine>;
+export function meshRefine(refine?: MeshRefine | null): Required<MeshRefine>;
+/** the tolerance extractMesh(..., refine) takes when none is given: 1/64 of the smallest cell side of `grid`, in fp32 -- a default, not a bar */
+export function meshRefineTolerance(grid: MeshGrid): number;
+/** what rm_mesh_refine says of its work (RmMeshRefinement): per round evaluated the unique edges, the edges split and the midpoints without a finite distance; maxFirst / maxLast: the largest |distance - iso| over the midpoints of the first / last round; stopped: 0 rounds done, 1 nothing to split, 2 budget; milliseconds: the split rounds, the projections and the normals */
+export interface MeshRefinement { verticesBefore: number; trianglesBefore: number; vertices: number; triangles: number; edges: number[]; splitEdges: number[]; nonfiniteMidpoints: number[]; flippedTriangles: number; maxFirst: number; maxLast: number; roundsRun: number; stopped: number; milliseconds: number }
 /** what rm_mesh_deviation says of a mesh (RmMeshDeviationReport): one-sided, mesh to surface, at `samples` fixed points per triangle -- a lower bound of the true maximum; area, meanSigned and rms are area-weighted over the evaluated triangles; milliseconds: evaluation and reduction */
 export interface MeshDeviationReport { vertices: number; triangles: number; skippedTriangles: number; unevaluatedTriangles: number; nonfiniteSamples: number; overTriangles: number; worstTriangle: number; area: number; overArea: number; meanSigned: number; rms: number; max: number; samples: number; milliseconds: number }
 /** binary little-endian PLY (normals, uchar colours and a float `quality` -- the occlusion -- when present): the bytes the Python host's write_ply writes */

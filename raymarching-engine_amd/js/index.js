@@ -375,9 +375,16 @@ class RenderJobContext {  // RenderJobContext + loadRenderJobContext (LoadRender
   // deviation (meshDeviation's): how far the triangles lie off the scene's level set at order * order fixed samples each (rm_mesh_deviation).  iso,
   //   where not given, is the extraction's.  Adds deviation (RmMeshDeviationReport's fields in camel case, and milliseconds) and triangleDeviation
   //   (Float32Array(T): each triangle's largest |distance - iso| over its samples)
-  extractMesh(scene, grid, opts, sharp, keep, components, simplify = null, quadric = null, occlusion = null, measures = false, slabs = null, project = null, deviation = null) {
-    const o = meshOptions(grid, opts, { sharp, keep, components, simplify, quadric, occlusion, measures, slabs, project, deviation });
+  // refine (meshRefine's): behind project and before measures, components, occlusion and deviation, the edges whose midpoint lies further than
+  //   `tolerance` off the scene's level set are split, for `rounds` rounds (rm_mesh_refine); every round's mesh is projected with the project block, or
+  //   with its defaults (iso and reach filled as above) where none is given.  iso, where not given, is the extraction's; tolerance, where not given,
+  //   is meshRefineTolerance of the grid the mesh lies on (a default, not a bar).  The criterion looks at edge midpoints only: deviation remains the
+  //   judge.  Adds refinement (RmMeshRefinement's fields in camel case, the per-round counts as arrays of eight, and milliseconds).  Only with refine
+  //   is the addon's extractMeshRefined called, which takes all fifteen arguments
+  extractMesh(scene, grid, opts, sharp, keep, components, simplify = null, quadric = null, occlusion = null, measures = false, slabs = null, project = null, deviation = null, refine = null) {
+    const o = meshOptions(grid, opts, { sharp, keep, components, simplify, quadric, occlusion, measures, slabs, project, deviation, refine });
     const stages = [o.sharp, o.keep, o.components, o.simplify, o.quadric, o.occlusion, o.measures, o.project, o.deviation], h = this.sceneHandle(scene);
+    if (o.refine !== null) return addon.extractMeshRefined(this.ctx, h, grid, o.refine, o.slabs, o.params, ...stages);
     if (o.slabs !== null) return addon.extractMeshSlabs(...meshArguments([this.ctx, h, grid, o.slabs, o.params, ...stages], 12));
     return addon.extractMesh(...meshArguments([this.ctx, h, grid, o.params, ...stages], 4, 5));
   }
@@ -681,6 +688,10 @@ const MESH_PROJECT_DEFAULTS = { iso: 0, rounds: 4, relax: 1, tolerance: 0, reach
 // deviation (rm_mesh_deviation): iso (the level the mesh stands for), order (n = 1, 2, 4 or 8: n * n samples per triangle), tolerance (>= 0: a
 // triangle whose largest |distance - iso| exceeds it counts as over) and flags
 const MESH_DEVIATION_DEFAULTS = { iso: 0, order: 4, tolerance: 0, flags: 0 };
+// refine (rm_mesh_refine): iso (the level the mesh stands for), tolerance (>= 0: an edge is split iff its midpoint's |distance - iso| exceeds it),
+// minEdge (>= 0: ... and its length exceeds it), rounds (1..8), maxTriangles (a round that would give more is not applied; 0 = the kernels' own
+// limit) and flags
+const MESH_REFINE_DEFAULTS = { iso: 0, tolerance: 0, minEdge: 0, rounds: 1, maxTriangles: 0, flags: 0 };
 // The checks' predicates as [holds(value, block), text]; `32`: the value must also hold as the float32 the addon stores.
 const toFlag = (v) => v === true || v === 1 ? 1 : v === false || v === 0 ? 0 : -1;
 const finite32 = (text) => [(v) => finite(v) && finite(Math.fround(v)), text];
@@ -710,6 +721,9 @@ const MESH_BLOCKS = {
                       ["reach", NOT_NEGATIVE32], ["normalDelta", POSITIVE32], ["flags", RENDER_FLAGS]] },
   deviation: { label: "deviation", defaults: MESH_DEVIATION_DEFAULTS,
                checks: [["iso", finite32("must be finite")], ["order", oneOf([1, 2, 4, 8], "must be 1, 2, 4 or 8")], ["tolerance", NOT_NEGATIVE32], ["flags", RENDER_FLAGS]] },
+  refine: { label: "refine", defaults: MESH_REFINE_DEFAULTS,
+            checks: [["iso", finite32("must be finite")], ["tolerance", NOT_NEGATIVE32], ["minEdge", NOT_NEGATIVE32], ["rounds", integerIn(1, 8)],
+                     ["maxTriangles", integerIn(0, Number.MAX_SAFE_INTEGER, "2^53 - 1")], ["flags", RENDER_FLAGS]] },
 };
 function meshBlock({ label, defaults, flags = [], checks }, opts) {
   const of = label && label + " ", p = { ...defaults };
@@ -732,6 +746,7 @@ function meshQuadric(opts) { return meshBlock(MESH_BLOCKS.quadric, opts); }
 function meshOcclusion(opts) { return meshBlock(MESH_BLOCKS.occlusion, opts); }
 function meshProject(opts) { return meshBlock(MESH_BLOCKS.project, opts); }
 function meshDeviation(opts) { return meshBlock(MESH_BLOCKS.deviation, opts); }
+function meshRefine(opts) { return meshBlock(MESH_BLOCKS.refine, opts); }
 
 // the simplify block of extractMesh / meshFromValues (include/hip_raymarch.h RmMeshSimplify and the RmGrid of clusters): an object with grid (a
 // meshGrid: one output vertex per occupied cell; it need not be related to the sampling grid) and, optionally, keepDuplicates (keep the triangles
@@ -753,6 +768,14 @@ function meshProjectReach(grid) {
   let least = Infinity;
   for (let a = 0; a < 3; a++) least = Math.min(least, Math.fround(Math.fround(Math.fround(grid.hi[a]) - Math.fround(grid.lo[a])) / Math.fround(grid.n[a])));
   return Math.fround(0.5 * least);
+}
+
+// the tolerance extractMesh(..., refine) takes when none is given: 1/64 of the smallest cell side of the grid, 2^-6 * min h[a] with h in fp32 by RmGrid's
+// rule -- the sagitta of a one-cell edge on a surface whose radius of curvature is 8 cells.  A default, not a bar
+function meshRefineTolerance(grid) {
+  let least = Infinity;
+  for (let a = 0; a < 3; a++) least = Math.min(least, Math.fround(Math.fround(Math.fround(grid.hi[a]) - Math.fround(grid.lo[a])) / Math.fround(grid.n[a])));
+  return Math.fround(2 ** -6 * least);
 }
 
 // Every option of extractMesh / meshFromValues as the addon takes it, each normalised once: a block that is undefined / null is null, true is the
@@ -780,6 +803,10 @@ function meshOptions(grid, opts, given) {
   o.keep = block(meshKeep, given.keep);
   o.slabs = block(meshSlabs, typeof given.slabs === "number" ? { layers: given.slabs } : given.slabs);
   if (o.slabs === null && grid && grid.slabs) throw new TypeError("mesh: a grid made with slabs: true is extracted in slabs: give slabs as well");
+  // refine: its block, and with it the projection inside its rounds -- the caller's project block, or the defaults filled as that one is
+  const lies = o.simplify !== null ? o.simplify.grid : grid;
+  const refine = scenePass(meshRefine, "refine", given.refine, () => ({ iso: o.params.iso, tolerance: meshRefineTolerance(lies) }));
+  o.refine = refine === null ? null : { ...refine, project: o.project !== null ? o.project : meshProject({ iso: o.params.iso, reach: meshProjectReach(lies) }) };
   return o;
 }
 // The addon's argument list of a mesh call, cut as the addon's optional arguments allow: the trailing entries that are null or false are
@@ -870,4 +897,4 @@ module.exports = { RM, addon, encodePng, Scene, CsgScene, Mandelbulb, singleSphe
                    tileRect, RenderJobContext, ShardedRenderJobContext, doRenderJob, U_OFFSET, DENOISE_DEFAULTS, denoiseParams,
                    DENOISE_VARIANCE_DEFAULTS, denoiseVarianceParams, DESPECKLE_DEFAULTS, despeckleParams, DISPLAY_DEFAULTS, AUTO_EXPOSURE_DEFAULTS,
                    displayParams, statsExposure, statsPercentile, MESH_DEFAULTS, meshGrid, meshParams, MESH_SHARP_DEFAULTS, meshSharp, MESH_KEEP_DEFAULTS, meshKeep, MESH_SLABS_DEFAULTS, meshSlabs,
-                   MESH_SIMPLIFY_DEFAULTS, meshSimplify, MESH_QUADRIC_DEFAULTS, meshQuadric, MESH_OCCLUSION_DEFAULTS, meshOcclusion, MESH_PROJECT_DEFAULTS, meshProject, meshProjectReach, MESH_DEVIATION_DEFAULTS, meshDeviation, encodePly, encodeStl };
+                   MESH_SIMPLIFY_DEFAULTS, meshSimplify, MESH_QUADRIC_DEFAULTS, meshQuadric, MESH_OCCLUSION_DEFAULTS, meshOcclusion, MESH_PROJECT_DEFAULTS, meshProject, meshProjectReach, MESH_DEVIATION_DEFAULTS, meshDeviation, MESH_REFINE_DEFAULTS, meshRefine, meshRefineTolerance, encodePly, encodeStl };

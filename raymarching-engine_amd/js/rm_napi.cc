@@ -250,10 +250,10 @@ static napi_value Present(napi_env env, napi_callback_info info) {
 
 // ---- the frame filters: denoise*, denoiseVariance*, filter* ----
 // A parameter block's fields as JS names them.  INT: a number truncated to int (-1 beyond +-1e9, which every range check refuses);
-// FLAG: 1 for a number other than 0, else 0.  The library checks the values (RM_ERR_INVALID before any device work).
+// FLAG: 1 for a number other than 0, else 0; UINT64: a number truncated to uint64_t (all-ones for one that is no such count).  The library checks the values (RM_ERR_INVALID before any device work).
 struct Field {
   const char* name;
-  enum Kind { INT, FLOAT, FLAG } kind;
+  enum Kind { INT, FLOAT, FLAG, UINT64 } kind;
   size_t offset;
 };
 static const Field DENOISE_FIELDS[] = {{"iterations", Field::INT, offsetof(RmDenoise, iterations)}, {"sigma_color", Field::FLOAT, offsetof(RmDenoise, sigma_color)},
@@ -281,6 +281,7 @@ static bool get_block(napi_env env, napi_value v, void* block, const Field (&fie
     if (napi_get_named_property(env, v, f.name, &x) != napi_ok || napi_get_value_double(env, x, &d) != napi_ok) return false;
     char* at = static_cast<char*>(block) + f.offset;
     if (f.kind == Field::FLOAT) *reinterpret_cast<float*>(at) = (float)d;
+    else if (f.kind == Field::UINT64) *reinterpret_cast<uint64_t*>(at) = (d >= 0.0 && d < 18446744073709551616.0) ? (uint64_t)d : ~(uint64_t)0;
     else *reinterpret_cast<int*>(at) = f.kind == Field::FLAG ? (d != 0.0 ? 1 : 0) : (d >= -1e9 && d <= 1e9) ? (int)d : -1;
   }
   return true;
@@ -491,6 +492,9 @@ static const Field MESH_PROJECT_FIELDS[] = {{"iso", Field::FLOAT, offsetof(RmMes
                                             {"flags", Field::INT, offsetof(RmMeshProject, flags)}};
 static const Field MESH_DEVIATION_FIELDS[] = {{"iso", Field::FLOAT, offsetof(RmMeshDeviation, iso)}, {"order", Field::INT, offsetof(RmMeshDeviation, order)},
                                               {"tolerance", Field::FLOAT, offsetof(RmMeshDeviation, tolerance)}, {"flags", Field::INT, offsetof(RmMeshDeviation, flags)}};
+static const Field MESH_REFINE_FIELDS[] = {{"iso", Field::FLOAT, offsetof(RmMeshRefine, iso)}, {"tolerance", Field::FLOAT, offsetof(RmMeshRefine, tolerance)},
+                                           {"minEdge", Field::FLOAT, offsetof(RmMeshRefine, min_edge)}, {"rounds", Field::INT, offsetof(RmMeshRefine, rounds)},
+                                           {"maxTriangles", Field::UINT64, offsetof(RmMeshRefine, max_triangles)}, {"flags", Field::INT, offsetof(RmMeshRefine, flags)}};
 static const Field MESH_SLABS_FIELDS[] = {{"layers", Field::INT, offsetof(RmMeshSlabs, layers)}};
 
 // A block of the mesh calls of a JS value: the library's defaults, then get_block's rules (null / undefined = the defaults and *given = false,
@@ -549,6 +553,7 @@ static napi_value MeshQuadricBlock(napi_env env, napi_callback_info info) { retu
 static napi_value MeshOcclusionBlock(napi_env env, napi_callback_info info) { return mesh_block_bytes(env, info, MESH_OCCLUSION_FIELDS, rm_mesh_occlusion_default, "meshOcclusionBlock(occlusion | null)"); }
 static napi_value MeshProjectBlock(napi_env env, napi_callback_info info) { return mesh_block_bytes(env, info, MESH_PROJECT_FIELDS, rm_mesh_project_default, "meshProjectBlock(project | null)"); }
 static napi_value MeshDeviationBlock(napi_env env, napi_callback_info info) { return mesh_block_bytes(env, info, MESH_DEVIATION_FIELDS, rm_mesh_deviation_default, "meshDeviationBlock(deviation | null)"); }
+static napi_value MeshRefineBlock(napi_env env, napi_callback_info info) { return mesh_block_bytes(env, info, MESH_REFINE_FIELDS, rm_mesh_refine_default, "meshRefineBlock(refine | null)"); }
 static napi_value MeshSlabsBlock(napi_env env, napi_callback_info info) { return mesh_block_bytes(env, info, MESH_SLABS_FIELDS, rm_mesh_slabs_default, "meshSlabsBlock(slabs | null)"); }
 
 // { grid: ArrayBuffer(RmGrid), params: ArrayBuffer(the block's struct) }: what meshBlocks and meshSimplifyBlock return
@@ -678,6 +683,9 @@ struct MeshStages {
   RmMeshOcclusion occlusion;
   RmMeshProject project;
   RmMeshDeviation deviation;
+  RmMeshRefine refine;           // extractMeshRefined alone: the block, and the projection inside its rounds
+  RmMeshProject refine_project;
+  bool has_refine = false;
   bool has_sharp = false, has_keep = false, components = false, has_simplify = false, has_quadric = false, has_occlusion = false, measures = false,
        has_project = false, has_deviation = false;
   bool normals = false, colours = false;  // whether the extraction was asked for them
@@ -760,6 +768,18 @@ static napi_value mesh_result(napi_env env, rm_ctx* ctx, rm_mesh* mesh, const Me
     rm_mesh_timings(mesh, slots);
     projected_ms = slots[1] + slots[2];
   }
+  // refine (with the scene): behind the projection, that mesh's chording edges are split (rm_mesh_refine) and everything below sees the refined mesh
+  RmMeshRefinement refined{};
+  float refined_ms = 0.0f;
+  if (m.has_refine) {
+    rm_mesh* finer = nullptr;
+    if (rm_mesh_refine(mesh, scene, &m.refine, &m.refine_project, &finer, &refined) != RM_OK) return throw_rm(env, ctx, "rm_mesh_refine");
+    rm_mesh_destroy(mesh);
+    guard.h = mesh = finer;
+    float slots[3] = {0.0f, 0.0f, 0.0f};
+    rm_mesh_timings(mesh, slots);
+    refined_ms = slots[1] + slots[2];
+  }
   RmMeshMeasures measured{};
   float measured_ms[2] = {0.0f, 0.0f};
   if (m.measures && rm_mesh_measure(mesh, &measured, measured_ms) != RM_OK) return throw_rm(env, ctx, "rm_mesh_measure");
@@ -804,6 +824,24 @@ static napi_value mesh_result(napi_env env, rm_ctx* ctx, rm_mesh* mesh, const Me
         {"milliseconds", (double)projected_ms}};
     if (!set_numbers(env, r, NUMBERS) || napi_set_named_property(env, o, "projection", r) != napi_ok || napi_set_named_property(env, o, "residual", residual) != napi_ok) return napi_failed();
   }
+  if (m.has_refine) {  // RmMeshRefinement's fields in camel case, the counts as Numbers (all below 2^53), the per-round counts as arrays of eight, and the milliseconds
+    napi_value r = nullptr;
+    if (napi_create_object(env, &r) != napi_ok) return napi_failed();
+    const Number NUMBERS[] = {
+        {"verticesBefore", (double)refined.vertices_before}, {"trianglesBefore", (double)refined.triangles_before}, {"vertices", (double)refined.vertices},
+        {"triangles", (double)refined.triangles}, {"flippedTriangles", (double)refined.flipped_triangles}, {"maxFirst", (double)refined.max_first},
+        {"maxLast", (double)refined.max_last}, {"roundsRun", (double)refined.rounds_run}, {"stopped", (double)refined.stopped}, {"milliseconds", (double)refined_ms}};
+    if (!set_numbers(env, r, NUMBERS)) return napi_failed();
+    const struct { const char* name; const uint64_t* values; } ROUNDS[] = {{"edges", refined.edges}, {"splitEdges", refined.split_edges}, {"nonfiniteMidpoints", refined.nonfinite_midpoints}};
+    for (const auto& rounds : ROUNDS) {
+      napi_value a = nullptr, x = nullptr;
+      if (napi_create_array_with_length(env, 8, &a) != napi_ok) return napi_failed();
+      for (uint32_t k = 0; k < 8; k++)
+        if (napi_create_double(env, (double)rounds.values[k], &x) != napi_ok || napi_set_element(env, a, k, x) != napi_ok) return napi_failed();
+      if (napi_set_named_property(env, r, rounds.name, a) != napi_ok) return napi_failed();
+    }
+    if (napi_set_named_property(env, o, "refinement", r) != napi_ok) return napi_failed();
+  }
   if (m.has_occlusion) {
     napi_value v = nullptr;
     void* data = nullptr;
@@ -846,20 +884,33 @@ static napi_value mesh_result(napi_env env, rm_ctx* ctx, rm_mesh* mesh, const Me
 // project | null[, deviation | null]]]]]]]]]) = rm_mesh_extract, or with a sharp block rm_mesh_extract_sharp
 // extractMeshSlabs(ctx, scene, grid, slabs | null, params | null, sharp | null, keep | null, components, simplify | null, quadric | null, occlusion | null,
 // measures[, project | null[, deviation | null]]) = rm_mesh_extract_slabs / rm_mesh_extract_sharp_slabs: the first twelve arguments are all given
-static napi_value extract_common(napi_env env, napi_callback_info info, bool slabbed) {
-  size_t argc = 14;
-  napi_value argv[14];
+static napi_value extract_common(napi_env env, napi_callback_info info, bool slabbed, bool with_refine = false) {
+  size_t argc = 16;
+  napi_value argv[16];
   NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
-  const bool counted = slabbed ? argc >= 12 && argc <= 14 : argc >= 4 && argc <= 13;
-  const size_t at = slabbed ? 4 : 3;  // where the parameters stand: behind the slabs block, or behind the grid
+  const bool counted = with_refine ? argc == 15 : slabbed ? argc >= 12 && argc <= 14 : argc >= 4 && argc <= 13;
   rm_ctx* ctx = counted ? get_external<rm_ctx>(env, argv[0]) : nullptr;
   MeshStages m;
   m.scene = counted ? get_external<rm_scene>(env, argv[1]) : nullptr;
   RmGrid g;
   RmMeshSlabs w;
   RmMeshParams p;
-  if (!ctx || !m.scene || !get_grid(env, argv[2], &g) || (slabbed && !get_mesh_block(env, argv[3], &w, MESH_SLABS_FIELDS, rm_mesh_slabs_default)) ||
-      !get_mesh_block(env, argv[at], &p, MESH_FIELDS, rm_mesh_params_default) || !get_mesh_stages(env, argv, at + 1, SCENE_STAGES, &m)) {
+  if (with_refine) {
+    napi_value inner = nullptr;
+    bool has_inner = false;
+    if (!ctx || !m.scene || !get_grid(env, argv[2], &g) || !get_mesh_block(env, argv[3], &m.refine, MESH_REFINE_FIELDS, rm_mesh_refine_default, &m.has_refine) || !m.has_refine ||
+        napi_get_named_property(env, argv[3], "project", &inner) != napi_ok ||
+        !get_mesh_block(env, inner, &m.refine_project, MESH_PROJECT_FIELDS, rm_mesh_project_default, &has_inner) || !has_inner ||
+        !get_mesh_block(env, argv[4], &w, MESH_SLABS_FIELDS, rm_mesh_slabs_default, &slabbed) || !get_mesh_block(env, argv[5], &p, MESH_FIELDS, rm_mesh_params_default) ||
+        !get_mesh_stages(env, argv, 6, SCENE_STAGES, &m)) {
+      napi_throw_type_error(env, nullptr, "extractMeshRefined(ctx, scene, grid, refine, slabs | null, params | null, sharp | null, keep | null, components, simplify | null, quadric | null, occlusion | null, measures, project | null, deviation | null)");
+      return nullptr;
+    }
+  }
+  const size_t at = slabbed ? 4 : 3;  // where the parameters stand: behind the slabs block, or behind the grid
+  if (!with_refine &&
+      (!ctx || !m.scene || !get_grid(env, argv[2], &g) || (slabbed && !get_mesh_block(env, argv[3], &w, MESH_SLABS_FIELDS, rm_mesh_slabs_default)) ||
+      !get_mesh_block(env, argv[at], &p, MESH_FIELDS, rm_mesh_params_default) || !get_mesh_stages(env, argv, at + 1, SCENE_STAGES, &m))) {
     napi_throw_type_error(env, nullptr, slabbed ? "extractMeshSlabs(ctx, scene, grid, slabs | null, params | null, sharp | null, keep | null, components, simplify | null, quadric | null, occlusion | null, measures[, project | null[, deviation | null]])"
                                                 : "extractMesh(ctx, scene, grid, params | null[, sharp | null[, keep | null[, components[, simplify | null[, quadric | null[, occlusion | null[, measures[, project | null[, deviation | null]]]]]]]]])");
     return nullptr;
@@ -876,8 +927,12 @@ static napi_value extract_common(napi_env env, napi_callback_info info, bool sla
   } else if (rm_mesh_extract(ctx, m.scene, &g, &p, &mesh) != RM_OK) return throw_rm(env, ctx, "rm_mesh_extract");
   return mesh_result(env, ctx, mesh, m);
 }
+// with_refine: extractMeshRefined(ctx, scene, grid, refine, slabs | null, params | null, sharp | null, keep | null, components, simplify | null, quadric | null,
+// occlusion | null, measures, project | null, deviation | null): all fifteen arguments are given; refine is the block's fields and `project`, the block of the
+// projection inside its rounds; slabs an object = the slabbed extraction
 static napi_value ExtractMesh(napi_env env, napi_callback_info info) { return extract_common(env, info, false); }
 static napi_value ExtractMeshSlabs(napi_env env, napi_callback_info info) { return extract_common(env, info, true); }
+static napi_value ExtractMeshRefined(napi_env env, napi_callback_info info) { return extract_common(env, info, false, true); }
 
 // meshFromValues(ctx, grid, values: Float32Array(corners), iso[, keep | null[, components[, simplify | null[, quadric | null[, measures]]]]]) = rm_mesh_from_values
 // meshFromValuesSlabs(ctx, grid, values, iso, slabs | null, keep | null, components, simplify | null, quadric | null, measures) = rm_mesh_from_values_slabs:
@@ -1117,7 +1172,7 @@ static napi_value Sizes(napi_env env, napi_callback_info) {
       {"RmMaterial", (uint32_t)sizeof(RmMaterial)}, {"RmRect", (uint32_t)sizeof(RmRect)}, {"RmSurface", (uint32_t)sizeof(RmSurface)}, {"RmDenoise", (uint32_t)sizeof(RmDenoise)},
       {"RmDenoiseVariance", (uint32_t)sizeof(RmDenoiseVariance)}, {"RmDespeckle", (uint32_t)sizeof(RmDespeckle)}, {"RmFilters", (uint32_t)sizeof(RmFilters)}, {"RmFrameStats", (uint32_t)sizeof(RmFrameStats)},
       {"RmAutoExposure", (uint32_t)sizeof(RmAutoExposure)}, {"RmDisplay", (uint32_t)sizeof(RmDisplay)}, {"RmGrid", (uint32_t)sizeof(RmGrid)},
-      {"RmMeshParams", (uint32_t)sizeof(RmMeshParams)}, {"RmMeshSharp", (uint32_t)sizeof(RmMeshSharp)}, {"RmMeshKeep", (uint32_t)sizeof(RmMeshKeep)}, {"RmMeshSimplify", (uint32_t)sizeof(RmMeshSimplify)}, {"RmMeshQuadric", (uint32_t)sizeof(RmMeshQuadric)}, {"RmMeshOcclusion", (uint32_t)sizeof(RmMeshOcclusion)}, {"RmMeshMeasures", (uint32_t)sizeof(RmMeshMeasures)}, {"RmMeshSlabs", (uint32_t)sizeof(RmMeshSlabs)}, {"RmMeshProject", (uint32_t)sizeof(RmMeshProject)}, {"RmMeshProjection", (uint32_t)sizeof(RmMeshProjection)}, {"RmMeshDeviation", (uint32_t)sizeof(RmMeshDeviation)}, {"RmMeshDeviationReport", (uint32_t)sizeof(RmMeshDeviationReport)}, {"abi", (uint32_t)rm_abi_version()}};
+      {"RmMeshParams", (uint32_t)sizeof(RmMeshParams)}, {"RmMeshSharp", (uint32_t)sizeof(RmMeshSharp)}, {"RmMeshKeep", (uint32_t)sizeof(RmMeshKeep)}, {"RmMeshSimplify", (uint32_t)sizeof(RmMeshSimplify)}, {"RmMeshQuadric", (uint32_t)sizeof(RmMeshQuadric)}, {"RmMeshOcclusion", (uint32_t)sizeof(RmMeshOcclusion)}, {"RmMeshMeasures", (uint32_t)sizeof(RmMeshMeasures)}, {"RmMeshSlabs", (uint32_t)sizeof(RmMeshSlabs)}, {"RmMeshProject", (uint32_t)sizeof(RmMeshProject)}, {"RmMeshProjection", (uint32_t)sizeof(RmMeshProjection)}, {"RmMeshDeviation", (uint32_t)sizeof(RmMeshDeviation)}, {"RmMeshDeviationReport", (uint32_t)sizeof(RmMeshDeviationReport)}, {"RmMeshRefine", (uint32_t)sizeof(RmMeshRefine)}, {"RmMeshRefinement", (uint32_t)sizeof(RmMeshRefinement)}, {"abi", (uint32_t)rm_abi_version()}};
   for (const auto& it : items) {
     NAPI_OK(napi_create_uint32(env, it.v, &v));
     NAPI_OK(napi_set_named_property(env, o, it.k, v));
@@ -1130,7 +1185,7 @@ static napi_value Init(napi_env env, napi_value exports) {
       {"ctxCreate", CtxCreate}, {"ctxDestroy", CtxDestroy}, {"sync", Sync}, {"sceneCreate", SceneCreate}, {"sceneDestroy", SceneDestroy},
       {"fbCreate", FbCreate}, {"fbClear", FbClear}, {"fbDestroy", FbDestroy}, {"fbDownload", FbDownload}, {"present", Present}, {"denoise", Denoise}, {"presentDenoised", PresentDenoised}, {"denoiseVariance", DenoiseVariance}, {"presentDenoisedVariance", PresentDenoisedVariance}, {"filter", Filter}, {"presentFiltered", PresentFiltered}, {"presentDisplay", PresentDisplay}, {"presentLinear", PresentLinear}, {"frameStats", FrameStats}, {"statsExposure", StatsExposure}, {"statsPercentile", StatsPercentile}, {"renderSample", RenderSample}, {"renderSamples", RenderSamples},
       {"fbCreateStriped", FbCreateStriped}, {"fbRows", FbRows}, {"setSamplesInFlight", SetSamplesInFlight}, {"presentSharded", PresentSharded}, {"presentShardedStart", PresentShardedStart}, {"presentShardedFinish", PresentShardedFinish},
-      {"meshBlocks", MeshBlocks}, {"meshSharpBlock", MeshSharpBlock}, {"meshKeepBlock", MeshKeepBlock}, {"meshSimplifyBlock", MeshSimplifyBlockOf}, {"meshQuadricBlock", MeshQuadricBlock}, {"meshOcclusionBlock", MeshOcclusionBlock}, {"meshProjectBlock", MeshProjectBlock}, {"meshDeviationBlock", MeshDeviationBlock}, {"sdfGrid", SdfGrid}, {"extractMesh", ExtractMesh}, {"meshFromValues", MeshFromValues}, {"meshSlabsBlock", MeshSlabsBlock}, {"extractMeshSlabs", ExtractMeshSlabs}, {"meshFromValuesSlabs", MeshFromValuesSlabs}, {"sizes", Sizes}};
+      {"meshBlocks", MeshBlocks}, {"meshSharpBlock", MeshSharpBlock}, {"meshKeepBlock", MeshKeepBlock}, {"meshSimplifyBlock", MeshSimplifyBlockOf}, {"meshQuadricBlock", MeshQuadricBlock}, {"meshOcclusionBlock", MeshOcclusionBlock}, {"meshProjectBlock", MeshProjectBlock}, {"meshDeviationBlock", MeshDeviationBlock}, {"meshRefineBlock", MeshRefineBlock}, {"extractMeshRefined", ExtractMeshRefined}, {"sdfGrid", SdfGrid}, {"extractMesh", ExtractMesh}, {"meshFromValues", MeshFromValues}, {"meshSlabsBlock", MeshSlabsBlock}, {"extractMeshSlabs", ExtractMeshSlabs}, {"meshFromValuesSlabs", MeshFromValuesSlabs}, {"sizes", Sizes}};
   for (const auto& f : fns) {
     napi_value fn;
     if (napi_create_function(env, f.name, NAPI_AUTO_LENGTH, f.fn, nullptr, &fn) != napi_ok) return nullptr;

@@ -244,6 +244,47 @@ def mesh_deviation(**fields) -> abi.RmMeshDeviation:
     return abi.RmMeshDeviation(iso=float(p["iso"]), order=int(order), tolerance=float(p["tolerance"]), flags=int(flags))
 
 
+def mesh_refine(**fields) -> abi.RmMeshRefine:
+    """The abi.RmMeshRefine of Context.extract_mesh(..., refine=...), over abi.MESH_REFINE_DEFAULTS: iso (the level the mesh stands for),
+    tolerance (an edge is split iff its midpoint's |distance - iso| exceeds it, >= 0), min_edge (... and its length exceeds it, >= 0), rounds
+    (1..8), max_triangles (a round that would give more is not applied; 0 = the kernels' own limit) and flags (rm_sdf_grid's).  Checked as the
+    library checks it: ValueError otherwise, and for unknown keys."""
+    unknown = set(fields) - set(abi.MESH_REFINE_DEFAULTS)
+    if unknown:
+        raise ValueError(f"mesh: unknown refine parameter {sorted(unknown)[0]}")
+    p = {**abi.MESH_REFINE_DEFAULTS, **fields}
+    for name in ("iso", "tolerance", "min_edge"):
+        if isinstance(p[name], bool) or not isinstance(p[name], (int, float, np.integer, np.floating)):
+            raise ValueError(f"mesh: refine {name} must be a number")
+    with np.errstate(over="ignore"):
+        iso, tolerance, min_edge = (np.float32(p[name]) for name in ("iso", "tolerance", "min_edge"))
+    if not math.isfinite(iso):
+        raise ValueError("mesh: refine iso must be finite")
+    if not (math.isfinite(tolerance) and tolerance >= 0):
+        raise ValueError("mesh: refine tolerance must be finite and >= 0")
+    if not (math.isfinite(min_edge) and min_edge >= 0):
+        raise ValueError("mesh: refine min_edge must be finite and >= 0")
+    rounds = p["rounds"]
+    if isinstance(rounds, bool) or not isinstance(rounds, (int, np.integer)) or not 1 <= int(rounds) <= 8:
+        raise ValueError("mesh: refine rounds must be an integer in 1..8")
+    most = p["max_triangles"]
+    if isinstance(most, bool) or not isinstance(most, (int, np.integer)) or not 0 <= int(most) < 2 ** 64:
+        raise ValueError("mesh: refine max_triangles must be an integer in 0..2^64 - 1")
+    flags = p["flags"]
+    if isinstance(flags, bool) or not isinstance(flags, (int, np.integer)) or int(flags) & ~(abi.RM_RENDER_FAST | abi.RM_RENDER_NO_CULL):
+        raise ValueError("mesh: refine flags must be 0, RM_RENDER_FAST, RM_RENDER_NO_CULL or both")
+    return abi.RmMeshRefine(iso=float(p["iso"]), tolerance=float(p["tolerance"]), min_edge=float(p["min_edge"]), rounds=int(rounds), max_triangles=int(most),
+                            flags=int(flags), reserved=0)
+
+
+def refine_tolerance(grid: Grid) -> float:
+    """The tolerance extract_mesh(..., refine=...) takes when none is named: 1/64 of the smallest cell side of `grid`, min h[a] * 2^-6 with h in
+    fp32 by RmGrid's rule -- the sagitta L^2 / (8 R) of a one-cell edge on a surface whose radius of curvature is 8 cells.  A default, not a
+    test bar: what is fine enough is the caller's to say, and `deviation` measures what came of it."""
+    f = np.float32
+    return float(f(2.0 ** -6) * min((f(b) - f(a)) / f(k) for a, b, k in zip(grid.lo, grid.hi, grid.n)))
+
+
 def project_reach(grid: Grid) -> float:
     """The reach extract_mesh(..., project=...) takes when none is given: half the smallest cell side of `grid`, 0.5f * min h[a] with h in
     fp32 by RmGrid's rule."""
@@ -273,6 +314,7 @@ class Mesh:
     residual = None  # Optional[np.ndarray]: [V] float32, the distance minus iso at the projected vertices; with `projection`
     deviation = None  # Optional[dict]: abi.RmMeshDeviationReport's fields (rm_mesh_deviation), only when the call asked for a deviation; taken the same way
     triangle_deviation = None  # Optional[np.ndarray]: [T] float32, each triangle's largest |distance - iso| over its samples; with `deviation`
+    refinement = None  # Optional[dict]: abi.RmMeshRefinement's fields (rm_mesh_refine), only when the call asked for a refinement; taken the same way
 
     @property
     def vertices(self) -> int:
@@ -280,7 +322,7 @@ class Mesh:
 
 
 def _with_occlusion(init):
-    def __init__(self, *args, occlusion=None, measures=None, projection=None, residual=None, deviation=None, triangle_deviation=None, **fields):
+    def __init__(self, *args, occlusion=None, measures=None, projection=None, residual=None, deviation=None, triangle_deviation=None, refinement=None, **fields):
         init(self, *args, **fields)
         self.occlusion = occlusion
         self.measures = measures
@@ -288,6 +330,7 @@ def _with_occlusion(init):
         self.residual = residual
         self.deviation = deviation
         self.triangle_deviation = triangle_deviation
+        self.refinement = refinement
 
     __init__.__doc__, __init__.__wrapped__ = init.__doc__, init
     return __init__

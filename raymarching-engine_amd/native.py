@@ -49,6 +49,7 @@ EXPORTS = [
     "rm_mesh_slabs_default", "rm_mesh_extract_slabs", "rm_mesh_extract_sharp_slabs", "rm_mesh_from_values_slabs",
     "rm_mesh_project_default", "rm_mesh_project",
     "rm_mesh_deviation_default", "rm_mesh_deviation_weights", "rm_mesh_deviation",
+    "rm_mesh_refine_default", "rm_mesh_refine",
 ]
 
 # G-buffer formats of a framebuffer (include/hip_raymarch.h RM_GBUFFER_*): "f32" (the default: the software GL stack's planes, which the
@@ -440,6 +441,8 @@ def load_library(path=None):
         "rm_mesh_deviation_default": (None, [C.POINTER(abi.RmMeshDeviation)]),
         "rm_mesh_deviation_weights": (ip, [ip, fp]),
         "rm_mesh_deviation": (ip, [vp, vp, C.POINTER(abi.RmMeshDeviation), C.POINTER(abi.RmMeshDeviationReport), fp, fp]),
+        "rm_mesh_refine_default": (None, [C.POINTER(abi.RmMeshRefine)]),
+        "rm_mesh_refine": (ip, [vp, vp, C.POINTER(abi.RmMeshRefine), C.POINTER(abi.RmMeshProject), C.POINTER(vp), C.POINTER(abi.RmMeshRefinement)]),
     }
     for name, (res, args) in sig.items():
         if name.startswith("rm_debug_") and not hasattr(lib, name) and os.environ.get("RM_LIB"):
@@ -737,7 +740,7 @@ class Context:
         self._check(self.lib.rm_sdf_grid_device(self.h, scene.h, C.byref(g), int(flags), C.c_void_p(out_ptr), C.c_void_p(stream) if stream else None))
 
     def _take_mesh(self, handle, grid, normals=False, colours=False, keep=None, components=False, simplify=None, quadric=None, scene=None, occlusion=None, measures=False,
-                   project=None, deviation=None):
+                   project=None, deviation=None, refine=None):
         """The arrays of a mesh handle as a mesh.Mesh (normals / colours: whether the call that made it asked for them); destroys the handle.
         simplify (_mesh_simplify's triple): the mesh is first clustered on the device (rm_mesh_simplify) and the Mesh's grid is the cluster grid,
         which its cells then index -- with quadric (an abi.RmMeshQuadric) by rm_mesh_simplify_quadric; keep (an abi.RmMeshKeep): that mesh is filtered on the device (rm_mesh_filter), which also removes the vertices
@@ -750,7 +753,9 @@ class Context:
         and the timings gain "projection", the milliseconds of its rounds and its normals; sampling, meshing and attributes stay those of the
         mesh that was projected, so nothing is counted twice.  deviation (an abi.RmMeshDeviation, with the scene): how far the triangles of
         the mesh that is returned lie off the scene's level set (rm_mesh_deviation): Mesh.deviation, Mesh.triangle_deviation, and the timings
-        gain "deviation", the milliseconds of its evaluation and its reduction."""
+        gain "deviation", the milliseconds of its evaluation and its reduction.  refine (_mesh_refine's function of the grid the mesh lies on, with
+        the scene): behind project, that mesh's chording edges are split on the device (rm_mesh_refine) and everything after sees the refined
+        mesh: Mesh.refinement, and the timings gain "refinement", the milliseconds of its split rounds, its projections and its normals."""
         from .mesh import Mesh
 
         handles = [handle]
@@ -780,6 +785,15 @@ class Context:
                 handles.append(moved)
                 handle = moved
                 projected = (abi.mesh_projection_dict(report), residual, produced_ms)
+            refined = None
+            if refine is not None:
+                (block, inner), finer, report = refine(grid), C.c_void_p(), abi.RmMeshRefinement()
+                stage_ms = (C.c_float * 3)()
+                self._check(self.lib.rm_mesh_timings(handle, stage_ms))  # (of the mesh that is refined: the producing mesh's, or the projection's)
+                self._check(self.lib.rm_mesh_refine(handle, scene.h, C.byref(block), C.byref(inner), C.byref(finer), C.byref(report)))
+                handles.append(finer)
+                handle = finer
+                refined = (abi.mesh_refinement_dict(report), stage_ms)
             measured = None
             if measures:
                 block, measure_ms = abi.RmMeshMeasures(), (C.c_float * 2)()
@@ -810,10 +824,17 @@ class Context:
                     self._check(self.lib.rm_mesh_components_download(handle, what, a.ctypes.data_as(C.c_void_p), a.nbytes))
                     arrays[name] = a
             timings = dict(sampling=float(ms[0]), meshing=float(ms[1]), attributes=float(ms[2]))
+            refinement_ms = None
+            if refined is not None:  # (the handle is the refinement's: its meshing slot is the split rounds, its attributes slot projections and normals)
+                arrays["refinement"], stage_ms = refined
+                refinement_ms, ms = float(ms[1]) + float(ms[2]), stage_ms
+                timings = dict(sampling=float(ms[0]), meshing=float(ms[1]), attributes=float(ms[2]))
             if projected is not None:  # (the handle is the projection's: its meshing slot is the rounds, its attributes slot the normals)
                 arrays["projection"], arrays["residual"], produced_ms = projected
                 timings = dict(sampling=float(produced_ms[0]), meshing=float(produced_ms[1]), attributes=float(produced_ms[2]),
                                projection=float(ms[1]) + float(ms[2]))
+            if refinement_ms is not None:
+                timings["refinement"] = refinement_ms
             if occlusion is not None:
                 ao, ms2 = np.empty(v, np.float32), (C.c_float * 2)()
                 self._check(self.lib.rm_mesh_occlusion(handle, scene.h, C.byref(occlusion), _fp(ao), ms2))
@@ -881,6 +902,28 @@ class Context:
         return lambda grid: mesh.mesh_project(**{"reach": mesh.project_reach(grid), **fields})
 
     @staticmethod
+    def _mesh_refine(refine, iso, project):
+        """The `refine` of extract_mesh as a function of the mesh.Grid the refined mesh lies on, which gives the pair (abi.RmMeshRefine,
+        abi.RmMeshProject) of rm_mesh_refine (_mesh_block's rules); None stays None.  True and a dict take the extraction's iso where they name
+        none, and mesh.refine_tolerance of that grid where they name no tolerance; a struct is taken as it stands.  The projection inside the
+        rounds is the caller's `project` (the function _mesh_project made of it), or the defaults filled the same way where there is none."""
+        from . import mesh
+
+        if refine is None:
+            return None
+        inner = project if project is not None else Context._mesh_project(True, iso)
+        if isinstance(refine, abi.RmMeshRefine):
+            block = Context._mesh_block("refine", refine, abi.RmMeshRefine)
+            return lambda grid: (block, inner(grid))
+        if refine is True:
+            refine = {}
+        if not isinstance(refine, dict):
+            raise ValueError("mesh: refine must be None, True, a dict of mesh_refine's arguments or an abi.RmMeshRefine")
+        fields = {"iso": iso, **refine}
+        mesh.mesh_refine(**fields)  # (refused before anything runs)
+        return lambda grid: (mesh.mesh_refine(**{"tolerance": mesh.refine_tolerance(grid), **fields}), inner(grid))
+
+    @staticmethod
     def _mesh_deviation(deviation, iso):
         """The `deviation` of extract_mesh as an abi.RmMeshDeviation (_mesh_block's rules); None stays None.  True and a dict take the
         extraction's iso where they name none; a struct is taken as it stands."""
@@ -939,7 +982,7 @@ class Context:
 
     def extract_mesh(self, scene: "SceneHandle", grid, iso: float = 0.0, normals: bool = True, colours: bool = False, flags: int = 0,
                      normal_delta: float = 1e-5, sharp=None, *, keep=None, components: bool = False, simplify=None, quadric=None,
-                     measures: bool = False, slabs=None, deviation=None, project=None, occlusion=None):
+                     measures: bool = False, slabs=None, deviation=None, refine=None, project=None, occlusion=None):
         """The level set `iso` of the scene on `grid` (mesh.Grid) as a mesh.Mesh: rm_mesh_extract -- the distances sampled and meshed
         (surface nets) on the device, with per-vertex normals / diffuse colours from the scene's probes when asked for.  `sharp`: None is
         that call; True (the defaults), a dict of mesh.mesh_sharp's arguments or an abi.RmMeshSharp is rm_mesh_extract_sharp -- the same
@@ -971,12 +1014,20 @@ class Context:
         device how far the triangles of the mesh that is returned -- behind every stage above, `project` included -- lie off the scene's level
         set at order * order fixed samples each (rm_mesh_deviation).  iso, where not given, is the extraction's.  The mesh carries
         Mesh.deviation (a dict of abi.RmMeshDeviationReport's fields), Mesh.triangle_deviation ([T] float32: each triangle's largest
-        |distance - iso| over its samples) and timings["deviation"]."""
+        |distance - iso| over its samples) and timings["deviation"].
+        `refine`: None is that mesh; True (the defaults), a dict of mesh.mesh_refine's arguments or an abi.RmMeshRefine splits, on the device,
+        the edges of the mesh that is returned whose midpoint lies further than `tolerance` off the scene's level set, and repeats for `rounds`
+        rounds (rm_mesh_refine) -- behind `simplify`, `quadric`, `keep` and `project`, before `components`, `measures`, `occlusion` and
+        `deviation`, which then see the refined mesh.  Every round's mesh is projected with the `project` block, or with its defaults (iso and
+        reach filled as above) where none is given.  iso, where not given, is the extraction's; tolerance, where not given, is 1/64 of the
+        smallest cell side of the grid the mesh lies on (mesh.refine_tolerance: a default, not a bar).  The criterion looks at edge midpoints
+        only: `deviation` remains the judge of the result.  The mesh carries Mesh.refinement (a dict of abi.RmMeshRefinement's fields) and
+        timings["refinement"]."""
         from .mesh import mesh_params
 
         keep, simplify, quadric = self._mesh_keep(keep), self._mesh_simplify(simplify), self._mesh_quadric(quadric, simplify)  # (refused before anything runs)
         occlusion, project = self._mesh_occlusion(occlusion), self._mesh_project(project, iso)
-        deviation = self._mesh_deviation(deviation, iso)
+        deviation, refine = self._mesh_deviation(deviation, iso), self._mesh_refine(refine, iso, project)
         g, p = grid.to_c(), mesh_params(iso=iso, normals=normals, colours=colours, flags=flags, normal_delta=normal_delta)
         h = C.c_void_p()
         s = self._mesh_block("sharp", sharp, abi.RmMeshSharp)
@@ -990,7 +1041,7 @@ class Context:
         else:
             self._check(self.lib.rm_mesh_extract_sharp_slabs(self.h, scene.h, C.byref(g), C.byref(p), C.byref(s), C.byref(w), C.byref(h)))
         return self._take_mesh(h, grid, normals=p.normals, colours=p.colours, keep=keep, components=components, simplify=simplify, quadric=quadric,
-                               scene=scene, occlusion=occlusion, measures=measures, project=project, deviation=deviation)
+                               scene=scene, occlusion=occlusion, measures=measures, project=project, deviation=deviation, refine=refine)
 
     def mesh_from_values(self, grid, values: np.ndarray, iso: float = 0.0, *, keep=None, components: bool = False, simplify=None, quadric=None,
                          measures: bool = False, slabs=None):
